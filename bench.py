@@ -34,13 +34,22 @@ Inputs are resident in HBM before the timed region.  --scaling weak (default): e
 --batch graphs per step.  --scaling strong (cfg2): --graphs is the GLOBAL batch, sharded contiguously over the ranks
 (kgcn_amd.parallel.shard_range); gradients combine with the shard weights.
 
+A plain run sets up, warms up, times --steps steps and prints the line; `ms_per_step` is the wall time of one timed step.
 `roofline` prices the dominant kernel against the 8 TB/s HBM peak (cfg2: the fused backward, ALGORITHMIC bytes of
-DESIGN.md, median / p10 / p90 of the per-launch HIP-event times inside the timed region; `roofline.spmm_kernel` prices
-the batched SpMM alone -- the kernel the north-star 60 % target is stated on).  cfg4 / cfg5: every C-ABI call of one
-extra eager step after the timed region is bracketed by HIP events and priced with its algorithmic bytes / flops
-(tools/abi_roofline.py); `roofline` is the call with the largest time.  `cpu_baseline` (cfg2, N = 1): the C
-restatement of the reference algorithm (oracle/kgcn_ref.c, OpenMP over graphs) on the host cores on a bounded sample,
-next to a reference-SHAPED leg (per-graph scipy CSR @ (X W + b) loop, the op structure of kgcn/layers.py:107-116).
+DESIGN.md, median / p10 / p90 of the per-launch HIP-event times inside the timed region).  Everything that needs runs
+of its own after the timed region comes with --full only: `roofline.spmm_kernel` (cfg2: the batched SpMM alone -- the
+kernel the north-star 60 % target is stated on), `roofline.box` (clocks, power and HBM probe rates under the same
+load), the per-call roofline of cfg1 / cfg3 / cfg4 / cfg5 (every C-ABI call of one extra eager step bracketed by HIP
+events and priced with its algorithmic bytes / flops, tools/abi_roofline.py; `roofline` is the call with the largest
+time) and `cpu_baseline` (cfg2, N = 1): the C restatement of the reference algorithm (oracle/kgcn_ref.c, OpenMP over
+graphs) on the host cores on a bounded sample, next to a reference-SHAPED leg (per-graph scipy CSR @ (X W + b) loop,
+the op structure of kgcn/layers.py:107-116).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step handed its caller as DIR/<name>.npy
+(float32; at most 64 MiB in all).  cfg2: `output` and `grad_x` of a fixed, seeded sample of 2,048 graphs (all of them
+when the batch is smaller), `grad_w`, `grad_bias`; cfg1 / cfg3 / cfg4 / cfg5: `logits`, `loss` and every parameter
+after the update (`param_NN`); --dry: the exchanged gradients (`grad_NN`).  The inputs are seeded: the same arguments
+give the same inputs in every run, so that two builds can be compared output for output.
 
 `collective` (N > 1): ranks, backend and RCCL version, bucket size, the all-reduce alone timed with HIP events after the
 timed region (and inside the step for cfg2), per-rank step times.
@@ -70,6 +79,8 @@ FEAT = 64
 EXTRA_EDGES = 3
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy)
 METRIC = "graphs/sec GraphConv fwd+bwd, 32-node mol graphs x64 feat"
+DUMP_GRAPHS = 2048             # --dump-outputs, cfg2: graphs of the seeded sample (2 x 16 MiB of output / dX)
+DUMP_BUDGET = 64 << 20         # --dump-outputs: bytes in all
 
 
 # ---------------------------------------------------------------------------------------------
@@ -205,6 +216,17 @@ def stats(ms):
     ms = sorted(ms)
     n = len(ms)
     return {"median_ms": ms[n // 2], "p10_ms": ms[n // 10], "p90_ms": ms[(9 * n) // 10], "mean_ms": float(np.mean(ms))}
+
+
+def dump_outputs(outs, out_dir):
+    """--dump-outputs: {name: tensor} -> out_dir/<name>.npy in float32, DUMP_BUDGET bytes at most."""
+    arrays = {name: np.asarray(t.detach().cpu().numpy(), dtype=np.float32) for name, t in outs.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET:
+        raise SystemExit("--dump-outputs: %d bytes of outputs, more than the %d allowed" % (total, DUMP_BUDGET))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -570,6 +592,7 @@ def make_cfg2(T, device, seed=1234, normalize=False):
 class Cfg2:
     name = "cfg2"
     n_events = 5
+    keep_outputs = False            # --dump-outputs: set for the last timed step, which then keeps its forward output
 
     def __init__(self, args, ctx):
         import torch
@@ -617,6 +640,19 @@ class Cfg2:
             self.bucket.all_reduce_mean(weight=self.weight)
             if ev:
                 ev[3].record()
+        if self.keep_outputs:
+            self.out = out
+
+    def outputs(self):
+        """What the last timed step gave its caller: the layer output and dX of a fixed, seeded sample of DUMP_GRAPHS graphs
+        (every graph of a smaller batch), dW and dbias."""
+        import torch
+        pick = np.arange(self.T)
+        if self.T > DUMP_GRAPHS:
+            pick = np.sort(np.random.default_rng(0).choice(self.T, DUMP_GRAPHS, replace=False))
+        sel = torch.as_tensor(pick, device=self.ctx.device)
+        return {"output": self.out.detach().index_select(0, sel), "grad_x": self.x.grad.index_select(0, sel),
+                "grad_w": self.layer.w[0].grad, "grad_bias": self.layer.bias[0].grad}
 
     def spmm_probe(self, reps):
         """The batched SpMM alone (the kernel of the north-star 60 % target): forward and adjoint launches on the
@@ -679,7 +715,7 @@ class Cfg2:
     def report(self, evs):
         """rank 0: config + roofline + cpu_baseline."""
         args, T, wl = self.args, self.T, self.wl
-        spmm = None if (args.unfused or args.profile) else self.spmm_probe(args.steps)
+        spmm = self.spmm_probe(args.steps) if (args.full and not args.unfused and not args.profile) else None
         traffic, traffic_stale = {}, None
         tpath = os.path.join(ROOT, "profiles", "traffic_cfg2.json")
         if os.path.exists(tpath) and not args.unfused:
@@ -731,7 +767,7 @@ class Cfg2:
                     "spmm_kernel": spmm_entry,
                     "layer_frac_of_hbm_peak": ab["layer"] * T / ((fwd_ms + bwd_ms) * 1e-3) / 1e9 / HBM_PEAK_GBS}
         extra = {}
-        if self.ctx.world == 1 and not args.no_cpu_baseline and not args.profile:
+        if self.ctx.world == 1 and args.full and not args.no_cpu_baseline and not args.profile:
             extra["cpu_baseline"] = cpu_baseline(wl)
         return config, roofline, extra
 
@@ -817,6 +853,7 @@ class _ModelStep:
     """Shared by cfg4 / cfg5: eager or hipGraph-captured train step + the per-call roofline of one eager step."""
     n_events = 2
     assemble_in_step = False        # a new mini-batch per step: the device-side assembly is the head of the (captured) step
+    keep_outputs = False            # --dump-outputs: set for the last timed step, which then keeps (loss, logits)
 
     def setup_passes(self):
         return 5
@@ -845,27 +882,38 @@ class _ModelStep:
         if self.assemble_in_step:
             self.sb.assemble()
         logits = self.model(self.sb.features, self.sb.adjacency, **self.kw)
-        cost_opt, _ = self.loss_fn(logits, self.labels, self.mask)
+        cost_opt, cost_sum = self.loss_fn(logits, self.labels, self.mask)
         with ops.deferred_reductions(root=cost_opt):
             cost_opt.backward()
         self.opt.step(packed=train_exchange(self.bucket, self.opt, self.weight))
+        return cost_sum, logits
 
     def step(self, ev=None):
         if ev:
             ev[0].record()
         self.next_batch()
         if self.graph_step is not None:
-            self.graph_step.replay()
+            res = self.graph_step.replay()
         else:
-            self._eager_step()
+            res = self._eager_step()
         if ev:
             ev[1].record()
+        if self.keep_outputs:
+            self.out = res
+
+    def outputs(self):
+        """What the last timed step gave its caller: the loss (GraphedTrainStep's cost_sum), the logits and the parameters
+        after the update."""
+        cost_sum, logits = self.out
+        outs = {"loss": cost_sum.detach().reshape(-1), "logits": logits.detach()}
+        outs.update(("param_%02d" % i, p.detach()) for i, p in enumerate(self.opt.params))
+        return outs
 
     def in_step_allreduce_us(self, evs):
         return None
 
     def model_roofline(self):
-        if self.args.profile:
+        if self.args.profile or not self.args.full:
             return roofline_from_rows([], [])
         rows, unpriced = abi_roofline_of(self._eager_step)
         return roofline_from_rows(rows, unpriced, self.name)
@@ -1164,6 +1212,9 @@ class Dry:
         if ev and ev[1] is not None:
             ev[1].record()
 
+    def outputs(self):
+        return {"grad_%02d" % i: p.grad for i, p in enumerate(self.params)}
+
     def in_step_allreduce_us(self, evs):
         return None
 
@@ -1210,6 +1261,11 @@ def build_parser():
                     help="under a launcher with ONE rank: still build the process group and run the gradient exchange")
     ap.add_argument("--dry", action="store_true",
                     help="launcher + gradient exchange only (no kernels); the only mode that runs without a GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements after the timed region: CPU baseline (cfg2), SpMM probe (cfg2), clocks / power / "
+                         "HBM probe (roofline.box), per-call roofline (cfg1 / cfg3 / cfg4 / cfg5)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, seeded sample of a large output)")
     return ap
 
 
@@ -1218,6 +1274,8 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.device == "cpu" and not args.dry:
         raise SystemExit("--device cpu needs --dry: the product path has no CPU fallback")
     if args.scaling == "strong" and args.config != "cfg2" and not args.dry:
@@ -1257,14 +1315,20 @@ def main(argv=None):
     ctx.barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
+        if args.dump_outputs and i == args.steps - 1:
+            wl.keep_outputs = True
         wl.step(ev[i] if ev else None)
     ctx.barrier()
     local_elapsed = time.perf_counter() - t0
     elapsed = ctx.max_over_ranks(local_elapsed)
     per_rank = ctx.gather_over_ranks(local_elapsed / args.steps * 1e3)
+    if args.dump_outputs:
+        wl.keep_outputs = False
+        if ctx.rank == 0:            # before anything below runs the step again or touches the gradients
+            dump_outputs(wl.outputs(), args.dump_outputs)
 
     box = None
-    if ctx.on_gpu and not args.dry and not args.profile:
+    if ctx.on_gpu and args.full and not args.dry and not args.profile:
         # first thing after the timed region: same load, same clocks.  On EVERY rank: the step holds the gradient all-reduce, and the
         # number of extra steps follows from `elapsed`, the maximum over the ranks -- the same on all of them; rank 0 reports its own GPU
         box = box_state(wl, ctx, elapsed / args.steps * 1e3)

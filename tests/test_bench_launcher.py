@@ -90,3 +90,27 @@ def test_bench_refuses_a_mismatched_launcher():
     r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry", "--device", "cpu", "--backend", "gloo"], env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120, cwd=ROOT)
     assert r.returncode != 0 and "WORLD_SIZE=4" in r.stderr
+
+
+def test_bench_dry_dump_outputs_and_step_count(tmp_path):
+    """--steps K times K steps; --dump-outputs writes the last step's exchanged gradients (--dry: the mean over the ranks of
+    (r + 1)(i + 1), 1.5 (i + 1) for two ranks) as float32 .npy files; --full is accepted."""
+    out = tmp_path / "dump"
+    r = _run("--gpus", "2", "--dry", "--device", "cpu", "--backend", "gloo", "--steps", "5", "--warmup", "2", "--full",
+             "--dump-outputs", str(out))
+    assert r.returncode == 0, r.stderr[-2000:]
+    res = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
+    assert res["steps"] == 5 and res["ms_per_step"] > 0 and res["config"]["exchanges_checked"] >= 5
+    import numpy as np
+    import bench
+    files = sorted(out.glob("*.npy"))
+    assert len(files) == len(bench.PARAM_SHAPES["cfg2"])
+    for i, f in enumerate(files):
+        a = np.load(f)
+        assert f.name == "grad_%02d.npy" % i and a.dtype == np.float32 and a.shape == bench.PARAM_SHAPES["cfg2"][i]
+        assert np.all(a == 1.5 * (i + 1))
+
+
+def test_bench_refuses_zero_steps():
+    r = _run("--dry", "--device", "cpu", "--steps", "0")
+    assert r.returncode != 0 and "--steps" in r.stderr

@@ -19,12 +19,12 @@ for cfg in cfg4 cfg5 cfg3 cfg1; do
   cp gpurun_out/prof_${TAG}_$cfg/traffic.json profiles/traffic_$cfg.json
 done
 bash tools/bench_lines.sh $TAG > $OUT/lines.txt 2>&1; cat $OUT/lines.txt
-python bench.py --normalize --no-cpu-baseline --steps 50 --warmup 5 2>/dev/null | tail -1 > $OUT/cfg2_normalize.json
-python bench.py --graphs 4096 --graph --no-cpu-baseline --steps 50 --warmup 5 2>/dev/null | tail -1 > $OUT/cfg2_graphs4096.json
+python bench.py --full --normalize --no-cpu-baseline --steps 50 --warmup 5 2>/dev/null | tail -1 > $OUT/cfg2_normalize.json
+python bench.py --full --graphs 4096 --graph --no-cpu-baseline --steps 50 --warmup 5 2>/dev/null | tail -1 > $OUT/cfg2_graphs4096.json
 port=29711
 for c in cfg2 cfg4 cfg5; do
   port=$((port+1))
-  timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port $port bench.py --gpus 1 --config $c --force-dist --no-cpu-baseline --steps 30 --warmup 5 2> $OUT/${c}_forcedist.err | tail -1 > $OUT/${c}_forcedist.json
+  timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port $port bench.py --gpus 1 --full --config $c --force-dist --no-cpu-baseline --steps 30 --warmup 5 2> $OUT/${c}_forcedist.err | tail -1 > $OUT/${c}_forcedist.json
 done
 python - <<PY
 import json

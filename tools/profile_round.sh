@@ -11,7 +11,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/prof_$TAG
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python $REPO/bench.py --steps 50 --warmup 5 $* > $OUT/bench.json 2> $OUT/bench.err
+python $REPO/bench.py --full --steps 50 --warmup 5 $* > $OUT/bench.json 2> $OUT/bench.err
 BENCH="python $REPO/bench.py --no-cpu-baseline --steps 30 --warmup 5 $*"
 pass() { tag=$1; shift; timeout 600 rocprofv3 --kernel-trace "$@" -d $OUT/$tag -o bench -- $BENCH > $OUT/$tag.log 2>&1; }
 pass stats --stats
