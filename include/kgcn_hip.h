@@ -64,7 +64,10 @@ extern "C" {
  * kgcn_csr_batch_size() with its own sizeof(kgcn_csr_batch) before the first call (kgcn_amd/_lib.py and
  * tests/abi_consumer.c do both).
  * Round 6 ADDED entry points only (no signature or layout changed, the version stays 2): kgcn_bconv_fanout_f32,
- * kgcn_copy2d_multi_f32 (+ kgcn_copy2d_job), kgcn_hbm_probe. */
+ * kgcn_copy2d_multi_f32 (+ kgcn_copy2d_job), kgcn_hbm_probe.
+ * The graph VAE added entry points only as well (version still 2): kgcn_philox4x64_raw, kgcn_normal_f32,
+ * kgcn_vae_sample_fwd_f32 / kgcn_vae_sample_bwd_f32, kgcn_vae_recon_workspace_bytes, kgcn_vae_recon_fwd_f32 /
+ * kgcn_vae_recon_bwd_f32. */
 #define KGCN_HIP_ABI_VERSION 2
 
 /* Column index of the padding entries of a row-padded batch (see row_pad): they carry value 0 and
@@ -693,6 +696,54 @@ int64_t kgcn_gin_aggregate_bwd_workspace_bytes(int32_t num_graphs, int32_t n_nod
 int kgcn_gin_aggregate_bwd_f32(const kgcn_csr_batch* at_ch, int32_t num_channels, const float* grad, int32_t d,
                                const float* eps, const float* x, float* dx, float* deps, void* workspace,
                                int64_t workspace_bytes, void* stream);
+
+/* -- graph VAE (example_model/model_vae.py) ------------------------------------------------------------------------------
+ * Noise: Philox4x64-10 (the Random123 generator numpy ships as np.random.Philox) with key (seed, 0) and counter
+ * (j, step, 0, 0) gives the four 64-bit words of block j; block j holds noise elements 4j .. 4j+3: words (0, 1) and (2, 3) each
+ * give two N(0, 1) values by Box-Muller in f32 -- u1 = ((w0 >> 40) + 1) 2^-24, u2 = (w1 >> 40) 2^-24,
+ * r = sqrt(-2 log u1), (r cos 2 pi u2, r sin 2 pi u2).  `step` is a DEVICE pointer (NULL = 0), read by the kernel: a replayed
+ * hipGraph draws new noise when the value behind it changes. */
+#define KGCN_VAE_MAX_NODES 128
+#define KGCN_VAE_MAX_CHANNELS 8
+#define KGCN_VAE_MAX_DIM 64
+/* out[4j + q] = word q of block j, j < num_blocks (device, uint64) */
+int kgcn_philox4x64_raw(uint64_t seed, const int64_t* step, int64_t num_blocks, uint64_t* out, void* stream);
+/* out[e] = noise element e, e < n */
+int kgcn_normal_f32(uint64_t seed, const int64_t* step, int64_t n, float* out, void* stream);
+/* Reparameterisation (model_vae.py:89-96, 169-181) of the [B, d] pre-activations of the mean and std Dense layers (rows `ld`
+ * floats apart, also for dm_pre / ds_pre: both may be column blocks of one [B, 2d] tensor):
+ * mean = clip(m, -100, 100), std = clip(sqrt(softplus(s)), -5, 5), z [B, N, d] = mean_b + std_b * eps[b, n, :] with eps the
+ * caller's [B, N, d] tensor or, when eps is NULL, noise elements b N d + n d + k of (seed, *step);
+ * kl [B] (may be NULL) = N * sum_k (1 + 2 log(std + 1e-10) - mean^2 - std) -- the KL loss is -1/2 mean_b kl[b].  d <= 64.
+ * The backward regenerates the same eps; dz[0 .. num_dz-1] (num_dz <= KGCN_VAE_MAX_CHANNELS + 1) are gradients of z from its
+ * consumers, added in order; dkl [B] (NULL = 0) is the gradient arriving at kl; tf.clip_by_value's gradient passes at
+ * equality. */
+int kgcn_vae_sample_fwd_f32(const float* m_pre, const float* s_pre, int32_t num_graphs, int32_t n_nodes, int32_t d, int32_t ld,
+                            const float* eps, uint64_t seed, const int64_t* step, float* z, float* kl, void* stream);
+int kgcn_vae_sample_bwd_f32(const float* m_pre, const float* s_pre, int32_t num_graphs, int32_t n_nodes, int32_t d, int32_t ld,
+                            const float* eps, uint64_t seed, const int64_t* step, const float* const* dz, int32_t num_dz,
+                            const float* dkl, float* dm_pre, float* ds_pre, void* stream);
+/* Reconstruction cost (model_vae.py:203-253) without the [B, C, N, N] logits: adj_ch[c] (host array of C descriptors, any
+ * row_pad) are the target adjacencies, label(i, j) = value of entry (i, j) (a repeated column: the last entry of the row);
+ * y[c] the [B, N, d] decoder outputs and w[c] the [d] DistMult kernels of channel c (host arrays of device pointers);
+ * feat_logits / feat_target [B, N, f].  Per graph b:
+ *   per_graph[b]      = mean over N, f of sigmoid CE(feat_logits, feat_target)
+ *   per_graph[B + b]  = mean over C, N, N of sigmoid CE(L_c, label_c), L_c = (y_c * w_c) y_c^T
+ *   per_graph[2B + b] = mean over N, N of [max_c L_c > 0] == [max_c label_c > 0.5]
+ * sums[0] = cost_opt = mean_b mask_b (feature + link) - 1/2 mean_b kl[b], sums[1] = cost_sum = mean_b mask_b (feature + link),
+ * sums[2] = correct_count = sum_b mask_b per_graph[2B + b]; mask / kl NULL = ones / zeros; means over the padded batch.
+ * Backward: g_opt / g_sum device scalars (NULL = 0) arriving at cost_opt / cost_sum; writes dy[c] [B, N, d], dfeat [B, N, f],
+ * dkl [B] (may be NULL) = -1/2 g_opt / B, and dw[c] [d] (dw or dw[c] may be NULL) through per-workgroup partials in
+ * `workspace` (>= kgcn_vae_recon_workspace_bytes(B, C, d)) and a fixed-order second stage (deferrable: kgcn_reduce_defer).
+ * Limits: N <= 128, C <= 8, d <= 64; outside them the call fails.  Results are bitwise reproducible. */
+int64_t kgcn_vae_recon_workspace_bytes(int32_t num_graphs, int32_t num_channels, int32_t d);
+int kgcn_vae_recon_fwd_f32(const kgcn_csr_batch* adj_ch, int32_t num_channels, const float* const* y, const float* const* w,
+                           int32_t d, const float* feat_logits, const float* feat_target, int32_t f, const float* mask,
+                           const float* kl, float* per_graph, float* sums, void* stream);
+int kgcn_vae_recon_bwd_f32(const kgcn_csr_batch* adj_ch, int32_t num_channels, const float* const* y, const float* const* w,
+                           int32_t d, const float* feat_logits, const float* feat_target, int32_t f, const float* mask,
+                           const float* g_opt, const float* g_sum, float* const* dy, float* const* dw, float* dfeat,
+                           float* dkl, void* workspace, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

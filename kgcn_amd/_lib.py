@@ -258,6 +258,18 @@ SIGNATURES = {
     "kgcn_gin_aggregate_bwd_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
     "kgcn_gin_aggregate_bwd_f32": (ctypes.c_int, [_CSRP, c_i32, c_f32p, c_i32, c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p,
                                                   c_i64, ctypes.c_void_p]),
+    # graph VAE (csrc/vae.hip)
+    "kgcn_philox4x64_raw": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_void_p, c_i64, ctypes.c_void_p, ctypes.c_void_p]),
+    "kgcn_normal_f32": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_void_p, c_i64, c_f32p, ctypes.c_void_p]),
+    "kgcn_vae_sample_fwd_f32": (ctypes.c_int, [c_f32p, c_f32p, c_i32, c_i32, c_i32, c_i32, c_f32p, ctypes.c_uint64, ctypes.c_void_p,
+                                               c_f32p, c_f32p, ctypes.c_void_p]),
+    "kgcn_vae_sample_bwd_f32": (ctypes.c_int, [c_f32p, c_f32p, c_i32, c_i32, c_i32, c_i32, c_f32p, ctypes.c_uint64, ctypes.c_void_p,
+                                               _PTRP, c_i32, c_f32p, c_f32p, c_f32p, ctypes.c_void_p]),
+    "kgcn_vae_recon_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
+    "kgcn_vae_recon_fwd_f32": (ctypes.c_int, [_CSRP, c_i32, _PTRP, _PTRP, c_i32, c_f32p, c_f32p, c_i32, c_f32p, c_f32p, c_f32p,
+                                              c_f32p, ctypes.c_void_p]),
+    "kgcn_vae_recon_bwd_f32": (ctypes.c_int, [_CSRP, c_i32, _PTRP, _PTRP, c_i32, c_f32p, c_f32p, c_i32, c_f32p, c_f32p, c_f32p,
+                                              _PTRP, _PTRP, c_f32p, c_f32p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
     "kgcn_graph_gather_bwd_add_f32": (ctypes.c_int, [c_f32p, c_f32p, c_i64, c_i32, c_i32, c_f32p, ctypes.c_void_p]),
     "kgcn_dot_workspace_bytes": (c_i64, [c_i64]),
     "kgcn_dot_f32": (ctypes.c_int, [c_f32p, c_f32p, c_i64, c_f32p, ctypes.c_void_p, c_i64,

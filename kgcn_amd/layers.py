@@ -43,11 +43,14 @@ def load_bspmm(args):
 
 
 def _init_tensor(shape, initializer, device):
-    """Keras initializer names used on this path: 'glorot_uniform' (kernels), 'zeros'."""
+    """Keras initializer names used on this path: 'glorot_uniform' (kernels), 'zeros', 'random_uniform' (Keras' RandomUniform
+    defaults, U(-0.05, 0.05): example_model/model_vae.py:89, :110)."""
     t = torch.empty(shape, dtype=torch.float32, device=device)
     if callable(initializer):
         with torch.no_grad():
             t.copy_(torch.as_tensor(initializer(shape), dtype=torch.float32))
+    elif initializer == "random_uniform":
+        nn.init.uniform_(t, -0.05, 0.05)
     elif initializer == "glorot_uniform":
         fan_in, fan_out = (shape[0], shape[1]) if len(shape) == 2 else (1, 1)
         lim = math.sqrt(6.0 / (fan_in + fan_out))
@@ -69,6 +72,8 @@ def _init_vector(d, initializer, device, fan=None):
         fi, fo = (d, d) if fan is None else fan
         lim = math.sqrt(6.0 / (fi + fo))
         nn.init.uniform_(t, -lim, lim)
+    elif initializer == "random_uniform":
+        nn.init.uniform_(t, -0.05, 0.05)
     elif initializer == "zeros":
         nn.init.zeros_(t)
     elif initializer == "ones":

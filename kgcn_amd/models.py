@@ -30,18 +30,23 @@ GraphBatchNormalization = layers.GraphBatchNormalization
 
 
 class KerasDense(nn.Module):
-    """K.layers.Dense(units) on [B, D] (model.py:55): kernel glorot-uniform, bias zeros."""
+    """K.layers.Dense(units) on [B, D] (model.py:55): kernel glorot-uniform (or `kernel_initializer`, a Keras name such as
+    'random_uniform': model_vae.py:89), bias zeros."""
 
-    def __init__(self, units):
+    def __init__(self, units, kernel_initializer="glorot_uniform"):
         super().__init__()
         self.units = units
+        self.kernel_initializer = kernel_initializer
         self.kernel = None
         self.bias = None
 
-    def forward(self, x):
+    def build(self, din, device):
         if self.kernel is None:
-            self.kernel = nn.Parameter(layers._init_tensor((x.shape[1], self.units), "glorot_uniform", x.device))
-            self.bias = nn.Parameter(torch.zeros(self.units, device=x.device))
+            self.kernel = nn.Parameter(layers._init_tensor((din, self.units), self.kernel_initializer, device))
+            self.bias = nn.Parameter(torch.zeros(self.units, device=device))
+
+    def forward(self, x):
+        self.build(x.shape[1], x.device)
         return ops.dense(x, self.kernel, self.bias)
 
 
@@ -277,3 +282,106 @@ class GATNet(nn.Module):
             if i > 0:
                 block_out.append(layer)
         return self.out(torch.cat([self.gather(o) for o in block_out], dim=1))
+
+
+class _LinkDecoder(nn.Module):
+    """decode_links of example_model/model_vae.py:115-133 for one adjacency channel: GraphDense(64), BN, sigmoid,
+    GraphDense(64), sigmoid, GraphDecoderDistMult (whose [B, N, N] product is left to ops.vae_recon)."""
+
+    def __init__(self):
+        super().__init__()
+        self.dense1 = layers.GraphDense(64)                                   # :124
+        self.bn = GraphBatchNormalization(activation="sigmoid")               # :125-128 tf.sigmoid(bn(...)), one pass
+        self.dense2 = layers.GraphDense(64, activation="sigmoid")             # :129-130
+        self.distmult = layers.GraphDecoderDistMult()                         # :132
+
+    def forward(self, z, n_nodes, enabled_node_nums=None):
+        y = self.dense2(self.bn(self.dense1(z), max_node_num=n_nodes, enabled_node_nums=enabled_node_nums))
+        if not self.distmult.built:
+            self.distmult.build(y.shape, y.device)
+        return y, self.distmult.w[0]
+
+
+class GraphVAE(nn.Module):
+    """example_model/model_vae.py (the kgcn-gen graph VAE of example_config/vae.json), call by call:
+      encode (:63-97)   GraphConv(64), BN, tanh, GraphConv(64), BN, tanh, GraphDense(64), sigmoid, GraphGather,
+                        Dense(64, random_uniform) -> mean, Dense(64) -> std
+      sample (:164-181) ops.vae_sample: mean = clip(., -100, 100), std = clip(sqrt(softplus(.)), -5, 5), z = mean + std eps
+                        on all N rows, the per-graph KL sum (csrc/vae.hip)
+      decode_nodes (:100-112)  GraphDense(F, random_uniform)
+      decode_links (:115-133)  per channel GraphDense(64), BN, sigmoid, GraphDense(64), sigmoid, GraphDecoderDistMult
+      cost (:203-253)   ops.vae_recon: node-feature and link sigmoid CE, correct_exist; the [B, C, N, N] logits are never formed.
+
+    forward(features, adjs, graph_mask=None, enabled_node_nums=None, eps=None) -> cost_opt (0-d tensor); cost_sum and
+    correct_count of the same call are left in .cost_sum / .correct_count, so that loss(out, labels, mask) -> (cost_opt,
+    cost_sum) lets train.GraphedTrainStep train it unchanged: the reference's `mask` (1 per real graph, 0 per dummy) reaches the
+    model as the fwd_kwarg graph_mask (the step's own `mask` argument is not passed to models).  eps: the reference's `epsilon` placeholder
+    [B, N, 64]; None draws the Philox noise of (seed, *step) -- bind_step(optimizer._t_dev) makes it a function of the training
+    step, read on the device, so every hipGraph replay draws fresh noise and eager and replayed steps match bit for bit.
+    The autoencoder's target is its input: pair adjacency = adjs, pair features = features.
+
+    Reference quirks kept:
+      - the KL term is 1 + 2 log(std + 1e-10) - mean^2 - std (-std, not -std^2), summed over the N tiled copies of the latent
+        rows (:170-180), and averaged over the PADDED batch: dummy graphs count and the mask is not applied to it (:181);
+      - the reconstruction counts padded node rows and columns: N = graph_node_num, label 0 there (:208-228);
+      - cost_sum = reduce_mean(cost) (:239), not a sum;
+      - the gradient of tf.clip_by_value passes at equality (TF's _ClipByValueGrad);
+      - BN in Keras inference mode with its moving statistics (quirk Q6).
+    Limits of the fused loss: N <= 128, C <= 8 (ops.vae_recon raises beyond them)."""
+
+    def __init__(self, feature_dim, adj_channel_num=1, seed=0):
+        super().__init__()
+        C = int(adj_channel_num)
+        self.seed = int(seed)
+        self.step = None
+        self.conv1 = layers.GraphConv(64, C)                                  # :75
+        self.bn1 = GraphBatchNormalization(activation="tanh")                 # :76-79 tf.tanh(bn(...)), one pass
+        self.conv2 = layers.GraphConv(64, C)                                  # :80
+        self.bn2 = GraphBatchNormalization(activation="tanh")                 # :81-84
+        self.dense = layers.GraphDense(64, activation="sigmoid")              # :85-86
+        self.gather = layers.GraphGather()                                    # :87
+        self.mean = KerasDense(64, kernel_initializer="random_uniform")       # :89-91
+        self.std = KerasDense(64)                                             # :92
+        self.node_decoder = layers.GraphDense(int(feature_dim), kernel_initializer="random_uniform")   # :109-111
+        self.link_decoders = nn.ModuleList([_LinkDecoder() for _ in range(C)])                        # :196-199
+        self.cost_sum = self.correct_count = None
+
+    def bind_step(self, step):
+        """step: a one-element int64 device tensor (TFAdam._t_dev) the noise kernels read at run time; None: step 0."""
+        self.step = step
+        return self
+
+    def _encode_decode(self, features, adjs, enabled_node_nums, eps):
+        adj = layers._pack(adjs, features)
+        N = features.shape[1]
+        h = self.bn1(self.conv1(features, adj=adj), max_node_num=N, enabled_node_nums=enabled_node_nums)
+        h = self.bn2(self.conv2(h, adj=adj), max_node_num=N, enabled_node_nums=enabled_node_nums)
+        g = self.gather(self.dense(h))
+        # the mean and std Dense layers (:89-92) as one GEMM over [W_mean | W_std]
+        self.mean.build(g.shape[1], g.device)
+        self.std.build(g.shape[1], g.device)
+        wcat, bcat = ops.cat_channels([self.mean.kernel, self.std.kernel], [self.mean.bias, self.std.bias])
+        ms = ops.dense(g, wcat, bcat)
+        kl, *zs = ops.vae_sample(ms, N, eps, self.seed, self.step, copies=1 + len(self.link_decoders))
+        xf = self.node_decoder(zs[0])
+        dec = [d(z, N, enabled_node_nums) for d, z in zip(self.link_decoders, zs[1:])]
+        return adj, kl, xf, [y for y, _ in dec], [w for _, w in dec]
+
+    def forward(self, features, adjs, graph_mask=None, enabled_node_nums=None, eps=None):
+        adj, kl, xf, ys, ws = self._encode_decode(features, adjs, enabled_node_nums, eps)
+        cost_opt, cost_sum, correct_count = ops.vae_recon(adj, ys, ws, xf, features, graph_mask, kl)
+        # detached: a kept reference must not hold this call's autograd graph (GraphedTrainStep's capture needs none alive)
+        self.cost_sum, self.correct_count = cost_sum.detach(), correct_count.detach()
+        return cost_opt
+
+    def loss(self, out, labels=None, mask=None):
+        """loss_fn for train.train_step / GraphedTrainStep: (cost_opt, cost_sum) of the forward call that produced `out`."""
+        return out, self.cost_sum
+
+    @torch.no_grad()
+    def reconstruct(self, features, adjs, enabled_node_nums=None, eps=None):
+        """The reference's `prediction` (:255-258): (sigmoid(decoded features) [B, N, F], sigmoid(decoded adjacency)
+        [B, C, N, N]) -- the dense adjacency is the output here, so it is materialised (ops.gram per channel)."""
+        _, _, xf, ys, ws = self._encode_decode(features, adjs, enabled_node_nums, eps)
+        adj = torch.stack([ops.gram(y, w) for y, w in zip(ys, ws)], dim=1)
+        return ops.activation(xf, "sigmoid"), ops.activation(adj, "sigmoid")

@@ -9,6 +9,7 @@ Gradients follow the reference's registered gradients:
 and TF's MatMul / BiasAdd gradients for the dense part.
 """
 import contextlib
+import ctypes
 
 import torch
 
@@ -1814,3 +1815,164 @@ def graph_bn(x, gamma, beta, mean, var, enabled=None, eps=1e-3, training=False, 
     var are THIS batch's statistics and the backward differentiates through them.  The activation rides in the same pass
     (and its derivative in the backward's reads)."""
     return _GraphBN.apply(x, gamma, beta, mean, var, enabled, eps, training, act_code(activation))
+
+
+# -------------------------------------------------------------------------------------------------
+# graph VAE (example_model/model_vae.py; csrc/vae.hip): counter-based noise, reparameterisation + KL, reconstruction loss
+# -------------------------------------------------------------------------------------------------
+VAE_MAX_NODES, VAE_MAX_CHANNELS, VAE_MAX_DIM = 128, 8, 64
+
+
+def _step_ptr(step):
+    """A device int64 scalar (read by the kernel at run time, e.g. TFAdam._t_dev) or None (step 0)."""
+    if step is None:
+        return None
+    if not (torch.is_tensor(step) and step.is_cuda and step.dtype == torch.int64 and step.numel() == 1):
+        raise _lib.KgcnHipError("step must be a one-element int64 device tensor (or None)")
+    return step
+
+
+def philox4x64_raw(seed, step, num_blocks, device):
+    """Words of Philox4x64-10 blocks 0 .. num_blocks-1, key (seed, 0), counter (j, step, 0, 0): int64 [num_blocks, 4]
+    holding the uint64 bit patterns."""
+    out = torch.empty((int(num_blocks), 4), device=device, dtype=torch.int64)
+    check(lib.kgcn_philox4x64_raw(int(seed) & (2 ** 64 - 1), ptr(_step_ptr(step)), int(num_blocks), ptr(out), current_stream()),
+          "kgcn_philox4x64_raw")
+    return out
+
+
+def normal(seed, step, shape, device):
+    """The noise the VAE sample kernels draw for (seed, step): N(0, 1) values of Philox4x64-10 + Box-Muller (include/kgcn_hip.h)."""
+    out = torch.empty(shape, device=device, dtype=torch.float32)
+    check(lib.kgcn_normal_f32(int(seed) & (2 ** 64 - 1), ptr(_step_ptr(step)), out.numel(), ptr(out), current_stream()),
+          "kgcn_normal_f32")
+    return out
+
+
+class _VaeSample(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ms, n_nodes, eps, seed, step, copies):
+        ms = _f32c(ms, "mean / std pre-activations")
+        if ms.dim() != 2 or ms.shape[1] % 2:
+            raise _lib.KgcnHipError("mean / std pre-activations must be [batch, 2 width], got %s" % (tuple(ms.shape),))
+        B, D = ms.shape[0], ms.shape[1] // 2
+        e = None if eps is None else _f32c(eps, "epsilon")
+        if e is not None and tuple(e.shape) != (B, n_nodes, D):
+            raise _lib.KgcnHipError("epsilon is %s, expected %s" % (tuple(e.shape), (B, n_nodes, D)))
+        z = torch.empty((B, n_nodes, D), device=ms.device, dtype=torch.float32)
+        kl = torch.empty((B,), device=ms.device, dtype=torch.float32)
+        check(lib.kgcn_vae_sample_fwd_f32(ptr(ms), ms.data_ptr() + 4 * D, B, n_nodes, D, 2 * D, ptr(e), int(seed) & (2 ** 64 - 1),
+                                          ptr(step), ptr(z), ptr(kl), current_stream()), "kgcn_vae_sample_fwd_f32")
+        ctx.save_for_backward(ms, e if e is not None else ms.new_empty(0))
+        ctx.has_eps, ctx.seed, ctx.step, ctx.n_nodes = e is not None, seed, step, n_nodes
+        ctx.set_materialize_grads(False)
+        # one view of z per consumer: their gradients are added inside the backward kernel, not by an autograd add
+        return (kl,) + tuple(z.view(B, n_nodes, D) for _ in range(copies))
+
+    @staticmethod
+    def backward(ctx, gkl, *gz):
+        ms, e = ctx.saved_tensors
+        B, D = ms.shape[0], ms.shape[1] // 2
+        gz = [_f32c(g, "grad") for g in gz if g is not None]
+        if not gz:
+            gz = [ms.new_zeros((B, ctx.n_nodes, D))]
+        gk = None if gkl is None else _f32c(gkl, "grad")
+        dms = torch.empty_like(ms)
+        check(lib.kgcn_vae_sample_bwd_f32(ptr(ms), ms.data_ptr() + 4 * D, B, ctx.n_nodes, D, 2 * D, ptr(e) if ctx.has_eps else None,
+                                          int(ctx.seed) & (2 ** 64 - 1), ptr(ctx.step), _ptr_array(gz), len(gz), ptr(gk), ptr(dms),
+                                          dms.data_ptr() + 4 * D, current_stream()), "kgcn_vae_sample_bwd_f32")
+        return dms, None, None, None, None, None
+
+
+def vae_sample(ms, n_nodes, eps=None, seed=0, step=None, copies=1):
+    """model_vae.py:89-96, 169-181 -> (kl [B], z [B, N, D] x copies).  ms [B, 2 D]: the mean Dense layer's pre-activation in
+    columns 0 .. D-1, the std layer's in D .. 2D-1 (both layers as ONE GEMM over [W_mean | W_std]: the read-out they share gets
+    one gradient, no autograd add).  mean = clip(., -100, 100), std = clip(sqrt(softplus(.)), -5, 5), z = mean + std * eps
+    (the reference's `epsilon` placeholder when `eps` is given, the (seed, step) Philox noise otherwise, step a device int64
+    read at run time); kl[b] = N sum_k (1 + 2 log(std + 1e-10) - mean^2 - std).  `copies` views of z, one per consumer, whose
+    gradients the backward kernel adds; eps is regenerated there, never stored."""
+    if not 1 <= int(copies) <= VAE_MAX_CHANNELS + 1:
+        raise _lib.KgcnHipError("vae_sample: 1..%d copies of z" % (VAE_MAX_CHANNELS + 1))
+    return _VaeSample.apply(ms, int(n_nodes), eps, seed, _step_ptr(step), int(copies))
+
+
+def _ptr_array(ts):
+    arr = (ctypes.c_void_p * len(ts))()
+    for i, t in enumerate(ts):
+        arr[i] = None if t is None else t.data_ptr()
+    return arr
+
+
+def _vae_adj(adj, C, B, N):
+    if not isinstance(adj, BatchedAdjacency):
+        raise _lib.KgcnHipError("vae_recon needs a packed kgcn_amd.BatchedAdjacency")
+    if adj.num_channels != C or adj.num_graphs != B or adj.n_nodes != N:
+        raise _lib.KgcnHipError("adjacency (%d channels, %d graphs x %d nodes) does not match the decoders (%d, %d x %d)"
+                                % (adj.num_channels, adj.num_graphs, adj.n_nodes, C, B, N))
+    return adj.desc_array(False)
+
+
+class _VaeRecon(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, adj, mask, feat_target, kl, feat_logits, *yw):
+        C = len(yw) // 2
+        ys = [_f32c(t, "decoder output") for t in yw[:C]]
+        ws = [_f32c(t.reshape(-1), "DistMult kernel") for t in yw[C:]]
+        xf, tf = _f32c(feat_logits, "decoded features"), _f32c(feat_target, "features")
+        B, N, D = ys[0].shape
+        F = xf.shape[2]
+        if any(tuple(y.shape) != (B, N, D) for y in ys) or any(w.numel() != D for w in ws) or tuple(tf.shape) != tuple(xf.shape) \
+                or tuple(xf.shape[:2]) != (B, N):
+            raise _lib.KgcnHipError("vae_recon: operand shapes disagree")
+        mk = None if mask is None else _f32c(mask.to(torch.float32).reshape(-1), "mask")
+        klc = None if kl is None else _f32c(kl, "kl")
+        desc = _vae_adj(adj, C, B, N)
+        per_graph = torch.empty((3, B), device=xf.device, dtype=torch.float32)
+        sums = torch.empty((3,), device=xf.device, dtype=torch.float32)
+        check(lib.kgcn_vae_recon_fwd_f32(desc, C, _ptr_array(ys), _ptr_array(ws), D, ptr(xf), ptr(tf), F, ptr(mk), ptr(klc),
+                                         ptr(per_graph), ptr(sums), current_stream()), "kgcn_vae_recon_fwd_f32")
+        ctx.adj, ctx.C, ctx.has_kl = adj, C, kl is not None
+        ctx.w_shapes = [tuple(t.shape) for t in yw[C:]]
+        ctx.defer_ok = all(t.is_leaf for t in yw[C:])
+        ctx.defer_ids = tuple(yw[C:])
+        _count_use(*yw[C:])
+        ctx.save_for_backward(xf, tf, mk if mk is not None else xf.new_empty(0), *ys, *ws)
+        ctx.has_mask = mk is not None
+        ctx.set_materialize_grads(False)
+        return sums[0], sums[1], sums[2]
+
+    @staticmethod
+    def backward(ctx, g_opt, g_sum, _g_count):
+        saved = ctx.saved_tensors
+        xf, tf, mk = saved[:3]
+        C = ctx.C
+        ys, ws = saved[3:3 + C], saved[3 + C:]
+        B, N, D = ys[0].shape
+        F = xf.shape[2]
+        if g_opt is None and g_sum is None:
+            return (None,) * (5 + 2 * C)
+        go = None if g_opt is None else _f32c(g_opt.reshape(1), "grad")
+        gs = None if g_sum is None else _f32c(g_sum.reshape(1), "grad")
+        dys = [torch.empty_like(y) for y in ys]
+        dws = [torch.empty((D,), device=xf.device, dtype=torch.float32) for _ in range(C)]
+        dxf = torch.empty_like(xf)
+        dkl = torch.empty((B,), device=xf.device, dtype=torch.float32) if (ctx.has_kl and go is not None) else None
+        wsb = lib.kgcn_vae_recon_workspace_bytes(B, C, D)
+        wsp = torch.empty((max(wsb, 4) // 4,), device=xf.device, dtype=torch.float32)
+        with _no_deferral_unless(ctx.defer_ok and _single_use(*ctx.defer_ids)):
+            check(lib.kgcn_vae_recon_bwd_f32(_vae_adj(ctx.adj, C, B, N), C, _ptr_array(ys), _ptr_array(ws), D, ptr(xf), ptr(tf), F,
+                                             ptr(mk) if ctx.has_mask else None, ptr(go), ptr(gs), _ptr_array(dys),
+                                             _ptr_array(dws), ptr(dxf), ptr(dkl), ptr(wsp), wsb, current_stream()),
+                  "kgcn_vae_recon_bwd_f32")
+        _keep_until_flush(wsp)
+        return (None, None, None, dkl, dxf) + tuple(dys) + tuple(dw.view(s) for dw, s in zip(dws, ctx.w_shapes))
+
+
+def vae_recon(adj, ys, ws, feat_logits, feat_target, mask=None, kl=None):
+    """model_vae.py:203-253 -> (cost_opt, cost_sum, correct_count), none of them materialising the [B, C, N, N] logits:
+    ys[c] [B, N, D] / ws[c] [D] the link decoder output and DistMult kernel of adjacency channel c, adj the packed target
+    adjacency (kgcn_amd.BatchedAdjacency, C channels), feat_logits / feat_target [B, N, F], mask [B] (None = ones), kl [B]
+    the per-graph KL sums of vae_sample (None = no KL term).  Limits: N <= 128, C <= 8, D <= 64 (larger shapes raise)."""
+    if len(ys) != len(ws) or not ys:
+        raise _lib.KgcnHipError("vae_recon: one decoder output and one DistMult kernel per channel")
+    return _VaeRecon.apply(adj, mask, feat_target, kl, feat_logits, *ys, *ws)
