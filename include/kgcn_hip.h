@@ -67,7 +67,10 @@ extern "C" {
  * kgcn_copy2d_multi_f32 (+ kgcn_copy2d_job), kgcn_hbm_probe.
  * The graph VAE added entry points only as well (version still 2): kgcn_philox4x64_raw, kgcn_normal_f32,
  * kgcn_vae_sample_fwd_f32 / kgcn_vae_sample_bwd_f32, kgcn_vae_recon_workspace_bytes, kgcn_vae_recon_fwd_f32 /
- * kgcn_vae_recon_bwd_f32. */
+ * kgcn_vae_recon_bwd_f32.
+ * The multimodal sequence encoder added entry points only (version still 2): kgcn_seq_convpool_fwd_f32 /
+ * kgcn_seq_convpool_bwd_f32 (+ kgcn_seq_convpool_workspace_bytes), kgcn_seq_lstm_fwd_f32 / kgcn_seq_lstm_bwd_f32
+ * (+ kgcn_seq_lstm_stash_floats, kgcn_seq_lstm_workspace_bytes), kgcn_graph_gather_bwd_ld_f32. */
 #define KGCN_HIP_ABI_VERSION 2
 
 /* Column index of the padding entries of a row-padded batch (see row_pad): they carry value 0 and
@@ -744,6 +747,54 @@ int kgcn_vae_recon_bwd_f32(const kgcn_csr_batch* adj_ch, int32_t num_channels, c
                            int32_t d, const float* feat_logits, const float* feat_target, int32_t f, const float* mask,
                            const float* g_opt, const float* g_sum, float* const* dy, float* const* dw, float* dfeat,
                            float* dkl, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* -- protein-sequence encoder of the multimodal model (example_model/model_multimodal.py:70-93) ---------------------------
+ * Embedding(S, E) -> Conv1D(F, k, padding="same", relu) -> MaxPooling1D(p) -> LSTM(H, go_backwards=True).
+ * Conv-pool: tokens [B, L] int32 in [0, S) (checked by the caller on the host, not here), table [S, E], w [k, E, F], bias [F]
+ * -> out [B, L / p, F] = max over each pool window of relu(conv), TF SAME padding at stride 1 ((k-1)/2 zero positions on the left,
+ * the rest on the right), positions >= (L / p) p dropped.  argmax (NULL under no_grad) [B, L / p, F] bytes: the lowest index in
+ * the window among equal maxima, 0xFF when the maximum is not > 0 (relu passes no gradient).  Backward: d out -> d table [S, E],
+ * d w, d bias through per-workgroup partials in `workspace` (>= kgcn_seq_convpool_workspace_bytes) and fixed-order second stages
+ * (deferrable: kgcn_reduce_defer).  Limits: E <= 32, F <= 64, k <= 8, p <= 8, S <= 1024, L <= 8192.
+ * LSTM: Keras v1 cell, gate order i, f, c, o, kernel wx [D, 4H], recurrent kernel wh [H, 4H], bias [4H]; recurrent activation
+ * KGCN_SEQ_ACT_HARD_SIGMOID (clip(0.2 z + 0.5, 0, 1), gradient passing at the boundaries) or KGCN_SEQ_ACT_SIGMOID, tanh elsewhere,
+ * zero initial state, x [B, T, D] processed from step T-1 down to 0 with no masking; h_out[b * h_ld + u] = h after step 0.
+ * stash (NULL under no_grad): kgcn_seq_lstm_stash_floats(B, T, H) floats, per (b, t) the 4H gate pre-activations, h and c
+ * (6H floats, 768 bytes a sequence step at H = 32).  The backward reads dh[b * dh_ld + u] (NULL = 0), OVERWRITES the
+ * pre-activations of the stash with their gradients, writes dx [B, T, D] (may be NULL) and -- all three or none -- d wx, d wh,
+ * d bias through partials in `workspace` (>= kgcn_seq_lstm_workspace_bytes) and fixed-order second stages (deferrable).
+ * Limits: D <= 64, H <= 64, T <= 8192.  No float atomics: results are bitwise reproducible. */
+#define KGCN_SEQ_MAX_EMBED 32
+#define KGCN_SEQ_MAX_FILTERS 64
+#define KGCN_SEQ_MAX_KERNEL 8
+#define KGCN_SEQ_MAX_POOL 8
+#define KGCN_SEQ_MAX_UNITS 64
+#define KGCN_SEQ_MAX_LSTM_INPUT 64
+#define KGCN_SEQ_MAX_SYMBOLS 1024
+#define KGCN_SEQ_MAX_LENGTH 8192
+#define KGCN_SEQ_ACT_HARD_SIGMOID 0
+#define KGCN_SEQ_ACT_SIGMOID 1
+int64_t kgcn_seq_convpool_workspace_bytes(int32_t batch, int32_t length, int32_t symbols, int32_t embed_dim, int32_t kernel_size,
+                                          int32_t filters, int32_t pool);
+int kgcn_seq_convpool_fwd_f32(const int32_t* tokens, int32_t batch, int32_t length, const float* table, int32_t symbols,
+                              int32_t embed_dim, const float* w, const float* bias, int32_t kernel_size, int32_t filters,
+                              int32_t pool, float* out, uint8_t* argmax, void* stream);
+int kgcn_seq_convpool_bwd_f32(const int32_t* tokens, int32_t batch, int32_t length, const float* table, int32_t symbols,
+                              int32_t embed_dim, const float* w, int32_t kernel_size, int32_t filters, int32_t pool,
+                              const float* dout, const uint8_t* argmax, float* dtable, float* dw, float* dbias, void* workspace,
+                              int64_t workspace_bytes, void* stream);
+int64_t kgcn_seq_lstm_stash_floats(int32_t batch, int32_t steps, int32_t units);
+int64_t kgcn_seq_lstm_workspace_bytes(int32_t batch, int32_t steps, int32_t in_dim, int32_t units);
+int kgcn_seq_lstm_fwd_f32(const float* x, int32_t batch, int32_t steps, int32_t in_dim, const float* wx, const float* wh,
+                          const float* bias, int32_t units, int32_t recurrent_act, float* h_out, int64_t h_ld, float* stash,
+                          void* stream);
+int kgcn_seq_lstm_bwd_f32(const float* x, int32_t batch, int32_t steps, int32_t in_dim, const float* wx, const float* wh,
+                          const float* bias, int32_t units, int32_t recurrent_act, const float* dh, int64_t dh_ld, float* stash,
+                          float* dx, float* dwx, float* dwh, float* dbias, void* workspace, int64_t workspace_bytes, void* stream);
+/* dx[b, n, :] = dout[b * dout_ld + :d]: the gradient of a GraphGather read-out written into a column block of a wider buffer
+ * (kgcn_graph_gather_fwd_ld_f32), read where it lies */
+int kgcn_graph_gather_bwd_ld_f32(const float* dout_grad, int64_t dout_ld, int64_t batch, int32_t n_nodes, int32_t d, float* dx,
+                                 void* stream);
 
 #ifdef __cplusplus
 }

@@ -270,6 +270,20 @@ SIGNATURES = {
                                               c_f32p, ctypes.c_void_p]),
     "kgcn_vae_recon_bwd_f32": (ctypes.c_int, [_CSRP, c_i32, _PTRP, _PTRP, c_i32, c_f32p, c_f32p, c_i32, c_f32p, c_f32p, c_f32p,
                                               _PTRP, _PTRP, c_f32p, c_f32p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
+    # multimodal sequence encoder (csrc/seq.hip)
+    "kgcn_seq_convpool_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32]),
+    "kgcn_seq_convpool_fwd_f32": (ctypes.c_int, [ctypes.c_void_p, c_i32, c_i32, c_f32p, c_i32, c_i32, c_f32p, c_f32p, c_i32, c_i32,
+                                                 c_i32, c_f32p, ctypes.c_void_p, ctypes.c_void_p]),
+    "kgcn_seq_convpool_bwd_f32": (ctypes.c_int, [ctypes.c_void_p, c_i32, c_i32, c_f32p, c_i32, c_i32, c_f32p, c_i32, c_i32, c_i32,
+                                                 c_f32p, ctypes.c_void_p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p, c_i64,
+                                                 ctypes.c_void_p]),
+    "kgcn_seq_lstm_stash_floats": (c_i64, [c_i32, c_i32, c_i32]),
+    "kgcn_seq_lstm_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i32]),
+    "kgcn_seq_lstm_fwd_f32": (ctypes.c_int, [c_f32p, c_i32, c_i32, c_i32, c_f32p, c_f32p, c_f32p, c_i32, c_i32, c_f32p, c_i64, c_f32p,
+                                             ctypes.c_void_p]),
+    "kgcn_seq_lstm_bwd_f32": (ctypes.c_int, [c_f32p, c_i32, c_i32, c_i32, c_f32p, c_f32p, c_f32p, c_i32, c_i32, c_f32p, c_i64, c_f32p,
+                                             c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
+    "kgcn_graph_gather_bwd_ld_f32": (ctypes.c_int, [c_f32p, c_i64, c_i64, c_i32, c_i32, c_f32p, ctypes.c_void_p]),
     "kgcn_graph_gather_bwd_add_f32": (ctypes.c_int, [c_f32p, c_f32p, c_i64, c_i32, c_i32, c_f32p, ctypes.c_void_p]),
     "kgcn_dot_workspace_bytes": (c_i64, [c_i64]),
     "kgcn_dot_f32": (ctypes.c_int, [c_f32p, c_f32p, c_i64, c_f32p, ctypes.c_void_p, c_i64,

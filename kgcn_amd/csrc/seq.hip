@@ -1,0 +1,677 @@
+// Protein-sequence encoder of example_model/model_multimodal.py:70-93:
+//   Embedding(S, E) -> Conv1D(F, k, padding="same", relu) -> MaxPooling1D(p) -> LSTM(H, go_backwards=True) -> h after step 0
+//
+//   conv-pool  one pass: the embedding rows of a window of tokens are gathered into LDS, the conv, bias, relu and the max over
+//              each pool window are formed in registers; neither the [B, L, E] embedding nor the [B, L, F] conv output is
+//              written.  SAME padding at stride 1: (k-1)/2 positions on the left, the rest on the right.  Training writes the
+//              arg-max of every pooled output as a byte (the lowest index among equal maxima; 0xFF when the maximum is not > 0,
+//              i.e. relu passes no gradient).  The backward routes d pooled to that position, forms d W / d bias and the
+//              per-position embedding gradient, and adds the latter into a per-workgroup [S, E] table (each table row is owned
+//              by one thread group, visited in position order): fixed-order partials, fixed-order second stage.
+//   LSTM       Keras v1 cell, gate order i, f, c, o; recurrent activation hard_sigmoid clip(0.2 z + 0.5, 0, 1) (or sigmoid),
+//              tanh elsewhere, zero initial state, the steps of the padded sequence last to first, no masking.  One workgroup
+//              owns 256 / H' sequences (H' = H rounded up to 16 / 32 / 64) for all steps; one thread per (sequence, unit)
+//              forms the four gate pre-activations from [x_t | h] against [W_x ; W_h] held in LDS (fp32 FMAs).  Training
+//              writes the BPTT stash: z (the 4H pre-activations), h and c of every step, 6H floats per sequence and step.
+//              The backward walks the steps in reverse processing order, writes dX and overwrites z with dz; a third kernel
+//              forms d W_x, d W_h, d bias from [x_t | h_prev | 1]^T dz in per-workgroup partials (fixed-order second stage).
+// Every second stage is a parameter gradient and goes through reduce_or_defer (kgcn_reduce_defer).  No float atomics: results
+// are bitwise reproducible.
+#include "kgcn_common.h"
+
+namespace kgcn {
+int reduce_or_defer(const float* part, int nparts, long n, float* out, hipStream_t s);
+
+namespace {
+constexpr int kTile = 16;                 // pooled positions per conv-pool tile (4 per wave)
+constexpr int kConvGridFwd = 2048;
+constexpr int kConvGridBwd = 512;
+constexpr int kLstmChunks = 256;          // row chunks of the LSTM weight-gradient kernel
+
+__host__ __device__ __forceinline__ int round4(int x) { return (x + 3) & ~3; }
+
+struct ConvArgs {
+  const int32_t* tok;
+  const float* table;
+  const float* w;       // [k, E, F]
+  int B, L, S, E, E4, F, k, p, padL, T;   // T = L / p pooled positions
+  long tiles;           // B * ceil(T / kTile)
+};
+
+// window of conv-input rows of tile (b, t0): rows r = 0 .. nrows-1 are sequence positions l = t0 p - padL + r
+__device__ __forceinline__ void stage_window(const ConvArgs& a, int b, int t0, int nrows, float* win, int* twin) {
+  const int l0 = t0 * a.p - a.padL;
+  for (int i = threadIdx.x; i < nrows; i += blockDim.x) {
+    const int l = l0 + i;
+    twin[i] = (l >= 0 && l < a.L) ? a.tok[(long)b * a.L + l] : -1;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < nrows * a.E4; i += blockDim.x) {
+    const int r = i / a.E4, e = i - r * a.E4;
+    const int s = twin[r];
+    win[i] = (s >= 0 && e < a.E) ? a.table[(long)s * a.E + e] : 0.f;
+  }
+}
+
+// lane = filter f (< 64), wave = 4 pooled positions of the tile; acc[i][j] = conv at position (t0 + 4 wave + i) p + j
+__global__ __launch_bounds__(256) void convpool_fwd_kernel(ConvArgs a, const float* __restrict__ bias, float* __restrict__ out,
+                                                           uint8_t* __restrict__ argmax) {
+  extern __shared__ float lds[];
+  const int KE4 = a.k * a.E4;
+  float* ws = lds;                              // [k * E4][64]
+  float* win = ws + KE4 * 64;                   // [kTile p + k - 1][E4]
+  int* twin = reinterpret_cast<int*>(win + (kTile * a.p + a.k - 1) * a.E4);
+  for (int i = threadIdx.x; i < KE4 * 64; i += blockDim.x) {
+    const int r = i >> 6, f = i & 63, dk = r / a.E4, e = r - dk * a.E4;
+    ws[i] = (f < a.F && e < a.E) ? a.w[((long)dk * a.E + e) * a.F + f] : 0.f;
+  }
+  const int f = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const float bf = f < a.F ? bias[f] : 0.f;
+  const int tpb = (a.T + kTile - 1) / kTile;
+  const int nrows = kTile * a.p + a.k - 1;
+  for (long tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
+    const int b = (int)(tile / tpb), t0 = (int)(tile - (long)b * tpb) * kTile;
+    __syncthreads();                            // the previous tile's window is no longer read
+    stage_window(a, b, t0, nrows, win, twin);
+    __syncthreads();
+    float acc[4][8];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[i][j] = 0.f;
+    for (int dk = 0; dk < a.k; ++dk) {
+      for (int e = 0; e < a.E4; e += 4) {
+        const float* wp = ws + (dk * a.E4 + e) * 64 + f;
+        const float w0 = wp[0], w1 = wp[64], w2 = wp[128], w3 = wp[192];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            if (j < a.p) {
+              const f32x4 x = *reinterpret_cast<const f32x4*>(win + ((wv * 4 + i) * a.p + j + dk) * a.E4 + e);
+              acc[i][j] = fmaf(x.x, w0, fmaf(x.y, w1, fmaf(x.z, w2, fmaf(x.w, w3, acc[i][j]))));
+            }
+          }
+        }
+      }
+    }
+    if (f < a.F) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int t = t0 + wv * 4 + i;
+        if (t >= a.T) continue;
+        float m = -1.f;
+        int arg = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          if (j < a.p) {
+            const float v = fmaxf(acc[i][j] + bf, 0.f);
+            if (v > m) { m = v; arg = j; }
+          }
+        }
+        const long o = ((long)b * a.T + t) * a.F + f;
+        out[o] = m;
+        if (argmax) argmax[o] = m > 0.f ? (uint8_t)arg : (uint8_t)0xFF;
+      }
+    }
+  }
+}
+
+// Backward.  Phase 1 (lane f, wave rows r = dk E + e): d W[r, f] += g * window[c + dk, e] for the routed position c of every
+// pooled output; d bias[f] += g.  Phase 2 (lane e, 8 groups over window rows): v[row, e] = sum_dk sum_f G[row - dk, f] W[dk, e, f]
+// with G the routed conv gradient of this tile.  Phase 3: group q adds v[row] into table row s = token(row) for s % 8 == q, rows
+// in order.
+template <bool kTableInLds>
+__global__ __launch_bounds__(256) void convpool_bwd_kernel(ConvArgs a, const float* __restrict__ dout, const uint8_t* __restrict__ argmax,
+                                                           float* __restrict__ part_w, float* __restrict__ part_b,
+                                                           float* __restrict__ part_t) {
+  extern __shared__ float lds[];
+  const int F4p = round4(a.F) + 4;               // row stride of W / G in LDS (lanes of phase 2 read different e rows)
+  const int nrows = kTile * a.p + a.k - 1;
+  const int ncpos = kTile * a.p;
+  float* wb = lds;                               // [k][E][F4p]
+  float* g = wb + a.k * a.E * F4p;               // [kTile p][F4p]
+  float* win = g + ncpos * F4p;                  // [nrows][E4]
+  float* v = win + nrows * a.E4;                 // [nrows][32]
+  int* twin = reinterpret_cast<int*>(v + nrows * 32);
+  float* tab = reinterpret_cast<float*>(twin + round4(nrows));   // [S][E] (kTableInLds)
+  float* mytab = kTableInLds ? tab : part_t + (long)blockIdx.x * a.S * a.E;
+  for (int i = threadIdx.x; i < a.k * a.E * F4p; i += blockDim.x) {
+    const int fr = i % F4p, r = i / F4p;
+    wb[i] = fr < a.F ? a.w[(long)r * a.F + fr] : 0.f;
+  }
+  for (int i = threadIdx.x; i < a.S * a.E; i += blockDim.x) mytab[i] = 0.f;
+  const int f = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int KE = a.k * a.E;
+  float accw[64];
+#pragma unroll
+  for (int q = 0; q < 64; ++q) accw[q] = 0.f;
+  float accb = 0.f;
+  const int tpb = (a.T + kTile - 1) / kTile;
+  const int e2 = threadIdx.x & 31, grp = threadIdx.x >> 5;
+  for (long tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
+    const int b = (int)(tile / tpb), t0 = (int)(tile - (long)b * tpb) * kTile;
+    __syncthreads();
+    stage_window(a, b, t0, nrows, win, twin);
+    for (int i = threadIdx.x; i < ncpos * F4p; i += blockDim.x) {
+      const int c = i / F4p, fr = i - c * F4p;
+      const int t = t0 + c / a.p, j = c % a.p;
+      float gv = 0.f;
+      if (fr < a.F && t < a.T) {
+        const long o = ((long)b * a.T + t) * a.F + fr;
+        if (argmax[o] == j) gv = dout[o];
+      }
+      g[i] = gv;
+    }
+    __syncthreads();
+    // phase 1
+    if (f < a.F) {
+      for (int tl = 0; tl < kTile; ++tl) {
+        const int t = t0 + tl;
+        if (t >= a.T) break;
+        const long o = ((long)b * a.T + t) * a.F + f;
+        const int am = argmax[o];
+        if (am == 0xFF) continue;
+        const float gv = dout[o];
+        const int c = tl * a.p + am;
+        if (wv == 0) accb += gv;
+#pragma unroll
+        for (int q = 0; q < 64; ++q) {
+          const int r = wv + 4 * q;
+          if (r < KE) {
+            const int dk = r / a.E, e = r - dk * a.E;
+            accw[q] = fmaf(gv, win[(c + dk) * a.E4 + e], accw[q]);
+          }
+        }
+      }
+    }
+    // phase 2
+    if (e2 < a.E) {
+      for (int row = grp; row < nrows; row += 8) {
+        float s = 0.f;
+        for (int dk = 0; dk < a.k; ++dk) {
+          const int c = row - dk;
+          if (c < 0 || c >= ncpos) continue;
+          const float* gp = g + c * F4p;
+          const float* wp = wb + (dk * a.E + e2) * F4p;
+          for (int fr = 0; fr < a.F; fr += 4) {
+            const f32x4 gg = *reinterpret_cast<const f32x4*>(gp + fr);
+            const f32x4 ww = *reinterpret_cast<const f32x4*>(wp + fr);
+            s = fmaf(gg.x, ww.x, fmaf(gg.y, ww.y, fmaf(gg.z, ww.z, fmaf(gg.w, ww.w, s))));
+          }
+        }
+        v[row * 32 + e2] = s;
+      }
+    }
+    __syncthreads();
+    // phase 3
+    if (e2 < a.E) {
+      for (int row = 0; row < nrows; ++row) {
+        const int s = twin[row];
+        if (s >= 0 && (s & 7) == grp) mytab[s * a.E + e2] += v[row * 32 + e2];
+      }
+    }
+  }
+  __syncthreads();
+  if (f < a.F) {
+#pragma unroll
+    for (int q = 0; q < 64; ++q) {
+      const int r = wv + 4 * q;
+      if (r < KE) part_w[(long)blockIdx.x * KE * a.F + (long)r * a.F + f] = accw[q];
+    }
+    if (wv == 0) part_b[(long)blockIdx.x * a.F + f] = accb;
+  }
+  if (kTableInLds)
+    for (int i = threadIdx.x; i < a.S * a.E; i += blockDim.x) part_t[(long)blockIdx.x * a.S * a.E + i] = tab[i];
+}
+
+int conv_args(const int32_t* tokens, int32_t B, int32_t L, const float* table, int32_t S, int32_t E, const float* w, int32_t k,
+              int32_t F, int32_t p, const char* who, ConvArgs& a) {
+  if (B < 0 || L < 1 || L > KGCN_SEQ_MAX_LENGTH) return fail("%s: length %d outside 1..%d", who, L, KGCN_SEQ_MAX_LENGTH);
+  if (E < 1 || E > KGCN_SEQ_MAX_EMBED) return fail("%s: embedding width %d outside 1..%d", who, E, KGCN_SEQ_MAX_EMBED);
+  if (F < 1 || F > KGCN_SEQ_MAX_FILTERS) return fail("%s: %d filters outside 1..%d", who, F, KGCN_SEQ_MAX_FILTERS);
+  if (k < 1 || k > KGCN_SEQ_MAX_KERNEL) return fail("%s: kernel size %d outside 1..%d", who, k, KGCN_SEQ_MAX_KERNEL);
+  if (p < 1 || p > KGCN_SEQ_MAX_POOL) return fail("%s: pool size %d outside 1..%d", who, p, KGCN_SEQ_MAX_POOL);
+  if (S < 1 || S > KGCN_SEQ_MAX_SYMBOLS) return fail("%s: %d symbols outside 1..%d", who, S, KGCN_SEQ_MAX_SYMBOLS);
+  if ((int64_t)B * L >= (int64_t)INT32_MAX) return fail("%s: batch x length exceeds int32", who);
+  if (B > 0 && (!tokens || !table || !w)) return fail("%s: NULL operand", who);
+  a.tok = tokens; a.table = table; a.w = w;
+  a.B = B; a.L = L; a.S = S; a.E = E; a.E4 = round4(E); a.F = F; a.k = k; a.p = p; a.padL = (k - 1) / 2; a.T = L / p;
+  a.tiles = (long)B * ((a.T + kTile - 1) / kTile);
+  return 0;
+}
+
+size_t convpool_fwd_lds(const ConvArgs& a) {
+  const int nrows = kTile * a.p + a.k - 1;
+  return ((size_t)a.k * a.E4 * 64 + (size_t)nrows * a.E4 + nrows) * 4;
+}
+size_t convpool_bwd_lds(const ConvArgs& a, bool table_in_lds) {
+  const int nrows = kTile * a.p + a.k - 1, F4p = round4(a.F) + 4;
+  return ((size_t)a.k * a.E * F4p + (size_t)kTile * a.p * F4p + (size_t)nrows * a.E4 + (size_t)nrows * 32 + round4(nrows) +
+          (table_in_lds ? (size_t)a.S * a.E : 0)) * 4;
+}
+int convpool_bwd_grid(const ConvArgs& a) { return (int)(a.tiles < kConvGridBwd ? (a.tiles > 0 ? a.tiles : 1) : kConvGridBwd); }
+
+// every kernel here takes its LDS dynamically: allow the whole 160 KB once per kernel (a host call, never inside a capture twice)
+template <auto Fn>
+int allow_lds(size_t bytes) {
+  static bool done = false;
+  if (bytes > (size_t)kLdsBytes) return fail("seq kernels: %zu bytes of LDS needed, %d available", bytes, kLdsBytes);
+  if (!done) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Fn), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
+    if (e != hipSuccess) return fail("hipFuncSetAttribute: %s", hipGetErrorString(e));
+    done = true;
+  }
+  return 0;
+}
+
+// ---- LSTM ---------------------------------------------------------------------------------------------------------------
+struct LstmArgs {
+  const float* x;       // [B, T, D]
+  const float* wx;      // [D, 4H]
+  const float* wh;      // [H, 4H]
+  const float* bias;    // [4H]
+  int B, T, D, H, Hp, seqs, KA4, wstride, act;
+};
+
+__device__ __forceinline__ float rec_act(float z, int act) {
+  if (act == KGCN_SEQ_ACT_SIGMOID) return 1.f / (1.f + expf(-z));
+  const float y = __fadd_rn(__fmul_rn(0.2f, z), 0.5f);          // Keras hard_sigmoid: 0.2 x + 0.5, then clip
+  return fminf(fmaxf(y, 0.f), 1.f);
+}
+// derivative; tf.clip_by_value passes the gradient at the boundaries
+__device__ __forceinline__ float rec_act_grad(float z, float a, int act) {
+  if (act == KGCN_SEQ_ACT_SIGMOID) return a * (1.f - a);
+  const float y = __fadd_rn(__fmul_rn(0.2f, z), 0.5f);
+  return (y >= 0.f && y <= 1.f) ? 0.2f : 0.f;
+}
+
+// thread (sequence s = tid / Hp, unit u = tid % Hp); LDS: W [4][Hp][wstride] over k = [x (D) | h (H)], state [2][seqs][KA4]
+__global__ __launch_bounds__(256) void lstm_fwd_kernel(LstmArgs a, float* __restrict__ h_out, long h_ld, float* __restrict__ stash) {
+  extern __shared__ float lds[];
+  float* wl = lds;
+  float* st = wl + 4 * a.Hp * a.wstride;
+  const int H = a.H, D = a.D;
+  for (int i = threadIdx.x; i < 4 * a.Hp * a.wstride; i += blockDim.x) {
+    const int kk = i % a.wstride, r = i / a.wstride, u = r % a.Hp, gt = r / a.Hp;
+    float v = 0.f;
+    if (u < H) {
+      const int n = gt * H + u;
+      if (kk < D) v = a.wx[(long)kk * 4 * H + n];
+      else if (kk < D + H) v = a.wh[(long)(kk - D) * 4 * H + n];
+    }
+    wl[i] = v;
+  }
+  for (int i = threadIdx.x; i < 2 * a.seqs * a.KA4; i += blockDim.x) st[i] = 0.f;
+  const int s = threadIdx.x / a.Hp, u = threadIdx.x - s * a.Hp;
+  const int b = blockIdx.x * a.seqs + s;
+  const bool live = u < H && b < a.B;
+  float bg[4];
+#pragma unroll
+  for (int gt = 0; gt < 4; ++gt) bg[gt] = u < H ? a.bias[gt * H + u] : 0.f;
+  float c = 0.f, h = 0.f;
+  // x staging: element q of the [seqs, D] slab of a step; <= 4 per thread (seqs D <= 256 * 4)
+  const int nx = a.seqs * D;
+  float xr[4];
+  auto load_x = [&](int t) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int i = threadIdx.x + q * 256;
+      xr[q] = 0.f;
+      if (i < nx && t >= 0) {
+        const int ss = i / D, kk = i - ss * D, bb = blockIdx.x * a.seqs + ss;
+        if (bb < a.B) xr[q] = a.x[((long)bb * a.T + t) * D + kk];
+      }
+    }
+  };
+  load_x(a.T - 1);
+  int buf = 0;
+  for (int t = a.T - 1; t >= 0; --t) {                        // go_backwards: the last input step first
+    float* cur = st + buf * a.seqs * a.KA4;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int i = threadIdx.x + q * 256;
+      if (i < nx) {
+        const int ss = i / D;
+        cur[ss * a.KA4 + (i - ss * D)] = xr[q];
+      }
+    }
+    load_x(t - 1);                                            // the next step's inputs are in flight during this one
+    __syncthreads();
+    float z[4] = {bg[0], bg[1], bg[2], bg[3]};
+    const float* xh = cur + s * a.KA4;
+    for (int kk = 0; kk < a.KA4; kk += 4) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(xh + kk);
+#pragma unroll
+      for (int gt = 0; gt < 4; ++gt) {
+        const f32x4 w = *reinterpret_cast<const f32x4*>(wl + (gt * a.Hp + u) * a.wstride + kk);
+        z[gt] = fmaf(v.x, w.x, fmaf(v.y, w.y, fmaf(v.z, w.z, fmaf(v.w, w.w, z[gt]))));
+      }
+    }
+    const float ig = rec_act(z[0], a.act), fg = rec_act(z[1], a.act), og = rec_act(z[3], a.act);
+    c = fg * c + ig * tanhf(z[2]);
+    h = og * tanhf(c);
+    float* nxt = st + (buf ^ 1) * a.seqs * a.KA4;
+    if (u < H) nxt[s * a.KA4 + D + u] = h;
+    if (stash && live) {
+      float* sp = stash + ((long)b * a.T + t) * 6 * H;
+#pragma unroll
+      for (int gt = 0; gt < 4; ++gt) sp[gt * H + u] = z[gt];
+      sp[4 * H + u] = h;
+      sp[5 * H + u] = c;
+    }
+    buf ^= 1;
+  }
+  if (live) h_out[(long)b * h_ld + u] = h;
+}
+
+// thread (s, u): dz of its four gates, then dh_prev[s, u] = dz[s, :] . W_h[u, :] and dx[s, t, kk] = dz[s, :] . W_x[kk, :] for
+// kk = u, u + Hp, ...  LDS: Wx [D][4H + 4], Wh [H][4H + 4], dz [seqs][4H + 4], dh [2][seqs][Hp]
+__global__ __launch_bounds__(256) void lstm_bwd_kernel(LstmArgs a, const float* __restrict__ dh_in, long dh_ld,
+                                                       float* __restrict__ stash, float* __restrict__ dx) {
+  extern __shared__ float lds[];
+  const int H = a.H, D = a.D, N4 = 4 * H, ws = 4 * H + 4;
+  float* wx = lds;
+  float* wh = wx + D * ws;
+  float* dzl = wh + H * ws;
+  float* dhl = dzl + a.seqs * ws;
+  for (int i = threadIdx.x; i < D * ws; i += blockDim.x) {
+    const int r = i / ws, n = i - r * ws;
+    wx[i] = n < N4 ? a.wx[(long)r * N4 + n] : 0.f;
+  }
+  for (int i = threadIdx.x; i < H * ws; i += blockDim.x) {
+    const int r = i / ws, n = i - r * ws;
+    wh[i] = n < N4 ? a.wh[(long)r * N4 + n] : 0.f;
+  }
+  const int s = threadIdx.x / a.Hp, u = threadIdx.x - s * a.Hp;
+  const int b = blockIdx.x * a.seqs + s;
+  const bool live = u < H && b < a.B;
+  for (int i = threadIdx.x; i < 2 * a.seqs * a.Hp; i += blockDim.x) dhl[i] = 0.f;
+  __syncthreads();
+  if (live && dh_in) dhl[s * a.Hp + u] = dh_in[(long)b * dh_ld + u];
+  float dc = 0.f;
+  int buf = 0;
+  for (int t = 0; t < a.T; ++t) {                            // reverse of the processing order
+    __syncthreads();                                          // dh of this step is complete; dz of the last step is read
+    float dz[4] = {0.f, 0.f, 0.f, 0.f};
+    if (live) {
+      float* sp = stash + ((long)b * a.T + t) * 6 * H;
+      const float zi = sp[u], zf = sp[H + u], zg = sp[2 * H + u], zo = sp[3 * H + u];
+      const float ct = sp[5 * H + u];
+      const float cp = t + 1 < a.T ? sp[6 * H + 5 * H + u] : 0.f;   // the state before this step: after input t + 1
+      const float dh = dhl[buf * a.seqs * a.Hp + s * a.Hp + u];
+      const float ig = rec_act(zi, a.act), fg = rec_act(zf, a.act), og = rec_act(zo, a.act), gg = tanhf(zg);
+      const float tc = tanhf(ct);
+      dc = dc + dh * og * (1.f - tc * tc);
+      dz[0] = dc * gg * rec_act_grad(zi, ig, a.act);
+      dz[1] = dc * cp * rec_act_grad(zf, fg, a.act);
+      dz[2] = dc * ig * (1.f - gg * gg);
+      dz[3] = dh * tc * rec_act_grad(zo, og, a.act);
+      dc = dc * fg;
+#pragma unroll
+      for (int gt = 0; gt < 4; ++gt) sp[gt * H + u] = dz[gt];          // z -> dz (read by the weight-gradient kernel)
+    }
+    if (u < H) {
+#pragma unroll
+      for (int gt = 0; gt < 4; ++gt) dzl[s * ws + gt * H + u] = dz[gt];
+    }
+    __syncthreads();
+    const float* dzs = dzl + s * ws;
+    if (u < H) {
+      const float* wr = wh + u * ws;
+      float acc = 0.f;
+      for (int n = 0; n < N4; n += 4) {
+        const f32x4 g4 = *reinterpret_cast<const f32x4*>(dzs + n);
+        const f32x4 w4 = *reinterpret_cast<const f32x4*>(wr + n);
+        acc = fmaf(g4.x, w4.x, fmaf(g4.y, w4.y, fmaf(g4.z, w4.z, fmaf(g4.w, w4.w, acc))));
+      }
+      dhl[(buf ^ 1) * a.seqs * a.Hp + s * a.Hp + u] = acc;
+    }
+    if (b < a.B) {
+      for (int kk = u; kk < D; kk += a.Hp) {
+        const float* wr = wx + kk * ws;
+        float acc = 0.f;
+        for (int n = 0; n < N4; n += 4) {
+          const f32x4 g4 = *reinterpret_cast<const f32x4*>(dzs + n);
+          const f32x4 w4 = *reinterpret_cast<const f32x4*>(wr + n);
+          acc = fmaf(g4.x, w4.x, fmaf(g4.y, w4.y, fmaf(g4.z, w4.z, fmaf(g4.w, w4.w, acc))));
+        }
+        if (dx) dx[((long)b * a.T + t) * D + kk] = acc;
+      }
+    }
+    buf ^= 1;
+  }
+}
+
+// rows r = (b, t) of chunk blockIdx.x; column n = threadIdx.x (< 4H); k tile blockIdx.y of a_r = [x_r (D) | h_prev (H) | 1]
+constexpr int kWgRows = 32, kWgK = 16;
+__global__ __launch_bounds__(256) void lstm_wgrad_kernel(LstmArgs a, const float* __restrict__ stash, long rows, long rows_per_chunk,
+                                                         float* __restrict__ part_x, float* __restrict__ part_h,
+                                                         float* __restrict__ part_b) {
+  __shared__ __attribute__((aligned(16))) float as[kWgRows][kWgK];
+  __shared__ float dzs[kWgRows][256];
+  const int H = a.H, D = a.D, N4 = 4 * H, KA = D + H + 1;
+  const int n = threadIdx.x, k0 = blockIdx.y * kWgK;
+  const long r0 = (long)blockIdx.x * rows_per_chunk;
+  const long r1 = r0 + rows_per_chunk < rows ? r0 + rows_per_chunk : rows;
+  float acc[kWgK];
+#pragma unroll
+  for (int q = 0; q < kWgK; ++q) acc[q] = 0.f;
+  for (long rb = r0; rb < r1; rb += kWgRows) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < kWgRows * kWgK; i += blockDim.x) {
+      const int rr = i / kWgK, kq = i - rr * kWgK, kk = k0 + kq;
+      const long r = rb + rr;
+      float v = 0.f;
+      if (r < r1) {
+        const long bb = r / a.T;
+        const int t = (int)(r - bb * a.T);
+        if (kk < D) v = a.x[r * D + kk];
+        else if (kk < D + H) v = t + 1 < a.T ? stash[(r + 1) * 6 * H + 4 * H + (kk - D)] : 0.f;
+        else if (kk == D + H) v = 1.f;
+      }
+      as[rr][kq] = v;
+    }
+    for (int i = threadIdx.x; i < kWgRows * N4; i += blockDim.x) {
+      const int rr = i / N4, nn = i - rr * N4;
+      const long r = rb + rr;
+      dzs[rr][nn] = r < r1 ? stash[r * 6 * H + nn] : 0.f;
+    }
+    __syncthreads();
+    if (n < N4) {
+      for (int rr = 0; rr < kWgRows; ++rr) {
+        const float g = dzs[rr][n];
+#pragma unroll
+        for (int q = 0; q < kWgK; q += 4) {
+          const f32x4 v = *reinterpret_cast<const f32x4*>(&as[rr][q]);
+          acc[q] = fmaf(v.x, g, acc[q]);
+          acc[q + 1] = fmaf(v.y, g, acc[q + 1]);
+          acc[q + 2] = fmaf(v.z, g, acc[q + 2]);
+          acc[q + 3] = fmaf(v.w, g, acc[q + 3]);
+        }
+      }
+    }
+  }
+  if (n < N4) {
+#pragma unroll
+    for (int q = 0; q < kWgK; ++q) {
+      const int kk = k0 + q;
+      if (kk < D) part_x[(long)blockIdx.x * D * N4 + (long)kk * N4 + n] = acc[q];
+      else if (kk < D + H) part_h[(long)blockIdx.x * H * N4 + (long)(kk - D) * N4 + n] = acc[q];
+      else if (kk == D + H) part_b[(long)blockIdx.x * N4 + n] = acc[q];
+    }
+  }
+  (void)KA;
+}
+
+int lstm_args(const float* x, int32_t B, int32_t T, int32_t D, const float* wx, const float* wh, const float* bias, int32_t H,
+              int32_t act, const char* who, LstmArgs& a) {
+  if (B < 0 || T < 0 || T > KGCN_SEQ_MAX_LENGTH) return fail("%s: %d steps outside 0..%d", who, T, KGCN_SEQ_MAX_LENGTH);
+  if (D < 1 || D > KGCN_SEQ_MAX_LSTM_INPUT) return fail("%s: input width %d outside 1..%d", who, D, KGCN_SEQ_MAX_LSTM_INPUT);
+  if (H < 1 || H > KGCN_SEQ_MAX_UNITS) return fail("%s: %d units outside 1..%d", who, H, KGCN_SEQ_MAX_UNITS);
+  if (act != KGCN_SEQ_ACT_HARD_SIGMOID && act != KGCN_SEQ_ACT_SIGMOID) return fail("%s: recurrent activation %d", who, act);
+  if ((int64_t)B * T * 6 * H >= (int64_t)INT32_MAX * 8) return fail("%s: batch x steps too large", who);
+  if (B > 0 && (!wx || !wh || !bias || (T > 0 && !x))) return fail("%s: NULL operand", who);
+  a.x = x; a.wx = wx; a.wh = wh; a.bias = bias;
+  a.B = B; a.T = T; a.D = D; a.H = H; a.act = act;
+  a.Hp = H <= 16 ? 16 : (H <= 32 ? 32 : 64);
+  a.seqs = 256 / a.Hp;
+  a.KA4 = round4(D + H);
+  a.wstride = ((a.KA4 / 4) & 1) ? a.KA4 : a.KA4 + 4;
+  return 0;
+}
+
+long wgrad_rows_per_chunk(const LstmArgs& a) {
+  const long rows = (long)a.B * a.T;
+  long per = (rows + kLstmChunks - 1) / kLstmChunks;
+  return per < 1 ? 1 : per;
+}
+}  // namespace
+}  // namespace kgcn
+
+using namespace kgcn;
+
+extern "C" int64_t kgcn_seq_convpool_workspace_bytes(int32_t batch, int32_t length, int32_t symbols, int32_t embed_dim,
+                                                     int32_t kernel_size, int32_t filters, int32_t pool) {
+  ConvArgs a;
+  if (conv_args(nullptr, 0, length, nullptr, symbols, embed_dim, nullptr, kernel_size, filters, pool, "workspace", a)) return -1;
+  a.tiles = (long)(batch > 0 ? batch : 0) * ((a.T + kTile - 1) / kTile);
+  const long grid = convpool_bwd_grid(a);
+  return (int64_t)grid * ((long)kernel_size * embed_dim * filters + filters + (long)symbols * embed_dim) * 4;
+}
+
+extern "C" int kgcn_seq_convpool_fwd_f32(const int32_t* tokens, int32_t batch, int32_t length, const float* table, int32_t symbols,
+                                         int32_t embed_dim, const float* w, const float* bias, int32_t kernel_size, int32_t filters,
+                                         int32_t pool, float* out, uint8_t* argmax, void* stream) {
+  const char* who = "kgcn_seq_convpool_fwd_f32";
+  ConvArgs a;
+  if (int rc = conv_args(tokens, batch, length, table, symbols, embed_dim, w, kernel_size, filters, pool, who, a)) return rc;
+  if (a.tiles == 0) return 0;
+  if (!bias || !out) return fail("%s: NULL operand", who);
+  const size_t lds = convpool_fwd_lds(a);
+  if (int rc = allow_lds<convpool_fwd_kernel>(lds)) return rc;
+  const int grid = (int)(a.tiles < kConvGridFwd ? a.tiles : kConvGridFwd);
+  hipLaunchKernelGGL(convpool_fwd_kernel, dim3(grid), dim3(256), lds, as_stream(stream), a, bias, out, argmax);
+  return check_launch("convpool_fwd_kernel");
+}
+
+extern "C" int kgcn_seq_convpool_bwd_f32(const int32_t* tokens, int32_t batch, int32_t length, const float* table, int32_t symbols,
+                                         int32_t embed_dim, const float* w, int32_t kernel_size, int32_t filters, int32_t pool,
+                                         const float* dout, const uint8_t* argmax, float* dtable, float* dw, float* dbias,
+                                         void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* who = "kgcn_seq_convpool_bwd_f32";
+  ConvArgs a;
+  if (int rc = conv_args(tokens, batch, length, table, symbols, embed_dim, w, kernel_size, filters, pool, who, a)) return rc;
+  if (!dtable || !dw || !dbias) return fail("%s: NULL gradient", who);
+  if (a.tiles > 0 && (!dout || !argmax)) return fail("%s: NULL operand", who);
+  const int64_t need = kgcn_seq_convpool_workspace_bytes(batch, length, symbols, embed_dim, kernel_size, filters, pool);
+  if (!workspace || workspace_bytes < need)
+    return fail("%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes, (long long)need);
+  hipStream_t s = as_stream(stream);
+  const int grid = convpool_bwd_grid(a);
+  float* part_w = static_cast<float*>(workspace);
+  float* part_b = part_w + (size_t)grid * kernel_size * embed_dim * filters;
+  float* part_t = part_b + (size_t)grid * filters;
+  if (a.tiles == 0) {                                 // no pooled output: zero gradients (the partials are zeroed and reduced)
+    if (hipMemsetAsync(workspace, 0, need, s) != hipSuccess) return fail("%s: memset failed", who);
+  } else {
+    const bool in_lds = convpool_bwd_lds(a, true) <= (size_t)kLdsBytes;
+    const size_t lds = convpool_bwd_lds(a, in_lds);
+    if (in_lds) {
+      if (int rc = allow_lds<convpool_bwd_kernel<true>>(lds)) return rc;
+      hipLaunchKernelGGL(convpool_bwd_kernel<true>, dim3(grid), dim3(256), lds, s, a, dout, argmax, part_w, part_b, part_t);
+    } else {
+      if (int rc = allow_lds<convpool_bwd_kernel<false>>(lds)) return rc;
+      hipLaunchKernelGGL(convpool_bwd_kernel<false>, dim3(grid), dim3(256), lds, s, a, dout, argmax, part_w, part_b, part_t);
+    }
+    if (int rc = check_launch("convpool_bwd_kernel")) return rc;
+  }
+  if (int rc = reduce_or_defer(part_w, grid, (long)kernel_size * embed_dim * filters, dw, s)) return rc;
+  if (int rc = reduce_or_defer(part_b, grid, filters, dbias, s)) return rc;
+  return reduce_or_defer(part_t, grid, (long)symbols * embed_dim, dtable, s);
+}
+
+extern "C" int64_t kgcn_seq_lstm_stash_floats(int32_t batch, int32_t steps, int32_t units) {
+  return (int64_t)batch * steps * 6 * units;
+}
+
+extern "C" int64_t kgcn_seq_lstm_workspace_bytes(int32_t batch, int32_t steps, int32_t in_dim, int32_t units) {
+  (void)batch; (void)steps;
+  return (int64_t)kLstmChunks * ((int64_t)in_dim + units + 1) * 4 * units * 4;
+}
+
+extern "C" int kgcn_seq_lstm_fwd_f32(const float* x, int32_t batch, int32_t steps, int32_t in_dim, const float* wx, const float* wh,
+                                     const float* bias, int32_t units, int32_t recurrent_act, float* h_out, int64_t h_ld,
+                                     float* stash, void* stream) {
+  const char* who = "kgcn_seq_lstm_fwd_f32";
+  LstmArgs a;
+  if (int rc = lstm_args(x, batch, steps, in_dim, wx, wh, bias, units, recurrent_act, who, a)) return rc;
+  if (batch == 0) return 0;
+  if (!h_out || h_ld < units) return fail("%s: output NULL or its row stride %lld < %d", who, (long long)h_ld, units);
+  const size_t lds = ((size_t)4 * a.Hp * a.wstride + 2 * (size_t)a.seqs * a.KA4) * 4;
+  if (int rc = allow_lds<lstm_fwd_kernel>(lds)) return rc;
+  hipLaunchKernelGGL(lstm_fwd_kernel, dim3((batch + a.seqs - 1) / a.seqs), dim3(256), lds, as_stream(stream), a, h_out, (long)h_ld,
+                     stash);
+  return check_launch("lstm_fwd_kernel");
+}
+
+extern "C" int kgcn_seq_lstm_bwd_f32(const float* x, int32_t batch, int32_t steps, int32_t in_dim, const float* wx, const float* wh,
+                                     const float* bias, int32_t units, int32_t recurrent_act, const float* dh, int64_t dh_ld,
+                                     float* stash, float* dx, float* dwx, float* dwh, float* dbias, void* workspace,
+                                     int64_t workspace_bytes, void* stream) {
+  const char* who = "kgcn_seq_lstm_bwd_f32";
+  LstmArgs a;
+  if (int rc = lstm_args(x, batch, steps, in_dim, wx, wh, bias, units, recurrent_act, who, a)) return rc;
+  if (dh && dh_ld < units) return fail("%s: gradient row stride %lld < %d", who, (long long)dh_ld, units);
+  if (batch > 0 && steps > 0 && !stash) return fail("%s: NULL stash", who);
+  hipStream_t s = as_stream(stream);
+  const int N4 = 4 * units;
+  if (batch > 0 && steps > 0) {
+    const size_t lds = ((size_t)(in_dim + units + a.seqs) * (N4 + 4) + 2 * (size_t)a.seqs * a.Hp) * 4;
+    if (int rc = allow_lds<lstm_bwd_kernel>(lds)) return rc;
+    hipLaunchKernelGGL(lstm_bwd_kernel, dim3((batch + a.seqs - 1) / a.seqs), dim3(256), lds, s, a, dh, (long)dh_ld, stash, dx);
+    if (int rc = check_launch("lstm_bwd_kernel")) return rc;
+  }
+  if (!dwx && !dwh && !dbias) return 0;
+  if (!dwx || !dwh || !dbias) return fail("%s: d W_x, d W_h and d bias are formed together", who);
+  const int64_t need = kgcn_seq_lstm_workspace_bytes(batch, steps, in_dim, units);
+  if (!workspace || workspace_bytes < need)
+    return fail("%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes, (long long)need);
+  float* part_x = static_cast<float*>(workspace);
+  float* part_h = part_x + (size_t)kLstmChunks * in_dim * N4;
+  float* part_b = part_h + (size_t)kLstmChunks * units * N4;
+  const long rows = (long)batch * steps;
+  if (rows == 0) {
+    if (hipMemsetAsync(workspace, 0, need, s) != hipSuccess) return fail("%s: memset failed", who);
+  } else {
+    const long per = wgrad_rows_per_chunk(a);
+    const int ktiles = (in_dim + units + 1 + kWgK - 1) / kWgK;
+    hipLaunchKernelGGL(lstm_wgrad_kernel, dim3(kLstmChunks, ktiles), dim3(N4 <= 64 ? 64 : (N4 <= 128 ? 128 : 256)), 0, s, a, stash,
+                       rows, per, part_x, part_h, part_b);
+    if (int rc = check_launch("lstm_wgrad_kernel")) return rc;
+  }
+  if (int rc = reduce_or_defer(part_x, kLstmChunks, (long)in_dim * N4, dwx, s)) return rc;
+  if (int rc = reduce_or_defer(part_h, kLstmChunks, (long)units * N4, dwh, s)) return rc;
+  return reduce_or_defer(part_b, kLstmChunks, N4, dbias, s);
+}
+
+// d x[b, n, :] = g[b * g_ld + :d] -- the gradient of a GraphGather read-out that was written into a column block of a wider
+// buffer (model_multimodal.py:96 tf.concat), read where it lies
+__global__ void gather_bwd_ld_kernel(const float* __restrict__ g, long g_ld, long B, int N, int d, float* __restrict__ dx) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * N * d) return;
+  const long b = i / ((long)N * d);
+  const int c = (int)(i % d);
+  dx[i] = g[b * g_ld + c];
+}
+
+extern "C" int kgcn_graph_gather_bwd_ld_f32(const float* dout_grad, int64_t dout_ld, int64_t batch, int32_t n_nodes, int32_t d,
+                                            float* dx, void* stream) {
+  if (batch < 0 || n_nodes < 0 || d < 1 || dout_ld < d) return fail("kgcn_graph_gather_bwd_ld_f32: bad sizes");
+  const long n = (long)batch * n_nodes * d;
+  if (n == 0) return 0;
+  if (!dout_grad || !dx) return fail("kgcn_graph_gather_bwd_ld_f32: NULL operand");
+  hipLaunchKernelGGL(gather_bwd_ld_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), dout_grad, (long)dout_ld,
+                     (long)batch, n_nodes, d, dx);
+  return check_launch("gather_bwd_ld_kernel");
+}

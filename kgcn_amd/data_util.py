@@ -213,6 +213,27 @@ def batch_features(features, batch_idx, batch_size=None, device="cuda"):
     return torch.from_numpy(out).to(device)
 
 
+def sequence_table(data, device="cuda"):
+    """kgcn/data_util.py:442-446, 496-498 for the multimodal model: the .jbl dict's `sequence` [G, L] token array and
+    `sequence_symbol_num` S -> (int32 [G, L] device tensor, S).  Every token must lie in [0, S) and the shape within the sequence
+    kernels' limits (S <= 1024, L <= 8192): checked here, on the host, once -- the kernels read tokens unchecked.  Short
+    batches get zero rows for their dummy graphs from StaticBatch.add_table (kgcn/feed.py:178-181)."""
+    import torch
+    from .ops import seq_limits_check
+    if "sequence" not in data or "sequence_symbol_num" not in data:
+        raise ValueError("the dataset has no `sequence` / `sequence_symbol_num` (a multimodal .jbl carries both)")
+    seq = np.asarray(data["sequence"])
+    S = int(np.asarray(data["sequence_symbol_num"]).reshape(()))
+    if seq.ndim != 2 or seq.shape[1] < 1:
+        raise ValueError("sequence must be a [graphs, length] array, got shape %s" % (seq.shape,))
+    if not np.issubdtype(seq.dtype, np.integer):
+        raise ValueError("sequence tokens must be integers, got %s" % seq.dtype)
+    seq_limits_check(length=seq.shape[1], symbols=S)
+    if seq.size and (seq.min() < 0 or seq.max() >= S):
+        raise ValueError("sequence tokens must lie in [0, %d): found %d .. %d" % (S, int(seq.min()), int(seq.max())))
+    return torch.from_numpy(np.ascontiguousarray(seq, dtype=np.int32)).to(device), S
+
+
 class DeviceGraphDataset:
     """The whole dataset resident in HBM: every adjacency channel as ONE batched-CSR
     container over all G graphs (plus, built lazily, its transpose and the row-padded copies the fused

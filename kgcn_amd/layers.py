@@ -633,3 +633,52 @@ __all__ = ["GraphConv", "GraphDense", "GINAggregate", "GraphGather", "GraphMaxPo
            "GraphBatchNormalization", "set_learning_phase", "learning_phase", "GAT", "GraphDecoderInnerProd",
            "GraphDecoderDistMult", "DistMult", "BatchGraphConv", "load_bspmm",
            "BatchedAdjacency", "fused_stack"]
+
+
+def _orthogonal(shape, generator=None):
+    """Keras' Orthogonal initializer (gain 1) on the host: QR of a normal [max, min] matrix, columns signed by diag(R),
+    transposed when the kernel has fewer rows than columns (the LSTM recurrent kernel [H, 4H])."""
+    import numpy as np
+    rows, cols = int(shape[0]), int(shape[1])
+    a = torch.randn((max(rows, cols), min(rows, cols)), generator=generator, dtype=torch.float64).numpy()
+    q, r = np.linalg.qr(a)
+    q = q * np.sign(np.diag(r))
+    if rows < cols:
+        q = q.T
+    return torch.as_tensor(np.ascontiguousarray(q.reshape(rows, cols)), dtype=torch.float32)
+
+
+class SequenceEncoder(nn.Module):
+    """The sequence branch of example_model/model_multimodal.py:70-93 with Keras' parameter names and initialisers:
+      Embedding(symbols, embedding_dim)            embeddings [S, E], U(-0.05, 0.05); mask_zero off (symbol 0 is a trained row)
+      Conv1D(filters, kernel_size, 'same', relu)   conv_kernel [k, E, F] glorot-uniform (fans k E, k F), conv_bias zeros
+      MaxPooling1D(pool)                           stride pool, valid: L // pool steps
+      LSTM(units, go_backwards=True)               kernel [F, 4H] glorot-uniform, recurrent_kernel [H, 4H] orthogonal (built on
+                                                   the host), bias zeros with the forget slice ones (unit_forget_bias)
+    forward(tokens [B, L] int32, out=None, out_col=0) -> h after input step 0 [B, H] (into columns out_col.. of `out` if given).
+    Two launches forward (ops.seq_conv_pool, ops.seq_lstm), csrc/seq.hip."""
+
+    def __init__(self, symbols, embedding_dim, filters=50, kernel_size=4, pool=4, units=32, recurrent_activation="hard_sigmoid"):
+        super().__init__()
+        ops.seq_limits_check(symbols=symbols, embed_dim=embedding_dim, kernel_size=kernel_size, filters=filters, pool=pool,
+                             units=units, in_dim=filters)
+        if recurrent_activation not in ops.RECURRENT_ACTIVATIONS:
+            raise ValueError("recurrent_activation must be one of %s" % sorted(ops.RECURRENT_ACTIVATIONS))
+        self.symbols, self.embedding_dim, self.filters = int(symbols), int(embedding_dim), int(filters)
+        self.kernel_size, self.pool, self.units = int(kernel_size), int(pool), int(units)
+        self.recurrent_activation = recurrent_activation
+        S, E, F, k, H = self.symbols, self.embedding_dim, self.filters, self.kernel_size, self.units
+        self.embeddings = nn.Parameter(torch.empty(S, E).uniform_(-0.05, 0.05))
+        lim = math.sqrt(6.0 / (k * E + k * F))
+        self.conv_kernel = nn.Parameter(torch.empty(k, E, F).uniform_(-lim, lim))
+        self.conv_bias = nn.Parameter(torch.zeros(F))
+        lim = math.sqrt(6.0 / (F + 4 * H))
+        self.kernel = nn.Parameter(torch.empty(F, 4 * H).uniform_(-lim, lim))
+        self.recurrent_kernel = nn.Parameter(_orthogonal((H, 4 * H)))
+        bias = torch.zeros(4 * H)
+        bias[H:2 * H] = 1.0
+        self.bias = nn.Parameter(bias)
+
+    def forward(self, tokens, out=None, out_col=0):
+        pooled = ops.seq_conv_pool(tokens, self.embeddings, self.conv_kernel, self.conv_bias, self.pool)
+        return ops.seq_lstm(pooled, self.kernel, self.recurrent_kernel, self.bias, self.recurrent_activation, out=out, out_col=out_col)

@@ -12,6 +12,10 @@ between layer and activation it is one HIP elementwise kernel (ops.activation). 
                   GraphDense 50, Gather, Dense(label_dim); masked (weighted) sigmoid cross entropy
   SparseGCN    -- example_model/sparse.py:45-134  block-diagonal batch of one: 3 x [GraphConv(256) relu],
                   GraphDense(256), BN, relu, per-molecule sum, tanh, Dense(num_classes); summed sparse softmax CE
+  GraphVAE     -- example_model/model_vae.py:63-253  GraphConv/BN encoder, reparameterisation, node and DistMult link
+                  decoders; fused reconstruction loss (csrc/vae.hip)
+  MultimodalGCN -- example_model/model_multimodal.py:53-118  GraphConv(50), GraphDense(50), Gather | Embedding, Conv1D(50, 4),
+                  MaxPooling1D(4), LSTM(32, go_backwards) (csrc/seq.hip); concat, Dense(52) relu, Dense(label_dim)
 
 Keras learning-phase semantics (quirk Q6): the reference calls BatchNormalization / Dropout
 without `training=`; under TF1 graph mode that is inference behaviour -- BN normalises with its
@@ -385,3 +389,49 @@ class GraphVAE(nn.Module):
         _, _, xf, ys, ws = self._encode_decode(features, adjs, enabled_node_nums, eps)
         adj = torch.stack([ops.gram(y, w) for y, w in zip(ys, ws)], dim=1)
         return ops.activation(xf, "sigmoid"), ops.activation(adj, "sigmoid")
+
+
+class MultimodalGCN(nn.Module):
+    """example_model/model_multimodal.py:53-118 (example_config/multimodal.json, the compound-protein interaction model), call by call:
+      graph branch (:60-66)    GraphConv(50, C) sigmoid, GraphDense(50) sigmoid, GraphGather -> [B, 50] (the file's
+                               graph_output_layer_dim = 32 is unused)
+      sequence branch (:70-93) layers.SequenceEncoder: Embedding(S, E), Conv1D(50, 4, same, relu), MaxPooling1D(4),
+                               LSTM(32, go_backwards=True) -> [B, 32]
+      shared part (:98-105)    concat([sequence, graph]) -> Dense(52) relu -> Dense(label_dim); loss masked_softmax_ce.
+    The activations ride in the epilogues of the producing kernels; the concatenation is one [B, 82] buffer whose columns 0-31
+    the LSTM kernel writes and 32-81 the graph read-out (ops.join_columns), so nothing is copied.
+    forward(features, adjs, sequences=None, enabled_node_nums=None) -> logits; `sequences` is the int32 [B, L] token batch
+    (data_util.sequence_table; GraphedTrainStep passes it as a forward kwarg).  enabled_node_nums is accepted and unused, as in
+    the file (every node row, padding included, reaches the read-out)."""
+
+    GRAPH_WIDTH, SEQ_WIDTH, HIDDEN = 50, 32, 52
+
+    def __init__(self, sequence_symbol_num, embedding_dim=4, adj_channel_num=1, label_dim=2, recurrent_activation="hard_sigmoid"):
+        super().__init__()
+        self.conv = layers.GraphConv(self.GRAPH_WIDTH, adj_channel_num, activation="sigmoid")     # :60-61
+        self.dense = layers.GraphDense(self.GRAPH_WIDTH, activation="sigmoid")                    # :62-63
+        self.sequence = layers.SequenceEncoder(sequence_symbol_num, embedding_dim, filters=50, kernel_size=4, pool=4,
+                                               units=self.SEQ_WIDTH, recurrent_activation=recurrent_activation)   # :73-91
+        self.hidden = KerasDense(self.HIDDEN)                                                     # :101-103
+        self.out = KerasDense(int(label_dim))                                                     # :104
+
+    def forward(self, features, adjs, sequences=None, enabled_node_nums=None):
+        if sequences is None:
+            raise ValueError("MultimodalGCN needs the sequences= token batch")
+        adj = layers._pack(adjs, features)
+        B = features.shape[0]
+        if sequences.shape[0] != B:
+            raise ValueError("%d sequences for %d graphs" % (sequences.shape[0], B))
+        joined = features.new_empty((B, self.SEQ_WIDTH + self.GRAPH_WIDTH))
+        seq = self.sequence(sequences, out=joined, out_col=0)
+        node = self.dense(self.conv(features, adj=adj))
+        graph = ops.graph_gather_into(node, joined, self.SEQ_WIDTH)
+        layer = ops.join_columns(joined, [seq, graph])                                            # :96 tf.concat
+        self.hidden.build(layer.shape[1], layer.device)
+        layer = ops.dense(layer, self.hidden.kernel, self.hidden.bias, activation="relu")
+        return self.out(layer)
+
+    @staticmethod
+    def loss(logits, labels, mask):
+        """model_multimodal.py:108-113 -> (cost_opt, cost_sum); correct_count (:115-118) is read off the logits by the caller."""
+        return masked_softmax_ce(logits, labels, mask)

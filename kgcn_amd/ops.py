@@ -1976,3 +1976,187 @@ def vae_recon(adj, ys, ws, feat_logits, feat_target, mask=None, kl=None):
     if len(ys) != len(ws) or not ys:
         raise _lib.KgcnHipError("vae_recon: one decoder output and one DistMult kernel per channel")
     return _VaeRecon.apply(adj, mask, feat_target, kl, feat_logits, *ys, *ws)
+
+
+# -------------------------------------------------------------------------------------------------
+# multimodal sequence encoder (example_model/model_multimodal.py:70-93; csrc/seq.hip): fused embedding + Conv1D + relu +
+# MaxPooling1D, and the go_backwards LSTM
+# -------------------------------------------------------------------------------------------------
+SEQ_MAX_EMBED, SEQ_MAX_FILTERS, SEQ_MAX_KERNEL, SEQ_MAX_POOL = 32, 64, 8, 8
+SEQ_MAX_UNITS, SEQ_MAX_LSTM_INPUT, SEQ_MAX_SYMBOLS, SEQ_MAX_LENGTH = 64, 64, 1024, 8192
+RECURRENT_ACTIVATIONS = {"hard_sigmoid": 0, "sigmoid": 1}
+
+
+def seq_limits_check(length=None, symbols=None, embed_dim=None, kernel_size=None, filters=None, pool=None, units=None,
+                     in_dim=None):
+    """Raise KgcnHipError for a sequence-encoder shape beyond the kernels' limits (include/kgcn_hip.h); None = not checked."""
+    for name, v, hi in (("length", length, SEQ_MAX_LENGTH), ("symbols", symbols, SEQ_MAX_SYMBOLS),
+                        ("embedding width", embed_dim, SEQ_MAX_EMBED), ("kernel size", kernel_size, SEQ_MAX_KERNEL),
+                        ("filters", filters, SEQ_MAX_FILTERS), ("pool size", pool, SEQ_MAX_POOL), ("units", units, SEQ_MAX_UNITS),
+                        ("LSTM input width", in_dim, SEQ_MAX_LSTM_INPUT)):
+        if v is not None and not 1 <= int(v) <= hi:
+            raise _lib.KgcnHipError("sequence encoder: %s %d outside 1..%d" % (name, int(v), hi))
+
+
+class _SeqConvPool(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, tokens, table, w, bias, pool):
+        if not (torch.is_tensor(tokens) and tokens.is_cuda and tokens.dtype == torch.int32 and tokens.dim() == 2):
+            raise _lib.KgcnHipError("tokens must be an int32 [batch, length] device tensor")
+        tokens = tokens.contiguous()
+        table, w, b = _f32c(table, "embedding table"), _f32c(w, "conv kernel"), _f32c(bias, "conv bias").reshape(-1)
+        B, L = tokens.shape
+        S, E = table.shape
+        k, F = w.shape[0], w.shape[2]
+        if w.dim() != 3 or w.shape[1] != E or b.numel() != F:
+            raise _lib.KgcnHipError("conv kernel %s / bias %s do not match an embedding width of %d" % (tuple(w.shape), tuple(b.shape), E))
+        seq_limits_check(L, S, E, k, F, pool)
+        T = L // pool
+        out = torch.empty((B, T, F), device=table.device, dtype=torch.float32)
+        train = any(ctx.needs_input_grad[1:4])
+        arg = torch.empty((B, T, F), device=table.device, dtype=torch.uint8) if train else None
+        check(lib.kgcn_seq_convpool_fwd_f32(ptr(tokens), B, L, ptr(table), S, E, ptr(w), ptr(b), k, F, int(pool), ptr(out), ptr(arg),
+                                            current_stream()), "kgcn_seq_convpool_fwd_f32")
+        if train:
+            ctx.save_for_backward(tokens, table, w, arg)
+            ctx.pool, ctx.bias_shape = int(pool), tuple(bias.shape)
+            ctx.defer_ok = all(t.is_leaf for t in (table, w, bias))
+            ctx.defer_ids = (table, w, bias)
+            _count_use(table, w, bias)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None or not any(ctx.needs_input_grad[1:4]):
+            return None, None, None, None, None
+        tokens, table, w, arg = ctx.saved_tensors
+        B, L = tokens.shape
+        S, E = table.shape
+        k, F = w.shape[0], w.shape[2]
+        g = _f32c(g, "grad")
+        dtable, dw = torch.empty_like(table), torch.empty_like(w)
+        db = torch.empty((F,), device=w.device, dtype=torch.float32)
+        wsb = lib.kgcn_seq_convpool_workspace_bytes(B, L, S, E, k, F, ctx.pool)
+        wsp = torch.empty((max(wsb, 4) // 4,), device=w.device, dtype=torch.float32)
+        with _no_deferral_unless(ctx.defer_ok and _single_use(*ctx.defer_ids)):
+            check(lib.kgcn_seq_convpool_bwd_f32(ptr(tokens), B, L, ptr(table), S, E, ptr(w), k, F, ctx.pool, ptr(g), ptr(arg), ptr(dtable),
+                                                ptr(dw), ptr(db), ptr(wsp), wsb, current_stream()), "kgcn_seq_convpool_bwd_f32")
+        _keep_until_flush(wsp)
+        n = ctx.needs_input_grad
+        return None, dtable if n[1] else None, dw if n[2] else None, db.view(ctx.bias_shape) if n[3] else None, None
+
+
+def seq_conv_pool(tokens, table, w, bias, pool):
+    """Embedding(table) -> Conv1D(w [k, E, F], bias, padding='same', relu) -> MaxPooling1D(pool) of model_multimodal.py:75-85 in one
+    pass: tokens [B, L] int32 (in [0, S): validated when the dataset is loaded, data_util.sequence_table) -> [B, L // pool, F].
+    The backward routes the gradient to the lowest-index maximum of each window (a byte per output, written only when a
+    gradient is needed) and forms d table / d w / d bias in deferrable fixed-order partials."""
+    return _SeqConvPool.apply(tokens, table, w, bias, int(pool))
+
+
+class _SeqLSTM(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, wx, wh, bias, act, out, out_col):
+        x, wx, wh = _f32c(x, "LSTM input"), _f32c(wx, "LSTM kernel"), _f32c(wh, "LSTM recurrent kernel")
+        b = _f32c(bias, "LSTM bias").reshape(-1)
+        B, T, D = x.shape
+        H = wh.shape[0]
+        if tuple(wx.shape) != (D, 4 * H) or tuple(wh.shape) != (H, 4 * H) or b.numel() != 4 * H:
+            raise _lib.KgcnHipError("LSTM weights %s / %s / %s do not match input width %d" % (tuple(wx.shape), tuple(wh.shape),
+                                                                                            tuple(b.shape), D))
+        seq_limits_check(length=max(T, 1), units=H, in_dim=D)
+        if out is None:
+            out = torch.empty((B, H), device=x.device, dtype=torch.float32)
+            out_col = 0
+        elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != B or not out.is_contiguous() or \
+                out_col < 0 or out_col + H > out.shape[1]:
+            raise _lib.KgcnHipError("output buffer %s does not take [%d, %d] at column %d" % (tuple(out.shape), B, H, out_col))
+        h = out[:, out_col:out_col + H]
+        train = any(ctx.needs_input_grad[:4])
+        stash = torch.empty((max(lib.kgcn_seq_lstm_stash_floats(B, T, H), 1),), device=x.device, dtype=torch.float32) if train else None
+        check(lib.kgcn_seq_lstm_fwd_f32(ptr(x), B, T, D, ptr(wx), ptr(wh), ptr(b), H, act, h.data_ptr(), out.shape[1], ptr(stash),
+                                        current_stream()), "kgcn_seq_lstm_fwd_f32")
+        if train:
+            ctx.save_for_backward(x, wx, wh, b, stash)
+            ctx.act, ctx.bias_shape, ctx.used = act, tuple(bias.shape), False
+            ctx.defer_ok = all(t.is_leaf for t in (wx, wh, bias))
+            ctx.defer_ids = (wx, wh, bias)
+            _count_use(wx, wh, bias)
+        ctx.set_materialize_grads(False)
+        return h
+
+    @staticmethod
+    def backward(ctx, g):
+        n = ctx.needs_input_grad
+        if g is None or not any(n[:4]):
+            return (None,) * 7
+        if ctx.used:
+            raise _lib.KgcnHipError("seq_lstm: the backward consumes its stash and runs once per forward")
+        ctx.used = True
+        x, wx, wh, b, stash = ctx.saved_tensors
+        B, T, D = x.shape
+        H = wh.shape[0]
+        if g.dtype != torch.float32 or g.stride(1) != 1 or g.stride(0) < H:
+            g = _f32c(g, "grad")
+        dx = torch.empty_like(x) if n[0] else None
+        need_w = any(n[1:4])
+        dwx = torch.empty_like(wx) if need_w else None
+        dwh = torch.empty_like(wh) if need_w else None
+        db = torch.empty((4 * H,), device=x.device, dtype=torch.float32) if need_w else None
+        wsb = lib.kgcn_seq_lstm_workspace_bytes(B, T, D, H) if need_w else 0
+        wsp = torch.empty((max(wsb, 4) // 4,), device=x.device, dtype=torch.float32) if need_w else None
+        with _no_deferral_unless(ctx.defer_ok and _single_use(*ctx.defer_ids)):
+            check(lib.kgcn_seq_lstm_bwd_f32(ptr(x), B, T, D, ptr(wx), ptr(wh), ptr(b), H, ctx.act, g.data_ptr(), g.stride(0), ptr(stash),
+                                            ptr(dx), ptr(dwx), ptr(dwh), ptr(db), ptr(wsp), wsb, current_stream()), "kgcn_seq_lstm_bwd_f32")
+        if need_w:
+            _keep_until_flush(wsp)
+        return (dx, dwx if n[1] else None, dwh if n[2] else None, db.view(ctx.bias_shape) if n[3] else None, None, None, None)
+
+
+def seq_lstm(x, wx, wh, bias, recurrent_activation="hard_sigmoid", out=None, out_col=0):
+    """K.layers.LSTM(H, return_sequences=False, go_backwards=True) of model_multimodal.py:88-91 (Keras v1 cell, gates i, f, c, o):
+    x [B, T, D], kernel wx [D, 4H], recurrent kernel wh [H, 4H], bias [4H] -> h after input step 0 [B, H].  out / out_col: h is
+    written into columns out_col .. out_col + H of the contiguous [B, wide] buffer `out` (a column block of a concatenation,
+    join_columns) and returned as that view.  Training keeps a stash of 6H floats per sequence step (gate pre-activations, h, c);
+    the backward consumes it (one backward per forward)."""
+    try:
+        act = RECURRENT_ACTIVATIONS[recurrent_activation]
+    except KeyError:
+        raise _lib.KgcnHipError("recurrent_activation must be one of %s" % sorted(RECURRENT_ACTIVATIONS)) from None
+    return _SeqLSTM.apply(x, wx, wh, bias, act, out, int(out_col))
+
+
+class _GatherInto(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, join, join_col):
+        y = _f32c(y, "inputs")
+        T, N, d = y.shape
+        if join.dtype != torch.float32 or join.dim() != 2 or join.shape[0] != T or not join.is_contiguous() or \
+                join_col < 0 or join_col + d > join.shape[1]:
+            raise _lib.KgcnHipError("join buffer %s does not take a [%d, %d] read-out at column %d" % (tuple(join.shape), T, d, join_col))
+        pooled = join[:, join_col:join_col + d]
+        check(lib.kgcn_graph_gather_fwd_ld_f32(ptr(y), T, N, d, pooled.data_ptr(), join.shape[1], current_stream()),
+              "kgcn_graph_gather_fwd_ld_f32")
+        ctx.shape = (T, N, d)
+        ctx.set_materialize_grads(False)
+        return pooled
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None
+        T, N, d = ctx.shape
+        if g.dtype != torch.float32 or g.stride(1) != 1 or g.stride(0) < d:
+            g = _f32c(g, "grad")
+        dx = torch.empty(ctx.shape, device=g.device, dtype=torch.float32)
+        check(lib.kgcn_graph_gather_bwd_ld_f32(g.data_ptr(), g.stride(0), T, N, d, ptr(dx), current_stream()),
+              "kgcn_graph_gather_bwd_ld_f32")
+        return dx, None, None
+
+
+def graph_gather_into(y, join, join_col):
+    """GraphGather (sum over nodes) of y [T, N, d] written into columns join_col .. join_col + d of the [T, wide] buffer `join`
+    (combine the blocks with join_columns); the backward reads the gradient's column block where it lies, whatever its row
+    stride (dense_gather(join=) needs a multiple of 4)."""
+    return _GatherInto.apply(y, join, int(join_col))
