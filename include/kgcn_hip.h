@@ -70,7 +70,9 @@ extern "C" {
  * kgcn_vae_recon_bwd_f32.
  * The multimodal sequence encoder added entry points only (version still 2): kgcn_seq_convpool_fwd_f32 /
  * kgcn_seq_convpool_bwd_f32 (+ kgcn_seq_convpool_workspace_bytes), kgcn_seq_lstm_fwd_f32 / kgcn_seq_lstm_bwd_f32
- * (+ kgcn_seq_lstm_stash_floats, kgcn_seq_lstm_workspace_bytes), kgcn_graph_gather_bwd_ld_f32. */
+ * (+ kgcn_seq_lstm_stash_floats, kgcn_seq_lstm_workspace_bytes), kgcn_graph_gather_bwd_ld_f32.
+ * Knowledge-graph link prediction added entry points only (version still 2): kgcn_linkpred_fwd_f32 / kgcn_linkpred_bwd_f32
+ * (+ kgcn_linkpred_workspace_bytes). */
 #define KGCN_HIP_ABI_VERSION 2
 
 /* Column index of the padding entries of a row-padded batch (see row_pad): they carry value 0 and
@@ -795,6 +797,38 @@ int kgcn_seq_lstm_bwd_f32(const float* x, int32_t batch, int32_t steps, int32_t 
  * (kgcn_graph_gather_fwd_ld_f32), read where it lies */
 int kgcn_graph_gather_bwd_ld_f32(const float* dout_grad, int64_t dout_ld, int64_t batch, int32_t n_nodes, int32_t d, float* dx,
                                  void* stream);
+
+/* -- knowledge-graph link prediction (sample_kg/network_prediction/model_py/{gcn,distmult,ip}.py) ---------------------------
+ * h [N, D] node rows, labels [M, 6] int32 (i, r, j, i', r', j'), perm [M] (NULL = identity), negatives [K] (the sorted node set
+ * of columns 0 and 2 of the fed list, kgcn/feed.py:8-16).  All node and relation ids must lie in [0, N) / [0, R): checked by the
+ * caller on the host, not here.
+ * Forward (one label batch of L rows): window j = *step mod floor(M / L) (step NULL = 0; read on the device), row i =
+ * labels[perm[j L + i]] with col 3 := col 0 and col 5 := negatives[u], u uniform in [0, K) without bias from Philox4x64-10,
+ * key (seed, 0), counter (i, *step, round, 0), words in order, Lemire's multiply-shift with rejection of the low halves below
+ * 2^64 mod K.  Writes rows [L, 6], s1 [L] = sum_d h[c0] h[c2] w[c1], s2 [L] = sum_d h[c3] h[c5] w[c4] (w = 1 unless DISTMULT),
+ * sums [5] = cost_opt, cost_sum, correct_count, S1, S2:
+ *   KGCN_LP_GCN       cost_i = -log(sigmoid(s1 - s2) + 1e-10), cost_opt = mean, correct = sum [s1 > s2]
+ *   KGCN_LP_DISTMULT  cost_i = -log(1 / (1 + exp(s2 - s1 + 0.1)) + 1e-10)
+ *   KGCN_LP_IP        one cost on S1 = sum_i s1_i, S2 = sum_i s2_i (cost_opt = cost_sum = cost, correct = [S1 > S2]); S1, S2 kept
+ * Where exp(s2 - s1 + 0.1) overflows, the gradient is 0 (TF: NaN).  Backward: g_opt / g_sum (device scalars, NULL = 0) ->
+ * dh [N, D] (every row written) and, for DISTMULT, dw [R, D] through per-workgroup partials in `workspace`
+ * (>= kgcn_linkpred_workspace_bytes) and a fixed-order second stage (deferrable: kgcn_reduce_defer).  No float atomics:
+ * results are bitwise reproducible.  Limits: D <= 256, L <= 2^22, R D <= 16384. */
+#define KGCN_LP_GCN 0
+#define KGCN_LP_DISTMULT 1
+#define KGCN_LP_IP 2
+#define KGCN_LP_MAX_DIM 256
+#define KGCN_LP_MAX_BATCH (1 << 22)
+#define KGCN_LP_MAX_REL_FLOATS 16384
+int64_t kgcn_linkpred_workspace_bytes(int64_t nodes, int32_t dim, int32_t relations, int32_t mode, int32_t batch);
+int kgcn_linkpred_fwd_f32(const float* h, int64_t nodes, int32_t dim, const float* w, int32_t relations, int32_t mode,
+                          const int32_t* labels, const int32_t* perm, int64_t num_labels, int32_t batch, const int32_t* negatives,
+                          int32_t num_negatives, uint64_t seed, const int64_t* step, int32_t* rows, float* s1, float* s2,
+                          float* sums, void* stream);
+int kgcn_linkpred_bwd_f32(const float* h, int64_t nodes, int32_t dim, const float* w, int32_t relations, int32_t mode,
+                          const int32_t* rows, const float* s1, const float* s2, const float* sums, int32_t batch,
+                          const float* g_opt, const float* g_sum, float* dh, float* dw, void* workspace, int64_t workspace_bytes,
+                          void* stream);
 
 #ifdef __cplusplus
 }

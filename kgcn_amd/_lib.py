@@ -283,6 +283,12 @@ SIGNATURES = {
                                              ctypes.c_void_p]),
     "kgcn_seq_lstm_bwd_f32": (ctypes.c_int, [c_f32p, c_i32, c_i32, c_i32, c_f32p, c_f32p, c_f32p, c_i32, c_i32, c_f32p, c_i64, c_f32p,
                                              c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
+    # knowledge-graph link prediction (csrc/linkpred.hip)
+    "kgcn_linkpred_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32, c_i32]),
+    "kgcn_linkpred_fwd_f32": (ctypes.c_int, [c_f32p, c_i64, c_i32, c_f32p, c_i32, c_i32, c_i32p, c_i32p, c_i64, c_i32, c_i32p, c_i32,
+                                             ctypes.c_uint64, ctypes.c_void_p, c_i32p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p]),
+    "kgcn_linkpred_bwd_f32": (ctypes.c_int, [c_f32p, c_i64, c_i32, c_f32p, c_i32, c_i32, c_i32p, c_f32p, c_f32p, c_f32p, c_i32,
+                                             c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
     "kgcn_graph_gather_bwd_ld_f32": (ctypes.c_int, [c_f32p, c_i64, c_i64, c_i32, c_i32, c_f32p, ctypes.c_void_p]),
     "kgcn_graph_gather_bwd_add_f32": (ctypes.c_int, [c_f32p, c_f32p, c_i64, c_i32, c_i32, c_f32p, ctypes.c_void_p]),
     "kgcn_dot_workspace_bytes": (c_i64, [c_i64]),

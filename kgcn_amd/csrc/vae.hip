@@ -16,32 +16,12 @@
 // One workgroup owns one graph at a time and keeps Y_c and the N x N label / gradient matrix in LDS; L is evaluated in
 // 4 x 4 register tiles of the upper triangle only (L is symmetric), in fp32 with fused multiply-adds.
 #include "kgcn_common.h"
+#include "philox.h"
 
 namespace kgcn {
 int reduce_or_defer(const float* part, int nparts, long n, float* out, hipStream_t s);
 
 namespace {
-constexpr uint64_t kPhiloxM0 = 0xD2E7470EE14C6C93ull, kPhiloxM1 = 0xCA5A826395121157ull;
-constexpr uint64_t kPhiloxW0 = 0x9E3779B97F4A7C15ull, kPhiloxW1 = 0xBB67AE8584CAA73Bull;
-
-struct Philox4 { uint64_t v[4]; };
-
-__device__ __forceinline__ Philox4 philox4x64_10(uint64_t c0, uint64_t c1, uint64_t seed) {
-  uint64_t x0 = c0, x1 = c1, x2 = 0, x3 = 0, k0 = seed, k1 = 0;
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t lo0 = kPhiloxM0 * x0, hi0 = __umul64hi(kPhiloxM0, x0);
-    const uint64_t lo1 = kPhiloxM1 * x2, hi1 = __umul64hi(kPhiloxM1, x2);
-    x0 = hi1 ^ x1 ^ k0;
-    x1 = lo1;
-    x2 = hi0 ^ x3 ^ k1;
-    x3 = lo0;
-    k0 += kPhiloxW0;
-    k1 += kPhiloxW1;
-  }
-  return Philox4{{x0, x1, x2, x3}};
-}
-
 // two 64-bit words -> two N(0, 1): u1 = (top 24 bits + 1) 2^-24 in (0, 1], u2 = top 24 bits 2^-24 in [0, 1)
 __device__ __forceinline__ void box_muller(uint64_t w0, uint64_t w1, float& n0, float& n1) {
   const float u1 = (float)((w0 >> 40) + 1) * 0x1p-24f;

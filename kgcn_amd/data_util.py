@@ -514,3 +514,90 @@ def block_diagonal_batch(size, adj_row, adj_column, adj_values, adj_elem_len, ad
     segments = BatchedCSR.from_arrays(zeros(total), np.repeat(np.arange(nmol, dtype=np.int64), size), node,
                                       np.ones(total, np.float32), 1, nmol, total, device=device)
     return BlockDiagonalBatch(adjacency, torch.from_numpy(net).to(device), size, segments)
+
+
+# ---- knowledge-graph link prediction (sample_kg/network_prediction) ---------------------------------------------------------
+class LinkPredictionData:
+    """The .jbl dict script/preprocessing_link_pred.py writes: `adj` (one COO graph with self loops, directed as written), `node`
+    [1, N] (must be 0 .. N-1: the embedding table is then the first layer's input as it is), `node_num`, `label_list` [1, M, 6]
+    and `test_label_list` [1, M', 6] of (i, r, j, i', r', j') rows.  Every node id must lie in [0, N) and every relation id be
+    >= 0: checked here, once -- the kernels read them unchecked.  num_relations = max relation id + 1 over both lists (the
+    DistMult table is sized by it; the reference's [adj_channel_num, D] = [1, D] table is gathered out of range by relation
+    ids 2 and 0)."""
+
+    def __init__(self, data):
+        N = int(np.asarray(data["node_num"]).reshape(()))
+        node = np.asarray(data["node"])
+        if node.size != N or not np.array_equal(node.reshape(-1), np.arange(N)):
+            raise ValueError("link prediction needs node = 0 .. node_num-1 (what preprocessing_link_pred.py writes); "
+                             "a general node gather is not supported")
+        self.num_nodes = N
+        self.channels, _ = build_adjs({"adj": data["adj"], "max_node_num": N})
+        lists = []
+        for key in ("label_list", "test_label_list"):
+            a = np.asarray(data[key])
+            if a.ndim != 3 or a.shape[0] != 1 or a.shape[2] != 6 or not np.issubdtype(a.dtype, np.integer):
+                raise ValueError("%s must be an integer [1, M, 6] array, got %s %s" % (key, a.shape, a.dtype))
+            a = a[0].astype(np.int64)
+            nodes, rels = a[:, [0, 2, 3, 5]], a[:, [1, 4]]
+            if a.size and (nodes.min() < 0 or nodes.max() >= N or rels.min() < 0):
+                raise ValueError("%s: node ids must lie in [0, %d) and relation ids be >= 0" % (key, N))
+            lists.append(a.astype(np.int32))
+        self.label_list, self.test_label_list = lists
+        self.num_relations = int(max(np.max(x[:, [1, 4]]) if x.size else 0 for x in lists)) + 1
+
+    def adjacency(self, device="cuda"):
+        """The graph as a one-graph BatchedAdjacency (what GraphConv takes)."""
+        return batch_adjacency(self.channels, [0], 1, device)
+
+
+def split_label_list(label_list, valid_data_rate=0.2, rng=np.random):
+    """kgcn/data_util.py:661-695: shuffle the row ids with rng.shuffle, the last int(n rate) of them are the validation rows
+    -> (train [n - v, 6], valid [v, 6])."""
+    n = len(label_list)
+    valid_num = int(n * valid_data_rate)
+    nid = np.array(list(range(n)))
+    rng.shuffle(nid)
+    return label_list[nid[:n - valid_num]], label_list[nid[n - valid_num:]]
+
+
+def all_label(label_list):
+    """kgcn/feed.py:8-16: the sorted set of the nodes in columns 0 and 2 (the negative table)."""
+    return np.unique(np.concatenate([label_list[:, 0], label_list[:, 2]])).astype(np.int32)
+
+
+class LinkPredFeed:
+    """The device-resident feed of one label list (kgcn/feed.py:34-59 with label_batch_size): the list [M, 6], the row
+    permutation of the epoch (identity until shuffle()) and the negative table all_label -- what ops.linkpred_loss reads.
+    shuffle(rng) restates shuffle_label_list (kgcn/data_util.py:647-649) as a new permutation, uploaded once per epoch into the
+    same buffer (a captured step keeps reading it).  batch = label_batch_size (None: the whole list, one window, as the
+    reference's validation feed); steps_per_epoch = floor(M / batch) (kgcn/core.py:220-222).  `features` / `adjacency` are
+    what train.GraphedTrainStep hands the model: None (with_feature: false) and the graph (gcn) or None."""
+
+    def __init__(self, label_list, batch=None, adjacency=None, device="cuda"):
+        import torch
+        lab = np.ascontiguousarray(label_list, np.int32)
+        if lab.ndim != 2 or lab.shape[1] != 6 or lab.shape[0] < 1:
+            raise ValueError("label list must be a non-empty [M, 6] array")
+        self.num_labels = lab.shape[0]
+        self.batch = self.num_labels if batch is None else int(batch)
+        if not 1 <= self.batch <= self.num_labels:
+            raise ValueError("label batch %d for %d rows" % (self.batch, self.num_labels))
+        self.steps_per_epoch = self.num_labels // self.batch
+        if lab.min() < 0:
+            raise ValueError("label list ids must be >= 0")
+        self.max_node = int(lab[:, [0, 2, 3, 5]].max())           # checked against the node rows by ops.linkpred_loss
+        self.max_relation = int(lab[:, [1, 4]].max())
+        self.label_list = lab
+        self.labels = torch.from_numpy(lab).to(device)
+        self.perm = torch.arange(self.num_labels, dtype=torch.int32, device=device)
+        self._perm_host = np.arange(self.num_labels, dtype=np.int32)
+        self.negatives = torch.from_numpy(all_label(lab)).to(device)
+        self.features, self.adjacency = None, adjacency
+
+    def shuffle(self, rng=np.random):
+        """The epoch's row order: rng.shuffle of the current order (the reference shuffles the list in place each epoch)."""
+        import torch
+        rng.shuffle(self._perm_host)
+        self.perm.copy_(torch.from_numpy(self._perm_host))
+        return self._perm_host

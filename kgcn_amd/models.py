@@ -435,3 +435,76 @@ class MultimodalGCN(nn.Module):
     def loss(logits, labels, mask):
         """model_multimodal.py:108-113 -> (cost_opt, cost_sum); correct_count (:115-118) is read off the logits by the caller."""
         return masked_softmax_ce(logits, labels, mask)
+
+
+class LinkPredictionNet(nn.Module):
+    """sample_kg/network_prediction/model_py/{gcn,distmult,ip}.py (config/config_*.json: with_feature false, with_node_embedding
+    true, embedding_dim 128), call by call:
+      embedding    K.layers.Embedding(N, 128) of nodes = 0 .. N-1: the table itself is the input, U(-0.05, 0.05) (Keras 'uniform')
+      gcn (:41-46) GraphConv(128) relu, GraphConv(128) relu on the one graph (relu in the aggregation epilogue)
+      distmult     kgcn.layers.DistMult relation vectors, glorot, one per relation id: [num_relations, 128] (the file builds
+                   adj_channel_num = 1 rows and gathers ids 2 and 0 from it, out of range; sized by the largest id here)
+      loss         ops.linkpred_loss (csrc/linkpred.hip): the four gathers, s1 / s2, the ranking cost and its metrics.
+    forward(features, adjs, feed=None) -> cost_opt; cost_sum, correct_count, s1, s2 and the assembled rows of the same call are
+    left in .cost_sum / .correct_count / .s1 / .s2 / .rows (detached), so loss(out, labels, mask) -> (cost_opt, cost_sum) lets
+    train.GraphedTrainStep train it unchanged (feed= as a forward kwarg; features is unused).  bind_step(optimizer._t_dev)
+    makes the label window and the negatives of step t a function of (seed, t), read on the device."""
+
+    VARIANTS = ("gcn", "distmult", "ip")
+
+    def __init__(self, variant, num_nodes, num_relations=1, embedding_dim=128, seed=0, device=None):
+        super().__init__()
+        if variant not in self.VARIANTS:
+            raise ValueError("variant must be one of %s (model_py/gin.py is not supported)" % (self.VARIANTS,))
+        self.variant, self.num_nodes, self.seed = variant, int(num_nodes), int(seed)
+        self.step = None
+        self.embedding = nn.Parameter(layers._init_tensor((self.num_nodes, int(embedding_dim)), "random_uniform", device))
+        if variant == "gcn":
+            self.conv1 = layers.GraphConv(128, 1, activation="relu")          # gcn.py:41-42
+            self.conv2 = layers.GraphConv(128, 1, activation="relu")          # gcn.py:44-45
+        self.distmult = None
+        if variant == "distmult":
+            self.distmult = layers.DistMult(adj_channel_num=int(num_relations))    # distmult.py:42
+            self.distmult.build((1, self.num_nodes, int(embedding_dim)), device)
+        self.cost_sum = self.correct_count = self.s1 = self.s2 = self.rows = None
+
+    def bind_step(self, step):
+        """step: a one-element int64 device tensor (TFAdam._t_dev) the feed kernel reads at run time; None: step 0."""
+        self.step = step
+        return self
+
+    def node_rows(self, adjs=None):
+        """The model's `prediction` [N, D]: the embedding table (distmult, ip) or the two GraphConv layers over it (gcn)."""
+        if self.variant != "gcn":
+            return self.embedding
+        if adjs is None:
+            raise ValueError("the gcn variant needs the graph (adjs)")
+        x = self.embedding.view(1, self.num_nodes, -1)
+        x = self.conv2(self.conv1(x, adj=adjs), adj=adjs)
+        return x.view(self.num_nodes, -1)
+
+    def forward(self, features, adjs, feed=None, seed=None, step=None):
+        if feed is None:
+            raise ValueError("LinkPredictionNet needs the feed= label list (data_util.LinkPredFeed)")
+        h = self.node_rows(adjs)
+        w = self.distmult.w[0] if self.distmult is not None else None
+        cost_opt, cost_sum, correct, s1, s2, rows = ops.linkpred_loss(h, feed, self.variant, w=w,
+                                                                      seed=self.seed if seed is None else seed,
+                                                                      step=self.step if step is None else step)
+        self.cost_sum, self.correct_count, self.s1, self.s2, self.rows = cost_sum.detach(), correct, s1, s2, rows
+        return cost_opt
+
+    def loss(self, out, labels=None, mask=None):
+        """loss_fn for train.train_step / GraphedTrainStep: (cost_opt, cost_sum) of the forward call that produced `out`."""
+        return out, self.cost_sum
+
+    @torch.no_grad()
+    def predict(self, adjs=None):
+        """(lp_prediction, prediction): H H^T [1, N, N] (gcn, ip) or the DistMult layer's [1, R, N, N] = H diag(w_r) H^T, and the
+        node rows H [N, D] (the reference's model.out) -- on the dense GEMM (ops.dense), H^T and H diag(w_r) formed once."""
+        h = self.node_rows(adjs).contiguous()
+        ht = h.t().contiguous()
+        if self.distmult is None:
+            return ops.dense(h, ht).unsqueeze(0), h
+        w = self.distmult.w[0]
+        return torch.stack([ops.dense(h * w[r], ht) for r in range(w.shape[0])]).unsqueeze(0), h

@@ -2160,3 +2160,95 @@ def graph_gather_into(y, join, join_col):
     (combine the blocks with join_columns); the backward reads the gradient's column block where it lies, whatever its row
     stride (dense_gather(join=) needs a multiple of 4)."""
     return _GatherInto.apply(y, join, int(join_col))
+
+
+# -------------------------------------------------------------------------------------------------
+# knowledge-graph link prediction (sample_kg/network_prediction/model_py/{gcn,distmult,ip}.py; csrc/linkpred.hip): label-batch
+# assembly with the negative draw, the pairwise ranking loss, and its atomic-free gradient
+# -------------------------------------------------------------------------------------------------
+LINKPRED_MODES = {"gcn": 0, "distmult": 1, "ip": 2}
+LINKPRED_MAX_DIM, LINKPRED_MAX_BATCH, LINKPRED_MAX_REL_FLOATS = 256, 1 << 22, 16384
+
+
+class _LinkPredLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, labels, perm, negatives, batch, mode, seed, step, h, w):
+        h = _f32c(h, "node rows")
+        N, D = h.shape
+        wc = _f32c(w, "relation vectors") if w is not None else None
+        R = wc.shape[0] if wc is not None else 0
+        L = int(batch)
+        rows = torch.empty((L, 6), device=h.device, dtype=torch.int32)
+        s1 = torch.empty((L,), device=h.device, dtype=torch.float32)
+        s2 = torch.empty((L,), device=h.device, dtype=torch.float32)
+        sums = torch.empty((5,), device=h.device, dtype=torch.float32)
+        check(lib.kgcn_linkpred_fwd_f32(ptr(h), N, D, ptr(wc), R, mode, ptr(labels), ptr(perm), labels.shape[0], L, ptr(negatives),
+                                        negatives.shape[0], int(seed) & (2 ** 64 - 1), ptr(step), ptr(rows), ptr(s1), ptr(s2),
+                                        ptr(sums), current_stream()), "kgcn_linkpred_fwd_f32")
+        ctx.mode, ctx.L, ctx.has_w = mode, L, wc is not None
+        ctx.defer_ok = w is not None and w.is_leaf
+        ctx.defer_ids = (w,) if w is not None else ()
+        if w is not None:
+            _count_use(w)
+        ctx.save_for_backward(h, wc if wc is not None else h.new_empty(0), rows, s1, s2, sums)
+        correct = sums[2]
+        ctx.mark_non_differentiable(correct, s1, s2, rows)
+        ctx.set_materialize_grads(False)
+        return sums[0], sums[1], correct, s1, s2, rows
+
+    @staticmethod
+    def backward(ctx, g_opt, g_sum, _g_count, _g_s1, _g_s2, _g_rows):
+        h, wc, rows, s1, s2, sums = ctx.saved_tensors
+        N, D = h.shape
+        if g_opt is None and g_sum is None:
+            return (None,) * 9
+        go = None if g_opt is None else _f32c(g_opt.reshape(1), "grad")
+        gs = None if g_sum is None else _f32c(g_sum.reshape(1), "grad")
+        R = wc.shape[0] if ctx.has_w else 0
+        dh = torch.empty_like(h)
+        dw = torch.empty_like(wc) if ctx.has_w else None
+        wsb = lib.kgcn_linkpred_workspace_bytes(N, D, R, ctx.mode, ctx.L)
+        wsp = torch.empty((max(wsb, 4) // 4,), device=h.device, dtype=torch.float32)
+        with _no_deferral_unless(ctx.defer_ok and _single_use(*ctx.defer_ids)):
+            check(lib.kgcn_linkpred_bwd_f32(ptr(h), N, D, ptr(wc) if ctx.has_w else None, R, ctx.mode, ptr(rows), ptr(s1), ptr(s2),
+                                            ptr(sums), ctx.L, ptr(go), ptr(gs), ptr(dh), ptr(dw), ptr(wsp), wsb, current_stream()),
+                  "kgcn_linkpred_bwd_f32")
+        _keep_until_flush(wsp)
+        return None, None, None, None, None, None, None, dh, dw
+
+
+def linkpred_loss(h, feed, mode, w=None, seed=0, step=None, batch=None, labels=None, perm=None, negatives=None):
+    """model_py/{gcn,distmult,ip}.py from the gathers to the metrics -> (cost_opt, cost_sum, correct_count, s1 [L], s2 [L],
+    rows [L, 6] int32).  h [N, D] the node rows (the embedding table, or the GraphConv output), w [R, D] the DistMult relation
+    vectors (mode 'distmult' only).  The batch comes from `feed` (data_util.LinkPredFeed: the device-resident label list, the row
+    permutation of the epoch and the negative table; keyword overrides for tests): window (*step mod floor(M / L)) of the
+    permuted list, col 3 := col 0, col 5 := a negative drawn on the device from (seed, *step, row).  rows are the assembled batch;
+    for 'ip' s1 / s2 are the per-row terms of the batch-wide sums the cost is taken on (ip.py:46-47).  Differentiable in h and w
+    through cost_opt and cost_sum; correct_count, s1, s2 and rows are metrics."""
+    if mode not in LINKPRED_MODES:
+        raise _lib.KgcnHipError("linkpred_loss: mode must be one of %s" % sorted(LINKPRED_MODES))
+    code = LINKPRED_MODES[mode]
+    if h.dim() != 2 or not 1 <= h.shape[1] <= LINKPRED_MAX_DIM:
+        raise _lib.KgcnHipError("linkpred_loss: node rows must be [N, D <= %d], got %s" % (LINKPRED_MAX_DIM, tuple(h.shape)))
+    if (mode == "distmult") != (w is not None):
+        raise _lib.KgcnHipError("linkpred_loss: relation vectors are required by 'distmult' and only by it")
+    if w is not None and (w.dim() != 2 or w.shape[1] != h.shape[1] or w.numel() > LINKPRED_MAX_REL_FLOATS):
+        raise _lib.KgcnHipError("linkpred_loss: relation vectors must be [R, %d] with R D <= %d" % (h.shape[1], LINKPRED_MAX_REL_FLOATS))
+    if labels is None:
+        # the kernels read the ids unchecked: the feed's host-side bounds against these node rows / relation vectors
+        if feed.max_node >= h.shape[0] or (w is not None and feed.max_relation >= w.shape[0]):
+            raise _lib.KgcnHipError("linkpred_loss: the label list names node %d / relation %d, beyond %d node rows / %s relations"
+                                    % (feed.max_node, feed.max_relation, h.shape[0], "-" if w is None else w.shape[0]))
+    labels = feed.labels if labels is None else labels
+    perm = (feed.perm if feed is not None else None) if perm is None else perm
+    negatives = feed.negatives if negatives is None else negatives
+    batch = feed.batch if batch is None else int(batch)
+    for t, name in ((labels, "label list"), (negatives, "negative table")) + (((perm, "permutation"),) if perm is not None else ()):
+        require_gpu(t, name)
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise _lib.KgcnHipError("linkpred_loss: the %s must be a contiguous int32 device tensor" % name)
+    if labels.dim() != 2 or labels.shape[1] != 6 or not 1 <= batch <= min(labels.shape[0], LINKPRED_MAX_BATCH):
+        raise _lib.KgcnHipError("linkpred_loss: label list %s cannot feed batches of %d rows" % (tuple(labels.shape), batch))
+    if perm is not None and perm.shape != (labels.shape[0],):
+        raise _lib.KgcnHipError("linkpred_loss: the permutation must have one entry per label row")
+    return _LinkPredLoss.apply(labels, perm, negatives, batch, code, seed, _step_ptr(step), h, w)
