@@ -72,7 +72,9 @@ extern "C" {
  * kgcn_seq_convpool_bwd_f32 (+ kgcn_seq_convpool_workspace_bytes), kgcn_seq_lstm_fwd_f32 / kgcn_seq_lstm_bwd_f32
  * (+ kgcn_seq_lstm_stash_floats, kgcn_seq_lstm_workspace_bytes), kgcn_graph_gather_bwd_ld_f32.
  * Knowledge-graph link prediction added entry points only (version still 2): kgcn_linkpred_fwd_f32 / kgcn_linkpred_bwd_f32
- * (+ kgcn_linkpred_workspace_bytes). */
+ * (+ kgcn_linkpred_workspace_bytes).
+ * Integrated gradients of the multimodal model added entry points only (version still 2): kgcn_seq_convpool_scaled_fwd_f32,
+ * kgcn_seq_convpool_input_grad_f32. */
 #define KGCN_HIP_ABI_VERSION 2
 
 /* Column index of the padding entries of a row-padded batch (see row_pad): they carry value 0 and
@@ -793,6 +795,22 @@ int kgcn_seq_lstm_fwd_f32(const float* x, int32_t batch, int32_t steps, int32_t 
 int kgcn_seq_lstm_bwd_f32(const float* x, int32_t batch, int32_t steps, int32_t in_dim, const float* wx, const float* wh,
                           const float* bias, int32_t units, int32_t recurrent_act, const float* dh, int64_t dh_ld, float* stash,
                           float* dx, float* dwx, float* dwh, float* dbias, void* workspace, int64_t workspace_bytes, void* stream);
+/* Integrated gradients over the embedded sequence (kgcn/visualization.py:187-231, the model built with feed_embedded_layer).
+ * `batch` rows are rep copies of each of the batch / rep token rows (batch a multiple of rep).  Scaled forward: row b reads token
+ * row b / rep and its embedding rows times scale[b] (the scaled [B, L, E] input is never written), otherwise exactly
+ * kgcn_seq_convpool_fwd_f32 (out and argmax [batch, L / p, F]).  Input gradient: d out [batch, L / p, F] routed through argmax ->
+ * dx [batch / rep, L, E] = sum over the copies r of compound c, in copy order, of row_weight[c rep + r] (NULL = 1; rows of weight 0
+ * are skipped) times the gradient with respect to that row's scaled embedded input,
+ *   sum_j sum_f dconv[m + (k-1)/2 - j, f] w[j, e, f]   (positions outside [0, (L / p) p) carry no conv gradient),
+ * times table[tokens[c, m], e] when times_table is non-zero.  No weight gradient, no float atomics (bitwise reproducible).
+ * Limits as the conv-pool above; a shape beyond them fails before any launch. */
+int kgcn_seq_convpool_scaled_fwd_f32(const int32_t* tokens, int32_t batch, int32_t rep, const float* scale, int32_t length,
+                                     const float* table, int32_t symbols, int32_t embed_dim, const float* w, const float* bias,
+                                     int32_t kernel_size, int32_t filters, int32_t pool, float* out, uint8_t* argmax, void* stream);
+int kgcn_seq_convpool_input_grad_f32(const int32_t* tokens, int32_t batch, int32_t rep, int32_t length, const float* table,
+                                     int32_t symbols, int32_t embed_dim, const float* w, int32_t kernel_size, int32_t filters,
+                                     int32_t pool, const float* dout, const uint8_t* argmax, const float* row_weight,
+                                     int32_t times_table, float* dx, void* stream);
 /* dx[b, n, :] = dout[b * dout_ld + :d]: the gradient of a GraphGather read-out written into a column block of a wider buffer
  * (kgcn_graph_gather_fwd_ld_f32), read where it lies */
 int kgcn_graph_gather_bwd_ld_f32(const float* dout_grad, int64_t dout_ld, int64_t batch, int32_t n_nodes, int32_t d, float* dx,

@@ -277,6 +277,11 @@ SIGNATURES = {
     "kgcn_seq_convpool_bwd_f32": (ctypes.c_int, [ctypes.c_void_p, c_i32, c_i32, c_f32p, c_i32, c_i32, c_f32p, c_i32, c_i32, c_i32,
                                                  c_f32p, ctypes.c_void_p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p, c_i64,
                                                  ctypes.c_void_p]),
+    "kgcn_seq_convpool_scaled_fwd_f32": (ctypes.c_int, [ctypes.c_void_p, c_i32, c_i32, c_f32p, c_i32, c_f32p, c_i32, c_i32, c_f32p,
+                                                        c_f32p, c_i32, c_i32, c_i32, c_f32p, ctypes.c_void_p, ctypes.c_void_p]),
+    "kgcn_seq_convpool_input_grad_f32": (ctypes.c_int, [ctypes.c_void_p, c_i32, c_i32, c_i32, c_f32p, c_i32, c_i32, c_f32p, c_i32,
+                                                        c_i32, c_i32, c_f32p, ctypes.c_void_p, c_f32p, c_i32, c_f32p,
+                                                        ctypes.c_void_p]),
     "kgcn_seq_lstm_stash_floats": (c_i64, [c_i32, c_i32, c_i32]),
     "kgcn_seq_lstm_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i32]),
     "kgcn_seq_lstm_fwd_f32": (ctypes.c_int, [c_f32p, c_i32, c_i32, c_i32, c_f32p, c_f32p, c_f32p, c_i32, c_i32, c_f32p, c_i64, c_f32p,

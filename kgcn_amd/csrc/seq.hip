@@ -15,6 +15,11 @@
 //              writes the BPTT stash: z (the 4H pre-activations), h and c of every step, 6H floats per sequence and step.
 //              The backward walks the steps in reverse processing order, writes dX and overwrites z with dz; a third kernel
 //              forms d W_x, d W_h, d bias from [x_t | h_prev | 1]^T dz in per-workgroup partials (fixed-order second stage).
+//   IG         integrated gradients of the multimodal model (kgcn/visualization.py:187-231 with the embedded sequence fed in):
+//              the scaled forward is the conv-pool with batch row b reading token row b / rep and its embedding rows times
+//              scale[b]; the input gradient routes d pooled through the arg-max bytes and forms the gradient with respect to the
+//              scaled embedded input, summed over the rep copies of every compound with per-row weights, optionally times the
+//              embedding row (the attribution itself).  It forms no weight gradient.
 // Every second stage is a parameter gradient and goes through reduce_or_defer (kgcn_reduce_defer).  No float atomics: results
 // are bitwise reproducible.
 #include "kgcn_common.h"
@@ -36,24 +41,32 @@ struct ConvArgs {
   const float* w;       // [k, E, F]
   int B, L, S, E, E4, F, k, p, padL, T;   // T = L / p pooled positions
   long tiles;           // B * ceil(T / kTile)
+  const float* scale;   // [B] per-row factor of the gathered embedding (scaled forward only)
+  int rep;              // batch row b reads token row b / rep (scaled forward and input gradient; 1 otherwise)
 };
 
-// window of conv-input rows of tile (b, t0): rows r = 0 .. nrows-1 are sequence positions l = t0 p - padL + r
+// window of conv-input rows of tile (b, t0): rows r = 0 .. nrows-1 are sequence positions l = t0 p - padL + r.  kScaled: row b
+// reads token row b / rep and its embedding rows times scale[b] (the scaled [B, L, E] input is never written)
+template <bool kScaled = false>
 __device__ __forceinline__ void stage_window(const ConvArgs& a, int b, int t0, int nrows, float* win, int* twin) {
   const int l0 = t0 * a.p - a.padL;
+  const long trow = kScaled ? (long)(b / a.rep) : (long)b;
   for (int i = threadIdx.x; i < nrows; i += blockDim.x) {
     const int l = l0 + i;
-    twin[i] = (l >= 0 && l < a.L) ? a.tok[(long)b * a.L + l] : -1;
+    twin[i] = (l >= 0 && l < a.L) ? a.tok[trow * a.L + l] : -1;
   }
   __syncthreads();
+  const float sc = kScaled ? a.scale[b] : 1.f;
   for (int i = threadIdx.x; i < nrows * a.E4; i += blockDim.x) {
     const int r = i / a.E4, e = i - r * a.E4;
     const int s = twin[r];
-    win[i] = (s >= 0 && e < a.E) ? a.table[(long)s * a.E + e] : 0.f;
+    const float x = (s >= 0 && e < a.E) ? a.table[(long)s * a.E + e] : 0.f;
+    win[i] = kScaled ? x * sc : x;
   }
 }
 
 // lane = filter f (< 64), wave = 4 pooled positions of the tile; acc[i][j] = conv at position (t0 + 4 wave + i) p + j
+template <bool kScaled>
 __global__ __launch_bounds__(256) void convpool_fwd_kernel(ConvArgs a, const float* __restrict__ bias, float* __restrict__ out,
                                                            uint8_t* __restrict__ argmax) {
   extern __shared__ float lds[];
@@ -72,7 +85,7 @@ __global__ __launch_bounds__(256) void convpool_fwd_kernel(ConvArgs a, const flo
   for (long tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
     const int b = (int)(tile / tpb), t0 = (int)(tile - (long)b * tpb) * kTile;
     __syncthreads();                            // the previous tile's window is no longer read
-    stage_window(a, b, t0, nrows, win, twin);
+    stage_window<kScaled>(a, b, t0, nrows, win, twin);
     __syncthreads();
     float acc[4][8];
 #pragma unroll
@@ -238,6 +251,7 @@ int conv_args(const int32_t* tokens, int32_t B, int32_t L, const float* table, i
   a.tok = tokens; a.table = table; a.w = w;
   a.B = B; a.L = L; a.S = S; a.E = E; a.E4 = round4(E); a.F = F; a.k = k; a.p = p; a.padL = (k - 1) / 2; a.T = L / p;
   a.tiles = (long)B * ((a.T + kTile - 1) / kTile);
+  a.scale = nullptr; a.rep = 1;
   return 0;
 }
 
@@ -262,6 +276,90 @@ int allow_lds(size_t bytes) {
     if (e != hipSuccess) return fail("hipFuncSetAttribute: %s", hipGetErrorString(e));
     done = true;
   }
+  return 0;
+}
+
+// ---- integrated gradients of the sequence input ---------------------------------------------------------------------------
+// Gradient with respect to the (scaled) embedded input of the conv-pool, summed over the rep copies of a compound:
+//   dx[c, m, e] = sum_r wt[c rep + r] sum_dk sum_f G_r[m + padL - dk, f] W[dk, e, f]   (times table[tok[c, m], e] if asked)
+// with G_r the conv gradient of row c rep + r routed through its arg-max bytes.  Workgroup (compound c, kIgPos output
+// positions); lane e (< 32), thread group grp (8 of them) owns positions grp + 8 q.  Per copy, in copy order: the routed conv
+// gradient of the window [kIgPos + k - 1][F4p] is staged in LDS, every thread forms its four positions against W (in LDS) and
+// adds them, times the copy's weight, into registers.  No weight gradient, no atomics: a fixed summation order.
+constexpr int kIgPos = 32;
+__global__ __launch_bounds__(256) void convpool_input_grad_kernel(ConvArgs a, const float* __restrict__ dout,
+                                                                  const uint8_t* __restrict__ argmax, const float* __restrict__ wt,
+                                                                  int times_table, float* __restrict__ dx) {
+  extern __shared__ float lds[];
+  const int F4p = round4(a.F) + 4;
+  const int nw = kIgPos + a.k - 1;
+  float* wb = lds;                               // [k][E][F4p]
+  float* g = wb + a.k * a.E * F4p;               // [nw][F4p]
+  const int c = blockIdx.x, m0 = blockIdx.y * kIgPos;
+  const int lbase = m0 + a.padL - (a.k - 1);     // conv position of window row 0
+  const int TP = a.T * a.p;
+  for (int i = threadIdx.x; i < a.k * a.E * F4p; i += blockDim.x) {
+    const int fr = i % F4p, r = i / F4p;
+    wb[i] = fr < a.F ? a.w[(long)r * a.F + fr] : 0.f;
+  }
+  const int e = threadIdx.x & 31, grp = threadIdx.x >> 5;
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int r = 0; r < a.rep; ++r) {
+    const long b = (long)c * a.rep + r;
+    const float wr = wt ? wt[b] : 1.f;
+    if (wr == 0.f) continue;                     // uniform over the workgroup
+    __syncthreads();                             // W is staged / the previous copy's window is no longer read
+    for (int i = threadIdx.x; i < nw * F4p; i += blockDim.x) {
+      const int row = i / F4p, fr = i - row * F4p;
+      const int l = lbase + row;
+      float gv = 0.f;
+      if (fr < a.F && l >= 0 && l < TP) {
+        const int t = l / a.p, j = l - t * a.p;
+        const long o = (b * a.T + t) * a.F + fr;
+        if (argmax[o] == j) gv = dout[o];
+      }
+      g[i] = gv;
+    }
+    __syncthreads();
+    if (e < a.E) {
+      float v[4] = {0.f, 0.f, 0.f, 0.f};
+      for (int dk = 0; dk < a.k; ++dk) {
+        const float* wp = wb + (dk * a.E + e) * F4p;
+        const float* gp = g + (grp + a.k - 1 - dk) * F4p;     // window row of position grp + 8 q: + 8 q rows
+        for (int fr = 0; fr < a.F; fr += 4) {
+          const f32x4 ww = *reinterpret_cast<const f32x4*>(wp + fr);
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const f32x4 gg = *reinterpret_cast<const f32x4*>(gp + 8 * q * F4p + fr);
+            v[q] = fmaf(gg.x, ww.x, fmaf(gg.y, ww.y, fmaf(gg.z, ww.z, fmaf(gg.w, ww.w, v[q]))));
+          }
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc[q] = fmaf(wr, v[q], acc[q]);
+    }
+  }
+  if (e < a.E) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int m = m0 + grp + 8 * q;
+      if (m >= a.L) continue;
+      float val = acc[q];
+      if (times_table) val *= a.table[(long)a.tok[(long)c * a.L + m] * a.E + e];
+      dx[((long)c * a.L + m) * a.E + e] = val;
+    }
+  }
+}
+
+size_t convpool_input_grad_lds(const ConvArgs& a) {
+  const int F4p = round4(a.F) + 4;
+  return ((size_t)a.k * a.E * F4p + (size_t)(kIgPos + a.k - 1) * F4p) * 4;
+}
+
+// the batch of the scaled forward / input gradient: `batch` rows, rep copies of each of the batch / rep token rows
+int rep_args(int32_t batch, int32_t rep, const char* who) {
+  if (rep < 1) return fail("%s: %d copies per token row", who, rep);
+  if (batch < 0 || batch % rep) return fail("%s: %d rows are not whole groups of %d copies", who, batch, rep);
   return 0;
 }
 
@@ -549,9 +647,9 @@ extern "C" int kgcn_seq_convpool_fwd_f32(const int32_t* tokens, int32_t batch, i
   if (a.tiles == 0) return 0;
   if (!bias || !out) return fail("%s: NULL operand", who);
   const size_t lds = convpool_fwd_lds(a);
-  if (int rc = allow_lds<convpool_fwd_kernel>(lds)) return rc;
+  if (int rc = allow_lds<convpool_fwd_kernel<false>>(lds)) return rc;
   const int grid = (int)(a.tiles < kConvGridFwd ? a.tiles : kConvGridFwd);
-  hipLaunchKernelGGL(convpool_fwd_kernel, dim3(grid), dim3(256), lds, as_stream(stream), a, bias, out, argmax);
+  hipLaunchKernelGGL(convpool_fwd_kernel<false>, dim3(grid), dim3(256), lds, as_stream(stream), a, bias, out, argmax);
   return check_launch("convpool_fwd_kernel");
 }
 
@@ -589,6 +687,42 @@ extern "C" int kgcn_seq_convpool_bwd_f32(const int32_t* tokens, int32_t batch, i
   if (int rc = reduce_or_defer(part_w, grid, (long)kernel_size * embed_dim * filters, dw, s)) return rc;
   if (int rc = reduce_or_defer(part_b, grid, filters, dbias, s)) return rc;
   return reduce_or_defer(part_t, grid, (long)symbols * embed_dim, dtable, s);
+}
+
+extern "C" int kgcn_seq_convpool_scaled_fwd_f32(const int32_t* tokens, int32_t batch, int32_t rep, const float* scale, int32_t length,
+                                                const float* table, int32_t symbols, int32_t embed_dim, const float* w, const float* bias,
+                                                int32_t kernel_size, int32_t filters, int32_t pool, float* out, uint8_t* argmax,
+                                                void* stream) {
+  const char* who = "kgcn_seq_convpool_scaled_fwd_f32";
+  ConvArgs a;
+  if (int rc = rep_args(batch, rep, who)) return rc;
+  if (int rc = conv_args(tokens, batch, length, table, symbols, embed_dim, w, kernel_size, filters, pool, who, a)) return rc;
+  if (a.tiles == 0) return 0;
+  if (!bias || !out || !scale) return fail("%s: NULL operand", who);
+  a.scale = scale; a.rep = rep;
+  const size_t lds = convpool_fwd_lds(a);
+  if (int rc = allow_lds<convpool_fwd_kernel<true>>(lds)) return rc;
+  const int grid = (int)(a.tiles < kConvGridFwd ? a.tiles : kConvGridFwd);
+  hipLaunchKernelGGL(convpool_fwd_kernel<true>, dim3(grid), dim3(256), lds, as_stream(stream), a, bias, out, argmax);
+  return check_launch("convpool_fwd_kernel<scaled>");
+}
+
+extern "C" int kgcn_seq_convpool_input_grad_f32(const int32_t* tokens, int32_t batch, int32_t rep, int32_t length, const float* table,
+                                                int32_t symbols, int32_t embed_dim, const float* w, int32_t kernel_size,
+                                                int32_t filters, int32_t pool, const float* dout, const uint8_t* argmax,
+                                                const float* row_weight, int32_t times_table, float* dx, void* stream) {
+  const char* who = "kgcn_seq_convpool_input_grad_f32";
+  ConvArgs a;
+  if (int rc = rep_args(batch, rep, who)) return rc;
+  if (int rc = conv_args(tokens, batch, length, table, symbols, embed_dim, w, kernel_size, filters, pool, who, a)) return rc;
+  if (batch == 0) return 0;
+  if (!dx || (a.T > 0 && (!dout || !argmax))) return fail("%s: NULL operand", who);
+  a.rep = rep;
+  const size_t lds = convpool_input_grad_lds(a);
+  if (int rc = allow_lds<convpool_input_grad_kernel>(lds)) return rc;
+  hipLaunchKernelGGL(convpool_input_grad_kernel, dim3(batch / rep, (length + kIgPos - 1) / kIgPos), dim3(256), lds,
+                     as_stream(stream), a, dout, argmax, row_weight, times_table ? 1 : 0, dx);
+  return check_launch("convpool_input_grad_kernel");
 }
 
 extern "C" int64_t kgcn_seq_lstm_stash_floats(int32_t batch, int32_t steps, int32_t units) {

@@ -402,7 +402,13 @@ class MultimodalGCN(nn.Module):
     the LSTM kernel writes and 32-81 the graph read-out (ops.join_columns), so nothing is copied.
     forward(features, adjs, sequences=None, enabled_node_nums=None) -> logits; `sequences` is the int32 [B, L] token batch
     (data_util.sequence_table; GraphedTrainStep passes it as a forward kwarg).  enabled_node_nums is accepted and unused, as in
-    the file (every node row, padding included, reaches the read-out)."""
+    the file (every node row, padding included, reaches the read-out).
+    sequence_scale / sequence_rep (integrated gradients, visualization.multimodal_integrated_gradients): `sequences` holds
+    B / rep token rows, row b of the batch runs the sequence branch on token row b // rep with its embedded input times
+    sequence_scale[b] (SequenceEncoder.scaled); the default None keeps the training path above.
+    The batch rows never mix (no dropout, no batch normalisation), which is what lets the attribution batch scaled copies."""
+
+    ROW_INDEPENDENT = True
 
     GRAPH_WIDTH, SEQ_WIDTH, HIDDEN = 50, 32, 52
 
@@ -415,21 +421,32 @@ class MultimodalGCN(nn.Module):
         self.hidden = KerasDense(self.HIDDEN)                                                     # :101-103
         self.out = KerasDense(int(label_dim))                                                     # :104
 
-    def forward(self, features, adjs, sequences=None, enabled_node_nums=None):
+    def forward(self, features, adjs, sequences=None, enabled_node_nums=None, sequence_scale=None, sequence_rep=1):
+        return self.run(features, adjs, sequences, sequence_scale, sequence_rep)[0]
+
+    def run(self, features, adjs, sequences, sequence_scale=None, sequence_rep=1, input_grad=False):
+        """forward() -> (logits, pooled, arg-max bytes); the last two are None on the default path, and with sequence_scale they are
+        what SequenceEncoder.scaled returns (input_grad: pooled is a leaf that requires grad)."""
         if sequences is None:
             raise ValueError("MultimodalGCN needs the sequences= token batch")
         adj = layers._pack(adjs, features)
         B = features.shape[0]
-        if sequences.shape[0] != B:
-            raise ValueError("%d sequences for %d graphs" % (sequences.shape[0], B))
+        rep = 1 if sequence_scale is None else int(sequence_rep)
+        if sequences.shape[0] * rep != B:
+            raise ValueError("%d sequences for %d graphs" % (sequences.shape[0], B) if rep == 1 else
+                             "%d sequences x %d copies for %d graphs" % (sequences.shape[0], rep, B))
         joined = features.new_empty((B, self.SEQ_WIDTH + self.GRAPH_WIDTH))
-        seq = self.sequence(sequences, out=joined, out_col=0)
+        pooled = arg = None
+        if sequence_scale is None:
+            seq = self.sequence(sequences, out=joined, out_col=0)
+        else:
+            seq, pooled, arg = self.sequence.scaled(sequences, sequence_scale, rep, out=joined, out_col=0, input_grad=input_grad)
         node = self.dense(self.conv(features, adj=adj))
         graph = ops.graph_gather_into(node, joined, self.SEQ_WIDTH)
         layer = ops.join_columns(joined, [seq, graph])                                            # :96 tf.concat
         self.hidden.build(layer.shape[1], layer.device)
         layer = ops.dense(layer, self.hidden.kernel, self.hidden.bias, activation="relu")
-        return self.out(layer)
+        return self.out(layer), pooled, arg
 
     @staticmethod
     def loss(logits, labels, mask):

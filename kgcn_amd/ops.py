@@ -2127,6 +2127,70 @@ def seq_lstm(x, wx, wh, bias, recurrent_activation="hard_sigmoid", out=None, out
     return _SeqLSTM.apply(x, wx, wh, bias, act, out, int(out_col))
 
 
+def _seq_conv_operands(tokens, table, w, pool, rows, rep):
+    if not (torch.is_tensor(tokens) and tokens.is_cuda and tokens.dtype == torch.int32 and tokens.dim() == 2):
+        raise _lib.KgcnHipError("tokens must be an int32 [batch, length] device tensor")
+    table, w = _f32c(table, "embedding table"), _f32c(w, "conv kernel")
+    S, E = table.shape
+    if w.dim() != 3 or w.shape[1] != E:
+        raise _lib.KgcnHipError("conv kernel %s does not match an embedding width of %d" % (tuple(w.shape), E))
+    rep = int(rep)
+    if rep < 1 or rows != tokens.shape[0] * rep:
+        raise _lib.KgcnHipError("%d rows are not %d copies of %d token rows" % (rows, rep, tokens.shape[0]))
+    seq_limits_check(tokens.shape[1], S, E, w.shape[0], w.shape[2], pool)
+    return tokens.contiguous(), table, w, rep
+
+
+def seq_conv_pool_scaled(tokens, table, w, bias, pool, scale, rep, argmax=False):
+    """The conv-pool of seq_conv_pool on rep scaled copies of every token row, without autograd (integrated gradients,
+    kgcn/feed.py:88-89 add_perturbation on the embedded layer): tokens [C, L] int32, scale [C rep] fp32 -> (pooled [C rep, L // pool, F],
+    arg-max bytes of the same shape when argmax=True, else None).  Row b reads token row b // rep and its embedding rows times
+    scale[b]; the scaled [C rep, L, E] input is never written."""
+    scale = _f32c(scale, "scale").reshape(-1)
+    B = scale.numel()
+    tokens, table, w, rep = _seq_conv_operands(tokens, table, w, pool, B, rep)
+    b = _f32c(bias, "conv bias").reshape(-1)
+    S, E = table.shape
+    k, F = w.shape[0], w.shape[2]
+    if b.numel() != F:
+        raise _lib.KgcnHipError("conv bias %s does not match %d filters" % (tuple(bias.shape), F))
+    L = tokens.shape[1]
+    T = L // int(pool)
+    out = torch.empty((B, T, F), device=table.device, dtype=torch.float32)
+    arg = torch.empty((B, T, F), device=table.device, dtype=torch.uint8) if argmax else None
+    check(lib.kgcn_seq_convpool_scaled_fwd_f32(ptr(tokens), B, rep, ptr(scale), L, ptr(table), S, E, ptr(w), ptr(b), k, F, int(pool),
+                                               ptr(out), ptr(arg), current_stream()), "kgcn_seq_convpool_scaled_fwd_f32")
+    return out, arg
+
+
+def seq_conv_pool_input_grad(dout, argmax, tokens, table, w, pool, rep, row_weight=None, times_table=False):
+    """Gradient with respect to the scaled embedded input of seq_conv_pool_scaled, summed over the rep copies of every token
+    row: d pooled [C rep, L // pool, F] and its arg-max bytes -> [C, L, E], the sum in copy order of row_weight[b] (None = 1)
+    times the gradient of copy b, times table[tokens] when times_table (the attribution of kgcn/visualization.py:207-215).
+    No weight gradient is formed."""
+    B = dout.shape[0]
+    tokens, table, w, rep = _seq_conv_operands(tokens, table, w, pool, B, rep)
+    dout = _f32c(dout, "grad")
+    S, E = table.shape
+    k, F = w.shape[0], w.shape[2]
+    C, L = tokens.shape
+    T = L // int(pool)
+    if tuple(dout.shape) != (B, T, F) or argmax is None or tuple(argmax.shape) != (B, T, F) or argmax.dtype != torch.uint8:
+        raise _lib.KgcnHipError("d pooled %s / arg-max bytes do not match [%d, %d, %d]" % (tuple(dout.shape), B, T, F))
+    require_gpu(argmax, "arg-max bytes")
+    argmax = argmax.contiguous()
+    wt = None
+    if row_weight is not None:
+        wt = _f32c(row_weight, "row weights").reshape(-1)
+        if wt.numel() != B:
+            raise _lib.KgcnHipError("%d row weights for %d rows" % (wt.numel(), B))
+    dx = torch.empty((C, L, E), device=table.device, dtype=torch.float32)
+    check(lib.kgcn_seq_convpool_input_grad_f32(ptr(tokens), B, rep, L, ptr(table), S, E, ptr(w), k, F, int(pool), ptr(dout), ptr(argmax),
+                                               ptr(wt), 1 if times_table else 0, ptr(dx), current_stream()),
+          "kgcn_seq_convpool_input_grad_f32")
+    return dx
+
+
 class _GatherInto(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, join, join_col):
