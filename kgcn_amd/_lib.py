@@ -349,6 +349,14 @@ def ptr(t):
     return ctypes.c_void_p(0 if t is None else t.data_ptr())
 
 
+def workspace(nbytes, device, dtype=None):
+    """Scratch tensor for a C call's workspace argument: at least `nbytes` bytes (rounded up to whole elements of `dtype`,
+    default float32) and at least one element, so its pointer is never NULL."""
+    import torch
+    dtype = torch.float32 if dtype is None else dtype
+    return torch.empty((max(-(-int(nbytes) // dtype.itemsize), 1),), device=device, dtype=dtype)
+
+
 def require_gpu(t, name):
     if not t.is_cuda:
         raise KgcnHipError(

@@ -187,7 +187,7 @@ class BatchedCSR:
         perm = torch.empty(nnz, device=dev, dtype=torch.int32)
         stats = torch.empty(2, device=dev, dtype=torch.int32)
         wsb = lib.kgcn_coo_pack_workspace_bytes(nnz, T, M, K)
-        ws = torch.empty(max(wsb, 8) // 8, device=dev, dtype=torch.int64)
+        ws = _lib.workspace(wsb, dev, torch.int64)
         _lib.check(lib.kgcn_coo_pack_f32(_lib.ptr(g), _lib.ptr(r), _lib.ptr(c), _lib.ptr(v), nnz, T, M, K,
                                          1 if _transposed else 0, _lib.ptr(rowptr), cv.data_ptr() if nnz else 0,
                                          _lib.ptr(perm) if nnz else None, _lib.ptr(stats), _lib.ptr(ws), wsb,
@@ -218,7 +218,7 @@ class BatchedCSR:
         gptr = torch.empty(T + 1, device=dev, dtype=torch.int32)
         stats = torch.empty(3, device=dev, dtype=torch.int32)
         wsb = lib.kgcn_csr_pad4_workspace_bytes(T, M)
-        ws = torch.empty(max(wsb, 8) // 8, device=dev, dtype=torch.int64)
+        ws = _lib.workspace(wsb, dev, torch.int64)
         _lib.check(lib.kgcn_csr_pad4(self.desc(), _lib.ptr(rp4), cv4.data_ptr(), cap, _lib.ptr(slots), _lib.ptr(gptr),
                                      _lib.ptr(stats), _lib.ptr(ws), wsb, _lib.current_stream()), "kgcn_csr_pad4")
         max_nnz, total, bad = (int(x) for x in stats.tolist())
@@ -415,7 +415,7 @@ class BatchedCSR:
             cv = torch.empty((total, 2), **i32)
             gptr = torch.empty(T + 1, **i32)
             slots = torch.empty(T * M, **i32) if self.row_pad else None
-            ws = torch.empty(max(wsb, 4) // 4, **i32)
+            ws = _lib.workspace(wsb, dev, torch.int32)
             cap = total
         else:
             if (out.num_graphs, out.rows, out.cols, out.row_pad) != (T, M, self.cols, self.row_pad):
@@ -454,7 +454,7 @@ class BatchedCSR:
                   row_pad=src.row_pad)
         out._refillable = True
         out._gptr_buf = torch.zeros(T + 1, **i32)
-        out._ws = torch.empty(max(_lib.lib.kgcn_csr_gather_workspace_bytes(T), 4) // 4, **i32)
+        out._ws = _lib.workspace(_lib.lib.kgcn_csr_gather_workspace_bytes(T), dev, torch.int32)
         if src.row_pad:
             out.slots = torch.zeros(T * M, **i32)
             out.graph_ptr = out._gptr_buf

@@ -14,12 +14,6 @@
 
 namespace kgcn {
 
-int launch_reduce_partials(const float* part, int nparts, long n, float* out, hipStream_t s);
-int launch_reduce_pair_now(const float* part_a, long n_a, float* out_a, const float* part_b, long n_b, float* out_b, int nparts,
-                       hipStream_t s);
-int launch_reduce_pair(const float* part_a, long n_a, float* out_a, const float* part_b, long n_b, float* out_b, int nparts,
-                       hipStream_t s);            // (dense.hip: queued inside a deferral scope, kgcn_reduce_defer)
-
 constexpr int BN_BLOCKS = 1024;    // partial rows of the first reduction stage
 
 // MODE 0: acc0 = sum x                       (mean numerator)

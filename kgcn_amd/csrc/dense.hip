@@ -826,8 +826,6 @@ namespace kgcn {
 int launch_gemmb(const float* grad, const float* act_out, long m, int din, int dout, long ld, const float* x, long x_ld,
                  const void* tabh, float* dx, long dx_ld, float* part_dw, float* part_db, int dact, const float* pooled_grad,
                  int n_nodes, long pooled_ld, hipStream_t s, float* dot_part);
-int launch_reduce_pair(const float* part_dw, long n_dw, float* dw, const float* part_db, long n_db, float* dbias, int nparts,
-                       hipStream_t s);
 }  // namespace kgcn
 
 extern "C" int kgcn_dense_bwd_supported(int64_t m, int32_t din, int32_t dout) {
@@ -933,9 +931,6 @@ extern "C" int kgcn_dense_fwd_ws_f32(const float* x, int64_t m, int32_t din, int
 
 // dW and dbias partials of one layer in ONE launch (either output may be NULL)
 namespace kgcn {
-// ... now, whatever the deferral state: for results the SAME call reads back (batch normalisation's d gamma / d beta enter its dx)
-int launch_reduce_pair_now(const float* part_dw, long n_dw, float* dw, const float* part_db, long n_db, float* dbias,
-                           int nparts, hipStream_t s);
 int launch_reduce_pair(const float* part_dw, long n_dw, float* dw, const float* part_db, long n_db, float* dbias,
                        int nparts, hipStream_t s) {
   if (g_defer_reduce.load()) {                           // a training step: all second stages in one launch at its end

@@ -31,12 +31,6 @@
 
 namespace kgcn {
 
-int launch_reduce_partials(const float* part, int nparts, long n, float* out, hipStream_t s);
-int launch_reduce_pair(const float* part_dw, long n_dw, float* dw, const float* part_db, long n_db, float* dbias, int nparts,
-                       hipStream_t s);
-int launch_reduce_partials2(const float* part, int nparts, long n, float* out, const float* part2, long n2,
-                            float* out2, hipStream_t s);
-
 constexpr int FN = 32;    // node tile (MFMA M)
 constexpr int FD = 64;    // feature tile (K of the forward GEMM, two 32-wide output tiles)
 constexpr int ALD = 68;   // padded row stride (floats) of the forward's A-fragment tile (b128 reads)

@@ -11,8 +11,6 @@
 
 namespace kgcn {
 
-int launch_reduce_partials(const float* part, int nparts, long n, float* out, hipStream_t s);
-
 constexpr float kGatSlope = 0.2f;     // tf.nn.leaky_relu default
 constexpr float kGatEps = 1.0e-10f;
 

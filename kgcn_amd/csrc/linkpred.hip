@@ -25,7 +25,6 @@
 #include "philox.h"
 
 namespace kgcn {
-int reduce_or_defer(const float* part, int nparts, long n, float* out, hipStream_t s);
 
 namespace {
 constexpr int kChunk = 16;           // sorted entries per wave of the sum pass (longer lists are split and re-added in order):

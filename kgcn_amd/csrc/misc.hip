@@ -345,7 +345,6 @@ extern "C" int kgcn_dot_f32(const float* a, const float* b, int64_t n, float* ou
 // with one partial per workgroup (deterministic second stage).
 // ------------------------------------------------------------------------------------------------
 namespace kgcn {
-int launch_reduce_partials(const float* part, int nparts, long n, float* out, hipStream_t s);
 
 __global__ __launch_bounds__(256) void gram_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                         float* __restrict__ out, int T, int N, int D) {

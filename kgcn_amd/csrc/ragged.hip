@@ -366,8 +366,6 @@ __global__ __launch_bounds__(256) void ragged_gather_pad_bwd_kernel(const float*
   }
 }
 
-int launch_reduce_partials(const float* part, int nparts, long n, float* out, hipStream_t s);
-
 // out[r, 0:din] = x[r, 0:din], out[r, din] = 1, out[r, din+1:out_ld] = 0: the operand of an aggregate-FIRST GraphConv,
 //   A (X W + 1 b) = (A [X | 1]) [W ; b]        (kgcn/layers.py:112-113 evaluated in the cheaper order when din + 1 < dout)
 // -- the column of ones turns the bias term rowsum(A) (x) b into one more row of the contraction.

@@ -25,7 +25,6 @@
 #include "kgcn_common.h"
 
 namespace kgcn {
-int reduce_or_defer(const float* part, int nparts, long n, float* out, hipStream_t s);
 
 namespace {
 constexpr int kTile = 16;                 // pooled positions per conv-pool tile (4 per wave)

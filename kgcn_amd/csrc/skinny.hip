@@ -13,9 +13,6 @@
 
 namespace kgcn {
 
-int launch_reduce_pair(const float* part_dw, long n_dw, float* dw, const float* part_db, long n_db, float* dbias, int nparts,
-                       hipStream_t s);
-
 constexpr int SKN = 16;          // narrow side at most
 constexpr int SK_KPL = 16;       // k values per lane at most (wide side <= 1024)
 

@@ -26,9 +26,6 @@
 
 namespace kgcn {
 
-int launch_reduce_partials(const float* part, int nparts, long n, float* out, hipStream_t s);
-int reduce_or_defer(const float* part, int nparts, long n, float* out, hipStream_t s);   // (dense.hip: queued inside a deferral scope)
-
 // LDS floats of one weight block: kind 0/1: W [din x 65] + b [64]; kind 2: scale [64] + shift [64]
 __host__ __device__ inline int sk_wblock(int kind, int din) { return kind == 2 ? 128 : din * SK_WLD + 64; }
 

@@ -19,7 +19,6 @@
 #include "philox.h"
 
 namespace kgcn {
-int reduce_or_defer(const float* part, int nparts, long n, float* out, hipStream_t s);
 
 namespace {
 // two 64-bit words -> two N(0, 1): u1 = (top 24 bits + 1) 2^-24 in (0, 1], u2 = top 24 bits 2^-24 in [0, 1)

@@ -396,7 +396,7 @@ class StaticBatch:
         if self._asm_ws is None:
             import torch
             wsb = _lib.lib.kgcn_batch_assemble_workspace_bytes(T)
-            self._asm_ws = torch.empty(max(wsb, 4) // 4, dtype=torch.int32, device=self._sel_dev.device)
+            self._asm_ws = _lib.workspace(wsb, self._sel_dev.device, torch.int32)
         _lib.check(_lib.lib.kgcn_batch_assemble(plan, self._sel_dev.data_ptr(), T, self._asm_ws.data_ptr(),
                                                 self._asm_ws.numel() * 4, _lib.current_stream()), "kgcn_batch_assemble")
 

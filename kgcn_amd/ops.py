@@ -55,7 +55,7 @@ class deferred_reductions:
     incoming edge (used twice -- by kgcn ops, by plain torch ops such as an L2 penalty or a tied torch.matmul, or both: autograd
     ADDS the contributions inside the pass), that carries a tensor hook, or whose .grad already exists (accumulated in place
     inside the pass) is excluded from deferral for this backward pass.  Without `root` only uses by kgcn ops are known
-    (_count_use): pass it whenever the model may contain anything else."""
+    (_record_params): pass it whenever the model may contain anything else."""
 
     def __init__(self, root=None):
         self.root = root
@@ -64,7 +64,7 @@ class deferred_reductions:
         _no_defer_params.clear()
         if self.root is not None:
             _no_defer_params.update(_readers_inside_backward(self.root))
-        self.prev = lib.kgcn_reduce_defer(0 if _no_defer_debug() else 1)
+        self.prev = lib.kgcn_reduce_defer(1)
         return self
 
     def __exit__(self, *exc):
@@ -104,26 +104,9 @@ def _readers_inside_backward(root):
     return out
 
 
-def _no_defer_debug():
-    import os
-    v = os.environ.get("KGCN_NO_DEFER", "")
-    if v == "1":
-        return True
-    if v == "capture":
-        return torch.cuda.is_current_stream_capturing()
-    if v == "eager":
-        return not torch.cuda.is_current_stream_capturing()
-    return False
-
-
 def flush_reductions():
     check(lib.kgcn_reduce_flush(current_stream()), "kgcn_reduce_flush")
     _deferred_keep.clear()
-
-
-def _keep_until_flush(t):
-    if lib.kgcn_reduce_pending() > 0:
-        _deferred_keep.append(t)
 
 
 # How often each parameter tensor entered a deferral-capable op since the step began: a parameter used TWICE receives two
@@ -132,28 +115,44 @@ def _keep_until_flush(t):
 _param_uses = {}
 
 
-def _count_use(*params):
+def _record_params(ctx, *params, when=True):
+    """Forward half of every op whose backward C call writes parameter gradients through the deferrable second stage: records
+    those parameters (None entries skipped) and counts one use of each.  stack_rows' operand is a fresh tensor on every call and
+    stands for the parameters behind it: those are counted and checked.  when=False: this call's backward never defers."""
+    ps = []
     for p in params:
         if p is not None:
-            _param_uses[id(p)] = _param_uses.get(id(p), 0) + 1
+            ps.extend(getattr(p, "_kgcn_defer_params", (p,)))
+    for p in ps:
+        _param_uses[id(p)] = _param_uses.get(id(p), 0) + 1
+    ctx.defer_params = tuple(ps) if when else ()
 
 
-def _single_use(*params):
-    return all(p is None or (_param_uses.get(id(p), 0) == 1 and id(p) not in _no_defer_params) for p in params)
+class _param_grad_stage:
+    """with _param_grad_stage(ctx, nbytes, device) as ws: <the op's C call>  -- the backward half of _record_params; ws is the
+    call's partials workspace (at least nbytes), kept alive until the flush.  Deferral stays on around the call only if nothing
+    reads or drops the recorded parameters' gradients before the flush: each one is a leaf (a computed weight's gradient is read
+    right away), requires a gradient (autograd drops an unwanted one when backward returns, and the flush would then write into
+    reused memory), is used once this step and not read inside the pass (deferred_reductions' root check); grad mode is off
+    (backward(create_graph=True) turns it on, and AccumulateGrad then copies each gradient before the flush); `when` holds."""
 
+    __slots__ = ("ok", "ws", "prev")
 
-class _no_deferral_unless:
-    """switches deferral off around one C call whose results are consumed inside the backward pass"""
-
-    def __init__(self, ok):
-        self.ok = ok
+    def __init__(self, ctx, nbytes, device, when=True):
+        self.ws = _lib.workspace(nbytes, device)
+        ps = ctx.defer_params
+        self.ok = bool(when and ps and not torch.is_grad_enabled() and all(
+            p.is_leaf and p.requires_grad and _param_uses.get(id(p), 0) == 1 and id(p) not in _no_defer_params for p in ps))
 
     def __enter__(self):
         self.prev = None if self.ok else lib.kgcn_reduce_defer(0)
+        return self.ws
 
     def __exit__(self, *exc):
         if self.prev is not None:
             lib.kgcn_reduce_defer(self.prev)
+        if lib.kgcn_reduce_pending() > 0:
+            _deferred_keep.append(self.ws)
         return False
 
 
@@ -502,7 +501,7 @@ def _dense_ws(din, dout, device):
     wsb = lib.kgcn_dense_fwd_workspace_bytes(din, dout)
     if wsb <= 0:
         return 0, None
-    return wsb, torch.empty((wsb // 4,), device=device, dtype=torch.float32)
+    return wsb, _lib.workspace(wsb, device)
 
 
 class WeightTables:
@@ -542,7 +541,7 @@ class WeightTables:
                 return None
             e = WeightTables._Entry()
             e.ref = weakref.ref(w)
-            e.tables = [None if b <= 0 else torch.empty((b // 4,), device=w.device, dtype=torch.float32) for b in sizes]
+            e.tables = [None if b <= 0 else _lib.workspace(b, w.device) for b in sizes]
             e.epoch, e.version, e.used = -1, -1, False
             self.entries[key] = e
         if e is not None:
@@ -583,7 +582,7 @@ class WeightTables:
                 return
             e = WeightTables._Entry()
             e.ref, e.ref2 = weakref.ref(w), weakref.ref(bias)
-            e.tables = [torch.empty((b // 4,), device=w.device, dtype=torch.float32), None]
+            e.tables = [_lib.workspace(b, w.device), None]
             e.epoch, e.version, e.used, e.rows = -1, (-1, -1), False, int(rows)
             self.entries[key] = e
         e.used = True
@@ -683,13 +682,11 @@ def _dense_bwd_fused(ctx, x2d, w, gy, yact, act, need_b, gp=None, gp_ld=0, n_nod
     if tab is None:
         tb, tab = _dense_ws(dout, din, x2d.device)
         ready = 0
-    with _no_deferral_unless(getattr(ctx, "defer_ok", False) and _single_use(*ctx.defer_ids)):
-        wsb = lib.kgcn_dense_wgrad_workspace_bytes(m, din, dout)
-        wsp = torch.empty((max(wsb, 4) // 4,), device=x2d.device, dtype=torch.float32)
+    wsb = lib.kgcn_dense_wgrad_workspace_bytes(m, din, dout)
+    with _param_grad_stage(ctx, wsb, x2d.device) as wsp:
         check(lib.kgcn_dense_bwd_f32(ptr(gy), None if gp is None else gp.data_ptr(), gp_ld, n_nodes, ptr(yact) if act else None,
                                      int(act), dout, ptr(x2d), din, m, din, dout, ptr(w), dout, ptr(dx), din, ptr(dw), ptr(db),
                                      ptr(tab), tb, ready, ptr(wsp), wsb, current_stream()), "kgcn_dense_bwd_f32")
-        _keep_until_flush(wsp)
     if db is not None:
         db = db.reshape(ctx.bias_shape)
     return dx, dw, db
@@ -698,6 +695,9 @@ def _dense_bwd_fused(ctx, x2d, w, gy, yact, act, need_b, gp=None, gp_ld=0, n_nod
 class _Dense(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x2d, w, bias, act=0):
+        # (a computed weight -- the concatenated kernels of a multi-channel GraphConv -- is not a leaf: autograd slices its gradient
+        # right away, so it does not defer; stack_rows' [w; bias; pad] stands for w and bias, whose gradients are views of it)
+        _record_params(ctx, w, bias)
         x2d, w = _f32c(x2d, "x"), _f32c(w, "w")
         m, din = x2d.shape
         dout = w.shape[1]
@@ -719,17 +719,6 @@ class _Dense(torch.autograd.Function):
         ctx.act = int(act)
         ctx.save_for_backward(x2d, w, y if act else x2d)
         ctx.bias_shape = None if bias is None else tuple(bias.shape)
-        # the second stage of dW / dbias may only wait (ops.deferred_reductions) when NOTHING reads them inside the backward pass:
-        # true for leaf parameters, false for a weight that is itself computed (the concatenated kernels of a multi-channel
-        # GraphConv: autograd slices its gradient right away; stack_rows' output is sliced into views only: see _StackRows)
-        ctx.defer_ok = bool((w.is_leaf or getattr(w, "_kgcn_defer_safe", False)) and (bias is None or bias.is_leaf))
-        # who receives this gradient: the operand itself, or -- for stack_rows' [w; bias; pad], a fresh tensor per call -- the
-        # PARAMETERS behind it (a GraphConv applied twice shares them: both contributions are added inside the pass)
-        under = getattr(w, "_kgcn_defer_params", None)
-        ctx.defer_ids = (w, bias) if under is None else tuple(under) + (bias,)
-        if under is None:
-            _count_use(w)
-        _count_use(bias)
         return y
 
     @staticmethod
@@ -791,12 +780,10 @@ class _Dense(torch.autograd.Function):
 
     @staticmethod
     def _wgrad(ctx, x2d, w, gy, yact, m, din, dout, need_w, need_b, fuse_dact):
-        db = None
-        with _no_deferral_unless(getattr(ctx, "defer_ok", False) and _single_use(*ctx.defer_ids)):
-            wsb = lib.kgcn_dense_wgrad_workspace_bytes(m, din, dout)
-            wsp = torch.empty((max(wsb, 4) // 4,), device=gy.device, dtype=torch.float32)
-            dw = torch.empty_like(w) if need_w else None
-            db = torch.empty((dout,), device=gy.device, dtype=torch.float32) if need_b else None
+        wsb = lib.kgcn_dense_wgrad_workspace_bytes(m, din, dout)
+        dw = torch.empty_like(w) if need_w else None
+        db = torch.empty((dout,), device=gy.device, dtype=torch.float32) if need_b else None
+        with _param_grad_stage(ctx, wsb, gy.device) as wsp:
             if fuse_dact:
                 check(lib.kgcn_dense_wgrad_dact_f32(ptr(x2d), din, ptr(gy), ptr(yact), dout, ctx.act, m, din, dout, ptr(dw),
                                                     ptr(db), ptr(wsp), wsb, current_stream()), "kgcn_dense_wgrad_dact_f32")
@@ -804,17 +791,17 @@ class _Dense(torch.autograd.Function):
                 check(lib.kgcn_dense_wgrad_f32(ptr(x2d), din, ptr(gy), dout, m, din, dout, ptr(dw),
                                                ptr(db), ptr(wsp), wsb, current_stream()),
                       "kgcn_dense_wgrad_f32")
-            _keep_until_flush(wsp)
-            if db is not None:
-                db = db.reshape(ctx.bias_shape)
+        if db is not None:
+            db = db.reshape(ctx.bias_shape)
         return dw, db
 
 
 class _StackRows(torch.autograd.Function):
     """[w; bias; pad] along dim 0 (the operand of an aggregate-first GraphConv, layers.py) with a backward that hands out ROW BLOCKS
     of the incoming gradient as views -- nothing reads the gradient's data inside the backward pass, so the second stage of the
-    weight-gradient GEMM that produces it may wait for the step's one reduction launch like a leaf parameter's (the output carries
-    `_kgcn_defer_safe`; torch.cat's backward does the same slicing, but that is torch's business and not a contract)."""
+    weight-gradient GEMM that produces it may wait for the step's one reduction launch like a leaf parameter's (the output names
+    the parameters behind it in `_kgcn_defer_params`; torch.cat's backward does the same slicing, but that is torch's business and
+    not a contract)."""
 
     @staticmethod
     def forward(ctx, w, bias, pad):
@@ -829,9 +816,7 @@ class _StackRows(torch.autograd.Function):
 
 def stack_rows(w, bias, pad):
     out = _StackRows.apply(w, bias, pad)
-    out._kgcn_defer_safe = bool(w.is_leaf and bias.is_leaf)
-    out._kgcn_defer_params = (w, bias)         # _Dense counts / checks THESE: `out` is a new tensor on every call
-    _count_use(w, bias)
+    out._kgcn_defer_params = (w, bias)         # _record_params counts / checks THESE: `out` is a new tensor on every call
     return out
 
 
@@ -850,9 +835,7 @@ class _DenseStacked(torch.autograd.Function):
                                          current_stream()), "kgcn_dense_fwd_tab_f32")
         ctx.act = int(act)
         ctx.save_for_backward(x2d, w, bias, y)
-        ctx.defer_ok = bool(w.is_leaf and bias.is_leaf)
-        ctx.defer_ids = (w, bias)
-        _count_use(w, bias)
+        _record_params(ctx, w, bias)
         return y
 
     @staticmethod
@@ -864,17 +847,15 @@ class _DenseStacked(torch.autograd.Function):
         fuse_dact = bool(ctx.act) and wgrad_dact_fusion and bool(lib.kgcn_dense_wgrad_dact_supported(rows, dout))
         if ctx.act and not fuse_dact:
             gy = activation_backward(y, gy, ctx.act)
-        with _no_deferral_unless(ctx.defer_ok and _single_use(*ctx.defer_ids)):
-            wsb = lib.kgcn_dense_wgrad_workspace_bytes(m, rows, dout)
-            wsp = torch.empty((max(wsb, 4) // 4,), device=gy.device, dtype=torch.float32)
-            dwa = torch.empty((rows, dout), device=gy.device, dtype=torch.float32)
+        wsb = lib.kgcn_dense_wgrad_workspace_bytes(m, rows, dout)
+        dwa = torch.empty((rows, dout), device=gy.device, dtype=torch.float32)
+        with _param_grad_stage(ctx, wsb, gy.device) as wsp:
             if fuse_dact:
                 check(lib.kgcn_dense_wgrad_dact_f32(ptr(x2d), rows, ptr(gy), ptr(y), dout, ctx.act, m, rows, dout, ptr(dwa), None,
                                                     ptr(wsp), wsb, current_stream()), "kgcn_dense_wgrad_dact_f32")
             else:
                 check(lib.kgcn_dense_wgrad_f32(ptr(x2d), rows, ptr(gy), dout, m, rows, dout, ptr(dwa), None, ptr(wsp), wsb,
                                                current_stream()), "kgcn_dense_wgrad_f32")
-            _keep_until_flush(wsp)
         return None, dwa[:din], dwa[din:din + 1].reshape(bias.shape), None, None, None
 
 
@@ -937,9 +918,7 @@ class _DenseGather(torch.autograd.Function):
         ctx.act, ctx.T, ctx.N = int(act), int(T), int(N)
         ctx.save_for_backward(x2d, w, y)
         ctx.bias_shape = None if bias is None else tuple(bias.shape)
-        ctx.defer_ok = bool(w.is_leaf and (bias is None or bias.is_leaf))
-        ctx.defer_ids = (w, bias)
-        _count_use(w, bias)
+        _record_params(ctx, w, bias)
         ctx.set_materialize_grads(False)
         return y.view(T, N, dout), pooled
 
@@ -1077,9 +1056,7 @@ class _GraphConvFused(torch.autograd.Function):
                                          ptr(out), current_stream()), "kgcn_graphconv_fwd_f32")
         ctx.csr = csr
         ctx.bias_shape = tuple(bias.shape)
-        ctx.defer_ok = bool(w.is_leaf and bias.is_leaf)
-        ctx.defer_ids = (w, bias)
-        _count_use(w, bias)
+        _record_params(ctx, w, bias)
         ctx.save_for_backward(x, w)
         return out
 
@@ -1095,12 +1072,10 @@ class _GraphConvFused(torch.autograd.Function):
         dwb = torch.empty((din * dout + dout,), device=x.device, dtype=torch.float32)
         dw, db = dwb[:din * dout].view(din, dout), dwb[din * dout:]
         wsb = lib.kgcn_graphconv_bwd_workspace_bytes(T, din, dout)
-        wsp = torch.empty((max(wsb, 4) // 4,), device=x.device, dtype=torch.float32)
-        with _no_deferral_unless(ctx.defer_ok and _single_use(*ctx.defer_ids)):
+        with _param_grad_stage(ctx, wsb, x.device) as wsp:
             check(lib.kgcn_graphconv_bwd_f32(ctx.csr.transpose().padded4().desc(), ptr(x), ptr(w),
                                              ptr(g), din, dout, ptr(dx), ptr(dw), ptr(db), ptr(wsp),
                                              wsb, current_stream()), "kgcn_graphconv_bwd_f32")
-        _keep_until_flush(wsp)
         return dx, dw, db.reshape(ctx.bias_shape), None
 
 
@@ -1143,7 +1118,7 @@ class _GinAggregate(torch.autograd.Function):
             dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
             one = torch.empty((1,), device=x.device, dtype=torch.float32) if want_eps else None
             wsb = lib.kgcn_gin_aggregate_bwd_workspace_bytes(T, N, d)
-            wsp = torch.empty((max(wsb, 4) // 4,), device=x.device, dtype=torch.float32)
+            wsp = _lib.workspace(wsb, x.device)
             check(lib.kgcn_gin_aggregate_bwd_f32(adj.desc_array(True), adj.num_channels, ptr(g), d,
                                                  ptr(e) if ctx.has_eps else None, ptr(x), ptr(dx), ptr(one), ptr(wsp), wsb,
                                                  current_stream()), "kgcn_gin_aggregate_bwd_f32")
@@ -1190,9 +1165,7 @@ class _GinDense(torch.autograd.Function):
                                             current_stream()), "kgcn_dense_fwd_ws_f32")
         ctx.act, ctx.eps_shape = int(act), tuple(eps.shape)
         ctx.bias_shape = None if bias is None else tuple(bias.shape)
-        ctx.defer_ok = bool(w.is_leaf and (bias is None or bias.is_leaf))
-        ctx.defer_ids = (w, bias)
-        _count_use(w, bias)
+        _record_params(ctx, w, bias)
         ctx.save_for_backward(x, agg, w, y)
         return y.view(T, N, dout)
 
@@ -1214,19 +1187,17 @@ class _GinDense(torch.autograd.Function):
             # ONE pass: d eps, dW and dbias from a single sweep over (gy, y, agg, x) -- no d pre-activation tensor either
             dw = torch.empty_like(w)
             db = torch.empty((dout,), device=gy.device, dtype=torch.float32) if need_b else None
-            with _no_deferral_unless(getattr(ctx, "defer_ok", False) and _single_use(*ctx.defer_ids)):
-                wsb = lib.kgcn_dense_wgrad_workspace_bytes(m, din, dout)
-                wsp = torch.empty((max(wsb, 4) // 4,), device=gy.device, dtype=torch.float32)
+            wsb = lib.kgcn_dense_wgrad_workspace_bytes(m, din, dout)
+            with _param_grad_stage(ctx, wsb, gy.device) as wsp:
                 check(lib.kgcn_dense_bwd_dot_f32(ptr(gy), ptr(y), ctx.act, dout, ptr(agg), din, m, din, dout, ptr(w), dout, ptr(x), din,
                                                  ptr(dw), ptr(db), ptr(deps), ptr(tab), tb, ready, ptr(wsp), wsb, current_stream()),
                       "kgcn_dense_bwd_dot_f32")
-                _keep_until_flush(wsp)
             if db is not None:
                 db = db.reshape(ctx.bias_shape)
             return None, (deps.reshape(ctx.eps_shape) if ctx.needs_input_grad[1] else None), None, dw, db, None
         dpre = torch.empty_like(gy)
         wsb = lib.kgcn_dense_dx_dact_dot_workspace_bytes(m, din)
-        wsp = torch.empty((max(wsb, 4) // 4,), device=gy.device, dtype=torch.float32)
+        wsp = _lib.workspace(wsb, gy.device)
         check(lib.kgcn_dense_dx_dact_dot_f32(ptr(gy), ptr(y), m, dout, dout, ptr(w), dout, din, ptr(x), din, ctx.act, ptr(dpre),
                                              ptr(tab), tb, ready, ptr(deps), ptr(wsp), wsb, current_stream()),
               "kgcn_dense_dx_dact_dot_f32")
@@ -1276,7 +1247,7 @@ class _MaxPool(torch.autograd.Function):
         T, N, d = x.shape
         dx = torch.empty_like(x)
         wsb = lib.kgcn_graph_maxpool_bwd_workspace_bytes(T, adj.n_nodes, d)
-        wsp = torch.empty((max(wsb, 4) // 4,), device=x.device, dtype=torch.float32)
+        wsp = _lib.workspace(wsb, x.device)
         for c, ch in enumerate(adj.channels):
             check(lib.kgcn_graph_maxpool_bwd_f32(ch.desc(), ch.transpose().desc(), ptr(x), ptr(g), d, ptr(dx),
                                                  0.0 if c == 0 else 1.0, ptr(wsp), wsb, current_stream()),
@@ -1303,7 +1274,7 @@ class _Gat(torch.autograd.Function):
             raise _lib.KgcnHipError("one weight_a [2*%d, 1] per adjacency channel is required" % d)
         out = torch.empty_like(x)
         wsb = lib.kgcn_gat_workspace_bytes(T, N, d)
-        ws = torch.empty((max(wsb, 4) // 4,), device=x.device, dtype=torch.float32)
+        ws = _lib.workspace(wsb, x.device)
         for c, ch in enumerate(adj.channels):
             check(lib.kgcn_gat_fwd_f32(ch.desc(), ptr(x), d, ptr(was[c]), ptr(out), 0.0 if c == 0 else 1.0, ptr(ws), wsb,
                                        current_stream()), "kgcn_gat_fwd_f32")
@@ -1319,7 +1290,7 @@ class _Gat(torch.autograd.Function):
         T, N, d = x.shape
         dx = torch.empty_like(x)
         wsb = lib.kgcn_gat_workspace_bytes(T, N, d)
-        ws = torch.empty((max(wsb, 4) // 4,), device=x.device, dtype=torch.float32)
+        ws = _lib.workspace(wsb, x.device)
         dws = []
         for c, ch in enumerate(adj.channels):
             dw = torch.empty(2 * d, device=x.device, dtype=torch.float32)
@@ -1359,7 +1330,7 @@ class _Gram(torch.autograd.Function):
         dx = torch.empty_like(x)
         dw = torch.empty(d, device=x.device, dtype=torch.float32) if ctx.has_w else None
         wsb = lib.kgcn_gram_workspace_bytes(d)
-        ws = torch.empty((max(wsb, 4) // 4,), device=x.device, dtype=torch.float32)
+        ws = _lib.workspace(wsb, x.device)
         check(lib.kgcn_gram_bwd_f32(ptr(x), T, N, d, ptr(wv) if ctx.has_w else 0, ptr(g), ptr(dx), 0.0,
                                     ptr(dw) if ctx.has_w else 0, ptr(ws), wsb, current_stream()), "kgcn_gram_bwd_f32")
         return dx, (dw.reshape(ctx.w_shape) if ctx.has_w else None)
@@ -1456,7 +1427,7 @@ class _RaggedGather(torch.autograd.Function):
         d = ctx.shape[-1]
         dx = torch.empty(ctx.shape, device=g.device, dtype=torch.float32)
         wsb = lib.kgcn_ragged_gather_bwd_workspace_bytes(d)
-        ws = torch.empty((wsb // 4,), device=g.device, dtype=torch.float32)
+        ws = _lib.workspace(wsb, g.device)
         check(lib.kgcn_ragged_gather_bwd_f32(ptr(g), ptr(rb.graph_ptr), rb.num_graphs, rb.n_nodes, d, rb.pad_row, rb.capacity,
                                              ptr(dx), ptr(ws), wsb, current_stream()), "kgcn_ragged_gather_bwd_f32")
         return dx, None
@@ -1542,9 +1513,7 @@ class _GcnStack(torch.autograd.Function):
         ctx.param_none = [p is None for p in params]
         ctx.param_shapes = [None if p is None else tuple(p.shape) for p in params]
         # (the gradients are views of ONE buffer nothing reads inside the pass: its second stage may wait -- see deferred_reductions)
-        ctx.defer_ok = all(p is None or p.is_leaf for p in params)
-        ctx.defer_ids = tuple(params)
-        _count_use(*params)
+        _record_params(ctx, *params)
         return pooled if gather else outs[-1]
 
     @staticmethod
@@ -1563,12 +1532,10 @@ class _GcnStack(torch.autograd.Function):
         dparams = torch.empty((n,), device=g.device, dtype=torch.float32)
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         wsb = lib.kgcn_gcn_stack_bwd_workspace_bytes(x.shape[0], arr, len(spec))
-        ws = torch.empty((max(wsb, 4) // 4,), device=g.device, dtype=torch.float32)
-        with _no_deferral_unless(ctx.defer_ok and _single_use(*ctx.defer_ids)):
+        with _param_grad_stage(ctx, wsb, g.device) as ws:
             check(lib.kgcn_gcn_stack_bwd_f32(ctx.csr.transpose().desc(), ptr(x), ptr(ctx.enabled), arr, len(spec), optr, ptr(g),
                                              1 if ctx.gather else 0, ptr(dx), ptr(dparams), ptr(ws), wsb, current_stream()),
                   "kgcn_gcn_stack_bwd_f32")
-            _keep_until_flush(ws)
         grads, off = [], 0
         for l, (kind, act, din, dout, eps) in enumerate(spec):
             nw = dout if kind == 2 else din * dout
@@ -1683,7 +1650,7 @@ class _MaskedCE(torch.autograd.Function):
         dlog = torch.empty_like(x)
         sums = torch.empty((2,), device=x.device, dtype=torch.float32)
         wsb = lib.kgcn_loss_workspace_bytes(B)
-        ws = torch.empty((max(wsb, 4) // 4,), device=x.device, dtype=torch.float32)
+        ws = _lib.workspace(wsb, x.device)
         if kind == "sigmoid":
             # info.pos_weight of the reference is one weight per label column (kgcn/data_util.py:563-568, consumed by
             # example_model/model_multitask.py:72-76); a scalar is accepted too and applies to every task
@@ -1717,7 +1684,7 @@ class _SparseCE(torch.autograd.Function):
         dlog = torch.empty_like(x)
         sums = torch.empty((2,), device=x.device, dtype=torch.float32)
         wsb = lib.kgcn_loss_workspace_bytes(B)
-        ws = torch.empty((max(wsb, 4) // 4,), device=x.device, dtype=torch.float32)
+        ws = _lib.workspace(wsb, x.device)
         check(lib.kgcn_sparse_softmax_ce_f32(ptr(x), ptr(idx), None, B, W, None, ptr(dlog), ptr(sums), ptr(ws), wsb,
                                              current_stream()), "kgcn_sparse_softmax_ce_f32")
         ctx.save_for_backward(dlog)
@@ -1761,7 +1728,7 @@ def graph_bn_stats(x, enabled=None):
     mean = torch.empty((D,), device=x.device, dtype=torch.float32)
     var = torch.empty_like(mean)
     wsb = lib.kgcn_graph_bn_workspace_bytes(D)
-    wsp = torch.empty((wsb // 4 + 1,), device=x.device, dtype=torch.float32)
+    wsp = _lib.workspace(wsb, x.device)
     check(lib.kgcn_graph_bn_stats_f32(ptr(x), T, N, D, ptr(enabled), ptr(mean), ptr(var), ptr(wsp), wsb,
                                       current_stream()), "kgcn_graph_bn_stats_f32")
     return mean, var
@@ -1773,9 +1740,7 @@ class _GraphBN(torch.autograd.Function):
         x = _f32c(x, "inputs")
         T, N, D = x.shape
         # learning phase 0: d gamma / d beta are not read inside the backward call (the C side queues their second stage in a deferral scope)
-        ctx.defer_ok = bool(not training and gamma.is_leaf and beta.is_leaf)
-        ctx.defer_ids = (gamma, beta)
-        _count_use(gamma, beta)
+        _record_params(ctx, gamma, beta, when=not training)
         gamma, beta = _f32c(gamma, "gamma"), _f32c(beta, "beta")
         y = torch.empty_like(x)
         check(lib.kgcn_graph_bn_apply_act_f32(ptr(x), T, N, D, ptr(enabled), ptr(mean), ptr(var), ptr(gamma), ptr(beta),
@@ -1793,20 +1758,14 @@ class _GraphBN(torch.autograd.Function):
         dgamma = torch.empty((D,), device=x.device, dtype=torch.float32)
         dbeta = torch.empty_like(dgamma)
         wsb = lib.kgcn_graph_bn_workspace_bytes(D)
-        wsp = torch.empty((wsb // 4 + 1,), device=x.device, dtype=torch.float32)
-        # d gamma / d beta receive their second stage at the flush: both must still be alive then.  autograd drops the
-        # gradient of an input that does not require one as soon as backward returns (frozen affine parameters, a
-        # detached gamma of the inference call), so deferral needs BOTH to be wanted: AccumulateGrad then takes the two
-        # tensors themselves as .grad (deferred_reductions excludes parameters whose .grad exists or that carry hooks).
-        # They must NOT be referenced from here as well: a second reference makes AccumulateGrad clone them -- before the
-        # flush has written them (and costs two copy launches per step).
-        want_affine = bool(ctx.needs_input_grad[1] and ctx.needs_input_grad[2])
-        with _no_deferral_unless(ctx.defer_ok and want_affine and dx is not None and _single_use(*ctx.defer_ids)):
+        # d gamma / d beta receive their second stage at the flush: AccumulateGrad must take the two tensors themselves as
+        # .grad.  They must NOT be referenced from here as well: a second reference makes AccumulateGrad clone them -- before
+        # the flush has written them (and costs two copy launches per step).
+        with _param_grad_stage(ctx, wsb, x.device, when=dx is not None) as wsp:
             check(lib.kgcn_graph_bn_bwd_dact_f32(ptr(x), ptr(g), ptr(yact) if ctx.act else None, ctx.act, T, N, D,
                                                  ptr(ctx.enabled), ptr(mean), ptr(var), ptr(gamma), ctx.eps, int(ctx.training),
                                                  ptr(dx), ptr(dgamma), ptr(dbeta), ptr(wsp), wsb, current_stream()),
                   "kgcn_graph_bn_bwd_dact_f32")
-            _keep_until_flush(wsp)
         return dx, dgamma, dbeta, None, None, None, None, None, None
 
 
@@ -1933,9 +1892,7 @@ class _VaeRecon(torch.autograd.Function):
                                          ptr(per_graph), ptr(sums), current_stream()), "kgcn_vae_recon_fwd_f32")
         ctx.adj, ctx.C, ctx.has_kl = adj, C, kl is not None
         ctx.w_shapes = [tuple(t.shape) for t in yw[C:]]
-        ctx.defer_ok = all(t.is_leaf for t in yw[C:])
-        ctx.defer_ids = tuple(yw[C:])
-        _count_use(*yw[C:])
+        _record_params(ctx, *yw[C:])
         ctx.save_for_backward(xf, tf, mk if mk is not None else xf.new_empty(0), *ys, *ws)
         ctx.has_mask = mk is not None
         ctx.set_materialize_grads(False)
@@ -1958,13 +1915,11 @@ class _VaeRecon(torch.autograd.Function):
         dxf = torch.empty_like(xf)
         dkl = torch.empty((B,), device=xf.device, dtype=torch.float32) if (ctx.has_kl and go is not None) else None
         wsb = lib.kgcn_vae_recon_workspace_bytes(B, C, D)
-        wsp = torch.empty((max(wsb, 4) // 4,), device=xf.device, dtype=torch.float32)
-        with _no_deferral_unless(ctx.defer_ok and _single_use(*ctx.defer_ids)):
+        with _param_grad_stage(ctx, wsb, xf.device) as wsp:
             check(lib.kgcn_vae_recon_bwd_f32(_vae_adj(ctx.adj, C, B, N), C, _ptr_array(ys), _ptr_array(ws), D, ptr(xf), ptr(tf), F,
                                              ptr(mk) if ctx.has_mask else None, ptr(go), ptr(gs), _ptr_array(dys),
                                              _ptr_array(dws), ptr(dxf), ptr(dkl), ptr(wsp), wsb, current_stream()),
                   "kgcn_vae_recon_bwd_f32")
-        _keep_until_flush(wsp)
         return (None, None, None, dkl, dxf) + tuple(dys) + tuple(dw.view(s) for dw, s in zip(dws, ctx.w_shapes))
 
 
@@ -2020,9 +1975,7 @@ class _SeqConvPool(torch.autograd.Function):
         if train:
             ctx.save_for_backward(tokens, table, w, arg)
             ctx.pool, ctx.bias_shape = int(pool), tuple(bias.shape)
-            ctx.defer_ok = all(t.is_leaf for t in (table, w, bias))
-            ctx.defer_ids = (table, w, bias)
-            _count_use(table, w, bias)
+            _record_params(ctx, table, w, bias)
         ctx.set_materialize_grads(False)
         return out
 
@@ -2038,11 +1991,9 @@ class _SeqConvPool(torch.autograd.Function):
         dtable, dw = torch.empty_like(table), torch.empty_like(w)
         db = torch.empty((F,), device=w.device, dtype=torch.float32)
         wsb = lib.kgcn_seq_convpool_workspace_bytes(B, L, S, E, k, F, ctx.pool)
-        wsp = torch.empty((max(wsb, 4) // 4,), device=w.device, dtype=torch.float32)
-        with _no_deferral_unless(ctx.defer_ok and _single_use(*ctx.defer_ids)):
+        with _param_grad_stage(ctx, wsb, w.device) as wsp:
             check(lib.kgcn_seq_convpool_bwd_f32(ptr(tokens), B, L, ptr(table), S, E, ptr(w), k, F, ctx.pool, ptr(g), ptr(arg), ptr(dtable),
                                                 ptr(dw), ptr(db), ptr(wsp), wsb, current_stream()), "kgcn_seq_convpool_bwd_f32")
-        _keep_until_flush(wsp)
         n = ctx.needs_input_grad
         return None, dtable if n[1] else None, dw if n[2] else None, db.view(ctx.bias_shape) if n[3] else None, None
 
@@ -2080,9 +2031,7 @@ class _SeqLSTM(torch.autograd.Function):
         if train:
             ctx.save_for_backward(x, wx, wh, b, stash)
             ctx.act, ctx.bias_shape, ctx.used = act, tuple(bias.shape), False
-            ctx.defer_ok = all(t.is_leaf for t in (wx, wh, bias))
-            ctx.defer_ids = (wx, wh, bias)
-            _count_use(wx, wh, bias)
+            _record_params(ctx, wx, wh, bias)
         ctx.set_materialize_grads(False)
         return h
 
@@ -2105,12 +2054,9 @@ class _SeqLSTM(torch.autograd.Function):
         dwh = torch.empty_like(wh) if need_w else None
         db = torch.empty((4 * H,), device=x.device, dtype=torch.float32) if need_w else None
         wsb = lib.kgcn_seq_lstm_workspace_bytes(B, T, D, H) if need_w else 0
-        wsp = torch.empty((max(wsb, 4) // 4,), device=x.device, dtype=torch.float32) if need_w else None
-        with _no_deferral_unless(ctx.defer_ok and _single_use(*ctx.defer_ids)):
+        with _param_grad_stage(ctx, wsb, x.device) as wsp:
             check(lib.kgcn_seq_lstm_bwd_f32(ptr(x), B, T, D, ptr(wx), ptr(wh), ptr(b), H, ctx.act, g.data_ptr(), g.stride(0), ptr(stash),
                                             ptr(dx), ptr(dwx), ptr(dwh), ptr(db), ptr(wsp), wsb, current_stream()), "kgcn_seq_lstm_bwd_f32")
-        if need_w:
-            _keep_until_flush(wsp)
         return (dx, dwx if n[1] else None, dwh if n[2] else None, db.view(ctx.bias_shape) if n[3] else None, None, None, None)
 
 
@@ -2250,10 +2196,7 @@ class _LinkPredLoss(torch.autograd.Function):
                                         negatives.shape[0], int(seed) & (2 ** 64 - 1), ptr(step), ptr(rows), ptr(s1), ptr(s2),
                                         ptr(sums), current_stream()), "kgcn_linkpred_fwd_f32")
         ctx.mode, ctx.L, ctx.has_w = mode, L, wc is not None
-        ctx.defer_ok = w is not None and w.is_leaf
-        ctx.defer_ids = (w,) if w is not None else ()
-        if w is not None:
-            _count_use(w)
+        _record_params(ctx, w)
         ctx.save_for_backward(h, wc if wc is not None else h.new_empty(0), rows, s1, s2, sums)
         correct = sums[2]
         ctx.mark_non_differentiable(correct, s1, s2, rows)
@@ -2272,12 +2215,10 @@ class _LinkPredLoss(torch.autograd.Function):
         dh = torch.empty_like(h)
         dw = torch.empty_like(wc) if ctx.has_w else None
         wsb = lib.kgcn_linkpred_workspace_bytes(N, D, R, ctx.mode, ctx.L)
-        wsp = torch.empty((max(wsb, 4) // 4,), device=h.device, dtype=torch.float32)
-        with _no_deferral_unless(ctx.defer_ok and _single_use(*ctx.defer_ids)):
+        with _param_grad_stage(ctx, wsb, h.device) as wsp:
             check(lib.kgcn_linkpred_bwd_f32(ptr(h), N, D, ptr(wc) if ctx.has_w else None, R, ctx.mode, ptr(rows), ptr(s1), ptr(s2),
                                             ptr(sums), ctx.L, ptr(go), ptr(gs), ptr(dh), ptr(dw), ptr(wsp), wsb, current_stream()),
                   "kgcn_linkpred_bwd_f32")
-        _keep_until_flush(wsp)
         return None, None, None, None, None, None, None, dh, dw
 
 

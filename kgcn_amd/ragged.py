@@ -164,7 +164,7 @@ def compact(features, adj, enabled_node_nums, capacity=None, check=True):
         raise ValueError("batch holds %d valid rows, capacity %d needs one more for the padding representative" % (R, capacity))
     i32 = dict(device=dev, dtype=torch.int32)
     graph_ptr = torch.empty(B + 1, **i32)
-    ws = torch.empty(max(_lib.lib.kgcn_ragged_workspace_bytes(B), 8) // 4, **i32)
+    ws = _lib.workspace(_lib.lib.kgcn_ragged_workspace_bytes(B), dev, torch.int32)
     status = torch.zeros(1, **i32)
     block_ptr = _new_block_ptr(capacity, dev)
     chans = []
@@ -242,7 +242,7 @@ class StaticRaggedBatch:
         self._sel_dev = torch.zeros(B, **i32)
         self._tables, self._ring, self._asm_ws = [], None, None
         self._graph_ptr = torch.zeros(B + 1, **i32)
-        self._ws = torch.empty(max(_lib.lib.kgcn_ragged_workspace_bytes(B), 8) // 4, **i32)
+        self._ws = _lib.workspace(_lib.lib.kgcn_ragged_workspace_bytes(B), dev, torch.int32)
         self.status = torch.zeros(1, **i32)
         self._block_ptr = _new_block_ptr(cap, dev)
         _blocks(self._graph_ptr, B, cap, self._block_ptr)         # an empty batch until load(): padding rows only
@@ -326,7 +326,7 @@ class StaticRaggedBatch:
             plan.num_csr, plan.num_tables = 0, _fill_tables(self, plan, with_features=False)
             if self._asm_ws is None:
                 wsb = _lib.lib.kgcn_batch_assemble_workspace_bytes(B)
-                self._asm_ws = torch.empty(max(wsb, 4) // 4, dtype=torch.int32, device=self._sel_dev.device)
+                self._asm_ws = _lib.workspace(wsb, self._sel_dev.device, torch.int32)
             _lib.check(_lib.lib.kgcn_batch_assemble(plan, self._sel_dev.data_ptr(), B, self._asm_ws.data_ptr(),
                                                     self._asm_ws.numel() * 4, _lib.current_stream()), "kgcn_batch_assemble")
         return self

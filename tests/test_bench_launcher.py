@@ -67,7 +67,13 @@ def test_bench_without_a_gpu_fails_inside_the_spawned_ranks():
     import torch
     if torch.cuda.is_available():
         pytest.skip("a GPU is present: the real path runs instead")
-    r = _run("--gpus", "2", "--steps", "1", "--warmup", "0")
+    # torch.distributed.run tears the other ranks down as soon as it sees the first one fail (every 0.1 s by default): on a busy
+    # machine rank 1 could be killed while still importing torch, before it reached its own check.  Polling every 10 s lets both
+    # ranks reach it (PET_MONITOR_INTERVAL is the launcher's --monitor-interval; bench.py's launch command does not set it).
+    env = _clean_env()
+    env["PET_MONITOR_INTERVAL"] = "10"
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "1", "--warmup", "0"], env=env, stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE, text=True, timeout=240, cwd=ROOT)
     assert r.returncode != 0
     assert "rank 0 of 2" in r.stderr and "rank 1 of 2" in r.stderr and "needs a GPU" in r.stderr
     assert "the 2-rank launch failed" in r.stderr

@@ -285,7 +285,8 @@ def test_deferred_second_stages_leave_every_gradient_unchanged(kind):
     """ops.deferred_reductions (one second-stage launch per training step) must be invisible: every parameter gradient of a
     backward pass inside the block is BIT-equal to the one taken without deferral -- also where a gradient is read inside the
     pass (batch normalisation's d gamma / d beta enter its dx; the concatenated kernels of a multi-channel GraphConv are sliced
-    by autograd; the ragged multitask model uses its last dense layer twice)."""
+    by autograd; the ragged multitask model uses its last dense layer twice) -- and under backward(create_graph=True), where grad
+    mode is on inside the pass and AccumulateGrad copies each gradient before the flush could have written it."""
     from kgcn_amd import data_util as D, models, ops
     torch.manual_seed(3)
     if kind == "multitask-ragged":
@@ -306,24 +307,28 @@ def test_deferred_second_stages_leave_every_gradient_unchanged(kind):
         adj0, x0 = ds.batch(np.arange(30), 30)
         kw = {}
 
-    def grads(defer):
+    def grads(defer, create_graph=False):
         for p in model.parameters():
             p.grad = None
         ops.weight_tables.refresh()
         cost = loss(model(x0, adj0, **kw))
         if defer:
             with ops.deferred_reductions():
-                cost.backward()
+                cost.backward(create_graph=create_graph)
         else:
             cost.backward()
         torch.cuda.synchronize()
-        return [(n, p.grad.clone()) for n, p in model.named_parameters()]
+        return [(n, p.grad.detach().clone()) for n, p in model.named_parameters()]
 
     grads(False)
     for trial in range(3):
         plain, waited = grads(False), grads(True)
         for (n, a), (_, b) in zip(plain, waited):
             assert torch.equal(a, b), (kind, trial, n, float((a - b).abs().max()))
+    for (n, a), (_, b) in zip(plain, grads(True, create_graph=True)):
+        assert torch.equal(a, b), (kind, "create_graph", n, float((a - b).abs().max()))
+    for p in model.parameters():
+        p.grad = None                                 # (create_graph: each .grad holds a reference to its parameter's graph)
 
 
 def _grads_with_and_without_deferral(params, make_loss):

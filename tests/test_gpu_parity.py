@@ -783,56 +783,111 @@ def test_graph_batch_normalization_fused_activation(act, phase):
     close(layer.beta.grad, dbeta, rel=1e-5, atol=1e-4, what="dbeta")
 
 
-@pytest.mark.parametrize("frozen", ["gamma", "both"])
+def _op_with_frozen_params(case, rng):
+    """One op whose backward writes parameter gradients through the deferrable second stage, with a frozen parameter ->
+    (forward() -> (cost, leaves whose gradients are compared), floats of a gradient autograd drops, check(grads) or None)."""
+    from kgcn_amd import BatchedCSR, layers, ops
+    from kgcn_amd.batched_csr import as_batched_adjacency
+    if case in ("gamma", "both"):                           # inference-mode batch normalisation
+        T, N, D = 64, 10, 50
+        x = rng.standard_normal((T, N, D)).astype(np.float32)
+        g = rng.standard_normal((T, N, D)).astype(np.float32)
+        en = rng.integers(0, N + 1, T).astype(np.int32)
+        layer = layers.GraphBatchNormalization(learning_phase=0)
+        layer.build(x.shape, dev())
+        with torch.no_grad():
+            layer.gamma.copy_(t32(rng.uniform(0.5, 1.5, D).astype(np.float32)))
+            layer.moving_variance.copy_(t32(rng.uniform(0.5, 2.0, D).astype(np.float32)))
+        layer.gamma.requires_grad_(False)
+        if case == "both":
+            layer.beta.requires_grad_(False)
+        ten = torch.from_numpy(en).to(dev())
+
+        def forward():
+            tx = t32(x).requires_grad_(True)
+            return (layer(tx, enabled_node_nums=ten) * t32(g)).sum(), [tx, layer.beta]
+
+        def check(grads):
+            gam = layer.gamma.detach().cpu().numpy()
+            ref_dx = K.graph_bn_bwd(x, gam, layer.moving_mean.cpu().numpy(), layer.moving_variance.cpu().numpy(), g, en,
+                                    training=False)[0]
+            close(grads[0], ref_dx, rel=1e-5, what="dx")
+        return forward, D, check
+    if case == "seq_conv_pool-table":
+        B, L, S, E, k, F = 16, 64, 25, 8, 5, 16
+        tok = torch.as_tensor(rng.integers(0, S, (B, L)).astype(np.int32), device=dev())
+        table = t32(rng.standard_normal((S, E)))
+        w = t32(rng.standard_normal((k, E, F)) * 0.2).requires_grad_(True)
+        b = t32(rng.standard_normal(F) * 0.1).requires_grad_(True)
+        g = t32(rng.standard_normal((B, L // 4, F)))
+        return lambda: ((ops.seq_conv_pool(tok, table, w, b, 4) * g).sum(), [w, b]), S * E, None
+    if case == "seq_lstm-wh":
+        B, T, D, H = 16, 12, 8, 16
+        x = t32(rng.standard_normal((B, T, D)))
+        wx = t32(rng.standard_normal((D, 4 * H)) * 0.2).requires_grad_(True)
+        wh = t32(rng.standard_normal((H, 4 * H)) * 0.2)
+        bias = t32(rng.standard_normal(4 * H) * 0.1).requires_grad_(True)
+        g = t32(rng.standard_normal((B, H)))
+        return lambda: ((ops.seq_lstm(x, wx, wh, bias) * g).sum(), [wx, bias]), H * 4 * H, None
+    if case == "vae_recon-kernel":
+        B, N, D, F = 24, 10, 16, 5
+        adj = as_batched_adjacency(K.synth_mol_graphs(rng, B, N, 3), n_nodes=N, device=dev())
+        y = t32(rng.random((B, N, D))).requires_grad_(True)
+        w = t32(rng.uniform(0.05, 0.3, D))                  # the DistMult kernel
+        xf = t32(rng.standard_normal((B, N, F))).requires_grad_(True)
+        tf = t32(rng.random((B, N, F)) < 0.3)
+        return lambda: (ops.vae_recon(adj, [y], [w], xf, tf)[0], [y, xf]), D, None
+    assert case == "graphconv_fused-w+bias"
+    T, N, din, dout = 64, 32, 64, 64
+    csr = BatchedCSR.from_coo_list([a[0] for a in K.synth_mol_graphs(rng, T, N, 3)], rows=N, cols=N, device=dev())
+    assert ops.graphconv_fused_supported(csr, din, dout)
+    x = rng.standard_normal((T, N, din)).astype(np.float32)
+    w, b = t32(K.glorot_uniform(rng, din, dout)), t32(rng.standard_normal((1, dout)))
+    g = t32(rng.standard_normal((T, N, dout)))
+
+    def forward():
+        tx = t32(x).requires_grad_(True)
+        return (ops.graphconv_fused(tx, w, b, csr) * g).sum(), [tx]
+    return forward, din * dout + dout, None
+
+
+@pytest.mark.parametrize("frozen", ["gamma", "both", "seq_conv_pool-table", "seq_lstm-wh", "vae_recon-kernel", "graphconv_fused-w+bias"])
 def test_inference_bn_backward_with_frozen_affine_inside_a_deferral_scope(frozen):
     """with learning phase 0 the BN backward queues the second stage of d gamma / d beta.  When gamma or
     beta does not require a gradient autograd drops that result as soon as backward() returns, and the flush would add D floats
     into whatever the caching allocator put there next.  The call must not defer then: a canary tensor allocated right after
     the backward (same size class as the dropped gradient) stays untouched by the flush, and dx / the wanted gradient are the
-    ones of the plain call."""
-    from kgcn_amd import layers, ops
-    rng = np.random.default_rng(77)
-    T, N, D = 64, 10, 50
-    x = rng.standard_normal((T, N, D)).astype(np.float32)
-    g = rng.standard_normal((T, N, D)).astype(np.float32)
-    en = rng.integers(0, N + 1, T).astype(np.int32)
-    layer = layers.GraphBatchNormalization(learning_phase=0)
-    layer.build(x.shape, dev())
-    with torch.no_grad():
-        layer.gamma.copy_(t32(rng.uniform(0.5, 1.5, D).astype(np.float32)))
-        layer.moving_variance.copy_(t32(rng.uniform(0.5, 2.0, D).astype(np.float32)))
-    layer.gamma.requires_grad_(False)
-    if frozen == "both":
-        layer.beta.requires_grad_(False)
-    ten = torch.from_numpy(en).to(dev())
+    ones of the plain call.  The same holds for every op that defers parameter gradients (the other cases: a conv-pool with a
+    frozen embedding table, an LSTM with a frozen recurrent kernel, the VAE loss with a frozen DistMult kernel, a fused GraphConv
+    with frozen w and bias)."""
+    from kgcn_amd import ops
+    forward, n, check = _op_with_frozen_params(frozen, np.random.default_rng(77))
 
     def run(defer):
-        layer.beta.grad = None
-        tx = t32(x).requires_grad_(True)
-        y = layer(tx, enabled_node_nums=ten)
-        cost = (y * t32(g)).sum()
+        ops.weight_tables.refresh()                         # a training step begins: parameter uses are counted afresh
+        cost, leaves = forward()
+        for t in leaves:
+            t.grad = None
         if defer:
             with ops.deferred_reductions(root=cost):
                 cost.backward()
-                canaries = [torch.full((D,), 7.0, device=dev()) for _ in range(8)]
-                assert ops.lib.kgcn_reduce_pending() == 0, "the BN backward deferred a gradient nobody keeps"
+                canaries = [torch.full((n,), 7.0, device=dev()) for _ in range(8)]
+                assert ops.lib.kgcn_reduce_pending() == 0, "%s: the backward deferred a gradient nobody keeps" % frozen
             torch.cuda.synchronize()
             for c in canaries:
                 assert bool((c == 7.0).all())
         else:
             cost.backward()
         torch.cuda.synchronize()
-        return tx.grad.clone(), None if layer.beta.grad is None else layer.beta.grad.clone()
+        for t in leaves:
+            assert (t.grad is None) == (not t.requires_grad)
+        return [None if t.grad is None else t.grad.clone() for t in leaves]
 
-    dx0, db0 = run(False)
-    dx1, db1 = run(True)
-    assert torch.equal(dx0, dx1)
-    assert (db0 is None) == (db1 is None) == (frozen == "both")
-    if db0 is not None:
-        assert torch.equal(db0, db1)
-    gam = layer.gamma.detach().cpu().numpy()
-    ref_dx = K.graph_bn_bwd(x, gam, layer.moving_mean.cpu().numpy(), layer.moving_variance.cpu().numpy(), g, en, training=False)[0]
-    close(dx1, ref_dx, rel=1e-5, what="dx")
+    plain, waited = run(False), run(True)
+    for a, b in zip(plain, waited):
+        assert (a is None) == (b is None) and (a is None or torch.equal(a, b))
+    if check is not None:
+        check(waited)
 
 
 @pytest.mark.parametrize("channels,D", [("plain", 3), ("split", 50), ("norm", 64)])
