@@ -74,12 +74,29 @@ extern "C" {
  * Knowledge-graph link prediction added entry points only (version still 2): kgcn_linkpred_fwd_f32 / kgcn_linkpred_bwd_f32
  * (+ kgcn_linkpred_workspace_bytes).
  * Integrated gradients of the multimodal model added entry points only (version still 2): kgcn_seq_convpool_scaled_fwd_f32,
- * kgcn_seq_convpool_input_grad_f32. */
+ * kgcn_seq_convpool_input_grad_f32.
+ * The compact row-padded adjacency (row_pad == KGCN_ROW_PAD_COMPACT) added a layout CODE and entry points only (version
+ * still 2): a library without it refuses that code in every entry point (validate_csr accepts row_pad 0 and 4 only), so
+ * an old library never misreads it; kgcn_csr_compact4 is the feature query (look it up before building such a batch). */
 #define KGCN_HIP_ABI_VERSION 2
 
 /* Column index of the padding entries of a row-padded batch (see row_pad): they carry value 0 and
  * gather an all-zero row the fused kernels keep in LDS, so they contribute exactly 0 (never 0*inf). */
 #define KGCN_PAD_COL 32
+
+/* row_pad code of the COMPACT row-padded layout (kgcn_csr_compact4): the structure of row_pad = 4 -- same rows, same
+ * entries in the same order, padding to multiples of 4 with column KGCN_PAD_COL, same graph_ptr -- in fewer bytes:
+ *   cv       [nnz / 4] uint32 column words: entry e's column is byte (e & 3) of word e >> 2 (one 4-entry group = one
+ *            word), followed -- unless reserved_ & KGCN_CSR_UNIT_VALUES -- by the value stream: [nnz] fp32 bits starting
+ *            at 32-bit word kgcn_compact_values_offset(nnz) of cv (16-byte aligned), 0.0 for padding entries
+ *   slots    [T*M] uint16 (the pointer is cast): per graph its M rows by decreasing length (the order of row_pad = 4),
+ *            slot = (first group of the row inside the graph, < 128) | (group count << 7, 1..15) | (row << 11)
+ *   rowptr   [T*M + 1] and graph_ptr [T + 1] as in row_pad = 4 (in entries)
+ * Only the FULL-shape fused kernels read it (kgcn_graphconv_fused_reads_compact); every other entry point refuses it. */
+#define KGCN_ROW_PAD_COMPACT 0x104
+/* reserved_ flag of a compact batch: every stored (non-padding) value is exactly 1.0f, no value stream is stored and the
+ * kernels add the gathered rows instead of multiplying them (fma(1, x, a) == a + x bit for bit). */
+#define KGCN_CSR_UNIT_VALUES 1
 
 /* Non-finite inputs, per route (see "Conventions").  bf16 x 3 (fused GraphConv kernels, route 2): p1 + p2 + p3 == x bit for
  * bit for finite x; +-inf splits into (inf, NaN, NaN) and NaN into (NaN, NaN, NaN).  f16 x 2 (wide-layer GEMMs, route 3): a
@@ -99,7 +116,7 @@ typedef struct kgcn_csr_batch {
                                 padded with (col = KGCN_PAD_COL, value = 0) -- the layout the fused
                                 GraphConv kernels read (mask-free 4-entry gathers); only those
                                 kernels accept it */
-  int32_t reserved_;
+  int32_t reserved_;         /* 0, or KGCN_CSR_UNIT_VALUES for a compact batch (row_pad == KGCN_ROW_PAD_COMPACT) */
   int64_t nnz;               /* total stored entries (including padding entries) */
   const int32_t* rowptr;     /* device, [T*M + 1], absolute offsets into cv (in entries) */
   const int32_t* cv;         /* device, [2*nnz], interleaved (local col, fp32 value bits) */
@@ -185,7 +202,8 @@ int kgcn_dense_wgrad_f32(const float* x, int64_t x_ld, const float* dy, int64_t 
  * Forward in ONE kernel (x tile -> LDS, fp32 MFMA, aggregation out of LDS; X.W never touches
  * HBM).  Supported fused shapes are reported by kgcn_graphconv_fused_supported(); other
  * shapes and multi-channel layers use kgcn_dense_* + kgcn_bconv_f32. */
-/* a / at of the fused entry points must be row-padded batches (row_pad == 4). */
+/* a / at of the fused entry points must be row-padded batches (row_pad == 4), or compact ones (KGCN_ROW_PAD_COMPACT)
+ * where kgcn_graphconv_fused_reads_compact says the selected kernel reads them; any other combination is refused. */
 int kgcn_graphconv_fused_supported(int32_t n_nodes, int32_t din, int32_t dout,
                                    int32_t max_nnz_per_graph);
 int kgcn_graphconv_fwd_f32(const kgcn_csr_batch* a, const float* x, const float* w,
@@ -493,6 +511,19 @@ int64_t kgcn_csr_pad4_workspace_bytes(int32_t num_graphs, int32_t rows);
 int kgcn_csr_pad4(const kgcn_csr_batch* a, int32_t* rowptr4_out, void* cv4_out, int64_t cv4_capacity,
                   int32_t* slots_out, int32_t* graph_ptr_out, int32_t* stats_out, void* workspace,
                   int64_t workspace_bytes, void* stream);
+/* row-padded container (row_pad = 4) -> the compact layout (KGCN_ROW_PAD_COMPACT, see there) of the same batch:
+ * cv_out [kgcn_compact_cv_words(nnz, with_values) uint32], slots_out [T*M] uint16 (rowptr / graph_ptr are shared with
+ * the source).  with_values = 0 writes no value stream.  stats_out: device int32[2] = {stored entries whose value is not
+ * exactly 1.0f (padding excluded; 0 means KGCN_CSR_UNIT_VALUES applies), number of rows the 16-bit slot cannot hold (a
+ * graph of more than 127 groups or a row of more than 15; must be 0 to use the result)}. */
+int64_t kgcn_compact_values_offset(int64_t nnz);
+int64_t kgcn_compact_cv_words(int64_t nnz, int32_t with_values);
+int kgcn_csr_compact4(const kgcn_csr_batch* a4, void* cv_out, int with_values, void* slots_out, int32_t* stats_out,
+                      void* stream);
+/* 1 if the fused GraphConv launcher, for these arguments, selects a kernel that reads the compact layout (the FULL
+ * forward; the pairs backward with dx), else 0.  backward: 0 forward, 1 backward; max_nnz of the row-padded batch. */
+int kgcn_graphconv_fused_reads_compact(int32_t backward, int32_t num_graphs, int32_t n_nodes, int32_t din, int32_t dout,
+                                       int32_t max_nnz_per_graph, int32_t with_dx);
 
 /* -- ragged-compact batches: the layer stack on the VALID node rows only ------------------------------------------------ */
 /* The reference pads every graph to max_node_num rows (kgcn/data_util.py:30-37, feed.py:127-133); its ragged layers

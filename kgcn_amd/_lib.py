@@ -199,6 +199,10 @@ SIGNATURES = {
     "kgcn_coo_pack_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32]),
     "kgcn_coo_pack_f32": (ctypes.c_int, [c_i32p, c_i32p, c_i32p, c_f32p, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32p,
                                          ctypes.c_void_p, c_i32p, c_i32p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
+    "kgcn_compact_values_offset": (c_i64, [c_i64]),
+    "kgcn_compact_cv_words": (c_i64, [c_i64, c_i32]),
+    "kgcn_csr_compact4": (ctypes.c_int, [_CSRP, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, c_i32p, ctypes.c_void_p]),
+    "kgcn_graphconv_fused_reads_compact": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32]),
     "kgcn_csr_pad4_workspace_bytes": (c_i64, [c_i32, c_i32]),
     "kgcn_csr_pad4": (ctypes.c_int, [_CSRP, c_i32p, ctypes.c_void_p, c_i64, c_i32p, c_i32p, c_i32p, ctypes.c_void_p,
                                      c_i64, ctypes.c_void_p]),

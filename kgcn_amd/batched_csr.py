@@ -91,6 +91,8 @@ class BatchedCSR:
     """One adjacency channel of a batch of T graphs, device resident."""
 
     PAD_COL = 32        # KGCN_PAD_COL of include/kgcn_hip.h
+    ROW_PAD_COMPACT = 0x104     # KGCN_ROW_PAD_COMPACT
+    UNIT_VALUES = 1             # KGCN_CSR_UNIT_VALUES
 
     def __init__(self, rowptr, cv, num_graphs, rows, cols, max_nnz, perm=None, host=None,
                  row_pad=0):
@@ -109,6 +111,7 @@ class BatchedCSR:
         self._vals = None
         self.row_pad = int(row_pad)     # 0 plain CSR, 4 = rows padded to multiples of 4 entries
         self._p4 = None
+        self._c4 = None                 # row_pad == 4: cache of compact4() (False: the batch does not fit the compact slot)
         self._make_t = None             # thunks set by gather(): build A^T / the padded copy on demand
         self._make_p4 = None
         self._graph_counts = None       # host int64 [T]: stored entries per graph
@@ -354,6 +357,22 @@ class BatchedCSR:
             self._p4._graph_counts = np.diff(gptr).astype(np.int64)
         return self._p4
 
+    def compact4(self, build=True):
+        """Compact copy of padded4() for the FULL-shape fused kernels (kgcn_csr_batch.row_pad = KGCN_ROW_PAD_COMPACT,
+        include/kgcn_hip.h): the same rows, entries and padding, with one byte per column, a value stream only when
+        some stored value is not 1.0f and 16-bit row slots.  Built on the device (kgcn_csr_compact4) once per batch
+        and cached on the row-padded container; the build reads two counters back to the host.  Returns a
+        CompactCSR, or None: the batch does not fit the 16-bit slot, the container is refilled in place
+        (static_like(): a copy would go stale), or build=False and nothing is cached yet."""
+        p4 = self.padded4()
+        if p4._refillable or self._refillable:
+            return None
+        if p4._c4 is None:
+            if not build:
+                return None
+            p4._c4 = CompactCSR.build(p4) or False
+        return p4._c4 or None
+
     def graph_counts(self):
         """Host int64 [T]: stored entries per graph (padding entries included for row_pad = 4)."""
         if self._graph_counts is None:
@@ -497,6 +516,50 @@ class BatchedCSR:
     def algorithmic_bytes(self):
         """CSR bytes of SURVEY 8d: 4(N+1) + 8 nnz per graph-channel."""
         return 4 * (self.num_graphs * (self.rows + 1)) + 8 * self.nnz
+
+
+class CompactCSR:
+    """The compact row-padded layout of a row-padded BatchedCSR (BatchedCSR.compact4()); rowptr and graph_ptr are the
+    source's, `cv` holds the column words and, unless unit_values, the value stream."""
+
+    def __init__(self, src, cv, slots, unit_values):
+        self.src = src                  # the row-padded container (owns rowptr / graph_ptr)
+        self.cv = cv                    # int32 [kgcn_compact_cv_words(nnz, not unit_values)]
+        self.slots = slots              # int16 [T*M]
+        self.unit_values = bool(unit_values)
+        self.num_graphs, self.rows, self.cols = src.num_graphs, src.rows, src.cols
+        self.max_nnz, self.nnz = src.max_nnz, src.nnz
+        self._desc = None
+
+    @classmethod
+    def build(cls, p4):
+        """kgcn_csr_compact4 on a row-padded container; None when a row does not fit the 16-bit slot."""
+        import torch
+        lib = _lib.lib
+        T, M, dev = p4.num_graphs, p4.rows, p4.rowptr.device
+        words = max(1, int(lib.kgcn_compact_cv_words(p4.nnz, 1)))
+        cv = torch.zeros(words, device=dev, dtype=torch.int32)
+        slots = torch.empty(max(1, T * M), device=dev, dtype=torch.int16)
+        stats = torch.empty(2, device=dev, dtype=torch.int32)
+        _lib.check(lib.kgcn_csr_compact4(p4.desc(), cv.data_ptr(), 1, slots.data_ptr(), _lib.ptr(stats),
+                                         _lib.current_stream()), "kgcn_csr_compact4")
+        non_unit, bad = (int(x) for x in stats.tolist())
+        if bad:
+            return None
+        if non_unit == 0:                                   # no value stream: the column words alone
+            cv = cv[:max(1, p4.nnz // 4)].clone()
+        return cls(p4, cv, slots, non_unit == 0)
+
+    def desc(self):
+        """ctypes struct kgcn_csr_batch of the compact layout."""
+        if self._desc is None:
+            self._desc = _lib.CsrBatch(self.num_graphs, self.rows, self.cols, self.max_nnz,
+                                       BatchedCSR.ROW_PAD_COMPACT, BatchedCSR.UNIT_VALUES if self.unit_values else 0,
+                                       self.nnz, self.src.rowptr.data_ptr(), self.cv.data_ptr() if self.nnz else 0,
+                                       self.slots.data_ptr() if self.src.slots is not None else 0,
+                                       self.src.graph_ptr.data_ptr() if self.src.graph_ptr is not None else 0,
+                                       0, 0, 0)
+        return self._desc
 
 
 class BatchedAdjacency:

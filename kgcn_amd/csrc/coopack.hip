@@ -140,6 +140,47 @@ __global__ __launch_bounds__(64) void pad_slots_kernel(const int* __restrict__ r
   }
 }
 
+// ---- compact row-padded layout (KGCN_ROW_PAD_COMPACT) ---------------------------------------------------------
+// one thread per 4-entry group: the column word, the four values (with_values), and a count of the stored values that
+// are not exactly 1.0f (one atomic per wave)
+__global__ __launch_bounds__(kPackBlock) void compact_groups_kernel(const int4* __restrict__ cv4, long groups,
+                                                                     unsigned* __restrict__ cw, int4* __restrict__ vals,
+                                                                     int* __restrict__ stats) {
+  const long gi = (long)blockIdx.x * kPackBlock + threadIdx.x;
+  int non_unit = 0;
+  if (gi < groups) {
+    const int4 e0 = cv4[2 * gi], e1 = cv4[2 * gi + 1];      // entries 4gi .. 4gi + 3: (col, value bits) x 4
+    cw[gi] = (unsigned)(e0.x & 0xff) | ((unsigned)(e0.z & 0xff) << 8) | ((unsigned)(e1.x & 0xff) << 16) |
+             ((unsigned)(e1.z & 0xff) << 24);
+    if (vals) vals[gi] = make_int4(e0.y, e0.w, e1.y, e1.w);
+    const int one = 0x3f800000;
+    non_unit = (e0.x != KGCN_PAD_COL && e0.y != one) + (e0.z != KGCN_PAD_COL && e0.w != one) +
+               (e1.x != KGCN_PAD_COL && e1.y != one) + (e1.z != KGCN_PAD_COL && e1.w != one);
+  }
+  const unsigned long long any = __ballot(non_unit != 0);
+  if (any) {
+    for (int off = 32; off > 0; off >>= 1) non_unit += __shfl_xor(non_unit, off, 64);
+    if ((threadIdx.x & 63) == 0) atomicAdd(stats, non_unit);
+  }
+}
+
+// one thread per row slot: the packer's 32-bit slot word -> the 16-bit compact slot
+__global__ __launch_bounds__(kPackBlock) void compact_slots_kernel(const int* __restrict__ slots, long nrows,
+                                                                    unsigned short* __restrict__ slots16,
+                                                                    int* __restrict__ stats) {
+  const long i = (long)blockIdx.x * kPackBlock + threadIdx.x;
+  if (i >= nrows) return;
+  const unsigned u = (unsigned)slots[i];
+  const unsigned off = u & 0xffffu, len = (u >> 16) & 0xffu, row = u >> 24;
+  const unsigned g0 = off >> 2, ng = len >> 2;
+  if ((off & 3u) || (len & 3u) || g0 > 127u || ng < 1u || ng > 15u || row > 31u) {
+    atomicAdd(stats + 1, 1);
+    slots16[i] = 0;
+    return;
+  }
+  slots16[i] = (unsigned short)(g0 | (ng << 7) | (row << 11));
+}
+
 static size_t sort_temp_bytes(long nnz, unsigned bits) {
   size_t b = 0;
   (void)rocprim::radix_sort_pairs(nullptr, b, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (int*)nullptr,
@@ -248,4 +289,30 @@ extern "C" int kgcn_csr_pad4(const kgcn_csr_batch* a, int32_t* rowptr4_out, void
   hipLaunchKernelGGL(pad_slots_kernel, dim3((unsigned)T), dim3(64), 0, s, rowptr4_out, T, M, slots_out, graph_ptr_out,
                      stats_out);
   return check_launch("kgcn_csr_pad4");
+}
+
+extern "C" int kgcn_csr_compact4(const kgcn_csr_batch* a4, void* cv_out, int with_values, void* slots_out,
+                                 int32_t* stats_out, void* stream) {
+  if (int rc = validate_csr(a4, "kgcn_csr_compact4", /*allow_row_pad=*/true)) return rc;
+  if (a4->row_pad != 4) return fail("kgcn_csr_compact4: the source must be row-padded (row_pad = 4), got %d", a4->row_pad);
+  if (a4->rows != a4->cols || a4->rows > KGCN_PAD_COL)
+    return fail("kgcn_csr_compact4: square graphs of at most %d nodes only (M=%d K=%d)", KGCN_PAD_COL, a4->rows, a4->cols);
+  if (a4->nnz & 3) return fail("kgcn_csr_compact4: nnz=%lld is not a multiple of 4", (long long)a4->nnz);
+  const long nrows = (long)a4->num_graphs * a4->rows;
+  if (!stats_out || (a4->nnz > 0 && !cv_out) || (nrows > 0 && (!slots_out || !a4->slots)))
+    return fail("kgcn_csr_compact4: NULL operand");
+  if ((a4->nnz > 0 && !aligned16(a4->cv)) || (with_values && !aligned16(cv_out)))
+    return fail("kgcn_csr_compact4: cv / cv_out not 16-byte aligned");
+  hipStream_t s = as_stream(stream);
+  (void)hipMemsetAsync(stats_out, 0, 2 * sizeof(int32_t), s);
+  const long groups = (long)(a4->nnz / 4);
+  unsigned* cw = static_cast<unsigned*>(cv_out);
+  if (groups > 0)
+    hipLaunchKernelGGL(compact_groups_kernel, dim3((unsigned)((groups + kPackBlock - 1) / kPackBlock)), dim3(kPackBlock), 0, s,
+                       reinterpret_cast<const int4*>(a4->cv), groups, cw,
+                       with_values ? reinterpret_cast<int4*>(cw + kgcn_compact_values_offset(a4->nnz)) : nullptr, stats_out);
+  if (nrows > 0)
+    hipLaunchKernelGGL(compact_slots_kernel, dim3((unsigned)((nrows + kPackBlock - 1) / kPackBlock)), dim3(kPackBlock), 0, s,
+                       a4->slots, nrows, static_cast<unsigned short*>(slots_out), stats_out);
+  return check_launch("kgcn_csr_compact4");
 }

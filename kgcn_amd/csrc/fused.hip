@@ -343,6 +343,149 @@ struct PassSteps {
   }
 };
 
+// ---- compact row-padded layout (KGCN_ROW_PAD_COMPACT, include/kgcn_hip.h) -------------------------------------
+// The FULL kernels are instantiated per adjacency layout: LAY_PAD4 reads (col, value) pairs (row_pad = 4), LAY_UNIT one
+// column word per 4-entry group and no values (every value 1.0f: the gathered rows are ADDED, fma(1, x, a) == a + x bit
+// for bit), LAY_VALS the column word plus the group's four values (one 16-byte read).  Entry order, padding and the order
+// of the sums are those of row_pad = 4, so all three give the same bits.  In LDS the ecv region of a compact slice holds
+// one 16-bit word per entry, the BYTE offset col * FD * 4 of the entry's gather row (entry e -> bytes 2e, 2e + 1; widened
+// at landing by one v_perm_b32 per two entries, so that a gather address is one v_add_u32_sdwa, as cheap as the
+// row-padded layout's v_lshl_add_u32), then the values (LAY_VALS) from byte cvals_off(max_nnz) on; the slot table keeps
+// the packer's 32-bit word (compact_slot_word at landing).
+constexpr int LAY_PAD4 = 0, LAY_UNIT = 1, LAY_VALS = 2;
+__host__ __device__ inline size_t cvals_off(int max_nnz) { return ((size_t)2 * max_nnz + 15) & ~(size_t)15; }
+static_assert(sizeof(int2) == 8, "the compact slice fits the row-padded one: cvals_off(n) + 4 n <= 8 n for n >= 4");
+static_assert(KGCN_PAD_COL * FD * 4 < 65536, "gather-row byte offsets fit 16 bits");
+
+// column word of a group (4 byte-columns) -> the two LDS words of its gather-row byte offsets (col << 8: FD * 4 == 256)
+static_assert(FD * 4 == 256, "col << 8 is the gather-row byte offset");
+__device__ __forceinline__ u32x2 widen_cols(unsigned c) {
+  u32x2 o;
+  o[0] = __builtin_amdgcn_perm(0u, c, 0x010c000cu);      // byte 1 = col 0, byte 3 = col 1, zeros elsewhere
+  o[1] = __builtin_amdgcn_perm(0u, c, 0x030c020cu);      // col 2, col 3
+  return o;
+}
+
+// 16-bit compact slot (group offset | group count << 7 | row << 11) -> the packer's slot word (offset | count << 16 | row << 24)
+__device__ __forceinline__ int compact_slot_word(int v) {
+  const unsigned u = (unsigned)v;
+  return (int)(((u & 127u) << 2) | (((u >> 7) & 15u) << 18) | ((u >> 11) << 24));
+}
+
+// compact slices in flight: lane l holds the column word (and the 4 values) of group l of the graph (the first 256 entries)
+struct CsrRegsC { int c; f32x4 v; };
+template <int LAY>
+__device__ __forceinline__ void issue_cv_c(CsrRegsC& f, const unsigned* __restrict__ cw, const float* __restrict__ cvals,
+                                           int base, int cnt, int lane) {
+  const bool in = 4 * lane < cnt;
+  f.c = in ? (int)cw[(base >> 2) + lane] : 0;
+  if constexpr (LAY == LAY_VALS) {
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    f.v = in ? ldv4(cvals + base + 4 * lane) : z;
+  }
+}
+template <int LAY>
+__device__ __forceinline__ void land_csr_c(const CsrRegsC& f, int2* ecv, int* tab, const unsigned* __restrict__ cw,
+                                           const float* __restrict__ cvals, int max_nnz, int slot_val, int base, int cnt,
+                                           int N, int lane) {
+  u32x2* dc = reinterpret_cast<u32x2*>(ecv);
+  float* dv = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(ecv) + cvals_off(max_nnz));
+  if (4 * lane < cnt) {
+    dc[lane] = widen_cols((unsigned)f.c);
+    if constexpr (LAY == LAY_VALS) stv4(dv + 4 * lane, f.v);
+  }
+  for (int i = 64 + lane; 4 * i < cnt; i += 64) {           // rare: > 256 entries
+    dc[i] = widen_cols(cw[(base >> 2) + i]);
+    if constexpr (LAY == LAY_VALS) stv4(dv + 4 * i, ldv4(cvals + base + 4 * i));
+  }
+  if (lane < N) tab[lane] = slot_val;
+}
+template <int LAY>
+__device__ __forceinline__ void issue_meta_l(MetaRegs& m, const int* __restrict__ slots, const int* __restrict__ gptr, int t,
+                                             int N, int lane) {
+  if constexpr (LAY == LAY_PAD4) {
+    issue_meta(m, slots, gptr, t, N, lane);
+  } else {
+    m.slot = reinterpret_cast<const unsigned short*>(slots)[(long)t * N + (lane < N ? lane : N - 1)];
+    m.gp = gptr[t + (lane & 1)];
+  }
+}
+template <int LAY>
+__device__ __forceinline__ int slot_word_l(int v) {
+  if constexpr (LAY == LAY_PAD4) return v;
+  else return compact_slot_word(v);
+}
+
+// One 4-entry group of a row in the layout LAY: ecv() -> tile() -> fma() leaves its contribution in `a` (PassSteps /
+// PlaneSteps for LAY_PAD4, statement for statement).  ecv_: the graph's ecv region in LDS, ev: its value stream.
+template <int LAY>
+struct Grp4 {
+  i32x4 q0, q1;                 // LAY_PAD4: the four (col, value bits) pairs
+  u32x2 cw;                     // compact: the four gather-row byte offsets, 16 bits each
+  f32x4 v;                      // LAY_VALS: the four values
+  f32x4 x0, x1, x2, x3;
+  f32x4 a;
+  __device__ __forceinline__ void ecv(const int2* ecv_, const float* ev, int s) {
+    if constexpr (LAY == LAY_PAD4) {
+      q0 = *reinterpret_cast<const i32x4*>(ecv_ + s);
+      q1 = *reinterpret_cast<const i32x4*>(ecv_ + s + 2);
+    } else {
+      cw = *reinterpret_cast<const u32x2*>(reinterpret_cast<const unsigned char*>(ecv_) + 2 * s);
+      if constexpr (LAY == LAY_VALS) v = ldv4(ev + s);
+    }
+  }
+  __device__ __forceinline__ void tile(const float* srcl) {
+    if constexpr (LAY == LAY_PAD4) {
+      x0 = ldv4(srcl + q0.x * FD); x1 = ldv4(srcl + q0.z * FD);
+      x2 = ldv4(srcl + q1.x * FD); x3 = ldv4(srcl + q1.z * FD);
+    } else {
+      const unsigned char* sb = reinterpret_cast<const unsigned char*>(srcl);
+      x0 = ldv4(reinterpret_cast<const float*>(sb + (cw[0] & 0xffffu)));
+      x1 = ldv4(reinterpret_cast<const float*>(sb + (cw[0] >> 16)));
+      x2 = ldv4(reinterpret_cast<const float*>(sb + (cw[1] & 0xffffu)));
+      x3 = ldv4(reinterpret_cast<const float*>(sb + (cw[1] >> 16)));
+    }
+  }
+  __device__ __forceinline__ void fma() {
+    if constexpr (LAY == LAY_UNIT) {
+      a = x0;
+      add4(a, x1); add4(a, x2); add4(a, x3);
+    } else {
+      const float v0 = LAY == LAY_PAD4 ? __int_as_float(q0.y) : v[0];
+      a[0] = v0 * x0[0]; a[1] = v0 * x0[1]; a[2] = v0 * x0[2]; a[3] = v0 * x0[3];
+      fma4(a, LAY == LAY_PAD4 ? __int_as_float(q0.w) : v[1], x1);
+      fma4(a, LAY == LAY_PAD4 ? __int_as_float(q1.y) : v[2], x2);
+      fma4(a, LAY == LAY_PAD4 ? __int_as_float(q1.w) : v[3], x3);
+    }
+  }
+};
+// gather4 in the layout LAY (the sum starts from +0, as gather4's does)
+template <int LAY>
+__device__ __forceinline__ f32x4 gather4_l(const int2* ecv, const float* ev, const float* srcl, int k) {
+  if constexpr (LAY == LAY_PAD4) {
+    return gather4(ecv, srcl, k);
+  } else {
+    Grp4<LAY> q;
+    q.ecv(ecv, ev, k);
+    q.tile(srcl);
+    f32x4 a0 = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (LAY == LAY_UNIT) {
+      add4(a0, q.x0); add4(a0, q.x1); add4(a0, q.x2); add4(a0, q.x3);
+    } else {
+      fma4(a0, q.v[0], q.x0); fma4(a0, q.v[1], q.x1); fma4(a0, q.v[2], q.x2); fma4(a0, q.v[3], q.x3);
+    }
+    return a0;
+  }
+}
+// rows longer than 4 entries (PassSteps::tail)
+template <int LAY>
+__device__ __forceinline__ void grp_tail(f32x4& a, int s, int len, const int2* ecv, const float* ev, const float* srcl) {
+  if (__builtin_amdgcn_ballot_w64(len > 4)) {
+    for (int k = 4; __builtin_amdgcn_ballot_w64(k < len); k += 4)
+      if (k < len) add4(a, gather4_l<LAY>(ecv, ev, srcl, s + k));
+  }
+}
+
 // Sparse aggregation of one graph out of a gather tile (row stride FD) without MFMA overlap: lane
 // (sub, cl) produces the float4 [4cl, 4cl+4) of the rows of slots j = 4p + sub.
 // emit(row, cl, acc) receives every row exactly once.
@@ -376,6 +519,26 @@ __device__ __forceinline__ void aggregate_rows(const int2* ecv, const int* tab, 
         if (k < len) add4(acc, gather4(ecv, srcl, s_ + k));
       if (ok) emit(row, cl, acc);
     }
+  }
+}
+
+// aggregate_rows<true> in the adjacency layout LAY (the FULL forward)
+template <int LAY, typename Emit>
+__device__ __forceinline__ void aggregate_rows_full(const int2* ecv, const float* ev, const int* tab, const float* tile,
+                                                    int lane, Emit&& emit) {
+  const int sub = lane >> 4, cl = lane & 15;
+  const float* srcl = tile + cl * 4;
+#pragma unroll
+  for (int p8 = 0; p8 < 8; ++p8) {
+    int s, len, row;
+    unpack_slot(tab[4 * p8 + sub], s, len, row);
+    Grp4<LAY> q;
+    q.ecv(ecv, ev, s);
+    q.tile(srcl);
+    q.fma();
+    grp_tail<LAY>(q.a, s, len, ecv, ev, srcl);
+    emit(row, cl, q.a);
+    __builtin_amdgcn_sched_barrier(0);
   }
 }
 
@@ -535,10 +698,13 @@ __global__ __launch_bounds__(512, 2) void graphconv_fwd_kernel(
 // step, after the aggregation of the previous graph released it).
 constexpr size_t FWD_FULL_SHARED = 2 * 4 * 64 * 16;   // W p3 fragments: [tile][k-step][lane] x 16 bytes
 
+// LAY: adjacency layout (LAY_PAD4: row_pad = 4, cv = (col, value) pairs; LAY_UNIT / LAY_VALS: compact, cv = column words,
+// cvals = the value stream of LAY_VALS)
+template <int LAY>
 __global__ __launch_bounds__(512, 2) void graphconv_fwd_full_kernel(
     const int* __restrict__ slots, const int* __restrict__ gptr, const int2* __restrict__ cv,
-    const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
-    float* __restrict__ out, int T, int max_nnz) {
+    const float* __restrict__ cvals, const float* __restrict__ x, const float* __restrict__ w,
+    const float* __restrict__ bias, float* __restrict__ out, int T, int max_nnz) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int N = FN, D = FD;
   const int tid = threadIdx.x;
@@ -547,6 +713,13 @@ __global__ __launch_bounds__(512, 2) void graphconv_fwd_full_kernel(
   const int wpb = blockDim.x >> 6;
   u32x4* w3 = reinterpret_cast<u32x4*>(smem);
   WaveSlice ws = carve(smem + FWD_FULL_SHARED, wave, max_nnz, A_FWD, 1);
+  const float* ev = reinterpret_cast<const float*>(reinterpret_cast<unsigned char*>(ws.ecv) + cvals_off(max_nnz));
+  const unsigned* cw = reinterpret_cast<const unsigned*>(cv);
+  using CsrIn = std::conditional_t<LAY == LAY_PAD4, CsrRegs, CsrRegsC>;
+  auto issue_csr = [&](CsrIn& f, int b_, int c_) __attribute__((always_inline)) {
+    if constexpr (LAY == LAY_PAD4) issue_cv(f, cv, b_, c_, lane);
+    else issue_cv_c<LAY>(f, cw, cvals, b_, c_, lane);
+  };
 
   // B fragments of FW = X W: lane (li, hi), tile nt, k-step ks holds W[k][32 nt + li] for
   // k = 16 ks + 8 hi + j as three bf16 pieces
@@ -579,14 +752,14 @@ __global__ __launch_bounds__(512, 2) void graphconv_fwd_full_kernel(
 
   // ---- prologue ------------------------------------------------------------------------------
   TileRegs fx;
-  CsrRegs fc;
+  CsrIn fc;
   MetaRegs m_cur, m_nxt;
-  issue_meta(m_cur, slots, gptr, hot(t), N, lane);
+  issue_meta_l<LAY>(m_cur, slots, gptr, hot(t), N, lane);
   int base = meta_base(m_cur), cnt = meta_cnt(m_cur);
   issue_tile<true>(fx, x + (long)hot(t) * N * D, 512, lane);
-  issue_cv(fc, cv, base, cnt, lane);
+  issue_csr(fc, base, cnt);
   int tn = t + nwaves;
-  issue_meta(m_nxt, slots, gptr, hot(tn < T ? tn : t), N, lane);
+  issue_meta_l<LAY>(m_nxt, slots, gptr, hot(tn < T ? tn : t), N, lane);
   wave_sync();
 
   int t_prev = t;      // graph whose FW sits in the gather tile (valid from the second step on)
@@ -594,7 +767,7 @@ __global__ __launch_bounds__(512, 2) void graphconv_fwd_full_kernel(
   PROBE_DECL
   auto aggregate_prev = [&]() __attribute__((always_inline)) {
     float* ot = out + (long)hot(t_prev) * N * D;
-    aggregate_rows<true>(ws.ecv, ws.rp, ws.b, N, D, lane, [&](int r, int c4, f32x4 v) {
+    aggregate_rows_full<LAY>(ws.ecv, ev, ws.rp, ws.b, lane, [&](int r, int c4, f32x4 v) {
       stv4(ot + r * D + c4 * 4, v);
     });
   };
@@ -617,16 +790,17 @@ __global__ __launch_bounds__(512, 2) void graphconv_fwd_full_kernel(
     PROBE(2)
 
     // ---- 3. CSR(t): registers -> LDS (the slice of t_prev is dead); CSR(t + nwaves) in flight ---------
-    land_csr(fc, ws.ecv, ws.rp, cv, m_cur.slot, base, cnt, N, lane);
+    if constexpr (LAY == LAY_PAD4) land_csr(fc, ws.ecv, ws.rp, cv, m_cur.slot, base, cnt, N, lane);
+    else land_csr_c<LAY>(fc, ws.ecv, ws.rp, cw, cvals, max_nnz, compact_slot_word(m_cur.slot), base, cnt, N, lane);
     const int base_n = meta_base(m_nxt), cnt_n = meta_cnt(m_nxt);
-    issue_cv(fc, cv, base_n, cnt_n, lane);
+    issue_csr(fc, base_n, cnt_n);
     // a REAL register move before the reload of m_nxt (a plain copy becomes a loop phi whose copy lands
     // behind the new load: s_waitcnt vmcnt(~0) on the prefetch at the top of the next step)
     asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %3"
                  : "=&v"(m_cur.slot), "=&v"(m_cur.gp) : "v"(m_nxt.slot), "v"(m_nxt.gp));
     {
       const int tnn = tn + nwaves;
-      issue_meta(m_nxt, slots, gptr, hot(tnn < T ? tnn : tp), N, lane);
+      issue_meta_l<LAY>(m_nxt, slots, gptr, hot(tnn < T ? tnn : tp), N, lane);
     }
 
     // ---- 4. FW(t) = X(t) W + b: per k-step 8 values of row li (k = 16 ks + 8 hi + j) are split, then
@@ -1511,10 +1685,12 @@ constexpr int BP_PAIRS = 4;
 #endif
 __device__ __forceinline__ void bp_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// LAY: adjacency layout of A^T, as in graphconv_fwd_full_kernel
+template <int LAY>
 __global__ __launch_bounds__(512, 2) void graphconv_bwd_pairs_kernel(
     const int* __restrict__ slots_t, const int* __restrict__ gptr_t, const int2* __restrict__ cv_t,
-    const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ g,
-    float* __restrict__ dx, float* __restrict__ part_dw, float* __restrict__ part_db, int T,
+    const float* __restrict__ cvals_t, const float* __restrict__ x, const float* __restrict__ w,
+    const float* __restrict__ g, float* __restrict__ dx, float* __restrict__ part_dw, float* __restrict__ part_db, int T,
     int max_nnz) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int N = FN, D = FD;
@@ -1534,6 +1710,10 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_pairs_kernel(
   int2* ecv0 = reinterpret_cast<int2*>(gt + (FN + 1) * FD);
   const size_t ecv_stride = ecv_bytes(max_nnz) / 8;
   int* tab0 = reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(ecv0) + 2 * ecv_bytes(max_nnz));
+  const size_t ev_off = cvals_off(max_nnz);                       // value stream inside a compact slice (bytes)
+  auto ev_of = [&](const int2* e) __attribute__((always_inline)) {
+    return reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(e) + ev_off);
+  };
 
   const int npairs = gridDim.x * BP_PAIRS;
   const int t0 = blockIdx.x * BP_PAIRS + pair;
@@ -1558,7 +1738,9 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_pairs_kernel(
   const unsigned h_e = (unsigned)cl >> 3;
   const unsigned lanexor = (h_e << 8) | (h_e << 6) | ((((unsigned)cl & 7) >> 1) << 4) | (((unsigned)cl & 1) << 3);
   const float* srcl = gt + cl * 4;
-  auto emit_to = [&](unsigned lx, const PlaneSteps& q) __attribute__((always_inline)) {
+  // one row of a pass: plane slot word (PlaneSteps::slot) + its first group in the layout LAY
+  struct PairRow : Grp4<LAY> { int s, len; unsigned rw; };
+  auto emit_to = [&](unsigned lx, const PairRow& q) __attribute__((always_inline)) {
     unsigned q1, q2, q3, r1, r2, r3;
     split_pair(q.a[0], q.a[1], q1, q2, q3);
     split_pair(q.a[2], q.a[3], r1, r2, r3);
@@ -1568,39 +1750,30 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_pairs_kernel(
     lds_st64(ad + 2 * PL_BYTES, q3, r3);
     add4(dbacc, q.a);
   };
+  auto row_slot = [&](PairRow& q, const int* tab, int j) __attribute__((always_inline)) {
+    const unsigned u = (unsigned)tab[j];
+    q.s = (int)(u & 0xfffu);
+    q.len = (int)((u >> 12) & 0xffu);
+    q.rw = (u >> 24) << 4;
+  };
   // row groups gq = G0 .. G1 - 1 of the graph in the gather tile -> planes at `plane_off`, two passes in flight
   auto aggregate = [&](auto maskc, const int2* ecv, const int* tab, unsigned plane_off) __attribute__((always_inline)) {
     const unsigned lx = lanexor | (pl0 + plane_off);
+    const float* ev = ev_of(ecv);
     static_for<4>([&](auto gqc) __attribute__((always_inline)) {
       constexpr int gq = decltype(gqc)::value;
       if constexpr (((decltype(maskc)::value >> gq) & 1) != 0) {
-      PlaneSteps qa, qb;
-      qa.slot(tab, 8 * gq + sub);
-      qb.slot(tab, 8 * gq + 4 + sub);
-      qa.q0 = *reinterpret_cast<const i32x4*>(ecv + qa.s);
-      qa.q1 = *reinterpret_cast<const i32x4*>(ecv + qa.s + 2);
-      qb.q0 = *reinterpret_cast<const i32x4*>(ecv + qb.s);
-      qb.q1 = *reinterpret_cast<const i32x4*>(ecv + qb.s + 2);
-      qa.x0 = ldv4(srcl + qa.q0.x * FD); qa.x1 = ldv4(srcl + qa.q0.z * FD);
-      qa.x2 = ldv4(srcl + qa.q1.x * FD); qa.x3 = ldv4(srcl + qa.q1.z * FD);
-      qb.x0 = ldv4(srcl + qb.q0.x * FD); qb.x1 = ldv4(srcl + qb.q0.z * FD);
-      qb.x2 = ldv4(srcl + qb.q1.x * FD); qb.x3 = ldv4(srcl + qb.q1.z * FD);
-      {
-        const float v = __int_as_float(qa.q0.y);
-        qa.a[0] = v * qa.x0[0]; qa.a[1] = v * qa.x0[1]; qa.a[2] = v * qa.x0[2]; qa.a[3] = v * qa.x0[3];
-        fma4(qa.a, __int_as_float(qa.q0.w), qa.x1);
-        fma4(qa.a, __int_as_float(qa.q1.y), qa.x2);
-        fma4(qa.a, __int_as_float(qa.q1.w), qa.x3);
-      }
-      {
-        const float v = __int_as_float(qb.q0.y);
-        qb.a[0] = v * qb.x0[0]; qb.a[1] = v * qb.x0[1]; qb.a[2] = v * qb.x0[2]; qb.a[3] = v * qb.x0[3];
-        fma4(qb.a, __int_as_float(qb.q0.w), qb.x1);
-        fma4(qb.a, __int_as_float(qb.q1.y), qb.x2);
-        fma4(qb.a, __int_as_float(qb.q1.w), qb.x3);
-      }
-      qa.tail(ecv, srcl);
-      qb.tail(ecv, srcl);
+      PairRow qa, qb;
+      row_slot(qa, tab, 8 * gq + sub);
+      row_slot(qb, tab, 8 * gq + 4 + sub);
+      qa.ecv(ecv, ev, qa.s);
+      qb.ecv(ecv, ev, qb.s);
+      qa.tile(srcl);
+      qb.tile(srcl);
+      qa.fma();
+      qb.fma();
+      grp_tail<LAY>(qa.a, qa.s, qa.len, ecv, ev, srcl);
+      grp_tail<LAY>(qb.a, qb.s, qb.len, ecv, ev, srcl);
       emit_to(lx, qa);
       emit_to(lx, qb);
       if constexpr (KGCN_BP_AGG_SCOPE == 0) __builtin_amdgcn_sched_barrier(0);
@@ -1660,33 +1833,44 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_pairs_kernel(
     __syncthreads();                                              // barrier 0: the W table
 
     TileRegs gpf;
-    CsrRegs cpf;
+    using CsrIn = std::conditional_t<LAY == LAY_PAD4, CsrRegs, CsrRegsC>;
+    CsrIn cpf;
+    const unsigned* cw_t = reinterpret_cast<const unsigned*>(cv_t);
+    auto issue_csr = [&](int b_, int c_) __attribute__((always_inline)) {
+      if constexpr (LAY == LAY_PAD4) issue_cv(cpf, cv_t, b_, c_, lane);
+      else issue_cv_c<LAY>(cpf, cw_t, cvals_t, b_, c_, lane);
+    };
+    auto land_csr_l = [&](int2* ecv_c, int* tab_c, int slot, int b_, int c_) __attribute__((always_inline)) {
+      if constexpr (LAY == LAY_PAD4) land_csr(cpf, ecv_c, tab_c, cv_t, slot_plane_word(slot), b_, c_, N, lane);
+      else land_csr_c<LAY>(cpf, ecv_c, tab_c, cw_t, cvals_t, max_nnz, slot_plane_word(compact_slot_word(slot)), b_, c_, N,
+                           lane);
+    };
     MetaRegs m_a, m_b;   // m_a: graph whose g / CSR are in flight; m_b: the one after it
     // ---- prologue: graph 0 aggregated into planes 0; g(1), CSR(1) in LDS; g(2), CSR(2) in flight ---------------
-    issue_meta(m_a, slots_t, gptr_t, gidx(0), N, lane);
+    issue_meta_l<LAY>(m_a, slots_t, gptr_t, gidx(0), N, lane);
     int base_a = meta_base(m_a), cnt_a = meta_cnt(m_a);
     issue_tile<true>(gpf, g + (long)gidx(0) * N * D, 512, lane);
-    issue_cv(cpf, cv_t, base_a, cnt_a, lane);
-    issue_meta(m_b, slots_t, gptr_t, gidx(1), N, lane);
+    issue_csr(base_a, cnt_a);
+    issue_meta_l<LAY>(m_b, slots_t, gptr_t, gidx(1), N, lane);
     land_tile<true>(gpf, gt, FD, 512, 16, lane);
-    land_csr(cpf, ecv0, tab0, cv_t, slot_plane_word(m_a.slot), base_a, cnt_a, N, lane);
+    land_csr_l(ecv0, tab0, m_a.slot, base_a, cnt_a);
     wave_sync();
     m_a = m_b;
     base_a = meta_base(m_a);
     cnt_a = meta_cnt(m_a);
     issue_tile<true>(gpf, g + (long)gidx(1) * N * D, 512, lane);
-    issue_cv(cpf, cv_t, base_a, cnt_a, lane);
-    issue_meta(m_b, slots_t, gptr_t, gidx(2), N, lane);
+    issue_csr(base_a, cnt_a);
+    issue_meta_l<LAY>(m_b, slots_t, gptr_t, gidx(2), N, lane);
     aggregate(MALL{}, ecv0, tab0, 0u);                        // graph 0: all four row groups
     wave_sync();
     land_tile<true>(gpf, gt, FD, 512, 16, lane);
-    land_csr(cpf, ecv0 + ecv_stride, tab0 + (FN + 4), cv_t, slot_plane_word(m_a.slot), base_a, cnt_a, N, lane);
+    land_csr_l(ecv0 + ecv_stride, tab0 + (FN + 4), m_a.slot, base_a, cnt_a);
     m_a = m_b;
     base_a = meta_base(m_a);
     cnt_a = meta_cnt(m_a);
     issue_tile<true>(gpf, g + (long)gidx(2) * N * D, 512, lane);
-    issue_cv(cpf, cv_t, base_a, cnt_a, lane);
-    issue_meta(m_b, slots_t, gptr_t, gidx(3), N, lane);
+    issue_csr(base_a, cnt_a);
+    issue_meta_l<LAY>(m_b, slots_t, gptr_t, gidx(3), N, lane);
     if (lane == 0) *arrive_mine = 0;
     bp_barrier();                                                 // barrier 1: dFW(0) in planes 0
 
@@ -1702,13 +1886,13 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_pairs_kernel(
         stv4(gt + 4 * lane + q * 256, gpf.v[q]);
         gpf.v[q] = ldv4((q >> 2 ? gsrc + 1024 : gsrc) + (q & 3) * 256);
       });
-      land_csr(cpf, ecv_c, tab_c, cv_t, slot_plane_word(m_a.slot), base_a, cnt_a, N, lane);
+      land_csr_l(ecv_c, tab_c, m_a.slot, base_a, cnt_a);
       const int base_n = meta_base(m_b), cnt_n = meta_cnt(m_b);
-      issue_cv(cpf, cv_t, base_n, cnt_n, lane);
+      issue_csr(base_n, cnt_n);
       // a REAL register move (see the planes kernel: a plain `m_a = m_b` becomes a phi whose copy lands behind the new load)
       asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %3"
                    : "=&v"(m_a.slot), "=&v"(m_a.gp) : "v"(m_b.slot), "v"(m_b.gp));
-      issue_meta(m_b, slots_t, gptr_t, gidx(i + 4), N, lane);
+      issue_meta_l<LAY>(m_b, slots_t, gptr_t, gidx(i + 4), N, lane);
       base_a = base_n;
       cnt_a = cnt_n;
     };
@@ -2005,15 +2189,40 @@ static void allow_big_lds(K kernel) {
                             hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
 }
 
+static bool is_compact(const kgcn_csr_batch* a) { return a->row_pad == KGCN_ROW_PAD_COMPACT; }
+
 static int check_padded(const kgcn_csr_batch* a, const char* who) {
-  if (int rc = validate_csr(a, who, true)) return rc;
-  if (a->row_pad != 4)
-    return fail("%s: the fused kernels read the row-padded layout (row_pad = 4), got row_pad=%d", who,
-                a->row_pad);
+  if (!a) return validate_csr(a, who, true);
+  kgcn_csr_batch v = *a;                                  // the compact layout shares the row-padded sizes and rowptr
+  if (is_compact(a)) v.row_pad = 4;
+  if (int rc = validate_csr(&v, who, true)) return rc;
+  if (a->row_pad != 4 && !is_compact(a))
+    return fail("%s: the fused kernels read the row-padded layout (row_pad = 4 or the compact %d), got row_pad=%d", who,
+                KGCN_ROW_PAD_COMPACT, a->row_pad);
+  if (is_compact(a) && (a->reserved_ & ~KGCN_CSR_UNIT_VALUES))
+    return fail("%s: unknown flags 0x%x in a compact batch", who, (unsigned)a->reserved_);
   if (a->num_graphs > 0 && (!a->slots || !a->graph_ptr))
     return fail("%s: row-padded batch without slots / graph_ptr", who);
   if (a->rows != a->cols) return fail("%s: adjacency must be square", who);
   return 0;
+}
+
+// layout template argument of the FULL kernels for a checked batch, and the value stream of a compact one
+static int lay_of(const kgcn_csr_batch* a) {
+  return !is_compact(a) ? LAY_PAD4 : (a->reserved_ & KGCN_CSR_UNIT_VALUES) ? LAY_UNIT : LAY_VALS;
+}
+static const float* compact_values(const kgcn_csr_batch* a) {
+  return lay_of(a) == LAY_VALS ? reinterpret_cast<const float*>(a->cv + kgcn_compact_values_offset(a->nnz)) : nullptr;
+}
+
+// the backward's kernel choice (kgcn_graphconv_bwd_f32): the planes kernel with one wave per graph slot when dx is wanted
+// and the FULL slice fits, the pairs kernel when moreover every pair owns at least two graphs (uniform barrier counts)
+static bool bwd_full_route(int n, int din, int dout, int max_nnz, bool with_dx) {
+  return with_dx && is_full(n, din, dout) && bwd_planes_lds_bytes(max_nnz) <= (size_t)kLdsBytes && max_nnz < 4096;
+}
+static bool bwd_pairs_route(int T, int n, int din, int dout, int max_nnz, bool with_dx) {
+  return KGCN_BWD_PAIRS != 0 && bwd_full_route(n, din, dout, max_nnz, with_dx) &&
+         T >= 2 * BP_PAIRS * fused_grid(T, BWD_FULL_WPB);
 }
 
 }  // namespace kgcn
@@ -2026,6 +2235,19 @@ extern "C" int kgcn_probe_set(void* buf) {
   return hipMemcpyToSymbol(HIP_SYMBOL(g_probe), &p, sizeof(p)) == hipSuccess ? 0 : 1;
 }
 #endif
+
+extern "C" int64_t kgcn_compact_values_offset(int64_t nnz) { return ((nnz / 4) + 3) & ~(int64_t)3; }
+
+extern "C" int64_t kgcn_compact_cv_words(int64_t nnz, int32_t with_values) {
+  return with_values ? kgcn_compact_values_offset(nnz) + nnz : nnz / 4;
+}
+
+extern "C" int kgcn_graphconv_fused_reads_compact(int32_t backward, int32_t num_graphs, int32_t n_nodes, int32_t din,
+                                                  int32_t dout, int32_t max_nnz_per_graph, int32_t with_dx) {
+  if (num_graphs <= 0 || !fused_shape_ok(n_nodes, din, dout, max_nnz_per_graph)) return 0;
+  if (!backward) return is_full(n_nodes, din, dout) ? 1 : 0;
+  return bwd_pairs_route(num_graphs, n_nodes, din, dout, max_nnz_per_graph, with_dx != 0) ? 1 : 0;
+}
 
 extern "C" int kgcn_graphconv_fused_supported(int32_t n_nodes, int32_t din, int32_t dout,
                                               int32_t max_nnz_per_graph) {
@@ -2049,6 +2271,9 @@ extern "C" int kgcn_graphconv_fwd_f32(const kgcn_csr_batch* a, const float* x, c
   // tile movement mode (see land_tile_f4): 1 when every graph's [N x d] block is a whole number of aligned float4
   const int mode = vec ? 2 : (((a->rows * din) & 3) == 0 && ((a->rows * dout) & 3) == 0 && aligned16(x)) ? 1 : 0;
   const bool full_shape = is_full(a->rows, din, dout);
+  if (is_compact(a) && !full_shape)
+    return fail("kgcn_graphconv_fwd_f32: the compact adjacency layout is read by the FULL-shape kernel only (N=%d din=%d "
+                "dout=%d): pass the row-padded batch", a->rows, din, dout);
   const int pack = full_shape ? 1 : pack_factor(a->rows, a->max_nnz_per_graph, 0);
   const size_t per = fwd_slice(a->rows, din, dout, a->max_nnz_per_graph * pack);
   const size_t shared = fwd_shared(a->rows, din, dout);
@@ -2057,7 +2282,9 @@ extern "C" int kgcn_graphconv_fwd_f32(const kgcn_csr_batch* a, const float* x, c
   const int tiles = (a->num_graphs + pack - 1) / pack;
   static thread_local bool attr_set = false;
   if (!attr_set) {
-    allow_big_lds(graphconv_fwd_full_kernel);
+    allow_big_lds(graphconv_fwd_full_kernel<LAY_PAD4>);
+    allow_big_lds(graphconv_fwd_full_kernel<LAY_UNIT>);
+    allow_big_lds(graphconv_fwd_full_kernel<LAY_VALS>);
     allow_big_lds(graphconv_fwd_kernel<2>);
     allow_big_lds(graphconv_fwd_kernel<1>);
     allow_big_lds(graphconv_fwd_kernel<0>);
@@ -2065,9 +2292,17 @@ extern "C" int kgcn_graphconv_fwd_f32(const kgcn_csr_batch* a, const float* x, c
   }
   const dim3 grid(fused_grid(tiles, wpb)), block(64 * wpb);
   const int2* cv = reinterpret_cast<const int2*>(a->cv);
-  if (full_shape)
-    hipLaunchKernelGGL(graphconv_fwd_full_kernel, grid, block, lds, as_stream(stream), a->slots,
-                       a->graph_ptr, cv, x, w, bias, out, a->num_graphs, a->max_nnz_per_graph);
+  const int lay = lay_of(a);
+  const float* cvals = compact_values(a);
+  if (full_shape && lay == LAY_UNIT)
+    hipLaunchKernelGGL(graphconv_fwd_full_kernel<LAY_UNIT>, grid, block, lds, as_stream(stream), a->slots,
+                       a->graph_ptr, cv, cvals, x, w, bias, out, a->num_graphs, a->max_nnz_per_graph);
+  else if (full_shape && lay == LAY_VALS)
+    hipLaunchKernelGGL(graphconv_fwd_full_kernel<LAY_VALS>, grid, block, lds, as_stream(stream), a->slots,
+                       a->graph_ptr, cv, cvals, x, w, bias, out, a->num_graphs, a->max_nnz_per_graph);
+  else if (full_shape)
+    hipLaunchKernelGGL(graphconv_fwd_full_kernel<LAY_PAD4>, grid, block, lds, as_stream(stream), a->slots,
+                       a->graph_ptr, cv, cvals, x, w, bias, out, a->num_graphs, a->max_nnz_per_graph);
   else if (mode == 2)
     hipLaunchKernelGGL(graphconv_fwd_kernel<2>, grid, block, lds, as_stream(stream), a->slots,
                        a->graph_ptr, cv, x, w, bias, out, a->num_graphs, a->rows, din, dout,
@@ -2116,14 +2351,16 @@ extern "C" int kgcn_graphconv_bwd_f32(const kgcn_csr_batch* at, const float* x, 
   const int mode = vec ? 2 : (((at->rows * din) & 3) == 0 && ((at->rows * dout) & 3) == 0 && aligned16(x) &&
                               aligned16(dout_grad) && (!dx || aligned16(dx))) ? 1 : 0;
   const size_t full_lds = bwd_planes_lds_bytes(at->max_nnz_per_graph);
-  const bool full = dx != nullptr && is_full(at->rows, din, dout) && full_lds <= (size_t)kLdsBytes &&
-                    at->max_nnz_per_graph < 4096;
+  const bool full = bwd_full_route(at->rows, din, dout, at->max_nnz_per_graph, dx != nullptr);
   const int pack = (full || is_full(at->rows, din, dout)) ? 1 : pack_factor(at->rows, at->max_nnz_per_graph, FD * FD * 4);
   const size_t per = full ? full_lds / BWD_FULL_WPB : bwd_slice(at->max_nnz_per_graph * pack);
   const int wpb = full ? BWD_FULL_WPB : fused_wpb(per, FD * FD * 4);
   int blocks = fused_grid((at->num_graphs + pack - 1) / pack, wpb);
   // two waves per graph slot (graphconv_bwd_pairs_kernel): every pair must own at least two graphs (uniform barrier counts)
-  const bool pairs = KGCN_BWD_PAIRS != 0 && full && at->num_graphs >= 2 * BP_PAIRS * blocks;
+  const bool pairs = bwd_pairs_route(at->num_graphs, at->rows, din, dout, at->max_nnz_per_graph, dx != nullptr);
+  if (is_compact(at) && !pairs)
+    return fail("kgcn_graphconv_bwd_f32: the compact adjacency layout is read by the pairs kernel only (T=%d N=%d din=%d "
+                "dout=%d, dx %s): pass the row-padded batch", at->num_graphs, at->rows, din, dout, dx ? "wanted" : "NULL");
   // development (the non-persistent form, measured): KGCN_BWD_GRID_MULT = k launches k workgroups per CU slot,
   // each walking 1 / k of the graphs with its own pipeline fill, W' split and dW partial (k x 256 partials in the second stage) --
   // the form the kernel's LDS footprint (one 4-wave workgroup per CU) allows.  profiles/r05_headline_experiments.txt
@@ -2139,16 +2376,28 @@ extern "C" int kgcn_graphconv_bwd_f32(const kgcn_csr_batch* at, const float* x, 
   static thread_local bool attr_set = false;
   if (!attr_set) {
     allow_big_lds(graphconv_bwd_planes_kernel);
-    allow_big_lds(graphconv_bwd_pairs_kernel);
+    allow_big_lds(graphconv_bwd_pairs_kernel<LAY_PAD4>);
+    allow_big_lds(graphconv_bwd_pairs_kernel<LAY_UNIT>);
+    allow_big_lds(graphconv_bwd_pairs_kernel<LAY_VALS>);
     allow_big_lds(graphconv_bwd_kernel<2>);
     allow_big_lds(graphconv_bwd_kernel<1>);
     allow_big_lds(graphconv_bwd_kernel<0>);
     attr_set = true;
   }
   const int2* cv = reinterpret_cast<const int2*>(at->cv);
-  if (pairs)
-    hipLaunchKernelGGL(graphconv_bwd_pairs_kernel, dim3(blocks), dim3(512), lds, s, at->slots,
-                       at->graph_ptr, cv, x, w, dout_grad, dx, part_dw, part_db, at->num_graphs,
+  const int lay = lay_of(at);
+  const float* cvals = compact_values(at);
+  if (pairs && lay == LAY_UNIT)
+    hipLaunchKernelGGL(graphconv_bwd_pairs_kernel<LAY_UNIT>, dim3(blocks), dim3(512), lds, s, at->slots,
+                       at->graph_ptr, cv, cvals, x, w, dout_grad, dx, part_dw, part_db, at->num_graphs,
+                       at->max_nnz_per_graph);
+  else if (pairs && lay == LAY_VALS)
+    hipLaunchKernelGGL(graphconv_bwd_pairs_kernel<LAY_VALS>, dim3(blocks), dim3(512), lds, s, at->slots,
+                       at->graph_ptr, cv, cvals, x, w, dout_grad, dx, part_dw, part_db, at->num_graphs,
+                       at->max_nnz_per_graph);
+  else if (pairs)
+    hipLaunchKernelGGL(graphconv_bwd_pairs_kernel<LAY_PAD4>, dim3(blocks), dim3(512), lds, s, at->slots,
+                       at->graph_ptr, cv, cvals, x, w, dout_grad, dx, part_dw, part_db, at->num_graphs,
                        at->max_nnz_per_graph);
   else if (full)
     hipLaunchKernelGGL(graphconv_bwd_planes_kernel, dim3(blocks), dim3(64 * wpb), lds, s, at->slots,

@@ -1044,6 +1044,18 @@ def graphconv_fused_supported(csr, din, dout):
     return bool(lib.kgcn_graphconv_fused_supported(csr.rows, din, dout, bound))
 
 
+def _fused_adjacency(csr, backward, T, din, dout, with_dx):
+    """Descriptor the fused launcher reads: the compact copy (BatchedCSR.compact4()) where the selected kernel reads
+    that layout (the FULL forward, the pairs backward), the row-padded one everywhere else.  The compact copy is built
+    on first use, never while a hipGraph is being captured (its build reads back to the host)."""
+    p4 = csr.padded4()
+    if lib.kgcn_graphconv_fused_reads_compact(int(backward), T, p4.rows, din, dout, p4.max_nnz, int(with_dx)):
+        c4 = p4.compact4(build=not torch.cuda.is_current_stream_capturing())
+        if c4 is not None:
+            return c4.desc()
+    return p4.desc()
+
+
 class _GraphConvFused(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, bias, csr):
@@ -1052,8 +1064,8 @@ class _GraphConvFused(torch.autograd.Function):
         dout = w.shape[1]
         b = _f32c(bias, "bias").reshape(-1)
         out = torch.empty((T, N, dout), device=x.device, dtype=torch.float32)
-        check(lib.kgcn_graphconv_fwd_f32(csr.padded4().desc(), ptr(x), ptr(w), ptr(b), din, dout,
-                                         ptr(out), current_stream()), "kgcn_graphconv_fwd_f32")
+        check(lib.kgcn_graphconv_fwd_f32(_fused_adjacency(csr, False, T, din, dout, False), ptr(x), ptr(w), ptr(b),
+                                         din, dout, ptr(out), current_stream()), "kgcn_graphconv_fwd_f32")
         ctx.csr = csr
         ctx.bias_shape = tuple(bias.shape)
         _record_params(ctx, w, bias)
@@ -1073,8 +1085,8 @@ class _GraphConvFused(torch.autograd.Function):
         dw, db = dwb[:din * dout].view(din, dout), dwb[din * dout:]
         wsb = lib.kgcn_graphconv_bwd_workspace_bytes(T, din, dout)
         with _param_grad_stage(ctx, wsb, x.device) as wsp:
-            check(lib.kgcn_graphconv_bwd_f32(ctx.csr.transpose().padded4().desc(), ptr(x), ptr(w),
-                                             ptr(g), din, dout, ptr(dx), ptr(dw), ptr(db), ptr(wsp),
+            check(lib.kgcn_graphconv_bwd_f32(_fused_adjacency(ctx.csr.transpose(), True, T, din, dout, dx is not None),
+                                             ptr(x), ptr(w), ptr(g), din, dout, ptr(dx), ptr(dw), ptr(db), ptr(wsp),
                                              wsb, current_stream()), "kgcn_graphconv_bwd_f32")
         return dx, dw, db.reshape(ctx.bias_shape), None
 
