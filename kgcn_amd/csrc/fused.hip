@@ -229,11 +229,6 @@ __device__ __forceinline__ void land_csr(const CsrRegs& f, int2* ecv, int* tab,
 // Per-graph metadata in flight: lane l < N holds slots[t*N + l]; `gp` holds graph_ptr[t + (l & 1)]
 // (lane 0: first entry of the graph, lane 1: one past its last entry).
 struct MetaRegs { int slot, gp; };
-__device__ __forceinline__ void issue_meta(MetaRegs& m, const int* __restrict__ slots,
-                                           const int* __restrict__ gptr, int t, int N, int lane) {
-  m.slot = slots[(long)t * N + (lane < N ? lane : N - 1)];
-  m.gp = gptr[t + (lane & 1)];
-}
 __device__ __forceinline__ int meta_base(const MetaRegs& m) { return __builtin_amdgcn_readlane(m.gp, 0); }
 __device__ __forceinline__ int meta_cnt(const MetaRegs& m) {
   return __builtin_amdgcn_readlane(m.gp, 1) - __builtin_amdgcn_readlane(m.gp, 0);
@@ -289,59 +284,6 @@ __device__ __forceinline__ void unpack_slot(int v, int& s, int& len, int& row) {
   len = (int)((u >> 16) & 0xffu);
   row = (int)(u >> 24);
 }
-
-// Gather of the four entries k..k+3 of one CSR row (k is a multiple of 4 in the row-padded layout):
-// 2 ds_read_b128 fetch the (col,val) pairs, 4 ds_read_b128 the neighbour rows.  Padding entries
-// are (col = FN, val = 0): they read the all-zero row, 0 * 0, never 0 * inf -- no masks.
-__device__ __forceinline__ f32x4 gather4(const int2* ecv, const float* srcl, int k) {
-  const i32x4 q0 = *reinterpret_cast<const i32x4*>(ecv + k);
-  const i32x4 q1 = *reinterpret_cast<const i32x4*>(ecv + k + 2);
-  const f32x4 x0 = ldv4(srcl + q0.x * FD);
-  const f32x4 x1 = ldv4(srcl + q0.z * FD);
-  const f32x4 x2 = ldv4(srcl + q1.x * FD);
-  const f32x4 x3 = ldv4(srcl + q1.z * FD);
-  f32x4 a0 = {0.f, 0.f, 0.f, 0.f};
-  fma4(a0, __int_as_float(q0.y), x0);
-  fma4(a0, __int_as_float(q0.w), x1);
-  fma4(a0, __int_as_float(q1.y), x2);
-  fma4(a0, __int_as_float(q1.w), x3);
-  return a0;
-}
-
-// One aggregation pass (4 slots j = 4p + sub of the graph's slot table, i.e. 4 rows) cut into
-// micro-steps, so that the FULL kernels can place one step behind every MFMA pair of the dense
-// contraction (the compiler keeps MFMAs in one clump otherwise, and an in-order wave cannot overlap
-// a clump with what follows it):   slot() -> ecv() -> tile() -> fma() -> [tail()] -> a / row ready.
-// Rows are ordered by decreasing length in the slot table, so tail() (rows with more than 4
-// entries) fires only in the first pass or two of a graph.
-struct PassSteps {
-  int s, len, row;
-  i32x4 q0, q1;
-  f32x4 x0, x1, x2, x3;
-  f32x4 a;
-  __device__ __forceinline__ void slot(const int* tab, int j) { unpack_slot(tab[j], s, len, row); }
-  __device__ __forceinline__ void ecv(const int2* ecv_) {
-    q0 = *reinterpret_cast<const i32x4*>(ecv_ + s);
-    q1 = *reinterpret_cast<const i32x4*>(ecv_ + s + 2);
-  }
-  __device__ __forceinline__ void tile(const float* srcl) {
-    x0 = ldv4(srcl + q0.x * FD); x1 = ldv4(srcl + q0.z * FD);
-    x2 = ldv4(srcl + q1.x * FD); x3 = ldv4(srcl + q1.z * FD);
-  }
-  __device__ __forceinline__ void fma() {
-    a[0] = __int_as_float(q0.y) * x0[0]; a[1] = __int_as_float(q0.y) * x0[1];
-    a[2] = __int_as_float(q0.y) * x0[2]; a[3] = __int_as_float(q0.y) * x0[3];
-    fma4(a, __int_as_float(q0.w), x1);
-    fma4(a, __int_as_float(q1.y), x2);
-    fma4(a, __int_as_float(q1.w), x3);
-  }
-  __device__ __forceinline__ void tail(const int2* ecv_, const float* srcl) {
-    if (__builtin_amdgcn_ballot_w64(len > 4)) {
-      for (int k = 4; __builtin_amdgcn_ballot_w64(k < len); k += 4)
-        if (k < len) add4(a, gather4(ecv_, srcl, s + k));
-    }
-  }
-};
 
 // ---- compact row-padded layout (KGCN_ROW_PAD_COMPACT, include/kgcn_hip.h) -------------------------------------
 // The FULL kernels are instantiated per adjacency layout: LAY_PAD4 reads (col, value) pairs (row_pad = 4), LAY_UNIT one
@@ -400,24 +342,22 @@ __device__ __forceinline__ void land_csr_c(const CsrRegsC& f, int2* ecv, int* ta
   }
   if (lane < N) tab[lane] = slot_val;
 }
+// metadata of graph t (MetaRegs): the compact layouts keep 16-bit slots
 template <int LAY>
 __device__ __forceinline__ void issue_meta_l(MetaRegs& m, const int* __restrict__ slots, const int* __restrict__ gptr, int t,
                                              int N, int lane) {
-  if constexpr (LAY == LAY_PAD4) {
-    issue_meta(m, slots, gptr, t, N, lane);
-  } else {
-    m.slot = reinterpret_cast<const unsigned short*>(slots)[(long)t * N + (lane < N ? lane : N - 1)];
-    m.gp = gptr[t + (lane & 1)];
-  }
-}
-template <int LAY>
-__device__ __forceinline__ int slot_word_l(int v) {
-  if constexpr (LAY == LAY_PAD4) return v;
-  else return compact_slot_word(v);
+  const long i = (long)t * N + (lane < N ? lane : N - 1);
+  if constexpr (LAY == LAY_PAD4) m.slot = slots[i];
+  else m.slot = reinterpret_cast<const unsigned short*>(slots)[i];
+  m.gp = gptr[t + (lane & 1)];
 }
 
-// One 4-entry group of a row in the layout LAY: ecv() -> tile() -> fma() leaves its contribution in `a` (PassSteps /
-// PlaneSteps for LAY_PAD4, statement for statement).  ecv_: the graph's ecv region in LDS, ev: its value stream.
+// One 4-entry group of a row in the layout LAY, the one place that knows how a group is read: ecv() -> tile() -> fma() leaves
+// its contribution in `a`.  The steps are separate so that the FULL kernels can place them between MFMAs (the compiler keeps
+// MFMAs in one clump otherwise, and an in-order wave cannot overlap a clump with what follows it).  ecv_: the graph's ecv region
+// in LDS, ev: its value stream (LAY_VALS), s: index of the group's first entry (a multiple of 4).  LAY_PAD4: 2 ds_read_b128
+// fetch the (col, value) pairs, 4 ds_read_b128 the neighbour rows.  Padding entries are (col = FN, val = 0): they read the
+// all-zero row, 0 * 0, never 0 * inf -- no masks.
 template <int LAY>
 struct Grp4 {
   i32x4 q0, q1;                 // LAY_PAD4: the four (col, value bits) pairs
@@ -446,83 +386,72 @@ struct Grp4 {
       x3 = ldv4(reinterpret_cast<const float*>(sb + (cw[1] >> 16)));
     }
   }
+  template <int I>
+  __device__ __forceinline__ float val() const {   // value of entry I (LAY_PAD4, LAY_VALS)
+    if constexpr (LAY == LAY_PAD4) return __int_as_float(I == 0 ? q0.y : I == 1 ? q0.w : I == 2 ? q1.y : q1.w);
+    else return v[I];
+  }
   __device__ __forceinline__ void fma() {
     if constexpr (LAY == LAY_UNIT) {
       a = x0;
       add4(a, x1); add4(a, x2); add4(a, x3);
     } else {
-      const float v0 = LAY == LAY_PAD4 ? __int_as_float(q0.y) : v[0];
+      const float v0 = val<0>();
       a[0] = v0 * x0[0]; a[1] = v0 * x0[1]; a[2] = v0 * x0[2]; a[3] = v0 * x0[3];
-      fma4(a, LAY == LAY_PAD4 ? __int_as_float(q0.w) : v[1], x1);
-      fma4(a, LAY == LAY_PAD4 ? __int_as_float(q1.y) : v[2], x2);
-      fma4(a, LAY == LAY_PAD4 ? __int_as_float(q1.w) : v[3], x3);
+      fma4(a, val<1>(), x1);
+      fma4(a, val<2>(), x2);
+      fma4(a, val<3>(), x3);
     }
   }
 };
-// gather4 in the layout LAY (the sum starts from +0, as gather4's does)
+// The whole group k..k+3 at once.  The sum starts from +0: a different instruction sequence from Grp4::fma.
 template <int LAY>
-__device__ __forceinline__ f32x4 gather4_l(const int2* ecv, const float* ev, const float* srcl, int k) {
-  if constexpr (LAY == LAY_PAD4) {
-    return gather4(ecv, srcl, k);
+__device__ __forceinline__ f32x4 gather4(const int2* ecv, const float* ev, const float* srcl, int k) {
+  Grp4<LAY> q;
+  q.ecv(ecv, ev, k);
+  q.tile(srcl);
+  f32x4 a0 = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (LAY == LAY_UNIT) {
+    add4(a0, q.x0); add4(a0, q.x1); add4(a0, q.x2); add4(a0, q.x3);
   } else {
-    Grp4<LAY> q;
-    q.ecv(ecv, ev, k);
-    q.tile(srcl);
-    f32x4 a0 = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (LAY == LAY_UNIT) {
-      add4(a0, q.x0); add4(a0, q.x1); add4(a0, q.x2); add4(a0, q.x3);
-    } else {
-      fma4(a0, q.v[0], q.x0); fma4(a0, q.v[1], q.x1); fma4(a0, q.v[2], q.x2); fma4(a0, q.v[3], q.x3);
-    }
-    return a0;
+    fma4(a0, q.template val<0>(), q.x0); fma4(a0, q.template val<1>(), q.x1);
+    fma4(a0, q.template val<2>(), q.x2); fma4(a0, q.template val<3>(), q.x3);
   }
+  return a0;
 }
-// rows longer than 4 entries (PassSteps::tail)
+// Rows longer than 4 entries.  Rows are ordered by decreasing length in the slot table, so this fires only in the first
+// pass or two of a graph.
 template <int LAY>
 __device__ __forceinline__ void grp_tail(f32x4& a, int s, int len, const int2* ecv, const float* ev, const float* srcl) {
   if (__builtin_amdgcn_ballot_w64(len > 4)) {
     for (int k = 4; __builtin_amdgcn_ballot_w64(k < len); k += 4)
-      if (k < len) add4(a, gather4_l<LAY>(ecv, ev, srcl, s + k));
+      if (k < len) add4(a, gather4<LAY>(ecv, ev, srcl, s + k));
   }
 }
 
 // Sparse aggregation of one graph out of a gather tile (row stride FD) without MFMA overlap: lane
 // (sub, cl) produces the float4 [4cl, 4cl+4) of the rows of slots j = 4p + sub.
 // emit(row, cl, acc) receives every row exactly once.
-template <bool FULL, typename Emit>
+template <typename Emit>
 __device__ __forceinline__ void aggregate_rows(const int2* ecv, const int* tab, const float* tile,
                                                int N, int dcols, int lane, Emit&& emit) {
   const int sub = lane >> 4, cl = lane & 15;
   const float* srcl = tile + cl * 4;
-  if constexpr (FULL) {
-#pragma unroll
-    for (int p8 = 0; p8 < 8; ++p8) {
-      PassSteps ps;
-      ps.slot(tab, 4 * p8 + sub);
-      ps.ecv(ecv);
-      ps.tile(srcl);
-      ps.fma();
-      ps.tail(ecv, srcl);
-      emit(ps.row, cl, ps.a);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  } else {
-    const bool col_ok = cl * 4 < dcols;
-    for (int j0 = 0; j0 < N; j0 += 4) {
-      const int j = j0 + sub;
-      const bool ok = (j < N) && col_ok;
-      int s_, len, row;
-      unpack_slot(tab[ok ? j : 0], s_, len, row);
-      if (!ok) len = 0;
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      for (int k = 0; __builtin_amdgcn_ballot_w64(k < len); k += 4)
-        if (k < len) add4(acc, gather4(ecv, srcl, s_ + k));
-      if (ok) emit(row, cl, acc);
-    }
+  const bool col_ok = cl * 4 < dcols;
+  for (int j0 = 0; j0 < N; j0 += 4) {
+    const int j = j0 + sub;
+    const bool ok = (j < N) && col_ok;
+    int s_, len, row;
+    unpack_slot(tab[ok ? j : 0], s_, len, row);
+    if (!ok) len = 0;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; __builtin_amdgcn_ballot_w64(k < len); k += 4)
+      if (k < len) add4(acc, gather4<LAY_PAD4>(ecv, nullptr, srcl, s_ + k));
+    if (ok) emit(row, cl, acc);
   }
 }
 
-// aggregate_rows<true> in the adjacency layout LAY (the FULL forward)
+// The FULL forward's aggregation in the adjacency layout LAY: 8 straight-line passes of 4 rows, one scheduling scope each
 template <int LAY, typename Emit>
 __device__ __forceinline__ void aggregate_rows_full(const int2* ecv, const float* ev, const int* tab, const float* tile,
                                                     int lane, Emit&& emit) {
@@ -663,7 +592,7 @@ __global__ __launch_bounds__(512, 2) void graphconv_fwd_kernel(
     wave_sync();
 
     float* ot = out + (long)t * N * dout;
-    aggregate_rows<false>(ws.ecv, ws.rp, ws.b, rows, dout, lane, [&](int r, int cl, f32x4 acc) {
+    aggregate_rows(ws.ecv, ws.rp, ws.b, rows, dout, lane, [&](int r, int cl, f32x4 acc) {
       if constexpr (VEC) {
         stv4(ot + (long)r * dout + cl * 4, acc);
       } else {
@@ -843,12 +772,6 @@ __global__ __launch_bounds__(512, 2) void graphconv_fwd_full_kernel(
     cnt = cnt_n;
   };
 
-#ifdef KGCN_FWD_STAGGER                          // development: the SIMD's second wave starts half a step late
-  if (wave >= wpb / 2) {
-#pragma unroll 1
-    for (int k = 0; k < KGCN_FWD_STAGGER; ++k) __builtin_amdgcn_s_sleep(16);
-  }
-#endif
   step(std::false_type{});                       // first graph: nothing to aggregate yet
   while (has_next) step(std::true_type{});
   aggregate_prev();                              // epilogue: the last graph
@@ -864,7 +787,6 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_kernel(
     const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ g,
     float* __restrict__ dx, float* __restrict__ part_dw, float* __restrict__ part_db, int T, int N,
     int din, int dout, int max_nnz, int pack) {
-  constexpr bool FULL = false;
   constexpr bool VEC = MODE == 2;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
@@ -922,7 +844,7 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_kernel(
 
       PROBE(1)
       // ---- 2. dFW = A^T @ g -> dFW tile (odd stride), dbias partial ----------------------------
-      aggregate_rows<FULL>(ws.ecv, ws.rp, ws.b, rows, dout, lane, [&](int r, int cl, f32x4 acc) {
+      aggregate_rows(ws.ecv, ws.rp, ws.b, rows, dout, lane, [&](int r, int cl, f32x4 acc) {
         float* d = ws.a + r * BLD + cl * 4;
         d[0] = acc[0]; d[1] = acc[1]; d[2] = acc[2]; d[3] = acc[3];
         dbacc += acc;
@@ -979,7 +901,7 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_kernel(
 
       PROBE(4)
       // ---- 6. dX = dFW @ W^T (A operand straight from the odd-stride LDS tile) ------------------
-      if (FULL || dx) {
+      if (dx) {
         f32x16 c0, c1;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { c0[r] = 0.f; c1[r] = 0.f; }
@@ -1151,25 +1073,44 @@ __device__ __forceinline__ int slot_plane_word(int v) {
   return (int)((u & 0xfffu) | (((u >> 16) & 0xffu) << 12) | (rw << 24));
 }
 
-struct PlaneSteps {       // PassSteps on the plane slot word
+// One row of an aggregation pass of the planes / pairs kernel: its plane slot word and its first group in the layout LAY
+template <int LAY>
+struct PlaneRow : Grp4<LAY> {
   int s, len;
   unsigned rw;            // row word << 4 (byte address share of the row)
-  i32x4 q0, q1;
-  f32x4 x0, x1, x2, x3;
-  f32x4 a;
   __device__ __forceinline__ void slot(const int* tab, int j) {
     const unsigned u = (unsigned)tab[j];
     s = (int)(u & 0xfffu);
     len = (int)((u >> 12) & 0xffu);
     rw = (u >> 24) << 4;
   }
-  __device__ __forceinline__ void tail(const int2* ecv_, const float* srcl) {
-    if (__builtin_amdgcn_ballot_w64(len > 4)) {
-      for (int k = 4; __builtin_amdgcn_ballot_w64(k < len); k += 4)
-        if (k < len) add4(a, gather4(ecv_, srcl, s + k));
-    }
+  __device__ __forceinline__ void tail(const int2* ecv_, const float* ev, const float* srcl) {
+    grp_tail<LAY>(this->a, s, len, ecv_, ev, srcl);
   }
 };
+using PlaneSteps = PlaneRow<LAY_PAD4>;
+
+// finished row -> the three planes at (row word ^ lx), lx = lane constant | plane buffer; its share of dbias
+template <int LAY>
+__device__ __forceinline__ void emit_planes(unsigned lx, const PlaneRow<LAY>& q, f32x4& dbacc) {
+  unsigned q1, q2, q3, r1, r2, r3;
+  split_pair(q.a[0], q.a[1], q1, q2, q3);
+  split_pair(q.a[2], q.a[3], r1, r2, r3);
+  const unsigned ad = q.rw ^ lx;
+  lds_st64(ad, q1, r1);
+  lds_st64(ad + PL_BYTES, q2, r2);
+  lds_st64(ad + 2 * PL_BYTES, q3, r3);
+  add4(dbacc, q.a);
+}
+
+// k-th graph of a wave / pair that owns t0, t0 + stride, .. tl, clamped to its last one
+__device__ __forceinline__ int graph_at(int t0, int stride, int tl, int k) {
+#ifdef KGCN_ABL_HOT       // development: two graphs per wave, cache resident -- the kernel without HBM traffic
+  k &= 1;
+#endif
+  const int t = t0 + k * stride;
+  return t < tl ? t : tl;
+}
 template <typename Emit>
 __device__ __forceinline__ void plane_half(PlaneSteps& P, int h, bool do_emit, const int* tab, int j,
                                            const int2* ecv, const float* srcl, Emit&& emit) {
@@ -1265,11 +1206,7 @@ __global__ __launch_bounds__(256, 1) void graphconv_bwd_planes_kernel(
   if (t0 < T) {
     const int cntw = (T - 1 - t0) / nwaves + 1;              // graphs of this wave
     const int tl = t0 + (cntw - 1) * nwaves;                  // its last graph
-#ifdef KGCN_ABL_HOT
-    auto gidx = [&](int k) { const int t = t0 + (k & 1) * nwaves; return t < tl ? t : tl; };
-#else
-    auto gidx = [&](int k) { const int t = t0 + k * nwaves; return t < tl ? t : tl; };  // clamped
-#endif
+    auto gidx = [&](int k) { return graph_at(t0, nwaves, tl, k); };
     const float* srcl = gt + cl * 4;
     const int xlane = (8 * hi) * D + 2 * li;                  // lane share of the x fragment addresses (floats)
 
@@ -1331,24 +1268,17 @@ __global__ __launch_bounds__(256, 1) void graphconv_bwd_planes_kernel(
     };
     // finished aggregation pass -> planes of buffer `eb` (lane constant ^ row word), dbias
     auto emit_to = [&](unsigned lx, const PlaneSteps& q) __attribute__((always_inline)) {
-      unsigned q1, q2, q3, r1, r2, r3;
-      split_pair(q.a[0], q.a[1], q1, q2, q3);
-      split_pair(q.a[2], q.a[3], r1, r2, r3);
-      const unsigned ad = q.rw ^ lx;
-      lds_st64(ad, q1, r1);
-      lds_st64(ad + PL_BYTES, q2, r2);
-      lds_st64(ad + 2 * PL_BYTES, q3, r3);
-      add4(dbacc, q.a);
+      emit_planes(lx, q, dbacc);
       KGCN_PIN4(dbacc[0], dbacc[1], dbacc[2], dbacc[3]);
     };
 
     // ---- prologue: graph 0 aggregated without overlap; the pipeline state of iteration 0 -------
-    issue_meta(m_a, slots_t, gptr_t, gidx(0), N, lane);
+    issue_meta_l<LAY_PAD4>(m_a, slots_t, gptr_t, gidx(0), N, lane);
     int base_a = meta_base(m_a), cnt_a = meta_cnt(m_a);
     issue_tile<true>(gpf, g + (long)gidx(0) * N * D, 512, lane);
     issue_cv(cpf, cv_t, base_a, cnt_a, lane);
     issue_x(0);
-    issue_meta(m_b, slots_t, gptr_t, gidx(1), N, lane);
+    issue_meta_l<LAY_PAD4>(m_b, slots_t, gptr_t, gidx(1), N, lane);
     land_tile<true>(gpf, gt, FD, 512, 16, lane);
     land_csr(cpf, ecv0, tab0, cv_t, slot_plane_word(m_a.slot), base_a, cnt_a, N, lane);
     wave_sync();
@@ -1358,23 +1288,17 @@ __global__ __launch_bounds__(256, 1) void graphconv_bwd_planes_kernel(
     cnt_a = meta_cnt(m_a);
     issue_tile<true>(gpf, g + (long)gidx(1) * N * D, 512, lane);
     issue_cv(cpf, cv_t, base_a, cnt_a, lane);
-    issue_meta(m_b, slots_t, gptr_t, gidx(2), N, lane);
+    issue_meta_l<LAY_PAD4>(m_b, slots_t, gptr_t, gidx(2), N, lane);
     {
       const unsigned lx0 = lanexor | pl0;
 #pragma unroll
       for (int p8 = 0; p8 < 8; ++p8) {
         PlaneSteps ps;
         ps.slot(tab0, 4 * p8 + sub);
-        ps.q0 = *reinterpret_cast<const i32x4*>(ecv0 + ps.s);
-        ps.q1 = *reinterpret_cast<const i32x4*>(ecv0 + ps.s + 2);
-        ps.x0 = ldv4(srcl + ps.q0.x * FD); ps.x1 = ldv4(srcl + ps.q0.z * FD);
-        ps.x2 = ldv4(srcl + ps.q1.x * FD); ps.x3 = ldv4(srcl + ps.q1.z * FD);
-        const float v = __int_as_float(ps.q0.y);
-        ps.a[0] = v * ps.x0[0]; ps.a[1] = v * ps.x0[1]; ps.a[2] = v * ps.x0[2]; ps.a[3] = v * ps.x0[3];
-        fma4(ps.a, __int_as_float(ps.q0.w), ps.x1);
-        fma4(ps.a, __int_as_float(ps.q1.y), ps.x2);
-        fma4(ps.a, __int_as_float(ps.q1.w), ps.x3);
-        ps.tail(ecv0, srcl);
+        ps.ecv(ecv0, nullptr, ps.s);
+        ps.tile(srcl);
+        ps.fma();
+        ps.tail(ecv0, nullptr, srcl);
         emit_to(lx0, ps);
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -1394,7 +1318,7 @@ __global__ __launch_bounds__(256, 1) void graphconv_bwd_planes_kernel(
     cnt_a = meta_cnt(m_a);
     issue_tile<true>(gpf, g + (long)gidx(2) * N * D, 512, lane);
     issue_cv(cpf, cv_t, base_a, cnt_a, lane);
-    issue_meta(m_b, slots_t, gptr_t, gidx(3), N, lane);
+    issue_meta_l<LAY_PAD4>(m_b, slots_t, gptr_t, gidx(3), N, lane);
     static_for<6>([&](auto c) __attribute__((always_inline)) {
       constexpr int v = decltype(c)::value;
       read_bf(BF0, std::integral_constant<int, 0>{}, std::integral_constant<int, v / 3>{},
@@ -1433,8 +1357,8 @@ __global__ __launch_bounds__(256, 1) void graphconv_bwd_planes_kernel(
         constexpr int j = decltype(jc)::value, gq = j >> 4, wq = j & 15;
         if constexpr ((wq & 1) == 0) plane_half(qa, wq >> 1, gq > 0, tab_n, 8 * gq + sub, ecv_n, srcl, emit);
         else plane_half(qb, wq >> 1, gq > 0, tab_n, 8 * gq + 4 + sub, ecv_n, srcl, emit);
-        if constexpr (wq == 14) qa.tail(ecv_n, srcl);
-        if constexpr (wq == 15) qb.tail(ecv_n, srcl);
+        if constexpr (wq == 14) qa.tail(ecv_n, nullptr, srcl);
+        if constexpr (wq == 15) qb.tail(ecv_n, nullptr, srcl);
       };
       u32x4 BF1[2][3];
       static_for<2>([&](auto ksc) __attribute__((always_inline)) {
@@ -1466,17 +1390,13 @@ __global__ __launch_bounds__(256, 1) void graphconv_bwd_planes_kernel(
           if constexpr (AGG) agg_half(std::integral_constant<int, 32 * ks + m>{});
           __builtin_amdgcn_sched_barrier(0);
         });
-#ifndef KGCN_PROBE_TAIL
         if constexpr (ks == 0) { PROBE(6) }
-#endif
         if constexpr (AGG) {
           static_for<8>([&](auto rc) __attribute__((always_inline)) {
             agg_half(std::integral_constant<int, 32 * ks + 24 + decltype(rc)::value>{});
           });
         }
-#ifndef KGCN_PROBE_TAIL
         if constexpr (ks == 0) { PROBE(7) }
-#endif
       });
       read_fa_at(std::integral_constant<int, 0>{}, cur_off);   // phase B(i), k-step 0: in flight behind the last emits
       if constexpr (AGG) {
@@ -1533,20 +1453,11 @@ __global__ __launch_bounds__(256, 1) void graphconv_bwd_planes_kernel(
           // s_waitcnt vmcnt(~0) on every prefetch load of this phase at the top of the next iteration)
           asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %3"
                        : "=&v"(m_a.slot), "=&v"(m_a.gp) : "v"(m_b.slot), "v"(m_b.gp));
-          issue_meta(m_b, slots_t, gptr_t, gidx(i + 4), N, lane);
+          issue_meta_l<LAY_PAD4>(m_b, slots_t, gptr_t, gidx(i + 4), N, lane);
         }
-#ifdef KGCN_PROBE_TAIL
-        if constexpr (m == 35) { PROBE(1) }
-        if constexpr (m == 39) { PROBE(2) }
-        if constexpr (m == 43) { PROBE(3) }
-        if constexpr (m == 44) { PROBE(4) }
-        if constexpr (m == 45) { PROBE(6) }
-        if constexpr (m == 46) { PROBE(7) }
-#else
         if constexpr (m == 11) { PROBE(2) }
         if constexpr (m == 23) { PROBE(3) }
         if constexpr (m == 35) { PROBE(4) }
-#endif
         if constexpr (MV && m >= 42) {                    // dFW(i+1), k-step 0: fragments for phase A(i+1)
           constexpr int v = m - 42;
           read_bf(BF0, std::integral_constant<int, 0>{}, std::integral_constant<int, v / 3>{},
@@ -1660,28 +1571,19 @@ __global__ __launch_bounds__(256, 1) void graphconv_bwd_planes_kernel(
 // Iteration counts are uniform (every wave passes the same barriers): the launcher takes this kernel for T >= 2 pairs-in-flight
 // graphs only, so a pair owns cnt_max or cnt_max - 1 >= 2 graphs; the one iteration a short pair lacks is skipped under uniform
 // branches that hold no vector-memory instruction.
+// Measured during round 6 and removed from the source since (profiles/r06_bwd_pairs_history.txt, items 2a - 2e):
+//   * The roles of a pair sat on different SIMDs (pair = wave >> 1): 0.518-0.524 ms against 0.475-0.485 (2c).
+//   * The rows were split 1 : 3, 3 : 1 and not at all between the roles (2b: slower), and role B took other pairs of row groups
+//     than {0, 2} (2d: within noise).
+//   * Role A aggregated before it multiplied, and role B multiplied before it aggregated (2b); one role alone reordered: no gain (2c).
+//   * One scheduling scope spanned a role's row groups instead of one scope per group: within noise (2d).
+//   * A pair-local rendezvous with arrival counters in LDS replaced the workgroup barrier: 0.4965-0.4984 against 0.4944-0.4949 (2e).
+// Outside this kernel: the forward's second wave per SIMD started half a step late (same file, item 3: nothing), and the planes
+// kernel ran as k workgroups per CU slot, each with 1 / k of the graphs (profiles/r05_headline_experiments.txt: 3 - 13 % slower).
 // ------------------------------------------------------------------------------------------------
 constexpr int BP_PAIRS = 4;
 #ifndef KGCN_BWD_PAIRS
 #define KGCN_BWD_PAIRS 1        // 0: the one-wave-per-graph planes kernel for every batch
-#endif
-#ifndef KGCN_BP_B_GROUPS
-#define KGCN_BP_B_GROUPS 5      // bit mask of the row groups (four of eight rows each, longest rows first) role B aggregates; role A the others
-#endif
-#ifndef KGCN_BP_AGG_SCOPE
-#define KGCN_BP_AGG_SCOPE 0     // 0: one scheduling scope per row group (two passes in flight); 1: a role's groups in ONE scope
-#endif
-#ifndef KGCN_BP_PAIR_SYNC
-#define KGCN_BP_PAIR_SYNC 0     // 1 (development): pair-local rendezvous instead of the workgroup barrier per graph
-#endif
-#ifndef KGCN_BP_A_ORDER
-#define KGCN_BP_A_ORDER 1       // role A: 0 aggregate, multiply, land; 1 multiply, aggregate, land
-#endif
-#ifndef KGCN_BP_B_ORDER
-#define KGCN_BP_B_ORDER 1       // role B: 0 multiply, aggregate, split; 1 aggregate, multiply, split
-#endif
-#ifndef KGCN_BP_ROLE_BIT
-#define KGCN_BP_ROLE_BIT 2      // 2: pair = wave & 3, role = wave >> 2 (the two roles of a pair share a SIMD); 0: pair = wave >> 1, role = wave & 1
 #endif
 __device__ __forceinline__ void bp_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
@@ -1696,8 +1598,7 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_pairs_kernel(
   constexpr int N = FN, D = FD;
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
-  const int pair = KGCN_BP_ROLE_BIT == 2 ? (wave & 3) : (wave >> 1);
-  const int role = KGCN_BP_ROLE_BIT == 2 ? (wave >> 2) : (wave & 1);
+  const int pair = wave & 3, role = wave >> 2;                    // the two roles of a pair share a SIMD
   const int li = lane & 31, hi = lane >> 5;
   const int sub = lane >> 4, cl = lane & 15;
   static_assert(BWD_WPB_ == BP_PAIRS, "one graph slot of the planes layout per pair");
@@ -1721,11 +1622,7 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_pairs_kernel(
   const int cntw = (T - 1 - t0) / npairs + 1;                     // graphs of this pair: cnt_max or cnt_max - 1
   const int tl = t0 + (cntw - 1) * npairs;                        // its last graph
   const bool whole = cntw == cnt_max;                             // uniform
-#ifdef KGCN_ABL_HOT                                                 // development: two graphs per pair, cache resident -- the kernel without HBM
-  auto gidx = [&](int k) { const int t = t0 + (k & 1) * npairs; return t < tl ? t : tl; };
-#else
-  auto gidx = [&](int k) { const int t = t0 + k * npairs; return t < tl ? t : tl; };  // clamped
-#endif
+  auto gidx = [&](int k) { return graph_at(t0, npairs, tl, k); };
   PROBE_DECL
 
   f32x16 dw00, dw01, dw10, dw11;                                  // role B
@@ -1738,71 +1635,41 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_pairs_kernel(
   const unsigned h_e = (unsigned)cl >> 3;
   const unsigned lanexor = (h_e << 8) | (h_e << 6) | ((((unsigned)cl & 7) >> 1) << 4) | (((unsigned)cl & 1) << 3);
   const float* srcl = gt + cl * 4;
-  // one row of a pass: plane slot word (PlaneSteps::slot) + its first group in the layout LAY
-  struct PairRow : Grp4<LAY> { int s, len; unsigned rw; };
-  auto emit_to = [&](unsigned lx, const PairRow& q) __attribute__((always_inline)) {
-    unsigned q1, q2, q3, r1, r2, r3;
-    split_pair(q.a[0], q.a[1], q1, q2, q3);
-    split_pair(q.a[2], q.a[3], r1, r2, r3);
-    const unsigned ad = q.rw ^ lx;
-    lds_st64(ad, q1, r1);
-    lds_st64(ad + PL_BYTES, q2, r2);
-    lds_st64(ad + 2 * PL_BYTES, q3, r3);
-    add4(dbacc, q.a);
-  };
-  auto row_slot = [&](PairRow& q, const int* tab, int j) __attribute__((always_inline)) {
-    const unsigned u = (unsigned)tab[j];
-    q.s = (int)(u & 0xfffu);
-    q.len = (int)((u >> 12) & 0xffu);
-    q.rw = (u >> 24) << 4;
-  };
-  // row groups gq = G0 .. G1 - 1 of the graph in the gather tile -> planes at `plane_off`, two passes in flight
+  // (a lambda of its own, as in the planes kernel: calling emit_planes directly renames two registers of the LAY_UNIT kernel)
+  auto emit_to = [&](unsigned lx, const PlaneRow<LAY>& q) __attribute__((always_inline)) { emit_planes(lx, q, dbacc); };
+  // the row groups of the bit mask `maskc` of the graph in the gather tile -> planes at `plane_off`, two passes in flight and
+  // one scheduling scope per row group
   auto aggregate = [&](auto maskc, const int2* ecv, const int* tab, unsigned plane_off) __attribute__((always_inline)) {
     const unsigned lx = lanexor | (pl0 + plane_off);
     const float* ev = ev_of(ecv);
     static_for<4>([&](auto gqc) __attribute__((always_inline)) {
       constexpr int gq = decltype(gqc)::value;
       if constexpr (((decltype(maskc)::value >> gq) & 1) != 0) {
-      PairRow qa, qb;
-      row_slot(qa, tab, 8 * gq + sub);
-      row_slot(qb, tab, 8 * gq + 4 + sub);
-      qa.ecv(ecv, ev, qa.s);
-      qb.ecv(ecv, ev, qb.s);
-      qa.tile(srcl);
-      qb.tile(srcl);
-      qa.fma();
-      qb.fma();
-      grp_tail<LAY>(qa.a, qa.s, qa.len, ecv, ev, srcl);
-      grp_tail<LAY>(qb.a, qb.s, qb.len, ecv, ev, srcl);
-      emit_to(lx, qa);
-      emit_to(lx, qb);
-      if constexpr (KGCN_BP_AGG_SCOPE == 0) __builtin_amdgcn_sched_barrier(0);
+        PlaneRow<LAY> qa, qb;
+        qa.slot(tab, 8 * gq + sub);
+        qb.slot(tab, 8 * gq + 4 + sub);
+        qa.ecv(ecv, ev, qa.s);
+        qb.ecv(ecv, ev, qb.s);
+        qa.tile(srcl);
+        qb.tile(srcl);
+        qa.fma();
+        qb.fma();
+        qa.tail(ecv, ev, srcl);
+        qb.tail(ecv, ev, srcl);
+        emit_to(lx, qa);
+        emit_to(lx, qb);
+        __builtin_amdgcn_sched_barrier(0);
       }
     });
-    if constexpr (KGCN_BP_AGG_SCOPE != 0) __builtin_amdgcn_sched_barrier(0);
   };
   using MALL = std::integral_constant<int, 15>;
-  using MB = std::integral_constant<int, KGCN_BP_B_GROUPS>;                  // role B's row groups (bit mask), role A's: the others
-  using MA = std::integral_constant<int, 15 & ~KGCN_BP_B_GROUPS>;
-  constexpr int NB = KGCN_BP_B_GROUPS;                                          // (0: role A aggregates alone)
-  constexpr int NA = 15 & ~KGCN_BP_B_GROUPS;
+  using MB = std::integral_constant<int, 5>;                      // role B's row groups {0, 2}
+  using MA = std::integral_constant<int, 10>;                     // role A's row groups {1, 3}
   // hand-over inside the pair: role B has finished READING the gather tile for graph i + 1 (flag = i + 1) before role A lands
   // g(i + 2) in it.  LDS executes a wave's operations in order, so the flag write follows B's last gather read.
   KGCN_LDS volatile int* const agg_flag = (KGCN_LDS volatile int*)(uintptr_t)lds_off(tab0 + FN + 2);
-  // development (KGCN_BP_PAIR_SYNC): the end-of-iteration rendezvous between the TWO waves of a pair only (arrival counters in LDS)
-  // instead of the workgroup barrier that also ties the four pairs together
-  KGCN_LDS volatile int* const arrive_mine = (KGCN_LDS volatile int*)(uintptr_t)lds_off(tab0 + (FN + 4) + FN + 2 + role);
-  KGCN_LDS volatile int* const arrive_other = (KGCN_LDS volatile int*)(uintptr_t)lds_off(tab0 + (FN + 4) + FN + 2 + (role ^ 1));
-  auto iter_sync = [&](int i) __attribute__((always_inline)) {
-    if constexpr (KGCN_BP_PAIR_SYNC != 0) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (lane == 0) *arrive_mine = i + 1;
-      while (*arrive_other < i + 1) __builtin_amdgcn_s_sleep(1);
-      asm volatile("" ::: "memory");
-    } else {
-      bp_barrier();
-    }
-  };
+  // spare word FN + 2 + role of the second slot table: zeroed once per role, read by nobody (kept: the schedule moves without the store)
+  KGCN_LDS volatile int* const spare_word = (KGCN_LDS volatile int*)(uintptr_t)lds_off(tab0 + (FN + 4) + FN + 2 + role);
 
   if (role == 0) {
     // =========================================== role A ===========================================================
@@ -1871,7 +1738,7 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_pairs_kernel(
     issue_tile<true>(gpf, g + (long)gidx(2) * N * D, 512, lane);
     issue_csr(base_a, cnt_a);
     issue_meta_l<LAY>(m_b, slots_t, gptr_t, gidx(3), N, lane);
-    if (lane == 0) *arrive_mine = 0;
+    if (lane == 0) *spare_word = 0;
     bp_barrier();                                                 // barrier 1: dFW(0) in planes 0
 
     f32x16 c0, c1;
@@ -1941,37 +1808,24 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_pairs_kernel(
     int cur = 0;
     PROBE(0)
     for (int i = 0; i < cnt_max - 2; ++i) {                       // graphs i and i + 1 exist for every pair
-      if constexpr (KGCN_BP_A_ORDER == 0) {
-        if constexpr (NA != 0)
-          aggregate(MA{}, ecv0 + (cur ^ 1) * ecv_stride, tab0 + (cur ^ 1) * (FN + 4), cur ? 0u : (unsigned)DFWP_BYTES);
-        PROBE(1)
-        dx_of(i, cur);
-        PROBE(3)
-      } else {                                                    // the multiplications of both roles first
-        dx_of(i, cur);
-        PROBE(3)
-        if constexpr (NA != 0)
-          aggregate(MA{}, ecv0 + (cur ^ 1) * ecv_stride, tab0 + (cur ^ 1) * (FN + 4), cur ? 0u : (unsigned)DFWP_BYTES);
-        PROBE(1)
-      }
-      if constexpr (NB != 0) {
-        while (*agg_flag < i + 1) __builtin_amdgcn_s_sleep(1);    // role B is through with the gather tile (normally long ago)
-      }
+      dx_of(i, cur);                                              // the multiplications of both roles first
+      PROBE(3)
+      aggregate(MA{}, ecv0 + (cur ^ 1) * ecv_stride, tab0 + (cur ^ 1) * (FN + 4), cur ? 0u : (unsigned)DFWP_BYTES);
+      PROBE(1)
+      while (*agg_flag < i + 1) __builtin_amdgcn_s_sleep(1);      // role B is through with the gather tile (normally long ago)
       wave_sync();
       PROBE(6)
       land_and_prefetch(i, cur);
       PROBE(2)
-      iter_sync(i);
+      bp_barrier();
       PROBE(4)
       cur ^= 1;
     }
     // iteration cnt_max - 2: graph cnt_max - 1 exists for a whole pair only
-    if constexpr (NA != 0) {
-      if (whole) aggregate(MA{}, ecv0 + (cur ^ 1) * ecv_stride, tab0 + (cur ^ 1) * (FN + 4), cur ? 0u : (unsigned)DFWP_BYTES);
-    }
+    if (whole) aggregate(MA{}, ecv0 + (cur ^ 1) * ecv_stride, tab0 + (cur ^ 1) * (FN + 4), cur ? 0u : (unsigned)DFWP_BYTES);
     wave_sync();
     dx_of(cnt_max - 2, cur);
-    iter_sync(cnt_max - 2);
+    bp_barrier();
     cur ^= 1;
     // iteration cnt_max - 1
     if (whole) dx_of(cnt_max - 1, cur);
@@ -2072,29 +1926,23 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_pairs_kernel(
       static_for<16>([&](auto qc) __attribute__((always_inline)) { load_x(xb, qc); });
     }
     split_and_reload(1);
-    if (lane == 0) { *agg_flag = 0; *arrive_mine = 0; }
+    if (lane == 0) { *agg_flag = 0; *spare_word = 0; }
     bp_barrier();                                                 // barrier 1: dFW(0) in planes 0
 
     int cur = 0;
     PROBE(0)
     for (int i = 0; i < cnt_max - 1; ++i) {                       // graph i exists for every pair
-      if constexpr (KGCN_BP_B_ORDER == 0) {
-        dw_of(cur);                                               // (matrix pipe) while role A aggregates (vector ALU)
-        PROBE(1)
-      }
-      if (NB != 0 && (i < cnt_max - 2 || whole)) {                // uniform; no vector-memory instruction inside
+      if (i < cnt_max - 2 || whole) {                             // uniform; no vector-memory instruction inside
         aggregate(MB{}, ecv0 + (cur ^ 1) * ecv_stride, tab0 + (cur ^ 1) * (FN + 4), cur ? 0u : (unsigned)DFWP_BYTES);
         wave_sync();
         if (lane == 0) *agg_flag = i + 1;
       }
       PROBE(3)
-      if constexpr (KGCN_BP_B_ORDER != 0) {
-        dw_of(cur);
-        PROBE(1)
-      }
+      dw_of(cur);                                                 // (matrix pipe) while role A aggregates (vector ALU)
+      PROBE(1)
       split_and_reload(i + 2);                                    // x(i+1) -> fragments, x(i+2) requested
       PROBE(2)
-      iter_sync(i);
+      bp_barrier();
       PROBE(4)
       cur ^= 1;
     }
@@ -2188,6 +2036,16 @@ static void allow_big_lds(K kernel) {
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
                             hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
 }
+
+// f(std::integral_constant<int, v>{}) for v = 0, 1, 2: a run-time adjacency layout (lay_of) or tile movement mode as the
+// template argument of the kernel to launch
+template <typename F>
+static void with_const3(int v, F&& f) {
+  if (v == 2) f(std::integral_constant<int, 2>{});
+  else if (v == 1) f(std::integral_constant<int, 1>{});
+  else f(std::integral_constant<int, 0>{});
+}
+static_assert(LAY_PAD4 == 0 && LAY_UNIT == 1 && LAY_VALS == 2, "with_const3 covers the three layouts");
 
 static bool is_compact(const kgcn_csr_batch* a) { return a->row_pad == KGCN_ROW_PAD_COMPACT; }
 
@@ -2294,27 +2152,16 @@ extern "C" int kgcn_graphconv_fwd_f32(const kgcn_csr_batch* a, const float* x, c
   const int2* cv = reinterpret_cast<const int2*>(a->cv);
   const int lay = lay_of(a);
   const float* cvals = compact_values(a);
-  if (full_shape && lay == LAY_UNIT)
-    hipLaunchKernelGGL(graphconv_fwd_full_kernel<LAY_UNIT>, grid, block, lds, as_stream(stream), a->slots,
-                       a->graph_ptr, cv, cvals, x, w, bias, out, a->num_graphs, a->max_nnz_per_graph);
-  else if (full_shape && lay == LAY_VALS)
-    hipLaunchKernelGGL(graphconv_fwd_full_kernel<LAY_VALS>, grid, block, lds, as_stream(stream), a->slots,
-                       a->graph_ptr, cv, cvals, x, w, bias, out, a->num_graphs, a->max_nnz_per_graph);
-  else if (full_shape)
-    hipLaunchKernelGGL(graphconv_fwd_full_kernel<LAY_PAD4>, grid, block, lds, as_stream(stream), a->slots,
-                       a->graph_ptr, cv, cvals, x, w, bias, out, a->num_graphs, a->max_nnz_per_graph);
-  else if (mode == 2)
-    hipLaunchKernelGGL(graphconv_fwd_kernel<2>, grid, block, lds, as_stream(stream), a->slots,
-                       a->graph_ptr, cv, x, w, bias, out, a->num_graphs, a->rows, din, dout,
-                       a->max_nnz_per_graph, pack);
-  else if (mode == 1)
-    hipLaunchKernelGGL(graphconv_fwd_kernel<1>, grid, block, lds, as_stream(stream), a->slots,
-                       a->graph_ptr, cv, x, w, bias, out, a->num_graphs, a->rows, din, dout,
-                       a->max_nnz_per_graph, pack);
+  if (full_shape)
+    with_const3(lay, [&](auto L) {
+      hipLaunchKernelGGL(graphconv_fwd_full_kernel<decltype(L)::value>, grid, block, lds, as_stream(stream), a->slots,
+                         a->graph_ptr, cv, cvals, x, w, bias, out, a->num_graphs, a->max_nnz_per_graph);
+    });
   else
-    hipLaunchKernelGGL(graphconv_fwd_kernel<0>, grid, block, lds, as_stream(stream), a->slots,
-                       a->graph_ptr, cv, x, w, bias, out, a->num_graphs, a->rows, din, dout,
-                       a->max_nnz_per_graph, pack);
+    with_const3(mode, [&](auto M) {
+      hipLaunchKernelGGL(graphconv_fwd_kernel<decltype(M)::value>, grid, block, lds, as_stream(stream), a->slots,
+                         a->graph_ptr, cv, x, w, bias, out, a->num_graphs, a->rows, din, dout, a->max_nnz_per_graph, pack);
+    });
   return check_launch("graphconv_fwd_kernel");
 }
 
@@ -2322,11 +2169,7 @@ extern "C" int64_t kgcn_graphconv_bwd_workspace_bytes(int32_t num_graphs, int32_
                                                       int32_t dout) {
   if (num_graphs <= 0 || din <= 0 || dout <= 0) return 0;
   // one partial per persistent workgroup (at most one workgroup per CU)
-#ifdef KGCN_DEV_KNOBS
-  return (int64_t)16 * kNumCU * ((int64_t)din * dout + dout) * 4;         // (room for the KGCN_BWD_GRID_MULT experiment)
-#else
   return (int64_t)kNumCU * ((int64_t)din * dout + dout) * 4;
-#endif
 }
 
 extern "C" int kgcn_graphconv_bwd_f32(const kgcn_csr_batch* at, const float* x, const float* w,
@@ -2355,17 +2198,12 @@ extern "C" int kgcn_graphconv_bwd_f32(const kgcn_csr_batch* at, const float* x, 
   const int pack = (full || is_full(at->rows, din, dout)) ? 1 : pack_factor(at->rows, at->max_nnz_per_graph, FD * FD * 4);
   const size_t per = full ? full_lds / BWD_FULL_WPB : bwd_slice(at->max_nnz_per_graph * pack);
   const int wpb = full ? BWD_FULL_WPB : fused_wpb(per, FD * FD * 4);
-  int blocks = fused_grid((at->num_graphs + pack - 1) / pack, wpb);
+  const int blocks = fused_grid((at->num_graphs + pack - 1) / pack, wpb);
   // two waves per graph slot (graphconv_bwd_pairs_kernel): every pair must own at least two graphs (uniform barrier counts)
   const bool pairs = bwd_pairs_route(at->num_graphs, at->rows, din, dout, at->max_nnz_per_graph, dx != nullptr);
   if (is_compact(at) && !pairs)
     return fail("kgcn_graphconv_bwd_f32: the compact adjacency layout is read by the pairs kernel only (T=%d N=%d din=%d "
                 "dout=%d, dx %s): pass the row-padded batch", at->num_graphs, at->rows, din, dout, dx ? "wanted" : "NULL");
-  // development (the non-persistent form, measured): KGCN_BWD_GRID_MULT = k launches k workgroups per CU slot,
-  // each walking 1 / k of the graphs with its own pipeline fill, W' split and dW partial (k x 256 partials in the second stage) --
-  // the form the kernel's LDS footprint (one 4-wave workgroup per CU) allows.  profiles/r05_headline_experiments.txt
-  static const char* gm = dev_knob("KGCN_BWD_GRID_MULT");
-  if (!pairs && gm && atoi(gm) > 1 && atoi(gm) <= 16 && (long)blocks * atoi(gm) * wpb * 2 <= at->num_graphs) blocks *= atoi(gm);
   const int64_t need = (int64_t)blocks * ((int64_t)din * dout + dout) * 4;
   if (!workspace || workspace_bytes < need)
     return fail("kgcn_graphconv_bwd_f32: workspace %lld < %lld bytes", (long long)workspace_bytes,
@@ -2387,34 +2225,22 @@ extern "C" int kgcn_graphconv_bwd_f32(const kgcn_csr_batch* at, const float* x, 
   const int2* cv = reinterpret_cast<const int2*>(at->cv);
   const int lay = lay_of(at);
   const float* cvals = compact_values(at);
-  if (pairs && lay == LAY_UNIT)
-    hipLaunchKernelGGL(graphconv_bwd_pairs_kernel<LAY_UNIT>, dim3(blocks), dim3(512), lds, s, at->slots,
-                       at->graph_ptr, cv, cvals, x, w, dout_grad, dx, part_dw, part_db, at->num_graphs,
-                       at->max_nnz_per_graph);
-  else if (pairs && lay == LAY_VALS)
-    hipLaunchKernelGGL(graphconv_bwd_pairs_kernel<LAY_VALS>, dim3(blocks), dim3(512), lds, s, at->slots,
-                       at->graph_ptr, cv, cvals, x, w, dout_grad, dx, part_dw, part_db, at->num_graphs,
-                       at->max_nnz_per_graph);
-  else if (pairs)
-    hipLaunchKernelGGL(graphconv_bwd_pairs_kernel<LAY_PAD4>, dim3(blocks), dim3(512), lds, s, at->slots,
-                       at->graph_ptr, cv, cvals, x, w, dout_grad, dx, part_dw, part_db, at->num_graphs,
-                       at->max_nnz_per_graph);
+  if (pairs)
+    with_const3(lay, [&](auto L) {
+      hipLaunchKernelGGL(graphconv_bwd_pairs_kernel<decltype(L)::value>, dim3(blocks), dim3(512), lds, s, at->slots,
+                         at->graph_ptr, cv, cvals, x, w, dout_grad, dx, part_dw, part_db, at->num_graphs,
+                         at->max_nnz_per_graph);
+    });
   else if (full)
     hipLaunchKernelGGL(graphconv_bwd_planes_kernel, dim3(blocks), dim3(64 * wpb), lds, s, at->slots,
                        at->graph_ptr, cv, x, w, dout_grad, dx, part_dw, part_db, at->num_graphs,
                        at->max_nnz_per_graph);
-  else if (mode == 2)
-    hipLaunchKernelGGL(graphconv_bwd_kernel<2>, dim3(blocks), dim3(64 * wpb), lds, s, at->slots,
-                       at->graph_ptr, cv, x, w, dout_grad, dx, part_dw, part_db, at->num_graphs,
-                       at->rows, din, dout, at->max_nnz_per_graph, pack);
-  else if (mode == 1)
-    hipLaunchKernelGGL(graphconv_bwd_kernel<1>, dim3(blocks), dim3(64 * wpb), lds, s, at->slots,
-                       at->graph_ptr, cv, x, w, dout_grad, dx, part_dw, part_db, at->num_graphs,
-                       at->rows, din, dout, at->max_nnz_per_graph, pack);
   else
-    hipLaunchKernelGGL(graphconv_bwd_kernel<0>, dim3(blocks), dim3(64 * wpb), lds, s, at->slots,
-                       at->graph_ptr, cv, x, w, dout_grad, dx, part_dw, part_db, at->num_graphs,
-                       at->rows, din, dout, at->max_nnz_per_graph, pack);
+    with_const3(mode, [&](auto M) {
+      hipLaunchKernelGGL(graphconv_bwd_kernel<decltype(M)::value>, dim3(blocks), dim3(64 * wpb), lds, s, at->slots,
+                         at->graph_ptr, cv, x, w, dout_grad, dx, part_dw, part_db, at->num_graphs, at->rows, din, dout,
+                         at->max_nnz_per_graph, pack);
+    });
   if (int rc = check_launch("graphconv_bwd_kernel")) return rc;
   return launch_reduce_pair(part_dw, (long)din * dout, dw, part_db, dout, dbias, blocks, s);      // (queued inside a deferral scope)
 }
