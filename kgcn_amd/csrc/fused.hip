@@ -68,6 +68,15 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));   // native vector: HIP's
 
 __device__ __forceinline__ f32x4 ldv4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void stv4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
+// Streaming (nontemporal) forms.  Only the FULL forward uses them, for BOTH of its streams (x in, out out: each touched once by
+// the kernel, 819 MB per tensor at the benchmark size against 256 MiB of last-level cache).  Either hint alone loses; together
+// they win, mostly in the BACKWARD that follows (the forward leaves the cache alone).  The backward's own streams stay plain:
+// every hint there loses over a whole step (profiles/fused_ingest_history.txt, DESIGN lesson 47).
+template <bool NT> __device__ __forceinline__ f32x4 ldv4s(const float* p) {
+  if constexpr (NT) return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
+  else return ldv4(p);
+}
+__device__ __forceinline__ void stv4_stream(float* p, f32x4 v) { __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(p)); }
 
 // acc += v * x, component by component as plain v_fma_f32.  Beside f32 MFMAs the packed forms
 // (v_pk_fma_f32 / v_pk_mul_f32, which hipcc forms from float4 arithmetic) cost ~22-26 extra cycles
@@ -118,14 +127,16 @@ struct TileRegs { f32x4 v[8]; };
 struct CsrRegs { i32x4 e0, e1; };   // lane l: entries 2l, 2l+1 and 128+2l, 128+2l+1 (plain members:
                                    // an array member ended up in scratch memory)
 
-template <bool FULL>
+// NT: streaming cache policy (FULL forward only, see ldv4s)
+template <bool FULL, bool NT = false>
 __device__ __forceinline__ void issue_tile(TileRegs& f, const float* __restrict__ src, int n4,
                                            int lane) {
+  static_assert(FULL || !NT, "the streaming policy exists for the FULL tile only");
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
     const int i = lane + q * 64;
     if constexpr (FULL) {
-      f.v[q] = ldv4(src + (long)i * 4);
+      f.v[q] = ldv4s<NT>(src + (long)i * 4);
     } else {
       f32x4 z = {0.f, 0.f, 0.f, 0.f};
       f.v[q] = (i < n4) ? ldv4(src + (long)i * 4) : z;
@@ -625,6 +636,10 @@ __global__ __launch_bounds__(512, 2) void graphconv_fwd_kernel(
 //
 // LDS: p3 table | per wave: x tile [32][68], gather tile [33][64], ONE CSR slice (landed at the end of the
 // step, after the aggregation of the previous graph released it).
+//
+// x is read and out is written with the streaming (nontemporal) cache policy, both or neither (see ldv4s).  The x tile still
+// waits in registers: in the memory skeleton an LDS-DMA into the wave's one tile buffer, requested behind phase 4, does not
+// move the forward's byte pattern beyond noise (tools/bwd_skeleton.hip, arms FI; profiles/fused_ingest_history.txt) -- not built.
 constexpr size_t FWD_FULL_SHARED = 2 * 4 * 64 * 16;   // W p3 fragments: [tile][k-step][lane] x 16 bytes
 
 // LAY: adjacency layout (LAY_PAD4: row_pad = 4, cv = (col, value) pairs; LAY_UNIT / LAY_VALS: compact, cv = column words,
@@ -685,7 +700,7 @@ __global__ __launch_bounds__(512, 2) void graphconv_fwd_full_kernel(
   MetaRegs m_cur, m_nxt;
   issue_meta_l<LAY>(m_cur, slots, gptr, hot(t), N, lane);
   int base = meta_base(m_cur), cnt = meta_cnt(m_cur);
-  issue_tile<true>(fx, x + (long)hot(t) * N * D, 512, lane);
+  issue_tile<true, true>(fx, x + (long)hot(t) * N * D, 512, lane);
   issue_csr(fc, base, cnt);
   int tn = t + nwaves;
   issue_meta_l<LAY>(m_nxt, slots, gptr, hot(tn < T ? tn : t), N, lane);
@@ -697,7 +712,7 @@ __global__ __launch_bounds__(512, 2) void graphconv_fwd_full_kernel(
   auto aggregate_prev = [&]() __attribute__((always_inline)) {
     float* ot = out + (long)hot(t_prev) * N * D;
     aggregate_rows_full<LAY>(ws.ecv, ev, ws.rp, ws.b, lane, [&](int r, int c4, f32x4 v) {
-      stv4(ot + r * D + c4 * 4, v);
+      stv4_stream(ot + r * D + c4 * 4, v);
     });
   };
   auto step = [&](auto agg_tag) __attribute__((always_inline)) {
@@ -705,11 +720,13 @@ __global__ __launch_bounds__(512, 2) void graphconv_fwd_full_kernel(
     PROBE(0)
     // ---- 1. x(t): registers -> LDS; x(t + nwaves) in flight (branch-free: values defined under
     // `if (has_next)` become phis whose copies make the compiler wait for the prefetch right after
-    // issuing it; on the last step the current graph is re-read (L2 hit), unused) ---------------------
+    // issuing it; on the last step the load reads the first 8 KB of W instead, unused: every wave has read W, it sits in L2,
+    // whereas a streamed x tile does not stay there -- re-reading x(t) cost 6 MB of HBM fetches per launch) ------------
     land_tile<true>(fx, ws.a, ALD, 512, 16, lane);
     has_next = tn < T;
     const int tp = has_next ? tn : t;
-    issue_tile<true>(fx, x + (long)hot(tp) * N * D, 512, lane);
+    static_assert(FD * FD >= FN * FD, "W holds at least one tile's floats");
+    issue_tile<true, true>(fx, has_next ? x + (long)hot(tn) * N * D : w, 512, lane);
     wave_sync();
     PROBE(1)
 

@@ -7,10 +7,11 @@
 //   PX  as P with x loaded in the dW A-fragment layout of the shipped kernel (16 x 8-byte loads, two 256-byte rows each)
 //   H   persistent PAIRS: two waves share a graph (wave A: g + CSR in, dX out; wave B: x in), 8 waves per CU   (the two-role form)
 //   N   non-persistent, one wave per graph, no prefetch, as many waves per CU as registers allow       (the SpMM's structure)
-// usage: bwd_skeleton [graphs]
+// usage: bwd_skeleton [graphs [ingest]]   (ingest: only the LDS-DMA / nontemporal arms of skel_fi / skel_hi and their references)
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f2 __attribute__((ext_vector_type(2)));
 
@@ -287,6 +288,199 @@ __global__ __launch_bounds__(NT) void skel_fd(const float* __restrict__ x, const
   }
 }
 
+// ---- ingest arms: how a tile gets from HBM into LDS and how the result leaves ---------------------------------------------------
+// global_load_lds_dwordx4: 1 KiB per wave-instruction, LDS destination = wave-uniform base + 16 x lane, no VGPR destination.
+// AUX 2 = the nt cache-policy bit of gfx950.
+typedef __attribute__((address_space(1))) const void* gptr_t;
+typedef __attribute__((address_space(3))) void* lptr_t;
+template <int AUX>
+__device__ __forceinline__ void glds16(const f4* src_lane, f4* lds_wave_base) {
+  __builtin_amdgcn_global_load_lds((gptr_t)src_lane, (lptr_t)lds_wave_base, 16, 0, AUX);
+}
+template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+template <int NTS> __device__ __forceinline__ void st16(f4* p, f4 v) {
+  if constexpr (NTS != 0) __builtin_nontemporal_store(v, p);
+  else *p = v;
+}
+// the arithmetic stand-ins of skel_h: 48 bf16 MFMAs (one contraction) / 400 v_fma_f32 (one aggregation)
+struct Standin {
+  f16v acc0 = {}, acc1 = {}, acc2 = {}, acc3 = {};
+  bf8 fa, fb;
+  float va[8] = {1.f, 2.f, 3.f, 4.f, 5.f, 6.f, 7.f, 8.f};
+  float vm, vb;
+  __device__ __forceinline__ Standin(int lane) : vm(0.999f + 1e-9f * lane), vb(1e-7f * lane) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { fa[e] = (__bf16)(0.001f * (lane + e)); fb[e] = (__bf16)(0.002f * (lane - e)); }
+  }
+  __device__ __forceinline__ void mfmas() {
+#pragma unroll
+    for (int m = 0; m < 12; ++m) {
+      acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, acc0, 0, 0, 0);
+      acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, acc1, 0, 0, 0);
+      acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, acc2, 0, 0, 0);
+      acc3 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, acc3, 0, 0, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  __device__ __forceinline__ void fmas() {
+#pragma unroll
+    for (int m = 0; m < 50; ++m) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) va[e] = __builtin_fmaf(va[e], vm, vb);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  __device__ __forceinline__ void keep(float* p, int lane) {
+    float z = va[0] + va[1] + va[2] + va[3] + va[4] + va[5] + va[6] + va[7];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) z += acc0[e] + acc1[e] + acc2[e] + acc3[e];
+    if (z == 123.456f) p[lane] = z;
+  }
+};
+
+// forward, the shipped structure (one persistent 512-thread workgroup per CU, no barrier), with the kernel's order of phases:
+//   x(t) LDS -> registers, 48 MFMAs [contraction] | request x(t + nw) | 400 v_fma_f32 [aggregation], 8 x 1 KiB out stores, CSR
+// GLDS 0: x and the CSR slice wait in registers (requested a whole step ahead, as shipped; the LDS round trip of the tile is the
+//         kernel's land_tile + fragment reads);  1: x and the CSR slice by LDS-DMA into the wave's ONE tile buffer, requested once
+//         the contraction stand-in has read it, retired by a counted vmcnt (the 8 younger stores stay in flight)
+// NTL: nontemporal loads (GLDS: the nt policy bit);  NTS: nontemporal stores;  LOAD 0: no arithmetic (the pure byte pattern)
+template <int GLDS, int NTL, int NTS, int LOAD>
+__global__ __launch_bounds__(512) void skel_fi(const float* __restrict__ x, const f4* __restrict__ cv, float* __restrict__ out, int T) {
+  __shared__ f4 tile[8][512 + 128];      // 80 KiB of static LDS: fits the 160 KiB of a gfx950 CU, not the 64 KiB of earlier parts
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int nw = gridDim.x * 8;
+  const int t0 = blockIdx.x * 8 + wave;
+  if (t0 >= T) return;
+  const int cnt = (T - 1 - t0) / nw + 1;
+  f4* tl = tile[wave];
+  Standin sa(lane);
+  f4 r[8], c0 = {0, 0, 0, 0}, c1 = {0, 0, 0, 0};
+  auto issue = [&](int k) __attribute__((always_inline)) {
+    const int t = t0 + (k < cnt ? k : cnt - 1) * nw;
+    const f4* s = reinterpret_cast<const f4*>(x + (long)t * 2048);
+    const f4* c = cv + (long)t * 80;
+    if constexpr (GLDS != 0) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) glds16<NTL ? 2 : 0>(s + lane + 64 * q, tl + 64 * q);
+      glds16<0>(c + lane, tl + 512);
+      glds16<0>(c + (lane < 16 ? 64 + lane : lane), tl + 576);      // (lanes >= 16 re-read the first piece: one wave-instruction)
+    } else {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) r[q] = NTL ? __builtin_nontemporal_load(s + lane + 64 * q) : s[lane + 64 * q];
+      c0 = c[lane];
+      c1 = lane < 16 ? c[64 + lane] : f4{0, 0, 0, 0};
+    }
+  };
+  issue(0);
+  for (int i = 0; i < cnt; ++i) {
+    f4 o[8];
+    if constexpr (GLDS != 0) {
+      if (i == 0) wait_vm<0>(); else wait_vm<8>();                  // the tile and its CSR slice; the previous graph's stores stay in flight
+#pragma unroll
+      for (int q = 0; q < 8; ++q) o[q] = tl[lane + 64 * q] + tl[512 + ((q & 1) ? 64 + (lane & 15) : lane)];
+    } else {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) tl[lane + 64 * q] = r[q];         // land_tile
+#pragma unroll
+      for (int q = 0; q < 8; ++q) o[q] = tl[lane + 64 * q] + ((q & 1) ? c1 : c0);
+    }
+    if constexpr (LOAD != 0) sa.mfmas();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");              // the tile buffer has been read
+    issue(i + 1);
+    if constexpr (LOAD != 0) sa.fmas();
+    f4* dst = reinterpret_cast<f4*>(out + (long)(t0 + i * nw) * 2048);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) st16<NTS>(dst + lane + 64 * q, o[q]);
+  }
+  if constexpr (LOAD != 0) sa.keep(out, lane);
+}
+
+// backward pairs with role A's g tile and CSR slice by LDS-DMA into the pair's ONE gather tile: role A reads g(i+1) out of LDS,
+// 400 v_fma_f32 [aggregation], requests g(i+2), 48 MFMAs [dX], the 8 dX stores, a counted vmcnt that retires the tile and leaves the
+// stores in flight, the barrier (role B gathers from the tile right behind it).  Role B as in skel_h (x in registers, 48 MFMAs).
+// GLDS 0: the same order of phases with g waiting in registers (requested behind the aggregation, landed in LDS before the barrier)
+template <int GLDS, int NTL, int NTS, int LOAD>
+__global__ __launch_bounds__(512) void skel_hi(const float* __restrict__ x, const float* __restrict__ g,
+                                               const f4* __restrict__ cv, float* __restrict__ dx, int T) {
+  __shared__ float hand[8][64];
+  __shared__ f4 gt[4][512 + 128];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, pair = wave >> 1, role = wave & 1;
+  const int npairs = gridDim.x * 4;
+  const int t0 = blockIdx.x * 4 + pair;
+  const int cnt_max = (T - 1) / npairs + 1;
+  const int cnt = t0 < T ? (T - 1 - t0) / npairs + 1 : 0;
+  const int li = lane & 31, hi = lane >> 5;
+  f4* tl = gt[pair];
+  Standin sa(lane);
+  f4 r[8], c0 = {0, 0, 0, 0}, c1 = {0, 0, 0, 0};
+  auto graph = [&](int k) { return cnt > 0 ? t0 + (k < cnt ? k : cnt - 1) * npairs : 0; };
+  auto issue = [&](int k) __attribute__((always_inline)) {
+    const int t = graph(k);
+    const f4* s = reinterpret_cast<const f4*>((role ? x : g) + (long)t * 2048);
+    const f4* c = cv + (long)t * 80;
+    if (GLDS != 0 && !role) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) glds16<NTL ? 2 : 0>(s + lane + 64 * q, tl + 64 * q);
+      glds16<0>(c + lane, tl + 512);
+      glds16<0>(c + (lane < 16 ? 64 + lane : lane), tl + 576);
+    } else {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) r[q] = NTL ? __builtin_nontemporal_load(s + lane + 64 * q) : s[lane + 64 * q];
+      if (!role) {
+        c0 = c[lane];
+        c1 = lane < 16 ? c[64 + lane] : f4{0, 0, 0, 0};
+      }
+    }
+  };
+  issue(0);
+  if (!role) {
+    if constexpr (GLDS != 0) {
+      wait_vm<0>();
+    } else {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) tl[lane + 64 * q] = r[q] + ((q & 1) ? c1 : c0);
+    }
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  for (int i = 0; i < cnt_max; ++i) {
+    const bool live = i < cnt;
+    f4 o[8];
+    if (role) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) o[q] = r[q];
+      const f4 s = o[0] + o[1] + o[2] + o[3] + o[4] + o[5] + o[6] + o[7];
+      hand[wave][lane] = s[0] + s[1] + s[2] + s[3] + tl[lane][0];   // role B reads the gather tile too
+      if constexpr (LOAD != 0) sa.mfmas();
+      issue(i + 1);
+    } else {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        o[q] = tl[lane + 64 * q];
+        if constexpr (GLDS != 0) o[q] += tl[512 + ((q & 1) ? 64 + (lane & 15) : lane)];
+      }
+      if constexpr (LOAD != 0) sa.fmas();
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      issue(i + 1);
+      if constexpr (LOAD != 0) sa.mfmas();
+      const float hv = hand[wave + 1][lane];
+      float* dst = dx + (long)graph(i) * 2048;
+      if (live) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+          st16<NTS>(reinterpret_cast<f4*>(dst + li * 64 + (q >> 2) * 32 + 8 * (q & 3) + 4 * hi), o[q] * hv);
+      }
+      if constexpr (GLDS != 0) {
+        if (live) wait_vm<8>(); else wait_vm<0>();
+      } else {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) tl[lane + 64 * q] = r[q] + ((q & 1) ? c1 : c0);
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+  }
+  if constexpr (LOAD != 0) sa.keep(dx, lane);
+}
+
 static float* X; static float* G; static float* DX; static f4* CV; static int T;
 template <typename L>
 static float timeit(L launch) {
@@ -319,7 +513,51 @@ int main(int argc, char** argv) {
   hipMemset(X, 0x11, tb); hipMemset(G, 0x22, tb); hipMemset(CV, 0, (size_t)T * 1280);
   printf("graphs = %d, algorithmic bytes per graph 25,508\n", T);
   char nm[128];
-  for (int rep = 0; rep < 2; ++rep) {
+  const bool ingest = argc > 2 && !strcmp(argv[2], "ingest");   // only the ingest arms, next to the best existing arm of each direction
+  if (ingest) for (int rep = 0; rep < 3; ++rep) {
+#define FI(G_, L_, S_, A_, name) \
+    linef(name, timeit([&] { hipLaunchKernelGGL((skel_fi<G_, L_, S_, A_>), dim3(256), dim3(512), 0, 0, X, CV, DX, T); }))
+#define HI(G_, L_, S_, A_, name) \
+    line(name, timeit([&] { hipLaunchKernelGGL((skel_hi<G_, L_, S_, A_>), dim3(256), dim3(512), 0, 0, X, G, CV, DX, T); }))
+    linef("F  forward: persistent, 8 waves/CU (2 x 256-thread workgroups), no barrier",
+          timeit([&] { hipLaunchKernelGGL((skel_f<0, 0, 256>), dim3(512), dim3(256), 0, 0, X, CV, DX, T); }));
+    linef("F  forward: persistent, 8 waves/CU (512-thread workgroup), no barrier",
+          timeit([&] { hipLaunchKernelGGL((skel_f<0, 0, 512>), dim3(256), dim3(512), 0, 0, X, CV, DX, T); }));
+    FI(0, 0, 0, 0, "FI forward, kernel order, registers + land_tile");
+    FI(1, 0, 0, 0, "FI forward, kernel order, (a) LDS-DMA single buffer");
+    FI(0, 0, 1, 0, "FI forward, kernel order, (b) nontemporal stores");
+    FI(0, 1, 0, 0, "FI forward, kernel order, (c) nontemporal loads");
+    FI(1, 1, 0, 0, "FI forward, kernel order, (a+c) LDS-DMA with the nt policy bit");
+    FI(1, 0, 1, 0, "FI forward, kernel order, (d) LDS-DMA + nontemporal stores");
+    FI(0, 1, 1, 0, "FI forward, kernel order, (b+c) nontemporal loads and stores");
+    FI(0, 0, 0, 1, "FI + 48 MFMAs + 400 FMAs, registers + land_tile");
+    FI(1, 0, 0, 1, "FI + 48 MFMAs + 400 FMAs, (a) LDS-DMA single buffer");
+    FI(0, 0, 1, 1, "FI + 48 MFMAs + 400 FMAs, (b) nontemporal stores");
+    FI(0, 1, 0, 1, "FI + 48 MFMAs + 400 FMAs, (c) nontemporal loads");
+    FI(1, 1, 0, 1, "FI + 48 MFMAs + 400 FMAs, (a+c) LDS-DMA with the nt policy bit");
+    FI(1, 0, 1, 1, "FI + 48 MFMAs + 400 FMAs, (d) LDS-DMA + nontemporal stores");
+    FI(0, 1, 1, 1, "FI + 48 MFMAs + 400 FMAs, (b+c) nontemporal loads and stores");
+    line("H  pairs (g+CSR+dX | x), depth 1, 8 waves/CU, barrier per graph",
+         timeit([&] { hipLaunchKernelGGL((skel_h<1>), dim3(256), dim3(512), 0, 0, X, G, CV, DX, T); }));
+    line("H  pairs + 48 bf16 MFMAs + 400 v_fma_f32 per wave and graph",
+         timeit([&] { hipLaunchKernelGGL((skel_h<1, 1, 2>), dim3(256), dim3(512), 0, 0, X, G, CV, DX, T); }));
+    line("H  pairs + MFMAs + FMAs, the next graph requested BEHIND the arithmetic",
+         timeit([&] { hipLaunchKernelGGL((skel_h<1, 1, 2, 0, 0, 1>), dim3(256), dim3(512), 0, 0, X, G, CV, DX, T); }));
+    HI(0, 0, 0, 0, "HI pairs, role-A order agg | request | dX, g in registers");
+    HI(1, 0, 0, 0, "HI pairs, role-A order agg | request | dX, (a) g by LDS-DMA");
+    HI(0, 0, 1, 0, "HI pairs, (b) nontemporal dX stores");
+    HI(0, 1, 0, 0, "HI pairs, (c) nontemporal loads");
+    HI(1, 1, 0, 0, "HI pairs, (a+c) g by LDS-DMA with the nt policy bit");
+    HI(0, 0, 0, 1, "HI + MFMAs + FMAs, g in registers");
+    HI(1, 0, 0, 1, "HI + MFMAs + FMAs, (a) g by LDS-DMA");
+    HI(0, 0, 1, 1, "HI + MFMAs + FMAs, (b) nontemporal dX stores");
+    HI(0, 1, 0, 1, "HI + MFMAs + FMAs, (c) nontemporal loads");
+    HI(1, 1, 0, 1, "HI + MFMAs + FMAs, (a+c) g by LDS-DMA with the nt policy bit");
+    HI(1, 0, 1, 1, "HI + MFMAs + FMAs, (d) g by LDS-DMA + nontemporal dX stores");
+#undef FI
+#undef HI
+  }
+  else for (int rep = 0; rep < 2; ++rep) {
     for (int wpc : {4, 8, 12}) {
       const int blocks = 256 * wpc / 4;
       snprintf(nm, sizeof nm, "P  persistent, depth 2, %2d waves/CU", wpc);
