@@ -68,10 +68,11 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));   // native vector: HIP's
 
 __device__ __forceinline__ f32x4 ldv4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void stv4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-// Streaming (nontemporal) forms.  Only the FULL forward uses them, for BOTH of its streams (x in, out out: each touched once by
+// Streaming (nontemporal) forms.  The FULL forward uses them for BOTH of its streams (x in, out out: each touched once by
 // the kernel, 819 MB per tensor at the benchmark size against 256 MiB of last-level cache).  Either hint alone loses; together
-// they win, mostly in the BACKWARD that follows (the forward leaves the cache alone).  The backward's own streams stay plain:
-// every hint there loses over a whole step (profiles/fused_ingest_history.txt, DESIGN lesson 47).
+// they win, mostly in the BACKWARD that follows (the forward leaves the cache alone: profiles/fused_ingest_history.txt, DESIGN
+// lesson 47).  The pairs backward takes them for its dX stores and g loads, together, once its tensors exceed that cache (its
+// whole-row dX stores made that possible: DESIGN lesson 48); its x loads stay plain.
 template <bool NT> __device__ __forceinline__ f32x4 ldv4s(const float* p) {
   if constexpr (NT) return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
   else return ldv4(p);
@@ -1574,7 +1575,7 @@ __global__ __launch_bounds__(256, 1) void graphconv_bwd_planes_kernel(
 // (plane buffers, gather tile, CSR slices: ~36 KB per graph in flight) now serves a PAIR, eight waves per CU, two per SIMD, 256
 // registers each, in two roles:
 //   wave A ("dX")  g + CSR in (one iteration ahead), the adjoint aggregation dFW(i+1) = A^T g(i+1) -> three bf16 planes + dbias,
-//                  dX(i)^T = W dFW(i)^T (48 MFMAs: W p1 resident, p2 / p3 from the workgroup's table), the dX stores
+//                  dX(i) = dFW(i) W^T (48 MFMAs: W p1 resident, p2 / p3 from the workgroup's table), the dX stores
 //   wave B ("dW")  x in (fragment layout, one iteration ahead), its 3-way split into resident fragments, dW += x(i)^T dFW(i)
 //                  (48 MFMAs against the planes read transposed), the four dW accumulator tiles
 // and ONE workgroup barrier per graph (s_waitcnt lgkmcnt(0) + s_barrier: vector-memory operations stay in flight across it): at the
@@ -1588,6 +1589,14 @@ __global__ __launch_bounds__(256, 1) void graphconv_bwd_planes_kernel(
 // Iteration counts are uniform (every wave passes the same barriers): the launcher takes this kernel for T >= 2 pairs-in-flight
 // graphs only, so a pair owns cnt_max or cnt_max - 1 >= 2 graphs; the one iteration a short pair lacks is skipped under uniform
 // branches that hold no vector-memory instruction.
+// The dX stores (profiles/dx_store_skeleton.txt, dx_store_ab.txt, DESIGN lesson 48): the planes kernel multiplies dX^T = W dFW^T, so a lane holds 4
+// consecutive features of one node and a dwordx4 store touches 32 rows (32-byte segments at 256-byte stride; a 128-byte line is
+// put together from four instructions in L2).  Here the SAME fragments go to the MFMA in the other order (the A and B layouts of
+// v_mfma_f32_32x32x16_bf16 are the same per lane: lane (li, hi) holds row / column li, k = 8 hi .. 8 hi + 7): dX comes out
+// un-transposed -- lane li holds feature 32 nt + li, register 4 q + j node 8 q + 4 hi + j -- with the same products in the same
+// k order, bit for bit.  One v_permlane32_swap between c0[r] and c1[r] (16 per graph) leaves a whole node row in each register:
+// 32 global_store_dword per graph, each ONE contiguous 256-byte row.  The stores are counted by vmcnt: the waits that land
+// g(i+2) went from vmcnt(16 / 17) to vmcnt(40 / 41) -- 24 more stores in flight, far from the 6-bit limit, none became vmcnt(0).
 // Measured during round 6 and removed from the source since (profiles/r06_bwd_pairs_history.txt, items 2a - 2e):
 //   * The roles of a pair sat on different SIMDs (pair = wave >> 1): 0.518-0.524 ms against 0.475-0.485 (2c).
 //   * The rows were split 1 : 3, 3 : 1 and not at all between the roles (2b: slower), and role B took other pairs of row groups
@@ -1602,10 +1611,18 @@ constexpr int BP_PAIRS = 4;
 #ifndef KGCN_BWD_PAIRS
 #define KGCN_BWD_PAIRS 1        // 0: the one-wave-per-graph planes kernel for every batch
 #endif
+// one element per lane of a dX row (STREAM: see the comment block above)
+template <bool STREAM> __device__ __forceinline__ void st_dx(float* p, float v) {
+  if constexpr (STREAM) __builtin_nontemporal_store(v, p);
+  else *p = v;
+}
+// The batch from which the pairs kernel streams: x, g and dX (3 x 8 KiB per graph) no longer fit the last-level cache together
+constexpr size_t kLastLevelCacheBytes = (size_t)256 << 20;
+static bool bwd_streams(int T) { return (size_t)T * FN * FD * 4 * 3 > kLastLevelCacheBytes; }
 __device__ __forceinline__ void bp_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-// LAY: adjacency layout of A^T, as in graphconv_fwd_full_kernel
-template <int LAY>
+// LAY: adjacency layout of A^T, as in graphconv_fwd_full_kernel;  STREAM: g loads and dX stores with the streaming policy
+template <int LAY, bool STREAM>
 __global__ __launch_bounds__(512, 2) void graphconv_bwd_pairs_kernel(
     const int* __restrict__ slots_t, const int* __restrict__ gptr_t, const int2* __restrict__ cv_t,
     const float* __restrict__ cvals_t, const float* __restrict__ x, const float* __restrict__ w,
@@ -1699,7 +1716,8 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_pairs_kernel(
         LB[ks] = pl0 + ((R << 9) | ((a ^ (unsigned)(ks >> 1)) << 6) |
                         (((2 * (unsigned)(ks & 1) + (unsigned)hi) ^ (R & 3)) << 4));
     }
-    // A fragments of dX^T = W dFW^T (as in the planes kernel): p1 resident, p2 / p3 in the workgroup's table
+    // W fragments of dX = dFW W^T (the planes kernel's A fragments of dX^T = W dFW^T: the A and B layouts of the 32 x 32 x 16
+    // MFMA are the same per lane, so they serve as B here): p1 resident, p2 / p3 in the workgroup's table
     u32x4 WF1[2][4];
     static_for<8>([&](auto c) __attribute__((always_inline)) {
       constexpr int nt = decltype(c)::value >> 2, ks = decltype(c)::value & 3;
@@ -1768,7 +1786,7 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_pairs_kernel(
       static_for<8>([&](auto qc) __attribute__((always_inline)) {
         constexpr int q = decltype(qc)::value;
         stv4(gt + 4 * lane + q * 256, gpf.v[q]);
-        gpf.v[q] = ldv4((q >> 2 ? gsrc + 1024 : gsrc) + (q & 3) * 256);
+        gpf.v[q] = ldv4s<STREAM>((q >> 2 ? gsrc + 1024 : gsrc) + (q & 3) * 256);
       });
       land_csr_l(ecv_c, tab_c, m_a.slot, base_a, cnt_a);
       const int base_n = meta_base(m_b), cnt_n = meta_cnt(m_b);
@@ -1780,7 +1798,7 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_pairs_kernel(
       base_a = base_n;
       cnt_a = cnt_n;
     };
-    // dX(i)^T = W dFW(i)^T out of planes `cur`, then its 16-byte stores
+    // dX(i) = dFW(i) W^T out of planes `cur`, then its 32 whole-row stores
     auto dx_of = [&](int i, int cur) __attribute__((always_inline)) {
       const unsigned cur_off = cur ? (unsigned)DFWP_BYTES : 0u;
       u32x4 FA[4][3];            // dFW(i) fragments [k-step][piece]
@@ -1803,22 +1821,24 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_pairs_kernel(
         constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};
         constexpr int wl = PB[pr] == 0 ? 0 : PB[pr] - 1;
         const u32x4 wv = PB[pr] == 0 ? WF1[nt][ks] : WL[ks][wl][nt];
-        if constexpr (m == 0) c0 = mfma_bf16(wv, FA[ks][PA[pr]], zero16);
-        else if constexpr (m == 1) c1 = mfma_bf16(wv, FA[ks][PA[pr]], zero16);
-        else if constexpr (nt == 0) c0 = mfma_bf16(wv, FA[ks][PA[pr]], c0);
-        else c1 = mfma_bf16(wv, FA[ks][PA[pr]], c1);
+        if constexpr (m == 0) c0 = mfma_bf16(FA[ks][PA[pr]], wv, zero16);
+        else if constexpr (m == 1) c1 = mfma_bf16(FA[ks][PA[pr]], wv, zero16);
+        else if constexpr (nt == 0) c0 = mfma_bf16(FA[ks][PA[pr]], wv, c0);
+        else c1 = mfma_bf16(FA[ks][PA[pr]], wv, c1);
         if constexpr (m % 12 == 1 && ks < 3) {                     // one k-step ahead
           read_fa(std::integral_constant<int, ks + 1>{});
           __builtin_amdgcn_sched_barrier(0);
         }
       });
-      float* dxp = dx + (long)gidx(i) * N * D + li * D + 4 * hi;
+      // lane (li, hi) holds feature 32 nt + li of the nodes 8 q + 4 hi + j (register 4 q + j of tile nt).  One half-wave swap per
+      // register pair gives c0[r] the node 8 q + j and c1[r] the node 8 q + 4 + j with feature = lane: a whole row per store
+      float* dxp = dx + (long)gidx(i) * N * D + lane;
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const f32x4 v0 = {c0[4 * q], c0[4 * q + 1], c0[4 * q + 2], c0[4 * q + 3]};
-        const f32x4 v1 = {c1[4 * q], c1[4 * q + 1], c1[4 * q + 2], c1[4 * q + 3]};
-        stv4(dxp + 8 * q, v0);
-        stv4(dxp + 32 + 8 * q, v1);
+      for (int r = 0; r < 16; ++r) {
+        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(c0[r]), __float_as_uint(c1[r]), false, false);
+        float* p = dxp + (8 * (r >> 2) + (r & 3)) * D;
+        st_dx<STREAM>(p, __uint_as_float(sw[0]));
+        st_dx<STREAM>(p + 4 * D, __uint_as_float(sw[1]));
       }
     };
 
@@ -2231,9 +2251,12 @@ extern "C" int kgcn_graphconv_bwd_f32(const kgcn_csr_batch* at, const float* x, 
   static thread_local bool attr_set = false;
   if (!attr_set) {
     allow_big_lds(graphconv_bwd_planes_kernel);
-    allow_big_lds(graphconv_bwd_pairs_kernel<LAY_PAD4>);
-    allow_big_lds(graphconv_bwd_pairs_kernel<LAY_UNIT>);
-    allow_big_lds(graphconv_bwd_pairs_kernel<LAY_VALS>);
+    allow_big_lds(graphconv_bwd_pairs_kernel<LAY_PAD4, false>);
+    allow_big_lds(graphconv_bwd_pairs_kernel<LAY_UNIT, false>);
+    allow_big_lds(graphconv_bwd_pairs_kernel<LAY_VALS, false>);
+    allow_big_lds(graphconv_bwd_pairs_kernel<LAY_PAD4, true>);
+    allow_big_lds(graphconv_bwd_pairs_kernel<LAY_UNIT, true>);
+    allow_big_lds(graphconv_bwd_pairs_kernel<LAY_VALS, true>);
     allow_big_lds(graphconv_bwd_kernel<2>);
     allow_big_lds(graphconv_bwd_kernel<1>);
     allow_big_lds(graphconv_bwd_kernel<0>);
@@ -2244,9 +2267,10 @@ extern "C" int kgcn_graphconv_bwd_f32(const kgcn_csr_batch* at, const float* x, 
   const float* cvals = compact_values(at);
   if (pairs)
     with_const3(lay, [&](auto L) {
-      hipLaunchKernelGGL(graphconv_bwd_pairs_kernel<decltype(L)::value>, dim3(blocks), dim3(512), lds, s, at->slots,
-                         at->graph_ptr, cv, cvals, x, w, dout_grad, dx, part_dw, part_db, at->num_graphs,
-                         at->max_nnz_per_graph);
+      auto kernel = bwd_streams(at->num_graphs) ? graphconv_bwd_pairs_kernel<decltype(L)::value, true>
+                                                : graphconv_bwd_pairs_kernel<decltype(L)::value, false>;
+      hipLaunchKernelGGL(kernel, dim3(blocks), dim3(512), lds, s, at->slots, at->graph_ptr, cv, cvals, x, w, dout_grad, dx,
+                         part_dw, part_db, at->num_graphs, at->max_nnz_per_graph);
     });
   else if (full)
     hipLaunchKernelGGL(graphconv_bwd_planes_kernel, dim3(blocks), dim3(64 * wpb), lds, s, at->slots,

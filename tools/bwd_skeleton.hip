@@ -7,7 +7,10 @@
 //   PX  as P with x loaded in the dW A-fragment layout of the shipped kernel (16 x 8-byte loads, two 256-byte rows each)
 //   H   persistent PAIRS: two waves share a graph (wave A: g + CSR in, dX out; wave B: x in), 8 waves per CU   (the two-role form)
 //   N   non-persistent, one wave per graph, no prefetch, as many waves per CU as registers allow       (the SpMM's structure)
-// usage: bwd_skeleton [graphs [ingest]]   (ingest: only the LDS-DMA / nontemporal arms of skel_fi / skel_hi and their references)
+// usage: bwd_skeleton [graphs [ingest | dxstore]]
+//   ingest:  only the LDS-DMA / nontemporal arms of skel_fi / skel_hi and their references
+//   dxstore: only the dX store forms of skel_hi (S0 / S1 / S2, plain and nontemporal, pure and beside the arithmetic) and the
+//            write-only / read-only streams that price a stored and a loaded byte on the box at hand
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -302,6 +305,16 @@ template <int NTS> __device__ __forceinline__ void st16(f4* p, f4 v) {
   if constexpr (NTS != 0) __builtin_nontemporal_store(v, p);
   else *p = v;
 }
+template <int NTS> __device__ __forceinline__ void st4(float* p, float v) {
+  if constexpr (NTS != 0) __builtin_nontemporal_store(v, p);
+  else *p = v;
+}
+// lanes 32-63 of a <-> lanes 0-31 of b (v_permlane32_swap_b32)
+__device__ __forceinline__ void swap32(float& a, float& b) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
+  a = __uint_as_float(r[0]);
+  b = __uint_as_float(r[1]);
+}
 // the arithmetic stand-ins of skel_h: 48 bf16 MFMAs (one contraction) / 400 v_fma_f32 (one aggregation)
 struct Standin {
   f16v acc0 = {}, acc1 = {}, acc2 = {}, acc3 = {};
@@ -399,7 +412,12 @@ __global__ __launch_bounds__(512) void skel_fi(const float* __restrict__ x, cons
 // 400 v_fma_f32 [aggregation], requests g(i+2), 48 MFMAs [dX], the 8 dX stores, a counted vmcnt that retires the tile and leaves the
 // stores in flight, the barrier (role B gathers from the tile right behind it).  Role B as in skel_h (x in registers, 48 MFMAs).
 // GLDS 0: the same order of phases with g waiting in registers (requested behind the aggregation, landed in LDS before the barrier)
-template <int GLDS, int NTL, int NTS, int LOAD>
+// DXF: the form of role A's dX stores, the 32 registers o[] read as the two 32 x 32 accumulators c0 = o[0..3], c1 = o[4..7]
+//   0  dX^T = W dFW^T (lane = node, 4 consecutive features per register quad): 8 x dwordx4, 32-byte segments at 256-byte stride
+//   1  dX = dFW W^T (lane = feature 32 nt + li, register 4 q + j = node 8 q + 4 hi + j) as it stands: 32 x dword, two 128-byte lines each
+//   2  as 1 behind v_permlane32_swap(c0[r], c1[r]): c0[r] is node 8 q + j, c1[r] node 8 q + 4 + j, lane = feature: 32 x dword,
+//      one 256-byte row each
+template <int GLDS, int NTL, int NTS, int LOAD, int DXF = 0>
 __global__ __launch_bounds__(512) void skel_hi(const float* __restrict__ x, const float* __restrict__ g,
                                                const f4* __restrict__ cv, float* __restrict__ dx, int T) {
   __shared__ float hand[8][64];
@@ -465,11 +483,29 @@ __global__ __launch_bounds__(512) void skel_hi(const float* __restrict__ x, cons
       const float hv = hand[wave + 1][lane];
       float* dst = dx + (long)graph(i) * 2048;
       if (live) {
+        if constexpr (DXF == 0) {
 #pragma unroll
-        for (int q = 0; q < 8; ++q)
-          st16<NTS>(reinterpret_cast<f4*>(dst + li * 64 + (q >> 2) * 32 + 8 * (q & 3) + 4 * hi), o[q] * hv);
+          for (int q = 0; q < 8; ++q)
+            st16<NTS>(reinterpret_cast<f4*>(dst + li * 64 + (q >> 2) * 32 + 8 * (q & 3) + 4 * hi), o[q] * hv);
+        } else {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            float v0 = o[r >> 2][r & 3] * hv, v1 = o[4 + (r >> 2)][r & 3] * hv;
+            if constexpr (DXF == 1) {
+              float* dp = dst + (8 * (r >> 2) + 4 * hi + (r & 3)) * 64 + li;
+              st4<NTS>(dp, v0);
+              st4<NTS>(dp + 32, v1);
+            } else {
+              swap32(v0, v1);
+              float* dp = dst + (8 * (r >> 2) + (r & 3)) * 64 + lane;
+              st4<NTS>(dp, v0);
+              st4<NTS>(dp + 4 * 64, v1);
+            }
+          }
+        }
       }
       if constexpr (GLDS != 0) {
+        static_assert(DXF == 0, "the counted wait of the LDS-DMA arm assumes 8 stores");
         if (live) wait_vm<8>(); else wait_vm<0>();
       } else {
 #pragma unroll
@@ -479,6 +515,44 @@ __global__ __launch_bounds__(512) void skel_hi(const float* __restrict__ x, cons
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
   }
   if constexpr (LOAD != 0) sa.keep(dx, lane);
+}
+
+// one stream alone, persistent, 8 waves per CU, 8 KiB tiles as 8 x 1 KiB wave-instructions: what a stored / a loaded byte costs
+template <int NTS>
+__global__ __launch_bounds__(512) void skel_w(float* __restrict__ out, int T) {
+  const int lane = threadIdx.x & 63, nw = gridDim.x * 8;
+  const f4 v = {1.f * lane, 2.f, 3.f, 4.f};
+  for (int t = blockIdx.x * 8 + (threadIdx.x >> 6); t < T; t += nw) {
+    f4* dst = reinterpret_cast<f4*>(out + (long)t * 2048);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) st16<NTS>(dst + lane + 64 * q, v);
+  }
+}
+// T tiles of each of a and b in (depth 1: the next pair of tiles is requested before the current one is summed)
+template <int NTL>
+__global__ __launch_bounds__(512) void skel_r(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, int T) {
+  const int lane = threadIdx.x & 63, nw = gridDim.x * 8;
+  const int t0 = blockIdx.x * 8 + (threadIdx.x >> 6);
+  if (t0 >= T) return;
+  f4 r[16], acc = {0, 0, 0, 0};
+  auto issue = [&](int t) __attribute__((always_inline)) {
+    const f4* sa = reinterpret_cast<const f4*>(a + (long)t * 2048);
+    const f4* sb = reinterpret_cast<const f4*>(b + (long)t * 2048);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      r[q] = NTL ? __builtin_nontemporal_load(sa + lane + 64 * q) : sa[lane + 64 * q];
+      r[8 + q] = NTL ? __builtin_nontemporal_load(sb + lane + 64 * q) : sb[lane + 64 * q];
+    }
+  };
+  issue(t0);
+  for (int t = t0; t < T; t += nw) {
+    f4 s = {0, 0, 0, 0};
+#pragma unroll
+    for (int q = 0; q < 16; ++q) s += r[q];
+    issue(t + nw < T ? t + nw : t);
+    acc += s;
+  }
+  if (acc[0] + acc[1] + acc[2] + acc[3] == 123.456f) out[lane] = acc[0];
 }
 
 static float* X; static float* G; static float* DX; static f4* CV; static int T;
@@ -500,6 +574,10 @@ static void linef(const char* name, float ms) {
   printf("  %-64s %.3f ms  %.0f GB/s  %.3f of 8 TB/s\n", name, ms, bytes / ms / 1e6, bytes / ms / 1e6 / 8000.0);
   fflush(stdout);
 }
+static void lineb(const char* name, float ms, double bytes) {
+  printf("  %-64s %.3f ms  %.0f GB/s (%.0f MB per launch)\n", name, ms, bytes / ms / 1e6, bytes / 1e6);
+  fflush(stdout);
+}
 static void line(const char* name, float ms) {
   const double bytes = (double)T * (8192 * 3 + 932);           // the kernel's ALGORITHMIC bytes (the skeleton reads 1,280 B of CSR)
   printf("  %-64s %.3f ms  %.0f GB/s  %.3f of 8 TB/s\n", name, ms, bytes / ms / 1e6, bytes / ms / 1e6 / 8000.0);
@@ -514,7 +592,33 @@ int main(int argc, char** argv) {
   printf("graphs = %d, algorithmic bytes per graph 25,508\n", T);
   char nm[128];
   const bool ingest = argc > 2 && !strcmp(argv[2], "ingest");   // only the ingest arms, next to the best existing arm of each direction
-  if (ingest) for (int rep = 0; rep < 3; ++rep) {
+  const bool dxstore = argc > 2 && !strcmp(argv[2], "dxstore");
+  if (dxstore) for (int rep = 0; rep < 3; ++rep) {
+#define HD(S_, A_, F_, name) \
+    line(name, timeit([&] { hipLaunchKernelGGL((skel_hi<0, 0, S_, A_, F_>), dim3(256), dim3(512), 0, 0, X, G, CV, DX, T); }))
+    HD(0, 0, 0, "HI pairs, S0 8 x dwordx4, 32-byte segments (shipped)");
+    HD(1, 0, 0, "HI pairs, S0 nontemporal");
+    HD(0, 0, 1, "HI pairs, S1 32 x dword, two 128-byte lines each");
+    HD(1, 0, 1, "HI pairs, S1 nontemporal");
+    HD(0, 0, 2, "HI pairs, S2 permlane32_swap, 32 x dword, one 256-byte row each");
+    HD(1, 0, 2, "HI pairs, S2 nontemporal");
+    HD(0, 1, 0, "HI + MFMAs + FMAs, S0 (shipped)");
+    HD(1, 1, 0, "HI + MFMAs + FMAs, S0 nontemporal");
+    HD(0, 1, 1, "HI + MFMAs + FMAs, S1");
+    HD(1, 1, 1, "HI + MFMAs + FMAs, S1 nontemporal");
+    HD(0, 1, 2, "HI + MFMAs + FMAs, S2");
+    HD(1, 1, 2, "HI + MFMAs + FMAs, S2 nontemporal");
+#undef HD
+    lineb("W  write-only stream, 1 KiB per wave-instruction",
+          timeit([&] { hipLaunchKernelGGL((skel_w<0>), dim3(256), dim3(512), 0, 0, DX, T); }), (double)T * 8192);
+    lineb("W  write-only stream, nontemporal",
+          timeit([&] { hipLaunchKernelGGL((skel_w<1>), dim3(256), dim3(512), 0, 0, DX, T); }), (double)T * 8192);
+    lineb("R  read-only stream (two tensors), 1 KiB per wave-instruction",
+          timeit([&] { hipLaunchKernelGGL((skel_r<0>), dim3(256), dim3(512), 0, 0, X, G, DX, T); }), (double)T * 16384);
+    lineb("R  read-only stream (two tensors), nontemporal",
+          timeit([&] { hipLaunchKernelGGL((skel_r<1>), dim3(256), dim3(512), 0, 0, X, G, DX, T); }), (double)T * 16384);
+  }
+  else if (ingest) for (int rep = 0; rep < 3; ++rep) {
 #define FI(G_, L_, S_, A_, name) \
     linef(name, timeit([&] { hipLaunchKernelGGL((skel_fi<G_, L_, S_, A_>), dim3(256), dim3(512), 0, 0, X, CV, DX, T); }))
 #define HI(G_, L_, S_, A_, name) \
