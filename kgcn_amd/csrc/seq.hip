@@ -373,14 +373,17 @@ struct LstmArgs {
 
 __device__ __forceinline__ float rec_act(float z, int act) {
   if (act == KGCN_SEQ_ACT_SIGMOID) return 1.f / (1.f + expf(-z));
-  const float y = __fadd_rn(__fmul_rn(0.2f, z), 0.5f);          // Keras hard_sigmoid: 0.2 x + 0.5, then clip
+  // Keras hard_sigmoid: 0.2 x + 0.5, then clip.  The _rn forms do not keep the compiler from fusing the two into one FMA
+  // (see rec_act_grad); the clip gives exactly 0 and 1 at z = -2.5 and 2.5 either way
+  const float y = __fadd_rn(__fmul_rn(0.2f, z), 0.5f);
   return fminf(fmaxf(y, 0.f), 1.f);
 }
-// derivative; tf.clip_by_value passes the gradient at the boundaries
+// derivative; tf.clip_by_value passes the gradient at the boundaries, z = -2.5 and z = 2.5, and nowhere beyond.  The test is on
+// z and not on y: rounded twice, 0.2 z + 0.5 is exactly 1 for the float above 2.5 as well (a tie that rounds to even), and
+// __fmul_rn is a plain product in HIP, so that under -ffp-contract=fast y is one FMA, -7.5e-9 at z = -2.5 (0.2f > 0.2)
 __device__ __forceinline__ float rec_act_grad(float z, float a, int act) {
   if (act == KGCN_SEQ_ACT_SIGMOID) return a * (1.f - a);
-  const float y = __fadd_rn(__fmul_rn(0.2f, z), 0.5f);
-  return (y >= 0.f && y <= 1.f) ? 0.2f : 0.f;
+  return (z >= -2.5f && z <= 2.5f) ? 0.2f : 0.f;
 }
 
 // thread (sequence s = tid / Hp, unit u = tid % Hp); LDS: W [4][Hp][wstride] over k = [x (D) | h (H)], state [2][seqs][KA4]
@@ -400,6 +403,7 @@ __global__ __launch_bounds__(256) void lstm_fwd_kernel(LstmArgs a, float* __rest
     wl[i] = v;
   }
   for (int i = threadIdx.x; i < 2 * a.seqs * a.KA4; i += blockDim.x) st[i] = 0.f;
+  __syncthreads();                              // the first step's x goes into the zeroed slab, written by other threads
   const int s = threadIdx.x / a.Hp, u = threadIdx.x - s * a.Hp;
   const int b = blockIdx.x * a.seqs + s;
   const bool live = u < H && b < a.B;

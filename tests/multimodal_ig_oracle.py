@@ -8,7 +8,7 @@ of adjacency channel 0 and the embedded protein sequence (the `embedded_layer` p
   IG          kgcn/feed.py:116-121, 126-131, 219-232: every input named in the modal set is scaled by s (the values of every
               adjacency channel); the gradient is taken with respect to the scaled placeholder (channel-0 values for adjs)
 
-Every function computes in float64."""
+Every function computes in float64 (the two conv-pool functions in fp32 when given dtype=np.float32, as in multimodal_oracle)."""
 import os
 import sys
 
@@ -33,36 +33,40 @@ def dense_adjs(adjs, N):
     return A, S
 
 
-def conv_pool_fwd_emb(emb, w, b, pool):
+def conv_pool_fwd_emb(emb, w, b, pool, dtype=F64):
     """Conv1D(same, relu) + MaxPooling1D on the embedded input [B, L, E] -> (pooled, arg-max (lowest on ties), conv)."""
-    emb, w, b = np.asarray(emb, F64), np.asarray(w, F64), np.asarray(b, F64)
+    emb, w, b = np.asarray(emb, dtype), np.asarray(w, dtype), np.asarray(b, dtype)
     B, L, E = emb.shape
     k = w.shape[0]
     left, _ = M.same_padding(k)
-    pad = np.zeros((B, L + k - 1, E), F64)
+    pad = np.zeros((B, L + k - 1, E), dtype)
     pad[:, left:left + L] = emb
     conv = np.broadcast_to(b, (B, L, w.shape[2])).copy()
     for dk in range(k):
-        conv += pad[:, dk:dk + L] @ w[dk]
+        if dtype is F64:
+            conv += pad[:, dk:dk + L] @ w[dk]
+        else:                                 # one term at a time, as in multimodal_oracle.conv_same
+            for e in range(E):
+                conv += pad[:, dk:dk + L, e:e + 1] * w[dk, e]
     T = L // pool
-    y = np.maximum(conv[:, :T * pool], 0.0).reshape(B, T, pool, -1)
+    y = np.maximum(conv[:, :T * pool], dtype(0.0)).reshape(B, T, pool, -1)
     return y.max(axis=2), y.argmax(axis=2), conv
 
 
-def conv_pool_input_grad(conv, arg, w, pool, g):
+def conv_pool_input_grad(conv, arg, w, pool, g, dtype=F64):
     """d pooled [B, T, F] -> d emb [B, L, E]: routed to the arg-max position (nothing where the maximum is not > 0), then
     demb[m, e] = sum_j sum_f dconv[m + padL - j, f] w[j, e, f]."""
-    w = np.asarray(w, F64)
+    w = np.asarray(w, dtype)
     B, L, F = conv.shape
     k = w.shape[0]
     T = np.asarray(g).shape[1]
-    dy = np.zeros((B, T, pool, F), F64)
+    dy = np.zeros((B, T, pool, F), dtype)
     bi, ti, fi = np.meshgrid(np.arange(B), np.arange(T), np.arange(F), indexing="ij")
-    dy[bi, ti, arg, fi] = np.asarray(g, F64)
-    dconv = np.zeros((B, L, F), F64)
+    dy[bi, ti, arg, fi] = np.asarray(g, dtype)
+    dconv = np.zeros((B, L, F), dtype)
     dconv[:, :T * pool] = dy.reshape(B, T * pool, F) * (conv[:, :T * pool] > 0)
     left, _ = M.same_padding(k)
-    dpad = np.zeros((B, L + k - 1, w.shape[1]), F64)
+    dpad = np.zeros((B, L + k - 1, w.shape[1]), dtype)
     for dk in range(k):
         dpad[:, dk:dk + L] += dconv @ w[dk].T
     return dpad[:, left:left + L]

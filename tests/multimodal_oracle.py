@@ -11,31 +11,33 @@ example_config/multimodal.json), TF 1.15 Keras semantics:
   shared        :96-104  concat([sequence 32, graph 50]) -> Dense(52) -> relu -> Dense(label_dim)
   cost          :107-113 mask * softmax_cross_entropy; cost_opt = reduce_mean over the padded batch, cost_sum = reduce_sum
 
-Every function computes in float64 whatever it is given."""
+Every function computes in float64 whatever it is given.  The conv-pool and LSTM functions take dtype=np.float32 to evaluate the
+same expressions in fp32 instead: that evaluation's distance from the fp64 one is what an honest fp32 implementation costs at
+a shape, and the GPU shape sweep (tests/test_gpu_seq_shapes.py) derives its bounds from it."""
 import numpy as np
 
 F64 = np.float64
 
 
 # ---- activations --------------------------------------------------------------------------------------------------------
-def hard_sigmoid(z):
-    return np.clip(0.2 * np.asarray(z, F64) + 0.5, 0.0, 1.0)
+def hard_sigmoid(z, dtype=F64):
+    return np.clip(dtype(0.2) * np.asarray(z, dtype) + dtype(0.5), dtype(0.0), dtype(1.0))
 
 
-def hard_sigmoid_grad(z):
-    y = 0.2 * np.asarray(z, F64) + 0.5
-    return np.where((y >= 0.0) & (y <= 1.0), 0.2, 0.0)
+def hard_sigmoid_grad(z, dtype=F64):
+    y = dtype(0.2) * np.asarray(z, dtype) + dtype(0.5)
+    return np.where((y >= 0.0) & (y <= 1.0), dtype(0.2), dtype(0.0))
 
 
-def sigmoid(z):
-    return 1.0 / (1.0 + np.exp(-np.asarray(z, F64)))
+def sigmoid(z, dtype=F64):
+    return dtype(1.0) / (dtype(1.0) + np.exp(-np.asarray(z, dtype)))
 
 
-def _rec(act):
+def _rec(act, dtype=F64):
     if act == "hard_sigmoid":
-        return hard_sigmoid, lambda z, a: hard_sigmoid_grad(z)
+        return (lambda z: hard_sigmoid(z, dtype)), (lambda z, a: hard_sigmoid_grad(z, dtype))
     if act == "sigmoid":
-        return sigmoid, lambda z, a: a * (1.0 - a)
+        return (lambda z: sigmoid(z, dtype)), (lambda z, a: a * (dtype(1.0) - a))
     raise ValueError(act)
 
 
@@ -46,44 +48,48 @@ def same_padding(k):
     return left, k - 1 - left
 
 
-def conv_same(tokens, table, w, b):
+def conv_same(tokens, table, w, b, dtype=F64):
     """-> (padded embedding [B, L + k - 1, E], conv pre-activation [B, L, F])."""
     tokens = np.asarray(tokens)
-    table, w, b = np.asarray(table, F64), np.asarray(w, F64), np.asarray(b, F64)
+    table, w, b = np.asarray(table, dtype), np.asarray(w, dtype), np.asarray(b, dtype)
     B, L = tokens.shape
     k = w.shape[0]
     left, right = same_padding(k)
-    emb = np.zeros((B, L + k - 1, table.shape[1]), F64)
+    emb = np.zeros((B, L + k - 1, table.shape[1]), dtype)
     emb[:, left:left + L] = table[tokens]
     conv = np.broadcast_to(b, (B, L, w.shape[2])).copy()
     for dk in range(k):
-        conv += emb[:, dk:dk + L] @ w[dk]
+        if dtype is F64:
+            conv += emb[:, dk:dk + L] @ w[dk]
+        else:                                 # one term at a time, as a plain fp32 loop sums (BLAS blocks the sum and is closer)
+            for e in range(w.shape[1]):
+                conv += emb[:, dk:dk + L, e:e + 1] * w[dk, e]
     return emb, conv
 
 
-def conv_pool_fwd(tokens, table, w, b, pool):
+def conv_pool_fwd(tokens, table, w, b, pool, dtype=F64):
     """-> (pooled [B, L // pool, F], arg-max index in the window [B, T', F] (lowest among ties), conv pre-activation)."""
-    _, conv = conv_same(tokens, table, w, b)
+    _, conv = conv_same(tokens, table, w, b, dtype)
     B, L, F = conv.shape
     T = L // pool
-    y = np.maximum(conv[:, :T * pool], 0.0).reshape(B, T, pool, F)
+    y = np.maximum(conv[:, :T * pool], dtype(0.0)).reshape(B, T, pool, F)
     return y.max(axis=2), y.argmax(axis=2), conv
 
 
-def conv_pool_bwd(tokens, table, w, b, pool, g):
+def conv_pool_bwd(tokens, table, w, b, pool, g, dtype=F64):
     """d pooled [B, T', F] -> (d table, d w, d b)."""
     tokens = np.asarray(tokens)
-    emb, conv = conv_same(tokens, table, w, b)
-    w = np.asarray(w, F64)
+    emb, conv = conv_same(tokens, table, w, b, dtype)
+    w = np.asarray(w, dtype)
     B, L, F = conv.shape
     k = w.shape[0]
     T = L // pool
-    y = np.maximum(conv[:, :T * pool], 0.0).reshape(B, T, pool, F)
+    y = np.maximum(conv[:, :T * pool], dtype(0.0)).reshape(B, T, pool, F)
     arg = y.argmax(axis=2)
-    dy = np.zeros((B, T, pool, F), F64)
+    dy = np.zeros((B, T, pool, F), dtype)
     bi, ti, fi = np.meshgrid(np.arange(B), np.arange(T), np.arange(F), indexing="ij")
-    dy[bi, ti, arg, fi] = np.asarray(g, F64)
-    dconv = np.zeros((B, L, F), F64)
+    dy[bi, ti, arg, fi] = np.asarray(g, dtype)
+    dconv = np.zeros((B, L, F), dtype)
     dconv[:, :T * pool] = dy.reshape(B, T * pool, F) * (conv[:, :T * pool] > 0)
     db = dconv.sum(axis=(0, 1))
     dw = np.stack([np.einsum("ble,blf->ef", emb[:, dk:dk + L], dconv) for dk in range(k)])
@@ -91,7 +97,7 @@ def conv_pool_bwd(tokens, table, w, b, pool, g):
     for dk in range(k):
         demb[:, dk:dk + L] += dconv @ w[dk].T
     left, _ = same_padding(k)
-    dtable = np.zeros(np.asarray(table).shape, F64)
+    dtable = np.zeros(np.asarray(table).shape, dtype)
     np.add.at(dtable, tokens.reshape(-1), demb[:, left:left + L].reshape(B * L, -1))
     return dtable, dw, db
 
@@ -125,13 +131,13 @@ def conv_pool_loop(tokens, table, w, b, pool):
 
 
 # ---- LSTM(go_backwards=True) -----------------------------------------------------------------------------------------------
-def lstm_fwd(x, wx, wh, b, act="hard_sigmoid"):
+def lstm_fwd(x, wx, wh, b, act="hard_sigmoid", dtype=F64):
     """x [B, T, D] -> (h after input step 0 [B, H], cache for lstm_bwd)."""
-    x, wx, wh, b = (np.asarray(t, F64) for t in (x, wx, wh, b))
+    x, wx, wh, b = (np.asarray(t, dtype) for t in (x, wx, wh, b))
     B, T, _ = x.shape
     H = wh.shape[0]
-    ra, _ = _rec(act)
-    h, c = np.zeros((B, H), F64), np.zeros((B, H), F64)
+    ra, _ = _rec(act, dtype)
+    h, c = np.zeros((B, H), dtype), np.zeros((B, H), dtype)
     zs, cs, hs = [None] * T, [None] * T, [None] * T
     for t in reversed(range(T)):
         z = x[:, t] @ wx + h @ wh + b
@@ -143,13 +149,14 @@ def lstm_fwd(x, wx, wh, b, act="hard_sigmoid"):
 
 
 def lstm_bwd(cache, dh):
-    """d h_final -> (dx [B, T, D], d wx, d wh, d b)."""
+    """d h_final -> (dx [B, T, D], d wx, d wh, d b), in the dtype of the cache."""
     x, wx, wh, b, act, zs, cs, hs = cache
     B, T, D = x.shape
     H = wh.shape[0]
-    ra, rg = _rec(act)
-    dh = np.asarray(dh, F64).copy()
-    dc = np.zeros((B, H), F64)
+    dtype = x.dtype.type
+    ra, rg = _rec(act, dtype)
+    dh = np.asarray(dh, dtype).copy()
+    dc = np.zeros((B, H), dtype)
     dx = np.zeros_like(x)
     dwx, dwh, db = np.zeros_like(wx), np.zeros_like(wh), np.zeros_like(b)
     for t in range(T):                       # reverse of the processing order

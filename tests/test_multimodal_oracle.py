@@ -93,6 +93,70 @@ def test_lstm_against_loop(act):
     assert np.allclose(M.lstm_fwd(x, wx, wh, b, act)[0], M.lstm_loop(x, wx, wh, b, act), rtol=0, atol=1e-12)
 
 
+# the corners of the shape box of include/kgcn_hip.h that tests/test_gpu_seq_shapes.py holds the kernels to, at small B and L
+CONV_CORNERS = [(9, k, pool, E, F) for k in (1, 8) for pool in (1, 8) for E in (1, 32) for F in (1, 64)] + \
+               [(5, 8, 1, 3, 4), (5, 8, 2, 32, 1), (6, 7, 3, 2, 5), (5, 4, 8, 3, 4)]      # k > L; odd k; pool > L (T' = 0)
+
+
+@pytest.mark.parametrize("L,k,pool,E,F", CONV_CORNERS)
+def test_conv_pool_against_loop_at_the_corner_shapes(L, k, pool, E, F):
+    rng = np.random.default_rng([L, k, pool, E, F])
+    tok = rng.integers(0, 5, size=(2, L))
+    table, w, b = rng.standard_normal((5, E)), rng.standard_normal((k, E, F)), rng.standard_normal(F)
+    out = M.conv_pool_fwd(tok, table, w, b, pool)[0]
+    assert out.shape == (2, L // pool, F)
+    assert np.allclose(out, M.conv_pool_loop(tok, table, w, b, pool), rtol=0, atol=1e-12)
+
+
+@pytest.mark.parametrize("act", ["hard_sigmoid", "sigmoid"])
+@pytest.mark.parametrize("D,H", [(D, H) for D in (1, 64) for H in (1, 17, 64)])
+def test_lstm_against_loop_at_the_corner_shapes(D, H, act):
+    rng = np.random.default_rng([D, H])
+    x = rng.standard_normal((2, 3, D))
+    wx, wh, b = rng.standard_normal((D, 4 * H)) * 0.3, rng.standard_normal((H, 4 * H)) * 0.3, rng.standard_normal(4 * H)
+    assert np.allclose(M.lstm_fwd(x, wx, wh, b, act)[0], M.lstm_loop(x, wx, wh, b, act), rtol=0, atol=1e-12)
+
+
+def test_fp32_evaluation_is_the_same_expressions_in_fp32():
+    """dtype=np.float32 (the yardstick of the GPU shape sweep): fp32 results throughout, within fp32 rounding of the fp64 ones."""
+    rng = np.random.default_rng(8)
+    f32 = np.float32
+    tok = rng.integers(0, 9, size=(3, 40))
+    table, w, b = rng.standard_normal((9, 5)).astype(f32), (rng.standard_normal((3, 5, 6)) * 0.4).astype(f32), rng.standard_normal(6).astype(f32)
+    g = rng.standard_normal((3, 10, 6)).astype(f32)
+    pairs = [(M.conv_pool_fwd(tok, table, w, b, 4, f32)[0], M.conv_pool_fwd(tok, table, w, b, 4)[0])]
+    pairs += list(zip(M.conv_pool_bwd(tok, table, w, b, 4, g, f32), M.conv_pool_bwd(tok, table, w, b, 4, g)))
+    wx, wh, bias = (rng.standard_normal(s).astype(f32) * f32(0.3) for s in ((6, 28), (7, 28), (28,)))
+    gh = rng.standard_normal((3, 7)).astype(f32)
+    for act in ("hard_sigmoid", "sigmoid"):
+        h32, c32 = M.lstm_fwd(pairs[0][0], wx, wh, bias, act, f32)
+        h64, c64 = M.lstm_fwd(pairs[0][0], wx, wh, bias, act)
+        pairs += [(h32, h64)] + list(zip(M.lstm_bwd(c32, gh), M.lstm_bwd(c64, gh)))
+    for a32, a64 in pairs:
+        assert a32.dtype == np.float32 and a64.dtype == np.float64 and a32.shape == a64.shape
+        err = np.abs(a32 - a64).max() / np.abs(a64).max()
+        assert 0 < err < 1e-5, err
+
+
+def test_hard_sigmoid_edges_in_fp32_and_fp64():
+    """What the device test of the clip edges relies on.  0.2 z + 0.5 at z = +-2.5 is exactly 1 / 0 in fp32 and in fp64, so the
+    kernel and the oracle stand on the same side.  The float above 2.5 does NOT separate in fp32: 0.2f z rounds to 0.5 + 2^-24
+    and the sum 1 + 2^-24 is a tie that rounds to 1, while fp64 gives y > 1 -- a derivative mask taken from the rounded fp32 y
+    passes a gradient there.  The kernel's rec_act_grad therefore tests z itself, which this pins as equivalent to the oracle."""
+    f32 = np.float32
+    up, lo = f32(2.5), f32(-2.5)
+    above, below = np.nextafter(up, f32(3)), np.nextafter(lo, f32(-3))
+    under, over = np.nextafter(up, f32(0)), np.nextafter(lo, f32(0))
+    assert f32(0.2) * up + f32(0.5) == f32(1.0) and 0.2 * float(up) + 0.5 == 1.0
+    assert f32(0.2) * lo + f32(0.5) == f32(0.0) and 0.2 * float(lo) + 0.5 == 0.0
+    assert f32(0.2) * above + f32(0.5) == f32(1.0) and 0.2 * float(above) + 0.5 > 1.0          # the fp32 tie
+    assert f32(0.2) * below + f32(0.5) < 0 and 0.2 * float(below) + 0.5 < 0.0
+    z = np.array([below, lo, over, under, up, above], f32)
+    assert M.hard_sigmoid_grad(z).tolist() == [0.0, 0.2, 0.2, 0.2, 0.2, 0.0]
+    assert (M.hard_sigmoid_grad(z) != 0).tolist() == ((z >= lo) & (z <= up)).tolist()          # the kernel's test on z
+    assert M.hard_sigmoid(z).tolist()[:2] == [0.0, 0.0] and M.hard_sigmoid(z).tolist()[-2:] == [1.0, 1.0]
+
+
 def _fd(f, a, eps=1e-6, n=12, rng=None):
     """central differences of scalar f at n random entries of array a (in place) -> (indices, values)."""
     rng = rng or np.random.default_rng(0)
@@ -127,6 +191,33 @@ def test_encoder_gradients_against_finite_differences(act):
     h, cache = M.lstm_fwd(pooled, wx, wh, bias, act)
     dx, dwx, dwh, dbias = M.lstm_bwd(cache, gh)
     dtab, dw, db = M.conv_pool_bwd(tok, table, w, b, 4, dx)
+    for arr, grad in ((table, dtab), (w, dw), (b, db), (wx, dwx), (wh, dwh), (bias, dbias)):
+        idx, num = _fd(loss, arr)
+        ana = np.array([grad[i] for i in idx])
+        assert np.allclose(ana, num, rtol=1e-5, atol=1e-7), (ana, num)
+
+
+@pytest.mark.parametrize("act", ["hard_sigmoid", "sigmoid"])
+@pytest.mark.parametrize("L,E,k,F,pool,H", [(6, 1, 1, 1, 1, 1), (17, 32, 8, 64, 8, 64), (5, 3, 8, 5, 1, 17), (9, 32, 1, 1, 8, 17),
+                                            (9, 1, 8, 64, 1, 1)])
+def test_encoder_gradients_against_finite_differences_at_the_corner_shapes(L, E, k, F, pool, H, act):
+    rng = np.random.default_rng([L, E, k, F, pool, H])
+    B, S = 2, 6
+    tok = rng.integers(0, S, size=(B, L))
+    table, w, b = rng.standard_normal((S, E)), rng.standard_normal((k, E, F)) / np.sqrt(k * E), rng.standard_normal(F) * 0.1 + 0.2
+    wx, wh = rng.standard_normal((F, 4 * H)) * 0.4 / np.sqrt(F), rng.standard_normal((H, 4 * H)) * 0.4 / np.sqrt(H)
+    bias = rng.standard_normal(4 * H) * 0.3
+    gh = rng.standard_normal((B, H))
+
+    def loss():
+        pooled = M.conv_pool_fwd(tok, table, w, b, pool)[0]
+        return float((M.lstm_fwd(pooled, wx, wh, bias, act)[0] * gh).sum())
+
+    pooled = M.conv_pool_fwd(tok, table, w, b, pool)[0]
+    assert pooled.shape == (B, L // pool, F) and L // pool >= 1
+    h, cache = M.lstm_fwd(pooled, wx, wh, bias, act)
+    dx, dwx, dwh, dbias = M.lstm_bwd(cache, gh)
+    dtab, dw, db = M.conv_pool_bwd(tok, table, w, b, pool, dx)
     for arr, grad in ((table, dtab), (w, dw), (b, db), (wx, dwx), (wh, dwh), (bias, dbias)):
         idx, num = _fd(loss, arr)
         ana = np.array([grad[i] for i in idx])
