@@ -9,11 +9,11 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # Development overrides.  KGCN_HIP_LIB: load another build of the library (tools/variant_bench.py times alternative builds).
-# KGCN_DENSE_ROUTE / KGCN_GEMM3_MW: kernel-routing knobs that the library itself only honours when it was compiled with
-# -DKGCN_DEV_KNOBS (make DEV_KNOBS=1) -- the shipped build ignores them.  Anything set here is reported by
+# KGCN_SPMM_BLOCKS / KGCN_GIN_JOIN / KGCN_GIN_DOT: Python-side routing switches.  (The library's own development knobs exist only
+# in a -DKGCN_DEV_KNOBS build, make DEV_KNOBS=1; the dense family has none left.)  Anything set here is reported by
 # active_overrides() (bench.py prints it in its JSON line) and warned about once at import, because a stray variable
 # changes summation order / which binary produced the numbers.
-DEV_ENV_VARS = ("KGCN_HIP_LIB", "KGCN_DENSE_ROUTE", "KGCN_GEMM3_MW", "KGCN_GEMM3_CUT", "KGCN_WGRADX", "KGCN_WGRADN", "KGCN_GEMMH", "KGCN_WGRADL", "KGCN_SPMM_BLOCKS", "KGCN_GIN_JOIN", "KGCN_GIN_DOT")
+DEV_ENV_VARS = ("KGCN_HIP_LIB", "KGCN_SPMM_BLOCKS", "KGCN_GIN_JOIN", "KGCN_GIN_DOT")
 LIB_PATH = os.environ.get("KGCN_HIP_LIB") or os.path.join(_HERE, "csrc", "libkgcn_hip.so")
 
 
@@ -24,8 +24,8 @@ def active_overrides():
 
 if active_overrides():
     import warnings
-    warnings.warn("kgcn_amd: development overrides active: %r (KGCN_HIP_LIB swaps the native library; the routing knobs "
-                  "act only on a -DKGCN_DEV_KNOBS build)" % (active_overrides(),), RuntimeWarning, stacklevel=2)
+    warnings.warn("kgcn_amd: development overrides active: %r (KGCN_HIP_LIB swaps the native library, the others "
+                  "change kernel routing)" % (active_overrides(),), RuntimeWarning, stacklevel=2)
 
 c_f32p = ctypes.c_void_p
 c_i32p = ctypes.c_void_p

@@ -15,40 +15,16 @@
 // The K index is permuted (half hi = l>>5 owns k in [16*hi, 16*hi+16) of every 32-wide chunk) so
 // that a lane's 16 A values are contiguous in LDS (4 x ds_read_b128 instead of 16 x ds_read_b32);
 // A and B use the same permutation, so the sum over k is unchanged.
+//
+// No longer in this file: dense_wgrad_kernel (row-chunk weight gradient of round 1, unreachable behind the persistent kernel; its
+// plan still sizes kgcn_dense_wgrad_workspace_bytes: profiles/r09_dense_routes.txt) and the switch KGCN_DENSE_ROUTE=gemm3 (never
+// read W from the fragment table: the table is +15 % forward / +5 % dX at 256 -> 256, profiles/r02_gemm_experiments.txt).
 #include <atomic>
-#include <cstdlib>
-#include <cstring>
 #include <mutex>
 
-#include "kgcn_common.h"
+#include "dense_kernels.h"
 
 namespace kgcn {
-
-int launch_gemm3_fwd(const float* x, long m, int din, long x_ld, const float* w, long w_ld, int trans_w,
-                     const float* bias, float* y, int dout, long y_ld, int act, const void* table, hipStream_t s);
-bool narrow_fwd_ok(const float* x, int din, long x_ld, const float* y, int dout, long y_ld);
-int launch_narrow_fwd(const float* x, long m, int din, const float* w, long w_ld, int trans_w, const float* bias,
-                      float* y, int dout, int act, hipStream_t s);
-bool narrow_wgrad_ok(const float* x, int din, long x_ld, const float* dy, int dout, long dy_ld);
-int launch_narrow_wgrad(const float* x, const float* dy, long m, int din, int dout, float* part_dw, float* part_db,
-                        int nblocks, hipStream_t s);
-int launch_gemm3_dx_dact(const float* grad, const float* act_out, float* dpre, long m, int k, long ld, const void* table,
-                         float* dx, int n, long dx_ld, int dact, hipStream_t s, const float* pooled_grad = nullptr,
-                         int n_nodes = 0, long pooled_ld = 0);
-bool gemmn_pays(const float* x, int din, long x_ld, int dout);
-int launch_gemmn_fwd(const float* x, long m, int din, long x_ld, const void* table, const float* bias, float* y, int dout,
-                     long y_ld, int act, hipStream_t s);
-bool wgradn_ok(const float* x, int din, long x_ld, int dout);
-int launch_wgradn(const float* x, long x_ld, const float* dy, long dy_ld, long m, int din, int dout, float* part_dw,
-                  float* part_db, int nblocks, hipStream_t s);
-int64_t wtable_bytes(int din, int dout);
-void launch_wtable_split(const float* w, long w_ld, int trans_w, int din, int dout, void* workspace, hipStream_t s);
-int launch_gemm3_wgrad(const float* x, long x_ld, const float* dy, long dy_ld, long m, int din, int dout,
-                       float* part_dw, float* part_db, int nblocks, hipStream_t s, const float* yact = nullptr,
-                       int act = KGCN_ACT_NONE);
-bool gemmh_wgrad_ok(int din, int dout, long m);
-int launch_gemmh_wgrad(const float* x, long x_ld, const float* dy, long dy_ld, long m, int din, int dout, float* part_dw,
-                       float* part_db, int nblocks, hipStream_t s, const float* yact, int act);
 
 constexpr int BM = 128;      // rows per workgroup (32 per wave)
 constexpr int BN = 64;       // output columns per workgroup
@@ -143,70 +119,6 @@ __global__ __launch_bounds__(256) void dense_fwd_kernel(
       if (c0 < dout) y[row * y_ld + c0] = acc0[r];
       if (c1 < dout) y[row * y_ld + c1] = acc1[r];
     }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// dW / dbias partials: block (chunk of rows, 64-wide din block, 64-wide dout block); wave (ti,tj)
-// owns one 32x32 tile of the 64x64 output block.  K dimension of the MFMA = the m rows.
-// ------------------------------------------------------------------------------------------------
-constexpr int WG_ROWS = 32;  // rows staged per step
-
-__global__ __launch_bounds__(256) void dense_wgrad_kernel(
-    const float* __restrict__ x, long x_ld, const float* __restrict__ dy, long dy_ld, long m,
-    int din, int dout, long rows_per_chunk, float* __restrict__ part_dw,
-    float* __restrict__ part_db) {
-  __shared__ __attribute__((aligned(16))) float Xs[WG_ROWS * 64];
-  __shared__ __attribute__((aligned(16))) float Gs[WG_ROWS * 64];
-
-  const int tid = threadIdx.x;
-  const int wave = tid >> 6, lane = tid & 63;
-  const int li = lane & 31, hi = lane >> 5;
-  const int ti = wave >> 1, tj = wave & 1;
-  const int i0 = blockIdx.y * 64, j0 = blockIdx.z * 64;
-  const long r_begin = (long)blockIdx.x * rows_per_chunk;
-  long r_end = r_begin + rows_per_chunk;
-  if (r_end > m) r_end = m;
-
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  float colsum = 0.f;
-
-  for (long r0 = r_begin; r0 < r_end; r0 += WG_ROWS) {
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-      const int idx = tid + it * 256;  // 2048 floats each
-      const int rr = idx >> 6, c = idx & 63;
-      const long row = r0 + rr;
-      const bool rok = row < r_end;
-      Xs[idx] = (rok && i0 + c < din) ? x[row * x_ld + i0 + c] : 0.f;
-      Gs[idx] = (rok && j0 + c < dout) ? dy[row * dy_ld + j0 + c] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int s = 0; s < 16; ++s) {
-      const int rr = s + 16 * hi;
-      const float a = Xs[rr * 64 + ti * 32 + li];   // A[i = din idx][k = row]
-      const float b = Gs[rr * 64 + tj * 32 + li];   // B[k = row][j = dout idx]
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
-      colsum += b;
-    }
-    __syncthreads();
-  }
-
-  // partial dW tile
-  float* pw = part_dw + (long)blockIdx.x * din * dout;
-  const int col = j0 + tj * 32 + li;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int row = i0 + ti * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-    if (row < din && col < dout) pw[(long)row * dout + col] = acc[r];
-  }
-  // partial dbias: only the blocks/waves of the first din block contribute
-  if (part_db && blockIdx.y == 0 && ti == 0) {
-    colsum += __shfl_xor(colsum, 32, 64);
-    if (hi == 0 && col < dout) part_db[(long)blockIdx.x * dout + col] = colsum;
   }
 }
 
@@ -467,6 +379,12 @@ __global__ __launch_bounds__(512, 2) void dense_wgrad_persist_kernel(
   }
 }
 
+// more than 64 KB of dynamic LDS has to be allowed per kernel (and per thread that launches it)
+template <typename Kernel>
+static void allow_full_lds(Kernel kernel) {
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
+}
+
 static int persist_blocks(long m) {
   long tiles = (m + 31) / 32;
   long b = (tiles + P_WAVES - 1) / P_WAVES;
@@ -474,33 +392,9 @@ static int persist_blocks(long m) {
   return b < 1 ? 1 : (int)b;
 }
 
-static void wgrad_plan(long m, long* rows_per_chunk, int* nchunks) {
-  // ~4 workgroups per CU worth of row chunks, each a multiple of WG_ROWS rows
-  long target = (long)kNumCU * 4;
-  long rpc = (m + target - 1) / target;
-  rpc = ((rpc + WG_ROWS - 1) / WG_ROWS) * WG_ROWS;
-  if (rpc < WG_ROWS) rpc = WG_ROWS;
-  *rows_per_chunk = rpc;
-  *nchunks = (int)((m + rpc - 1) / rpc);
-  if (*nchunks < 1) *nchunks = 1;
-}
-
 int launch_reduce_partials(const float* part, int nparts, long n, float* out, hipStream_t s) {
   hipLaunchKernelGGL(reduce_partials_kernel, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, s,
                      part, nparts, n, out, nullptr, 0L, nullptr);
-  return check_launch("reduce_partials_kernel");
-}
-
-// both reductions of a layer (dW [n], dbias [n2]) in one launch; n is rounded up to whole 32-output groups
-// of the first array, so no workgroup straddles the two
-int launch_reduce_partials2(const float* part, int nparts, long n, float* out, const float* part2, long n2,
-                            float* out2, hipStream_t s) {
-  if (n % 32) {                         // keep the simple kernel: two launches when dW is not a multiple of 32
-    if (int rc = launch_reduce_partials(part, nparts, n, out, s)) return rc;
-    return launch_reduce_partials(part2, nparts, n2, out2, s);
-  }
-  hipLaunchKernelGGL(reduce_partials_kernel, dim3((unsigned)((n + n2 + 31) / 32)), dim3(256), 0, s,
-                     part, nparts, n, out, part2, n2, out2);
   return check_launch("reduce_partials_kernel");
 }
 
@@ -589,42 +483,79 @@ int reduce_or_defer(const float* part, int nparts, long n, float* out, hipStream
   g_pending[g_npending++] = PendingReduce{part, nparts, n, out};
   return 0;
 }
-static int flush_pending(hipStream_t s) {
-  std::lock_guard<std::mutex> lock(g_pending_mutex);
-  return flush_pending_locked(s);
-}
 
 }  // namespace kgcn
 
 using namespace kgcn;
 
-extern "C" int kgcn_reduce_defer(int32_t on) {
-  return g_defer_reduce.exchange(on != 0) ? 1 : 0;
-}
+extern "C" int kgcn_reduce_defer(int32_t on) { return g_defer_reduce.exchange(on != 0) ? 1 : 0; }
 extern "C" int kgcn_reduce_pending(void) { return g_npending; }
-extern "C" int kgcn_reduce_flush(void* stream) { return flush_pending(as_stream(stream)); }
+extern "C" int kgcn_reduce_flush(void* stream) {
+  std::lock_guard<std::mutex> lock(g_pending_mutex);
+  return flush_pending_locked(as_stream(stream));
+}
 
-// wide layers take the bf16-split GEMM of gemm3.hip (W pre-split into the fragment table of wtable.hip when the caller
-// provides the workspace for it)
+// ---- routing -----------------------------------------------------------------------------------------------------------
+// Which kernel a call takes is decided by fwd_route (forward and dX) and wgrad_route (weight gradient) and nowhere else: the
+// entry points switch over their answer, and so do the ABI's reporting functions (mfma_products, *_supported, *_workspace_bytes).
+// The alignment facts of a call's two row-major operands as plain values.  a: the streamed input (x, the gradient of a dX);
+// b: the output of a forward / dX, the gradient of a weight gradient.
+struct RowFacts { bool a16; long a_ld; bool b16; long b_ld; };
+// what the reporting functions assume: 16-byte aligned operands, input rows padded to whole float4
+static RowFacts aligned_rows(int din, int dout) { return RowFacts{true, (long)((din + 3) & ~3), true, (long)dout}; }
+constexpr long kManyRows = 1L << 20;      // stands for "a large batch" where a query has no row count
+
+enum class FwdRoute {
+  SkinnyN, SkinnyK,      // read-out layers (2..16 columns on one side): a row per wave, no panels (skinny.hip)
+  Gemmh,                 // wide layer, f16 two-piece kernel, W' from the table (gemmh.hip)
+  Gemm3Table, Gemm3,     // wide layer, bf16 three-piece kernel: W from the table / split inside the kernel (gemm3.hip)
+  Gemmn,                 // wide input, narrow output (256 -> 50): one 64-column block per wave, W from the table (gemmn.hip)
+  Narrow,                // 50-wide layers: flat tile movement (narrow.hip)
+  Persist, Tiled         // f32 MFMA with the weight panel resident in LDS / tiled fallback when it does not fit
+};
+
+// wide layers are f32-MFMA bound -> the split GEMMs.  With a workspace W is split ONCE into a fragment table (wtable.hip) that
+// the waves read from L2, and the kernel's staging only splits x: measured ahead of splitting W inside the kernel
+// (tools/gemm_bench.py, 204,800 rows: 256 -> 256 +15% forward / +5% dX, 512 -> 256 +5% / -3%, 256 -> 512 +2%)
 static bool wide_layer(int din, int dout) { return dout > 128 && din >= 32; }
-// where reading W pre-split from the fragment table measured ahead of splitting it inside the kernel (tools/gemm_bench.py,
-// 204,800 rows: 256 -> 256 +15% forward / +5% dX, 512 -> 256 +5% / -3%, 256 -> 512 +2%; 128 -> 256 -14%: few k-steps)
-static bool table_pays(int din, int dout) { return wide_layer(din, dout) && din >= 32; }
+// LDS of dense_fwd_persist_kernel: weight panel [din_pad x 64] next to 8 per-wave x tiles
+static size_t persist_fwd_lds(int din) { return (size_t)((din + 63) / 64) * 64 * 64 * 4 + (size_t)P_WAVES * PT_FLOATS * 4; }
 
-namespace kgcn {
-bool skinny_n_ok(int din, int dout, int trans_w);
-bool skinny_k_ok(int din, int dout);
-int launch_skinny_n_fwd(const float* x, long m, int din, long x_ld, const float* w, long w_ld, const float* bias, float* y,
-                        int dout, long y_ld, int act, hipStream_t s);
-int launch_skinny_k_fwd(const float* x, long m, int din, long x_ld, const float* w, long w_ld, int trans_w, const float* bias,
-                        float* y, int dout, long y_ld, int act, hipStream_t s);
-int skinny_wgrad_parts(long m);
-int launch_skinny_n_wgrad(const float* x, long m, int din, long x_ld, const float* g, long g_ld, int dout, float* part_dw,
-                          float* part_db, int nparts, hipStream_t s);
-bool wgradx_ok(int din, int dout, long x_ld, long dy_ld);
-int launch_wgradx(const float* x, long x_ld, const float* dy, long dy_ld, long m, int din, int dout, float* part_dw, float* part_db,
-                  int nparts, hipStream_t s, const float* yact, int act);
-}  // namespace kgcn
+// have_table: the caller's workspace holds (or has room for) the fragment table of this layer
+static FwdRoute fwd_route(long m, int din, int dout, int trans_w, const RowFacts& f, bool have_table) {
+  if (skinny_n_ok(din, dout, trans_w)) return FwdRoute::SkinnyN;
+  if (skinny_k_ok(din, dout)) return FwdRoute::SkinnyK;
+  const bool table = have_table && m >= 1024;
+  if (wide_layer(din, dout)) {
+    if (!table) return FwdRoute::Gemm3;
+    return gemmh_fwd_ok(f.a16, m, din, f.a_ld, dout) ? FwdRoute::Gemmh : FwdRoute::Gemm3Table;
+  }
+  if (table && gemmn_pays(f.a16, din, f.a_ld, dout)) return FwdRoute::Gemmn;
+  if (narrow_fwd_ok(f.a16, din, f.a_ld, f.b16, dout, f.b_ld)) return FwdRoute::Narrow;
+  return persist_fwd_lds(din) <= (size_t)kLdsBytes ? FwdRoute::Persist : FwdRoute::Tiled;
+}
+static bool wide_table_route(FwdRoute r) { return r == FwdRoute::Gemmh || r == FwdRoute::Gemm3Table; }
+static bool reads_table(FwdRoute r) { return wide_table_route(r) || r == FwdRoute::Gemmn; }
+
+static int launch_fwd_persist(const float* x, long m, int din, long x_ld, const float* w, long w_ld, int trans_w,
+                              const float* bias, float* y, int dout, long y_ld, int act, hipStream_t s) {
+  const int kp = ((din + 63) / 64) * 64;
+  const size_t lds = persist_fwd_lds(din);
+  const bool vec = (din % 4 == 0) && (x_ld % 4 == 0) && aligned16(x);
+  static thread_local bool attr_set = false;
+  if (!attr_set) {
+    allow_full_lds(dense_fwd_persist_kernel<true>);
+    allow_full_lds(dense_fwd_persist_kernel<false>);
+    attr_set = true;
+  }
+  // two workgroups per CU when the panel is small enough (4 waves per SIMD in total)
+  int blocks = persist_blocks(m);
+  if (2 * lds <= (size_t)kLdsBytes && blocks == kNumCU) blocks = 2 * kNumCU;
+  dim3 grid((unsigned)blocks, (unsigned)((dout + 63) / 64));
+  hipLaunchKernelGGL(vec ? dense_fwd_persist_kernel<true> : dense_fwd_persist_kernel<false>, grid, dim3(64 * P_WAVES), lds, s, x,
+                     m, din, x_ld, w, w_ld, trans_w, bias, y, dout, y_ld, kp, act);
+  return check_launch("dense_fwd_persist_kernel");
+}
 
 // table_ready: `workspace` already holds the fragment table of (w, trans_w) (kgcn_wtable_split_multi at the start of the step)
 static int dense_fwd_impl(const float* x, int64_t m, int32_t din, int64_t x_ld, const float* w, int64_t w_ld,
@@ -637,68 +568,35 @@ static int dense_fwd_impl(const float* x, int64_t m, int32_t din, int64_t x_ld, 
   if (!x || !w || !y) return fail("kgcn_dense_fwd_f32: NULL operand");
   if (x_ld < din || y_ld < dout) return fail("kgcn_dense_fwd_f32: leading dimension too small");
   if (w_ld < (trans_w ? din : dout)) return fail("kgcn_dense_fwd_f32: w_ld too small");
-  // read-out layers (2..16 columns on one side): a row per wave, no panels (skinny.hip)
-  if (skinny_n_ok(din, dout, trans_w))
-    return launch_skinny_n_fwd(x, (long)m, din, (long)x_ld, w, (long)w_ld, bias, y, dout, (long)y_ld, act, as_stream(stream));
-  if (skinny_k_ok(din, dout))
-    return launch_skinny_k_fwd(x, (long)m, din, (long)x_ld, w, (long)w_ld, trans_w, bias, y, dout, (long)y_ld, act,
-                               as_stream(stream));
-  // wide layers: f32-MFMA bound -> the bf16-split GEMM (gemm3.hip).  With a workspace W is split ONCE into a fragment
-  // table (wtable.hip) that the waves read from L2, and the kernel's staging only splits x.
-  if (wide_layer(din, dout)) {
-    static const char* route = dev_knob("KGCN_DENSE_ROUTE");         // development: "gemm3" = never use the table
-    const void* table = nullptr;
-    if (!(route && !strcmp(route, "gemm3")) && table_pays(din, dout) && workspace &&
-        workspace_bytes >= wtable_bytes(din, dout) && m >= 1024) {
-      if (!table_ready) launch_wtable_split(w, (long)w_ld, trans_w, din, dout, workspace, as_stream(stream));
-      table = workspace;
-    }
-    return launch_gemm3_fwd(x, (long)m, din, (long)x_ld, w, (long)w_ld, trans_w, bias, y, dout, (long)y_ld, act, table,
-                            as_stream(stream));
-  }
-  // wide input, narrow output (256 -> 50): one 64-column block per wave on the bf16 pipe (gemmn.hip), W from the table
-  if (gemmn_pays(x, din, (long)x_ld, dout) && workspace && workspace_bytes >= wtable_bytes(din, dout) && m >= 1024) {
-    static const char* route = dev_knob("KGCN_DENSE_ROUTE");
-    if (!(route && !strcmp(route, "gemm3"))) {
-      if (!table_ready) launch_wtable_split(w, (long)w_ld, trans_w, din, dout, workspace, as_stream(stream));
-      return launch_gemmn_fwd(x, (long)m, din, (long)x_ld, workspace, bias, y, dout, (long)y_ld, act, as_stream(stream));
-    }
-  }
-  // 50-wide layers: flat tile movement (narrow.hip)
-  if (narrow_fwd_ok(x, din, (long)x_ld, y, dout, (long)y_ld))
-    return launch_narrow_fwd(x, (long)m, din, w, (long)w_ld, trans_w, bias, y, dout, act, as_stream(stream));
-  {
-    // fast path: weight panel [din_pad x 64] resident in LDS next to 8 per-wave x tiles
-    const int kp = ((din + 63) / 64) * 64;
-    const size_t lds = (size_t)kp * 64 * 4 + (size_t)P_WAVES * PT_FLOATS * 4;
-    if (lds <= (size_t)kLdsBytes) {
-      const bool vec = (din % 4 == 0) && (x_ld % 4 == 0) && aligned16(x);
-      static thread_local bool attr_set = false;
-      if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dense_fwd_persist_kernel<true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dense_fwd_persist_kernel<false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        attr_set = true;
-      }
-      // two workgroups per CU when the panel is small enough (4 waves per SIMD in total)
-      int blocks = persist_blocks(m);
-      if (2 * lds <= (size_t)kLdsBytes && blocks == kNumCU) blocks = 2 * kNumCU;
-      dim3 grid((unsigned)blocks, (unsigned)((dout + 63) / 64));
-      if (vec)
-        hipLaunchKernelGGL(dense_fwd_persist_kernel<true>, grid, dim3(64 * P_WAVES), lds, as_stream(stream), x,
-                           (long)m, din, (long)x_ld, w, (long)w_ld, trans_w, bias, y, dout, (long)y_ld, kp, act);
-      else
-        hipLaunchKernelGGL(dense_fwd_persist_kernel<false>, grid, dim3(64 * P_WAVES), lds, as_stream(stream), x,
-                           (long)m, din, (long)x_ld, w, (long)w_ld, trans_w, bias, y, dout, (long)y_ld, kp, act);
-      return check_launch("dense_fwd_persist_kernel");
-    }
+  hipStream_t s = as_stream(stream);
+  const FwdRoute route = fwd_route((long)m, din, dout, trans_w, RowFacts{aligned16(x), (long)x_ld, aligned16(y), (long)y_ld},
+                                   workspace && workspace_bytes >= wtable_bytes(din, dout));
+  if (reads_table(route) && !table_ready) launch_wtable_split(w, (long)w_ld, trans_w, din, dout, workspace, s);
+  switch (route) {
+    case FwdRoute::SkinnyN:
+      return launch_skinny_n_fwd(x, (long)m, din, (long)x_ld, w, (long)w_ld, bias, y, dout, (long)y_ld, act, s);
+    case FwdRoute::SkinnyK:
+      return launch_skinny_k_fwd(x, (long)m, din, (long)x_ld, w, (long)w_ld, trans_w, bias, y, dout, (long)y_ld, act, s);
+    case FwdRoute::Gemmh:                                // W' lives behind the bf16 section of the table
+      return launch_gemmh_fwd(x, (long)m, din, (long)x_ld, static_cast<const char*>(workspace) + wtable_bf16_bytes(din, dout),
+                              bias, y, dout, (long)y_ld, act, s);
+    case FwdRoute::Gemm3Table:
+    case FwdRoute::Gemm3:
+      return launch_gemm3_fwd(x, (long)m, din, (long)x_ld, w, (long)w_ld, trans_w, bias, y, dout, (long)y_ld, act,
+                              route == FwdRoute::Gemm3Table ? workspace : nullptr, s);
+    case FwdRoute::Gemmn:
+      return launch_gemmn_fwd(x, (long)m, din, (long)x_ld, workspace, bias, y, dout, (long)y_ld, act, s);
+    case FwdRoute::Narrow:
+      return launch_narrow_fwd(x, (long)m, din, w, (long)w_ld, trans_w, bias, y, dout, act, s);
+    case FwdRoute::Persist:
+      return launch_fwd_persist(x, (long)m, din, (long)x_ld, w, (long)w_ld, trans_w, bias, y, dout, (long)y_ld, act, s);
+    case FwdRoute::Tiled: break;
   }
   const long gx = (m + BM - 1) / BM;
   if (gx > 0x7fffffffL) return fail("kgcn_dense_fwd_f32: m too large");
   dim3 grid((unsigned)gx, (unsigned)((dout + BN - 1) / BN));
-  hipLaunchKernelGGL(dense_fwd_kernel, grid, dim3(256), 0, as_stream(stream), x, (long)m, din,
-                     (long)x_ld, w, (long)w_ld, trans_w, bias, y, dout, (long)y_ld, act);
+  hipLaunchKernelGGL(dense_fwd_kernel, grid, dim3(256), 0, s, x, (long)m, din, (long)x_ld, w, (long)w_ld, trans_w, bias, y,
+                     dout, (long)y_ld, act);
   return check_launch("dense_fwd_kernel");
 }
 
@@ -718,10 +616,10 @@ static int dense_dx_dact_impl(const float* grad, const float* act_out, int64_t m
   if (!grad || !act_out || !w || !dx || !dpre) return fail("kgcn_dense_dx_dact_f32: NULL operand");
   if (dpre == grad) return fail("kgcn_dense_dx_dact_f32: dpre must not alias grad");
   if (ld < dout || dx_ld < din || w_ld < dout) return fail("kgcn_dense_dx_dact_f32: leading dimension too small");
-  // the contraction runs over the layer's OUTPUT width: K = dout, N = din, W used transposed
-  static const char* route = dev_knob("KGCN_DENSE_ROUTE");
-  if (!(route && !strcmp(route, "gemm3")) && table_pays(dout, din) && workspace && workspace_bytes >= wtable_bytes(dout, din) &&
-      m >= 1024) {
+  // the contraction runs over the layer's OUTPUT width: K = dout, N = din, W used transposed.  Where that product takes a wide
+  // table kernel, act' is formed inside it (the launcher tries the f16 kernel first and falls through to the bf16 one)
+  if (wide_table_route(fwd_route((long)m, dout, din, 1, RowFacts{aligned16(grad), (long)ld, aligned16(dx), (long)dx_ld},
+                                 workspace && workspace_bytes >= wtable_bytes(dout, din)))) {
     if (!table_ready) launch_wtable_split(w, (long)w_ld, 1, dout, din, workspace, as_stream(stream));
     const int rc = launch_gemm3_dx_dact(grad, act_out, dpre, (long)m, dout, (long)ld, workspace, dx, din, (long)dx_ld, act,
                                         as_stream(stream));
@@ -737,7 +635,8 @@ static int dense_dx_dact_impl(const float* grad, const float* act_out, int64_t m
 
 // 1 when kgcn_dense_dx_dact_gather_f32 takes this shape (the fused table form of the wide layers)
 extern "C" int kgcn_dense_dx_dact_gather_supported(int64_t m, int32_t din, int32_t dout) {
-  return (m >= 1024 && din > 0 && dout > 0 && dout % 4 == 0 && table_pays(dout, din)) ? 1 : 0;
+  return (din > 0 && dout > 0 && dout % 4 == 0 && wide_table_route(fwd_route((long)m, dout, din, 1, aligned_rows(dout, din), true)))
+             ? 1 : 0;
 }
 
 extern "C" int kgcn_dense_dx_dact_gather_f32(const float* grad, const float* pooled_grad, int64_t pooled_ld, int32_t n_nodes,
@@ -766,11 +665,6 @@ extern "C" int kgcn_dense_dx_dact_gather_f32(const float* grad, const float* poo
 // d epsilon of a GINAggregate in front of an activated wide layer whose INPUT needs no gradient (the first block of model_gin.py):
 // <(grad (.) act'(act_out)) W^T, dotx> with the product never stored (gemmh.hip, dot form); d pre-activation is written as usual.
 namespace kgcn {
-int launch_gemmh_dx_dact(const float* grad, const float* act_out, float* dpre, long m, int k, long ld, const void* tabh, float* dx,
-                         int n, long dx_ld, int dact, hipStream_t s, const float* pooled_grad, int n_nodes, long pooled_ld,
-                         float* dot_part);
-int gemmh_dot_parts(long m, int dout);
-int64_t wtable_bf16_bytes(int din, int dout);
 __global__ __launch_bounds__(256) void dx_dot_final_kernel(const float* __restrict__ part, int nparts, float* __restrict__ out) {
   __shared__ float red[4];
   float s = 0.f;
@@ -822,12 +716,6 @@ extern "C" int kgcn_dense_dx_dact_dot_f32(const float* grad, const float* act_ou
 // ---- one-pass backward of a wide dense layer (gemmb.hip): dX, dW and dbias from ONE sweep over (grad, act_out, x); the
 // d pre-activation tensor is never written.  The weight-gradient partials go through the same second stage as every other
 // weight gradient (deferrable: kgcn_reduce_defer).
-namespace kgcn {
-int launch_gemmb(const float* grad, const float* act_out, long m, int din, int dout, long ld, const float* x, long x_ld,
-                 const void* tabh, float* dx, long dx_ld, float* part_dw, float* part_db, int dact, const float* pooled_grad,
-                 int n_nodes, long pooled_ld, hipStream_t s, float* dot_part);
-}  // namespace kgcn
-
 extern "C" int kgcn_dense_bwd_supported(int64_t m, int32_t din, int32_t dout) {
   return (din > 128 && din <= 256 && dout == 256 && din % 4 == 0 && m >= (int64_t)kNumCU * 64) ? 1 : 0;
 }
@@ -912,7 +800,9 @@ extern "C" int kgcn_dense_dx_dact_tab_f32(const float* grad, const float* act_ou
 }
 
 extern "C" int64_t kgcn_dense_fwd_workspace_bytes(int32_t din, int32_t dout) {
-  if (din <= 0 || dout <= 0 || !(table_pays(din, dout) || (dout <= 64 && din >= 128 && din % 4 == 0))) return 0;
+  // the query does not know W's orientation: asked for the transposed one (dX), which has no read-out kernel in front of
+  // the table routes
+  if (din <= 0 || dout <= 0 || !reads_table(fwd_route(kManyRows, din, dout, 1, aligned_rows(din, dout), true))) return 0;
   return wtable_bytes(din, dout);
 }
 
@@ -959,61 +849,97 @@ extern "C" int kgcn_dense_fwd_act_f32(const float* x, int64_t m, int32_t din, in
   return dense_fwd_impl(x, m, din, x_ld, w, w_ld, trans_w, bias, y, dout, y_ld, act, nullptr, 0, stream);
 }
 
-namespace kgcn { bool gemmh_fwd_ok(const float* x, long m, int din, long x_ld, int dout); }
+// ---- weight-gradient route ---------------------------------------------------------------------------------------------
+enum class WgradRoute {
+  Skinny,                // read-out layers: lanes own k, the 2..16 gradient columns of a row are wave-uniform (skinny.hip)
+  Wgradx,                // narrow input, wide output (81 -> 256): operands straight from memory, split in registers (wgradx.hip)
+  Gemmh, Gemm3,          // wide layers: f16 two-piece (gemmh.hip) / bf16 three-piece (gemm3.hip) GEMM over row ranges
+  Wgradn,                // wide input, narrow output (256 x 50): the whole dW block per wave on the bf16 pipe (wgradn.hip)
+  Narrow,                // 50-wide layers: flat tile movement (narrow.hip)
+  Persist                // f32 MFMA, one workgroup (8 waves) per CU and per 64x64 output block
+};
+struct WgradPlan { WgradRoute route; int nparts; };      // nparts partial results [din x dout] + [dout] in the workspace
+
+// wide layers, at least this many rows per row range: a range's partial is a whole [din x dout] block (256 KB at 256 x 256) --
+// with one 32-row chunk per workgroup sparse.py's 4,457 rows wrote 128 partials = 32 MB per layer and the step's reduction
+// launch read 119 MB (profiles/r05_h_cfg3_rocprof.txt).  A/B on one box, cfg3 whole step: 32 rows 0.308 ms, 64 rows 0.301,
+// 128 rows 0.318 (too few workgroups), 256 rows 0.364
+constexpr long kWgradMinRows = 64;
+
+// dact: d pre-activation = dy (.) act'(layer output) is formed inside the kernel (kgcn_dense_wgrad_dact_f32)
+static WgradPlan wgrad_route(long m, int din, int dout, bool dact, const RowFacts& f) {
+  if (!dact && skinny_n_ok(din, dout, 0)) return {WgradRoute::Skinny, skinny_wgrad_parts(m)};
+  // one workgroup per CU (four per CU: 101 instead of 94 us and a four times larger second stage)
+  if (wgradx_ok(din, dout) && m >= 4096) return {WgradRoute::Wgradx, kNumCU};
+  if (din > 64 && dout > 128) {
+    // one partial per row-range workgroup, <= kNumCU of them over the [128 x 256] blocks of dW
+    const int tiles = ((din + 127) / 128) * ((dout + 255) / 256);
+    long nb = kNumCU / tiles;
+    if (nb < 1) nb = 1;
+    const long chunks = (m + kWgradMinRows - 1) / kWgradMinRows;
+    if (nb > chunks) nb = chunks;
+    return {gemmh_wgrad_ok(din, dout, m) ? WgradRoute::Gemmh : WgradRoute::Gemm3, (int)nb};
+  }
+  if (wgradn_ok(f.a16, din, f.a_ld, dout) && m >= 4096) return {WgradRoute::Wgradn, kNumCU};
+  return {narrow_wgrad_ok(f.a16, din, f.a_ld, f.b16, dout, f.b_ld) ? WgradRoute::Narrow : WgradRoute::Persist, persist_blocks(m)};
+}
+static bool fuses_dact(WgradRoute r) { return r == WgradRoute::Wgradx || r == WgradRoute::Gemmh || r == WgradRoute::Gemm3; }
 
 extern "C" int kgcn_dense_mfma_products(int32_t kind, int64_t m, int32_t din, int32_t dout) {
   if (m <= 0 || din <= 0 || dout <= 0) return 0;
-  const float* aligned = reinterpret_cast<const float*>(uintptr_t(256));      // stands for a 16-byte aligned operand
-  const long ld = (din + 3) & ~3;
+  const RowFacts f = aligned_rows(din, dout);
   if (kind == 0 || kind == 1) {
-    if (kind == 0 && (skinny_n_ok(din, dout, 0) || skinny_k_ok(din, dout))) return 0;
-    if (wide_layer(din, dout)) return (m >= 1024 && din % 4 == 0 && gemmh_fwd_ok(aligned, (long)m, din, ld, dout)) ? 3 : 6;
-    if (gemmn_pays(aligned, din, ld, dout) && m >= 1024) return 6;
-    return 1;
+    switch (fwd_route((long)m, din, dout, kind, f, true)) {
+      // kind 1 has never looked at the read-out kernels: a dX over a contraction of <= 16 columns is reported as an f32-MFMA
+      // call although skinny_k_fwd_kernel runs it.  Kept: what this function answers is recorded behaviour of the ABI
+      case FwdRoute::SkinnyN: case FwdRoute::SkinnyK: return kind == 0 ? 0 : 1;
+      case FwdRoute::Gemmh: return 3;
+      case FwdRoute::Gemm3Table: case FwdRoute::Gemm3: case FwdRoute::Gemmn: return 6;
+      case FwdRoute::Narrow: case FwdRoute::Persist: case FwdRoute::Tiled: return 1;
+    }
   }
-  if (skinny_n_ok(din, dout, 0)) return 0;
-  if (wgradx_ok(din, dout, ld, dout) && m >= 4096) return 6;
-  if (din > 64 && dout > 128) return gemmh_wgrad_ok(din, dout, (long)m) ? 3 : 6;
-  if (wgradn_ok(aligned, din, ld, dout) && m >= 4096) return 6;
+  switch (wgrad_route((long)m, din, dout, false, f).route) {
+    case WgradRoute::Skinny: return 0;
+    case WgradRoute::Gemmh: return 3;
+    case WgradRoute::Wgradx: case WgradRoute::Gemm3: case WgradRoute::Wgradn: return 6;
+    case WgradRoute::Narrow: case WgradRoute::Persist: return 1;
+  }
   return 1;
 }
 
 extern "C" int64_t kgcn_dense_wgrad_workspace_bytes(int64_t m, int32_t din, int32_t dout) {
   if (m <= 0 || din <= 0 || dout <= 0) return 0;
-  long rpc;
-  int nchunks;
-  wgrad_plan(m, &rpc, &nchunks);
-  if (nchunks < kNumCU) nchunks = kNumCU;   // the persistent kernel writes one partial per workgroup
-  if (skinny_n_ok(din, dout, 0) && nchunks < 4 * kNumCU) nchunks = 4 * kNumCU;     // skinny.hip: up to 1,024 partials
+  // Room for ~4 row chunks of whole 32-row steps per CU (the plan of a kernel this file no longer has), at least the one partial
+  // per CU of the persistent kernels and the up to 1,024 partials of skinny.hip.  No route needs more; most need less
+  // (WgradPlan::nparts), but the sizes this query answers are part of the ABI's behaviour and stay.
+  const long target = (long)kNumCU * 4;
+  long rpc = (((m + target - 1) / target + 31) / 32) * 32;
+  if (rpc < 32) rpc = 32;
+  int nchunks = (int)((m + rpc - 1) / rpc);
+  if (nchunks < kNumCU) nchunks = kNumCU;
+  if (wgrad_route((long)m, din, dout, false, aligned_rows(din, dout)).route == WgradRoute::Skinny && nchunks < 4 * kNumCU)
+    nchunks = 4 * kNumCU;
   return (int64_t)nchunks * ((int64_t)din * dout + dout) * 4;
 }
 
-static int dense_wgrad_impl(const float* x, int64_t x_ld, const float* dy, int64_t dy_ld, int64_t m, int32_t din,
-                            int32_t dout, float* dw, float* dbias, void* workspace, int64_t workspace_bytes, void* stream,
-                            const float* yact, int act);
-
-extern "C" int kgcn_dense_wgrad_f32(const float* x, int64_t x_ld, const float* dy, int64_t dy_ld,
-                                    int64_t m, int32_t din, int32_t dout, float* dw, float* dbias,
-                                    void* workspace, int64_t workspace_bytes, void* stream) {
-  return dense_wgrad_impl(x, x_ld, dy, dy_ld, m, din, dout, dw, dbias, workspace, workspace_bytes, stream, nullptr,
-                          KGCN_ACT_NONE);
+static int launch_wgrad_persist(const float* x, long x_ld, const float* dy, long dy_ld, long m, int din, int dout,
+                                float* part_dw, float* part_db, int nblocks, hipStream_t s) {
+  // the waves' parked accumulators and column sums; their 2 x [32][64] staging tiles fit inside
+  const size_t lds = (size_t)P_WAVES * (64 * 64 + 64) * 4;
+  static thread_local bool attr_set = false;
+  if (!attr_set) {
+    allow_full_lds(dense_wgrad_persist_kernel<true>);
+    allow_full_lds(dense_wgrad_persist_kernel<false>);
+    attr_set = true;
+  }
+  const bool vec = (din % 4 == 0) && (dout % 4 == 0) && (x_ld % 4 == 0) && (dy_ld % 4 == 0) && aligned16(x) && aligned16(dy);
+  dim3 grid((unsigned)nblocks, (unsigned)((din + 63) / 64), (unsigned)((dout + 63) / 64));
+  hipLaunchKernelGGL(vec ? dense_wgrad_persist_kernel<true> : dense_wgrad_persist_kernel<false>, grid, dim3(64 * P_WAVES), lds, s,
+                     x, x_ld, dy, dy_ld, m, din, dout, part_dw, part_db);
+  return check_launch("dense_wgrad_persist_kernel");
 }
 
-// 1 when kgcn_dense_wgrad_dact_f32 forms d pre-activation inside the weight-gradient GEMM for this shape (else the caller
-// runs kgcn_act_bwd_f32 first)
-extern "C" int kgcn_dense_wgrad_dact_supported(int32_t din, int32_t dout) { return din > 64 && dout > 128 ? 1 : 0; }
-
-extern "C" int kgcn_dense_wgrad_dact_f32(const float* x, int64_t x_ld, const float* dy, const float* act_out, int64_t dy_ld,
-                                         int32_t act, int64_t m, int32_t din, int32_t dout, float* dw, float* dbias,
-                                         void* workspace, int64_t workspace_bytes, void* stream) {
-  if (act <= KGCN_ACT_NONE || act > KGCN_ACT_TANH) return fail("kgcn_dense_wgrad_dact_f32: activation code %d", act);
-  if (!kgcn_dense_wgrad_dact_supported(din, dout))
-    return fail("kgcn_dense_wgrad_dact_f32: shape %d x %d is not a wide layer (run kgcn_act_bwd_f32 + kgcn_dense_wgrad_f32)",
-                din, dout);
-  if (m > 0 && !act_out) return fail("kgcn_dense_wgrad_dact_f32: act_out is NULL");
-  return dense_wgrad_impl(x, x_ld, dy, dy_ld, m, din, dout, dw, dbias, workspace, workspace_bytes, stream, act_out, act);
-}
-
+// yact != nullptr: dy is the gradient of the ACTIVATED output yact (same layout); d pre-activation is formed inside the kernel
 static int dense_wgrad_impl(const float* x, int64_t x_ld, const float* dy, int64_t dy_ld, int64_t m, int32_t din,
                             int32_t dout, float* dw, float* dbias, void* workspace, int64_t workspace_bytes, void* stream,
                             const float* yact, int act) {
@@ -1029,110 +955,45 @@ static int dense_wgrad_impl(const float* x, int64_t x_ld, const float* dy, int64
   if (!x || !dy) return fail("kgcn_dense_wgrad_f32: NULL operand");
   const int64_t need = kgcn_dense_wgrad_workspace_bytes(m, din, dout);
   if (!workspace || workspace_bytes < need)
-    return fail("kgcn_dense_wgrad_f32: workspace %lld < %lld bytes", (long long)workspace_bytes,
-                (long long)need);
-  long rpc;
-  int nchunks;
-  if (!yact && skinny_n_ok(din, dout, 0)) {
-    // read-out layers: lanes own k, the 2..16 gradient columns of a row are wave-uniform (skinny.hip)
-    nchunks = skinny_wgrad_parts(m);
-    float* part_dw = static_cast<float*>(workspace);
-    float* part_db = part_dw + (long)nchunks * din * dout;
-    if (int rc = launch_skinny_n_wgrad(x, (long)m, din, (long)x_ld, dy, (long)dy_ld, dout, part_dw, part_db, nchunks, s))
-      return rc;
-    return launch_reduce_pair(part_dw, (long)din * dout, dw, part_db, dout, dbias, nchunks, s);
-  }
-  if (wgradx_ok(din, dout, (long)x_ld, (long)dy_ld) && m >= 4096) {
-    // narrow input, wide output (81 -> 256): operands straight from memory into the f32 MFMA (wgradx.hip); one workgroup per
-    // CU (four per CU: 101 instead of 94 us and a four times larger second stage)
-    nchunks = kNumCU;
-    float* part_dw = static_cast<float*>(workspace);
-    float* part_db = part_dw + (long)nchunks * din * dout;
-    if (int rc = launch_wgradx(x, (long)x_ld, dy, (long)dy_ld, (long)m, din, dout, part_dw, part_db, nchunks, s, yact, act))
-      return rc;
-    return launch_reduce_pair(part_dw, (long)din * dout, dw, part_db, dout, dbias, nchunks, s);
-  }
-  if (din > 64 && dout > 128) {
-    // wide layers: bf16-split GEMM (gemm3.hip); one partial per row-range workgroup, <= kNumCU of them
-    const int tiles = ((din + 127) / 128) * ((dout + 255) / 256);
-    long nb = kNumCU / tiles;
-    if (nb < 1) nb = 1;
-    // at least 64 rows per row range: a range's partial is a whole [din x dout] block (256 KB at 256 x 256) -- with one 32-row
-    // chunk per workgroup sparse.py's 4,457 rows wrote 128 partials = 32 MB per layer and the step's reduction launch read 119 MB
-    // (profiles/r05_h_cfg3_rocprof.txt).  A/B on one box, cfg3 whole step: 32 rows 0.308 ms, 64 rows 0.301, 128 rows 0.318 (too few
-    // workgroups), 256 rows 0.364
-#ifndef KGCN_WGRAD_MIN_ROWS
-#define KGCN_WGRAD_MIN_ROWS 64
-#endif
-    const long chunks = (m + KGCN_WGRAD_MIN_ROWS - 1) / KGCN_WGRAD_MIN_ROWS;
-    if (nb > chunks) nb = chunks;
-    float* part_dw = static_cast<float*>(workspace);
-    float* part_db = part_dw + nb * din * dout;
-    static const char* hknob = dev_knob("KGCN_GEMMH");         // development: see gemm3.hip ("w" = the f16 weight gradient)
-    if (!(hknob && !strchr(hknob, 'w')) && gemmh_wgrad_ok(din, dout, (long)m)) {
-      if (int rc = launch_gemmh_wgrad(x, (long)x_ld, dy, (long)dy_ld, (long)m, din, dout, part_dw, part_db, (int)nb, s, yact, act))
-        return rc;
-      return launch_reduce_pair(part_dw, (long)din * dout, dw, part_db, dout, dbias, (int)nb, s);
-    }
-    if (int rc = launch_gemm3_wgrad(x, (long)x_ld, dy, (long)dy_ld, (long)m, din, dout, part_dw, part_db, (int)nb, s, yact,
-                                    act))
-      return rc;
-    return launch_reduce_pair(part_dw, (long)din * dout, dw, part_db, dout, dbias, (int)nb, s);
-  }
-  if (wgradn_ok(x, din, (long)x_ld, dout) && m >= 4096) {
-    // wide input, narrow output (256 x 50): the whole dW block per wave on the bf16 pipe (wgradn.hip)
-    nchunks = kNumCU;
-    float* part_dw = static_cast<float*>(workspace);
-    float* part_db = part_dw + (long)nchunks * din * dout;
-    if (int rc = launch_wgradn(x, (long)x_ld, dy, (long)dy_ld, (long)m, din, dout, part_dw, part_db, nchunks, s)) return rc;
-    return launch_reduce_pair(part_dw, (long)din * dout, dw, part_db, dout, dbias, nchunks, s);
-  }
-  if (narrow_wgrad_ok(x, din, (long)x_ld, dy, dout, (long)dy_ld)) {
-    // 50-wide layers: flat tile movement (narrow.hip), one partial per workgroup
-    nchunks = persist_blocks(m);
-    float* part_dw = static_cast<float*>(workspace);
-    float* part_db = part_dw + (long)nchunks * din * dout;
-    if (int rc = launch_narrow_wgrad(x, dy, (long)m, din, dout, part_dw, part_db, nchunks, s)) return rc;
-    return launch_reduce_pair(part_dw, (long)din * dout, dw, part_db, dout, dbias, nchunks, s);
-  }
-  {
-    // persistent kernel: one workgroup (8 waves) per CU and per 64x64 output block
-    nchunks = persist_blocks(m);
-    const size_t lds = (size_t)P_WAVES * (2 * 32 * 64) * 4;      // >= P_WAVES * (64*64+64)*4 ? no: park needs more
-    const size_t lds_park = (size_t)P_WAVES * (64 * 64 + 64) * 4;
-    const size_t lds_use = lds > lds_park ? lds : lds_park;
-    static thread_local bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dense_wgrad_persist_kernel<true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dense_wgrad_persist_kernel<false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-      attr_set = true;
-    }
-    float* part_dw = static_cast<float*>(workspace);
-    float* part_db = part_dw + (long)nchunks * din * dout;
-    const bool vec = (din % 4 == 0) && (dout % 4 == 0) && (x_ld % 4 == 0) && (dy_ld % 4 == 0) &&
-                     aligned16(x) && aligned16(dy);
-    dim3 grid((unsigned)nchunks, (unsigned)((din + 63) / 64), (unsigned)((dout + 63) / 64));
-    if (vec)
-      hipLaunchKernelGGL(dense_wgrad_persist_kernel<true>, grid, dim3(64 * P_WAVES), lds_use, s, x, (long)x_ld, dy,
-                         (long)dy_ld, (long)m, din, dout, part_dw, part_db);
-    else
-      hipLaunchKernelGGL(dense_wgrad_persist_kernel<false>, grid, dim3(64 * P_WAVES), lds_use, s, x, (long)x_ld, dy,
-                         (long)dy_ld, (long)m, din, dout, part_dw, part_db);
-    if (int rc = check_launch("dense_wgrad_persist_kernel")) return rc;
-    return launch_reduce_pair(part_dw, (long)din * dout, dw, part_db, dout, dbias, nchunks, s);
-  }
-  wgrad_plan(m, &rpc, &nchunks);
+    return fail("kgcn_dense_wgrad_f32: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
+  const long M = (long)m, xl = (long)x_ld, gl = (long)dy_ld;
+  const WgradPlan plan = wgrad_route(M, din, dout, yact != nullptr, RowFacts{aligned16(x), xl, aligned16(dy), gl});
+  const int np = plan.nparts;
   float* part_dw = static_cast<float*>(workspace);
-  float* part_db = part_dw + (long)nchunks * din * dout;
-  dim3 grid((unsigned)nchunks, (unsigned)((din + 63) / 64), (unsigned)((dout + 63) / 64));
-  hipLaunchKernelGGL(dense_wgrad_kernel, grid, dim3(256), 0, s, x, (long)x_ld, dy, (long)dy_ld,
-                     (long)m, din, dout, rpc, part_dw, part_db);
-  if (int rc = check_launch("dense_wgrad_kernel")) return rc;
-  if (dw)
-    if (int rc = reduce_or_defer(part_dw, nchunks, (long)din * dout, dw, s)) return rc;
-  if (dbias)
-    if (int rc = reduce_or_defer(part_db, nchunks, dout, dbias, s)) return rc;
-  return 0;
+  float* part_db = part_dw + (long)np * din * dout;
+  int rc = 0;
+  switch (plan.route) {
+    case WgradRoute::Skinny: rc = launch_skinny_n_wgrad(x, M, din, xl, dy, gl, dout, part_dw, part_db, np, s); break;
+    case WgradRoute::Wgradx: rc = launch_wgradx(x, xl, dy, gl, M, din, dout, part_dw, part_db, np, s, yact, act); break;
+    case WgradRoute::Gemmh: rc = launch_gemmh_wgrad(x, xl, dy, gl, M, din, dout, part_dw, part_db, np, s, yact, act); break;
+    case WgradRoute::Gemm3: rc = launch_gemm3_wgrad(x, xl, dy, gl, M, din, dout, part_dw, part_db, np, s, yact, act); break;
+    case WgradRoute::Wgradn: rc = launch_wgradn(x, xl, dy, gl, M, din, dout, part_dw, part_db, np, s); break;
+    case WgradRoute::Narrow: rc = launch_narrow_wgrad(x, dy, M, din, dout, part_dw, part_db, np, s); break;
+    case WgradRoute::Persist: rc = launch_wgrad_persist(x, xl, dy, gl, M, din, dout, part_dw, part_db, np, s); break;
+  }
+  return rc ? rc : launch_reduce_pair(part_dw, (long)din * dout, dw, part_db, dout, dbias, np, s);
+}
+
+extern "C" int kgcn_dense_wgrad_f32(const float* x, int64_t x_ld, const float* dy, int64_t dy_ld,
+                                    int64_t m, int32_t din, int32_t dout, float* dw, float* dbias,
+                                    void* workspace, int64_t workspace_bytes, void* stream) {
+  return dense_wgrad_impl(x, x_ld, dy, dy_ld, m, din, dout, dw, dbias, workspace, workspace_bytes, stream, nullptr,
+                          KGCN_ACT_NONE);
+}
+
+// 1 when kgcn_dense_wgrad_dact_f32 forms d pre-activation inside the weight-gradient GEMM for this shape (else the caller
+// runs kgcn_act_bwd_f32 first): the routes that take it do so whatever the row count
+extern "C" int kgcn_dense_wgrad_dact_supported(int32_t din, int32_t dout) {
+  return fuses_dact(wgrad_route(kManyRows, din, dout, true, aligned_rows(din, dout)).route) ? 1 : 0;
+}
+
+extern "C" int kgcn_dense_wgrad_dact_f32(const float* x, int64_t x_ld, const float* dy, const float* act_out, int64_t dy_ld,
+                                         int32_t act, int64_t m, int32_t din, int32_t dout, float* dw, float* dbias,
+                                         void* workspace, int64_t workspace_bytes, void* stream) {
+  if (act <= KGCN_ACT_NONE || act > KGCN_ACT_TANH) return fail("kgcn_dense_wgrad_dact_f32: activation code %d", act);
+  if (!kgcn_dense_wgrad_dact_supported(din, dout))
+    return fail("kgcn_dense_wgrad_dact_f32: shape %d x %d is not a wide layer (run kgcn_act_bwd_f32 + kgcn_dense_wgrad_f32)",
+                din, dout);
+  if (m > 0 && !act_out) return fail("kgcn_dense_wgrad_dact_f32: act_out is NULL");
+  return dense_wgrad_impl(x, x_ld, dy, dy_ld, m, din, dout, dw, dbias, workspace, workspace_bytes, stream, act_out, act);
 }

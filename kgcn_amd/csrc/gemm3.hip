@@ -23,21 +23,16 @@
 // hipBLASLt fp32: 1.07-1.13 ms); compiled-out experiments: MFMAs + y stores alone 0.68 ms, staging alone
 // 0.54 ms -- the workgroup-wide lockstep (barrier per chunk, y stores of all waves at once) keeps the
 // two from overlapping fully; that is where the remaining time is.
-#include <cstdlib>
-#include <cstring>
-
-#include "kgcn_common.h"
+// Settled and no longer switchable (the history stays findable without the code):
+//   * KGCN_GEMM3_MW=2, the table variant with 8-wave workgroups (<*, true, 2>): 0.244 against 0.207 ms for 4 waves, two
+//     workgroups per CU, 204,800 x 256 x 256 (profiles/r02_gemm_experiments.txt).
+//   * KGCN_GEMM3_CUT=0, whole 256-column blocks only: 23.8 against 20.3 us per 256 x 256 layer at 4,457 rows
+//     (profiles/r03_i_gemm_cut.txt).
+//   * KGCN_GEMMH, the f16 two-piece kernels of gemmh.hip per direction: 62-67 us there against 81-110 us here for a
+//     256 x 256 layer of cfg4 (profiles/r04_gemmh_history.txt, profiles/r03_n_cfg4_rocprof.txt).
+#include "dense_kernels.h"
 
 namespace kgcn {
-
-// the f16 two-piece kernels (gemmh.hip) take the shapes they were built for; their W' lives behind the bf16 section of the table
-bool gemmh_fwd_ok(const float* x, long m, int din, long x_ld, int dout);
-int launch_gemmh_fwd(const float* x, long m, int din, long x_ld, const void* tabh, const float* bias, float* y, int dout,
-                     long y_ld, int act, hipStream_t s);
-int launch_gemmh_dx_dact(const float* grad, const float* act_out, float* dpre, long m, int k, long ld, const void* tabh,
-                         float* dx, int n, long dx_ld, int dact, hipStream_t s, const float* pooled_grad, int n_nodes, long pooled_ld,
-                         float* dot_part);
-int64_t wtable_bf16_bytes(int din, int dout);
 
 #ifdef KGCN_PROBE   // development: per-workgroup cycle sums per phase (tools/gemm3_probe.py)
 __device__ long long* g3_probe = nullptr;
@@ -474,7 +469,7 @@ __global__ __launch_bounds__(256 * MW, 2) void gemm3_fwd_kernel(
 // Table variant, 4-wave workgroups: how a launch is cut into workgroup jobs.  Fewer 64-row tiles than a quarter of the
 // workgroups the chip runs at once (two per CU): 64-column blocks (sparse.py's 4,457 node rows: 70 tiles -> 280 workgroups;
 // 20.3 against 23.8 us per 256 x 256 layer, its training step 0.335 against 0.362 ms).  Measured and NOT kept
-// (tools/gemm_cut_bench.py, profiles/r03_i_gemm_cut.txt): 128-column blocks up to half of the slots (equal or slower), and
+// (profiles/r03_i_gemm_cut.txt): 128-column blocks up to half of the slots (equal or slower), and
 // a second, narrow-block launch over the rows of a last, partial round (200,000 rows = 6 rounds + 53 tiles: 190.7 against
 // 186.6 us -- the lone workgroups of the seventh round run faster than the launch gap + a latency-bound launch cost).
 template <int DK, int MT, int NT>
@@ -493,60 +488,41 @@ template <int DK>
 static void g3_table_launch(const float* x, long m, int din, long x_ld, const float* tw, long w_ld, int trans_w, const float* bias,
                             float* y, int dout, long y_ld, int act, const G3Dact& da, hipStream_t s) {
   const long jobs = ((m + 63) / 64) * ((dout + G3_BN - 1) / G3_BN), slots = 2L * kNumCU;
-  static const char* knob = dev_knob("KGCN_GEMM3_CUT");       // development: "0" = whole column blocks only
   // the backward form carries more staging per row (two or three operands, the d pre-activation store): it pays up to 96 tiles
   const long limit = DK == 0 ? slots : slots * 3 / 4;
-  if (!(knob && knob[0] == '0') && jobs * 4 <= limit)
+  if (jobs * 4 <= limit)
     return g3_table_launch_shape<DK, 1, 1>(x, m, din, x_ld, tw, w_ld, trans_w, bias, y, dout, y_ld, act, da, s);
   g3_table_launch_shape<DK, 2, 2>(x, m, din, x_ld, tw, w_ld, trans_w, bias, y, dout, y_ld, act, da, s);
 }
 
-// table == nullptr: W is split inside the kernel; else `table` is the fragment table of wtable.hip for (w, trans_w)
+// table == nullptr: W is split inside the kernel; else `table` is the fragment table of wtable.hip for (w, trans_w) and the
+// 4-wave workgroups read it (the shapes of the f16 kernel are routed to gemmh.hip by the caller)
 int launch_gemm3_fwd(const float* x, long m, int din, long x_ld, const float* w, long w_ld, int trans_w,
                      const float* bias, float* y, int dout, long y_ld, int act, const void* table, hipStream_t s) {
+  const bool xvec = (din % 4 == 0) && (x_ld % 4 == 0) && aligned16(x);
+  if (table) {
+    const float* tw = static_cast<const float*>(table);
+    if (xvec) {
+      g3_table_launch<0>(x, m, din, x_ld, tw, w_ld, trans_w, bias, y, dout, y_ld, act, G3Dact{}, s);
+    } else {
+      const size_t lds = 2 * (size_t)G3_XP * 16;
+      const long nt64 = (m + 63) / 64;
+      const long cap = 2L * kNumCU;
+      const dim3 grid((unsigned)(nt64 < cap ? nt64 : cap), (unsigned)((dout + G3_BN - 1) / G3_BN));
+      hipLaunchKernelGGL((gemm3_fwd_kernel<false, true, 1>), grid, dim3(256), lds, s, x, m, din, x_ld, tw, w_ld, trans_w,
+                         bias, y, dout, y_ld, act, G3Dact{});
+    }
+    return check_launch("gemm3_fwd_kernel");
+  }
   static thread_local bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm3_fwd_kernel<true, false, 2>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm3_fwd_kernel<false, false, 2>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm3_fwd_kernel<true, true, 2>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm3_fwd_kernel<false, true, 2>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
     attr_set = true;
   }
   const long ntiles = (m + G3_BM - 1) / G3_BM;
-  const bool xvec = (din % 4 == 0) && (x_ld % 4 == 0) && aligned16(x);
-  static const char* hknob = dev_knob("KGCN_GEMMH");           // development: the f16 kernels to use, e.g. "fw" (f forward / dX, d dX with act', w weight gradient); "0" = none
-  if (table && !(hknob && !strchr(hknob, 'f')) && gemmh_fwd_ok(x, m, din, x_ld, dout))
-    return launch_gemmh_fwd(x, m, din, x_ld, static_cast<const char*>(table) + wtable_bf16_bytes(din, dout), bias, y, dout, y_ld,
-                            act, s);
-  if (table) {
-    const size_t lds = 2 * (size_t)G3_XP * 16;
-    const float* tw = static_cast<const float*>(table);
-    static const char* mw = dev_knob("KGCN_GEMM3_MW");         // development: "2" = the 8-wave workgroup
-    if (!(mw && mw[0] == '2')) {
-      if (xvec) {
-        g3_table_launch<0>(x, m, din, x_ld, tw, w_ld, trans_w, bias, y, dout, y_ld, act, G3Dact{}, s);
-      } else {
-        const long nt64 = (m + 63) / 64;
-        const long cap = 2L * kNumCU;
-        const dim3 grid((unsigned)(nt64 < cap ? nt64 : cap), (unsigned)((dout + G3_BN - 1) / G3_BN));
-        hipLaunchKernelGGL((gemm3_fwd_kernel<false, true, 1>), grid, dim3(256), lds, s, x, m, din, x_ld, tw, w_ld, trans_w,
-                           bias, y, dout, y_ld, act, G3Dact{});
-      }
-      return check_launch("gemm3_fwd_kernel");
-    }
-    const dim3 grid((unsigned)(ntiles < kNumCU ? ntiles : kNumCU), (unsigned)((dout + G3_BN - 1) / G3_BN));
-    if (xvec)
-      hipLaunchKernelGGL((gemm3_fwd_kernel<true, true, 2>), grid, dim3(512), lds, s, x, m, din, x_ld, tw, w_ld, trans_w, bias,
-                         y, dout, y_ld, act, G3Dact{});
-    else
-      hipLaunchKernelGGL((gemm3_fwd_kernel<false, true, 2>), grid, dim3(512), lds, s, x, m, din, x_ld, tw, w_ld, trans_w,
-                         bias, y, dout, y_ld, act, G3Dact{});
-    return check_launch("gemm3_fwd_kernel");
-  }
   const dim3 grid((unsigned)(ntiles < kNumCU ? ntiles : kNumCU), (unsigned)((dout + G3_BN - 1) / G3_BN));
   if (xvec)
     hipLaunchKernelGGL((gemm3_fwd_kernel<true, false, 2>), grid, dim3(512), G3_LDS, s, x, m, din, x_ld, w, w_ld, trans_w,
@@ -567,12 +543,10 @@ int launch_gemm3_dx_dact(const float* grad, const float* act_out, float* dpre, l
                   dact != KGCN_ACT_NONE && dpre != grad && (grad || pooled_grad) &&
                   (!pooled_grad || (aligned16(pooled_grad) && n_nodes > 0 && pooled_ld % 4 == 0 && pooled_ld >= k));
   if (!ok) return -1;
-  static const char* hknob = dev_knob("KGCN_GEMMH");
-  if (!(hknob && !strchr(hknob, 'd'))) {
-    const int rc = launch_gemmh_dx_dact(grad, act_out, dpre, m, k, ld, static_cast<const char*>(table) + wtable_bf16_bytes(k, n), dx,
-                                        n, dx_ld, dact, s, pooled_grad, n_nodes, pooled_ld, nullptr);
-    if (rc >= 0) return rc;
-  }
+  // the f16 kernel where the operands fit it (its W' lives behind the bf16 section of the table), else the bf16 one below
+  const int rc = launch_gemmh_dx_dact(grad, act_out, dpre, m, k, ld, static_cast<const char*>(table) + wtable_bf16_bytes(k, n), dx, n,
+                                      dx_ld, dact, s, pooled_grad, n_nodes, pooled_ld, nullptr);
+  if (rc >= 0) return rc;
   G3Dact da;
   const float* base = grad ? grad : act_out;             // the staging threads address everything relative to their x row
   da.ydiff = act_out - base;

@@ -42,6 +42,7 @@
 //   quarters (the 8-byte row writes of 16 lanes cover 32 distinct banks), 16-byte chunks are rotated by the row quad (the
 //   16-lane groups of ds_read_b128 see 16 distinct bank quads).  Everything that depends on the k-step / column tile is an
 //   IMMEDIATE offset on one of two lane bases.
+#include "dense_kernels.h"
 #include "gemmh.h"
 
 namespace kgcn {

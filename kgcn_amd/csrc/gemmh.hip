@@ -41,6 +41,9 @@
 //   wave rescales its accumulators (exact) and goes on -- the online form of the row scale above.  One partial dW per
 //   workgroup (written unscaled), fixed-order second stage as everywhere.  Shipped for the fused act' form; the plain weight
 //   gradient takes gemmh_wgradl_kernel below (every value split once, shared through LDS).
+//   Settled and no longer switchable: KGCN_WGRADL=0 (the register-split kernel for the plain gradient too), 88-94 against
+//   75-84 us (profiles/r04_gemmh_history.txt).
+#include "dense_kernels.h"
 #include "gemmh.h"
 
 namespace kgcn {
@@ -410,10 +413,10 @@ int gemmh_dot_parts(long m, int dout) {
 }
 
 // x: 16-byte aligned rows of <= 256 columns (din % 4 == 0, x_ld % 4 == 0); the table holds the f16 section for (din, dout)
-bool gemmh_fwd_ok(const float* x, long m, int din, long x_ld, int dout) {
+bool gemmh_fwd_ok(bool x16, long m, int din, long x_ld, int dout) {
   // one 64-row tile per workgroup and fewer workgroups than CUs is the regime of gemm3's 64 x 64 column cut (sparse.py's 4,457
   // rows: 0.320 ms per step with it, 0.332 ms through this kernel)
-  return din % 4 == 0 && din <= GH_KMAX && din >= 32 && x_ld % 4 == 0 && aligned16(x) && dout > 128 && m >= (long)kNumCU * GH_BM;
+  return din % 4 == 0 && din <= GH_KMAX && din >= 32 && x_ld % 4 == 0 && x16 && dout > 128 && m >= (long)kNumCU * GH_BM;
 }
 
 template <int DK>
@@ -452,7 +455,7 @@ int launch_gemmh_dx_dact(const float* grad, const float* act_out, float* dpre, l
   // dot_part != nullptr: `dx` is READ ([m, n], row stride dx_ld) and <product, dx> goes to dot_part[workgroups of the launch]
   // (gemmh_dot_parts(m, n) floats) instead of the product being stored
   const float* base = grad ? grad : act_out;
-  if (!(gemmh_fwd_ok(base, m, k, ld, n) && (!grad || aligned16(grad)) && aligned16(act_out) && aligned16(dpre) && tabh &&
+  if (!(gemmh_fwd_ok(aligned16(base), m, k, ld, n) && (!grad || aligned16(grad)) && aligned16(act_out) && aligned16(dpre) && tabh &&
         dact != KGCN_ACT_NONE && dpre != grad && (grad || pooled_grad) &&
         (!pooled_grad || (aligned16(pooled_grad) && n_nodes > 0 && pooled_ld % 4 == 0))))
     return -1;
@@ -1022,8 +1025,7 @@ bool gemmh_wgrad_ok(int din, int dout, long m) { return din > 96 && dout > 128 &
 int launch_gemmh_wgrad(const float* x, long x_ld, const float* dy, long dy_ld, long m, int din, int dout, float* part_dw,
                        float* part_db, int nblocks, hipStream_t s, const float* yact, int act) {
   const dim3 grid((unsigned)nblocks, (unsigned)((din + 127) / 128), (unsigned)((dout + 255) / 256));
-  static const char* lknob = dev_knob("KGCN_WGRADL");          // development: "0" = the register-split kernel only
-  if (!(yact && act != KGCN_ACT_NONE) && !(lknob && lknob[0] == '0')) {
+  if (!(yact && act != KGCN_ACT_NONE)) {
     static thread_local bool attr_set = false;
     if (!attr_set) {
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemmh_wgradl_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1039,7 +1041,7 @@ int launch_gemmh_wgrad(const float* x, long x_ld, const float* dy, long dy_ld, l
   if (yact && act != KGCN_ACT_NONE)
     hipLaunchKernelGGL(gemmh_wgrad_kernel<true>, grid, dim3(512), 0, s, x, x_ld, dy, dy_ld, m, din, dout, spb, part_dw, part_db,
                        yact, c0, c1, c2, act == KGCN_ACT_RELU ? 1 : 0);
-  else
+  else  // not reached since the plain gradient always takes gemmh_wgradl_kernel; kept so that the code object is unchanged
     hipLaunchKernelGGL(gemmh_wgrad_kernel<false>, grid, dim3(512), 0, s, x, x_ld, dy, dy_ld, m, din, dout, spb, part_dw, part_db,
                        nullptr, 0.f, 0.f, 0.f, 0);
   return check_launch("gemmh_wgrad_kernel");

@@ -16,7 +16,7 @@
 //   * W comes pre-split from the fragment table of wtable.hip (L2 / L1 resident), one k-step ahead, straight into registers;
 //   * two waves per SIMD (<= 256 registers) hide each other's vector work; bias is the initial accumulator value, the
 //     activation is applied in registers, a lane owns one COLUMN of its tiles.
-#include "kgcn_common.h"
+#include "dense_kernels.h"
 
 namespace kgcn {
 
@@ -174,8 +174,8 @@ __global__ __launch_bounds__(256, 2) void gemmn_fwd_kernel(const float* __restri
   }
 }
 
-bool gemmn_pays(const float* x, int din, long x_ld, int dout) {
-  return dout <= 64 && din >= 128 && din % 4 == 0 && x_ld % 4 == 0 && aligned16(x);
+bool gemmn_pays(bool x16, int din, long x_ld, int dout) {
+  return dout <= 64 && din >= 128 && din % 4 == 0 && x_ld % 4 == 0 && x16;
 }
 
 // `table`: fragment table of wtable.hip for (w, trans_w)

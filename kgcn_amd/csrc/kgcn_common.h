@@ -28,9 +28,6 @@ inline int check_launch(const char* what) {
 
 // ---- second stage of the two-stage reductions (dense.hip): out[0:n] = sum over nparts rows of part [nparts, n] -------------
 int launch_reduce_partials(const float* part, int nparts, long n, float* out, hipStream_t s);
-// two arrays in one launch (dW [n], dbias [n2])
-int launch_reduce_partials2(const float* part, int nparts, long n, float* out, const float* part2, long n2, float* out2,
-                            hipStream_t s);
 // the second stage of a PARAMETER gradient: queued while deferral is on (kgcn_reduce_defer), launched otherwise
 int reduce_or_defer(const float* part, int nparts, long n, float* out, hipStream_t s);
 // dW and dbias of one layer (either output may be NULL): through reduce_or_defer inside a deferral scope, one launch otherwise
@@ -40,9 +37,9 @@ int launch_reduce_pair(const float* part_dw, long n_dw, float* dw, const float* 
 int launch_reduce_pair_now(const float* part_dw, long n_dw, float* dw, const float* part_db, long n_db, float* dbias,
                            int nparts, hipStream_t s);
 
-// Development routing knobs (KGCN_DENSE_ROUTE, KGCN_GEMM3_MW) exist only in a -DKGCN_DEV_KNOBS build (make DEV_KNOBS=1,
-// what tools/variant_bench.py / tools/gemm_route_bench.py use): the shipped library never reads the environment, so a
-// stray variable cannot change kernel routing (and with it summation order) behind the parity tests' back.
+// Development knobs (KGCN_S2_ABL of stack_tile.hip) exist only in a -DKGCN_DEV_KNOBS build (make DEV_KNOBS=1, what
+// tools/variant_bench.py uses): the shipped library never reads the environment, so a stray variable cannot change kernel
+// routing (and with it summation order) behind the parity tests' back.
 #ifdef KGCN_DEV_KNOBS
 inline const char* dev_knob(const char* name) { return getenv(name); }
 #else

@@ -12,7 +12,7 @@
 // the same way: accumulators -> LDS tile [32 x dout] -> flat dwordx4 stores.
 // The contraction itself stays on v_mfma_f32_32x32x2_f32 (exact fp32 products): <= 2 x 32 MFMAs of 64 cycles per 32-row
 // tile is below the tile's HBM time.
-#include "kgcn_common.h"
+#include "dense_kernels.h"
 
 namespace kgcn {
 
@@ -244,8 +244,8 @@ __global__ __launch_bounds__(512, 1) void narrow_wgrad_kernel(
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------
-bool narrow_fwd_ok(const float* x, int din, long x_ld, const float* y, int dout, long y_ld) {
-  return din <= 64 && dout <= 64 && x_ld == din && y_ld == dout && aligned16(x) && aligned16(y) && din % 4 != 0;
+bool narrow_fwd_ok(bool x16, int din, long x_ld, bool y16, int dout, long y_ld) {
+  return din <= 64 && dout <= 64 && x_ld == din && y_ld == dout && x16 && y16 && din % 4 != 0;
 }
 
 int launch_narrow_fwd(const float* x, long m, int din, const float* w, long w_ld, int trans_w, const float* bias,
@@ -271,8 +271,8 @@ int launch_narrow_fwd(const float* x, long m, int din, const float* w, long w_ld
   return check_launch("narrow_fwd_kernel");
 }
 
-bool narrow_wgrad_ok(const float* x, int din, long x_ld, const float* dy, int dout, long dy_ld) {
-  return din <= 64 && dout <= 64 && x_ld == din && dy_ld == dout && aligned16(x) && aligned16(dy) &&
+bool narrow_wgrad_ok(bool x16, int din, long x_ld, bool dy16, int dout, long dy_ld) {
+  return din <= 64 && dout <= 64 && x_ld == din && dy_ld == dout && x16 && dy16 &&
          (din % 4 != 0 || dout % 4 != 0);
 }
 

@@ -9,7 +9,7 @@
 //                    columns, their W entries live in registers, the k inputs of a row are wave-uniform
 //   skinny_n_wgrad   dW[k, n] = x^T g, db = colsum g, n <= 16: lanes own k (their dW rows in registers across the wave's
 //                    rows), one partial per workgroup, fixed-order second stage (reduce_partials)
-#include "kgcn_common.h"
+#include "dense_kernels.h"
 
 namespace kgcn {
 

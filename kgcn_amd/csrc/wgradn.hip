@@ -4,8 +4,8 @@
 //   dW[din, dout] = x^T @ dy,   dbias[dout] = colsum(dy)           (per-workgroup partials, reduced in fixed order)
 //
 // Shipped: wgradnb_kernel (below) -- the register-split form of wgradx.hip with the roles exchanged; 49 us per call incl. the
-// second stage at m = 117,888 (the kernel above it in the file: 58; cfg4 step 1.477 against 1.491 ms).
-// DEV_KNOBS builds keep the first kernel (KGCN_WGRADN=lds) for A/B:
+// second stage at m = 117,888 (the first kernel: 58; cfg4 step 1.477 against 1.491 ms, profiles/r03_l_cfg4_rocprof.txt).
+// The first kernel (wgradn_kernel, KGCN_WGRADN=lds in DEV_KNOBS builds until it was removed) and what it taught:
 // The f32-MFMA kernel of dense.hip cuts din into four 64-column blocks (each re-reading dy, x in 256-byte segments) and
 // spends 256 MFMAs of 64 cycles per 32 rows on a pipe it shares with the VALU: 146 us at m = 204,800 (HBM time 31 us).
 // There a wave owns a [128 x 64] half of dW in 128 accumulator registers, two waves per SIMD (the two column halves of the
@@ -20,170 +20,9 @@
 //   * dy is loaded lane = column, the 8 rows of the lane's parity: B fragments without any data movement; the column-half-0
 //     waves sum it for dbias;
 //   * the row-range groups of a workgroup are summed through LDS (two rounds), one [din x dout] partial per workgroup.
-#include "kgcn_common.h"
+#include "dense_kernels.h"
 
 namespace kgcn {
-
-#ifdef KGCN_DEV_KNOBS
-constexpr int WN_LDS_WAVE = 4 * 3 * 64 * 16;               // (m-tile, piece) x 64 lanes x 16 bytes = 12 KB
-constexpr int WN_WAVES = 8;                                 // 4 row-range groups x 2 column halves
-
-__global__ __launch_bounds__(512, 1) void wgradn_kernel(const float* __restrict__ x, long x_ld,
-                                                        const float* __restrict__ dy, long dy_ld, long m, int din,
-                                                        int dout, float* __restrict__ part_dw, float* __restrict__ part_db) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char wn_smem[];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int li = lane & 31, hi = lane >> 5;
-  const int grp = wave >> 1, ch = wave & 1;                  // row-range group, column half (x columns 128 ch ..)
-  unsigned char* xp = wn_smem + (size_t)wave * WN_LDS_WAVE;
-  const long nsteps = (m + 15) / 16;                         // k-steps of 16 rows
-  const long ngroups = (long)gridDim.x * 4;
-  const long gg = (long)blockIdx.x * 4 + grp;
-  const long per = (nsteps + ngroups - 1) / ngroups;         // contiguous range of k-steps per group
-  const long s_begin = gg * per;
-  long s_end = s_begin + per;
-  if (s_end > nsteps) s_end = nsteps;
-
-  // x staging: lane = (row parity hi, 16-byte column group li): columns 128 ch + 4 li .. + 3 (beyond din: clamped, masked)
-  const int c0x = 128 * ch + 4 * li;
-  const bool xok = c0x < din;
-  const int xcol = xok ? c0x : 0;
-  const int mt_w = li >> 3;
-  // entry of column e inside its m-tile block, XOR-rotated by the m-tile: 32 hi + 4 (li & 7) + (e ^ (mt & 3))
-  const int wr_base = mt_w * 3072 + (32 * hi + (li & 7) * 4) * 16;
-  // dy staging: column 32 nt + li (clamped / masked), rows of parity hi
-  const bool dok0 = li < dout, dok1 = 32 + li < dout;
-  const int dc0 = dok0 ? li : 0, dc1 = dok1 ? 32 + li : 0;
-
-  f32x16 acc[4][2];
-#pragma unroll
-  for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[mt][nt][r] = 0.f;
-  float cs0 = 0.f, cs1 = 0.f;
-
-  f32x4 rawx[8];                                             // rows 2 j + hi of the k-step
-  float rawd[2][8];                                          // dy[row 2 j + hi][column of tile nt]
-  auto load_step = [&](long s) __attribute__((always_inline)) {
-    const long row0 = s * 16 + hi;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const long r = row0 + 2 * j;
-      const long rc = r < m ? r : m - 1;
-      rawx[j] = *reinterpret_cast<const f32x4*>(x + rc * x_ld + xcol);
-      const float* dr = dy + rc * dy_ld;
-      rawd[0][j] = dr[dc0];
-      rawd[1][j] = dr[dc1];
-    }
-  };
-  // rawx -> pieces in LDS (fragment order); rawd -> B fragments
-  auto stage = [&](long s, Frag3 (&B)[2]) __attribute__((always_inline)) {
-    const long row0 = s * 16 + hi;
-    const bool full = row0 + 14 < m;                        // every row of this lane's parity exists (uniform per half wave)
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = (xok && (full || row0 + 2 * j < m)) ? rawx[j][e] : 0.f;
-      Frag3 f;
-      split8(v, f);
-      unsigned char* d = xp + wr_base + (e ^ (mt_w & 3)) * 16;
-      *reinterpret_cast<u32x4*>(d) = f.p1;
-      *reinterpret_cast<u32x4*>(d + 1024) = f.p2;
-      *reinterpret_cast<u32x4*>(d + 2048) = f.p3;
-    }
-    float v0[8], v1[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const bool rok = full || row0 + 2 * j < m;
-      v0[j] = (dok0 && rok) ? rawd[0][j] : 0.f;
-      v1[j] = (dok1 && rok) ? rawd[1][j] : 0.f;
-      cs0 += v0[j];
-      cs1 += v1[j];
-    }
-    split8(v0, B[0]);
-    split8(v1, B[1]);
-  };
-
-  if (s_begin < s_end) {
-    Frag3 B[2];
-    load_step(s_begin);
-    stage(s_begin, B);
-    if (s_begin + 1 < s_end) load_step(s_begin + 1);
-    for (long s = s_begin; s < s_end; ++s) {
-      // A fragments of this k-step -> registers (then the LDS buffer is free for the next one)
-      u32x4 A[4][3];
-#pragma unroll
-      for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-        for (int pc = 0; pc < 3; ++pc)
-          A[mt][pc] = *reinterpret_cast<const u32x4*>(xp + (mt * 3 + pc) * 1024 + (32 * hi + (li ^ (mt & 3))) * 16);
-      static_for<48>([&](auto sc) __attribute__((always_inline)) {
-        constexpr int q = decltype(sc)::value, mt = q / 12, r12 = q % 12, pr = r12 >> 1, nt = r12 & 1;
-        constexpr int PA[6] = {2, 1, 0, 1, 0, 0}, PB[6] = {0, 1, 2, 0, 1, 0};   // smallest terms first
-        const u32x4 bv = PB[pr] == 0 ? B[nt].p1 : PB[pr] == 1 ? B[nt].p2 : B[nt].p3;
-        acc[mt][nt] = mfma_bf16(A[mt][PA[pr]], bv, acc[mt][nt]);
-      });
-      // the next k-step: pieces -> LDS (its A reads above are through: in-order LDS) / B registers; the one after that is
-      // requested.  The other wave of the SIMD issues its MFMAs meanwhile.
-      if (s + 1 < s_end) {
-        stage(s + 1, B);
-        if (s + 2 < s_end) load_step(s + 2);
-      }
-    }
-  }
-
-  // ---- the four row-range groups summed through LDS: groups 2, 3 -> 0, 1; group 1 -> 0 -----------------------------------
-  cs0 += __shfl_xor(cs0, 32, 64);
-  cs1 += __shfl_xor(cs1, 32, 64);
-  float* red = reinterpret_cast<float*>(wn_smem);            // four slabs of [4][2][16][64] floats (32 KB each)
-  float* csr = red + 4 * 8192;                               // [4 groups][64] column sums (column-half-0 waves)
-  if (ch == 0 && hi == 0) { csr[grp * 64 + li] = cs0; csr[grp * 64 + 32 + li] = cs1; }
-  __syncthreads();                                           // every wave is through with its fragment region
-  auto put = [&](float* slab) __attribute__((always_inline)) {
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) slab[((mt * 2 + nt) * 16 + r) * 64 + lane] = acc[mt][nt][r];
-  };
-  auto add = [&](const float* slab) __attribute__((always_inline)) {
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[mt][nt][r] += slab[((mt * 2 + nt) * 16 + r) * 64 + lane];
-  };
-  if (grp >= 2) put(red + ((grp - 2) * 2 + ch) * 8192);
-  __syncthreads();
-  if (grp < 2) add(red + (grp * 2 + ch) * 8192);
-  __syncthreads();
-  if (grp == 1) put(red + ch * 8192);
-  __syncthreads();
-  if (grp == 0) {
-    add(red + ch * 8192);
-    float* pw = part_dw + (long)blockIdx.x * din * dout;
-#pragma unroll
-    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt) {
-        const int col = 32 * nt + li;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int row = 128 * ch + 32 * mt + (r & 3) + 8 * (r >> 2) + 4 * hi;
-          if (row < din && col < dout) pw[(long)row * dout + col] = acc[mt][nt][r];
-        }
-      }
-    if (part_db && ch == 0 && lane < dout)
-      part_db[(long)blockIdx.x * dout + lane] = (csr[lane] + csr[64 + lane]) + (csr[128 + lane] + csr[192 + lane]);
-  }
-}
-
-#endif  // KGCN_DEV_KNOBS
 
 // The register-split form (wgradx.hip: wgradxb_kernel) with the roles exchanged: wave w owns x block w (32 of the up to 256
 // input columns -- its own slice of the HBM stream, 8 coalesced row loads per 16 rows) and BOTH dy blocks (64 output columns,
@@ -301,40 +140,17 @@ __global__ __launch_bounds__(512, 2) void wgradnb_kernel(const float* __restrict
   }
 }
 
-bool wgradn_ok(const float* x, int din, long x_ld, int dout) {
-  return dout <= 64 && din >= 128 && din <= 256 && din % 4 == 0 && x_ld % 4 == 0 && aligned16(x);
+bool wgradn_ok(bool x16, int din, long x_ld, int dout) {
+  return dout <= 64 && din >= 128 && din <= 256 && din % 4 == 0 && x_ld % 4 == 0 && x16;
 }
 
 // nblocks partials ([nblocks][din*dout], [nblocks][dout]); nblocks <= kNumCU
 int launch_wgradn(const float* x, long x_ld, const float* dy, long dy_ld, long m, int din, int dout, float* part_dw,
                   float* part_db, int nblocks, hipStream_t s) {
-#ifdef KGCN_DEV_KNOBS
-  static const char* route = dev_knob("KGCN_WGRADN");            // development: "lds" = the kernel with the LDS transposition
-  const bool lds_route = route && route[0] == 'l';
-#else
-  const bool lds_route = false;
-#endif
-  if (!lds_route) {
-    const long nsteps = (m + 15) / 16, spb = (nsteps + nblocks - 1) / nblocks;
-    hipLaunchKernelGGL(wgradnb_kernel, dim3((unsigned)nblocks), dim3(512), 0, s, x, x_ld, dy, dy_ld, m, din, dout, spb, part_dw,
-                       part_db);
-    return check_launch("wgradnb_kernel");
-  }
-#ifdef KGCN_DEV_KNOBS
-  const size_t frag_b = WN_WAVES * (size_t)WN_LDS_WAVE, red_b = (size_t)(4 * 8192 + 256) * 4;
-  const size_t lds = frag_b > red_b ? frag_b : red_b;
-  static thread_local bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgradn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              kLdsBytes);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(wgradn_kernel, dim3((unsigned)nblocks), dim3(64 * WN_WAVES), lds, s, x, x_ld, dy, dy_ld, m, din, dout,
-                     part_dw, part_db);
-  return check_launch("wgradn_kernel");
-#else
-  return fail("wgradn: no route");
-#endif
+  const long nsteps = (m + 15) / 16, spb = (nsteps + nblocks - 1) / nblocks;
+  hipLaunchKernelGGL(wgradnb_kernel, dim3((unsigned)nblocks), dim3(512), 0, s, x, x_ld, dy, dy_ld, m, din, dout, spb, part_dw,
+                     part_db);
+  return check_launch("wgradnb_kernel");
 }
 
 }  // namespace kgcn

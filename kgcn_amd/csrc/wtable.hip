@@ -11,6 +11,7 @@
 // (Round 2 also tried two GEMMs that share nothing between waves on this table -- one wave per SIMD with a [128 x 64]
 // block in registers, and two waves per SIMD with [64 x 64] blocks, no LDS, no barrier.  Both lost to gemm3 + table because
 // every wave then re-splits its x rows: measurements and ablations in profiles/r02_gemm_experiments.txt.)
+#include "dense_kernels.h"
 #include "gemmh.h"
 
 namespace kgcn {

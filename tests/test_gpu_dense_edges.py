@@ -469,3 +469,35 @@ def test_f16_two_piece_rows_spanning_2_to_16_stay_within_fp32_arithmetic():
         factor = 2                                  # (measured, profiles/r05_accuracy.json: 0.67 / 0.68 / 0.58 of numpy's own error)
         conftest.record_accuracy("span 2^16 %s: err / sum|x||w| (tolerance = %d x numpy float32's)" % (name, factor), e_hip, factor * e_np, 1.0)
         assert e_hip <= factor * e_np, (name, e_hip, e_np)
+
+
+# One shape per route of csrc/dense.hip (fwd_route / wgrad_route), the smallest that selects it, through the C entry points
+# themselves (ops.dense would send the 16,384-row wide layer to the one-pass backward).  Columns: forward / weight-gradient
+# answer of kgcn_dense_mfma_products -- 0 read-out kernels, 1 f32 MFMA (narrow, persistent, tiled), 3 f16 x 2, 6 bf16 x 3.
+ROUTE_SHAPES = [("skinny", 300, 64, 2, 0, 0), ("wgradx", 4096, 81, 256, 6, 6), ("gemmh", 16384, 256, 256, 3, 3),
+                ("gemm3", 333, 100, 300, 6, 6), ("wgradn", 4096, 256, 50, 6, 6), ("narrow", 300, 50, 50, 1, 1),
+                ("persistent", 300, 64, 64, 1, 1), ("tiled forward", 300, 324, 64, 1, 1)]
+
+
+@pytest.mark.parametrize("route,M,din,dout,fwd_products,wgrad_products", ROUTE_SHAPES)
+def test_every_dense_route_at_its_smallest_shape(route, M, din, dout, fwd_products, wgrad_products):
+    from kgcn_amd import _lib
+    lib, ptr, stream = _lib.lib, _lib.ptr, _lib.current_stream
+    assert lib.kgcn_dense_mfma_products(0, M, din, dout) == fwd_products, route
+    assert lib.kgcn_dense_mfma_products(2, M, din, dout) == wgrad_products, route
+    x, g, w, b = _inputs("normal", M, din, dout, seed=M + din + dout)
+    tx, tg, tw, tb = t32(x), t32(g), t32(w), t32(b)
+    y = torch.empty((M, dout), device=dev(), dtype=torch.float32)
+    dw, db = torch.empty_like(tw), torch.empty_like(tb)
+    nb = lib.kgcn_dense_fwd_workspace_bytes(din, dout)
+    ws = _lib.workspace(nb, dev())
+    _lib.check(lib.kgcn_dense_fwd_ws_f32(ptr(tx), M, din, din, ptr(tw), dout, 0, ptr(tb), ptr(y), dout, dout, 0, ptr(ws), nb,
+                                         stream()), "kgcn_dense_fwd_ws_f32")
+    nb = lib.kgcn_dense_wgrad_workspace_bytes(M, din, dout)
+    ws2 = _lib.workspace(nb, dev())
+    _lib.check(lib.kgcn_dense_wgrad_f32(ptr(tx), din, ptr(tg), dout, M, din, dout, ptr(dw), ptr(db), ptr(ws2), nb, stream()),
+               "kgcn_dense_wgrad_f32")
+    x64, w64, g64 = x.astype(np.float64), w.astype(np.float64), g.astype(np.float64)
+    close(y, x64 @ w64 + b, atol=1e-6, rel=1e-6, what="%s route: dense fwd" % route)
+    close(dw, x64.T @ g64, atol=0, rel=3e-6, what="%s route: dense dW" % route)
+    close(db, g64.sum(0), atol=0, rel=3e-6, what="%s route: dense dbias" % route)

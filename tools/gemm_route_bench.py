@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""One line per shape: forward time of the wide dense layer through the workspace API (route by KGCN_DENSE_ROUTE)."""
+"""One line per shape: forward time of the wide dense layer through the workspace API (the table route)."""
 import json, os, sys
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
