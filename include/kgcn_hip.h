@@ -75,6 +75,8 @@ extern "C" {
  * (+ kgcn_linkpred_workspace_bytes).
  * Integrated gradients of the multimodal model added entry points only (version still 2): kgcn_seq_convpool_scaled_fwd_f32,
  * kgcn_seq_convpool_input_grad_f32.
+ * The protein-sequence CNN added entry points only (version still 2): kgcn_conv1d_pool_fwd_f32 / kgcn_conv1d_pool_bwd_f32
+ * (+ kgcn_conv1d_pool_workspace_bytes), kgcn_embedding_grad_f32.
  * The compact row-padded adjacency (row_pad == KGCN_ROW_PAD_COMPACT) added a layout CODE and entry points only (version
  * still 2): a library without it refuses that code in every entry point (validate_csr accepts row_pad 0 and 4 only), so
  * an old library never misreads it; kgcn_csr_compact4 is the feature query (look it up before building such a batch). */
@@ -878,6 +880,34 @@ int kgcn_linkpred_bwd_f32(const float* h, int64_t nodes, int32_t dim, const floa
                           const int32_t* rows, const float* s1, const float* s2, const float* sums, int32_t batch,
                           const float* g_opt, const float* g_sum, float* dh, float* dw, void* workspace, int64_t workspace_bytes,
                           void* stream);
+
+/* -- general Conv1D -> MaxPooling1D on the matrix pipe (sample_protein/sequence/cnn.py:36-79; csrc/conv1d.hip) ---------------
+ * out [B, L / pool, F] = max over each pool window of act(conv(rows, w [k, Cin, F]) + bias [F]), Keras padding="same" at stride 1
+ * ((k-1)/2 zero positions on the left, the rest on the right, per sequence), pool = 1: no pooling.  The rows are x [B, L, Cin]
+ * (tokens and table NULL) or table[tokens[b, l]] (x NULL; tokens [B, L] int32, table [S, Cin]; a token outside [0, S) reads a zero
+ * row).  act: KGCN_ACT_NONE / KGCN_ACT_RELU / KGCN_ACT_TANH.  Conv positions >= (L / pool) pool lie outside every window.  argmax
+ * (NULL under no_grad) [B, L / pool, F] bytes: the lowest index in the window among equal maxima.
+ * Backward: dout, argmax and the forward's out [B, L / pool, F] -> dx [B, L, Cin] (may be NULL; every row written), dw, dbias (both or
+ * neither) through fixed-order partials in `workspace` (>= kgcn_conv1d_pool_workspace_bytes) and fixed-order second stages (deferrable:
+ * kgcn_reduce_defer).  kgcn_embedding_grad_f32: dtable [S, E] = sum by symbol of dembedded [B, L, E] in a fixed order (rows of
+ * unused symbols are zeros).  No float atomics: results are bitwise reproducible.
+ * Limits: Cin, F, E <= 1024, k <= 8, pool <= 8, L <= 8192, S <= 1024; a shape beyond them fails before any launch. */
+#define KGCN_CONV1D_MAX_CHANNELS 1024
+#define KGCN_CONV1D_MAX_KERNEL 8
+#define KGCN_CONV1D_MAX_POOL 8
+#define KGCN_CONV1D_MAX_LENGTH 8192
+#define KGCN_CONV1D_MAX_SYMBOLS 1024
+int64_t kgcn_conv1d_pool_workspace_bytes(int32_t batch, int32_t length, int32_t in_dim, int32_t kernel_size, int32_t filters,
+                                         int32_t pool);
+int kgcn_conv1d_pool_fwd_f32(const float* x, const int32_t* tokens, const float* table, int32_t symbols, int32_t batch,
+                             int32_t length, int32_t in_dim, const float* w, const float* bias, int32_t kernel_size,
+                             int32_t filters, int32_t pool, int32_t act, float* out, uint8_t* argmax, void* stream);
+int kgcn_conv1d_pool_bwd_f32(const float* x, const int32_t* tokens, const float* table, int32_t symbols, int32_t batch,
+                             int32_t length, int32_t in_dim, const float* w, int32_t kernel_size, int32_t filters, int32_t pool,
+                             int32_t act, const float* dout, const uint8_t* argmax, const float* out, float* dx, float* dw,
+                             float* dbias, void* workspace, int64_t workspace_bytes, void* stream);
+int kgcn_embedding_grad_f32(const int32_t* tokens, int32_t batch, int32_t length, const float* dembedded, int32_t symbols,
+                            int32_t embed_dim, float* dtable, void* stream);
 
 #ifdef __cplusplus
 }

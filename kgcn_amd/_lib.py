@@ -292,6 +292,14 @@ SIGNATURES = {
                                              ctypes.c_void_p]),
     "kgcn_seq_lstm_bwd_f32": (ctypes.c_int, [c_f32p, c_i32, c_i32, c_i32, c_f32p, c_f32p, c_f32p, c_i32, c_i32, c_f32p, c_i64, c_f32p,
                                              c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
+    # general Conv1D + max-pool and the embedding gradient (csrc/conv1d.hip)
+    "kgcn_conv1d_pool_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32]),
+    "kgcn_conv1d_pool_fwd_f32": (ctypes.c_int, [c_f32p, c_i32p, c_f32p, c_i32, c_i32, c_i32, c_i32, c_f32p, c_f32p, c_i32, c_i32,
+                                                c_i32, c_i32, c_f32p, ctypes.c_void_p, ctypes.c_void_p]),
+    "kgcn_conv1d_pool_bwd_f32": (ctypes.c_int, [c_f32p, c_i32p, c_f32p, c_i32, c_i32, c_i32, c_i32, c_f32p, c_i32, c_i32, c_i32,
+                                                c_i32, c_f32p, ctypes.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p,
+                                                c_i64, ctypes.c_void_p]),
+    "kgcn_embedding_grad_f32": (ctypes.c_int, [c_i32p, c_i32, c_i32, c_f32p, c_i32, c_i32, c_f32p, ctypes.c_void_p]),
     # knowledge-graph link prediction (csrc/linkpred.hip)
     "kgcn_linkpred_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32, c_i32]),
     "kgcn_linkpred_fwd_f32": (ctypes.c_int, [c_f32p, c_i64, c_i32, c_f32p, c_i32, c_i32, c_i32p, c_i32p, c_i64, c_i32, c_i32p, c_i32,

@@ -694,3 +694,35 @@ class SequenceEncoder(nn.Module):
             pooled.requires_grad_(True)
         h = ops.seq_lstm(pooled, self.kernel, self.recurrent_kernel, self.bias, self.recurrent_activation, out=out, out_col=out_col)
         return h, pooled, arg
+
+
+class Conv1DPool(nn.Module):
+    """tf.keras.layers.Conv1D(filters, kernel_size, padding='same', activation) followed by MaxPooling1D(pool)
+    (sample_protein/sequence/cnn.py:46-61; pool = 1: no pooling) with Keras' parameter names and initialisers: conv_kernel
+    [k, Cin, F] glorot-uniform (fans k Cin, k F), conv_bias zeros; built on the first input's width.  One launch forward
+    (ops.conv1d_pool, csrc/conv1d.hip): the [B, L, F] conv output is never written.
+    forward(x [B, L, Cin]) or forward(tokens=[B, L] int32, table=[S, Cin]) (the rows are table[tokens]) -> [B, L // pool, F]."""
+
+    def __init__(self, filters, kernel_size, pool=1, activation=None):
+        super().__init__()
+        ops.conv1d_limits_check(filters=filters, kernel_size=kernel_size, pool=pool)
+        if activation not in ops.CONV1D_ACTIVATIONS:
+            raise ValueError("activation must be None, 'relu' or 'tanh'")
+        self.filters, self.kernel_size, self.pool, self.activation = int(filters), int(kernel_size), int(pool), activation
+        self.conv_kernel = None
+        self.conv_bias = None
+
+    def build(self, din, device):
+        if self.conv_kernel is None:
+            ops.conv1d_limits_check(in_dim=din)
+            k, F = self.kernel_size, self.filters
+            lim = math.sqrt(6.0 / (k * din + k * F))
+            self.conv_kernel = nn.Parameter(torch.empty(k, int(din), F, device=device).uniform_(-lim, lim))
+            self.conv_bias = nn.Parameter(torch.zeros(F, device=device))
+
+    def forward(self, x=None, tokens=None, table=None):
+        src = x if x is not None else table
+        if src is None:
+            raise ValueError("Conv1DPool needs a dense input or tokens= and table=")
+        self.build(src.shape[-1], src.device)
+        return ops.conv1d_pool(x, self.conv_kernel, self.conv_bias, self.pool, self.activation, tokens=tokens, table=table)

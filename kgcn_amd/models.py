@@ -17,6 +17,9 @@ between layer and activation it is one HIP elementwise kernel (ops.activation). 
   MultimodalGCN -- example_model/model_multimodal.py:53-118  GraphConv(50), GraphDense(50), Gather | Embedding, Conv1D(50, 4),
                   MaxPooling1D(4), LSTM(32, go_backwards) (csrc/seq.hip); concat, Dense(52) relu, Dense(label_dim)
 
+  SeqCNN       -- sample_protein/sequence/cnn.py:36-90  Embedding, 3 x [Conv1D relu, MaxPooling1D], Conv1D(1, tanh), BN, Dense(52), BN,
+                  relu, Dense(label_dim) (csrc/conv1d.hip); class-weighted softmax CE
+
 Keras learning-phase semantics (quirk Q6): the reference calls BatchNormalization / Dropout
 without `training=`; under TF1 graph mode that is inference behaviour -- BN normalises with its
 moving statistics (0, 1) and Dropout is the identity.  That is what is implemented here
@@ -525,3 +528,97 @@ class LinkPredictionNet(nn.Module):
             return ops.dense(h, ht).unsqueeze(0), h
         w = self.distmult.w[0]
         return torch.stack([ops.dense(h * w[r], ht) for r in range(w.shape[0])]).unsqueeze(0), h
+
+
+class KerasBatchNorm(nn.Module):
+    """K.layers.BatchNormalization() on [B, D], called without `training=` (sample_protein/sequence/cnn.py:74, :76): under the
+    TF1 learning phase 0 (quirk Q6, the module docstring) it normalises with its moving statistics, which start at mean 0 /
+    variance 1 and are never updated, while the trainable gamma (ones) / beta (zeros) receive gradients:
+      y = act(gamma x / sqrt(1 + 1e-3) + beta).
+    The per-channel affine (and a following relu) is the GraphBatchNormalization kernel in inference mode on a [B, 1, D] view."""
+
+    def __init__(self, eps=1e-3, activation=None):
+        super().__init__()
+        self.eps, self.activation = eps, activation
+        self.gamma = None
+        self.beta = None
+
+    def build(self, d, device):
+        if self.gamma is None:
+            self.gamma = nn.Parameter(torch.ones(d, device=device))
+            self.beta = nn.Parameter(torch.zeros(d, device=device))
+            self.register_buffer("moving_mean", torch.zeros(d, device=device))
+            self.register_buffer("moving_variance", torch.ones(d, device=device))
+
+    def forward(self, x):
+        B, D = x.shape
+        self.build(D, x.device)
+        y = ops.graph_bn(x.reshape(B, 1, D), self.gamma, self.beta, self.moving_mean, self.moving_variance, None, self.eps, False,
+                         self.activation)
+        return y.reshape(B, D)
+
+
+class SeqCNN(nn.Module):
+    """sample_protein/sequence/cnn.py:36-90 (config_cnn.json: embedding_dim 25, batch_size 1, learning_rate 1e-4), call by call:
+      :37      Embedding(sequence_symbol_num, embedding_dim)     embeddings [S, E], U(-0.05, 0.05); gathered inside the first
+                                                                 conv kernel (token mode), never written
+      :39-42   feed_embedded_layer                               forward(embedded=[B, L, E]): the first layer reads it (dense mode)
+      :45-48   Conv1D(505, 4, same, relu), MaxPooling1D(4)       layers.Conv1DPool, one launch each
+      :50-53   Conv1D(200, 3, same, relu), MaxPooling1D(3)
+      :55-58   Conv1D(100, 2, same, relu), MaxPooling1D(2)
+      :60-62   Conv1D(1, 2, same, tanh), tf.squeeze              [B, T3, 1] -> [B, T3].  The reference's squeeze drops the batch
+                                                                 axis at B = 1 and repairs it (:64-66); here [B, T3] always
+      :74-77   BatchNormalization, Dense(52), BatchNormalization, relu    KerasBatchNorm (learning phase 0), KerasDense
+      :79      Dense(label_dim)                                  logits
+    forward(features, adjs, sequences=None, embedded=None) -> logits [B, label_dim]; features / adjs are accepted and unused (the
+    sample's dataset carries a dummy 2 x 2 graph), `sequences` is the int32 [B, L] token batch (data_util.sequence_table;
+    GraphedTrainStep passes it as a forward kwarg).  The gradient with respect to `embedded` comes through autograd (what
+    kgcn visualize --ig_label_target differentiates).  Dense(52) fixes the model to one sequence length."""
+
+    ROW_INDEPENDENT = True
+
+    WIDTHS, KERNELS, HIDDEN = (505, 200, 100), (4, 3, 2), 52
+
+    def __init__(self, sequence_symbol_num, embedding_dim=25, label_dim=2, class_weight=None):
+        super().__init__()
+        ops.conv1d_limits_check(symbols=sequence_symbol_num, in_dim=embedding_dim)
+        self.label_dim = int(label_dim)
+        self.embeddings = nn.Parameter(torch.empty(int(sequence_symbol_num), int(embedding_dim)).uniform_(-0.05, 0.05))   # :37
+        self.convs = nn.ModuleList([layers.Conv1DPool(f, k, k, "relu") for f, k in zip(self.WIDTHS, self.KERNELS)])  # :45-58
+        self.conv_out = layers.Conv1DPool(1, self.KERNELS[-1], 1, "tanh")                         # :60-61
+        self.bn1 = KerasBatchNorm()                                                               # :74
+        self.hidden = KerasDense(self.HIDDEN)                                                     # :75
+        self.bn2 = KerasBatchNorm(activation="relu")                                              # :76-77
+        self.out = KerasDense(self.label_dim)                                                     # :79
+        cw = torch.ones(self.label_dim) if class_weight is None else torch.as_tensor(class_weight, dtype=torch.float32).reshape(-1)
+        if cw.numel() != self.label_dim:
+            raise ValueError("class_weight has %d entries for %d classes" % (cw.numel(), self.label_dim))
+        self.register_buffer("class_weight", cw)
+
+    def forward(self, features=None, adjs=None, sequences=None, embedded=None):
+        if embedded is not None:
+            layer = self.convs[0](embedded)                                                       # :39-40
+        elif sequences is not None:
+            layer = self.convs[0](tokens=sequences, table=self.embeddings)
+        else:
+            raise ValueError("SeqCNN needs the sequences= token batch (or embedded=)")
+        layer = self.convs[2](self.convs[1](layer))
+        layer = self.conv_out(layer)
+        layer = layer.reshape(layer.shape[0], layer.shape[1])                                     # :62-66
+        layer = self.bn2(self.hidden(self.bn1(layer)))
+        return self.out(layer)
+
+    def loss(self, logits, labels, mask=None):
+        """cnn.py:84-90 -> (cost_opt, cost_sum): cost_b = softmax CE, cost_sum = sum_b mask_b cost_b (unweighted, :90), and
+        cost_opt = reduce_mean(cost * labels * class_weight) (:85-87).  That product broadcasts cost [B] against [B, C], which is
+        defined at B = 1 only (the config's batch size), where it is cost_0 class_weight[label_0] / C; here, for any B,
+          cost_opt = (1 / (B C)) sum_b mask_b cost_b class_weight[label_b]
+        (a deviation for B > 1, where the reference expression fails to broadcast or, at B = C, pairs costs with other rows'
+        labels).  Both sums are the masked-CE kernel with the per-row weight as its mask operand."""
+        labels = labels.to(torch.float32)
+        B, C = labels.shape
+        mask = torch.ones(B, device=labels.device) if mask is None else mask.to(torch.float32).reshape(-1)
+        row_weight = mask * (labels * self.class_weight).sum(dim=1) * (1.0 / C)
+        cost_opt, _ = ops.masked_softmax_ce(logits, labels, row_weight)
+        _, cost_sum = ops.masked_softmax_ce(logits, labels, mask)
+        return cost_opt, cost_sum

@@ -2149,6 +2149,113 @@ def seq_conv_pool_input_grad(dout, argmax, tokens, table, w, pool, rep, row_weig
     return dx
 
 
+# -------------------------------------------------------------------------------------------------
+# general Conv1D -> MaxPooling1D on the matrix pipe (sample_protein/sequence/cnn.py:36-61; csrc/conv1d.hip)
+# -------------------------------------------------------------------------------------------------
+CONV1D_MAX_CHANNELS, CONV1D_MAX_KERNEL, CONV1D_MAX_POOL, CONV1D_MAX_LENGTH, CONV1D_MAX_SYMBOLS = 1024, 8, 8, 8192, 1024
+CONV1D_ACTIVATIONS = (None, "none", "linear", "relu", "tanh")
+
+
+def conv1d_limits_check(length=None, in_dim=None, filters=None, kernel_size=None, pool=None, symbols=None):
+    """Raise KgcnHipError for a Conv1D shape beyond the kernels' limits (include/kgcn_hip.h); None = not checked."""
+    for name, v, hi in (("length", length, CONV1D_MAX_LENGTH), ("input width", in_dim, CONV1D_MAX_CHANNELS),
+                        ("filters", filters, CONV1D_MAX_CHANNELS), ("kernel size", kernel_size, CONV1D_MAX_KERNEL),
+                        ("pool size", pool, CONV1D_MAX_POOL), ("symbols", symbols, CONV1D_MAX_SYMBOLS)):
+        if v is not None and not 1 <= int(v) <= hi:
+            raise _lib.KgcnHipError("conv1d_pool: %s %d outside 1..%d" % (name, int(v), hi))
+
+
+class _Conv1DPool(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, bias, pool, act, tokens, table):
+        w, b = _f32c(w, "conv kernel"), _f32c(bias, "conv bias").reshape(-1)
+        if w.dim() != 3:
+            raise _lib.KgcnHipError("conv kernel must be [kernel_size, in_dim, filters], got %s" % (tuple(w.shape),))
+        k, Cin, F = w.shape
+        S = 0
+        if tokens is not None:
+            if x is not None or table is None:
+                raise _lib.KgcnHipError("conv1d_pool takes a dense input or a (tokens, table) pair")
+            if not (torch.is_tensor(tokens) and tokens.is_cuda and tokens.dtype == torch.int32 and tokens.dim() == 2):
+                raise _lib.KgcnHipError("tokens must be an int32 [batch, length] device tensor")
+            tokens, table = tokens.contiguous(), _f32c(table, "embedding table")
+            if table.dim() != 2 or table.shape[1] != Cin:
+                raise _lib.KgcnHipError("embedding table %s does not match a conv kernel %s" % (tuple(table.shape), tuple(w.shape)))
+            (B, L), S = tokens.shape, table.shape[0]
+        else:
+            if x is None or table is not None:
+                raise _lib.KgcnHipError("conv1d_pool takes a dense input or a (tokens, table) pair")
+            x = _f32c(x, "conv input")
+            if x.dim() != 3 or x.shape[2] != Cin:
+                raise _lib.KgcnHipError("conv input %s does not match a conv kernel %s" % (tuple(x.shape), tuple(w.shape)))
+            B, L = x.shape[:2]
+        if b.numel() != F:
+            raise _lib.KgcnHipError("conv bias %s does not match %d filters" % (tuple(bias.shape), F))
+        conv1d_limits_check(L, Cin, F, k, pool, S if tokens is not None else None)
+        T = L // pool
+        out = torch.empty((B, T, F), device=w.device, dtype=torch.float32)
+        n = ctx.needs_input_grad
+        train = n[0] or n[1] or n[2] or n[6]
+        arg = torch.empty((B, T, F), device=w.device, dtype=torch.uint8) if train else None
+        check(lib.kgcn_conv1d_pool_fwd_f32(ptr(x), ptr(tokens), ptr(table), S, B, L, Cin, ptr(w), ptr(b), k, F, pool, act, ptr(out),
+                                           ptr(arg), current_stream()), "kgcn_conv1d_pool_fwd_f32")
+        if train:
+            ctx.save_for_backward(x, tokens, table, w, arg, out)
+            ctx.pool, ctx.act, ctx.bias_shape = pool, act, tuple(bias.shape)
+            _record_params(ctx, w, bias, when=n[1] or n[2])
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        n = ctx.needs_input_grad
+        if g is None or not (n[0] or n[1] or n[2] or n[6]):
+            return (None,) * 7
+        x, tokens, table, w, arg, out = ctx.saved_tensors
+        k, Cin, F = w.shape
+        B, L = (x if tokens is None else tokens).shape[:2]
+        S = 0 if tokens is None else table.shape[0]
+        g = _f32c(g, "grad")
+        dx = torch.empty((B, L, Cin), device=w.device, dtype=torch.float32) if (n[0] or n[6]) else None
+        params = n[1] or n[2]
+        dw = torch.empty_like(w) if params else None
+        db = torch.empty((F,), device=w.device, dtype=torch.float32) if params else None
+        wsb = lib.kgcn_conv1d_pool_workspace_bytes(B, L, Cin, k, F, ctx.pool)
+        with _param_grad_stage(ctx, wsb, w.device, when=params) as wsp:
+            check(lib.kgcn_conv1d_pool_bwd_f32(ptr(x), ptr(tokens), ptr(table), S, B, L, Cin, ptr(w), k, F, ctx.pool, ctx.act, ptr(g),
+                                               ptr(arg), ptr(out), ptr(dx), ptr(dw), ptr(db), ptr(wsp), wsb, current_stream()),
+                  "kgcn_conv1d_pool_bwd_f32")
+        dtable = None
+        if n[6]:
+            dtable = torch.empty_like(table)
+            check(lib.kgcn_embedding_grad_f32(ptr(tokens), B, L, ptr(dx), S, Cin, ptr(dtable), current_stream()),
+                  "kgcn_embedding_grad_f32")
+        return (dx if n[0] else None, dw if n[1] else None, db.view(ctx.bias_shape) if n[2] else None, None, None, None, dtable)
+
+
+def conv1d_pool(x, w, bias, pool=1, activation=None, tokens=None, table=None):
+    """Keras Conv1D(F, k, padding='same', activation) -> MaxPooling1D(pool) in one pass (pool = 1: no pooling): x [B, L, Cin] (or
+    x None and tokens [B, L] int32 with table [S, Cin]: the rows are table[tokens], the embedded tensor is never written),
+    w [k, Cin, F], bias [F] -> [B, L // pool, F].  activation: None, 'relu' or 'tanh'.  The backward routes the gradient to the
+    lowest-index maximum of each window and forms d x (dense mode) or d table (token mode; kgcn_embedding_grad_f32), d w and d bias
+    (deferrable fixed-order partials)."""
+    if activation not in CONV1D_ACTIVATIONS:
+        raise _lib.KgcnHipError("conv1d_pool: unsupported activation %r (None, 'relu', 'tanh')" % (activation,))
+    return _Conv1DPool.apply(x, w, bias, int(pool), act_code(activation), tokens, table)
+
+
+def embedding_grad(tokens, dembedded, symbols):
+    """d table [S, E] = the rows of dembedded [B, L, E] summed by the symbol tokens [B, L] holds there (fixed order, no atomics)."""
+    g = _f32c(dembedded, "embedded gradient")
+    if not (torch.is_tensor(tokens) and tokens.is_cuda and tokens.dtype == torch.int32 and tuple(tokens.shape) == tuple(g.shape[:2])):
+        raise _lib.KgcnHipError("tokens must be an int32 device tensor matching the gradient's [batch, length]")
+    conv1d_limits_check(length=g.shape[1], in_dim=g.shape[2], symbols=symbols)
+    dtable = torch.empty((int(symbols), g.shape[2]), device=g.device, dtype=torch.float32)
+    check(lib.kgcn_embedding_grad_f32(ptr(tokens.contiguous()), g.shape[0], g.shape[1], ptr(g), int(symbols), g.shape[2], ptr(dtable),
+                                      current_stream()), "kgcn_embedding_grad_f32")
+    return dtable
+
+
 class _GatherInto(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, join, join_col):
