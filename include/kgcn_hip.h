@@ -77,6 +77,7 @@ extern "C" {
  * kgcn_seq_convpool_input_grad_f32.
  * The protein-sequence CNN added entry points only (version still 2): kgcn_conv1d_pool_fwd_f32 / kgcn_conv1d_pool_bwd_f32
  * (+ kgcn_conv1d_pool_workspace_bytes), kgcn_embedding_grad_f32.
+ * Integrated gradients of the link-prediction model added an entry point only (version still 2): kgcn_kg_ig_f32.
  * The compact row-padded adjacency (row_pad == KGCN_ROW_PAD_COMPACT) added a layout CODE and entry points only (version
  * still 2): a library without it refuses that code in every entry point (validate_csr accepts row_pad 0 and 4 only), so
  * an old library never misreads it; kgcn_csr_compact4 is the feature query (look it up before building such a batch). */
@@ -908,6 +909,35 @@ int kgcn_conv1d_pool_bwd_f32(const float* x, const int32_t* tokens, const float*
                              float* dbias, void* workspace, int64_t workspace_bytes, void* stream);
 int kgcn_embedding_grad_f32(const int32_t* tokens, int32_t batch, int32_t length, const float* dembedded, int32_t symbols,
                             int32_t embed_dim, float* dtable, void* stream);
+
+/* -- integrated gradients of the link-prediction model (kgcn visualize, kgcn/visualization.py:289-439, on model_py/gcn.py;
+ * csrc/kgig.hip) -----------------------------------------------------------------------------------------------------------
+ * The network is relu(A (relu(A (E W1 + b1)) W2 + b2)) over ONE graph A [N, N] given as a plain CSR (indptr [N + 1], indices
+ * [nnz], values [nnz]; A need not be symmetric or have unit values).  The embedded layer is scaled by scales[k], k = 0 .. K-1.
+ * The caller computes once, for all targets: p = E W1 [N, C], g1 = A p [N, C], rowsum = A 1 [N], and the stash
+ * h2 [K, N, C] = relu(A (relu(Z1_k) W2 + b2)) with Z1_k = scales[k] * g1 + rowsum (x) b1 formed as fp32 product, product, sum
+ * (the kernel recomputes the layer-1 relu mask with exactly these roundings).  targets [T, 4] int32 = (a, b, a', b'):
+ *   KGCN_KGIG_SCORE  the attributed quantity is s = h[a] . h[b] (a', b' are not read); score [T, K] = s per step
+ *   KGCN_KGIG_LOSS   it is -log(sigmoid(s1 - s2) + 1e-10), s1 = h[a] . h[b], s2 = h[a'] . h[b']; score [T, K] = s1 - s2 per step
+ * Outputs: node_ig [T, N], node_ig[t, j] = sum_d E[j, d] * (sum_k weights[k] d quantity / d (scales[k] E)[j, d]) -- the
+ * attribution summed over the embedding axis, all the dump reads -- and, when u is not NULL, u [T, N, C] += sum_k weights[k]
+ * dZ1_k (the caller zeroes it; rows outside the seeds' neighbourhoods stay zero), from which the full attribution is
+ * E (.) ((A^T u) W1^T).  One persistent workgroup per target, `groups` of them (0: KGCN_KGIG_GROUPS) in a grid-stride loop.
+ * No float atomics: bitwise reproducible.  NOT checked here (device memory), the caller checks on the host: indptr is
+ * monotone from 0 to nnz, every row's columns are strictly increasing (sorted, no duplicates) and lie in [0, N), target ids
+ * lie in [0, N).  A bad id never reads or writes out of bounds (the entry / target is skipped), but the result is undefined.
+ * Limits: C == 128; N <= KGCN_KGIG_MAX_NODES (the target's node_ig row lives in LDS beside W2 and the 128-row product block);
+ * 1 <= K <= KGCN_KGIG_MAX_STEPS. */
+#define KGCN_KGIG_SCORE 0
+#define KGCN_KGIG_LOSS 1
+#define KGCN_KGIG_WIDTH 128
+#define KGCN_KGIG_MAX_NODES 7168
+#define KGCN_KGIG_MAX_STEPS 4096
+#define KGCN_KGIG_GROUPS 256
+int kgcn_kg_ig_f32(const int32_t* indptr, const int32_t* indices, const float* values, int64_t nnz, int32_t nodes, int32_t width,
+                   const float* g1, const float* rowsum, const float* b1, const float* w2, const float* h2, const float* p,
+                   const float* scales, const float* weights, int32_t steps, const int32_t* targets, int32_t num_targets,
+                   int32_t mode, int32_t groups, float* node_ig, float* score, float* u, void* stream);
 
 #ifdef __cplusplus
 }

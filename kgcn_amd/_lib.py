@@ -306,6 +306,9 @@ SIGNATURES = {
                                              ctypes.c_uint64, ctypes.c_void_p, c_i32p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p]),
     "kgcn_linkpred_bwd_f32": (ctypes.c_int, [c_f32p, c_i64, c_i32, c_f32p, c_i32, c_i32, c_i32p, c_f32p, c_f32p, c_f32p, c_i32,
                                              c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
+    # integrated gradients of the link-prediction model (csrc/kgig.hip)
+    "kgcn_kg_ig_f32": (ctypes.c_int, [c_i32p, c_i32p, c_f32p, c_i64, c_i32, c_i32, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
+                                      c_f32p, c_f32p, c_i32, c_i32p, c_i32, c_i32, c_i32, c_f32p, c_f32p, c_f32p, ctypes.c_void_p]),
     "kgcn_graph_gather_bwd_ld_f32": (ctypes.c_int, [c_f32p, c_i64, c_i64, c_i32, c_i32, c_f32p, ctypes.c_void_p]),
     "kgcn_graph_gather_bwd_add_f32": (ctypes.c_int, [c_f32p, c_f32p, c_i64, c_i32, c_i32, c_f32p, ctypes.c_void_p]),
     "kgcn_dot_workspace_bytes": (c_i64, [c_i64]),

@@ -2376,3 +2376,93 @@ def linkpred_loss(h, feed, mode, w=None, seed=0, step=None, batch=None, labels=N
     if perm is not None and perm.shape != (labels.shape[0],):
         raise _lib.KgcnHipError("linkpred_loss: the permutation must have one entry per label row")
     return _LinkPredLoss.apply(labels, perm, negatives, batch, code, seed, _step_ptr(step), h, w)
+
+
+# -------------------------------------------------------------------------------------------------
+# integrated gradients of the link-prediction model (kgcn visualize on model_py/gcn.py; csrc/kgig.hip): many targets over
+# one graph, from the stash of the K scaled layer-2 outputs
+# -------------------------------------------------------------------------------------------------
+KG_IG_MODES = {"score": 0, "loss": 1}
+KG_IG_WIDTH, KG_IG_MAX_NODES, KG_IG_MAX_STEPS, KG_IG_GROUPS = 128, 7168, 4096, 256
+
+
+def kg_ig_check_host(indptr, indices, num_nodes, targets=None, mode="score", steps=1, width=KG_IG_WIDTH):
+    """Everything the kernel reads unchecked, on host (numpy) copies: raises ValueError, returns the targets as int32 [T, 4]
+    (None when none were given).  The CSR must have monotone row offsets and, in every row, strictly increasing columns inside
+    [0, N) -- sorted and duplicate-free: the scatter spreads a row's entries over lanes and relies on their being distinct."""
+    import numpy as np
+    N = int(num_nodes)
+    if mode not in KG_IG_MODES:
+        raise ValueError("kg_ig: mode must be one of %s, got %r" % (sorted(KG_IG_MODES), mode))
+    if int(width) != KG_IG_WIDTH:
+        raise ValueError("kg_ig: the layers must be %d wide (model_py/gcn.py), got %d" % (KG_IG_WIDTH, int(width)))
+    if not 1 <= N <= KG_IG_MAX_NODES:
+        raise ValueError("kg_ig: %d nodes outside 1..%d (the target's row lives in LDS)" % (N, KG_IG_MAX_NODES))
+    if not 1 <= int(steps) <= KG_IG_MAX_STEPS:
+        raise ValueError("kg_ig: %d steps outside 1..%d" % (int(steps), KG_IG_MAX_STEPS))
+    indptr = np.asarray(indptr).astype(np.int64).reshape(-1)
+    indices = np.asarray(indices).astype(np.int64).reshape(-1)
+    if indptr.shape[0] != N + 1 or indptr[0] != 0 or indptr[-1] != indices.shape[0] or np.any(np.diff(indptr) < 0):
+        raise ValueError("kg_ig: the row offsets must rise from 0 to nnz = %d over %d rows" % (indices.shape[0], N))
+    if indices.size:
+        if indices.min() < 0 or indices.max() >= N:
+            raise ValueError("kg_ig: adjacency column outside [0, %d)" % N)
+        inside = np.ones(indices.shape[0], bool)
+        inside[indptr[:-1][indptr[:-1] < indices.shape[0]]] = False            # the first entry of every non-empty row
+        if np.any((np.diff(indices, prepend=-1) <= 0) & inside):
+            raise ValueError("kg_ig: every adjacency row must hold sorted, duplicate-free columns")
+    if targets is None:
+        return None
+    tg = np.asarray(targets)
+    if tg.ndim != 2 or tg.shape[1] != 4 or not np.issubdtype(tg.dtype, np.integer):
+        raise ValueError("kg_ig: targets must be an integer [T, 4] array of (a, b, a', b'), got %s %s" % (tg.shape, tg.dtype))
+    used = tg if mode == "loss" else tg[:, :2]
+    if used.size and (used.min() < 0 or used.max() >= N):
+        raise ValueError("kg_ig: target node outside [0, %d)" % N)
+    return np.ascontiguousarray(tg, np.int32)
+
+
+def kg_ig(csr, g1, rowsum, b1, w2, h2, p, scales, weights, targets, mode="score", want_u=False, groups=None):
+    """csrc/kgig.hip: integrated gradients of T targets of the link-prediction gcn from the stash -> (node_ig [T, N], score [T, K],
+    u [T, N, C] or None).  csr: the one graph (a BatchedCSR of one graph); g1 = A (E W1), rowsum = A 1, p = E W1, h2 [K, N, C] the
+    layer-2 outputs at scales [K] (formed from fp32 scales[k] * g1 + rowsum[:, None] * b1), weights [K] the step weights;
+    targets: host integer [T, 4] rows (a, b, a', b'), mode 'score' (a, b only) or 'loss'.  groups: workgroups of the launch
+    (default KG_IG_GROUPS; each walks whole targets in a grid-stride loop).  A read-out: no autograd, runs under no_grad.
+    The CSR and the targets are validated on the host (kg_ig_check_host), once per container."""
+    import numpy as np
+    if csr.num_graphs != 1 or csr.rows != csr.cols or csr.row_pad:
+        raise ValueError("kg_ig: the adjacency must be one square graph in the plain CSR layout")
+    N = csr.rows
+    h2 = _f32c(h2, "h2")
+    if h2.dim() != 3 or h2.shape[1] != N:
+        raise ValueError("kg_ig: h2 must be [K, %d, C], got %s" % (N, tuple(h2.shape)))
+    K, _, C = h2.shape
+    host = getattr(csr, "_kg_ig_host", None)
+    if host is None:
+        host = (csr.rowptr.cpu().numpy(), csr.cv[:, 0].cpu().numpy())
+        kg_ig_check_host(host[0], host[1], N, None, mode, K, C)
+        csr._kg_ig_host = host
+        csr._kg_ig_dev = (csr.cv[:, 0].contiguous(), csr.values)
+    tg = kg_ig_check_host(host[0], host[1], N, targets.cpu().numpy() if torch.is_tensor(targets) else targets, mode, K, C)
+    indices, values = csr._kg_ig_dev
+    dev = h2.device
+    with torch.no_grad():
+        g1, p, w2 = _f32c(g1.detach(), "g1"), _f32c(p.detach(), "p"), _f32c(w2.detach(), "w2")
+        rowsum, b1 = _f32c(rowsum.detach(), "rowsum").reshape(-1), _f32c(b1.detach(), "b1").reshape(-1)
+        sc = torch.as_tensor(np.asarray(scales, np.float32), device=dev) if not torch.is_tensor(scales) else _f32c(scales, "scales")
+        wt = torch.as_tensor(np.asarray(weights, np.float32), device=dev) if not torch.is_tensor(weights) else _f32c(weights, "weights")
+        if tuple(g1.shape) != (N, C) or tuple(p.shape) != (N, C) or tuple(w2.shape) != (C, C) or rowsum.numel() != N or \
+                b1.numel() != C or sc.numel() != K or wt.numel() != K:
+            raise ValueError("kg_ig: operand shapes disagree with N = %d, C = %d, K = %d" % (N, C, K))
+        T = tg.shape[0]
+        tgd = torch.from_numpy(tg).to(dev)
+        node_ig = torch.empty((T, N), device=dev, dtype=torch.float32)
+        score = torch.empty((T, K), device=dev, dtype=torch.float32)
+        u = torch.zeros((T, N, C), device=dev, dtype=torch.float32) if want_u else None
+        g = KG_IG_GROUPS if groups is None else int(groups)
+        if not 1 <= g <= 65535:
+            raise ValueError("kg_ig: %d workgroups" % g)
+        check(lib.kgcn_kg_ig_f32(ptr(csr.rowptr), ptr(indices), ptr(values), csr.nnz, N, C, ptr(g1), ptr(rowsum), ptr(b1), ptr(w2),
+                                 ptr(h2), ptr(p), ptr(sc), ptr(wt), K, ptr(tgd), T, KG_IG_MODES[mode], g, ptr(node_ig), ptr(score),
+                                 ptr(u), current_stream()), "kgcn_kg_ig_f32")
+    return node_ig, score, u

@@ -329,3 +329,255 @@ def multimodal_integrated_gradients(model, features, adjacency, tokens, labels=N
                     "true_label": true_label})
         results.append(rec)
     return results
+
+
+# -------------------------------------------------------------------------------------------------
+# the link-prediction model (sample_kg/network_prediction/model_py/{gcn,distmult,ip}.py): kgcn/visualization.py:289-439
+# (KnowledgeGraphVisualizer, cal_feature_IG_for_kg), many targets per launch
+# -------------------------------------------------------------------------------------------------
+KG_VISUALIZE_TYPES = ("edge_score", "edge_loss", "node")
+KG_IG_NODE_BYTES = 512 << 20          # default bound of one launch's node_ig [T, N] (reduce='node')
+KG_IG_FULL_BYTES = 256 << 20          # ... and of one launch's u [T, N, C] (reduce=None)
+
+
+def _kg_targets(visualize_type, label_list, target, num_nodes):
+    """-> the target indices: `target` (an int or a sequence), or every label row / every node (:401-407)."""
+    import numpy as np
+    n = num_nodes if visualize_type == "node" else len(label_list)
+    if target is None:
+        return np.arange(n, dtype=np.int64)
+    ids = np.atleast_1d(np.asarray(target, np.int64)).reshape(-1)
+    if ids.size and (ids.min() < 0 or ids.max() >= n):
+        raise ValueError("visualize target outside 0..%d" % (n - 1))
+    return ids
+
+
+def _kg_table_ig(model, label_list, visualize_type, ids, scales, weights, method, reduce):
+    """distmult / ip: s = sum_d e_a e_b w_r is bilinear in the table, so IG[a] = e_a w e_b sum_k w_k alpha_k in closed form."""
+    import numpy as np
+    if visualize_type != "edge_score":
+        raise ValueError("visualize_type %r is not defined for the %r model: the reference's model.loss[target] and "
+                         "prediction[:, target, idx] exist for model_py/gcn.py only (distmult.py / ip.py set model.score alone)"
+                         % (visualize_type, model.variant))
+    E = model.embedding.detach()
+    f = float(sum(s * w for s, w in zip(scales, weights)))
+    rows = np.asarray(label_list)[ids]
+    results = []
+    for tid, row in zip(ids, rows):
+        a, r, b = int(row[0]), int(row[1]), int(row[2])
+        w = model.distmult.w[0][r].detach() if model.distmult is not None else torch.ones_like(E[0])
+        ga, gb = E[b] * w * f, E[a] * w * f                       # sum_k w_k d s / d (alpha_k E) rows a and b
+        ig = torch.zeros_like(E)
+        ig[a] += ga if method == "grad" else ga * E[a]
+        ig[b] += gb if method == "grad" else gb * E[b]
+        s = float((E[a] * E[b] * w).sum())
+        rec = {"target": int(tid), "vis_nodes": [a, b], "node_ig": ig.sum(-1).cpu().numpy(), "start_score": 0.0, "end_score": s}
+        if reduce is None:
+            rec["ig"] = ig.cpu().numpy()
+        rec["sum_of_ig"] = float(rec["node_ig"].astype(np.float64).sum())
+        results.append(rec)
+    return results
+
+
+def linkpred_ig_stash(model, adj, scales):
+    """What linkpred_integrated_gradients computes ONCE for all targets of a models.LinkPredictionNet('gcn') on the one-graph
+    BatchedAdjacency `adj`: E, w1, b1, w2, p = E W1, g1 = A p, rowsum = A 1 (fp64 on the host, rounded once) and
+    h2 [K, N, C] = conv2(relu(scales[k] * g1 + rowsum (x) b1)), the layer-2 output at every scale -- the operands of ops.kg_ig.
+    Layer 1 is affine in the scale, so its K forwards are K scaled adds; layer 2 runs K times through the model's own layer."""
+    import numpy as np
+    from . import ops
+    csr = adj.channels[0]
+    N = model.num_nodes
+    with torch.no_grad():
+        if not model.conv1.built or not model.conv2.built:
+            model.node_rows(adj)
+        E = model.embedding.detach().contiguous()
+        w1, b1 = model.conv1.w[0].detach(), model.conv1.bias[0].detach().reshape(-1)
+        w2 = model.conv2.w[0].detach()
+        p = ops.dense(E, w1)
+        g1 = ops.bspmm(csr, p)
+        rp = csr.rowptr.cpu().numpy().astype(np.int64)
+        vals = csr.values.cpu().numpy().astype(np.float64)
+        rowsum = torch.from_numpy(np.bincount(np.repeat(np.arange(N), np.diff(rp)), weights=vals, minlength=N)).to(torch.float32).to(E.device)
+        bias_rows = rowsum[:, None] * b1[None, :]
+        h2 = torch.empty((len(scales), N, w2.shape[1]), device=E.device, dtype=torch.float32)
+        for k, al in enumerate(scales):
+            z1 = g1 * float(np.float32(al)) + bias_rows
+            h2[k] = model.conv2(torch.relu(z1).view(1, N, -1), adj=adj).view(N, -1)
+    return dict(E=E, w1=w1, b1=b1, w2=w2, p=p, g1=g1, rowsum=rowsum, h2=h2)
+
+
+def linkpred_integrated_gradients(model, adjs, label_list, visualize_type="edge_score", target=None, divide_number=30, method="ig",
+                                  reduce="node", chunk=None):
+    """`kgcn visualize` of sample_kg/network_prediction (cal_feature_IG_for_kg, KnowledgeGraphVisualizer): integrated gradients
+    with respect to the embedded layer of
+      edge_score  model.score[target] = s1 of label row `target` (columns 0 and 2),
+      edge_loss   model.loss[target]  = -log(sigmoid(s1 - s2) + 1e-10) of the row (columns 0, 2 against 3, 5),
+      node        prediction[:, target, argmax_j prediction[:, target, j]]: node `target` paired with its best partner at scale 1.
+    target: an index, a sequence of them, or None = every label row (every node for 'node'), as --visualize_target unset.
+    Returns one dict per target: target, vis_nodes (and partner for 'node'), node_ig [N] (the attribution summed over the embedding axis: all that
+    _dump_dml reads), sum_of_ig, start_score / end_score (the attributed quantity at scale 0 and 1: the reference's check),
+    and with reduce=None also ig [N, De].
+
+    gcn: models.LinkPredictionNet('gcn').  The K scaled forwards are run ONCE for all targets (layer 1 is affine in the scale,
+    layer 2 is stashed as [K, N, 128]); the per-target work is one launch of ops.kg_ig over `chunk` targets (default: as many as
+    keep one launch's output under KG_IG_NODE_BYTES, or KG_IG_FULL_BYTES of u for reduce=None).  reduce=None forms the full
+    attribution E (.) ((A^T u) W1^T) with the existing SpMM and dense ops: meant for a handful of targets.
+    distmult / ip: edge_score only, in closed form.
+    The attribution multiplies by the TRAINED table (the reference's model.embedding(sess, ...) re-initialises it)."""
+    import numpy as np
+    from . import models, ops
+    from .batched_csr import as_batched_adjacency
+    if not isinstance(model, models.LinkPredictionNet):
+        raise TypeError("linkpred_integrated_gradients needs a models.LinkPredictionNet, got %s" % type(model).__name__)
+    if visualize_type not in KG_VISUALIZE_TYPES:
+        raise ValueError("visualize_type must be one of %s, got %r" % (", ".join(KG_VISUALIZE_TYPES), visualize_type))
+    if reduce not in ("node", None):
+        raise ValueError("reduce must be 'node' or None")
+    scales, weights = ig_scales(method, divide_number)
+    if method == "grad" and reduce == "node":
+        raise ValueError("method 'grad' is not multiplied by the table: it has no node-reduced form (use reduce=None)")
+    label_list = np.asarray(label_list)
+    if visualize_type != "node" and (label_list.ndim != 2 or label_list.shape[1] != 6):
+        raise ValueError("label_list must be [M, 6]")
+    N = model.num_nodes
+    ids = _kg_targets(visualize_type, label_list, target, N)
+    if model.variant != "gcn":
+        return _kg_table_ig(model, label_list, visualize_type, ids, scales, weights, method, reduce)
+    if adjs is None:
+        raise ValueError("the gcn variant needs the graph (adjs)")
+    adj = as_batched_adjacency(adjs)
+    if adj.num_channels != 1 or adj.num_graphs != 1 or adj.n_nodes != N:
+        raise ValueError("the link-prediction graph is one adjacency channel of one %d-node graph" % N)
+    csr = adj.channels[0]
+    K = len(scales)
+    with torch.no_grad():
+        st = linkpred_ig_stash(model, adj, scales)
+        E, w1, b1, w2, p, g1, rowsum, h2 = (st[k] for k in ("E", "w1", "b1", "w2", "p", "g1", "rowsum", "h2"))
+        dev = E.device
+        # the targets as (a, b, a', b') rows
+        if visualize_type == "node":
+            pred, _ = model.predict(adj)
+            partner = pred[0][torch.as_tensor(ids, device=dev)].argmax(dim=1).cpu().numpy()
+            tg = np.stack([ids, partner, np.full_like(ids, -1), np.full_like(ids, -1)], 1)
+            vis = [[int(t)] for t in ids]
+            partners = [int(j) for j in partner]
+        else:
+            rows = label_list[ids].astype(np.int64)
+            if visualize_type == "edge_loss":
+                tg = rows[:, [0, 2, 3, 5]]
+            else:
+                tg = np.concatenate([rows[:, [0, 2]], np.full((len(ids), 2), -1, np.int64)], 1)
+            vis = [[int(r[0]), int(r[2])] for r in rows]
+            partners = None
+        mode = "loss" if visualize_type == "edge_loss" else "score"
+        if chunk is None:
+            per = 4 * N * (1 if reduce == "node" else w2.shape[0] + 1)
+            chunk = max(1, (KG_IG_NODE_BYTES if reduce == "node" else KG_IG_FULL_BYTES) // per)
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError("chunk must be >= 1")
+        sc = torch.tensor(np.asarray(scales, np.float32), device=dev)
+        wt = torch.tensor(np.asarray(weights, np.float32), device=dev)
+        results = []
+        for c0 in range(0, len(ids), chunk):
+            part = tg[c0:c0 + chunk].astype(np.int32)
+            node_ig, score, u = ops.kg_ig(csr, g1, rowsum, b1, w2, h2, p, sc, wt, part, mode=mode, want_u=reduce is None)
+            nig = node_ig.cpu().numpy()
+            s = score.cpu().numpy().astype(np.float64)
+            if mode == "loss":                                   # the attributed quantity is the cost of s1 - s2
+                with np.errstate(over="ignore"):
+                    s = -np.log(1.0 / (1.0 + np.exp(-s)) + 1e-10)
+            full = None
+            if reduce is None:
+                T = part.shape[0]
+                full = []
+                w1t = w1.t().contiguous()
+                for t in range(T):
+                    de = ops.dense(ops.bspmm(csr.transpose(), u[t]), w1t)
+                    full.append((de if method == "grad" else de * E).cpu().numpy())
+            for t in range(part.shape[0]):
+                rec = {"target": int(ids[c0 + t]), "vis_nodes": vis[c0 + t], "node_ig": nig[t],
+                       "start_score": float(s[t, 0]), "end_score": float(s[t, K - 1])}
+                if partners is not None:
+                    rec["partner"] = partners[c0 + t]
+                if full is not None:
+                    rec["ig"] = full[t]
+                    rec["sum_of_ig"] = float(full[t].astype(np.float64).sum())
+                else:
+                    rec["sum_of_ig"] = float(nig[t].astype(np.float64).sum())
+                results.append(rec)
+    return results
+
+
+def kg_undirected_edges(indptr, indices):
+    """The distinct undirected edges (u <= v, sorted, self loops included) of a CSR pattern -> int64 [E, 2]."""
+    import numpy as np
+    indptr = np.asarray(indptr, np.int64).reshape(-1)
+    indices = np.asarray(indices, np.int64).reshape(-1)
+    rows = np.repeat(np.arange(indptr.shape[0] - 1, dtype=np.int64), np.diff(indptr))
+    lo, hi = np.minimum(rows, indices), np.maximum(rows, indices)
+    return np.unique(np.stack([lo, hi], 1), axis=0) if rows.size else np.zeros((0, 2), np.int64)
+
+
+def kg_subgraph(indptr, indices, vis_nodes, graph_distance, und=None):
+    """_dump_dml (:364-374) without networkx: the graph is undirected there (nx.from_scipy_sparse_matrix: an edge wherever A or
+    A^T has an entry, self loops included), the node set grows by `graph_distance` rounds of neighbours from vis_nodes (a BFS
+    over the CSR and its transpose), and the subgraph is the one induced on it -> (nodes ascending, edges (u, v) with u <= v,
+    sorted).  networkx's own node and edge order (insertion order) is not reproduced."""
+    import numpy as np
+    N = np.asarray(indptr).reshape(-1).shape[0] - 1
+    und = kg_undirected_edges(indptr, indices) if und is None else und
+    inside = np.zeros(N, bool)
+    inside[np.asarray(list(vis_nodes), np.int64)] = True
+    for _ in range(int(graph_distance)):
+        touch = inside[und[:, 0]] | inside[und[:, 1]]
+        inside[und[touch, 0]] = True
+        inside[und[touch, 1]] = True
+    keep = inside[und[:, 0]] & inside[und[:, 1]]
+    return np.nonzero(inside)[0], und[keep]
+
+
+def kg_dump_name(visualize_type, vis_nodes):
+    """:425, :433."""
+    if visualize_type == "node":
+        return "nodepred-%d" % int(vis_nodes[0])
+    return "edgepred-%d-%d" % (int(vis_nodes[0]), int(vis_nodes[1]))
+
+
+def dump_kg(result, adjs, outdir, graph_distance, visualize_type=None):
+    """KnowledgeGraphVisualizer.dump / _dump_dml (:348-386) for the dicts of linkpred_integrated_gradients (one or a list):
+    <name>-edge.csv holds the `u,v` lines of the subgraph within graph_distance hops of the vis_nodes, <name>-node.csv starts with
+    `label,ig` and has one line per subgraph node with ig = (node_ig - mean) / std over ALL nodes.  name = edgepred-{n1}-{n2} for
+    two vis_nodes, nodepred-{t} for one (or as visualize_type says).  adjs: the graph (BatchedAdjacency / BatchedCSR, read back
+    once) or a host (indptr, indices) pair.  Edges are written u <= v, sorted, nodes ascending: networkx's order is not
+    reproduced.  Returns the list of (edge file, node file)."""
+    import os
+    import numpy as np
+    results = [result] if isinstance(result, dict) else list(result)
+    if isinstance(adjs, (tuple, list)) and len(adjs) == 2 and not hasattr(adjs[0], "rowptr"):
+        indptr, indices = adjs
+    else:
+        from .batched_csr import as_batched_adjacency
+        csr = as_batched_adjacency(adjs).channels[0]
+        indptr, indices = csr.rowptr.cpu().numpy(), csr.cv[:, 0].cpu().numpy()
+    os.makedirs(outdir, exist_ok=True)
+    und = kg_undirected_edges(indptr, indices)
+    files = []
+    for rec in results:
+        vis = list(rec["vis_nodes"])
+        kind = visualize_type if visualize_type is not None else ("node" if len(vis) == 1 else "edge_score")
+        name = kg_dump_name(kind, vis)
+        ig = np.asarray(rec["node_ig"], np.float64).reshape(-1)
+        norm = (ig - ig.mean()) / ig.std()
+        nodes, edges = kg_subgraph(indptr, indices, vis, graph_distance, und)
+        ef, nf = os.path.join(outdir, name + "-edge.csv"), os.path.join(outdir, name + "-node.csv")
+        with open(ef, "w") as f:
+            for u, v in edges:
+                f.write("%d,%d\n" % (u, v))
+        with open(nf, "w") as f:
+            f.write("label,ig\n")
+            for n in nodes:
+                f.write("%d,%s\n" % (n, repr(float(norm[n]))))
+        files.append((ef, nf))
+    return files
