@@ -80,7 +80,8 @@ extern "C" {
  * Integrated gradients of the link-prediction model added an entry point only (version still 2): kgcn_kg_ig_f32.
  * The compact row-padded adjacency (row_pad == KGCN_ROW_PAD_COMPACT) added a layout CODE and entry points only (version
  * still 2): a library without it refuses that code in every entry point (validate_csr accepts row_pad 0 and 4 only), so
- * an old library never misreads it; kgcn_csr_compact4 is the feature query (look it up before building such a batch). */
+ * an old library never misreads it; kgcn_csr_compact4 is the feature query (look it up before building such a batch).
+ * The SpMM route report added an entry point only (version still 2): kgcn_spmm_route_query (+ kgcn_spmm_route). */
 #define KGCN_HIP_ABI_VERSION 2
 
 /* Column index of the padding entries of a row-padded batch (see row_pad): they carry value 0 and
@@ -701,6 +702,39 @@ int kgcn_reduce_flush(void* stream);
  * wgradn / wgradx, 2.5 PF / 6), 1: v_mfma_f32_32x32x2_f32 kernels (157.3 TF), 0: no matrix pipe (read-out layers).
  * kind 0: y = act(x W + b) / dx = dy W^T (din = contraction width), 1: dx with the activation derivative, 2: weight gradient. */
 int kgcn_dense_mfma_products(int32_t kind, int64_t m, int32_t din, int32_t dout);
+
+/* Which kernel a batched SpMM call takes (csrc/spmm.hip decides it in one host function, spmm_route; this reports its answer).
+ * Host only: no launch, no device pointer followed (the descriptors' rowptr / cv may be anything; block_ptr only counts as
+ * present or NULL), so it answers without a GPU.  a_ch: num_channels (1..8) descriptors of one launch; strides as the entry
+ * point takes them -- channel_stride is the rhs channel stride of an aggregation (kgcn_bconv*_f32; 0 for single-channel calls)
+ * and the out channel stride of a fan-out; align_bytes: the common alignment of the operand pointers, 16, 8 or 4. */
+enum {
+  KGCN_SPMM_NONE = 0,          /* nothing to launch (empty batch); fan-out: one single-channel launch per channel instead */
+  KGCN_SPMM_TILE = 1,          /* spmm_tile_kernel<LPR, VEC, NW, false> */
+  KGCN_SPMM_TILE_DOT = 2,      /* spmm_tile_kernel<LPR, 4, NW, true>: <grad, x> of GINAggregate's backward rides along */
+  KGCN_SPMM_SLICES = 3,        /* spmm_slices_kernel<NS> */
+  KGCN_SPMM_BLOCK = 4,         /* spmm_block_kernel<VEC, LPR, DACT> */
+  KGCN_SPMM_ROWS = 5,          /* spmm_rows_kernel<VEC, LPR, DACT, ROWS> */
+  KGCN_SPMM_GATHER = 6,        /* spmm_gather_kernel<VEC> */
+  KGCN_SPMM_BCONV_LOOP = 7,    /* bconv_loop_kernel<VEC, NVL, NP> */
+  KGCN_SPMM_BCONV_FANOUT = 8   /* bconv_fanout_kernel<VEC, NVL> */
+};
+/* flags of the call */
+#define KGCN_SPMM_DACT 1         /* the operand is multiplied by act'(act_out) (kgcn_bspmm_dact_f32, fan-out with act != 0) */
+#define KGCN_SPMM_SELF_SCALE 2   /* eps * x is added (kgcn_gin_aggregate_f32 and its backward with eps) */
+#define KGCN_SPMM_DOT 4          /* first channel of kgcn_gin_aggregate_bwd_f32 with deps */
+#define KGCN_SPMM_FANOUT 8       /* kgcn_bconv_fanout_f32 */
+typedef struct kgcn_spmm_route {
+  int32_t kernel;              /* KGCN_SPMM_* */
+  int32_t template_args[4];    /* of the instantiation, in declaration order (bool as 0 / 1); unused entries 0 */
+  int32_t ds, slices;          /* columns per workgroup and column slices (d = ds * slices) */
+  int32_t workgroup;           /* threads per workgroup */
+  int64_t grid;                /* workgroups */
+  int64_t lds_bytes;           /* dynamic LDS of the launch */
+} kgcn_spmm_route;
+int kgcn_spmm_route_query(const kgcn_csr_batch* a_ch, int32_t num_channels, int32_t d, int64_t rhs_ld, int64_t rhs_graph_stride,
+                          int64_t channel_stride, int64_t out_ld, int64_t out_graph_stride, int32_t align_bytes, int32_t flags,
+                          kgcn_spmm_route* route);
 
 /* Several strided 2-D fp32 copies in ONE launch: dst[r * dst_ld + c] = src[r * src_ld + c] for r < rows, c < cols of every job.
  * Used for the operand of a multi-channel GraphConv's single GEMM, [W_0 | W_1 | ...] and [b_0 | b_1 | ...] (kgcn/layers.py:68-78

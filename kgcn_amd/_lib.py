@@ -9,11 +9,11 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # Development overrides.  KGCN_HIP_LIB: load another build of the library (tools/variant_bench.py times alternative builds).
-# KGCN_SPMM_BLOCKS / KGCN_GIN_JOIN / KGCN_GIN_DOT: Python-side routing switches.  (The library's own development knobs exist only
-# in a -DKGCN_DEV_KNOBS build, make DEV_KNOBS=1; the dense family has none left.)  Anything set here is reported by
-# active_overrides() (bench.py prints it in its JSON line) and warned about once at import, because a stray variable
-# changes summation order / which binary produced the numbers.
-DEV_ENV_VARS = ("KGCN_HIP_LIB", "KGCN_SPMM_BLOCKS", "KGCN_GIN_JOIN", "KGCN_GIN_DOT")
+# KGCN_GIN_JOIN / KGCN_GIN_DOT: Python-side routing switches.  (The library's own development knobs exist only
+# in a -DKGCN_DEV_KNOBS build, make DEV_KNOBS=1; the dense family and the batched SpMM have none left.)  Anything set here is
+# reported by active_overrides() (bench.py prints it in its JSON line) and warned about once at import, because a stray
+# variable changes summation order / which binary produced the numbers.
+DEV_ENV_VARS = ("KGCN_HIP_LIB", "KGCN_GIN_JOIN", "KGCN_GIN_DOT")
 LIB_PATH = os.environ.get("KGCN_HIP_LIB") or os.path.join(_HERE, "csrc", "libkgcn_hip.so")
 
 
@@ -98,6 +98,17 @@ class AssemblePlan(ctypes.Structure):
                 ("table", ctypes.c_void_p * ASSEMBLE_MAX_TABLES), ("table_out", ctypes.c_void_p * ASSEMBLE_MAX_TABLES),
                 ("row_floats", c_i64 * ASSEMBLE_MAX_TABLES)]
 
+
+class SpmmRoute(ctypes.Structure):
+    """struct kgcn_spmm_route (include/kgcn_hip.h): the answer of kgcn_spmm_route_query."""
+    _fields_ = [("kernel", c_i32), ("template_args", c_i32 * 4), ("ds", c_i32), ("slices", c_i32), ("workgroup", c_i32),
+                ("grid", c_i64), ("lds_bytes", c_i64)]
+
+
+# KGCN_SPMM_* kernel codes (the kernels of csrc/spmm.hip without their _kernel suffix) and call flags
+SPMM_KERNELS = ("none", "spmm_tile", "spmm_tile_dot", "spmm_slices", "spmm_block", "spmm_rows", "spmm_gather", "bconv_loop",
+                "bconv_fanout")
+SPMM_DACT, SPMM_SELF_SCALE, SPMM_DOT, SPMM_FANOUT = 1, 2, 4, 8
 
 _ASMP = ctypes.POINTER(AssemblePlan)
 _PTRP = ctypes.POINTER(ctypes.c_void_p)
@@ -231,6 +242,8 @@ SIGNATURES = {
     "kgcn_ragged_gather_bwd_f32": (ctypes.c_int, [c_f32p, c_i32p, c_i64, c_i32, c_i32, c_i32, c_i32, c_f32p,
                                                   ctypes.c_void_p, c_i64, ctypes.c_void_p]),
     "kgcn_dense_mfma_products": (ctypes.c_int, [c_i32, c_i64, c_i32, c_i32]),
+    "kgcn_spmm_route_query": (ctypes.c_int, [_CSRP, c_i32, c_i32, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32,
+                                             ctypes.POINTER(SpmmRoute)]),
     "kgcn_copy2d_multi_f32": (ctypes.c_int, [ctypes.c_void_p, c_i32, ctypes.c_void_p]),
     "kgcn_hbm_probe": (ctypes.c_int, [c_i32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
     "kgcn_reduce_defer": (ctypes.c_int, [c_i32]),
@@ -352,6 +365,16 @@ def check(rc, what=""):
         msg = lib.kgcn_last_error()
         raise KgcnHipError("%s failed: %s" % (what or "kgcn_hip call",
                                               msg.decode() if msg else "unknown error"))
+
+
+def spmm_route(descs, num_channels, d, rhs_ld, rhs_gs, channel_stride, out_ld, out_gs, align=16, flags=0):
+    """kgcn_spmm_route_query: which kernel of csrc/spmm.hip the call described takes -> (kernel name out of SPMM_KERNELS, its
+    template arguments, the filled SpmmRoute).  descs: a kgcn_csr_batch or an array of them (BatchedCSR.desc(),
+    BatchedAdjacency.desc_array()); host code, no GPU needed."""
+    r = SpmmRoute()
+    check(lib.kgcn_spmm_route_query(descs, num_channels, d, rhs_ld, rhs_gs, channel_stride, out_ld, out_gs, align, flags,
+                                    ctypes.byref(r)), "kgcn_spmm_route_query")
+    return SPMM_KERNELS[r.kernel], list(r.template_args), r
 
 
 def current_stream():

@@ -264,15 +264,8 @@ size_t gemm_lds(int k) {
 
 template <int kSrc>
 int launch_gemm(const ConvArgs& a, float* out, uint8_t* argmax, hipStream_t s, const char* what) {
-  static bool done = false;
   const size_t lds = gemm_lds(a.k);
-  if (lds > (size_t)kLdsBytes) return fail("%s: %zu bytes of LDS needed, %d available", what, lds, kLdsBytes);
-  if (!done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv1d_gemm_kernel<kSrc>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    if (e != hipSuccess) return fail("hipFuncSetAttribute: %s", hipGetErrorString(e));
-    done = true;
-  }
+  if (int rc = allow_full_lds<conv1d_gemm_kernel<kSrc>>(lds, what)) return rc;
   hipLaunchKernelGGL(conv1d_gemm_kernel<kSrc>, dim3((unsigned)(a.B * a.tiles_per_seq), (unsigned)((a.N + kCols - 1) / kCols)),
                      dim3(256), lds, s, a, out, argmax);
   return check_launch(what);

@@ -379,12 +379,6 @@ __global__ __launch_bounds__(512, 2) void dense_wgrad_persist_kernel(
   }
 }
 
-// more than 64 KB of dynamic LDS has to be allowed per kernel (and per thread that launches it)
-template <typename Kernel>
-static void allow_full_lds(Kernel kernel) {
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-}
-
 static int persist_blocks(long m) {
   long tiles = (m + 31) / 32;
   long b = (tiles + P_WAVES - 1) / P_WAVES;
@@ -542,12 +536,8 @@ static int launch_fwd_persist(const float* x, long m, int din, long x_ld, const 
   const int kp = ((din + 63) / 64) * 64;
   const size_t lds = persist_fwd_lds(din);
   const bool vec = (din % 4 == 0) && (x_ld % 4 == 0) && aligned16(x);
-  static thread_local bool attr_set = false;
-  if (!attr_set) {
-    allow_full_lds(dense_fwd_persist_kernel<true>);
-    allow_full_lds(dense_fwd_persist_kernel<false>);
-    attr_set = true;
-  }
+  if (int rc = allow_full_lds<dense_fwd_persist_kernel<true>>(lds, "dense_fwd_persist_kernel")) return rc;
+  if (int rc = allow_full_lds<dense_fwd_persist_kernel<false>>(lds, "dense_fwd_persist_kernel")) return rc;
   // two workgroups per CU when the panel is small enough (4 waves per SIMD in total)
   int blocks = persist_blocks(m);
   if (2 * lds <= (size_t)kLdsBytes && blocks == kNumCU) blocks = 2 * kNumCU;
@@ -926,12 +916,8 @@ static int launch_wgrad_persist(const float* x, long x_ld, const float* dy, long
                                 float* part_dw, float* part_db, int nblocks, hipStream_t s) {
   // the waves' parked accumulators and column sums; their 2 x [32][64] staging tiles fit inside
   const size_t lds = (size_t)P_WAVES * (64 * 64 + 64) * 4;
-  static thread_local bool attr_set = false;
-  if (!attr_set) {
-    allow_full_lds(dense_wgrad_persist_kernel<true>);
-    allow_full_lds(dense_wgrad_persist_kernel<false>);
-    attr_set = true;
-  }
+  if (int rc = allow_full_lds<dense_wgrad_persist_kernel<true>>(lds, "dense_wgrad_persist_kernel")) return rc;
+  if (int rc = allow_full_lds<dense_wgrad_persist_kernel<false>>(lds, "dense_wgrad_persist_kernel")) return rc;
   const bool vec = (din % 4 == 0) && (dout % 4 == 0) && (x_ld % 4 == 0) && (dy_ld % 4 == 0) && aligned16(x) && aligned16(dy);
   dim3 grid((unsigned)nblocks, (unsigned)((din + 63) / 64), (unsigned)((dout + 63) / 64));
   hipLaunchKernelGGL(vec ? dense_wgrad_persist_kernel<true> : dense_wgrad_persist_kernel<false>, grid, dim3(64 * P_WAVES), lds, s,

@@ -2068,12 +2068,6 @@ static bool fused_shape_ok(int n, int din, int dout, int max_nnz) {
          fused_wpb(bwd_slice(max_nnz), FD * FD * 4) >= 4;
 }
 
-template <typename K>
-static void allow_big_lds(K kernel) {
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-}
-
 // f(std::integral_constant<int, v>{}) for v = 0, 1, 2: a run-time adjacency layout (lay_of) or tile movement mode as the
 // template argument of the kernel to launch
 template <typename F>
@@ -2175,30 +2169,26 @@ extern "C" int kgcn_graphconv_fwd_f32(const kgcn_csr_batch* a, const float* x, c
   const int wpb = fused_wpb(per, shared);
   const size_t lds = shared + (size_t)wpb * per;
   const int tiles = (a->num_graphs + pack - 1) / pack;
-  static thread_local bool attr_set = false;
-  if (!attr_set) {
-    allow_big_lds(graphconv_fwd_full_kernel<LAY_PAD4>);
-    allow_big_lds(graphconv_fwd_full_kernel<LAY_UNIT>);
-    allow_big_lds(graphconv_fwd_full_kernel<LAY_VALS>);
-    allow_big_lds(graphconv_fwd_kernel<2>);
-    allow_big_lds(graphconv_fwd_kernel<1>);
-    allow_big_lds(graphconv_fwd_kernel<0>);
-    attr_set = true;
-  }
   const dim3 grid(fused_grid(tiles, wpb)), block(64 * wpb);
   const int2* cv = reinterpret_cast<const int2*>(a->cv);
   const int lay = lay_of(a);
   const float* cvals = compact_values(a);
+  int rc = 0;
   if (full_shape)
     with_const3(lay, [&](auto L) {
-      hipLaunchKernelGGL(graphconv_fwd_full_kernel<decltype(L)::value>, grid, block, lds, as_stream(stream), a->slots,
-                         a->graph_ptr, cv, cvals, x, w, bias, out, a->num_graphs, a->max_nnz_per_graph);
+      constexpr auto kernel = graphconv_fwd_full_kernel<decltype(L)::value>;
+      if ((rc = allow_full_lds<kernel>(lds, "graphconv_fwd_full_kernel"))) return;
+      hipLaunchKernelGGL(kernel, grid, block, lds, as_stream(stream), a->slots, a->graph_ptr, cv, cvals, x, w, bias, out,
+                         a->num_graphs, a->max_nnz_per_graph);
     });
   else
     with_const3(mode, [&](auto M) {
-      hipLaunchKernelGGL(graphconv_fwd_kernel<decltype(M)::value>, grid, block, lds, as_stream(stream), a->slots,
-                         a->graph_ptr, cv, x, w, bias, out, a->num_graphs, a->rows, din, dout, a->max_nnz_per_graph, pack);
+      constexpr auto kernel = graphconv_fwd_kernel<decltype(M)::value>;
+      if ((rc = allow_full_lds<kernel>(lds, "graphconv_fwd_kernel"))) return;
+      hipLaunchKernelGGL(kernel, grid, block, lds, as_stream(stream), a->slots, a->graph_ptr, cv, x, w, bias, out, a->num_graphs,
+                         a->rows, din, dout, a->max_nnz_per_graph, pack);
     });
+  if (rc) return rc;
   return check_launch("graphconv_fwd_kernel");
 }
 
@@ -2248,40 +2238,33 @@ extern "C" int kgcn_graphconv_bwd_f32(const kgcn_csr_batch* at, const float* x, 
   float* part_dw = static_cast<float*>(workspace);
   float* part_db = part_dw + (long)blocks * din * dout;
   const size_t lds = full ? full_lds : FD * FD * 4 + (size_t)wpb * per;
-  static thread_local bool attr_set = false;
-  if (!attr_set) {
-    allow_big_lds(graphconv_bwd_planes_kernel);
-    allow_big_lds(graphconv_bwd_pairs_kernel<LAY_PAD4, false>);
-    allow_big_lds(graphconv_bwd_pairs_kernel<LAY_UNIT, false>);
-    allow_big_lds(graphconv_bwd_pairs_kernel<LAY_VALS, false>);
-    allow_big_lds(graphconv_bwd_pairs_kernel<LAY_PAD4, true>);
-    allow_big_lds(graphconv_bwd_pairs_kernel<LAY_UNIT, true>);
-    allow_big_lds(graphconv_bwd_pairs_kernel<LAY_VALS, true>);
-    allow_big_lds(graphconv_bwd_kernel<2>);
-    allow_big_lds(graphconv_bwd_kernel<1>);
-    allow_big_lds(graphconv_bwd_kernel<0>);
-    attr_set = true;
-  }
   const int2* cv = reinterpret_cast<const int2*>(at->cv);
   const int lay = lay_of(at);
   const float* cvals = compact_values(at);
+  int rc = 0;
   if (pairs)
     with_const3(lay, [&](auto L) {
-      auto kernel = bwd_streams(at->num_graphs) ? graphconv_bwd_pairs_kernel<decltype(L)::value, true>
-                                                : graphconv_bwd_pairs_kernel<decltype(L)::value, false>;
-      hipLaunchKernelGGL(kernel, dim3(blocks), dim3(512), lds, s, at->slots, at->graph_ptr, cv, cvals, x, w, dout_grad, dx,
-                         part_dw, part_db, at->num_graphs, at->max_nnz_per_graph);
+      auto go = [&](auto streams) {
+        constexpr auto kernel = graphconv_bwd_pairs_kernel<decltype(L)::value, decltype(streams)::value>;
+        if ((rc = allow_full_lds<kernel>(lds, "graphconv_bwd_pairs_kernel"))) return;
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(512), lds, s, at->slots, at->graph_ptr, cv, cvals, x, w, dout_grad, dx,
+                           part_dw, part_db, at->num_graphs, at->max_nnz_per_graph);
+      };
+      if (bwd_streams(at->num_graphs)) go(std::true_type{}); else go(std::false_type{});
     });
-  else if (full)
+  else if (full) {
+    if ((rc = allow_full_lds<graphconv_bwd_planes_kernel>(lds, "graphconv_bwd_planes_kernel"))) return rc;
     hipLaunchKernelGGL(graphconv_bwd_planes_kernel, dim3(blocks), dim3(64 * wpb), lds, s, at->slots,
                        at->graph_ptr, cv, x, w, dout_grad, dx, part_dw, part_db, at->num_graphs,
                        at->max_nnz_per_graph);
-  else
+  } else
     with_const3(mode, [&](auto M) {
-      hipLaunchKernelGGL(graphconv_bwd_kernel<decltype(M)::value>, dim3(blocks), dim3(64 * wpb), lds, s, at->slots,
-                         at->graph_ptr, cv, x, w, dout_grad, dx, part_dw, part_db, at->num_graphs, at->rows, din, dout,
-                         at->max_nnz_per_graph, pack);
+      constexpr auto kernel = graphconv_bwd_kernel<decltype(M)::value>;
+      if ((rc = allow_full_lds<kernel>(lds, "graphconv_bwd_kernel"))) return;
+      hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64 * wpb), lds, s, at->slots, at->graph_ptr, cv, x, w, dout_grad, dx, part_dw,
+                         part_db, at->num_graphs, at->rows, din, dout, at->max_nnz_per_graph, pack);
     });
-  if (int rc = check_launch("graphconv_bwd_kernel")) return rc;
+  if (rc) return rc;
+  if ((rc = check_launch("graphconv_bwd_kernel"))) return rc;
   return launch_reduce_pair(part_dw, (long)din * dout, dw, part_db, dout, dbias, blocks, s);      // (queued inside a deferral scope)
 }

@@ -514,14 +514,8 @@ int launch_gemm3_fwd(const float* x, long m, int din, long x_ld, const float* w,
     }
     return check_launch("gemm3_fwd_kernel");
   }
-  static thread_local bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm3_fwd_kernel<true, false, 2>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm3_fwd_kernel<false, false, 2>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    attr_set = true;
-  }
+  if (int rc = allow_full_lds<gemm3_fwd_kernel<true, false, 2>>(0, "gemm3_fwd_kernel")) return rc;
+  if (int rc = allow_full_lds<gemm3_fwd_kernel<false, false, 2>>(0, "gemm3_fwd_kernel")) return rc;
   const long ntiles = (m + G3_BM - 1) / G3_BM;
   const dim3 grid((unsigned)(ntiles < kNumCU ? ntiles : kNumCU), (unsigned)((dout + G3_BN - 1) / G3_BN));
   if (xvec)
@@ -733,14 +727,8 @@ __global__ __launch_bounds__(512, 2) void gemm3_wgrad_kernel(
 
 int launch_gemm3_wgrad(const float* x, long x_ld, const float* dy, long dy_ld, long m, int din, int dout,
                        float* part_dw, float* part_db, int nblocks, hipStream_t s, const float* yact, int act) {
-  static thread_local bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm3_wgrad_kernel<false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm3_wgrad_kernel<true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    attr_set = true;
-  }
+  if (int rc = allow_full_lds<gemm3_wgrad_kernel<false>>(0, "gemm3_wgrad_kernel")) return rc;
+  if (int rc = allow_full_lds<gemm3_wgrad_kernel<true>>(0, "gemm3_wgrad_kernel")) return rc;
   const long nchunks = (m + G3_BK - 1) / G3_BK;
   const long cpb = (nchunks + nblocks - 1) / nblocks;
   const dim3 grid((unsigned)nblocks, (unsigned)((din + G3W_BM - 1) / G3W_BM), (unsigned)((dout + G3_BN - 1) / G3_BN));

@@ -648,15 +648,11 @@ int launch_gemmb(const float* grad, const float* act_out, long m, int din, int d
   const u32x4* tab = static_cast<const u32x4*>(tabh);
   const int bc = pooled_grad ? (grad ? 1 : 2) : 0;
   const int dk = dact == KGCN_ACT_NONE ? 0 : (dact == KGCN_ACT_RELU ? 2 : 1);
+  int refused = 0;
   auto go = [&](auto dkc, auto bcc, auto dotc) {
     constexpr int DKc = decltype(dkc)::value, BCc = decltype(bcc)::value;
     constexpr bool DOTc = decltype(dotc)::value;
-    static thread_local bool attr_set = false;                 // (one flag per instantiation of this lambda)
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemmb_kernel<DKc, BCc, DOTc>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                kLdsBytes);
-      attr_set = true;
-    }
+    if ((refused = allow_full_lds<gemmb_kernel<DKc, BCc, DOTc>>(gb_lds(DOTc), "gemmb_kernel"))) return;
     hipLaunchKernelGGL((gemmb_kernel<DKc, BCc, DOTc>), grid, dim3(512), gb_lds(DOTc), s, base, m, dout, ld, x, din, x_ld, tab, dx, dx_ld,
                        part_dw, part_db, da, niter);
   };
@@ -669,7 +665,7 @@ int launch_gemmb(const float* grad, const float* act_out, long m, int din, int d
   else if (dk == 0) go(I0{}, I0{}, F{});
   else if (dk == 1) { if (bc == 0) go(I1{}, I0{}, F{}); else if (bc == 1) go(I1{}, I1{}, F{}); else go(I1{}, I2{}, F{}); }
   else { if (bc == 0) go(I2{}, I0{}, F{}); else if (bc == 1) go(I2{}, I1{}, F{}); else go(I2{}, I2{}, F{}); }
-  if (check_launch("gemmb_kernel")) return -2;
+  if (refused || check_launch("gemmb_kernel")) return -2;
   return pairs;
 }
 

@@ -422,14 +422,8 @@ bool gemmh_fwd_ok(bool x16, long m, int din, long x_ld, int dout) {
 template <int DK>
 static int gh_fwd_launch(const float* x, long m, int din, long x_ld, const void* tabh, const float* bias, float* y, int dout,
                          long y_ld, int act, const GhDact& da, hipStream_t s) {
-  static thread_local bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemmh_fwd_kernel<DK, 16>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              kLdsBytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemmh_fwd_kernel<DK, 8>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              kLdsBytes);
-    attr_set = true;
-  }
+  if (int rc = allow_full_lds<gemmh_fwd_kernel<DK, 16>>(0, "gemmh_fwd_kernel")) return rc;
+  if (int rc = allow_full_lds<gemmh_fwd_kernel<DK, 8>>(0, "gemmh_fwd_kernel")) return rc;
   const long ntiles = (m + GH_BM - 1) / GH_BM, cap = kNumCU;
   const dim3 grid((unsigned)(ntiles < cap ? ntiles : cap), (unsigned)((dout + 255) / 256));
   if (din > 128)
@@ -1026,12 +1020,7 @@ int launch_gemmh_wgrad(const float* x, long x_ld, const float* dy, long dy_ld, l
                        float* part_db, int nblocks, hipStream_t s, const float* yact, int act) {
   const dim3 grid((unsigned)nblocks, (unsigned)((din + 127) / 128), (unsigned)((dout + 255) / 256));
   if (!(yact && act != KGCN_ACT_NONE)) {
-    static thread_local bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemmh_wgradl_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                kLdsBytes);
-      attr_set = true;
-    }
+    if (int rc = allow_full_lds<gemmh_wgradl_kernel>(0, "gemmh_wgradl_kernel")) return rc;
     const long nfull = m / 32, spb = (nfull + nblocks - 1) / nblocks;
     hipLaunchKernelGGL(gemmh_wgradl_kernel, grid, dim3(512), GWL_LDS, s, x, x_ld, dy, dy_ld, m, din, dout, spb, part_dw, part_db);
     return check_launch("gemmh_wgradl_kernel");

@@ -68,6 +68,24 @@ constexpr int kWave = 64;        // CDNA wavefront
 constexpr int kNumCU = 256;      // MI355X
 constexpr int kLdsBytes = 160 * 1024;
 
+// A launch with more than 64 KB of dynamic LDS has to be allowed per kernel: this raises the kernel's limit to the CU's full
+// 160 KB, once per host thread and kernel instantiation (the flag is per thread: a backward kernel is first launched from
+// autograd's thread).  need: the bytes the launch is about to ask for, refused beyond the CU's LDS.  Returns a status (fail()).
+template <auto Kernel>
+int allow_full_lds(size_t need = 0, const char* who = nullptr) {
+  if (need > (size_t)kLdsBytes)
+    return fail("%s: %zu bytes of LDS needed, %d available", who ? who : "kernel", need, kLdsBytes);
+  static thread_local bool done = false;
+  if (!done) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             kLdsBytes);
+    if (e != hipSuccess)
+      return fail("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize): %s", who ? who : "kernel", hipGetErrorString(e));
+    done = true;
+  }
+  return 0;
+}
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));

@@ -246,14 +246,7 @@ extern "C" int kgcn_kg_ig_f32(const int32_t* indptr, const int32_t* indices, con
     return fail("%s: NULL operand", who);
   if (!aligned16(p)) return fail("%s: p must be 16-byte aligned", who);
   const size_t lds = lds_floats(nodes) * 4;
-  if (lds > (size_t)kLdsBytes) return fail("%s: %zu bytes of LDS needed, %d available", who, lds, kLdsBytes);
-  static bool done = false;
-  if (!done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kg_ig_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       kLdsBytes);
-    if (e != hipSuccess) return fail("hipFuncSetAttribute: %s", hipGetErrorString(e));
-    done = true;
-  }
+  if (int rc = allow_full_lds<kg_ig_kernel>(lds, who)) return rc;
   int grid = groups > 0 ? groups : KGCN_KGIG_GROUPS;
   if (grid > num_targets) grid = num_targets;
   Args a{indptr, indices, values, g1, rowsum, b1, w2, h2, p, scales, weights, targets, node_ig, score, u, nodes, steps, num_targets, mode};

@@ -424,14 +424,8 @@ extern "C" int kgcn_gram_fwd_f32(const float* x, int32_t num_graphs, int32_t n_n
   if (!x || !out) return kgcn::fail("kgcn_gram_fwd_f32: NULL operand");
   const size_t lds = gram_lds(n_nodes, d, false);
   if (lds > (size_t)kgcn::kLdsBytes) return kgcn::fail("kgcn_gram_fwd_f32: graph tile %d x %d does not fit LDS", n_nodes, d);
-  static thread_local bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kgcn::gram_fwd_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kgcn::kLdsBytes);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kgcn::gram_bwd_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kgcn::kLdsBytes);
-    attr_set = true;
-  }
+  if (int rc = kgcn::allow_full_lds<kgcn::gram_fwd_kernel>(0, "gram_fwd_kernel")) return rc;
+  if (int rc = kgcn::allow_full_lds<kgcn::gram_bwd_kernel>(0, "gram_bwd_kernel")) return rc;
   const int blocks = num_graphs < 2048 ? num_graphs : 2048;
   hipLaunchKernelGGL(kgcn::gram_fwd_kernel, dim3(blocks), dim3(256), lds, kgcn::as_stream(stream), x, w, out, num_graphs,
                      n_nodes, d);
@@ -455,12 +449,7 @@ extern "C" int kgcn_gram_bwd_f32(const float* x, int32_t num_graphs, int32_t n_n
   if (dw && (!workspace || workspace_bytes < (int64_t)blocks * d * 4))
     return kgcn::fail("kgcn_gram_bwd_f32: workspace %lld < %lld bytes", (long long)workspace_bytes,
                       (long long)blocks * d * 4);
-  static thread_local bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kgcn::gram_bwd_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kgcn::kLdsBytes);
-    attr_set = true;
-  }
+  if (int rc = kgcn::allow_full_lds<kgcn::gram_bwd_kernel>(0, "gram_bwd_kernel")) return rc;
   float* part = dw ? static_cast<float*>(workspace) : nullptr;
   hipLaunchKernelGGL(kgcn::gram_bwd_kernel, dim3(blocks), dim3(256), lds, s, x, w, dout_grad, dx, part, num_graphs,
                      n_nodes, d, beta);

@@ -253,12 +253,7 @@ int launch_narrow_fwd(const float* x, long m, int din, const float* w, long w_ld
   const int kh = (din + 1) / 2;
   const int tile_floats = 32 * (din > dout ? din : dout) + 64;   // x tile, then y tile (+ pad, see NR_TILE); 16-byte multiple
   const size_t lds = ((size_t)2 * kh * 64 + (size_t)NR_WAVES * tile_floats) * 4;
-  static thread_local bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(narrow_fwd_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    attr_set = true;
-  }
+  if (int rc = allow_full_lds<narrow_fwd_kernel>(0, "narrow_fwd_kernel")) return rc;
   const long tiles = (m + 31) / 32;
   long blocks = (tiles + NR_WAVES - 1) / NR_WAVES;
 #ifdef NR_WPE4
@@ -281,12 +276,7 @@ int launch_narrow_wgrad(const float* x, const float* dy, long m, int din, int do
                         int nblocks, hipStream_t s) {
   const size_t tiles_b = (size_t)NR_WAVES * 2 * NR_TILE * 4, park_b = (size_t)NR_WAVES * (64 * 64 + 64) * 4;
   const size_t lds = tiles_b > park_b ? tiles_b : park_b;
-  static thread_local bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(narrow_wgrad_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    attr_set = true;
-  }
+  if (int rc = allow_full_lds<narrow_wgrad_kernel>(0, "narrow_wgrad_kernel")) return rc;
   hipLaunchKernelGGL(narrow_wgrad_kernel, dim3((unsigned)nblocks), dim3(64 * NR_WAVES), lds, s, x, dy, m, din, dout,
                      part_dw, part_db);
   return check_launch("narrow_wgrad_kernel");

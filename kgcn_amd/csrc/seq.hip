@@ -265,19 +265,6 @@ size_t convpool_bwd_lds(const ConvArgs& a, bool table_in_lds) {
 }
 int convpool_bwd_grid(const ConvArgs& a) { return (int)(a.tiles < kConvGridBwd ? (a.tiles > 0 ? a.tiles : 1) : kConvGridBwd); }
 
-// every kernel here takes its LDS dynamically: allow the whole 160 KB once per kernel (a host call, never inside a capture twice)
-template <auto Fn>
-int allow_lds(size_t bytes) {
-  static bool done = false;
-  if (bytes > (size_t)kLdsBytes) return fail("seq kernels: %zu bytes of LDS needed, %d available", bytes, kLdsBytes);
-  if (!done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Fn), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-    if (e != hipSuccess) return fail("hipFuncSetAttribute: %s", hipGetErrorString(e));
-    done = true;
-  }
-  return 0;
-}
-
 // ---- integrated gradients of the sequence input ---------------------------------------------------------------------------
 // Gradient with respect to the (scaled) embedded input of the conv-pool, summed over the rep copies of a compound:
 //   dx[c, m, e] = sum_r wt[c rep + r] sum_dk sum_f G_r[m + padL - dk, f] W[dk, e, f]   (times table[tok[c, m], e] if asked)
@@ -650,7 +637,7 @@ extern "C" int kgcn_seq_convpool_fwd_f32(const int32_t* tokens, int32_t batch, i
   if (a.tiles == 0) return 0;
   if (!bias || !out) return fail("%s: NULL operand", who);
   const size_t lds = convpool_fwd_lds(a);
-  if (int rc = allow_lds<convpool_fwd_kernel<false>>(lds)) return rc;
+  if (int rc = allow_full_lds<convpool_fwd_kernel<false>>(lds, "seq kernels")) return rc;
   const int grid = (int)(a.tiles < kConvGridFwd ? a.tiles : kConvGridFwd);
   hipLaunchKernelGGL(convpool_fwd_kernel<false>, dim3(grid), dim3(256), lds, as_stream(stream), a, bias, out, argmax);
   return check_launch("convpool_fwd_kernel");
@@ -679,10 +666,10 @@ extern "C" int kgcn_seq_convpool_bwd_f32(const int32_t* tokens, int32_t batch, i
     const bool in_lds = convpool_bwd_lds(a, true) <= (size_t)kLdsBytes;
     const size_t lds = convpool_bwd_lds(a, in_lds);
     if (in_lds) {
-      if (int rc = allow_lds<convpool_bwd_kernel<true>>(lds)) return rc;
+      if (int rc = allow_full_lds<convpool_bwd_kernel<true>>(lds, "seq kernels")) return rc;
       hipLaunchKernelGGL(convpool_bwd_kernel<true>, dim3(grid), dim3(256), lds, s, a, dout, argmax, part_w, part_b, part_t);
     } else {
-      if (int rc = allow_lds<convpool_bwd_kernel<false>>(lds)) return rc;
+      if (int rc = allow_full_lds<convpool_bwd_kernel<false>>(lds, "seq kernels")) return rc;
       hipLaunchKernelGGL(convpool_bwd_kernel<false>, dim3(grid), dim3(256), lds, s, a, dout, argmax, part_w, part_b, part_t);
     }
     if (int rc = check_launch("convpool_bwd_kernel")) return rc;
@@ -704,7 +691,7 @@ extern "C" int kgcn_seq_convpool_scaled_fwd_f32(const int32_t* tokens, int32_t b
   if (!bias || !out || !scale) return fail("%s: NULL operand", who);
   a.scale = scale; a.rep = rep;
   const size_t lds = convpool_fwd_lds(a);
-  if (int rc = allow_lds<convpool_fwd_kernel<true>>(lds)) return rc;
+  if (int rc = allow_full_lds<convpool_fwd_kernel<true>>(lds, "seq kernels")) return rc;
   const int grid = (int)(a.tiles < kConvGridFwd ? a.tiles : kConvGridFwd);
   hipLaunchKernelGGL(convpool_fwd_kernel<true>, dim3(grid), dim3(256), lds, as_stream(stream), a, bias, out, argmax);
   return check_launch("convpool_fwd_kernel<scaled>");
@@ -722,7 +709,7 @@ extern "C" int kgcn_seq_convpool_input_grad_f32(const int32_t* tokens, int32_t b
   if (!dx || (a.T > 0 && (!dout || !argmax))) return fail("%s: NULL operand", who);
   a.rep = rep;
   const size_t lds = convpool_input_grad_lds(a);
-  if (int rc = allow_lds<convpool_input_grad_kernel>(lds)) return rc;
+  if (int rc = allow_full_lds<convpool_input_grad_kernel>(lds, "seq kernels")) return rc;
   hipLaunchKernelGGL(convpool_input_grad_kernel, dim3(batch / rep, (length + kIgPos - 1) / kIgPos), dim3(256), lds,
                      as_stream(stream), a, dout, argmax, row_weight, times_table ? 1 : 0, dx);
   return check_launch("convpool_input_grad_kernel");
@@ -746,7 +733,7 @@ extern "C" int kgcn_seq_lstm_fwd_f32(const float* x, int32_t batch, int32_t step
   if (batch == 0) return 0;
   if (!h_out || h_ld < units) return fail("%s: output NULL or its row stride %lld < %d", who, (long long)h_ld, units);
   const size_t lds = ((size_t)4 * a.Hp * a.wstride + 2 * (size_t)a.seqs * a.KA4) * 4;
-  if (int rc = allow_lds<lstm_fwd_kernel>(lds)) return rc;
+  if (int rc = allow_full_lds<lstm_fwd_kernel>(lds, "seq kernels")) return rc;
   hipLaunchKernelGGL(lstm_fwd_kernel, dim3((batch + a.seqs - 1) / a.seqs), dim3(256), lds, as_stream(stream), a, h_out, (long)h_ld,
                      stash);
   return check_launch("lstm_fwd_kernel");
@@ -765,7 +752,7 @@ extern "C" int kgcn_seq_lstm_bwd_f32(const float* x, int32_t batch, int32_t step
   const int N4 = 4 * units;
   if (batch > 0 && steps > 0) {
     const size_t lds = ((size_t)(in_dim + units + a.seqs) * (N4 + 4) + 2 * (size_t)a.seqs * a.Hp) * 4;
-    if (int rc = allow_lds<lstm_bwd_kernel>(lds)) return rc;
+    if (int rc = allow_full_lds<lstm_bwd_kernel>(lds, "seq kernels")) return rc;
     hipLaunchKernelGGL(lstm_bwd_kernel, dim3((batch + a.seqs - 1) / a.seqs), dim3(256), lds, s, a, dh, (long)dh_ld, stash, dx);
     if (int rc = check_launch("lstm_bwd_kernel")) return rc;
   }

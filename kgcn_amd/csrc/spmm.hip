@@ -6,16 +6,35 @@
 // (~0.7 flop/B): the design goal is to touch every rhs/out byte exactly once with 16-byte
 // coalesced accesses and to keep all irregular (gather) traffic inside LDS.
 //
-// Two kernels:
-//  * spmm_tile_kernel   -- small graphs (the molecular case): ONE WAVE PER GRAPH.  The graph's
-//    rhs block [K x d] is streamed HBM -> LDS with 1 KiB-per-instruction dwordx4 loads, its CSR
-//    slice (rowptr + interleaved col/val pairs) is staged next to it, then 64/LPR rows are
-//    aggregated concurrently (LPR lanes x float4 cover one row), neighbours gathered from LDS
-//    with conflict-free ds_read_b128, and 64/LPR consecutive output rows leave as ONE fully
-//    coalesced dwordx4 store instruction.  A one-wave workgroup needs no cross-wave barrier.
-//  * spmm_gather_kernel -- any shape (big graphs, the block-diagonal [sumN x sumN] matrix of
-//    kgcn/data_util.py:698-845, d not a multiple of 4): classic CSR-vector, LPR lanes per row,
-//    neighbours gathered through L1/L2.
+// Seven aggregation kernels and the adjoint of one of them; WHICH one a call takes is decided in one place, the pure host
+// function spmm_route() (no HIP call, no device pointer followed); launch_spmm_multi() launches its answer, and
+// kgcn_spmm_route_query() reports it (tests/test_spmm_routes.py, tests/test_gpu_spmm_routes.py).  In the order spmm_route asks:
+//  * bconv_loop_kernel   -- two or more channels of small graphs (N <= 64): one wave per graph, one channel's block in LDS
+//    at a time, the rows' sums in registers.  bconv_fanout_kernel is its adjoint (kgcn_bconv_fanout_f32).
+//  * spmm_block_kernel   -- ragged-compact batches (one block-diagonal matrix with a block table): a workgroup stages the
+//    rows of one block of whole molecules once.
+//  * spmm_tile_kernel    -- small graphs (the molecular case): ONE WAVE PER GRAPH (four for tiles beyond 20 KiB).  The
+//    graph's rhs block [K x d] is streamed HBM -> LDS with 1 KiB-per-instruction dwordx4 loads, its CSR slice (rowptr +
+//    interleaved col/val pairs) is staged next to it, then 64/LPR rows are aggregated concurrently (LPR lanes x float4 cover
+//    one row), neighbours gathered from LDS with conflict-free ds_read_b128, and 64/LPR consecutive output rows leave as ONE
+//    fully coalesced dwordx4 store instruction.  Its DOT form adds <grad, x> of GINAggregate's backward to the staging.
+//  * spmm_slices_kernel  -- 17..32-node graphs at d = 64 / 128: the 32-column slices of a graph as the waves of one
+//    workgroup, taken out of the tile route.
+//  * spmm_rows_kernel    -- rows that fit no LDS tile but allow 8- or 16-byte vectors (big graphs, the block-diagonal
+//    [sumN x sumN] matrix of kgcn/data_util.py:698-845): eight (two below 32,768 rows) consecutive rows per lane group.
+//  * spmm_gather_kernel  -- anything else: classic CSR-vector, neighbours gathered through L1/L2.  The rows route takes
+//    every call that allows vectors unless a leading dimension reaches 2^31 floats, so spmm_gather_kernel<4> runs for
+//    such operands only; it stays instantiated because those calls are accepted.  (The rows route also declines 2^31 rows or
+//    more; validate_csr refuses such a batch in every entry point, so only kgcn_spmm_route_query, which validates nothing,
+//    can be told of one.)
+//
+// Compile-time switches whose experiments are settled and which are gone (the code they guarded is unconditional):
+//   KGCN_BCONV_NO_LOOP       round 6: all channels staged by spmm_tile_kernel instead of the channel loop (0.33 of the HBM peak at
+//                            six channels of 32 x 64, see bconv_loop_kernel; tools/bconv_bench.py, profiles/r06y_bconv_c6.jsonl)
+//   SPB_SLICE32              round 4: 32- instead of 64-column slices in the block kernel: 67.3 / 91.9 us against 68-70 / 82-84
+//                            forward / adjoint (profiles/r04_spmm_block.txt)
+//   KGCN_SPMM_NO_SLICE_WAVES round 5: one workgroup per 32-column slice instead of spmm_slices_kernel: traffic x 1.109 against
+//                            x 1.028 of the algorithmic bytes (profiles/r05_headline_experiments.txt)
 #include "kgcn_common.h"
 
 namespace kgcn {
@@ -1024,7 +1043,8 @@ __global__ __launch_bounds__(64) void bconv_fanout_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------
-// host-side dispatch
+// host side.  spmm_route() decides -- from the scalar facts of a call alone -- which of the kernels above runs, with which
+// template arguments, grid and LDS; launch_spmm_multi() launches what it says.  kgcn_spmm_route_query() reports it.
 // ------------------------------------------------------------------------------------------------
 static int ilog2_ceil(int v) {
   int l = 0;
@@ -1032,30 +1052,85 @@ static int ilog2_ceil(int v) {
   return l;
 }
 
+// Grid of the kernels that walk one row per group of 2^lpr_log2 lanes (gather, values_grad, max-pool): as many lanes as the
+// row is wide, at most a wave; one 256-thread workgroup per 256 lanes, at most 64 per CU.  At least one -- which changes nothing:
+// every caller has returned before on an empty batch (T, rows or d of 0; kgcn_graph_maxpool_bwd_f32 also on cols == 0, and its
+// transposed batch's rows are checked to equal those cols), so total_rows >= 1 here.
+struct LaneGrid { int lpr_log2; unsigned blocks; };
+static LaneGrid lane_group_grid(long total_rows, int width) {
+  int lpr_log2 = ilog2_ceil(width);
+  if (lpr_log2 > 6) lpr_log2 = 6;
+  long blocks = ((total_rows << lpr_log2) + 255) / 256;
+  const long max_blocks = (long)kNumCU * 64;
+  if (blocks > max_blocks) blocks = max_blocks;
+  if (blocks < 1) blocks = 1;
+  return {lpr_log2, (unsigned)blocks};
+}
+
+// Floats per lane: 4 (16-byte vectors) when every width / stride OR-ed into `dims` is a multiple of 4 floats and every pointer
+// OR-ed into `ptrs` is 16-byte aligned, else 2 (8-byte) on the same terms, else 0.  Which strides take part is the route's business.
+static int vec_width(long dims, uintptr_t ptrs) {
+  return (dims % 4 == 0 && ptrs % 16 == 0) ? 4 : (dims % 2 == 0 && ptrs % 8 == 0) ? 2 : 0;
+}
+
+// The facts of one call that the route depends on; no device pointer is followed.
+struct SpmmCall {
+  bool fanout;                    // kgcn_bconv_fanout_f32 (out_c = A_c g) instead of an aggregation (out = sum_c A_c rhs_c)
+  int nch, T, M, K, d;            // channels (<= MAX_CH), batch shape of every channel, operand width
+  int max_nnz[MAX_CH];
+  bool has_blocks;                // kgcn_csr_batch.block_ptr of channel 0 ...
+  int num_blocks, block_rows_max;
+  long rhs_ld, rhs_gs, out_ld, out_gs;
+  long cs;                        // channel stride: of rhs in an aggregation, of out in a fan-out
+  unsigned ptr_low;               // low four bits of rhs | out | (dact ? aout : 0): the operands' common alignment
+  bool dact, self_scale, dotx;
+};
+
+struct SpmmRoute {
+  int kernel;                     // KGCN_SPMM_* of include/kgcn_hip.h; KGCN_SPMM_NONE: nothing to launch / fan-out per channel
+  int targ[4];                    // the instantiation's template arguments in declaration order
+  int ds, slices;                 // columns per workgroup, column slices
+  long grid;                      // workgroups
+  int wg;                         // threads per workgroup
+  size_t lds;                     // dynamic LDS bytes
+  int rows_cap, ecap;             // block kernel: rows and entries of a block that the LDS layout behind `lds` holds
+  int lpr_log2;                   // gather kernel: log2 of the lanes per row behind `grid`
+};
+
+static SpmmCall spmm_call(bool fanout, const kgcn_csr_batch* a, int nch, int d, long rhs_ld, long rhs_gs, long cs, long out_ld,
+                          long out_gs, uintptr_t ptrs, bool dact, bool self_scale, bool dotx) {
+  SpmmCall c = {};
+  c.fanout = fanout;
+  c.nch = nch; c.T = a->num_graphs; c.M = a->rows; c.K = a->cols; c.d = d;
+  for (int i = 0; i < nch && i < MAX_CH; ++i) c.max_nnz[i] = a[i].max_nnz_per_graph;
+  c.has_blocks = a->block_ptr != nullptr;
+  c.num_blocks = a->num_blocks; c.block_rows_max = a->block_rows_max;
+  c.rhs_ld = rhs_ld; c.rhs_gs = rhs_gs; c.out_ld = out_ld; c.out_gs = out_gs; c.cs = cs;
+  c.ptr_low = (unsigned)(ptrs & 15u);
+  c.dact = dact; c.self_scale = self_scale; c.dotx = dotx;
+  return c;
+}
+
 // Tile kernel is used when one graph's working set (all channels of the launch) leaves >= 8 waves per CU resident.
 // Can the LDS-staged kernel take this launch, and how?  vec = floats per lane (4, or 2 for even widths), slices = column
 // slices of d/slices floats each (one workgroup per graph and slice) so that a tile stays within 20 KiB (8 waves / CU).
 struct TilePlan { bool ok; int vec; int slices; int nw; };
-static TilePlan tile_plan(const kgcn_csr_batch* a, int nch, const float* rhs, long rhs_ld, long rhs_gs, long rhs_cs,
-                          int d, const float* out, long out_ld, long out_gs, const float* aout, bool whole_rows = false) {
+static TilePlan tile_plan(const SpmmCall& c, long dims, bool whole_rows) {
   TilePlan p = {false, 4, 1, 1};
-  if (d <= 0 || d > 1024 || a->rows <= 0 || a->cols <= 0) return p;
-  const long all = rhs_ld | rhs_gs | out_ld | out_gs | rhs_cs | d;
-  const uintptr_t ptrs = reinterpret_cast<uintptr_t>(rhs) | reinterpret_cast<uintptr_t>(out) |
-                         reinterpret_cast<uintptr_t>(aout);
-  if (all % 4 == 0 && ptrs % 16 == 0) p.vec = 4;
-  else if (all % 2 == 0 && ptrs % 8 == 0) p.vec = 2;
-  else return p;
+  const int d = c.d;
+  if (d <= 0 || d > 1024 || c.M <= 0 || c.K <= 0) return p;
+  p.vec = vec_width(dims, c.ptr_low);
+  if (!p.vec) return p;
   // This kernel lives off occupancy (a wave per graph runs load -> LDS -> gather -> store with nothing overlapped inside it): for
   // 17..32-node graphs 32-column slices (128-byte row segments, the CSR read once per slice) put 31 instead of 17 / 9 workgroups on
   // a CU: d = 64: 0.62 -> 0.645 of the HBM peak, d = 128: 0.56 -> 0.64.  Not a general rule: 10-, 16- and 50-node graphs and
   // 256-wide operands lose 4-25 % with narrower slices (profiles/r03_i_spmm_slices.txt).
-  const int sl0 = (!whole_rows && nch == 1 && p.vec == 4 && a->rows > 16 && a->rows <= 32 && (d == 64 || d == 128)) ? d / 32 : 1;
+  const int sl0 = (!whole_rows && c.nch == 1 && p.vec == 4 && c.M > 16 && c.M <= 32 && (d == 64 || d == 128)) ? d / 32 : 1;
   for (int sl = sl0; sl <= 16; sl *= 2) {
     if (d % sl != 0 || (d / sl) % p.vec != 0 || (sl > 1 && d / sl < 32)) break;
     if (d / sl > 64 * p.vec) continue;                  // one wave covers a row of the slice
     size_t lds = 0;
-    for (int c = 0; c < nch; ++c) lds += tile_chan_bytes(a[c].rows, a[c].cols, d / sl, a[c].max_nnz_per_graph);
+    for (int i = 0; i < c.nch; ++i) lds += tile_chan_bytes(c.M, c.K, d / sl, c.max_nnz[i]);
     if (lds <= 20 * 1024 || (sl == 1 && lds <= 53 * 1024)) {
       p.ok = true;
       p.slices = sl;
@@ -1067,13 +1142,13 @@ static TilePlan tile_plan(const kgcn_csr_batch* a, int nch, const float* rhs, lo
 }
 
 // Channel-loop kernels (bconv_loop_kernel / bconv_fanout_kernel): vec and the column slice ds of one wave (<= 64 vectors per row,
-// the block of ONE channel within 16 KiB, <= 16 block vectors and <= 16 row passes per lane); 0 = not this route.
+// the block of ONE channel within 16 KiB, <= 16 block vectors and <= 16 row passes per lane); vec = 0: not this route.
 struct LoopPlan { int vec, ds, nvl, np; size_t lds; };
-static LoopPlan loop_plan(const kgcn_csr_batch* a, int nch, long ld_all, uintptr_t ptrs, int d) {
+static LoopPlan loop_plan(const SpmmCall& c, long dims) {
   LoopPlan p = {0, 0, 0, 0, 0};
-  const int M = a->rows, K = a->cols;
+  const int M = c.M, K = c.K, d = c.d;
   if (M <= 0 || K <= 0 || M > 64 || K > 64 || d <= 0) return p;
-  const int vec = (ld_all % 4 == 0 && ptrs % 16 == 0) ? 4 : (ld_all % 2 == 0 && ptrs % 8 == 0) ? 2 : 0;
+  const int vec = vec_width(dims, c.ptr_low);
   if (!vec) return p;
   int ds = d;
   while (ds / vec > 64 || (long)K * ds * 4 > 16 * 1024) {     // halve while the halves stay whole vectors of >= 32 columns
@@ -1085,31 +1160,191 @@ static LoopPlan loop_plan(const kgcn_csr_batch* a, int nch, long ld_all, uintptr
   const int nvl = (nv + 63) / 64, np = (M + rpw - 1) / rpw;
   if (nvl > 16 || np > 16) return p;
   int max_nnz = 0;
-  for (int c = 0; c < nch; ++c) max_nnz = a[c].max_nnz_per_graph > max_nnz ? a[c].max_nnz_per_graph : max_nnz;
+  for (int i = 0; i < c.nch; ++i) max_nnz = c.max_nnz[i] > max_nnz ? c.max_nnz[i] : max_nnz;
   p.vec = vec; p.ds = ds; p.nvl = nvl <= 8 ? 8 : 16; p.np = np <= 8 ? 8 : 16;
   p.lds = (((size_t)K * ds * 4 + 15) & ~(size_t)15) + (size_t)max_nnz * 8 + (size_t)(M + 2) * 4;
   if (p.lds > 40 * 1024) p.vec = 0;
   return p;
 }
 
-// out[t] = act(beta*out[t] + sum_c A_c[t] @ (rhs_c[t] (.) act'(aout[t])));  a: nch channel descriptors of one batch shape
-int launch_spmm_multi(const kgcn_csr_batch* a, int nch, const float* rhs, long rhs_ld, long rhs_gs, long rhs_cs, int d,
-                      float* out, long out_ld, long out_gs, float beta, const float* self_scale, int act,
-                      const float* aout, int dact, hipStream_t stream, const float* dotx = nullptr,
-                      float* dot_part = nullptr, bool* dot_done = nullptr) {
-  const int T = a->num_graphs, M = a->rows, K = a->cols;
-  if (T == 0 || M == 0 || d == 0) return 0;
-  if (nch > MAX_CH) {                       // more channels than one launch takes: groups of MAX_CH, accumulate
-    for (int c0 = 0; c0 < nch; c0 += MAX_CH) {
-      const int n = nch - c0 < MAX_CH ? nch - c0 : MAX_CH;
-      const bool last = c0 + n >= nch;      // the activation belongs to the last group only
-      int rc = launch_spmm_multi(a + c0, n, rhs + c0 * rhs_cs, rhs_ld, rhs_gs, rhs_cs, d, out, out_ld, out_gs,
-                                 c0 == 0 ? beta : 1.f, c0 == 0 ? self_scale : nullptr, last ? act : KGCN_ACT_NONE, aout,
-                                 dact, stream);
-      if (rc) return rc;
+static int lanes_per_row(int lanes) { return lanes <= 8 ? 8 : lanes <= 16 ? 16 : lanes <= 32 ? 32 : 64; }
+
+static SpmmRoute spmm_route(const SpmmCall& c) {
+  SpmmRoute r = {};               // KGCN_SPMM_NONE
+  const int T = c.T, M = c.M, K = c.K, d = c.d;
+  if (T == 0 || M == 0 || d == 0 || c.nch > MAX_CH) return r;
+  auto take = [&r](int kernel, int t0, int t1, int t2, int t3, int ds, int slices, long grid, int wg, size_t lds) -> SpmmRoute& {
+    r = {kernel, {t0, t1, t2, t3}, ds, slices, grid, wg, lds, 0, 0, 0};
+    return r;
+  };
+  const long dims = c.rhs_ld | c.rhs_gs | c.out_ld | c.out_gs | c.cs | d;
+  // several channels: one channel's block in LDS at a time, the sums in registers (bconv_loop_kernel); the fan-out is its adjoint
+  if (c.fanout || (c.nch >= 2 && !c.dact && !c.self_scale && !c.dotx)) {
+    const LoopPlan lp = loop_plan(c, dims);
+    if (lp.vec && (long)T * (d / lp.ds) <= 0x7fffffffL) {
+      const int nsl = d / lp.ds;
+      return c.fanout ? take(KGCN_SPMM_BCONV_FANOUT, lp.vec, lp.nvl, 0, 0, lp.ds, nsl, (long)T * nsl, 64, lp.lds)
+                      : take(KGCN_SPMM_BCONV_LOOP, lp.vec, lp.nvl, lp.np, 0, lp.ds, nsl, (long)T * nsl, 64, lp.lds);
     }
-    return 0;
+    if (c.fanout) return r;                               // shapes the channel-loop kernel does not take: one launch per channel
   }
+  // ragged-compact batches with their block structure: every rhs row staged once (spmm_block_kernel)
+  if (c.nch == 1 && T == 1 && c.has_blocks && c.num_blocks > 0 && c.block_rows_max > 0 && !c.dotx) {
+    const int vec = vec_width(c.rhs_ld | c.out_ld | d, c.ptr_low);
+    const int rows_cap = c.block_rows_max < 255 ? c.block_rows_max : 255;      // (one row offset per lane)
+    // slice width: whole rows while the tile stays within 24 KiB (>= 6 workgroups per CU), else 64 / 32 columns
+    int ds = 0;
+    if (vec) {
+      if ((long)rows_cap * d * 4 <= 24 * 1024 && d / vec <= 64) ds = d;
+      else if (vec == 4 && d % 64 == 0 && (long)rows_cap * 64 * 4 <= 40 * 1024) ds = 64;
+      else if (vec == 4 && d % 32 == 0 && (long)rows_cap * 32 * 4 <= 40 * 1024) ds = 32;
+    }
+    if (ds && (long)c.num_blocks * (d / ds) <= 0x7fffffffL) {
+      const int nslices = d / ds;
+      int ecap = rows_cap * 6;
+      if (ecap > SPB_MAXE * 256) ecap = SPB_MAXE * 256;
+      const size_t lds = (((size_t)rows_cap * ds * 4 + 15) & ~(size_t)15) + (size_t)ecap * 8 + (size_t)(rows_cap + 1) * 4;
+      take(KGCN_SPMM_BLOCK, vec, lanes_per_row(ds / vec), c.dact, 0, ds, nslices, (long)c.num_blocks * nslices, 256, lds);
+      r.rows_cap = rows_cap;
+      r.ecap = ecap;
+      return r;
+    }
+  }
+  // small graphs: the graph's rhs block in LDS (the fused <rhs, dotx> needs a graph's whole rows in one workgroup)
+  const TilePlan plan = tile_plan(c, dims, c.dotx);
+  if (plan.ok && (long)T * plan.slices <= 0x7fffffffL) {
+    const int ds = d / plan.slices;
+    if (c.nch == 1 && plan.vec == 4 && ds == 32 && plan.nw == 1 && (plan.slices == 2 || plan.slices == 4) && !c.dotx) {
+      // the slices of a graph as the waves of one workgroup: its CSR staged once (spmm_slices_kernel).  The tile plan budgets
+      // its LDS per SLICE workgroup; this kernel holds all slices of the graph in one: beyond the 64 KiB a launch gets without
+      // an attribute (K around 121..150 at d = 128) the slice-per-workgroup kernel runs instead
+      const size_t lds2 = (size_t)plan.slices * K * 32 * 4 + (size_t)c.max_nnz[0] * 8 + (size_t)(M + 1) * 4;
+      if (lds2 <= 64 * 1024) return take(KGCN_SPMM_SLICES, plan.slices, 0, 0, 0, 32, plan.slices, T, 64 * plan.slices, lds2);
+    }
+    size_t lds = 0;
+    for (int i = 0; i < c.nch; ++i) lds += tile_chan_bytes(M, K, ds, c.max_nnz[i]);
+    // <rhs, dotx> of every graph rides in the staging of channel 0 (one partial per workgroup = per graph)
+    const bool dot = c.dotx && plan.vec == 4 && plan.slices == 1 && c.rhs_ld == ds && !c.dact;
+    return take(dot ? KGCN_SPMM_TILE_DOT : KGCN_SPMM_TILE, lanes_per_row(ds / plan.vec), plan.vec, plan.nw, dot, ds, plan.slices,
+                (long)T * plan.slices, 64 * plan.nw, lds);
+  }
+  // rows that do not fit an LDS tile: the row-chunk kernel when 8- or 16-byte vectors are possible
+  const long total_rows = (long)T * M;
+  const int vec = vec_width(dims, c.ptr_low);
+  if (vec && total_rows < (1L << 31) && c.rhs_ld < (1L << 31) && c.out_ld < (1L << 31)) {
+    const int lanes = d / vec;
+    const int lpr = lanes <= 16 ? 16 : (lanes <= 32 ? 32 : 64);
+    const int rows_per_group = total_rows >= 32768 ? 8 : 2;
+    const long rows_per_block = (long)(256 / lpr) * rows_per_group;
+    const long nblocks = (total_rows + rows_per_block - 1) / rows_per_block;
+    return take(KGCN_SPMM_ROWS, vec, lpr, c.dact, rows_per_group, d, 1, (nblocks + 7) / 8 * 8, 256, 0);    // whole XCD rounds
+  }
+  // anything else: one row per lane group, neighbours through L1 / L2
+  const int gvec = vec == 4 ? 4 : 1;
+  const LaneGrid g = lane_group_grid(total_rows, d / gvec);
+  take(KGCN_SPMM_GATHER, gvec, 0, 0, 0, d, 1, g.blocks, 256, 0).lpr_log2 = g.lpr_log2;
+  return r;
+}
+
+// f(std::integral_constant<int, V>{}) for the V among Vs that equals v: a run-time choice as a template argument.  Returns what
+// f returned (the launchers' lambdas: true once they launched), false when v is none of Vs.
+template <int... Vs, typename F>
+static bool with_const(int v, F&& f) {
+  return ((v == Vs && f(std::integral_constant<int, Vs>{})) || ...);
+}
+// a launcher's status: the route named an instantiation this file does not have (an error, never a silent no-op), else the launch's
+static int launched(bool matched, const char* what) {
+  return matched ? check_launch(what) : fail("%s: the route names an instantiation that does not exist", what);
+}
+
+// What the kernels of one launch read and write (launch_spmm_multi's arguments past the channel descriptors).
+struct SpmmOperands {
+  const float* rhs; long rhs_ld, rhs_gs;
+  float* out; long out_ld, out_gs;
+  float beta; const float* self_scale; int act;
+  const float* aout; int dact;
+  const float* dotx; float* dot_part;
+};
+
+static int launch_bconv_loop(const SpmmRoute& r, const SpmmChannels& ch, const SpmmOperands& o, int M, int K, hipStream_t s) {
+  const bool ok = with_const<4, 2>(r.targ[0], [&](auto vec) { return with_const<8, 16>(r.targ[1], [&](auto nvl) {
+  return with_const<8, 16>(r.targ[2], [&](auto np) {
+    constexpr auto kernel = bconv_loop_kernel<decltype(vec)::value, decltype(nvl)::value, decltype(np)::value>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)r.grid), dim3(r.wg), r.lds, s, ch, o.rhs, o.rhs_ld, o.rhs_gs, o.out, o.out_ld, o.out_gs,
+                       M, K, r.ds, r.slices, o.beta, o.act);
+    return true;
+  }); }); });
+  return launched(ok, "bconv_loop_kernel");
+}
+
+static int launch_block(const SpmmRoute& r, const kgcn_csr_batch* a, const SpmmOperands& o, hipStream_t s) {
+  const bool ok = with_const<4, 2>(r.targ[0], [&](auto vec) { return with_const<8, 16, 32, 64>(r.targ[1], [&](auto lpr) {
+  return with_const<0, 1>(r.targ[2], [&](auto da) {
+    constexpr auto kernel = spmm_block_kernel<decltype(vec)::value, decltype(lpr)::value, decltype(da)::value != 0>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)r.grid), dim3(r.wg), r.lds, s, a->rowptr, reinterpret_cast<const int2*>(a->cv),
+                       a->block_ptr, (int)r.grid, r.slices, r.ds, r.rows_cap, r.ecap, o.rhs, o.rhs_ld, o.out, o.out_ld, o.beta,
+                       o.self_scale, o.act, o.aout, o.dact);
+    return true;
+  }); }); });
+  return launched(ok, "spmm_block_kernel");
+}
+
+static int launch_slices(const SpmmRoute& r, const kgcn_csr_batch* a, const SpmmOperands& o, hipStream_t s) {
+  const bool ok = with_const<2, 4>(r.targ[0], [&](auto ns) {
+    hipLaunchKernelGGL(spmm_slices_kernel<decltype(ns)::value>, dim3((unsigned)r.grid), dim3(r.wg), r.lds, s, a->rowptr,
+                       reinterpret_cast<const int2*>(a->cv), a->max_nnz_per_graph, o.rhs, o.rhs_ld, o.rhs_gs, o.out, o.out_ld, o.out_gs,
+                       a->rows, a->cols, o.beta, o.self_scale, o.act, o.aout, o.dact);
+    return true;
+  });
+  return launched(ok, "spmm_slices_kernel");
+}
+
+// DOT: spmm_tile_kernel<LPR, 4, NW, true> with dotx / dot_part.  The four-wave instantiations hold tiles beyond 64 KB.
+template <bool DOT>
+static int launch_tile(const SpmmRoute& r, const SpmmChannels& ch, const SpmmOperands& o, int M, int K, hipStream_t s) {
+  int rc = 0;
+  auto go = [&](auto lpr, auto vec, auto nw) {
+    constexpr auto kernel = spmm_tile_kernel<decltype(lpr)::value, decltype(vec)::value, decltype(nw)::value, DOT>;
+    if constexpr (decltype(nw)::value == 4) {
+      if ((rc = allow_full_lds<kernel>(r.lds, "spmm_tile_kernel"))) return true;      // (matched; rc carries the refusal)
+    }
+    hipLaunchKernelGGL(kernel, dim3((unsigned)r.grid), dim3(r.wg), r.lds, s, ch, o.rhs, o.rhs_ld, o.rhs_gs, o.out, o.out_ld, o.out_gs,
+                       M, K, r.ds, r.slices, o.beta, o.self_scale, o.act, o.aout, o.dact, DOT ? o.dotx : nullptr,
+                       DOT ? o.dot_part : nullptr);
+    return true;
+  };
+  const bool ok = with_const<8, 16, 32, 64>(r.targ[0], [&](auto lpr) { return with_const<1, 4>(r.targ[2], [&](auto nw) {
+    if constexpr (DOT) return go(lpr, std::integral_constant<int, 4>{}, nw);
+    else return with_const<4, 2>(r.targ[1], [&](auto vec) { return go(lpr, vec, nw); });
+  }); });
+  if (rc) return rc;
+  return launched(ok, DOT ? "spmm_tile_kernel<dot>" : "spmm_tile_kernel");
+}
+
+static int launch_rows(const SpmmRoute& r, const SpmmChannels& ch, const SpmmOperands& o, int M, long total_rows, int d,
+                       hipStream_t s) {
+  const bool ok = with_const<4, 2>(r.targ[0], [&](auto vec) { return with_const<16, 32, 64>(r.targ[1], [&](auto lpr) {
+  return with_const<0, 1>(r.targ[2], [&](auto da) { return with_const<8, 2>(r.targ[3], [&](auto rows) {
+    constexpr auto kernel =
+        spmm_rows_kernel<decltype(vec)::value, decltype(lpr)::value, decltype(da)::value != 0, decltype(rows)::value>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)r.grid), dim3(r.wg), 0, s, ch, o.rhs, (int)o.rhs_ld, o.rhs_gs, o.out, (int)o.out_ld,
+                       o.out_gs, M, total_rows, d, o.beta, o.self_scale, o.act, o.aout, o.dact, (int)(r.grid / 8));  // blocks per XCD
+    return true;
+  }); }); }); });
+  return launched(ok, "spmm_rows_kernel");
+}
+
+static int launch_gather(const SpmmRoute& r, const SpmmChannels& ch, const SpmmOperands& o, int M, long total_rows, int d,
+                         hipStream_t s) {
+  const bool ok = with_const<4, 1>(r.targ[0], [&](auto vec) {
+    hipLaunchKernelGGL(spmm_gather_kernel<decltype(vec)::value>, dim3((unsigned)r.grid), dim3(r.wg), 0, s, ch, o.rhs, o.rhs_ld,
+                       o.rhs_gs, o.out, o.out_ld, o.out_gs, M, total_rows, d, r.lpr_log2, o.beta, o.self_scale, o.act, o.aout, o.dact);
+    return true;
+  });
+  return launched(ok, "spmm_gather_kernel");
+}
+
+static SpmmChannels spmm_channels(const kgcn_csr_batch* a, int nch, long rhs_cs) {
   SpmmChannels ch;
   ch.n = nch;
   ch.rhs_cs = rhs_cs;
@@ -1118,223 +1353,90 @@ int launch_spmm_multi(const kgcn_csr_batch* a, int nch, const float* rhs, long r
     ch.cv[c] = reinterpret_cast<const int2*>(a[c].cv);
     ch.max_nnz[c] = a[c].max_nnz_per_graph;
   }
-#ifndef KGCN_BCONV_NO_LOOP
-  if (nch >= 2 && dact == KGCN_ACT_NONE && !self_scale && !dotx) {
-    // several channels: one channel's block in LDS at a time, the sums in registers (bconv_loop_kernel)
-    const LoopPlan lp = loop_plan(a, nch, rhs_ld | rhs_gs | out_ld | out_gs | rhs_cs | d,
-                                  reinterpret_cast<uintptr_t>(rhs) | reinterpret_cast<uintptr_t>(out), d);
-    if (lp.vec && (long)T * (d / lp.ds) <= 0x7fffffffL) {
-      const int nsl = d / lp.ds;
-      const dim3 grid((unsigned)(T * nsl));
-#define KGCN_LOOP(VEC, NVL, NP)                                                                                            \
-  hipLaunchKernelGGL((bconv_loop_kernel<VEC, NVL, NP>), grid, dim3(64), lp.lds, stream, ch, rhs, rhs_ld, rhs_gs, out, out_ld, \
-                     out_gs, M, K, lp.ds, nsl, beta, act)
-      if (lp.vec == 4) {
-        if (lp.nvl == 8 && lp.np == 8) KGCN_LOOP(4, 8, 8); else if (lp.nvl == 8) KGCN_LOOP(4, 8, 16);
-        else if (lp.np == 8) KGCN_LOOP(4, 16, 8); else KGCN_LOOP(4, 16, 16);
-      } else {
-        if (lp.nvl == 8 && lp.np == 8) KGCN_LOOP(2, 8, 8); else if (lp.nvl == 8) KGCN_LOOP(2, 8, 16);
-        else if (lp.np == 8) KGCN_LOOP(2, 16, 8); else KGCN_LOOP(2, 16, 16);
-      }
-#undef KGCN_LOOP
-      return check_launch("bconv_loop_kernel");
-    }
-  }
-#endif
-  // ragged-compact batches with their block structure: every rhs row staged once (spmm_block_kernel)
-  if (nch == 1 && T == 1 && a->block_ptr && a->num_blocks > 0 && a->block_rows_max > 0 && !dotx) {
-    const long all = rhs_ld | out_ld | d;
-    const uintptr_t ptrs = reinterpret_cast<uintptr_t>(rhs) | reinterpret_cast<uintptr_t>(out) |
-                           (dact ? reinterpret_cast<uintptr_t>(aout) : 0);
-    const int vec = (all % 4 == 0 && ptrs % 16 == 0) ? 4 : (all % 2 == 0 && ptrs % 8 == 0) ? 2 : 0;
-    const int rows_cap = a->block_rows_max < 255 ? a->block_rows_max : 255;      // (one row offset per lane)
-    // slice width: whole rows while the tile stays within 24 KiB (>= 6 workgroups per CU), else 64 / 32 columns
-    int ds = 0;
-    if (vec) {
-      if ((long)rows_cap * d * 4 <= 24 * 1024 && d / vec <= 64) ds = d;
-#ifndef SPB_SLICE32
-      else if (vec == 4 && d % 64 == 0 && (long)rows_cap * 64 * 4 <= 40 * 1024) ds = 64;
-#endif
-      else if (vec == 4 && d % 32 == 0 && (long)rows_cap * 32 * 4 <= 40 * 1024) ds = 32;
-    }
-    if (ds && (long)a->num_blocks * (d / ds) <= 0x7fffffffL) {
-      const int nslices = d / ds, dv = ds / vec;
-      int ecap = rows_cap * 6;
-      if (ecap > SPB_MAXE * 256) ecap = SPB_MAXE * 256;
-      const size_t lds = (((size_t)rows_cap * ds * 4 + 15) & ~(size_t)15) + (size_t)ecap * 8 +
-                         (size_t)(rows_cap + 1) * 4;
-      const int nitems = a->num_blocks * nslices;
-      const dim3 grid((unsigned)nitems);
-#define KGCN_BLK2(VEC, LPR, DACT)                                                                                       \
-  hipLaunchKernelGGL((spmm_block_kernel<VEC, LPR, DACT>), grid, dim3(256), lds, stream, a->rowptr,                       \
-                     reinterpret_cast<const int2*>(a->cv), a->block_ptr, nitems, nslices, ds, rows_cap, ecap, rhs, rhs_ld, out, \
-                     out_ld, beta, self_scale, act, aout, dact)
-#define KGCN_BLK(VEC, LPR)                                                                                              \
-  {                                                                                                                     \
-    if (dact != KGCN_ACT_NONE) KGCN_BLK2(VEC, LPR, true); else KGCN_BLK2(VEC, LPR, false);                              \
-  }
-      if (vec == 4) {
-        if (dv <= 8) KGCN_BLK(4, 8) else if (dv <= 16) KGCN_BLK(4, 16) else if (dv <= 32) KGCN_BLK(4, 32) else KGCN_BLK(4, 64)
-      } else {
-        if (dv <= 8) KGCN_BLK(2, 8) else if (dv <= 16) KGCN_BLK(2, 16) else if (dv <= 32) KGCN_BLK(2, 32) else KGCN_BLK(2, 64)
-      }
-#undef KGCN_BLK
-#undef KGCN_BLK2
-      return check_launch("spmm_block_kernel");
-    }
-  }
-  const TilePlan plan = tile_plan(a, nch, rhs, rhs_ld, rhs_gs, rhs_cs, d, out, out_ld, out_gs, dact ? aout : nullptr,
-                                  dotx != nullptr);      // the fused <rhs, dotx> needs a graph's whole rows in one workgroup
-  if (plan.ok && (long)T * plan.slices <= 0x7fffffffL) {
-    const int ds = d / plan.slices;
-#ifndef KGCN_SPMM_NO_SLICE_WAVES
-    if (nch == 1 && plan.vec == 4 && ds == 32 && plan.nw == 1 && (plan.slices == 2 || plan.slices == 4) && !dotx) {
-      // the slices of a graph as the waves of one workgroup: its CSR staged once (spmm_slices_kernel)
-      const size_t lds2 = (size_t)plan.slices * K * 32 * 4 + (size_t)a->max_nnz_per_graph * 8 + (size_t)(M + 1) * 4;
-      const int2* cvp = reinterpret_cast<const int2*>(a->cv);
-      // the tile plan budgets its LDS per SLICE workgroup; this kernel holds all slices of the graph in one: beyond the
-      // 64 KiB a launch gets without an attribute (K around 121..150 at d = 128) the slice-per-workgroup kernel runs instead
-      if (lds2 > 64 * 1024) goto tile_route;
-      if (plan.slices == 2)
-        hipLaunchKernelGGL(spmm_slices_kernel<2>, dim3((unsigned)T), dim3(128), lds2, stream, a->rowptr, cvp, a->max_nnz_per_graph, rhs,
-                           rhs_ld, rhs_gs, out, out_ld, out_gs, M, K, beta, self_scale, act, aout, dact);
-      else
-        hipLaunchKernelGGL(spmm_slices_kernel<4>, dim3((unsigned)T), dim3(256), lds2, stream, a->rowptr, cvp, a->max_nnz_per_graph, rhs,
-                           rhs_ld, rhs_gs, out, out_ld, out_gs, M, K, beta, self_scale, act, aout, dact);
-      return check_launch("spmm_slices_kernel");
-    }
-  tile_route:
-#endif
-    size_t lds = 0;
-    for (int c = 0; c < nch; ++c) lds += tile_chan_bytes(M, K, ds, a[c].max_nnz_per_graph);
-    const int lanes = ds / plan.vec;
-    const dim3 grid((unsigned)(T * plan.slices));
-    if (dotx && dot_part && dot_done && plan.vec == 4 && plan.slices == 1 && rhs_ld == ds && dact == KGCN_ACT_NONE) {
-      // <rhs, dotx> of every graph rides in the staging of channel 0 (one partial per workgroup = per graph)
-#define KGCN_TILE_DOT2(LPR, NW)                                                                                       \
-  hipLaunchKernelGGL((spmm_tile_kernel<LPR, 4, NW, true>), grid, dim3(64 * NW), lds, stream, ch, rhs, rhs_ld, rhs_gs, \
-                     out, out_ld, out_gs, M, K, ds, plan.slices, beta, self_scale, act, aout, dact, dotx, dot_part)
-#define KGCN_TILE_DOT(LPR)                                                                                            \
-  {                                                                                                                   \
-    if (plan.nw == 1) KGCN_TILE_DOT2(LPR, 1);                                                                         \
-    else {                                                                                                            \
-      static thread_local bool big = false;                                                                           \
-      if (!big) {                                                                                                     \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(spmm_tile_kernel<LPR, 4, 4, true>),                   \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);                            \
-        big = true;                                                                                                   \
-      }                                                                                                               \
-      KGCN_TILE_DOT2(LPR, 4);                                                                                         \
-    }                                                                                                                 \
-  }
-      if (lanes <= 8) KGCN_TILE_DOT(8)
-      else if (lanes <= 16) KGCN_TILE_DOT(16)
-      else if (lanes <= 32) KGCN_TILE_DOT(32)
-      else KGCN_TILE_DOT(64)
-#undef KGCN_TILE_DOT
-#undef KGCN_TILE_DOT2
-      *dot_done = true;
-      return check_launch("spmm_tile_kernel<dot>");
-    }
-#define KGCN_TILE2(LPR, VEC, NW)                                                                                      \
-  hipLaunchKernelGGL((spmm_tile_kernel<LPR, VEC, NW>), grid, dim3(64 * NW), lds, stream, ch, rhs, rhs_ld, rhs_gs, out,   \
-                     out_ld, out_gs, M, K, ds, plan.slices, beta, self_scale, act, aout, dact)
-#define KGCN_TILE(LPR, VEC)                                                                                           \
-  {                                                                                                                   \
-    if (plan.nw == 1) KGCN_TILE2(LPR, VEC, 1);                                                                        \
-    else {                                                                                                            \
-      static thread_local bool big = false;                                                                           \
-      if (!big) {                                                                                                     \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(spmm_tile_kernel<LPR, VEC, 4>),                       \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);                            \
-        big = true;                                                                                                   \
-      }                                                                                                               \
-      KGCN_TILE2(LPR, VEC, 4);                                                                                        \
-    }                                                                                                                 \
-  }
-    if (plan.vec == 4) {
-      if (lanes <= 8) KGCN_TILE(8, 4)
-      else if (lanes <= 16) KGCN_TILE(16, 4)
-      else if (lanes <= 32) KGCN_TILE(32, 4)
-      else KGCN_TILE(64, 4)
-    } else {
-      if (lanes <= 8) KGCN_TILE(8, 2)
-      else if (lanes <= 16) KGCN_TILE(16, 2)
-      else if (lanes <= 32) KGCN_TILE(32, 2)
-      else KGCN_TILE(64, 2)
-    }
-#undef KGCN_TILE2
-#undef KGCN_TILE
-    return check_launch("spmm_tile_kernel");
-  }
-  const long total_rows = (long)T * M;
-  {
-    // rows that do not fit an LDS tile: the row-chunk kernel when 8- or 16-byte vectors are possible
-    const long all = rhs_ld | rhs_gs | out_ld | out_gs | rhs_cs | d;
-    const uintptr_t ptrs = reinterpret_cast<uintptr_t>(rhs) | reinterpret_cast<uintptr_t>(out) |
-                           (dact ? reinterpret_cast<uintptr_t>(aout) : 0);
-    const int vec = (all % 4 == 0 && ptrs % 16 == 0) ? 4 : ((all % 2 == 0 && ptrs % 8 == 0) ? 2 : 0);
-    if (vec && total_rows < (1L << 31) && rhs_ld < (1L << 31) && out_ld < (1L << 31)) {
-      const int lanes = d / vec;
-      const int lpr = lanes <= 16 ? 16 : (lanes <= 32 ? 32 : 64);
-      const int rows_per_group = total_rows >= 32768 ? 8 : 2;
-      const long rows_per_block = (long)(256 / lpr) * rows_per_group;
-      const long nblocks = (total_rows + rows_per_block - 1) / rows_per_block;
-      const int per_xcd = (int)((nblocks + 7) / 8);
-      const dim3 grid((unsigned)(per_xcd * 8));
-#define KGCN_ROWS3(VEC, LPR, DACT, R)                                                                                 \
-  hipLaunchKernelGGL((spmm_rows_kernel<VEC, LPR, DACT, R>), grid, dim3(256), 0, stream, ch, rhs, (int)rhs_ld, rhs_gs, \
-                     out, (int)out_ld, out_gs, M, total_rows, d, beta, self_scale, act, aout, dact, per_xcd)
-#define KGCN_ROWS2(VEC, LPR, DACT)                                                                                    \
-  {                                                                                                                   \
-    if (rows_per_group == 8) KGCN_ROWS3(VEC, LPR, DACT, 8);                                                           \
-    else KGCN_ROWS3(VEC, LPR, DACT, 2);                                                                               \
-  }
-#define KGCN_ROWS(VEC, LPR)                                                                                           \
-  {                                                                                                                   \
-    if (dact != KGCN_ACT_NONE) KGCN_ROWS2(VEC, LPR, true)                                                             \
-    else KGCN_ROWS2(VEC, LPR, false)                                                                                  \
-  }
-      if (vec == 4) {
-        if (lpr == 16) KGCN_ROWS(4, 16) else if (lpr == 32) KGCN_ROWS(4, 32) else KGCN_ROWS(4, 64)
-      } else {
-        if (lpr == 16) KGCN_ROWS(2, 16) else if (lpr == 32) KGCN_ROWS(2, 32) else KGCN_ROWS(2, 64)
-      }
-#undef KGCN_ROWS
-#undef KGCN_ROWS2
-#undef KGCN_ROWS3
-      return check_launch("spmm_rows_kernel");
-    }
-  }
-  const bool vec4 = (d % 4 == 0) && (rhs_ld % 4 == 0) && (rhs_gs % 4 == 0) && (out_ld % 4 == 0) &&
-                    (out_gs % 4 == 0) && (rhs_cs % 4 == 0) && aligned16(rhs) && aligned16(out) &&
-                    (dact == KGCN_ACT_NONE || aligned16(aout));
-  const int per_row = vec4 ? d / 4 : d;
-  int lpr_log2 = ilog2_ceil(per_row);
-  if (lpr_log2 > 6) lpr_log2 = 6;
-  long blocks = ((total_rows << lpr_log2) + 255) / 256;
-  const long max_blocks = (long)kNumCU * 64;
-  if (blocks > max_blocks) blocks = max_blocks;
-  if (blocks < 1) blocks = 1;
-  if (vec4)
-    hipLaunchKernelGGL((spmm_gather_kernel<4>), dim3((unsigned)blocks), dim3(256), 0, stream, ch, rhs, rhs_ld, rhs_gs,
-                       out, out_ld, out_gs, M, total_rows, d, lpr_log2, beta, self_scale, act, aout, dact);
-  else
-    hipLaunchKernelGGL((spmm_gather_kernel<1>), dim3((unsigned)blocks), dim3(256), 0, stream, ch, rhs, rhs_ld, rhs_gs,
-                       out, out_ld, out_gs, M, total_rows, d, lpr_log2, beta, self_scale, act, aout, dact);
-  return check_launch("spmm_gather_kernel");
+  return ch;
 }
 
-int launch_spmm(const kgcn_csr_batch* a, const float* rhs, long rhs_ld, long rhs_gs, int d,
-                float* out, long out_ld, long out_gs, float beta, const float* self_scale,
-                hipStream_t stream) {
-  return launch_spmm_multi(a, 1, rhs, rhs_ld, rhs_gs, 0, d, out, out_ld, out_gs, beta, self_scale, KGCN_ACT_NONE,
-                           nullptr, KGCN_ACT_NONE, stream);
+static uintptr_t ptr_bits(const float* rhs, const float* out, const float* aout, int dact) {
+  return reinterpret_cast<uintptr_t>(rhs) | reinterpret_cast<uintptr_t>(out) | (dact ? reinterpret_cast<uintptr_t>(aout) : 0);
+}
+
+// out[t] = act(beta*out[t] + sum_c A_c[t] @ (rhs_c[t] (.) act'(aout[t])));  a: nch channel descriptors of one batch shape.
+// dot_done (with dotx and dot_part): set when the launch also left <rhs, dotx> per graph in dot_part.
+static int launch_spmm_multi(const kgcn_csr_batch* a, int nch, long rhs_cs, int d, const SpmmOperands& o, hipStream_t stream,
+                             bool* dot_done = nullptr) {
+  const int T = a->num_graphs, M = a->rows, K = a->cols;
+  if (T == 0 || M == 0 || d == 0) return 0;
+  if (nch > MAX_CH) {                       // more channels than one launch takes: groups of MAX_CH, accumulate
+    for (int c0 = 0; c0 < nch; c0 += MAX_CH) {
+      const int n = nch - c0 < MAX_CH ? nch - c0 : MAX_CH;
+      SpmmOperands g = o;
+      g.rhs = o.rhs + c0 * rhs_cs;
+      if (c0 > 0) { g.beta = 1.f; g.self_scale = nullptr; }
+      if (c0 + n < nch) g.act = KGCN_ACT_NONE;          // the activation belongs to the last group only
+      g.dotx = nullptr; g.dot_part = nullptr;
+      if (int rc = launch_spmm_multi(a + c0, n, rhs_cs, d, g, stream)) return rc;
+    }
+    return 0;
+  }
+  const SpmmChannels ch = spmm_channels(a, nch, rhs_cs);
+  const bool dot = o.dotx && o.dot_part && dot_done;
+  const SpmmRoute r = spmm_route(spmm_call(false, a, nch, d, o.rhs_ld, o.rhs_gs, rhs_cs, o.out_ld, o.out_gs,
+                                           ptr_bits(o.rhs, o.out, o.aout, o.dact), o.dact != KGCN_ACT_NONE,
+                                           o.self_scale != nullptr, dot));
+  const long total_rows = (long)T * M;
+  switch (r.kernel) {
+    case KGCN_SPMM_BCONV_LOOP: return launch_bconv_loop(r, ch, o, M, K, stream);
+    case KGCN_SPMM_BLOCK: return launch_block(r, a, o, stream);
+    case KGCN_SPMM_SLICES: return launch_slices(r, a, o, stream);
+    case KGCN_SPMM_TILE: return launch_tile<false>(r, ch, o, M, K, stream);
+    case KGCN_SPMM_TILE_DOT: *dot_done = true; return launch_tile<true>(r, ch, o, M, K, stream);
+    case KGCN_SPMM_ROWS: return launch_rows(r, ch, o, M, total_rows, d, stream);
+    case KGCN_SPMM_GATHER: return launch_gather(r, ch, o, M, total_rows, d, stream);
+  }
+  return fail("launch_spmm_multi: no route");
+}
+
+// `square`: whether every channel must be square, and whether the refusal names the sizes
+enum ChannelShape { ANY_SHAPE, SQUARE, SQUARE_NAMED };
+// every channel a valid descriptor of channel 0's batch shape
+static int validate_channels(const kgcn_csr_batch* a, int n, const char* who, ChannelShape square) {
+  for (int c = 0; c < n; ++c) {
+    if (int rc = validate_csr(a + c, who)) return rc;
+    if (square == SQUARE_NAMED && a[c].rows != a[c].cols)
+      return fail("%s: adjacency must be square (M=%d K=%d)", who, a[c].rows, a[c].cols);
+    if (square == SQUARE && a[c].rows != a[c].cols) return fail("%s: adjacency must be square", who);
+    if (a[c].num_graphs != a[0].num_graphs || a[c].rows != a[0].rows || a[c].cols != a[0].cols)
+      return fail("%s: channel %d has a different batch shape", who, c);
+  }
+  return 0;
 }
 
 }  // namespace kgcn
 
 using namespace kgcn;
+
+extern "C" int kgcn_spmm_route_query(const kgcn_csr_batch* a_ch, int32_t num_channels, int32_t d, int64_t rhs_ld,
+                                     int64_t rhs_graph_stride, int64_t channel_stride, int64_t out_ld, int64_t out_graph_stride,
+                                     int32_t align_bytes, int32_t flags, kgcn_spmm_route* route) {
+  if (!a_ch || !route) return fail("kgcn_spmm_route_query: NULL argument");
+  if (num_channels <= 0 || num_channels > MAX_CH)
+    return fail("kgcn_spmm_route_query: num_channels=%d (one launch takes 1..%d)", num_channels, MAX_CH);
+  if (align_bytes != 16 && align_bytes != 8 && align_bytes != 4)
+    return fail("kgcn_spmm_route_query: align_bytes=%d (16, 8 or 4)", align_bytes);
+  if (d < 0) return fail("kgcn_spmm_route_query: d=%d < 0", d);
+  const SpmmRoute r = spmm_route(spmm_call((flags & KGCN_SPMM_FANOUT) != 0, a_ch, num_channels, d, rhs_ld, rhs_graph_stride,
+                                           channel_stride, out_ld, out_graph_stride, (uintptr_t)align_bytes,
+                                           (flags & KGCN_SPMM_DACT) != 0, (flags & KGCN_SPMM_SELF_SCALE) != 0,
+                                           (flags & KGCN_SPMM_DOT) != 0));
+  route->kernel = r.kernel;
+  for (int i = 0; i < 4; ++i) route->template_args[i] = r.targ[i];
+  route->ds = r.ds;
+  route->slices = r.slices;
+  route->workgroup = r.wg;
+  route->grid = r.grid;
+  route->lds_bytes = (int64_t)r.lds;
+  return 0;
+}
 
 extern "C" int kgcn_bspmm_f32(const kgcn_csr_batch* a, const float* rhs, int64_t rhs_ld,
                               int64_t rhs_graph_stride, int32_t d, float* out, int64_t out_ld,
@@ -1345,8 +1447,7 @@ extern "C" int kgcn_bspmm_f32(const kgcn_csr_batch* a, const float* rhs, int64_t
   if (!rhs || !out) return fail("kgcn_bspmm_f32: rhs/out is NULL");
   if (rhs_ld < d || out_ld < d) return fail("kgcn_bspmm_f32: leading dimension smaller than d");
   if (beta != 0.f && beta != 1.f) return fail("kgcn_bspmm_f32: beta must be 0 or 1");
-  return launch_spmm(a, rhs, rhs_ld, rhs_graph_stride, d, out, out_ld, out_graph_stride, beta,
-                     nullptr, as_stream(stream));
+  return launch_spmm_multi(a, 1, 0, d, {rhs, rhs_ld, rhs_graph_stride, out, out_ld, out_graph_stride, beta}, as_stream(stream));
 }
 
 extern "C" int kgcn_bconv_f32(const kgcn_csr_batch* a_ch, int32_t num_channels, const float* rhs,
@@ -1355,18 +1456,13 @@ extern "C" int kgcn_bconv_f32(const kgcn_csr_batch* a_ch, int32_t num_channels, 
                               int64_t out_graph_stride, void* stream) {
   if (num_channels <= 0) return fail("kgcn_bconv_f32: num_channels=%d", num_channels);
   if (!a_ch) return fail("kgcn_bconv_f32: a_ch is NULL");
-  for (int c = 0; c < num_channels; ++c) {
-    if (int rc = validate_csr(a_ch + c, "kgcn_bconv_f32")) return rc;
-    if (a_ch[c].num_graphs != a_ch[0].num_graphs || a_ch[c].rows != a_ch[0].rows ||
-        a_ch[c].cols != a_ch[0].cols)
-      return fail("kgcn_bconv_f32: channel %d has a different batch shape", c);
-  }
+  if (int rc = validate_channels(a_ch, num_channels, "kgcn_bconv_f32", ANY_SHAPE)) return rc;
   if (a_ch[0].num_graphs == 0 || a_ch[0].rows == 0 || d == 0) return 0;
   if (!rhs || !out) return fail("kgcn_bconv_f32: rhs/out is NULL");
   if (rhs_ld < d || out_ld < d) return fail("kgcn_bconv_f32: leading dimension smaller than d");
   // channel add-n (tf.add_n, kgcn/layers.py:115) inside the kernel: every output row is written once
-  return launch_spmm_multi(a_ch, num_channels, rhs, rhs_ld, rhs_graph_stride, rhs_channel_stride, d, out, out_ld,
-                           out_graph_stride, 0.f, nullptr, KGCN_ACT_NONE, nullptr, KGCN_ACT_NONE, as_stream(stream));
+  return launch_spmm_multi(a_ch, num_channels, rhs_channel_stride, d,
+                           {rhs, rhs_ld, rhs_graph_stride, out, out_ld, out_graph_stride}, as_stream(stream));
 }
 
 static int check_act(const char* who, int act) {
@@ -1380,45 +1476,29 @@ extern "C" int kgcn_bconv_fanout_f32(const kgcn_csr_batch* at_ch, int32_t num_ch
   if (num_channels <= 0) return fail("kgcn_bconv_fanout_f32: num_channels=%d", num_channels);
   if (!at_ch) return fail("kgcn_bconv_fanout_f32: at_ch is NULL");
   if (int rc = check_act("kgcn_bconv_fanout_f32", act)) return rc;
-  for (int c = 0; c < num_channels; ++c) {
-    if (int rc = validate_csr(at_ch + c, "kgcn_bconv_fanout_f32")) return rc;
-    if (at_ch[c].num_graphs != at_ch[0].num_graphs || at_ch[c].rows != at_ch[0].rows || at_ch[c].cols != at_ch[0].cols)
-      return fail("kgcn_bconv_fanout_f32: channel %d has a different batch shape", c);
-  }
+  if (int rc = validate_channels(at_ch, num_channels, "kgcn_bconv_fanout_f32", ANY_SHAPE)) return rc;
   if (d < 0) return fail("kgcn_bconv_fanout_f32: d=%d < 0", d);
   const int T = at_ch[0].num_graphs, M = at_ch[0].rows, K = at_ch[0].cols;
   if (T == 0 || M == 0 || d == 0) return 0;
   if (!grad || !out || (act != KGCN_ACT_NONE && !act_out)) return fail("kgcn_bconv_fanout_f32: NULL operand");
   if (ld < d || out_ld < d) return fail("kgcn_bconv_fanout_f32: leading dimension smaller than d");
   hipStream_t s = as_stream(stream);
-  const uintptr_t ptrs = reinterpret_cast<uintptr_t>(grad) | reinterpret_cast<uintptr_t>(out) |
-                         (act != KGCN_ACT_NONE ? reinterpret_cast<uintptr_t>(act_out) : 0);
-  const LoopPlan lp = num_channels <= MAX_CH
-      ? loop_plan(at_ch, num_channels, ld | graph_stride | out_ld | out_graph_stride | out_channel_stride | d, ptrs, d)
-      : LoopPlan{0, 0, 0, 0, 0};
-  if (lp.vec && (long)T * (d / lp.ds) <= 0x7fffffffL) {
-    SpmmChannels ch;
-    ch.n = num_channels;
-    ch.rhs_cs = 0;
-    for (int c = 0; c < num_channels; ++c) {
-      ch.rowptr[c] = at_ch[c].rowptr;
-      ch.cv[c] = reinterpret_cast<const int2*>(at_ch[c].cv);
-      ch.max_nnz[c] = at_ch[c].max_nnz_per_graph;
-    }
-    const int nsl = d / lp.ds;
-    const dim3 grid((unsigned)(T * nsl));
+  const SpmmRoute r = spmm_route(spmm_call(true, at_ch, num_channels, d, ld, graph_stride, out_channel_stride, out_ld,
+                                           out_graph_stride, ptr_bits(grad, out, act_out, act), act != KGCN_ACT_NONE, false, false));
+  if (r.kernel == KGCN_SPMM_BCONV_FANOUT) {
+    const SpmmChannels ch = spmm_channels(at_ch, num_channels, 0);
     const float* ao = act != KGCN_ACT_NONE ? act_out : nullptr;
-#define KGCN_FAN(VEC, NVL)                                                                                                 \
-  hipLaunchKernelGGL((bconv_fanout_kernel<VEC, NVL>), grid, dim3(64), lp.lds, s, ch, grad, (long)ld, (long)graph_stride, ao, \
-                     (int)act, out, (long)out_ld, (long)out_graph_stride, (long)out_channel_stride, M, K, lp.ds, nsl)
-    if (lp.vec == 4) { if (lp.nvl == 8) KGCN_FAN(4, 8); else KGCN_FAN(4, 16); }
-    else { if (lp.nvl == 8) KGCN_FAN(2, 8); else KGCN_FAN(2, 16); }
-#undef KGCN_FAN
-    return check_launch("bconv_fanout_kernel");
+    const bool ok = with_const<4, 2>(r.targ[0], [&](auto vec) { return with_const<8, 16>(r.targ[1], [&](auto nvl) {
+      hipLaunchKernelGGL((bconv_fanout_kernel<decltype(vec)::value, decltype(nvl)::value>), dim3((unsigned)r.grid), dim3(r.wg), r.lds,
+                         s, ch, grad, (long)ld, (long)graph_stride, ao, (int)act, out, (long)out_ld, (long)out_graph_stride,
+                         (long)out_channel_stride, M, K, r.ds, r.slices);
+      return true;
+    }); });
+    return launched(ok, "bconv_fanout_kernel");
   }
   for (int c = 0; c < num_channels; ++c) {                  // shapes the channel-loop kernel does not take: one launch per channel
-    int rc = launch_spmm_multi(at_ch + c, 1, grad, ld, graph_stride, 0, d, out + c * out_channel_stride, out_ld, out_graph_stride,
-                               0.f, nullptr, KGCN_ACT_NONE, act_out, act, s);
+    int rc = launch_spmm_multi(at_ch + c, 1, 0, d, {grad, ld, graph_stride, out + c * out_channel_stride, out_ld, out_graph_stride,
+                                                    0.f, nullptr, KGCN_ACT_NONE, act_out, act}, s);
     if (rc) return rc;
   }
   return 0;
@@ -1430,16 +1510,12 @@ extern "C" int kgcn_bconv_act_f32(const kgcn_csr_batch* a_ch, int32_t num_channe
   if (num_channels <= 0) return fail("kgcn_bconv_act_f32: num_channels=%d", num_channels);
   if (!a_ch) return fail("kgcn_bconv_act_f32: a_ch is NULL");
   if (int rc = check_act("kgcn_bconv_act_f32", act)) return rc;
-  for (int c = 0; c < num_channels; ++c) {
-    if (int rc = validate_csr(a_ch + c, "kgcn_bconv_act_f32")) return rc;
-    if (a_ch[c].num_graphs != a_ch[0].num_graphs || a_ch[c].rows != a_ch[0].rows || a_ch[c].cols != a_ch[0].cols)
-      return fail("kgcn_bconv_act_f32: channel %d has a different batch shape", c);
-  }
+  if (int rc = validate_channels(a_ch, num_channels, "kgcn_bconv_act_f32", ANY_SHAPE)) return rc;
   if (a_ch[0].num_graphs == 0 || a_ch[0].rows == 0 || d == 0) return 0;
   if (!rhs || !out) return fail("kgcn_bconv_act_f32: rhs/out is NULL");
   if (rhs_ld < d || out_ld < d) return fail("kgcn_bconv_act_f32: leading dimension smaller than d");
-  return launch_spmm_multi(a_ch, num_channels, rhs, rhs_ld, rhs_graph_stride, rhs_channel_stride, d, out, out_ld,
-                           out_graph_stride, 0.f, nullptr, act, nullptr, KGCN_ACT_NONE, as_stream(stream));
+  return launch_spmm_multi(a_ch, num_channels, rhs_channel_stride, d,
+                           {rhs, rhs_ld, rhs_graph_stride, out, out_ld, out_graph_stride, 0.f, nullptr, act}, as_stream(stream));
 }
 
 extern "C" int kgcn_bspmm_dact_f32(const kgcn_csr_batch* a, const float* grad, const float* act_out, int64_t ld,
@@ -1452,8 +1528,8 @@ extern "C" int kgcn_bspmm_dact_f32(const kgcn_csr_batch* a, const float* grad, c
   if (!grad || !out || (act != KGCN_ACT_NONE && !act_out)) return fail("kgcn_bspmm_dact_f32: NULL operand");
   if (ld < d || out_ld < d) return fail("kgcn_bspmm_dact_f32: leading dimension smaller than d");
   if (beta != 0.f && beta != 1.f) return fail("kgcn_bspmm_dact_f32: beta must be 0 or 1");
-  return launch_spmm_multi(a, 1, grad, ld, graph_stride, 0, d, out, out_ld, out_graph_stride, beta, nullptr,
-                           KGCN_ACT_NONE, act_out, act, as_stream(stream));
+  return launch_spmm_multi(a, 1, 0, d, {grad, ld, graph_stride, out, out_ld, out_graph_stride, beta, nullptr, KGCN_ACT_NONE,
+                                        act_out, act}, as_stream(stream));
 }
 
 extern "C" int kgcn_gin_aggregate_f32(const kgcn_csr_batch* a_ch, int32_t num_channels,
@@ -1461,20 +1537,13 @@ extern "C" int kgcn_gin_aggregate_f32(const kgcn_csr_batch* a_ch, int32_t num_ch
                                       void* stream) {
   if (num_channels <= 0) return fail("kgcn_gin_aggregate_f32: num_channels=%d", num_channels);
   if (!a_ch) return fail("kgcn_gin_aggregate_f32: a_ch is NULL");
-  for (int c = 0; c < num_channels; ++c) {
-    if (int rc = validate_csr(a_ch + c, "kgcn_gin_aggregate_f32")) return rc;
-    if (a_ch[c].rows != a_ch[c].cols)
-      return fail("kgcn_gin_aggregate_f32: adjacency must be square (M=%d K=%d)", a_ch[c].rows,
-                  a_ch[c].cols);
-    if (a_ch[c].num_graphs != a_ch[0].num_graphs || a_ch[c].rows != a_ch[0].rows)
-      return fail("kgcn_gin_aggregate_f32: channel %d has a different batch shape", c);
-  }
+  if (int rc = validate_channels(a_ch, num_channels, "kgcn_gin_aggregate_f32", SQUARE_NAMED)) return rc;
   if (a_ch[0].num_graphs == 0 || a_ch[0].rows == 0 || d == 0) return 0;
   if (!x || !out) return fail("kgcn_gin_aggregate_f32: x/out is NULL");
   const long gs = (long)a_ch[0].rows * d;
   for (int c = 0; c < num_channels; ++c) {
-    int rc = launch_spmm(a_ch + c, x, d, gs, d, out, d, gs, c == 0 ? 0.f : 1.f,
-                         eps ? eps + c : nullptr, as_stream(stream));
+    int rc = launch_spmm_multi(a_ch + c, 1, 0, d, {x, d, gs, out, d, gs, c == 0 ? 0.f : 1.f, eps ? eps + c : nullptr},
+                               as_stream(stream));
     if (rc) return rc;
   }
   return 0;
@@ -1496,12 +1565,7 @@ extern "C" int kgcn_gin_aggregate_bwd_f32(const kgcn_csr_batch* at_ch, int32_t n
                                           int64_t workspace_bytes, void* stream) {
   if (num_channels <= 0) return fail("kgcn_gin_aggregate_bwd_f32: num_channels=%d", num_channels);
   if (!at_ch) return fail("kgcn_gin_aggregate_bwd_f32: at_ch is NULL");
-  for (int c = 0; c < num_channels; ++c) {
-    if (int rc = validate_csr(at_ch + c, "kgcn_gin_aggregate_bwd_f32")) return rc;
-    if (at_ch[c].rows != at_ch[c].cols) return fail("kgcn_gin_aggregate_bwd_f32: adjacency must be square");
-    if (at_ch[c].num_graphs != at_ch[0].num_graphs || at_ch[c].rows != at_ch[0].rows)
-      return fail("kgcn_gin_aggregate_bwd_f32: channel %d has a different batch shape", c);
-  }
+  if (int rc = validate_channels(at_ch, num_channels, "kgcn_gin_aggregate_bwd_f32", SQUARE)) return rc;
   hipStream_t s = as_stream(stream);
   const int T = at_ch[0].num_graphs, N = at_ch[0].rows;
   if (T == 0 || N == 0 || d == 0) {
@@ -1516,11 +1580,10 @@ extern "C" int kgcn_gin_aggregate_bwd_f32(const kgcn_csr_batch* at_ch, int32_t n
   bool dot_done = false;
   if (dx) {
     for (int c = 0; c < num_channels; ++c) {
-      const bool try_dot = deps && c == 0;
-      int rc = launch_spmm_multi(at_ch + c, 1, grad, d, gs, 0, d, dx, d, gs, c == 0 ? 0.f : 1.f, eps ? eps + c : nullptr,
-                                 KGCN_ACT_NONE, nullptr, KGCN_ACT_NONE, s, try_dot ? x : nullptr,
-                                 try_dot ? static_cast<float*>(workspace) : nullptr, try_dot ? &dot_done : nullptr);
-      if (rc) return rc;
+      const bool try_dot = deps && c == 0;                 // <g, x> rides in the first channel's launch where its route allows
+      SpmmOperands o = {grad, d, gs, dx, d, gs, c == 0 ? 0.f : 1.f, eps ? eps + c : nullptr};
+      if (try_dot) { o.dotx = x; o.dot_part = static_cast<float*>(workspace); }
+      if (int rc = launch_spmm_multi(at_ch + c, 1, 0, d, o, s, try_dot ? &dot_done : nullptr)) return rc;
     }
   }
   if (!deps) return 0;
@@ -1540,16 +1603,12 @@ extern "C" int kgcn_spmm_values_grad_f32(const kgcn_csr_batch* a, const float* g
   if (a->nnz == 0 || a->num_graphs == 0 || a->rows == 0) return 0;
   if (!grad || !rhs || !dval) return fail("kgcn_spmm_values_grad_f32: NULL operand");
   if (d <= 0) return fail("kgcn_spmm_values_grad_f32: d=%d", d);
-  int lpr_log2 = ilog2_ceil(d);
-  if (lpr_log2 > 6) lpr_log2 = 6;
   const long total_rows = (long)a->num_graphs * a->rows;
-  long blocks = ((total_rows << lpr_log2) + 255) / 256;
-  const long max_blocks = (long)kNumCU * 64;
-  if (blocks > max_blocks) blocks = max_blocks;
-  hipLaunchKernelGGL(spmm_values_grad_kernel, dim3((unsigned)blocks), dim3(256), 0,
+  const LaneGrid g = lane_group_grid(total_rows, d);
+  hipLaunchKernelGGL(spmm_values_grad_kernel, dim3(g.blocks), dim3(256), 0,
                      as_stream(stream), a->rowptr, reinterpret_cast<const int2*>(a->cv), grad,
                      grad_ld, grad_graph_stride, rhs, rhs_ld, rhs_graph_stride, dval, a->rows,
-                     total_rows, d, lpr_log2);
+                     total_rows, d, g.lpr_log2);
   return check_launch("spmm_values_grad_kernel");
 }
 
@@ -1559,14 +1618,11 @@ extern "C" int kgcn_graph_maxpool_fwd_f32(const kgcn_csr_batch* a, const float* 
   if (a->num_graphs == 0 || a->rows == 0 || d <= 0) return 0;
   if (!x || !out) return fail("kgcn_graph_maxpool_fwd_f32: NULL operand");
   if (beta != 0.f && beta != 1.f) return fail("kgcn_graph_maxpool_fwd_f32: beta must be 0 or 1");
-  int lpr_log2 = ilog2_ceil(d);
-  if (lpr_log2 > 6) lpr_log2 = 6;
   const long total_rows = (long)a->num_graphs * a->rows;
-  long blocks = ((total_rows << lpr_log2) + 255) / 256;
-  if (blocks > (long)kNumCU * 64) blocks = (long)kNumCU * 64;
-  hipLaunchKernelGGL((maxpool_fwd_kernel<false>), dim3((unsigned)blocks), dim3(256), 0, as_stream(stream),
+  const LaneGrid g = lane_group_grid(total_rows, d);
+  hipLaunchKernelGGL((maxpool_fwd_kernel<false>), dim3(g.blocks), dim3(256), 0, as_stream(stream),
                      a->rowptr, reinterpret_cast<const int2*>(a->cv), x, out, nullptr, nullptr, a->rows,
-                     a->cols, total_rows, d, lpr_log2, beta);
+                     a->cols, total_rows, d, g.lpr_log2, beta);
   return check_launch("maxpool_fwd_kernel");
 }
 
@@ -1592,21 +1648,17 @@ extern "C" int kgcn_graph_maxpool_bwd_f32(const kgcn_csr_batch* a, const kgcn_cs
                 (long long)need);
   float* mm = static_cast<float*>(workspace);
   float* inv = mm + (long)a->num_graphs * a->rows * d;
-  int lpr_log2 = ilog2_ceil(d);
-  if (lpr_log2 > 6) lpr_log2 = 6;
   hipStream_t s = as_stream(stream);
   const long total_rows = (long)a->num_graphs * a->rows;
-  long blocks = ((total_rows << lpr_log2) + 255) / 256;
-  if (blocks > (long)kNumCU * 64) blocks = (long)kNumCU * 64;
-  hipLaunchKernelGGL((maxpool_fwd_kernel<true>), dim3((unsigned)blocks), dim3(256), 0, s, a->rowptr,
+  const LaneGrid g = lane_group_grid(total_rows, d);
+  hipLaunchKernelGGL((maxpool_fwd_kernel<true>), dim3(g.blocks), dim3(256), 0, s, a->rowptr,
                      reinterpret_cast<const int2*>(a->cv), x, nullptr, mm, inv, a->rows, a->cols, total_rows,
-                     d, lpr_log2, 0.f);
+                     d, g.lpr_log2, 0.f);
   if (int rc = check_launch("maxpool_fwd_kernel<count>")) return rc;
   const long total_cols = (long)at->num_graphs * at->rows;
-  blocks = ((total_cols << lpr_log2) + 255) / 256;
-  if (blocks > (long)kNumCU * 64) blocks = (long)kNumCU * 64;
-  hipLaunchKernelGGL(maxpool_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, s, at->rowptr,
+  const LaneGrid gt = lane_group_grid(total_cols, d);
+  hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(gt.blocks), dim3(256), 0, s, at->rowptr,
                      reinterpret_cast<const int2*>(at->cv), x, dout_grad, mm, inv, dx, a->rows, a->cols,
-                     total_cols, d, lpr_log2, beta);
+                     total_cols, d, gt.lpr_log2, beta);
   return check_launch("maxpool_bwd_kernel");
 }

@@ -461,12 +461,7 @@ extern "C" int kgcn_gcn_stack_fwd_f32(const kgcn_csr_batch* a, const float* x, c
   const int2* cvp = reinterpret_cast<const int2*>(a->cv);
 #define KGCN_SK_FWD(NQ)                                                                                               \
   {                                                                                                                   \
-    static thread_local bool attr = false;                                                                            \
-    if (!attr) {                                                                                                      \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(stack_fwd_kernel<NQ>),                                  \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);                              \
-      attr = true;                                                                                                    \
-    }                                                                                                                 \
+    if (int rc = allow_full_lds<stack_fwd_kernel<NQ>>(p.lds_fwd, "stack_fwd_kernel")) return rc;                      \
     hipLaunchKernelGGL(stack_fwd_kernel<NQ>, grid, dim3(256), p.lds_fwd, as_stream(stream), p.a, a->rowptr, cvp, x,   \
                        enabled, (long)a->num_graphs, pooled);                                                         \
   }
@@ -527,12 +522,7 @@ extern "C" int kgcn_gcn_stack_bwd_f32(const kgcn_csr_batch* at, const float* x, 
   }
 #define KGCN_SK_BWD(NQ)                                                                                               \
   {                                                                                                                   \
-    static thread_local bool attr = false;                                                                            \
-    if (!attr) {                                                                                                      \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(stack_bwd_kernel<NQ>),                                  \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);                              \
-      attr = true;                                                                                                    \
-    }                                                                                                                 \
+    if (int rc = allow_full_lds<stack_bwd_kernel<NQ>>(p.lds_bwd, "stack_bwd_kernel")) return rc;                      \
     hipLaunchKernelGGL(stack_bwd_kernel<NQ>, dim3(blocks), dim3(256), p.lds_bwd, s, p.a, at->rowptr, cvp, x, enabled, \
                        (long)at->num_graphs, dlast, dx, part, p.gtotal);                                              \
   }

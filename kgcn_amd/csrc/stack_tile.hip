@@ -680,22 +680,16 @@ __global__ __launch_bounds__(256) void stack2_bwd_kernel(StackArgs a, const int*
   S2_PROF_DUMP("s2bwd stage ell+vmask topbar+Htstore bn agg bar dW dX tail fetchissue loadP ttwrite");
 }
 
-static void s2_attr(const void* fn) {
-  (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-}
-
 int launch_stack2_fwd(const StackArgs& a, const Stack2Plan& p, const int* rowptr, const int2* cv, const float* x,
                       const int* enabled, long T, float* pooled, hipStream_t s) {
-  static thread_local bool attr = false;
-  if (!attr) { s2_attr(reinterpret_cast<const void*>(stack2_fwd_kernel)); attr = true; }
+  if (int rc = allow_full_lds<stack2_fwd_kernel>(p.lds_fwd, "stack2_fwd_kernel")) return rc;
   hipLaunchKernelGGL(stack2_fwd_kernel, dim3(stack2_blocks(T, a.G)), dim3(256), p.lds_fwd, s, a, rowptr, cv, x, enabled, T, pooled);
   return check_launch("stack2_fwd_kernel");
 }
 
 int launch_stack2_bwd(const StackArgs& a, const Stack2Plan& p, const int* rowptr_t, const int2* cv_t, const float* x,
                       const int* enabled, long T, const float* dlast, float* dx, float* part, int blocks, hipStream_t s) {
-  static thread_local bool attr = false;
-  if (!attr) { s2_attr(reinterpret_cast<const void*>(stack2_bwd_kernel)); attr = true; }
+  if (int rc = allow_full_lds<stack2_bwd_kernel>(p.lds_bwd, "stack2_bwd_kernel")) return rc;
   hipLaunchKernelGGL(stack2_bwd_kernel, dim3(blocks), dim3(256), p.lds_bwd, s, a, rowptr_t, cv_t, x, enabled, T, dlast, dx, part);
   return check_launch("stack2_bwd_kernel");
 }

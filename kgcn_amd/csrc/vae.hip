@@ -486,11 +486,6 @@ int recon_args(const kgcn_csr_batch* adj_ch, int C, const float* const* y, const
   return 0;
 }
 
-int set_lds_attr(const void* fn) {
-  return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes) == hipSuccess
-             ? 0 : fail("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-}
-
 int recon_bwd_grid(int B) { return B < 1024 ? B : 1024; }
 }  // namespace
 }  // namespace kgcn
@@ -568,11 +563,7 @@ extern "C" int kgcn_vae_recon_fwd_f32(const kgcn_csr_batch* adj_ch, int32_t num_
   if (!feat_logits || !feat_target || !per_graph || !sums) return fail("%s: NULL operand", who);
   if (a.B == 0) return fail("%s: empty batch", who);
   hipStream_t s = as_stream(stream);
-  static thread_local bool attr = false;
-  if (!attr) {
-    if (int rc = set_lds_attr(reinterpret_cast<const void*>(vae_recon_fwd_kernel))) return rc;
-    attr = true;
-  }
+  if (int rc = allow_full_lds<vae_recon_fwd_kernel>(0, who)) return rc;
   const size_t lds = recon_lds_floats(a.NP, a.D4, false, a.C) * 4;
   hipLaunchKernelGGL(vae_recon_fwd_kernel, dim3(a.B), dim3(256), lds, s, a, feat_logits, feat_target, per_graph);
   if (int rc = check_launch("vae_recon_fwd_kernel")) return rc;
@@ -599,11 +590,7 @@ extern "C" int kgcn_vae_recon_bwd_f32(const kgcn_csr_batch* adj_ch, int32_t num_
     return fail("%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes,
                 (long long)kgcn_vae_recon_workspace_bytes(a.B, a.C, d));
   hipStream_t s = as_stream(stream);
-  static thread_local bool attr = false;
-  if (!attr) {
-    if (int rc = set_lds_attr(reinterpret_cast<const void*>(vae_recon_bwd_kernel))) return rc;
-    attr = true;
-  }
+  if (int rc = allow_full_lds<vae_recon_bwd_kernel>(0, who)) return rc;
   float* part = dw ? static_cast<float*>(workspace) : nullptr;
   const size_t lds = recon_lds_floats(a.NP, a.D4, true, a.C) * 4;
   hipLaunchKernelGGL(vae_recon_bwd_kernel, dim3(grid), dim3(256), lds, s, a, feat_logits, feat_target, mask, g_opt, g_sum, dfeat,

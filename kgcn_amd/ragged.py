@@ -21,8 +21,6 @@ zeros) and no adjacency entry touches a node >= n_b (checked on the device when 
 Not defined on this layout: GraphMaxPooling (its implicit-zero rule counts the padded columns) and
 GraphBatchNormalization in training phase WITHOUT enabled_node_nums (its statistics would include the padded rows).
 """
-import os
-
 import numpy as np
 
 from . import _lib
@@ -96,7 +94,7 @@ def _compact_csr(src, sel_dev, B, graph_ptr, entry_ptr, capacity, rowptr, cv, st
 
 def _container(rowptr, cv, capacity, block_ptr=None, n_nodes=0):
     c = BatchedCSR(rowptr, cv, 1, capacity, capacity, max(int(cv.shape[0]), 1))
-    if block_ptr is not None and os.environ.get("KGCN_SPMM_BLOCKS") != "0":          # (development A/B: the row-chunk kernel)
+    if block_ptr is not None:
         # the row blocks of whole molecules: the aggregation kernels stage a block's rows in LDS once (csrc/spmm.hip, spmm_block_kernel)
         c.block_ptr, c.block_rows_max = block_ptr, _lib.lib.kgcn_ragged_block_rows() + max(int(n_nodes), 1) - 1
     return c

@@ -68,11 +68,22 @@ def _dact(a, act):
 ])
 def test_bconv_forward_and_fanout(T, N, C, d, act, dense_channel):
     from kgcn_amd import ops
-    from kgcn_amd._lib import lib, ptr, current_stream, check
+    from kgcn_amd._lib import lib, ptr, current_stream, check, spmm_route, SPMM_DACT, SPMM_FANOUT
     from kgcn_amd.batched_csr import BatchedAdjacency
     rng = np.random.default_rng(T * 1000 + N * 10 + C)
     adjs = _channels(rng, T, N, C, 0.12, empty_graph_every=5, dense_channel=dense_channel)
     adj = BatchedAdjacency.from_adjs(adjs, n_nodes=N, device=dev())
+    if C <= 8:
+        # the kernels behind the two calls ops.bconv makes below.  "The old kernels": an odd width allows no vectors (the gather
+        # kernel), graphs of more than 64 nodes go to the tile kernel with all channels staged; there the fan-out is one
+        # single-channel launch per channel
+        fwd, bwd, bwd1 = {(10, 51): ("spmm_gather", "none", "spmm_gather"),
+                          (70, 64): ("spmm_tile", "none", "spmm_tile")}.get((N, d), ("bconv_loop", "bconv_fanout", None))
+        dflag = SPMM_DACT if act else 0
+        assert spmm_route(adj.desc_array(), C, d, C * d, N * C * d, d, d, N * d)[0] == fwd
+        assert spmm_route(adj.desc_array(True), C, d, d, N * d, d, C * d, N * C * d, flags=SPMM_FANOUT | dflag)[0] == bwd
+        if bwd1:
+            assert spmm_route(adj.channels[0].transpose().desc(), 1, d, d, N * d, 0, C * d, N * C * d, flags=dflag)[0] == bwd1
     rhs = rng.standard_normal((T * N, C * d)).astype(np.float32)
     g = rng.standard_normal((T * N, d)).astype(np.float32)
     dense = [[rhs[b * N:(b + 1) * N, c * d:(c + 1) * d] for c in range(C)] for b in range(T)]
