@@ -75,5 +75,6 @@ else:
     score = np.stack([pred[0, tl[:, 1], tl[:, 0], tl[:, 2]], pred[0, tl[:, 4], tl[:, 3], tl[:, 5]]], 1)
 os.makedirs(out_dir, exist_ok=True)
 np.save(os.path.join(out_dir, "pred_data.npy"), pred)
-np.savez(os.path.join(out_dir, "test_edge_result.npz"), output=h.cpu().numpy(), score=score)
+extra = {"relation_w": model.distmult.w[0].detach().cpu().numpy()} if variant == "distmult" else {}    # for enrich_linkpred.py
+np.savez(os.path.join(out_dir, "test_edge_result.npz"), output=h.detach().cpu().numpy(), score=score, **extra)
 print("prediction_data %s and edge result (output %s, score %s) -> %s" % (pred.shape, tuple(h.shape), score.shape, out_dir))

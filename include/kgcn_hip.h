@@ -81,7 +81,8 @@ extern "C" {
  * The compact row-padded adjacency (row_pad == KGCN_ROW_PAD_COMPACT) added a layout CODE and entry points only (version
  * still 2): a library without it refuses that code in every entry point (validate_csr accepts row_pad 0 and 4 only), so
  * an old library never misreads it; kgcn_csr_compact4 is the feature query (look it up before building such a batch).
- * The SpMM route report added an entry point only (version still 2): kgcn_spmm_route_query (+ kgcn_spmm_route). */
+ * The SpMM route report added an entry point only (version still 2): kgcn_spmm_route_query (+ kgcn_spmm_route).
+ * The pair ranking added entry points only (version still 2): kgcn_pair_rank_select_f32 / _emit_f32 / _table_i32 (+ _workspace_bytes). */
 #define KGCN_HIP_ABI_VERSION 2
 
 /* Column index of the padding entries of a row-padded batch (see row_pad): they carry value 0 and
@@ -972,6 +973,38 @@ int kgcn_kg_ig_f32(const int32_t* indptr, const int32_t* indices, const float* v
                    const float* g1, const float* rowsum, const float* b1, const float* w2, const float* h2, const float* p,
                    const float* scales, const float* weights, int32_t steps, const int32_t* targets, int32_t num_targets,
                    int32_t mode, int32_t groups, float* node_ig, float* score, float* u, void* stream);
+
+/* -- ranking of all node pairs of the link-prediction model (run_enrichment.sh: script/predscore.py; csrc/pairrank.hip) -------
+ * The score of pair (i, j), i < j, is s_ij = sum_k (h[i,k] w[k]) h[j,k] over h [nodes, dim] (w NULL: gcn / ip; one relation's
+ * DistMult vector otherwise), fp32 on the f32 MFMA, k ascending; the [N, N] matrix is never formed.  The list is in the order of
+ * predscore.py:153: score, then row, then col, all descending; -0.0 ranks as +0.0 and NaN below every number.
+ *   select  counts [3] (device int64) = T, count(key > T), count(key == T): T the uint32 key of the cutoff-th largest score
+ *           (cutoff 0, or more than N (N - 1) / 2: of the smallest).  Asynchronous; workspace >= workspace_bytes(.., 0, 0).
+ *   emit    score / row / col [min(cutoff or all, all)]: the head of the sorted list.  counts is select's output for the same
+ *           operands, capacity >= counts[1] + counts[2] (the caller reads them: one synchronisation) and <=
+ *           KGCN_PAIRRANK_MAX_CANDIDATES; workspace >= workspace_bytes(.., capacity, 0).  Nothing is written past the capacity:
+ *           the call reads the candidate counter back (it synchronises the stream) and fails when the buffer was too small.
+ *   table   on a sorted list of `entries` rows: train_edge / test_edge / new_edge [entries] uint8 by membership of
+ *           row << 16 | col in target_codes (train + test) and test_codes (both sorted ascending, duplicate-free, device uint32),
+ *           score_ranking [entries] int64 = 1 + the entries with a larger score (ties share the smallest rank), and for the
+ *           num_top <= KGCN_PAIRRANK_MAX_TOP HOST thresholds top_ratio[p]: hits[p] = test entries among the first top_ratio[p]
+ *           entries that are no train edge, covered[p] = whether the list holds that many such entries (device int64 each).
+ *           workspace >= workspace_bytes(.., 0, entries).
+ * No float atomics: bitwise reproducible.  Not for hipGraph capture (emit synchronises). */
+#define KGCN_PAIRRANK_MAX_NODES 65536
+#define KGCN_PAIRRANK_MAX_CANDIDATES (1 << 28)
+#define KGCN_PAIRRANK_MAX_TOP 16
+int64_t kgcn_pair_rank_workspace_bytes(int32_t nodes, int32_t dim, int64_t capacity, int64_t entries);
+int kgcn_pair_rank_select_f32(const float* h, int32_t nodes, int32_t dim, const float* w, int64_t cutoff, int64_t* counts,
+                              void* workspace, int64_t workspace_bytes, void* stream);
+int kgcn_pair_rank_emit_f32(const float* h, int32_t nodes, int32_t dim, const float* w, int64_t cutoff, const int64_t* counts,
+                            int64_t capacity, float* score, int32_t* row, int32_t* col, void* workspace, int64_t workspace_bytes,
+                            void* stream);
+int kgcn_pair_rank_table_i32(const float* score, const int32_t* row, const int32_t* col, int64_t entries,
+                             const uint32_t* target_codes, int64_t num_target, const uint32_t* test_codes, int64_t num_test,
+                             const int64_t* top_ratio, int32_t num_top, uint8_t* train_edge, uint8_t* test_edge, uint8_t* new_edge,
+                             int64_t* score_ranking, int64_t* hits, int64_t* covered, void* workspace, int64_t workspace_bytes,
+                             void* stream);
 
 #ifdef __cplusplus
 }

@@ -322,6 +322,16 @@ SIGNATURES = {
     # integrated gradients of the link-prediction model (csrc/kgig.hip)
     "kgcn_kg_ig_f32": (ctypes.c_int, [c_i32p, c_i32p, c_f32p, c_i64, c_i32, c_i32, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
                                       c_f32p, c_f32p, c_i32, c_i32p, c_i32, c_i32, c_i32, c_f32p, c_f32p, c_f32p, ctypes.c_void_p]),
+    # ranking of all node pairs of the link-prediction model (csrc/pairrank.hip)
+    "kgcn_pair_rank_workspace_bytes": (c_i64, [c_i32, c_i32, c_i64, c_i64]),
+    "kgcn_pair_rank_select_f32": (ctypes.c_int, [c_f32p, c_i32, c_i32, c_f32p, c_i64, ctypes.c_void_p, ctypes.c_void_p, c_i64,
+                                                 ctypes.c_void_p]),
+    "kgcn_pair_rank_emit_f32": (ctypes.c_int, [c_f32p, c_i32, c_i32, c_f32p, c_i64, ctypes.c_void_p, c_i64, c_f32p, c_i32p, c_i32p,
+                                               ctypes.c_void_p, c_i64, ctypes.c_void_p]),
+    "kgcn_pair_rank_table_i32": (ctypes.c_int, [c_f32p, c_i32p, c_i32p, c_i64, ctypes.c_void_p, c_i64, ctypes.c_void_p, c_i64,
+                                                ctypes.POINTER(c_i64), c_i32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i64,
+                                                ctypes.c_void_p]),
     "kgcn_graph_gather_bwd_ld_f32": (ctypes.c_int, [c_f32p, c_i64, c_i64, c_i32, c_i32, c_f32p, ctypes.c_void_p]),
     "kgcn_graph_gather_bwd_add_f32": (ctypes.c_int, [c_f32p, c_f32p, c_i64, c_i32, c_i32, c_f32p, ctypes.c_void_p]),
     "kgcn_dot_workspace_bytes": (c_i64, [c_i64]),

@@ -529,6 +529,21 @@ class LinkPredictionNet(nn.Module):
         w = self.distmult.w[0]
         return torch.stack([ops.dense(h * w[r], ht) for r in range(w.shape[0])]).unsqueeze(0), h
 
+    @torch.no_grad()
+    def rank_links(self, adjs, label_list, test_label_list, relation=None, cutoff=10000):
+        """run_enrichment.sh on this model (kgcn_amd.predscore.rank_links): all node pairs in score order with their train /
+        test / new marks and the enrichment of the test edges, from node_rows(adjs) without the [N, N] prediction.  distmult
+        ranks ONE relation's scores, H diag(w[relation]) H^T: `relation` is required there and refused elsewhere."""
+        from . import predscore
+        if (self.distmult is not None) != (relation is not None):
+            raise ValueError("rank_links: relation= is required by 'distmult' and only by it")
+        w = None
+        if relation is not None:
+            if not 0 <= int(relation) < self.distmult.w[0].shape[0]:
+                raise ValueError("rank_links: relation %d outside [0, %d)" % (int(relation), self.distmult.w[0].shape[0]))
+            w = self.distmult.w[0][int(relation)]
+        return predscore.rank_links(self.node_rows(adjs).contiguous(), label_list, test_label_list, w=w, cutoff=cutoff)
+
 
 class KerasBatchNorm(nn.Module):
     """K.layers.BatchNormalization() on [B, D], called without `training=` (sample_protein/sequence/cnn.py:74, :76): under the

@@ -2466,3 +2466,106 @@ def kg_ig(csr, g1, rowsum, b1, w2, h2, p, scales, weights, targets, mode="score"
                                  ptr(h2), ptr(p), ptr(sc), ptr(wt), K, ptr(tgd), T, KG_IG_MODES[mode], g, ptr(node_ig), ptr(score),
                                  ptr(u), current_stream()), "kgcn_kg_ig_f32")
     return node_ig, score, u
+
+
+# -------------------------------------------------------------------------------------------------
+# ranking of all node pairs of the link-prediction model (run_enrichment.sh: script/predscore.py; csrc/pairrank.hip): the
+# score-ordered pair list straight from the node rows, and its train / test / new marks with the enrichment counts
+# -------------------------------------------------------------------------------------------------
+PAIRRANK_MAX_NODES, PAIRRANK_MAX_CANDIDATES, PAIRRANK_MAX_TOP = 65536, 1 << 28, 16
+
+
+def _pair_rank_ws(n, d, capacity, entries, device):
+    nbytes = lib.kgcn_pair_rank_workspace_bytes(n, d, capacity, entries)
+    if nbytes < 0:
+        check(1, "kgcn_pair_rank_workspace_bytes")
+    return _lib.workspace(nbytes, device, torch.uint8), nbytes
+
+
+@torch.no_grad()
+def pair_rank(h, w=None, cutoff=10000):
+    """The first `cutoff` entries (0, or more than there are: all N (N - 1) / 2) of the list of node pairs i < j ordered as
+    predscore.py:153 orders its (score, row, col) tuples -- score, then row, then col, all descending -> (score [K] float32,
+    row [K] int32, col [K] int32) device tensors.  The score is s_ij = sum_k (h[i,k] w[k]) h[j,k] in fp32 on the f32 MFMA, k
+    ascending (w: one relation's DistMult vector [D], None for gcn / ip); -0.0 ranks as +0.0 and NaN below every number.
+    The [N, N] matrix is never formed: a radix select finds the key of the cutoff-th score, its three counts are read (the
+    one synchronisation besides the end of the call: not for hipGraph capture), and the pairs at or above it are gathered,
+    sorted and cut.  A read-out: no autograd.  Bitwise reproducible."""
+    h = _f32c(h.detach(), "node rows")
+    if h.dim() != 2 or not 2 <= h.shape[0] <= PAIRRANK_MAX_NODES or not 1 <= h.shape[1] <= LINKPRED_MAX_DIM:
+        raise _lib.KgcnHipError("pair_rank: node rows must be [2 <= N <= %d, 1 <= D <= %d], got %s"
+                                % (PAIRRANK_MAX_NODES, LINKPRED_MAX_DIM, tuple(h.shape)))
+    N, D = h.shape
+    cutoff = int(cutoff)
+    if cutoff < 0:
+        raise _lib.KgcnHipError("pair_rank: negative cutoff %d" % cutoff)
+    wc = None
+    if w is not None:
+        wc = _f32c(w.detach(), "relation vector").reshape(-1)
+        if wc.numel() != D:
+            raise _lib.KgcnHipError("pair_rank: the relation vector must have %d entries, got %s" % (D, tuple(w.shape)))
+    total = N * (N - 1) // 2
+    k = total if cutoff == 0 or cutoff > total else cutoff
+    counts = torch.empty((3,), device=h.device, dtype=torch.int64)
+    ws, wsb = _pair_rank_ws(N, D, 0, 0, h.device)
+    check(lib.kgcn_pair_rank_select_f32(ptr(h), N, D, ptr(wc), cutoff, ptr(counts), ptr(ws), wsb, current_stream()),
+          "kgcn_pair_rank_select_f32")
+    _, above, equal = counts.tolist()
+    capacity = above + equal
+    if not k <= capacity <= total:
+        raise _lib.KgcnHipError("pair_rank: the select counted %d + %d candidates for %d of %d entries" % (above, equal, k, total))
+    if capacity > PAIRRANK_MAX_CANDIDATES:
+        raise _lib.KgcnHipError("pair_rank: %d pairs score at or above the cutoff's (%d of them tie at it), more than the %d "
+                                "candidates one call sorts: lower the cutoff" % (capacity, equal, PAIRRANK_MAX_CANDIDATES))
+    ws, wsb = _pair_rank_ws(N, D, capacity, 0, h.device)
+    score = torch.empty((k,), device=h.device, dtype=torch.float32)
+    row = torch.empty((k,), device=h.device, dtype=torch.int32)
+    col = torch.empty((k,), device=h.device, dtype=torch.int32)
+    check(lib.kgcn_pair_rank_emit_f32(ptr(h), N, D, ptr(wc), cutoff, ptr(counts), capacity, ptr(score), ptr(row), ptr(col), ptr(ws),
+                                      wsb, current_stream()), "kgcn_pair_rank_emit_f32")
+    return score, row, col
+
+
+def pair_codes(pairs, device):
+    """Host pairs (row < col) -> the sorted, duplicate-free uint32 codes row << 16 | col the table kernel searches, as an
+    int32-typed device tensor of those bits."""
+    import numpy as np
+    p = np.asarray(pairs, np.int64).reshape(-1, 2)
+    if p.size and (p.min() < 0 or p.max() >= PAIRRANK_MAX_NODES or np.any(p[:, 0] >= p[:, 1])):
+        raise ValueError("pair_codes: pairs must be (row, col) with 0 <= row < col < %d" % PAIRRANK_MAX_NODES)
+    codes = np.unique((p[:, 0] << 16) | p[:, 1]).astype(np.uint32)
+    return torch.from_numpy(codes.view(np.int32)).to(device)
+
+
+@torch.no_grad()
+def pair_rank_table(score, row, col, target_codes, test_codes, top_ratio):
+    """convert / process_table / enrichment of predscore.py:194-280 on a sorted list (pair_rank's output) -> (train_edge,
+    test_edge, new_edge [K] uint8, score_ranking [K] int64, hits [P] int64, covered [P] int64).  target_codes (train + test)
+    and test_codes: pair_codes tensors.  train = in target and not in test, test = in test, new = neither; score_ranking =
+    1 + the entries with a larger score (len - rankdata(max) + 1); hits[p] = test entries among the first top_ratio[p]
+    entries that are no train edge; covered[p] = the list holds that many such entries.  P <= 16 host integers."""
+    score = _f32c(score, "score")
+    K = score.numel()
+    top = [int(t) for t in top_ratio]
+    if K < 1 or K > PAIRRANK_MAX_CANDIDATES or len(top) > PAIRRANK_MAX_TOP or any(t < 0 for t in top):
+        raise _lib.KgcnHipError("pair_rank_table: %d entries, %d thresholds (up to %d entries, %d thresholds >= 0)"
+                                % (K, len(top), PAIRRANK_MAX_CANDIDATES, PAIRRANK_MAX_TOP))
+    for t, name in ((row, "row"), (col, "col"), (target_codes, "target codes"), (test_codes, "test codes")):
+        require_gpu(t, name)
+        if t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 1:
+            raise _lib.KgcnHipError("pair_rank_table: %s must be a contiguous 1-D int32 device tensor" % name)
+    if row.numel() != K or col.numel() != K:
+        raise _lib.KgcnHipError("pair_rank_table: score, row and col must have one length")
+    dev = score.device
+    flags = torch.empty((3, K), device=dev, dtype=torch.uint8)
+    ranking = torch.empty((K,), device=dev, dtype=torch.int64)
+    hits = torch.zeros((len(top),), device=dev, dtype=torch.int64)
+    covered = torch.zeros((len(top),), device=dev, dtype=torch.int64)
+    ws, wsb = _pair_rank_ws(2, 1, 0, K, dev)
+    tops = (ctypes.c_int64 * max(len(top), 1))(*top)
+    check(lib.kgcn_pair_rank_table_i32(ptr(score), ptr(row), ptr(col), K, ptr(target_codes) if target_codes.numel() else None,
+                                       target_codes.numel(), ptr(test_codes) if test_codes.numel() else None, test_codes.numel(),
+                                       tops, len(top), ptr(flags[0]), ptr(flags[1]), ptr(flags[2]), ptr(ranking),
+                                       ptr(hits) if top else None, ptr(covered) if top else None, ptr(ws), wsb, current_stream()),
+          "kgcn_pair_rank_table_i32")
+    return flags[0], flags[1], flags[2], ranking, hits, covered
