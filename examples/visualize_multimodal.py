@@ -7,7 +7,11 @@ examples/train_multimodal.py (batch 10, TF-style Adam at 0.3, --epochs).  Writes
 {header}_{id:04d}_task_0_{assay}_{modal}_scaling.jbl per compound (joblib, the keys kgcn/visualization.py dumps) and logs the
 prediction score, check score (end - start) and sum of IG of each compound and the accuracy over the visualised ones.
 
-    python examples/visualize_multimodal.py [--params FILE] [--epochs 5] [--outdir viz_mm] [--modal all] [--method ig]
+--method smooth_grad / smooth_ig average --divide-number noisy samples (N(0, --noise-scale) on the targeted inputs, drawn on
+the device from --seed); file names and dump keys are the same for every method.
+
+    python examples/visualize_multimodal.py [--params FILE] [--epochs 5] [--outdir viz_mm] [--modal all]
+                                            [--method ig|grad_prod|grad|smooth_grad|smooth_ig] [--noise-scale 0.1] [--seed 1234]
                                             [--label-target max] [--divide-number 100] [--header mol]
 """
 import argparse
@@ -28,7 +32,9 @@ ap.add_argument("--params", default=None, help="state_dict of a MultimodalGCN (t
 ap.add_argument("--epochs", type=int, default=5, help="training epochs when no --params are given")
 ap.add_argument("--outdir", default="viz_mm")
 ap.add_argument("--modal", default="all", choices=("all",) + V.IG_MODALS)
-ap.add_argument("--method", default="ig", choices=V.IG_METHODS)
+ap.add_argument("--method", default="ig", choices=V.IG_METHODS + V.SMOOTH_METHODS)
+ap.add_argument("--noise-scale", type=float, default=0.1, help="standard deviation of the noise of the smooth methods")
+ap.add_argument("--seed", type=int, default=1234, help="seed of the noise of the smooth methods")
 ap.add_argument("--label-target", default="max")
 ap.add_argument("--divide-number", type=int, default=100)
 ap.add_argument("--header", default="mol")
@@ -69,7 +75,8 @@ else:
 os.makedirs(args.outdir, exist_ok=True)
 t0 = time.time()
 results = V.multimodal_integrated_gradients(model, None, dataset, tokens, labels=raw["label"], divide_number=args.divide_number,
-                                            modal=args.modal, method=args.method, label_target=args.label_target)
+                                            modal=args.modal, method=args.method, label_target=args.label_target,
+                                            noise_scale=args.noise_scale, seed=args.seed)
 elapsed = time.time() - t0
 correct = 0
 for r in results:

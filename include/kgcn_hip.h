@@ -82,7 +82,9 @@ extern "C" {
  * still 2): a library without it refuses that code in every entry point (validate_csr accepts row_pad 0 and 4 only), so
  * an old library never misreads it; kgcn_csr_compact4 is the feature query (look it up before building such a batch).
  * The SpMM route report added an entry point only (version still 2): kgcn_spmm_route_query (+ kgcn_spmm_route).
- * The pair ranking added entry points only (version still 2): kgcn_pair_rank_select_f32 / _emit_f32 / _table_i32 (+ _workspace_bytes). */
+ * The pair ranking added entry points only (version still 2): kgcn_pair_rank_select_f32 / _emit_f32 / _table_i32 (+ _workspace_bytes).
+ * The smooth attribution methods added entry points only (version still 2): kgcn_ig_perturb_rows_f32, kgcn_ig_perturb_values_f32,
+ * kgcn_seq_convpool_perturbed_fwd_f32. */
 #define KGCN_HIP_ABI_VERSION 2
 
 /* Column index of the padding entries of a row-padded batch (see row_pad): they carry value 0 and
@@ -880,6 +882,36 @@ int kgcn_seq_convpool_input_grad_f32(const int32_t* tokens, int32_t batch, int32
                                      int32_t symbols, int32_t embed_dim, const float* w, int32_t kernel_size, int32_t filters,
                                      int32_t pool, const float* dout, const uint8_t* argmax, const float* row_weight,
                                      int32_t times_table, float* dx, void* stream);
+/* Noise of the smooth attribution methods (kgcn/visualization.py:235-259 smooth_grad / smooth_ig; kgcn/feed.py:88-89
+ * add_perturbation draws it on the host).  One N(0, 1) value z per (seed, stream s, compound g, sample k, row r, column w) of a
+ * 2-D array [R, W]: normal number w & 3 of the Philox4x64-10 block with counter (r ceil(W / 4) + (w >> 2), k, g, s) and key
+ * (seed, 0), by the Box-Muller of the VAE noise above (24-bit uniforms; words 0, 1 give normals 0, 1 and words 2, 3 give normals
+ * 2, 3).  g is the compound's index in the dataset and k the sample number (both read as unsigned 32-bit values), never the
+ * position of the copy in a launch.  Streams: KGCN_IG_STREAM_FEATURES the node features [N, F], padding rows included;
+ * KGCN_IG_STREAM_ADJACENCY + ch the stored values of adjacency channel ch of graph g as [1, nnz_g] in the CSR order of the batch;
+ * KGCN_IG_STREAM_SEQUENCE the embedded sequence [L, E].  The perturbed value is fma(sigma, z, x * scale) in fp32; a copy with
+ * sigma == 0 is x * scale, the clean path's product, and draws nothing.
+ * Rows: out [batch, rows, width], copy b = x[b / rep] (x [batch / rep, rows, width]) with scale[b], sigma[b], sample[b] and
+ * ids[b / rep] (16-byte accesses when width % 4 == 0 and x, out are 16-byte aligned).  Values: out[e] for the entries e of a plain batched CSR (rowptr
+ * [num_graphs rows + 1], nnz entries, values [nnz]), graph b owning rowptr[b rows] .. rowptr[(b + 1) rows] with scale[b],
+ * sigma[b], sample[b], ids[b] (all PER GRAPH); graphs without entries and repeated (row, col) entries need nothing special (the
+ * noise is per stored entry); max_nnz_per_graph only sizes the grid.  Perturbed conv-pool: kgcn_seq_convpool_scaled_fwd_f32 with
+ * the window element at position l, column e = table[tok] * scale[b] + sigma[b] * z (stream KGCN_IG_STREAM_SEQUENCE, row l,
+ * column e, g = ids[b / rep], k = sample[b]); positions outside [0, L) stay 0.  kgcn_seq_convpool_input_grad_f32 serves it
+ * unchanged (it needs the arg-max bytes and the clean table only). */
+#define KGCN_IG_STREAM_FEATURES 0u
+#define KGCN_IG_STREAM_ADJACENCY 1u
+#define KGCN_IG_STREAM_SEQUENCE 0x100u
+int kgcn_ig_perturb_rows_f32(const float* x, int64_t batch, int32_t rep, int32_t rows, int32_t width, const float* scale,
+                             const float* sigma, const int32_t* sample, const int32_t* ids, uint32_t noise_stream, uint64_t seed,
+                             float* out, void* stream);
+int kgcn_ig_perturb_values_f32(const int32_t* rowptr, int32_t num_graphs, int32_t rows, int64_t nnz, int32_t max_nnz_per_graph,
+                               const float* values, const float* scale, const float* sigma, const int32_t* sample,
+                               const int32_t* ids, uint32_t noise_stream, uint64_t seed, float* out, void* stream);
+int kgcn_seq_convpool_perturbed_fwd_f32(const int32_t* tokens, int32_t batch, int32_t rep, const float* scale, const float* sigma,
+                                        const int32_t* sample, const int32_t* ids, uint64_t seed, int32_t length, const float* table,
+                                        int32_t symbols, int32_t embed_dim, const float* w, const float* bias, int32_t kernel_size,
+                                        int32_t filters, int32_t pool, float* out, uint8_t* argmax, void* stream);
 /* dx[b, n, :] = dout[b * dout_ld + :d]: the gradient of a GraphGather read-out written into a column block of a wider buffer
  * (kgcn_graph_gather_fwd_ld_f32), read where it lies */
 int kgcn_graph_gather_bwd_ld_f32(const float* dout_grad, int64_t dout_ld, int64_t batch, int32_t n_nodes, int32_t d, float* dx,

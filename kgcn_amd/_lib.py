@@ -296,6 +296,14 @@ SIGNATURES = {
                                                  ctypes.c_void_p]),
     "kgcn_seq_convpool_scaled_fwd_f32": (ctypes.c_int, [ctypes.c_void_p, c_i32, c_i32, c_f32p, c_i32, c_f32p, c_i32, c_i32, c_f32p,
                                                         c_f32p, c_i32, c_i32, c_i32, c_f32p, ctypes.c_void_p, ctypes.c_void_p]),
+    "kgcn_seq_convpool_perturbed_fwd_f32": (ctypes.c_int, [ctypes.c_void_p, c_i32, c_i32, c_f32p, c_f32p, c_i32p, c_i32p, ctypes.c_uint64,
+                                                           c_i32, c_f32p, c_i32, c_i32, c_f32p, c_f32p, c_i32, c_i32, c_i32, c_f32p,
+                                                           ctypes.c_void_p, ctypes.c_void_p]),
+    # perturbed inputs of the smooth attribution methods (csrc/igprep.hip)
+    "kgcn_ig_perturb_rows_f32": (ctypes.c_int, [c_f32p, c_i64, c_i32, c_i32, c_i32, c_f32p, c_f32p, c_i32p, c_i32p, ctypes.c_uint32,
+                                                ctypes.c_uint64, c_f32p, ctypes.c_void_p]),
+    "kgcn_ig_perturb_values_f32": (ctypes.c_int, [c_i32p, c_i32, c_i32, c_i64, c_i32, c_f32p, c_f32p, c_f32p, c_i32p, c_i32p,
+                                                  ctypes.c_uint32, ctypes.c_uint64, c_f32p, ctypes.c_void_p]),
     "kgcn_seq_convpool_input_grad_f32": (ctypes.c_int, [ctypes.c_void_p, c_i32, c_i32, c_i32, c_f32p, c_i32, c_i32, c_f32p, c_i32,
                                                         c_i32, c_i32, c_f32p, ctypes.c_void_p, c_f32p, c_i32, c_f32p,
                                                         ctypes.c_void_p]),

@@ -19,10 +19,13 @@
 //              the scaled forward is the conv-pool with batch row b reading token row b / rep and its embedding rows times
 //              scale[b]; the input gradient routes d pooled through the arg-max bytes and forms the gradient with respect to the
 //              scaled embedded input, summed over the rep copies of every compound with per-row weights, optionally times the
-//              embedding row (the attribution itself).  It forms no weight gradient.
+//              embedding row (the attribution itself).  It forms no weight gradient.  The smooth methods (:235-259) add noise to
+//              the embedded input: a third staging mode draws sigma[b] * N(0, 1) per window element from a counter-based
+//              stream keyed by (seed, compound, sample, position, column), so the noisy input is never written either.
 // Every second stage is a parameter gradient and goes through reduce_or_defer (kgcn_reduce_defer).  No float atomics: results
 // are bitwise reproducible.
 #include "kgcn_common.h"
+#include "philox.h"
 
 namespace kgcn {
 
@@ -42,12 +45,21 @@ struct ConvArgs {
   long tiles;           // B * ceil(T / kTile)
   const float* scale;   // [B] per-row factor of the gathered embedding (scaled forward only)
   int rep;              // batch row b reads token row b / rep (scaled forward and input gradient; 1 otherwise)
+  const float* sigma;   // [B] noise scale of the row (perturbed forward only, as the next three)
+  const int32_t* sample;   // [B] sample number k of the row
+  const int32_t* ids;   // [B / rep] dataset index g of the token row
+  uint64_t seed;
 };
 
-// window of conv-input rows of tile (b, t0): rows r = 0 .. nrows-1 are sequence positions l = t0 p - padL + r.  kScaled: row b
-// reads token row b / rep and its embedding rows times scale[b] (the scaled [B, L, E] input is never written)
-template <bool kScaled = false>
+// window of conv-input rows of tile (b, t0): rows r = 0 .. nrows-1 are sequence positions l = t0 p - padL + r.  kStageScaled: row b
+// reads token row b / rep and its embedding rows times scale[b] (the scaled [B, L, E] input is never written).  kStagePerturbed:
+// the same plus sigma[b] times the attribution noise of stream KGCN_IG_STREAM_SEQUENCE (philox.h), keyed by the ABSOLUTE
+// position l (row l of the [L, E] array), so neighbouring tiles regenerate identical halo rows; padding positions and the
+// columns e >= E stay exactly 0, and a row with sigma[b] == 0 takes the scaled expression and draws nothing
+enum { kStagePlain = 0, kStageScaled = 1, kStagePerturbed = 2 };
+template <int kMode = kStagePlain>
 __device__ __forceinline__ void stage_window(const ConvArgs& a, int b, int t0, int nrows, float* win, int* twin) {
+  constexpr bool kScaled = kMode != kStagePlain;
   const int l0 = t0 * a.p - a.padL;
   const long trow = kScaled ? (long)(b / a.rep) : (long)b;
   for (int i = threadIdx.x; i < nrows; i += blockDim.x) {
@@ -56,6 +68,30 @@ __device__ __forceinline__ void stage_window(const ConvArgs& a, int b, int t0, i
   }
   __syncthreads();
   const float sc = kScaled ? a.scale[b] : 1.f;
+  if constexpr (kMode == kStagePerturbed) {
+    const float sg = a.sigma[b];
+    if (sg != 0.f) {                             // uniform over the workgroup
+      const int E4q = a.E4 >> 2;                 // Philox blocks per row = ceil(E / 4)
+      const uint32_t g = (uint32_t)a.ids[trow], smp = (uint32_t)a.sample[b];
+      for (int i = threadIdx.x; i < nrows * E4q; i += blockDim.x) {
+        const int r = i / E4q, q = i - r * E4q;
+        const int s = twin[r];
+        f32x4 o = {0.f, 0.f, 0.f, 0.f};
+        if (s >= 0) {
+          float z[4];
+          ig_noise4(a.seed, KGCN_IG_STREAM_SEQUENCE, g, smp, (uint64_t)((long)(l0 + r) * E4q + q), z);
+          const float* tp = a.table + (long)s * a.E;
+          const int e = 4 * q;
+          o.x = fmaf(sg, z[0], tp[e] * sc);
+          if (e + 1 < a.E) o.y = fmaf(sg, z[1], tp[e + 1] * sc);
+          if (e + 2 < a.E) o.z = fmaf(sg, z[2], tp[e + 2] * sc);
+          if (e + 3 < a.E) o.w = fmaf(sg, z[3], tp[e + 3] * sc);
+        }
+        *reinterpret_cast<f32x4*>(win + r * a.E4 + 4 * q) = o;
+      }
+      return;
+    }
+  }
   for (int i = threadIdx.x; i < nrows * a.E4; i += blockDim.x) {
     const int r = i / a.E4, e = i - r * a.E4;
     const int s = twin[r];
@@ -65,7 +101,7 @@ __device__ __forceinline__ void stage_window(const ConvArgs& a, int b, int t0, i
 }
 
 // lane = filter f (< 64), wave = 4 pooled positions of the tile; acc[i][j] = conv at position (t0 + 4 wave + i) p + j
-template <bool kScaled>
+template <int kMode>
 __global__ __launch_bounds__(256) void convpool_fwd_kernel(ConvArgs a, const float* __restrict__ bias, float* __restrict__ out,
                                                            uint8_t* __restrict__ argmax) {
   extern __shared__ float lds[];
@@ -84,7 +120,7 @@ __global__ __launch_bounds__(256) void convpool_fwd_kernel(ConvArgs a, const flo
   for (long tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
     const int b = (int)(tile / tpb), t0 = (int)(tile - (long)b * tpb) * kTile;
     __syncthreads();                            // the previous tile's window is no longer read
-    stage_window<kScaled>(a, b, t0, nrows, win, twin);
+    stage_window<kMode>(a, b, t0, nrows, win, twin);
     __syncthreads();
     float acc[4][8];
 #pragma unroll
@@ -251,6 +287,7 @@ int conv_args(const int32_t* tokens, int32_t B, int32_t L, const float* table, i
   a.B = B; a.L = L; a.S = S; a.E = E; a.E4 = round4(E); a.F = F; a.k = k; a.p = p; a.padL = (k - 1) / 2; a.T = L / p;
   a.tiles = (long)B * ((a.T + kTile - 1) / kTile);
   a.scale = nullptr; a.rep = 1;
+  a.sigma = nullptr; a.sample = nullptr; a.ids = nullptr; a.seed = 0;
   return 0;
 }
 
@@ -637,9 +674,9 @@ extern "C" int kgcn_seq_convpool_fwd_f32(const int32_t* tokens, int32_t batch, i
   if (a.tiles == 0) return 0;
   if (!bias || !out) return fail("%s: NULL operand", who);
   const size_t lds = convpool_fwd_lds(a);
-  if (int rc = allow_full_lds<convpool_fwd_kernel<false>>(lds, "seq kernels")) return rc;
+  if (int rc = allow_full_lds<convpool_fwd_kernel<kStagePlain>>(lds, "seq kernels")) return rc;
   const int grid = (int)(a.tiles < kConvGridFwd ? a.tiles : kConvGridFwd);
-  hipLaunchKernelGGL(convpool_fwd_kernel<false>, dim3(grid), dim3(256), lds, as_stream(stream), a, bias, out, argmax);
+  hipLaunchKernelGGL(convpool_fwd_kernel<kStagePlain>, dim3(grid), dim3(256), lds, as_stream(stream), a, bias, out, argmax);
   return check_launch("convpool_fwd_kernel");
 }
 
@@ -691,10 +728,29 @@ extern "C" int kgcn_seq_convpool_scaled_fwd_f32(const int32_t* tokens, int32_t b
   if (!bias || !out || !scale) return fail("%s: NULL operand", who);
   a.scale = scale; a.rep = rep;
   const size_t lds = convpool_fwd_lds(a);
-  if (int rc = allow_full_lds<convpool_fwd_kernel<true>>(lds, "seq kernels")) return rc;
+  if (int rc = allow_full_lds<convpool_fwd_kernel<kStageScaled>>(lds, "seq kernels")) return rc;
   const int grid = (int)(a.tiles < kConvGridFwd ? a.tiles : kConvGridFwd);
-  hipLaunchKernelGGL(convpool_fwd_kernel<true>, dim3(grid), dim3(256), lds, as_stream(stream), a, bias, out, argmax);
+  hipLaunchKernelGGL(convpool_fwd_kernel<kStageScaled>, dim3(grid), dim3(256), lds, as_stream(stream), a, bias, out, argmax);
   return check_launch("convpool_fwd_kernel<scaled>");
+}
+
+extern "C" int kgcn_seq_convpool_perturbed_fwd_f32(const int32_t* tokens, int32_t batch, int32_t rep, const float* scale,
+                                                   const float* sigma, const int32_t* sample, const int32_t* ids, uint64_t seed,
+                                                   int32_t length, const float* table, int32_t symbols, int32_t embed_dim,
+                                                   const float* w, const float* bias, int32_t kernel_size, int32_t filters,
+                                                   int32_t pool, float* out, uint8_t* argmax, void* stream) {
+  const char* who = "kgcn_seq_convpool_perturbed_fwd_f32";
+  ConvArgs a;
+  if (int rc = rep_args(batch, rep, who)) return rc;
+  if (int rc = conv_args(tokens, batch, length, table, symbols, embed_dim, w, kernel_size, filters, pool, who, a)) return rc;
+  if (a.tiles == 0) return 0;
+  if (!bias || !out || !scale || !sigma || !sample || !ids) return fail("%s: NULL operand", who);
+  a.scale = scale; a.rep = rep; a.sigma = sigma; a.sample = sample; a.ids = ids; a.seed = seed;
+  const size_t lds = convpool_fwd_lds(a);
+  if (int rc = allow_full_lds<convpool_fwd_kernel<kStagePerturbed>>(lds, "seq kernels")) return rc;
+  const int grid = (int)(a.tiles < kConvGridFwd ? a.tiles : kConvGridFwd);
+  hipLaunchKernelGGL(convpool_fwd_kernel<kStagePerturbed>, dim3(grid), dim3(256), lds, as_stream(stream), a, bias, out, argmax);
+  return check_launch("convpool_fwd_kernel<perturbed>");
 }
 
 extern "C" int kgcn_seq_convpool_input_grad_f32(const int32_t* tokens, int32_t batch, int32_t rep, int32_t length, const float* table,

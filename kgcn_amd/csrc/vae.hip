@@ -21,17 +21,7 @@
 namespace kgcn {
 
 namespace {
-// two 64-bit words -> two N(0, 1): u1 = (top 24 bits + 1) 2^-24 in (0, 1], u2 = top 24 bits 2^-24 in [0, 1)
-__device__ __forceinline__ void box_muller(uint64_t w0, uint64_t w1, float& n0, float& n1) {
-  const float u1 = (float)((w0 >> 40) + 1) * 0x1p-24f;
-  const float u2 = (float)(w1 >> 40) * 0x1p-24f;
-  const float r = sqrtf(-2.0f * logf(u1));
-  float s, c;
-  sincospif(2.0f * u2, &s, &c);
-  n0 = r * c;
-  n1 = r * s;
-}
-
+// box_muller: philox.h
 __device__ __forceinline__ float normal_at(uint64_t seed, uint64_t step, long e) {
   const Philox4 p = philox4x64_10((uint64_t)(e >> 2), step, seed);
   const int q = (int)(e & 3);

@@ -683,13 +683,21 @@ class SequenceEncoder(nn.Module):
         pooled = ops.seq_conv_pool(tokens, self.embeddings, self.conv_kernel, self.conv_bias, self.pool)
         return ops.seq_lstm(pooled, self.kernel, self.recurrent_kernel, self.bias, self.recurrent_activation, out=out, out_col=out_col)
 
-    def scaled(self, tokens, scale, rep, out=None, out_col=0, input_grad=False):
+    def scaled(self, tokens, scale, rep, out=None, out_col=0, input_grad=False, noise=None):
         """The branch on rep copies of every token row [C, L], copy b with its embedded input times scale[b] (the reference's
         feed_embedded_layer placeholder fed with add_perturbation, kgcn/feed.py:219-232) -> (h [C rep, H], pooled, arg-max bytes).
         input_grad: pooled is returned as a leaf that requires grad and the arg-max bytes are kept, so that the caller can take
-        d pooled through the LSTM and hand it to ops.seq_conv_pool_input_grad; the parameters get no gradient from this path."""
-        pooled, arg = ops.seq_conv_pool_scaled(tokens, self.embeddings.detach(), self.conv_kernel.detach(), self.conv_bias.detach(),
-                                               self.pool, scale, rep, argmax=input_grad)
+        d pooled through the LSTM and hand it to ops.seq_conv_pool_input_grad; the parameters get no gradient from this path.
+        noise = (sigma [C rep], sample [C rep], ids [C], seed): add_perturbation's enabled_noise, drawn inside the conv-pool
+        (ops.seq_conv_pool_perturbed); None keeps the clean kernel."""
+        if noise is None:
+            pooled, arg = ops.seq_conv_pool_scaled(tokens, self.embeddings.detach(), self.conv_kernel.detach(), self.conv_bias.detach(),
+                                                   self.pool, scale, rep, argmax=input_grad)
+        else:
+            sigma, sample, ids, seed = noise
+            pooled, arg = ops.seq_conv_pool_perturbed(tokens, self.embeddings.detach(), self.conv_kernel.detach(),
+                                                      self.conv_bias.detach(), self.pool, scale, rep, sigma, sample, ids, seed,
+                                                      argmax=input_grad)
         if input_grad:
             pooled.requires_grad_(True)
         h = ops.seq_lstm(pooled, self.kernel, self.recurrent_kernel, self.bias, self.recurrent_activation, out=out, out_col=out_col)

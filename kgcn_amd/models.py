@@ -427,9 +427,10 @@ class MultimodalGCN(nn.Module):
     def forward(self, features, adjs, sequences=None, enabled_node_nums=None, sequence_scale=None, sequence_rep=1):
         return self.run(features, adjs, sequences, sequence_scale, sequence_rep)[0]
 
-    def run(self, features, adjs, sequences, sequence_scale=None, sequence_rep=1, input_grad=False):
+    def run(self, features, adjs, sequences, sequence_scale=None, sequence_rep=1, input_grad=False, sequence_noise=None):
         """forward() -> (logits, pooled, arg-max bytes); the last two are None on the default path, and with sequence_scale they are
-        what SequenceEncoder.scaled returns (input_grad: pooled is a leaf that requires grad)."""
+        what SequenceEncoder.scaled returns (input_grad: pooled is a leaf that requires grad).  sequence_noise (with
+        sequence_scale only) is SequenceEncoder.scaled's noise = (sigma, sample, ids, seed)."""
         if sequences is None:
             raise ValueError("MultimodalGCN needs the sequences= token batch")
         adj = layers._pack(adjs, features)
@@ -441,9 +442,12 @@ class MultimodalGCN(nn.Module):
         joined = features.new_empty((B, self.SEQ_WIDTH + self.GRAPH_WIDTH))
         pooled = arg = None
         if sequence_scale is None:
+            if sequence_noise is not None:
+                raise ValueError("sequence_noise needs sequence_scale")
             seq = self.sequence(sequences, out=joined, out_col=0)
         else:
-            seq, pooled, arg = self.sequence.scaled(sequences, sequence_scale, rep, out=joined, out_col=0, input_grad=input_grad)
+            seq, pooled, arg = self.sequence.scaled(sequences, sequence_scale, rep, out=joined, out_col=0, input_grad=input_grad,
+                                                    noise=sequence_noise)
         node = self.dense(self.conv(features, adj=adj))
         graph = ops.graph_gather_into(node, joined, self.SEQ_WIDTH)
         layer = ops.join_columns(joined, [seq, graph])                                            # :96 tf.concat

@@ -2121,6 +2121,109 @@ def seq_conv_pool_scaled(tokens, table, w, bias, pool, scale, rep, argmax=False)
     return out, arg
 
 
+# noise streams of the smooth attribution methods (KGCN_IG_STREAM_* of include/kgcn_hip.h)
+IG_STREAM_FEATURES, IG_STREAM_ADJACENCY, IG_STREAM_SEQUENCE = 0, 1, 0x100
+
+
+def _i32_row(v, name, n, device):
+    """ids / sample numbers -> int32 device tensor [n].  The kernels read them as unsigned 32-bit counter words
+    (include/kgcn_hip.h): a host sequence is checked to lie in 0 .. 2^31 - 1; a device tensor is passed as it is, without the
+    device -> host read a check would need, and a negative entry there is the counter word 2^32 + v."""
+    if torch.is_tensor(v) and v.is_cuda:
+        if v.dtype != torch.int32:
+            raise _lib.KgcnHipError("%s must be int32 on the device" % name)
+        t = v.reshape(-1).contiguous()
+    else:
+        import numpy as np
+        a = np.asarray(v.cpu().numpy() if torch.is_tensor(v) else v).reshape(-1)
+        if a.size and (a.min() < 0 or a.max() > 2 ** 31 - 1):
+            raise _lib.KgcnHipError("%s outside 0..2^31-1" % name)
+        t = torch.as_tensor(a.astype(np.int32), device=device)
+    if t.numel() != n:
+        raise _lib.KgcnHipError("%d %s for %d rows" % (t.numel(), name, n))
+    return t
+
+
+def _perturb_operands(scale, sigma, sample, ids, n_ids, seed):
+    """scale / sigma [B] fp32, sample [B], ids [n_ids(B)] -> validated device operands; sigma may be a number (every row)."""
+    scale = _f32c(scale, "scale").reshape(-1)
+    B = scale.numel()
+    if not torch.is_tensor(sigma):
+        if float(sigma) < 0.0:
+            raise _lib.KgcnHipError("noise scale %r is negative" % (sigma,))
+        sigma = torch.full((B,), float(sigma), device=scale.device, dtype=torch.float32)
+    sigma = _f32c(sigma, "sigma").reshape(-1)
+    if sigma.numel() != B:
+        raise _lib.KgcnHipError("%d sigmas for %d rows" % (sigma.numel(), B))
+    sample = _i32_row(sample, "sample numbers", B, scale.device)
+    ids = _i32_row(ids, "ids", n_ids(B), scale.device)
+    return scale, sigma, sample, ids, B, int(seed) & (2 ** 64 - 1)
+
+
+def ig_perturb(x, scale, sigma, sample, ids, rep, stream, seed):
+    """rep perturbed copies of every [R, W] array of x [C, R, W] (smooth_grad / smooth_ig, kgcn/feed.py:88-89 add_perturbation
+    with the noise drawn on the device): out[b] = x[b // rep] * scale[b] + sigma[b] * z with z the N(0, 1) noise of
+    (seed, stream, compound ids[b // rep], sample sample[b]) defined in include/kgcn_hip.h -> [C rep, R, W].  A row with
+    sigma[b] == 0 is x * scale[b] exactly.  sigma: a [C rep] tensor or one non-negative number."""
+    x = _f32c(x, "x")
+    if x.dim() != 3:
+        raise _lib.KgcnHipError("x must be [compounds, rows, width], got %s" % (tuple(x.shape),))
+    C, R, W = x.shape
+    rep = int(rep)
+    if rep < 1:
+        raise _lib.KgcnHipError("%d copies per compound" % rep)
+    scale, sigma, sample, ids, B, seed = _perturb_operands(scale, sigma, sample, ids, lambda b: C, seed)
+    if B != C * rep:
+        raise _lib.KgcnHipError("%d rows are not %d copies of %d compounds" % (B, rep, C))
+    out = torch.empty((B, R, W), device=x.device, dtype=torch.float32)
+    check(lib.kgcn_ig_perturb_rows_f32(ptr(x), B, rep, R, W, ptr(scale), ptr(sigma), ptr(sample), ptr(ids), int(stream), seed,
+                                       ptr(out), current_stream()), "kgcn_ig_perturb_rows_f32")
+    return out
+
+
+def ig_perturb_values(csr, values, scale, sigma, sample, ids, stream, seed):
+    """The same for the stored values [nnz] of one channel of a plain BatchedCSR: entry e of graph b (CSR order) becomes
+    values[e] * scale[b] + sigma[b] * z(ids[b], sample[b], column = position of e among graph b's entries); scale, sigma, sample
+    and ids are per graph.  -> [nnz]."""
+    if csr.row_pad != 0:
+        raise _lib.KgcnHipError("ig_perturb_values takes a plain batched CSR (row_pad 0)")
+    values = _f32c(values, "values").reshape(-1)
+    if values.numel() != csr.nnz:
+        raise _lib.KgcnHipError("%d values for %d stored entries" % (values.numel(), csr.nnz))
+    scale, sigma, sample, ids, B, seed = _perturb_operands(scale, sigma, sample, ids, lambda b: b, seed)
+    if B != csr.num_graphs:
+        raise _lib.KgcnHipError("%d scales for %d graphs" % (B, csr.num_graphs))
+    out = torch.empty_like(values)
+    check(lib.kgcn_ig_perturb_values_f32(ptr(csr.rowptr), csr.num_graphs, csr.rows, csr.nnz, csr.max_nnz, ptr(values), ptr(scale),
+                                         ptr(sigma), ptr(sample), ptr(ids), int(stream), seed, ptr(out), current_stream()),
+          "kgcn_ig_perturb_values_f32")
+    return out
+
+
+def seq_conv_pool_perturbed(tokens, table, w, bias, pool, scale, rep, sigma, sample, ids, seed, argmax=False):
+    """seq_conv_pool_scaled with noise on the embedded input: the window element at position l, column e of row b is
+    table[tokens[b // rep, l], e] * scale[b] + sigma[b] * z, z the N(0, 1) noise of (seed, stream IG_STREAM_SEQUENCE, compound
+    ids[b // rep], sample sample[b], row l, column e) (include/kgcn_hip.h), drawn inside the window staging: the noisy
+    [C rep, L, E] input is never written.  Rows with sigma[b] == 0 are exactly seq_conv_pool_scaled's.  ops.seq_conv_pool_input_grad
+    takes the result as it takes the scaled forward's."""
+    C = tokens.shape[0] if torch.is_tensor(tokens) and tokens.dim() == 2 else 0
+    scale, sigma, sample, ids, B, seed = _perturb_operands(scale, sigma, sample, ids, lambda b: C, seed)
+    tokens, table, w, rep = _seq_conv_operands(tokens, table, w, pool, B, rep)
+    b = _f32c(bias, "conv bias").reshape(-1)
+    S, E = table.shape
+    k, F = w.shape[0], w.shape[2]
+    if b.numel() != F:
+        raise _lib.KgcnHipError("conv bias %s does not match %d filters" % (tuple(bias.shape), F))
+    L = tokens.shape[1]
+    T = L // int(pool)
+    out = torch.empty((B, T, F), device=table.device, dtype=torch.float32)
+    arg = torch.empty((B, T, F), device=table.device, dtype=torch.uint8) if argmax else None
+    check(lib.kgcn_seq_convpool_perturbed_fwd_f32(ptr(tokens), B, rep, ptr(scale), ptr(sigma), ptr(sample), ptr(ids), seed, L, ptr(table),
+                                                  S, E, ptr(w), ptr(b), k, F, int(pool), ptr(out), ptr(arg), current_stream()),
+          "kgcn_seq_convpool_perturbed_fwd_f32")
+    return out, arg
+
+
 def seq_conv_pool_input_grad(dout, argmax, tokens, table, w, pool, rep, row_weight=None, times_table=False):
     """Gradient with respect to the scaled embedded input of seq_conv_pool_scaled, summed over the rep copies of every token
     row: d pooled [C rep, L // pool, F] and its arg-max bytes -> [C, L, E], the sum in copy order of row_weight[b] (None = 1)

@@ -14,10 +14,14 @@ import torch
 
 
 def integrated_gradients(score_fn, features, adjacency, divide_number=100, modal=("features", "adjs"),
-                         perturbation=None, method="ig"):
+                         perturbation=None, method="ig", noise_scale=0.1, seed=1234):
     """Returns {"features": [B, N, F] tensor, "adjs": [nnz] tensor in the CSR order of channel 0,
     "sum_of_ig": float, "start_score": f(scale 0), "end_score": f(scale 1)} (only the requested modals).
-    For method "ig" the completeness check of the reference (:262-275) is sum_of_ig ~ end - start."""
+    For method "ig" the completeness check of the reference (:262-275) is sum_of_ig ~ end - start.
+    "smooth_grad" / "smooth_ig" (:235-259): D noisy steps, step k at scale 1 (smooth_grad) or (k + 1) / D (smooth_ig) plus N(0, noise_scale) noise drawn
+    on the device (ops.ig_perturb / ops.ig_perturb_values, the noise of include/kgcn_hip.h with compound g = the batch row
+    and sample k = the step, streams 0 and 1); the mean gradient, for smooth_ig times the clean data.  start_score and end_score
+    come from clean inputs."""
     modal = tuple(modal)
     pert = modal if perturbation is None else tuple(perturbation)
     base_vals = [c.values for c in adjacency.channels]
@@ -28,11 +32,22 @@ def integrated_gradients(score_fn, features, adjacency, divide_number=100, modal
     if "adjs" in modal:
         ig["adjs"] = torch.zeros_like(base_vals[0])
 
-    def grads_at(scale):
-        x = (x0 * scale if "features" in pert else x0).clone().requires_grad_("features" in modal)
+    def grads_at(scale, sample=None):
         vals = [v.clone() for v in base_vals]
-        if "adjs" in pert:
-            vals[0] = vals[0] * scale
+        if sample is None:
+            x = (x0 * scale if "features" in pert else x0).clone().requires_grad_("features" in modal)
+            if "adjs" in pert:
+                vals[0] = vals[0] * scale
+        else:                                            # step `sample` of a smooth method: scale and noise in one launch
+            from . import ops
+            B = x0.shape[0]
+            sc = torch.full((B,), float(scale), device=x0.device, dtype=torch.float32)
+            smp, rows = [int(sample)] * B, list(range(B))
+            x = (ops.ig_perturb(x0, sc, noise_scale, smp, rows, 1, ops.IG_STREAM_FEATURES, seed) if "features" in pert
+                 else x0.clone()).requires_grad_("features" in modal)
+            if "adjs" in pert:
+                vals[0] = ops.ig_perturb_values(adjacency.channels[0], base_vals[0], sc, noise_scale, smp, rows,
+                                                ops.IG_STREAM_ADJACENCY, seed)
         vals[0] = vals[0].requires_grad_("adjs" in modal)
         score = score_fn(x, adjacency.with_values(vals))
         wrt = ([x] if "features" in modal else []) + ([vals[0]] if "adjs" in modal else [])
@@ -54,8 +69,18 @@ def integrated_gradients(score_fn, features, adjacency, divide_number=100, modal
         g, _ = grads_at(1.0)
         for m in ig:
             ig[m] += g[m] * data[m] if method == "grad_prod" else g[m]
+    elif method in SMOOTH_METHODS:
+        D = int(divide_number)
+        if D < 1:
+            raise ValueError("divide_number must be >= 1")
+        if not float(noise_scale) >= 0.0:
+            raise ValueError("noise_scale must be >= 0, got %r" % (noise_scale,))
+        for k in range(D):
+            g, _ = grads_at((k + 1) / float(D) if method == "smooth_ig" else 1.0, sample=k)
+            for m in ig:
+                ig[m] += g[m] * data[m] / float(D) if method == "smooth_ig" else g[m] / float(D)
     else:
-        raise ValueError("unsupported method %r (ig, grad_prod, grad)" % (method,))
+        raise ValueError("unsupported method %r (%s)" % (method, ", ".join(IG_METHODS + SMOOTH_METHODS)))
     with torch.no_grad():
         xs = x0 * 0.0 if "features" in pert else x0
         vs = [v.clone() for v in base_vals]
@@ -100,6 +125,26 @@ def ig_scales(method, divide_number):
         return [0.0, 1.0], [0.0, 1.0]
     raise ValueError("unsupported method %r (%s; smooth_grad / smooth_ig draw host noise and are not supported)"
                      % (method, ", ".join(IG_METHODS)))
+
+
+SMOOTH_METHODS = ("smooth_grad", "smooth_ig")
+
+
+def smooth_rows(method, divide_number, noise_scale):
+    """The copies of one compound for 'smooth_grad' / 'smooth_ig' (:235-259) -> (scales, sigmas, samples, weights, start_row,
+    end_row), D + 2 rows: row 0 (scale 0) and row 1 (scale 1) are clean and carry weight 0 -- they give start_score and end_score,
+    which the reference takes from clean feeds (:279-286); row 2 + k is sample k with noise N(0, noise_scale), weight 1 / D and
+    scale 1 (smooth_grad) or (k + 1) / D (smooth_ig)."""
+    if method not in SMOOTH_METHODS:
+        raise ValueError("smooth_rows: method must be one of %s, got %r" % (", ".join(SMOOTH_METHODS), method))
+    D = int(divide_number)
+    if D < 1:
+        raise ValueError("divide_number must be >= 1")
+    ns = float(noise_scale)
+    if not ns >= 0.0:
+        raise ValueError("noise_scale must be >= 0, got %r" % (noise_scale,))
+    scales = [0.0, 1.0] + [1.0 if method == "smooth_grad" else (k + 1) / float(D) for k in range(D)]
+    return scales, [0.0, 0.0] + [ns] * D, [0, 0] + list(range(D)), [0.0, 0.0] + [1.0 / D] * D, 0, 1
 
 
 def ig_modal_targets(modal):
@@ -174,55 +219,100 @@ def _entry_graphs(csr):
     return torch.div(rows, csr.rows, rounding_mode="floor")
 
 
-def _attribute(model, dataset, tokens, ids, scales, weights, targets, masks, method, table, conv_w, pool):
-    """One forward + backward over len(ids) compounds x len(scales) copies -> per compound: IG arrays (unmultiplied by the data
-    for 'grad'), start and end score.  masks [C, K] selects the target class(es) of each compound."""
+def _copy_grads(model, dataset, tokens, ids, scales, targets, masks, noise=None, need_grad=True):
+    """One forward + backward over len(ids) compounds x len(scales) copies -> the per-copy quantities _reduce_copies sums: the clean
+    features x, the gradients with respect to the targeted inputs ('features' [B, N, F], 'adjs' channel 0 dense [B, N, N] beside
+    its data 'adjs_data', 'pooled' d pooled with its arg-max bytes 'arg' for the embedded sequence), the token rows and the score
+    [B].  masks [C, K] selects the target class(es) of each compound.  noise = (sigmas, samples, seed) per copy: the targeted
+    inputs are x * scale + sigma * z with z drawn on the device for (seed, dataset index, sample) (ops.ig_perturb,
+    ops.ig_perturb_values, ops.seq_conv_pool_perturbed); None is the clean path.  need_grad=False: the forward alone (a copy of
+    weight 0, run for its score), the gradients zero and the arg-max bytes 0xFF."""
     ids = [int(i) for i in ids]
     C, rep = len(ids), len(scales)
     dev = dataset.features.device
     sel = [i for i in ids for _ in range(rep)]
     adj, x = dataset.batch(sel)
     sc = torch.tensor(scales, dtype=torch.float32, device=dev).repeat(C)
-    wt = torch.tensor(weights, dtype=torch.float32, device=dev).repeat(C)
     ones = torch.ones_like(sc)
     N, F = x.shape[1], x.shape[2]
-    x_in = (x * sc.view(-1, 1, 1) if "features" in targets else x).requires_grad_("features" in targets)
+    want = lambda m: need_grad and m in targets
+    seq_noise = None
+    if noise is None:
+        x_in = (x * sc.view(-1, 1, 1) if "features" in targets else x).requires_grad_(want("features"))
+    else:
+        from . import ops
+        sg = torch.tensor(noise[0], dtype=torch.float32, device=dev).repeat(C)
+        smp = torch.tensor(noise[1], dtype=torch.int32, device=dev).repeat(C)
+        cid = torch.tensor(ids, dtype=torch.int32, device=dev)
+        seed = noise[2]
+        x_in = (ops.ig_perturb(x.view(C, rep, N, F)[:, 0], sc, sg, smp, cid, rep, ops.IG_STREAM_FEATURES, seed)
+                if "features" in targets else x).requires_grad_(want("features"))
+        seq_noise = (sg, smp, cid, seed)
     adj_in, v0 = adj, None
     if "adjs" in targets:                       # kgcn/feed.py:116-121: the values of every channel are scaled
-        vals = [c.values * sc[_entry_graphs(c)] for c in adj.channels]
-        v0 = vals[0].requires_grad_(True)
+        if noise is None:
+            vals = [c.values * sc[_entry_graphs(c)] for c in adj.channels]
+        else:
+            rows = cid.repeat_interleave(rep)
+            vals = [ops.ig_perturb_values(c, c.values, sc, sg, smp, rows, ops.IG_STREAM_ADJACENCY + ch, seed)
+                    for ch, c in enumerate(adj.channels)]
+        v0 = vals[0].requires_grad_(need_grad)
         adj_in = adj.with_values(vals)
     emb = "embedded_layer" in targets
     tok = tokens[torch.as_tensor(ids, device=tokens.device)]
-    logits, pooled, arg = model.run(x_in, adj_in, tok, sc if emb else ones, rep, input_grad=emb)
-    score = (torch.softmax(logits, dim=1) * torch.as_tensor(masks, device=dev).repeat_interleave(rep, 0)).sum(1)
-    wrt = ([x_in] if "features" in targets else []) + ([v0] if "adjs" in targets else []) + ([pooled] if emb else [])
-    grads = list(torch.autograd.grad(score.sum(), wrt))
-    out = {}
-    wv = wt.view(C, rep)
+    with torch.set_grad_enabled(need_grad):
+        logits, pooled, arg = model.run(x_in, adj_in, tok, sc if emb else ones, rep, input_grad=want("embedded_layer"),
+                                        sequence_noise=seq_noise if emb else None)
+        score = (torch.softmax(logits, dim=1) * torch.as_tensor(masks, device=dev).repeat_interleave(rep, 0)).sum(1)
+    gr = {"x": x, "tok": tok, "score": score.detach()}
+    grads = []
+    if need_grad:
+        wrt = ([x_in] if "features" in targets else []) + ([v0] if "adjs" in targets else []) + ([pooled] if emb else [])
+        grads = list(torch.autograd.grad(score.sum(), wrt))
     if "features" in targets:
-        g = grads.pop(0)
-        ig = (g.view(C, rep, N, F) * wv.view(C, rep, 1, 1)).sum(1)
-        out["features"] = ig if method == "grad" else ig * x.view(C, rep, N, F)[:, 0]
+        gr["features"] = grads.pop(0) if need_grad else torch.zeros_like(x)
     if "adjs" in targets:
-        g = grads.pop(0)
         c0 = adj.channels[0]
-        dense_g = values_to_dense(c0, g).view(C, rep, c0.rows, c0.cols)
-        ig = (dense_g * wv.view(C, rep, 1, 1)).sum(1)
-        data = values_to_dense(c0, c0.values).view(C, rep, c0.rows, c0.cols)[:, 0]
-        out["adjs"] = ig if method == "grad" else ig * data
-        out["adjs_data"] = data
+        gr["adjs_data"] = values_to_dense(c0, c0.values)
+        gr["adjs"] = values_to_dense(c0, grads.pop(0)) if need_grad else torch.zeros_like(gr["adjs_data"])
     if emb:
+        gr["pooled"] = grads.pop(0) if need_grad else torch.zeros_like(pooled)
+        gr["arg"] = arg if need_grad else torch.full(pooled.shape, 0xFF, dtype=torch.uint8, device=dev)
+    return gr
+
+
+def _reduce_copies(gr, C, weights, targets, method, table, conv_w, pool, ends=None):
+    """The copies of _copy_grads (C compounds x len(weights) copies, or as many one-copy results concatenated) -> per compound:
+    the weighted sums over the copies, in one fixed order for the batched and the per-step form alike (unmultiplied by the data
+    for 'grad' and 'smooth_grad'), start and end score (the copies ends = (start_row, end_row), default the first and the last)."""
+    rep = len(weights)
+    wt = torch.tensor(weights, dtype=torch.float32, device=gr["score"].device).repeat(C)
+    wv = wt.view(C, rep, 1, 1)
+    raw = method in ("grad", "smooth_grad")
+    out = {}
+    if "features" in targets:
+        N, F = gr["x"].shape[1], gr["x"].shape[2]
+        ig = (gr["features"].view(C, rep, N, F) * wv).sum(1)
+        out["features"] = ig if raw else ig * gr["x"].view(C, rep, N, F)[:, 0]
+    if "adjs" in targets:
+        M, K = gr["adjs"].shape[1], gr["adjs"].shape[2]
+        ig = (gr["adjs"].view(C, rep, M, K) * wv).sum(1)
+        data = gr["adjs_data"].view(C, rep, M, K)[:, 0]
+        out["adjs"] = ig if raw else ig * data
+        out["adjs_data"] = data
+    if "embedded_layer" in targets:
         from . import ops
-        out["embedded_layer"] = ops.seq_conv_pool_input_grad(grads.pop(0), arg, tok, table, conv_w, pool, rep, row_weight=wt,
-                                                             times_table=method != "grad")
-    s = score.detach().view(C, rep)
-    out["start"], out["end"] = s[:, 0], s[:, rep - 1]
+        out["embedded_layer"] = ops.seq_conv_pool_input_grad(gr["pooled"], gr["arg"], gr["tok"], table, conv_w, pool, rep,
+                                                             row_weight=wt, times_table=not raw)
+    s = gr["score"].view(C, rep)
+    start_row, end_row = (0, rep - 1) if ends is None else ends
+    out["start"], out["end"] = s[:, start_row], s[:, end_row]
     return out
 
 
 def multimodal_integrated_gradients(model, features, adjacency, tokens, labels=None, divide_number=100, modal="all", method="ig",
-                                    label_target="max", chunk=None, compounds=None, sequence_symbol=None, batched=True):
+                                    label_target="max", chunk=None, compounds=None, sequence_symbol=None, batched=True,
+                                    noise_scale=0.1, seed=1234):
     """Integrated gradients of models.MultimodalGCN (kgcn visualize on example_model/model_multimodal.py, cal_feature_IG and
     CompoundVisualizer of kgcn/visualization.py) -> one dict per visualised compound with the keys the reference dumps:
     features [N, F], adjs [N, N] (channel 0, dense), embedded_layer [L, E] and their *_IG arrays (the modals named by `modal`),
@@ -233,10 +323,16 @@ def multimodal_integrated_gradients(model, features, adjacency, tokens, labels=N
     (features None); tokens int32 [G, L] device tensor (data_util.sequence_table); labels [G, K] (needed by label_target 'label',
     'correct', 'uncorrect').  The target class comes from an unscaled forward pass, the score is its softmax probability.
     The D + 1 scaled copies of every compound (ig_scales) run as batch rows of ONE forward and ONE backward, `chunk` compounds
-    (default IG_ROWS_PER_CHUNK // (D + 1)) at a time; this is valid only because the model mixes no rows, and any other model is
+    (default IG_ROWS_PER_CHUNK // copies) at a time; this is valid only because the model mixes no rows, and any other model is
     refused.  The embedded-sequence attribution comes from the HIP input-gradient kernel (ops.seq_conv_pool_input_grad), which
     sums the copies in order.  batched=False runs the reference's loop instead: one batch-1 pass per compound and step through the
-    same ops, summed on the host in step order."""
+    same ops (forward only for a copy of weight 0), the per-step gradients summed by the reduction the batched form uses.
+    method 'smooth_grad' / 'smooth_ig' (:235-259): D noisy samples per compound beside two clean copies (smooth_rows, D + 2 rows),
+    the targeted inputs being x * scale + N(0, noise_scale) (kgcn/feed.py:88, gcn.py:661 default 0.1; the values of every
+    adjacency channel when 'adjs' is a target).  The noise is drawn on the device from (seed, dataset index of the compound,
+    sample number) -- include/kgcn_hip.h -- so chunking, `compounds` subsets and batched=False all see the same values; the
+    embedded sequence is perturbed inside the conv-pool's window staging (ops.seq_conv_pool_perturbed).  smooth_grad returns the
+    mean gradient, smooth_ig the mean gradient times the clean data; check_score comes from the two clean copies."""
     import numpy as np
     import string
     from . import models
@@ -245,7 +341,14 @@ def multimodal_integrated_gradients(model, features, adjacency, tokens, labels=N
         raise TypeError("multimodal_integrated_gradients batches the scaled copies as rows: it needs a model whose rows never "
                         "mix (models.MultimodalGCN), got %s" % type(model).__name__)
     targets = ig_modal_targets(modal)
-    scales, weights = ig_scales(method, divide_number)
+    if method in SMOOTH_METHODS:
+        scales, sigmas, samples, weights, start_row, end_row = smooth_rows(method, divide_number, noise_scale)
+        seed = int(seed)
+    elif method in IG_METHODS:
+        scales, weights = ig_scales(method, divide_number)
+        sigmas, start_row, end_row = None, 0, len(scales) - 1
+    else:
+        raise ValueError("unsupported method %r (%s)" % (method, ", ".join(IG_METHODS + SMOOTH_METHODS)))
     if isinstance(adjacency, DeviceGraphDataset):
         dataset = adjacency
     else:
@@ -283,29 +386,24 @@ def multimodal_integrated_gradients(model, features, adjacency, tokens, labels=N
     try:
         for p, _ in frozen:
             p.requires_grad_(False)
+        noise = None if sigmas is None else (sigmas, samples, seed)
         if batched:
             for i in range(0, len(jobs), chunk):
                 part = jobs[i:i + chunk]
-                out = _attribute(model, dataset, tokens, [j[0] for j in part], scales, weights, targets,
-                                 np.stack([j[5] for j in part]), method, table, conv_w, pool)
+                gr = _copy_grads(model, dataset, tokens, [j[0] for j in part], scales, targets, np.stack([j[5] for j in part]), noise)
+                out = _reduce_copies(gr, len(part), weights, targets, method, table, conv_w, pool, (start_row, end_row))
                 for k, j in enumerate(part):
                     res[j[0]] = {m: out[m][k] for m in out if m not in ("start", "end")}
                     res[j[0]]["start"], res[j[0]]["end"] = float(out["start"][k]), float(out["end"][k])
         else:
-            for j in jobs:
-                acc = {}
-                for s, w in zip(scales, weights):
-                    out = _attribute(model, dataset, tokens, [j[0]], [s], [w], targets, j[5][None], method, table, conv_w, pool)
-                    for m in out:
-                        if m in ("start", "end"):
-                            continue
-                        acc[m] = out[m][0] if m not in acc or m == "adjs_data" else acc[m] + out[m][0]
-                    if s == scales[0]:
-                        start = float(out["start"][0])
-                    if s == scales[-1]:
-                        end = float(out["end"][0])
-                acc["start"], acc["end"] = start, end
-                res[j[0]] = acc
+            for j in jobs:                                   # one batch-1 pass per copy; a copy of weight 0 runs forward only
+                rows = [_copy_grads(model, dataset, tokens, [j[0]], [s], targets, j[5][None],
+                                    None if noise is None else ([sigmas[r]], [samples[r]], seed), need_grad=w != 0.0)
+                        for r, (s, w) in enumerate(zip(scales, weights))]
+                gr = {k: rows[0][k] if k == "tok" else torch.cat([p[k] for p in rows]) for k in rows[0]}
+                out = _reduce_copies(gr, 1, weights, targets, method, table, conv_w, pool, (start_row, end_row))
+                res[j[0]] = {m: out[m][0] for m in out if m not in ("start", "end")}
+                res[j[0]]["start"], res[j[0]]["end"] = float(out["start"][0]), float(out["end"][0])
     finally:
         for p, r in frozen:
             p.requires_grad_(r)
