@@ -1,6 +1,6 @@
 // Library bookkeeping (error text, ABI version) and the small reductions of the path:
-// GraphGather (kgcn/layers.py:163-164) forward/backward and the dot product behind d eps of
-// GINAggregate (kgcn/layers.py:469).
+// GraphGather (kgcn/layers.py:163-164) forward/backward, also into / out of a column block of a wider
+// buffer, and the dot product behind d eps of GINAggregate (kgcn/layers.py:469).
 #include "kgcn_common.h"
 
 namespace kgcn {
@@ -275,6 +275,27 @@ extern "C" int kgcn_graph_gather_fwd_f32(const float* x, int64_t batch, int32_t 
 extern "C" int kgcn_graph_gather_fwd_ld_f32(const float* x, int64_t batch, int32_t n_nodes, int32_t d, float* out,
                                             int64_t out_ld, void* stream) {
   return gather_fwd_impl("kgcn_graph_gather_fwd_ld_f32", x, batch, n_nodes, d, out, out_ld, stream);
+}
+
+// d x[b, n, :] = g[b * g_ld + :d] -- the gradient of a GraphGather read-out that was written into a column block of a wider
+// buffer (model_multimodal.py:96 tf.concat), read where it lies
+__global__ void gather_bwd_ld_kernel(const float* __restrict__ g, long g_ld, long B, int N, int d, float* __restrict__ dx) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * N * d) return;
+  const long b = i / ((long)N * d);
+  const int c = (int)(i % d);
+  dx[i] = g[b * g_ld + c];
+}
+
+extern "C" int kgcn_graph_gather_bwd_ld_f32(const float* dout_grad, int64_t dout_ld, int64_t batch, int32_t n_nodes, int32_t d,
+                                            float* dx, void* stream) {
+  if (batch < 0 || n_nodes < 0 || d < 1 || dout_ld < d) return fail("kgcn_graph_gather_bwd_ld_f32: bad sizes");
+  const long n = (long)batch * n_nodes * d;
+  if (n == 0) return 0;
+  if (!dout_grad || !dx) return fail("kgcn_graph_gather_bwd_ld_f32: NULL operand");
+  hipLaunchKernelGGL(gather_bwd_ld_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), dout_grad, (long)dout_ld,
+                     (long)batch, n_nodes, d, dx);
+  return check_launch("gather_bwd_ld_kernel");
 }
 
 extern "C" int kgcn_graph_gather_bwd_f32(const float* dout_grad, int64_t batch, int32_t n_nodes,

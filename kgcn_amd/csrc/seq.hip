@@ -165,6 +165,11 @@ __global__ __launch_bounds__(256) void convpool_fwd_kernel(ConvArgs a, const flo
   }
 }
 
+// d pooled of output o as the conv gradient at offset j of its pool window: all of it where the arg-max byte says j, else 0
+__device__ __forceinline__ float routed_grad(const float* __restrict__ dout, const uint8_t* __restrict__ argmax, long o, int j) {
+  return argmax[o] == j ? dout[o] : 0.f;
+}
+
 // Backward.  Phase 1 (lane f, wave rows r = dk E + e): d W[r, f] += g * window[c + dk, e] for the routed position c of every
 // pooled output; d bias[f] += g.  Phase 2 (lane e, 8 groups over window rows): v[row, e] = sum_dk sum_f G[row - dk, f] W[dk, e, f]
 // with G the routed conv gradient of this tile.  Phase 3: group q adds v[row] into table row s = token(row) for s % 8 == q, rows
@@ -204,12 +209,7 @@ __global__ __launch_bounds__(256) void convpool_bwd_kernel(ConvArgs a, const flo
     for (int i = threadIdx.x; i < ncpos * F4p; i += blockDim.x) {
       const int c = i / F4p, fr = i - c * F4p;
       const int t = t0 + c / a.p, j = c % a.p;
-      float gv = 0.f;
-      if (fr < a.F && t < a.T) {
-        const long o = ((long)b * a.T + t) * a.F + fr;
-        if (argmax[o] == j) gv = dout[o];
-      }
-      g[i] = gv;
+      g[i] = (fr < a.F && t < a.T) ? routed_grad(dout, argmax, ((long)b * a.T + t) * a.F + fr, j) : 0.f;
     }
     __syncthreads();
     // phase 1
@@ -302,6 +302,21 @@ size_t convpool_bwd_lds(const ConvArgs& a, bool table_in_lds) {
 }
 int convpool_bwd_grid(const ConvArgs& a) { return (int)(a.tiles < kConvGridBwd ? (a.tiles > 0 ? a.tiles : 1) : kConvGridBwd); }
 
+// the one forward launch (a.tiles > 0).  The staging mode follows from the operands the entry point put into ConvArgs
+template <int kMode>
+int launch_convpool_fwd_as(const ConvArgs& a, const float* bias, float* out, uint8_t* argmax, hipStream_t s, const char* label) {
+  const size_t lds = convpool_fwd_lds(a);
+  if (int rc = allow_full_lds<convpool_fwd_kernel<kMode>>(lds, "seq kernels")) return rc;
+  const int grid = (int)(a.tiles < kConvGridFwd ? a.tiles : kConvGridFwd);
+  hipLaunchKernelGGL(convpool_fwd_kernel<kMode>, dim3(grid), dim3(256), lds, s, a, bias, out, argmax);
+  return check_launch(label);
+}
+int launch_convpool_fwd(const ConvArgs& a, const float* bias, float* out, uint8_t* argmax, hipStream_t s) {
+  if (a.sigma) return launch_convpool_fwd_as<kStagePerturbed>(a, bias, out, argmax, s, "convpool_fwd_kernel<perturbed>");
+  if (a.scale) return launch_convpool_fwd_as<kStageScaled>(a, bias, out, argmax, s, "convpool_fwd_kernel<scaled>");
+  return launch_convpool_fwd_as<kStagePlain>(a, bias, out, argmax, s, "convpool_fwd_kernel");
+}
+
 // ---- integrated gradients of the sequence input ---------------------------------------------------------------------------
 // Gradient with respect to the (scaled) embedded input of the conv-pool, summed over the rep copies of a compound:
 //   dx[c, m, e] = sum_r wt[c rep + r] sum_dk sum_f G_r[m + padL - dk, f] W[dk, e, f]   (times table[tok[c, m], e] if asked)
@@ -335,13 +350,8 @@ __global__ __launch_bounds__(256) void convpool_input_grad_kernel(ConvArgs a, co
     for (int i = threadIdx.x; i < nw * F4p; i += blockDim.x) {
       const int row = i / F4p, fr = i - row * F4p;
       const int l = lbase + row;
-      float gv = 0.f;
-      if (fr < a.F && l >= 0 && l < TP) {
-        const int t = l / a.p, j = l - t * a.p;
-        const long o = (b * a.T + t) * a.F + fr;
-        if (argmax[o] == j) gv = dout[o];
-      }
-      g[i] = gv;
+      const int t = l / a.p, j = l - t * a.p;
+      g[i] = (fr < a.F && l >= 0 && l < TP) ? routed_grad(dout, argmax, (b * a.T + t) * a.F + fr, j) : 0.f;
     }
     __syncthreads();
     if (e < a.E) {
@@ -673,11 +683,7 @@ extern "C" int kgcn_seq_convpool_fwd_f32(const int32_t* tokens, int32_t batch, i
   if (int rc = conv_args(tokens, batch, length, table, symbols, embed_dim, w, kernel_size, filters, pool, who, a)) return rc;
   if (a.tiles == 0) return 0;
   if (!bias || !out) return fail("%s: NULL operand", who);
-  const size_t lds = convpool_fwd_lds(a);
-  if (int rc = allow_full_lds<convpool_fwd_kernel<kStagePlain>>(lds, "seq kernels")) return rc;
-  const int grid = (int)(a.tiles < kConvGridFwd ? a.tiles : kConvGridFwd);
-  hipLaunchKernelGGL(convpool_fwd_kernel<kStagePlain>, dim3(grid), dim3(256), lds, as_stream(stream), a, bias, out, argmax);
-  return check_launch("convpool_fwd_kernel");
+  return launch_convpool_fwd(a, bias, out, argmax, as_stream(stream));
 }
 
 extern "C" int kgcn_seq_convpool_bwd_f32(const int32_t* tokens, int32_t batch, int32_t length, const float* table, int32_t symbols,
@@ -727,11 +733,7 @@ extern "C" int kgcn_seq_convpool_scaled_fwd_f32(const int32_t* tokens, int32_t b
   if (a.tiles == 0) return 0;
   if (!bias || !out || !scale) return fail("%s: NULL operand", who);
   a.scale = scale; a.rep = rep;
-  const size_t lds = convpool_fwd_lds(a);
-  if (int rc = allow_full_lds<convpool_fwd_kernel<kStageScaled>>(lds, "seq kernels")) return rc;
-  const int grid = (int)(a.tiles < kConvGridFwd ? a.tiles : kConvGridFwd);
-  hipLaunchKernelGGL(convpool_fwd_kernel<kStageScaled>, dim3(grid), dim3(256), lds, as_stream(stream), a, bias, out, argmax);
-  return check_launch("convpool_fwd_kernel<scaled>");
+  return launch_convpool_fwd(a, bias, out, argmax, as_stream(stream));
 }
 
 extern "C" int kgcn_seq_convpool_perturbed_fwd_f32(const int32_t* tokens, int32_t batch, int32_t rep, const float* scale,
@@ -746,11 +748,7 @@ extern "C" int kgcn_seq_convpool_perturbed_fwd_f32(const int32_t* tokens, int32_
   if (a.tiles == 0) return 0;
   if (!bias || !out || !scale || !sigma || !sample || !ids) return fail("%s: NULL operand", who);
   a.scale = scale; a.rep = rep; a.sigma = sigma; a.sample = sample; a.ids = ids; a.seed = seed;
-  const size_t lds = convpool_fwd_lds(a);
-  if (int rc = allow_full_lds<convpool_fwd_kernel<kStagePerturbed>>(lds, "seq kernels")) return rc;
-  const int grid = (int)(a.tiles < kConvGridFwd ? a.tiles : kConvGridFwd);
-  hipLaunchKernelGGL(convpool_fwd_kernel<kStagePerturbed>, dim3(grid), dim3(256), lds, as_stream(stream), a, bias, out, argmax);
-  return check_launch("convpool_fwd_kernel<perturbed>");
+  return launch_convpool_fwd(a, bias, out, argmax, as_stream(stream));
 }
 
 extern "C" int kgcn_seq_convpool_input_grad_f32(const int32_t* tokens, int32_t batch, int32_t rep, int32_t length, const float* table,
@@ -833,25 +831,4 @@ extern "C" int kgcn_seq_lstm_bwd_f32(const float* x, int32_t batch, int32_t step
   if (int rc = reduce_or_defer(part_x, kLstmChunks, (long)in_dim * N4, dwx, s)) return rc;
   if (int rc = reduce_or_defer(part_h, kLstmChunks, (long)units * N4, dwh, s)) return rc;
   return reduce_or_defer(part_b, kLstmChunks, N4, dbias, s);
-}
-
-// d x[b, n, :] = g[b * g_ld + :d] -- the gradient of a GraphGather read-out that was written into a column block of a wider
-// buffer (model_multimodal.py:96 tf.concat), read where it lies
-__global__ void gather_bwd_ld_kernel(const float* __restrict__ g, long g_ld, long B, int N, int d, float* __restrict__ dx) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B * N * d) return;
-  const long b = i / ((long)N * d);
-  const int c = (int)(i % d);
-  dx[i] = g[b * g_ld + c];
-}
-
-extern "C" int kgcn_graph_gather_bwd_ld_f32(const float* dout_grad, int64_t dout_ld, int64_t batch, int32_t n_nodes, int32_t d,
-                                            float* dx, void* stream) {
-  if (batch < 0 || n_nodes < 0 || d < 1 || dout_ld < d) return fail("kgcn_graph_gather_bwd_ld_f32: bad sizes");
-  const long n = (long)batch * n_nodes * d;
-  if (n == 0) return 0;
-  if (!dout_grad || !dx) return fail("kgcn_graph_gather_bwd_ld_f32: NULL operand");
-  hipLaunchKernelGGL(gather_bwd_ld_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), dout_grad, (long)dout_ld,
-                     (long)batch, n_nodes, d, dx);
-  return check_launch("gather_bwd_ld_kernel");
 }

@@ -690,14 +690,8 @@ class SequenceEncoder(nn.Module):
         d pooled through the LSTM and hand it to ops.seq_conv_pool_input_grad; the parameters get no gradient from this path.
         noise = (sigma [C rep], sample [C rep], ids [C], seed): add_perturbation's enabled_noise, drawn inside the conv-pool
         (ops.seq_conv_pool_perturbed); None keeps the clean kernel."""
-        if noise is None:
-            pooled, arg = ops.seq_conv_pool_scaled(tokens, self.embeddings.detach(), self.conv_kernel.detach(), self.conv_bias.detach(),
-                                                   self.pool, scale, rep, argmax=input_grad)
-        else:
-            sigma, sample, ids, seed = noise
-            pooled, arg = ops.seq_conv_pool_perturbed(tokens, self.embeddings.detach(), self.conv_kernel.detach(),
-                                                      self.conv_bias.detach(), self.pool, scale, rep, sigma, sample, ids, seed,
-                                                      argmax=input_grad)
+        pooled, arg = ops._seq_conv_pool_copies(tokens, self.embeddings.detach(), self.conv_kernel.detach(), self.conv_bias.detach(),
+                                                self.pool, scale, rep, noise, input_grad)
         if input_grad:
             pooled.requires_grad_(True)
         h = ops.seq_lstm(pooled, self.kernel, self.recurrent_kernel, self.bias, self.recurrent_activation, out=out, out_col=out_col)

@@ -1965,12 +1965,23 @@ def seq_limits_check(length=None, symbols=None, embed_dim=None, kernel_size=None
             raise _lib.KgcnHipError("sequence encoder: %s %d outside 1..%d" % (name, int(v), hi))
 
 
+def _tokens2d(tokens):
+    if not (torch.is_tensor(tokens) and tokens.is_cuda and tokens.dtype == torch.int32 and tokens.dim() == 2):
+        raise _lib.KgcnHipError("tokens must be an int32 [batch, length] device tensor")
+    return tokens.contiguous()
+
+
+def _conv_bias(bias, filters):
+    b = _f32c(bias, "conv bias").reshape(-1)
+    if b.numel() != filters:
+        raise _lib.KgcnHipError("conv bias %s does not match %d filters" % (tuple(bias.shape), filters))
+    return b
+
+
 class _SeqConvPool(torch.autograd.Function):
     @staticmethod
     def forward(ctx, tokens, table, w, bias, pool):
-        if not (torch.is_tensor(tokens) and tokens.is_cuda and tokens.dtype == torch.int32 and tokens.dim() == 2):
-            raise _lib.KgcnHipError("tokens must be an int32 [batch, length] device tensor")
-        tokens = tokens.contiguous()
+        tokens = _tokens2d(tokens)
         table, w, b = _f32c(table, "embedding table"), _f32c(w, "conv kernel"), _f32c(bias, "conv bias").reshape(-1)
         B, L = tokens.shape
         S, E = table.shape
@@ -2086,8 +2097,7 @@ def seq_lstm(x, wx, wh, bias, recurrent_activation="hard_sigmoid", out=None, out
 
 
 def _seq_conv_operands(tokens, table, w, pool, rows, rep):
-    if not (torch.is_tensor(tokens) and tokens.is_cuda and tokens.dtype == torch.int32 and tokens.dim() == 2):
-        raise _lib.KgcnHipError("tokens must be an int32 [batch, length] device tensor")
+    tokens = _tokens2d(tokens)
     table, w = _f32c(table, "embedding table"), _f32c(w, "conv kernel")
     S, E = table.shape
     if w.dim() != 3 or w.shape[1] != E:
@@ -2095,8 +2105,30 @@ def _seq_conv_operands(tokens, table, w, pool, rows, rep):
     rep = int(rep)
     if rep < 1 or rows != tokens.shape[0] * rep:
         raise _lib.KgcnHipError("%d rows are not %d copies of %d token rows" % (rows, rep, tokens.shape[0]))
-    seq_limits_check(tokens.shape[1], S, E, w.shape[0], w.shape[2], pool)
-    return tokens.contiguous(), table, w, rep
+    (C, L), k, F = tokens.shape, w.shape[0], w.shape[2]
+    seq_limits_check(L, S, E, k, F, pool)
+    return tokens, table, w, rep, (C, L, S, E, k, F, L // int(pool))
+
+
+def _seq_conv_pool_copies(tokens, table, w, bias, pool, scale, rep, noise, argmax):
+    """The one body of seq_conv_pool_scaled (noise None) and seq_conv_pool_perturbed (noise = (sigma, sample, ids, seed))."""
+    if noise is None:
+        scale = _f32c(scale, "scale").reshape(-1)
+        B = scale.numel()
+    else:
+        C = tokens.shape[0] if torch.is_tensor(tokens) and tokens.dim() == 2 else 0
+        scale, sigma, sample, ids, B, seed = _perturb_operands(scale, *noise[:3], lambda b: C, noise[3])
+    tokens, table, w, rep, (_, L, S, E, k, F, T) = _seq_conv_operands(tokens, table, w, pool, B, rep)
+    b = _conv_bias(bias, F)
+    out = torch.empty((B, T, F), device=table.device, dtype=torch.float32)
+    arg = torch.empty((B, T, F), device=table.device, dtype=torch.uint8) if argmax else None
+    conv = (L, ptr(table), S, E, ptr(w), ptr(b), k, F, int(pool), ptr(out), ptr(arg), current_stream())
+    if noise is None:
+        check(lib.kgcn_seq_convpool_scaled_fwd_f32(ptr(tokens), B, rep, ptr(scale), *conv), "kgcn_seq_convpool_scaled_fwd_f32")
+    else:
+        check(lib.kgcn_seq_convpool_perturbed_fwd_f32(ptr(tokens), B, rep, ptr(scale), ptr(sigma), ptr(sample), ptr(ids), seed, *conv),
+              "kgcn_seq_convpool_perturbed_fwd_f32")
+    return out, arg
 
 
 def seq_conv_pool_scaled(tokens, table, w, bias, pool, scale, rep, argmax=False):
@@ -2104,21 +2136,7 @@ def seq_conv_pool_scaled(tokens, table, w, bias, pool, scale, rep, argmax=False)
     kgcn/feed.py:88-89 add_perturbation on the embedded layer): tokens [C, L] int32, scale [C rep] fp32 -> (pooled [C rep, L // pool, F],
     arg-max bytes of the same shape when argmax=True, else None).  Row b reads token row b // rep and its embedding rows times
     scale[b]; the scaled [C rep, L, E] input is never written."""
-    scale = _f32c(scale, "scale").reshape(-1)
-    B = scale.numel()
-    tokens, table, w, rep = _seq_conv_operands(tokens, table, w, pool, B, rep)
-    b = _f32c(bias, "conv bias").reshape(-1)
-    S, E = table.shape
-    k, F = w.shape[0], w.shape[2]
-    if b.numel() != F:
-        raise _lib.KgcnHipError("conv bias %s does not match %d filters" % (tuple(bias.shape), F))
-    L = tokens.shape[1]
-    T = L // int(pool)
-    out = torch.empty((B, T, F), device=table.device, dtype=torch.float32)
-    arg = torch.empty((B, T, F), device=table.device, dtype=torch.uint8) if argmax else None
-    check(lib.kgcn_seq_convpool_scaled_fwd_f32(ptr(tokens), B, rep, ptr(scale), L, ptr(table), S, E, ptr(w), ptr(b), k, F, int(pool),
-                                               ptr(out), ptr(arg), current_stream()), "kgcn_seq_convpool_scaled_fwd_f32")
-    return out, arg
+    return _seq_conv_pool_copies(tokens, table, w, bias, pool, scale, rep, None, argmax)
 
 
 # noise streams of the smooth attribution methods (KGCN_IG_STREAM_* of include/kgcn_hip.h)
@@ -2206,22 +2224,7 @@ def seq_conv_pool_perturbed(tokens, table, w, bias, pool, scale, rep, sigma, sam
     ids[b // rep], sample sample[b], row l, column e) (include/kgcn_hip.h), drawn inside the window staging: the noisy
     [C rep, L, E] input is never written.  Rows with sigma[b] == 0 are exactly seq_conv_pool_scaled's.  ops.seq_conv_pool_input_grad
     takes the result as it takes the scaled forward's."""
-    C = tokens.shape[0] if torch.is_tensor(tokens) and tokens.dim() == 2 else 0
-    scale, sigma, sample, ids, B, seed = _perturb_operands(scale, sigma, sample, ids, lambda b: C, seed)
-    tokens, table, w, rep = _seq_conv_operands(tokens, table, w, pool, B, rep)
-    b = _f32c(bias, "conv bias").reshape(-1)
-    S, E = table.shape
-    k, F = w.shape[0], w.shape[2]
-    if b.numel() != F:
-        raise _lib.KgcnHipError("conv bias %s does not match %d filters" % (tuple(bias.shape), F))
-    L = tokens.shape[1]
-    T = L // int(pool)
-    out = torch.empty((B, T, F), device=table.device, dtype=torch.float32)
-    arg = torch.empty((B, T, F), device=table.device, dtype=torch.uint8) if argmax else None
-    check(lib.kgcn_seq_convpool_perturbed_fwd_f32(ptr(tokens), B, rep, ptr(scale), ptr(sigma), ptr(sample), ptr(ids), seed, L, ptr(table),
-                                                  S, E, ptr(w), ptr(b), k, F, int(pool), ptr(out), ptr(arg), current_stream()),
-          "kgcn_seq_convpool_perturbed_fwd_f32")
-    return out, arg
+    return _seq_conv_pool_copies(tokens, table, w, bias, pool, scale, rep, (sigma, sample, ids, seed), argmax)
 
 
 def seq_conv_pool_input_grad(dout, argmax, tokens, table, w, pool, rep, row_weight=None, times_table=False):
@@ -2230,12 +2233,8 @@ def seq_conv_pool_input_grad(dout, argmax, tokens, table, w, pool, rep, row_weig
     times the gradient of copy b, times table[tokens] when times_table (the attribution of kgcn/visualization.py:207-215).
     No weight gradient is formed."""
     B = dout.shape[0]
-    tokens, table, w, rep = _seq_conv_operands(tokens, table, w, pool, B, rep)
+    tokens, table, w, rep, (C, L, S, E, k, F, T) = _seq_conv_operands(tokens, table, w, pool, B, rep)
     dout = _f32c(dout, "grad")
-    S, E = table.shape
-    k, F = w.shape[0], w.shape[2]
-    C, L = tokens.shape
-    T = L // int(pool)
     if tuple(dout.shape) != (B, T, F) or argmax is None or tuple(argmax.shape) != (B, T, F) or argmax.dtype != torch.uint8:
         raise _lib.KgcnHipError("d pooled %s / arg-max bytes do not match [%d, %d, %d]" % (tuple(dout.shape), B, T, F))
     require_gpu(argmax, "arg-max bytes")
@@ -2271,7 +2270,7 @@ def conv1d_limits_check(length=None, in_dim=None, filters=None, kernel_size=None
 class _Conv1DPool(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, bias, pool, act, tokens, table):
-        w, b = _f32c(w, "conv kernel"), _f32c(bias, "conv bias").reshape(-1)
+        w = _f32c(w, "conv kernel")
         if w.dim() != 3:
             raise _lib.KgcnHipError("conv kernel must be [kernel_size, in_dim, filters], got %s" % (tuple(w.shape),))
         k, Cin, F = w.shape
@@ -2279,9 +2278,7 @@ class _Conv1DPool(torch.autograd.Function):
         if tokens is not None:
             if x is not None or table is None:
                 raise _lib.KgcnHipError("conv1d_pool takes a dense input or a (tokens, table) pair")
-            if not (torch.is_tensor(tokens) and tokens.is_cuda and tokens.dtype == torch.int32 and tokens.dim() == 2):
-                raise _lib.KgcnHipError("tokens must be an int32 [batch, length] device tensor")
-            tokens, table = tokens.contiguous(), _f32c(table, "embedding table")
+            tokens, table = _tokens2d(tokens), _f32c(table, "embedding table")
             if table.dim() != 2 or table.shape[1] != Cin:
                 raise _lib.KgcnHipError("embedding table %s does not match a conv kernel %s" % (tuple(table.shape), tuple(w.shape)))
             (B, L), S = tokens.shape, table.shape[0]
@@ -2292,8 +2289,7 @@ class _Conv1DPool(torch.autograd.Function):
             if x.dim() != 3 or x.shape[2] != Cin:
                 raise _lib.KgcnHipError("conv input %s does not match a conv kernel %s" % (tuple(x.shape), tuple(w.shape)))
             B, L = x.shape[:2]
-        if b.numel() != F:
-            raise _lib.KgcnHipError("conv bias %s does not match %d filters" % (tuple(bias.shape), F))
+        b = _conv_bias(bias, F)
         conv1d_limits_check(L, Cin, F, k, pool, S if tokens is not None else None)
         T = L // pool
         out = torch.empty((B, T, F), device=w.device, dtype=torch.float32)
@@ -2350,11 +2346,12 @@ def conv1d_pool(x, w, bias, pool=1, activation=None, tokens=None, table=None):
 def embedding_grad(tokens, dembedded, symbols):
     """d table [S, E] = the rows of dembedded [B, L, E] summed by the symbol tokens [B, L] holds there (fixed order, no atomics)."""
     g = _f32c(dembedded, "embedded gradient")
-    if not (torch.is_tensor(tokens) and tokens.is_cuda and tokens.dtype == torch.int32 and tuple(tokens.shape) == tuple(g.shape[:2])):
+    tokens = _tokens2d(tokens)
+    if tuple(tokens.shape) != tuple(g.shape[:2]):
         raise _lib.KgcnHipError("tokens must be an int32 device tensor matching the gradient's [batch, length]")
     conv1d_limits_check(length=g.shape[1], in_dim=g.shape[2], symbols=symbols)
     dtable = torch.empty((int(symbols), g.shape[2]), device=g.device, dtype=torch.float32)
-    check(lib.kgcn_embedding_grad_f32(ptr(tokens.contiguous()), g.shape[0], g.shape[1], ptr(g), int(symbols), g.shape[2], ptr(dtable),
+    check(lib.kgcn_embedding_grad_f32(ptr(tokens), g.shape[0], g.shape[1], ptr(g), int(symbols), g.shape[2], ptr(dtable),
                                       current_stream()), "kgcn_embedding_grad_f32")
     return dtable
 

@@ -123,7 +123,7 @@ def ig_scales(method, divide_number):
         return [k / float(D) for k in range(D + 1)], [0.0] + [1.0 / D] * D
     if method in ("grad_prod", "grad"):
         return [0.0, 1.0], [0.0, 1.0]
-    raise ValueError("unsupported method %r (%s; smooth_grad / smooth_ig draw host noise and are not supported)"
+    raise ValueError("unsupported method %r (%s; the rows of smooth_grad / smooth_ig come from smooth_rows)"
                      % (method, ", ".join(IG_METHODS)))
 
 

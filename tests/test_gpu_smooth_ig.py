@@ -391,6 +391,52 @@ def test_generic_integrated_gradients_match_the_oracle_loop(method):
     assert res["start_score"] == clean["start_score"] and res["end_score"] == clean["end_score"]
 
 
+# ---- the three staging modes of the one conv-pool forward, through the C ABI ------------------------------------------------
+def test_convpool_staging_modes_agree_bit_for_bit_through_the_c_abi():
+    """The equalities include/kgcn_hip.h promises, at the smallest shape in which every staging path differs: C = 2 token rows
+    x rep = 2; E = 5 (E4 = 8: the tail of the Philox block and the zero columns); k = 4 (asymmetric SAME padding); F = 50 (idle
+    lanes); p = 2, L = 37 -> T = 18 > 16: two tiles per sequence, whose halo rows the neighbouring tile draws again; S = 7.
+    Pooled values and arg-max bytes go into buffers bracketed by sentinels."""
+    import torch
+    from kgcn_amd import _lib
+    lib, ptr = _lib.lib, _lib.ptr
+    C, rep, E, k, F, p, L, S = 2, 2, 5, 4, 50, 2, 37, 7
+    B, T, GUARD = C * rep, L // p, 256
+    rng = np.random.default_rng(11)
+    tok = _t(rng.integers(0, S, (C, L)), np.int32)
+    table, w, bias = _t(rng.standard_normal((S, E))), _t(rng.standard_normal((k, E, F)) * 0.3), _t(rng.standard_normal(F) * 0.1)
+    scale, one = _t([0.0, 0.5, 1.0, 0.75]), _t(np.ones(C))
+    zero, sigma = _t(np.zeros(B)), _t([0.1, 0.0, 0.2, 0.1])
+    sample, ids = _t([0, 1, 0, 3], np.int32), _t([5, 2], np.int32)
+    conv = (L, ptr(table), S, E, ptr(w), ptr(bias), k, F, p)
+    guarded = []
+
+    def run(fn, rows, *head):
+        bufs = []
+        for dtype, fill in ((torch.float32, 1.2345e30), (torch.uint8, 0xA5)):
+            big = torch.full((rows * T * F + 2 * GUARD,), fill, device="cuda", dtype=dtype)
+            guarded.append((big, fill))
+            bufs.append(big[GUARD:-GUARD])
+        _lib.check(getattr(lib, fn)(ptr(tok), rows, *head, *conv, ptr(bufs[0]), ptr(bufs[1]), _lib.current_stream()), fn)
+        return bufs
+
+    def same(a, b):
+        return torch.equal(a[0].view(torch.int32), b[0].view(torch.int32)) and torch.equal(a[1], b[1])
+
+    noise = lambda sg: (rep, ptr(scale), ptr(sg), ptr(sample), ptr(ids), SEED)
+    scaled = run("kgcn_seq_convpool_scaled_fwd_f32", B, rep, ptr(scale))
+    assert same(run("kgcn_seq_convpool_perturbed_fwd_f32", B, *noise(zero)), scaled), "sigma = 0 is not the scaled forward"
+    plain = run("kgcn_seq_convpool_fwd_f32", C)
+    assert same(run("kgcn_seq_convpool_scaled_fwd_f32", C, 1, ptr(one)), plain), "scale = 1, rep = 1 is not the plain forward"
+    noisy = run("kgcn_seq_convpool_perturbed_fwd_f32", B, *noise(sigma))
+    assert same(run("kgcn_seq_convpool_perturbed_fwd_f32", B, *noise(sigma)), noisy), "the same draw differs between two launches"
+    assert not same(noisy, scaled) and float(plain[0].max()) > 0.0                # noise was drawn; relu passed something
+    torch.cuda.synchronize()
+    for big, fill in guarded:
+        edge = torch.full((GUARD,), fill, device="cuda", dtype=big.dtype)
+        assert torch.equal(big[:GUARD], edge) and torch.equal(big[-GUARD:], edge), "wrote outside its buffer"
+
+
 # ---- limits and argument errors -------------------------------------------------------------------------------------------
 def test_limits_and_argument_errors_raise_before_launch(g7):
     import torch

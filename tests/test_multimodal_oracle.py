@@ -308,6 +308,31 @@ def test_convpool_limits_refused_without_a_gpu(args):
     assert lib.kgcn_seq_convpool_workspace_bytes(2, 100, 25, 4, 4, 50, 4) > 0
 
 
+def test_convpool_forwards_validate_under_their_own_name_without_a_gpu():
+    """The three forwards share one launcher; each validates first, under its own name, and fails before any HIP call."""
+    from kgcn_amd import _lib
+    lib = _lib.lib
+    L, S, E, k, F, p = 16, 4, 8, 4, 8, 4
+    conv = (L, None, S, E, None, None, k, F, p, None, None, None)      # length .. stream, the operands NULL
+
+    def calls(batch, rep):
+        return (("kgcn_seq_convpool_fwd_f32", lambda: lib.kgcn_seq_convpool_fwd_f32(None, batch, *conv)),
+                ("kgcn_seq_convpool_scaled_fwd_f32", lambda: lib.kgcn_seq_convpool_scaled_fwd_f32(None, batch, rep, None, *conv)),
+                ("kgcn_seq_convpool_perturbed_fwd_f32",
+                 lambda: lib.kgcn_seq_convpool_perturbed_fwd_f32(None, batch, rep, None, None, None, None, 0, *conv)))
+
+    for name, call in calls(4, 2):
+        assert call() != 0
+        assert lib.kgcn_last_error().decode().startswith(name + ":"), name
+    for name, call in calls(0, 2):
+        assert call() == 0, name
+    input_grad = ("kgcn_seq_convpool_input_grad_f32",
+                  lambda: lib.kgcn_seq_convpool_input_grad_f32(None, 3, 2, L, None, S, E, None, k, F, p, None, None, None, 0, None, None))
+    for name, call in calls(3, 2)[1:] + (input_grad,):                  # 3 rows are not whole groups of 2 copies
+        assert call() != 0
+        assert "whole groups" in lib.kgcn_last_error().decode(), name
+
+
 @pytest.mark.parametrize("D,H", [(65, 32), (50, 65), (0, 32)])
 def test_lstm_limits_refused_without_a_gpu(D, H):
     from kgcn_amd import _lib, layers, ops

@@ -4,7 +4,13 @@
 A host-side refactor may change the ORDER in which template kernels are instantiated, and with it the order of the functions in
 the file and the function index inside local labels (.LBB<index>_<block>, .Lfunc_end<index>).  So: file-path / ident lines
 dropped, the function index in local labels and the translation unit's __hip_cuid hash blanked, the file cut into chunks at
-every section start and every entry of the metadata's kernel list, and the chunks compared as sorted lists.  Prints the counts; exit status 1 when they differ."""
+every section start and every entry of the metadata's kernel list, and the chunks compared as sorted lists.  Prints the counts; exit status 1 when they differ.
+
+A kernel may also MOVE between two source files; then each side is the concatenation of both files' assembly.  For that the
+cuts fall at every `.text` as well (a kernel that is no template is in .text, behind its predecessor's kernel info) and at the
+end of the metadata's kernel list (its last entry is followed by the file's trailer), and what the assembler writes once per
+file and section in use rather than per kernel is dropped: the line that places __hip_cuid in whichever section came last, a
+bare section switch, and the padding that closes .text."""
 import re
 import sys
 
@@ -18,12 +24,14 @@ def chunks(path):
         line = re.sub(r"\.Lfunc_(begin|end)\d+", r".Lfunc_\1", line)
         line = re.sub(r":\s+;", ": ;", line)                                    # the comment column follows the label's width
         line = re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid", line)             # a hash of the translation unit's text
-        if re.match(r"\t\.section\b|  - \.", line) and cur:
+        if re.match(r"\t\.type\t__hip_cuid,", line):
+            continue
+        if re.match(r"\t\.section\b|\t\.text$|  - \.|amdhsa\.target:", line) and cur:
             out.append("".join(cur))
             cur = []
         cur.append(line)
     out.append("".join(cur))
-    return out
+    return [c for c in out if not re.fullmatch(r"\t\.(text|section\t\S+)\n(\t\.p2alignl .*\n\t\.fill .*\n)?", c)]
 
 
 a, b = chunks(sys.argv[1]), chunks(sys.argv[2])
