@@ -496,14 +496,6 @@ def activation(x, name):
 # -------------------------------------------------------------------------------------------------
 # dense contraction
 # -------------------------------------------------------------------------------------------------
-def _dense_ws(din, dout, device):
-    """Workspace of the wide-layer GEMM (pre-split weight fragments): (bytes, tensor or None)."""
-    wsb = lib.kgcn_dense_fwd_workspace_bytes(din, dout)
-    if wsb <= 0:
-        return 0, None
-    return wsb, _lib.workspace(wsb, device)
-
-
 class WeightTables:
     """bf16 fragment tables of the weight operands of wide dense layers (csrc/wtable.hip), split ONCE per training step.
 
@@ -649,6 +641,117 @@ enabled_weight_tables = True
 weight_tables = WeightTables()
 
 
+# ---- the host protocol of a dense call, one helper per step: the Functions below decide WHICH route a call takes, these issue it ----
+def _w_operand(w, trans, device):
+    """-> (tab, nbytes, ready): the weight operand of a wide-layer GEMM -- the fragment table of W (trans = 0) or W^T (trans = 1)
+    split by the step's one table launch (ready = 1), else a workspace the call splits into itself (ready = 0); (None, 0, 0)
+    where the layer has no table route."""
+    tab, nbytes = weight_tables.lookup(w, trans)
+    if tab is not None:
+        return tab, nbytes, 1
+    k, n = (w.shape[1], w.shape[0]) if trans else w.shape
+    nbytes = lib.kgcn_dense_fwd_workspace_bytes(k, n)
+    if nbytes <= 0:
+        return None, 0, 0
+    return _lib.workspace(nbytes, device), nbytes, 0
+
+
+def _dense_fwd(x2d, w, bias, act, stacked=None):
+    """-> y = act(x2d @ w + bias).  stacked = (table, bytes) of [w; bias; 0] with x2d.shape[1] rows (WeightTables.lookup_stacked):
+    the operand of dense_stacked, which exists only as that table."""
+    m, din = x2d.shape
+    dout = w.shape[1]
+    if stacked is None:
+        if w.shape[0] != din:
+            raise _lib.KgcnHipError("kernel is %s but inputs have %d features" % (tuple(w.shape), din))
+        b = None if bias is None else _f32c(bias, "bias").reshape(-1)
+        if b is not None and b.numel() != dout:
+            raise _lib.KgcnHipError("bias has %d elements, expected %d" % (b.numel(), dout))
+        tab, tb, ready = _w_operand(w, 0, x2d.device)
+        if not ready:
+            weight_tables.register(w)
+    else:
+        b, (tab, tb), ready = None, stacked, 1
+    y = torch.empty((m, dout), device=x2d.device, dtype=torch.float32)
+    if ready:
+        check(lib.kgcn_dense_fwd_tab_f32(ptr(x2d), m, din, din, ptr(w), dout, 0, ptr(b), ptr(y), dout,
+                                         dout, int(act), ptr(tab), tb, current_stream()), "kgcn_dense_fwd_tab_f32")
+    else:
+        check(lib.kgcn_dense_fwd_ws_f32(ptr(x2d), m, din, din, ptr(w), dout, 0, ptr(b), ptr(y), dout,
+                                        dout, int(act), ptr(tab), tb, current_stream()), "kgcn_dense_fwd_ws_f32")
+    return y
+
+
+def _dense_dx(g, w, x2d):
+    """-> dx = g @ w^T (w [din, dout] used transposed), laid out like x2d."""
+    m, dout = g.shape
+    din = w.shape[0]
+    dx = torch.empty_like(x2d)
+    tab, tb, ready = _w_operand(w, 1, g.device)
+    if ready:
+        check(lib.kgcn_dense_fwd_tab_f32(ptr(g), m, dout, dout, ptr(w), dout, 1, None, ptr(dx),
+                                         din, din, 0, ptr(tab), tb, current_stream()), "kgcn_dense_fwd_tab_f32(dx)")
+    else:
+        check(lib.kgcn_dense_fwd_ws_f32(ptr(g), m, dout, dout, ptr(w), dout, 1, None, ptr(dx),
+                                        din, din, 0, ptr(tab), tb, current_stream()), "kgcn_dense_fwd_ws_f32(dx)")
+    return dx
+
+
+def _dense_dx_dact(gy, yact, w, act, x2d):
+    """-> (dx, dpre): d pre-activation is produced by the dX GEMM itself while it stages the gradient rows (wide layers); the
+    weight-gradient GEMM reads it afterwards."""
+    m, dout = gy.shape
+    din = w.shape[0]
+    dx = torch.empty_like(x2d)
+    dpre = torch.empty_like(gy)
+    tab, tb, ready = _w_operand(w, 1, gy.device)
+    if ready:
+        check(lib.kgcn_dense_dx_dact_tab_f32(ptr(gy), ptr(yact), m, dout, dout, ptr(w), dout, din, ptr(dx), din, act,
+                                             ptr(dpre), ptr(tab), tb, current_stream()), "kgcn_dense_dx_dact_tab_f32")
+    else:
+        check(lib.kgcn_dense_dx_dact_f32(ptr(gy), ptr(yact), m, dout, dout, ptr(w), dout, din, ptr(dx), din, act,
+                                         ptr(dpre), ptr(tab), tb, current_stream()), "kgcn_dense_dx_dact_f32")
+    return dx, dpre
+
+
+_same_stream = contextlib.nullcontext()
+
+
+def _dense_wgrad(ctx, x2d, w, g, yact, need_w, need_b, dact_pending=False, side=False):
+    """-> (dw [x2d.shape[1], dout], db in the bias' shape) = (x2d^T dpre, column sums of dpre).  dact_pending: g is still the gradient
+    of the ACTIVATED output and no dX GEMM has formed d pre-activation (a layer whose input needs no gradient): a wide layer
+    forms it while the weight-gradient GEMM stages the gradient rows -- no elementwise pass over the [m, dout] tensor -- any
+    other takes that pass first.  side: the GEMM may run on the side stream (side_stream_wgrad)."""
+    m, din = x2d.shape
+    dout = g.shape[1]
+    fuse_dact = dact_pending and wgrad_dact_fusion and bool(lib.kgcn_dense_wgrad_dact_supported(din, dout))
+    if dact_pending and not fuse_dact:
+        g = activation_backward(yact, g, ctx.act)
+    stream = None
+    if side and side_stream_wgrad and m >= side_wgrad_min_rows:
+        stream = _fork_side(g.device)
+        for t in (g, x2d, yact):
+            t.record_stream(stream)          # the caching allocator must not hand their memory out while the side stream reads it
+    with torch.cuda.stream(stream) if stream is not None else _same_stream:
+        wsb = lib.kgcn_dense_wgrad_workspace_bytes(m, din, dout)
+        # (the operand of dense_stacked, [w; bias; 0], has x2d's width in rows, not w's)
+        dw = None if not need_w else torch.empty_like(w) if w.shape[0] == din else \
+            torch.empty((din, dout), device=g.device, dtype=torch.float32)
+        db = torch.empty((dout,), device=g.device, dtype=torch.float32) if need_b else None
+        with _param_grad_stage(ctx, wsb, g.device) as wsp:
+            if fuse_dact:
+                check(lib.kgcn_dense_wgrad_dact_f32(ptr(x2d), din, ptr(g), ptr(yact), dout, ctx.act, m, din, dout, ptr(dw),
+                                                    ptr(db), ptr(wsp), wsb, current_stream()), "kgcn_dense_wgrad_dact_f32")
+            else:
+                check(lib.kgcn_dense_wgrad_f32(ptr(x2d), din, ptr(g), dout, m, din, dout, ptr(dw),
+                                               ptr(db), ptr(wsp), wsb, current_stream()), "kgcn_dense_wgrad_f32")
+    return dw, _bias_grad(ctx, db)
+
+
+def _bias_grad(ctx, db):
+    return None if db is None else db.reshape(ctx.bias_shape)
+
+
 # One-pass backward of the wide layers (kgcn_dense_bwd_f32, csrc/gemmb.hip): dX, dW and dbias from ONE sweep over (grad, act_out,
 # x) -- the d pre-activation tensor is never written and read back (six passes over [m, 256] tensors -> four).
 dense_bwd_fusion = True
@@ -677,19 +780,13 @@ def _dense_bwd_fused(ctx, x2d, w, gy, yact, act, need_b, gp=None, gp_ld=0, n_nod
     dx = torch.empty_like(x2d)
     dw = torch.empty_like(w)
     db = torch.empty((dout,), device=x2d.device, dtype=torch.float32) if need_b else None
-    tab, tb = weight_tables.lookup(w, 1)
-    ready = 1
-    if tab is None:
-        tb, tab = _dense_ws(dout, din, x2d.device)
-        ready = 0
+    tab, tb, ready = _w_operand(w, 1, x2d.device)
     wsb = lib.kgcn_dense_wgrad_workspace_bytes(m, din, dout)
     with _param_grad_stage(ctx, wsb, x2d.device) as wsp:
         check(lib.kgcn_dense_bwd_f32(ptr(gy), None if gp is None else gp.data_ptr(), gp_ld, n_nodes, ptr(yact) if act else None,
                                      int(act), dout, ptr(x2d), din, m, din, dout, ptr(w), dout, ptr(dx), din, ptr(dw), ptr(db),
                                      ptr(tab), tb, ready, ptr(wsp), wsb, current_stream()), "kgcn_dense_bwd_f32")
-    if db is not None:
-        db = db.reshape(ctx.bias_shape)
-    return dx, dw, db
+    return dx, dw, _bias_grad(ctx, db)
 
 
 class _Dense(torch.autograd.Function):
@@ -699,23 +796,7 @@ class _Dense(torch.autograd.Function):
         # right away, so it does not defer; stack_rows' [w; bias; pad] stands for w and bias, whose gradients are views of it)
         _record_params(ctx, w, bias)
         x2d, w = _f32c(x2d, "x"), _f32c(w, "w")
-        m, din = x2d.shape
-        dout = w.shape[1]
-        if w.shape[0] != din:
-            raise _lib.KgcnHipError("kernel is %s but inputs have %d features" % (tuple(w.shape), din))
-        b = None if bias is None else _f32c(bias, "bias").reshape(-1)
-        if b is not None and b.numel() != dout:
-            raise _lib.KgcnHipError("bias has %d elements, expected %d" % (b.numel(), dout))
-        y = torch.empty((m, dout), device=x2d.device, dtype=torch.float32)
-        tab, tb = weight_tables.lookup(w, 0)
-        if tab is not None:
-            check(lib.kgcn_dense_fwd_tab_f32(ptr(x2d), m, din, din, ptr(w), dout, 0, ptr(b), ptr(y), dout,
-                                             dout, int(act), ptr(tab), tb, current_stream()), "kgcn_dense_fwd_tab_f32")
-        else:
-            weight_tables.register(w)
-            wsb, wsp = _dense_ws(din, dout, x2d.device)
-            check(lib.kgcn_dense_fwd_ws_f32(ptr(x2d), m, din, din, ptr(w), dout, 0, ptr(b), ptr(y), dout,
-                                            dout, int(act), ptr(wsp), wsb, current_stream()), "kgcn_dense_fwd_ws_f32")
+        y = _dense_fwd(x2d, w, bias, act)
         ctx.act = int(act)
         ctx.save_for_backward(x2d, w, y if act else x2d)
         ctx.bias_shape = None if bias is None else tuple(bias.shape)
@@ -725,75 +806,23 @@ class _Dense(torch.autograd.Function):
     def backward(ctx, gy):
         x2d, w, yact = ctx.saved_tensors
         gy = _f32c(gy, "grad")
-        m, din = x2d.shape
-        dout = w.shape[1]
+        m = x2d.shape[0]
         dx = dw = db = None
+        need_x, need_w = ctx.needs_input_grad[:2]
         need_b = ctx.bias_shape is not None and ctx.needs_input_grad[2]
-        if ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and not (side_stream_wgrad and m >= side_wgrad_min_rows) and \
+        if need_x and need_w and not (side_stream_wgrad and m >= side_wgrad_min_rows) and \
                 _dense_bwd_fused_ok(x2d, w, gy, yact if ctx.act else None):
             # wide layer that hands a gradient on: dX, dW and dbias in ONE pass over (gy, y, x)
             dx, dw, db = _dense_bwd_fused(ctx, x2d, w, gy, yact, ctx.act, need_b)
             return dx, dw, db, None
-        # first layer of a model (no d inputs), wide layer: d pre-activation is formed while the weight-gradient GEMM stages
-        # the gradient rows -- no elementwise pass over the [m, dout] tensor
-        fuse_dact = bool(ctx.act) and not ctx.needs_input_grad[0] and wgrad_dact_fusion and \
-            bool(lib.kgcn_dense_wgrad_dact_supported(din, dout))
-        if ctx.act and ctx.needs_input_grad[0]:
-            # d pre-activation is produced by the dX GEMM itself while it stages the gradient rows (wide layers); the
-            # weight-gradient GEMM reads it afterwards
-            dx = torch.empty_like(x2d)
-            dpre = torch.empty_like(gy)
-            tab, tb = weight_tables.lookup(w, 1)
-            if tab is not None:
-                check(lib.kgcn_dense_dx_dact_tab_f32(ptr(gy), ptr(yact), m, dout, dout, ptr(w), dout, din, ptr(dx), din, ctx.act,
-                                                     ptr(dpre), ptr(tab), tb, current_stream()), "kgcn_dense_dx_dact_tab_f32")
-            else:
-                wsb, wsp = _dense_ws(dout, din, gy.device)
-                check(lib.kgcn_dense_dx_dact_f32(ptr(gy), ptr(yact), m, dout, dout, ptr(w), dout, din, ptr(dx), din, ctx.act,
-                                                 ptr(dpre), ptr(wsp), wsb, current_stream()), "kgcn_dense_dx_dact_f32")
-            gy = dpre
-        else:
-            if ctx.act and not fuse_dact:
-                gy = activation_backward(yact, gy, ctx.act)
-            if ctx.needs_input_grad[0]:
-                dx = torch.empty_like(x2d)
-                # dx = gy @ w^T : w [din, dout] used transposed
-                tab, tb = weight_tables.lookup(w, 1)
-                if tab is not None:
-                    check(lib.kgcn_dense_fwd_tab_f32(ptr(gy), m, dout, dout, ptr(w), dout, 1, None, ptr(dx),
-                                                     din, din, 0, ptr(tab), tb, current_stream()), "kgcn_dense_fwd_tab_f32(dx)")
-                else:
-                    wsb, wsp = _dense_ws(dout, din, gy.device)
-                    check(lib.kgcn_dense_fwd_ws_f32(ptr(gy), m, dout, dout, ptr(w), dout, 1, None, ptr(dx),
-                                                    din, din, 0, ptr(wsp), wsb, current_stream()), "kgcn_dense_fwd_ws_f32(dx)")
-        need_w = ctx.needs_input_grad[1]
-        need_b = ctx.bias_shape is not None and ctx.needs_input_grad[2]
+        if ctx.act and need_x:
+            dx, gy = _dense_dx_dact(gy, yact, w, ctx.act, x2d)
+        elif need_x:
+            dx = _dense_dx(gy, w, x2d)
         if need_w or need_b:
-            side = None
-            if side_stream_wgrad and m >= side_wgrad_min_rows:
-                side = _fork_side(gy.device)
-                for t in (gy, x2d, yact):
-                    t.record_stream(side)        # the caching allocator must not hand their memory out while `side` reads it
-            with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
-                dw, db = _Dense._wgrad(ctx, x2d, w, gy, yact, m, din, dout, need_w, need_b, fuse_dact)
+            # (first layer of a model -- no d inputs: the derivative of the activation is still to be applied)
+            dw, db = _dense_wgrad(ctx, x2d, w, gy, yact, need_w, need_b, dact_pending=bool(ctx.act) and not need_x, side=True)
         return dx, dw, db, None
-
-    @staticmethod
-    def _wgrad(ctx, x2d, w, gy, yact, m, din, dout, need_w, need_b, fuse_dact):
-        wsb = lib.kgcn_dense_wgrad_workspace_bytes(m, din, dout)
-        dw = torch.empty_like(w) if need_w else None
-        db = torch.empty((dout,), device=gy.device, dtype=torch.float32) if need_b else None
-        with _param_grad_stage(ctx, wsb, gy.device) as wsp:
-            if fuse_dact:
-                check(lib.kgcn_dense_wgrad_dact_f32(ptr(x2d), din, ptr(gy), ptr(yact), dout, ctx.act, m, din, dout, ptr(dw),
-                                                    ptr(db), ptr(wsp), wsb, current_stream()), "kgcn_dense_wgrad_dact_f32")
-            else:
-                check(lib.kgcn_dense_wgrad_f32(ptr(x2d), din, ptr(gy), dout, m, din, dout, ptr(dw),
-                                               ptr(db), ptr(wsp), wsb, current_stream()),
-                      "kgcn_dense_wgrad_f32")
-        if db is not None:
-            db = db.reshape(ctx.bias_shape)
-        return dw, db
 
 
 class _StackRows(torch.autograd.Function):
@@ -828,11 +857,7 @@ class _DenseStacked(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x2d, w, bias, act, tab, tb):
-        m, rows = x2d.shape
-        dout = w.shape[1]
-        y = torch.empty((m, dout), device=x2d.device, dtype=torch.float32)
-        check(lib.kgcn_dense_fwd_tab_f32(ptr(x2d), m, rows, rows, ptr(w), dout, 0, None, ptr(y), dout, dout, int(act), ptr(tab), tb,
-                                         current_stream()), "kgcn_dense_fwd_tab_f32")
+        y = _dense_fwd(x2d, w, None, act, stacked=(tab, tb))
         ctx.act = int(act)
         ctx.save_for_backward(x2d, w, bias, y)
         _record_params(ctx, w, bias)
@@ -841,21 +866,8 @@ class _DenseStacked(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         x2d, w, bias, y = ctx.saved_tensors
-        gy = _f32c(gy, "grad")
-        m, rows = x2d.shape
-        din, dout = w.shape
-        fuse_dact = bool(ctx.act) and wgrad_dact_fusion and bool(lib.kgcn_dense_wgrad_dact_supported(rows, dout))
-        if ctx.act and not fuse_dact:
-            gy = activation_backward(y, gy, ctx.act)
-        wsb = lib.kgcn_dense_wgrad_workspace_bytes(m, rows, dout)
-        dwa = torch.empty((rows, dout), device=gy.device, dtype=torch.float32)
-        with _param_grad_stage(ctx, wsb, gy.device) as wsp:
-            if fuse_dact:
-                check(lib.kgcn_dense_wgrad_dact_f32(ptr(x2d), rows, ptr(gy), ptr(y), dout, ctx.act, m, rows, dout, ptr(dwa), None,
-                                                    ptr(wsp), wsb, current_stream()), "kgcn_dense_wgrad_dact_f32")
-            else:
-                check(lib.kgcn_dense_wgrad_f32(ptr(x2d), rows, ptr(gy), dout, m, rows, dout, ptr(dwa), None, ptr(wsp), wsb,
-                                               current_stream()), "kgcn_dense_wgrad_f32")
+        din = w.shape[0]
+        dwa, _ = _dense_wgrad(ctx, x2d, w, _f32c(gy, "grad"), y, True, False, dact_pending=bool(ctx.act))
         return None, dwa[:din], dwa[din:din + 1].reshape(bias.shape), None, None, None
 
 
@@ -879,6 +891,35 @@ def dense(x2d, w, bias=None, activation=None):
     return _Dense.apply(x2d, w, bias, act_code(activation))
 
 
+def _readout(y, T, N, d, join=None, join_col=0):
+    """-> pooled [T, d], the sum over the N node rows of every graph of y [T * N, d] (GraphGather).  join: a [T, wide] buffer whose
+    columns join_col .. join_col + d receive it (the concatenation of several read-outs, model_gin.py:61, without a concatenation
+    pass: see join_columns); pooled is then that column block."""
+    if join is None:
+        pooled = torch.empty((T, d), device=y.device, dtype=torch.float32)
+        check(lib.kgcn_graph_gather_fwd_f32(ptr(y), T, N, d, ptr(pooled), current_stream()), "kgcn_graph_gather_fwd_f32")
+        return pooled
+    if join.dtype != torch.float32 or join.dim() != 2 or join.shape[0] != T or not join.is_contiguous() or \
+            join_col < 0 or join_col + d > join.shape[1]:
+        raise _lib.KgcnHipError("join buffer %s does not take a [%d, %d] read-out at column %d" % (tuple(join.shape), T, d, join_col))
+    pooled = join[:, join_col:join_col + d]
+    check(lib.kgcn_graph_gather_fwd_ld_f32(ptr(y), T, N, d, pooled.data_ptr(), join.shape[1], current_stream()),
+          "kgcn_graph_gather_fwd_ld_f32")
+    return pooled
+
+
+def _readout_grad(gp, gy, T, N, d, shape):
+    """-> broadcast of gp [T, d] over the N nodes of every graph (+ gy, the gradient of the rows themselves, when there is one) as a
+    new tensor of `shape` -- ONE pass where the row length allows 16-byte accesses.  gp: contiguous float32."""
+    g = torch.empty(shape, device=gp.device, dtype=torch.float32)
+    if gy is None or d % 4 != 0:
+        check(lib.kgcn_graph_gather_bwd_f32(ptr(gp), T, N, d, ptr(g), current_stream()), "kgcn_graph_gather_bwd_f32")
+        return g if gy is None else g + gy
+    check(lib.kgcn_graph_gather_bwd_add_f32(ptr(gp), ptr(_f32c(gy, "grad")), T, N, d, ptr(g), current_stream()),
+          "kgcn_graph_gather_bwd_add_f32")
+    return g
+
+
 class _DenseGather(torch.autograd.Function):
     """y = act(x W + b) of a layer whose output is read out by GraphGather -- and also handed on to the next layer when the
     caller uses y (example_model/model_gin.py:45-60): returns (y [T, N, dout], pooled [T, dout]).  Backward: the incoming
@@ -887,34 +928,12 @@ class _DenseGather(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x2d, w, bias, act, T, N, join=None, join_col=0):
-        # join: a [T, wide] buffer whose columns join_col .. join_col + dout receive the read-out (the concatenation of several
-        # read-outs, model_gin.py:61, without a concatenation pass: see join_columns)
         x2d, w = _f32c(x2d, "x"), _f32c(w, "w")
-        m, din = x2d.shape
-        dout = w.shape[1]
-        if w.shape[0] != din or m != T * N:
+        m, dout = x2d.shape[0], w.shape[1]
+        if m != T * N:
             raise _lib.KgcnHipError("kernel %s / %d graphs of %d nodes do not match inputs %s" % (tuple(w.shape), T, N, tuple(x2d.shape)))
-        b = None if bias is None else _f32c(bias, "bias").reshape(-1)
-        y = torch.empty((m, dout), device=x2d.device, dtype=torch.float32)
-        tab, tb = weight_tables.lookup(w, 0)
-        if tab is not None:
-            check(lib.kgcn_dense_fwd_tab_f32(ptr(x2d), m, din, din, ptr(w), dout, 0, ptr(b), ptr(y), dout,
-                                             dout, int(act), ptr(tab), tb, current_stream()), "kgcn_dense_fwd_tab_f32")
-        else:
-            weight_tables.register(w)
-            wsb, wsp = _dense_ws(din, dout, x2d.device)
-            check(lib.kgcn_dense_fwd_ws_f32(ptr(x2d), m, din, din, ptr(w), dout, 0, ptr(b), ptr(y), dout,
-                                            dout, int(act), ptr(wsp), wsb, current_stream()), "kgcn_dense_fwd_ws_f32")
-        if join is None:
-            pooled = torch.empty((T, dout), device=x2d.device, dtype=torch.float32)
-            check(lib.kgcn_graph_gather_fwd_f32(ptr(y), T, N, dout, ptr(pooled), current_stream()), "kgcn_graph_gather_fwd_f32")
-        else:
-            if join.dtype != torch.float32 or join.dim() != 2 or join.shape[0] != T or not join.is_contiguous() or \
-                    join_col < 0 or join_col + dout > join.shape[1]:
-                raise _lib.KgcnHipError("join buffer %s does not take a [%d, %d] read-out at column %d" % (tuple(join.shape), T, dout, join_col))
-            pooled = join[:, join_col:join_col + dout]
-            check(lib.kgcn_graph_gather_fwd_ld_f32(ptr(y), T, N, dout, pooled.data_ptr(), join.shape[1], current_stream()),
-                  "kgcn_graph_gather_fwd_ld_f32")
+        y = _dense_fwd(x2d, w, bias, act)
+        pooled = _readout(y, T, N, dout, join, join_col)
         ctx.act, ctx.T, ctx.N = int(act), int(T), int(N)
         ctx.save_for_backward(x2d, w, y)
         ctx.bias_shape = None if bias is None else tuple(bias.shape)
@@ -932,64 +951,38 @@ class _DenseGather(torch.autograd.Function):
             return None, None, None, None, None, None, None, None
         gy = None if gy is None else _f32c(gy.reshape(m, dout), "grad")
         gp_ld = dout
+        need_x, need_w = ctx.needs_input_grad[:2]
+        need_b = ctx.bias_shape is not None and ctx.needs_input_grad[2]
         if gp is not None:
             # a column block of a wider gradient (the backward of join_columns / torch.cat) is read where it lies
             strided = gp.dtype == torch.float32 and gp.dim() == 2 and gp.stride(1) == 1 and gp.stride(0) % 4 == 0 and \
                 gp.stride(0) >= dout and gp.data_ptr() % 16 == 0
-            if strided and ctx.act and ctx.needs_input_grad[0] and lib.kgcn_dense_dx_dact_gather_supported(m, din, dout):
+            if strided and ctx.act and need_x and lib.kgcn_dense_dx_dact_gather_supported(m, din, dout):
                 gp_ld = gp.stride(0)
             else:
                 gp = _f32c(gp, "grad")
         dx = dw = db = None
-        need_x = ctx.needs_input_grad[0]
-        need_b = ctx.bias_shape is not None and ctx.needs_input_grad[2]
-        if need_x and ctx.needs_input_grad[1] and (gp is None or (ctx.act and gp.dtype == torch.float32 and gp.dim() == 2 and
-                                                                  gp.stride(1) == 1)) and \
+        if need_x and need_w and (gp is None or (ctx.act and gp.dtype == torch.float32 and gp.dim() == 2 and gp.stride(1) == 1)) and \
                 _dense_bwd_fused_ok(x2d, w, gy, y if ctx.act else None, gp, gp_ld if gp is not None else 0, N, ctx.act in (1, 3)):
             # the whole backward in one pass: the read-out's gradient joins (or stands for) the row gradient while the rows are staged
             dx, dw, db = _dense_bwd_fused(ctx, x2d, w, gy, y, ctx.act, need_b, gp, gp_ld if gp is not None else 0, N)
             return dx, dw, db, None, None, None, None, None
         if gp is not None and ctx.act and need_x and lib.kgcn_dense_dx_dact_gather_supported(m, din, dout):
             dx = torch.empty_like(x2d)
-            dpre = torch.empty((m, dout), device=x2d.device, dtype=torch.float32)
-            tab, tb = weight_tables.lookup(w, 1)
-            ready = 1
-            if tab is None:
-                tb, tab = _dense_ws(dout, din, x2d.device)
-                ready = 0
+            g = torch.empty((m, dout), device=x2d.device, dtype=torch.float32)
+            tab, tb, ready = _w_operand(w, 1, x2d.device)
             check(lib.kgcn_dense_dx_dact_gather_f32(ptr(gy), gp.data_ptr(), gp_ld, N, ptr(y), m, dout, dout, ptr(w), dout, din, ptr(dx), din,
-                                                    ctx.act, ptr(dpre), ptr(tab), tb, ready, current_stream()),
+                                                    ctx.act, ptr(g), ptr(tab), tb, ready, current_stream()),
                   "kgcn_dense_dx_dact_gather_f32")
-            g = dpre
         else:
             # incoming gradient as a tensor, then the plain dense backward
-            if gp is not None:
-                g = torch.empty((m, dout), device=x2d.device, dtype=torch.float32)
-                if gy is not None and dout % 4 == 0:
-                    check(lib.kgcn_graph_gather_bwd_add_f32(ptr(gp), ptr(gy), T, N, dout, ptr(g), current_stream()),
-                          "kgcn_graph_gather_bwd_add_f32")
-                else:
-                    check(lib.kgcn_graph_gather_bwd_f32(ptr(gp), T, N, dout, ptr(g), current_stream()), "kgcn_graph_gather_bwd_f32")
-                    if gy is not None:
-                        g = g + gy
-            else:
-                g = gy
+            g = gy if gp is None else _readout_grad(gp, gy, T, N, dout, (m, dout))
             if ctx.act:
                 g = activation_backward(y, g, ctx.act)
             if need_x:
-                dx = torch.empty_like(x2d)
-                tab, tb = weight_tables.lookup(w, 1)
-                if tab is not None:
-                    check(lib.kgcn_dense_fwd_tab_f32(ptr(g), m, dout, dout, ptr(w), dout, 1, None, ptr(dx), din, din, 0, ptr(tab), tb,
-                                                     current_stream()), "kgcn_dense_fwd_tab_f32(dx)")
-                else:
-                    wsb, wsp = _dense_ws(dout, din, g.device)
-                    check(lib.kgcn_dense_fwd_ws_f32(ptr(g), m, dout, dout, ptr(w), dout, 1, None, ptr(dx), din, din, 0, ptr(wsp), wsb,
-                                                    current_stream()), "kgcn_dense_fwd_ws_f32(dx)")
-        need_w = ctx.needs_input_grad[1]
-        need_b = ctx.bias_shape is not None and ctx.needs_input_grad[2]
+                dx = _dense_dx(g, w, x2d)
         if need_w or need_b:
-            dw, db = _Dense._wgrad(ctx, x2d, w, g, y, m, din, dout, need_w, need_b, False)
+            dw, db = _dense_wgrad(ctx, x2d, w, g, y, need_w, need_b)
         return dx, dw, db, None, None, None, None, None
 
 
@@ -1164,17 +1157,7 @@ class _GinDense(torch.autograd.Function):
         agg = torch.empty((m, din), device=x.device, dtype=torch.float32)
         check(lib.kgcn_gin_aggregate_f32(adj.desc_array(False), 1, ptr(x), din, ptr(e), ptr(agg), current_stream()),
               "kgcn_gin_aggregate_f32")
-        b = None if bias is None else _f32c(bias, "bias").reshape(-1)
-        y = torch.empty((m, dout), device=x.device, dtype=torch.float32)
-        tab, tb = weight_tables.lookup(w, 0)
-        if tab is not None:
-            check(lib.kgcn_dense_fwd_tab_f32(ptr(agg), m, din, din, ptr(w), dout, 0, ptr(b), ptr(y), dout, dout, int(act), ptr(tab), tb,
-                                             current_stream()), "kgcn_dense_fwd_tab_f32")
-        else:
-            weight_tables.register(w)
-            wsb, wsp = _dense_ws(din, dout, x.device)
-            check(lib.kgcn_dense_fwd_ws_f32(ptr(agg), m, din, din, ptr(w), dout, 0, ptr(b), ptr(y), dout, dout, int(act), ptr(wsp), wsb,
-                                            current_stream()), "kgcn_dense_fwd_ws_f32")
+        y = _dense_fwd(agg, w, bias, act)
         ctx.act, ctx.eps_shape = int(act), tuple(eps.shape)
         ctx.bias_shape = None if bias is None else tuple(bias.shape)
         _record_params(ctx, w, bias)
@@ -1188,11 +1171,7 @@ class _GinDense(torch.autograd.Function):
         dout = w.shape[1]
         gy = _f32c(gy.reshape(m, dout), "grad")
         deps = torch.empty((1,), device=gy.device, dtype=torch.float32)
-        tab, tb = weight_tables.lookup(w, 1)
-        ready = 1
-        if tab is None:
-            tb, tab = _dense_ws(dout, din, gy.device)
-            ready = 0
+        tab, tb, ready = _w_operand(w, 1, gy.device)
         need_w = ctx.needs_input_grad[3]
         need_b = ctx.bias_shape is not None and ctx.needs_input_grad[4]
         if need_w and _dense_bwd_fused_ok(agg, w, gy, y):
@@ -1204,9 +1183,7 @@ class _GinDense(torch.autograd.Function):
                 check(lib.kgcn_dense_bwd_dot_f32(ptr(gy), ptr(y), ctx.act, dout, ptr(agg), din, m, din, dout, ptr(w), dout, ptr(x), din,
                                                  ptr(dw), ptr(db), ptr(deps), ptr(tab), tb, ready, ptr(wsp), wsb, current_stream()),
                       "kgcn_dense_bwd_dot_f32")
-            if db is not None:
-                db = db.reshape(ctx.bias_shape)
-            return None, (deps.reshape(ctx.eps_shape) if ctx.needs_input_grad[1] else None), None, dw, db, None
+            return None, (deps.reshape(ctx.eps_shape) if ctx.needs_input_grad[1] else None), None, dw, _bias_grad(ctx, db), None
         dpre = torch.empty_like(gy)
         wsb = lib.kgcn_dense_dx_dact_dot_workspace_bytes(m, din)
         wsp = _lib.workspace(wsb, gy.device)
@@ -1215,7 +1192,7 @@ class _GinDense(torch.autograd.Function):
               "kgcn_dense_dx_dact_dot_f32")
         dw = db = None
         if need_w or need_b:
-            dw, db = _Dense._wgrad(ctx, agg, w, dpre, y, m, din, dout, need_w, need_b, False)
+            dw, db = _dense_wgrad(ctx, agg, w, dpre, y, need_w, need_b)
         return None, (deps.reshape(ctx.eps_shape) if ctx.needs_input_grad[1] else None), None, dw, db, None
 
 
@@ -1361,11 +1338,8 @@ class _Gather(torch.autograd.Function):
     def forward(ctx, x):
         x = _f32c(x, "inputs")
         B, N, d = x.shape
-        out = torch.empty((B, d), device=x.device, dtype=torch.float32)
-        check(lib.kgcn_graph_gather_fwd_f32(ptr(x), B, N, d, ptr(out), current_stream()),
-              "kgcn_graph_gather_fwd_f32")
         ctx.shape = (B, N, d)
-        return out
+        return _readout(x, B, N, d)
 
     @staticmethod
     def backward(ctx, g):
@@ -1390,25 +1364,13 @@ class _GatherTee(torch.autograd.Function):
     def forward(ctx, x):
         x = _f32c(x, "inputs")
         B, N, d = x.shape
-        out = torch.empty((B, d), device=x.device, dtype=torch.float32)
-        check(lib.kgcn_graph_gather_fwd_f32(ptr(x), B, N, d, ptr(out), current_stream()), "kgcn_graph_gather_fwd_f32")
         ctx.shape = (B, N, d)
-        return x.view_as(x), out
+        return x.view_as(x), _readout(x, B, N, d)
 
     @staticmethod
     def backward(ctx, gx, gp):
         B, N, d = ctx.shape
-        if gp is None:
-            return gx
-        gp = _f32c(gp, "grad")
-        dx = torch.empty((B, N, d), device=gp.device, dtype=torch.float32)
-        if gx is None or d % 4 != 0:
-            check(lib.kgcn_graph_gather_bwd_f32(ptr(gp), B, N, d, ptr(dx), current_stream()), "kgcn_graph_gather_bwd_f32")
-            return dx if gx is None else dx + gx
-        gx = _f32c(gx, "grad")
-        check(lib.kgcn_graph_gather_bwd_add_f32(ptr(gp), ptr(gx), B, N, d, ptr(dx), current_stream()),
-              "kgcn_graph_gather_bwd_add_f32")
-        return dx
+        return gx if gp is None else _readout_grad(_f32c(gp, "grad"), gx, B, N, d, (B, N, d))
 
 
 def graph_gather_tee(x):
@@ -2361,15 +2323,9 @@ class _GatherInto(torch.autograd.Function):
     def forward(ctx, y, join, join_col):
         y = _f32c(y, "inputs")
         T, N, d = y.shape
-        if join.dtype != torch.float32 or join.dim() != 2 or join.shape[0] != T or not join.is_contiguous() or \
-                join_col < 0 or join_col + d > join.shape[1]:
-            raise _lib.KgcnHipError("join buffer %s does not take a [%d, %d] read-out at column %d" % (tuple(join.shape), T, d, join_col))
-        pooled = join[:, join_col:join_col + d]
-        check(lib.kgcn_graph_gather_fwd_ld_f32(ptr(y), T, N, d, pooled.data_ptr(), join.shape[1], current_stream()),
-              "kgcn_graph_gather_fwd_ld_f32")
         ctx.shape = (T, N, d)
         ctx.set_materialize_grads(False)
-        return pooled
+        return _readout(y, T, N, d, join, join_col)
 
     @staticmethod
     def backward(ctx, g):
