@@ -84,7 +84,9 @@ extern "C" {
  * The SpMM route report added an entry point only (version still 2): kgcn_spmm_route_query (+ kgcn_spmm_route).
  * The pair ranking added entry points only (version still 2): kgcn_pair_rank_select_f32 / _emit_f32 / _table_i32 (+ _workspace_bytes).
  * The smooth attribution methods added entry points only (version still 2): kgcn_ig_perturb_rows_f32, kgcn_ig_perturb_values_f32,
- * kgcn_seq_convpool_perturbed_fwd_f32. */
+ * kgcn_seq_convpool_perturbed_fwd_f32.
+ * Cross-validation added entry points only (version still 2): kgcn_multitask_softmax2_ce_f32, kgcn_binary_metrics_f32
+ * (+ kgcn_binary_metrics_workspace_bytes). */
 #define KGCN_HIP_ABI_VERSION 2
 
 /* Column index of the padding entries of a row-padded batch (see row_pad): they carry value 0 and
@@ -1037,6 +1039,36 @@ int kgcn_pair_rank_table_i32(const float* score, const int32_t* row, const int32
                              const int64_t* top_ratio, int32_t num_top, uint8_t* train_edge, uint8_t* test_edge, uint8_t* new_edge,
                              int64_t* score_ranking, int64_t* hits, int64_t* covered, void* workspace, int64_t workspace_bytes,
                              void* stream);
+
+/* -- k-fold cross-validation of the compound-protein interaction networks (gcn.py train_cv; csrc/cvloss.hip, csrc/cvmetrics.hip)
+ * Loss head of sample_chem/compound-protein_interaction/multitask.py:53-86 (singletask.py: tasks = 1): logits [batch, 2, tasks],
+ * labels and mask_label [batch, tasks] (a row counts where mask_label != 0, is positive where labels != 0).
+ *   stats      [3 tasks + 1] = each_cost | each_correct_count | each_count | cost: the summed two-class sparse softmax cross entropy
+ *              softplus(z_other - z_label) per task, the rows whose argmax (a tie is class 0) is the label, the rows counted, and
+ *              cost = sum over tasks (a sum, not a mean).  Counts are floats holding integers.
+ *   prediction [batch, tasks] = softmax(logits, axis 1)[:, 1, :] = sigmoid(z1 - z0), for every row whatever its mask
+ *   dlogits    [batch, 2, tasks] = d cost / d logits (0 for rows not counted)
+ *   accum      NULL, or a [3 tasks + 1] block that the call adds stats to in place as its last step (fixed order, one addition
+ *              per entry per call): a captured step accumulates an epoch on the device.
+ * Fixed summation order, no float atomics; asynchronous and capturable. */
+#define KGCN_SOFTMAX2_MAX_BATCH (1 << 24)
+#define KGCN_SOFTMAX2_MAX_TASKS 65535
+int kgcn_multitask_softmax2_ce_f32(const float* logits, const float* labels, const float* mask_label, int64_t batch, int32_t tasks,
+                                   float* dlogits, float* prediction, float* stats, float* accum, void* stream);
+
+/* Binary-classification metrics of compute_metrics (gcn.py:170-256) for all tasks in one call: score [n, tasks] with row stride
+ * score_ld, label and mask [n, tasks] contiguous (mask NULL: every row counts, as the reference; a row counts where mask != 0,
+ * is positive where label != 0).  Per task, counts [tasks, 8] int64, all exact:
+ *   n_used, P, TP, FP (at score > threshold, strict), n_nonfinite, auc_num2, n_groups, 0
+ * with auc_num2 = sum over the distinct scores g in descending order of (fp_g - fp_g-1) (tp_g + tp_g-1), so that
+ * ROC-AUC = auc_num2 / (2 P (n_used - P)), and ap [tasks] fp64 = sum_g ((tp_g - tp_g-1) / P) (tp_g / (tp_g + fp_g)) (0 when P = 0),
+ * added in a fixed order.  -0.0 ties with +0.0.  A task with n_nonfinite != 0 has no meaningful curve sums (the caller refuses it).
+ * One radix sort of n * tasks 64-bit keys (rocPRIM) + one workgroup per task; no atomics: bitwise reproducible.  Asynchronous. */
+#define KGCN_BINARY_METRICS_MAX_ELEMENTS (1ll << 31)
+#define KGCN_BINARY_METRICS_MAX_TASKS (1 << 20)
+int64_t kgcn_binary_metrics_workspace_bytes(int64_t n, int32_t tasks);
+int kgcn_binary_metrics_f32(const float* score, int64_t score_ld, const float* label, const float* mask, int64_t n, int32_t tasks,
+                            float threshold, int64_t* counts, double* ap, void* workspace, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -340,6 +340,12 @@ SIGNATURES = {
                                                 ctypes.POINTER(c_i64), c_i32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i64,
                                                 ctypes.c_void_p]),
+    # cross-validation: loss head of the compound-protein interaction networks and the ranking metrics (csrc/cvloss.hip, cvmetrics.hip)
+    "kgcn_multitask_softmax2_ce_f32": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_i64, c_i32, c_f32p, c_f32p, c_f32p, c_f32p,
+                                                      ctypes.c_void_p]),
+    "kgcn_binary_metrics_workspace_bytes": (c_i64, [c_i64, c_i32]),
+    "kgcn_binary_metrics_f32": (ctypes.c_int, [c_f32p, c_i64, c_f32p, c_f32p, c_i64, c_i32, ctypes.c_float, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
     "kgcn_graph_gather_bwd_ld_f32": (ctypes.c_int, [c_f32p, c_i64, c_i64, c_i32, c_i32, c_f32p, ctypes.c_void_p]),
     "kgcn_graph_gather_bwd_add_f32": (ctypes.c_int, [c_f32p, c_f32p, c_i64, c_i32, c_i32, c_f32p, ctypes.c_void_p]),
     "kgcn_dot_workspace_bytes": (c_i64, [c_i64]),

@@ -19,6 +19,8 @@ between layer and activation it is one HIP elementwise kernel (ops.activation). 
 
   SeqCNN       -- sample_protein/sequence/cnn.py:36-90  Embedding, 3 x [Conv1D relu, MaxPooling1D], Conv1D(1, tanh), BN, Dense(52), BN,
                   relu, Dense(label_dim) (csrc/conv1d.hip); class-weighted softmax CE
+  CPIMultitaskNet -- sample_chem/compound-protein_interaction/multitask.py:35-86  GraphConv(512) sigmoid, GraphGather, Dense(2 T)
+                  read as [B, 2, T]; two-way softmax cross entropy per task under mask_label (csrc/cvloss.hip)
 
 Keras learning-phase semantics (quirk Q6): the reference calls BatchNormalization / Dropout
 without `training=`; under TF1 graph mode that is inference behaviour -- BN normalises with its
@@ -172,6 +174,33 @@ class MultitaskGCN(nn.Module):
         layer = self.dense2(layer)
         layer = self.gather(layer, ragged=rb)
         return self.out(layer)                      # prediction = sigmoid(logits)
+
+
+class CPIMultitaskNet(nn.Module):
+    """sample_chem/compound-protein_interaction/multitask.py:35-51 (singletask.py: label_dim = 1): GraphConv(512) -> sigmoid ->
+    GraphGather -> Dense(2 label_dim), read as logits [B, 2, label_dim] (logits[b, c, t] = out[b, c label_dim + t]) with a
+    two-way softmax per task.  enabled_node_nums is accepted and unused, as in the file."""
+
+    WIDTH = 512
+
+    def __init__(self, adj_channel_num=1, label_dim=1):
+        super().__init__()
+        self.label_dim = int(label_dim)
+        self.conv = layers.GraphConv(self.WIDTH, adj_channel_num, activation="sigmoid")     # :39-40
+        self.gather = layers.GraphGather()                                                  # :41
+        self.out = KerasDense(2 * self.label_dim)                                           # :42
+
+    def forward(self, features, adjs, enabled_node_nums=None):
+        adjs = layers._pack(adjs, features)
+        layer = self.gather(self.conv(features, adj=adjs))
+        return self.out(layer).view(-1, 2, self.label_dim)                                  # :44
+
+    @staticmethod
+    def loss(logits, labels, mask_label, accum=None):
+        """compute_metrics (:53-86) -> (cost_opt, cost_sum): the same tensor, the sum over tasks of the summed cross entropy
+        of the rows with mask_label != 0.  accum: ops.multitask_softmax2_ce's device accumulator block."""
+        cost = ops.multitask_softmax2_ce(logits, labels, mask_label, accum=accum)[0]
+        return cost, cost
 
 
 def wants_augmented_features(model, n_features):

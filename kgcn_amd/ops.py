@@ -2625,3 +2625,91 @@ def pair_rank_table(score, row, col, target_codes, test_codes, top_ratio):
                                        ptr(hits) if top else None, ptr(covered) if top else None, ptr(ws), wsb, current_stream()),
           "kgcn_pair_rank_table_i32")
     return flags[0], flags[1], flags[2], ranking, hits, covered
+
+
+# -------------------------------------------------------------------------------------------------
+# k-fold cross-validation of the compound-protein interaction networks (gcn.py train_cv): the loss head of
+# sample_chem/compound-protein_interaction/multitask.py (csrc/cvloss.hip) and the ranking metrics of compute_metrics
+# (gcn.py:170-256; csrc/cvmetrics.hip)
+# -------------------------------------------------------------------------------------------------
+class _MultitaskSoftmax2CE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, labels, mask_label, accum):
+        x = _f32c(logits, "logits")
+        z = _f32c(labels, "labels")
+        ml = _f32c(mask_label, "mask_label")
+        if z.dim() != 2 or z.shape != ml.shape or x.shape[0] != z.shape[0] or x.numel() != 2 * z.numel():
+            raise _lib.KgcnHipError("multitask_softmax2_ce: logits %s must be [B, 2, T] (or [B, 2 T]) for labels %s and mask_label %s"
+                                    % (tuple(x.shape), tuple(z.shape), tuple(ml.shape)))
+        B, T = z.shape
+        if accum is not None:
+            require_gpu(accum, "accum")
+            if accum.dtype != torch.float32 or not accum.is_contiguous() or accum.numel() != 3 * T + 1:
+                raise _lib.KgcnHipError("multitask_softmax2_ce: the accumulator is a contiguous float32 block of 3 T + 1 = %d" % (3 * T + 1))
+        dlog = torch.empty_like(x)
+        pred = torch.empty((B, T), device=x.device, dtype=torch.float32)
+        stats = torch.empty((3 * T + 1,), device=x.device, dtype=torch.float32)
+        check(lib.kgcn_multitask_softmax2_ce_f32(ptr(x), ptr(z), ptr(ml), B, T, ptr(dlog), ptr(pred), ptr(stats), ptr(accum),
+                                                 current_stream()), "kgcn_multitask_softmax2_ce_f32")
+        ctx.save_for_backward(dlog)
+        ctx.set_materialize_grads(False)
+        each = stats[:3 * T]
+        ctx.mark_non_differentiable(each, pred)
+        return stats[3 * T], each, pred
+
+    @staticmethod
+    def backward(ctx, g, g_each, g_pred):
+        (dlog,) = ctx.saved_tensors
+        return _loss_grad(dlog, None, g, 1), None, None, None
+
+
+def multitask_softmax2_ce(logits, labels, mask_label, accum=None):
+    """compute_metrics of sample_chem/compound-protein_interaction/multitask.py:53-86 in one HIP pass -> (cost, each_cost [T],
+    each_correct_count [T], each_count [T], prediction [B, T]).  logits [B, 2, T] (or the Dense output [B, 2 T] it is a view
+    of), labels and mask_label [B, T] float32; each_cost[t] sums the two-class sparse softmax cross entropy over the rows with
+    mask_label != 0, cost = sum_t each_cost[t] (cost_opt and cost_sum of the model alike), a tie of the two logits predicts
+    class 0, prediction = softmax(logits, axis=1)[:, 1, :] for every row.  accum: a float32 device block [3 T + 1] =
+    each_cost | each_correct_count | each_count | cost that the call adds its values to in place (an epoch's sums with one
+    read-back).  Only cost is differentiable."""
+    cost, each, pred = _MultitaskSoftmax2CE.apply(logits, labels, mask_label, accum)
+    T = labels.shape[1]
+    return cost, each[:T], each[T:2 * T], each[2 * T:], pred
+
+
+BINARY_METRICS_COLUMNS = ("n_used", "P", "TP", "FP", "n_nonfinite", "auc_num2", "n_groups", "spare")
+BINARY_METRICS_MAX_ELEMENTS, BINARY_METRICS_MAX_TASKS = 1 << 31, 1 << 20
+
+
+@torch.no_grad()
+def binary_metrics(score, label, mask=None, threshold=0.5):
+    """The sums behind compute_metrics (gcn.py:170-256) for every task at once -> (counts [T, 8] int64 numpy array with the
+    columns BINARY_METRICS_COLUMNS, ap [T] float64 numpy array).  score [n, T] float32 (rows may be strided), label [n, T],
+    mask None (every row counts, as the reference) or [n, T] (a row counts where mask != 0).  TP / FP count score > threshold;
+    auc_num2 / (2 P N) is roc_curve + auc, ap is average_precision_score (kgcn_amd.cv.metrics_from_counts derives every
+    metric).  One radix sort of all tasks' keys and one scan per task on the device; all integers exact, two runs agree bit
+    for bit.  Raises ValueError when a counted score is NaN or infinite (as scikit-learn's input check)."""
+    require_gpu(score, "score")
+    if score.dtype != torch.float32 or score.dim() != 2 or score.shape[0] < 1 or score.shape[1] < 1:
+        raise _lib.KgcnHipError("binary_metrics: score must be a float32 [n >= 1, T >= 1] tensor, got %s %s" % (score.dtype, tuple(score.shape)))
+    if score.stride(1) != 1 or score.stride(0) < score.shape[1]:
+        score = score.contiguous()
+    n, T = score.shape
+    if n * T > BINARY_METRICS_MAX_ELEMENTS or T > BINARY_METRICS_MAX_TASKS:
+        raise _lib.KgcnHipError("binary_metrics: %d x %d elements (at most 2^31, %d tasks)" % (n, T, BINARY_METRICS_MAX_TASKS))
+    lab = _f32c(label.to(torch.float32), "label")
+    mk = None if mask is None else _f32c(mask.to(torch.float32), "mask")
+    if tuple(lab.shape) != (n, T) or (mk is not None and tuple(mk.shape) != (n, T)):
+        raise _lib.KgcnHipError("binary_metrics: label / mask do not match score %s" % ((n, T),))
+    counts = torch.empty((T, 8), device=score.device, dtype=torch.int64)
+    ap = torch.empty((T,), device=score.device, dtype=torch.float64)
+    wsb = lib.kgcn_binary_metrics_workspace_bytes(n, T)
+    if wsb < 0:
+        check(1, "kgcn_binary_metrics_workspace_bytes")
+    ws = _lib.workspace(wsb, score.device, torch.uint8)
+    check(lib.kgcn_binary_metrics_f32(ptr(score), score.stride(0), ptr(lab), ptr(mk), n, T, float(threshold), ptr(counts), ptr(ap),
+                                      ptr(ws), wsb, current_stream()), "kgcn_binary_metrics_f32")
+    counts, ap = counts.cpu().numpy(), ap.cpu().numpy()
+    if counts[:, 4].any():
+        raise ValueError("binary_metrics: %d scores are NaN or infinite (tasks %s)"
+                         % (int(counts[:, 4].sum()), [int(t) for t in counts[:, 4].nonzero()[0]]))
+    return counts, ap

@@ -1,0 +1,115 @@
+"""models.CPIMultitaskNet (sample_chem/compound-protein_interaction/multitask.py) on the GPU against tests/cv_oracle in fp64 at
+B = 5, N = 10, F = 8, T = 3 with one and two adjacency channels: logits, cost and every parameter gradient within the bounds of
+tests/golden/cv_bounds.json; then ten replays of the captured training step against ten eager steps, bit for bit."""
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import cv_oracle as O  # noqa: E402
+from oracle import kgcn_oracle as K  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+BOUNDS = json.load(open(os.path.join(ROOT, "tests", "golden", "cv_bounds.json")))["bounds"]
+B, N, F, T = 5, 10, 8, 3
+
+
+def nerr(got, ref):
+    ref = np.asarray(ref, np.float64)
+    return float(np.abs(np.asarray(got, np.float64) - ref).max()) / max(1.0, float(np.abs(ref).max()))
+
+
+def held(what, got, ref, label=""):
+    e = nerr(got, ref)
+    print("%-12s %-10s err / max(1, |ref|) = %.3e (bound %.3e)" % (what, label, e, BOUNDS[what]))
+    assert e <= BOUNDS[what], (what, label, e, BOUNDS[what])
+
+
+@pytest.mark.parametrize("C", [1, 2])
+def test_forward_loss_and_gradients(C):
+    import torch
+    from kgcn_amd import models
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(40 + C)
+    per_channel = [K.synth_mol_graphs(rng, B, N, 2) for _ in range(C)]
+    adjs = [[per_channel[c][b][0] for c in range(C)] for b in range(B)]
+    x = rng.standard_normal((B, N, F)).astype(np.float32)
+    labels = (rng.random((B, T)) < 0.5).astype(np.float32)
+    mask = np.ones((B, T), np.float32)
+    mask[1, 0] = mask[3, 2] = 0.0
+    torch.manual_seed(C)
+    model = models.CPIMultitaskNet(adj_channel_num=C, label_dim=T).to(dev)
+    tx = torch.as_tensor(x, device=dev)
+    logits = model(tx, adjs)
+    assert tuple(logits.shape) == (B, 2, T)
+    with torch.no_grad():                                           # a bias that is not zero, so that its path is checked too
+        for b in model.conv.bias:
+            b.copy_(torch.as_tensor(rng.standard_normal(tuple(b.shape)).astype(np.float32) * 0.1, device=dev))
+        model.out.bias.copy_(torch.as_tensor(rng.standard_normal(2 * T).astype(np.float32) * 0.1, device=dev))
+    logits = model(tx, adjs)
+    cost, cost_sum = models.CPIMultitaskNet.loss(logits, torch.as_tensor(labels, device=dev), torch.as_tensor(mask, device=dev))
+    assert cost is cost_sum
+    cost.backward()
+    p = {"w": [w.detach().cpu().numpy() for w in model.conv.w], "b": [b.detach().cpu().numpy() for b in model.conv.bias],
+         "kernel": model.out.kernel.detach().cpu().numpy(), "bias": model.out.bias.detach().cpu().numpy()}
+    L, ref_logits, g = O.model_loss_grads(x, adjs, p, labels, mask)
+    held("model_logits", logits.detach().cpu().numpy(), ref_logits)
+    held("model_cost", float(cost.detach()), L["cost"])
+    for c in range(C):
+        held("model_grad", model.conv.w[c].grad.cpu().numpy(), g["w"][c], "w%d" % c)
+        held("model_grad", model.conv.bias[c].grad.cpu().numpy().reshape(-1), g["b"][c], "b%d" % c)
+    held("model_grad", model.out.kernel.grad.cpu().numpy(), g["kernel"], "kernel")
+    held("model_grad", model.out.bias.grad.cpu().numpy(), g["bias"], "bias")
+
+
+def _setup():
+    import torch
+    from kgcn_amd import data_util as D, models, train
+    dev = torch.device("cuda:0")
+    z = np.load(os.path.join(ROOT, "tests", "golden", "g11_cv.npz"), allow_pickle=False)
+    channels, _ = D.build_adjs({"dense_adj": z["ds_dense_adj"], "max_node_num": int(z["ds_max_node_num"])})
+    ds = D.DeviceGraphDataset(channels, z["ds_feature"], device=dev)
+    sb = ds.static_batch(B)
+    labels = sb.add_table(torch.as_tensor(z["ds_label"], device=dev))
+    mask = sb.add_table(torch.as_tensor(z["ds_mask_label"], device=dev))
+    sb.load(np.arange(B))
+    torch.manual_seed(0)
+    model = models.CPIMultitaskNet(adj_channel_num=len(channels), label_dim=T).to(dev)
+    model(sb.features, sb.adjacency)
+    return model, train.TFAdam(model.parameters(), lr=1e-2), sb, labels, mask
+
+
+def test_ten_replays_equal_ten_eager_steps():
+    import torch
+    from kgcn_amd import models, train
+    k = 10
+    model, opt, sb, labels, mask = _setup()
+    batches = [np.arange(i * B, (i + 1) * B) % 60 for i in range(k)]
+    batches[3] = batches[3][:3]                                    # a short batch: two dummy graphs
+    p0 = [q.detach().clone() for q in model.parameters()]
+    eager = []
+    for idx in batches:
+        sb.load(idx)
+        cs, _ = train.train_step(model, opt, models.CPIMultitaskNet.loss, sb.features, sb.adjacency, labels, mask)
+        eager.append(cs)
+    p_eager = [q.detach().cpu().numpy() for q in model.parameters()]
+    with torch.no_grad():
+        for q, q0 in zip(model.parameters(), p0):
+            q.copy_(q0)
+    opt2 = train.TFAdam(model.parameters(), lr=1e-2)
+    step = train.GraphedTrainStep(model, opt2, models.CPIMultitaskNet.loss, sb, labels, mask, capture_assembly=True)
+    replayed = []
+    for idx in batches:
+        sb.stage(idx)
+        cs, _ = step.replay()
+        replayed.append(float(cs))
+    torch.cuda.synchronize()
+    assert replayed == eager, (replayed, eager)
+    for a, q in zip(p_eager, model.parameters()):
+        assert np.array_equal(a, q.detach().cpu().numpy())
+    assert len(set(eager)) == k
