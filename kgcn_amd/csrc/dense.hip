@@ -530,6 +530,27 @@ static FwdRoute fwd_route(long m, int din, int dout, int trans_w, const RowFacts
 }
 static bool wide_table_route(FwdRoute r) { return r == FwdRoute::Gemmh || r == FwdRoute::Gemm3Table; }
 static bool reads_table(FwdRoute r) { return wide_table_route(r) || r == FwdRoute::Gemmn; }
+// W' of the f16 kernels lives behind the bf16 section of the table
+static const void* f16_table(const void* table, int din, int dout) { return static_cast<const char*>(table) + wtable_bf16_bytes(din, dout); }
+
+// dX of an ACTIVATED layer, dx = ((grad [+ d pooled of the row's graph]) (.) act'(act_out)) W^T, where that product -- the
+// contraction runs over the layer's OUTPUT width: K = dout, N = din, W used transposed -- takes a wide table kernel: act' is
+// formed inside it and d pre-activation written on the way.  dot_part: <product, dx> instead of the product (f16 kernel only).
+// -1: another route, or operands the kernel does not take (the launchers' own tests).
+static int launch_dx_dact_wide(const float* grad, const float* act_out, float* dpre, long m, int dout, long ld, const float* w,
+                               long w_ld, void* table, bool have_table, bool table_ready, float* dx, int din, long dx_ld, int act,
+                               hipStream_t s, const float* pooled_grad = nullptr, int n_nodes = 0, long pooled_ld = 0,
+                               float* dot_part = nullptr) {
+  const RowFacts f{aligned16(dact_base(grad, act_out)), ld, aligned16(dx), dx_ld};
+  const FwdRoute route = fwd_route(m, dout, din, 1, f, have_table);
+  if (!wide_table_route(route)) return -1;
+  if (!table_ready) launch_wtable_split(w, w_ld, 1, dout, din, table, s);
+  if (route == FwdRoute::Gemmh)
+    return launch_gemmh_dx_dact(grad, act_out, dpre, m, dout, ld, f16_table(table, dout, din), dx, din, dx_ld, act, s, pooled_grad,
+                                n_nodes, pooled_ld, dot_part);
+  if (dot_part) return -1;
+  return launch_gemm3_dx_dact(grad, act_out, dpre, m, dout, ld, table, dx, din, dx_ld, act, s, pooled_grad, n_nodes, pooled_ld);
+}
 
 static int launch_fwd_persist(const float* x, long m, int din, long x_ld, const float* w, long w_ld, int trans_w,
                               const float* bias, float* y, int dout, long y_ld, int act, hipStream_t s) {
@@ -567,9 +588,8 @@ static int dense_fwd_impl(const float* x, int64_t m, int32_t din, int64_t x_ld, 
       return launch_skinny_n_fwd(x, (long)m, din, (long)x_ld, w, (long)w_ld, bias, y, dout, (long)y_ld, act, s);
     case FwdRoute::SkinnyK:
       return launch_skinny_k_fwd(x, (long)m, din, (long)x_ld, w, (long)w_ld, trans_w, bias, y, dout, (long)y_ld, act, s);
-    case FwdRoute::Gemmh:                                // W' lives behind the bf16 section of the table
-      return launch_gemmh_fwd(x, (long)m, din, (long)x_ld, static_cast<const char*>(workspace) + wtable_bf16_bytes(din, dout),
-                              bias, y, dout, (long)y_ld, act, s);
+    case FwdRoute::Gemmh:
+      return launch_gemmh_fwd(x, (long)m, din, (long)x_ld, f16_table(workspace, din, dout), bias, y, dout, (long)y_ld, act, s);
     case FwdRoute::Gemm3Table:
     case FwdRoute::Gemm3:
       return launch_gemm3_fwd(x, (long)m, din, (long)x_ld, w, (long)w_ld, trans_w, bias, y, dout, (long)y_ld, act,
@@ -606,15 +626,10 @@ static int dense_dx_dact_impl(const float* grad, const float* act_out, int64_t m
   if (!grad || !act_out || !w || !dx || !dpre) return fail("kgcn_dense_dx_dact_f32: NULL operand");
   if (dpre == grad) return fail("kgcn_dense_dx_dact_f32: dpre must not alias grad");
   if (ld < dout || dx_ld < din || w_ld < dout) return fail("kgcn_dense_dx_dact_f32: leading dimension too small");
-  // the contraction runs over the layer's OUTPUT width: K = dout, N = din, W used transposed.  Where that product takes a wide
-  // table kernel, act' is formed inside it (the launcher tries the f16 kernel first and falls through to the bf16 one)
-  if (wide_table_route(fwd_route((long)m, dout, din, 1, RowFacts{aligned16(grad), (long)ld, aligned16(dx), (long)dx_ld},
-                                 workspace && workspace_bytes >= wtable_bytes(dout, din)))) {
-    if (!table_ready) launch_wtable_split(w, (long)w_ld, 1, dout, din, workspace, as_stream(stream));
-    const int rc = launch_gemm3_dx_dact(grad, act_out, dpre, (long)m, dout, (long)ld, workspace, dx, din, (long)dx_ld, act,
-                                        as_stream(stream));
-    if (rc >= 0) return rc;
-  }
+  const int rc = launch_dx_dact_wide(grad, act_out, dpre, (long)m, dout, (long)ld, w, (long)w_ld, workspace,
+                                     workspace && workspace_bytes >= wtable_bytes(dout, din), table_ready, dx, din, (long)dx_ld,
+                                     act, as_stream(stream));
+  if (rc >= 0) return rc;
   if (ld != dout) return fail("kgcn_dense_dx_dact_f32: rows must be contiguous (ld == dout) outside the fused form");
   // (50-wide layers: act' inside the operand tile of narrow.hip's kernel -- which then also writes d pre-activation -- was built
   // and measured: 34.2 us against 11.2 + 22.2 us of the two launches at 117,888 rows, 35-43 spilled registers; not kept)
@@ -645,9 +660,9 @@ extern "C" int kgcn_dense_dx_dact_gather_f32(const float* grad, const float* poo
   if (dpre == grad) return fail("kgcn_dense_dx_dact_gather_f32: dpre must not alias grad");
   if (ld < dout || dx_ld < din || w_ld < dout) return fail("kgcn_dense_dx_dact_gather_f32: leading dimension too small");
   if (!table || table_bytes < wtable_bytes(dout, din)) return fail("kgcn_dense_dx_dact_gather_f32: table / workspace too small");
-  if (!table_ready) launch_wtable_split(w, (long)w_ld, 1, dout, din, table, as_stream(stream));
-  const int rc = launch_gemm3_dx_dact(grad, act_out, dpre, (long)m, dout, (long)ld, table, dx, din, (long)dx_ld, act,
-                                      as_stream(stream), pooled_grad, n_nodes, (long)pooled_ld);
+  // (a wide table route whatever the operands' alignment: kgcn_dense_dx_dact_gather_supported above)
+  const int rc = launch_dx_dact_wide(grad, act_out, dpre, (long)m, dout, (long)ld, w, (long)w_ld, table, true, table_ready != 0, dx,
+                                     din, (long)dx_ld, act, as_stream(stream), pooled_grad, n_nodes, (long)pooled_ld);
   if (rc < 0) return fail("kgcn_dense_dx_dact_gather_f32: operands must be 16-byte aligned with ld %% 4 == 0");
   return rc;
 }
@@ -692,11 +707,9 @@ extern "C" int kgcn_dense_dx_dact_dot_f32(const float* grad, const float* act_ou
     return fail("kgcn_dense_dx_dact_dot_f32: workspace %lld < %lld bytes", (long long)workspace_bytes,
                 (long long)kgcn_dense_dx_dact_dot_workspace_bytes(m, din));
   hipStream_t s = as_stream(stream);
-  if (!table_ready) launch_wtable_split(w, (long)w_ld, 1, dout, din, table, s);
   float* part = static_cast<float*>(workspace);
-  const int rc = launch_gemmh_dx_dact(grad, act_out, dpre, (long)m, dout, (long)ld,
-                                      static_cast<const char*>(table) + wtable_bf16_bytes(dout, din), const_cast<float*>(dotx), din,
-                                      (long)dotx_ld, act, s, nullptr, 0, 0, part);
+  const int rc = launch_dx_dact_wide(grad, act_out, dpre, (long)m, dout, (long)ld, w, (long)w_ld, table, true, table_ready != 0,
+                                     const_cast<float*>(dotx), din, (long)dotx_ld, act, s, nullptr, 0, 0, part);
   if (rc < 0) return fail("kgcn_dense_dx_dact_dot_f32: operands must be 16-byte aligned with ld %% 4 == 0");
   if (rc) return rc;
   hipLaunchKernelGGL(dx_dot_final_kernel, dim3(1), dim3(256), 0, s, part, gemmh_dot_parts((long)m, din), dot_out);
@@ -736,8 +749,8 @@ extern "C" int kgcn_dense_bwd_f32(const float* grad, const float* pooled_grad, i
   float* part_dw = static_cast<float*>(workspace);
   float* part_db = part_dw + (long)pairs * din * dout;
   const int rc = launch_gemmb(grad, act_out, (long)m, din, dout, (long)ld, x, (long)x_ld,
-                              static_cast<const char*>(table) + wtable_bf16_bytes(dout, din), dx, (long)dx_ld, part_dw,
-                              dbias ? part_db : nullptr, act, pooled_grad, n_nodes, (long)pooled_ld, s, nullptr);
+                              f16_table(table, dout, din), dx, (long)dx_ld, part_dw, dbias ? part_db : nullptr, act, pooled_grad,
+                              n_nodes, (long)pooled_ld, s, nullptr);
   if (rc == -1) return fail("kgcn_dense_bwd_f32: operands must be 16-byte aligned with ld %% 4 == 0");
   if (rc < 0) return 1;
   return launch_reduce_pair(part_dw, (long)din * dout, dw, part_db, dout, dbias, rc, s);
@@ -766,8 +779,8 @@ extern "C" int kgcn_dense_bwd_dot_f32(const float* grad, const float* act_out, i
   float* part_db = part_dw + (long)pairs * din * dout;
   float* part_dot = part_db + (long)pairs * dout;                // one partial per workgroup: kNumCU floats
   const int rc = launch_gemmb(grad, act_out, (long)m, din, dout, (long)ld, x, (long)x_ld,
-                              static_cast<const char*>(table) + wtable_bf16_bytes(dout, din), const_cast<float*>(dotx), (long)dotx_ld,
-                              part_dw, dbias ? part_db : nullptr, act, nullptr, 0, 0, s, part_dot);
+                              f16_table(table, dout, din), const_cast<float*>(dotx), (long)dotx_ld, part_dw,
+                              dbias ? part_db : nullptr, act, nullptr, 0, 0, s, part_dot);
   if (rc == -1) return fail("kgcn_dense_bwd_dot_f32: operands must be 16-byte aligned with ld %% 4 == 0");
   if (rc < 0) return 1;
   hipLaunchKernelGGL(dx_dot_final_kernel, dim3(1), dim3(256), 0, s, part_dot, kNumCU, dot_out);

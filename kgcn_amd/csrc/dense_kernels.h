@@ -15,6 +15,30 @@ int64_t wtable_bf16_bytes(int din, int dout);
 int64_t wtable_bytes(int din, int dout);
 void launch_wtable_split(const float* w, long w_ld, int trans_w, int din, int dout, void* workspace, hipStream_t s);
 
+// ---- the backward operand of the wide kernels (gemm3 / gemmh / gemmb), passed by value in their arguments ---------------------
+// The contraction's operand is dpre = (grad [+ d pooled of the row's graph]) (.) act'(act_out).  The staging threads address
+// everything relative to the row they read (`base` = grad, or act_out where the read-out's gradient is all there is): the saved
+// output lies `ydiff` and the d pre-activation to write `pdiff` elements away; act' = c0 + c1 a + c2 a^2 (sigmoid 0, 1, -1;
+// tanh 1, 0, -1; relu is a template argument); bc != nullptr: row r adds bc[(r / bc_n) * bc_ld + .], bc_only: and has no grad.
+// (G3Dact after its first user; the name is part of the kernels' symbols.  gemmh.h's GhDact adds `dot_part` behind it.)
+struct G3Dact { long ydiff, pdiff; float c0, c1, c2; const float* bc; long bc_ld; int bc_n, bc_only; };
+inline const float* dact_base(const float* grad, const float* act_out) { return grad ? grad : act_out; }
+inline G3Dact dact_operands(const float* grad, const float* act_out, const float* dpre, const float* pooled_grad, long pooled_ld,
+                            int n_nodes, int dact) {
+  const float* base = dact_base(grad, act_out);
+  G3Dact da{};
+  da.ydiff = act_out ? act_out - base : 0;
+  da.pdiff = dpre ? dpre - base : 0;
+  da.c0 = dact == KGCN_ACT_TANH ? 1.f : 0.f;
+  da.c1 = dact == KGCN_ACT_SIGMOID ? 1.f : 0.f;
+  da.c2 = -1.f;
+  da.bc = pooled_grad;
+  da.bc_ld = pooled_ld;
+  da.bc_n = n_nodes > 0 ? n_nodes : 1;
+  da.bc_only = grad ? 0 : 1;
+  return da;
+}
+
 // ---- gemm3.hip: bf16 three-piece GEMMs of the wide layers -----------------------------------------------------------------
 // table == nullptr: W is split inside the kernel; else `table` is the fragment table of wtable.hip for (w, trans_w)
 int launch_gemm3_fwd(const float* x, long m, int din, long x_ld, const float* w, long w_ld, int trans_w, const float* bias,

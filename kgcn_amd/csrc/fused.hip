@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "kgcn_common.h"
+#include "kgcn_probe.h"
 
 namespace kgcn {
 
@@ -41,16 +42,7 @@ constexpr int MAX_WPB = 8;
 
 // Phase probe (tools/phase_probe.py builds a second library with -DKGCN_PROBE): per-wave sums of
 // s_memtime deltas per phase, written to a device buffer.  Compiled out of the product library.
-#ifdef KGCN_PROBE
-__device__ long long* g_probe = nullptr;
-#define PROBE_DECL long long pt_[8] = {0, 0, 0, 0, 0, 0, 0, 0}; long long pc_ = __builtin_readcyclecounter();
-#define PROBE(k) { const long long n_ = __builtin_readcyclecounter(); pt_[k] += n_ - pc_; pc_ = n_; }
-#define PROBE_FLUSH(gw) if (g_probe && lane == 0) { for (int k_ = 0; k_ < 8; ++k_) g_probe[(long)(gw) * 8 + k_] = pt_[k_]; }
-#else
-#define PROBE_DECL
-#define PROBE(k)
-#define PROBE_FLUSH(gw)
-#endif
+KP_BUFFER(g_probe, kgcn_probe_set)
 
 __device__ __forceinline__ void wave_sync() {
   // Hand-off of LDS data between lanes of ONE wave.  The LDS unit executes a wave's DS
@@ -709,7 +701,7 @@ __global__ __launch_bounds__(512, 2) void graphconv_fwd_full_kernel(
 
   int t_prev = t;      // graph whose FW sits in the gather tile (valid from the second step on)
   bool has_next = true;
-  PROBE_DECL
+  KP_DECL(8)
   auto aggregate_prev = [&]() __attribute__((always_inline)) {
     float* ot = out + (long)hot(t_prev) * N * D;
     aggregate_rows_full<LAY>(ws.ecv, ev, ws.rp, ws.b, lane, [&](int r, int c4, f32x4 v) {
@@ -718,7 +710,7 @@ __global__ __launch_bounds__(512, 2) void graphconv_fwd_full_kernel(
   };
   auto step = [&](auto agg_tag) __attribute__((always_inline)) {
     constexpr bool AGG = decltype(agg_tag)::value;
-    PROBE(0)
+    KP_STAMP(0)
     // ---- 1. x(t): registers -> LDS; x(t + nwaves) in flight (branch-free: values defined under
     // `if (has_next)` become phis whose copies make the compiler wait for the prefetch right after
     // issuing it; on the last step the load reads the first 8 KB of W instead, unused: every wave has read W, it sits in L2,
@@ -729,12 +721,12 @@ __global__ __launch_bounds__(512, 2) void graphconv_fwd_full_kernel(
     static_assert(FD * FD >= FN * FD, "W holds at least one tile's floats");
     issue_tile<true, true>(fx, has_next ? x + (long)hot(tn) * N * D : w, 512, lane);
     wave_sync();
-    PROBE(1)
+    KP_STAMP(1)
 
     // ---- 2. aggregation of graph t_prev (its FW sits in the gather tile, its CSR slice in LDS) ------
     if constexpr (AGG) aggregate_prev();
     wave_sync();
-    PROBE(2)
+    KP_STAMP(2)
 
     // ---- 3. CSR(t): registers -> LDS (the slice of t_prev is dead); CSR(t + nwaves) in flight ---------
     if constexpr (LAY == LAY_PAD4) land_csr(fc, ws.ecv, ws.rp, cv, m_cur.slot, base, cnt, N, lane);
@@ -777,11 +769,11 @@ __global__ __launch_bounds__(512, 2) void graphconv_fwd_full_kernel(
       acc1 = mfma_bf16(fa.p1, WF[1][ks][0], acc1);
       __builtin_amdgcn_sched_barrier(0);   // one k-step of fragments live at a time (register budget)
     });
-    PROBE(3)
+    KP_STAMP(3)
     // ---- 5. FW(t) replaces the gather tile ------------------------------------------------------
     store_c_tiles(ws.b, acc0, acc1, li, hi);
     wave_sync();
-    PROBE(4)
+    KP_STAMP(4)
 
     t_prev = t;
     t = tn;
@@ -793,7 +785,7 @@ __global__ __launch_bounds__(512, 2) void graphconv_fwd_full_kernel(
   step(std::false_type{});                       // first graph: nothing to aggregate yet
   while (has_next) step(std::true_type{});
   aggregate_prev();                              // epilogue: the last graph
-  PROBE_FLUSH(blockIdx.x * wpb + wave)
+  KP_FLUSH(g_probe, blockIdx.x * wpb + wave, 8)
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -846,9 +838,9 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_kernel(
     int Pn = graphs_at(tn < T ? tn : t);
     issue_meta_p(m_nxt, slots_t, gptr_t, tn < T ? tn : t, Pn, N, lane);
 
-    PROBE_DECL
+    KP_DECL(8)
     for (;;) {
-      PROBE(0)
+      KP_STAMP(0)
       // ---- 1. g[t], CSR(A^T) slice: registers -> LDS ------------------------------------------
       const int rows = P * N;
       const int nxe = rows * din, nge = rows * dout, nx4 = rows * din4;
@@ -860,7 +852,7 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_kernel(
       }
       wave_sync();
 
-      PROBE(1)
+      KP_STAMP(1)
       // ---- 2. dFW = A^T @ g -> dFW tile (odd stride), dbias partial ----------------------------
       aggregate_rows(ws.ecv, ws.rp, ws.b, rows, dout, lane, [&](int r, int cl, f32x4 acc) {
         float* d = ws.a + r * BLD + cl * 4;
@@ -868,13 +860,13 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_kernel(
         dbacc += acc;
       });
       wave_sync();
-      PROBE(2)
+      KP_STAMP(2)
 
       // ---- 3. x[t] -> gather tile (g is dead) --------------------------------------------------
       land_tile_g<MODE>(fx, ws.b, FD, nxe, din, lane);
 
       wave_sync();
-      PROBE(3)
+      KP_STAMP(3)
       // ---- 4. dW += x^T @ dFW on the bf16 matrix pipe (exact 3-way split, 6 products) ------------------
       // lane (li, hi): columns li / 32+li of x and dFW over its 16 nodes n = hi*16 + s; bf16 k-step ks
       // takes nodes hi*16 + 8ks .. +7 (the same node set for both operands).  The second wave of the
@@ -917,7 +909,7 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_kernel(
         issue_meta_p(m_nxt, slots_t, gptr_t, tq, Pn, N, lane);
       }
 
-      PROBE(4)
+      KP_STAMP(4)
       // ---- 6. dX = dFW @ W^T (A operand straight from the odd-stride LDS tile) ------------------
       if (dx) {
         f32x16 c0, c1;
@@ -931,7 +923,7 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_kernel(
           c1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, Wt[k * FD + 32 + li], c1, 0, 0, 0);
         }
         // C layout -> LDS (the x tile is dead) -> whole rows as dwordx4
-        PROBE(5)
+        KP_STAMP(5)
         wave_sync();
         store_c_tiles(ws.b, c0, c1, li, hi);
         wave_sync();
@@ -978,7 +970,7 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_kernel(
         }
       }
       wave_sync();
-      PROBE(6)
+      KP_STAMP(6)
 
       if (!has_next) break;
       t = tn;
@@ -987,7 +979,7 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_kernel(
       base = base_n;
       cnt = cnt_n;
     }
-    PROBE_FLUSH(blockIdx.x * wpb + wave)
+    KP_FLUSH(g_probe, blockIdx.x * wpb + wave, 8)
   }
 
   // ---- reduce the workgroup's waves through LDS; one partial per workgroup leaves the chip -----
@@ -1360,7 +1352,7 @@ __global__ __launch_bounds__(256, 1) void graphconv_bwd_planes_kernel(
     };
     int cur = 0;               // plane / CSR buffer of the MFMA graph i; the aggregated graph i+1 uses cur^1
 
-    PROBE_DECL
+    KP_DECL(8)
     // ---- phase A: dW(i) MFMAs  ||  aggregation of graph i+1 -> planes(cur^1)  ||  stores of dX(i-1) ----------
     auto phase_a = [&](auto agg_tag, auto st_tag, int iprev) __attribute__((always_inline)) {
       constexpr bool AGG = decltype(agg_tag)::value, ST = decltype(st_tag)::value;
@@ -1408,13 +1400,13 @@ __global__ __launch_bounds__(256, 1) void graphconv_bwd_planes_kernel(
           if constexpr (AGG) agg_half(std::integral_constant<int, 32 * ks + m>{});
           __builtin_amdgcn_sched_barrier(0);
         });
-        if constexpr (ks == 0) { PROBE(6) }
+        if constexpr (ks == 0) { KP_STAMP(6) }
         if constexpr (AGG) {
           static_for<8>([&](auto rc) __attribute__((always_inline)) {
             agg_half(std::integral_constant<int, 32 * ks + 24 + decltype(rc)::value>{});
           });
         }
-        if constexpr (ks == 0) { PROBE(7) }
+        if constexpr (ks == 0) { KP_STAMP(7) }
       });
       read_fa_at(std::integral_constant<int, 0>{}, cur_off);   // phase B(i), k-step 0: in flight behind the last emits
       if constexpr (AGG) {
@@ -1473,9 +1465,9 @@ __global__ __launch_bounds__(256, 1) void graphconv_bwd_planes_kernel(
                        : "=&v"(m_a.slot), "=&v"(m_a.gp) : "v"(m_b.slot), "v"(m_b.gp));
           issue_meta_l<LAY_PAD4>(m_b, slots_t, gptr_t, gidx(i + 4), N, lane);
         }
-        if constexpr (m == 11) { PROBE(2) }
-        if constexpr (m == 23) { PROBE(3) }
-        if constexpr (m == 35) { PROBE(4) }
+        if constexpr (m == 11) { KP_STAMP(2) }
+        if constexpr (m == 23) { KP_STAMP(3) }
+        if constexpr (m == 35) { KP_STAMP(4) }
         if constexpr (MV && m >= 42) {                    // dFW(i+1), k-step 0: fragments for phase A(i+1)
           constexpr int v = m - 42;
           read_bf(BF0, std::integral_constant<int, 0>{}, std::integral_constant<int, v / 3>{},
@@ -1497,7 +1489,7 @@ __global__ __launch_bounds__(256, 1) void graphconv_bwd_planes_kernel(
       phase_a(Y{}, Nn{}, 0);
       phase_b(Y{}, 0);
       cur ^= 1;
-      PROBE(0)
+      KP_STAMP(0)
       // The peeled first iteration needs more registers than the loop, so the loop's fragment registers come back from
       // scratch in the preheader.  A reload that is still pending at the loop header makes the compiler put its wait THERE,
       // where the back edge shares it -- as vmcnt(0): it drained the prefetch of every iteration.  A use in front of the
@@ -1509,9 +1501,9 @@ __global__ __launch_bounds__(256, 1) void graphconv_bwd_planes_kernel(
                         "+v"(BF0[1][2]), "+v"(FA[0][0]), "+v"(FA[0][1]), "+v"(FA[0][2]));
       for (int i = 1; i < cntw - 1; ++i) {
         phase_a(Y{}, Y{}, i - 1);
-        PROBE(1)
+        KP_STAMP(1)
         phase_b(Y{}, i);
-        PROBE(5)
+        KP_STAMP(5)
         cur ^= 1;
       }
       // last graph i = cntw-1: its dFW is ready, nothing left to aggregate or prefetch
@@ -1521,7 +1513,7 @@ __global__ __launch_bounds__(256, 1) void graphconv_bwd_planes_kernel(
       phase_a(Nn{}, Nn{}, 0);
       phase_b(Nn{}, 0);
     }
-    PROBE_FLUSH(blockIdx.x * BWD_FULL_WPB + wave)
+    KP_FLUSH(g_probe, blockIdx.x * BWD_FULL_WPB + wave, 8)
     {                                           // dX of the last graph
       float* dxp = dx + (long)tl * N * D + li * D + 4 * hi;
 #pragma unroll
@@ -1604,13 +1596,11 @@ __global__ __launch_bounds__(256, 1) void graphconv_bwd_planes_kernel(
 //   * Role A aggregated before it multiplied, and role B multiplied before it aggregated (2b); one role alone reordered: no gain (2c).
 //   * One scheduling scope spanned a role's row groups instead of one scope per group: within noise (2d).
 //   * A pair-local rendezvous with arrival counters in LDS replaced the workgroup barrier: 0.4965-0.4984 against 0.4944-0.4949 (2e).
+//   * KGCN_BWD_PAIRS=0, the one-wave-per-graph planes kernel for every batch: 0.497-0.510 against 0.475-0.485 ms in the same calls.
 // Outside this kernel: the forward's second wave per SIMD started half a step late (same file, item 3: nothing), and the planes
 // kernel ran as k workgroups per CU slot, each with 1 / k of the graphs (profiles/r05_headline_experiments.txt: 3 - 13 % slower).
 // ------------------------------------------------------------------------------------------------
 constexpr int BP_PAIRS = 4;
-#ifndef KGCN_BWD_PAIRS
-#define KGCN_BWD_PAIRS 1        // 0: the one-wave-per-graph planes kernel for every batch
-#endif
 // one element per lane of a dX row (STREAM: see the comment block above)
 template <bool STREAM> __device__ __forceinline__ void st_dx(float* p, float v) {
   if constexpr (STREAM) __builtin_nontemporal_store(v, p);
@@ -1657,7 +1647,7 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_pairs_kernel(
   const int tl = t0 + (cntw - 1) * npairs;                        // its last graph
   const bool whole = cntw == cnt_max;                             // uniform
   auto gidx = [&](int k) { return graph_at(t0, npairs, tl, k); };
-  PROBE_DECL
+  KP_DECL(8)
 
   f32x16 dw00, dw01, dw10, dw11;                                  // role B
   f32x4 dbacc = {0.f, 0.f, 0.f, 0.f};                             // both roles (each aggregates half of a graph's rows)
@@ -1843,19 +1833,19 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_pairs_kernel(
     };
 
     int cur = 0;
-    PROBE(0)
+    KP_STAMP(0)
     for (int i = 0; i < cnt_max - 2; ++i) {                       // graphs i and i + 1 exist for every pair
       dx_of(i, cur);                                              // the multiplications of both roles first
-      PROBE(3)
+      KP_STAMP(3)
       aggregate(MA{}, ecv0 + (cur ^ 1) * ecv_stride, tab0 + (cur ^ 1) * (FN + 4), cur ? 0u : (unsigned)DFWP_BYTES);
-      PROBE(1)
+      KP_STAMP(1)
       while (*agg_flag < i + 1) __builtin_amdgcn_s_sleep(1);      // role B is through with the gather tile (normally long ago)
       wave_sync();
-      PROBE(6)
+      KP_STAMP(6)
       land_and_prefetch(i, cur);
-      PROBE(2)
+      KP_STAMP(2)
       bp_barrier();
-      PROBE(4)
+      KP_STAMP(4)
       cur ^= 1;
     }
     // iteration cnt_max - 2: graph cnt_max - 1 exists for a whole pair only
@@ -1866,7 +1856,7 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_pairs_kernel(
     cur ^= 1;
     // iteration cnt_max - 1
     if (whole) dx_of(cnt_max - 1, cur);
-    PROBE(5)
+    KP_STAMP(5)
   } else {
     // =========================================== role B ===========================================================
     // transpose reads: lane l addresses 4 features (16 nb + 4 a4 ..) of node 16 ks + 8 hi + 4 rd + jj
@@ -1967,26 +1957,26 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_pairs_kernel(
     bp_barrier();                                                 // barrier 1: dFW(0) in planes 0
 
     int cur = 0;
-    PROBE(0)
+    KP_STAMP(0)
     for (int i = 0; i < cnt_max - 1; ++i) {                       // graph i exists for every pair
       if (i < cnt_max - 2 || whole) {                             // uniform; no vector-memory instruction inside
         aggregate(MB{}, ecv0 + (cur ^ 1) * ecv_stride, tab0 + (cur ^ 1) * (FN + 4), cur ? 0u : (unsigned)DFWP_BYTES);
         wave_sync();
         if (lane == 0) *agg_flag = i + 1;
       }
-      PROBE(3)
+      KP_STAMP(3)
       dw_of(cur);                                                 // (matrix pipe) while role A aggregates (vector ALU)
-      PROBE(1)
+      KP_STAMP(1)
       split_and_reload(i + 2);                                    // x(i+1) -> fragments, x(i+2) requested
-      PROBE(2)
+      KP_STAMP(2)
       bp_barrier();
-      PROBE(4)
+      KP_STAMP(4)
       cur ^= 1;
     }
     if (whole) dw_of(cur);                                        // iteration cnt_max - 1
-    PROBE(5)
+    KP_STAMP(5)
   }
-  PROBE_FLUSH(blockIdx.x * 8 + wave)
+  KP_FLUSH(g_probe, blockIdx.x * 8 + wave, 8)
 
   // ---- reduce the workgroup's pairs through LDS; one partial per workgroup ---------------------
   __syncthreads();
@@ -2110,20 +2100,13 @@ static bool bwd_full_route(int n, int din, int dout, int max_nnz, bool with_dx) 
   return with_dx && is_full(n, din, dout) && bwd_planes_lds_bytes(max_nnz) <= (size_t)kLdsBytes && max_nnz < 4096;
 }
 static bool bwd_pairs_route(int T, int n, int din, int dout, int max_nnz, bool with_dx) {
-  return KGCN_BWD_PAIRS != 0 && bwd_full_route(n, din, dout, max_nnz, with_dx) &&
+  return bwd_full_route(n, din, dout, max_nnz, with_dx) &&
          T >= 2 * BP_PAIRS * fused_grid(T, BWD_FULL_WPB);
 }
 
 }  // namespace kgcn
 
 using namespace kgcn;
-
-#ifdef KGCN_PROBE
-extern "C" int kgcn_probe_set(void* buf) {
-  long long* p = static_cast<long long*>(buf);
-  return hipMemcpyToSymbol(HIP_SYMBOL(g_probe), &p, sizeof(p)) == hipSuccess ? 0 : 1;
-}
-#endif
 
 extern "C" int64_t kgcn_compact_values_offset(int64_t nnz) { return ((nnz / 4) + 3) & ~(int64_t)3; }
 

@@ -31,19 +31,11 @@
 //   * KGCN_GEMMH, the f16 two-piece kernels of gemmh.hip per direction: 62-67 us there against 81-110 us here for a
 //     256 x 256 layer of cfg4 (profiles/r04_gemmh_history.txt, profiles/r03_n_cfg4_rocprof.txt).
 #include "dense_kernels.h"
+#include "kgcn_probe.h"
 
 namespace kgcn {
 
-#ifdef KGCN_PROBE   // development: per-workgroup cycle sums per phase (tools/gemm3_probe.py)
-__device__ long long* g3_probe = nullptr;
-#define G3P_DECL long long pt_[4] = {0, 0, 0, 0}; long long pc_ = __builtin_readcyclecounter();
-#define G3P(k) { const long long n_ = __builtin_readcyclecounter(); pt_[k] += n_ - pc_; pc_ = n_; }
-#define G3P_FLUSH if (g3_probe && (threadIdx.x & 63) == 0) { for (int k_ = 0; k_ < 4; ++k_) g3_probe[((long)blockIdx.x * 8 + (threadIdx.x >> 6)) * 4 + k_] = pt_[k_]; }
-#else
-#define G3P_DECL
-#define G3P(k)
-#define G3P_FLUSH
-#endif
+KP_BUFFER(g3_probe, kgcn_g3_probe_set)   // (tools/gemm3_probe.py)
 
 constexpr int G3_BM = 128;            // rows per workgroup tile
 constexpr int G3_BN = 256;            // columns per workgroup
@@ -174,7 +166,7 @@ __device__ __forceinline__ void g3_write(u32x4* table, int tile, int q, int li, 
 // Gathered gradient (bc != nullptr): the incoming gradient of row r is g[r] + bc[(r / bc_n) * bc_ld + .] -- the layer's output was
 // read out by GraphGather (kgcn/layers.py:163-164: d pooled reaches every node row of its graph) and, unless bc_only, also handed
 // on (g): the broadcast never exists in HBM.
-struct G3Dact { long ydiff, pdiff; float c0, c1, c2; const float* bc; long bc_ld; int bc_n, bc_only; };
+// (the operands: G3Dact, dense_kernels.h)
 
 // MT x NT (table variant, 4-wave workgroups): 32 x 32 tiles per wave.  2 x 2: the workgroup covers 64 rows x 256 columns
 // (waves side by side).  When a launch has fewer such tiles than a quarter of the chip's workgroup slots (2 per CU) --
@@ -308,7 +300,7 @@ __global__ __launch_bounds__(256 * MW, 2) void gemm3_fwd_kernel(
   int buf = 0;
   bool done = false;
   float touch = 0.f, sink = 0.f;
-  G3P_DECL
+  KP_DECL(4)
   // one pipeline step: multiply chunk (t0, k0c) out of LDS buffer `buf` || split chunk (t1, k1c) (raw set RS)
   // into buffer buf^1 || request chunk (t2c, k2c) into raw set RL
   auto step = [&](G3Raw& RS, G3Raw& RL) __attribute__((always_inline)) {
@@ -343,7 +335,7 @@ __global__ __launch_bounds__(256 * MW, 2) void gemm3_fwd_kernel(
     const int gnext = (k0c + 1 < nkc) ? 2 * (k0c + 1) : 0;
     G3Coord cs = co;
     cs.rowok = rowok_split;
-    G3P(0)
+    KP_STAMP(0)
     static_for<2>([&](auto ksc) __attribute__((always_inline)) {
       constexpr int ks = decltype(ksc)::value;
       u32x4 A[MT][3], B[NT][3];
@@ -408,7 +400,7 @@ __global__ __launch_bounds__(256 * MW, 2) void gemm3_fwd_kernel(
         }
       });
     });
-    G3P(1)
+    KP_STAMP(1)
     if (k0c + 1 == nkc) {                                // last chunk of the tile: y <- act(acc)
       if (act != KGCN_ACT_NONE) {                        // ONE uniform branch: the plain epilogue stays what it was
 #pragma unroll
@@ -448,9 +440,9 @@ __global__ __launch_bounds__(256 * MW, 2) void gemm3_fwd_kernel(
       }
     }
     done = !have1;
-    G3P(2)
+    KP_STAMP(2)
     __syncthreads();
-    G3P(3)
+    KP_STAMP(3)
     buf ^= 1;
     t0 = t1; k0c = k1c;
     t1 = t2c; k1c = k2c;
@@ -463,7 +455,7 @@ __global__ __launch_bounds__(256 * MW, 2) void gemm3_fwd_kernel(
     if (done) break;
   }
   if (sink == 1.2345e-30f && tid == 4097) y[0] = sink;   // never true: keeps the touch loads alive
-  G3P_FLUSH
+  KP_FLUSH(g3_probe, (long)blockIdx.x * 8 + (threadIdx.x >> 6), 4)
 }
 
 // Table variant, 4-wave workgroups: how a launch is cut into workgroup jobs.  Fewer 64-row tiles than a quarter of the
@@ -528,7 +520,8 @@ int launch_gemm3_fwd(const float* x, long m, int din, long x_ld, const float* w,
 }
 
 // dx = (grad (.) act'(act_out)) @ W^T through the table variant, dpre written on the way (see G3Dact).  Returns -1 when the
-// shape / alignment is not one the fused form takes (the caller then runs the activation backward on its own).
+// shape / alignment is not one the fused form takes (the caller then runs the activation backward on its own).  The shapes of
+// the f16 kernel are routed to gemmh.hip by the caller.
 // pooled_grad != nullptr: gathered gradient (see G3Dact), `grad` may then be nullptr (nothing handed on besides the read-out)
 int launch_gemm3_dx_dact(const float* grad, const float* act_out, float* dpre, long m, int k, long ld, const void* table,
                          float* dx, int n, long dx_ld, int dact, hipStream_t s, const float* pooled_grad, int n_nodes, long pooled_ld) {
@@ -537,21 +530,8 @@ int launch_gemm3_dx_dact(const float* grad, const float* act_out, float* dpre, l
                   dact != KGCN_ACT_NONE && dpre != grad && (grad || pooled_grad) &&
                   (!pooled_grad || (aligned16(pooled_grad) && n_nodes > 0 && pooled_ld % 4 == 0 && pooled_ld >= k));
   if (!ok) return -1;
-  // the f16 kernel where the operands fit it (its W' lives behind the bf16 section of the table), else the bf16 one below
-  const int rc = launch_gemmh_dx_dact(grad, act_out, dpre, m, k, ld, static_cast<const char*>(table) + wtable_bf16_bytes(k, n), dx, n,
-                                      dx_ld, dact, s, pooled_grad, n_nodes, pooled_ld, nullptr);
-  if (rc >= 0) return rc;
-  G3Dact da;
-  const float* base = grad ? grad : act_out;             // the staging threads address everything relative to their x row
-  da.ydiff = act_out - base;
-  da.pdiff = dpre - base;
-  da.bc = pooled_grad;
-  da.bc_ld = pooled_ld;
-  da.bc_n = n_nodes > 0 ? n_nodes : 1;
-  da.bc_only = grad ? 0 : 1;
-  da.c0 = dact == KGCN_ACT_TANH ? 1.f : 0.f;
-  da.c1 = dact == KGCN_ACT_SIGMOID ? 1.f : 0.f;
-  da.c2 = -1.f;
+  const float* base = dact_base(grad, act_out);
+  const G3Dact da = dact_operands(grad, act_out, dpre, pooled_grad, pooled_ld, n_nodes, dact);
   const float* tw = static_cast<const float*>(table);
   if (dact == KGCN_ACT_RELU) g3_table_launch<2>(base, m, k, ld, tw, 0L, 1, nullptr, dx, n, dx_ld, KGCN_ACT_NONE, da, s);
   else g3_table_launch<1>(base, m, k, ld, tw, 0L, 1, nullptr, dx, n, dx_ld, KGCN_ACT_NONE, da, s);
@@ -742,10 +722,3 @@ int launch_gemm3_wgrad(const float* x, long x_ld, const float* dy, long dy_ld, l
 }
 
 }  // namespace kgcn
-
-#ifdef KGCN_PROBE
-extern "C" int kgcn_g3_probe_set(void* buf) {
-  long long* p = static_cast<long long*>(buf);
-  return hipMemcpyToSymbol(HIP_SYMBOL(kgcn::g3_probe), &p, sizeof(p)) == hipSuccess ? 0 : 1;
-}
-#endif

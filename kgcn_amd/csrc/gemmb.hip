@@ -42,8 +42,17 @@
 //   quarters (the 8-byte row writes of 16 lanes cover 32 distinct banks), 16-byte chunks are rotated by the row quad (the
 //   16-lane groups of ds_read_b128 see 16 distinct bank quads).  Everything that depends on the k-step / column tile is an
 //   IMMEDIATE offset on one of two lane bases.
+// Settled and no longer switchable (profiles/r05_gemmb_history.txt unless noted):
+//   * GB_DW_ROWS=1 / 2 / 4, that many of a wave quarter's eight rows staged by its dW wave (which idles ~1,400 cycles at the
+//     barrier): 220.0 / 213.9-219.9 / 218.2-219.9 against 215.8 us with the dX waves staging all of them -- inside the noise.
+//   * GB_DOT_WREG=10 / 9, W' k-steps the dot form keeps in registers: cfg5 1.740-1.744 (12 spilled registers) / 1.714-1.718
+//     against 1.713-1.720 ms with 8.  GB_DOT_KS=5 / 2, the k-step at which it requests its dot operand: 1.716-1.718 /
+//     1.713-1.719 against 1.716-1.720 ms at the head of the stage -- the spills were the cost, not the distance.
+//   * GB_NO_RESCALE (the dW role without its accumulator rescale: wrong results, what the cold block costs) and GB_PIN_ACC (the
+//     accumulators pinned to the accumulator file behind the rescale): development builds, no figure of either was kept.
 #include "dense_kernels.h"
 #include "gemmh.h"
+#include "kgcn_probe.h"
 
 namespace kgcn {
 
@@ -55,35 +64,15 @@ constexpr int GB_R = 32;                      // rows per stage
 #endif
 constexpr int GB_PLANE = 20480;               // bytes of one piece plane
 constexpr int GB_BUF = 2 * GB_PLANE;          // h | l
-// k-steps of W' held in registers; the others live in LDS (below).  The form that adds the read-out's gradient to a row gradient
-// (BC = 1) keeps eight more staging registers alive through the multiplication: four k-steps fewer in registers there.
-#ifndef GB_DOT_WREG
-#define GB_DOT_WREG 8
-#endif
-#ifndef GB_DOT_KS
-#define GB_DOT_KS 0                             // the k-step of a stage at which the dot form requests its dot operand
-#endif
 // W' k-steps a dX wave keeps in registers (the rest wait in LDS).  The dot form gives two more of them to LDS: its sixteen values of
 // the dot operand are requested at the HEAD of a stage -- a whole multiplication ahead of the epilogue that uses them -- and live in
 // the registers that frees (requested at k-step 5 they were ~1,500 cycles ahead of their use, under the loaded HBM latency:
 // 248 us per launch at 200,000 rows against 196 us of the plain form that moves the same bytes, profiles/r05_p_cfg5_rocprof.txt)
-__host__ __device__ constexpr int gb_wreg(bool dot) { return dot ? GB_DOT_WREG : 10; }
+__host__ __device__ constexpr int gb_wreg(bool dot) { return dot ? 8 : 10; }
 __host__ __device__ constexpr size_t gb_lds(bool dot) { return 2 * (size_t)GB_BUF + 2 * GB_R * 4 + 4 * (size_t)(16 - gb_wreg(dot)) * 2 * 1024; }
-#ifndef GB_DW_ROWS
-#define GB_DW_ROWS 0                            // rows (of a wave quarter's eight per stage) staged by the dW wave
-#endif
 constexpr int GB_ZERO_ROW_K = 120;            // row exponent of an all-zero dpre row: x 2^(K - 120) vanishes
 
-#ifdef KGCN_PROBE   // development: per-wave cycle sums per phase of gemmb_kernel (tools/gemmb_probe.py)
-__device__ long long* gb_probe = nullptr;
-#define GBP_DECL long long pt_[8] = {0, 0, 0, 0, 0, 0, 0, 0}; long long pc_ = __builtin_readcyclecounter();
-#define GBP(k) { const long long n_ = __builtin_readcyclecounter(); pt_[k] += n_ - pc_; pc_ = n_; }
-#define GBP_FLUSH if (gb_probe && lane == 0) { for (int k_ = 0; k_ < 8; ++k_) gb_probe[((long)blockIdx.x * 8 + wave) * 8 + k_] = pt_[k_]; }
-#else
-#define GBP_DECL
-#define GBP(k)
-#define GBP_FLUSH
-#endif
+KP_BUFFER(gb_probe, kgcn_gb_probe_set)   // (tools/gemmb_probe.py)
 
 typedef short gb_i16x4 __attribute__((ext_vector_type(4)));
 #define GB_LDS_AS __attribute__((address_space(3)))
@@ -152,7 +141,7 @@ __global__ __launch_bounds__(512, 2) void gemmb_kernel(const float* __restrict__
   const long G = gridDim.x >> 1;
   const unsigned lds0 = gb_lds_off(dsm);
   int* rowk_base = reinterpret_cast<int*>(dsm + 2 * (size_t)GB_BUF);          // [2][32] row exponents
-  GBP_DECL
+  KP_DECL(8)
 
   // ---- staging (dX role): rows 8 w .. 8 w + 7 of a stage; lane = 4 consecutive columns --------------------------------------
   const int c4 = 4 * lane;
@@ -260,9 +249,6 @@ __global__ __launch_bounds__(512, 2) void gemmb_kernel(const float* __restrict__
   };
 
   long t = q0;
-  // Rows 0 .. GB_DX_ROWS-1 of a wave quarter's eight are staged by its dX wave, the rest by its dW wave (same w4): the dX waves are
-  // the stage's critical path, the dW waves waited ~1,400 cycles at its barrier (tools/gemmb_probe.py)
-  constexpr int GB_DX_ROWS = 8 - GB_DW_ROWS;
 
   if (wave < 4) {
     // =============================== dX role ====================================================================
@@ -332,7 +318,7 @@ __global__ __launch_bounds__(512, 2) void gemmb_kernel(const float* __restrict__
         if constexpr (ks < GB_WREG) { wh = Wh[ks]; wl = Wl[ks]; } else { wh = F[ks].wh; wl = F[ks].wl; }
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (ks + 1 < 16) read_p(F[ks + 1], std::integral_constant<int, (ks + 1 < 16 ? ks + 1 : 0)>{});
-        if constexpr (DOT && ks == GB_DOT_KS) {
+        if constexpr (DOT && ks == 0) {
           // (with ten k-steps of W' in registers these sixteen values, requested at the head of the stage, were sixteen more registers
           // alive through the whole multiplication: 18 spilled, reloaded from scratch memory inside the loop -- see gb_wreg)
           const __amdgpu_buffer_rsrc_t rz = gh_rows(dx, st * GB_R, GB_R, m, dx_ld);
@@ -348,10 +334,8 @@ __global__ __launch_bounds__(512, 2) void gemmb_kernel(const float* __restrict__
         // MFMAs form one dependent chain: issued back to back they hold the wave's issue port until the last one starts, and
         // vector work placed behind them overlaps only that one (the first interleaved build: 6,200 cycles for the phase
         // against 1,770 + 3,740 apart) -- the group barriers ask the scheduler for MFMA, 7 vector instructions, MFMA, ...
-        if constexpr (ks / 2 < GB_DX_ROWS) {
-          if constexpr ((ks & 1) == 0) stage_row_a(st_next, std::integral_constant<int, ks / 2>{});
-          else stage_row_b(st_load, buf ^ 1, std::integral_constant<int, ks / 2>{});
-        }
+        if constexpr ((ks & 1) == 0) stage_row_a(st_next, std::integral_constant<int, ks / 2>{});
+        else stage_row_b(st_load, buf ^ 1, std::integral_constant<int, ks / 2>{});
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         __builtin_amdgcn_sched_group_barrier(0x002, 7, 0);
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -360,7 +344,7 @@ __global__ __launch_bounds__(512, 2) void gemmb_kernel(const float* __restrict__
         __builtin_amdgcn_sched_group_barrier(0x002, 12, 0);
       });
       load_bc(st_load);                                      // (the rows staged above used the previous request)
-      GBP(1)
+      KP_STAMP(1)
       __builtin_amdgcn_sched_barrier(0);
       // ---- dX <- 2^-(kr + kc) ax -----------------------------------------------------------------------------------------
       // (dword buffer stores, 2 rows x 128 bytes each.  The transposed form -- dX^T = W' dpre^T, a lane then owns 4 consecutive
@@ -378,12 +362,12 @@ __global__ __launch_bounds__(512, 2) void gemmb_kernel(const float* __restrict__
           }
         }
       }
-      GBP(2)
+      KP_STAMP(2)
     };
 
-    static_for<GB_DX_ROWS>([&](auto ic) __attribute__((always_inline)) { load_ga_row(t, ic); });
+    static_for<8>([&](auto ic) __attribute__((always_inline)) { load_ga_row(t, ic); });
     load_bc(t);
-    static_for<GB_DX_ROWS>([&](auto ic) __attribute__((always_inline)) {          // the first stage: staged without a multiplication to hide in
+    static_for<8>([&](auto ic) __attribute__((always_inline)) {          // the first stage: staged without a multiplication to hide in
       stage_row_a(t, ic);
       stage_row_b(t + G, 0, ic);
     });
@@ -393,7 +377,7 @@ __global__ __launch_bounds__(512, 2) void gemmb_kernel(const float* __restrict__
       const int buf = it & 1;
       compute_dx(t, t + G, t + 2 * G, buf);
       gh_barrier_lds();
-      GBP(5)
+      KP_STAMP(5)
       t += GB_HOT_STEP;
     }
     if constexpr (DOT) {                                      // fixed order: lanes (butterfly), then the four dX waves (below)
@@ -442,7 +426,7 @@ __global__ __launch_bounds__(512, 2) void gemmb_kernel(const float* __restrict__
       return tmx;
     };
 
-    auto compute_dw = [&](long st, long st_next, long st_load, int buf) __attribute__((always_inline)) {
+    auto compute_dw = [&](long st_next, int buf) __attribute__((always_inline)) {
       const int* rowk = rowk_base + GB_R * buf;
       const unsigned boff = (unsigned)(buf * GB_BUF);
       // ---- x'' = x 2^(K - kr[row]) in fragment layout, split once per stage ----------------------------------------------
@@ -463,7 +447,6 @@ __global__ __launch_bounds__(512, 2) void gemmb_kernel(const float* __restrict__
         load_x(st_next);                                      // the next stage's x: in flight behind this stage's arithmetic
         __builtin_amdgcn_sched_barrier(0);
         const float cm = fmaxf(max8(tv[0]), max8(tv[1]));
-#ifndef GB_NO_RESCALE
         if (__builtin_amdgcn_ballot_w64(cm > sx.lim) != 0) {  // wave-uniform, rare after the first stages
           float mxc = fmaxf(cm, __shfl_xor(cm, 32, 64));      // both lane halves hold rows of the same column
           mxc = fmaxf(sx.run, mxc);
@@ -494,12 +477,7 @@ __global__ __launch_bounds__(512, 2) void gemmb_kernel(const float* __restrict__
             }
             __builtin_amdgcn_sched_barrier(0);
           });
-#ifdef GB_PIN_ACC
-#pragma unroll
-          for (int jt = 0; jt < 8; ++jt) asm volatile("" : "+a"(acc[jt]));
-#endif
         }
-#endif
 #pragma unroll
         for (int q = 0; q < 2; ++q)
 #pragma unroll
@@ -509,7 +487,7 @@ __global__ __launch_bounds__(512, 2) void gemmb_kernel(const float* __restrict__
             Xh[q][e] = h; Xl[q][e] = l;
           }
       }
-      GBP(0)
+      KP_STAMP(0)
       // ---- 8 groups of 6 MFMAs over two tiles each ---------------------------------------------------------------------------
       const unsigned tb0 = tbase[0] + boff, tb1 = tbase[1] + boff;
       // fragments of tile (q, jt): requested one tile ahead; th is read twice (l.H first, h.H last)
@@ -542,36 +520,18 @@ __global__ __launch_bounds__(512, 2) void gemmb_kernel(const float* __restrict__
           read_t(F[g0 + 2 < 16 ? g0 + 2 : 16], std::integral_constant<int, (g0 + 2 < 16 ? g0 + 2 : 0)>{});
           read_t(F[g0 + 3 < 16 ? g0 + 3 : 16], std::integral_constant<int, (g0 + 3 < 16 ? g0 + 3 : 0)>{});
         }
-        // this wave's share of the NEXT stage's staging: a row's two parts behind two consecutive groups
-        if constexpr (GB_DW_ROWS > 0) {
-          constexpr int pp = decltype(pc)::value, sp = 8 / (GB_DW_ROWS > 0 ? GB_DW_ROWS : 1), jr = pp / sp;
-          if constexpr (pp % sp == 0) stage_row_a(st_next, std::integral_constant<int, GB_DX_ROWS + jr>{});
-          else if constexpr (pp % sp == 1) stage_row_b(st_load, buf ^ 1, std::integral_constant<int, GB_DX_ROWS + jr>{});
-        }
       });
-      if constexpr (GB_DW_ROWS > 0) load_bc(st_load);
-      GBP(1)
+      KP_STAMP(1)
     };
 
     load_x(t);
-    if constexpr (GB_DW_ROWS > 0) {
-      static_for<GB_DW_ROWS>([&](auto ic) __attribute__((always_inline)) {
-        load_ga_row(t, std::integral_constant<int, GB_DX_ROWS + decltype(ic)::value>{});
-      });
-      load_bc(t);
-      static_for<GB_DW_ROWS>([&](auto ic) __attribute__((always_inline)) {
-        stage_row_a(t, std::integral_constant<int, GB_DX_ROWS + decltype(ic)::value>{});
-        stage_row_b(t + G, 0, std::integral_constant<int, GB_DX_ROWS + decltype(ic)::value>{});
-      });
-      load_bc(t + G);
-    }
     gh_barrier_lds();
     for (int it = 0; it < niter; ++it) {
       const int buf = it & 1;
-      compute_dw(t, t + G, t + 2 * G, buf);
-      GBP(2)
+      compute_dw(t + G, buf);
+      KP_STAMP(2)
       gh_barrier_lds();
-      GBP(5)
+      KP_STAMP(5)
       t += GB_HOT_STEP;
     }
     // ---- the wave's partial dW rows [128 half + 32 w4 .. + 32) x all columns, unscaled; one partial per PAIR --------------------
@@ -588,7 +548,7 @@ __global__ __launch_bounds__(512, 2) void gemmb_kernel(const float* __restrict__
       }
     }
   }
-  GBP_FLUSH
+  KP_FLUSH(gb_probe, (long)blockIdx.x * 8 + wave, 8)
   if constexpr (DOT) {
     __syncthreads();
     if (tid == 0) {
@@ -606,10 +566,16 @@ __global__ __launch_bounds__(512, 2) void gemmb_kernel(const float* __restrict__
     if (tid < kdim) {
       float sum = 0.f;
 #pragma unroll
-      for (int w8 = 0; w8 < (GB_DW_ROWS > 0 ? 8 : 4); ++w8) sum += red[w8 * 256 + tid];
+      for (int w8 = 0; w8 < 4; ++w8) sum += red[w8 * 256 + tid];      // (the dX waves staged every row)
       part_db[q0 * kdim + tid] = sum;
     }
   }
+}
+
+// f(std::integral_constant<int, V>{}) for the V that v equals (false: none): a run-time value as a kernel's template argument
+template <int... Vs, typename F>
+static bool with_const(int v, F&& f) {
+  return ((v == Vs && f(std::integral_constant<int, Vs>{})) || ...);
 }
 
 bool gemmb_ok(const float* g, const float* act_out, const float* x, long m, int din, int dout, long ld, long x_ld, long dx_ld,
@@ -626,21 +592,12 @@ int launch_gemmb(const float* grad, const float* act_out, long m, int din, int d
                  const void* tabh, float* dx, long dx_ld, float* part_dw, float* part_db, int dact, const float* pooled_grad,
                  int n_nodes, long pooled_ld, hipStream_t s, float* dot_part) {
   // dot_part != nullptr: `dx` is READ ([m, din], row stride dx_ld) and <dpre W^T, dx> goes to dot_part[workgroups] (256 floats)
-  const float* base = grad ? grad : act_out;
+  const float* base = dact_base(grad, act_out);
   if (!base || !gemmb_ok(grad, act_out, x, m, din, dout, ld, x_ld, dx_ld, dx) || !tabh || (!grad && !pooled_grad) ||
       (dact != KGCN_ACT_NONE && !act_out) || (dact == KGCN_ACT_NONE && pooled_grad) || (dot_part && (pooled_grad || dact == KGCN_ACT_NONE)) ||
       (pooled_grad && !(aligned16(pooled_grad) && n_nodes >= 8 && pooled_ld % 4 == 0)))     // (eight rows of a wave: <= 2 graphs)
     return -1;
-  GhDact da{};
-  da.ydiff = act_out ? act_out - base : 0;
-  da.bc = pooled_grad;
-  da.bc_ld = pooled_ld;
-  da.bc_n = n_nodes > 0 ? n_nodes : 1;
-  da.bc_only = grad ? 0 : 1;
-  da.c0 = dact == KGCN_ACT_TANH ? 1.f : 0.f;
-  da.c1 = dact == KGCN_ACT_SIGMOID ? 1.f : 0.f;
-  da.c2 = -1.f;
-  da.dot_part = dot_part;
+  const GhDact da{dact_operands(grad, act_out, nullptr, pooled_grad, pooled_ld, n_nodes, dact), dot_part};   // (no dpre: never written)
   const int pairs = kNumCU / 2;
   const long stages = (m + GB_R - 1) / GB_R;
   const int niter = (int)((stages + pairs - 1) / pairs);
@@ -649,31 +606,22 @@ int launch_gemmb(const float* grad, const float* act_out, long m, int din, int d
   const int bc = pooled_grad ? (grad ? 1 : 2) : 0;
   const int dk = dact == KGCN_ACT_NONE ? 0 : (dact == KGCN_ACT_RELU ? 2 : 1);
   int refused = 0;
-  auto go = [&](auto dkc, auto bcc, auto dotc) {
+  const bool ok = with_const<0, 1, 2>(dk, [&](auto dkc) { return with_const<0, 1, 2>(bc, [&](auto bcc) {
+  return with_const<0, 1>(dot_part ? 1 : 0, [&](auto dotc) {
     constexpr int DKc = decltype(dkc)::value, BCc = decltype(bcc)::value;
-    constexpr bool DOTc = decltype(dotc)::value;
-    if ((refused = allow_full_lds<gemmb_kernel<DKc, BCc, DOTc>>(gb_lds(DOTc), "gemmb_kernel"))) return;
-    hipLaunchKernelGGL((gemmb_kernel<DKc, BCc, DOTc>), grid, dim3(512), gb_lds(DOTc), s, base, m, dout, ld, x, din, x_ld, tab, dx, dx_ld,
-                       part_dw, part_db, da, niter);
-  };
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
-  using I2 = std::integral_constant<int, 2>;
-  using F = std::false_type;
-  using Tt = std::true_type;
-  if (dot_part) { if (dk == 1) go(I1{}, I0{}, Tt{}); else go(I2{}, I0{}, Tt{}); }
-  else if (dk == 0) go(I0{}, I0{}, F{});
-  else if (dk == 1) { if (bc == 0) go(I1{}, I0{}, F{}); else if (bc == 1) go(I1{}, I1{}, F{}); else go(I1{}, I2{}, F{}); }
-  else { if (bc == 0) go(I2{}, I0{}, F{}); else if (bc == 1) go(I2{}, I1{}, F{}); else go(I2{}, I2{}, F{}); }
-  if (refused || check_launch("gemmb_kernel")) return -2;
+    constexpr bool DOTc = decltype(dotc)::value != 0;
+    // nine instantiations: the read-out's gradient and the dot form need an activation, and exclude each other (refused above)
+    if constexpr (DKc == 0 ? (BCc != 0 || DOTc) : (BCc != 0 && DOTc)) return false;
+    else {
+      if ((refused = allow_full_lds<gemmb_kernel<DKc, BCc, DOTc>>(gb_lds(DOTc), "gemmb_kernel"))) return true;
+      hipLaunchKernelGGL((gemmb_kernel<DKc, BCc, DOTc>), grid, dim3(512), gb_lds(DOTc), s, base, m, dout, ld, x, din, x_ld, tab, dx,
+                         dx_ld, part_dw, part_db, da, niter);
+      return true;
+    }
+  }); }); });
+  if (!ok) fail("gemmb_kernel: the operands name an instantiation that does not exist");
+  if (!ok || refused || check_launch("gemmb_kernel")) return -2;
   return pairs;
 }
 
 }  // namespace kgcn
-
-#ifdef KGCN_PROBE
-extern "C" int kgcn_gb_probe_set(void* buf) {
-  long long* p = static_cast<long long*>(buf);
-  return hipMemcpyToSymbol(HIP_SYMBOL(kgcn::gb_probe), &p, sizeof(p)) == hipSuccess ? 0 : 1;
-}
-#endif

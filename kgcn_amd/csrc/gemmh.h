@@ -2,7 +2,7 @@
 // exponent and the table layout.  See gemmh.hip for the arithmetic and its error bound.
 #pragma once
 
-#include "kgcn_common.h"
+#include "dense_kernels.h"
 
 namespace kgcn {
 
@@ -79,7 +79,7 @@ __device__ __forceinline__ unsigned wave_umax1(unsigned v) {
 // dot_part != nullptr (backward forms): the product is NOT stored; its inner product with `y` (read as an [m, dout] operand of the
 // same row stride) is accumulated instead, one partial per workgroup -- d epsilon of a GINAggregate whose input needs no gradient
 // (kgcn/layers.py:469: <d out, x>; the d out tensor then never exists in HBM).
-struct GhDact { long ydiff, pdiff; float c0, c1, c2; const float* bc; long bc_ld; int bc_n, bc_only; float* dot_part; };
+struct GhDact : G3Dact { float* dot_part; };
 
 
 // Row-block buffer descriptors (see gemmh_fwd_kernel): loads outside the descriptor return 0, stores outside it are dropped.

@@ -34,39 +34,31 @@
 //     then multiplies the whole tile with its columns: 2 m-tiles x 16 k-steps x 3 products (smallest terms first);
 //   * epilogue: v_ldexp by -(kr + kc), + bias, activation, buffer stores.  The LDS hand-over is s_waitcnt lgkmcnt(0) + s_barrier
 //     (gh_barrier_lds): __syncthreads() would also drain vmcnt -- the next tile's rows and this tile's stores.
-// gemmh_wgrad_kernel<DACT> (dW = x^T dy, db = colsum dy): no LDS.  The batch rows are the contraction index: with lane (li, hi)
-//   reading x[r + 8 hi + j][c + li], j = 0..7, a coalesced dword load IS the MFMA operand layout (wgradx.hip), so a wave
+// gemmh_wgrad_kernel (dW = x^T dpre, db = colsum dpre, dpre = dy (.) act'(yact) formed on the way): no LDS.  The batch rows are the
+//   contraction index: with lane (li, hi) reading x[r + 8 hi + j][c + li], j = 0..7, a coalesced dword load IS the MFMA operand layout (wgradx.hip), so a wave
 //   splits its own operands in registers and runs without barriers.  Scales are per COLUMN here and not known in advance:
 //   every lane keeps the scale of its column(s) and a limit; when a value exceeds the limit (first step, rarely later) the
 //   wave rescales its accumulators (exact) and goes on -- the online form of the row scale above.  One partial dW per
 //   workgroup (written unscaled), fixed-order second stage as everywhere.  Shipped for the fused act' form; the plain weight
 //   gradient takes gemmh_wgradl_kernel below (every value split once, shared through LDS).
-//   Settled and no longer switchable: KGCN_WGRADL=0 (the register-split kernel for the plain gradient too), 88-94 against
-//   75-84 us (profiles/r04_gemmh_history.txt).
+// Settled and no longer switchable (the history stays findable without the code):
+//   * KGCN_WGRADL=0, the register-split kernel for the plain gradient too: 88-94 against 75-84 us (profiles/r04_gemmh_history.txt).
+//   * GH_INTERLEAVE=0, the forward's next tile staged AFTER the multiplication (round-4 form): a vector-ALU phase with the matrix
+//     pipe idle, 0.47 of the HBM floor at 65 / 107 us (profiles/r05_gemmb_history.txt).
+//   * GH_TWO_PHASES=0, the eight waves in lock-step: cfg5 1.749-1.756 against 1.738-1.740 ms, cfg4 1.131-1.133 against 1.119-1.127
+//     (profiles/r05_gemmb_history.txt).
+//   * GH_GROUP_SHIFT=1 / 0, groups that put both waves of a SIMD in the same phase: cfg5 1.757-1.766 / 1.768-1.777 against
+//     1.683-1.689 ms for bit 2 of the wave index (profiles/r05_gemmb_history.txt).
+//   * GH_VARIANT, builds with one part of a kernel compiled out: forward without the y stores 59.3, without the x loads 61.7 of 62-67 us;
+//     gemmh_wgradl without the MFMAs 71.1, without the split 74.4, without the loads 68.6 of 84.1 us -- no single part is the bound
+//     (profiles/r04_gemmh_history.txt).
 #include "dense_kernels.h"
 #include "gemmh.h"
+#include "kgcn_probe.h"
 
 namespace kgcn {
 
-#ifdef KGCN_PROBE   // development: per-wave cycle sums per phase of gemmh_wgradl_kernel (tools/gemmh_probe.py)
-__device__ long long* gh_probe = nullptr;
-#define GHP_DECL long long pt_[8] = {0, 0, 0, 0, 0, 0, 0, 0}; long long pc_ = __builtin_readcyclecounter();
-#define GHP(k) { const long long n_ = __builtin_readcyclecounter(); pt_[k] += n_ - pc_; pc_ = n_; }
-#define GHP_FLUSH if (gh_probe && lane == 0) { for (int k_ = 0; k_ < 8; ++k_) gh_probe[(((long)blockIdx.y * gridDim.x + blockIdx.x) * 8 + wave) * 8 + k_] = pt_[k_]; }
-#else
-#define GHP_DECL
-#define GHP(k)
-#define GHP_FLUSH
-#endif
-#ifndef GH_INTERLEAVE
-#define GH_INTERLEAVE 1          // 0: the next tile staged AFTER the multiplication (rounds 4 form; build/variants A/B)
-#endif
-#ifndef GH_TWO_PHASES
-#define GH_TWO_PHASES 1          // 1: waves 0-3 and 4-7 (one of each per SIMD) run half a tile apart (see the forward kernel's main loop)
-#endif
-#ifndef GH_VARIANT
-#define GH_VARIANT 0             // development (tools/gemmh_variants.sh): 2 no y stores, 3 no x loads (forward); 5 no MFMAs, 6 no
-#endif                           // split, 7 no loads (gemmh_wgradl) -- what each part of the kernels costs
+KP_BUFFER(gh_probe, kgcn_gh_probe_set)   // (tools/gemmh_probe.py, tools/gemmh_fwd_probe.py)
 constexpr int GH_BM = 64;        // rows per tile
 constexpr int GH_KMAX = 256;     // widest x row one lane quad layout covers (64 lanes x 4 columns)
 
@@ -98,12 +90,15 @@ __global__ __launch_bounds__(512, 2) void gemmh_fwd_kernel(const float* __restri
   const int tid = threadIdx.x, lane = tid & 63, li = lane & 31, hi = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // scalar: row indices stay on the SALU
   int* rowk_base = reinterpret_cast<int*>(dsm + 2 * (size_t)GH_PIECES * 16);     // [2 or 3][64] row exponents
-  GHP_DECL                                                 // (development: tools/gemmh_fwd_probe.py)
+  KP_DECL(8)
   const long ntiles = (m + GH_BM - 1) / GH_BM;
   const long G = gridDim.x;
   long t = blockIdx.x;
   if (t >= ntiles) return;                              // uniform for the whole workgroup
   const long ntw = (ntiles - t + G - 1) / G;            // tiles of this workgroup
+  // the plain form with all 16 k-steps stages the next tile row by row between its MFMAs, and its two wave groups run half a
+  // tile apart (TWO PHASES, below); the backward forms and the 8-k-step form stage a tile after the multiplication, in lock-step
+  constexpr bool kInterleave = DK == 0 && NKS == 16, kTwoPhases = kInterleave;
 
   // ---- this wave's slice of W' and its column constants -------------------------------------------------------------
   const int nt32 = gh_nt32(dout), kse = gh_kse(din);
@@ -143,10 +138,7 @@ __global__ __launch_bounds__(512, 2) void gemmh_fwd_kernel(const float* __restri
     }
     const __amdgpu_buffer_rsrc_t rx = gh_rows(x, tt * GH_BM + 8 * wave, 8, m, x_ld);    // tiles past the end: empty, zeros
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      if constexpr (GH_VARIANT == 3) raw[i] = f32x4{1.f + (float)i, 2.f, 3.f, (float)lane};
-      else raw[i] = gh_ld4(rx, voff_x, i * ldx4);
-    }
+    for (int i = 0; i < 8; ++i) raw[i] = gh_ld4(rx, voff_x, i * ldx4);
   };
   auto stage = [&](long tt, int buf) __attribute__((always_inline)) {
     const long r0 = tt * GH_BM + 8 * wave;
@@ -267,7 +259,7 @@ __global__ __launch_bounds__(512, 2) void gemmh_fwd_kernel(const float* __restri
       acc[1] = mfma_f16(A1[2], Bl[ks + 1], acc[1]);
       acc[0] = mfma_f16(A1[0], Bh[ks + 1], acc[0]);
       acc[1] = mfma_f16(A1[2], Bh[ks + 1], acc[1]);
-      if constexpr (DK == 0 && GH_INTERLEAVE != 0 && NKS == 16) {
+      if constexpr (kInterleave) {
         // between these six MFMAs: row ks / 2 of the NEXT tile (already in the registers) -> the other buffer
         stage_row(buf ^ 1, kslot_next, std::integral_constant<int, ks / 2>{});
         // ... and its registers take the same row of the tile after that: a whole multiplication ahead of its use
@@ -286,11 +278,11 @@ __global__ __launch_bounds__(512, 2) void gemmh_fwd_kernel(const float* __restri
         __builtin_amdgcn_sched_group_barrier(0x002, 12, 0);
       }
     });
-    GHP(1)
+    KP_STAMP(1)
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (DK == 0 && GH_INTERLEAVE != 0 && NKS == 16 && GH_TWO_PHASES != 0) {
+    if constexpr (kTwoPhases) {
       gh_barrier_lds();                                  // (the other group's multiplication starts / has ended here: see the main loop)
-      GHP(4)
+      KP_STAMP(4)
     }
     // ---- y <- act(2^-(kr + kc) acc + bias) ---------------------------------------------------------------------------
     const long row0 = tt * GH_BM;
@@ -313,8 +305,7 @@ __global__ __launch_bounds__(512, 2) void gemmh_fwd_kernel(const float* __restri
     if (act == KGCN_ACT_SIGMOID) apply(std::integral_constant<int, KGCN_ACT_SIGMOID>{});
     else if (act == KGCN_ACT_RELU) apply(std::integral_constant<int, KGCN_ACT_RELU>{});
     else if (act == KGCN_ACT_TANH) apply(std::integral_constant<int, KGCN_ACT_TANH>{});
-    if (GH_VARIANT == 2 && acc[0][0] != 1.2345e-30f) return;
-    GHP(2)
+    KP_STAMP(2)
     if (DK != 0 && da.dot_part) {                        // uniform: <product, y operand> instead of the stores
       if (col < dout) {
         const __amdgpu_buffer_rsrc_t rz = gh_rows(y, row0, GH_BM, m, y_ld);   // rows >= m: read as 0
@@ -344,7 +335,7 @@ __global__ __launch_bounds__(512, 2) void gemmh_fwd_kernel(const float* __restri
 
   load_tile(t);
   stage(t, 0);
-  if constexpr (DK == 0 && GH_INTERLEAVE != 0 && NKS == 16) load_tile(t + G);      // the rows the first multiplication stages
+  if constexpr (kInterleave) load_tile(t + G);      // the rows the first multiplication stages
   gh_barrier_lds();
   // No exit between a request and its use (hipcc proves a requested tile dead on an exit path and sinks its loads behind
   // everything in between -- seen in the ISA of an earlier form): the tile after the last one clamps to the last row (cached)
@@ -355,40 +346,36 @@ __global__ __launch_bounds__(512, 2) void gemmh_fwd_kernel(const float* __restri
   // behind its k-steps and one in front of them, and the instances pair up as  X: A has multiplied tile t, B starts to;  Y: B has, A
   // starts on tile t + 1 -- one group's epilogue and loop head run under the other group's MFMAs.  Who stages what and which buffer is
   // free when is unchanged: a group's rows of tile t + 1 are staged during ITS k-steps of tile t, both before either group reads them.
-  constexpr bool kTwoPhases = DK == 0 && GH_INTERLEAVE != 0 && NKS == 16 && GH_TWO_PHASES != 0;
-#ifndef GH_GROUP_SHIFT
-#define GH_GROUP_SHIFT 2
-#endif
-  const bool group_b = ((wave >> GH_GROUP_SHIFT) & 1) != 0;    // uniform; waves w and w + 4 share a SIMD
+  const bool group_b = ((wave >> 2) & 1) != 0;             // uniform; waves w and w + 4 share a SIMD
   int k3 = 0;                                              // the tile's set of row exponents (two phases: one of three)
   for (long i = 0; i < ntw; ++i) {
     const int buf = (int)(i & 1);
     if constexpr (kTwoPhases) {
       if (group_b) gh_barrier_lds();                     // X: group A's k-steps of this tile are done
     }
-    if constexpr (DK == 0 && !(GH_INTERLEAVE != 0 && NKS == 16)) {
+    if constexpr (DK == 0 && !kInterleave) {
       __builtin_amdgcn_sched_barrier(0);
       load_tile(t + G);                                  // on its way from HBM while this tile is multiplied
       __builtin_amdgcn_sched_barrier(0);
     }
-    GHP(0)
+    KP_STAMP(0)
     const int kslot = kTwoPhases ? k3 : buf;
     if constexpr (kTwoPhases) k3 = k3 == 2 ? 0 : k3 + 1;
     compute(t, buf, t + 2 * G, kslot, kTwoPhases ? k3 : (buf ^ 1));
-    GHP(3)
+    KP_STAMP(3)
     if constexpr (DK != 0) load_tile(t + G);             // backward form: gradient and saved output travel together below
-    if constexpr (!(DK == 0 && GH_INTERLEAVE != 0 && NKS == 16)) stage(t + G, buf ^ 1);
+    if constexpr (!kInterleave) stage(t + G, buf ^ 1);
     if constexpr (kTwoPhases) {
       if (!group_b) gh_barrier_lds();                    // Y: group B's k-steps of this tile are done
     } else {
       gh_barrier_lds();
     }
-    GHP(4)
+    KP_STAMP(4)
 #ifndef KGCN_ABL_HOT                          // (development: with it every workgroup re-reads its first tile -- the kernel without HBM traffic)
     t += G;
 #endif
   }
-  GHP_FLUSH
+  KP_FLUSH(gh_probe, ((long)blockIdx.y * gridDim.x + blockIdx.x) * 8 + wave, 8)
   if constexpr (DK != 0) {
     if (da.dot_part) {                                   // uniform.  Fixed order: lanes (butterfly), then the eight waves
 #pragma unroll
@@ -448,22 +435,12 @@ int launch_gemmh_dx_dact(const float* grad, const float* act_out, float* dpre, l
                          float* dot_part) {
   // dot_part != nullptr: `dx` is READ ([m, n], row stride dx_ld) and <product, dx> goes to dot_part[workgroups of the launch]
   // (gemmh_dot_parts(m, n) floats) instead of the product being stored
-  const float* base = grad ? grad : act_out;
+  const float* base = dact_base(grad, act_out);
   if (!(gemmh_fwd_ok(aligned16(base), m, k, ld, n) && (!grad || aligned16(grad)) && aligned16(act_out) && aligned16(dpre) && tabh &&
         dact != KGCN_ACT_NONE && dpre != grad && (grad || pooled_grad) &&
         (!pooled_grad || (aligned16(pooled_grad) && n_nodes > 0 && pooled_ld % 4 == 0))))
     return -1;
-  GhDact da;
-  da.ydiff = act_out - base;
-  da.pdiff = dpre - base;
-  da.bc = pooled_grad;
-  da.bc_ld = pooled_ld;
-  da.bc_n = n_nodes > 0 ? n_nodes : 1;
-  da.bc_only = grad ? 0 : 1;
-  da.c0 = dact == KGCN_ACT_TANH ? 1.f : 0.f;
-  da.c1 = dact == KGCN_ACT_SIGMOID ? 1.f : 0.f;
-  da.c2 = -1.f;
-  da.dot_part = dot_part;
+  const GhDact da{dact_operands(grad, act_out, dpre, pooled_grad, pooled_ld, n_nodes, dact), dot_part};
   if (dact == KGCN_ACT_RELU) return gh_fwd_launch<2>(base, m, k, ld, tabh, nullptr, dx, n, dx_ld, KGCN_ACT_NONE, da, s);
   return gh_fwd_launch<1>(base, m, k, ld, tabh, nullptr, dx, n, dx_ld, KGCN_ACT_NONE, da, s);
 }
@@ -479,7 +456,6 @@ int launch_gemmh_dx_dact(const float* grad, const float* act_out, float* dpre, l
 // (two bits of headroom), accumulators rescaled by the exact powers of two (x columns are accumulator ROWS: their deltas are
 // fetched across lanes).  Partials are written unscaled.
 // ------------------------------------------------------------------------------------------------------------------
-template <bool DACT>
 __global__ __launch_bounds__(512, 2) void gemmh_wgrad_kernel(const float* __restrict__ x, long x_ld, const float* __restrict__ dy,
                                                              long dy_ld, long m, int din, int dout, long steps_per_block,
                                                              float* __restrict__ part_dw, float* __restrict__ part_db,
@@ -502,14 +478,14 @@ __global__ __launch_bounds__(512, 2) void gemmh_wgrad_kernel(const float* __rest
     offa[t] = 4u * (unsigned)(8 * hi * x_ld + (ca < din ? ca : din - 1));      // BYTE offsets: scalar base + 32-bit lane offset
     offb[t] = 4u * (unsigned)(8 * hi * dy_ld + (cb < dout ? cb : dout - 1));    // is an addressing mode of global_load
   }
-  struct Raw { float a[2][8], b[2][8], y[DACT ? 2 : 1][DACT ? 8 : 1]; };
+  struct Raw { float a[2][8], b[2][8], y[2][8]; };
   auto at = [](const float* base, unsigned byte_off) __attribute__((always_inline)) {
     return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
   };
   auto load = [&](long s, Raw& r) __attribute__((always_inline)) {
     const float* xs = x + s * 16 * x_ld;
     const float* gs = dy + s * 16 * dy_ld;
-    const float* ys = DACT ? yact + s * 16 * dy_ld : nullptr;
+    const float* ys = yact + s * 16 * dy_ld;
     // uniform row pointers + ONE per-lane byte offset per operand block.  (hipcc still spends a 64-bit vector add per load on
     // them -- loop strength reduction makes per-lane pointer inductions out of `uniform base + lane offset`; buffer loads with a
     // scalar row offset, as the forward kernel uses them, have no vector address arithmetic at all but cost 75 spilled
@@ -518,12 +494,12 @@ __global__ __launch_bounds__(512, 2) void gemmh_wgrad_kernel(const float* __rest
     for (int j = 0; j < 8; ++j) {
       const float* xr = xs + j * x_ld;
       const float* gr = gs + j * dy_ld;
-      const float* yr = DACT ? ys + j * dy_ld : nullptr;
+      const float* yr = ys + j * dy_ld;
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         r.a[t][j] = at(xr, offa[t]);
         r.b[t][j] = at(gr, offb[t]);
-        if constexpr (DACT) r.y[t][j] = at(yr, offb[t]);
+        r.y[t][j] = at(yr, offb[t]);
       }
     }
   };
@@ -536,7 +512,7 @@ __global__ __launch_bounds__(512, 2) void gemmh_wgrad_kernel(const float* __rest
       for (int t = 0; t < 2; ++t) {
         r.a[t][j] = x[row * x_ld + (offa[t] / 4u - (unsigned)(8 * hi * x_ld))];
         r.b[t][j] = dy[row * dy_ld + (offb[t] / 4u - (unsigned)(8 * hi * dy_ld))];
-        if constexpr (DACT) r.y[t][j] = yact[row * dy_ld + (offb[t] / 4u - (unsigned)(8 * hi * dy_ld))];
+        r.y[t][j] = yact[row * dy_ld + (offb[t] / 4u - (unsigned)(8 * hi * dy_ld))];
       }
     }
   };
@@ -580,26 +556,21 @@ __global__ __launch_bounds__(512, 2) void gemmh_wgrad_kernel(const float* __rest
   };
   auto mma = [&](long s, Raw& r, auto tailc) __attribute__((always_inline)) {
     constexpr bool TAIL = decltype(tailc)::value;
-    if constexpr (DACT || TAIL) {
 #pragma unroll
-      for (int t = 0; t < 2; ++t)
+    for (int t = 0; t < 2; ++t)
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          float g = r.b[t][j];
-          if constexpr (DACT) {
-            const float a = r.y[t][j];
-            float d = __builtin_fmaf(__builtin_fmaf(c2, a, c1), a, c0);
-            d = relu ? (a > 0.f ? 1.f : 0.f) : d;
-            g *= d;
-          }
-          if constexpr (TAIL) {
-            const bool ok = s * 16 + 8 * hi + j < m;
-            g = ok ? g : 0.f;
-            r.a[t][j] = ok ? r.a[t][j] : 0.f;
-          }
-          r.b[t][j] = g;
+      for (int j = 0; j < 8; ++j) {
+        const float a = r.y[t][j];
+        float d = __builtin_fmaf(__builtin_fmaf(c2, a, c1), a, c0);
+        d = relu ? (a > 0.f ? 1.f : 0.f) : d;
+        float g = r.b[t][j] * d;
+        if constexpr (TAIL) {
+          const bool ok = s * 16 + 8 * hi + j < m;
+          g = ok ? g : 0.f;
+          r.a[t][j] = ok ? r.a[t][j] : 0.f;
         }
-    }
+        r.b[t][j] = g;
+      }
     float ma[2], mb[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
@@ -741,13 +712,6 @@ __global__ __launch_bounds__(512, 2) void gemmh_wgradl_kernel(const float* __res
     return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + byte_off);
   };
   auto load = [&](long st, Raw& r) __attribute__((always_inline)) {
-    if constexpr (GH_VARIANT == 7) {
-#pragma unroll
-      for (int q = 0; q < 2; ++q)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) { r.y[q][j] = 1e-3f * (float)(lane + j + (int)st); r.a[q][j] = 0.5f + (float)j; }
-      return;
-    }
     // (plain pointers: uniform row pointer + one per-lane byte offset.  Buffer loads with scalar row offsets, as the forward
     // kernel uses them, cost this kernel 185 spilled registers -- as they did the register-split kernel above)
     const float* gs = dy + st * 32 * dy_ld;
@@ -809,7 +773,6 @@ __global__ __launch_bounds__(512, 2) void gemmh_wgradl_kernel(const float* __res
     }
   };
   auto emit = [&](const float (&v)[8], int k, int tile, int q, int buf) __attribute__((always_inline)) {
-    if constexpr (GH_VARIANT == 6) { if (v[0] != 1.2345e-30f) return; }
     u32x4 h, l;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -881,7 +844,6 @@ __global__ __launch_bounds__(512, 2) void gemmh_wgradl_kernel(const float* __res
   };
   // the twelve MFMAs of a k-step in two halves (smallest terms first)
   auto mma_lo = [&](const Frags& f) __attribute__((always_inline)) {
-    if constexpr (GH_VARIANT == 5) { acc[0][0][0] += __uint_as_float(f.al[0][0] ^ f.bh[0][0] ^ f.ah[1][1] ^ f.bl[1][1]); return; }
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -890,7 +852,6 @@ __global__ __launch_bounds__(512, 2) void gemmh_wgradl_kernel(const float* __res
     for (int nt = 0; nt < 2; ++nt) acc[0][nt] = mfma_f16(f.ah[0], f.bl[nt], acc[0][nt]);
   };
   auto mma_hi = [&](const Frags& f) __attribute__((always_inline)) {
-    if constexpr (GH_VARIANT == 5) { acc[1][1][0] += __uint_as_float(f.ah[0][2] ^ f.bh[1][3] ^ f.al[1][2] ^ f.bl[0][3]); return; }
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) acc[1][nt] = mfma_f16(f.ah[1], f.bl[nt], acc[1][nt]);
 #pragma unroll
@@ -906,7 +867,7 @@ __global__ __launch_bounds__(512, 2) void gemmh_wgradl_kernel(const float* __res
   };
 
   int buf = 0;
-  GHP_DECL
+  KP_DECL(8)
   if (s0 < s1) {
     const long sl = s1 - 1;                              // requests past the range repeat its last stage (valid, unused)
     Raw r0, r1, r2;
@@ -923,35 +884,35 @@ __global__ __launch_bounds__(512, 2) void gemmh_wgradl_kernel(const float* __res
     // the other both waves of a SIMD collided on each pipe in turn (75 us at 117,888 rows; WAIT_ANY 42 %).
     auto iter_fast = [&](long s, Raw& rnext, Raw& rfree) __attribute__((always_inline)) {
       __builtin_amdgcn_sched_barrier(0);
-      GHP(7)                                              // (loop overhead / what the previous iteration left)
+      KP_STAMP(7)                                         // (loop overhead / what the previous iteration left)
       load(s + 3 < sl ? s + 3 : sl, rfree);
       __builtin_amdgcn_sched_barrier(0);
-      GHP(0)
+      KP_STAMP(0)
       split_check(rnext);
-      GHP(1)
+      KP_STAMP(1)
       mult_check(buf);
       Frags f;
       read_frags(f, 0, buf);
       __builtin_amdgcn_sched_barrier(0);
-      GHP(2)
+      KP_STAMP(2)
       mma_lo(f);
       emit_y(rnext, 0, buf ^ 1);
       __builtin_amdgcn_sched_barrier(0);
       mma_hi(f);
       emit_y(rnext, 1, buf ^ 1);
       __builtin_amdgcn_sched_barrier(0);
-      GHP(3)
+      KP_STAMP(3)
       read_frags(f, 1, buf);
       __builtin_amdgcn_sched_barrier(0);
-      GHP(4)
+      KP_STAMP(4)
       mma_lo(f);
       emit_x(rnext, 0, buf ^ 1);
       __builtin_amdgcn_sched_barrier(0);
       mma_hi(f);
       emit_x(rnext, 1, buf ^ 1);
-      GHP(5)
+      KP_STAMP(5)
       gh_barrier_lds();
-      GHP(6)
+      KP_STAMP(6)
       buf ^= 1;
     };
     auto iter = [&](long s, Raw& rnext, Raw& rfree) __attribute__((always_inline)) {
@@ -990,7 +951,7 @@ __global__ __launch_bounds__(512, 2) void gemmh_wgradl_kernel(const float* __res
     multiply(buf);
   }
 
-  GHP_FLUSH
+  KP_FLUSH(gh_probe, ((long)blockIdx.y * gridDim.x + blockIdx.x) * 8 + wave, 8)
   // ---- the workgroup's partial dW block, unscaled -----------------------------------------------------------------
   float* pw = part_dw + (long)blockIdx.x * din * dout;
 #pragma unroll
@@ -1019,7 +980,7 @@ bool gemmh_wgrad_ok(int din, int dout, long m) { return din > 96 && dout > 128 &
 int launch_gemmh_wgrad(const float* x, long x_ld, const float* dy, long dy_ld, long m, int din, int dout, float* part_dw,
                        float* part_db, int nblocks, hipStream_t s, const float* yact, int act) {
   const dim3 grid((unsigned)nblocks, (unsigned)((din + 127) / 128), (unsigned)((dout + 255) / 256));
-  if (!(yact && act != KGCN_ACT_NONE)) {
+  if (!(yact && act != KGCN_ACT_NONE)) {                 // the plain gradient
     if (int rc = allow_full_lds<gemmh_wgradl_kernel>(0, "gemmh_wgradl_kernel")) return rc;
     const long nfull = m / 32, spb = (nfull + nblocks - 1) / nblocks;
     hipLaunchKernelGGL(gemmh_wgradl_kernel, grid, dim3(512), GWL_LDS, s, x, x_ld, dy, dy_ld, m, din, dout, spb, part_dw, part_db);
@@ -1027,20 +988,9 @@ int launch_gemmh_wgrad(const float* x, long x_ld, const float* dy, long dy_ld, l
   }
   const long nsteps = (m + 15) / 16, spb = (nsteps + nblocks - 1) / nblocks;
   const float c0 = act == KGCN_ACT_TANH ? 1.f : 0.f, c1 = act == KGCN_ACT_SIGMOID ? 1.f : 0.f, c2 = -1.f;
-  if (yact && act != KGCN_ACT_NONE)
-    hipLaunchKernelGGL(gemmh_wgrad_kernel<true>, grid, dim3(512), 0, s, x, x_ld, dy, dy_ld, m, din, dout, spb, part_dw, part_db,
-                       yact, c0, c1, c2, act == KGCN_ACT_RELU ? 1 : 0);
-  else  // not reached since the plain gradient always takes gemmh_wgradl_kernel; kept so that the code object is unchanged
-    hipLaunchKernelGGL(gemmh_wgrad_kernel<false>, grid, dim3(512), 0, s, x, x_ld, dy, dy_ld, m, din, dout, spb, part_dw, part_db,
-                       nullptr, 0.f, 0.f, 0.f, 0);
+  hipLaunchKernelGGL(gemmh_wgrad_kernel, grid, dim3(512), 0, s, x, x_ld, dy, dy_ld, m, din, dout, spb, part_dw, part_db, yact, c0,
+                     c1, c2, act == KGCN_ACT_RELU ? 1 : 0);
   return check_launch("gemmh_wgrad_kernel");
 }
 
 }  // namespace kgcn
-
-#ifdef KGCN_PROBE
-extern "C" int kgcn_gh_probe_set(void* buf) {
-  long long* p = static_cast<long long*>(buf);
-  return hipMemcpyToSymbol(HIP_SYMBOL(kgcn::gh_probe), &p, sizeof(p)) == hipSuccess ? 0 : 1;
-}
-#endif

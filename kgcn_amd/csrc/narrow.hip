@@ -12,6 +12,9 @@
 // the same way: accumulators -> LDS tile [32 x dout] -> flat dwordx4 stores.
 // The contraction itself stays on v_mfma_f32_32x32x2_f32 (exact fp32 products): <= 2 x 32 MFMAs of 64 cycles per 32-row
 // tile is below the tile's HBM time.
+// Settled and no longer switchable (development builds; no figure of either was kept in profiles/):
+//   * NR_WPE4, narrow_fwd_kernel held to four waves per SIMD (128 registers) with two workgroups per CU.
+//   * NR_ABL_NOMFMA, the forward without its MFMAs (the movement alone).
 #include "dense_kernels.h"
 
 namespace kgcn {
@@ -61,9 +64,6 @@ __device__ __forceinline__ void nr_handoff() {   // intra-wave LDS hand-off: com
 // One workgroup (8 waves) per CU and launch, every wave owns whole 32-row tiles; the weight panel [din x 64] (zero
 // padded) stays in LDS.  MFMA k index of lane half hi, step s: k = hi * kh + s with kh = ceil(din / 2) -- both halves
 // walk contiguous floats of their row.
-#ifdef NR_WPE4
-__attribute__((amdgpu_waves_per_eu(4, 4)))
-#endif
 __global__ __launch_bounds__(512) void narrow_fwd_kernel(
     const float* __restrict__ x, long m, int din, const float* __restrict__ w, long w_ld, int trans_w,
     const float* __restrict__ bias, float* __restrict__ y, int dout, int act, int tile_floats) {
@@ -102,7 +102,6 @@ __global__ __launch_bounds__(512) void narrow_fwd_kernel(
     f32x16 acc0, acc1;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { acc0[r] = b0; acc1[r] = b1; }
-#ifndef NR_ABL_NOMFMA
     if (two) {
       for (int s = 0; s < kh; ++s) {
         float a = xa[s];
@@ -117,7 +116,6 @@ __global__ __launch_bounds__(512) void narrow_fwd_kernel(
         acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a, wb[s * 64], acc0, 0, 0, 0);
       }
     }
-#endif
     nr_handoff();
     if (act != KGCN_ACT_NONE) {                     // one uniform branch around the whole activation
 #pragma unroll
@@ -256,11 +254,7 @@ int launch_narrow_fwd(const float* x, long m, int din, const float* w, long w_ld
   if (int rc = allow_full_lds<narrow_fwd_kernel>(0, "narrow_fwd_kernel")) return rc;
   const long tiles = (m + 31) / 32;
   long blocks = (tiles + NR_WAVES - 1) / NR_WAVES;
-#ifdef NR_WPE4
-  if (blocks > 2 * kNumCU) blocks = 2 * kNumCU;
-#else
   if (blocks > kNumCU) blocks = kNumCU;              // 256 VGPRs: one workgroup per CU
-#endif
   hipLaunchKernelGGL(narrow_fwd_kernel, dim3((unsigned)blocks), dim3(64 * NR_WAVES), lds, s, x, m, din, w, w_ld,
                      trans_w, bias, y, dout, act, tile_floats);
   return check_launch("narrow_fwd_kernel");
