@@ -86,7 +86,9 @@ extern "C" {
  * The smooth attribution methods added entry points only (version still 2): kgcn_ig_perturb_rows_f32, kgcn_ig_perturb_values_f32,
  * kgcn_seq_convpool_perturbed_fwd_f32.
  * Cross-validation added entry points only (version still 2): kgcn_multitask_softmax2_ce_f32, kgcn_binary_metrics_f32
- * (+ kgcn_binary_metrics_workspace_bytes). */
+ * (+ kgcn_binary_metrics_workspace_bytes).
+ * The vector-modality models and regression added entry points only (version still 2): kgcn_dense_bn_short_fwd_f32 / _bwd_f32 /
+ * _dx_f32 (+ kgcn_dense_bn_short_supported), kgcn_act_cols_fwd_f32 / _bwd_f32, kgcn_masked_sqerr_f32, kgcn_regression_sums_f64. */
 #define KGCN_HIP_ABI_VERSION 2
 
 /* Column index of the padding entries of a row-padded batch (see row_pad): they carry value 0 and
@@ -1069,6 +1071,53 @@ int kgcn_multitask_softmax2_ce_f32(const float* logits, const float* labels, con
 int64_t kgcn_binary_metrics_workspace_bytes(int64_t n, int32_t tasks);
 int kgcn_binary_metrics_f32(const float* score, int64_t score_ld, const float* label, const float* mask, int64_t n, int32_t tasks,
                             float threshold, int64_t* counts, double* ap, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* -- vector-modality models and regression (example_model/model_multimodal_vec.py, model_multimodal_regression.py;
+ * csrc/shortm.hip, csrc/regress.hip)
+ * Dense + BatchNormalization in learning phase 0 + activation for short batches, x [rows, k] with row stride x_ld:
+ *   pre = x w + bias,  y = act(s (pre - mean) + beta),  s = gamma / sqrt(var + eps);   gamma NULL (then beta, mean, var NULL too):
+ *   y = act(pre).  bias may be NULL.  y has row stride y_ld (a column block of a wider buffer).
+ * One workgroup owns 16 output columns and every row: the forward is one launch; the backward is one launch that writes
+ * dw [k, n], dbias, dgamma, dbeta [n] complete (each may be NULL) and dpre [rows, n] = d loss / d pre (NULL when no dX follows)
+ * from x, the forward's y, dy (row stride dy_ld) and -- with gamma -- the pre-activations `pre` [rows, n] the forward stashed
+ * (its `pre` argument; NULL there when no backward follows).  kgcn_dense_bn_short_dx_f32: dx [rows, k] (row stride dx_ld) =
+ * dpre w^T.  Plain fp32 FMAs, fixed summation order, no float atomics, no alignment requirement.  kgcn_dense_bn_short_supported
+ * answers the shape question on the host (1 / 0); every call outside it is refused before any launch. */
+#define KGCN_DENSE_BN_SHORT_MAX_ROWS 256
+#define KGCN_DENSE_BN_SHORT_MAX_K 8192
+#define KGCN_DENSE_BN_SHORT_MAX_N 1024
+int kgcn_dense_bn_short_supported(int64_t rows, int64_t k, int64_t n);
+int kgcn_dense_bn_short_fwd_f32(const float* x, int64_t x_ld, int64_t rows, int32_t k, const float* w, const float* bias, int32_t n,
+                                const float* gamma, const float* beta, const float* mean, const float* var, float eps, int32_t act,
+                                float* y, int64_t y_ld, float* pre, void* stream);
+int kgcn_dense_bn_short_bwd_f32(const float* x, int64_t x_ld, int64_t rows, int32_t k, int32_t n, const float* y, int64_t y_ld,
+                                const float* dy, int64_t dy_ld, const float* pre, const float* gamma, const float* mean,
+                                const float* var, float eps, int32_t act, float* dw, float* dbias, float* dgamma, float* dbeta,
+                                float* dpre, void* stream);
+int kgcn_dense_bn_short_dx_f32(const float* dpre, int64_t rows, int32_t n, const float* w, int32_t k, float* dx, int64_t dx_ld,
+                               void* stream);
+/* y[b, 0:n] = act(x[b, 0:n]) between column blocks with row strides x_ld / y_ld, and its backward dx = g act'(y). */
+int kgcn_act_cols_fwd_f32(const float* x, int64_t x_ld, int64_t rows, int32_t n, int32_t act, float* y, int64_t y_ld, void* stream);
+int kgcn_act_cols_bwd_f32(const float* y, int64_t y_ld, const float* g, int64_t g_ld, int64_t rows, int32_t n, int32_t act, float* dx,
+                          int64_t dx_ld, void* stream);
+
+/* Masked squared error of model_multimodal_regression.py:94-101: pred, labels, mask_label [batch, tasks] contiguous.
+ *   stats [2 tasks + 2] = error_sum [tasks] | count [tasks] | cost_sum | cost_opt with error_sum[t] = sum_b mask_label (labels -
+ *         pred)^2, count[t] = sum_b mask_label, cost_sum = sum_t error_sum[t], cost_opt = cost_sum / (batch tasks)
+ *   dpred [batch, tasks] = d cost_sum / d pred (exactly 0 where mask_label == 0)
+ *   accum NULL, or a [2 tasks + 1] block error_sum | count | cost_sum that the call adds its values to in place.
+ * Fixed summation order, no float atomics; asynchronous and capturable. */
+#define KGCN_SQERR_MAX_BATCH (1 << 24)
+#define KGCN_SQERR_MAX_TASKS 65535
+int kgcn_masked_sqerr_f32(const float* pred, const float* labels, const float* mask_label, int64_t batch, int32_t tasks, float* dpred,
+                          float* stats, float* accum, void* stream);
+/* The sums behind r2 / mse / gmfe (gcn.py:204-208) per task over n evaluated rows: pred and label [n, tasks] with row strides
+ * pred_ld / label_ld, mask NULL or [n, tasks] contiguous (a row counts where mask != 0).  sums [tasks, 6] fp64 =
+ *   n | sum y | sum (y - mean y)^2 | sum (y - p)^2 | sum log(y / p) over the rows with 0 < y / p < inf | the count of the other rows
+ * two passes in fp64, fixed order, no atomics.  Asynchronous. */
+#define KGCN_REGRESSION_SUMS_MAX_ROWS (1ll << 31)
+int kgcn_regression_sums_f64(const float* pred, int64_t pred_ld, const float* label, int64_t label_ld, const float* mask, int64_t n,
+                             int32_t tasks, double* sums, void* stream);
 
 #ifdef __cplusplus
 }

@@ -346,6 +346,20 @@ SIGNATURES = {
     "kgcn_binary_metrics_workspace_bytes": (c_i64, [c_i64, c_i32]),
     "kgcn_binary_metrics_f32": (ctypes.c_int, [c_f32p, c_i64, c_f32p, c_f32p, c_i64, c_i32, ctypes.c_float, ctypes.c_void_p,
                                                ctypes.c_void_p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
+    # vector-modality models and regression: short-batch Dense + BN + activation, regression head (csrc/shortm.hip, regress.hip)
+    "kgcn_dense_bn_short_supported": (ctypes.c_int, [c_i64, c_i64, c_i64]),
+    "kgcn_dense_bn_short_fwd_f32": (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64, c_i32, c_f32p, c_f32p, c_i32, c_f32p, c_f32p, c_f32p,
+                                                   c_f32p, ctypes.c_float, c_i32, ctypes.c_void_p, c_i64, c_f32p, ctypes.c_void_p]),
+    "kgcn_dense_bn_short_bwd_f32": (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64, c_i32, c_i32, ctypes.c_void_p, c_i64,
+                                                   ctypes.c_void_p, c_i64, c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_float, c_i32,
+                                                   c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p]),
+    "kgcn_dense_bn_short_dx_f32": (ctypes.c_int, [c_f32p, c_i64, c_i32, c_f32p, c_i32, c_f32p, c_i64, ctypes.c_void_p]),
+    "kgcn_act_cols_fwd_f32": (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64, c_i32, c_i32, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
+    "kgcn_act_cols_bwd_f32": (ctypes.c_int, [ctypes.c_void_p, c_i64, ctypes.c_void_p, c_i64, c_i64, c_i32, c_i32, ctypes.c_void_p,
+                                             c_i64, ctypes.c_void_p]),
+    "kgcn_masked_sqerr_f32": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_i64, c_i32, c_f32p, c_f32p, c_f32p, ctypes.c_void_p]),
+    "kgcn_regression_sums_f64": (ctypes.c_int, [ctypes.c_void_p, c_i64, ctypes.c_void_p, c_i64, c_f32p, c_i64, c_i32, ctypes.c_void_p,
+                                                ctypes.c_void_p]),
     "kgcn_graph_gather_bwd_ld_f32": (ctypes.c_int, [c_f32p, c_i64, c_i64, c_i32, c_i32, c_f32p, ctypes.c_void_p]),
     "kgcn_graph_gather_bwd_add_f32": (ctypes.c_int, [c_f32p, c_f32p, c_i64, c_i32, c_i32, c_f32p, ctypes.c_void_p]),
     "kgcn_dot_workspace_bytes": (c_i64, [c_i64]),

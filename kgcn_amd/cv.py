@@ -103,6 +103,24 @@ def metrics_from_counts(counts, ap):
     return el
 
 
+def regression_metrics_from_sums(sums):
+    """One task's dict of compute_metrics under config["task"] == "regression" / "regression_gmfe" (gcn.py:204-208) from a row of
+    ops.regression_metrics (n, sum y, ss_tot = sum (y - mean y)^2, ss_res = sum (y - p)^2, sum log(y / p), n_bad_ratio), in fp64:
+      r2   sklearn.metrics.r2_score: 1 - ss_res / ss_tot; a constant target (ss_tot = 0) gives 1.0 for a perfect prediction,
+           else 0.0 (force_finite); fewer than two rows give NaN
+      mse  sklearn.metrics.mean_squared_error: ss_res / n (NaN without rows)
+      gmfe exp(mean(log(y / p))); NaN when any ratio is <= 0 or not finite (numpy's log of a negative ratio)."""
+    n, _, ss_tot, ss_res, slog, bad = (float(v) for v in sums[:6])
+    if n < 2:
+        r2 = float("nan")
+    elif ss_tot != 0.0:
+        r2 = 1.0 - ss_res / ss_tot
+    else:
+        r2 = 1.0 if ss_res == 0.0 else 0.0
+    return {"r2": r2, "mse": ss_res / n if n else float("nan"),
+            "gmfe": float(np.exp(slog / n)) if n and not bad else float("nan")}
+
+
 def save_result_cv(result_cv, path):
     """cv.json of gcn.py:492-500: a list over folds of a list over tasks of the metric dicts (NaN is written as json.dump
     writes it, `sup` as null)."""
@@ -127,15 +145,22 @@ def auc_table(result_cv, key="auc"):
 # ---- the fit --------------------------------------------------------------------------------------------------------------------
 DEFAULT_CONFIG = {"batch_size": 50, "learning_rate": 1e-3, "patience": 3, "k-fold_num": 5, "validation_data_rate": 0.2,
                   "epoch": 50, "shuffle_data": True, "stratified_kfold": False, "seed": 0, "metrics_mask": False,
-                  "threshold": 0.5, "save_result_cv": None, "save_info_cv": None, "save_model_path": None}
+                  "threshold": 0.5, "save_result_cv": None, "save_info_cv": None, "save_model_path": None, "task": "classification"}
+TASKS = ("classification", "regression")
 
 
 class CrossValidator:
     """The captured steps and device state that all folds share.  model_factory() -> a fresh network taking
     (features, adjacency) and returning logits [B, 2, T] (models.CPIMultitaskNet); dataset: data_util.DeviceGraphDataset;
-    labels / mask_label: [G, T] arrays."""
+    labels / mask_label: [G, T] arrays.
+    forward_tables: {keyword: [G, ...] array or device tensor} of further per-graph inputs of the network (the vector modality,
+    data_util.vector_table: {"vectors": table}); each is registered with the static batch and handed to every forward call --
+    warm-up, captured training step, captured evaluation step, reset -- under its keyword.
+    config["task"] = "regression" (gcn.py:204-206, kgcn/core.py:184-186): the network returns predictions [B, T]
+    (models.MultimodalRegressionGCN), the loss is ops.masked_squared_error, the epoch summaries carry mse = error_sum / count in
+    place of the accuracy, and a test fold's metric dicts are regression_metrics_from_sums' {"r2", "mse", "gmfe"}."""
 
-    def __init__(self, model_factory, dataset, labels, mask_label, config=None):
+    def __init__(self, model_factory, dataset, labels, mask_label, config=None, forward_tables=None):
         import torch
         from . import ops, train
         self.config = dict(DEFAULT_CONFIG)
@@ -144,6 +169,9 @@ class CrossValidator:
         if unknown:
             raise ValueError("unknown train_cv settings: %s" % sorted(unknown))
         kfold_indices(2, 2, stratified=self.config["stratified_kfold"])                 # refuses what is not implemented, early
+        if self.config["task"] not in TASKS:
+            raise ValueError("config['task'] must be one of %s, got %r" % (TASKS, self.config["task"]))
+        self.regression = regression = self.config["task"] == "regression"
         # a dead hipGraph that only the cycle collector can free must go NOW: destroying one while a stream captures is an error
         # that ends the process, and torch.cuda.graph() no longer collects on entry
         import gc
@@ -160,24 +188,34 @@ class CrossValidator:
         self.batch = dataset.static_batch(B)
         self.lab = self.batch.add_table(self.labels)
         self.ml = self.batch.add_table(self.mask_label)
+        self.kw = {}
+        for name, table in (forward_tables or {}).items():
+            t = table if torch.is_tensor(table) else torch.as_tensor(np.ascontiguousarray(table, dtype=np.float32))
+            if t.shape[0] != G:
+                raise ValueError("forward table %r has %d rows for %d graphs" % (name, t.shape[0], G))
+            self.kw[name] = self.batch.add_table(t.to(dev))
         self.batch.load(np.arange(min(B, G)))
         torch.manual_seed(int(self.config["seed"]))
         self.model = model_factory().to(dev)
-        self.model(self.batch.features, self.batch.adjacency)                           # creates the parameters (lazy build)
+        self.model(self.batch.features, self.batch.adjacency, **self.kw)                # creates the parameters (lazy build)
         self.opt = train.TFAdam(self.model.parameters(), lr=float(self.config["learning_rate"]))
         self.flat = self.opt.flat
         # [each_cost | each_correct | each_count | cost] of the batches since the last zero_(): training and evaluation
-        self.train_sums = torch.zeros(3 * T + 1, device=dev)
-        self.eval_sums = torch.zeros(3 * T + 1, device=dev)
+        # (regression: [error_sum | count | cost_sum], ops.masked_squared_error)
+        self.train_sums = torch.zeros((2 if regression else 3) * T + 1, device=dev)
+        self.eval_sums = torch.zeros_like(self.train_sums)
         self.best = torch.empty_like(self.flat.data)
 
         sums = self.train_sums                         # not `self`: a closure over self would tie the validator into a reference
 
         def loss_fn(logits, labels_, mask_):           # cycle, and its hipGraphs would then die whenever the collector runs
+            if regression:
+                return ops.masked_squared_error(logits, labels_, mask_, accum=sums)[:2]
             cost = ops.multitask_softmax2_ce(logits, labels_, mask_, accum=sums)[0]
             return cost, cost
 
-        self.step = train.GraphedTrainStep(self.model, self.opt, loss_fn, self.batch, self.lab, self.ml, capture_assembly=True)
+        self.step = train.GraphedTrainStep(self.model, self.opt, loss_fn, self.batch, self.lab, self.ml, capture_assembly=True,
+                                           **self.kw)
         # the evaluation step: assembly, forward and loss (sums into eval_sums, predictions at a fixed address)
         self.prediction = None
         side = torch.cuda.Stream()
@@ -199,8 +237,12 @@ class CrossValidator:
         with torch.no_grad():
             ops.weight_tables.refresh()
             self.batch.assemble()
-            logits = self.model(self.batch.features, self.batch.adjacency)
-            self.prediction = ops.multitask_softmax2_ce(logits, self.lab, self.ml, accum=self.eval_sums)[4]
+            logits = self.model(self.batch.features, self.batch.adjacency, **self.kw)
+            if self.regression:
+                ops.masked_squared_error(logits, self.lab, self.ml, accum=self.eval_sums)
+                self.prediction = logits
+            else:
+                self.prediction = ops.multitask_softmax2_ce(logits, self.lab, self.ml, accum=self.eval_sums)[4]
 
     # -- state of a fold ----------------------------------------------------------------------------------------------------------
     def reset(self, seed):
@@ -211,7 +253,7 @@ class CrossValidator:
         torch.manual_seed(int(seed))
         fresh = self.factory().to(self.flat.data.device)
         with torch.no_grad():
-            fresh(self.batch.features, self.batch.adjacency)
+            fresh(self.batch.features, self.batch.adjacency, **self.kw)
             new = list(fresh.parameters())
             if [tuple(p.shape) for p in new] != [tuple(p.shape) for p in self.flat.params]:
                 raise RuntimeError("model_factory() built a network with other parameters than the captured one")
@@ -227,9 +269,14 @@ class CrossValidator:
         self.flat.data.copy_(flat_values)
         ops.weight_tables.invalidate()
 
-    @staticmethod
-    def _summary(sums, T, num):
+    def _summary(self, sums, T, num):
         s = sums.double().cpu().numpy()                # the one read-back of an epoch / an evaluation
+        if self.regression:
+            # kgcn/core.py:184-186: mse = error_sum / count over all tasks (the model's metrics are scalars); per task beside it
+            with np.errstate(divide="ignore", invalid="ignore"):
+                each_mse = s[:T] / s[T:2 * T]
+                mse = float(s[:T].sum() / s[T:2 * T].sum())
+            return float(s[2 * T]) / num, mse, each_mse
         with np.errstate(divide="ignore", invalid="ignore"):
             each_acc = s[T:2 * T] / s[2 * T:3 * T]
         # kgcn/core.py:200-206: each_accuracy = each_correct_count / each_count, accuracy = its nanmean
@@ -270,7 +317,8 @@ class CrossValidator:
         train_idx = np.array(train_idx, np.int64)
         valid_idx = np.asarray(valid_idx, np.int64)
         stopper = EarlyStopping(cfg["patience"])
-        out = {"training_cost": [], "validation_cost": [], "training_acc": [], "validation_acc": [], "best_epoch": None}
+        acc = "mse" if self.regression else "acc"
+        out = {"training_cost": [], "validation_cost": [], "training_" + acc: [], "validation_" + acc: [], "best_epoch": None}
         best = None
         for epoch in range(int(cfg["epoch"])):
             rs.shuffle(train_idx)                                                      # kgcn/core.py:248
@@ -280,10 +328,10 @@ class CrossValidator:
             else:
                 vcost, vacc = 0.0, 0.0
             out["training_cost"].append(tcost)
-            out["training_acc"].append(tacc)
+            out["training_" + acc].append(tacc)
             if len(valid_idx):
                 out["validation_cost"].append(vcost)
-                out["validation_acc"].append(vacc)
+                out["validation_" + acc].append(vacc)
             seen = vcost if validation_cost_fn is None else float(validation_cost_fn(epoch, vcost))
             if stopper.evaluate_validation(seen) or np.isnan(seen):
                 break
@@ -321,6 +369,11 @@ class CrossValidator:
         cost, acc, pred = self.pred_and_eval(test_idx)
         sel = torch.as_tensor(test_idx, device=pred.device)
         mask = self.mask_label.index_select(0, sel) if cfg["metrics_mask"] else None
+        if self.regression:
+            sums = ops.regression_metrics(pred, self.labels.index_select(0, sel), mask)
+            info["infer_time"] = time.time() - t0
+            info.update(test_cost=cost, test_mse=acc, test_data_idx=[int(i) for i in test_idx], sums=sums.tolist())
+            return [regression_metrics_from_sums(sums[t]) for t in range(self.tasks)], info, pred
         counts, ap = ops.binary_metrics(pred, self.labels.index_select(0, sel), mask, threshold=cfg["threshold"])
         info["infer_time"] = time.time() - t0
         info.update(test_cost=cost, test_acc=acc, test_data_idx=[int(i) for i in test_idx], counts=counts.tolist(), ap=ap.tolist())
@@ -342,9 +395,9 @@ class CrossValidator:
         return {"result_cv": result_cv, "info_cv": info_cv, "predictions": predictions, "folds": folds}
 
 
-def train_cv(model_factory, dataset, labels, mask_label, config=None):
+def train_cv(model_factory, dataset, labels, mask_label, config=None, forward_tables=None):
     """gcn.py train_cv -> {"result_cv": cv.json's content, "info_cv": the save_info_cv fields per fold (costs and accuracies
     per epoch, best_epoch, test_cost, test_acc, test_data_idx, train_time, infer_time, the metric sums), "predictions": the
     test folds' [n_test, T] device tensors, "folds": the (train, test) index pairs}.  config: DEFAULT_CONFIG's keys (the names
     of the reference's config where it has them); save_result_cv / save_info_cv write the two JSON files."""
-    return CrossValidator(model_factory, dataset, labels, mask_label, config).run()
+    return CrossValidator(model_factory, dataset, labels, mask_label, config, forward_tables).run()

@@ -234,6 +234,40 @@ def sequence_table(data, device="cuda"):
     return torch.from_numpy(np.ascontiguousarray(seq, dtype=np.int32)).to(device), S
 
 
+VECTOR_MODAL_NAMES = ("vector_modal", "profeat", "dragon", "chemical_fp")      # kgcn/data_util.py:451, in the loader's order
+
+
+def vector_modal_info(data):
+    """kgcn/data_util.py:449-455, 558-559 -> (vector_modal_name {name: position}, vector_modal_dim [width per position]) of the
+    per-graph vector tables a .jbl dict carries."""
+    names, dims = {}, []
+    for name in VECTOR_MODAL_NAMES:
+        if name in data:
+            names[name] = len(dims)
+            dims.append(int(np.asarray(data[name]).shape[1]))
+    return names, dims
+
+
+def vector_table(data, name=None, device="cuda"):
+    """The per-graph vector modality `name` of a .jbl dict (kgcn/data_util.py:449-455; name None: the first of
+    VECTOR_MODAL_NAMES the dict holds) as a float32 [G, Dv] device tensor.  StaticBatch.add_table serves it per batch, with zero
+    rows for the dummy graphs of a short batch (kgcn/feed.py:201-204)."""
+    import torch
+    if name is None:
+        name = next((n for n in VECTOR_MODAL_NAMES if n in data), None)
+    if name is None or name not in data:
+        raise ValueError("the dataset has no vector modality %s (one of %s)" % ("" if name is None else repr(name),
+                                                                                ", ".join(VECTOR_MODAL_NAMES)))
+    if name not in VECTOR_MODAL_NAMES:
+        raise ValueError("%r is not a vector modality the loader reads (%s)" % (name, ", ".join(VECTOR_MODAL_NAMES)))
+    vec = np.asarray(data[name])
+    if vec.ndim != 2 or vec.shape[1] < 1:
+        raise ValueError("%s must be a [graphs, width] array, got shape %s" % (name, vec.shape))
+    if not np.isfinite(vec).all():
+        raise ValueError("%s holds NaN or infinite values" % name)
+    return torch.from_numpy(np.ascontiguousarray(vec, dtype=np.float32)).to(device)
+
+
 class DeviceGraphDataset:
     """The whole dataset resident in HBM: every adjacency channel as ONE batched-CSR
     container over all G graphs (plus, built lazily, its transpose and the row-padded copies the fused

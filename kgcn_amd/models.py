@@ -21,6 +21,10 @@ between layer and activation it is one HIP elementwise kernel (ops.activation). 
                   relu, Dense(label_dim) (csrc/conv1d.hip); class-weighted softmax CE
   CPIMultitaskNet -- sample_chem/compound-protein_interaction/multitask.py:35-86  GraphConv(512) sigmoid, GraphGather, Dense(2 T)
                   read as [B, 2, T]; two-way softmax cross entropy per task under mask_label (csrc/cvloss.hip)
+  MultimodalVecGCN -- example_model/model_multimodal_vec.py:56-127  GraphConv(50), GraphDense(50), Gather | Dense+BN+relu 300/100/64
+                  on the per-graph vector (csrc/shortm.hip); concat, Dense(52)+BN+relu, Dense(label_dim); masked softmax CE
+  MultimodalRegressionGCN -- example_model/model_multimodal_regression.py:60-101  3 x [GraphDense(32), BN], Gather, tanh |
+                  Dense(8)+BN+relu on the vector; concat, Dense(label_dim); masked squared error (csrc/regress.hip)
 
 Keras learning-phase semantics (quirk Q6): the reference calls BatchNormalization / Dropout
 without `training=`; under TF1 graph mode that is inference behaviour -- BN normalises with its
@@ -669,4 +673,131 @@ class SeqCNN(nn.Module):
         row_weight = mask * (labels * self.class_weight).sum(dim=1) * (1.0 / C)
         cost_opt, _ = ops.masked_softmax_ce(logits, labels, row_weight)
         _, cost_sum = ops.masked_softmax_ce(logits, labels, mask)
+        return cost_opt, cost_sum
+
+
+class KerasDenseBN(nn.Module):
+    """K.layers.Dense(units) -> K.layers.BatchNormalization() -> activation on [B, D] (model_multimodal_vec.py:84-86): kernel
+    glorot-uniform, bias zeros, gamma ones, beta zeros, moving mean 0 / variance 1, eps 1e-3; the normalisation runs in learning
+    phase 0 (quirk Q6: the moving statistics, never updated).  batch_norm=False: Dense + activation alone.  One op
+    (ops.dense_bn), which picks the short-batch kernels of csrc/shortm.hip or dense -> graph_bn.
+    forward(x, out=None, out_col=0): the result goes into columns out_col.. of the [B, wide] buffer `out` when given."""
+
+    def __init__(self, units, batch_norm=True, activation=None, eps=1e-3):
+        super().__init__()
+        ops.act_code(activation)
+        self.units, self.batch_norm, self.activation, self.eps = int(units), bool(batch_norm), activation, float(eps)
+        self.kernel = self.bias = self.gamma = self.beta = None
+
+    def build(self, din, device):
+        if self.kernel is None:
+            self.kernel = nn.Parameter(layers._init_tensor((din, self.units), "glorot_uniform", device))
+            self.bias = nn.Parameter(torch.zeros(self.units, device=device))
+            if self.batch_norm:
+                self.gamma = nn.Parameter(torch.ones(self.units, device=device))
+                self.beta = nn.Parameter(torch.zeros(self.units, device=device))
+                self.register_buffer("moving_mean", torch.zeros(self.units, device=device))
+                self.register_buffer("moving_variance", torch.ones(self.units, device=device))
+
+    def forward(self, x, out=None, out_col=0):
+        self.build(x.shape[1], x.device)
+        if not self.batch_norm:
+            return ops.dense_bn(x, self.kernel, self.bias, activation=self.activation, out=out, out_col=out_col)
+        return ops.dense_bn(x, self.kernel, self.bias, self.gamma, self.beta, self.moving_mean, self.moving_variance, self.eps,
+                            self.activation, out=out, out_col=out_col)
+
+
+class MultimodalVecGCN(nn.Module):
+    """example_model/model_multimodal_vec.py:56-127 (compound graph + per-graph protein vector `profeat`), call by call:
+      graph branch (:60-75)   GraphConv(50, C) sigmoid, GraphDense(50) sigmoid, GraphGather -> [B, 50]
+      vector branch (:83-94)  Dense(300), BatchNormalization, relu; Dense(100), BN, relu; Dense(64), BN, relu -> [B, 64]
+      shared part (:103-110)  concat([vector, graph]) -> Dense(52), BN, relu -> Dense(label_dim); loss masked_softmax_ce (:112-120)
+    The concatenation is one [B, 114] buffer: the tower's last layer writes columns 0-63, the graph read-out 64-113
+    (ops.join_columns), nothing is copied.  forward(features, adjs, vectors=None, enabled_node_nums=None) -> logits; `vectors`
+    is the float32 [B, Dv] batch of data_util.vector_table (GraphedTrainStep passes it as a forward kwarg); enabled_node_nums is
+    accepted and unused, as in the file.  The rows never mix (learning phase 0, no dropout)."""
+
+    ROW_INDEPENDENT = True
+
+    GRAPH_WIDTH, TOWER, HIDDEN = 50, (300, 100, 64), 52
+
+    def __init__(self, adj_channel_num=1, label_dim=2):
+        super().__init__()
+        self.conv = layers.GraphConv(self.GRAPH_WIDTH, adj_channel_num, activation="sigmoid")     # :60-61
+        self.dense = layers.GraphDense(self.GRAPH_WIDTH, activation="sigmoid")                    # :73-74
+        self.tower = nn.ModuleList([KerasDenseBN(u, activation="relu") for u in self.TOWER])      # :84-94
+        self.hidden = KerasDenseBN(self.HIDDEN, activation="relu")                                # :106-108
+        self.out = KerasDenseBN(int(label_dim), batch_norm=False)                                 # :110
+
+    def forward(self, features, adjs, vectors=None, enabled_node_nums=None):
+        if vectors is None:
+            raise ValueError("MultimodalVecGCN needs the vectors= batch")
+        adj = layers._pack(adjs, features)
+        B, vw = features.shape[0], self.TOWER[-1]
+        if vectors.shape[0] != B:
+            raise ValueError("%d vectors for %d graphs" % (vectors.shape[0], B))
+        joined = features.new_empty((B, vw + self.GRAPH_WIDTH))
+        layer = self.tower[1](self.tower[0](vectors))
+        vec = self.tower[2](layer, out=joined, out_col=0)
+        node = self.dense(self.conv(features, adj=adj))
+        graph = ops.graph_gather_into(node, joined, vw)                                           # :75
+        layer = ops.join_columns(joined, [vec, graph])                                            # :103 tf.concat
+        return self.out(self.hidden(layer))
+
+    @staticmethod
+    def loss(logits, labels, mask):
+        """model_multimodal_vec.py:114-120 -> (cost_opt, cost_sum)."""
+        return masked_softmax_ce(logits, labels, mask)
+
+
+class MultimodalRegressionGCN(nn.Module):
+    """example_model/model_multimodal_regression.py:60-101 (graph + per-graph descriptor vector `dragon`, regression), call by call:
+      graph branch (:63-81)   GraphDense(32), GraphBatchNormalization, relu (twice); GraphDense(32), GraphBatchNormalization;
+                              GraphGather, tanh -> [B, 32].  The adjacency is not read (no GraphConv in the file).
+      vector branch (:83-86)  Dense(8), BatchNormalization, relu -> [B, 8]
+      head (:88-90)           concat([vector, graph]) -> Dense(label_dim): the predictions
+    The node-level body runs through layers.fused_stack when eligible (one launch each way), else layer by layer;
+    GraphBatchNormalization honours enabled_node_nums.  The concatenation is one [B, 40] buffer (vector 0-7, graph 8-39).
+    forward(features, adjs, vectors=None, enabled_node_nums=None) -> predictions [B, label_dim]; loss: masked squared error."""
+
+    ROW_INDEPENDENT = True
+
+    WIDTH, VEC_WIDTH = 32, 8
+
+    def __init__(self, label_dim=1):
+        super().__init__()
+        self.dense1 = layers.GraphDense(self.WIDTH)                                               # :63
+        self.bn1 = GraphBatchNormalization(activation="relu")                                     # :64-67
+        self.dense2 = layers.GraphDense(self.WIDTH)                                               # :69
+        self.bn2 = GraphBatchNormalization(activation="relu")                                     # :70-73
+        self.dense3 = layers.GraphDense(self.WIDTH)                                               # :75
+        self.bn3 = GraphBatchNormalization()                                                      # :76-78
+        self.gather = layers.GraphGather()                                                        # :80
+        self.vec = KerasDenseBN(self.VEC_WIDTH, activation="relu")                                # :84-86
+        self.out = KerasDenseBN(int(label_dim), batch_norm=False)                                 # :90
+
+    def forward(self, features, adjs, vectors=None, enabled_node_nums=None):
+        if vectors is None:
+            raise ValueError("MultimodalRegressionGCN needs the vectors= batch")
+        B, N = features.shape[0], features.shape[1]
+        if vectors.shape[0] != B:
+            raise ValueError("%d vectors for %d graphs" % (vectors.shape[0], B))
+        joined = features.new_empty((B, self.VEC_WIDTH + self.WIDTH))
+        vec = self.vec(vectors, out=joined, out_col=0)
+        body = [self.dense1, self.bn1, self.dense2, self.bn2, self.dense3, self.bn3]
+        pooled = None if adjs is None else layers.fused_stack(body, features, layers._pack(adjs, features),
+                                                              enabled_node_nums=enabled_node_nums, gather=True)
+        if pooled is None:
+            layer = features
+            for dense, bn in zip(body[0::2], body[1::2]):
+                layer = bn(dense(layer), max_node_num=N, enabled_node_nums=enabled_node_nums)
+            pooled = self.gather(layer)
+        graph = ops.activation_into(pooled, "tanh", joined, self.VEC_WIDTH)                       # :81 tf.nn.tanh
+        layer = ops.join_columns(joined, [vec, graph])                                            # :88 tf.concat
+        return self.out(layer)
+
+    @staticmethod
+    def loss(logits, labels, mask_label, accum=None):
+        """model_multimodal_regression.py:94-101 -> (cost_opt, cost_sum); accum: ops.masked_squared_error's accumulator block."""
+        cost_opt, cost_sum = ops.masked_squared_error(logits, labels, mask_label, accum=accum)[:2]
         return cost_opt, cost_sum

@@ -2713,3 +2713,225 @@ def binary_metrics(score, label, mask=None, threshold=0.5):
         raise ValueError("binary_metrics: %d scores are NaN or infinite (tasks %s)"
                          % (int(counts[:, 4].sum()), [int(t) for t in counts[:, 4].nonzero()[0]]))
     return counts, ap
+
+
+# -------------------------------------------------------------------------------------------------
+# vector-modality models and regression (example_model/model_multimodal_vec.py, model_multimodal_regression.py): the
+# Dense + BatchNormalization + activation layer of the vector towers at short batches (csrc/shortm.hip) and the regression
+# head (csrc/regress.hip)
+# -------------------------------------------------------------------------------------------------
+# The short-batch kernels take a Dense(+BN)(+activation) layer of at most short_dense_max_rows rows when short_dense_fusion is
+# on; everything else -- and every shape kgcn_dense_bn_short_supported refuses -- runs dense -> graph_bn.  Both values follow
+# tools/vecmodal_bench.py (profiles/vecmodal_bench.json; DESIGN.md, "Vector-modality models and regression"): OFF by default.
+# On the MI355X the short route was ahead at one of the fifteen measured (rows, K, N) -- 50 x 114 -> 52, by 10 % -- and behind
+# at the other fourteen (by 7 % to 6x, growing with rows and K), and the whole captured step of both models was 10 % slower
+# with it at 50 rows and up to 3x at 256.  The row limit is the kernels' own: no measured row count favours the route.
+short_dense_fusion = False
+short_dense_max_rows = 256
+
+
+def dense_bn_short_supported(rows, k, n):
+    """Whether csrc/shortm.hip takes a [rows, k] x [k, n] layer (host query, no launch)."""
+    return bool(lib.kgcn_dense_bn_short_supported(int(rows), int(k), int(n)))
+
+
+def dense_bn_route(rows, k, n):
+    """-> 'short' (the fused short-batch kernels) or 'composed' (dense -> graph_bn): the one place that decides."""
+    if short_dense_fusion and rows <= short_dense_max_rows and dense_bn_short_supported(rows, k, n):
+        return "short"
+    return "composed"
+
+
+def _row_strided(t, width, name):
+    """A float32 device matrix whose rows may be strided (a column block of a wider buffer) as it lies, anything else contiguous."""
+    require_gpu(t, name)
+    if t.dtype != torch.float32 or t.dim() != 2:
+        raise _lib.KgcnHipError("%s must be a float32 matrix, got %s %s" % (name, t.dtype, tuple(t.shape)))
+    if t.stride(1) != 1 or t.stride(0) < width:
+        t = t.contiguous()
+    return t
+
+
+def _column_block(out, out_col, rows, n, device):
+    """-> (buffer, the [rows, n] view at column out_col): a fresh [rows, n] tensor when out is None."""
+    if out is None:
+        out = torch.empty((rows, n), device=device, dtype=torch.float32)
+        return out, out
+    if out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != rows or not out.is_contiguous() or not out.is_cuda or \
+            out_col < 0 or out_col + n > out.shape[1]:
+        raise _lib.KgcnHipError("output buffer %s does not take [%d, %d] at column %d" % (tuple(out.shape), rows, n, out_col))
+    return out, out[:, out_col:out_col + n]
+
+
+class _DenseBNShort(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, bias, gamma, beta, mean, var, eps, act, out, out_col):
+        w = _f32c(w, "w")
+        K, N = w.shape
+        x = _row_strided(x, K, "x")
+        B = x.shape[0]
+        if x.shape[1] != K:
+            raise _lib.KgcnHipError("dense_bn: x %s does not match the kernel %s" % (tuple(x.shape), tuple(w.shape)))
+        vecs = [None if v is None else _f32c(v, "vector").reshape(-1) for v in (bias, gamma, beta, mean, var)]
+        if any(v is not None and v.numel() != N for v in vecs):
+            raise _lib.KgcnHipError("dense_bn: bias / gamma / beta / moving statistics must hold %d values" % N)
+        b, ga, be, mu, va = vecs
+        out, y = _column_block(out, out_col, B, N, x.device)
+        train = any(ctx.needs_input_grad[:5])
+        pre = torch.empty((B, N), device=x.device, dtype=torch.float32) if train and ga is not None else None
+        check(lib.kgcn_dense_bn_short_fwd_f32(x.data_ptr(), x.stride(0), B, K, ptr(w), ptr(b), N, ptr(ga), ptr(be), ptr(mu), ptr(va),
+                                              float(eps), int(act), y.data_ptr(), y.stride(0), ptr(pre), current_stream()),
+              "kgcn_dense_bn_short_fwd_f32")
+        if train:
+            ctx.save_for_backward(x, w, ga, mu, va, y, pre)
+            ctx.eps, ctx.act = float(eps), int(act)
+            ctx.vec_shapes = [None if v is None else tuple(v.shape) for v in (bias, gamma, beta)]
+        ctx.set_materialize_grads(False)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        n = ctx.needs_input_grad
+        if g is None or not any(n[:5]):
+            return (None,) * 11
+        x, w, ga, mu, va, y, pre = ctx.saved_tensors
+        B, K = x.shape
+        N = w.shape[1]
+        g = _row_strided(g, N, "grad")
+        new = lambda *shape: torch.empty(shape, device=x.device, dtype=torch.float32)
+        dw = new(K, N) if n[1] else None
+        db = new(N) if n[2] else None
+        dga = new(N) if n[3] else None
+        dbe = new(N) if n[4] else None
+        dpre = new(B, N) if n[0] else None
+        check(lib.kgcn_dense_bn_short_bwd_f32(x.data_ptr(), x.stride(0), B, K, N, y.data_ptr(), y.stride(0), g.data_ptr(), g.stride(0),
+                                              ptr(pre), ptr(ga), ptr(mu), ptr(va), ctx.eps, ctx.act, ptr(dw), ptr(db), ptr(dga),
+                                              ptr(dbe), ptr(dpre), current_stream()), "kgcn_dense_bn_short_bwd_f32")
+        dx = None
+        if n[0]:
+            dx = new(B, K)
+            check(lib.kgcn_dense_bn_short_dx_f32(ptr(dpre), B, N, ptr(w), K, ptr(dx), K, current_stream()), "kgcn_dense_bn_short_dx_f32")
+        sb, sg, se = ctx.vec_shapes
+        return (dx, dw, None if db is None else db.view(sb), None if dga is None else dga.view(sg),
+                None if dbe is None else dbe.view(se), None, None, None, None, None, None)
+
+
+class _ActInto(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, act, out, out_col):
+        x = _row_strided(x, x.shape[1] if x.dim() == 2 else 0, "inputs")
+        B, N = x.shape
+        out, y = _column_block(out, out_col, B, N, x.device)
+        check(lib.kgcn_act_cols_fwd_f32(x.data_ptr(), x.stride(0), B, N, int(act), y.data_ptr(), y.stride(0), current_stream()),
+              "kgcn_act_cols_fwd_f32")
+        ctx.save_for_backward(y)
+        ctx.act = int(act)
+        ctx.set_materialize_grads(False)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None or not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        (y,) = ctx.saved_tensors
+        B, N = y.shape
+        g = _row_strided(g, N, "grad")
+        dx = torch.empty((B, N), device=y.device, dtype=torch.float32)
+        check(lib.kgcn_act_cols_bwd_f32(y.data_ptr(), y.stride(0), g.data_ptr(), g.stride(0), B, N, ctx.act, ptr(dx), N,
+                                        current_stream()), "kgcn_act_cols_bwd_f32")
+        return dx, None, None, None
+
+
+def activation_into(x, activation, out=None, out_col=0):
+    """act(x) of a [B, N] matrix (rows may be strided) written into columns out_col .. out_col + N of the contiguous [B, wide]
+    buffer `out` and returned as that view (a block of a concatenation, join_columns): one launch each way, and the backward
+    reads the gradient's column block where it lies."""
+    return _ActInto.apply(x, act_code(activation), out, int(out_col))
+
+
+def dense_bn(x, w, b, gamma=None, beta=None, moving_mean=None, moving_variance=None, eps=1e-3, activation=None, out=None, out_col=0):
+    """K.layers.Dense -> K.layers.BatchNormalization (learning phase 0: the moving statistics are constants, quirk Q6) ->
+    activation on x [B, K] (rows may be strided):  y = act(gamma (x w + b - moving_mean) / sqrt(moving_variance + eps) + beta);
+    gamma None (then beta and the statistics None too): y = act(x w + b).  out / out_col: y is written into columns out_col ..
+    out_col + N of the contiguous [B, wide] buffer `out` and returned as that view; the other columns are not touched.
+    Route (dense_bn_route): the short-batch kernels of csrc/shortm.hip -- one launch forward, one for dW / db / dgamma / dbeta,
+    one more for dX when x requires grad -- or dense -> graph_bn on a [B, 1, N] view.  Same function either way."""
+    act = act_code(activation)
+    if (gamma is None) != (beta is None) or (gamma is None) != (moving_mean is None) or (gamma is None) != (moving_variance is None):
+        raise _lib.KgcnHipError("dense_bn: gamma, beta, moving_mean and moving_variance come together or not at all")
+    if x.dim() != 2 or w.dim() != 2:
+        raise _lib.KgcnHipError("dense_bn: x [B, K] and w [K, N] are matrices, got %s and %s" % (tuple(x.shape), tuple(w.shape)))
+    B, (K, N) = x.shape[0], w.shape
+    if dense_bn_route(B, K, N) == "short":
+        return _DenseBNShort.apply(x, w, b, gamma, beta, moving_mean, moving_variance, float(eps), act, out, int(out_col))
+    if gamma is None:
+        y = dense(x, w, b, activation=activation)
+    else:
+        y = graph_bn(dense(x, w, b).reshape(B, 1, N), gamma, beta, moving_mean, moving_variance, None, eps, False, activation).reshape(B, N)
+    return y if out is None else activation_into(y, None, out, out_col)
+
+
+class _MaskedSqErr(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, labels, mask_label, accum):
+        p = _f32c(pred, "pred")
+        z = _f32c(labels.to(torch.float32), "labels")
+        ml = _f32c(mask_label.to(torch.float32), "mask_label")
+        if p.dim() != 2 or z.shape != p.shape or ml.shape != p.shape:
+            raise _lib.KgcnHipError("masked_squared_error: pred %s, labels %s and mask_label %s must be one [B, T] shape"
+                                    % (tuple(p.shape), tuple(z.shape), tuple(ml.shape)))
+        B, T = p.shape
+        if accum is not None:
+            require_gpu(accum, "accum")
+            if accum.dtype != torch.float32 or not accum.is_contiguous() or accum.numel() != 2 * T + 1:
+                raise _lib.KgcnHipError("masked_squared_error: the accumulator is a contiguous float32 block of 2 T + 1 = %d" % (2 * T + 1))
+        dpred = torch.empty_like(p)
+        stats = torch.empty((2 * T + 2,), device=p.device, dtype=torch.float32)
+        check(lib.kgcn_masked_sqerr_f32(ptr(p), ptr(z), ptr(ml), B, T, ptr(dpred), ptr(stats), ptr(accum), current_stream()),
+              "kgcn_masked_sqerr_f32")
+        ctx.save_for_backward(dpred)
+        ctx.batch = B * T
+        ctx.set_materialize_grads(False)
+        each = stats[:2 * T]
+        ctx.mark_non_differentiable(each)
+        return stats[2 * T + 1], stats[2 * T], each
+
+    @staticmethod
+    def backward(ctx, g_opt, g_sum, g_each):
+        (dpred,) = ctx.saved_tensors
+        return _loss_grad(dpred, g_opt, g_sum, ctx.batch), None, None, None
+
+
+def masked_squared_error(pred, labels, mask_label, accum=None):
+    """model_multimodal_regression.py:94-101 in one HIP pass -> (cost_opt, cost_sum, error_sum [T], count [T]): loss =
+    mask_label (labels - pred)^2 on [B, T]; cost_opt = reduce_mean(loss) over the padded batch, cost_sum = reduce_sum(loss),
+    error_sum / count per task (their totals are the file's metrics; mse = error_sum / count, kgcn/core.py:184-186).  accum: a
+    float32 device block [2 T + 1] = error_sum | count | cost_sum the call adds its values to in place.  cost_opt and cost_sum
+    are differentiable; a row with mask_label 0 has gradient exactly 0."""
+    cost_opt, cost_sum, each = _MaskedSqErr.apply(pred, labels, mask_label, accum)
+    T = pred.shape[1]
+    return cost_opt, cost_sum, each[:T], each[T:]
+
+
+REGRESSION_SUMS_COLUMNS = ("n", "sum_y", "ss_tot", "ss_res", "sum_log_ratio", "n_bad_ratio")
+
+
+@torch.no_grad()
+def regression_metrics(pred, label, mask=None):
+    """The sums behind r2 / mse / gmfe (gcn.py:204-208) for every task at once -> [T, 6] float64 numpy array with the columns
+    REGRESSION_SUMS_COLUMNS: n, sum y, sum (y - mean y)^2, sum (y - p)^2, sum log(y / p) over the rows with a positive finite
+    ratio, the count of the other rows.  pred / label [n, T] float32 (rows may be strided), mask None (every row counts, as the
+    reference) or [n, T].  Two passes in fp64 on the device in a fixed order; kgcn_amd.cv.regression_metrics_from_sums derives
+    the metrics."""
+    if pred.dim() != 2 or pred.shape[0] < 1 or pred.shape[1] < 1:
+        raise _lib.KgcnHipError("regression_metrics: pred must be a [n >= 1, T >= 1] tensor, got %s" % (tuple(pred.shape),))
+    n, T = pred.shape
+    pred = _row_strided(pred, T, "pred")
+    label = _row_strided(label.to(torch.float32), T, "label")
+    mk = None if mask is None else _f32c(mask.to(torch.float32), "mask")
+    if tuple(label.shape) != (n, T) or (mk is not None and tuple(mk.shape) != (n, T)):
+        raise _lib.KgcnHipError("regression_metrics: label / mask do not match pred %s" % ((n, T),))
+    sums = torch.empty((T, 6), device=pred.device, dtype=torch.float64)
+    check(lib.kgcn_regression_sums_f64(pred.data_ptr(), pred.stride(0), label.data_ptr(), label.stride(0), ptr(mk), n, T,
+                                       sums.data_ptr(), current_stream()), "kgcn_regression_sums_f64")
+    return sums.cpu().numpy()
