@@ -88,7 +88,9 @@ extern "C" {
  * Cross-validation added entry points only (version still 2): kgcn_multitask_softmax2_ce_f32, kgcn_binary_metrics_f32
  * (+ kgcn_binary_metrics_workspace_bytes).
  * The vector-modality models and regression added entry points only (version still 2): kgcn_dense_bn_short_fwd_f32 / _bwd_f32 /
- * _dx_f32 (+ kgcn_dense_bn_short_supported), kgcn_act_cols_fwd_f32 / _bwd_f32, kgcn_masked_sqerr_f32, kgcn_regression_sums_f64. */
+ * _dx_f32 (+ kgcn_dense_bn_short_supported), kgcn_act_cols_fwd_f32 / _bwd_f32, kgcn_masked_sqerr_f32, kgcn_regression_sums_f64.
+ * Integrated gradients of the compound-protein interaction network added entry points only (version still 2): kgcn_cpi_ig_f32
+ * (+ kgcn_cpi_ig_workspace_bytes). */
 #define KGCN_HIP_ABI_VERSION 2
 
 /* Column index of the padding entries of a row-padded batch (see row_pad): they carry value 0 and
@@ -1118,6 +1120,27 @@ int kgcn_masked_sqerr_f32(const float* pred, const float* labels, const float* m
 #define KGCN_REGRESSION_SUMS_MAX_ROWS (1ll << 31)
 int kgcn_regression_sums_f64(const float* pred, int64_t pred_ld, const float* label, int64_t label_ld, const float* mask, int64_t n,
                              int32_t tasks, double* sums, void* stream);
+
+/* Integrated gradients of the compound-protein interaction multitask network (multitask.py:35-51: GraphConv(Wd), sigmoid, sum
+ * over the node rows, Dense(2 T); kgcn/visualization.py:187-286): the sweep over the `steps` scaled copies of `compounds`
+ * compounds for all `tasks` tasks (csrc/cpiig.hip; an entry point only, version still 2).
+ * The caller forms once per compound P = sum_ch A_ch X W_ch and Q = sum_ch rowsum(A_ch) (x) b_ch, both [compounds, nodes, width]
+ * contiguous, and per task u_t = V[:, T + t] - V[:, t] ([tasks, width]) and e_t = c[T + t] - c[t] ([tasks]) of the Dense layer.
+ * Copy k has the pre-activation Z_k = alpha[k] P + gamma[k] Q, H_k = sigmoid(Z_k), and
+ *   p [compounds, steps, tasks]         p[c, k, t] = sigmoid(sum_{n, j} H_k[n, j] u_t[j] + e_t): task t's prediction of copy k
+ *   GA [compounds, tasks, nodes, width] GA[c, t] = sum_k wA[k] p (1 - p)[c, k, t] u_t[j] H_k (1 - H_k): the weighted sum over the
+ *                                       copies of d prediction / d Z_k; GB the same with wB (wB and GB both NULL: not formed).
+ * The sigmoid is evaluated from exp(-|z|): no overflow, no NaN, no cancellation in H (1 - H) or p (1 - p) at any |z|.  All sums
+ * run in a fixed order without atomics and no workgroup spans two compounds: bitwise reproducible, and a compound's rows do
+ * not depend on which other compounds the call holds.  A lane of the accumulate pass carries KGCN_CPIIG_TASKS_PER_PASS tasks;
+ * more tasks take further passes over the copies.  workspace: kgcn_cpi_ig_workspace_bytes(compounds, width, tasks, steps) bytes.
+ * Limits: nodes, width, tasks >= 1, steps >= 2 (the start and the end copy); the three grids must stay below 2^31 workgroups.
+ * Asynchronous. */
+#define KGCN_CPIIG_TASKS_PER_PASS 8
+int64_t kgcn_cpi_ig_workspace_bytes(int32_t compounds, int32_t width, int32_t tasks, int32_t steps);
+int kgcn_cpi_ig_f32(const float* P, const float* Q, int32_t compounds, int32_t nodes, int32_t width, const float* u, const float* e,
+                    int32_t tasks, const float* alpha, const float* gamma, const float* wA, const float* wB, int32_t steps, float* p,
+                    float* GA, float* GB, void* workspace, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

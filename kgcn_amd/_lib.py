@@ -360,6 +360,10 @@ SIGNATURES = {
     "kgcn_masked_sqerr_f32": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_i64, c_i32, c_f32p, c_f32p, c_f32p, ctypes.c_void_p]),
     "kgcn_regression_sums_f64": (ctypes.c_int, [ctypes.c_void_p, c_i64, ctypes.c_void_p, c_i64, c_f32p, c_i64, c_i32, ctypes.c_void_p,
                                                 ctypes.c_void_p]),
+    # integrated gradients of the compound-protein interaction multitask network: the sweep over the scaled copies (csrc/cpiig.hip)
+    "kgcn_cpi_ig_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i32]),
+    "kgcn_cpi_ig_f32": (ctypes.c_int, [c_f32p, c_f32p, c_i32, c_i32, c_i32, c_f32p, c_f32p, c_i32, c_f32p, c_f32p, c_f32p, c_f32p,
+                                       c_i32, c_f32p, c_f32p, c_f32p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
     "kgcn_graph_gather_bwd_ld_f32": (ctypes.c_int, [c_f32p, c_i64, c_i64, c_i32, c_i32, c_f32p, ctypes.c_void_p]),
     "kgcn_graph_gather_bwd_add_f32": (ctypes.c_int, [c_f32p, c_f32p, c_i64, c_i32, c_i32, c_f32p, ctypes.c_void_p]),
     "kgcn_dot_workspace_bytes": (c_i64, [c_i64]),

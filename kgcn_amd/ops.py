@@ -2935,3 +2935,83 @@ def regression_metrics(pred, label, mask=None):
     check(lib.kgcn_regression_sums_f64(pred.data_ptr(), pred.stride(0), label.data_ptr(), label.stride(0), ptr(mk), n, T,
                                        sums.data_ptr(), current_stream()), "kgcn_regression_sums_f64")
     return sums.cpu().numpy()
+
+
+# -------------------------------------------------------------------------------------------------
+# integrated gradients of the compound-protein interaction multitask network (kgcn visualize on multitask.py; csrc/cpiig.hip): the
+# sweep over the scaled copies of many compounds, all tasks at once
+# -------------------------------------------------------------------------------------------------
+CPI_IG_TASKS_PER_PASS = 8           # KGCN_CPIIG_TASKS_PER_PASS: tasks a lane of the accumulate pass carries
+
+
+def cpi_ig_limits_check(nodes, width, tasks, steps):
+    """The ranges csrc/cpiig.hip serves, on the host: N, Wd, T >= 1 and K >= 2 copies (the start and the end copy)."""
+    N, Wd, T, K = int(nodes), int(width), int(tasks), int(steps)
+    if N < 1 or Wd < 1 or T < 1:
+        raise ValueError("cpi_ig: N = %d nodes, Wd = %d columns, T = %d tasks: each must be >= 1" % (N, Wd, T))
+    if K < 2:
+        raise ValueError("cpi_ig: %d scaled copies, at least 2 (the start and the end copy)" % K)
+    return N, Wd, T, K
+
+
+def _f32_vector(v, n, name, device):
+    import numpy as np
+    t = _f32c(v.detach(), name).reshape(-1) if torch.is_tensor(v) else torch.as_tensor(np.asarray(v, np.float32).reshape(-1), device=device)
+    if t.numel() != n:
+        raise ValueError("cpi_ig: %s has %d entries, expected %d" % (name, t.numel(), n))
+    return t
+
+
+@torch.no_grad()
+def cpi_ig(P, Q, u, e, alpha, gamma, wA, wB=None):
+    """csrc/cpiig.hip -> (p [C, K, T], GA [C, T, N, Wd], GB [C, T, N, Wd] or None).  P = sum_ch A_ch X W_ch and
+    Q = sum_ch rowsum(A_ch) (x) b_ch, both [C, N, Wd]; u [T, Wd] and e [T] the per-task difference of the Dense layer's two
+    columns and biases; alpha, gamma [K]: copy k has the pre-activation alpha[k] P + gamma[k] Q; wA, wB [K] copy weights.
+    p[c, k, t] is task t's prediction of copy k, GA[c, t] = sum_k wA[k] d p[c, k, t] / d Z_k (GB with wB; not formed when wB is
+    None).  A read-out: no autograd.  Bitwise reproducible, and a compound's rows do not depend on the others in the call."""
+    P, Q = _f32c(P.detach(), "P"), _f32c(Q.detach(), "Q")
+    u = _f32c(u.detach(), "u")
+    if P.dim() != 3 or tuple(Q.shape) != tuple(P.shape):
+        raise ValueError("cpi_ig: P and Q must both be [C, N, Wd], got %s and %s" % (tuple(P.shape), tuple(Q.shape)))
+    if u.dim() != 2 or u.shape[1] != P.shape[2]:
+        raise ValueError("cpi_ig: u must be [T, %d], got %s" % (P.shape[2], tuple(u.shape)))
+    C = P.shape[0]
+    dev = P.device
+    K = alpha.numel() if torch.is_tensor(alpha) else len(alpha)
+    N, Wd, T, K = cpi_ig_limits_check(P.shape[1], P.shape[2], u.shape[0], K)
+    e = _f32_vector(e, T, "e", dev)
+    alpha, gamma, wA = (_f32_vector(v, K, n, dev) for v, n in ((alpha, "alpha"), (gamma, "gamma"), (wA, "wA")))
+    wB = None if wB is None else _f32_vector(wB, K, "wB", dev)
+    p = torch.empty((C, K, T), device=dev, dtype=torch.float32)
+    GA = torch.empty((C, T, N, Wd), device=dev, dtype=torch.float32)
+    GB = None if wB is None else torch.empty_like(GA)
+    nbytes = lib.kgcn_cpi_ig_workspace_bytes(C, Wd, T, K)
+    ws = _lib.workspace(nbytes, dev)
+    check(lib.kgcn_cpi_ig_f32(ptr(P), ptr(Q), C, N, Wd, ptr(u), ptr(e), T, ptr(alpha), ptr(gamma), ptr(wA), ptr(wB), K, ptr(p),
+                              ptr(GA), ptr(GB), ptr(ws), nbytes, current_stream()), "kgcn_cpi_ig_f32")
+    return p, GA, GB
+
+
+@torch.no_grad()
+def spmm_values_grad(csr, grad, rhs, rhs_ld=None, rhs_gs=None):
+    """d values[e] = <grad[row_e, :], rhs[col_e, :]> for every stored entry of the batched CSR (the values gradient of bspmm as
+    a read-out) -> [nnz] in CSR order.  grad [T*M, d]; rhs [T*K, d], or any fp32 tensor addressed by the row stride rhs_ld and
+    the graph stride rhs_gs in floats (0, 0: one d-vector met by every entry)."""
+    grad = _f32c(grad.detach(), "grad")
+    rhs = _f32c(rhs.detach(), "rhs")
+    if grad.dim() != 2 or grad.shape[0] != csr.num_graphs * csr.rows:
+        raise ValueError("spmm_values_grad: grad must be [T*M, d] = [%d, d], got %s" % (csr.num_graphs * csr.rows, tuple(grad.shape)))
+    d = grad.shape[1]
+    if rhs_ld is None:
+        if tuple(rhs.shape) != (csr.num_graphs * csr.cols, d):
+            raise ValueError("spmm_values_grad: rhs must be [T*K, d] = [%d, %d], got %s" % (csr.num_graphs * csr.cols, d, tuple(rhs.shape)))
+        rhs_ld, rhs_gs = d, csr.cols * d
+    else:
+        rhs_ld, rhs_gs = int(rhs_ld), int(rhs_gs)
+        last = (csr.num_graphs - 1) * rhs_gs + (csr.cols - 1) * rhs_ld + d
+        if rhs_ld < 0 or rhs_gs < 0 or last > rhs.numel():
+            raise ValueError("spmm_values_grad: strides (%d, %d) reach past the %d floats of rhs" % (rhs_ld, rhs_gs, rhs.numel()))
+    dv = torch.empty((csr.nnz,), device=grad.device, dtype=torch.float32)
+    check(lib.kgcn_spmm_values_grad_f32(csr.desc(), ptr(grad), d, csr.rows * d, ptr(rhs), rhs_ld, rhs_gs, d, ptr(dv),
+                                        current_stream()), "kgcn_spmm_values_grad_f32")
+    return dv

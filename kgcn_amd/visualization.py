@@ -679,3 +679,256 @@ def dump_kg(result, adjs, outdir, graph_distance, visualize_type=None):
                 f.write("%d,%s\n" % (n, repr(float(norm[n]))))
         files.append((ef, nf))
     return files
+
+
+# -------------------------------------------------------------------------------------------------
+# the compound-protein interaction multitask network (sample_chem/compound-protein_interaction/multitask.py:35-51, run_viz.sh
+# block name=mt): kgcn/visualization.py:187-286 and :442-574, fused over the scaled copies (csrc/cpiig.hip)
+# -------------------------------------------------------------------------------------------------
+CPI_IG_MODALS = ("features", "adjs")
+CPI_IG_FULL_BYTES = 256 << 20         # default bound of one sweep's G tensors [C, T, N, Wd] (one or two of them)
+CPI_IG_DENSE_ROWS = 1023              # rows of one dense call of the fused route: below the dense op's 1,024-row table routes
+
+
+def cpi_ig_coefficients(modal, method, divide_number=100):
+    """The per-copy coefficients of the fused route for one modal set and method -> dict:
+      targets        the inputs that are scaled and attributed: ('features', 'adjs') for 'all', else the one named
+      scales, weights  ig_scales(method, divide_number): s_k and w_k, K = len(scales) copies
+      alpha, gamma   copy k's pre-activation is alpha[k] P + gamma[k] Q: alpha = a c, gamma = c with a = s where the features
+                     are a target (else 1) and c = s where the adjacency values are (else 1; kgcn/feed.py:116-121 scales the
+                     values of EVERY channel)
+      wA, wB         the copy weights of the two G tensors of ops.cpi_ig (wB None: one tensor): G^A = sum_k w_k beta_k G_k with
+                     beta = c for the features and beta = a for the Y0 term of the adjacency values -- for 'all' both are s,
+                     for a single modal both are 1 -- and G^B = sum_k w_k G_k, the bias term of the adjacency values, which
+                     is G^A itself unless both modals are targets
+      bias_from      'A' or 'B': the tensor that carries that bias term.
+    Refused: 'embedded_layer' (the network has none) and the smooth methods (per-element noise leaves the two-parameter family
+    alpha P + gamma Q)."""
+    if modal == "all":
+        targets = CPI_IG_MODALS
+    elif modal in CPI_IG_MODALS:
+        targets = (modal,)
+    else:
+        raise ValueError("modal must be 'all', 'features' or 'adjs' for the compound-protein interaction network, got %r" % (modal,))
+    if method in SMOOTH_METHODS:
+        raise ValueError("method %r adds per-element noise: the scaled copies are no longer alpha P + gamma Q (use "
+                         "integrated_gradients, the per-step loop)" % (method,))
+    scales, weights = ig_scales(method, divide_number)
+    both = len(targets) == 2
+    a = list(scales) if "features" in targets else [1.0] * len(scales)
+    c = list(scales) if "adjs" in targets else [1.0] * len(scales)
+    return {"targets": targets, "scales": list(scales), "weights": list(weights),
+            "alpha": [ak * ck for ak, ck in zip(a, c)], "gamma": c,
+            "wA": [w * s for w, s in zip(weights, scales)] if both else list(weights),
+            "wB": list(weights) if both else None, "bias_from": "B" if both else "A"}
+
+
+def cpi_dump_record(result):
+    """The dict CompoundVisualizer.dump writes (:133-160) for one result of cpi_integrated_gradients."""
+    return {k: v for k, v in result.items() if k not in ("compound_id", "task", "assay", "start_score", "end_score")}
+
+
+def _cpi_dense(x2d, w, rows_per_graph):
+    """x2d @ w through ops.dense in slices of whole compounds of at most CPI_IG_DENSE_ROWS rows: every compound takes the same
+    GEMM kernel however many share the chunk (the dense op picks another kernel from 1,024 rows on), so that chunking leaves
+    the bits alone."""
+    from . import ops
+    m = x2d.shape[0]
+    per = max(1, CPI_IG_DENSE_ROWS // int(rows_per_graph)) * int(rows_per_graph)
+    if m <= per:
+        return ops.dense(x2d, w)
+    return torch.cat([ops.dense(x2d[i:i + per], w) for i in range(0, m, per)])
+
+
+def _cpi_fused_chunk(dataset, part, par, coef, method):
+    """The fused route for the compounds `part` and the tasks of par['u'] -> {features [C, T, N, F], adjs / adjs_data, start, end}."""
+    import numpy as np
+    from . import ops
+    targets = coef["targets"]
+    adj, x = dataset.batch(part)
+    C, N, F = x.shape
+    W, b, u, e = par["W"], par["b"], par["u"], par["e"]
+    Wd, Tn = W[0].shape[1], u.shape[0]
+    x2d = x.reshape(C * N, F)
+    ones = torch.ones((C * N, 4), device=x.device, dtype=torch.float32)
+    P = Q = Y0 = None
+    for ch, csr in enumerate(adj.channels):                  # the two aggregated products, once per compound
+        y = _cpi_dense(x2d, W[ch], N)
+        Y0 = y if ch == 0 else Y0
+        pc = ops.bspmm(csr, y)
+        qc = ops.bspmm(csr, ones)[:, :1] * b[ch].view(1, Wd)
+        P, Q = (pc, qc) if P is None else (P + pc, Q + qc)
+    p, GA, GB = ops.cpi_ig(P.view(C, N, Wd), Q.view(C, N, Wd), u, e, coef["alpha"], coef["gamma"], coef["wA"], coef["wB"])
+    # the contraction: one ordinary GraphConv backward per (compound, task) -- the adjacency of every compound batched T times
+    rows = np.repeat(np.asarray(part, np.int64), Tn)
+    g2d = GA.view(C * Tn * N, Wd)
+    raw = method == "grad"
+    out = {"start": p[:, 0, :], "end": p[:, -1, :], "features_data": x}
+    chT = [c.gather(rows) for c in (dataset.channels if "features" in targets else dataset.channels[:1])]
+    if "features" in targets:
+        dx = None
+        for ch, csr in enumerate(chT):
+            d = _cpi_dense(ops.bspmm(csr.transpose(), g2d), par["Wt"][ch], N)
+            dx = d if dx is None else dx + d
+        dx = dx.view(C, Tn, N, F)
+        out["features"] = dx if raw else dx * x.view(C, 1, N, F)
+    if "adjs" in targets:
+        csr0 = chT[0]
+        y0 = Y0.view(C, 1, N, Wd).expand(C, Tn, N, Wd).reshape(C * Tn * N, Wd)
+        gb = g2d if coef["bias_from"] == "A" else GB.view(C * Tn * N, Wd)
+        dv = ops.spmm_values_grad(csr0, g2d, y0) + ops.spmm_values_grad(csr0, gb, b[0].reshape(-1), rhs_ld=0, rhs_gs=0)
+        out["adjs"] = values_to_dense(csr0, dv if raw else dv * csr0.values).view(C, Tn, N, N)
+        out["adjs_data"] = values_to_dense(adj.channels[0], adj.channels[0].values)
+    return out
+
+
+def _cpi_composed_chunk(model, dataset, part, tasks, coef, method):
+    """The composed route: the copies of every compound as batch rows of one forward through the model, one autograd backward
+    per task, the copies summed in order -> what _cpi_fused_chunk returns."""
+    targets, scales, weights = coef["targets"], coef["scales"], coef["weights"]
+    C, rep = len(part), len(scales)
+    adj, x = dataset.batch([i for i in part for _ in range(rep)])
+    N, F = x.shape[1], x.shape[2]
+    dev = x.device
+    sc = torch.tensor(scales, dtype=torch.float32, device=dev).repeat(C)
+    wv = torch.tensor(weights, dtype=torch.float32, device=dev).repeat(C).view(C, rep, 1, 1)
+    x_in = (x * sc.view(-1, 1, 1) if "features" in targets else x.clone()).requires_grad_("features" in targets)
+    adj_in, v0 = adj, None
+    if "adjs" in targets:                                    # kgcn/feed.py:116-121: the values of every channel are scaled
+        vals = [c.values * sc[_entry_graphs(c)] for c in adj.channels]
+        v0 = vals[0].requires_grad_(True)
+        adj_in = adj.with_values(vals)
+    p1 = torch.softmax(model(x_in, adj_in), dim=1)[:, 1, :]                       # prediction[:, t, 0] of every task
+    wrt = ([x_in] if "features" in targets else []) + ([v0] if v0 is not None else [])
+    raw = method == "grad"
+    s = p1.detach().view(C, rep, -1)[:, :, tasks]
+    out = {"start": s[:, 0, :], "end": s[:, -1, :], "features_data": x.view(C, rep, N, F)[:, 0]}
+    feats, adjs = [], []
+    c0 = adj.channels[0]
+    for j, t in enumerate(tasks):
+        grads = list(torch.autograd.grad(p1[:, t].sum(), wrt, retain_graph=j + 1 < len(tasks)))
+        if "features" in targets:
+            feats.append((grads.pop(0).view(C, rep, N, F) * wv).sum(1))
+        if "adjs" in targets:
+            adjs.append((values_to_dense(c0, grads.pop(0)).view(C, rep, N, N) * wv).sum(1))
+    if "features" in targets:
+        ig = torch.stack(feats, 1)
+        out["features"] = ig if raw else ig * x.view(C, rep, N, F)[:, :1]
+    if "adjs" in targets:
+        data = values_to_dense(c0, c0.values).view(C, rep, N, N)[:, 0]
+        ig = torch.stack(adjs, 1)
+        out["adjs"] = ig if raw else ig * data.unsqueeze(1)
+        out["adjs_data"] = data
+    return out
+
+
+def cpi_integrated_gradients(model, features, adjacency, labels=None, divide_number=100, modal="all", method="ig",
+                             label_target="max", tasks=None, compounds=None, chunk=None, fused=True):
+    """`kgcn visualize` of the compound-protein interaction sample (run_viz.sh, block name=mt) for a models.CPIMultitaskNet: integrated
+    gradients of every task's prediction[:, t, 0] -- the two-way softmax's second entry, sigmoid(h . u_t + e_t) -- with respect to
+    the node features and / or the values of adjacency channel 0 -> one dict per (compound, task) with the reference's dump keys:
+    features / features_IG [N, F], adjs / adjs_IG [N, N] (channel 0, dense) for the modals named by `modal` ('all', 'features',
+    'adjs'), check_score (end - start), sum_of_IG, prediction_score, target_label, true_label, mol / mol_smiles / mol_id (None: no
+    RDKit) -- plus compound_id, task, assay, start_score and end_score (the prediction of the first and the last copy;
+    cpi_dump_record drops the five; ig_filename(..., task=t) uses the first three).
+
+    features [G, N, F] and adjacency (the channels of data_util.build_adjs), or a data_util.DeviceGraphDataset as `adjacency`
+    (features None); labels [G, T] (needed by label_target 'label', 'correct', 'uncorrect'): the true label of task t is
+    labels[cid, t] for T > 1, argmax(labels[cid]) for one task.  The target comes from an unscaled forward pass through
+    select_label_target on the one-entry prediction [p1] (:497-529), so label_target 'label' with label 1 indexes outside it and
+    raises, as it would in the reference.  tasks: the tasks to visualise (default all); compounds: dataset indices (default all).
+    method 'ig', 'grad_prod' or 'grad' (ig_scales).
+
+    fused=True: the network is one GraphConv, a sigmoid, a sum and one Dense, so copy k's pre-activation is
+    alpha_k P + gamma_k Q (cpi_ig_coefficients): P, Q and Y0 = X W_0 are formed once per compound by the dense and SpMM ops,
+    ops.cpi_ig sweeps the copies, and the sums it returns go through ONE GraphConv input gradient (A^T G W^T) and SpMM values
+    gradient per (compound, task).  Compounds run `chunk` at a time (default: as many as keep the G tensors under
+    CPI_IG_FULL_BYTES); chunking does not change a bit of any compound's rows.
+    fused=False: the copies run as batch rows through the model itself with one autograd backward per task (`chunk` defaults to
+    IG_ROWS_PER_CHUNK // copies).
+
+    Unlike the reference, every (compound, task) differentiates its OWN prediction: the reference builds its gradient graph for
+    the first visualised compound and task and reuses it (tf_grads, :466 and :555)."""
+    import numpy as np
+    from . import models
+    from .data_util import DeviceGraphDataset
+    if not isinstance(model, models.CPIMultitaskNet):
+        raise TypeError("cpi_integrated_gradients needs a models.CPIMultitaskNet (the closed form is that network's), got %s"
+                        % type(model).__name__)
+    coef = cpi_ig_coefficients(modal, method, divide_number)
+    targets = coef["targets"]
+    if isinstance(adjacency, DeviceGraphDataset):
+        dataset = adjacency
+    else:
+        dev = next(model.parameters(), torch.zeros(0, device="cuda")).device
+        dataset = DeviceGraphDataset(adjacency, features.detach().cpu().numpy() if torch.is_tensor(features) else features, device=dev)
+    if dataset.features is None:
+        raise ValueError("the dataset carries no node features")
+    G, T = dataset.num_graphs, model.label_dim
+    ids = list(range(G)) if compounds is None else [int(i) for i in compounds]
+    tasks = list(range(T)) if tasks is None else [int(t) for t in np.atleast_1d(tasks)]
+    if not tasks or min(tasks) < 0 or max(tasks) >= T:
+        raise ValueError("tasks must name some of the network's %d tasks" % T)
+    lab = None if labels is None else np.asarray(labels.detach().cpu().numpy() if torch.is_tensor(labels) else labels)
+    N, rep = dataset.features.shape[1], len(coef["scales"])
+    Wd = model.conv.output_dim
+    if chunk is None:
+        chunk = max(1, CPI_IG_FULL_BYTES // (4 * len(tasks) * N * Wd * (1 if coef["wB"] is None else 2))) if fused \
+            else max(1, IG_ROWS_PER_CHUNK // rep)
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError("chunk must be >= 1")
+    # the unscaled pass: the prediction the target is read from (:479-485); it also builds a freshly made model
+    preds = []
+    with torch.no_grad():
+        step = max(1, IG_ROWS_PER_CHUNK // 8)
+        for i in range(0, len(ids), step):
+            adj, x = dataset.batch(ids[i:i + step])
+            preds.append(torch.softmax(model(x, adj), dim=1)[:, 1, :].cpu().numpy())
+    preds = np.concatenate(preds) if preds else np.zeros((0, T), np.float32)
+    jobs = []
+    for j, cid in enumerate(ids):
+        for t in tasks:
+            true_label = None if lab is None else int(lab[cid, t]) if T > 1 else int(np.argmax(lab[cid]))
+            sel = select_label_target(preds[j, t:t + 1], label_target, true_label)
+            if sel is not None:
+                jobs.append((cid, t, preds[j, t:t + 1], true_label, sel[0], sel[1]))
+    wanted = sorted({j[0] for j in jobs}, key=ids.index)
+    frozen = [(p, p.requires_grad) for p in model.parameters()]
+    res = {}
+    try:
+        for p, _ in frozen:
+            p.requires_grad_(False)
+        if fused and wanted:
+            V, c = model.out.kernel.detach(), model.out.bias.detach()
+            ts = torch.as_tensor(tasks, device=V.device)
+            par = {"W": [w.detach().contiguous() for w in model.conv.w], "b": [b.detach().reshape(-1) for b in model.conv.bias],
+                   "u": (V[:, T:] - V[:, :T]).t()[ts].contiguous(), "e": (c[T:] - c[:T])[ts].contiguous()}
+            par["Wt"] = [w.t().contiguous() for w in par["W"]]
+        for i in range(0, len(wanted), chunk):
+            part = wanted[i:i + chunk]
+            with torch.set_grad_enabled(not fused):
+                out = _cpi_fused_chunk(dataset, part, par, coef, method) if fused else \
+                    _cpi_composed_chunk(model, dataset, part, tasks, coef, method)
+            host = {m: v.detach().cpu().numpy() for m, v in out.items()}
+            # sum_of_IG of every (compound, task) at once: the fp64 sum of the record's own arrays, one modal after the other
+            host["total"] = sum(host[m].astype(np.float64).reshape(len(part), len(tasks), -1).sum(-1) for m in targets)
+            for k, cid in enumerate(part):
+                res[cid] = {m: v[k] for m, v in host.items()}
+    finally:
+        for p, r in frozen:
+            p.requires_grad_(r)
+    results = []
+    for cid, t, pred, true_label, tidx, tscore in jobs:
+        r, k = res[cid], tasks.index(t)
+        rec = {"compound_id": cid, "task": t, "assay": assay_string(pred, tidx)}
+        for m in targets:
+            rec[m] = r["features_data"] if m == "features" else r["adjs_data"]
+            rec[m + "_IG"] = r[m][k]
+        rec["start_score"], rec["end_score"] = float(r["start"][k]), float(r["end"][k])
+        rec["check_score"] = rec["end_score"] - rec["start_score"]
+        rec["sum_of_IG"] = float(r["total"][k])
+        rec.update({"mol": None, "mol_smiles": None, "mol_id": None, "prediction_score": tscore, "target_label": tidx,
+                    "true_label": true_label})
+        results.append(rec)
+    return results
