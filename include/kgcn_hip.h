@@ -635,7 +635,9 @@ int kgcn_loss_grad_f32(const float* dlogits, const float* g_opt, const float* g_
 int kgcn_adam_tf_f32(float* params, const float* grads, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                      float eps, int64_t* step_counter, void* stream);
 /* The same update without a packed gradient buffer: segment q covers `numel` floats at `offset` of params / m / v and reads its
- * gradient from `grad` (the tensor the backward pass produced for that parameter); floats outside the segments are untouched. */
+ * gradient from `grad` (the tensor the backward pass produced for that parameter); floats outside the segments are untouched.
+ * More than KGCN_ADAM_MAX_SEGMENTS segments take several launches; ALL segments are checked before the first one, so a refused
+ * list leaves params, m, v and the counter as they were. */
 #define KGCN_ADAM_MAX_SEGMENTS 32
 typedef struct kgcn_adam_segment {
   const float* grad;
@@ -748,7 +750,9 @@ int kgcn_spmm_route_query(const kgcn_csr_batch* a_ch, int32_t num_channels, int3
 /* Several strided 2-D fp32 copies in ONE launch: dst[r * dst_ld + c] = src[r * src_ld + c] for r < rows, c < cols of every job.
  * Used for the operand of a multi-channel GraphConv's single GEMM, [W_0 | W_1 | ...] and [b_0 | b_1 | ...] (kgcn/layers.py:68-78
  * builds one MatMul per channel; one GEMM over the concatenated kernels produces the same FW[b][ch] blocks side by side), and for
- * the split of that operand's gradient into one contiguous tensor per parameter. */
+ * the split of that operand's gradient into one contiguous tensor per parameter.  Jobs without rows or columns are legal (their
+ * pointers may be NULL); more than KGCN_COPY2D_MAX_JOBS jobs take several launches, and ALL jobs are checked (rows, cols >= 0,
+ * both leading dimensions >= cols) before the first one: a refused list has copied nothing. */
 #define KGCN_COPY2D_MAX_JOBS 16
 typedef struct kgcn_copy2d_job {
   const float* src;

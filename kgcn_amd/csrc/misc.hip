@@ -200,16 +200,20 @@ using namespace kgcn;
 
 extern "C" int kgcn_copy2d_multi_f32(const kgcn_copy2d_job* jobs, int32_t num_jobs, void* stream) {
   if (num_jobs < 0 || (num_jobs > 0 && !jobs)) return fail("kgcn_copy2d_multi_f32: bad job list");
+  // every job is checked before the FIRST launch: a bad job behind the 16th must not leave the jobs in front of it copied
+  for (int q = 0; q < num_jobs; ++q) {
+    const kgcn_copy2d_job& j = jobs[q];
+    if (j.rows < 0 || j.cols < 0 || j.src_ld < j.cols || j.dst_ld < j.cols)
+      return fail("kgcn_copy2d_multi_f32: job %d: rows=%lld cols=%lld src_ld=%lld dst_ld=%lld", q, (long long)j.rows,
+                  (long long)j.cols, (long long)j.src_ld, (long long)j.dst_ld);
+    if (j.rows * j.cols > 0 && (!j.src || !j.dst)) return fail("kgcn_copy2d_multi_f32: job %d: NULL operand", q);
+  }
   for (int base = 0; base < num_jobs; base += KGCN_COPY2D_MAX_JOBS) {
     const int n = num_jobs - base < KGCN_COPY2D_MAX_JOBS ? num_jobs - base : KGCN_COPY2D_MAX_JOBS;
     Copy2dJobs jb{};
     long most = 0;
     for (int q = 0; q < n; ++q) {
       const kgcn_copy2d_job& j = jobs[base + q];
-      if (j.rows < 0 || j.cols < 0 || j.src_ld < j.cols || j.dst_ld < j.cols)
-        return fail("kgcn_copy2d_multi_f32: job %d: rows=%lld cols=%lld src_ld=%lld dst_ld=%lld", base + q, (long long)j.rows,
-                    (long long)j.cols, (long long)j.src_ld, (long long)j.dst_ld);
-      if (j.rows * j.cols > 0 && (!j.src || !j.dst)) return fail("kgcn_copy2d_multi_f32: job %d: NULL operand", base + q);
       jb.src[q] = j.src; jb.dst[q] = j.dst; jb.rows[q] = (long)j.rows; jb.cols[q] = (long)j.cols;
       jb.src_ld[q] = (long)j.src_ld; jb.dst_ld[q] = (long)j.dst_ld;
       if (j.rows * j.cols > most) most = (long)(j.rows * j.cols);
