@@ -1,11 +1,16 @@
-"""ctypes binding of libkgcn_hip.so (the C ABI declared in include/kgcn_hip.h).
+"""ctypes binding of libkgcn_hip.so, derived at import from the C ABI's own text, include/kgcn_hip.h.
 
-There is no CPU fallback: if the shared library is missing or lacks a symbol, importing this
-module raises.  PyTorch is used only for device memory and streams; every call passes raw device
-pointers and the current HIP stream.
+The header is the only place an entry point, a structure or a limit is written down: parse_header() turns its prototypes
+into SIGNATURES, its structures into the ctypes.Structure classes below and its #define / enum values into K.  A new entry
+point is added to the header and the library, and nothing here.
+
+There is no CPU fallback: if the header or the shared library is missing, or the library lacks a symbol, importing this
+module raises.  PyTorch is used only for device memory and streams; every call passes raw device pointers and the current
+HIP stream.
 """
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # Development overrides.  KGCN_HIP_LIB: load another build of the library (tools/variant_bench.py times alternative builds).
@@ -15,6 +20,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # variable changes summation order / which binary produced the numbers.
 DEV_ENV_VARS = ("KGCN_HIP_LIB", "KGCN_GIN_JOIN", "KGCN_GIN_DOT")
 LIB_PATH = os.environ.get("KGCN_HIP_LIB") or os.path.join(_HERE, "csrc", "libkgcn_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "kgcn_hip.h")
 
 
 def active_overrides():
@@ -27,349 +33,195 @@ if active_overrides():
     warnings.warn("kgcn_amd: development overrides active: %r (KGCN_HIP_LIB swaps the native library, the others "
                   "change kernel routing)" % (active_overrides(),), RuntimeWarning, stacklevel=2)
 
-c_f32p = ctypes.c_void_p
-c_i32p = ctypes.c_void_p
-c_i64 = ctypes.c_int64
-c_i32 = ctypes.c_int32
+
+# -- the header's grammar ---------------------------------------------------------------------------
+# parse_header accepts what include/kgcn_hip.h uses and nothing wider; text it does not understand raises a ValueError
+# that quotes it, so a declaration is never skipped silently.
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32,
+            "uint64_t": ctypes.c_uint64, "float": ctypes.c_float}
+_FIELD_SCALARS = ("int32_t", "int64_t", "float")
+_POINTEES = tuple(_SCALARS) + ("void", "char", "uint8_t", "double")      # what an untyped pointer may point to
+# Structures an entry point takes by typed pointer (ctypes then checks what a caller passes).  Pointers to the other
+# structures stay untyped like every pointer to plain data: their callers hand over job arrays or raw addresses.
+_TYPED_POINTERS = ("kgcn_csr_batch", "kgcn_stack_layer", "kgcn_assemble_plan", "kgcn_spmm_route")
+_PREAMBLE = re.compile(r'\s*#ifndef (\w+)\n#define \1\n\s*#include <stdint\.h>\n\s*#ifdef __cplusplus\nextern "C" \{\n#endif\n')
+_EPILOGUE = "#ifdef __cplusplus\n}\n#endif\n#endif"
+_DEFINE = re.compile(r"#define[ \t]+(\w+)[ \t]*([^\n]*)\n\s*")
+_ENUM = re.compile(r"enum\s*\{([^{}]*)\}\s*;\s*")
+_STRUCT = re.compile(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*(\w+)\s*;\s*")
+_PROTOTYPE = re.compile(r"([\w\s*]+?)\b(kgcn_\w+)\s*\(([^(){};]*)\)\s*;\s*")
+_EXPR_TOKEN = re.compile(r"\s*(?:(0[xX][0-9a-fA-F]+|\d+)(?:[uU]?(?:ll|LL)?)(?!\w)|(<<|[()])|([A-Za-z_]\w*))")
+_DECLARATOR = re.compile(r"(\**)\s*(\w+)\s*(?:\[\s*(\w+)\s*\])?$")
 
 
-# KGCN_HIP_ABI_VERSION this binding was written against (include/kgcn_hip.h); the library must report the same
-ABI_VERSION = 2
+def _integer(expr, constants):
+    """Value of a constant expression: decimal or hex literals (u / ll / ull suffix), <<, parentheses, earlier constants."""
+    tokens, pos = [], 0
+    while expr[pos:].strip():
+        m = _EXPR_TOKEN.match(expr, pos)
+        if not m:
+            raise ValueError("kgcn_hip.h: %r is not an integer expression" % expr)
+        lit, op, name = m.groups()
+        if name is not None and name not in constants:
+            raise ValueError("kgcn_hip.h: %r names %r, which is no earlier constant" % (expr, name))
+        tokens.append(int(lit, 0) if lit is not None else op if op is not None else constants[name])
+        pos = m.end()
+
+    def shifts():
+        v = atom()
+        while tokens and tokens[0] == "<<":
+            tokens.pop(0)
+            v <<= atom()
+        return v
+
+    def atom():
+        if not tokens or tokens[0] in ("<<", ")"):
+            raise ValueError("kgcn_hip.h: %r is not an integer expression" % expr)
+        t = tokens.pop(0)
+        if t != "(":
+            return t
+        v = shifts()
+        if not tokens or tokens.pop(0) != ")":
+            raise ValueError("kgcn_hip.h: unbalanced parentheses in %r" % expr)
+        return v
+
+    v = shifts()
+    if tokens:
+        raise ValueError("kgcn_hip.h: %r is not an integer expression" % expr)
+    return v
 
 
-class CsrBatch(ctypes.Structure):
-    """struct kgcn_csr_batch (include/kgcn_hip.h)."""
-    _fields_ = [
-        ("num_graphs", c_i32),
-        ("rows", c_i32),
-        ("cols", c_i32),
-        ("max_nnz_per_graph", c_i32),
-        ("row_pad", c_i32),
-        ("reserved_", c_i32),
-        ("nnz", c_i64),
-        ("rowptr", ctypes.c_void_p),
-        ("cv", ctypes.c_void_p),
-        ("slots", ctypes.c_void_p),
-        ("graph_ptr", ctypes.c_void_p),
-        ("block_ptr", ctypes.c_void_p),
-        ("num_blocks", c_i32),
-        ("block_rows_max", c_i32),
-    ]
+def _pointer(base, stars, structs, what):
+    if base not in _POINTEES and base not in structs:
+        raise ValueError("kgcn_hip.h: unknown type %r in %r" % (base, what))
+    return ctypes.POINTER(ctypes.c_void_p) if stars == 2 else ctypes.c_void_p
 
 
-_CSRP = ctypes.POINTER(CsrBatch)
+def _struct(c_name, body, structs, constants):
+    fields = []
+    for stmt in filter(None, (s.strip() for s in body.split(";"))):
+        m = re.match(r"(\w+)\b\s*(.+)$", re.sub(r"\bconst\b", " ", stmt).strip(), flags=re.S)
+        if not m:
+            raise ValueError("kgcn_hip.h: cannot type the field %r of %s" % (stmt, c_name))
+        base = m.group(1)
+        for decl in m.group(2).split(","):
+            m = _DECLARATOR.match(decl.strip())
+            if not m:
+                raise ValueError("kgcn_hip.h: cannot type the field %r of %s" % (stmt, c_name))
+            stars, name, extent = len(m.group(1)), m.group(2), m.group(3)
+            if stars == 0 and base in _FIELD_SCALARS:
+                ctype = _SCALARS[base]
+            elif stars == 1 and base in structs:
+                ctype = ctypes.POINTER(structs[base])
+            elif stars == 1:
+                ctype = _pointer(base, 1, structs, stmt)
+            else:
+                raise ValueError("kgcn_hip.h: cannot type the field %r of %s" % (stmt, c_name))
+            fields.append((name, ctype if extent is None else ctype * _integer(extent, constants)))
+    cls_name = "".join(w.capitalize() for w in c_name[len("kgcn_"):].split("_"))
+    return type(cls_name, (ctypes.Structure,), {"_fields_": fields, "__doc__": "struct %s (include/kgcn_hip.h)." % c_name})
 
 
-class StackLayer(ctypes.Structure):
-    """struct kgcn_stack_layer (include/kgcn_hip.h)."""
-    _fields_ = [("kind", c_i32), ("act", c_i32), ("din", c_i32), ("dout", c_i32), ("w", ctypes.c_void_p),
-                ("b", ctypes.c_void_p), ("mean", ctypes.c_void_p), ("var", ctypes.c_void_p), ("eps", ctypes.c_float),
-                ("route", c_i32)]
+def _prototype(restype, name, params, structs):
+    what = "%s %s(%s)" % (restype.strip(), name, " ".join(params.split()))
+    restype, params = (re.sub(r"\bconst\b", " ", s).replace("*", " * ") for s in (restype, params))
+
+    def ctype(text, is_return):
+        words = text.split()
+        stars = words.count("*")
+        words = [w for w in words if w != "*"]
+        if len(words) != (1 if is_return else 2) or stars > 2:
+            raise ValueError("kgcn_hip.h: cannot type %r in %r" % (text.strip(), what))
+        base = words[0]
+        if stars == 0:
+            if base not in _SCALARS:
+                raise ValueError("kgcn_hip.h: unknown type %r in %r" % (base, what))
+            return _SCALARS[base]
+        if is_return:
+            if (base, stars) != ("char", 1):
+                raise ValueError("kgcn_hip.h: unknown return type %r in %r" % (text.strip(), what))
+            return ctypes.c_char_p
+        if stars == 1 and base in _TYPED_POINTERS and base in structs:
+            return ctypes.POINTER(structs[base])
+        return _pointer(base, stars, structs, what)
+
+    args = [] if params.strip() == "void" else [ctype(p, False) for p in params.split(",")]
+    return ctype(restype, True), args
 
 
-_STKP = ctypes.POINTER(StackLayer)
+def parse_header(text):
+    """The text of include/kgcn_hip.h -> (functions, structs, constants):
+      functions  name -> (restype, [argtypes]) of every prototype: scalars by name; one * to a structure of _TYPED_POINTERS
+                 is a POINTER to its class, two * are POINTER(c_void_p), every other pointer is c_void_p, and a
+                 `const char*` return is c_char_p
+      structs    C name -> ctypes.Structure class (kgcn_csr_batch -> CsrBatch) with the header's fields in the header's order
+      constants  name -> int for every `#define KGCN_*` and every enumerator
+    Pure: reads no file and touches no library."""
+    functions, structs, constants = {}, {}, {}
 
-class AdamSegment(ctypes.Structure):
-    """struct kgcn_adam_segment (include/kgcn_hip.h)."""
-    _fields_ = [("grad", ctypes.c_void_p), ("offset", c_i64), ("numel", c_i64)]
+    def constant(name, value, what):
+        if not name.startswith("KGCN_") or name in constants or not value:
+            raise ValueError("kgcn_hip.h: unexpected or repeated name, or no value, in %r" % what)
+        constants[name] = _integer(value, constants)
+
+    def define(m):
+        constant(m.group(1), m.group(2), m.group(0).strip())
+
+    def enum(m):
+        for item in filter(None, (s.strip() for s in m.group(1).split(","))):
+            name, _, value = (s.strip() for s in item.partition("="))
+            constant(name, value, item)
+
+    def struct(m):
+        if m.group(1) != m.group(3) or m.group(1) in structs or not m.group(1).startswith("kgcn_"):
+            raise ValueError("kgcn_hip.h: unexpected or repeated structure name in %r" % " ".join(m.group(0).split()))
+        structs[m.group(1)] = _struct(m.group(1), m.group(2), structs, constants)
+
+    def prototype(m):
+        if m.group(2) in functions:
+            raise ValueError("kgcn_hip.h: %s is declared twice" % m.group(2))
+        functions[m.group(2)] = _prototype(m.group(1), m.group(2), m.group(3), structs)
+
+    text = re.sub(r"/\*.*?\*/", lambda c: " " + "\n" * c.group(0).count("\n"), text, flags=re.S)   # a comment ends no line early
+    text = "\n".join(line.rstrip() for line in text.split("\n")).rstrip()
+    head = _PREAMBLE.match(text)
+    if not head or not text.endswith(_EPILOGUE):
+        raise ValueError("kgcn_hip.h: include guard / extern \"C\" frame not found")
+    body, pos = text[head.end():-len(_EPILOGUE)].strip() + "\n", 0
+    while pos < len(body):
+        for pattern, read in ((_DEFINE, define), (_ENUM, enum), (_STRUCT, struct), (_PROTOTYPE, prototype)):
+            m = pattern.match(body, pos)
+            if m:
+                read(m)
+                pos = m.end()
+                break
+        else:
+            raise ValueError("kgcn_hip.h: cannot read %r" % " ".join(body[pos:body.find(";", pos) + 1 or pos + 120].split()))
+    return functions, structs, constants
 
 
-class Copy2dJob(ctypes.Structure):
-    """struct kgcn_copy2d_job (include/kgcn_hip.h)."""
-    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("rows", c_i64), ("cols", c_i64), ("src_ld", c_i64), ("dst_ld", c_i64)]
+def _read_header():
+    try:
+        with open(HEADER_PATH) as f:
+            return f.read()
+    except OSError as e:
+        raise ImportError("kgcn_amd: the C header %s is missing (%s); the binding is derived from it" % (HEADER_PATH, e)) from e
 
 
-class WtableJob(ctypes.Structure):
-    """struct kgcn_wtable_job (include/kgcn_hip.h)."""
-    _fields_ = [("w", ctypes.c_void_p), ("w_ld", c_i64), ("trans_w", c_i32), ("k", c_i32), ("n", c_i32), ("k_w", c_i32),
-                ("table", ctypes.c_void_p), ("extra_row", ctypes.c_void_p)]
+# name -> (restype, argtypes) of every function the header declares; C structure name -> class; K: every constant by name
+SIGNATURES, _STRUCTS, K = parse_header(_read_header())
 
-
-ASSEMBLE_MAX_CSR, ASSEMBLE_MAX_TABLES = 4, 6
-
-
-class AssemblePlan(ctypes.Structure):
-    """struct kgcn_assemble_plan (include/kgcn_hip.h)."""
-    _fields_ = [("num_csr", c_i32), ("num_tables", c_i32),
-                ("src", _CSRP * ASSEMBLE_MAX_CSR),
-                ("dst_rowptr", ctypes.c_void_p * ASSEMBLE_MAX_CSR), ("dst_cv", ctypes.c_void_p * ASSEMBLE_MAX_CSR),
-                ("dst_cv_capacity", c_i64 * ASSEMBLE_MAX_CSR), ("dst_slots", ctypes.c_void_p * ASSEMBLE_MAX_CSR),
-                ("dst_graph_ptr", ctypes.c_void_p * ASSEMBLE_MAX_CSR),
-                ("table", ctypes.c_void_p * ASSEMBLE_MAX_TABLES), ("table_out", ctypes.c_void_p * ASSEMBLE_MAX_TABLES),
-                ("row_floats", c_i64 * ASSEMBLE_MAX_TABLES)]
-
-
-class SpmmRoute(ctypes.Structure):
-    """struct kgcn_spmm_route (include/kgcn_hip.h): the answer of kgcn_spmm_route_query."""
-    _fields_ = [("kernel", c_i32), ("template_args", c_i32 * 4), ("ds", c_i32), ("slices", c_i32), ("workgroup", c_i32),
-                ("grid", c_i64), ("lds_bytes", c_i64)]
-
-
-# KGCN_SPMM_* kernel codes (the kernels of csrc/spmm.hip without their _kernel suffix) and call flags
+CsrBatch, AssemblePlan, WtableJob, AdamSegment, StackLayer, SpmmRoute, Copy2dJob = (_STRUCTS[s] for s in (
+    "kgcn_csr_batch", "kgcn_assemble_plan", "kgcn_wtable_job", "kgcn_adam_segment", "kgcn_stack_layer", "kgcn_spmm_route",
+    "kgcn_copy2d_job"))
+# the library must report the same version and the same sizeof(kgcn_csr_batch) as the header this binding was read from
+ABI_VERSION = K["KGCN_HIP_ABI_VERSION"]
+ASSEMBLE_MAX_CSR, ASSEMBLE_MAX_TABLES = K["KGCN_ASSEMBLE_MAX_CSR"], K["KGCN_ASSEMBLE_MAX_TABLES"]
+# kgcn_spmm_route.kernel (the KGCN_SPMM_* enumerators) -> the kernel of csrc/spmm.hip without its _kernel suffix; call flags
 SPMM_KERNELS = ("none", "spmm_tile", "spmm_tile_dot", "spmm_slices", "spmm_block", "spmm_rows", "spmm_gather", "bconv_loop",
                 "bconv_fanout")
-SPMM_DACT, SPMM_SELF_SCALE, SPMM_DOT, SPMM_FANOUT = 1, 2, 4, 8
-
-_ASMP = ctypes.POINTER(AssemblePlan)
-_PTRP = ctypes.POINTER(ctypes.c_void_p)
-
-# name -> (restype, argtypes); must list EVERY function include/kgcn_hip.h declares
-# (tests/test_abi.py parses the header and compares).
-SIGNATURES = {
-    "kgcn_abi_version": (ctypes.c_int, []),
-    "kgcn_csr_batch_size": (c_i64, []),
-    "kgcn_last_error": (ctypes.c_char_p, []),
-    "kgcn_build_arch": (ctypes.c_char_p, []),
-    "kgcn_bspmm_f32": (ctypes.c_int, [_CSRP, c_f32p, c_i64, c_i64, c_i32, c_f32p, c_i64, c_i64,
-                                      ctypes.c_float, ctypes.c_void_p]),
-    "kgcn_bconv_f32": (ctypes.c_int, [_CSRP, c_i32, c_f32p, c_i64, c_i64, c_i64, c_i32, c_f32p,
-                                      c_i64, c_i64, ctypes.c_void_p]),
-    "kgcn_spmm_values_grad_f32": (ctypes.c_int, [_CSRP, c_f32p, c_i64, c_i64, c_f32p, c_i64,
-                                                 c_i64, c_i32, c_f32p, ctypes.c_void_p]),
-    "kgcn_dense_fwd_f32": (ctypes.c_int, [c_f32p, c_i64, c_i32, c_i64, c_f32p, c_i64, c_i32,
-                                          c_f32p, c_f32p, c_i32, c_i64, ctypes.c_void_p]),
-    "kgcn_dense_wgrad_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32]),
-    "kgcn_dense_bwd_supported": (ctypes.c_int, [c_i64, c_i32, c_i32]),
-    "kgcn_dense_bwd_dot_f32": (ctypes.c_int, [c_f32p, c_f32p, c_i32, c_i64, c_f32p, c_i64, c_i64, c_i32, c_i32, c_f32p, c_i64, c_f32p, c_i64,
-                                              c_f32p, c_f32p, c_f32p, ctypes.c_void_p, c_i64, c_i32, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
-    "kgcn_dense_bwd_f32": (ctypes.c_int, [c_f32p, c_f32p, c_i64, c_i32, c_f32p, c_i32, c_i64, c_f32p, c_i64, c_i64, c_i32, c_i32,
-                                          c_f32p, c_i64, c_f32p, c_i64, c_f32p, c_f32p, ctypes.c_void_p, c_i64, c_i32,
-                                          ctypes.c_void_p, c_i64, ctypes.c_void_p]),
-    "kgcn_dense_wgrad_f32": (ctypes.c_int, [c_f32p, c_i64, c_f32p, c_i64, c_i64, c_i32, c_i32,
-                                            c_f32p, c_f32p, ctypes.c_void_p, c_i64,
-                                            ctypes.c_void_p]),
-    "kgcn_graphconv_fused_supported": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32]),
-    "kgcn_graphconv_fwd_f32": (ctypes.c_int, [_CSRP, c_f32p, c_f32p, c_f32p, c_i32, c_i32,
-                                              c_f32p, ctypes.c_void_p]),
-    "kgcn_graphconv_bwd_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
-    "kgcn_graphconv_bwd_f32": (ctypes.c_int, [_CSRP, c_f32p, c_f32p, c_f32p, c_i32, c_i32,
-                                              c_f32p, c_f32p, c_f32p, ctypes.c_void_p, c_i64,
-                                              ctypes.c_void_p]),
-    "kgcn_gin_aggregate_f32": (ctypes.c_int, [_CSRP, c_i32, c_f32p, c_i32, c_f32p, c_f32p,
-                                              ctypes.c_void_p]),
-    "kgcn_csr_gather_workspace_bytes": (c_i64, [c_i32]),
-    "kgcn_csr_gather_graphs": (ctypes.c_int, [_CSRP, c_i32p, c_i32, c_i32p, c_i32p, c_i64, c_i32p, c_i32p,
-                                              ctypes.c_void_p, c_i64, ctypes.c_void_p]),
-    "kgcn_batch_assemble_workspace_bytes": (c_i64, [c_i32]),
-    "kgcn_batch_assemble": (ctypes.c_int, [_ASMP, c_i32p, c_i32, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
-    "kgcn_graph_maxpool_fwd_f32": (ctypes.c_int, [_CSRP, c_f32p, c_i32, c_f32p, ctypes.c_float,
-                                                  ctypes.c_void_p]),
-    "kgcn_graph_maxpool_bwd_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
-    "kgcn_graph_maxpool_bwd_f32": (ctypes.c_int, [_CSRP, _CSRP, c_f32p, c_f32p, c_i32, c_f32p,
-                                                  ctypes.c_float, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
-    "kgcn_gat_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
-    "kgcn_gat_fwd_f32": (ctypes.c_int, [_CSRP, c_f32p, c_i32, c_f32p, c_f32p, ctypes.c_float, ctypes.c_void_p, c_i64,
-                                        ctypes.c_void_p]),
-    "kgcn_gat_bwd_f32": (ctypes.c_int, [_CSRP, _CSRP, c_f32p, c_i32, c_f32p, c_f32p, c_f32p, ctypes.c_float, c_f32p,
-                                        ctypes.c_void_p, c_i64, ctypes.c_void_p]),
-    "kgcn_gram_workspace_bytes": (c_i64, [c_i32]),
-    "kgcn_gram_fwd_f32": (ctypes.c_int, [c_f32p, c_i32, c_i32, c_i32, c_f32p, c_f32p, ctypes.c_void_p]),
-    "kgcn_gram_bwd_f32": (ctypes.c_int, [c_f32p, c_i32, c_i32, c_i32, c_f32p, c_f32p, c_f32p, ctypes.c_float, c_f32p,
-                                         ctypes.c_void_p, c_i64, ctypes.c_void_p]),
-    "kgcn_graph_gather_fwd_f32": (ctypes.c_int, [c_f32p, c_i64, c_i32, c_i32, c_f32p,
-                                                 ctypes.c_void_p]),
-    "kgcn_graph_gather_fwd_ld_f32": (ctypes.c_int, [c_f32p, c_i64, c_i32, c_i32, c_f32p, c_i64, ctypes.c_void_p]),
-    "kgcn_graph_gather_bwd_f32": (ctypes.c_int, [c_f32p, c_i64, c_i32, c_i32, c_f32p,
-                                                 ctypes.c_void_p]),
-    "kgcn_bconv_fanout_f32": (ctypes.c_int, [_CSRP, c_i32, c_f32p, c_f32p, c_i64, c_i64, c_i32, c_i32, c_f32p, c_i64, c_i64, c_i64,
-                                             ctypes.c_void_p]),
-    "kgcn_bconv_act_f32": (ctypes.c_int, [_CSRP, c_i32, c_f32p, c_i64, c_i64, c_i64, c_i32, c_f32p, c_i64, c_i64, c_i32,
-                                          ctypes.c_void_p]),
-    "kgcn_bspmm_dact_f32": (ctypes.c_int, [_CSRP, c_f32p, c_f32p, c_i64, c_i64, c_i32, c_i32, c_f32p, c_i64, c_i64,
-                                           ctypes.c_float, ctypes.c_void_p]),
-    "kgcn_dense_fwd_act_f32": (ctypes.c_int, [c_f32p, c_i64, c_i32, c_i64, c_f32p, c_i64, c_i32, c_f32p, c_f32p, c_i32,
-                                              c_i64, c_i32, ctypes.c_void_p]),
-    "kgcn_dense_fwd_workspace_bytes": (c_i64, [c_i32, c_i32]),
-    "kgcn_dense_fwd_ws_f32": (ctypes.c_int, [c_f32p, c_i64, c_i32, c_i64, c_f32p, c_i64, c_i32, c_f32p, c_f32p, c_i32,
-                                             c_i64, c_i32, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
-    "kgcn_dense_dx_dact_f32": (ctypes.c_int, [c_f32p, c_f32p, c_i64, c_i32, c_i64, c_f32p, c_i64, c_i32, c_f32p, c_i64, c_i32,
-                                              c_f32p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
-    "kgcn_dense_dx_dact_tab_f32": (ctypes.c_int, [c_f32p, c_f32p, c_i64, c_i32, c_i64, c_f32p, c_i64, c_i32, c_f32p, c_i64,
-                                                  c_i32, c_f32p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
-    "kgcn_dense_dx_dact_gather_supported": (ctypes.c_int, [c_i64, c_i32, c_i32]),
-    "kgcn_dense_dx_dact_gather_f32": (ctypes.c_int, [c_f32p, c_f32p, c_i64, c_i32, c_f32p, c_i64, c_i32, c_i64, c_f32p, c_i64, c_i32,
-                                                     c_f32p, c_i64, c_i32, c_f32p, ctypes.c_void_p, c_i64, c_i32, ctypes.c_void_p]),
-    "kgcn_dense_dx_dact_dot_supported": (ctypes.c_int, [c_i64, c_i32, c_i32]),
-    "kgcn_dense_dx_dact_dot_workspace_bytes": (c_i64, [c_i64, c_i32]),
-    "kgcn_dense_dx_dact_dot_f32": (ctypes.c_int, [c_f32p, c_f32p, c_i64, c_i32, c_i64, c_f32p, c_i64, c_i32, c_f32p, c_i64, c_i32,
-                                                  c_f32p, ctypes.c_void_p, c_i64, c_i32, c_f32p, ctypes.c_void_p, c_i64,
-                                                  ctypes.c_void_p]),
-    "kgcn_dense_fwd_tab_f32": (ctypes.c_int, [c_f32p, c_i64, c_i32, c_i64, c_f32p, c_i64, c_i32, c_f32p, c_f32p, c_i32,
-                                              c_i64, c_i32, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
-    "kgcn_wtable_split_multi": (ctypes.c_int, [ctypes.c_void_p, c_i32, ctypes.c_void_p]),
-    "kgcn_act_fwd_f32": (ctypes.c_int, [c_f32p, c_i64, c_i32, c_f32p, ctypes.c_void_p]),
-    "kgcn_act_bwd_f32": (ctypes.c_int, [c_f32p, c_f32p, c_i64, c_i32, c_f32p, ctypes.c_void_p]),
-    "kgcn_graph_bn_workspace_bytes": (c_i64, [c_i32]),
-    "kgcn_graph_bn_stats_f32": (ctypes.c_int, [c_f32p, c_i64, c_i32, c_i32, c_i32p, c_f32p, c_f32p, ctypes.c_void_p, c_i64,
-                                               ctypes.c_void_p]),
-    "kgcn_graph_bn_apply_f32": (ctypes.c_int, [c_f32p, c_i64, c_i32, c_i32, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p,
-                                               ctypes.c_float, c_f32p, ctypes.c_void_p]),
-    "kgcn_graph_bn_bwd_f32": (ctypes.c_int, [c_f32p, c_f32p, c_i64, c_i32, c_i32, c_i32p, c_f32p, c_f32p, c_f32p,
-                                             ctypes.c_float, c_i32, c_f32p, c_f32p, c_f32p, ctypes.c_void_p, c_i64,
-                                             ctypes.c_void_p]),
-    "kgcn_coo_pack_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32]),
-    "kgcn_coo_pack_f32": (ctypes.c_int, [c_i32p, c_i32p, c_i32p, c_f32p, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32p,
-                                         ctypes.c_void_p, c_i32p, c_i32p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
-    "kgcn_compact_values_offset": (c_i64, [c_i64]),
-    "kgcn_compact_cv_words": (c_i64, [c_i64, c_i32]),
-    "kgcn_csr_compact4": (ctypes.c_int, [_CSRP, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, c_i32p, ctypes.c_void_p]),
-    "kgcn_graphconv_fused_reads_compact": (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32]),
-    "kgcn_csr_pad4_workspace_bytes": (c_i64, [c_i32, c_i32]),
-    "kgcn_csr_pad4": (ctypes.c_int, [_CSRP, c_i32p, ctypes.c_void_p, c_i64, c_i32p, c_i32p, c_i32p, ctypes.c_void_p,
-                                     c_i64, ctypes.c_void_p]),
-    "kgcn_graph_bn_apply_act_f32": (ctypes.c_int, [c_f32p, c_i64, c_i32, c_i32, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p,
-                                                   ctypes.c_float, c_i32, c_f32p, ctypes.c_void_p]),
-    "kgcn_graph_bn_bwd_dact_f32": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_i32, c_i64, c_i32, c_i32, c_i32p, c_f32p, c_f32p,
-                                                  c_f32p, ctypes.c_float, c_i32, c_f32p, c_f32p, c_f32p, ctypes.c_void_p,
-                                                  c_i64, ctypes.c_void_p]),
-    "kgcn_ragged_workspace_bytes": (c_i64, [c_i32]),
-    "kgcn_ragged_plan": (ctypes.c_int, [_CSRP, c_i32p, c_i32p, c_i32, c_i32p, c_i32p, ctypes.c_void_p, c_i64,
-                                        ctypes.c_void_p]),
-    "kgcn_ragged_compact_csr": (ctypes.c_int, [_CSRP, c_i32p, c_i32, c_i32p, c_i32p, c_i32, c_i32p, c_i32p, c_i64, c_i32p,
-                                               ctypes.c_void_p]),
-    "kgcn_ragged_compact_csr_pair": (ctypes.c_int, [_CSRP, _CSRP, c_i32p, c_i32, c_i32p, c_i32p, c_i32, c_i32p, c_i32p, c_i64, c_i32p,
-                                                    c_i32p, c_i64, c_i32p, ctypes.c_void_p]),
-    "kgcn_ragged_block_rows": (c_i32, []),
-    "kgcn_ragged_num_blocks": (c_i32, [c_i32]),
-    "kgcn_ragged_blocks": (ctypes.c_int, [c_i32p, c_i32, c_i32, c_i32p, ctypes.c_void_p]),
-    "kgcn_ragged_compact_rows_f32": (ctypes.c_int, [c_f32p, c_i32p, c_i32, c_i32, c_i32, c_i32p, c_i32, c_f32p,
-                                                    ctypes.c_void_p]),
-    "kgcn_ragged_compact_rows_aug_f32": (ctypes.c_int, [c_f32p, c_i32p, c_i32, c_i32, c_i32, c_i32p, c_i32, c_f32p, c_i32,
-                                                        ctypes.c_void_p]),
-    "kgcn_ragged_expand_rows_f32": (ctypes.c_int, [c_f32p, c_i32, c_i32, c_i32, c_i32p, c_i32, c_f32p, ctypes.c_void_p]),
-    "kgcn_ragged_gather_fwd_f32": (ctypes.c_int, [c_f32p, c_i32p, c_i64, c_i32, c_i32, c_i32, c_f32p, ctypes.c_void_p]),
-    "kgcn_ragged_gather_bwd_workspace_bytes": (c_i64, [c_i32]),
-    "kgcn_ragged_gather_bwd_f32": (ctypes.c_int, [c_f32p, c_i32p, c_i64, c_i32, c_i32, c_i32, c_i32, c_f32p,
-                                                  ctypes.c_void_p, c_i64, ctypes.c_void_p]),
-    "kgcn_dense_mfma_products": (ctypes.c_int, [c_i32, c_i64, c_i32, c_i32]),
-    "kgcn_spmm_route_query": (ctypes.c_int, [_CSRP, c_i32, c_i32, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32,
-                                             ctypes.POINTER(SpmmRoute)]),
-    "kgcn_copy2d_multi_f32": (ctypes.c_int, [ctypes.c_void_p, c_i32, ctypes.c_void_p]),
-    "kgcn_hbm_probe": (ctypes.c_int, [c_i32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
-    "kgcn_reduce_defer": (ctypes.c_int, [c_i32]),
-    "kgcn_reduce_pending": (ctypes.c_int, []),
-    "kgcn_reduce_flush": (ctypes.c_int, [ctypes.c_void_p]),
-    "kgcn_loss_workspace_bytes": (c_i64, [c_i64]),
-    "kgcn_masked_sigmoid_ce_f32": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_i32, c_i32, ctypes.c_float, c_f32p,
-                                                  c_f32p, c_f32p, c_f32p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
-    "kgcn_masked_softmax_ce_f32": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_i64, c_i32, c_f32p, c_f32p, c_f32p,
-                                                  ctypes.c_void_p, c_i64, ctypes.c_void_p]),
-    "kgcn_sparse_softmax_ce_f32": (ctypes.c_int, [c_f32p, ctypes.c_void_p, c_f32p, c_i64, c_i32, c_f32p, c_f32p, c_f32p,
-                                                  ctypes.c_void_p, c_i64, ctypes.c_void_p]),
-    "kgcn_adam_tf_multi_f32": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_i64, ctypes.c_void_p, c_i32, ctypes.c_float,
-                                              ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]),
-    "kgcn_loss_grad_f32": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_i64, c_i64, c_f32p, ctypes.c_void_p]),
-    "kgcn_adam_tf_f32": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_i64, ctypes.c_float, ctypes.c_float,
-                                        ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]),
-    "kgcn_augment_ones_f32": (ctypes.c_int, [c_f32p, c_i64, c_i32, c_i64, c_f32p, c_i64, ctypes.c_void_p]),
-    "kgcn_augment_ones_bwd_f32": (ctypes.c_int, [c_f32p, c_i64, c_i32, c_i64, c_f32p, c_i64, ctypes.c_void_p]),
-    "kgcn_gcn_stack_supported": (ctypes.c_int, [c_i32, c_i32, _STKP, c_i32]),
-    "kgcn_gcn_stack_param_floats": (c_i64, [_STKP, c_i32]),
-    "kgcn_gcn_stack_fwd_f32": (ctypes.c_int, [_CSRP, c_f32p, c_i32p, _STKP, c_i32, _PTRP, c_f32p, ctypes.c_void_p]),
-    "kgcn_gcn_stack_bwd_workspace_bytes": (c_i64, [c_i32, _STKP, c_i32]),
-    "kgcn_gcn_stack_bwd_f32": (ctypes.c_int, [_CSRP, c_f32p, c_i32p, _STKP, c_i32, _PTRP, c_f32p, c_i32, c_f32p, c_f32p,
-                                              ctypes.c_void_p, c_i64, ctypes.c_void_p]),
-    "kgcn_dense_wgrad_dact_supported": (ctypes.c_int, [c_i32, c_i32]),
-    "kgcn_dense_wgrad_dact_f32": (ctypes.c_int, [c_f32p, c_i64, c_f32p, c_f32p, c_i64, c_i32, c_i64, c_i32, c_i32, c_f32p,
-                                                 c_f32p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
-    "kgcn_gin_aggregate_bwd_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
-    "kgcn_gin_aggregate_bwd_f32": (ctypes.c_int, [_CSRP, c_i32, c_f32p, c_i32, c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p,
-                                                  c_i64, ctypes.c_void_p]),
-    # graph VAE (csrc/vae.hip)
-    "kgcn_philox4x64_raw": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_void_p, c_i64, ctypes.c_void_p, ctypes.c_void_p]),
-    "kgcn_normal_f32": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_void_p, c_i64, c_f32p, ctypes.c_void_p]),
-    "kgcn_vae_sample_fwd_f32": (ctypes.c_int, [c_f32p, c_f32p, c_i32, c_i32, c_i32, c_i32, c_f32p, ctypes.c_uint64, ctypes.c_void_p,
-                                               c_f32p, c_f32p, ctypes.c_void_p]),
-    "kgcn_vae_sample_bwd_f32": (ctypes.c_int, [c_f32p, c_f32p, c_i32, c_i32, c_i32, c_i32, c_f32p, ctypes.c_uint64, ctypes.c_void_p,
-                                               _PTRP, c_i32, c_f32p, c_f32p, c_f32p, ctypes.c_void_p]),
-    "kgcn_vae_recon_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32]),
-    "kgcn_vae_recon_fwd_f32": (ctypes.c_int, [_CSRP, c_i32, _PTRP, _PTRP, c_i32, c_f32p, c_f32p, c_i32, c_f32p, c_f32p, c_f32p,
-                                              c_f32p, ctypes.c_void_p]),
-    "kgcn_vae_recon_bwd_f32": (ctypes.c_int, [_CSRP, c_i32, _PTRP, _PTRP, c_i32, c_f32p, c_f32p, c_i32, c_f32p, c_f32p, c_f32p,
-                                              _PTRP, _PTRP, c_f32p, c_f32p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
-    # multimodal sequence encoder (csrc/seq.hip)
-    "kgcn_seq_convpool_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32]),
-    "kgcn_seq_convpool_fwd_f32": (ctypes.c_int, [ctypes.c_void_p, c_i32, c_i32, c_f32p, c_i32, c_i32, c_f32p, c_f32p, c_i32, c_i32,
-                                                 c_i32, c_f32p, ctypes.c_void_p, ctypes.c_void_p]),
-    "kgcn_seq_convpool_bwd_f32": (ctypes.c_int, [ctypes.c_void_p, c_i32, c_i32, c_f32p, c_i32, c_i32, c_f32p, c_i32, c_i32, c_i32,
-                                                 c_f32p, ctypes.c_void_p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p, c_i64,
-                                                 ctypes.c_void_p]),
-    "kgcn_seq_convpool_scaled_fwd_f32": (ctypes.c_int, [ctypes.c_void_p, c_i32, c_i32, c_f32p, c_i32, c_f32p, c_i32, c_i32, c_f32p,
-                                                        c_f32p, c_i32, c_i32, c_i32, c_f32p, ctypes.c_void_p, ctypes.c_void_p]),
-    "kgcn_seq_convpool_perturbed_fwd_f32": (ctypes.c_int, [ctypes.c_void_p, c_i32, c_i32, c_f32p, c_f32p, c_i32p, c_i32p, ctypes.c_uint64,
-                                                           c_i32, c_f32p, c_i32, c_i32, c_f32p, c_f32p, c_i32, c_i32, c_i32, c_f32p,
-                                                           ctypes.c_void_p, ctypes.c_void_p]),
-    # perturbed inputs of the smooth attribution methods (csrc/igprep.hip)
-    "kgcn_ig_perturb_rows_f32": (ctypes.c_int, [c_f32p, c_i64, c_i32, c_i32, c_i32, c_f32p, c_f32p, c_i32p, c_i32p, ctypes.c_uint32,
-                                                ctypes.c_uint64, c_f32p, ctypes.c_void_p]),
-    "kgcn_ig_perturb_values_f32": (ctypes.c_int, [c_i32p, c_i32, c_i32, c_i64, c_i32, c_f32p, c_f32p, c_f32p, c_i32p, c_i32p,
-                                                  ctypes.c_uint32, ctypes.c_uint64, c_f32p, ctypes.c_void_p]),
-    "kgcn_seq_convpool_input_grad_f32": (ctypes.c_int, [ctypes.c_void_p, c_i32, c_i32, c_i32, c_f32p, c_i32, c_i32, c_f32p, c_i32,
-                                                        c_i32, c_i32, c_f32p, ctypes.c_void_p, c_f32p, c_i32, c_f32p,
-                                                        ctypes.c_void_p]),
-    "kgcn_seq_lstm_stash_floats": (c_i64, [c_i32, c_i32, c_i32]),
-    "kgcn_seq_lstm_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i32]),
-    "kgcn_seq_lstm_fwd_f32": (ctypes.c_int, [c_f32p, c_i32, c_i32, c_i32, c_f32p, c_f32p, c_f32p, c_i32, c_i32, c_f32p, c_i64, c_f32p,
-                                             ctypes.c_void_p]),
-    "kgcn_seq_lstm_bwd_f32": (ctypes.c_int, [c_f32p, c_i32, c_i32, c_i32, c_f32p, c_f32p, c_f32p, c_i32, c_i32, c_f32p, c_i64, c_f32p,
-                                             c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
-    # general Conv1D + max-pool and the embedding gradient (csrc/conv1d.hip)
-    "kgcn_conv1d_pool_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i32, c_i32, c_i32]),
-    "kgcn_conv1d_pool_fwd_f32": (ctypes.c_int, [c_f32p, c_i32p, c_f32p, c_i32, c_i32, c_i32, c_i32, c_f32p, c_f32p, c_i32, c_i32,
-                                                c_i32, c_i32, c_f32p, ctypes.c_void_p, ctypes.c_void_p]),
-    "kgcn_conv1d_pool_bwd_f32": (ctypes.c_int, [c_f32p, c_i32p, c_f32p, c_i32, c_i32, c_i32, c_i32, c_f32p, c_i32, c_i32, c_i32,
-                                                c_i32, c_f32p, ctypes.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p,
-                                                c_i64, ctypes.c_void_p]),
-    "kgcn_embedding_grad_f32": (ctypes.c_int, [c_i32p, c_i32, c_i32, c_f32p, c_i32, c_i32, c_f32p, ctypes.c_void_p]),
-    # knowledge-graph link prediction (csrc/linkpred.hip)
-    "kgcn_linkpred_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32, c_i32]),
-    "kgcn_linkpred_fwd_f32": (ctypes.c_int, [c_f32p, c_i64, c_i32, c_f32p, c_i32, c_i32, c_i32p, c_i32p, c_i64, c_i32, c_i32p, c_i32,
-                                             ctypes.c_uint64, ctypes.c_void_p, c_i32p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p]),
-    "kgcn_linkpred_bwd_f32": (ctypes.c_int, [c_f32p, c_i64, c_i32, c_f32p, c_i32, c_i32, c_i32p, c_f32p, c_f32p, c_f32p, c_i32,
-                                             c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
-    # integrated gradients of the link-prediction model (csrc/kgig.hip)
-    "kgcn_kg_ig_f32": (ctypes.c_int, [c_i32p, c_i32p, c_f32p, c_i64, c_i32, c_i32, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
-                                      c_f32p, c_f32p, c_i32, c_i32p, c_i32, c_i32, c_i32, c_f32p, c_f32p, c_f32p, ctypes.c_void_p]),
-    # ranking of all node pairs of the link-prediction model (csrc/pairrank.hip)
-    "kgcn_pair_rank_workspace_bytes": (c_i64, [c_i32, c_i32, c_i64, c_i64]),
-    "kgcn_pair_rank_select_f32": (ctypes.c_int, [c_f32p, c_i32, c_i32, c_f32p, c_i64, ctypes.c_void_p, ctypes.c_void_p, c_i64,
-                                                 ctypes.c_void_p]),
-    "kgcn_pair_rank_emit_f32": (ctypes.c_int, [c_f32p, c_i32, c_i32, c_f32p, c_i64, ctypes.c_void_p, c_i64, c_f32p, c_i32p, c_i32p,
-                                               ctypes.c_void_p, c_i64, ctypes.c_void_p]),
-    "kgcn_pair_rank_table_i32": (ctypes.c_int, [c_f32p, c_i32p, c_i32p, c_i64, ctypes.c_void_p, c_i64, ctypes.c_void_p, c_i64,
-                                                ctypes.POINTER(c_i64), c_i32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i64,
-                                                ctypes.c_void_p]),
-    # cross-validation: loss head of the compound-protein interaction networks and the ranking metrics (csrc/cvloss.hip, cvmetrics.hip)
-    "kgcn_multitask_softmax2_ce_f32": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_i64, c_i32, c_f32p, c_f32p, c_f32p, c_f32p,
-                                                      ctypes.c_void_p]),
-    "kgcn_binary_metrics_workspace_bytes": (c_i64, [c_i64, c_i32]),
-    "kgcn_binary_metrics_f32": (ctypes.c_int, [c_f32p, c_i64, c_f32p, c_f32p, c_i64, c_i32, ctypes.c_float, ctypes.c_void_p,
-                                               ctypes.c_void_p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
-    # vector-modality models and regression: short-batch Dense + BN + activation, regression head (csrc/shortm.hip, regress.hip)
-    "kgcn_dense_bn_short_supported": (ctypes.c_int, [c_i64, c_i64, c_i64]),
-    "kgcn_dense_bn_short_fwd_f32": (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64, c_i32, c_f32p, c_f32p, c_i32, c_f32p, c_f32p, c_f32p,
-                                                   c_f32p, ctypes.c_float, c_i32, ctypes.c_void_p, c_i64, c_f32p, ctypes.c_void_p]),
-    "kgcn_dense_bn_short_bwd_f32": (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64, c_i32, c_i32, ctypes.c_void_p, c_i64,
-                                                   ctypes.c_void_p, c_i64, c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_float, c_i32,
-                                                   c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p]),
-    "kgcn_dense_bn_short_dx_f32": (ctypes.c_int, [c_f32p, c_i64, c_i32, c_f32p, c_i32, c_f32p, c_i64, ctypes.c_void_p]),
-    "kgcn_act_cols_fwd_f32": (ctypes.c_int, [ctypes.c_void_p, c_i64, c_i64, c_i32, c_i32, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
-    "kgcn_act_cols_bwd_f32": (ctypes.c_int, [ctypes.c_void_p, c_i64, ctypes.c_void_p, c_i64, c_i64, c_i32, c_i32, ctypes.c_void_p,
-                                             c_i64, ctypes.c_void_p]),
-    "kgcn_masked_sqerr_f32": (ctypes.c_int, [c_f32p, c_f32p, c_f32p, c_i64, c_i32, c_f32p, c_f32p, c_f32p, ctypes.c_void_p]),
-    "kgcn_regression_sums_f64": (ctypes.c_int, [ctypes.c_void_p, c_i64, ctypes.c_void_p, c_i64, c_f32p, c_i64, c_i32, ctypes.c_void_p,
-                                                ctypes.c_void_p]),
-    # integrated gradients of the compound-protein interaction multitask network: the sweep over the scaled copies (csrc/cpiig.hip)
-    "kgcn_cpi_ig_workspace_bytes": (c_i64, [c_i32, c_i32, c_i32, c_i32]),
-    "kgcn_cpi_ig_f32": (ctypes.c_int, [c_f32p, c_f32p, c_i32, c_i32, c_i32, c_f32p, c_f32p, c_i32, c_f32p, c_f32p, c_f32p, c_f32p,
-                                       c_i32, c_f32p, c_f32p, c_f32p, ctypes.c_void_p, c_i64, ctypes.c_void_p]),
-    "kgcn_graph_gather_bwd_ld_f32": (ctypes.c_int, [c_f32p, c_i64, c_i64, c_i32, c_i32, c_f32p, ctypes.c_void_p]),
-    "kgcn_graph_gather_bwd_add_f32": (ctypes.c_int, [c_f32p, c_f32p, c_i64, c_i32, c_i32, c_f32p, ctypes.c_void_p]),
-    "kgcn_dot_workspace_bytes": (c_i64, [c_i64]),
-    "kgcn_dot_f32": (ctypes.c_int, [c_f32p, c_f32p, c_i64, c_f32p, ctypes.c_void_p, c_i64,
-                                    ctypes.c_void_p]),
-}
+SPMM_DACT, SPMM_SELF_SCALE, SPMM_DOT, SPMM_FANOUT = (K[n] for n in (
+    "KGCN_SPMM_DACT", "KGCN_SPMM_SELF_SCALE", "KGCN_SPMM_DOT", "KGCN_SPMM_FANOUT"))
 
 
 def _load():

@@ -90,9 +90,7 @@ DEVICE_PACK_MIN_NNZ = 20000
 class BatchedCSR:
     """One adjacency channel of a batch of T graphs, device resident."""
 
-    PAD_COL = 32        # KGCN_PAD_COL of include/kgcn_hip.h
-    ROW_PAD_COMPACT = 0x104     # KGCN_ROW_PAD_COMPACT
-    UNIT_VALUES = 1             # KGCN_CSR_UNIT_VALUES
+    PAD_COL, ROW_PAD_COMPACT, UNIT_VALUES = (_lib.K[n] for n in ("KGCN_PAD_COL", "KGCN_ROW_PAD_COMPACT", "KGCN_CSR_UNIT_VALUES"))
 
     def __init__(self, rowptr, cv, num_graphs, rows, cols, max_nnz, perm=None, host=None,
                  row_pad=0):

@@ -18,7 +18,9 @@ from ._lib import check, current_stream, lib, ptr, require_gpu
 from .batched_csr import BatchedAdjacency, BatchedCSR
 
 
-ACT_CODES = {None: 0, "none": 0, "linear": 0, "sigmoid": 1, "relu": 2, "tanh": 3}
+# Every limit and code below is read from include/kgcn_hip.h (_lib.K: its constants by name); none is restated here.
+ACT_CODES = {None: _lib.K["KGCN_ACT_NONE"], "none": _lib.K["KGCN_ACT_NONE"], "linear": _lib.K["KGCN_ACT_NONE"],
+             "sigmoid": _lib.K["KGCN_ACT_SIGMOID"], "relu": _lib.K["KGCN_ACT_RELU"], "tanh": _lib.K["KGCN_ACT_TANH"]}
 # A/B switch: d pre-activation inside the wide weight-gradient GEMM when the layer input needs no gradient
 wgrad_dact_fusion = True
 # OPTION (off): weight gradients of the big dense layers on a SIDE HIP stream.  In a backward pass dW / dbias hang off the
@@ -1459,7 +1461,7 @@ def _stack_descriptors(spec, params, buffers):
 
 def gcn_stack_supported(csr, spec):
     import ctypes
-    if csr.row_pad or csr.rows != csr.cols or csr.rows > 32 or len(spec) > 8:
+    if csr.row_pad or csr.rows != csr.cols or csr.rows > 32 or len(spec) > _lib.K["KGCN_STACK_MAX_LAYERS"]:
         return False
     arr = (_lib.StackLayer * len(spec))()
     for l, (kind, act, din, dout, eps) in enumerate(spec):
@@ -1753,7 +1755,7 @@ def graph_bn(x, gamma, beta, mean, var, enabled=None, eps=1e-3, training=False, 
 # -------------------------------------------------------------------------------------------------
 # graph VAE (example_model/model_vae.py; csrc/vae.hip): counter-based noise, reparameterisation + KL, reconstruction loss
 # -------------------------------------------------------------------------------------------------
-VAE_MAX_NODES, VAE_MAX_CHANNELS, VAE_MAX_DIM = 128, 8, 64
+VAE_MAX_NODES, VAE_MAX_CHANNELS, VAE_MAX_DIM = (_lib.K[n] for n in ("KGCN_VAE_MAX_NODES", "KGCN_VAE_MAX_CHANNELS", "KGCN_VAE_MAX_DIM"))
 
 
 def _step_ptr(step):
@@ -1911,9 +1913,11 @@ def vae_recon(adj, ys, ws, feat_logits, feat_target, mask=None, kl=None):
 # multimodal sequence encoder (example_model/model_multimodal.py:70-93; csrc/seq.hip): fused embedding + Conv1D + relu +
 # MaxPooling1D, and the go_backwards LSTM
 # -------------------------------------------------------------------------------------------------
-SEQ_MAX_EMBED, SEQ_MAX_FILTERS, SEQ_MAX_KERNEL, SEQ_MAX_POOL = 32, 64, 8, 8
-SEQ_MAX_UNITS, SEQ_MAX_LSTM_INPUT, SEQ_MAX_SYMBOLS, SEQ_MAX_LENGTH = 64, 64, 1024, 8192
-RECURRENT_ACTIVATIONS = {"hard_sigmoid": 0, "sigmoid": 1}
+SEQ_MAX_EMBED, SEQ_MAX_FILTERS, SEQ_MAX_KERNEL, SEQ_MAX_POOL = (_lib.K[n] for n in (
+    "KGCN_SEQ_MAX_EMBED", "KGCN_SEQ_MAX_FILTERS", "KGCN_SEQ_MAX_KERNEL", "KGCN_SEQ_MAX_POOL"))
+SEQ_MAX_UNITS, SEQ_MAX_LSTM_INPUT, SEQ_MAX_SYMBOLS, SEQ_MAX_LENGTH = (_lib.K[n] for n in (
+    "KGCN_SEQ_MAX_UNITS", "KGCN_SEQ_MAX_LSTM_INPUT", "KGCN_SEQ_MAX_SYMBOLS", "KGCN_SEQ_MAX_LENGTH"))
+RECURRENT_ACTIVATIONS = {"hard_sigmoid": _lib.K["KGCN_SEQ_ACT_HARD_SIGMOID"], "sigmoid": _lib.K["KGCN_SEQ_ACT_SIGMOID"]}
 
 
 def seq_limits_check(length=None, symbols=None, embed_dim=None, kernel_size=None, filters=None, pool=None, units=None,
@@ -2101,8 +2105,9 @@ def seq_conv_pool_scaled(tokens, table, w, bias, pool, scale, rep, argmax=False)
     return _seq_conv_pool_copies(tokens, table, w, bias, pool, scale, rep, None, argmax)
 
 
-# noise streams of the smooth attribution methods (KGCN_IG_STREAM_* of include/kgcn_hip.h)
-IG_STREAM_FEATURES, IG_STREAM_ADJACENCY, IG_STREAM_SEQUENCE = 0, 1, 0x100
+# noise streams of the smooth attribution methods
+IG_STREAM_FEATURES, IG_STREAM_ADJACENCY, IG_STREAM_SEQUENCE = (_lib.K[n] for n in (
+    "KGCN_IG_STREAM_FEATURES", "KGCN_IG_STREAM_ADJACENCY", "KGCN_IG_STREAM_SEQUENCE"))
 
 
 def _i32_row(v, name, n, device):
@@ -2216,7 +2221,8 @@ def seq_conv_pool_input_grad(dout, argmax, tokens, table, w, pool, rep, row_weig
 # -------------------------------------------------------------------------------------------------
 # general Conv1D -> MaxPooling1D on the matrix pipe (sample_protein/sequence/cnn.py:36-61; csrc/conv1d.hip)
 # -------------------------------------------------------------------------------------------------
-CONV1D_MAX_CHANNELS, CONV1D_MAX_KERNEL, CONV1D_MAX_POOL, CONV1D_MAX_LENGTH, CONV1D_MAX_SYMBOLS = 1024, 8, 8, 8192, 1024
+CONV1D_MAX_CHANNELS, CONV1D_MAX_KERNEL, CONV1D_MAX_POOL, CONV1D_MAX_LENGTH, CONV1D_MAX_SYMBOLS = (_lib.K[n] for n in (
+    "KGCN_CONV1D_MAX_CHANNELS", "KGCN_CONV1D_MAX_KERNEL", "KGCN_CONV1D_MAX_POOL", "KGCN_CONV1D_MAX_LENGTH", "KGCN_CONV1D_MAX_SYMBOLS"))
 CONV1D_ACTIVATIONS = (None, "none", "linear", "relu", "tanh")
 
 
@@ -2351,8 +2357,9 @@ def graph_gather_into(y, join, join_col):
 # knowledge-graph link prediction (sample_kg/network_prediction/model_py/{gcn,distmult,ip}.py; csrc/linkpred.hip): label-batch
 # assembly with the negative draw, the pairwise ranking loss, and its atomic-free gradient
 # -------------------------------------------------------------------------------------------------
-LINKPRED_MODES = {"gcn": 0, "distmult": 1, "ip": 2}
-LINKPRED_MAX_DIM, LINKPRED_MAX_BATCH, LINKPRED_MAX_REL_FLOATS = 256, 1 << 22, 16384
+LINKPRED_MODES = {"gcn": _lib.K["KGCN_LP_GCN"], "distmult": _lib.K["KGCN_LP_DISTMULT"], "ip": _lib.K["KGCN_LP_IP"]}
+LINKPRED_MAX_DIM, LINKPRED_MAX_BATCH, LINKPRED_MAX_REL_FLOATS = (_lib.K[n] for n in (
+    "KGCN_LP_MAX_DIM", "KGCN_LP_MAX_BATCH", "KGCN_LP_MAX_REL_FLOATS"))
 
 
 class _LinkPredLoss(torch.autograd.Function):
@@ -2438,8 +2445,9 @@ def linkpred_loss(h, feed, mode, w=None, seed=0, step=None, batch=None, labels=N
 # integrated gradients of the link-prediction model (kgcn visualize on model_py/gcn.py; csrc/kgig.hip): many targets over
 # one graph, from the stash of the K scaled layer-2 outputs
 # -------------------------------------------------------------------------------------------------
-KG_IG_MODES = {"score": 0, "loss": 1}
-KG_IG_WIDTH, KG_IG_MAX_NODES, KG_IG_MAX_STEPS, KG_IG_GROUPS = 128, 7168, 4096, 256
+KG_IG_MODES = {"score": _lib.K["KGCN_KGIG_SCORE"], "loss": _lib.K["KGCN_KGIG_LOSS"]}
+KG_IG_WIDTH, KG_IG_MAX_NODES, KG_IG_MAX_STEPS, KG_IG_GROUPS = (_lib.K[n] for n in (
+    "KGCN_KGIG_WIDTH", "KGCN_KGIG_MAX_NODES", "KGCN_KGIG_MAX_STEPS", "KGCN_KGIG_GROUPS"))
 
 
 def kg_ig_check_host(indptr, indices, num_nodes, targets=None, mode="score", steps=1, width=KG_IG_WIDTH):
@@ -2528,7 +2536,8 @@ def kg_ig(csr, g1, rowsum, b1, w2, h2, p, scales, weights, targets, mode="score"
 # ranking of all node pairs of the link-prediction model (run_enrichment.sh: script/predscore.py; csrc/pairrank.hip): the
 # score-ordered pair list straight from the node rows, and its train / test / new marks with the enrichment counts
 # -------------------------------------------------------------------------------------------------
-PAIRRANK_MAX_NODES, PAIRRANK_MAX_CANDIDATES, PAIRRANK_MAX_TOP = 65536, 1 << 28, 16
+PAIRRANK_MAX_NODES, PAIRRANK_MAX_CANDIDATES, PAIRRANK_MAX_TOP = (_lib.K[n] for n in (
+    "KGCN_PAIRRANK_MAX_NODES", "KGCN_PAIRRANK_MAX_CANDIDATES", "KGCN_PAIRRANK_MAX_TOP"))
 
 
 def _pair_rank_ws(n, d, capacity, entries, device):
@@ -2677,7 +2686,7 @@ def multitask_softmax2_ce(logits, labels, mask_label, accum=None):
 
 
 BINARY_METRICS_COLUMNS = ("n_used", "P", "TP", "FP", "n_nonfinite", "auc_num2", "n_groups", "spare")
-BINARY_METRICS_MAX_ELEMENTS, BINARY_METRICS_MAX_TASKS = 1 << 31, 1 << 20
+BINARY_METRICS_MAX_ELEMENTS, BINARY_METRICS_MAX_TASKS = _lib.K["KGCN_BINARY_METRICS_MAX_ELEMENTS"], _lib.K["KGCN_BINARY_METRICS_MAX_TASKS"]
 
 
 @torch.no_grad()
@@ -2727,7 +2736,7 @@ def binary_metrics(score, label, mask=None, threshold=0.5):
 # at the other fourteen (by 7 % to 6x, growing with rows and K), and the whole captured step of both models was 10 % slower
 # with it at 50 rows and up to 3x at 256.  The row limit is the kernels' own: no measured row count favours the route.
 short_dense_fusion = False
-short_dense_max_rows = 256
+short_dense_max_rows = _lib.K["KGCN_DENSE_BN_SHORT_MAX_ROWS"]
 
 
 def dense_bn_short_supported(rows, k, n):
@@ -2941,7 +2950,7 @@ def regression_metrics(pred, label, mask=None):
 # integrated gradients of the compound-protein interaction multitask network (kgcn visualize on multitask.py; csrc/cpiig.hip): the
 # sweep over the scaled copies of many compounds, all tasks at once
 # -------------------------------------------------------------------------------------------------
-CPI_IG_TASKS_PER_PASS = 8           # KGCN_CPIIG_TASKS_PER_PASS: tasks a lane of the accumulate pass carries
+CPI_IG_TASKS_PER_PASS = _lib.K["KGCN_CPIIG_TASKS_PER_PASS"]           # tasks a lane of the accumulate pass carries
 
 
 def cpi_ig_limits_check(nodes, width, tasks, steps):

@@ -3,8 +3,9 @@
  * __graft_entry__.build() / tests with gcc, linked to libkgcn_hip.so and libamdhip64 only -- the binding a maintainer of
  * the reference would write for kgcn/bspmm_call.py:9-19 starts exactly like this.
  *
- *   abi_consumer layout   no GPU needed: sizeof / offsetof of kgcn_csr_batch as THIS compiler sees the header, the
- *                         library's kgcn_csr_batch_size() / kgcn_abi_version(), and the error convention
+ *   abi_consumer layout   no GPU needed: sizeof / offsetof of kgcn_csr_batch as THIS compiler sees the header, sizeof and the
+ *                         last field's offset of all seven structures, the library's kgcn_csr_batch_size() /
+ *                         kgcn_abi_version(), and the error convention
  *                         (a NULL descriptor -> non-zero status + kgcn_last_error() text)
  *   abi_consumer bspmm    on the GPU box: one kgcn_bspmm_f32 call on a 2-graph batch built here by hand, checked against
  *                         the products computed in C (exact: small integers), then a refused call (row_pad batch)
@@ -42,6 +43,16 @@ static int layout(void) {
   printf("sizeof_wtable_job %zu\n", sizeof(kgcn_wtable_job));
   printf("offsetof_wtable_job_table %zu\n", offsetof(kgcn_wtable_job, table));
   printf("offsetof_wtable_job_extra_row %zu\n", offsetof(kgcn_wtable_job, extra_row));
+  /* every structure of the header: its size, and the name and offset of its last field */
+#define LAYOUT(s, last) printf("layout_" #s " %zu " #last " %zu\n", sizeof(s), offsetof(s, last))
+  LAYOUT(kgcn_csr_batch, block_rows_max);
+  LAYOUT(kgcn_assemble_plan, row_floats);
+  LAYOUT(kgcn_wtable_job, extra_row);
+  LAYOUT(kgcn_adam_segment, numel);
+  LAYOUT(kgcn_stack_layer, route);
+  LAYOUT(kgcn_spmm_route, lds_bytes);
+  LAYOUT(kgcn_copy2d_job, dst_ld);
+#undef LAYOUT
   CHECK(kgcn_abi_version() == KGCN_HIP_ABI_VERSION, "library and header ABI versions differ");
   CHECK(kgcn_csr_batch_size() == (int64_t)sizeof(kgcn_csr_batch), "kgcn_csr_batch size differs between header and library");
   CHECK(strcmp(kgcn_build_arch(), "gfx950") == 0, "build arch");

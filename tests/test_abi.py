@@ -1,6 +1,7 @@
 """CPU-side checks of the drop-in boundary: libkgcn_hip.so loads (no GPU needed), exports every
-symbol include/kgcn_hip.h declares, the Python binding lists exactly those symbols, shape queries
-answer, and argument validation fails loudly (no compute launches here)."""
+symbol include/kgcn_hip.h declares, the Python binding -- derived from that header by _lib.parse_header --
+lists exactly those symbols, every structure and every constant, the parser refuses what it does not
+understand, shape queries answer, and argument validation fails loudly (no compute launches here)."""
 import ctypes
 import os
 import re
@@ -16,6 +17,15 @@ def declared_functions():
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     names = re.findall(r"\b(kgcn_[a-z0-9_]+)\s*\(", src)
     return sorted(set(names))
+
+
+def header_without_comments():
+    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+
+
+STRUCTS = {"kgcn_csr_batch": "CsrBatch", "kgcn_assemble_plan": "AssemblePlan", "kgcn_wtable_job": "WtableJob",
+           "kgcn_adam_segment": "AdamSegment", "kgcn_stack_layer": "StackLayer", "kgcn_spmm_route": "SpmmRoute",
+           "kgcn_copy2d_job": "Copy2dJob"}
 
 
 def header_abi_version():
@@ -59,6 +69,11 @@ def test_c_consumer_sees_the_layout_the_binding_mirrors():
     assert int(facts["offsetof_wtable_job_table"]) == _lib.WtableJob.table.offset
     assert int(facts["offsetof_wtable_job_extra_row"]) == _lib.WtableJob.extra_row.offset
     assert "NULL" in facts["last_error"]
+    for c_name, cls_name in STRUCTS.items():            # all seven: sizeof and the last field, as the C compiler lays them out
+        cls = getattr(_lib, cls_name)
+        size, last, offset = facts["layout_" + c_name].split()
+        assert int(size) == ctypes.sizeof(cls), c_name
+        assert last == cls._fields_[-1][0] and int(offset) == getattr(cls, last).offset, c_name
 
 
 def test_header_declares_the_path():
@@ -78,6 +93,101 @@ def test_library_exports_every_declared_symbol():
     assert _lib.lib.kgcn_abi_version() == _lib.ABI_VERSION == header_abi_version()
     assert _lib.lib.kgcn_csr_batch_size() == ctypes.sizeof(_lib.CsrBatch)
     assert _lib.lib.kgcn_build_arch() == b"gfx950"
+
+
+def test_binding_holds_every_structure_and_constant_of_the_header():
+    """A second, independent reader of the header (plain regular expressions here) counts what parse_header must have found:
+    a structure or a #define its expressions fail to match would be missing from the binding."""
+    from kgcn_amd import _lib
+    src = header_without_comments()
+    functions, structs, constants = _lib.parse_header(open(HEADER).read())
+    assert functions.keys() == _lib.SIGNATURES.keys() and constants == _lib.K
+    typedefs = re.findall(r"typedef\s+struct\s+(kgcn_\w+)", src)
+    assert len(typedefs) == len(structs) == 7 and sorted(typedefs) == sorted(structs) == sorted(STRUCTS)
+    for c_name, cls_name in STRUCTS.items():
+        assert structs[c_name].__name__ == cls_name and issubclass(getattr(_lib, cls_name), ctypes.Structure)
+        assert [f[0] for f in structs[c_name]._fields_] == [f[0] for f in getattr(_lib, cls_name)._fields_]
+    defines = re.findall(r"^[ \t]*#[ \t]*define[ \t]+(KGCN_\w+)[ \t]+\S", src, flags=re.M)    # the include guard has no value
+    assert len(defines) == len(set(defines)) == 66
+    for name in defines:
+        assert isinstance(_lib.K[name], int), name
+    assert _lib.K["KGCN_ROW_PAD_COMPACT"] == 0x104 and _lib.K["KGCN_LP_MAX_BATCH"] == 1 << 22
+    assert _lib.K["KGCN_BINARY_METRICS_MAX_ELEMENTS"] == 1 << 31 and _lib.K["KGCN_IG_STREAM_SEQUENCE"] == 0x100
+    # SPMM_KERNELS spells kernel names, not enumerators: it must have one name per enumerator of the route codes
+    enum = re.search(r"enum\s*\{(.*?)\}", src, flags=re.S).group(1)
+    codes = {n: int(v) for n, v in re.findall(r"(KGCN_SPMM_\w+)\s*=\s*(\d+)", enum)}
+    assert codes and all(_lib.K[n] == v for n, v in codes.items())
+    assert len(_lib.SPMM_KERNELS) == max(codes.values()) + 1
+    assert (_lib.SPMM_DACT, _lib.SPMM_SELF_SCALE, _lib.SPMM_DOT, _lib.SPMM_FANOUT) == (1, 2, 4, 8)
+
+
+SNIPPET = """/* a header in the grammar of kgcn_hip.h */
+#ifndef X_H_
+#define X_H_
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define KGCN_N (1 << 2)   /* a limit */
+#define KGCN_BIG (1ll << 33)
+#define KGCN_MASK 0x10u
+typedef struct kgcn_csr_batch {
+  int32_t a, b[KGCN_N];   /* two declarators */
+  const float* p;
+  int64_t n[2];
+} kgcn_csr_batch;
+typedef struct kgcn_pair {
+  const kgcn_csr_batch* src[KGCN_N];
+  float eps;
+} kgcn_pair;
+%s
+int kgcn_first(const kgcn_csr_batch* a, const float* x, int64_t ld, float* const* outs, uint64_t seed, float beta,
+               const kgcn_pair* pairs, void* stream);
+const char* kgcn_second(void);
+#ifdef __cplusplus
+}
+#endif
+#endif /* X_H_ */
+"""
+
+
+def test_parse_header_types_a_snippet():
+    from kgcn_amd import _lib
+    functions, structs, constants = _lib.parse_header(SNIPPET % "")
+    assert constants == {"KGCN_N": 4, "KGCN_BIG": 1 << 33, "KGCN_MASK": 16}
+    batch, pair = structs["kgcn_csr_batch"], structs["kgcn_pair"]
+    assert (batch.__name__, pair.__name__) == ("CsrBatch", "Pair") and list(structs) == ["kgcn_csr_batch", "kgcn_pair"]
+    assert [(n, t) for n, t in batch._fields_] == [("a", ctypes.c_int32), ("b", ctypes.c_int32 * 4), ("p", ctypes.c_void_p),
+                                                   ("n", ctypes.c_int64 * 2)]
+    assert pair._fields_ == [("src", ctypes.POINTER(batch) * 4), ("eps", ctypes.c_float)]
+    assert ctypes.sizeof(batch) == 48 and batch.p.offset == 24 and ctypes.sizeof(pair) == 40
+    assert list(functions) == ["kgcn_first", "kgcn_second"]
+    res, args = functions["kgcn_first"]
+    assert res is ctypes.c_int
+    # typed pointer for kgcn_csr_batch; a structure outside the typed set, like any data pointer, is c_void_p
+    assert args == [ctypes.POINTER(batch), ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint64,
+                    ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]
+    assert functions["kgcn_second"] == (ctypes.c_char_p, [])
+
+
+@pytest.mark.parametrize("bad, quoted", [
+    ("int kgcn_third(const float* x, size_t n);", "size_t"),                       # unknown scalar in a prototype
+    ("int kgcn_third(const half* x);", "half"),                                    # unknown pointee
+    ("double kgcn_third(void);", "double"),                                        # unknown return type
+    ("#define KGCN_X 1.5f", "1.5f"),                                               # not an integer
+    ("#define KGCN_X (KGCN_LATER << 1)", "KGCN_LATER"),                            # no EARLIER constant
+    ("#define KGCN_N 5", "KGCN_N"),                                                # defined twice
+    ("typedef struct kgcn_t { int32_t a; double d; } kgcn_t;", "double d"),        # field of unknown type
+    ("typedef struct kgcn_t { kgcn_csr_batch inner; } kgcn_t;", "kgcn_csr_batch inner"),   # structure by value
+    ("typedef struct kgcn_t { float** pp; } kgcn_t;", "float** pp"),
+    ("static inline int kgcn_third(void) { return 0; }", "kgcn_third"),            # not a declaration
+    ("typedef int32_t kgcn_index;", "kgcn_index"),
+])
+def test_parse_header_refuses_what_it_does_not_understand(bad, quoted):
+    from kgcn_amd import _lib
+    with pytest.raises(ValueError) as e:
+        _lib.parse_header(SNIPPET % bad)
+    assert quoted in str(e.value), str(e.value)
 
 
 def test_code_object_is_gfx950_only():
