@@ -15,7 +15,9 @@ No dragon / profeat dataset ships, so the default is the synthetic stand-in of t
 4-12 nodes, profeat 70 wide, dragon 37 wide, labels planted in vector and graph); --dataset takes a .jbl (joblib) dict with
 dense_adj | adj, feature, label, the vector modality and -- for the regression -- mask_label.
 
-    python examples/train_vecmodal.py --model vec|regression [--epochs 30] [--batch 50] [--dataset x.jbl]
+    python examples/train_vecmodal.py --model vec|regression [--epochs 30] [--batch 50] [--dataset x.jbl] [--save PATH]
+
+--save PATH writes the trained model's state dict (torch.save), which examples/visualize_vecmodal.py --params reads.
 """
 import argparse
 import os
@@ -97,20 +99,24 @@ def fit(kind, raw, epochs=30, batch=50, lr=1e-3, seed=0, device="cuda:0", log=pr
     return model, history
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", choices=("vec", "regression"), required=True)
     ap.add_argument("--epochs", type=int, default=30)
     ap.add_argument("--batch", type=int, default=50)
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--dataset", default=None)
-    a = ap.parse_args()
+    ap.add_argument("--save", default=None, help="write the trained model's state dict here (torch.save)")
+    a = ap.parse_args(argv)
     if a.dataset:
         import joblib
         raw = joblib.load(a.dataset)
     else:
         raw = standin(a.model)
-    fit(a.model, raw, a.epochs, a.batch, a.lr)
+    model, _ = fit(a.model, raw, a.epochs, a.batch, a.lr)
+    if a.save:
+        torch.save(model.state_dict(), a.save)
+        print("state dict saved to %s" % a.save)
 
 
 if __name__ == "__main__":

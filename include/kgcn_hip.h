@@ -90,7 +90,9 @@ extern "C" {
  * The vector-modality models and regression added entry points only (version still 2): kgcn_dense_bn_short_fwd_f32 / _bwd_f32 /
  * _dx_f32 (+ kgcn_dense_bn_short_supported), kgcn_act_cols_fwd_f32 / _bwd_f32, kgcn_masked_sqerr_f32, kgcn_regression_sums_f64.
  * Integrated gradients of the compound-protein interaction network added entry points only (version still 2): kgcn_cpi_ig_f32
- * (+ kgcn_cpi_ig_workspace_bytes). */
+ * (+ kgcn_cpi_ig_workspace_bytes).
+ * Integrated gradients over the vector modality added entry points and a noise stream only (version still 2):
+ * kgcn_ig_copies_expand_f32, kgcn_ig_copies_reduce_f32, KGCN_IG_STREAM_VECTOR. */
 #define KGCN_HIP_ABI_VERSION 2
 
 /* Column index of the padding entries of a row-padded batch (see row_pad): they carry value 0 and
@@ -899,7 +901,8 @@ int kgcn_seq_convpool_input_grad_f32(const int32_t* tokens, int32_t batch, int32
  * 2, 3).  g is the compound's index in the dataset and k the sample number (both read as unsigned 32-bit values), never the
  * position of the copy in a launch.  Streams: KGCN_IG_STREAM_FEATURES the node features [N, F], padding rows included;
  * KGCN_IG_STREAM_ADJACENCY + ch the stored values of adjacency channel ch of graph g as [1, nnz_g] in the CSR order of the batch;
- * KGCN_IG_STREAM_SEQUENCE the embedded sequence [L, E].  The perturbed value is fma(sigma, z, x * scale) in fp32; a copy with
+ * KGCN_IG_STREAM_SEQUENCE the embedded sequence [L, E]; KGCN_IG_STREAM_VECTOR the per-graph vector of the vector-modality models
+ * as [1, Dv] (adjacency channels occupy 1 .. 0xff, so 0x200 meets none of them).  The perturbed value is fma(sigma, z, x * scale) in fp32; a copy with
  * sigma == 0 is x * scale, the clean path's product, and draws nothing.
  * Rows: out [batch, rows, width], copy b = x[b / rep] (x [batch / rep, rows, width]) with scale[b], sigma[b], sample[b] and
  * ids[b / rep] (16-byte accesses when width % 4 == 0 and x, out are 16-byte aligned).  Values: out[e] for the entries e of a plain batched CSR (rowptr
@@ -912,6 +915,7 @@ int kgcn_seq_convpool_input_grad_f32(const int32_t* tokens, int32_t batch, int32
 #define KGCN_IG_STREAM_FEATURES 0u
 #define KGCN_IG_STREAM_ADJACENCY 1u
 #define KGCN_IG_STREAM_SEQUENCE 0x100u
+enum { KGCN_IG_STREAM_VECTOR = 0x200 };
 int kgcn_ig_perturb_rows_f32(const float* x, int64_t batch, int32_t rep, int32_t rows, int32_t width, const float* scale,
                              const float* sigma, const int32_t* sample, const int32_t* ids, uint32_t noise_stream, uint64_t seed,
                              float* out, void* stream);
@@ -1145,6 +1149,35 @@ int64_t kgcn_cpi_ig_workspace_bytes(int32_t compounds, int32_t width, int32_t ta
 int kgcn_cpi_ig_f32(const float* P, const float* Q, int32_t compounds, int32_t nodes, int32_t width, const float* u, const float* e,
                     int32_t tasks, const float* alpha, const float* gamma, const float* wA, const float* wB, int32_t steps, float* p,
                     float* GA, float* GB, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Integrated gradients over the per-graph vector of the vector-modality models (model_multimodal_vec.py:83-94,
+ * model_multimodal_regression.py:83-86; kgcn/visualization.py:187-260): the sweeps over the `copies` scaled copies of `compounds`
+ * compounds through the vector branch's first layer, Dense(Dv -> width) + BatchNormalization (learning phase 0) + activation
+ * (csrc/vecig.hip; entry points only, version still 2).
+ * expand: P [compounds, width] contiguous is v W of every compound, formed once by the caller; copy k of compound c is row
+ *   c copies + k of Y (row stride y_ld >= width: Y may be a column block of a wider buffer, the other columns are not touched):
+ *     Y[c copies + k, j] = act(bn(fma(alpha[k], P[c, j], bias[j])))     bn(x) = (x - mean[j]) * (1 / sqrt(var[j] + eps)) * gamma[j] + beta[j]
+ *   in fp32, the operation order of kgcn_graph_bn_apply_act_f32, so that a copy with alpha == 1 equals that pass applied to
+ *   P + bias bit for bit.  (With scale = gamma / sqrt(var + eps) and shift = beta - scale mean this is act(scale (alpha P + bias) +
+ *   shift); the entry point takes the layer's own four vectors because the folded form rounds differently.)  bias may be NULL
+ *   (zeros); gamma, beta, mean, var are all NULL (no normalisation) or all given.
+ * reduce: dY and Y [compounds copies, width] with row strides dy_ld, y_ld >= width, w [copies], scale [width] or NULL (ones):
+ *     S[c, j] = scale[j] sum_k w[k] dY[c copies + k, j] act'(Y[c copies + k, j])        S [compounds, width] contiguous
+ *   -- the weighted sum over the copies of d score / d pre-activation.  The sum runs over k = 0, 1, ... in that order in fp32 in
+ *   one register (acc = fma(w[k], dY act'(Y), acc)) without atomics; a copy with w[k] == 0 is skipped: whatever its rows hold, NaN
+ *   included, never reaches the sum (the rows themselves must exist).
+ * Both: act is a KGCN_ACT_* code; a compound's rows do not depend on the other compounds of the call (chunking changes no bit);
+ * 16-byte accesses when the base pointers are 16-byte aligned and width and the row strides are multiples of 4, single floats
+ * otherwise; each output element is written once, Y and dY are read once.  compounds == 0 is a no-op.
+ * Limits: 1 <= width <= KGCN_IG_COPIES_MAX_WIDTH, 1 <= copies <= KGCN_IG_COPIES_MAX_COPIES, compounds >= 0 with compounds copies <=
+ * KGCN_IG_COPIES_MAX_ROWS and a grid below 2^31 workgroups (pass fewer compounds); anything else is refused before any launch.
+ * Asynchronous. */
+enum { KGCN_IG_COPIES_MAX_WIDTH = 1 << 20, KGCN_IG_COPIES_MAX_COPIES = 65535, KGCN_IG_COPIES_MAX_ROWS = 0x7fffffff };
+int kgcn_ig_copies_expand_f32(const float* P, int64_t compounds, int32_t copies, int32_t width, const float* alpha, const float* bias,
+                              const float* gamma, const float* beta, const float* mean, const float* var, float eps, int32_t act,
+                              float* Y, int64_t y_ld, void* stream);
+int kgcn_ig_copies_reduce_f32(const float* dY, int64_t dy_ld, const float* Y, int64_t y_ld, int64_t compounds, int32_t copies,
+                              int32_t width, const float* w, const float* scale, int32_t act, float* S, void* stream);
 
 #ifdef __cplusplus
 }

@@ -715,7 +715,8 @@ class MultimodalVecGCN(nn.Module):
     The concatenation is one [B, 114] buffer: the tower's last layer writes columns 0-63, the graph read-out 64-113
     (ops.join_columns), nothing is copied.  forward(features, adjs, vectors=None, enabled_node_nums=None) -> logits; `vectors`
     is the float32 [B, Dv] batch of data_util.vector_table (GraphedTrainStep passes it as a forward kwarg); enabled_node_nums is
-    accepted and unused, as in the file.  The rows never mix (learning phase 0, no dropout)."""
+    accepted and unused, as in the file.  vector_first [B, 300]: the already computed output of tower[0], in place of `vectors`
+    (visualization.vecmodal_integrated_gradients differentiates to it).  The rows never mix (learning phase 0, no dropout)."""
 
     ROW_INDEPENDENT = True
 
@@ -729,7 +730,9 @@ class MultimodalVecGCN(nn.Module):
         self.hidden = KerasDenseBN(self.HIDDEN, activation="relu")                                # :106-108
         self.out = KerasDenseBN(int(label_dim), batch_norm=False)                                 # :110
 
-    def forward(self, features, adjs, vectors=None, enabled_node_nums=None):
+    def forward(self, features, adjs, vectors=None, enabled_node_nums=None, vector_first=None):
+        if vector_first is not None:                  # the output of tower[0] [B, 300], already computed, in place of `vectors`
+            vectors = vector_first
         if vectors is None:
             raise ValueError("MultimodalVecGCN needs the vectors= batch")
         adj = layers._pack(adjs, features)
@@ -737,7 +740,7 @@ class MultimodalVecGCN(nn.Module):
         if vectors.shape[0] != B:
             raise ValueError("%d vectors for %d graphs" % (vectors.shape[0], B))
         joined = features.new_empty((B, vw + self.GRAPH_WIDTH))
-        layer = self.tower[1](self.tower[0](vectors))
+        layer = self.tower[1](self.tower[0](vectors) if vector_first is None else vector_first)
         vec = self.tower[2](layer, out=joined, out_col=0)
         node = self.dense(self.conv(features, adj=adj))
         graph = ops.graph_gather_into(node, joined, vw)                                           # :75
@@ -758,7 +761,8 @@ class MultimodalRegressionGCN(nn.Module):
       head (:88-90)           concat([vector, graph]) -> Dense(label_dim): the predictions
     The node-level body runs through layers.fused_stack when eligible (one launch each way), else layer by layer;
     GraphBatchNormalization honours enabled_node_nums.  The concatenation is one [B, 40] buffer (vector 0-7, graph 8-39).
-    forward(features, adjs, vectors=None, enabled_node_nums=None) -> predictions [B, label_dim]; loss: masked squared error."""
+    forward(features, adjs, vectors=None, enabled_node_nums=None) -> predictions [B, label_dim]; loss: masked squared error.
+    vector_first [B, 8]: the already computed output of `vec`, in place of `vectors` (copied into the joined buffer)."""
 
     ROW_INDEPENDENT = True
 
@@ -776,14 +780,16 @@ class MultimodalRegressionGCN(nn.Module):
         self.vec = KerasDenseBN(self.VEC_WIDTH, activation="relu")                                # :84-86
         self.out = KerasDenseBN(int(label_dim), batch_norm=False)                                 # :90
 
-    def forward(self, features, adjs, vectors=None, enabled_node_nums=None):
+    def forward(self, features, adjs, vectors=None, enabled_node_nums=None, vector_first=None):
+        if vector_first is not None:                  # the output of `vec` [B, 8], already computed, in place of `vectors`
+            vectors = vector_first
         if vectors is None:
             raise ValueError("MultimodalRegressionGCN needs the vectors= batch")
         B, N = features.shape[0], features.shape[1]
         if vectors.shape[0] != B:
             raise ValueError("%d vectors for %d graphs" % (vectors.shape[0], B))
         joined = features.new_empty((B, self.VEC_WIDTH + self.WIDTH))
-        vec = self.vec(vectors, out=joined, out_col=0)
+        vec = self.vec(vectors, out=joined, out_col=0) if vector_first is None else ops.activation_into(vector_first, None, joined, 0)
         body = [self.dense1, self.bn1, self.dense2, self.bn2, self.dense3, self.bn3]
         pooled = None if adjs is None else layers.fused_stack(body, features, layers._pack(adjs, features),
                                                               enabled_node_nums=enabled_node_nums, gather=True)

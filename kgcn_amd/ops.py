@@ -2106,8 +2106,8 @@ def seq_conv_pool_scaled(tokens, table, w, bias, pool, scale, rep, argmax=False)
 
 
 # noise streams of the smooth attribution methods
-IG_STREAM_FEATURES, IG_STREAM_ADJACENCY, IG_STREAM_SEQUENCE = (_lib.K[n] for n in (
-    "KGCN_IG_STREAM_FEATURES", "KGCN_IG_STREAM_ADJACENCY", "KGCN_IG_STREAM_SEQUENCE"))
+IG_STREAM_FEATURES, IG_STREAM_ADJACENCY, IG_STREAM_SEQUENCE, IG_STREAM_VECTOR = (_lib.K[n] for n in (
+    "KGCN_IG_STREAM_FEATURES", "KGCN_IG_STREAM_ADJACENCY", "KGCN_IG_STREAM_SEQUENCE", "KGCN_IG_STREAM_VECTOR"))
 
 
 def _i32_row(v, name, n, device):
@@ -2963,11 +2963,11 @@ def cpi_ig_limits_check(nodes, width, tasks, steps):
     return N, Wd, T, K
 
 
-def _f32_vector(v, n, name, device):
+def _f32_vector(v, n, name, device, who="cpi_ig"):
     import numpy as np
     t = _f32c(v.detach(), name).reshape(-1) if torch.is_tensor(v) else torch.as_tensor(np.asarray(v, np.float32).reshape(-1), device=device)
     if t.numel() != n:
-        raise ValueError("cpi_ig: %s has %d entries, expected %d" % (name, t.numel(), n))
+        raise ValueError("%s: %s has %d entries, expected %d" % (who, name, t.numel(), n))
     return t
 
 
@@ -3024,3 +3024,78 @@ def spmm_values_grad(csr, grad, rhs, rhs_ld=None, rhs_gs=None):
     check(lib.kgcn_spmm_values_grad_f32(csr.desc(), ptr(grad), d, csr.rows * d, ptr(rhs), rhs_ld, rhs_gs, d, ptr(dv),
                                         current_stream()), "kgcn_spmm_values_grad_f32")
     return dv
+
+
+# -------------------------------------------------------------------------------------------------
+# integrated gradients over the per-graph vector of the vector-modality models (csrc/vecig.hip): the scaled copies of the vector
+# branch's first layer, expanded from one product per compound and reduced to one gradient per compound
+# -------------------------------------------------------------------------------------------------
+IG_COPIES_MAX_WIDTH, IG_COPIES_MAX_COPIES, IG_COPIES_MAX_ROWS = (_lib.K[n] for n in (
+    "KGCN_IG_COPIES_MAX_WIDTH", "KGCN_IG_COPIES_MAX_COPIES", "KGCN_IG_COPIES_MAX_ROWS"))
+
+
+def ig_copies_limits_check(compounds, copies, width):
+    """The ranges csrc/vecig.hip serves, on the host: 1 <= H <= IG_COPIES_MAX_WIDTH, 1 <= K <= IG_COPIES_MAX_COPIES, C >= 0 with
+    C K <= IG_COPIES_MAX_ROWS -> (C, K, H)."""
+    C, K, H = int(compounds), int(copies), int(width)
+    if not 1 <= H <= IG_COPIES_MAX_WIDTH:
+        raise ValueError("ig_copies: H = %d columns outside 1..%d" % (H, IG_COPIES_MAX_WIDTH))
+    if not 1 <= K <= IG_COPIES_MAX_COPIES:
+        raise ValueError("ig_copies: K = %d copies outside 1..%d" % (K, IG_COPIES_MAX_COPIES))
+    if C < 0 or C * K > IG_COPIES_MAX_ROWS:
+        raise ValueError("ig_copies: %d compounds x %d copies outside 0..%d rows" % (C, K, IG_COPIES_MAX_ROWS))
+    return C, K, H
+
+
+@torch.no_grad()
+def ig_copies_expand(P, alpha, bias=None, gamma=None, beta=None, moving_mean=None, moving_variance=None, eps=1e-3, activation=None,
+                     out=None, out_col=0):
+    """The first Dense + BatchNormalization + activation layer of K scaled copies of C inputs from ONE product per input:
+    P [C, H] = v W, alpha [K] -> Y [C K, H], Y[c K + k] = act(bn(alpha[k] P[c] + bias)) with bn(x) = gamma (x - moving_mean) /
+    sqrt(moving_variance + eps) + beta (learning phase 0; gamma None, then beta and the statistics None too: no normalisation).
+    The fp32 operations are those of dense -> graph_bn after the GEMM: a copy with alpha 1 is that layer applied to the same P,
+    bit for bit.  out / out_col: Y goes into columns out_col .. out_col + H of the contiguous [C K, wide] buffer `out` and is
+    returned as that view (as dense_bn writes).  A read-out: no autograd."""
+    act = act_code(activation)
+    if (gamma is None) != (beta is None) or (gamma is None) != (moving_mean is None) or (gamma is None) != (moving_variance is None):
+        raise ValueError("ig_copies_expand: gamma, beta, moving_mean and moving_variance come together or not at all")
+    require_gpu(P, "P")
+    if P.dim() != 2:
+        raise ValueError("ig_copies_expand: P must be [C, H], got %s" % (tuple(P.shape),))
+    P = _f32c(P.detach(), "P")
+    dev = P.device
+    K = alpha.numel() if torch.is_tensor(alpha) else len(alpha)
+    C, K, H = ig_copies_limits_check(P.shape[0], K, P.shape[1])
+    alpha = _f32_vector(alpha, K, "alpha", dev, "ig_copies_expand")
+    b, ga, be, mu, va = (None if v is None else _f32_vector(v, H, n, dev, "ig_copies_expand") for v, n in (
+        (bias, "bias"), (gamma, "gamma"), (beta, "beta"), (moving_mean, "moving_mean"), (moving_variance, "moving_variance")))
+    out, y = _column_block(out, int(out_col), C * K, H, dev)
+    check(lib.kgcn_ig_copies_expand_f32(ptr(P), C, K, H, ptr(alpha), ptr(b), ptr(ga), ptr(be), ptr(mu), ptr(va), float(eps), int(act),
+                                        y.data_ptr(), y.stride(0) if C * K else H, current_stream()), "kgcn_ig_copies_expand_f32")
+    return y
+
+
+@torch.no_grad()
+def ig_copies_reduce(dY, Y, weights, scale=None, activation=None):
+    """The weighted sum over the K copies of every input of the gradient with respect to the first layer's pre-activation:
+    dY, Y [C K, H] (the gradient arriving at the layer's output and that output; rows may be strided), weights [K], scale [H]
+    (the normalisation's gamma / sqrt(moving_variance + eps); None: ones) -> S [C, H] = scale sum_k weights[k] dY[c K + k]
+    act'(Y[c K + k]), summed over k in order in fp32.  A copy of weight 0 is skipped: whatever its dY rows hold (NaN included) never reaches the sum.  S W^T is then
+    the summed gradient with respect to the layer's input.  A read-out: no autograd; bitwise reproducible, and an input's row
+    does not depend on the others in the call."""
+    act = act_code(activation)
+    if Y.dim() != 2 or tuple(dY.shape) != tuple(Y.shape):
+        raise ValueError("ig_copies_reduce: dY and Y must both be [C K, H], got %s and %s" % (tuple(dY.shape), tuple(Y.shape)))
+    rows, H = Y.shape
+    K = weights.numel() if torch.is_tensor(weights) else len(weights)
+    if K < 1 or rows % K:
+        raise ValueError("ig_copies_reduce: %d rows are not copies of %d weights" % (rows, K))
+    C, K, H = ig_copies_limits_check(rows // K, K, H)
+    dY, Y = _row_strided(dY.detach(), H, "dY"), _row_strided(Y.detach(), H, "Y")
+    dev = Y.device
+    w = _f32_vector(weights, K, "weights", dev, "ig_copies_reduce")
+    sc = None if scale is None else _f32_vector(scale, H, "scale", dev, "ig_copies_reduce")
+    S = torch.empty((C, H), device=dev, dtype=torch.float32)
+    check(lib.kgcn_ig_copies_reduce_f32(dY.data_ptr(), dY.stride(0) if rows else H, Y.data_ptr(), Y.stride(0) if rows else H, C, K, H,
+                                        ptr(w), ptr(sc), int(act), ptr(S), current_stream()), "kgcn_ig_copies_reduce_f32")
+    return S

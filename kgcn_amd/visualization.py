@@ -430,6 +430,287 @@ def multimodal_integrated_gradients(model, features, adjacency, tokens, labels=N
 
 
 # -------------------------------------------------------------------------------------------------
+# the vector-modality models (example_model/model_multimodal_vec.py, vector `profeat`; model_multimodal_regression.py, vector
+# `dragon`): kgcn/visualization.py:106-111, :128-132 and kgcn/feed.py:201-206 treat the per-graph vector like any other modality.
+# The vector branch is fused over the copies (csrc/vecig.hip)
+# -------------------------------------------------------------------------------------------------
+VECMODAL_VECTOR_NAMES = {"MultimodalVecGCN": "profeat", "MultimodalRegressionGCN": "dragon"}
+# The default of `fused` per model follows the measurement (tools/vecmodal_ig_bench.py, profiles/vecmodal_ig_bench.json: 256 compounds,
+# N = 50, F = 81, D = 100 on the MI355X).  The fused route was NOT ahead at either model: the whole call took 16.0 ms fused against
+# 15.5 ms composed for MultimodalVecGCN (Dv = 1437 -> 300; 29.2 against 28.7 ms with every modal) and 12.7 against 12.7 ms for
+# MultimodalRegressionGCN (Dv = 37 -> 8), differences inside the run-to-run spread of 3-4 %.  The D + 1 copies of the GRAPH branch
+# (1.3 million node rows), which both routes run through the same layers, and the host side of the call carry the time; the first
+# vector layer's GEMM over all copies, which the fused route removes, is a small part of it.  So both models default to the
+# composed route, as ops.short_dense_fusion is off: the fused route stays available (fused=True), tested to the same bounds.
+VECMODAL_IG_FUSED = {"MultimodalVecGCN": False, "MultimodalRegressionGCN": False}
+
+
+def vecmodal_ig_targets(model, modal, vector_name=None):
+    """-> (targets, vector name): the modals `modal` names for a vector-modality model.  'features', 'adjs' and the vector's own
+    name ('profeat' / 'dragon', or vector_name) are the modals; 'all' is every modal the model differentiates.
+    MultimodalRegressionGCN never reads the adjacency -- the reference drops a target whose tf.gradients is None (:80-87) -- so
+    'adjs' is not in its 'all', and asking for it raises."""
+    from . import models
+    if not isinstance(model, (models.MultimodalVecGCN, models.MultimodalRegressionGCN)) or not getattr(model, "ROW_INDEPENDENT", False):
+        raise TypeError("vecmodal_integrated_gradients batches the scaled copies as rows and feeds the vector branch's first layer: "
+                        "it needs a models.MultimodalVecGCN or models.MultimodalRegressionGCN, got %s" % type(model).__name__)
+    name = VECMODAL_VECTOR_NAMES[type(model).__name__] if vector_name is None else str(vector_name)
+    if name in ("features", "adjs", "all"):
+        raise ValueError("vector_name %r is the name of another modal" % (name,))
+    regression = isinstance(model, models.MultimodalRegressionGCN)
+    modals = ("features", name) if regression else ("features", "adjs", name)
+    if modal == "all":
+        return modals, name
+    if modal == "adjs" and regression:
+        raise ValueError("models.MultimodalRegressionGCN never reads the adjacency: its prediction has no gradient with respect to "
+                         "'adjs' (modal must be 'all' or one of %s)" % ", ".join(modals))
+    if modal not in modals:
+        raise ValueError("modal must be 'all' or one of %s, got %r" % (", ".join(modals), modal))
+    return (modal,), name
+
+
+def _vecmodal_first_layer(model):
+    """The vector branch's first Dense + BatchNormalization + relu and what the fused route needs of it, formed once per call."""
+    from . import models
+    layer = model.vec if isinstance(model, models.MultimodalRegressionGCN) else model.tower[0]
+    W = layer.kernel.detach().contiguous()
+    par = {"layer": layer, "W": W, "Wt": W.t().contiguous(), "bias": layer.bias.detach(), "act": layer.activation, "bn": {}, "scale": None}
+    if layer.batch_norm:
+        par["bn"] = {"gamma": layer.gamma.detach(), "beta": layer.beta.detach(), "moving_mean": layer.moving_mean,
+                     "moving_variance": layer.moving_variance, "eps": layer.eps}
+        par["scale"] = layer.gamma.detach() / torch.sqrt(layer.moving_variance + layer.eps)
+    return par
+
+
+def _vecmodal_chunk(model, dataset, vtab, sizes, ids, plan, targets, vname, masks, first, fused, need_grad=True):
+    """One forward + backward over len(ids) compounds x len(plan['scales']) copies -> per compound the weighted sums over the copies
+    ('features' [C, N, F], 'adjs' dense [C, N, N] beside 'adjs_data', the vector [C, 1, Dv]; unmultiplied by the data for 'grad'
+    and 'smooth_grad') and the scores of the start and the end copy.  The graph branch is _copy_grads': the copies are batch rows
+    of the model's own layers.  The vector branch, fused: P = v W once per compound (ops.dense), the first layer of every clean
+    copy from ops.ig_copies_expand (of every noisy copy from the layer itself, without a graph), handed to the model as
+    vector_first; the gradient arriving there goes through ops.ig_copies_reduce and ONE [C, H] x W^T product.  Not fused: the
+    scaled or perturbed vectors go in as vectors= and the per-copy gradients are summed."""
+    from . import models, ops
+    scales, weights, noise, method = plan["scales"], plan["weights"], plan["noise"], plan["method"]
+    ids = [int(i) for i in ids]
+    C, rep = len(ids), len(scales)
+    dev = dataset.features.device
+    regression = isinstance(model, models.MultimodalRegressionGCN)
+    adj, x = dataset.batch([i for i in ids for _ in range(rep)])
+    N, F = x.shape[1], x.shape[2]
+    sc = torch.tensor(scales, dtype=torch.float32, device=dev).repeat(C)
+    idt = torch.as_tensor(ids, device=dev)
+    v = vtab[idt]
+    Dv = v.shape[1]
+    if noise is not None:
+        sg = torch.tensor(noise[0], dtype=torch.float32, device=dev).repeat(C)
+        smp = torch.tensor(noise[1], dtype=torch.int32, device=dev).repeat(C)
+        cid = torch.tensor(ids, dtype=torch.int32, device=dev)
+        seed = noise[2]
+    want = lambda m: need_grad and m in targets
+    # the graph branch: node features and adjacency values as batch rows
+    if "features" not in targets:
+        x_in = x
+    elif noise is None:
+        x_in = (x * sc.view(-1, 1, 1)).requires_grad_(need_grad)
+    else:
+        x_in = ops.ig_perturb(x.view(C, rep, N, F)[:, 0], sc, sg, smp, cid, rep, ops.IG_STREAM_FEATURES, seed).requires_grad_(need_grad)
+    adj_in, v0 = adj, None
+    if "adjs" in targets:                       # kgcn/feed.py:116-121: the values of every channel are scaled
+        if noise is None:
+            vals = [c.values * sc[_entry_graphs(c)] for c in adj.channels]
+        else:
+            rows = cid.repeat_interleave(rep)
+            vals = [ops.ig_perturb_values(c, c.values, sc, sg, smp, rows, ops.IG_STREAM_ADJACENCY + ch, seed)
+                    for ch, c in enumerate(adj.channels)]
+        v0 = vals[0].requires_grad_(need_grad)
+        adj_in = adj.with_values(vals)
+    # the vector branch
+    leaf = None
+    if vname not in targets:                    # kgcn/feed.py:205: not a target, fed as it is
+        kw = {"vectors": v.repeat_interleave(rep, 0)}
+    else:
+        with torch.no_grad():
+            if noise is not None:
+                fed = ops.ig_perturb(v.view(C, 1, Dv), sc, sg, smp, cid, rep, ops.IG_STREAM_VECTOR, seed).view(C * rep, Dv)
+                leaf = first["layer"](fed) if fused else fed
+            elif fused:
+                P = _cpi_dense(v, first["W"], 1)
+                leaf = ops.ig_copies_expand(P, scales, first["bias"], activation=first["act"], **first["bn"])
+            else:
+                leaf = v.repeat_interleave(rep, 0) * sc.view(-1, 1)
+        leaf = leaf.detach().requires_grad_(need_grad)
+        kw = {"vector_first" if fused else "vectors": leaf}
+    if regression and sizes is not None:
+        kw["enabled_node_nums"] = sizes[idt].repeat_interleave(rep)
+    with torch.set_grad_enabled(need_grad):
+        out = model(x_in, adj_in, **kw)
+        pred = out if regression else torch.softmax(out, dim=1)
+        score = (pred * torch.as_tensor(masks, device=dev).repeat_interleave(rep, 0)).sum(1)
+    grads = []
+    if need_grad:
+        wrt = ([x_in] if "features" in targets else []) + ([v0] if v0 is not None else []) + ([leaf] if leaf is not None else [])
+        grads = list(torch.autograd.grad(score.sum(), wrt))
+    wt = torch.tensor(weights, dtype=torch.float32, device=dev)
+    wv = wt.repeat(C).view(C, rep, 1, 1)
+    raw = method in ("grad", "smooth_grad")
+    res = {}
+    with torch.no_grad():
+        if "features" in targets:
+            ig = (grads.pop(0).view(C, rep, N, F) * wv).sum(1) if need_grad else torch.zeros((C, N, F), device=dev)
+            res["features"] = ig if raw else ig * x.view(C, rep, N, F)[:, 0]
+        if "adjs" in targets:
+            c0 = adj.channels[0]
+            data = values_to_dense(c0, c0.values).view(C, rep, N, N)[:, 0]
+            ig = (values_to_dense(c0, grads.pop(0)).view(C, rep, N, N) * wv).sum(1) if need_grad else torch.zeros_like(data)
+            res["adjs"], res["adjs_data"] = (ig if raw else ig * data), data
+        if vname in targets:
+            if not need_grad:
+                dv = torch.zeros_like(v)
+            elif fused:
+                S = ops.ig_copies_reduce(grads.pop(0), leaf, wt, first["scale"], first["act"])
+                dv = _cpi_dense(S, first["Wt"], 1)
+            else:
+                dv = (grads.pop(0).view(C, rep, Dv) * wv.view(C, rep, 1)).sum(1)
+            res[vname] = (dv if raw else dv * v).view(C, 1, Dv)
+    s = score.detach().view(C, rep)
+    res["start"], res["end"] = s[:, plan["start_row"]], s[:, plan["end_row"]]
+    return res
+
+
+def vecmodal_integrated_gradients(model, features, adjacency, vectors, labels=None, divide_number=100, modal="all", method="ig",
+                                  label_target="max", vector_name=None, chunk=None, compounds=None, fused=None, noise_scale=0.1,
+                                  seed=1234, enabled_node_nums=None):
+    """`kgcn visualize` of the vector-modality models (kgcn/visualization.py:22-285 and :442-574 with info.vector_modal_name set,
+    :106-111 and :128-132) for a models.MultimodalVecGCN (vector `profeat`) or models.MultimodalRegressionGCN (vector `dragon`)
+    -> one dict per visualised compound with the keys the reference dumps: features / features_IG [N, F], adjs / adjs_IG [N, N]
+    (channel 0, dense), <vector name> [Dv] / <vector name>_IG [1, Dv] (the reference accumulates into zeros((1, Dv))) for the
+    modals named by `modal`, check_score (end - start), sum_of_IG, prediction_score, target_label, true_label, mol / mol_smiles /
+    mol_id (None: no RDKit) -- plus compound_id and assay (dump_record drops them; ig_filename uses them).
+
+    features [G, N, F] and adjacency (the channels of data_util.build_adjs), or a data_util.DeviceGraphDataset as `adjacency`
+    (features None); vectors [G, Dv] (data_util.vector_table, or a host array); labels [G, K] (true_label = argmax; needed by
+    label_target 'label', 'correct', 'uncorrect'); enabled_node_nums [G]: the node counts MultimodalRegressionGCN's
+    GraphBatchNormalization masks with (None: every row counts; the other model ignores them).
+    modal: 'all', 'features', 'adjs' or the vector's name (vecmodal_ig_targets; vector_name defaults to the model's).  The same
+    set is scaled and attributed; a vector that is not a target is fed unscaled (kgcn/feed.py:205).
+    method: 'ig', 'grad_prod', 'grad' (ig_scales) or 'smooth_grad', 'smooth_ig' (smooth_rows), with noise N(0, noise_scale)
+    drawn on the device from (seed, dataset index, sample): the vector is perturbed as a [1, Dv] row set on the stream
+    ops.IG_STREAM_VECTOR, so chunking and `compounds` subsets see the same values.
+    Score: the softmax probability of the target class (MultimodalVecGCN); the prediction column itself
+    (MultimodalRegressionGCN: predictions = logits, one task of label_dim entries, cal_feature_IG :488-499).  The target comes
+    from an unscaled forward pass through select_label_target.
+
+    The copies of every compound run as batch rows of one forward and one backward, `chunk` compounds (default
+    IG_ROWS_PER_CHUNK // copies) at a time; chunking does not change a bit.  fused=True: the vector branch's first layer --
+    Dense(Dv -> 300), respectively Dense(Dv -> 8), by far the largest of the tower -- is not run per copy: a clean copy's
+    pre-activation is alpha_k (v W) + b, so v W is formed once per compound and ops.ig_copies_expand sweeps the copies; the
+    gradient with respect to the fed vector is dpre_k W^T, linear in dpre_k for the smooth methods too, so
+    ops.ig_copies_reduce sums the copies and ONE [C, H] x W^T product follows.  No per-copy [C K, Dv] gradient is formed.
+    fused=False: the scaled or perturbed vectors go through the model as vectors=, with autograd to them.  fused=None (the
+    default): the route the measurement favours for the model, VECMODAL_IG_FUSED -- at present the composed one for both, see
+    there."""
+    import numpy as np
+    from . import models
+    from .data_util import DeviceGraphDataset
+    targets, vname = vecmodal_ig_targets(model, modal, vector_name)
+    regression = isinstance(model, models.MultimodalRegressionGCN)
+    if method in SMOOTH_METHODS:
+        scales, sigmas, samples, weights, start_row, end_row = smooth_rows(method, divide_number, noise_scale)
+        noise = (sigmas, samples, int(seed))
+    elif method in IG_METHODS:
+        scales, weights = ig_scales(method, divide_number)
+        noise, start_row, end_row = None, 0, len(scales) - 1
+    else:
+        raise ValueError("unsupported method %r (%s)" % (method, ", ".join(IG_METHODS + SMOOTH_METHODS)))
+    rep = len(scales)
+    chunk = max(1, IG_ROWS_PER_CHUNK // rep) if chunk is None else int(chunk)
+    if chunk < 1:
+        raise ValueError("chunk must be >= 1")
+    if vectors is None:
+        raise ValueError("the vector modality %r is missing (vectors [G, Dv])" % (vname,))
+    fused = VECMODAL_IG_FUSED[type(model).__name__] if fused is None else bool(fused)
+    if isinstance(adjacency, DeviceGraphDataset):
+        dataset = adjacency
+    else:
+        dev = next(model.parameters(), torch.zeros(0, device="cuda")).device
+        dataset = DeviceGraphDataset(adjacency, features.detach().cpu().numpy() if torch.is_tensor(features) else features, device=dev)
+    if dataset.features is None:
+        raise ValueError("the dataset carries no node features")
+    dev = dataset.features.device
+    G = dataset.num_graphs
+    vtab = (vectors.detach() if torch.is_tensor(vectors) else torch.as_tensor(np.asarray(vectors, np.float32))).to(dev, torch.float32)
+    if vtab.dim() != 2 or vtab.shape[0] != G:
+        raise ValueError("vectors %s for %d graphs: expected [G, Dv]" % (tuple(vtab.shape), G))
+    vtab = vtab.contiguous()
+    sizes = None
+    if enabled_node_nums is not None:
+        sizes = torch.as_tensor(np.asarray(enabled_node_nums.detach().cpu().numpy() if torch.is_tensor(enabled_node_nums)
+                                           else enabled_node_nums).astype(np.int32).reshape(-1), device=dev)
+        if sizes.numel() != G:
+            raise ValueError("%d enabled_node_nums for %d graphs" % (sizes.numel(), G))
+    ids = list(range(G)) if compounds is None else [int(i) for i in compounds]
+    lab = None if labels is None else np.asarray(labels.detach().cpu().numpy() if torch.is_tensor(labels) else labels)
+
+    def forward_kw(part):
+        idt = torch.as_tensor(part, device=dev)
+        kw = {"vectors": vtab[idt]}
+        if regression and sizes is not None:
+            kw["enabled_node_nums"] = sizes[idt]
+        return kw
+
+    # the unscaled pass: the prediction the target is read from (:479-485); it also builds a freshly made model
+    preds = []
+    with torch.no_grad():
+        for i in range(0, len(ids), chunk):
+            part = ids[i:i + chunk]
+            adj, x = dataset.batch(part)
+            out = model(x, adj, **forward_kw(part))
+            preds.append((out if regression else torch.softmax(out, 1)).cpu().numpy())
+    preds = np.concatenate(preds) if preds else np.zeros((0, 0), np.float32)
+    jobs = []
+    for j, cid in enumerate(ids):
+        true_label = None if lab is None else int(np.argmax(lab[cid]))
+        sel = select_label_target(preds[j], label_target, true_label)
+        if sel is not None:
+            jobs.append((cid, preds[j], true_label) + sel)
+    plan = {"scales": scales, "weights": weights, "noise": noise, "method": method, "start_row": start_row, "end_row": end_row}
+    frozen = [(p, p.requires_grad) for p in model.parameters()]
+    res = {}
+    try:
+        for p, _ in frozen:
+            p.requires_grad_(False)
+        first = _vecmodal_first_layer(model) if jobs else None
+        for i in range(0, len(jobs), chunk):
+            part = jobs[i:i + chunk]
+            out = _vecmodal_chunk(model, dataset, vtab, sizes, [j[0] for j in part], plan, targets, vname,
+                                  np.stack([j[5] for j in part]), first, fused)
+            host = {m: t.detach().cpu().numpy() for m, t in out.items()}
+            for k, j in enumerate(part):
+                res[j[0]] = {m: a[k] for m, a in host.items()}
+    finally:
+        for p, r in frozen:
+            p.requires_grad_(r)
+    results = []
+    for cid, pred, true_label, tidx, tscore, _ in jobs:
+        r = res[cid]
+        rec = {"compound_id": cid, "assay": assay_string(pred, tidx)}
+        data = {"features": lambda: dataset.features[cid].cpu().numpy(), "adjs": lambda: r["adjs_data"],
+                vname: lambda: vtab[cid].cpu().numpy()}
+        total = 0.0
+        for m in targets:
+            rec[m] = data[m]()
+            rec[m + "_IG"] = r[m]
+            total += float(rec[m + "_IG"].astype(np.float64).sum())
+        rec["check_score"] = float(r["end"]) - float(r["start"])
+        rec["sum_of_IG"] = total
+        rec.update({"mol": None, "mol_smiles": None, "mol_id": None, "prediction_score": tscore, "target_label": tidx,
+                    "true_label": true_label})
+        results.append(rec)
+    return results
+
+
+# -------------------------------------------------------------------------------------------------
 # the link-prediction model (sample_kg/network_prediction/model_py/{gcn,distmult,ip}.py): kgcn/visualization.py:289-439
 # (KnowledgeGraphVisualizer, cal_feature_IG_for_kg), many targets per launch
 # -------------------------------------------------------------------------------------------------
