@@ -10,6 +10,9 @@ score_fn(features, adjacency) -> scalar tensor (e.g. one softmax probability of 
 is a kgcn_amd.BatchedAdjacency whose channel-0 values arrive as a differentiable tensor
 (BatchedAdjacency.with_values), features a [B, N, F] tensor.
 """
+import collections
+import contextlib
+
 import torch
 
 
@@ -94,18 +97,46 @@ def integrated_gradients(score_fn, features, adjacency, divide_number=100, modal
     return res
 
 
+def _entry_rows(csr):
+    """Row index (graph * rows + row) of every stored entry of a batched CSR, in CSR order."""
+    rp = csr.rowptr.long()
+    return torch.repeat_interleave(torch.arange(rp.numel() - 1, device=rp.device), rp[1:] - rp[:-1])
+
+
+def _entry_graphs(csr):
+    """Graph index of every stored entry of a batched CSR, in CSR order."""
+    return torch.div(_entry_rows(csr), csr.rows, rounding_mode="floor")
+
+
 def values_to_dense(csr, values):
     """sparse_to_dense_core of the reference (:208): per-entry values of channel 0 -> dense [T, M, K]."""
-    rp = csr.rowptr.long()
-    rows = torch.repeat_interleave(torch.arange(rp.numel() - 1, device=rp.device), rp[1:] - rp[:-1])
     dense = torch.zeros((csr.num_graphs * csr.rows, csr.cols), device=values.device, dtype=values.dtype)
-    dense.index_put_((rows, csr.cv[:, 0].long()), values, accumulate=True)
+    dense.index_put_((_entry_rows(csr), csr.cv[:, 0].long()), values, accumulate=True)
     return dense.reshape(csr.num_graphs, csr.rows, csr.cols)
 
 
 # -------------------------------------------------------------------------------------------------
-# the multimodal model (example_model/model_multimodal.py built with feed_embedded_layer=True, gcn.py:637-656):
-# kgcn/visualization.py:22-285 (CompoundVisualizer) and :442-574 (cal_feature_IG), batched
+# the compound drivers (multimodal_, vecmodal_ and cpi_integrated_gradients) and the host protocol they share:
+# kgcn/visualization.py:22-285 (CompoundVisualizer) and :442-574 (cal_feature_IG), batched.  What holds for all three:
+#   inputs   features [G, N, F] and adjacency (the channels of data_util.build_adjs), or a data_util.DeviceGraphDataset as
+#            `adjacency` (features None); labels, needed by label_target 'label', 'correct' and 'uncorrect'; compounds: dataset
+#            indices (default all).  The modals named by `modal` are both scaled and attributed (:58-71, :552-553).
+#   methods  'ig', 'grad_prod', 'grad' (ig_scales) and, where the driver takes them, 'smooth_grad' / 'smooth_ig' (:235-259,
+#            smooth_rows): D noisy samples beside two clean copies, the targeted inputs being x * scale + N(0, noise_scale)
+#            (kgcn/feed.py:88, gcn.py:661 default 0.1; the values of EVERY adjacency channel when 'adjs' is a target, feed.py:116-121).
+#            smooth_grad returns the mean gradient, smooth_ig the mean gradient times the clean data; check_score comes from the
+#            two clean copies.
+#   targets  every compound's target is read from an unscaled forward pass through select_label_target (_ig_jobs).
+#   copies   the copies of one compound -- its scaled or perturbed inputs, ig_row_plan -- are batch rows of ONE forward and ONE
+#            backward, `chunk` compounds (default IG_ROWS_PER_CHUNK // copies) at a time with the parameters frozen
+#            (frozen_parameters); this is valid only because the model mixes no rows, and any other model is refused.  The graph
+#            branch of the copies is _graph_copies', their weighted sum _reduce_graph_copies'.  Chunking and `compounds` subsets do
+#            not change a bit of a compound's result: the noise of the smooth methods is drawn on the device from (seed, dataset
+#            index of the compound, sample number) -- include/kgcn_hip.h.
+#   records  one dict per job with the keys the reference dumps (_ig_record): features / features_IG [N, F], adjs / adjs_IG [N, N]
+#            (channel 0, dense) for the targeted modals, check_score (end - start), sum_of_IG, prediction_score, target_label,
+#            true_label, mol / mol_smiles / mol_id (None: no RDKit) -- plus compound_id and assay, which dump_record drops and
+#            ig_filename uses.
 # -------------------------------------------------------------------------------------------------
 IG_MODALS = ("features", "adjs", "embedded_layer")
 IG_METHODS = ("ig", "grad_prod", "grad")
@@ -145,6 +176,29 @@ def smooth_rows(method, divide_number, noise_scale):
         raise ValueError("noise_scale must be >= 0, got %r" % (noise_scale,))
     scales = [0.0, 1.0] + [1.0 if method == "smooth_grad" else (k + 1) / float(D) for k in range(D)]
     return scales, [0.0, 0.0] + [ns] * D, [0, 0] + list(range(D)), [0.0, 0.0] + [1.0 / D] * D, 0, 1
+
+
+IG_RAW_METHODS = ("grad", "smooth_grad")          # the summed gradient itself, not multiplied by the clean data
+IGRowPlan = collections.namedtuple("IGRowPlan", "scales weights noise method start_row end_row")
+
+
+def ig_row_plan(method, divide_number, noise_scale=0.1, seed=1234):
+    """The copies of one compound for any method, as the chunk functions take them -> IGRowPlan: scales and weights per copy,
+    noise = None (ig_scales: 'ig', 'grad_prod', 'grad') or (sigmas, samples, seed) per copy (smooth_rows), the method, and the
+    copies whose scores are start_score and end_score."""
+    if method in SMOOTH_METHODS:
+        scales, sigmas, samples, weights, start_row, end_row = smooth_rows(method, divide_number, noise_scale)
+        return IGRowPlan(scales, weights, (sigmas, samples, int(seed)), method, start_row, end_row)
+    if method in IG_METHODS:
+        scales, weights = ig_scales(method, divide_number)
+        return IGRowPlan(scales, weights, None, method, 0, len(scales) - 1)
+    raise ValueError("unsupported method %r (%s)" % (method, ", ".join(IG_METHODS + SMOOTH_METHODS)))
+
+
+def ig_plan_row(plan, row):
+    """The one-copy plan of copy `row`: what a per-step loop hands the chunk functions, one batch-1 pass per copy."""
+    noise = None if plan.noise is None else ([plan.noise[0][row]], [plan.noise[1][row]], plan.noise[2])
+    return plan._replace(scales=[plan.scales[row]], weights=[plan.weights[row]], noise=noise, start_row=0, end_row=0)
 
 
 def ig_modal_targets(modal):
@@ -212,42 +266,104 @@ def dump_record(result):
     return {k: v for k, v in result.items() if k not in ("compound_id", "assay")}
 
 
-def _entry_graphs(csr):
-    """Graph index of every stored entry of a batched CSR, in CSR order."""
-    rp = csr.rowptr.long()
-    rows = torch.repeat_interleave(torch.arange(rp.numel() - 1, device=rp.device), rp[1:] - rp[:-1])
-    return torch.div(rows, csr.rows, rounding_mode="floor")
+def _host_array(a):
+    """A host array of labels or sizes given as a tensor or anything numpy takes; None stays None."""
+    import numpy as np
+    return None if a is None else np.asarray(a.detach().cpu().numpy() if torch.is_tensor(a) else a)
 
 
-def _copy_grads(model, dataset, tokens, ids, scales, targets, masks, noise=None, need_grad=True):
-    """One forward + backward over len(ids) compounds x len(scales) copies -> the per-copy quantities _reduce_copies sums: the clean
-    features x, the gradients with respect to the targeted inputs ('features' [B, N, F], 'adjs' channel 0 dense [B, N, N] beside
-    its data 'adjs_data', 'pooled' d pooled with its arg-max bytes 'arg' for the embedded sequence), the token rows and the score
-    [B].  masks [C, K] selects the target class(es) of each compound.  noise = (sigmas, samples, seed) per copy: the targeted
-    inputs are x * scale + sigma * z with z drawn on the device for (seed, dataset index, sample) (ops.ig_perturb,
-    ops.ig_perturb_values, ops.seq_conv_pool_perturbed); None is the clean path.  need_grad=False: the forward alone (a copy of
-    weight 0, run for its score), the gradients zero and the arg-max bytes 0xFF."""
-    ids = [int(i) for i in ids]
-    C, rep = len(ids), len(scales)
-    dev = dataset.features.device
-    sel = [i for i in ids for _ in range(rep)]
-    adj, x = dataset.batch(sel)
-    sc = torch.tensor(scales, dtype=torch.float32, device=dev).repeat(C)
-    ones = torch.ones_like(sc)
-    N, F = x.shape[1], x.shape[2]
-    want = lambda m: need_grad and m in targets
-    seq_noise = None
-    if noise is None:
-        x_in = (x * sc.view(-1, 1, 1) if "features" in targets else x).requires_grad_(want("features"))
+def _parameter_device(model):
+    return next(model.parameters(), torch.zeros(0, device="cuda")).device
+
+
+def _compound_dataset(features, adjacency, device):
+    """The compounds as a data_util.DeviceGraphDataset: `adjacency` itself when it is one (features None), else one built from
+    features [G, N, F] and the channels of data_util.build_adjs on device(), which is called only then."""
+    from .data_util import DeviceGraphDataset
+    if isinstance(adjacency, DeviceGraphDataset):
+        dataset = adjacency
     else:
+        dev = device()
+        dataset = DeviceGraphDataset(adjacency, features.detach().cpu().numpy() if torch.is_tensor(features) else features, device=dev)
+    if dataset.features is None:
+        raise ValueError("the dataset carries no node features")
+    return dataset
+
+
+def _compounds_per_chunk(chunk, default):
+    """`chunk` as given, or the driver's default; at least one compound."""
+    chunk = max(1, default) if chunk is None else int(chunk)
+    if chunk < 1:
+        raise ValueError("chunk must be >= 1")
+    return chunk
+
+
+def _ig_jobs(predict, ids, step, label_target, entries):
+    """The unscaled pass (:479-485) and the choice of targets (:502-529).  predict(part) -> the predictions of the compounds `part`
+    as a host array [len(part), K]; it runs without autograd, `step` compounds at a time (and builds a freshly made model).
+    entries(cid, row) -> (key, prediction, true_label) of every attribution of compound cid, whose row of predictions is `row`.
+    Yields (key, prediction, true_label, target_index, target_score, class mask) for those select_label_target does not skip."""
+    import numpy as np
+    with torch.no_grad():
+        preds = [predict(ids[i:i + step]) for i in range(0, len(ids), step)]
+    preds = np.concatenate(preds) if preds else np.zeros((0, 0), np.float32)
+    for cid, row in zip(ids, preds):
+        for key, pred, true_label in entries(cid, row):
+            sel = select_label_target(pred, label_target, true_label)
+            if sel is not None:
+                yield (key, pred, true_label) + sel
+
+
+def _one_job_per_compound(lab):
+    """entries of _ig_jobs for one attribution per compound: the whole row of predictions, true_label = argmax of the label row."""
+    import numpy as np
+    return lambda cid, row: [(cid, row, None if lab is None else int(np.argmax(lab[cid])))]
+
+
+@contextlib.contextmanager
+def frozen_parameters(model):
+    """Inside the block no parameter of `model` requires a gradient (the attribution differentiates with respect to inputs alone);
+    on exit, after an exception too, every parameter has its own requires_grad back."""
+    frozen = [(p, p.requires_grad) for p in model.parameters()]
+    try:
+        for p, _ in frozen:
+            p.requires_grad_(False)
+        yield
+    finally:
+        for p, r in frozen:
+            p.requires_grad_(r)
+
+
+GraphCopies = collections.namedtuple("GraphCopies", "adj x x_in adj_in v0 sc wt noise")
+
+
+def _graph_copies(dataset, ids, plan, targets, need_grad=True):
+    """The graph branch of len(ids) compounds x len(plan.scales) copies -> GraphCopies: the repeated clean batch (adj, x); what
+    the model is fed, x_in and adj_in -- a targeted input is x * scale on the clean path and x * scale + sigma * z on the noisy
+    one (ops.ig_perturb, ops.ig_perturb_values), an input that is no target is fed as it is; v0, the values of channel 0 the
+    gradient is taken at (None unless 'adjs' is a target); the scale and the weight of every row, sc and wt [B] (formed before
+    the model runs: a host-to-device copy later would wait for it); and the noise operands (sigmas [B], samples [B], dataset
+    indices [C], seed) or None.  x_in and v0 are leaves that require a gradient iff need_grad."""
+    C, rep = len(ids), len(plan.scales)
+    dev = dataset.features.device
+    adj, x = dataset.batch([i for i in ids for _ in range(rep)])
+    sc = torch.tensor(plan.scales, dtype=torch.float32, device=dev).repeat(C)
+    wt = torch.tensor(plan.weights, dtype=torch.float32, device=dev).repeat(C)
+    noise = None
+    if plan.noise is not None:
         from . import ops
-        sg = torch.tensor(noise[0], dtype=torch.float32, device=dev).repeat(C)
-        smp = torch.tensor(noise[1], dtype=torch.int32, device=dev).repeat(C)
+        sg = torch.tensor(plan.noise[0], dtype=torch.float32, device=dev).repeat(C)
+        smp = torch.tensor(plan.noise[1], dtype=torch.int32, device=dev).repeat(C)
         cid = torch.tensor(ids, dtype=torch.int32, device=dev)
-        seed = noise[2]
-        x_in = (ops.ig_perturb(x.view(C, rep, N, F)[:, 0], sc, sg, smp, cid, rep, ops.IG_STREAM_FEATURES, seed)
-                if "features" in targets else x).requires_grad_(want("features"))
-        seq_noise = (sg, smp, cid, seed)
+        seed = plan.noise[2]
+        noise = (sg, smp, cid, seed)
+    x_in = x
+    if "features" in targets:
+        if noise is None:
+            x_in = x * sc.view(-1, 1, 1)
+        else:
+            x_in = ops.ig_perturb(x.view(C, rep, x.shape[1], x.shape[2])[:, 0], sc, sg, smp, cid, rep, ops.IG_STREAM_FEATURES, seed)
+        x_in.requires_grad_(need_grad)
     adj_in, v0 = adj, None
     if "adjs" in targets:                       # kgcn/feed.py:116-121: the values of every channel are scaled
         if noise is None:
@@ -258,37 +374,37 @@ def _copy_grads(model, dataset, tokens, ids, scales, targets, masks, noise=None,
                     for ch, c in enumerate(adj.channels)]
         v0 = vals[0].requires_grad_(need_grad)
         adj_in = adj.with_values(vals)
-    emb = "embedded_layer" in targets
-    tok = tokens[torch.as_tensor(ids, device=tokens.device)]
-    with torch.set_grad_enabled(need_grad):
-        logits, pooled, arg = model.run(x_in, adj_in, tok, sc if emb else ones, rep, input_grad=want("embedded_layer"),
-                                        sequence_noise=seq_noise if emb else None)
-        score = (torch.softmax(logits, dim=1) * torch.as_tensor(masks, device=dev).repeat_interleave(rep, 0)).sum(1)
-    gr = {"x": x, "tok": tok, "score": score.detach()}
-    grads = []
-    if need_grad:
-        wrt = ([x_in] if "features" in targets else []) + ([v0] if "adjs" in targets else []) + ([pooled] if emb else [])
-        grads = list(torch.autograd.grad(score.sum(), wrt))
-    if "features" in targets:
-        gr["features"] = grads.pop(0) if need_grad else torch.zeros_like(x)
+    return GraphCopies(adj, x, x_in, adj_in, v0, sc, wt, noise)
+
+
+def _copies_data(g, targets):
+    """What _reduce_graph_copies needs of the copies g beside their gradients and scores: the clean features 'x', the weights
+    'weight' and, where 'adjs' is a target, channel 0 dense as 'adjs_data' [B, N, N]."""
+    gr = {"x": g.x, "weight": g.wt}
     if "adjs" in targets:
-        c0 = adj.channels[0]
-        gr["adjs_data"] = values_to_dense(c0, c0.values)
-        gr["adjs"] = values_to_dense(c0, grads.pop(0)) if need_grad else torch.zeros_like(gr["adjs_data"])
-    if emb:
-        gr["pooled"] = grads.pop(0) if need_grad else torch.zeros_like(pooled)
-        gr["arg"] = arg if need_grad else torch.full(pooled.shape, 0xFF, dtype=torch.uint8, device=dev)
+        gr["adjs_data"] = values_to_dense(g.adj.channels[0], g.adj.channels[0].values)
     return gr
 
 
-def _reduce_copies(gr, C, weights, targets, method, table, conv_w, pool, ends=None):
-    """The copies of _copy_grads (C compounds x len(weights) copies, or as many one-copy results concatenated) -> per compound:
-    the weighted sums over the copies, in one fixed order for the batched and the per-step form alike (unmultiplied by the data
-    for 'grad' and 'smooth_grad'), start and end score (the copies ends = (start_row, end_row), default the first and the last)."""
-    rep = len(weights)
-    wt = torch.tensor(weights, dtype=torch.float32, device=gr["score"].device).repeat(C)
-    wv = wt.view(C, rep, 1, 1)
-    raw = method in ("grad", "smooth_grad")
+def _copies_grads(data, g, targets, grads):
+    """_copies_data plus the per-copy gradients of the targeted graph inputs, taken off the front of `grads` (what autograd returned
+    for [x_in, v0]; None = a forward-only pass, the gradients zero): 'features' [B, N, F], 'adjs' channel 0 dense [B, N, N]."""
+    gr = dict(data)
+    if "features" in targets:
+        gr["features"] = torch.zeros_like(g.x) if grads is None else grads.pop(0)
+    if "adjs" in targets:
+        gr["adjs"] = torch.zeros_like(data["adjs_data"]) if grads is None else values_to_dense(g.adj.channels[0], grads.pop(0))
+    return gr
+
+
+def _reduce_graph_copies(gr, C, plan, targets):
+    """The per-copy quantities of _copies_grads beside 'score' [B] (C compounds x B / C copies, or as many one-copy results
+    concatenated) -> per compound: 'features' and 'adjs', the sums over the copies weighted by 'weight', in one fixed order for
+    the batched and the per-step form alike, times the clean data unless plan.method is one of IG_RAW_METHODS; 'adjs_data';
+    'start' and 'end', the scores of the copies plan.start_row and plan.end_row."""
+    rep = gr["score"].shape[0] // C
+    wv = gr["weight"].view(C, rep, 1, 1)
+    raw = plan.method in IG_RAW_METHODS
     out = {}
     if "features" in targets:
         N, F = gr["x"].shape[1], gr["x"].shape[2]
@@ -300,132 +416,138 @@ def _reduce_copies(gr, C, weights, targets, method, table, conv_w, pool, ends=No
         data = gr["adjs_data"].view(C, rep, M, K)[:, 0]
         out["adjs"] = ig if raw else ig * data
         out["adjs_data"] = data
+    s = gr["score"].view(C, rep)
+    out["start"], out["end"] = s[:, plan.start_row], s[:, plan.end_row]
+    return out
+
+
+def _rows_to_host(res, keys, out):
+    """res[key] = row k of every tensor of `out` as a host array, for the k-th of `keys`; returns the host arrays."""
+    host = {m: t.detach().cpu().numpy() for m, t in out.items()}
+    for k, key in enumerate(keys):
+        res[key] = {m: a[k] for m, a in host.items()}
+    return host
+
+
+def _ig_record(rec, job, targets, data, ig, start, end, sum_of_ig=None):
+    """Completes the record of one job of _ig_jobs with the keys every compound driver dumps: for each target m the clean data
+    data[m]() as m and the attribution ig[m] as m + '_IG', and DUMP_KEYS_FIXED -- check_score = end - start; sum_of_IG, the fp64
+    sum of the record's own *_IG arrays, modal after modal (sum_of_ig where the driver has formed exactly that already); mol,
+    mol_smiles and mol_id None (no RDKit); the job's prediction_score, target_label and true_label."""
+    import numpy as np
+    _, _, true_label, tidx, tscore, _ = job
+    total = 0.0
+    for m in targets:
+        rec[m] = data[m]()
+        rec[m + "_IG"] = ig[m]
+        if sum_of_ig is None:
+            total += float(ig[m].astype(np.float64).sum())
+    rec["check_score"] = float(end) - float(start)
+    rec["sum_of_IG"] = total if sum_of_ig is None else float(sum_of_ig)
+    rec.update({"mol": None, "mol_smiles": None, "mol_id": None, "prediction_score": tscore, "target_label": tidx,
+                "true_label": true_label})
+    return rec
+
+
+# -------------------------------------------------------------------------------------------------
+# the multimodal model (example_model/model_multimodal.py built with feed_embedded_layer=True, gcn.py:637-656): the embedded
+# sequence is the third modal, attributed by the HIP input-gradient kernel of the conv-pool
+# -------------------------------------------------------------------------------------------------
+def _copy_grads(model, dataset, tokens, ids, plan, targets, masks, need_grad=True):
+    """One forward + backward over len(ids) compounds x len(plan.scales) copies -> the per-copy quantities _reduce_copies sums:
+    those of _copies_grads, 'pooled' d pooled with its arg-max bytes 'arg' for the embedded sequence (perturbed, on the noisy
+    path, by ops.seq_conv_pool_perturbed), the token rows and the score [B].  masks [C, K] selects the target class(es) of each
+    compound.  need_grad=False: the forward alone (a copy of weight 0, run for its score), the gradients zero and the arg-max
+    bytes 0xFF."""
+    ids = [int(i) for i in ids]
+    rep = len(plan.scales)
+    g = _graph_copies(dataset, ids, plan, targets, need_grad)
+    emb = "embedded_layer" in targets
+    tok = tokens[torch.as_tensor(ids, device=tokens.device)]
+    with torch.set_grad_enabled(need_grad):
+        logits, pooled, arg = model.run(g.x_in, g.adj_in, tok, g.sc if emb else torch.ones_like(g.sc), rep, input_grad=need_grad and emb,
+                                        sequence_noise=g.noise if emb else None)
+        score = (torch.softmax(logits, dim=1) * torch.as_tensor(masks, device=g.x.device).repeat_interleave(rep, 0)).sum(1)
+    grads = None
+    if need_grad:
+        wrt = ([g.x_in] if "features" in targets else []) + ([g.v0] if g.v0 is not None else []) + ([pooled] if emb else [])
+        grads = list(torch.autograd.grad(score.sum(), wrt))
+    gr = _copies_grads(_copies_data(g, targets), g, targets, grads)
+    gr["tok"], gr["score"] = tok, score.detach()
+    if emb:
+        gr["pooled"] = grads.pop(0) if need_grad else torch.zeros_like(pooled)
+        gr["arg"] = arg if need_grad else torch.full(pooled.shape, 0xFF, dtype=torch.uint8, device=g.x.device)
+    return gr
+
+
+def _reduce_copies(gr, C, plan, targets, table, conv_w, pool):
+    """_reduce_graph_copies plus 'embedded_layer', which ops.seq_conv_pool_input_grad sums over the copies in order."""
+    out = _reduce_graph_copies(gr, C, plan, targets)
     if "embedded_layer" in targets:
         from . import ops
-        out["embedded_layer"] = ops.seq_conv_pool_input_grad(gr["pooled"], gr["arg"], gr["tok"], table, conv_w, pool, rep,
-                                                             row_weight=wt, times_table=not raw)
-    s = gr["score"].view(C, rep)
-    start_row, end_row = (0, rep - 1) if ends is None else ends
-    out["start"], out["end"] = s[:, start_row], s[:, end_row]
+        out["embedded_layer"] = ops.seq_conv_pool_input_grad(gr["pooled"], gr["arg"], gr["tok"], table, conv_w, pool,
+                                                             gr["score"].shape[0] // C, row_weight=gr["weight"],
+                                                             times_table=plan.method not in IG_RAW_METHODS)
     return out
 
 
 def multimodal_integrated_gradients(model, features, adjacency, tokens, labels=None, divide_number=100, modal="all", method="ig",
                                     label_target="max", chunk=None, compounds=None, sequence_symbol=None, batched=True,
                                     noise_scale=0.1, seed=1234):
-    """Integrated gradients of models.MultimodalGCN (kgcn visualize on example_model/model_multimodal.py, cal_feature_IG and
-    CompoundVisualizer of kgcn/visualization.py) -> one dict per visualised compound with the keys the reference dumps:
-    features [N, F], adjs [N, N] (channel 0, dense), embedded_layer [L, E] and their *_IG arrays (the modals named by `modal`),
-    check_score (end - start), sum_of_IG, prediction_score, target_label, true_label, mol / mol_smiles / mol_id (None: no RDKit),
-    amino_acid_seq (when sequence_symbol is given) -- plus compound_id and assay (dump_record drops them; ig_filename uses them).
+    """Integrated gradients of models.MultimodalGCN (kgcn visualize on example_model/model_multimodal.py), by the protocol of the
+    section above -> its records, with embedded_layer [L, E] / embedded_layer_IG as the third modal and amino_acid_seq (when
+    sequence_symbol is given).
 
-    features [G, N, F] and adjacency (the channels of data_util.build_adjs), or a data_util.DeviceGraphDataset as `adjacency`
-    (features None); tokens int32 [G, L] device tensor (data_util.sequence_table); labels [G, K] (needed by label_target 'label',
-    'correct', 'uncorrect').  The target class comes from an unscaled forward pass, the score is its softmax probability.
-    The D + 1 scaled copies of every compound (ig_scales) run as batch rows of ONE forward and ONE backward, `chunk` compounds
-    (default IG_ROWS_PER_CHUNK // copies) at a time; this is valid only because the model mixes no rows, and any other model is
-    refused.  The embedded-sequence attribution comes from the HIP input-gradient kernel (ops.seq_conv_pool_input_grad), which
-    sums the copies in order.  batched=False runs the reference's loop instead: one batch-1 pass per compound and step through the
-    same ops (forward only for a copy of weight 0), the per-step gradients summed by the reduction the batched form uses.
-    method 'smooth_grad' / 'smooth_ig' (:235-259): D noisy samples per compound beside two clean copies (smooth_rows, D + 2 rows),
-    the targeted inputs being x * scale + N(0, noise_scale) (kgcn/feed.py:88, gcn.py:661 default 0.1; the values of every
-    adjacency channel when 'adjs' is a target).  The noise is drawn on the device from (seed, dataset index of the compound,
-    sample number) -- include/kgcn_hip.h -- so chunking, `compounds` subsets and batched=False all see the same values; the
-    embedded sequence is perturbed inside the conv-pool's window staging (ops.seq_conv_pool_perturbed).  smooth_grad returns the
-    mean gradient, smooth_ig the mean gradient times the clean data; check_score comes from the two clean copies."""
+    tokens int32 [G, L] device tensor (data_util.sequence_table); labels [G, K], true_label = argmax.  The score is the softmax
+    probability of the target class.  All five methods.  The embedded-sequence attribution comes from the HIP input-gradient
+    kernel (ops.seq_conv_pool_input_grad), which sums the copies in order; on the noisy path the embedded sequence is perturbed
+    inside the conv-pool's window staging (ops.seq_conv_pool_perturbed).  batched=False runs the reference's loop instead: one
+    batch-1 pass per compound and step through the same ops (forward only for a copy of weight 0), the per-step gradients summed
+    by the reduction the batched form uses; it sees the same noise."""
     import numpy as np
     import string
     from . import models
-    from .data_util import DeviceGraphDataset
     if not isinstance(model, models.MultimodalGCN) or not getattr(model, "ROW_INDEPENDENT", False):
         raise TypeError("multimodal_integrated_gradients batches the scaled copies as rows: it needs a model whose rows never "
                         "mix (models.MultimodalGCN), got %s" % type(model).__name__)
     targets = ig_modal_targets(modal)
-    if method in SMOOTH_METHODS:
-        scales, sigmas, samples, weights, start_row, end_row = smooth_rows(method, divide_number, noise_scale)
-        seed = int(seed)
-    elif method in IG_METHODS:
-        scales, weights = ig_scales(method, divide_number)
-        sigmas, start_row, end_row = None, 0, len(scales) - 1
-    else:
-        raise ValueError("unsupported method %r (%s)" % (method, ", ".join(IG_METHODS + SMOOTH_METHODS)))
-    if isinstance(adjacency, DeviceGraphDataset):
-        dataset = adjacency
-    else:
-        dataset = DeviceGraphDataset(adjacency, features.detach().cpu().numpy() if torch.is_tensor(features) else features,
-                                     device=tokens.device)
-    if dataset.features is None:
-        raise ValueError("the dataset carries no node features")
+    plan = ig_row_plan(method, divide_number, noise_scale, seed)
+    dataset = _compound_dataset(features, adjacency, lambda: tokens.device)
     G = dataset.num_graphs
     if tokens.shape[0] != G:
         raise ValueError("%d token rows for %d graphs" % (tokens.shape[0], G))
     ids = list(range(G)) if compounds is None else [int(i) for i in compounds]
-    lab = None if labels is None else np.asarray(labels.detach().cpu().numpy() if torch.is_tensor(labels) else labels)
-    rep = len(scales)
-    chunk = max(1, IG_ROWS_PER_CHUNK // rep) if chunk is None else int(chunk)
-    if chunk < 1:
-        raise ValueError("chunk must be >= 1")
+    chunk = _compounds_per_chunk(chunk, IG_ROWS_PER_CHUNK // len(plan.scales))
     seqm = model.sequence
     table, conv_w, pool = seqm.embeddings.detach(), seqm.conv_kernel.detach(), seqm.pool
-    # the unscaled pass: the prediction the target class is read from (:479-485)
-    preds = []
-    with torch.no_grad():
-        for i in range(0, len(ids), chunk):
-            part = ids[i:i + chunk]
-            adj, x = dataset.batch(part)
-            preds.append(torch.softmax(model(x, adj, sequences=tokens[torch.as_tensor(part, device=tokens.device)]), 1).cpu().numpy())
-    preds = np.concatenate(preds) if preds else np.zeros((0, 0), np.float32)
-    jobs = []
-    for j, cid in enumerate(ids):
-        true_label = None if lab is None else int(np.argmax(lab[cid]))
-        sel = select_label_target(preds[j], label_target, true_label)
-        if sel is not None:
-            jobs.append((cid, preds[j], true_label) + sel)
-    frozen = [(p, p.requires_grad) for p in model.parameters()]
+
+    def predict(part):
+        adj, x = dataset.batch(part)
+        return torch.softmax(model(x, adj, sequences=tokens[torch.as_tensor(part, device=tokens.device)]), 1).cpu().numpy()
+
+    jobs = list(_ig_jobs(predict, ids, chunk, label_target, _one_job_per_compound(_host_array(labels))))
     res = {}
-    try:
-        for p, _ in frozen:
-            p.requires_grad_(False)
-        noise = None if sigmas is None else (sigmas, samples, seed)
+    with frozen_parameters(model):
         if batched:
             for i in range(0, len(jobs), chunk):
                 part = jobs[i:i + chunk]
-                gr = _copy_grads(model, dataset, tokens, [j[0] for j in part], scales, targets, np.stack([j[5] for j in part]), noise)
-                out = _reduce_copies(gr, len(part), weights, targets, method, table, conv_w, pool, (start_row, end_row))
-                for k, j in enumerate(part):
-                    res[j[0]] = {m: out[m][k] for m in out if m not in ("start", "end")}
-                    res[j[0]]["start"], res[j[0]]["end"] = float(out["start"][k]), float(out["end"][k])
+                gr = _copy_grads(model, dataset, tokens, [j[0] for j in part], plan, targets, np.stack([j[5] for j in part]))
+                _rows_to_host(res, [j[0] for j in part], _reduce_copies(gr, len(part), plan, targets, table, conv_w, pool))
         else:
             for j in jobs:                                   # one batch-1 pass per copy; a copy of weight 0 runs forward only
-                rows = [_copy_grads(model, dataset, tokens, [j[0]], [s], targets, j[5][None],
-                                    None if noise is None else ([sigmas[r]], [samples[r]], seed), need_grad=w != 0.0)
-                        for r, (s, w) in enumerate(zip(scales, weights))]
+                rows = [_copy_grads(model, dataset, tokens, [j[0]], ig_plan_row(plan, r), targets, j[5][None], need_grad=w != 0.0)
+                        for r, w in enumerate(plan.weights)]
                 gr = {k: rows[0][k] if k == "tok" else torch.cat([p[k] for p in rows]) for k in rows[0]}
-                out = _reduce_copies(gr, 1, weights, targets, method, table, conv_w, pool, (start_row, end_row))
-                res[j[0]] = {m: out[m][0] for m in out if m not in ("start", "end")}
-                res[j[0]]["start"], res[j[0]]["end"] = float(out["start"][0]), float(out["end"][0])
-    finally:
-        for p, r in frozen:
-            p.requires_grad_(r)
+                _rows_to_host(res, [j[0]], _reduce_copies(gr, 1, plan, targets, table, conv_w, pool))
     results = []
-    for cid, pred, true_label, tidx, tscore, _ in jobs:
-        r = res[cid]
-        rec = {"compound_id": cid, "assay": assay_string(pred, tidx)}
+    for job in jobs:
+        cid, r = job[0], res[job[0]]
+        rec = {"compound_id": cid, "assay": assay_string(job[1], job[3])}
         if sequence_symbol is not None:
             rec["amino_acid_seq"] = "".join(string.ascii_uppercase[int(t)] for t in np.asarray(sequence_symbol[cid]).reshape(-1))
-        data = {"features": lambda: dataset.features[cid].cpu().numpy(),
-                "adjs": lambda: r["adjs_data"].cpu().numpy(),
+        data = {"features": lambda: dataset.features[cid].cpu().numpy(), "adjs": lambda: r["adjs_data"],
                 "embedded_layer": lambda: table[tokens[cid].long()].cpu().numpy()}
-        total = 0.0
-        for m in targets:
-            rec[m] = data[m]()
-            rec[m + "_IG"] = r[m].detach().cpu().numpy()
-            total += float(rec[m + "_IG"].astype(np.float64).sum())
-        rec["check_score"] = r["end"] - r["start"]
-        rec["sum_of_IG"] = total
-        rec.update({"mol": None, "mol_smiles": None, "mol_id": None, "prediction_score": tscore, "target_label": tidx,
-                    "true_label": true_label})
-        results.append(rec)
+        results.append(_ig_record(rec, job, targets, data, r, r["start"], r["end"]))
     return results
 
 
@@ -483,60 +605,34 @@ def _vecmodal_first_layer(model):
 
 
 def _vecmodal_chunk(model, dataset, vtab, sizes, ids, plan, targets, vname, masks, first, fused, need_grad=True):
-    """One forward + backward over len(ids) compounds x len(plan['scales']) copies -> per compound the weighted sums over the copies
-    ('features' [C, N, F], 'adjs' dense [C, N, N] beside 'adjs_data', the vector [C, 1, Dv]; unmultiplied by the data for 'grad'
-    and 'smooth_grad') and the scores of the start and the end copy.  The graph branch is _copy_grads': the copies are batch rows
-    of the model's own layers.  The vector branch, fused: P = v W once per compound (ops.dense), the first layer of every clean
-    copy from ops.ig_copies_expand (of every noisy copy from the layer itself, without a graph), handed to the model as
-    vector_first; the gradient arriving there goes through ops.ig_copies_reduce and ONE [C, H] x W^T product.  Not fused: the
-    scaled or perturbed vectors go in as vectors= and the per-copy gradients are summed."""
+    """One forward + backward over len(ids) compounds x len(plan.scales) copies -> per compound what _reduce_graph_copies returns
+    and the vector's weighted sum over the copies [C, 1, Dv] (unmultiplied by the data for IG_RAW_METHODS).  The graph branch is
+    _graph_copies': the copies are batch rows of the model's own layers.  The vector branch, fused: P = v W once per compound
+    (ops.dense), the first layer of every clean copy from ops.ig_copies_expand (of every noisy copy from the layer itself,
+    without a graph), handed to the model as vector_first; the gradient arriving there goes through ops.ig_copies_reduce and ONE
+    [C, H] x W^T product.  Not fused: the scaled or perturbed vectors go in as vectors= and the per-copy gradients are summed.
+    need_grad=False: the forward alone, the sums zero."""
     from . import models, ops
-    scales, weights, noise, method = plan["scales"], plan["weights"], plan["noise"], plan["method"]
     ids = [int(i) for i in ids]
-    C, rep = len(ids), len(scales)
-    dev = dataset.features.device
+    C, rep = len(ids), len(plan.scales)
     regression = isinstance(model, models.MultimodalRegressionGCN)
-    adj, x = dataset.batch([i for i in ids for _ in range(rep)])
-    N, F = x.shape[1], x.shape[2]
-    sc = torch.tensor(scales, dtype=torch.float32, device=dev).repeat(C)
+    g = _graph_copies(dataset, ids, plan, targets, need_grad)
+    sc, dev = g.sc, g.x.device
     idt = torch.as_tensor(ids, device=dev)
     v = vtab[idt]
     Dv = v.shape[1]
-    if noise is not None:
-        sg = torch.tensor(noise[0], dtype=torch.float32, device=dev).repeat(C)
-        smp = torch.tensor(noise[1], dtype=torch.int32, device=dev).repeat(C)
-        cid = torch.tensor(ids, dtype=torch.int32, device=dev)
-        seed = noise[2]
-    want = lambda m: need_grad and m in targets
-    # the graph branch: node features and adjacency values as batch rows
-    if "features" not in targets:
-        x_in = x
-    elif noise is None:
-        x_in = (x * sc.view(-1, 1, 1)).requires_grad_(need_grad)
-    else:
-        x_in = ops.ig_perturb(x.view(C, rep, N, F)[:, 0], sc, sg, smp, cid, rep, ops.IG_STREAM_FEATURES, seed).requires_grad_(need_grad)
-    adj_in, v0 = adj, None
-    if "adjs" in targets:                       # kgcn/feed.py:116-121: the values of every channel are scaled
-        if noise is None:
-            vals = [c.values * sc[_entry_graphs(c)] for c in adj.channels]
-        else:
-            rows = cid.repeat_interleave(rep)
-            vals = [ops.ig_perturb_values(c, c.values, sc, sg, smp, rows, ops.IG_STREAM_ADJACENCY + ch, seed)
-                    for ch, c in enumerate(adj.channels)]
-        v0 = vals[0].requires_grad_(need_grad)
-        adj_in = adj.with_values(vals)
-    # the vector branch
     leaf = None
     if vname not in targets:                    # kgcn/feed.py:205: not a target, fed as it is
         kw = {"vectors": v.repeat_interleave(rep, 0)}
     else:
         with torch.no_grad():
-            if noise is not None:
+            if g.noise is not None:
+                sg, smp, cid, seed = g.noise
                 fed = ops.ig_perturb(v.view(C, 1, Dv), sc, sg, smp, cid, rep, ops.IG_STREAM_VECTOR, seed).view(C * rep, Dv)
                 leaf = first["layer"](fed) if fused else fed
             elif fused:
                 P = _cpi_dense(v, first["W"], 1)
-                leaf = ops.ig_copies_expand(P, scales, first["bias"], activation=first["act"], **first["bn"])
+                leaf = ops.ig_copies_expand(P, plan.scales, first["bias"], activation=first["act"], **first["bn"])
             else:
                 leaf = v.repeat_interleave(rep, 0) * sc.view(-1, 1)
         leaf = leaf.detach().requires_grad_(need_grad)
@@ -544,37 +640,26 @@ def _vecmodal_chunk(model, dataset, vtab, sizes, ids, plan, targets, vname, mask
     if regression and sizes is not None:
         kw["enabled_node_nums"] = sizes[idt].repeat_interleave(rep)
     with torch.set_grad_enabled(need_grad):
-        out = model(x_in, adj_in, **kw)
+        out = model(g.x_in, g.adj_in, **kw)
         pred = out if regression else torch.softmax(out, dim=1)
         score = (pred * torch.as_tensor(masks, device=dev).repeat_interleave(rep, 0)).sum(1)
-    grads = []
+    grads = None
     if need_grad:
-        wrt = ([x_in] if "features" in targets else []) + ([v0] if v0 is not None else []) + ([leaf] if leaf is not None else [])
+        wrt = ([g.x_in] if "features" in targets else []) + ([g.v0] if g.v0 is not None else []) + ([leaf] if leaf is not None else [])
         grads = list(torch.autograd.grad(score.sum(), wrt))
-    wt = torch.tensor(weights, dtype=torch.float32, device=dev)
-    wv = wt.repeat(C).view(C, rep, 1, 1)
-    raw = method in ("grad", "smooth_grad")
-    res = {}
     with torch.no_grad():
-        if "features" in targets:
-            ig = (grads.pop(0).view(C, rep, N, F) * wv).sum(1) if need_grad else torch.zeros((C, N, F), device=dev)
-            res["features"] = ig if raw else ig * x.view(C, rep, N, F)[:, 0]
-        if "adjs" in targets:
-            c0 = adj.channels[0]
-            data = values_to_dense(c0, c0.values).view(C, rep, N, N)[:, 0]
-            ig = (values_to_dense(c0, grads.pop(0)).view(C, rep, N, N) * wv).sum(1) if need_grad else torch.zeros_like(data)
-            res["adjs"], res["adjs_data"] = (ig if raw else ig * data), data
+        gr = _copies_grads(_copies_data(g, targets), g, targets, grads)
+        gr["score"] = score.detach()
+        res = _reduce_graph_copies(gr, C, plan, targets)
         if vname in targets:
             if not need_grad:
                 dv = torch.zeros_like(v)
             elif fused:
-                S = ops.ig_copies_reduce(grads.pop(0), leaf, wt, first["scale"], first["act"])
+                S = ops.ig_copies_reduce(grads.pop(0), leaf, g.wt[:rep], first["scale"], first["act"])
                 dv = _cpi_dense(S, first["Wt"], 1)
             else:
-                dv = (grads.pop(0).view(C, rep, Dv) * wv.view(C, rep, 1)).sum(1)
-            res[vname] = (dv if raw else dv * v).view(C, 1, Dv)
-    s = score.detach().view(C, rep)
-    res["start"], res["end"] = s[:, plan["start_row"]], s[:, plan["end_row"]]
+                dv = (grads.pop(0).view(C, rep, Dv) * g.wt.view(C, rep, 1)).sum(1)
+            res[vname] = (dv if plan.method in IG_RAW_METHODS else dv * v).view(C, 1, Dv)
     return res
 
 
@@ -583,26 +668,18 @@ def vecmodal_integrated_gradients(model, features, adjacency, vectors, labels=No
                                   seed=1234, enabled_node_nums=None):
     """`kgcn visualize` of the vector-modality models (kgcn/visualization.py:22-285 and :442-574 with info.vector_modal_name set,
     :106-111 and :128-132) for a models.MultimodalVecGCN (vector `profeat`) or models.MultimodalRegressionGCN (vector `dragon`)
-    -> one dict per visualised compound with the keys the reference dumps: features / features_IG [N, F], adjs / adjs_IG [N, N]
-    (channel 0, dense), <vector name> [Dv] / <vector name>_IG [1, Dv] (the reference accumulates into zeros((1, Dv))) for the
-    modals named by `modal`, check_score (end - start), sum_of_IG, prediction_score, target_label, true_label, mol / mol_smiles /
-    mol_id (None: no RDKit) -- plus compound_id and assay (dump_record drops them; ig_filename uses them).
+    by the protocol of the section above -> its records, with <vector name> [Dv] / <vector name>_IG [1, Dv] (the reference
+    accumulates into zeros((1, Dv))) as the third modal.
 
-    features [G, N, F] and adjacency (the channels of data_util.build_adjs), or a data_util.DeviceGraphDataset as `adjacency`
-    (features None); vectors [G, Dv] (data_util.vector_table, or a host array); labels [G, K] (true_label = argmax; needed by
-    label_target 'label', 'correct', 'uncorrect'); enabled_node_nums [G]: the node counts MultimodalRegressionGCN's
-    GraphBatchNormalization masks with (None: every row counts; the other model ignores them).
-    modal: 'all', 'features', 'adjs' or the vector's name (vecmodal_ig_targets; vector_name defaults to the model's).  The same
-    set is scaled and attributed; a vector that is not a target is fed unscaled (kgcn/feed.py:205).
-    method: 'ig', 'grad_prod', 'grad' (ig_scales) or 'smooth_grad', 'smooth_ig' (smooth_rows), with noise N(0, noise_scale)
-    drawn on the device from (seed, dataset index, sample): the vector is perturbed as a [1, Dv] row set on the stream
-    ops.IG_STREAM_VECTOR, so chunking and `compounds` subsets see the same values.
+    vectors [G, Dv] (data_util.vector_table, or a host array); labels [G, K], true_label = argmax; enabled_node_nums [G]: the
+    node counts MultimodalRegressionGCN's GraphBatchNormalization masks with (None: every row counts; the other model ignores
+    them).  modal: 'all', 'features', 'adjs' or the vector's name (vecmodal_ig_targets; vector_name defaults to the model's); a
+    vector that is not a target is fed unscaled (kgcn/feed.py:205).  All five methods: the vector is perturbed as a [1, Dv] row
+    set on the stream ops.IG_STREAM_VECTOR.
     Score: the softmax probability of the target class (MultimodalVecGCN); the prediction column itself
-    (MultimodalRegressionGCN: predictions = logits, one task of label_dim entries, cal_feature_IG :488-499).  The target comes
-    from an unscaled forward pass through select_label_target.
+    (MultimodalRegressionGCN: predictions = logits, one task of label_dim entries, cal_feature_IG :488-499).
 
-    The copies of every compound run as batch rows of one forward and one backward, `chunk` compounds (default
-    IG_ROWS_PER_CHUNK // copies) at a time; chunking does not change a bit.  fused=True: the vector branch's first layer --
+    fused=True: the vector branch's first layer --
     Dense(Dv -> 300), respectively Dense(Dv -> 8), by far the largest of the tower -- is not run per copy: a clean copy's
     pre-activation is alpha_k (v W) + b, so v W is formed once per compound and ops.ig_copies_expand sweeps the copies; the
     gradient with respect to the fed vector is dpre_k W^T, linear in dpre_k for the smooth methods too, so
@@ -612,31 +689,14 @@ def vecmodal_integrated_gradients(model, features, adjacency, vectors, labels=No
     there."""
     import numpy as np
     from . import models
-    from .data_util import DeviceGraphDataset
     targets, vname = vecmodal_ig_targets(model, modal, vector_name)
     regression = isinstance(model, models.MultimodalRegressionGCN)
-    if method in SMOOTH_METHODS:
-        scales, sigmas, samples, weights, start_row, end_row = smooth_rows(method, divide_number, noise_scale)
-        noise = (sigmas, samples, int(seed))
-    elif method in IG_METHODS:
-        scales, weights = ig_scales(method, divide_number)
-        noise, start_row, end_row = None, 0, len(scales) - 1
-    else:
-        raise ValueError("unsupported method %r (%s)" % (method, ", ".join(IG_METHODS + SMOOTH_METHODS)))
-    rep = len(scales)
-    chunk = max(1, IG_ROWS_PER_CHUNK // rep) if chunk is None else int(chunk)
-    if chunk < 1:
-        raise ValueError("chunk must be >= 1")
+    plan = ig_row_plan(method, divide_number, noise_scale, seed)
+    chunk = _compounds_per_chunk(chunk, IG_ROWS_PER_CHUNK // len(plan.scales))
     if vectors is None:
         raise ValueError("the vector modality %r is missing (vectors [G, Dv])" % (vname,))
     fused = VECMODAL_IG_FUSED[type(model).__name__] if fused is None else bool(fused)
-    if isinstance(adjacency, DeviceGraphDataset):
-        dataset = adjacency
-    else:
-        dev = next(model.parameters(), torch.zeros(0, device="cuda")).device
-        dataset = DeviceGraphDataset(adjacency, features.detach().cpu().numpy() if torch.is_tensor(features) else features, device=dev)
-    if dataset.features is None:
-        raise ValueError("the dataset carries no node features")
+    dataset = _compound_dataset(features, adjacency, lambda: _parameter_device(model))
     dev = dataset.features.device
     G = dataset.num_graphs
     vtab = (vectors.detach() if torch.is_tensor(vectors) else torch.as_tensor(np.asarray(vectors, np.float32))).to(dev, torch.float32)
@@ -645,68 +705,34 @@ def vecmodal_integrated_gradients(model, features, adjacency, vectors, labels=No
     vtab = vtab.contiguous()
     sizes = None
     if enabled_node_nums is not None:
-        sizes = torch.as_tensor(np.asarray(enabled_node_nums.detach().cpu().numpy() if torch.is_tensor(enabled_node_nums)
-                                           else enabled_node_nums).astype(np.int32).reshape(-1), device=dev)
+        sizes = torch.as_tensor(_host_array(enabled_node_nums).astype(np.int32).reshape(-1), device=dev)
         if sizes.numel() != G:
             raise ValueError("%d enabled_node_nums for %d graphs" % (sizes.numel(), G))
     ids = list(range(G)) if compounds is None else [int(i) for i in compounds]
-    lab = None if labels is None else np.asarray(labels.detach().cpu().numpy() if torch.is_tensor(labels) else labels)
 
-    def forward_kw(part):
+    def predict(part):
+        adj, x = dataset.batch(part)
         idt = torch.as_tensor(part, device=dev)
         kw = {"vectors": vtab[idt]}
         if regression and sizes is not None:
             kw["enabled_node_nums"] = sizes[idt]
-        return kw
+        out = model(x, adj, **kw)
+        return (out if regression else torch.softmax(out, 1)).cpu().numpy()
 
-    # the unscaled pass: the prediction the target is read from (:479-485); it also builds a freshly made model
-    preds = []
-    with torch.no_grad():
-        for i in range(0, len(ids), chunk):
-            part = ids[i:i + chunk]
-            adj, x = dataset.batch(part)
-            out = model(x, adj, **forward_kw(part))
-            preds.append((out if regression else torch.softmax(out, 1)).cpu().numpy())
-    preds = np.concatenate(preds) if preds else np.zeros((0, 0), np.float32)
-    jobs = []
-    for j, cid in enumerate(ids):
-        true_label = None if lab is None else int(np.argmax(lab[cid]))
-        sel = select_label_target(preds[j], label_target, true_label)
-        if sel is not None:
-            jobs.append((cid, preds[j], true_label) + sel)
-    plan = {"scales": scales, "weights": weights, "noise": noise, "method": method, "start_row": start_row, "end_row": end_row}
-    frozen = [(p, p.requires_grad) for p in model.parameters()]
+    jobs = list(_ig_jobs(predict, ids, chunk, label_target, _one_job_per_compound(_host_array(labels))))
     res = {}
-    try:
-        for p, _ in frozen:
-            p.requires_grad_(False)
+    with frozen_parameters(model):
         first = _vecmodal_first_layer(model) if jobs else None
         for i in range(0, len(jobs), chunk):
             part = jobs[i:i + chunk]
-            out = _vecmodal_chunk(model, dataset, vtab, sizes, [j[0] for j in part], plan, targets, vname,
-                                  np.stack([j[5] for j in part]), first, fused)
-            host = {m: t.detach().cpu().numpy() for m, t in out.items()}
-            for k, j in enumerate(part):
-                res[j[0]] = {m: a[k] for m, a in host.items()}
-    finally:
-        for p, r in frozen:
-            p.requires_grad_(r)
+            _rows_to_host(res, [j[0] for j in part], _vecmodal_chunk(model, dataset, vtab, sizes, [j[0] for j in part], plan, targets,
+                                                                     vname, np.stack([j[5] for j in part]), first, fused))
     results = []
-    for cid, pred, true_label, tidx, tscore, _ in jobs:
-        r = res[cid]
-        rec = {"compound_id": cid, "assay": assay_string(pred, tidx)}
+    for job in jobs:
+        cid, r = job[0], res[job[0]]
         data = {"features": lambda: dataset.features[cid].cpu().numpy(), "adjs": lambda: r["adjs_data"],
                 vname: lambda: vtab[cid].cpu().numpy()}
-        total = 0.0
-        for m in targets:
-            rec[m] = data[m]()
-            rec[m + "_IG"] = r[m]
-            total += float(rec[m + "_IG"].astype(np.float64).sum())
-        rec["check_score"] = float(r["end"]) - float(r["start"])
-        rec["sum_of_IG"] = total
-        rec.update({"mol": None, "mol_smiles": None, "mol_id": None, "prediction_score": tscore, "target_label": tidx,
-                    "true_label": true_label})
-        results.append(rec)
+        results.append(_ig_record({"compound_id": cid, "assay": assay_string(job[1], job[3])}, job, targets, data, r, r["start"], r["end"]))
     return results
 
 
@@ -1063,43 +1089,24 @@ def _cpi_fused_chunk(dataset, part, par, coef, method):
     return out
 
 
-def _cpi_composed_chunk(model, dataset, part, tasks, coef, method):
-    """The composed route: the copies of every compound as batch rows of one forward through the model, one autograd backward
-    per task, the copies summed in order -> what _cpi_fused_chunk returns."""
-    targets, scales, weights = coef["targets"], coef["scales"], coef["weights"]
-    C, rep = len(part), len(scales)
-    adj, x = dataset.batch([i for i in part for _ in range(rep)])
-    N, F = x.shape[1], x.shape[2]
-    dev = x.device
-    sc = torch.tensor(scales, dtype=torch.float32, device=dev).repeat(C)
-    wv = torch.tensor(weights, dtype=torch.float32, device=dev).repeat(C).view(C, rep, 1, 1)
-    x_in = (x * sc.view(-1, 1, 1) if "features" in targets else x.clone()).requires_grad_("features" in targets)
-    adj_in, v0 = adj, None
-    if "adjs" in targets:                                    # kgcn/feed.py:116-121: the values of every channel are scaled
-        vals = [c.values * sc[_entry_graphs(c)] for c in adj.channels]
-        v0 = vals[0].requires_grad_(True)
-        adj_in = adj.with_values(vals)
-    p1 = torch.softmax(model(x_in, adj_in), dim=1)[:, 1, :]                       # prediction[:, t, 0] of every task
-    wrt = ([x_in] if "features" in targets else []) + ([v0] if v0 is not None else [])
-    raw = method == "grad"
-    s = p1.detach().view(C, rep, -1)[:, :, tasks]
-    out = {"start": s[:, 0, :], "end": s[:, -1, :], "features_data": x.view(C, rep, N, F)[:, 0]}
-    feats, adjs = [], []
-    c0 = adj.channels[0]
+def _cpi_composed_chunk(model, dataset, part, tasks, plan, targets):
+    """The composed route: the copies of every compound as batch rows of one forward through the model (_graph_copies), one
+    autograd backward per task, the copies summed in order (_reduce_graph_copies) and the tasks stacked -> what _cpi_fused_chunk
+    returns."""
+    C, rep = len(part), len(plan.scales)
+    g = _graph_copies(dataset, part, plan, targets)
+    p1 = torch.softmax(model(g.x_in, g.adj_in), dim=1)[:, 1, :]                   # prediction[:, t, 0] of every task
+    wrt = ([g.x_in] if "features" in targets else []) + ([g.v0] if g.v0 is not None else [])
+    data = _copies_data(g, targets)
+    per_task = []
     for j, t in enumerate(tasks):
-        grads = list(torch.autograd.grad(p1[:, t].sum(), wrt, retain_graph=j + 1 < len(tasks)))
-        if "features" in targets:
-            feats.append((grads.pop(0).view(C, rep, N, F) * wv).sum(1))
-        if "adjs" in targets:
-            adjs.append((values_to_dense(c0, grads.pop(0)).view(C, rep, N, N) * wv).sum(1))
-    if "features" in targets:
-        ig = torch.stack(feats, 1)
-        out["features"] = ig if raw else ig * x.view(C, rep, N, F)[:, :1]
+        gr = _copies_grads(data, g, targets, list(torch.autograd.grad(p1[:, t].sum(), wrt, retain_graph=j + 1 < len(tasks))))
+        gr["score"] = p1[:, t].detach()
+        per_task.append(_reduce_graph_copies(gr, C, plan, targets))
+    out = {m: torch.stack([r[m] for r in per_task], 1) for m in targets + ("start", "end")}
+    out["features_data"] = g.x.view(C, rep, g.x.shape[1], g.x.shape[2])[:, 0]
     if "adjs" in targets:
-        data = values_to_dense(c0, c0.values).view(C, rep, N, N)[:, 0]
-        ig = torch.stack(adjs, 1)
-        out["adjs"] = ig if raw else ig * data.unsqueeze(1)
-        out["adjs_data"] = data
+        out["adjs_data"] = per_task[0]["adjs_data"]
     return out
 
 
@@ -1107,18 +1114,13 @@ def cpi_integrated_gradients(model, features, adjacency, labels=None, divide_num
                              label_target="max", tasks=None, compounds=None, chunk=None, fused=True):
     """`kgcn visualize` of the compound-protein interaction sample (run_viz.sh, block name=mt) for a models.CPIMultitaskNet: integrated
     gradients of every task's prediction[:, t, 0] -- the two-way softmax's second entry, sigmoid(h . u_t + e_t) -- with respect to
-    the node features and / or the values of adjacency channel 0 -> one dict per (compound, task) with the reference's dump keys:
-    features / features_IG [N, F], adjs / adjs_IG [N, N] (channel 0, dense) for the modals named by `modal` ('all', 'features',
-    'adjs'), check_score (end - start), sum_of_IG, prediction_score, target_label, true_label, mol / mol_smiles / mol_id (None: no
-    RDKit) -- plus compound_id, task, assay, start_score and end_score (the prediction of the first and the last copy;
-    cpi_dump_record drops the five; ig_filename(..., task=t) uses the first three).
+    the node features and / or the values of adjacency channel 0 (modal 'all', 'features', 'adjs'), by the protocol of the section
+    above -> its records, one per (compound, task), which also hold task, start_score and end_score (the prediction of the first
+    and the last copy; cpi_dump_record drops these beside compound_id and assay; ig_filename(..., task=t) uses task).
 
-    features [G, N, F] and adjacency (the channels of data_util.build_adjs), or a data_util.DeviceGraphDataset as `adjacency`
-    (features None); labels [G, T] (needed by label_target 'label', 'correct', 'uncorrect'): the true label of task t is
-    labels[cid, t] for T > 1, argmax(labels[cid]) for one task.  The target comes from an unscaled forward pass through
-    select_label_target on the one-entry prediction [p1] (:497-529), so label_target 'label' with label 1 indexes outside it and
-    raises, as it would in the reference.  tasks: the tasks to visualise (default all); compounds: dataset indices (default all).
-    method 'ig', 'grad_prod' or 'grad' (ig_scales).
+    labels [G, T]: the true label of task t is labels[cid, t] for T > 1, argmax(labels[cid]) for one task.  The target is chosen on
+    the one-entry prediction [p1] (:497-529), so label_target 'label' with label 1 indexes outside it and raises, as it would in
+    the reference.  tasks: the tasks to visualise (default all).  method 'ig', 'grad_prod' or 'grad'.
 
     fused=True: the network is one GraphConv, a sigmoid, a sum and one Dense, so copy k's pre-activation is
     alpha_k P + gamma_k Q (cpi_ig_coefficients): P, Q and Y0 = X W_0 are formed once per compound by the dense and SpMM ops,
@@ -1132,54 +1134,34 @@ def cpi_integrated_gradients(model, features, adjacency, labels=None, divide_num
     the first visualised compound and task and reuses it (tf_grads, :466 and :555)."""
     import numpy as np
     from . import models
-    from .data_util import DeviceGraphDataset
     if not isinstance(model, models.CPIMultitaskNet):
         raise TypeError("cpi_integrated_gradients needs a models.CPIMultitaskNet (the closed form is that network's), got %s"
                         % type(model).__name__)
     coef = cpi_ig_coefficients(modal, method, divide_number)
-    targets = coef["targets"]
-    if isinstance(adjacency, DeviceGraphDataset):
-        dataset = adjacency
-    else:
-        dev = next(model.parameters(), torch.zeros(0, device="cuda")).device
-        dataset = DeviceGraphDataset(adjacency, features.detach().cpu().numpy() if torch.is_tensor(features) else features, device=dev)
-    if dataset.features is None:
-        raise ValueError("the dataset carries no node features")
+    targets, plan = coef["targets"], ig_row_plan(method, divide_number)
+    dataset = _compound_dataset(features, adjacency, lambda: _parameter_device(model))
     G, T = dataset.num_graphs, model.label_dim
     ids = list(range(G)) if compounds is None else [int(i) for i in compounds]
     tasks = list(range(T)) if tasks is None else [int(t) for t in np.atleast_1d(tasks)]
     if not tasks or min(tasks) < 0 or max(tasks) >= T:
         raise ValueError("tasks must name some of the network's %d tasks" % T)
-    lab = None if labels is None else np.asarray(labels.detach().cpu().numpy() if torch.is_tensor(labels) else labels)
-    N, rep = dataset.features.shape[1], len(coef["scales"])
-    Wd = model.conv.output_dim
-    if chunk is None:
-        chunk = max(1, CPI_IG_FULL_BYTES // (4 * len(tasks) * N * Wd * (1 if coef["wB"] is None else 2))) if fused \
-            else max(1, IG_ROWS_PER_CHUNK // rep)
-    chunk = int(chunk)
-    if chunk < 1:
-        raise ValueError("chunk must be >= 1")
-    # the unscaled pass: the prediction the target is read from (:479-485); it also builds a freshly made model
-    preds = []
-    with torch.no_grad():
-        step = max(1, IG_ROWS_PER_CHUNK // 8)
-        for i in range(0, len(ids), step):
-            adj, x = dataset.batch(ids[i:i + step])
-            preds.append(torch.softmax(model(x, adj), dim=1)[:, 1, :].cpu().numpy())
-    preds = np.concatenate(preds) if preds else np.zeros((0, T), np.float32)
-    jobs = []
-    for j, cid in enumerate(ids):
-        for t in tasks:
-            true_label = None if lab is None else int(lab[cid, t]) if T > 1 else int(np.argmax(lab[cid]))
-            sel = select_label_target(preds[j, t:t + 1], label_target, true_label)
-            if sel is not None:
-                jobs.append((cid, t, preds[j, t:t + 1], true_label, sel[0], sel[1]))
-    wanted = sorted({j[0] for j in jobs}, key=ids.index)
-    frozen = [(p, p.requires_grad) for p in model.parameters()]
+    lab = _host_array(labels)
+    N, Wd = dataset.features.shape[1], model.conv.output_dim
+    chunk = _compounds_per_chunk(chunk, CPI_IG_FULL_BYTES // (4 * len(tasks) * N * Wd * (1 if coef["wB"] is None else 2)) if fused
+                                 else IG_ROWS_PER_CHUNK // len(plan.scales))
+
+    def predict(part):
+        adj, x = dataset.batch(part)
+        return torch.softmax(model(x, adj), dim=1)[:, 1, :].cpu().numpy()
+
+    def entries(cid, row):                                   # one attribution per task, of the one-entry prediction [p1]
+        return [((cid, t), row[t:t + 1], None if lab is None else int(lab[cid, t]) if T > 1 else int(np.argmax(lab[cid])))
+                for t in tasks]
+
+    jobs = list(_ig_jobs(predict, ids, max(1, IG_ROWS_PER_CHUNK // 8), label_target, entries))
+    wanted = sorted({j[0][0] for j in jobs}, key=ids.index)
     res = {}
-    try:
-        for p, _ in frozen:
-            p.requires_grad_(False)
+    with frozen_parameters(model):
         if fused and wanted:
             V, c = model.out.kernel.detach(), model.out.bias.detach()
             ts = torch.as_tensor(tasks, device=V.device)
@@ -1190,26 +1172,19 @@ def cpi_integrated_gradients(model, features, adjacency, labels=None, divide_num
             part = wanted[i:i + chunk]
             with torch.set_grad_enabled(not fused):
                 out = _cpi_fused_chunk(dataset, part, par, coef, method) if fused else \
-                    _cpi_composed_chunk(model, dataset, part, tasks, coef, method)
-            host = {m: v.detach().cpu().numpy() for m, v in out.items()}
+                    _cpi_composed_chunk(model, dataset, part, tasks, plan, targets)
+            host = _rows_to_host(res, part, out)
             # sum_of_IG of every (compound, task) at once: the fp64 sum of the record's own arrays, one modal after the other
-            host["total"] = sum(host[m].astype(np.float64).reshape(len(part), len(tasks), -1).sum(-1) for m in targets)
+            total = sum(host[m].astype(np.float64).reshape(len(part), len(tasks), -1).sum(-1) for m in targets)
             for k, cid in enumerate(part):
-                res[cid] = {m: v[k] for m, v in host.items()}
-    finally:
-        for p, r in frozen:
-            p.requires_grad_(r)
+                res[cid]["total"] = total[k]
     results = []
-    for cid, t, pred, true_label, tidx, tscore in jobs:
+    for job in jobs:
+        (cid, t), pred, tidx = job[0], job[1], job[3]
         r, k = res[cid], tasks.index(t)
-        rec = {"compound_id": cid, "task": t, "assay": assay_string(pred, tidx)}
-        for m in targets:
-            rec[m] = r["features_data"] if m == "features" else r["adjs_data"]
-            rec[m + "_IG"] = r[m][k]
-        rec["start_score"], rec["end_score"] = float(r["start"][k]), float(r["end"][k])
-        rec["check_score"] = rec["end_score"] - rec["start_score"]
-        rec["sum_of_IG"] = float(r["total"][k])
-        rec.update({"mol": None, "mol_smiles": None, "mol_id": None, "prediction_score": tscore, "target_label": tidx,
-                    "true_label": true_label})
-        results.append(rec)
+        rec = {"compound_id": cid, "task": t, "assay": assay_string(pred, tidx),
+               "start_score": float(r["start"][k]), "end_score": float(r["end"][k])}
+        data = {"features": lambda: r["features_data"], "adjs": lambda: r["adjs_data"]}
+        results.append(_ig_record(rec, job, targets, data, {m: r[m][k] for m in targets}, rec["start_score"], rec["end_score"],
+                                  sum_of_ig=r["total"][k]))
     return results

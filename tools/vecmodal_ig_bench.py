@@ -79,15 +79,15 @@ def stats(ms):
 def loop_route(model, vtab, sz, cids, modal):
     """The reference's loop: one batch-1 pass per step and compound, the weighted gradients summed on the host side of the loop."""
     targets, name = V.vecmodal_ig_targets(model, modal)
-    scales, weights = V.ig_scales("ig", STEPS)
+    plan = V.ig_row_plan("ig", STEPS)
     first = V._vecmodal_first_layer(model)
     mask = np.array([[1.0, 0.0]], np.float32)
     out = []
     for cid in cids:
         total = None
-        for s, w in zip(scales, weights):
-            plan = {"scales": [s], "weights": [w], "noise": None, "method": "ig", "start_row": 0, "end_row": 0}
-            r = V._vecmodal_chunk(model, dataset, vtab, sz, [cid], plan, targets, name, mask, first, False, need_grad=w != 0.0)
+        for k, w in enumerate(plan.weights):
+            r = V._vecmodal_chunk(model, dataset, vtab, sz, [cid], V.ig_plan_row(plan, k), targets, name, mask, first, False,
+                                  need_grad=w != 0.0)
             total = r[name] if total is None else total + r[name]
         out.append(total)
     return out
