@@ -10,6 +10,7 @@
 //                                training:  dx = gamma rstd (g - dbeta / n - xhat dgamma / n)
 //                                inference: dx = gamma rstd g                       (valid rows; 0 on padding rows)
 // All of them are HBM-bound streaming passes; reductions are deterministic (per-workgroup partials, fixed-order second stage).
+#include "block_reduce.h"
 #include "kgcn_common.h"
 
 namespace kgcn {
@@ -89,13 +90,7 @@ __global__ void bn_scale_kernel(float* __restrict__ v, int d, const int* __restr
   } else if (threadIdx.x == 0) {
     n = graphs * n_nodes;
   }
-  red[threadIdx.x] = n;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-    __syncthreads();
-  }
-  n = red[0];
+  n = block_sum(n, red);
   if (threadIdx.x == 0 && count_out) *count_out = n;
   const float inv = n > 0 ? 1.0f / (float)n : 0.f;
   for (int c = threadIdx.x; c < d; c += 256) v[c] *= inv;

@@ -20,6 +20,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
+#include "block_reduce.h"
 #include "kgcn_common.h"
 
 namespace kgcn {
@@ -159,7 +160,7 @@ __global__ __launch_bounds__(kPackBlock) void compact_groups_kernel(const int4* 
   }
   const unsigned long long any = __ballot(non_unit != 0);
   if (any) {
-    for (int off = 32; off > 0; off >>= 1) non_unit += __shfl_xor(non_unit, off, 64);
+    non_unit = wave_sum(non_unit);
     if ((threadIdx.x & 63) == 0) atomicAdd(stats, non_unit);
   }
 }

@@ -21,6 +21,7 @@
 //   p(1 - p) is formed the same way by the score kernel and handed on in the workspace, not recomputed as p - p p.
 //   Every sum runs in one fixed order, there are no atomics, and no block works on more than one compound: the outputs are
 //   bitwise reproducible and do not depend on which compounds share a launch.
+#include "block_reduce.h"
 #include "kgcn_common.h"
 
 namespace kgcn {
@@ -44,12 +45,6 @@ __device__ __forceinline__ Sig stable_sigmoid(float z) {
 }
 
 __device__ __forceinline__ float pre_activation(float alpha, float p, float gamma, float q) { return fmaf(alpha, p, gamma * q); }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
 
 // S[c, k, j] = sum_n sigmoid(alpha_k P[c, n, j] + gamma_k Q[c, n, j]): block = (compound, kStepBlock copies, 256 columns)
 __global__ __launch_bounds__(256) void cpi_ig_colsum_kernel(const float* __restrict__ P, const float* __restrict__ Q,

@@ -7,38 +7,18 @@
 //   argmax   = d > 0 ? 1 : 0                                 (a tie goes to class 0, as tf.argmax)
 //   dlogits  = mask ? (p1 - label) : 0 for class 1, its negation for class 0
 //
-// One workgroup per task sums its column over the rows in a fixed order (thread-strided partials, one tree): no float atomics.
-// A one-workgroup kernel behind it adds the task costs (cost = sum_t each_cost[t]: a sum, not a mean) and, when the call carries
+// One workgroup per task sums its column over the rows in a fixed order (thread-strided partials, one block_sum): no float atomics.
+// The finish kernel of block_reduce.h behind it, shared with the squared-error head of regress.hip, adds the task costs (cost = sum_t each_cost[t]: a sum, not a mean) and, when the call carries
 // an accumulator block, adds the batch's [each_cost | each_correct | each_count | cost] into it in place -- a captured step
 // accumulates a whole epoch on the device and the host reads one block back (the reference sums on the host per batch,
 // kgcn/core.py:269-271).  Counts are floats holding integers: exact up to 2^24 rows per accumulator.
+#include "block_reduce.h"
 #include "kgcn_common.h"
 
 namespace kgcn {
 namespace {
 
 constexpr int kBlock = 256;
-
-// sums of a, b, c over the workgroup, the same tree for every call
-__device__ __forceinline__ void block_sum3(float& a, float& b, float& c, float (*red)[kBlock]) {
-  const int t = threadIdx.x;
-  red[0][t] = a;
-  red[1][t] = b;
-  red[2][t] = c;
-  __syncthreads();
-#pragma unroll
-  for (int off = kBlock / 2; off > 0; off >>= 1) {
-    if (t < off) {
-      red[0][t] += red[0][t + off];
-      red[1][t] += red[1][t + off];
-      red[2][t] += red[2][t + off];
-    }
-    __syncthreads();
-  }
-  a = red[0][0];
-  b = red[1][0];
-  c = red[2][0];
-}
 
 // stats [3 T + 1] = each_cost [T] | each_correct [T] | each_count [T] | cost; this kernel writes the first 3 T
 __global__ __launch_bounds__(kBlock) void softmax2_ce_kernel(const float* __restrict__ logits, const float* __restrict__ labels,
@@ -47,7 +27,7 @@ __global__ __launch_bounds__(kBlock) void softmax2_ce_kernel(const float* __rest
                                                             float* __restrict__ stats) {
   __shared__ float red[3][kBlock];
   const int t = blockIdx.x;
-  float cost = 0.f, correct = 0.f, count = 0.f;
+  float v[3] = {0.f, 0.f, 0.f};                // cost, correct, count
   for (long b = threadIdx.x; b < B; b += kBlock) {
     const long i0 = b * 2 * T + t, i1 = i0 + T;
     const float d = logits[i1] - logits[i0];
@@ -60,34 +40,23 @@ __global__ __launch_bounds__(kBlock) void softmax2_ce_kernel(const float* __rest
     float g = 0.f;
     if (used) {
       const float u = pos ? -d : d;
-      cost += fmaxf(u, 0.f) + log1pf(e);
-      correct += ((d > 0.f) == pos) ? 1.f : 0.f;
-      count += 1.f;
+      v[0] += fmaxf(u, 0.f) + log1pf(e);
+      v[1] += ((d > 0.f) == pos) ? 1.f : 0.f;
+      v[2] += 1.f;
       g = p1 - (pos ? 1.f : 0.f);
     }
     dlogits[i1] = g;
     dlogits[i0] = -g;
   }
-  block_sum3(cost, correct, count, red);
+  block_sum(v, red);
   if (threadIdx.x == 0) {
-    stats[t] = cost;
-    stats[T + t] = correct;
-    stats[2 * T + t] = count;
+    stats[t] = v[0];
+    stats[T + t] = v[1];
+    stats[2 * T + t] = v[2];
   }
 }
 
-// cost = sum_t each_cost[t], t ascending in thread-strided partials and one tree; accum += stats
-__global__ __launch_bounds__(kBlock) void softmax2_finish_kernel(float* __restrict__ stats, int T, float* __restrict__ accum) {
-  __shared__ float red[3][kBlock];
-  float c = 0.f, z0 = 0.f, z1 = 0.f;
-  for (int t = threadIdx.x; t < T; t += kBlock) c += stats[t];
-  block_sum3(c, z0, z1, red);
-  if (threadIdx.x == 0) stats[3 * T] = c;
-  if (accum) {
-    for (int i = threadIdx.x; i < 3 * T; i += kBlock) accum[i] += stats[i];
-    if (threadIdx.x == 0) accum[3 * T] += c;
-  }
-}
+// the kernel behind it: task_loss_finish_kernel<3, false> (block_reduce.h)
 
 }  // namespace
 }  // namespace kgcn
@@ -104,6 +73,6 @@ extern "C" int kgcn_multitask_softmax2_ce_f32(const float* logits, const float* 
   hipStream_t s = as_stream(stream);
   hipLaunchKernelGGL(softmax2_ce_kernel, dim3((unsigned)tasks), dim3(kBlock), 0, s, logits, labels, mask_label, (long)batch, tasks,
                      dlogits, prediction, stats);
-  hipLaunchKernelGGL(softmax2_finish_kernel, dim3(1), dim3(kBlock), 0, s, stats, tasks, accum);
+  hipLaunchKernelGGL((task_loss_finish_kernel<3, false>), dim3(1), dim3(kBlock), 0, s, stats, (long)batch, (int)tasks, accum);
   return check_launch(who);
 }

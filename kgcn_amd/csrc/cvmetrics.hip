@@ -18,6 +18,7 @@
 //            once per task and uses no atomics.
 #include <rocprim/device/device_radix_sort.hpp>
 
+#include "block_reduce.h"
 #include "kgcn_common.h"
 
 namespace kgcn {
@@ -67,19 +68,6 @@ __device__ __forceinline__ long task_begin(const u64* __restrict__ keys, long m,
   return lo;
 }
 
-__device__ __forceinline__ u64 block_sum_u64(u64 v, u64* red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-#pragma unroll
-  for (int off = kBlock / 2; off > 0; off >>= 1) {
-    if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-    __syncthreads();
-  }
-  const u64 s = red[0];
-  __syncthreads();
-  return s;
-}
-
 // out [T, 8] int64: n_used, P, TP, FP (score > threshold), n_nonfinite, auc_num2, n_groups, 0;  ap [T] fp64
 __global__ __launch_bounds__(kBlock) void metrics_scan_kernel(const u64* __restrict__ keys, long m, float threshold,
                                                               long long* __restrict__ out, double* __restrict__ ap_out) {
@@ -110,10 +98,10 @@ __global__ __launch_bounds__(kBlock) void metrics_scan_kernel(const u64* __restr
       cfp += pos ? 0 : 1;
     }
   }
-  const u64 P = block_sum_u64(cp, red);
-  const u64 TP = block_sum_u64(ctp, red);
-  const u64 FP = block_sum_u64(cfp, red);
-  const u64 NF = block_sum_u64(cnf, red);
+  const u64 P = block_sum(cp, red);
+  const u64 TP = block_sum(ctp, red);
+  const u64 FP = block_sum(cfp, red);
+  const u64 NF = block_sum(cnf, red);
   const double Pd = (double)P;
 
   // carries, the same in every thread
@@ -212,8 +200,8 @@ __global__ __launch_bounds__(kBlock) void metrics_scan_kernel(const u64* __restr
     for (int w = 1; w < kWaves; ++w) chunk += wap[w];
     ap += chunk;
   }
-  const u64 auc_all = block_sum_u64(auc, red);
-  const u64 groups_all = block_sum_u64(groups, red);
+  const u64 auc_all = block_sum(auc, red);
+  const u64 groups_all = block_sum(groups, red);
   if (tid == 0) {
     long long* o = out + (long)task * 8;
     o[0] = (long long)(e - s);

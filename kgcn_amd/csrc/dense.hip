@@ -22,6 +22,7 @@
 #include <atomic>
 #include <mutex>
 
+#include "block_reduce.h"
 #include "dense_kernels.h"
 
 namespace kgcn {
@@ -674,7 +675,7 @@ __global__ __launch_bounds__(256) void dx_dot_final_kernel(const float* __restri
   __shared__ float red[4];
   float s = 0.f;
   for (int i = threadIdx.x; i < nparts; i += 256) s += part[i];
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) out[0] = (red[0] + red[1]) + (red[2] + red[3]);

@@ -21,6 +21,7 @@
 //   four at a time: wave w forms the U row of pair q + w, then the four rows are scattered one after the other, the entries
 //   of row i of A spread over the 256 threads -- columns within a CSR row are distinct (the caller checks it), so no two
 //   threads meet on a node_ig slot.  No float atomics anywhere: results are bitwise reproducible.
+#include "block_reduce.h"
 #include "kgcn_common.h"
 
 namespace kgcn {
@@ -60,12 +61,6 @@ __device__ __forceinline__ float gcn_dcost(float x1, float x2) {
   const float x = x1 - x2;
   const float y = 1.0f / (1.0f + expf(-x)), q = 1.0f / (1.0f + expf(x));
   return -(y * q) / (y + kLogEps);
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
 }
 
 __global__ __launch_bounds__(256) void kg_ig_kernel(Args a) {

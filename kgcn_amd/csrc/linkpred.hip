@@ -21,6 +21,7 @@
 //            fixed-order second stage (deferrable: kgcn_reduce_defer).
 #include <rocprim/device/device_radix_sort.hpp>
 
+#include "block_reduce.h"
 #include "kgcn_common.h"
 #include "philox.h"
 
@@ -100,11 +101,8 @@ __global__ __launch_bounds__(256) void lp_score_kernel(FwdArgs a) {
       p2 += h3[d] * h5[d];
     }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    p1 += __shfl_xor(p1, off);
-    p2 += __shfl_xor(p2, off);
-  }
+  p1 = wave_sum(p1);
+  p2 = wave_sum(p2);
   if (lane == 0) {
     a.s1[i] = p1;
     a.s2[i] = p2;
@@ -134,41 +132,32 @@ __device__ __forceinline__ float pair_dcost(float x1, float x2, int mode) {
 // sums: cost_opt, cost_sum, correct_count, S1, S2 (the last two: ip only)
 __global__ __launch_bounds__(256) void lp_cost_kernel(const float* __restrict__ s1, const float* __restrict__ s2, int L, int mode,
                                                       float* __restrict__ sums) {
-  __shared__ float r0[256], r1[256];
+  __shared__ float red[2][256];
   const int t = threadIdx.x;
-  float u = 0.f, v = 0.f;
+  float a[2] = {0.f, 0.f};
   for (int i = t; i < L; i += 256) {
     const float x1 = s1[i], x2 = s2[i];
     if (mode == KGCN_LP_IP) {
-      u += x1;
-      v += x2;
+      a[0] += x1;
+      a[1] += x2;
     } else {
-      u += pair_cost(x1, x2, mode);
-      v += x1 > x2 ? 1.f : 0.f;
+      a[0] += pair_cost(x1, x2, mode);
+      a[1] += x1 > x2 ? 1.f : 0.f;
     }
   }
-  r0[t] = u;
-  r1[t] = v;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (t < w) {
-      r0[t] += r0[t + w];
-      r1[t] += r1[t + w];
-    }
-    __syncthreads();
-  }
+  block_sum(a, red);
   if (t == 0) {
     if (mode == KGCN_LP_IP) {
-      const float S1 = r0[0], S2 = r1[0], c = pair_cost(S1, S2, mode);
+      const float S1 = a[0], S2 = a[1], c = pair_cost(S1, S2, mode);
       sums[0] = c;
       sums[1] = c;
       sums[2] = S1 > S2 ? 1.f : 0.f;
       sums[3] = S1;
       sums[4] = S2;
     } else {
-      sums[0] = r0[0] / (float)L;
-      sums[1] = r0[0];
-      sums[2] = r1[0];
+      sums[0] = a[0] / (float)L;
+      sums[1] = a[0];
+      sums[2] = a[1];
       sums[3] = 0.f;
       sums[4] = 0.f;
     }

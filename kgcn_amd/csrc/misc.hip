@@ -1,6 +1,7 @@
 // Library bookkeeping (error text, ABI version) and the small reductions of the path:
 // GraphGather (kgcn/layers.py:163-164) forward/backward, also into / out of a column block of a wider
 // buffer, and the dot product behind d eps of GINAggregate (kgcn/layers.py:469).
+#include "block_reduce.h"
 #include "kgcn_common.h"
 
 namespace kgcn {
@@ -121,7 +122,7 @@ __global__ __launch_bounds__(256) void dot_partial_kernel(const float* __restric
   }
   for (long i = done + tid; i < n; i += nthr) s1 += a[i] * b[i];
   float s = (s0 + s1) + (s2 + s3);
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
@@ -142,7 +143,7 @@ __global__ __launch_bounds__(256) void dot_final_kernel(const float* __restrict_
     for (int u = 0; u < 8; ++u) s += v[u];
   }
   for (; i < nparts; i += 256) s += part[i];
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+  s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) out[0] = (red[0] + red[1]) + (red[2] + red[3]);

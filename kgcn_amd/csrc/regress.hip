@@ -7,38 +7,21 @@
 //   error_sum [T], count [T] = sum_b mask_label                  (per task; their totals are the file's metrics)
 //   dpred     = d cost_sum / d pred = -2 mask_label (labels - pred)
 //
-// As csrc/cvloss.hip: one workgroup per task sums its column over the rows in a fixed order (thread-strided partials, one tree),
-// a one-workgroup kernel behind it adds the tasks and, when the call carries an accumulator block [2 T + 1] =
-// error_sum | count | cost_sum, adds the batch's values into it in place (an epoch is read back once).  No float atomics.
+// A task-column head, like the softmax2 head of cvloss.hip: one workgroup per task sums its column over the rows in a fixed
+// order (thread-strided partials, one block_sum), the shared finish kernel of block_reduce.h behind it adds the tasks and, when
+// the call carries an accumulator block [2 T + 1] = error_sum | count | cost_sum, adds the batch's values into it in place (an
+// epoch is read back once).  No float atomics.
 //
 // kgcn_regression_sums_f64: per task over n rows, two passes in fp64 inside one workgroup (pass 1: n, sum y; pass 2 around the
 // mean: sum (y - mean)^2, sum (y - p)^2, sum log(y / p) over the rows whose ratio is positive and finite, the count of the
 // others), thread-strided partials and one tree: fixed order, no atomics.
+#include "block_reduce.h"
 #include "kgcn_common.h"
 
 namespace kgcn {
 namespace {
 
 constexpr int kBlock = 256;
-
-template <typename V, int M>
-__device__ __forceinline__ void block_sum(V (&v)[M], V (*red)[kBlock]) {
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int q = 0; q < M; ++q) red[q][t] = v[q];
-  __syncthreads();
-#pragma unroll
-  for (int off = kBlock / 2; off > 0; off >>= 1) {
-    if (t < off) {
-#pragma unroll
-      for (int q = 0; q < M; ++q) red[q][t] += red[q][t + off];
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int q = 0; q < M; ++q) v[q] = red[q][0];
-  __syncthreads();
-}
 
 // stats [2 T + 3] = error_sum [T] | count [T] | cost_sum | cost_opt | spare; this kernel writes the first 2 T
 __global__ __launch_bounds__(kBlock) void sqerr_kernel(const float* __restrict__ pred, const float* __restrict__ labels,
@@ -64,20 +47,7 @@ __global__ __launch_bounds__(kBlock) void sqerr_kernel(const float* __restrict__
   }
 }
 
-__global__ __launch_bounds__(kBlock) void sqerr_finish_kernel(float* __restrict__ stats, long B, int T, float* __restrict__ accum) {
-  __shared__ float red[1][kBlock];
-  float v[1] = {0.f};
-  for (int t = threadIdx.x; t < T; t += kBlock) v[0] += stats[t];
-  block_sum(v, red);
-  if (threadIdx.x == 0) {
-    stats[2 * T] = v[0];
-    stats[2 * T + 1] = v[0] / ((float)B * (float)T);
-  }
-  if (accum) {
-    for (int i = threadIdx.x; i < 2 * T; i += kBlock) accum[i] += stats[i];
-    if (threadIdx.x == 0) accum[2 * T] += v[0];
-  }
-}
+// the kernel behind it: task_loss_finish_kernel<2, true> (block_reduce.h)
 
 // out [T, 6] = n | sum y | sum (y - mean)^2 | sum (y - p)^2 | sum log(y / p) | rows with y / p <= 0 or not finite
 __global__ __launch_bounds__(kBlock) void regression_sums_kernel(const float* __restrict__ pred, long pred_ld,
@@ -128,7 +98,7 @@ extern "C" int kgcn_masked_sqerr_f32(const float* pred, const float* labels, con
   hipStream_t s = as_stream(stream);
   hipLaunchKernelGGL(sqerr_kernel, dim3((unsigned)tasks), dim3(kBlock), 0, s, pred, labels, mask_label, (long)batch, (int)tasks, dpred,
                      stats);
-  hipLaunchKernelGGL(sqerr_finish_kernel, dim3(1), dim3(kBlock), 0, s, stats, (long)batch, (int)tasks, accum);
+  hipLaunchKernelGGL((task_loss_finish_kernel<2, true>), dim3(1), dim3(kBlock), 0, s, stats, (long)batch, (int)tasks, accum);
   return check_launch(who);
 }
 

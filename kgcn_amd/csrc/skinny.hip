@@ -9,6 +9,7 @@
 //                    columns, their W entries live in registers, the k inputs of a row are wave-uniform
 //   skinny_n_wgrad   dW[k, n] = x^T g, db = colsum g, n <= 16: lanes own k (their dW rows in registers across the wave's
 //                    rows), one partial per workgroup, fixed-order second stage (reduce_partials)
+#include "block_reduce.h"
 #include "dense_kernels.h"
 
 namespace kgcn {
@@ -35,10 +36,7 @@ __global__ __launch_bounds__(256) void skinny_n_fwd_kernel(const float* __restri
       for (int j = 0; j < N; ++j) acc[j] = __builtin_fmaf(xv, j < n ? wr[j] : 0.f, acc[j]);
     }
 #pragma unroll
-    for (int j = 0; j < N; ++j) {
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) acc[j] += __shfl_xor(acc[j], o, 64);
-    }
+    for (int j = 0; j < N; ++j) acc[j] = wave_sum(acc[j]);
     float out = 0.f;
 #pragma unroll
     for (int j = 0; j < N; ++j) out = lane == j ? acc[j] : out;

@@ -11,23 +11,24 @@
 //                                             m = b1 m + (1 - b1) g ; v = b2 v + (1 - b2) g^2
 //                                             p -= lr_t m / (sqrt(v) + eps)              ("epsilon hat" OUTSIDE the root)
 //                                           t lives in device memory (a captured hipGraph advances it on replay).
+#include "block_reduce.h"
 #include "kgcn_common.h"
 
 namespace kgcn {
 
 constexpr int kLossBlock = 256;
 
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-#pragma unroll
-  for (int off = 128; off > 0; off >>= 1) {
-    if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-    __syncthreads();
+// the tail of both loss kernels: this workgroup's partial, and the totals themselves when the batch fits this one workgroup (no
+// finishing launch)
+__device__ __forceinline__ void loss_epilogue(float c, float* red, long B, float* __restrict__ part, float* __restrict__ sums_direct) {
+  const float s = block_sum(c, red);
+  if (threadIdx.x == 0) {
+    part[blockIdx.x] = s;
+    if (sums_direct) {
+      sums_direct[0] = s;
+      sums_direct[1] = s / (float)B;
+    }
   }
-  const float s = red[0];
-  __syncthreads();
-  return s;
 }
 
 // example_model/model_multitask.py:66-76:  cost[b] = mask[b] * sum_t mask_label[b,t] * ce(logits[b,t], labels[b,t])
@@ -72,14 +73,7 @@ __global__ __launch_bounds__(kLossBlock) void sigmoid_ce_kernel(const float* __r
     c *= mk;
     if (cost) cost[b] = c;
   }
-  const float s = block_sum_256(c, red);
-  if (threadIdx.x == 0) {
-    part[blockIdx.x] = s;
-    if (sums_direct) {                                 // the batch fits this one workgroup: no finishing launch
-      sums_direct[0] = s;
-      sums_direct[1] = s / (float)B;
-    }
-  }
+  loss_epilogue(c, red, B, part, sums_direct);
 }
 
 // example_model/model.py:56-61:  cost[b] = mask[b] * -(sum_c labels[b,c] log_softmax(logits[b])[c])
@@ -118,14 +112,7 @@ __global__ __launch_bounds__(kLossBlock) void softmax_ce_kernel(const float* __r
       dlogits[b * C + k] = mk * (__expf(x[k] - mx) * inv * zs - (z ? z[k] : (k == li ? 1.f : 0.f)));
     if (cost) cost[b] = c;
   }
-  const float s = block_sum_256(c, red);
-  if (threadIdx.x == 0) {
-    part[blockIdx.x] = s;
-    if (sums_direct) {                                 // the batch fits this one workgroup: no finishing launch
-      sums_direct[0] = s;
-      sums_direct[1] = s / (float)B;
-    }
-  }
+  loss_epilogue(c, red, B, part, sums_direct);
 }
 
 // sums[0] = sum of the block partials (fixed order), sums[1] = sums[0] / B  (reduce_sum / reduce_mean over the PADDED batch)
@@ -134,7 +121,7 @@ __global__ __launch_bounds__(kLossBlock) void loss_finish_kernel(const float* __
   __shared__ float red[kLossBlock];
   float a = 0.f;
   for (int i = threadIdx.x; i < nparts; i += kLossBlock) a += part[i];
-  const float s = block_sum_256(a, red);
+  const float s = block_sum(a, red);
   if (threadIdx.x == 0) {
     sums[0] = s;
     sums[1] = s / (float)B;
@@ -211,68 +198,72 @@ extern "C" int64_t kgcn_loss_workspace_bytes(int64_t batch) {
   return ((batch + kLossBlock - 1) / kLossBlock) * 4;
 }
 
-static int loss_args(const char* who, const void* logits, const void* labels, const void* mask, int64_t batch, int32_t width,
-                     const void* dlogits, const void* sums, const void* ws, int64_t wsb) {
+// the checks of the three loss heads; labels = the dense labels or the class indices; the sparse head alone may go without a mask
+static int loss_args(const char* who, const void* logits, const void* labels, const void* mask, bool need_mask, int64_t batch,
+                     int32_t width, const void* dlogits, const void* sums, const void* ws, int64_t wsb) {
   if (batch <= 0 || width <= 0) return fail("%s: bad shape batch=%lld width=%d", who, (long long)batch, width);
-  if (!logits || !labels || !mask || !dlogits || !sums) return fail("%s: NULL operand", who);
+  if (!logits || !labels || (need_mask && !mask) || !dlogits || !sums) return fail("%s: NULL operand", who);
   if (!ws || wsb < kgcn_loss_workspace_bytes(batch))
     return fail("%s: workspace %lld < %lld bytes", who, (long long)wsb, (long long)kgcn_loss_workspace_bytes(batch));
   if ((batch + kLossBlock - 1) / kLossBlock > 0x7fffffffLL) return fail("%s: batch too large", who);
   return 0;
 }
 
+static int loss_blocks(int64_t batch) { return (int)((batch + kLossBlock - 1) / kLossBlock); }
+
+// behind a loss kernel of nb workgroups: one workgroup wrote the totals itself, more leave their partials to loss_finish_kernel
+static int finish_loss(int nb, const float* part, int64_t batch, float* sums, hipStream_t s) {
+  if (nb == 1) return 0;
+  hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(kLossBlock), 0, s, part, nb, (long)batch, sums);
+  return check_launch("loss_finish_kernel");
+}
+
 extern "C" int kgcn_masked_sigmoid_ce_f32(const float* logits, const float* labels, const float* mask,
                                           const float* mask_label, int64_t batch, int32_t tasks, int32_t weighted,
                                           float pos_weight, const float* pos_weight_per_task, float* cost, float* dlogits,
                                           float* sums, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (int rc = loss_args("kgcn_masked_sigmoid_ce_f32", logits, labels, mask, batch, tasks, dlogits, sums, workspace,
+  if (int rc = loss_args("kgcn_masked_sigmoid_ce_f32", logits, labels, mask, true, batch, tasks, dlogits, sums, workspace,
                          workspace_bytes))
     return rc;
-  const int nb = (int)((batch + kLossBlock - 1) / kLossBlock);
+  const int nb = loss_blocks(batch);
   float* part = static_cast<float*>(workspace);
   hipStream_t s = as_stream(stream);
   hipLaunchKernelGGL(sigmoid_ce_kernel, dim3(nb), dim3(kLossBlock), 0, s, logits, labels, mask, mask_label, (long)batch, tasks,
                      weighted ? 1 : 0, pos_weight, weighted ? pos_weight_per_task : nullptr, cost, dlogits, part,
                      nb == 1 ? sums : nullptr);
   if (int rc = check_launch("sigmoid_ce_kernel")) return rc;
-  if (nb == 1) return 0;
-  hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(kLossBlock), 0, s, part, nb, (long)batch, sums);
-  return check_launch("loss_finish_kernel");
+  return finish_loss(nb, part, batch, sums, s);
 }
 
 extern "C" int kgcn_masked_softmax_ce_f32(const float* logits, const float* labels, const float* mask, int64_t batch,
                                           int32_t classes, float* cost, float* dlogits, float* sums, void* workspace,
                                           int64_t workspace_bytes, void* stream) {
-  if (int rc = loss_args("kgcn_masked_softmax_ce_f32", logits, labels, mask, batch, classes, dlogits, sums, workspace,
+  if (int rc = loss_args("kgcn_masked_softmax_ce_f32", logits, labels, mask, true, batch, classes, dlogits, sums, workspace,
                          workspace_bytes))
     return rc;
-  const int nb = (int)((batch + kLossBlock - 1) / kLossBlock);
+  const int nb = loss_blocks(batch);
   float* part = static_cast<float*>(workspace);
   hipStream_t s = as_stream(stream);
   hipLaunchKernelGGL(softmax_ce_kernel, dim3(nb), dim3(kLossBlock), 0, s, logits, labels, nullptr, mask, (long)batch, classes,
                      cost, dlogits, part, nb == 1 ? sums : nullptr);
   if (int rc = check_launch("softmax_ce_kernel")) return rc;
-  if (nb == 1) return 0;
-  hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(kLossBlock), 0, s, part, nb, (long)batch, sums);
-  return check_launch("loss_finish_kernel");
+  return finish_loss(nb, part, batch, sums, s);
 }
 
 extern "C" int kgcn_sparse_softmax_ce_f32(const float* logits, const int64_t* label_idx, const float* mask, int64_t batch,
                                           int32_t classes, float* cost, float* dlogits, float* sums, void* workspace,
                                           int64_t workspace_bytes, void* stream) {
-  if (batch <= 0 || classes <= 0) return fail("kgcn_sparse_softmax_ce_f32: bad shape batch=%lld classes=%d", (long long)batch, classes);
-  if (!logits || !label_idx || !dlogits || !sums) return fail("kgcn_sparse_softmax_ce_f32: NULL operand");
-  if (!workspace || workspace_bytes < kgcn_loss_workspace_bytes(batch)) return fail("kgcn_sparse_softmax_ce_f32: workspace too small");
-  const int nb = (int)((batch + kLossBlock - 1) / kLossBlock);
+  if (int rc = loss_args("kgcn_sparse_softmax_ce_f32", logits, label_idx, mask, false, batch, classes, dlogits, sums, workspace,
+                         workspace_bytes))
+    return rc;
+  const int nb = loss_blocks(batch);
   float* part = static_cast<float*>(workspace);
   hipStream_t s = as_stream(stream);
   hipLaunchKernelGGL(softmax_ce_kernel, dim3(nb), dim3(kLossBlock), 0, s, logits, nullptr,
                      reinterpret_cast<const long long*>(label_idx), mask, (long)batch, classes, cost, dlogits, part,
                      nb == 1 ? sums : nullptr);
   if (int rc = check_launch("softmax_ce_kernel")) return rc;
-  if (nb == 1) return 0;
-  hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(kLossBlock), 0, s, part, nb, (long)batch, sums);
-  return check_launch("loss_finish_kernel");
+  return finish_loss(nb, part, batch, sums, s);
 }
 
 extern "C" int kgcn_loss_grad_f32(const float* dlogits, const float* g_opt, const float* g_sum, int64_t batch, int64_t n,

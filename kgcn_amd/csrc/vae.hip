@@ -15,6 +15,7 @@
 //           dY_c = (H Y_c) * w_c, dw_c = 1/2 sum_i Y_c[i] * (H Y_c)[i] (per-workgroup partials, deferrable second stage).
 // One workgroup owns one graph at a time and keeps Y_c and the N x N label / gradient matrix in LDS; L is evaluated in
 // 4 x 4 register tiles of the upper triangle only (L is symmetric), in fp32 with fused multiply-adds.
+#include "block_reduce.h"
 #include "kgcn_common.h"
 #include "philox.h"
 
@@ -75,7 +76,9 @@ __global__ __launch_bounds__(256) void vae_sample_fwd_kernel(const float* __rest
     red[t] = term;
   }
   __syncthreads();
-  for (int w = 32; w > 0; w >>= 1) {           // fixed-order tree over the 64 columns
+  // fixed-order tree over the 64 columns, levels 32 .. 1 with the pairing of block_sum (block_reduce.h); kept in place: red is
+  // 64 floats here, block_sum's tree wants 256
+  for (int w = 32; w > 0; w >>= 1) {
     if (t < w) red[t] += red[t + w];
     __syncthreads();
   }
@@ -151,17 +154,6 @@ struct ReconArgs {
 
 __device__ __forceinline__ float sig_ce(float l, float a) { return fmaxf(l, 0.f) - l * a + log1pf(expf(-fabsf(l))); }
 __device__ __forceinline__ float sigmoid_f(float l) { return 1.f / (1.f + expf(-l)); }
-
-__device__ __forceinline__ float block_sum(float v, float* red) {   // fixed-order tree over 256 threads
-  __syncthreads();
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
-  return red[0];
-}
 
 // tile u of the upper triangle (I <= J) of a T4 x T4 tile grid, row-major
 __device__ __forceinline__ void upper_tile(int u, int T4, int& I, int& J) {

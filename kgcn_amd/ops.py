@@ -1562,12 +1562,29 @@ def augment_ones(x2d, width):
 # -------------------------------------------------------------------------------------------------
 # losses of the model files: one HIP pass (cost per graph, d cost_sum / d logits, partial sums) + one finishing block
 # -------------------------------------------------------------------------------------------------
-def _loss_grad(dlog, g_opt, g_sum, batch):
-    """d logits = dlog * (g_sum + g_opt / batch) in one launch (kgcn_loss_grad_f32)."""
+def _grad_scalars(g_opt, g_sum):
+    """The upstream gradients of a loss head's (cost_opt, cost_sum) as device scalars (go, gs), either of them None where autograd
+    passed none; None when it passed neither."""
     if g_opt is None and g_sum is None:
         return None
-    go = None if g_opt is None else _f32c(g_opt.reshape(1), "grad")
-    gs = None if g_sum is None else _f32c(g_sum.reshape(1), "grad")
+    return tuple(None if g is None else _f32c(g.reshape(1), "grad") for g in (g_opt, g_sum))
+
+
+def _accum_block(accum, n, who, layout):
+    """Check the optional epoch accumulator of a task-column loss head: n = `layout` floats."""
+    if accum is None:
+        return
+    require_gpu(accum, "accum")
+    if accum.dtype != torch.float32 or not accum.is_contiguous() or accum.numel() != n:
+        raise _lib.KgcnHipError("%s: the accumulator is a contiguous float32 block of %s = %d" % (who, layout, n))
+
+
+def _loss_grad(dlog, g_opt, g_sum, batch):
+    """d logits = dlog * (g_sum + g_opt / batch) in one launch (kgcn_loss_grad_f32)."""
+    g = _grad_scalars(g_opt, g_sum)
+    if g is None:
+        return None
+    go, gs = g
     out = torch.empty_like(dlog)
     check(lib.kgcn_loss_grad_f32(ptr(dlog), ptr(go), ptr(gs), batch, dlog.numel(), ptr(out), current_stream()), "kgcn_loss_grad_f32")
     return out
@@ -1882,10 +1899,10 @@ class _VaeRecon(torch.autograd.Function):
         ys, ws = saved[3:3 + C], saved[3 + C:]
         B, N, D = ys[0].shape
         F = xf.shape[2]
-        if g_opt is None and g_sum is None:
+        g = _grad_scalars(g_opt, g_sum)
+        if g is None:
             return (None,) * (5 + 2 * C)
-        go = None if g_opt is None else _f32c(g_opt.reshape(1), "grad")
-        gs = None if g_sum is None else _f32c(g_sum.reshape(1), "grad")
+        go, gs = g
         dys = [torch.empty_like(y) for y in ys]
         dws = [torch.empty((D,), device=xf.device, dtype=torch.float32) for _ in range(C)]
         dxf = torch.empty_like(xf)
@@ -2389,10 +2406,10 @@ class _LinkPredLoss(torch.autograd.Function):
     def backward(ctx, g_opt, g_sum, _g_count, _g_s1, _g_s2, _g_rows):
         h, wc, rows, s1, s2, sums = ctx.saved_tensors
         N, D = h.shape
-        if g_opt is None and g_sum is None:
+        g = _grad_scalars(g_opt, g_sum)
+        if g is None:
             return (None,) * 9
-        go = None if g_opt is None else _f32c(g_opt.reshape(1), "grad")
-        gs = None if g_sum is None else _f32c(g_sum.reshape(1), "grad")
+        go, gs = g
         R = wc.shape[0] if ctx.has_w else 0
         dh = torch.empty_like(h)
         dw = torch.empty_like(wc) if ctx.has_w else None
@@ -2651,10 +2668,7 @@ class _MultitaskSoftmax2CE(torch.autograd.Function):
             raise _lib.KgcnHipError("multitask_softmax2_ce: logits %s must be [B, 2, T] (or [B, 2 T]) for labels %s and mask_label %s"
                                     % (tuple(x.shape), tuple(z.shape), tuple(ml.shape)))
         B, T = z.shape
-        if accum is not None:
-            require_gpu(accum, "accum")
-            if accum.dtype != torch.float32 or not accum.is_contiguous() or accum.numel() != 3 * T + 1:
-                raise _lib.KgcnHipError("multitask_softmax2_ce: the accumulator is a contiguous float32 block of 3 T + 1 = %d" % (3 * T + 1))
+        _accum_block(accum, 3 * T + 1, "multitask_softmax2_ce", "3 T + 1")
         dlog = torch.empty_like(x)
         pred = torch.empty((B, T), device=x.device, dtype=torch.float32)
         stats = torch.empty((3 * T + 1,), device=x.device, dtype=torch.float32)
@@ -2890,10 +2904,7 @@ class _MaskedSqErr(torch.autograd.Function):
             raise _lib.KgcnHipError("masked_squared_error: pred %s, labels %s and mask_label %s must be one [B, T] shape"
                                     % (tuple(p.shape), tuple(z.shape), tuple(ml.shape)))
         B, T = p.shape
-        if accum is not None:
-            require_gpu(accum, "accum")
-            if accum.dtype != torch.float32 or not accum.is_contiguous() or accum.numel() != 2 * T + 1:
-                raise _lib.KgcnHipError("masked_squared_error: the accumulator is a contiguous float32 block of 2 T + 1 = %d" % (2 * T + 1))
+        _accum_block(accum, 2 * T + 1, "masked_squared_error", "2 T + 1")
         dpred = torch.empty_like(p)
         stats = torch.empty((2 * T + 2,), device=p.device, dtype=torch.float32)
         check(lib.kgcn_masked_sqerr_f32(ptr(p), ptr(z), ptr(ml), B, T, ptr(dpred), ptr(stats), ptr(accum), current_stream()),

@@ -63,10 +63,19 @@ def case(rng, B, T, scale=3.0):
     return logits, labels, mask
 
 
-@pytest.mark.parametrize("T", [1, 4, 7])
-@pytest.mark.parametrize("B", [1, 3, 50, 257])
+# (2, 257): more tasks than the finish kernel has threads, so its task loop takes a second trip
+@pytest.mark.parametrize("B,T", [(B, T) for T in (1, 4, 7) for B in (1, 3, 50, 257)] + [(2, 257)])
 def test_against_the_oracle(B, T):
-    compare(*case(np.random.default_rng(100 * B + T), B, T))
+    import torch
+    logits, labels, mask = case(np.random.default_rng(100 * B + T), B, T)
+    got, _ = compare(logits, labels, mask)
+    # the same call twice with an accumulator: its own values unchanged, the block = the float32 sum of the two
+    acc = torch.zeros(3 * T + 1, device="cuda:0")
+    block = np.concatenate([got["each_cost"], got["each_correct"], got["each_count"], np.frombuffer(got["cost_bits"], np.float32)])
+    for _ in range(2):
+        again = run(logits, labels, mask, accum=acc, backward=False)
+        assert again["cost_bits"] == got["cost_bits"] and again["each_cost"].tobytes() == got["each_cost"].tobytes()
+    assert acc.cpu().numpy().tobytes() == (block + block).astype(np.float32).tobytes()
 
 
 def test_large_logits_stay_finite():

@@ -163,7 +163,7 @@ def test_fused_route_twice_bit_for_bit(fused):
 
 
 # ---- the regression head --------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("B,Tn", [(1, 1), (50, 2), (257, 12)])
+@pytest.mark.parametrize("B,Tn", [(1, 1), (50, 2), (257, 12), (2, 257)])     # 257 tasks: a second trip of the finish kernel's task loop
 def test_masked_squared_error(B, Tn):
     import torch
     from kgcn_amd import ops
@@ -171,7 +171,8 @@ def test_masked_squared_error(B, Tn):
     pred = rng.standard_normal((B, Tn)).astype(np.float32)
     lab = (rng.standard_normal((B, Tn)) + 1.0).astype(np.float32)
     mask = (rng.random((B, Tn)) < 0.8).astype(np.float32)
-    mask[:, Tn - 1] = 0.0                                           # an all-masked task: count 0
+    mask[0, np.flatnonzero(mask.sum(axis=0) == 0)] = 1.0            # (two rows, 257 tasks: some column draws no row) every task counts one ...
+    mask[:, Tn - 1] = 0.0                                           # ... but the last, an all-masked task: count 0
     pred[0, Tn - 1] = np.inf                                        # ... whose rows must not leak into cost or gradient
     tp = T(pred, True)
     accum = torch.zeros(2 * Tn + 1, device=dev())
