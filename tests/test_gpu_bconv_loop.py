@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import act64, dact64
 from test_gpu_parity import K, close, dev, t32
 
 pytestmark = pytest.mark.gpu
@@ -34,26 +35,6 @@ def _channels(rng, T, N, C, density, empty_graph_every=0, dense_channel=None):
             row.append((idx, val, [N, N]))
         adjs.append(row)
     return adjs
-
-
-def _act(v, act):
-    if act == "sigmoid":
-        return 1.0 / (1.0 + np.exp(-v))
-    if act == "relu":
-        return np.maximum(v, 0.0)
-    if act == "tanh":
-        return np.tanh(v)
-    return v
-
-
-def _dact(a, act):
-    if act == "sigmoid":
-        return a * (1.0 - a)
-    if act == "relu":
-        return (a > 0).astype(np.float64)
-    if act == "tanh":
-        return 1.0 - a * a
-    return np.ones_like(a)
 
 
 @pytest.mark.parametrize("T,N,C,d,act,dense_channel", [
@@ -88,14 +69,14 @@ def test_bconv_forward_and_fanout(T, N, C, d, act, dense_channel):
     g = rng.standard_normal((T * N, d)).astype(np.float32)
     dense = [[rhs[b * N:(b + 1) * N, c * d:(c + 1) * d] for c in range(C)] for b in range(T)]
     ref = np.stack(K.bconv(adjs, dense)).astype(np.float64)
-    ref_act = _act(ref, act)
+    ref_act = act64(ref, act)
     tr = t32(rhs).requires_grad_(True)
     out = ops.bconv(adj, tr, d, activation=act)
     close(out, ref_act.reshape(T * N, d), rel=2e-6, what="bconv forward (%s)" % act)
     out.backward(t32(g))
     # d rhs_c = A_c^T (g (.) act'(out))
     aout = out.detach().cpu().numpy().astype(np.float64) if act == "relu" else ref_act.reshape(T * N, d)
-    dpre = (g.astype(np.float64) * _dact(aout, act)).reshape(T, N, d)
+    dpre = (g.astype(np.float64) * dact64(aout, act)).reshape(T, N, d)
     _, rg = K.bconv_grad(adjs, dense, list(dpre))
     want = np.concatenate([np.concatenate([rg[b][c] for c in range(C)], axis=1) for b in range(T)], axis=0)
     close(tr.grad, want, rel=2e-6, what="bconv fan-out adjoint (%s)" % act)

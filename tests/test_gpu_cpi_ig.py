@@ -7,7 +7,6 @@ every compound holds its self loop only; rows past the size are padding and stil
 Bound: 1e-5 of max|oracle| per output array (the family's bound: test_gpu_kg_ig.py, test_gpu_multimodal_ig.py), ratcheted to ten
 times the error measured on the MI355X (tests/golden/cpi_ig_bounds.json; never below one fp32 ulp, 2^-23: the outputs are fp32;
 never above 1e-5).  KGCN_CPI_IG_RECORD=<file> writes the errors of a run."""
-import json
 import os
 import sys
 
@@ -18,6 +17,7 @@ torch = pytest.importorskip("torch")
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import cpi_ig_oracle as O  # noqa: E402
+import family_bounds  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -25,40 +25,11 @@ N, F, WD = 10, 6, 512
 SIZES = [7, 0, 10, 4, 1]
 D = 8
 TOL = 1e-5
-ULP = 2.0 ** -23
-BOUNDS_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cpi_ig_bounds.json")
-MEASURED = {}
+# FB.check: equal shapes, finite values, a reference that is not all zero; then max|got - ref| / max|oracle| under `key`, held to
+# min(1e-5, max(2^-23, stored))
+FB = family_bounds.FAMILIES["cpi_ig"]
 MODALS = ("all", "features", "adjs")
 METHODS = ("ig", "grad_prod", "grad")
-
-
-def _bounds():
-    if not os.path.exists(BOUNDS_PATH):
-        return {}
-    return json.load(open(BOUNDS_PATH)).get("bounds", {})
-
-
-def _check(key, got, ref, tag=""):
-    """max|got - ref| / max|ref| printed, recorded under `key`, and held to min(1e-5, the ratcheted bound)."""
-    ref = np.asarray(ref, np.float64)
-    got = np.asarray(got, np.float64)
-    assert got.shape == ref.shape, (key, got.shape, ref.shape)
-    assert np.isfinite(got).all(), key
-    assert np.abs(ref).max() > 0, key
-    err = float(np.abs(got - ref).max() / np.abs(ref).max())
-    MEASURED[key] = max(MEASURED.get(key, 0.0), err)
-    bound = min(TOL, max(ULP, _bounds().get(key, TOL)))
-    print("cpi_ig %-28s %-34s err / max|oracle| = %.3e  (bound %.3e)" % (key, tag, err, bound))
-    assert err <= bound, (key, tag, err, bound)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _record():
-    yield
-    path = os.environ.get("KGCN_CPI_IG_RECORD")
-    if path:
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        json.dump({"measured": MEASURED}, open(path, "w"), indent=1, sort_keys=True)
 
 
 # ---- the op against the sweep ------------------------------------------------------------------------------------------------
@@ -108,9 +79,9 @@ def test_op_parity(shape):
     assert tuple(p.shape) == (2, K, T) and tuple(GA.shape) == (2, T, n, wd) == tuple(GB.shape)
     for name, got in (("p", p), ("GA", GA), ("GB", GB)):
         assert torch.isfinite(got).all(), name
-    _check("op p", p.cpu().numpy(), rp, shape)
-    _check("op GA", GA.cpu().numpy(), rGA, shape)
-    _check("op GB", GB.cpu().numpy(), rGB, shape)
+    FB.check("op p", p.cpu().numpy(), rp, shape)
+    FB.check("op GA", GA.cpu().numpy(), rGA, shape)
+    FB.check("op GB", GB.cpu().numpy(), rGB, shape)
     p1, GA1, GB1 = _run_op(case, with_b=False)                        # the one-tensor kernel: the same bits, no G^B
     assert GB1 is None and torch.equal(p1, p) and torch.equal(GA1, GA)
     one = _run_op(tuple(a[1:2] if i < 2 else a for i, a in enumerate(case)))      # a compound alone: the same bits
@@ -182,12 +153,12 @@ def _stack(recs, ref, name):
 def _against_literal(prefix, recs, ref, modal, tag):
     assert [(r["compound_id"], r["task"]) for r in recs] == [(g, t) for g in range(len(SIZES)) for t in range(len(ref[0]))]
     for m in O.modal_targets(modal):
-        _check(prefix + " " + m + "_IG", *_stack(recs, ref, m + "_IG"), tag)
+        FB.check(prefix + " " + m + "_IG", *_stack(recs, ref, m + "_IG"), tag)
     se = np.array([[ref[r["compound_id"]][r["task"]]["start"], ref[r["compound_id"]][r["task"]]["end"]] for r in recs])
-    _check(prefix + " start", [r["start_score"] for r in recs], se[:, 0], tag)
-    _check(prefix + " end", [r["end_score"] for r in recs], se[:, 1], tag)
-    _check(prefix + " check_score", [r["check_score"] for r in recs], se[:, 1] - se[:, 0], tag)
-    _check(prefix + " prediction_score", [r["prediction_score"] for r in recs], se[:, 1], tag)      # the unscaled forward pass
+    FB.check(prefix + " start", [r["start_score"] for r in recs], se[:, 0], tag)
+    FB.check(prefix + " end", [r["end_score"] for r in recs], se[:, 1], tag)
+    FB.check(prefix + " check_score", [r["check_score"] for r in recs], se[:, 1] - se[:, 0], tag)
+    FB.check(prefix + " prediction_score", [r["prediction_score"] for r in recs], se[:, 1], tag)      # the unscaled forward pass
     for r in recs:
         total = sum(float(r[m + "_IG"].astype(np.float64).sum()) for m in O.modal_targets(modal))
         assert r["sum_of_IG"] == total and r["check_score"] == r["end_score"] - r["start_score"]
@@ -302,11 +273,8 @@ def test_completeness_with_the_reference_step_count():
             assert r["compound_id"] == 1 and gpu_gap == 0 and r["sum_of_IG"] == 0
             continue
         excess = max(0.0, gpu_gap - oracle_gap) / scale
-        key = "completeness excess / scale"
-        MEASURED[key] = max(MEASURED.get(key, 0.0), excess)
-        print("cpi_ig compound %d task %d: gap gpu %.3e oracle %.3e of %.3e (excess / scale %.2e)"
-              % (r["compound_id"], r["task"], gpu_gap, oracle_gap, abs(want), excess))
-        assert excess <= TOL
+        print("cpi_ig compound %d task %d: gap gpu %.3e oracle %.3e of %.3e" % (r["compound_id"], r["task"], gpu_gap, oracle_gap, abs(want)))
+        FB.hold("completeness excess / scale", excess, "compound %d task %d" % (r["compound_id"], r["task"]))
         assert oracle_gap <= 0.05 * abs(want) + 1e-9                   # D = 100 is close to the integral
 
 

@@ -1,7 +1,7 @@
 """models.CPIMultitaskNet (sample_chem/compound-protein_interaction/multitask.py) on the GPU against tests/cv_oracle in fp64 at
 B = 5, N = 10, F = 8, T = 3 with one and two adjacency channels: logits, cost and every parameter gradient within the bounds of
-tests/golden/cv_bounds.json; then ten replays of the captured training step against ten eager steps, bit for bit."""
-import json
+tests/golden/cv_bounds.json (KGCN_CV_RECORD=<file> writes the errors of a run); then ten replays of the captured training step
+against ten eager steps, bit for bit."""
 import os
 import sys
 
@@ -11,23 +11,13 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import cv_oracle as O  # noqa: E402
+import family_bounds  # noqa: E402
 from oracle import kgcn_oracle as K  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-BOUNDS = json.load(open(os.path.join(ROOT, "tests", "golden", "cv_bounds.json")))["bounds"]
+FB = family_bounds.FAMILIES["cv"]               # FB.check: max|got - ref| / max(1, max|ref|), held to the stored bound
 B, N, F, T = 5, 10, 8, 3
-
-
-def nerr(got, ref):
-    ref = np.asarray(ref, np.float64)
-    return float(np.abs(np.asarray(got, np.float64) - ref).max()) / max(1.0, float(np.abs(ref).max()))
-
-
-def held(what, got, ref, label=""):
-    e = nerr(got, ref)
-    print("%-12s %-10s err / max(1, |ref|) = %.3e (bound %.3e)" % (what, label, e, BOUNDS[what]))
-    assert e <= BOUNDS[what], (what, label, e, BOUNDS[what])
 
 
 @pytest.mark.parametrize("C", [1, 2])
@@ -58,13 +48,13 @@ def test_forward_loss_and_gradients(C):
     p = {"w": [w.detach().cpu().numpy() for w in model.conv.w], "b": [b.detach().cpu().numpy() for b in model.conv.bias],
          "kernel": model.out.kernel.detach().cpu().numpy(), "bias": model.out.bias.detach().cpu().numpy()}
     L, ref_logits, g = O.model_loss_grads(x, adjs, p, labels, mask)
-    held("model_logits", logits.detach().cpu().numpy(), ref_logits)
-    held("model_cost", float(cost.detach()), L["cost"])
+    FB.check("model_logits", logits.detach().cpu().numpy(), ref_logits)
+    FB.check("model_cost", float(cost.detach()), L["cost"])
     for c in range(C):
-        held("model_grad", model.conv.w[c].grad.cpu().numpy(), g["w"][c], "w%d" % c)
-        held("model_grad", model.conv.bias[c].grad.cpu().numpy().reshape(-1), g["b"][c], "b%d" % c)
-    held("model_grad", model.out.kernel.grad.cpu().numpy(), g["kernel"], "kernel")
-    held("model_grad", model.out.bias.grad.cpu().numpy(), g["bias"], "bias")
+        FB.check("model_grad", model.conv.w[c].grad.cpu().numpy(), g["w"][c], "w%d" % c)
+        FB.check("model_grad", model.conv.bias[c].grad.cpu().numpy().reshape(-1), g["b"][c], "b%d" % c)
+    FB.check("model_grad", model.out.kernel.grad.cpu().numpy(), g["kernel"], "kernel")
+    FB.check("model_grad", model.out.bias.grad.cpu().numpy(), g["bias"], "bias")
 
 
 def _setup():

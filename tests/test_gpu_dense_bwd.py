@@ -13,31 +13,12 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import act64, dact64
 from oracle import kgcn_oracle as K
 from test_gpu_parity import close, dev, t32
 
 pytestmark = pytest.mark.gpu
 ACTS = {None: 0, "sigmoid": 1, "relu": 2, "tanh": 3}
-
-
-def _act64(v, act):
-    if act == "sigmoid":
-        return 1.0 / (1.0 + np.exp(-v))
-    if act == "relu":
-        return np.maximum(v, 0)
-    if act == "tanh":
-        return np.tanh(v)
-    return v
-
-
-def _dact64(a, act):
-    if act == "sigmoid":
-        return a * (1 - a)
-    if act == "relu":
-        return (a > 0).astype(np.float64)
-    if act == "tanh":
-        return 1 - a * a
-    return np.ones_like(a)
 
 
 def _call(x, g, a, w, act, pooled=None, n_nodes=0, ld_pad=0, want_bias=True):
@@ -83,7 +64,7 @@ def _reference(x, g, a, w, act, pooled=None, n_nodes=0):
     g64 = 0.0 if g is None else g.astype(np.float64)
     if pooled is not None:
         g64 = g64 + np.repeat(pooled.astype(np.float64), n_nodes, axis=0)
-    dpre = g64 * (_dact64(a.astype(np.float64), act) if act else 1.0)
+    dpre = g64 * (dact64(a.astype(np.float64), act) if act else 1.0)
     x64, w64 = x.astype(np.float64), w.astype(np.float64)
     return dpre, dpre @ w64.T, x64.T @ dpre, dpre.sum(0)
 
@@ -108,7 +89,7 @@ def _layer(rng, m, din, dout, act):
     g = rng.standard_normal((m, dout)).astype(np.float32)
     w = K.glorot_uniform(rng, din, dout)
     b = (rng.standard_normal(dout) * 0.1).astype(np.float32)
-    a = _act64(x.astype(np.float64) @ w.astype(np.float64) + b, act).astype(np.float32) if act else None
+    a = act64(x.astype(np.float64) @ w.astype(np.float64) + b, act).astype(np.float32) if act else None
     return x, g, a, w
 
 

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_helpers import act64, dact64
 from oracle import kgcn_oracle as K
 from test_gpu_parity import _row_close, close, dev, t32
 
@@ -24,26 +25,6 @@ pytestmark = pytest.mark.gpu
 SHAPES = [(4100, 256, 256), (300, 256, 256), (4101, 81, 256), (4100, 256, 50), (1500, 300, 256), (4100, 512, 96),
           (16500, 256, 256), (16450, 84, 256), (16390, 128, 192)]
 ACTS = {None: 0, "sigmoid": 1, "relu": 2, "tanh": 3}
-
-
-def _act64(v, act):
-    if act == "sigmoid":
-        return 1.0 / (1.0 + np.exp(-v))
-    if act == "relu":
-        return np.maximum(v, 0)
-    if act == "tanh":
-        return np.tanh(v)
-    return v
-
-
-def _dact64(a, act):
-    if act == "sigmoid":
-        return a * (1 - a)
-    if act == "relu":
-        return (a > 0).astype(np.float64)
-    if act == "tanh":
-        return 1 - a * a
-    return np.ones_like(a)
 
 
 def _inputs(case, M, din, dout, seed):
@@ -109,11 +90,11 @@ def test_dense_dx_dact_all_routes(act, M, din, dout):
     y = ops.dense(tx, tw, tb, activation=act)
     y.backward(t32(g))
     x64, w64 = x.astype(np.float64), w.astype(np.float64)
-    a = _act64(x64 @ w64 + b, act)
+    a = act64(x64 @ w64 + b, act)
     if act == "relu":                   # the mask comes from the GPU activations (a pre-activation of 1e-9 may flip its sign)
         dpre = g.astype(np.float64) * (y.detach().cpu().numpy() > 0)
     else:
-        dpre = g.astype(np.float64) * _dact64(a, act)
+        dpre = g.astype(np.float64) * dact64(a, act)
     close(y, a, atol=1e-6, rel=1e-6, what="act(dense) fwd")
     close(tx.grad, dpre @ w64.T, atol=0, rel=3e-6, what="dX with d activation")
     close(tw.grad, x64.T @ dpre, atol=0, rel=3e-6, what="dW from the stored d pre-activation")
@@ -146,8 +127,8 @@ def test_dense_wgrad_with_fused_activation_derivative(act, M, din, dout):
         finally:
             ops.wgrad_dact_fusion = True
     yo = res[True][0]
-    a = _act64(x.astype(np.float64) @ w.astype(np.float64) + b, act)
-    dpre = g.astype(np.float64) * ((yo > 0) if act == "relu" else _dact64(a, act))
+    a = act64(x.astype(np.float64) @ w.astype(np.float64) + b, act)
+    dpre = g.astype(np.float64) * ((yo > 0) if act == "relu" else dact64(a, act))
     close(res[True][1], x.astype(np.float64).T @ dpre, atol=0, rel=3e-6, what="dW, d activation inside the weight-gradient GEMM")
     close(res[True][2], dpre.sum(0), atol=0, rel=3e-6, what="dbias, d activation inside the weight-gradient GEMM")
     close(res[True][1], res[False][1], atol=0, rel=3e-6, what="fused vs unfused dW")

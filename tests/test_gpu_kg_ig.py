@@ -8,7 +8,6 @@ and the test asserts on the CPU that each is exactly 0 or at least 2^-12 away fr
 Bound: 1e-5 of max|oracle| per output array, ratcheted to ten times the error measured on the MI355X
 (tests/golden/kg_ig_bounds.json; never below one fp32 ulp, 2^-23: the outputs are fp32).  KGCN_KG_IG_RECORD=<file> writes the
 errors of a run."""
-import json
 import os
 import sys
 
@@ -18,6 +17,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import family_bounds  # noqa: E402
 import kg_ig_oracle as O  # noqa: E402
 import linkpred_oracle as LO  # noqa: E402
 
@@ -25,37 +25,10 @@ pytestmark = pytest.mark.gpu
 
 N, DE, C = 70, 16, 128
 TOL = 1e-5
-ULP = 2.0 ** -23
-BOUNDS_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kg_ig_bounds.json")
-MEASURED = {}
+FB = family_bounds.FAMILIES["kg_ig"]          # FB.check: max|got - ref| / max|oracle|, held to min(1e-5, max(2^-23, stored))
 
 # label rows (i, r, j, i', r', j'): a == b, the hub (node 0) as a seed, the hub on both sides, node 21 on both sides
 LABELS = np.array([[5, 0, 9, 5, 0, 30], [3, 0, 3, 3, 0, 40], [7, 0, 0, 30, 0, 0], [20, 0, 21, 21, 0, 40], [1, 0, 14, 20, 0, 16]], np.int64)
-
-
-def _bounds():
-    if not os.path.exists(BOUNDS_PATH):
-        return {}
-    return json.load(open(BOUNDS_PATH)).get("bounds", {})
-
-
-def _check(key, got, ref):
-    """max|got - ref| / max|ref| printed, recorded, and held to min(1e-5, the ratcheted bound)."""
-    ref = np.asarray(ref, np.float64)
-    err = float(np.abs(np.asarray(got, np.float64) - ref).max() / np.abs(ref).max())
-    MEASURED[key] = max(MEASURED.get(key, 0.0), err)
-    bound = min(TOL, _bounds().get(key, TOL))
-    print("kg_ig %-40s err / max|oracle| = %.3e  (bound %.3e)" % (key, err, bound))
-    assert err <= bound, (key, err, bound)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _record():
-    yield
-    path = os.environ.get("KGCN_KG_IG_RECORD")
-    if path:
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        json.dump({"measured": MEASURED}, open(path, "w"), indent=1, sort_keys=True)
 
 
 @pytest.fixture(scope="module")
@@ -153,14 +126,14 @@ def test_parity_on_the_dyadic_grid(graph, grid, mode, K, T):
     assert np.array_equal(st["h2"].cpu().numpy().astype(np.float64), ost["H2"])           # the stash is exact on the grid
     tag = "%s K=%d T=%d " % (mode, K, T)
     assert np.abs(ref["node_ig"]).max() > 0 and np.abs(ref["u"]).max() > 0
-    _check(tag + "score", score.cpu().numpy(), ref["score"])
-    _check(tag + "u", u.cpu().numpy(), ref["u"])
-    _check(tag + "node_ig", node_ig.cpu().numpy(), ref["node_ig"])
+    FB.check(tag + "score", score.cpu().numpy(), ref["score"])
+    FB.check(tag + "u", u.cpu().numpy(), ref["u"])
+    FB.check(tag + "node_ig", node_ig.cpu().numpy(), ref["node_ig"])
     csr = adj.channels[0]
     w1t = st["w1"].t().contiguous()
     n_full = min(T, 5)
     full = torch.stack([ops.dense(ops.bspmm(csr.transpose(), u[t]), w1t) * st["E"] for t in range(n_full)])
-    _check(tag + "ig", full.cpu().numpy(), ref["ig"][:n_full])
+    FB.check(tag + "ig", full.cpu().numpy(), ref["ig"][:n_full])
 
 
 @pytest.mark.parametrize("kind", ["edge_score", "edge_loss"])
@@ -172,11 +145,11 @@ def test_public_function_matches_the_reference_loop(graph, grid, kind):
     _, ref = _oracle(params, graph[2], tg, mode, 8)
     out = V.linkpred_integrated_gradients(model, adj, LABELS, kind, divide_number=8, reduce=None)
     assert [r["target"] for r in out] == [0, 1, 2, 3, 4] and [r["vis_nodes"] for r in out] == LABELS[:, [0, 2]].tolist()
-    _check(kind + " public ig", np.stack([r["ig"] for r in out]), ref["ig"])
-    _check(kind + " public node_ig", np.stack([r["node_ig"] for r in out]), ref["node_ig"])
+    FB.check(kind + " public ig", np.stack([r["ig"] for r in out]), ref["ig"])
+    FB.check(kind + " public node_ig", np.stack([r["node_ig"] for r in out]), ref["node_ig"])
     m = O.LOSS if mode == "loss" else O.SCORE
     ends = np.array([[O.score_at(params, graph[2], t, m, 0.0), O.score_at(params, graph[2], t, m, 1.0)] for t in tg])
-    _check(kind + " public start/end", np.array([[r["start_score"], r["end_score"]] for r in out]), ends)
+    FB.check(kind + " public start/end", np.array([[r["start_score"], r["end_score"]] for r in out]), ends)
     one = V.linkpred_integrated_gradients(model, adj, LABELS, kind, target=3, divide_number=8)
     assert len(one) == 1 and np.array_equal(one[0]["node_ig"], out[3]["node_ig"]) and "ig" not in one[0]
 
@@ -215,11 +188,9 @@ def test_completeness_with_the_reference_scales(graph, rand, kind):
         scale = np.abs(ref["node_ig"]).sum() + abs(want)
         key = "%s completeness excess / scale" % kind
         excess = max(0.0, gpu_gap - oracle_gap) / scale
-        MEASURED[key] = max(MEASURED.get(key, 0.0), excess)
-        margin = max(TOL, _bounds().get(key, 0.0))
-        print("kg_ig %s target %d: gap gpu %.3e oracle %.3e of %.3e (excess / scale %.2e, margin %.2e)"
-              % (kind, rec["target"], gpu_gap, oracle_gap, abs(want), excess, margin))
-        assert excess <= margin
+        margin = max(TOL, FB.stored(key) or 0.0)               # (a recording run without an entry: TOL)
+        print("kg_ig %s target %d: gap gpu %.3e oracle %.3e of %.3e" % (kind, rec["target"], gpu_gap, oracle_gap, abs(want)))
+        FB.hold(key, excess, "target %d" % rec["target"], bound=margin)
 
 
 def test_node_type_picks_the_argmax_of_predict(grid):

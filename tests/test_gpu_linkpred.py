@@ -11,6 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, ROOT)
 import linkpred_oracle as O  # noqa: E402
+from gpu_helpers import to_device as _t, to_f64 as _np  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -20,18 +21,8 @@ GOLDEN = os.path.join(ROOT, "tests", "golden", "g8_kg_linkpred.npz")
 LR = {"gcn": 0.001, "distmult": 0.01, "ip": 0.001}
 
 
-def _t(a):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(a, np.float32), device="cuda")
-
-
 def _i(a):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(a, np.int32), device="cuda")
-
-
-def _np(t):
-    return t.detach().cpu().numpy().astype(np.float64)
+    return _t(a, np.int32)
 
 
 def err(a, ref):

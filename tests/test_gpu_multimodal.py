@@ -12,6 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, ROOT)
 import multimodal_oracle as M  # noqa: E402
+from family_bounds import rel_err  # noqa: E402
+from gpu_helpers import to_device as _t, to_f64 as _np  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -20,20 +22,6 @@ pytestmark = pytest.mark.gpu
 # bias); the long sequences need no wider bound
 TOL = 1e-5
 GOLDEN = os.path.join(ROOT, "tests", "golden", "g7_sample_multimodal.npz")
-
-
-def _t(a, dev="cuda"):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(a, np.float32), device=dev)
-
-
-def _np(t):
-    return t.detach().cpu().numpy().astype(np.float64)
-
-
-def rel(a, ref):
-    ref = np.asarray(ref, np.float64)
-    return float(np.abs(np.asarray(a, np.float64) - ref).max(initial=0.0) / max(1e-30, np.abs(ref).max(initial=0.0)))
 
 
 def _report(tag, errs, tol):
@@ -99,11 +87,11 @@ def test_encoder_forward_backward_against_oracle(B, L, E, kind, act):
     dtab, dw, db = M.conv_pool_bwd(tok, p["table"], p["w"], p["b"], 4, gp)
     ref_h, cache = M.lstm_fwd(_np(pooled), p["wx"], p["wh"], p["bias"], act)
     dx, dwx, dwh, dbias = M.lstm_bwd(cache, gh)
-    errs = {"pooled": rel(_np(pooled), ref_pooled) if T else 0.0, "h": rel(_np(h), ref_h)}
+    errs = {"pooled": rel_err(_np(pooled), ref_pooled) if T else 0.0, "h": rel_err(_np(h), ref_h)}
     if T:
-        errs.update({"d_table": rel(_np(tp["table"].grad), dtab), "d_w": rel(_np(tp["w"].grad), dw), "d_b": rel(_np(tp["b"].grad), db),
-                     "dx": rel(_np(x.grad), dx), "d_wx": rel(_np(tp["wx"].grad), dwx), "d_wh": rel(_np(tp["wh"].grad), dwh),
-                     "d_bias": rel(_np(tp["bias"].grad), dbias)})
+        errs.update({"d_table": rel_err(_np(tp["table"].grad), dtab), "d_w": rel_err(_np(tp["w"].grad), dw), "d_b": rel_err(_np(tp["b"].grad), db),
+                     "dx": rel_err(_np(x.grad), dx), "d_wx": rel_err(_np(tp["wx"].grad), dwx), "d_wh": rel_err(_np(tp["wh"].grad), dwh),
+                     "d_bias": rel_err(_np(tp["bias"].grad), dbias)})
     else:
         assert tuple(pooled.shape) == (B, 0, 50)
         assert not np.any(_np(h)) and not np.any(_np(tp["table"].grad)) and not np.any(_np(tp["wx"].grad))
@@ -124,7 +112,7 @@ def test_no_grad_writes_only_the_final_h():
     assert h.data_ptr() == buf.data_ptr() + 20
     b = _np(buf)
     assert np.all(b[:, :5] == 7.0) and np.all(b[:, 37:] == 7.0)
-    _report("no_grad h into columns 5..36", {"h": rel(b[:, 5:37], ref)}, TOL)
+    _report("no_grad h into columns 5..36", {"h": rel_err(b[:, 5:37], ref)}, TOL)
 
 
 def test_sigmoid_lstm_matches_torch_nn_lstm():
@@ -144,7 +132,7 @@ def test_sigmoid_lstm_matches_torch_nn_lstm():
         lstm.bias_hh_l0.zero_()
         _, (hn, _) = lstm(_t(x).flip(1))
         ours = ops.seq_lstm(_t(x), _t(p["wx"]), _t(p["wh"]), _t(p["bias"]), "sigmoid")
-    _report("sigmoid LSTM vs torch.nn.LSTM", {"h": rel(_np(ours), _np(hn[0]))}, TOL)
+    _report("sigmoid LSTM vs torch.nn.LSTM", {"h": rel_err(_np(ours), _np(hn[0]))}, TOL)
 
 
 def _sample_batch(dev="cuda"):
@@ -198,12 +186,12 @@ def _check_model(model, features, adj, tok, labels, mask, adjs_np, tag, act="har
     p, grads = _model_params_np(model)
     rl, rc, rs, cache = M.model_fwd(p, _np(features), adjs_np, tok.cpu().numpy(), _np(labels), _np(mask), act)
     rg = M.model_bwd(p, cache)
-    errs = {"logits": rel(_np(logits), rl), "cost_opt": rel(float(cost_opt.detach()), rc), "cost_sum": rel(float(cost_sum.detach()), rs)}
+    errs = {"logits": rel_err(_np(logits), rl), "cost_opt": rel_err(float(cost_opt.detach()), rc), "cost_sum": rel_err(float(cost_sum.detach()), rs)}
     for k in M.PARAM_NAMES:
         if isinstance(rg[k], list):
-            errs["d_" + k] = max(rel(a, b) for a, b in zip(grads[k], rg[k]))
+            errs["d_" + k] = max(rel_err(a, b) for a, b in zip(grads[k], rg[k]))
         else:
-            errs["d_" + k] = rel(grads[k], rg[k])
+            errs["d_" + k] = rel_err(grads[k], rg[k])
     _report(tag, errs, TOL)
 
 

@@ -11,34 +11,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, ROOT)
 import multimodal_ig_oracle as IG  # noqa: E402
+from family_bounds import rel_err  # noqa: E402
+from gpu_helpers import conv_case, g7_case, multimodal_params, oracle_inputs, to_device as _t, to_f64 as _np  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-5
-GOLDEN = os.path.join(ROOT, "tests", "golden", "g7_sample_multimodal.npz")
-
-
-def _t(a):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(a, np.float32), device="cuda")
-
-
-def _np(t):
-    return t.detach().cpu().numpy().astype(np.float64)
-
-
-def rel(a, ref):
-    ref = np.asarray(ref, np.float64)
-    return float(np.abs(np.asarray(a, np.float64) - ref).max(initial=0.0) / max(1e-30, np.abs(ref).max(initial=0.0)))
-
-
-def _conv_case(rng, C, L, E, k, p, S=7, F=50):
-    import torch
-    tok = rng.integers(0, S, size=(C, L)).astype(np.int32)
-    table = rng.uniform(-1, 1, (S, E)).astype(np.float32)
-    w = (rng.standard_normal((k, E, F)) / np.sqrt(k * E)).astype(np.float32)
-    b = (rng.standard_normal(F) * 0.3).astype(np.float32)
-    return torch.as_tensor(tok, device="cuda"), table, w, b, tok
 
 
 @pytest.mark.parametrize("L,k,p", [(37, 4, 4), (70, 3, 3), (129, 4, 2)])
@@ -47,12 +25,12 @@ def test_scaled_forward_matches_oracle(L, k, p):
     from kgcn_amd import ops
     rng = np.random.default_rng(L)
     C, rep, E = 3, 5, 6
-    ttok, table, w, b, tok = _conv_case(rng, C, L, E, k, p)
+    ttok, table, w, b, tok = conv_case(rng, C, L, E, k, p)
     scale = np.tile(np.array([0.0, 0.25, 0.5, 1.0, 0.8], np.float32), C)
     pooled, arg = ops.seq_conv_pool_scaled(ttok, _t(table), _t(w), _t(b), p, _t(scale), rep, argmax=True)
     emb = table[np.repeat(tok, rep, 0)].astype(np.float64) * scale.astype(np.float64)[:, None, None]
     ref, ref_arg, _ = IG.conv_pool_fwd_emb(emb, w, b, p)
-    err = rel(_np(pooled), ref)
+    err = rel_err(_np(pooled), ref)
     print("scaled conv-pool L=%d k=%d p=%d: pooled %.2e" % (L, k, p, err))
     assert err <= TOL
     a = arg.cpu().numpy()
@@ -69,7 +47,7 @@ def test_input_grad_kernel_matches_oracle(L, k, p):
     from kgcn_amd import ops
     rng = np.random.default_rng(100 + L + k)
     C, rep, E = 2, 4, 25
-    ttok, table, w, b, tok = _conv_case(rng, C, L, E, k, p, S=25)
+    ttok, table, w, b, tok = conv_case(rng, C, L, E, k, p, S=25)
     scale = np.tile(np.array([0.0, 0.3, 0.7, 1.0], np.float32), C)
     pooled, arg = ops.seq_conv_pool_scaled(ttok, _t(table), _t(w), _t(b), p, _t(scale), rep, argmax=True)
     assert int((arg == 0xFF).sum()) > 0                             # relu-dead outputs (the scale-0 rows at least)
@@ -80,64 +58,30 @@ def test_input_grad_kernel_matches_oracle(L, k, p):
     a = arg.cpu().numpy()
     ref = IG.conv_pool_input_grad(conv, np.where(a == 0xFF, 0, a), w, p, g * (a != 0xFF))
     per_row = ops.seq_conv_pool_input_grad(_t(g), arg, ttok.repeat_interleave(rep, 0), _t(table), _t(w), p, 1)
-    err = rel(_np(per_row), ref)
+    err = rel_err(_np(per_row), ref)
     wt = rng.uniform(0.1, 1.0, C * rep).astype(np.float32)
     wt[::rep] = 0.0
     summed = ops.seq_conv_pool_input_grad(_t(g), arg, ttok, _t(table), _t(w), p, rep, row_weight=_t(wt))
     host = (_np(per_row) * wt[:, None, None]).reshape(C, rep, L, E).sum(1)
-    err_sum = rel(_np(summed), host)
+    err_sum = rel_err(_np(summed), host)
     attr = ops.seq_conv_pool_input_grad(_t(g), arg, ttok, _t(table), _t(w), p, rep, row_weight=_t(wt), times_table=True)
-    err_attr = rel(_np(attr), _np(summed) * table[tok])
+    err_attr = rel_err(_np(attr), _np(summed) * table[tok])
     print("input gradient L=%d k=%d p=%d: per row %.2e, sum over copies %.2e, times table %.2e" % (L, k, p, err, err_sum, err_attr))
     assert err <= TOL and err_sum <= 1e-6 and err_attr <= 1e-6
     again = ops.seq_conv_pool_input_grad(_t(g), arg, ttok, _t(table), _t(w), p, rep, row_weight=_t(wt))
     assert torch.equal(summed, again)
 
 
-def _g7(E=4, seed=0):
-    import torch
-    from kgcn_amd import data_util as D, models
-    g = np.load(GOLDEN)
-    channels, _ = D.build_adjs({"dense_adj": g["dense_adj"], "max_node_num": int(g["max_node_num"])})
-    tokens, S = D.sequence_table({"sequence": g["sequence"], "sequence_symbol_num": g["sequence_symbol_num"]}, "cuda")
-    dataset = D.DeviceGraphDataset(channels, g["feature"], device="cuda")
-    torch.manual_seed(seed)
-    model = models.MultimodalGCN(S, embedding_dim=E, adj_channel_num=len(channels), label_dim=2).cuda()
-    with torch.no_grad():                              # larger embeddings than Keras' U(-0.05, 0.05): visible attributions
-        model.sequence.embeddings.uniform_(-1.0, 1.0)
-    adj, x = dataset.batch(np.arange(dataset.num_graphs))
-    model(x, adj, sequences=tokens)
-    return g, channels, dataset, tokens, model
-
-
-def _params(model):
-    return {"conv_w": [_np(w) for w in model.conv.w], "conv_b": [_np(b).reshape(-1) for b in model.conv.bias],
-            "dense_w": _np(model.dense.kernel), "dense_b": _np(model.dense.bias), "conv_kernel": _np(model.sequence.conv_kernel),
-            "conv_bias": _np(model.sequence.conv_bias), "kernel": _np(model.sequence.kernel),
-            "recurrent_kernel": _np(model.sequence.recurrent_kernel), "bias": _np(model.sequence.bias),
-            "hidden_w": _np(model.hidden.kernel), "hidden_b": _np(model.hidden.bias), "out_w": _np(model.out.kernel),
-            "out_b": _np(model.out.bias)}
-
-
-def _oracle_inputs(channels, features, tokens, table, b, N):
-    adjs = [[]]
-    for c in channels:
-        sel = c.graph == b
-        adjs[0].append((np.stack([c.row[sel], c.col[sel]], 1), c.val[sel].astype(np.float64), [N, N]))
-    A, Sm = IG.dense_adjs(adjs, N)
-    return np.asarray(features[b], np.float64), A[0], Sm[0], table[tokens[b]]
-
-
 def _compare(res, p, channels, features, tok_np, table, N, D, modal, method, tag):
     worst = {}
     for r in res:
         cid = r["compound_id"]
-        x, A, Sm, emb = _oracle_inputs(channels, features, tok_np, table, cid, N)
+        x, A, Sm, emb = oracle_inputs(channels, features, tok_np, table, cid, N)
         mask = np.zeros(2)
         mask[r["target_label"]] = 1.0
         ref = IG.integrated_gradients(p, x, A, Sm, emb, mask, D, modal, method)
         for m in ((IG.MODALS) if modal == "all" else (modal,)):
-            worst[m] = max(worst.get(m, 0.0), rel(r[m + "_IG"], ref[m + "_IG"]))
+            worst[m] = max(worst.get(m, 0.0), rel_err(r[m + "_IG"], ref[m + "_IG"]))
         worst["check_score"] = max(worst.get("check_score", 0.0), abs(r["check_score"] - ref["check_score"]))
         worst["sum_of_IG"] = max(worst.get("sum_of_IG", 0.0), abs(r["sum_of_IG"] - ref["sum_of_IG"]))
         assert np.allclose(r["embedded_layer"] if "embedded_layer" in r else emb, emb, atol=0)
@@ -149,7 +93,7 @@ def _compare(res, p, channels, features, tok_np, table, N, D, modal, method, tag
 @pytest.mark.parametrize("method", ["ig", "grad_prod", "grad"])
 def test_ig_on_g7_matches_oracle(modal, method):
     from kgcn_amd import visualization as V
-    g, channels, dataset, tokens, model = _g7()
+    g, channels, dataset, tokens, model = g7_case()
     D = 100
     res = V.multimodal_integrated_gradients(model, None, dataset, tokens, labels=g["label"], divide_number=D, modal=modal,
                                             method=method, sequence_symbol=g["sequence"])
@@ -161,7 +105,7 @@ def test_ig_on_g7_matches_oracle(modal, method):
         assert r0["adjs"].shape == r0["adjs_IG"].shape == (3, 3)
     if "embedded_layer" in keys:
         assert r0["embedded_layer_IG"].shape == (5, 4)
-    worst = _compare(res, _params(model), channels, g["feature"], g["sequence"], _np(model.sequence.embeddings), 3, D, modal,
+    worst = _compare(res, multimodal_params(model), channels, g["feature"], g["sequence"], _np(model.sequence.embeddings), 3, D, modal,
                      method, "g7 %s %s" % (modal, method))
     assert max(worst.values()) <= TOL
 
@@ -188,7 +132,7 @@ def test_ig_at_cpi_shape_matches_oracle():
         model.out.kernel.mul_(0.02)
     res = V.multimodal_integrated_gradients(model, None, dataset, ttok, divide_number=Dn, chunk=3)
     assert min(abs(r["check_score"]) for r in res) > 1e-4          # an unsaturated prediction: the attribution is not all zero
-    worst = _compare(res, _params(model), channels, x, tok, _np(model.sequence.embeddings), N, Dn, "all", "ig",
+    worst = _compare(res, multimodal_params(model), channels, x, tok, _np(model.sequence.embeddings), N, Dn, "all", "ig",
                      "CPI shape, C = 8, N = 50, L = 700, E = 25, D = 100")
     assert max(worst.values()) <= TOL
 
@@ -196,7 +140,7 @@ def test_ig_at_cpi_shape_matches_oracle():
 def test_batched_matches_the_step_loop_and_is_deterministic():
     import torch
     from kgcn_amd import visualization as V
-    g, channels, dataset, tokens, model = _g7()
+    g, channels, dataset, tokens, model = g7_case()
     kw = dict(labels=g["label"], divide_number=10, modal="all", method="ig")
     a = V.multimodal_integrated_gradients(model, None, dataset, tokens, **kw)
     b = V.multimodal_integrated_gradients(model, None, dataset, tokens, batched=False, **kw)
@@ -204,7 +148,7 @@ def test_batched_matches_the_step_loop_and_is_deterministic():
     worst = 0.0
     for ra, rb, rc in zip(a, b, c):
         for m in IG.MODALS:
-            worst = max(worst, rel(ra[m + "_IG"], rb[m + "_IG"]))
+            worst = max(worst, rel_err(ra[m + "_IG"], rb[m + "_IG"]))
             assert np.array_equal(ra[m + "_IG"], rc[m + "_IG"])      # chunking does not change a compound's rows
         worst = max(worst, abs(ra["sum_of_IG"] - rb["sum_of_IG"]) / max(1e-30, abs(rb["sum_of_IG"])))
         assert ra["check_score"] == rc["check_score"]
@@ -219,7 +163,7 @@ def test_batched_matches_the_step_loop_and_is_deterministic():
 
 def test_default_path_and_scale_one_are_bit_identical():
     import torch
-    g, channels, dataset, tokens, model = _g7()
+    g, channels, dataset, tokens, model = g7_case()
     adj, x = dataset.batch(np.arange(5))
     with torch.no_grad():
         a = model(x, adj, sequences=tokens)

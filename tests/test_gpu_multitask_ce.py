@@ -1,7 +1,6 @@
 """ops.multitask_softmax2_ce (csrc/cvloss.hip) against tests/cv_oracle.softmax2_ce in fp64: costs, predictions and the gradient
 within the bounds of tests/golden/cv_bounds.json (ten times the error measured on the MI355X against the oracle, relative to
-max(1, max |ref|) per tensor), counts exact, and the device accumulator."""
-import json
+max(1, max |ref|) per tensor; KGCN_CV_RECORD=<file> writes the errors of a run), counts exact, and the device accumulator."""
 import os
 import sys
 
@@ -11,21 +10,11 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import cv_oracle as O  # noqa: E402
+import family_bounds  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-BOUNDS = json.load(open(os.path.join(ROOT, "tests", "golden", "cv_bounds.json")))["bounds"]
-
-
-def nerr(got, ref):
-    ref = np.asarray(ref, np.float64)
-    return float(np.abs(np.asarray(got, np.float64) - ref).max()) / max(1.0, float(np.abs(ref).max()))
-
-
-def held(what, got, ref):
-    e = nerr(got, ref)
-    print("%-16s err / max(1, |ref|) = %.3e (bound %.3e)" % (what, e, BOUNDS[what]))
-    assert e <= BOUNDS[what], (what, e, BOUNDS[what])
+FB = family_bounds.FAMILIES["cv"]               # FB.check: max|got - ref| / max(1, max|ref|), held to the stored bound
 
 
 def run(logits, labels, mask, accum=None, backward=True):
@@ -48,10 +37,10 @@ def compare(logits, labels, mask):
     ref = O.softmax2_ce(logits, labels, mask)
     np.testing.assert_array_equal(got["each_correct"], ref["each_correct"].astype(np.float32))
     np.testing.assert_array_equal(got["each_count"], ref["each_count"].astype(np.float32))
-    held("loss_cost", got["cost"], ref["cost"])
-    held("loss_each_cost", got["each_cost"], ref["each_cost"])
-    held("loss_prediction", got["prediction"], ref["prediction"])
-    held("loss_dlogits", got["dlogits"], ref["dlogits"])
+    FB.check("loss_cost", got["cost"], ref["cost"])
+    FB.check("loss_each_cost", got["each_cost"], ref["each_cost"])
+    FB.check("loss_prediction", got["prediction"], ref["prediction"])
+    FB.check("loss_dlogits", got["dlogits"], ref["dlogits"])
     assert np.isfinite(got["dlogits"]).all() and np.isfinite(got["each_cost"]).all()
     return got, ref
 
@@ -116,7 +105,7 @@ def test_zero_padded_tail_rows():
     np.testing.assert_array_equal(got["each_count"], head["each_count"])
     np.testing.assert_array_equal(got["each_correct"], head["each_correct"])
     assert not got["dlogits"][37:].any()
-    held("loss_each_cost", got["each_cost"], head["each_cost"].astype(np.float64))
+    FB.check("loss_each_cost", got["each_cost"], head["each_cost"].astype(np.float64))
 
 
 def test_flat_logits_are_the_same_call():

@@ -13,15 +13,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, ROOT)
 import predscore_oracle as O  # noqa: E402
+from gpu_helpers import to_device as _t  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(ROOT, "tests", "golden", "g10_predscore.npz")
-
-
-def _t(a):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(a, np.float32), device="cuda")
 
 
 def _bits(t):

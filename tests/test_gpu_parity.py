@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from conftest import load_golden, unflatten_adjs
+from gpu_helpers import act64, dact64
 from oracle import kgcn_oracle as K
 
 pytestmark = pytest.mark.gpu
@@ -188,20 +189,6 @@ def test_op_wrappers_api():
         close(r[b].grad, rg[b], what="d rhs[%d]" % b)
 
 
-def _np_act(v, name):
-    if name == "sigmoid":
-        return 1.0 / (1.0 + np.exp(-v))
-    if name == "relu":
-        return np.maximum(v, 0)
-    if name == "tanh":
-        return np.tanh(v)
-    return v
-
-
-def _np_dact(a, name):
-    return {"sigmoid": a * (1 - a), "relu": (a > 0).astype(np.float64), "tanh": 1 - a * a}.get(name, np.ones_like(a))
-
-
 @pytest.mark.parametrize("act", ["sigmoid", "relu", "tanh"])
 @pytest.mark.parametrize("N,D,channels", [(10, 16, "split"), (10, 50, "split"), (50, 256, "one"), (10, 64, "norm")])
 def test_fused_activation_aggregation(act, N, D, channels):
@@ -224,13 +211,13 @@ def test_fused_activation_aggregation(act, N, D, channels):
     tr = t32(cat).requires_grad_(True)
     out = ops.bconv(adj, tr, D, activation=act)
     pre = np.stack(K.bconv(adjs, rhs))
-    ref = _np_act(pre, act)
+    ref = act64(pre, act)
     close(out.reshape(B, N, D), ref, rel=1e-6, what="act(bconv) " + act)
     out.backward(t32(g).reshape(B * N, D))
     # relu': read from the kernel's own output, like tf.nn.relu's gradient (a pre-activation within one rounding of 0 may
     # land on either side in fp32)
     aout = out.detach().cpu().numpy().reshape(np.shape(ref)).astype(np.float64) if act == "relu" else ref
-    _, rg = K.bconv_grad(adjs, rhs, list(g * _np_dact(aout, act)))
+    _, rg = K.bconv_grad(adjs, rhs, list(g * dact64(aout, act)))
     want = np.stack([np.concatenate(r, 1) for r in rg]).reshape(B * N, C * D)
     close(tr.grad, want, rel=1e-6, what="d rhs through act(bconv) " + act)
 
@@ -251,19 +238,19 @@ def test_fused_activation_dense(act, M, din, dout):
     tx, tw, tb = t32(x).requires_grad_(True), t32(w).requires_grad_(True), t32(b).requires_grad_(True)
     y = ops.dense(tx, tw, tb, activation=act)
     x64, w64 = x.astype(np.float64), w.astype(np.float64)
-    ref = _np_act(x64 @ w64 + b, act)
+    ref = act64(x64 @ w64 + b, act)
     close(y, ref, rel=2e-6, what="act(dense) " + act)
     y.backward(t32(g))
-    gz = g * _np_dact(y.detach().cpu().numpy().astype(np.float64) if act == "relu" else ref, act)
+    gz = g * dact64(y.detach().cpu().numpy().astype(np.float64) if act == "relu" else ref, act)
     close(tx.grad, gz @ w64.T, rel=2e-6, what="dx")
     close(tw.grad, x64.T @ gz, rel=1e-5, what="dw")
     close(tb.grad, gz.sum(0), rel=1e-5, what="db")
     # the stand-alone activation op
     tz = t32(x).requires_grad_(True)
     a = ops.activation(tz, act)
-    close(a, _np_act(x64, act), rel=1e-6)
+    close(a, act64(x64, act), rel=1e-6)
     a.backward(t32(x))
-    close(tz.grad, x64 * _np_dact(_np_act(x64, act), act), rel=1e-6)
+    close(tz.grad, x64 * dact64(act64(x64, act), act), rel=1e-6)
 
 
 def test_dense_entry_points_with_padded_leading_dimensions():
@@ -774,10 +761,10 @@ def test_graph_batch_normalization_fused_activation(act, phase):
     y = layer(tx, enabled_node_nums=torch.from_numpy(en).to(dev()))
     y.backward(t32(g))
     pre, mean, var, _, _ = K.graph_bn_fwd(x, gamma, beta, mm, mv, en, training=bool(phase))
-    ref = _np_act(pre, act)
+    ref = act64(pre, act)
     close(y, ref, rel=2e-6, what="act(bn) " + act)
     aout = y.detach().cpu().numpy().astype(np.float64) if act == "relu" else ref
-    dx, dgamma, dbeta = K.graph_bn_bwd(x, gamma, mean, var, g * _np_dact(aout, act), en, training=bool(phase))
+    dx, dgamma, dbeta = K.graph_bn_bwd(x, gamma, mean, var, g * dact64(aout, act), en, training=bool(phase))
     close(tx.grad, dx, rel=1e-5, what="dx")
     close(layer.gamma.grad, dgamma, rel=1e-5, atol=1e-4, what="dgamma")
     close(layer.beta.grad, dbeta, rel=1e-5, atol=1e-4, what="dbeta")

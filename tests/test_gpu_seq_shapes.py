@@ -107,6 +107,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, ROOT)
 import multimodal_ig_oracle as IG  # noqa: E402
 import multimodal_oracle as M  # noqa: E402
+from gpu_helpers import to_device as _t, to_f64 as _np  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -121,15 +122,6 @@ LONG_RUN = 512              # LSTM steps up to which TOL was measured
 K_TILE, K_IG_POS = 16, 32   # kTile, kIgPos of seq.hip
 GUARD = 256                 # sentinel elements on either side of a guarded buffer
 SENTINEL = 1.2345e30
-
-
-def _t(a, dev="cuda"):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(a, np.float32), device=dev)
-
-
-def _np(t):
-    return t.detach().cpu().numpy().astype(np.float64)
 
 
 def _lds_limit():

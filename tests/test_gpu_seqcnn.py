@@ -13,7 +13,6 @@ kernel's tanh is good to a few ulp, about 2.4e-7): where every output of the lay
 here, the whole gradient below it carries the relative error 2 |y| d / (1 - y^2), which at |y| = 0.999 is 2.4e-4 -- a property of
 the fp32 output, not of the kernels.  So a case must also keep the tanh layer in its working range: max |y| <= TANH_MAX = 0.975,
 where 2 |y| 2.4e-7 / (1 - y^2) = 9.5e-6 stays below the ceiling of the bounds (1e-5).  Asserted on the oracle like the rest."""
-import json
 import os
 import sys
 
@@ -22,12 +21,13 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import family_bounds  # noqa: E402
 import seqcnn_oracle as O  # noqa: E402
-from test_gpu_conv1d import nerr, well_conditioned  # noqa: E402
+from test_gpu_conv1d import well_conditioned  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-BOUNDS = json.load(open(os.path.join(ROOT, "tests", "golden", "seqcnn_bounds.json")))["bounds"]
+FB = family_bounds.FAMILIES["seqcnn"]           # as in test_gpu_conv1d.py
 S, E, L = 26, 25, 50
 CLASS_WEIGHT = np.array([1.25, 5.0])
 TANH_MAX = 0.975
@@ -35,8 +35,8 @@ TANH_MAX = 0.975
 
 def conditioned(c):
     """The preconditions of the module docstring on a model_fwd cache."""
-    ok = all(well_conditioned(cc, BOUNDS["forward"])[0] for cc in c["convs"])
-    ok = ok and float(np.abs(c["n2"]).min()) > BOUNDS["forward"] * float(np.abs(c["n2"]).max())
+    ok = all(well_conditioned(cc, FB.bound("forward"))[0] for cc in c["convs"])
+    ok = ok and float(np.abs(c["n2"]).min()) > FB.bound("forward") * float(np.abs(c["n2"]).max())
     return ok and float(np.abs(c["s"]).max()) <= TANH_MAX
 
 
@@ -101,20 +101,16 @@ def test_model_against_the_oracle(B, embedded):
     with ops.deferred_reductions(root=root):
         root.backward()
     torch.cuda.synchronize()
-    figs = [("model_logits", nerr(logits.detach().cpu().numpy(), c["logits"])),
-            ("model_loss", max(abs(float(cost_opt) - c["cost_opt"]) / abs(c["cost_opt"]), abs(float(cost_sum) - c["cost_sum"]) / abs(c["cost_sum"])))]
+    FB.check("model_logits", logits.detach().cpu().numpy(), c["logits"])
+    FB.hold("model_loss", max(abs(float(cost_opt) - c["cost_opt"]) / abs(c["cost_opt"]), abs(float(cost_sum) - c["cost_sum"]) / abs(c["cost_sum"])),
+            figure="|ref|, the larger of cost_opt and cost_sum")
     for k, q in names.items():
         if k == "embeddings" and embedded:
             assert q.grad is None
             continue
-        figs.append(("model_grad", nerr(q.grad.cpu().numpy().reshape(ref[k].shape), ref[k])))
-        print("SEQCNN_ERR model_grad[%s] %.3e" % (k, figs[-1][1]))
+        FB.check("model_grad", q.grad.cpu().numpy().reshape(ref[k].shape), ref[k], k)
     if embedded:
-        figs.append(("model_d_embedded", nerr(temb.grad.cpu().numpy(), ref["d_embedded"])))
-    for name, e in figs:
-        print("SEQCNN_ERR %s %.3e (bound %.3e)" % (name, e, BOUNDS[name]))
-    for name, e in figs:
-        assert e <= BOUNDS[name], (name, e, BOUNDS[name])
+        FB.check("model_d_embedded", temb.grad.cpu().numpy(), ref["d_embedded"])
 
 
 def _fixture_training(lr=1e-3, batch=8):

@@ -7,7 +7,6 @@ ulp of sigma |z| on top of the clean path's rounding.  Each comparison prints it
 for check_score and sum_of_IG), records it, and is held to the bound of tests/golden/smooth_ig_bounds.json = max(10 x the error
 measured on an MI355X, 2^-23), and never to more than CAP = 1e-4 (ten times the clean path's tolerance): an error beyond CAP is a
 defect, not a bound to record.  KGCN_SMOOTH_IG_RECORD=<file> writes the errors of a run."""
-import json
 import os
 import sys
 
@@ -18,59 +17,18 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, ROOT)
 import multimodal_ig_oracle as IG  # noqa: E402
+import family_bounds  # noqa: E402
 import smooth_ig_oracle as SO  # noqa: E402
+from family_bounds import rel_err  # noqa: E402
+from gpu_helpers import conv_case, g7_case, multimodal_params, oracle_inputs, to_device as _t, to_f64 as _np  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-CAP = 1e-4
-GOLDEN = os.path.join(ROOT, "tests", "golden", "g7_sample_multimodal.npz")
-BOUNDS_PATH = os.path.join(ROOT, "tests", "golden", "smooth_ig_bounds.json")
-MEASURED = {}
+# FB.check: max|got - ref| / max(1e-30, max|oracle|) (absolute=True: max|got - ref|) under `key`, held to min(CAP, max(2^-23, stored)),
+# CAP = 1e-4; a comparison without a stored bound is an error, except in a recording run, where CAP alone holds
+FB = family_bounds.FAMILIES["smooth_ig"]
 SEED = 1234
 NS = float(np.float32(0.1))                    # the noise scale as the device holds it
-
-
-RECORDING = bool(os.environ.get("KGCN_SMOOTH_IG_RECORD"))
-BOUNDS = json.load(open(BOUNDS_PATH))["bounds"] if os.path.exists(BOUNDS_PATH) else None
-
-
-def _check(key, got, ref, absolute=False):
-    """A comparison without a recorded bound is an error, except in a recording run, where CAP alone holds."""
-    ref = np.asarray(ref, np.float64)
-    err = float(np.abs(np.asarray(got, np.float64) - ref).max(initial=0.0))
-    if not absolute:
-        err /= max(1e-30, float(np.abs(ref).max(initial=0.0)))
-    MEASURED[key] = max(MEASURED.get(key, 0.0), err)
-    if BOUNDS is not None and key in BOUNDS:
-        bound = min(CAP, BOUNDS[key])
-    else:
-        assert RECORDING, "no bound for %r in %s" % (key, BOUNDS_PATH)
-        bound = CAP
-    print("smooth_ig %-60s err %.3e  (bound %.3e)" % (key, err, bound))
-    assert err <= bound, (key, err, bound)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _record():
-    yield
-    path = os.environ.get("KGCN_SMOOTH_IG_RECORD")
-    if path:
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        json.dump({"measured": MEASURED}, open(path, "w"), indent=1, sort_keys=True)
-
-
-def _t(a, dtype=np.float32):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(a, dtype), device="cuda")
-
-
-def _np(t):
-    return t.detach().cpu().numpy().astype(np.float64)
-
-
-def rel(a, ref):
-    ref = np.asarray(ref, np.float64)
-    return float(np.abs(np.asarray(a, np.float64) - ref).max(initial=0.0) / max(1e-30, np.abs(ref).max(initial=0.0)))
 
 
 # ---- the perturbation kernels ---------------------------------------------------------------------------------------------
@@ -94,7 +52,7 @@ def test_perturb_rows_match_the_oracle_noise(N, F):
             assert torch.equal(out[b], _t(x[c]) * float(scale[b])), b
         z = SO.noise(SEED, SO.STREAM_FEATURES, ids[c], int(sample[b]), N, F)
         ref[b] = SO.add_perturbation(x[c].astype(np.float64), float(scale[b]), z, float(sigma[b]))
-    _check("perturb rows N=%d F=%d" % (N, F), _np(out), ref)
+    FB.check("perturb rows N=%d F=%d" % (N, F), _np(out), ref)
     assert torch.equal(out, ops.ig_perturb(_t(x), _t(scale), _t(sigma), _t(sample, np.int32), ids, rep, ops.IG_STREAM_FEATURES, SEED))
     other = ops.ig_perturb(_t(x), _t(scale), _t(sigma), _t(sample, np.int32), ids, rep, ops.IG_STREAM_FEATURES, SEED + 1)
     assert not torch.equal(out, other)
@@ -130,7 +88,7 @@ def test_perturb_values_empty_single_and_duplicate_entries():
         e0, e1 = rp[b * M], rp[(b + 1) * M]
         z = SO.noise(SEED, stream, ids[b], int(sample[b]), 1, int(e1 - e0))[0]
         ref[e0:e1] = SO.add_perturbation(vals[e0:e1], float(scale[b]), z, float(sigma[b]))
-    _check("perturb values", _np(out), ref)
+    FB.check("perturb values", _np(out), ref)
     # the two stored copies of (1, 2) in graph 2 carry their own noise
     e0 = rp[2 * M]
     assert len({float(x) for x in (out[e0:e0 + 3] - v[e0:e0 + 3] * 0.25).cpu()}) == 3
@@ -141,15 +99,6 @@ def test_perturb_values_empty_single_and_duplicate_entries():
 
 
 # ---- the noisy conv-pool forward ------------------------------------------------------------------------------------------
-def _conv_case(rng, C, L, E, k, p, S=7, F=50):
-    import torch
-    tok = rng.integers(0, S, size=(C, L)).astype(np.int32)
-    table = rng.uniform(-1, 1, (S, E)).astype(np.float32)
-    w = (rng.standard_normal((k, E, F)) / np.sqrt(k * E)).astype(np.float32)
-    b = (rng.standard_normal(F) * 0.3).astype(np.float32)
-    return torch.as_tensor(tok, device="cuda"), table, w, b, tok
-
-
 @pytest.mark.parametrize("L,k,p", [(37, 4, 4), (70, 3, 3), (129, 4, 2)])
 def test_perturbed_forward_matches_oracle(L, k, p):
     import torch
@@ -157,7 +106,7 @@ def test_perturbed_forward_matches_oracle(L, k, p):
     rng = np.random.default_rng(L)
     C, rep, E = 3, 5, 6
     ids = [4, 0, 9]
-    ttok, table, w, b, tok = _conv_case(rng, C, L, E, k, p)
+    ttok, table, w, b, tok = conv_case(rng, C, L, E, k, p)
     scale = np.tile(np.array([0.0, 0.25, 0.5, 1.0, 0.8], np.float32), C)
     sigma = np.tile(np.array([0.0, 0.1, 0.0, 0.1, 0.1], np.float32), C)
     sample = np.tile(np.array([0, 0, 1, 2, 7], np.int32), C)
@@ -168,7 +117,7 @@ def test_perturbed_forward_matches_oracle(L, k, p):
         z = SO.noise(SEED, SO.STREAM_SEQUENCE, ids[r // rep], int(sample[r]), L, E)
         emb[r] = SO.add_perturbation(table[tok[r // rep]].astype(np.float64), float(scale[r]), z, float(sigma[r]))
     ref, ref_arg, _ = IG.conv_pool_fwd_emb(emb, w, b, p)
-    _check("perturbed conv-pool L=%d k=%d p=%d pooled" % (L, k, p), _np(pooled), ref)
+    FB.check("perturbed conv-pool L=%d k=%d p=%d pooled" % (L, k, p), _np(pooled), ref)
     a = arg.cpu().numpy()
     live = ref > 1e-4
     assert np.array_equal(a[live], ref_arg[live]) and np.all(a[ref == 0] == 0xFF)
@@ -187,43 +136,9 @@ def test_perturbed_forward_matches_oracle(L, k, p):
 
 
 # ---- the whole attribution ------------------------------------------------------------------------------------------------
-def _g7(E=4, seed=0):
-    import torch
-    from kgcn_amd import data_util as D, models
-    g = np.load(GOLDEN)
-    channels, _ = D.build_adjs({"dense_adj": g["dense_adj"], "max_node_num": int(g["max_node_num"])})
-    tokens, S = D.sequence_table({"sequence": g["sequence"], "sequence_symbol_num": g["sequence_symbol_num"]}, "cuda")
-    dataset = D.DeviceGraphDataset(channels, g["feature"], device="cuda")
-    torch.manual_seed(seed)
-    model = models.MultimodalGCN(S, embedding_dim=E, adj_channel_num=len(channels), label_dim=2).cuda()
-    with torch.no_grad():                              # larger embeddings than Keras' U(-0.05, 0.05): visible attributions
-        model.sequence.embeddings.uniform_(-1.0, 1.0)
-    adj, x = dataset.batch(np.arange(dataset.num_graphs))
-    model(x, adj, sequences=tokens)
-    return g, channels, dataset, tokens, model
-
-
 @pytest.fixture(scope="module")
 def g7():
-    return _g7()
-
-
-def _params(model):
-    return {"conv_w": [_np(w) for w in model.conv.w], "conv_b": [_np(b).reshape(-1) for b in model.conv.bias],
-            "dense_w": _np(model.dense.kernel), "dense_b": _np(model.dense.bias), "conv_kernel": _np(model.sequence.conv_kernel),
-            "conv_bias": _np(model.sequence.conv_bias), "kernel": _np(model.sequence.kernel),
-            "recurrent_kernel": _np(model.sequence.recurrent_kernel), "bias": _np(model.sequence.bias),
-            "hidden_w": _np(model.hidden.kernel), "hidden_b": _np(model.hidden.bias), "out_w": _np(model.out.kernel),
-            "out_b": _np(model.out.bias)}
-
-
-def _oracle_inputs(channels, features, tokens, table, b, N):
-    adjs = [[]]
-    for c in channels:
-        sel = c.graph == b
-        adjs[0].append((np.stack([c.row[sel], c.col[sel]], 1), c.val[sel].astype(np.float64), [N, N]))
-    A, Sm = IG.dense_adjs(adjs, N)
-    return np.asarray(features[b], np.float64), A[0], Sm[0], table[tokens[b]]
+    return g7_case()
 
 
 def _device_entries(dataset, cid):
@@ -241,14 +156,14 @@ def _device_entries(dataset, cid):
 def _compare(res, p, dataset, channels, features, tok_np, table, N, D, modal, method, tag):
     for r in res:
         cid = r["compound_id"]
-        x, A, Sm, emb = _oracle_inputs(channels, features, tok_np, table, cid, N)
+        x, A, Sm, emb = oracle_inputs(channels, features, tok_np, table, cid, N)
         mask = np.zeros(2)
         mask[r["target_label"]] = 1.0
         ref = SO.smooth(p, x, A, Sm, emb, mask, D, modal, method, NS, SEED, cid, entries=_device_entries(dataset, cid))
         for m in (IG.MODALS if modal == "all" else (modal,)):
-            _check("%s %s_IG" % (tag, m), r[m + "_IG"], ref[m + "_IG"])
-        _check("%s check_score" % tag, r["check_score"], ref["check_score"], absolute=True)
-        _check("%s sum_of_IG" % tag, r["sum_of_IG"], ref["sum_of_IG"], absolute=True)
+            FB.check("%s %s_IG" % (tag, m), r[m + "_IG"], ref[m + "_IG"])
+        FB.check("%s check_score" % tag, r["check_score"], ref["check_score"], absolute=True)
+        FB.check("%s sum_of_IG" % tag, r["sum_of_IG"], ref["sum_of_IG"], absolute=True)
 
 
 @pytest.mark.parametrize("modal", ["all", "features", "adjs", "embedded_layer"])
@@ -262,7 +177,7 @@ def test_smooth_on_g7_matches_oracle(g7, modal, method):
     assert len(res) == 5
     keys = set(IG.MODALS if modal == "all" else (modal,))
     assert keys | {m + "_IG" for m in keys} | set(V.DUMP_KEYS_FIXED) | {"amino_acid_seq"} <= set(V.dump_record(res[0]))
-    _compare(res, _params(model), dataset, channels, g["feature"], g["sequence"], _np(model.sequence.embeddings), 3, D, modal,
+    _compare(res, multimodal_params(model), dataset, channels, g["feature"], g["sequence"], _np(model.sequence.embeddings), 3, D, modal,
              method, "g7 %s %s" % (method, modal))
 
 
@@ -288,7 +203,7 @@ def test_smooth_ig_at_cpi_shape_matches_oracle():
         model.out.kernel.mul_(0.02)
     res = V.multimodal_integrated_gradients(model, None, dataset, ttok, divide_number=Dn, method="smooth_ig", chunk=1, seed=SEED)
     assert min(abs(r["check_score"]) for r in res) > 1e-4          # an unsaturated prediction: the attribution is not all zero
-    _compare(res, _params(model), dataset, channels, x, tok, _np(model.sequence.embeddings), N, Dn, "all", "smooth_ig",
+    _compare(res, multimodal_params(model), dataset, channels, x, tok, _np(model.sequence.embeddings), N, Dn, "all", "smooth_ig",
              "CPI shape smooth_ig all")
 
 
@@ -324,7 +239,7 @@ def test_invariants_of_the_smooth_attribution(g7):
         worst = {}
         for ra, rb in zip(a, b):
             for m in IG.MODALS:
-                worst[m] = max(worst.get(m, 0.0), rel(ra[m + "_IG"], rb[m + "_IG"]))
+                worst[m] = max(worst.get(m, 0.0), rel_err(ra[m + "_IG"], rb[m + "_IG"]))
             worst["sum_of_IG"] = max(worst.get("sum_of_IG", 0.0),
                                      abs(ra["sum_of_IG"] - rb["sum_of_IG"]) / max(1e-30, abs(rb["sum_of_IG"])))
             assert ra["check_score"] == rb["check_score"]
@@ -345,7 +260,7 @@ def test_zero_noise_is_the_clean_method(g7, smooth, clean):
     worst = 0.0
     for ra, rb in zip(a, b):
         for m in IG.MODALS:
-            worst = max(worst, rel(ra[m + "_IG"], rb[m + "_IG"]))
+            worst = max(worst, rel_err(ra[m + "_IG"], rb[m + "_IG"]))
         assert ra["check_score"] == rb["check_score"]
     print("%s at noise_scale 0 vs %s: max rel err %.2e" % (smooth, clean, worst))
     assert worst <= 1e-6
@@ -385,8 +300,8 @@ def test_generic_integrated_gradients_match_the_oracle_loop(method):
         for g in range(B):
             ig_a[g] += dvals[g][0] / D if method == "smooth_grad" else dvals[g][0] * vals[g] / D
     # the reference's COO order is row-major here, = the CSR order of the container
-    _check("generic %s features" % method, _np(res["features"]), ig_x)
-    _check("generic %s adjs" % method, _np(res["adjs"]), np.concatenate(ig_a))
+    FB.check("generic %s features" % method, _np(res["features"]), ig_x)
+    FB.check("generic %s adjs" % method, _np(res["adjs"]), np.concatenate(ig_a))
     clean = V.integrated_gradients(score_fn, _t(x), adj, divide_number=D, method="grad")
     assert res["start_score"] == clean["start_score"] and res["end_score"] == clean["end_score"]
 

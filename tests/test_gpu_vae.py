@@ -13,19 +13,11 @@ sys.path.insert(0, ROOT)
 import vae_oracle as V  # noqa: E402
 from test_vae_oracle import make_batch  # noqa: E402
 from oracle import kgcn_oracle as K  # noqa: E402
+from gpu_helpers import to_device as _t, to_f64 as _np  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-5
-
-
-def _t(a, dev="cuda"):
-    import torch
-    return torch.as_tensor(np.ascontiguousarray(a, np.float32), device=dev)
-
-
-def _np(t):
-    return t.detach().cpu().numpy().astype(np.float64)
 
 
 def rel(a, ref):

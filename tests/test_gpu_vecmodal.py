@@ -4,7 +4,8 @@ models.MultimodalVecGCN / MultimodalRegressionGCN on the batches of tests/golden
 and cv.train_cv(task="regression").
 
 Error figure: max |err| / max(1, max |ref|) per tensor.  Bounds come from tests/golden/vecmodal_bounds.json: ten times the largest
-figure measured on an MI355X against the oracle (the file records them), never below 2^-22; the measuring run used 1e-4."""
+figure measured on an MI355X against the oracle (the file records them), never below 2^-22; the measuring run used 1e-4.
+KGCN_VECMODAL_RECORD=<file> writes the errors of a run."""
 import json
 import os
 import sys
@@ -16,24 +17,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, os.path.join(ROOT, "examples"))
+import family_bounds  # noqa: E402
 import vecmodal_oracle as O  # noqa: E402
+from gpu_helpers import load_dense_bn, set_param  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-BOUNDS = json.load(open(os.path.join(ROOT, "tests", "golden", "vecmodal_bounds.json")))["bounds"]
+FB = family_bounds.FAMILIES["vecmodal"]         # FB.check: max|got - ref| / max(1, max|ref|), held to the stored bound
 Z = np.load(os.path.join(ROOT, "tests", "golden", "g12_vecmodal.npz"), allow_pickle=False)
 ACTS = (None, "relu", "tanh", "sigmoid")
-
-
-def nerr(got, ref):
-    ref = np.asarray(ref, np.float64)
-    return float(np.abs(np.asarray(got, np.float64) - ref).max()) / max(1.0, float(np.abs(ref).max()))
-
-
-def held(what, got, ref, label=""):
-    e = nerr(got, ref)
-    print("%-14s %-28s err / max(1, |ref|) = %.3e (bound %.3e)" % (what, label, e, BOUNDS[what]))
-    assert e <= BOUNDS[what], (what, label, e, BOUNDS[what])
 
 
 def dev():
@@ -86,7 +78,7 @@ def run_layer(rng, B, K, N, act, bn=True, x_grad=True, x_wide=0, out_wide=0, out
     ref_y = O.dense_bn_fwd(x, p, act)
     g = O.dense_bn_bwd(x, p, dy, act)
     tag = "%s %dx%d->%d %s%s" % (label, B, K, N, act, "" if bn else " no-bn")
-    held("layer_y", y.detach().cpu().numpy(), ref_y, tag)
+    FB.check("layer_y", y.detach().cpu().numpy(), ref_y, tag)
     got = {"w": tp["w"].grad, "b": tp["b"].grad}
     if bn:
         got.update(gamma=tp["gamma"].grad, beta=tp["beta"].grad)
@@ -96,7 +88,7 @@ def run_layer(rng, B, K, N, act, bn=True, x_grad=True, x_wide=0, out_wide=0, out
         assert tx.grad is None
     for k, v in got.items():
         assert v is not None, "no gradient for %s" % k
-        held("layer_d" + k, v.cpu().numpy(), g[k], tag)
+        FB.check("layer_d" + k, v.cpu().numpy(), g[k], tag)
     if out_wide:
         after = out.detach().cpu().numpy()
         keep = np.ones(out_wide, bool)
@@ -183,14 +175,14 @@ def test_masked_squared_error(B, Tn):
         cost_opt, cost_sum, err, cnt = ops.masked_squared_error(tp, T(lab), T(mask), accum=accum)
         (cost_opt * 3.0 + cost_sum * 0.5).backward()
         totals += np.concatenate([err.cpu().numpy().astype(np.float64), cnt.cpu().numpy(), [float(cost_sum)]])
-    held("loss_cost", float(cost_opt), ref["cost_opt"], "cost_opt")
-    held("loss_cost", float(cost_sum), ref["cost_sum"], "cost_sum")
-    held("loss_each", err.cpu().numpy(), ref["error_sum"], "error_sum")
+    FB.check("loss_cost", float(cost_opt), ref["cost_opt"], "cost_opt")
+    FB.check("loss_cost", float(cost_sum), ref["cost_sum"], "cost_sum")
+    FB.check("loss_each", err.cpu().numpy(), ref["error_sum"], "error_sum")
     assert np.array_equal(cnt.cpu().numpy(), ref["count"])
     g = tp.grad.cpu().numpy()
     assert np.isfinite(g).all() and not g[mask == 0].any()
-    held("loss_dpred", g, ref["dpred"] * (3.0 / (B * Tn) + 0.5), "d(3 opt + sum / 2)")
-    held("loss_each", accum.cpu().numpy(), totals, "accumulator after three calls")
+    FB.check("loss_dpred", g, ref["dpred"] * (3.0 / (B * Tn) + 0.5), "d(3 opt + sum / 2)")
+    FB.check("loss_each", accum.cpu().numpy(), totals, "accumulator after three calls")
     assert np.array_equal(accum.cpu().numpy()[Tn:2 * Tn], 3 * ref["count"])
     with np.errstate(divide="ignore", invalid="ignore"):
         mse = err.cpu().numpy() / cnt.cpu().numpy()
@@ -207,7 +199,7 @@ def test_regression_metrics_on_the_fixture_sets():
         got = ops.regression_metrics(T(p), T(y), None if m is None else T(m))
         ref = O.regression_sums(p, y, m)
         assert np.array_equal(got[:, [0, 5]], ref[:, [0, 5]]), name
-        held("metric_sums", got / np.maximum(1.0, np.abs(ref)), ref / np.maximum(1.0, np.abs(ref)), name)
+        FB.check("metric_sums", got / np.maximum(1.0, np.abs(ref)), ref / np.maximum(1.0, np.abs(ref)), name)
         d = cv.regression_metrics_from_sums(got[0])
         for key, want in zip(Z["r_keys"].tolist(), Z["r%d_metrics" % j]):
             assert (np.isnan(d[key]) and np.isnan(want)) or abs(d[key] - want) <= 1e-9 * max(1.0, abs(want)), (name, key, d[key], want)
@@ -230,7 +222,7 @@ def test_regression_metrics_on_many_strided_rows():
         assert a.tobytes() == b.tobytes()
         ref = O.regression_sums(p, y, m)
         assert np.array_equal(a[:, [0, 5]], ref[:, [0, 5]])
-        held("metric_sums", a / np.maximum(1.0, np.abs(ref)), ref / np.maximum(1.0, np.abs(ref)), "70,000 x 3 %s" % ("masked" if m is not None else ""))
+        FB.check("metric_sums", a / np.maximum(1.0, np.abs(ref)), ref / np.maximum(1.0, np.abs(ref)), "70,000 x 3 %s" % ("masked" if m is not None else ""))
 
 
 # ---- the models -------------------------------------------------------------------------------------------------------------------------
@@ -246,20 +238,6 @@ def fixture_batch(tag):
     return idx, feat, dense, adj
 
 
-def _set(param, value):
-    import torch
-    with torch.no_grad():
-        param.copy_(torch.as_tensor(np.asarray(value, np.float32), device=param.device).reshape(param.shape))
-
-
-def _load_dense_bn(layer, p):
-    _set(layer.kernel, p["w"])
-    _set(layer.bias, p["b"])
-    if "gamma" in p:
-        _set(layer.gamma, p["gamma"]); _set(layer.beta, p["beta"])
-        _set(layer.moving_mean, p["mean"]); _set(layer.moving_variance, p["var"])
-
-
 def _grads_dense_bn(layer, bn=True):
     g = {"w": layer.kernel.grad, "b": layer.bias.grad}
     if bn:
@@ -273,7 +251,7 @@ def _check_tree(got, ref):
     assert sorted(got) == sorted(ref)
     for path in sorted(ref):
         assert got[path] is not None, path
-        held("model_grad", got[path].cpu().numpy().reshape(ref[path].shape), ref[path], path)
+        FB.check("model_grad", got[path].cpu().numpy().reshape(ref[path].shape), ref[path], path)
 
 
 @pytest.mark.parametrize("fusion", [True, False])
@@ -288,17 +266,17 @@ def test_vec_model_against_the_oracle(tag, fusion, monkeypatch):
     model = models.MultimodalVecGCN(1, 2).to(dev())
     with torch.no_grad():
         model(T(feat), adj, vectors=T(vec))
-    _set(model.conv.w[0], P["conv"]["w"]); _set(model.conv.bias[0], P["conv"]["b"])
-    _set(model.dense.kernel, P["dense"]["w"]); _set(model.dense.bias, P["dense"]["b"])
+    set_param(model.conv.w[0], P["conv"]["w"]); set_param(model.conv.bias[0], P["conv"]["b"])
+    set_param(model.dense.kernel, P["dense"]["w"]); set_param(model.dense.bias, P["dense"]["b"])
     for layer, p in zip(list(model.tower) + [model.hidden, model.out], P["tower"] + [P["hidden"], P["out"]]):
-        _load_dense_bn(layer, p)
+        load_dense_bn(layer, p)
     logits = model(T(feat), adj, vectors=T(vec))
     cost_opt, cost_sum = model.loss(logits, T(labels), T(mask))
     cost_opt.backward()
     ref_logits, (ref_opt, ref_sum), G = O.vec_model(feat, dense, vec, P, labels, mask)
-    held("model_logits", logits.detach().cpu().numpy(), ref_logits, tag)
-    held("model_cost", float(cost_opt), ref_opt, "cost_opt")
-    held("model_cost", float(cost_sum), ref_sum, "cost_sum")
+    FB.check("model_logits", logits.detach().cpu().numpy(), ref_logits, tag)
+    FB.check("model_cost", float(cost_opt), ref_opt, "cost_opt")
+    FB.check("model_cost", float(cost_sum), ref_sum, "cost_sum")
     got = {"conv": {"w": model.conv.w[0].grad, "b": model.conv.bias[0].grad},
            "dense": {"w": model.dense.kernel.grad, "b": model.dense.bias.grad},
            "tower": [_grads_dense_bn(m) for m in model.tower], "hidden": _grads_dense_bn(model.hidden),
@@ -322,18 +300,18 @@ def test_regression_model_against_the_oracle(tag, fusion, monkeypatch):
     with torch.no_grad():
         model(T(feat), adj, vectors=T(vec), enabled_node_nums=en)
     for i, (d, b) in enumerate(((model.dense1, model.bn1), (model.dense2, model.bn2), (model.dense3, model.bn3))):
-        _set(d.kernel, P["gd"][i]["w"]); _set(d.bias, P["gd"][i]["b"])
-        _set(b.gamma, P["bn"][i]["gamma"]); _set(b.beta, P["bn"][i]["beta"])
-        _set(b.moving_mean, P["bn"][i]["mean"]); _set(b.moving_variance, P["bn"][i]["var"])
-    _load_dense_bn(model.vec, P["vec"])
-    _load_dense_bn(model.out, P["out"])
+        set_param(d.kernel, P["gd"][i]["w"]); set_param(d.bias, P["gd"][i]["b"])
+        set_param(b.gamma, P["bn"][i]["gamma"]); set_param(b.beta, P["bn"][i]["beta"])
+        set_param(b.moving_mean, P["bn"][i]["mean"]); set_param(b.moving_variance, P["bn"][i]["var"])
+    load_dense_bn(model.vec, P["vec"])
+    load_dense_bn(model.out, P["out"])
     pred = model(T(feat), adj, vectors=T(vec), enabled_node_nums=en)
     cost_opt, cost_sum = model.loss(pred, T(y), T(ml))
     cost_opt.backward()
     ref_pred, L, G = O.regression_model(feat, sizes, vec, P, y, ml)
-    held("model_logits", pred.detach().cpu().numpy(), ref_pred, tag)
-    held("model_cost", float(cost_opt), L["cost_opt"], "cost_opt")
-    held("model_cost", float(cost_sum), L["cost_sum"], "cost_sum")
+    FB.check("model_logits", pred.detach().cpu().numpy(), ref_pred, tag)
+    FB.check("model_cost", float(cost_opt), L["cost_opt"], "cost_opt")
+    FB.check("model_cost", float(cost_sum), L["cost_sum"], "cost_sum")
     got = {"gd": [{"w": d.kernel.grad, "b": d.bias.grad} for d in (model.dense1, model.dense2, model.dense3)],
            "bn": [{"gamma": b.gamma.grad, "beta": b.beta.grad} for b in (model.bn1, model.bn2, model.bn3)],
            "vec": _grads_dense_bn(model.vec), "out": _grads_dense_bn(model.out, bn=False)}
@@ -488,7 +466,7 @@ def test_train_cv_regression_and_the_default_task_beside_it(tmp_path):
         assert np.array_equal(eager[:len(part)].cpu().numpy(), got[it:it + len(part)])
     sums = np.asarray(out["info_cv"][-1]["sums"])
     ref = O.regression_sums(got, Z["ds_label_reg"][test_idx])
-    held("metric_sums", sums / np.maximum(1.0, np.abs(ref)), ref / np.maximum(1.0, np.abs(ref)), "test fold")
+    FB.check("metric_sums", sums / np.maximum(1.0, np.abs(ref)), ref / np.maximum(1.0, np.abs(ref)), "test fold")
     # a default-task validator built beside the regression one: the costs of the one built before, bit for bit
     after, pred_after, _ = _cpi_costs()
     assert before == after and np.array_equal(pred_before, pred_after)

@@ -11,7 +11,6 @@ Bound: 1e-5 of max|oracle| per output array (the family's bound: test_gpu_cpi_ig
 the error measured on the MI355X (tests/golden/vecmodal_ig_bounds.json; never below one fp32 ulp, 2^-23; never above 1e-5).
 KGCN_VECMODAL_IG_RECORD=<file> writes the errors of a run."""
 import ctypes
-import json
 import os
 import sys
 
@@ -22,55 +21,19 @@ torch = pytest.importorskip("torch")
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import family_bounds  # noqa: E402
 import vecmodal_ig_oracle as IO  # noqa: E402
+from gpu_helpers import load_dense_bn, set_param, to_device as t  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 Z = np.load(os.path.join(ROOT, "tests", "golden", "g12_vecmodal.npz"), allow_pickle=False)
-TOL = 1e-5
-ULP = 2.0 ** -23
-BOUNDS_PATH = os.path.join(ROOT, "tests", "golden", "vecmodal_ig_bounds.json")
-MEASURED = {}
+# FB.check: equal shapes, finite values, a reference that is not all zero; then max|got - ref| / max|oracle| (big=: over the given
+# magnitude instead) under `key`, held to min(1e-5, max(2^-23, stored))
+FB = family_bounds.FAMILIES["vecmodal_ig"]
 ACTS = (None, "relu", "tanh", "sigmoid")
 G = len(IO.COMPOUNDS)
 D = IO.DIVIDE
-
-
-def _bounds():
-    if not os.path.exists(BOUNDS_PATH):
-        return {}
-    return json.load(open(BOUNDS_PATH)).get("bounds", {})
-
-
-def _bound(key):
-    return min(TOL, max(ULP, _bounds().get(key, TOL)))
-
-
-def _check(key, got, ref, tag="", big=None):
-    """max|got - ref| / max|ref| printed, recorded under `key`, and held to min(1e-5, the ratcheted bound).  big: the magnitude
-    the error is taken of in place of max|ref| (for a difference of two outputs: the outputs' own magnitude)."""
-    ref = np.asarray(ref, np.float64)
-    got = np.asarray(got, np.float64)
-    assert got.shape == ref.shape, (key, got.shape, ref.shape)
-    assert np.isfinite(got).all(), key
-    assert np.abs(ref).max() > 0, key
-    err = float(np.abs(got - ref).max() / (np.abs(ref).max() if big is None else big))
-    MEASURED[key] = max(MEASURED.get(key, 0.0), err)
-    print("vecmodal_ig %-34s %-40s err / max|oracle| = %.3e  (bound %.3e)" % (key, tag, err, _bound(key)))
-    assert err <= _bound(key), (key, tag, err, _bound(key))
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _record():
-    yield
-    path = os.environ.get("KGCN_VECMODAL_IG_RECORD")
-    if path:
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        json.dump({"measured": MEASURED}, open(path, "w"), indent=1, sort_keys=True)
-
-
-def t(a, dtype=np.float32):
-    return torch.as_tensor(np.ascontiguousarray(a, dtype=dtype), device="cuda")
 
 
 # ---- the kernels against the oracle's sweeps ------------------------------------------------------------------------------------------
@@ -147,7 +110,7 @@ def test_kernels_against_the_sweeps(H):
                     y, _ = _expand(Pm, alpha, p, act, wide=False)
                     yw, _ = _expand(Pm, alpha, p, act, wide=True)
                     if np.abs(ref_y).max() > 0:
-                        _check("op expand", y, ref_y, tag)
+                        FB.check("op expand", y, ref_y, tag)
                     assert np.array_equal(y, yw), tag                # the unaligned column block: the same bits
                     assert np.array_equal(y, _expand(Pm, alpha, p, act, wide=False)[0]), tag
                     # reduce: on the DEVICE's Y, so that a relu unit is on or off on both sides; NaN where the weight is 0
@@ -159,7 +122,7 @@ def test_kernels_against_the_sweeps(H):
                     ss = ops.ig_copies_reduce(_strided(dY), _strided(y), t(w), sc, act)
                     assert tuple(s.shape) == (C, H) and torch.isfinite(s).all(), tag
                     if np.abs(ref_s).max() > 0:
-                        _check("op reduce", s.cpu().numpy(), ref_s, tag)
+                        FB.check("op reduce", s.cpu().numpy(), ref_s, tag)
                     assert torch.equal(s, ss) and torch.equal(s, ops.ig_copies_reduce(t(dY), t(y), w, sc, act)), tag
                     if C == 5:                                        # a compound alone: the same bits
                         for c in range(C):
@@ -247,19 +210,6 @@ def test_entry_points_refuse_what_they_do_not_serve():
 _SETUPS = {}
 
 
-def _set(param, value):
-    with torch.no_grad():
-        param.copy_(torch.as_tensor(np.asarray(value, np.float32), device=param.device).reshape(param.shape))
-
-
-def _load_dense_bn(layer, p):
-    _set(layer.kernel, p["w"])
-    _set(layer.bias, p["b"])
-    if "gamma" in p:
-        _set(layer.gamma, p["gamma"]); _set(layer.beta, p["beta"])
-        _set(layer.moving_mean, p["mean"]); _set(layer.moving_variance, p["var"])
-
-
 def _setup(kind):
     """Parameters, data, dataset and model of one kind, made once -> dict"""
     if kind not in _SETUPS:
@@ -274,17 +224,17 @@ def _setup(kind):
         with torch.no_grad():
             model(xb, adj, vectors=t(V))                                        # builds the layers
         if kind == "vec":
-            _set(model.conv.w[0], P["conv"]["w"]); _set(model.conv.bias[0], P["conv"]["b"])
-            _set(model.dense.kernel, P["dense"]["w"]); _set(model.dense.bias, P["dense"]["b"])
+            set_param(model.conv.w[0], P["conv"]["w"]); set_param(model.conv.bias[0], P["conv"]["b"])
+            set_param(model.dense.kernel, P["dense"]["w"]); set_param(model.dense.bias, P["dense"]["b"])
             for layer, p in zip(list(model.tower) + [model.hidden, model.out], P["tower"] + [P["hidden"], P["out"]]):
-                _load_dense_bn(layer, p)
+                load_dense_bn(layer, p)
         else:
             for i, (d, b) in enumerate(((model.dense1, model.bn1), (model.dense2, model.bn2), (model.dense3, model.bn3))):
-                _set(d.kernel, P["gd"][i]["w"]); _set(d.bias, P["gd"][i]["b"])
-                _set(b.gamma, P["bn"][i]["gamma"]); _set(b.beta, P["bn"][i]["beta"])
-                _set(b.moving_mean, P["bn"][i]["mean"]); _set(b.moving_variance, P["bn"][i]["var"])
-            _load_dense_bn(model.vec, P["vec"])
-            _load_dense_bn(model.out, P["out"])
+                set_param(d.kernel, P["gd"][i]["w"]); set_param(d.bias, P["gd"][i]["b"])
+                set_param(b.gamma, P["bn"][i]["gamma"]); set_param(b.beta, P["bn"][i]["beta"])
+                set_param(b.moving_mean, P["bn"][i]["mean"]); set_param(b.moving_variance, P["bn"][i]["var"])
+            load_dense_bn(model.vec, P["vec"])
+            load_dense_bn(model.out, P["out"])
         labels = Z["ds_label_reg"][:G] if kind == "regression" else Z["ds_label_cls"][:G]
         _SETUPS[kind] = dict(P=P, X=X, A=A, V=V, sizes=sizes, ds=ds, model=model, labels=labels,
                              name="dragon" if kind == "regression" else "profeat")
@@ -361,13 +311,13 @@ def _against_literal(prefix, kind, recs, ref, modal, tag):
     assert [r["compound_id"] for r in recs] == list(range(G))
     assert [r["target_label"] for r in recs] == [q["target"] for q in ref]
     for m in targets:
-        _check("%s %s %s_IG" % (prefix, kind, "vector" if m == name else m), np.stack([r[m + "_IG"] for r in recs]),
+        FB.check("%s %s %s_IG" % (prefix, kind, "vector" if m == name else m), np.stack([r[m + "_IG"] for r in recs]),
                np.stack([q[m + "_IG"] for q in ref]), tag)
     # check_score = end - start is the difference of two fp32 scores (two softmax probabilities close to each other, or two
     # predictions): each carries an error of its own magnitude, so the difference is held to 1e-5 of the scores it is formed from
-    _check("%s %s check_score" % (prefix, kind), [r["check_score"] for r in recs], [q["end"] - q["start"] for q in ref], tag,
+    FB.check("%s %s check_score" % (prefix, kind), [r["check_score"] for r in recs], [q["end"] - q["start"] for q in ref], tag,
            big=max(max(abs(q["end"]), abs(q["start"])) for q in ref))
-    _check("%s %s prediction_score" % (prefix, kind), [r["prediction_score"] for r in recs], [q["prediction"] for q in ref], tag)
+    FB.check("%s %s prediction_score" % (prefix, kind), [r["prediction_score"] for r in recs], [q["prediction"] for q in ref], tag)
     N, F = s["X"].shape[1:]
     Dv = s["V"].shape[1]
     for r in recs:
@@ -406,7 +356,7 @@ def test_public_function_matches_the_literal_loop(kind, modal, method):
         a, b = (np.stack([r[m + "_IG"] for r in recs]).astype(np.float64) for recs in (fused, comp))
         err = float(np.abs(a - b).max() / np.abs(np.stack([q[m + "_IG"] for q in ref])).max())
         print("vecmodal_ig fused vs composed %s %s: %.3e of max|oracle|" % (key, tag, err))
-        assert err <= _bound("fused " + key) + _bound("composed " + key)
+        assert err <= FB.bound("fused " + key) + FB.bound("composed " + key)
 
 
 @pytest.mark.parametrize("fused", [True, False])
@@ -463,7 +413,8 @@ def test_refusals_targets_and_the_untargeted_vector():
 
 
 def test_completeness_with_the_reference_step_count():
-    """D = 100, every modal: sum_of_IG ~ end - start; the GPU's gap is held to the oracle's own gap plus 1e-5 of the magnitudes."""
+    """D = 100, every modal: sum_of_IG ~ end - start; the GPU's gap is held to the oracle's own gap plus the family's bound for this key
+    (at most 1e-5) of the magnitudes."""
     for kind in ("vec", "regression"):
         s = _setup(kind)
         recs = _run(kind, modal="all", divide_number=100)
@@ -477,11 +428,9 @@ def test_completeness_with_the_reference_step_count():
             want = ref["end"] - ref["start"]
             scale = sum(np.abs(ref[m + "_IG"]).sum() for m in targets) + abs(want)
             excess = max(0.0, abs(r["sum_of_IG"] - r["check_score"]) - abs(ref["sum_of_IG"] - want)) / scale
-            key = "completeness excess / scale"
-            MEASURED[key] = max(MEASURED.get(key, 0.0), excess)
-            print("vecmodal_ig %s compound %d: sum_of_IG %.6f check_score %.6f (oracle %.6f / %.6f), excess / scale %.2e"
-                  % (kind, g, r["sum_of_IG"], r["check_score"], ref["sum_of_IG"], want, excess))
-            assert excess <= TOL
+            print("vecmodal_ig %s compound %d: sum_of_IG %.6f check_score %.6f (oracle %.6f / %.6f)"
+                  % (kind, g, r["sum_of_IG"], r["check_score"], ref["sum_of_IG"], want))
+            FB.hold("completeness excess / scale", excess, "%s compound %d" % (kind, g))
 
 
 def test_example_writes_its_dumps(tmp_path):
