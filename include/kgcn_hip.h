@@ -539,6 +539,10 @@ int kgcn_csr_compact4(const kgcn_csr_batch* a4, void* cv_out, int with_values, v
  * forward; the pairs backward with dx), else 0.  backward: 0 forward, 1 backward; max_nnz of the row-padded batch. */
 int kgcn_graphconv_fused_reads_compact(int32_t backward, int32_t num_graphs, int32_t n_nodes, int32_t din, int32_t dout,
                                        int32_t max_nnz_per_graph, int32_t with_dx);
+/* 1 if kgcn_graphconv_fwd_f32, for these arguments, runs the FULL forward as reader | aggregator wave pairs
+ * (graphconv_fwd_full_kernel), 0 if one wave per graph (small batches, slices too large for the pairs' LDS, other shapes).
+ * Both compute the same bits.  max_nnz of the row-padded batch. */
+int kgcn_graphconv_fwd_pairs_route(int32_t num_graphs, int32_t n_nodes, int32_t din, int32_t dout, int32_t max_nnz_per_graph);
 
 /* -- ragged-compact batches: the layer stack on the VALID node rows only ------------------------------------------------ */
 /* The reference pads every graph to max_node_num rows (kgcn/data_util.py:30-37, feed.py:127-133); its ragged layers

@@ -475,6 +475,33 @@ __device__ __forceinline__ void aggregate_rows_full(const int2* ecv, const float
   }
 }
 
+// The same rows with the same sums, TWO passes in flight (a wave that only aggregates has the registers; the LDS latency chain
+// slot -> entries -> neighbour rows -> sum is walked four times per graph instead of eight)
+template <int LAY, typename Emit>
+__device__ __forceinline__ void aggregate_rows_full2(const int2* ecv, const float* ev, const int* tab, const float* tile,
+                                                     int lane, Emit&& emit) {
+  const int sub = lane >> 4, cl = lane & 15;
+  const float* srcl = tile + cl * 4;
+#pragma unroll
+  for (int p4 = 0; p4 < 4; ++p4) {
+    int sa, lena, rowa, sb, lenb, rowb;
+    unpack_slot(tab[8 * p4 + sub], sa, lena, rowa);
+    unpack_slot(tab[8 * p4 + 4 + sub], sb, lenb, rowb);
+    Grp4<LAY> qa, qb;
+    qa.ecv(ecv, ev, sa);
+    qb.ecv(ecv, ev, sb);
+    qa.tile(srcl);
+    qb.tile(srcl);
+    qa.fma();
+    qb.fma();
+    grp_tail<LAY>(qa.a, sa, lena, ecv, ev, srcl);
+    grp_tail<LAY>(qb.a, sb, lenb, ecv, ev, srcl);
+    emit(rowa, cl, qa.a);
+    emit(rowb, cl, qb.a);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------
@@ -508,6 +535,59 @@ __device__ __forceinline__ void store_c_tiles(float* tile, const f32x16& c0, con
     tile[row * FD + li] = c0[r];
     tile[row * FD + 32 + li] = c1[r];
   }
+}
+
+// The FULL forward's contraction, shared by its two kernels (graphconv_fwd_full_kernel, graphconv_fwd_wave_kernel).
+// B fragments of FW = X W: lane (li, hi), tile nt, k-step ks holds W[k][32 nt + li] for k = 16 ks + 8 hi + j as three bf16
+// pieces: p1 and p2 resident in WF, p3 in the workgroup's table w3 (written by the waves with `table` set)
+__device__ __forceinline__ void fwd_w_frags(u32x4 (&WF)[2][4][2], u32x4* w3, bool table, const float* __restrict__ w, int lane) {
+  const int li = lane & 31, hi = lane >> 5;
+  static_for<8>([&](auto c) __attribute__((always_inline)) {
+    constexpr int nt = decltype(c)::value >> 2, ks = decltype(c)::value & 3;
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = w[(16 * ks + 8 * hi + j) * FD + 32 * nt + li];
+    Frag3 f;
+    split8(v, f);
+    WF[nt][ks][0] = f.p1; WF[nt][ks][1] = f.p2;
+    if (table) w3[(nt * 4 + ks) * 64 + lane] = f.p3;
+  });
+}
+// FW = X W + b out of the A tile `a` ([FN][ALD]): per k-step 8 values of row li (k = 16 ks + 8 hi + j) are split, then
+// 6 products x 2 output tiles; the accumulators start from the bias
+// AHEAD: the values of k-step ks + 1 are read before the products of k-step ks (8 more registers live)
+template <bool AHEAD = false>
+__device__ __forceinline__ void fwd_contract(f32x16& acc0, f32x16& acc1, const float* a, const u32x4 (&WF)[2][4][2],
+                                             const u32x4* w3, float b0, float b1, int lane) {
+  const int li = lane & 31, hi = lane >> 5;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) { acc0[r] = b0; acc1[r] = b1; }
+  const float* src0 = a + li * ALD + 8 * hi;
+  f32x4 lo, hi4;
+  if constexpr (AHEAD) { lo = ldv4(src0); hi4 = ldv4(src0 + 4); }
+  static_for<4>([&](auto ksc) __attribute__((always_inline)) {
+    constexpr int ks = decltype(ksc)::value;
+    const float* src = src0 + 16 * ks;
+    if constexpr (!AHEAD) { lo = ldv4(src); hi4 = ldv4(src + 4); }
+    const float v[8] = {lo[0], lo[1], lo[2], lo[3], hi4[0], hi4[1], hi4[2], hi4[3]};
+    if constexpr (AHEAD && ks < 3) { lo = ldv4(src + 16); hi4 = ldv4(src + 20); }
+    Frag3 fa;
+    split8(v, fa);
+    const u32x4 w30 = w3[ks * 64 + lane], w31 = w3[(4 + ks) * 64 + lane];
+    acc0 = mfma_bf16(fa.p3, WF[0][ks][0], acc0);      // smallest terms first
+    acc1 = mfma_bf16(fa.p3, WF[1][ks][0], acc1);
+    acc0 = mfma_bf16(fa.p2, WF[0][ks][1], acc0);
+    acc1 = mfma_bf16(fa.p2, WF[1][ks][1], acc1);
+    acc0 = mfma_bf16(fa.p1, w30, acc0);
+    acc1 = mfma_bf16(fa.p1, w31, acc1);
+    acc0 = mfma_bf16(fa.p2, WF[0][ks][0], acc0);
+    acc1 = mfma_bf16(fa.p2, WF[1][ks][0], acc1);
+    acc0 = mfma_bf16(fa.p1, WF[0][ks][1], acc0);
+    acc1 = mfma_bf16(fa.p1, WF[1][ks][1], acc1);
+    acc0 = mfma_bf16(fa.p1, WF[0][ks][0], acc0);
+    acc1 = mfma_bf16(fa.p1, WF[1][ks][0], acc1);
+    __builtin_amdgcn_sched_barrier(0);   // one k-step of fragments live at a time (register budget)
+  });
 }
 
 // Generic shapes (N <= 32, din/dout <= 64; VEC: both multiples of 4): prefetch + phase-sequential per graph.
@@ -638,7 +718,7 @@ constexpr size_t FWD_FULL_SHARED = 2 * 4 * 64 * 16;   // W p3 fragments: [tile][
 // LAY: adjacency layout (LAY_PAD4: row_pad = 4, cv = (col, value) pairs; LAY_UNIT / LAY_VALS: compact, cv = column words,
 // cvals = the value stream of LAY_VALS)
 template <int LAY>
-__global__ __launch_bounds__(512, 2) void graphconv_fwd_full_kernel(
+__global__ __launch_bounds__(512, 2) void graphconv_fwd_wave_kernel(
     const int* __restrict__ slots, const int* __restrict__ gptr, const int2* __restrict__ cv,
     const float* __restrict__ cvals, const float* __restrict__ x, const float* __restrict__ w,
     const float* __restrict__ bias, float* __restrict__ out, int T, int max_nnz) {
@@ -658,19 +738,8 @@ __global__ __launch_bounds__(512, 2) void graphconv_fwd_full_kernel(
     else issue_cv_c<LAY>(f, cw, cvals, b_, c_, lane);
   };
 
-  // B fragments of FW = X W: lane (li, hi), tile nt, k-step ks holds W[k][32 nt + li] for
-  // k = 16 ks + 8 hi + j as three bf16 pieces
   u32x4 WF[2][4][2];
-  static_for<8>([&](auto c) __attribute__((always_inline)) {
-    constexpr int nt = decltype(c)::value >> 2, ks = decltype(c)::value & 3;
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = w[(16 * ks + 8 * hi + j) * D + 32 * nt + li];
-    Frag3 f;
-    split8(v, f);
-    WF[nt][ks][0] = f.p1; WF[nt][ks][1] = f.p2;
-    if (wave == 0) w3[(nt * 4 + ks) * 64 + lane] = f.p3;
-  });
+  fwd_w_frags(WF, w3, wave == 0, w, lane);
   __syncthreads();
 
   const int nwaves = gridDim.x * wpb;
@@ -742,33 +811,9 @@ __global__ __launch_bounds__(512, 2) void graphconv_fwd_full_kernel(
       issue_meta_l<LAY>(m_nxt, slots, gptr, hot(tnn < T ? tnn : tp), N, lane);
     }
 
-    // ---- 4. FW(t) = X(t) W + b: per k-step 8 values of row li (k = 16 ks + 8 hi + j) are split, then
-    // 6 products x 2 output tiles ------------------------------------------------------------------------
+    // ---- 4. FW(t) = X(t) W + b (fwd_contract) --------------------------------------------------------------
     f32x16 acc0, acc1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { acc0[r] = b0; acc1[r] = b1; }
-    static_for<4>([&](auto ksc) __attribute__((always_inline)) {
-      constexpr int ks = decltype(ksc)::value;
-      const float* src = ws.a + li * ALD + 16 * ks + 8 * hi;
-      const f32x4 lo = ldv4(src), hi4 = ldv4(src + 4);
-      const float v[8] = {lo[0], lo[1], lo[2], lo[3], hi4[0], hi4[1], hi4[2], hi4[3]};
-      Frag3 fa;
-      split8(v, fa);
-      const u32x4 w30 = w3[ks * 64 + lane], w31 = w3[(4 + ks) * 64 + lane];
-      acc0 = mfma_bf16(fa.p3, WF[0][ks][0], acc0);      // smallest terms first
-      acc1 = mfma_bf16(fa.p3, WF[1][ks][0], acc1);
-      acc0 = mfma_bf16(fa.p2, WF[0][ks][1], acc0);
-      acc1 = mfma_bf16(fa.p2, WF[1][ks][1], acc1);
-      acc0 = mfma_bf16(fa.p1, w30, acc0);
-      acc1 = mfma_bf16(fa.p1, w31, acc1);
-      acc0 = mfma_bf16(fa.p2, WF[0][ks][0], acc0);
-      acc1 = mfma_bf16(fa.p2, WF[1][ks][0], acc1);
-      acc0 = mfma_bf16(fa.p1, WF[0][ks][1], acc0);
-      acc1 = mfma_bf16(fa.p1, WF[1][ks][1], acc1);
-      acc0 = mfma_bf16(fa.p1, WF[0][ks][0], acc0);
-      acc1 = mfma_bf16(fa.p1, WF[1][ks][0], acc1);
-      __builtin_amdgcn_sched_barrier(0);   // one k-step of fragments live at a time (register budget)
-    });
+    fwd_contract(acc0, acc1, ws.a, WF, w3, b0, b1, lane);
     KP_STAMP(3)
     // ---- 5. FW(t) replaces the gather tile ------------------------------------------------------
     store_c_tiles(ws.b, acc0, acc1, li, hi);
@@ -1611,7 +1656,7 @@ constexpr size_t kLastLevelCacheBytes = (size_t)256 << 20;
 static bool bwd_streams(int T) { return (size_t)T * FN * FD * 4 * 3 > kLastLevelCacheBytes; }
 __device__ __forceinline__ void bp_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-// LAY: adjacency layout of A^T, as in graphconv_fwd_full_kernel;  STREAM: g loads and dX stores with the streaming policy
+// LAY: adjacency layout of A^T, as in graphconv_fwd_wave_kernel;  STREAM: g loads and dX stores with the streaming policy
 template <int LAY, bool STREAM>
 __global__ __launch_bounds__(512, 2) void graphconv_bwd_pairs_kernel(
     const int* __restrict__ slots_t, const int* __restrict__ gptr_t, const int2* __restrict__ cv_t,
@@ -2015,6 +2060,153 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_pairs_kernel(
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// forward, FULL shape, "pairs" version: the one-wave-per-graph kernel above (graphconv_fwd_wave_kernel) with its phases dealt to
+// TWO waves that share a graph slot, four pairs per persistent workgroup, in two roles:
+//   wave R (reader / multiplier)  x(i) registers -> the pair's A tile; x(i+1), CSR(i+1), slots(i+2) requested (x streaming; the
+//                                 load nobody uses reads W); CSR(i) -> slice i & 1; FW(i) = x(i) W + b (fwd_contract: the same
+//                                 products in the same order, the values of the next k-step read ahead) -> gather tile i & 1
+//   wave W (aggregator / writer)  one graph behind: out(i-1) = A(i-1) FW(i-1) out of gather tile and slice (i-1) & 1
+//                                 (aggregate_rows_full2: the same sums in the same order, two passes in flight), streaming stores
+// and ONE workgroup barrier per graph (bp_barrier: vector-memory operations stay in flight across it).  Wave R has only loads on
+// its vmcnt counter, wave W only stores.  Outputs are bit-identical to the one-wave kernel's.
+// Why (tools/bwd_skeleton.hip `fwdpairs`, profiles/fwd_pairs_skeleton.txt): as a byte pattern beside the arithmetic stand-ins the
+// pair form runs at 0.288 ms per 100,000 graphs against 0.317 ms for eight waves that each read, multiply, aggregate and store.
+// The kernel keeps a third of that (0.297 against 0.316 ms, profiles/fwd_pairs_ab.txt): with one barrier per graph a step lasts as
+// long as the longer of the two roles' dependence chains, so what counted after the split was the length of those chains.
+// Measured on the way and not kept (same file):
+//   * The roles of a pair on ADJACENT waves (pair = wave >> 1, different SIMDs), the skeleton's winner (0.288 against 0.311 ms
+//     there): 0.3326 ms in the kernel against 0.3196 for the parent -- the two multiplying waves of two pairs share one SIMD's matrix
+//     pipe and the two aggregating waves another's vector ALU.  Crossed (every SIMD one R and one W of DIFFERENT pairs): 0.3204.
+//   * Both roles on one SIMD with the one-wave kernel's phases as they were (eight aggregation passes one after the other, the
+//     fragment reads of a k-step in front of its products): 0.3113-0.3164 against 0.3148-0.3196.  Two passes in flight: 0.3016;
+//     with the k-step read ahead as well: 0.2956 (shipped).
+//   * A reader two tiles ahead: slower than one tile ahead in the skeleton (0.299 / 0.311 against 0.288 / 0.311), not built.
+// Iteration counts are uniform as in graphconv_bwd_pairs_kernel: the launcher guarantees every pair two graphs, a pair owns
+// cnt_max or cnt_max - 1 of them, every wave passes cnt_max barriers and the one graph a short pair lacks is skipped under a
+// uniform branch behind the loop.  No wave leaves before its last barrier.
+// LDS: W p3 table | per pair: A tile [FN][ALD], two gather tiles [FN+1][FD] (row FN stays zero), two CSR slices, two slot tables
+// (117 KiB at max_nnz = 128).  Batches below KGCN_FWD_PAIRS_MIN_GRAPHS keep one wave per graph: the pipeline's fill (one graph of
+// lag per pair) costs more than the pairing returns there.
+// ------------------------------------------------------------------------------------------------
+constexpr int FP_PAIRS = 4;
+constexpr size_t FP_GT_FLOATS = (size_t)(FN + 1) * FD;
+__host__ __device__ inline size_t fwd_pairs_pair_bytes(int max_nnz) {
+  return (size_t)A_FWD * 4 + 2 * FP_GT_FLOATS * 4 + 2 * (ecv_bytes(max_nnz) + RP_BYTES);
+}
+static_assert((A_FWD * 4) % 16 == 0 && (FP_GT_FLOATS * 4) % 16 == 0 && RP_BYTES % 16 == 0, "16-byte aligned LDS regions");
+static size_t fwd_pairs_lds_bytes(int max_nnz) { return FWD_FULL_SHARED + FP_PAIRS * fwd_pairs_pair_bytes(max_nnz); }
+
+template <int LAY>
+__global__ __launch_bounds__(512, 2) void graphconv_fwd_full_kernel(
+    const int* __restrict__ slots, const int* __restrict__ gptr, const int2* __restrict__ cv,
+    const float* __restrict__ cvals, const float* __restrict__ x, const float* __restrict__ w,
+    const float* __restrict__ bias, float* __restrict__ out, int T, int max_nnz) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int N = FN, D = FD;
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const int pair = wave & 3, role = wave >> 2;                    // the two roles of a pair share a SIMD
+  const int li = lane & 31, hi = lane >> 5;
+  u32x4* w3 = reinterpret_cast<u32x4*>(smem);
+  float* at = reinterpret_cast<float*>(smem + FWD_FULL_SHARED + (size_t)pair * fwd_pairs_pair_bytes(max_nnz));
+  float* gt0 = at + A_FWD;                                        // gather tile b: gt0 + b * FP_GT_FLOATS
+  int2* ecv0 = reinterpret_cast<int2*>(gt0 + 2 * FP_GT_FLOATS);   // CSR slice b: ecv0 + b * ecv_stride
+  const size_t ecv_stride = ecv_bytes(max_nnz) / 8;
+  int* tab0 = reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(ecv0) + 2 * ecv_bytes(max_nnz));   // slot table b: + b * (FN + 4)
+
+  const int npairs = gridDim.x * FP_PAIRS;
+  const int t0 = blockIdx.x * FP_PAIRS + pair;
+  const int cnt_max = (T - 1) / npairs + 1;                       // barriers of EVERY wave; >= 2 (launcher)
+  const int cntw = (T - 1 - t0) / npairs + 1;                     // graphs of this pair: cnt_max or cnt_max - 1
+  const int tl = t0 + (cntw - 1) * npairs;                        // its last graph
+  const bool whole = cntw == cnt_max;                             // uniform
+  auto gidx = [&](int k) { return graph_at(t0, npairs, tl, k); };
+
+  if (role == 0) {
+    // =========================================== wave R ===========================================================
+    u32x4 WF[2][4][2];
+    fwd_w_frags(WF, w3, pair == 0, w, lane);
+    if (lane < D) { gt0[FN * FD + lane] = 0.f; gt0[FP_GT_FLOATS + FN * FD + lane] = 0.f; }   // the zero rows for padding entries
+    __syncthreads();                                              // barrier 0: the W table
+    const float b0 = bias ? bias[li] : 0.f;
+    const float b1 = bias ? bias[32 + li] : 0.f;
+    const unsigned* cw = reinterpret_cast<const unsigned*>(cv);
+    using CsrIn = std::conditional_t<LAY == LAY_PAD4, CsrRegs, CsrRegsC>;
+    auto issue_csr = [&](CsrIn& f, int b_, int c_) __attribute__((always_inline)) {
+      if constexpr (LAY == LAY_PAD4) issue_cv(f, cv, b_, c_, lane);
+      else issue_cv_c<LAY>(f, cw, cvals, b_, c_, lane);
+    };
+    TileRegs fx;
+    CsrIn fc;
+    MetaRegs m_cur, m_nxt;
+    issue_meta_l<LAY>(m_cur, slots, gptr, gidx(0), N, lane);
+    int base = meta_base(m_cur), cnt = meta_cnt(m_cur);
+    issue_tile<true, true>(fx, x + (long)gidx(0) * N * D, 512, lane);
+    issue_csr(fc, base, cnt);
+    issue_meta_l<LAY>(m_nxt, slots, gptr, gidx(1), N, lane);
+    wave_sync();
+    auto land_csr_l = [&](int cur) __attribute__((always_inline)) {
+      int2* ecv_c = ecv0 + cur * ecv_stride;
+      int* tab_c = tab0 + cur * (FN + 4);
+      if constexpr (LAY == LAY_PAD4) land_csr(fc, ecv_c, tab_c, cv, m_cur.slot, base, cnt, N, lane);
+      else land_csr_c<LAY>(fc, ecv_c, tab_c, cw, cvals, max_nnz, compact_slot_word(m_cur.slot), base, cnt, N, lane);
+    };
+    auto multiply = [&](int cur) __attribute__((always_inline)) {
+      f32x16 acc0, acc1;
+      fwd_contract<true>(acc0, acc1, at, WF, w3, b0, b1, lane);
+      store_c_tiles(gt0 + cur * FP_GT_FLOATS, acc0, acc1, li, hi);
+    };
+    int cur = 0;
+    for (int i = 0; i < cnt_max - 1; ++i) {                       // graph i exists for every pair
+      // x(i): registers -> A tile; x(i+1) in flight (branch-free; a short pair's last request reads the first 8 KB of W, unused)
+      land_tile<true>(fx, at, ALD, 512, 16, lane);
+      static_assert(FD * FD >= FN * FD, "W holds at least one tile's floats");
+      issue_tile<true, true>(fx, i + 1 < cntw ? x + (long)gidx(i + 1) * N * D : w, 512, lane);
+      wave_sync();
+      // CSR(i): registers -> slice `cur` (wave W read graph i - 2 out of it before the barrier this wave has just passed)
+      land_csr_l(cur);
+      const int base_n = meta_base(m_nxt), cnt_n = meta_cnt(m_nxt);
+      issue_csr(fc, base_n, cnt_n);
+      // a REAL register move (see graphconv_fwd_wave_kernel: a plain copy becomes a phi whose copy lands behind the new load)
+      asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %3"
+                   : "=&v"(m_cur.slot), "=&v"(m_cur.gp) : "v"(m_nxt.slot), "v"(m_nxt.gp));
+      issue_meta_l<LAY>(m_nxt, slots, gptr, gidx(i + 2), N, lane);
+      multiply(cur);
+      base = base_n;
+      cnt = cnt_n;
+      bp_barrier();
+      cur ^= 1;
+    }
+    if (whole) {                                                  // graph cnt_max - 1: nothing left to request
+      land_tile<true>(fx, at, ALD, 512, 16, lane);
+      wave_sync();
+      land_csr_l(cur);
+      multiply(cur);
+    }
+    bp_barrier();
+  } else {
+    // =========================================== wave W ===========================================================
+    __syncthreads();                                              // barrier 0: the W table
+    auto aggregate = [&](int k, int cur) __attribute__((always_inline)) {
+      float* ot = out + (long)gidx(k) * N * D;
+      const int2* ecv_c = ecv0 + cur * ecv_stride;
+      const float* ev = reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(ecv_c) + cvals_off(max_nnz));
+      aggregate_rows_full2<LAY>(ecv_c, ev, tab0 + cur * (FN + 4), gt0 + cur * FP_GT_FLOATS, lane, [&](int r, int c4, f32x4 v) {
+        stv4_stream(ot + r * D + c4 * 4, v);
+      });
+    };
+    bp_barrier();                                                 // FW(0) and CSR(0) are in buffer 0
+    int cur = 0;
+    for (int i = 1; i < cnt_max; ++i) {                           // graph i - 1 exists for every pair
+      aggregate(i - 1, cur);
+      bp_barrier();
+      cur ^= 1;
+    }
+    if (whole) aggregate(cnt_max - 1, cur);
+  }
+}
+
 // waves per block that fit the LDS budget (0 = does not fit at all)
 static int fused_wpb(size_t per_wave, size_t shared_bytes) {
   long fit = ((long)kLdsBytes - (long)shared_bytes) / (long)per_wave;
@@ -2104,6 +2296,17 @@ static bool bwd_pairs_route(int T, int n, int din, int dout, int max_nnz, bool w
          T >= 2 * BP_PAIRS * fused_grid(T, BWD_FULL_WPB);
 }
 
+// the forward's kernel choice for the FULL shape (kgcn_graphconv_fwd_f32): the pairs kernel when its LDS fits, every pair owns at
+// least two graphs (uniform barrier counts) and the batch is long enough to pay for the pipeline's fill (one graph of lag per
+// pair; measured: profiles/fwd_pairs_ab.txt), else one wave per graph
+#ifndef KGCN_FWD_PAIRS_MIN_GRAPHS
+#define KGCN_FWD_PAIRS_MIN_GRAPHS 16384
+#endif
+static bool fwd_pairs_route(int T, int n, int din, int dout, int max_nnz) {
+  return is_full(n, din, dout) && fwd_pairs_lds_bytes(max_nnz) <= (size_t)kLdsBytes && T >= KGCN_FWD_PAIRS_MIN_GRAPHS &&
+         T >= 2 * FP_PAIRS * fused_grid(T, FP_PAIRS);
+}
+
 }  // namespace kgcn
 
 using namespace kgcn;
@@ -2119,6 +2322,12 @@ extern "C" int kgcn_graphconv_fused_reads_compact(int32_t backward, int32_t num_
   if (num_graphs <= 0 || !fused_shape_ok(n_nodes, din, dout, max_nnz_per_graph)) return 0;
   if (!backward) return is_full(n_nodes, din, dout) ? 1 : 0;
   return bwd_pairs_route(num_graphs, n_nodes, din, dout, max_nnz_per_graph, with_dx != 0) ? 1 : 0;
+}
+
+extern "C" int kgcn_graphconv_fwd_pairs_route(int32_t num_graphs, int32_t n_nodes, int32_t din, int32_t dout,
+                                              int32_t max_nnz_per_graph) {
+  if (num_graphs <= 0 || !fused_shape_ok(n_nodes, din, dout, max_nnz_per_graph)) return 0;
+  return fwd_pairs_route(num_graphs, n_nodes, din, dout, max_nnz_per_graph) ? 1 : 0;
 }
 
 extern "C" int kgcn_graphconv_fused_supported(int32_t n_nodes, int32_t din, int32_t dout,
@@ -2157,10 +2366,18 @@ extern "C" int kgcn_graphconv_fwd_f32(const kgcn_csr_batch* a, const float* x, c
   const int lay = lay_of(a);
   const float* cvals = compact_values(a);
   int rc = 0;
-  if (full_shape)
+  if (fwd_pairs_route(a->num_graphs, a->rows, din, dout, a->max_nnz_per_graph))
     with_const3(lay, [&](auto L) {
       constexpr auto kernel = graphconv_fwd_full_kernel<decltype(L)::value>;
-      if ((rc = allow_full_lds<kernel>(lds, "graphconv_fwd_full_kernel"))) return;
+      const size_t pairs_lds = fwd_pairs_lds_bytes(a->max_nnz_per_graph);
+      if ((rc = allow_full_lds<kernel>(pairs_lds, "graphconv_fwd_full_kernel"))) return;
+      hipLaunchKernelGGL(kernel, dim3(fused_grid(a->num_graphs, FP_PAIRS)), dim3(128 * FP_PAIRS), pairs_lds, as_stream(stream),
+                         a->slots, a->graph_ptr, cv, cvals, x, w, bias, out, a->num_graphs, a->max_nnz_per_graph);
+    });
+  else if (full_shape)
+    with_const3(lay, [&](auto L) {
+      constexpr auto kernel = graphconv_fwd_wave_kernel<decltype(L)::value>;
+      if ((rc = allow_full_lds<kernel>(lds, "graphconv_fwd_wave_kernel"))) return;
       hipLaunchKernelGGL(kernel, grid, block, lds, as_stream(stream), a->slots, a->graph_ptr, cv, cvals, x, w, bias, out,
                          a->num_graphs, a->max_nnz_per_graph);
     });

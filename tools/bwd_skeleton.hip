@@ -7,10 +7,12 @@
 //   PX  as P with x loaded in the dW A-fragment layout of the shipped kernel (16 x 8-byte loads, two 256-byte rows each)
 //   H   persistent PAIRS: two waves share a graph (wave A: g + CSR in, dX out; wave B: x in), 8 waves per CU   (the two-role form)
 //   N   non-persistent, one wave per graph, no prefetch, as many waves per CU as registers allow       (the SpMM's structure)
-// usage: bwd_skeleton [graphs [ingest | dxstore]]
+// usage: bwd_skeleton [graphs [ingest | dxstore | fwdpairs]]
 //   ingest:  only the LDS-DMA / nontemporal arms of skel_fi / skel_hi and their references
 //   dxstore: only the dX store forms of skel_hi (S0 / S1 / S2, plain and nontemporal, pure and beside the arithmetic) and the
 //            write-only / read-only streams that price a stored and a loaded byte on the box at hand
+//   fwdpairs: only the forward as reader | aggregator wave pairs (skel_fp) against the shipped structure (skel_fi), both streams
+//            nontemporal, pure and beside the arithmetic, three repetitions, with the medians, the spreads and the gate at the end
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -555,6 +557,87 @@ __global__ __launch_bounds__(512) void skel_r(const float* __restrict__ a, const
   if (acc[0] + acc[1] + acc[2] + acc[3] == 123.456f) out[lane] = acc[0];
 }
 
+// forward as reader | aggregator wave PAIRS (one persistent 512-thread workgroup per CU, four pairs), both streams nontemporal,
+// ONE barrier per graph, the hand-over double-buffered in LDS.  In iteration i
+//   role R: x(i) registers -> the pair's A tile, x(i + AHEAD) + CSR(i + AHEAD) requested, A tile read back, 48 MFMAs [contraction],
+//           the product tile and CSR(i) -> gather buffer i & 1, barrier                                  (loads only on its vmcnt)
+//   role W: gather buffer (i - 1) & 1 -> registers, 400 v_fma_f32 [aggregation], 8 x 1 KiB out stores of graph i - 1, barrier
+//                                                                                                          (stores only on its vmcnt)
+// PLACE 0: the two roles of a pair on the same SIMD (pair = wave & 3, role = wave >> 2, as graphconv_bwd_pairs_kernel);
+//       1: on adjacent waves (pair = wave >> 1, role = wave & 1, as arm FH)
+// AHEAD: tiles the reader holds in registers beyond the one it is landing (1 or 2);  LOAD as skel_fi
+// Every wave runs the same number of iterations (barrier counts cannot differ); a pair that owns a graph less re-requests its last
+// one and stores nothing for it.
+template <int PLACE, int AHEAD, int LOAD>
+__global__ __launch_bounds__(512) void skel_fp(const float* __restrict__ x, const f4* __restrict__ cv, float* __restrict__ out, int T) {
+  __shared__ f4 at[4][512];               // 32 KiB
+  __shared__ f4 gt[4][2][512 + 128];      // 80 KiB: 112 KiB of the 160 KiB of a gfx950 CU
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int pair = PLACE ? wave >> 1 : wave & 3, role = PLACE ? wave & 1 : wave >> 2;      // role 0 = R, 1 = W
+  const int npairs = gridDim.x * 4;
+  const int t0 = blockIdx.x * 4 + pair;
+  const int cnt_max = (T - 1) / npairs + 1;
+  const int cnt = t0 < T ? (T - 1 - t0) / npairs + 1 : 0;
+  const int steps = (cnt_max + 1 + AHEAD - 1) / AHEAD * AHEAD;      // + 1: the writer runs one graph behind the reader
+  f4* ta = at[pair];
+  Standin sa(lane);
+  f4 r[AHEAD][8], c0[AHEAD], c1[AHEAD];
+#pragma unroll
+  for (int d = 0; d < AHEAD; ++d) { c0[d] = f4{0, 0, 0, 0}; c1[d] = f4{0, 0, 0, 0}; }
+  auto graph = [&](int k) { return cnt > 0 ? t0 + (k < cnt ? k : cnt - 1) * npairs : 0; };
+  auto issue = [&](int k, int slot) __attribute__((always_inline)) {
+    const int t = graph(k);
+    const f4* s = reinterpret_cast<const f4*>(x + (long)t * 2048);
+    const f4* c = cv + (long)t * 80;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) r[slot][q] = __builtin_nontemporal_load(s + lane + 64 * q);
+    c0[slot] = c[lane];
+    c1[slot] = lane < 16 ? c[64 + lane] : f4{0, 0, 0, 0};
+  };
+  // the roles run loops of their own, as in graphconv_bwd_pairs_kernel (one loop with role branches inside makes the reader's tile
+  // registers a merge of two paths, and the copies behind the merge wait for the loads just requested: s_waitcnt vmcnt(0) per graph)
+  if (!role) {
+#pragma unroll
+    for (int d = 0; d < AHEAD; ++d) issue(d, d);
+    for (int i = 0; i < steps; i += AHEAD) {
+#pragma unroll
+      for (int d = 0; d < AHEAD; ++d) {
+        f4* tg = gt[pair][(i + d) & 1];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) ta[lane + 64 * q] = r[d][q];    // land_tile
+        tg[512 + lane] = c0[d];                                     // CSR(i) -> the slice of buffer i & 1
+        if (lane < 16) tg[576 + lane] = c1[d];
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        issue(i + d + AHEAD, d);       // nothing that was loaded lives across the request: the loads land in the registers they left
+        f4 o[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) o[q] = ta[lane + 64 * q];       // the fragment reads
+        if constexpr (LOAD != 0) sa.mfmas();
+#pragma unroll
+        for (int q = 0; q < 8; ++q) tg[lane + 64 * q] = o[q];       // the product tile
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+      }
+    }
+  } else {
+    for (int i = 0; i < steps; ++i) {
+      if (i > 0) {
+        const f4* tp = gt[pair][(i - 1) & 1];
+        f4 o[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) o[q] = tp[lane + 64 * q] + tp[512 + ((q & 1) ? 64 + (lane & 15) : lane)];
+        if constexpr (LOAD != 0) sa.fmas();
+        if (i - 1 < cnt) {
+          f4* dst = reinterpret_cast<f4*>(out + (long)graph(i - 1) * 2048);
+#pragma unroll
+          for (int q = 0; q < 8; ++q) st16<1>(dst + lane + 64 * q, o[q]);
+        }
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    }
+  }
+  if constexpr (LOAD != 0) sa.keep(out, lane);
+}
+
 static float* X; static float* G; static float* DX; static f4* CV; static int T;
 template <typename L>
 static float timeit(L launch) {
@@ -593,7 +676,51 @@ int main(int argc, char** argv) {
   char nm[128];
   const bool ingest = argc > 2 && !strcmp(argv[2], "ingest");   // only the ingest arms, next to the best existing arm of each direction
   const bool dxstore = argc > 2 && !strcmp(argv[2], "dxstore");
-  if (dxstore) for (int rep = 0; rep < 3; ++rep) {
+  const bool fwdpairs = argc > 2 && !strcmp(argv[2], "fwdpairs");
+  if (fwdpairs) {
+    constexpr int NA = 10, NR = 3;
+    const char* names[NA] = {
+        "F   512-thread workgroup, kernel order, nt loads and stores (reference)",
+        "FP  pairs, roles on the same SIMD, reader 1 tile ahead",
+        "FP  pairs, roles on adjacent waves, reader 1 tile ahead",
+        "FP  pairs, roles on the same SIMD, reader 2 tiles ahead",
+        "FP  pairs, roles on adjacent waves, reader 2 tiles ahead",
+        "F   + 48 MFMAs + 400 FMAs per wave and graph (reference)",
+        "FP  + 48 MFMAs (reader) + 400 FMAs (writer), same SIMD, 1 ahead",
+        "FP  + 48 MFMAs (reader) + 400 FMAs (writer), adjacent waves, 1 ahead",
+        "FP  + 48 MFMAs (reader) + 400 FMAs (writer), same SIMD, 2 ahead",
+        "FP  + 48 MFMAs (reader) + 400 FMAs (writer), adjacent waves, 2 ahead"};
+    float ms[NA][NR];
+    for (int rep = 0; rep < NR; ++rep) {
+      int a = 0;
+#define FR(A_) ms[a][rep] = timeit([&] { hipLaunchKernelGGL((skel_fi<0, 1, 1, A_>), dim3(256), dim3(512), 0, 0, X, CV, DX, T); }); \
+    linef(names[a], ms[a][rep]); ++a
+#define FP(P_, D_, A_) ms[a][rep] = timeit([&] { hipLaunchKernelGGL((skel_fp<P_, D_, A_>), dim3(256), dim3(512), 0, 0, X, CV, DX, T); }); \
+    linef(names[a], ms[a][rep]); ++a
+      FR(0); FP(0, 1, 0); FP(1, 1, 0); FP(0, 2, 0); FP(1, 2, 0);
+      FR(1); FP(0, 1, 1); FP(1, 1, 1); FP(0, 2, 1); FP(1, 2, 1);
+#undef FR
+#undef FP
+    }
+    const hipError_t err = hipDeviceSynchronize();
+    if (err != hipSuccess) { printf("HIP error: %s\n", hipGetErrorString(err)); return 1; }
+    printf("median / min / max of the %d repetitions (ms)\n", NR);
+    float med[NA], spread = 0.f;
+    for (int a = 0; a < NA; ++a) {
+      float lo = ms[a][0], hi = ms[a][0], sum = 0.f;
+      for (int rep = 0; rep < NR; ++rep) { lo = ms[a][rep] < lo ? ms[a][rep] : lo; hi = ms[a][rep] > hi ? ms[a][rep] : hi; sum += ms[a][rep]; }
+      med[a] = sum - lo - hi;
+      if (a >= NA / 2 && hi - lo > spread) spread = hi - lo;
+      printf("  %-72s %.4f  %.4f  %.4f\n", names[a], med[a], lo, hi);
+    }
+    int best = NA / 2 + 1;
+    for (int a = NA / 2 + 1; a < NA; ++a) if (med[a] < med[best]) best = a;
+    const float gain = med[NA / 2] - med[best];
+    printf("gate: F beside the arithmetic %.4f ms, best pair arm %.4f ms (%s), difference %.4f ms, widest spread of the arms beside the\n"
+           "      arithmetic %.4f ms: the gate (difference > 2 x spread) %s\n",
+           med[NA / 2], med[best], names[best], gain, spread, gain > 2.f * spread ? "PASSES" : "FAILS");
+  }
+  else if (dxstore) for (int rep = 0; rep < 3; ++rep) {
 #define HD(S_, A_, F_, name) \
     line(name, timeit([&] { hipLaunchKernelGGL((skel_hi<0, 0, S_, A_, F_>), dim3(256), dim3(512), 0, 0, X, G, CV, DX, T); }))
     HD(0, 0, 0, "HI pairs, S0 8 x dwordx4, 32-byte segments (shipped)");
