@@ -407,21 +407,25 @@ struct Grp4 {
       fma4(a, val<3>(), x3);
     }
   }
+  // the group's sum started from +0 (what a row's second and later groups contribute): a different instruction sequence from fma()
+  __device__ __forceinline__ f32x4 sum0() const {
+    f32x4 a0 = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (LAY == LAY_UNIT) {
+      add4(a0, x0); add4(a0, x1); add4(a0, x2); add4(a0, x3);
+    } else {
+      fma4(a0, val<0>(), x0); fma4(a0, val<1>(), x1);
+      fma4(a0, val<2>(), x2); fma4(a0, val<3>(), x3);
+    }
+    return a0;
+  }
 };
-// The whole group k..k+3 at once.  The sum starts from +0: a different instruction sequence from Grp4::fma.
+// The whole group k..k+3 at once.
 template <int LAY>
 __device__ __forceinline__ f32x4 gather4(const int2* ecv, const float* ev, const float* srcl, int k) {
   Grp4<LAY> q;
   q.ecv(ecv, ev, k);
   q.tile(srcl);
-  f32x4 a0 = {0.f, 0.f, 0.f, 0.f};
-  if constexpr (LAY == LAY_UNIT) {
-    add4(a0, q.x0); add4(a0, q.x1); add4(a0, q.x2); add4(a0, q.x3);
-  } else {
-    fma4(a0, q.template val<0>(), q.x0); fma4(a0, q.template val<1>(), q.x1);
-    fma4(a0, q.template val<2>(), q.x2); fma4(a0, q.template val<3>(), q.x3);
-  }
-  return a0;
+  return q.sum0();
 }
 // Rows longer than 4 entries.  Rows are ordered by decreasing length in the slot table, so this fires only in the first
 // pass or two of a graph.
@@ -500,6 +504,68 @@ __device__ __forceinline__ void aggregate_rows_full2(const int2* ecv, const floa
     emit(rowb, cl, qb.a);
     __builtin_amdgcn_sched_barrier(0);
   }
+}
+
+// The same rows with the same sums, the chain cut at its head and G passes (4 G rows per lane group) in flight per scheduling
+// scope.  All eight slot words of the lane are read first, then behind ONE wait the first group (column word / pairs, values) of
+// all eight rows: two LDS round trips per graph where aggregate_rows_full2 walks two per stage.  A row's SECOND group no longer
+// waits for its first sum in the first NT passes (rows come by decreasing length: long rows sit there): where such a pass has a
+// row of more than four entries (the uniform ballot of grp_tail), the second groups of its rows are read with the first ones
+// and their neighbour rows gathered beside them.  A lane whose row has no second group re-reads its first group there (a valid
+// address) and its sum is dropped by a select, never added: no +0 term that would turn a -0 sum into +0, no row the sum must not
+// see.  Groups from the third on, and the later passes, keep grp_tail's loop.  The order of the additions of every row is that
+// of aggregate_rows_full.  mark(integral_constant<scope>) is called behind each scope (the cycle probe's stamps; empty otherwise).
+template <int LAY, int G, int NT, typename Emit, typename Mark>
+__device__ __forceinline__ void aggregate_rows_full4(const int2* ecv, const float* ev, const int* tab, const float* tile,
+                                                     int lane, Emit&& emit, Mark&& mark) {
+  static_assert((G == 4 || G == 8) && NT >= 0 && NT <= G, "passes per scheduling scope; the speculated passes lie in the first one");
+  const int sub = lane >> 4, cl = lane & 15;
+  const float* srcl = tile + cl * 4;
+  int sw[8], s[8], len[8], row[8];
+#pragma unroll
+  for (int p = 0; p < 8; ++p) sw[p] = tab[4 * p + sub];
+#pragma unroll
+  for (int p = 0; p < 8; ++p) unpack_slot(sw[p], s[p], len[p], row[p]);
+  Grp4<LAY> q[8], t[NT > 0 ? NT : 1];
+  bool tails[NT > 0 ? NT : 1];
+#pragma unroll
+  for (int p = 0; p < 8; ++p) q[p].ecv(ecv, ev, s[p]);
+#pragma unroll
+  for (int p = 0; p < NT; ++p) {
+    tails[p] = __builtin_amdgcn_ballot_w64(len[p] > 4) != 0;      // uniform
+    if (tails[p]) t[p].ecv(ecv, ev, len[p] > 4 ? s[p] + 4 : s[p]);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  static_for<8 / G>([&](auto hc) __attribute__((always_inline)) {
+    constexpr int h = decltype(hc)::value;
+    constexpr int NS = h == 0 ? NT : 0;                           // speculated passes of this scope
+#pragma unroll
+    for (int p = G * h; p < G * h + G; ++p) q[p].tile(srcl);
+#pragma unroll
+    for (int p = 0; p < NS; ++p)
+      if (tails[p]) t[p].tile(srcl);
+#pragma unroll
+    for (int p = G * h; p < G * h + G; ++p) q[p].fma();
+#pragma unroll
+    for (int p = 0; p < NS; ++p)
+      if (tails[p]) {
+        f32x4 a2 = q[p].a;
+        add4(a2, t[p].sum0());
+        const bool has2 = len[p] > 4;
+        q[p].a[0] = has2 ? a2[0] : q[p].a[0]; q[p].a[1] = has2 ? a2[1] : q[p].a[1];
+        q[p].a[2] = has2 ? a2[2] : q[p].a[2]; q[p].a[3] = has2 ? a2[3] : q[p].a[3];
+        if (__builtin_amdgcn_ballot_w64(len[p] > 8)) {            // groups from the third on
+          for (int k = 8; __builtin_amdgcn_ballot_w64(k < len[p]); k += 4)
+            if (k < len[p]) add4(q[p].a, gather4<LAY>(ecv, ev, srcl, s[p] + k));
+        }
+      }
+#pragma unroll
+    for (int p = G * h + NS; p < G * h + G; ++p) grp_tail<LAY>(q[p].a, s[p], len[p], ecv, ev, srcl);
+#pragma unroll
+    for (int p = G * h; p < G * h + G; ++p) emit(row[p], cl, q[p].a);
+    mark(hc);
+    __builtin_amdgcn_sched_barrier(0);
+  });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1642,6 +1708,9 @@ __global__ __launch_bounds__(256, 1) void graphconv_bwd_planes_kernel(
 //   * One scheduling scope spanned a role's row groups instead of one scope per group: within noise (2d).
 //   * A pair-local rendezvous with arrival counters in LDS replaced the workgroup barrier: 0.4965-0.4984 against 0.4944-0.4949 (2e).
 //   * KGCN_BWD_PAIRS=0, the one-wave-per-graph planes kernel for every batch: 0.497-0.510 against 0.475-0.485 ms in the same calls.
+// Measured beside the forward's aggregate_rows_full4 and not kept (profiles/fwd_chain_ab.txt, table 3): the slot and column words of
+// a role's four passes read up front and all four in flight: 244 registers and no scratch in the unit layout only (16 and 52 bytes
+// of scratch in the values and the row-padded layout); backward events 0.4492 against 0.4434 ms, the step 0.7270 against 0.7243.
 // Outside this kernel: the forward's second wave per SIMD started half a step late (same file, item 3: nothing), and the planes
 // kernel ran as k workgroups per CU slot, each with 1 / k of the graphs (profiles/r05_headline_experiments.txt: 3 - 13 % slower).
 // ------------------------------------------------------------------------------------------------
@@ -2067,7 +2136,8 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_pairs_kernel(
 //                                 load nobody uses reads W); CSR(i) -> slice i & 1; FW(i) = x(i) W + b (fwd_contract: the same
 //                                 products in the same order, the values of the next k-step read ahead) -> gather tile i & 1
 //   wave W (aggregator / writer)  one graph behind: out(i-1) = A(i-1) FW(i-1) out of gather tile and slice (i-1) & 1
-//                                 (aggregate_rows_full2: the same sums in the same order, two passes in flight), streaming stores
+//                                 (aggregate_rows_full4: the same sums in the same order, slot and column words of all rows read
+//                                 up front, all eight passes in flight; row-padded layout: aggregate_rows_full2), streaming stores
 // and ONE workgroup barrier per graph (bp_barrier: vector-memory operations stay in flight across it).  Wave R has only loads on
 // its vmcnt counter, wave W only stores.  Outputs are bit-identical to the one-wave kernel's.
 // Why (tools/bwd_skeleton.hip `fwdpairs`, profiles/fwd_pairs_skeleton.txt): as a byte pattern beside the arithmetic stand-ins the
@@ -2082,6 +2152,16 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_pairs_kernel(
 //     fragment reads of a k-step in front of its products): 0.3113-0.3164 against 0.3148-0.3196.  Two passes in flight: 0.3016;
 //     with the k-step read ahead as well: 0.2956 (shipped).
 //   * A reader two tiles ahead: slower than one tile ahead in the skeleton (0.299 / 0.311 against 0.288 / 0.311), not built.
+// The aggregator's chain (tools/fwd_pairs_probe.py, profiles/fwd_chain_probe.txt, profiles/fwd_chain_ab.txt): with two passes in
+// flight wave W aggregated for 5,040 of the 5,570 cycles of a step and wave R waited 1,360 cycles at the barrier: W bounds the step.
+// Forward events of one call, parent 0.2928 ms:
+//   * slot and column words up front, FOUR passes in flight, second groups of the first four passes beside the first ones: 0.2888;
+//     of the first two passes only (the benchmark's graphs have a row of more than four entries in pass 0 always, in pass 1 half
+//     the time, never later): 0.2859.
+//   * all EIGHT passes in flight: 0.2757 with the second groups of two passes, 0.2758 without (shipped: with; the values layout
+//     had 0.2934 against 0.2947).  Second groups of four passes beside eight passes in flight: scratch in the values layout, not run.
+//   * s_setprio 3 in wave W: slower in every form (two passes 0.2965, four 0.2849 against 0.2859, eight 0.2814 against 0.2757).
+//   * Wave R left as it was: it still waits about 1,000 cycles per graph at the barrier.
 // Iteration counts are uniform as in graphconv_bwd_pairs_kernel: the launcher guarantees every pair two graphs, a pair owns
 // cnt_max or cnt_max - 1 of them, every wave passes cnt_max barriers and the one graph a short pair lacks is skipped under a
 // uniform branch behind the loop.  No wave leaves before its last barrier.
@@ -2090,6 +2170,8 @@ __global__ __launch_bounds__(512, 2) void graphconv_bwd_pairs_kernel(
 // lag per pair) costs more than the pairing returns there.
 // ------------------------------------------------------------------------------------------------
 constexpr int FP_PAIRS = 4;
+constexpr int FP_AGG_SCOPE = 8;                   // aggregation passes in flight in wave W (aggregate_rows_full4)
+constexpr int FP_AGG_SPEC = 2;                    // leading passes whose second groups are gathered beside the first ones
 constexpr size_t FP_GT_FLOATS = (size_t)(FN + 1) * FD;
 __host__ __device__ inline size_t fwd_pairs_pair_bytes(int max_nnz) {
   return (size_t)A_FWD * 4 + 2 * FP_GT_FLOATS * 4 + 2 * (ecv_bytes(max_nnz) + RP_BYTES);
@@ -2122,6 +2204,7 @@ __global__ __launch_bounds__(512, 2) void graphconv_fwd_full_kernel(
   const int tl = t0 + (cntw - 1) * npairs;                        // its last graph
   const bool whole = cntw == cnt_max;                             // uniform
   auto gidx = [&](int k) { return graph_at(t0, npairs, tl, k); };
+  KP_DECL(8)
 
   if (role == 0) {
     // =========================================== wave R ===========================================================
@@ -2155,15 +2238,18 @@ __global__ __launch_bounds__(512, 2) void graphconv_fwd_full_kernel(
     auto multiply = [&](int cur) __attribute__((always_inline)) {
       f32x16 acc0, acc1;
       fwd_contract<true>(acc0, acc1, at, WF, w3, b0, b1, lane);
+      KP_STAMP(3)
       store_c_tiles(gt0 + cur * FP_GT_FLOATS, acc0, acc1, li, hi);
     };
     int cur = 0;
+    KP_STAMP(0)
     for (int i = 0; i < cnt_max - 1; ++i) {                       // graph i exists for every pair
       // x(i): registers -> A tile; x(i+1) in flight (branch-free; a short pair's last request reads the first 8 KB of W, unused)
       land_tile<true>(fx, at, ALD, 512, 16, lane);
       static_assert(FD * FD >= FN * FD, "W holds at least one tile's floats");
       issue_tile<true, true>(fx, i + 1 < cntw ? x + (long)gidx(i + 1) * N * D : w, 512, lane);
       wave_sync();
+      KP_STAMP(1)
       // CSR(i): registers -> slice `cur` (wave W read graph i - 2 out of it before the barrier this wave has just passed)
       land_csr_l(cur);
       const int base_n = meta_base(m_nxt), cnt_n = meta_cnt(m_nxt);
@@ -2172,10 +2258,13 @@ __global__ __launch_bounds__(512, 2) void graphconv_fwd_full_kernel(
       asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %3"
                    : "=&v"(m_cur.slot), "=&v"(m_cur.gp) : "v"(m_nxt.slot), "v"(m_nxt.gp));
       issue_meta_l<LAY>(m_nxt, slots, gptr, gidx(i + 2), N, lane);
+      KP_STAMP(2)
       multiply(cur);
+      KP_STAMP(4)
       base = base_n;
       cnt = cnt_n;
       bp_barrier();
+      KP_STAMP(5)
       cur ^= 1;
     }
     if (whole) {                                                  // graph cnt_max - 1: nothing left to request
@@ -2185,6 +2274,7 @@ __global__ __launch_bounds__(512, 2) void graphconv_fwd_full_kernel(
       multiply(cur);
     }
     bp_barrier();
+    KP_STAMP(6)
   } else {
     // =========================================== wave W ===========================================================
     __syncthreads();                                              // barrier 0: the W table
@@ -2192,19 +2282,30 @@ __global__ __launch_bounds__(512, 2) void graphconv_fwd_full_kernel(
       float* ot = out + (long)gidx(k) * N * D;
       const int2* ecv_c = ecv0 + cur * ecv_stride;
       const float* ev = reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(ecv_c) + cvals_off(max_nnz));
-      aggregate_rows_full2<LAY>(ecv_c, ev, tab0 + cur * (FN + 4), gt0 + cur * FP_GT_FLOATS, lane, [&](int r, int c4, f32x4 v) {
-        stv4_stream(ot + r * D + c4 * 4, v);
-      });
+      auto store = [&](int r, int c4, f32x4 v) { stv4_stream(ot + r * D + c4 * 4, v); };
+      // the row-padded layout holds 8 registers per group: its groups and rows in flight do not fit the 256 registers (scratch in the
+      // assembly from four passes on), so it keeps two passes in flight
+      if constexpr (LAY == LAY_PAD4) {
+        aggregate_rows_full2<LAY>(ecv_c, ev, tab0 + cur * (FN + 4), gt0 + cur * FP_GT_FLOATS, lane, store);
+        KP_STAMP(1)
+      } else {
+        aggregate_rows_full4<LAY, FP_AGG_SCOPE, FP_AGG_SPEC>(ecv_c, ev, tab0 + cur * (FN + 4), gt0 + cur * FP_GT_FLOATS, lane, store,
+          [&](auto hc) { if constexpr (decltype(hc)::value == 0) { KP_STAMP(1) } else { KP_STAMP(2) } });
+      }
     };
     bp_barrier();                                                 // FW(0) and CSR(0) are in buffer 0
     int cur = 0;
+    KP_STAMP(0)
     for (int i = 1; i < cnt_max; ++i) {                           // graph i - 1 exists for every pair
       aggregate(i - 1, cur);
       bp_barrier();
+      KP_STAMP(5)
       cur ^= 1;
     }
     if (whole) aggregate(cnt_max - 1, cur);
+    KP_STAMP(6)
   }
+  KP_FLUSH(g_probe, blockIdx.x * 8 + wave, 8)
 }
 
 // waves per block that fit the LDS budget (0 = does not fit at all)

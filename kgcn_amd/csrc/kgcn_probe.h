@@ -1,6 +1,6 @@
 // Cycle probe of the development builds (-DKGCN_PROBE; compiled out of the product library): a wave sums the cycles it spends
 // between consecutive stamps per phase and writes the sums to a device buffer that a tool under tools/ hands in and reads back
-// (phase_probe.py, pairs_probe.py, gemm3_probe.py, gemmh_probe.py, gemmh_fwd_probe.py, gemmb_probe.py).
+// (phase_probe.py, pairs_probe.py, fwd_pairs_probe.py, gemm3_probe.py, gemmh_probe.py, gemmh_fwd_probe.py, gemmb_probe.py).
 //   KP_BUFFER(name, setter)       the file's buffer pointer and the extern "C" entry point that sets it
 //   KP_DECL(n)                    n phase sums, the clock starts
 //   KP_STAMP(k)                   the cycles since the previous stamp belong to phase k
