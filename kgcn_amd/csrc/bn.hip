@@ -15,7 +15,7 @@
 
 namespace kgcn {
 
-constexpr int BN_BLOCKS = 1024;    // partial rows of the first reduction stage
+constexpr int BN_BLOCKS = 1024;    // partial rows of the first reduction stage (restated in tests/bn_cases.py: route())
 
 // MODE 0: acc0 = sum x                       (mean numerator)
 // MODE 1: acc0 = sum (x - mean)^2            (variance numerator)
@@ -208,7 +208,7 @@ __global__ __launch_bounds__(256) void bn_bwd_dx_kernel(const float* __restrict_
 
 static int bn_grid(long work) {
   long b = (work + 255) / 256;
-  if (b > (long)kNumCU * 16) b = (long)kNumCU * 16;
+  if (b > (long)kNumCU * 16) b = (long)kNumCU * 16;   // restated in tests/bn_cases.py: route()
   return b < 1 ? 1 : (int)b;
 }
 
@@ -270,12 +270,12 @@ static int bn_apply_impl(const float* x, int64_t graphs, int32_t n_nodes, int32_
     // fixed column group per thread (d / V <= 256 groups): V = 4, or 2 for even widths like the 50 of model.py / model_multitask.py
     const int V = vec ? 4 : ((d % 2 == 0) && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) % 8 == 0) ? 2 : 1);
     const int dv = d / V;
-    if (dv <= 256) {
+    if (dv <= 256) {                                   // restated in tests/bn_cases.py: route()
       int lg = 0;
       while ((1 << lg) < dv) ++lg;
       const int rpp = 256 >> lg;
       long nb = (rows + rpp - 1) / rpp;
-      if (nb > (long)kNumCU * 8) nb = (long)kNumCU * 8;
+      if (nb > (long)kNumCU * 8) nb = (long)kNumCU * 8;   // restated in tests/bn_cases.py: route()
       const dim3 grid((unsigned)(nb < 1 ? 1 : nb));
       if (V == 4)
         hipLaunchKernelGGL(bn_apply_cols_kernel<4>, grid, dim3(256), 0, as_stream(stream), x, rows, n_nodes, d, lg, enabled, mean,
