@@ -92,7 +92,10 @@ extern "C" {
  * Integrated gradients of the compound-protein interaction network added entry points only (version still 2): kgcn_cpi_ig_f32
  * (+ kgcn_cpi_ig_workspace_bytes).
  * Integrated gradients over the vector modality added entry points and a noise stream only (version still 2):
- * kgcn_ig_copies_expand_f32, kgcn_ig_copies_reduce_f32, KGCN_IG_STREAM_VECTOR. */
+ * kgcn_ig_copies_expand_f32, kgcn_ig_copies_reduce_f32, KGCN_IG_STREAM_VECTOR.
+ * The classical graph kernels added entry points only (version still 2): kgcn_wl_refine_i32, kgcn_wl_rank_i32
+ * (+ kgcn_wl_rank_workspace_bytes), kgcn_wl_runs_i32, kgcn_sp_features_i32 (+ kgcn_graph_runs_workspace_bytes), kgcn_gram_plan_i64,
+ * kgcn_gram_dense_f64 (+ kgcn_graph_gram_workspace_bytes), kgcn_gram_normalize_f64. */
 #define KGCN_HIP_ABI_VERSION 2
 
 /* Column index of the padding entries of a row-padded batch (see row_pad): they carry value 0 and
@@ -1055,6 +1058,59 @@ int kgcn_pair_rank_table_i32(const float* score, const int32_t* row, const int32
                              const int64_t* top_ratio, int32_t num_top, uint8_t* train_edge, uint8_t* test_edge, uint8_t* new_edge,
                              int64_t* score_ranking, int64_t* hits, int64_t* covered, void* workspace, int64_t workspace_bytes,
                              void* stream);
+
+/* -- classical graph kernels of graph_kernel/gk.py (csrc/graphkern.hip, kgcn_amd/graph_kernel.py) ------------------------------
+ * Weisfeiler-Lehman subtree and shortest-path features of a batch of graphs and the Gram matrix over them, integer-exact and
+ * bitwise reproducible.  a: a plain (row_pad == 0) square batch of T graphs x M padded rows; num_nodes [T]: rows >=
+ * num_nodes[t] do not exist; stored values are ignored and every stored entry is one edge occurrence (a repeated entry is a
+ * multi-edge); labels / colors [T*M]: dense ranks >= 0 (what rows that do not exist hold is not read as a colour of theirs).
+ * Every call is asynchronous on `stream`; workspaces are the caller's, sized by the *_workspace_bytes queries.
+ *
+ * Feature runs: (run_col, run_graph, run_count), one run per (feature column, graph) with a non-zero count.  kgcn_wl_runs_i32
+ * and kgcn_sp_features_i32 are called twice: with run_col == NULL they count the runs of every graph and write run_ptr [T + 1]
+ * (run_ptr[0] = 0, then the inclusive scan: run_ptr[T] is the total; needs the workspace of kgcn_graph_runs_workspace_bytes),
+ * with the three buffers (capacity entries each) they write graph t's runs from run_ptr[t] on in ascending column order and
+ * never past the capacity.
+ *
+ *   kgcn_wl_refine_i32   one refinement step, first half: sorted_nbr [nnz] receives every row's neighbour colours in ascending
+ *                        order (at the row's own rowptr range; any degree), key_hi / key_lo [T*M] a 128-bit mix of the row's
+ *                        signature (own colour, degree, multiset of neighbour colours), both words and-ed with hash_mask (all
+ *                        ones in production; a narrow mask forces collisions for tests).  Rows that do not exist: all ones.
+ *   kgcn_wl_rank_i32     second half: rows ordered by key (two stable 64-bit radix passes), a new colour wherever the key
+ *                        changes, dense colours by a scan -> new_colors [T*M] (-1 for rows that do not exist).  info[0] = the
+ *                        number of colours; info[1] = pairs of neighbours in that order with EQUAL keys whose true signatures
+ *                        (existence, own colour, degree, sorted list) differ: the partition is exact iff it is 0.
+ *   kgcn_wl_runs_i32     the colour histogram of every graph as runs, column = column_offset + colour (rows <= 4,096).
+ *   kgcn_sp_features_i32 unweighted all-pairs shortest paths (breadth-first search in LDS, one workgroup a graph) and the runs of
+ *                        the keys label_k << 20 | label_j << 8 | distance over ALL ordered pairs (k, j), k = j and unreachable
+ *                        pairs (distance 255) included.  Refuses M > 128 and num_labels > 4,096 (labels must be < num_labels).
+ *   kgcn_gram_plan_i64   sorts the runs by column; a column that occurs in one graph goes to an exact int64 diagonal sum of
+ *                        count^2 (integer atomics), the others get dense indices.  stats [3] = columns, one-graph columns, dense
+ *                        columns.  Leaves its plan in the workspace.
+ *   kgcn_gram_dense_f64  gram [G, G] from the plan in the SAME workspace (same runs, graphs, chunk_cols; dense_cols = stats[2]):
+ *                        the dense columns are laid out chunk_cols (a multiple of 16) at a time as [G_pad, chunk_cols] int32 counts
+ *                        and multiplied on v_mfma_f64_16x16x4_f64 into the upper-triangle tiles, mirrored on store; then the
+ *                        diagonal sums are added.  Sums of non-negative integers: exact below 2^53, in any order.  G <= 46,340.
+ *   kgcn_gram_normalize_f64  out_ij = gram_ij / sqrt(gram_ii * gram_jj), 0 where either diagonal entry is 0 (out != gram). */
+int kgcn_wl_refine_i32(const kgcn_csr_batch* a, const int32_t* num_nodes, const int32_t* colors, uint64_t hash_mask,
+                       int32_t* sorted_nbr, uint64_t* key_hi, uint64_t* key_lo, void* stream);
+int64_t kgcn_wl_rank_workspace_bytes(int64_t rows);
+int kgcn_wl_rank_i32(const kgcn_csr_batch* a, const int32_t* num_nodes, const int32_t* colors, const int32_t* sorted_nbr,
+                     const uint64_t* key_hi, const uint64_t* key_lo, int32_t* new_colors, int64_t* info, void* workspace,
+                     int64_t workspace_bytes, void* stream);
+int64_t kgcn_graph_runs_workspace_bytes(int32_t graphs);
+int kgcn_wl_runs_i32(const int32_t* colors, const int32_t* num_nodes, int32_t graphs, int32_t rows, uint64_t column_offset,
+                     int64_t* run_ptr, uint64_t* run_col, int32_t* run_graph, int32_t* run_count, int64_t capacity, void* workspace,
+                     int64_t workspace_bytes, void* stream);
+int kgcn_sp_features_i32(const kgcn_csr_batch* a, const int32_t* num_nodes, const int32_t* labels, int32_t num_labels,
+                         int64_t* run_ptr, uint64_t* run_col, int32_t* run_graph, int32_t* run_count, int64_t capacity,
+                         void* workspace, int64_t workspace_bytes, void* stream);
+int64_t kgcn_graph_gram_workspace_bytes(int64_t runs, int32_t graphs, int32_t chunk_cols);
+int kgcn_gram_plan_i64(const uint64_t* run_col, const int32_t* run_graph, const int32_t* run_count, int64_t runs, int32_t graphs,
+                       int32_t chunk_cols, int64_t* stats, void* workspace, int64_t workspace_bytes, void* stream);
+int kgcn_gram_dense_f64(const int32_t* run_graph, const int32_t* run_count, int64_t runs, int32_t graphs, int64_t dense_cols,
+                        int32_t chunk_cols, double* gram, void* workspace, int64_t workspace_bytes, void* stream);
+int kgcn_gram_normalize_f64(const double* gram, int32_t graphs, double* out, void* stream);
 
 /* -- k-fold cross-validation of the compound-protein interaction networks (gcn.py train_cv; csrc/cvloss.hip, csrc/cvmetrics.hip)
  * Loss head of sample_chem/compound-protein_interaction/multitask.py:53-86 (singletask.py: tasks = 1): logits [batch, 2, tasks],

@@ -3110,3 +3110,130 @@ def ig_copies_reduce(dY, Y, weights, scale=None, activation=None):
     check(lib.kgcn_ig_copies_reduce_f32(dY.data_ptr(), dY.stride(0) if rows else H, Y.data_ptr(), Y.stride(0) if rows else H, C, K, H,
                                         ptr(w), ptr(sc), int(act), ptr(S), current_stream()), "kgcn_ig_copies_reduce_f32")
     return S
+
+
+# -------------------------------------------------------------------------------------------------
+# classical graph kernels of graph_kernel/gk.py (csrc/graphkern.hip; the drivers are kgcn_amd/graph_kernel.py): colour
+# refinement, feature runs and the exact f64 Gram over them.  Read-outs: no autograd.  Integer-exact, bitwise reproducible.
+# -------------------------------------------------------------------------------------------------
+GRAM_CHUNK_COLS = 1024              # dense columns laid out per MFMA pass of gram_from_runs (a multiple of 16)
+HASH_MASK_FULL = (1 << 64) - 1
+
+
+def _ws_bytes(nbytes, what, device):
+    if nbytes < 0:
+        check(1, what)
+    return _lib.workspace(nbytes, device, torch.uint8), nbytes
+
+
+def _i32_dev(t, name, numel):
+    require_gpu(t, name)
+    if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != numel:
+        raise _lib.KgcnHipError("%s must be a contiguous int32 device tensor of %d elements, got %s %s"
+                                % (name, numel, t.dtype, tuple(t.shape)))
+    return t
+
+
+def _plain_square(csr, who):
+    if not isinstance(csr, BatchedCSR) or csr.row_pad != 0 or csr.rows != csr.cols:
+        raise _lib.KgcnHipError("%s takes a plain square BatchedCSR" % who)
+    return csr.num_graphs, csr.rows
+
+
+@torch.no_grad()
+def wl_refine(csr, num_nodes, colors, hash_mask=HASH_MASK_FULL):
+    """First half of one Weisfeiler-Lehman refinement -> (sorted_nbr [nnz] int32: every row's neighbour colours ascending,
+    key_hi, key_lo [T*M] int64 holding the two words of the 128-bit signature mix, and-ed with hash_mask)."""
+    T, M = _plain_square(csr, "wl_refine")
+    dev = csr.device
+    _i32_dev(num_nodes, "num_nodes", T), _i32_dev(colors, "colors", T * M)
+    sorted_nbr = torch.empty((max(csr.nnz, 1),), device=dev, dtype=torch.int32)
+    keys = torch.empty((2, max(T * M, 1)), device=dev, dtype=torch.int64)
+    check(lib.kgcn_wl_refine_i32(ctypes.byref(csr.desc()), ptr(num_nodes), ptr(colors), int(hash_mask) & HASH_MASK_FULL,
+                                 ptr(sorted_nbr), ptr(keys[0]), ptr(keys[1]), current_stream()), "kgcn_wl_refine_i32")
+    return sorted_nbr, keys[0], keys[1]
+
+
+@torch.no_grad()
+def wl_rank(csr, num_nodes, colors, sorted_nbr, key_hi, key_lo):
+    """Second half: dense colours of the key classes -> (new_colors [T*M] int32, -1 for rows that do not exist; info [2] int64
+    device tensor = number of colours, pairs of equal keys with different true signatures -- 0 iff the partition is exact)."""
+    T, M = _plain_square(csr, "wl_rank")
+    dev = csr.device
+    new = torch.empty((max(T * M, 1),), device=dev, dtype=torch.int32)
+    info = torch.empty((2,), device=dev, dtype=torch.int64)
+    ws, wsb = _ws_bytes(lib.kgcn_wl_rank_workspace_bytes(T * M), "kgcn_wl_rank_workspace_bytes", dev)
+    check(lib.kgcn_wl_rank_i32(ctypes.byref(csr.desc()), ptr(num_nodes), ptr(colors), ptr(sorted_nbr), ptr(key_hi), ptr(key_lo),
+                               ptr(new), ptr(info), ptr(ws), wsb, current_stream()), "kgcn_wl_rank_i32")
+    return new[:T * M], info
+
+
+def _two_pass_runs(call, T, dev, what):
+    """The count call, the read of the total, the emit call -> (run_col int64 (u64 bits), run_graph, run_count int32)."""
+    run_ptr = torch.empty((T + 1,), device=dev, dtype=torch.int64)
+    ws, wsb = _ws_bytes(lib.kgcn_graph_runs_workspace_bytes(T), "kgcn_graph_runs_workspace_bytes", dev)
+    check(call(run_ptr, None, None, None, 0, ws, wsb), what)
+    total = int(run_ptr[T].item())
+    col = torch.empty((max(total, 1),), device=dev, dtype=torch.int64)
+    graph = torch.empty((max(total, 1),), device=dev, dtype=torch.int32)
+    count = torch.empty((max(total, 1),), device=dev, dtype=torch.int32)
+    check(call(run_ptr, col, graph, count, total, ws, wsb), what)
+    return col[:total], graph[:total], count[:total]
+
+
+@torch.no_grad()
+def wl_runs(colors, num_nodes, T, M, column_offset):
+    """The colour histogram of every graph as feature runs, column = column_offset + colour."""
+    _i32_dev(num_nodes, "num_nodes", T), _i32_dev(colors, "colors", T * M)
+    return _two_pass_runs(lambda rp, c, g, n, cap, ws, wsb: lib.kgcn_wl_runs_i32(
+        ptr(colors), ptr(num_nodes), T, M, int(column_offset), ptr(rp), ptr(c), ptr(g), ptr(n), cap, ptr(ws), wsb,
+        current_stream()), T, colors.device, "kgcn_wl_runs_i32")
+
+
+@torch.no_grad()
+def sp_features(csr, num_nodes, labels, num_labels):
+    """Shortest-path feature runs: per graph the counts of (label_k, label_j, distance) over all ordered node pairs, k = j
+    and unreachable pairs (distance 255) included; column = label_k << 20 | label_j << 8 | distance."""
+    T, M = _plain_square(csr, "sp_features")
+    _i32_dev(num_nodes, "num_nodes", T), _i32_dev(labels, "labels", T * M)
+    return _two_pass_runs(lambda rp, c, g, n, cap, ws, wsb: lib.kgcn_sp_features_i32(
+        ctypes.byref(csr.desc()), ptr(num_nodes), ptr(labels), int(num_labels), ptr(rp), ptr(c), ptr(g), ptr(n), cap, ptr(ws),
+        wsb, current_stream()), T, csr.device, "kgcn_sp_features_i32")
+
+
+@torch.no_grad()
+def gram_from_runs(run_col, run_graph, run_count, G, chunk_cols=None, normalize=False, return_stats=False):
+    """K [G, G] float64 = F F^T of the count matrix the runs describe, exact (csrc/graphkern.hip: one-graph columns on an
+    int64 diagonal, the others through v_mfma_f64_16x16x4_f64, chunk_cols dense columns a pass).  normalize: K_ij /
+    sqrt(K_ii K_jj).  return_stats: also {"columns", "diag_columns", "dense_columns"}.  One read-back (the dense column count)."""
+    chunk_cols = GRAM_CHUNK_COLS if chunk_cols is None else int(chunk_cols)
+    n = int(run_col.numel())
+    dev = run_col.device
+    for t, name, dt in ((run_col, "run_col", torch.int64), (run_graph, "run_graph", torch.int32), (run_count, "run_count", torch.int32)):
+        require_gpu(t, name)
+        if t.dtype != dt or not t.is_contiguous() or t.numel() != n:
+            raise _lib.KgcnHipError("gram_from_runs: %s must be a contiguous %s device tensor of %d elements" % (name, dt, n))
+    ws, wsb = _ws_bytes(lib.kgcn_graph_gram_workspace_bytes(n, G, chunk_cols), "kgcn_graph_gram_workspace_bytes", dev)
+    stats = torch.empty((3,), device=dev, dtype=torch.int64)
+    check(lib.kgcn_gram_plan_i64(ptr(run_col) if n else None, ptr(run_graph) if n else None, ptr(run_count) if n else None, n, G,
+                                 chunk_cols, ptr(stats), ptr(ws), wsb, current_stream()), "kgcn_gram_plan_i64")
+    cols, diag_cols, dense_cols = stats.tolist()
+    K = torch.empty((G, G), device=dev, dtype=torch.float64)
+    check(lib.kgcn_gram_dense_f64(ptr(run_graph) if n else None, ptr(run_count) if n else None, n, G, dense_cols, chunk_cols, ptr(K),
+                                  ptr(ws), wsb, current_stream()), "kgcn_gram_dense_f64")
+    if normalize:
+        K = gram_normalize(K)
+    if return_stats:
+        return K, {"columns": cols, "diag_columns": diag_cols, "dense_columns": dense_cols}
+    return K
+
+
+@torch.no_grad()
+def gram_normalize(K):
+    """auxiliary_methods.normalize_gram_matrix in fp64 on the device: K_ij / sqrt(K_ii K_jj), 0 where a diagonal entry is 0."""
+    require_gpu(K, "gram")
+    if K.dtype != torch.float64 or K.dim() != 2 or K.shape[0] != K.shape[1] or not K.is_contiguous():
+        raise _lib.KgcnHipError("gram_normalize: a contiguous square float64 matrix is required, got %s %s" % (K.dtype, tuple(K.shape)))
+    out = torch.empty_like(K)
+    check(lib.kgcn_gram_normalize_f64(ptr(K), K.shape[0], ptr(out), current_stream()), "kgcn_gram_normalize_f64")
+    return out
