@@ -3,7 +3,10 @@
 //
 //   input    a plain (row_pad == 0) kgcn_csr_batch of T graphs x M padded rows, num_nodes [T] and dense-rank node labels [T*M].
 //            Rows >= num_nodes[t] do not exist; stored values are ignored, every stored entry is one edge occurrence (a repeated
-//            entry is a multi-edge); an entry whose column is no node of the graph is skipped.
+//            entry is a multi-edge).  An entry whose column is no node of its graph (num_nodes <= column < M) is not the same to
+//            the two feature kernels: the shortest-path search ignores it; the refinement counts it in the degree and takes the
+//            colour the colour array holds at that column, -1 from the drivers, into the signature.  GraphSet, the public driver,
+//            refuses such input; tests/test_gpu_graph_kernel_ops.py holds each kernel to its half (cases `directed`, wl_direct).
 //   runs     both feature kernels end in (column u64, graph i32, count i32), one run per (feature, graph) with a non-zero count.
 //            A call with run_col == NULL counts the runs of every graph and scans the counts into run_ptr [T + 1]; the call with
 //            the buffers writes graph t's runs at run_ptr[t], in ascending column order: no atomics, the list is reproducible.
@@ -134,9 +137,13 @@ __device__ __forceinline__ bool row_exists(const RankArgs& a, uint32_t row) {
   return (int)(row - t * (uint32_t)a.M) < a.num_nodes[t];
 }
 
-// true signatures of two rows: existence, own colour, degree, sorted neighbour colours
+// true signatures of two rows: existence, own colour, degree, sorted neighbour colours.  Two rows that do not exist are one
+// signature whatever the batch stores in them (entries, a colour): they share the all-ones key and get no colour.
 __device__ bool same_signature(const RankArgs& a, uint32_t x, uint32_t y) {
-  if (row_exists(a, x) != row_exists(a, y) || a.colors[x] != a.colors[y]) return false;
+  const bool ex = row_exists(a, x);
+  if (ex != row_exists(a, y)) return false;
+  if (!ex) return true;
+  if (a.colors[x] != a.colors[y]) return false;
   const int bx = a.rowptr[x], by = a.rowptr[y], d = a.rowptr[x + 1] - bx;
   if (a.rowptr[y + 1] - by != d) return false;
   for (int e = 0; e < d; ++e)
