@@ -95,7 +95,11 @@ extern "C" {
  * kgcn_ig_copies_expand_f32, kgcn_ig_copies_reduce_f32, KGCN_IG_STREAM_VECTOR.
  * The classical graph kernels added entry points only (version still 2): kgcn_wl_refine_i32, kgcn_wl_rank_i32
  * (+ kgcn_wl_rank_workspace_bytes), kgcn_wl_runs_i32, kgcn_sp_features_i32 (+ kgcn_graph_runs_workspace_bytes), kgcn_gram_plan_i64,
- * kgcn_gram_dense_f64 (+ kgcn_graph_gram_workspace_bytes), kgcn_gram_normalize_f64. */
+ * kgcn_gram_dense_f64 (+ kgcn_graph_gram_workspace_bytes), kgcn_gram_normalize_f64.
+ * The hash graph kernels added entry points only (version still 2): kgcn_attr_scale_f64 (+ kgcn_attr_scale_workspace_bytes),
+ * kgcn_lsh_buckets_f64, kgcn_rank_pairs_i64 (+ kgcn_rank_pairs_workspace_bytes), kgcn_wl_refine_copies_i32, kgcn_wl_rank_copies_i32
+ * (+ kgcn_wl_rank_copies_workspace_bytes), kgcn_wl_runs_copies_i32, kgcn_sp_features_copies_i32
+ * (+ kgcn_graph_runs_copies_workspace_bytes). */
 #define KGCN_HIP_ABI_VERSION 2
 
 /* Column index of the padding entries of a row-padded batch (see row_pad): they carry value 0 and
@@ -1111,6 +1115,61 @@ int kgcn_gram_plan_i64(const uint64_t* run_col, const int32_t* run_graph, const 
 int kgcn_gram_dense_f64(const int32_t* run_graph, const int32_t* run_count, int64_t runs, int32_t graphs, int64_t dense_cols,
                         int32_t chunk_cols, double* gram, void* workspace, int64_t workspace_bytes, void* stream);
 int kgcn_gram_normalize_f64(const double* gram, int32_t graphs, double* out, void* stream);
+
+/* -- hash graph kernels for continuous node attributes (csrc/hashkern.hip, kgcn_amd/graph_kernel.py hash_graph_kernel) ----------
+ * graph_kernel/graphkernel/hash_graph_kernel.py of the reference: the attribute rows of all existing nodes, x [rows, d] fp64 in
+ * graph order, are scaled, projected on R random directions and cut into buckets; the classical kernels above then run on R
+ * colourings of the same graphs at once.  fp64 and integers, no float atomics: bitwise reproducible.  Asynchronous on `stream`.
+ *
+ *   kgcn_attr_scale_f64  scaled [rows, d], mean [d], std_dev [d] (population): per column the rows are added one after another in
+ *                        ascending order inside chunks of 256 rows, then the chunk sums in ascending chunk order, every sum from
+ *                        +0.0; mean = sum / rows; the same two stages over (x - mean) * (x - mean); std_dev = sqrt(sum / rows);
+ *                        scaled = (x - mean) / (std_dev == 0 ? 1 : std_dev).  No operation is fused.  1 <= d <= KGCN_LSH_MAX_DIM.
+ *   kgcn_lsh_buckets_f64 bucket [draws, rows] = floor((x . v_r + b_r) / w): v [draws, d], b [draws] on the device, bin_width one
+ *                        HOST value w > 0; acc = 0, acc = acc + x_k * v_rk for k ascending, unfused.  errors [1] (device) counts
+ *                        the values that are not finite or not below 2^62 in magnitude (their bucket is written as 0): the caller
+ *                        refuses a non-zero count, nothing wraps.  Every attribute row is read once for all draws.
+ *   kgcn_rank_pairs_i64  ranks [n] = the dense rank of (hi, lo) among the distinct pairs in ascending signed order (numpy's
+ *                        unique(..., return_inverse) of the pairs), by two stable 64-bit radix passes as kgcn_wl_rank_i32.  mark
+ *                        NULL or [n]: a row with mark < 0 does not exist, takes no part and gets -1.  info[0] = the number of
+ *                        classes, info[1] = existing rows with hi = 2^63 - 1, which cannot be told from missing rows: refuse.
+ *
+ * R colourings ("copies") of the same T graphs over ONE stored batch: colors / labels / new_colors / key_hi / key_lo are
+ * [copies, T*M], row c * T*M + p reading rowptr / cv of row p; sorted_nbr is [copies, nnz].  One launch sequence and one info
+ * serve all copies.  kgcn_wl_rank_copies_i32 ranks all copies together: where the initial colours of different copies are
+ * disjoint (the ranks of (copy, bucket)) every signature holds its copy's own colour, so the copies never share a colour and each
+ * copy's partition is the one its own refinement gives.  The runs are written in slot order, slot = c * T + t (all graphs of copy
+ * 0, then copy 1, ...): run_ptr is [copies * T + 1], run_graph holds t, and
+ *   kgcn_wl_runs_copies_i32      column = column_offset + c * column_stride + colour
+ *                                (the driver: offset = iteration << 32, stride = (iterations + 1) << 32);
+ *   kgcn_sp_features_copies_i32  column = c << 32 | key; the breadth-first searches of a graph run once and their distance bytes stay
+ *                                in LDS while the keys of every copy are built, sorted and run-length encoded.  M <= 128 and
+ *                                labels < num_labels <= 4,096 in every copy.
+ * copies >= 1, copies * T * M < 2^31 - 1 (refused beyond: positions and colours are int32).  Workspaces: those of the plain kernels
+ * for copies * T*M rows and copies * T slots, kgcn_wl_rank_copies_workspace_bytes(T*M, copies) and
+ * kgcn_graph_runs_copies_workspace_bytes(T, copies). */
+enum { KGCN_LSH_MAX_DIM = 4096 };   /* attributes a row: a staged row of d | 1 doubles leaves a workgroup at least one in 64 KB */
+int64_t kgcn_attr_scale_workspace_bytes(int64_t rows, int32_t d);
+int kgcn_attr_scale_f64(const double* x, int64_t rows, int32_t d, double* scaled, double* mean, double* std_dev, void* workspace,
+                        int64_t workspace_bytes, void* stream);
+int kgcn_lsh_buckets_f64(const double* scaled, int64_t rows, int32_t d, const double* v, const double* b, int32_t draws,
+                         const double* bin_width, int64_t* bucket, int64_t* errors, void* stream);
+int64_t kgcn_rank_pairs_workspace_bytes(int64_t n);
+int kgcn_rank_pairs_i64(const int64_t* hi, const int64_t* lo, const int32_t* mark, int64_t n, int32_t* ranks, int64_t* info,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+int kgcn_wl_refine_copies_i32(const kgcn_csr_batch* a, const int32_t* num_nodes, const int32_t* colors, int32_t copies,
+                              uint64_t hash_mask, int32_t* sorted_nbr, uint64_t* key_hi, uint64_t* key_lo, void* stream);
+int64_t kgcn_wl_rank_copies_workspace_bytes(int64_t rows, int32_t copies);
+int kgcn_wl_rank_copies_i32(const kgcn_csr_batch* a, const int32_t* num_nodes, const int32_t* colors, int32_t copies,
+                            const int32_t* sorted_nbr, const uint64_t* key_hi, const uint64_t* key_lo, int32_t* new_colors,
+                            int64_t* info, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t kgcn_graph_runs_copies_workspace_bytes(int32_t graphs, int32_t copies);
+int kgcn_wl_runs_copies_i32(const int32_t* colors, const int32_t* num_nodes, int32_t graphs, int32_t rows, int32_t copies,
+                            uint64_t column_offset, uint64_t column_stride, int64_t* run_ptr, uint64_t* run_col, int32_t* run_graph,
+                            int32_t* run_count, int64_t capacity, void* workspace, int64_t workspace_bytes, void* stream);
+int kgcn_sp_features_copies_i32(const kgcn_csr_batch* a, const int32_t* num_nodes, const int32_t* labels, int32_t copies,
+                                int32_t num_labels, int64_t* run_ptr, uint64_t* run_col, int32_t* run_graph, int32_t* run_count,
+                                int64_t capacity, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* -- k-fold cross-validation of the compound-protein interaction networks (gcn.py train_cv; csrc/cvloss.hip, csrc/cvmetrics.hip)
  * Loss head of sample_chem/compound-protein_interaction/multitask.py:53-86 (singletask.py: tasks = 1): logits [batch, 2, tasks],

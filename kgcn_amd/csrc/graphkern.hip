@@ -32,15 +32,14 @@
 //            mirrored on store.  All summands are non-negative integers, so every partial sum is exact below 2^53: the result
 //            has the bits of the reference's float64 csr.dot, in any order.  No float atomics.
 //   norm     K_ij / sqrt(K_ii K_jj), 0 where a diagonal entry is 0: one f64 product, one correctly rounded sqrt and division.
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-
-#include "kgcn_common.h"
+//   copies   refine, rank, wl runs and sp also serve `copies` colourings of the same graphs in one launch sequence (graphkern.h;
+//            the hash graph kernels of hashkern.hip): colours [copies, T*M] over the one stored batch.  Copies whose initial
+//            colours are disjoint stay apart in the one global ranking.  copies == 1 is the plain kernel, bit for bit.
+#include "graphkern.h"
 
 namespace kgcn {
 namespace {
 
-typedef unsigned long long u64;
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kGroup = 8;            // lanes that share a row in the refinement
@@ -51,8 +50,6 @@ constexpr int kTile = 64;            // Gram tile edge of a workgroup
 constexpr int kKc = 16;              // columns staged per step; chunk_cols is a multiple of it
 constexpr int kLd = kKc + 1;
 
-__host__ __device__ __forceinline__ size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 __device__ __forceinline__ u64 mix64(u64 x) {
   x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
   x ^= x >> 27; x *= 0x94d049bb133111ebull;
@@ -62,20 +59,23 @@ __device__ __forceinline__ u64 mix64(u64 x) {
 // ---- refinement ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void wl_refine_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ cv,
                                                         const int32_t* __restrict__ num_nodes, const int32_t* __restrict__ colors,
-                                                        int T, int M, u64 mask, int32_t* __restrict__ sorted,
-                                                        u64* __restrict__ key_hi, u64* __restrict__ key_lo) {
-  const long row = ((long)blockIdx.x * 256 + threadIdx.x) / kGroup, rows = (long)T * M;
+                                                        int T, int M, int copies, long nnz, u64 mask,
+                                                        int32_t* __restrict__ sorted, u64* __restrict__ key_hi,
+                                                        u64* __restrict__ key_lo) {
+  const long row = ((long)blockIdx.x * 256 + threadIdx.x) / kGroup, stored = (long)T * M, rows = copies * stored;
   const int sub = threadIdx.x & (kGroup - 1);
   const bool in = row < rows;
   int beg = 0, deg = 0;
-  long base = 0;
+  long base = 0, out = 0;                                    // of the copy's colours of this graph, of its sorted lists
   bool exists = false;
   if (in) {
-    const int t = (int)(row / M);
-    base = (long)t * M;
-    exists = (int)(row - base) < num_nodes[t];
-    beg = rowptr[row];
-    deg = rowptr[row + 1] - beg;
+    const long c = copies > 1 ? row / stored : 0, p = row - c * stored;
+    const int t = (int)(p / M);
+    base = c * stored + (long)t * M;
+    out = c * nnz;
+    exists = (int)(p - (long)t * M) < num_nodes[t];
+    beg = rowptr[p];
+    deg = rowptr[p + 1] - beg;
   }
   auto colour_of = [&](int e) -> int32_t {
     const int32_t c = cv[2 * (long)(beg + e)];
@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void wl_refine_kernel(const int32_t* __restric
       const int32_t cq = colour_of(q);
       pos += (cq < c || (cq == c && q < e)) ? 1 : 0;
     }
-    sorted[beg + pos] = c;
+    sorted[out + beg + pos] = c;
     s1 += mix64((u64)(uint32_t)c + 0x9e3779b97f4a7c15ull);
     s2 += mix64(((u64)(uint32_t)c << 1 | 1ull) * 0xd6e8feb86659fd93ull);
   }
@@ -105,17 +105,6 @@ __global__ __launch_bounds__(256) void wl_refine_kernel(const int32_t* __restric
   }
 }
 
-__global__ __launch_bounds__(256) void iota_kernel(uint32_t* __restrict__ idx, long n) {
-  const long p = (long)blockIdx.x * 256 + threadIdx.x;
-  if (p < n) idx[p] = (uint32_t)p;
-}
-
-__global__ __launch_bounds__(256) void gather_u64_kernel(const u64* __restrict__ src, const uint32_t* __restrict__ idx,
-                                                         u64* __restrict__ dst, long n) {
-  const long p = (long)blockIdx.x * 256 + threadIdx.x;
-  if (p < n) dst[p] = src[idx[p]];
-}
-
 struct RankArgs {
   const int32_t* rowptr;
   const int32_t* num_nodes;
@@ -128,13 +117,15 @@ struct RankArgs {
   const int* pos;
   int32_t* out;
   u64* info;                         // colours, mismatches
-  long n;
+  long n;                            // copies * stored
+  long nnz;
+  uint32_t stored;                   // T * M
   int M;
 };
 
 __device__ __forceinline__ bool row_exists(const RankArgs& a, uint32_t row) {
-  const uint32_t t = row / (uint32_t)a.M;
-  return (int)(row - t * (uint32_t)a.M) < a.num_nodes[t];
+  const uint32_t p = row % a.stored, t = p / (uint32_t)a.M;
+  return (int)(p - t * (uint32_t)a.M) < a.num_nodes[t];
 }
 
 // true signatures of two rows: existence, own colour, degree, sorted neighbour colours.  Two rows that do not exist are one
@@ -144,10 +135,12 @@ __device__ bool same_signature(const RankArgs& a, uint32_t x, uint32_t y) {
   if (ex != row_exists(a, y)) return false;
   if (!ex) return true;
   if (a.colors[x] != a.colors[y]) return false;
-  const int bx = a.rowptr[x], by = a.rowptr[y], d = a.rowptr[x + 1] - bx;
-  if (a.rowptr[y + 1] - by != d) return false;
+  const uint32_t cx = x / a.stored, px = x - cx * a.stored, cy = y / a.stored, py = y - cy * a.stored;
+  const int bx = a.rowptr[px], by = a.rowptr[py], d = a.rowptr[px + 1] - bx;
+  if (a.rowptr[py + 1] - by != d) return false;
+  const int32_t *sx = a.sorted + cx * a.nnz + bx, *sy = a.sorted + cy * a.nnz + by;
   for (int e = 0; e < d; ++e)
-    if (a.sorted[bx + e] != a.sorted[by + e]) return false;
+    if (sx[e] != sy[e]) return false;
   return true;
 }
 
@@ -174,17 +167,17 @@ __global__ __launch_bounds__(256) void wl_colour_kernel(RankArgs a) {
 
 // ---- runs of a sorted key list in LDS -----------------------------------------------------------------------------------------
 struct RunOut {
-  long long* counts;                 // count mode: runs of graph t
+  long long* counts;                 // count mode: runs of every slot
   const long long* run_ptr;          // emit mode
   u64* col;
   int32_t* graph;
   int32_t* count;
   long long capacity;
-  u64 offset;
+  u64 offset, stride;                // column = offset + copy * stride + key
 };
 
-// s [n] ascending in LDS; part [256] LDS scratch.  All 256 threads call.
-__device__ void emit_runs(const uint32_t* s, int n, int t, const RunOut& o, int* part) {
+// s [n] ascending in LDS; part [256] LDS scratch.  All 256 threads call.  slot = copy * T + t.
+__device__ void emit_runs(const uint32_t* s, int n, int slot, int t, u64 offset, const RunOut& o, int* part) {
   const int tid = threadIdx.x, per = (n + 255) / 256, lo = min(n, tid * per), hi = min(n, lo + per);
   int heads = 0;
   for (int p = lo; p < hi; ++p) heads += (p == 0 || s[p] != s[p - 1]) ? 1 : 0;
@@ -193,10 +186,10 @@ __device__ void emit_runs(const uint32_t* s, int n, int t, const RunOut& o, int*
   int k = 0;
   for (int q = 0; q < tid; ++q) k += part[q];
   if (!o.col) {
-    if (tid == 255) o.counts[t] = (long long)(k + heads);
+    if (tid == 255) o.counts[slot] = (long long)(k + heads);
     return;
   }
-  const long long base = o.run_ptr[t];
+  const long long base = o.run_ptr[slot];
   for (int p = lo; p < hi; ++p) {
     if (p != 0 && s[p] == s[p - 1]) continue;
     const uint32_t v = s[p];
@@ -208,7 +201,7 @@ __device__ void emit_runs(const uint32_t* s, int n, int t, const RunOut& o, int*
     }
     const long long at = base + k++;
     if (at < o.capacity) {
-      o.col[at] = o.offset + (u64)v;
+      o.col[at] = offset + (u64)v;
       o.graph[at] = t;
       o.count[at] = a - p;
     }
@@ -216,12 +209,12 @@ __device__ void emit_runs(const uint32_t* s, int n, int t, const RunOut& o, int*
 }
 
 __global__ __launch_bounds__(256) void wl_runs_kernel(const int32_t* __restrict__ colors, const int32_t* __restrict__ num_nodes,
-                                                      int M, RunOut o) {
+                                                      int T, int M, RunOut o) {
   extern __shared__ uint32_t lds[];
   __shared__ int part[256];
   uint32_t *cs = lds, *ss = lds + M;
-  const int t = blockIdx.x, tid = threadIdx.x, n = max(0, min(M, num_nodes[t]));
-  for (int i = tid; i < n; i += 256) cs[i] = (uint32_t)colors[(long)t * M + i];
+  const int slot = blockIdx.x, c = slot / T, t = slot - c * T, tid = threadIdx.x, n = max(0, min(M, num_nodes[t]));
+  for (int i = tid; i < n; i += 256) cs[i] = (uint32_t)colors[(long)slot * M + i];
   __syncthreads();
   for (int i = tid; i < n; i += 256) {
     const uint32_t c = cs[i];
@@ -230,13 +223,13 @@ __global__ __launch_bounds__(256) void wl_runs_kernel(const int32_t* __restrict_
     ss[pos] = c;
   }
   __syncthreads();
-  emit_runs(ss, n, t, o, part);
+  emit_runs(ss, n, slot, t, o.offset + (u64)c * o.stride, o, part);
 }
 
 // ---- shortest-path features -------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void sp_features_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ cv,
                                                           const int32_t* __restrict__ num_nodes, const int32_t* __restrict__ labels,
-                                                          int M, int key_words, RunOut o) {
+                                                          int M, int copies, int key_words, RunOut o) {
   extern __shared__ uint32_t lds[];                            // all of it dynamic: the opt-in to the full LDS leaves no room
   uint32_t* keys = lds;                                        // for a static array beside it.  [key_words]; the queues of
   int* part = reinterpret_cast<int*>(lds + key_words);         // the search live in the keys first
@@ -266,30 +259,35 @@ __global__ __launch_bounds__(256) void sp_features_kernel(const int32_t* __restr
   __syncthreads();
   int np2 = 1;
   while (np2 < nn) np2 <<= 1;                                  // <= key_words: the host sized it for M
-  for (int i = tid; i < np2; i += 256) {
-    uint32_t key = 0xffffffffu;
-    if (i < nn) {
-      const int k = i / n, j = i - k * n;
-      key = ((uint32_t)labels[base + k] & 0xfffu) << 20 | ((uint32_t)labels[base + j] & 0xfffu) << 8 | (uint32_t)dist[i];
+  const int T = gridDim.x;
+  for (int c = 0; c < copies; ++c) {                           // the distances stay; the keys, their sort and the runs per copy
+    const int32_t* lab = labels + ((long)c * T + t) * M;
+    for (int i = tid; i < np2; i += 256) {
+      uint32_t key = 0xffffffffu;
+      if (i < nn) {
+        const int k = i / n, j = i - k * n;
+        key = ((uint32_t)lab[k] & 0xfffu) << 20 | ((uint32_t)lab[j] & 0xfffu) << 8 | (uint32_t)dist[i];
+      }
+      keys[i] = key;
     }
-    keys[i] = key;
-  }
-  __syncthreads();
-  for (int k = 2; k <= np2; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < np2; i += 256) {
-        const int x = i ^ j;
-        if (x > i) {
-          const uint32_t a = keys[i], b = keys[x];
-          if ((a > b) == ((i & k) == 0)) {
-            keys[i] = b;
-            keys[x] = a;
+    __syncthreads();
+    for (int k = 2; k <= np2; k <<= 1)
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        for (int i = tid; i < np2; i += 256) {
+          const int x = i ^ j;
+          if (x > i) {
+            const uint32_t a = keys[i], b = keys[x];
+            if ((a > b) == ((i & k) == 0)) {
+              keys[i] = b;
+              keys[x] = a;
+            }
           }
         }
+        __syncthreads();
       }
-      __syncthreads();
-    }
-  emit_runs(keys, nn, t, o, part);
+    emit_runs(keys, nn, c * T + t, t, (u64)c << 32, o, part);
+    __syncthreads();                                           // the next copy rewrites keys and part
+  }
 }
 
 // ---- Gram -------------------------------------------------------------------------------------------------------------------
@@ -429,61 +427,11 @@ __global__ __launch_bounds__(256) void gram_normalize_kernel(const double* __res
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
-size_t sort_temp_bytes(size_t n) {
-  size_t b = 0;
-  (void)rocprim::radix_sort_pairs(nullptr, b, (u64*)nullptr, (u64*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, n, 0u, 64u,
-                                  (hipStream_t)0);
-  return b;
-}
-size_t scan_temp_bytes(size_t n) {
-  size_t b = 0;
-  (void)rocprim::inclusive_scan(nullptr, b, (int*)nullptr, (int*)nullptr, n, rocprim::plus<int>(), (hipStream_t)0);
-  return b;
-}
 size_t scan64_temp_bytes(size_t n) {
   size_t b = 0;
   (void)rocprim::inclusive_scan(nullptr, b, (long long*)nullptr, (long long*)nullptr, n, rocprim::plus<long long>(), (hipStream_t)0);
   return b;
 }
-inline unsigned blocks_of(long n) { return (unsigned)((n + 255) / 256); }
-
-struct Taker {
-  unsigned char* base;
-  size_t off = 0;
-  template <typename T>
-  T* take(size_t count) {
-    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off += al256(count * sizeof(T));
-    return p;
-  }
-};
-unsigned char* aligned_base(void* ws) { return reinterpret_cast<unsigned char*>(al256(reinterpret_cast<size_t>(ws))); }
-
-struct RankLayout {
-  uint32_t *idx0, *idx1, *idx2;
-  u64 *lo_s, *hi_g, *hi_s;
-  int *flags, *pos;
-  void* temp;
-  size_t temp_bytes, total;
-};
-RankLayout rank_layout(unsigned char* base, size_t n) {
-  RankLayout o{};
-  Taker t{base};
-  o.idx0 = t.take<uint32_t>(n);
-  o.idx1 = t.take<uint32_t>(n);
-  o.idx2 = t.take<uint32_t>(n);
-  o.lo_s = t.take<u64>(n);
-  o.hi_g = t.take<u64>(n);
-  o.hi_s = t.take<u64>(n);
-  o.flags = t.take<int>(n);
-  o.pos = t.take<int>(n);
-  const size_t a = n ? sort_temp_bytes(n) : 0, b = n ? scan_temp_bytes(n) : 0;
-  o.temp_bytes = a > b ? a : b;
-  o.temp = t.take<unsigned char>(o.temp_bytes);
-  o.total = t.off + 256;
-  return o;
-}
-
 struct RunsLayout {
   long long* counts;
   void* temp;
@@ -565,38 +513,37 @@ int check_runs_args(const char* who, int64_t* run_ptr, uint64_t* run_col, int32_
 }
 
 }  // namespace
-}  // namespace kgcn
 
-using namespace kgcn;
+// ---- the launchers graphkern.h declares -----------------------------------------------------------------------------------------
+int check_copies(const char* who, const kgcn_csr_batch* a, int32_t copies) {
+  if (copies < 1) return fail("%s: %d copies", who, copies);
+  if ((int64_t)copies * a->num_graphs * a->rows >= (int64_t)INT32_MAX)
+    return fail("%s: %d copies x %d graphs x %d rows: positions and colours are int32, up to 2^31-2 rows in all", who, copies,
+                a->num_graphs, a->rows);
+  if ((int64_t)copies * a->num_graphs >= (int64_t)INT32_MAX) return fail("%s: %d copies x %d graphs of run slots", who, copies, a->num_graphs);
+  return 0;
+}
 
-extern "C" int kgcn_wl_refine_i32(const kgcn_csr_batch* a, const int32_t* num_nodes, const int32_t* colors, uint64_t hash_mask,
-                                  int32_t* sorted_nbr, uint64_t* key_hi, uint64_t* key_lo, void* stream) {
-  const char* who = "kgcn_wl_refine_i32";
+int wl_refine_run(const char* who, const kgcn_csr_batch* a, const int32_t* num_nodes, const int32_t* colors, int copies,
+                  uint64_t hash_mask, int32_t* sorted_nbr, uint64_t* key_hi, uint64_t* key_lo, void* stream) {
   if (int rc = check_graph_batch(who, a, num_nodes, colors)) return rc;
+  if (int rc = check_copies(who, a, copies)) return rc;
   if (!key_hi || !key_lo || (a->nnz > 0 && !sorted_nbr)) return fail("%s: NULL output", who);
-  const long rows = (long)a->num_graphs * a->rows;
+  const long rows = (long)copies * a->num_graphs * a->rows;
   if (rows == 0) return 0;
   hipLaunchKernelGGL(wl_refine_kernel, dim3(blocks_of(rows * kGroup)), dim3(256), 0, as_stream(stream), a->rowptr, a->cv, num_nodes,
-                     colors, a->num_graphs, a->rows, (u64)hash_mask, sorted_nbr, reinterpret_cast<u64*>(key_hi),
+                     colors, a->num_graphs, a->rows, copies, (long)a->nnz, (u64)hash_mask, sorted_nbr, reinterpret_cast<u64*>(key_hi),
                      reinterpret_cast<u64*>(key_lo));
   return check_launch(who);
 }
 
-extern "C" int64_t kgcn_wl_rank_workspace_bytes(int64_t rows) {
-  if (rows < 0 || rows >= (int64_t)INT32_MAX) {
-    fail("kgcn_wl_rank_workspace_bytes: %lld rows outside 0..2^31-2", (long long)rows);
-    return -1;
-  }
-  return (int64_t)rank_layout(nullptr, (size_t)rows).total;
-}
-
-extern "C" int kgcn_wl_rank_i32(const kgcn_csr_batch* a, const int32_t* num_nodes, const int32_t* colors, const int32_t* sorted_nbr,
-                                const uint64_t* key_hi, const uint64_t* key_lo, int32_t* new_colors, int64_t* info, void* workspace,
-                                int64_t workspace_bytes, void* stream) {
-  const char* who = "kgcn_wl_rank_i32";
+int wl_rank_run(const char* who, const kgcn_csr_batch* a, const int32_t* num_nodes, const int32_t* colors, int copies,
+                const int32_t* sorted_nbr, const uint64_t* key_hi, const uint64_t* key_lo, int32_t* new_colors, int64_t* info,
+                void* workspace, int64_t workspace_bytes, void* stream) {
   if (int rc = check_graph_batch(who, a, num_nodes, colors)) return rc;
+  if (int rc = check_copies(who, a, copies)) return rc;
   if (!key_hi || !key_lo || !new_colors || !info || (a->nnz > 0 && !sorted_nbr)) return fail("%s: NULL operand", who);
-  const long n = (long)a->num_graphs * a->rows;
+  const long stored = (long)a->num_graphs * a->rows, n = copies * stored;
   const int64_t need = (int64_t)rank_layout(nullptr, (size_t)n).total;
   if (!workspace || workspace_bytes < need) return fail("%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes, (long long)need);
   hipStream_t s = as_stream(stream);
@@ -613,13 +560,87 @@ extern "C" int kgcn_wl_rank_i32(const kgcn_csr_batch* a, const int32_t* num_node
   temp = o.temp_bytes;
   if (rocprim::radix_sort_pairs(o.temp, temp, o.hi_g, o.hi_s, o.idx1, o.idx2, (size_t)n, 0u, 64u, s) != hipSuccess)
     return fail("%s: rocprim::radix_sort_pairs failed", who);
-  RankArgs r{a->rowptr, num_nodes, colors, sorted_nbr, hi, lo, o.idx2, o.flags, o.pos, new_colors, reinterpret_cast<u64*>(info), n, a->rows};
+  RankArgs r{a->rowptr, num_nodes, colors, sorted_nbr, hi, lo, o.idx2, o.flags, o.pos, new_colors, reinterpret_cast<u64*>(info), n,
+             (long)a->nnz, (uint32_t)stored, a->rows};
   hipLaunchKernelGGL(wl_flag_kernel, dim3(nb), dim3(256), 0, s, r);
   temp = o.temp_bytes;
   if (rocprim::inclusive_scan(o.temp, temp, o.flags, o.pos, (size_t)n, rocprim::plus<int>(), s) != hipSuccess)
     return fail("%s: rocprim::inclusive_scan failed", who);
   hipLaunchKernelGGL(wl_colour_kernel, dim3(nb), dim3(256), 0, s, r);
   return check_launch(who);
+}
+
+int wl_runs_run(const char* who, const int32_t* colors, const int32_t* num_nodes, int32_t graphs, int32_t rows, int copies,
+                uint64_t column_offset, uint64_t column_stride, int64_t* run_ptr, uint64_t* run_col, int32_t* run_graph,
+                int32_t* run_count, int64_t capacity, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (graphs < 0 || rows < 0 || copies < 1 || (int64_t)copies * graphs * rows >= (int64_t)INT32_MAX ||
+      (int64_t)copies * graphs >= (int64_t)INT32_MAX)
+    return fail("%s: %d copies x %d graphs x %d rows", who, copies, graphs, rows);
+  if (rows > kWlRunsMaxNodes) return fail("%s: %d rows a graph, up to %d (its colours are sorted in LDS)", who, rows, kWlRunsMaxNodes);
+  if (!colors || !num_nodes) return fail("%s: NULL operand", who);
+  const int slots = copies * graphs;
+  if (int rc = check_runs_args(who, run_ptr, run_col, run_graph, run_count, capacity, workspace, workspace_bytes, slots)) return rc;
+  hipStream_t s = as_stream(stream);
+  if (slots == 0) return hipMemsetAsync(run_ptr, 0, sizeof(int64_t), s) == hipSuccess ? 0 : fail("%s: hipMemsetAsync failed", who);
+  RunsLayout o = runs_layout(run_col ? nullptr : aligned_base(workspace), (size_t)slots);
+  RunOut ro{o.counts, reinterpret_cast<const long long*>(run_ptr), reinterpret_cast<u64*>(run_col), run_graph, run_count,
+            (long long)capacity, (u64)column_offset, (u64)column_stride};
+  hipLaunchKernelGGL(wl_runs_kernel, dim3((unsigned)slots), dim3(256), (size_t)(2 * rows + 2) * sizeof(uint32_t), s, colors, num_nodes,
+                     graphs, rows, ro);
+  if (int rc = check_launch(who)) return rc;
+  return run_col ? 0 : scan_counts(who, o, slots, run_ptr, s);
+}
+
+int sp_features_run(const char* who, const kgcn_csr_batch* a, const int32_t* num_nodes, const int32_t* labels, int copies,
+                    int32_t num_labels, int64_t* run_ptr, uint64_t* run_col, int32_t* run_graph, int32_t* run_count,
+                    int64_t capacity, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (int rc = check_graph_batch(who, a, num_nodes, labels)) return rc;
+  if (int rc = check_copies(who, a, copies)) return rc;
+  if (a->rows > kSpMaxNodes)
+    return fail("%s: %d nodes a graph, up to %d: a distance and a queue entry are one byte each and the n^2 sorted keys of a graph "
+                "(64 KB at 128 nodes) must fit the LDS of its workgroup", who, a->rows, kSpMaxNodes);
+  if (num_labels < 0 || num_labels > kSpMaxLabels)
+    return fail("%s: %d distinct labels, up to %d: the key packs (label, label, distance) into 12 + 12 + 8 bits", who, num_labels,
+                kSpMaxLabels);
+  const int graphs = a->num_graphs, M = a->rows, slots = copies * graphs;
+  if (int rc = check_runs_args(who, run_ptr, run_col, run_graph, run_count, capacity, workspace, workspace_bytes, slots)) return rc;
+  hipStream_t s = as_stream(stream);
+  if (graphs == 0) return hipMemsetAsync(run_ptr, 0, sizeof(int64_t), s) == hipSuccess ? 0 : fail("%s: hipMemsetAsync failed", who);
+  int key_words = 1;
+  while (key_words < M * M) key_words <<= 1;
+  const size_t lds = (size_t)key_words * 4 + 256 * sizeof(int) + (((size_t)M * M + 3) & ~(size_t)3);
+  if (int rc = allow_full_lds<sp_features_kernel>(lds, who)) return rc;
+  RunsLayout o = runs_layout(run_col ? nullptr : aligned_base(workspace), (size_t)slots);
+  RunOut ro{o.counts, reinterpret_cast<const long long*>(run_ptr), reinterpret_cast<u64*>(run_col), run_graph, run_count,
+            (long long)capacity, 0ull, 0ull};
+  hipLaunchKernelGGL(sp_features_kernel, dim3((unsigned)graphs), dim3(256), lds, s, a->rowptr, a->cv, num_nodes, labels, M, copies,
+                     key_words, ro);
+  if (int rc = check_launch(who)) return rc;
+  return run_col ? 0 : scan_counts(who, o, slots, run_ptr, s);
+}
+
+}  // namespace kgcn
+
+using namespace kgcn;
+
+extern "C" int kgcn_wl_refine_i32(const kgcn_csr_batch* a, const int32_t* num_nodes, const int32_t* colors, uint64_t hash_mask,
+                                  int32_t* sorted_nbr, uint64_t* key_hi, uint64_t* key_lo, void* stream) {
+  return wl_refine_run("kgcn_wl_refine_i32", a, num_nodes, colors, 1, hash_mask, sorted_nbr, key_hi, key_lo, stream);
+}
+
+extern "C" int64_t kgcn_wl_rank_workspace_bytes(int64_t rows) {
+  if (rows < 0 || rows >= (int64_t)INT32_MAX) {
+    fail("kgcn_wl_rank_workspace_bytes: %lld rows outside 0..2^31-2", (long long)rows);
+    return -1;
+  }
+  return (int64_t)rank_layout(nullptr, (size_t)rows).total;
+}
+
+extern "C" int kgcn_wl_rank_i32(const kgcn_csr_batch* a, const int32_t* num_nodes, const int32_t* colors, const int32_t* sorted_nbr,
+                                const uint64_t* key_hi, const uint64_t* key_lo, int32_t* new_colors, int64_t* info, void* workspace,
+                                int64_t workspace_bytes, void* stream) {
+  return wl_rank_run("kgcn_wl_rank_i32", a, num_nodes, colors, 1, sorted_nbr, key_hi, key_lo, new_colors, info, workspace,
+                     workspace_bytes, stream);
 }
 
 extern "C" int64_t kgcn_graph_runs_workspace_bytes(int32_t graphs) {
@@ -633,47 +654,15 @@ extern "C" int64_t kgcn_graph_runs_workspace_bytes(int32_t graphs) {
 extern "C" int kgcn_wl_runs_i32(const int32_t* colors, const int32_t* num_nodes, int32_t graphs, int32_t rows, uint64_t column_offset,
                                 int64_t* run_ptr, uint64_t* run_col, int32_t* run_graph, int32_t* run_count, int64_t capacity,
                                 void* workspace, int64_t workspace_bytes, void* stream) {
-  const char* who = "kgcn_wl_runs_i32";
-  if (graphs < 0 || rows < 0 || (int64_t)graphs * rows >= (int64_t)INT32_MAX) return fail("%s: %d graphs x %d rows", who, graphs, rows);
-  if (rows > kWlRunsMaxNodes) return fail("%s: %d rows a graph, up to %d (its colours are sorted in LDS)", who, rows, kWlRunsMaxNodes);
-  if (!colors || !num_nodes) return fail("%s: NULL operand", who);
-  if (int rc = check_runs_args(who, run_ptr, run_col, run_graph, run_count, capacity, workspace, workspace_bytes, graphs)) return rc;
-  hipStream_t s = as_stream(stream);
-  if (graphs == 0) return hipMemsetAsync(run_ptr, 0, sizeof(int64_t), s) == hipSuccess ? 0 : fail("%s: hipMemsetAsync failed", who);
-  RunsLayout o = runs_layout(run_col ? nullptr : aligned_base(workspace), (size_t)graphs);
-  RunOut ro{o.counts, reinterpret_cast<const long long*>(run_ptr), reinterpret_cast<u64*>(run_col), run_graph, run_count,
-            (long long)capacity, (u64)column_offset};
-  hipLaunchKernelGGL(wl_runs_kernel, dim3((unsigned)graphs), dim3(256), (size_t)(2 * rows + 2) * sizeof(uint32_t), s, colors, num_nodes,
-                     rows, ro);
-  if (int rc = check_launch(who)) return rc;
-  return run_col ? 0 : scan_counts(who, o, graphs, run_ptr, s);
+  return wl_runs_run("kgcn_wl_runs_i32", colors, num_nodes, graphs, rows, 1, column_offset, 0, run_ptr, run_col, run_graph, run_count,
+                     capacity, workspace, workspace_bytes, stream);
 }
 
 extern "C" int kgcn_sp_features_i32(const kgcn_csr_batch* a, const int32_t* num_nodes, const int32_t* labels, int32_t num_labels,
                                     int64_t* run_ptr, uint64_t* run_col, int32_t* run_graph, int32_t* run_count, int64_t capacity,
                                     void* workspace, int64_t workspace_bytes, void* stream) {
-  const char* who = "kgcn_sp_features_i32";
-  if (int rc = check_graph_batch(who, a, num_nodes, labels)) return rc;
-  if (a->rows > kSpMaxNodes)
-    return fail("%s: %d nodes a graph, up to %d: a distance and a queue entry are one byte each and the n^2 sorted keys of a graph "
-                "(64 KB at 128 nodes) must fit the LDS of its workgroup", who, a->rows, kSpMaxNodes);
-  if (num_labels < 0 || num_labels > kSpMaxLabels)
-    return fail("%s: %d distinct labels, up to %d: the key packs (label, label, distance) into 12 + 12 + 8 bits", who, num_labels,
-                kSpMaxLabels);
-  const int graphs = a->num_graphs, M = a->rows;
-  if (int rc = check_runs_args(who, run_ptr, run_col, run_graph, run_count, capacity, workspace, workspace_bytes, graphs)) return rc;
-  hipStream_t s = as_stream(stream);
-  if (graphs == 0) return hipMemsetAsync(run_ptr, 0, sizeof(int64_t), s) == hipSuccess ? 0 : fail("%s: hipMemsetAsync failed", who);
-  int key_words = 1;
-  while (key_words < M * M) key_words <<= 1;
-  const size_t lds = (size_t)key_words * 4 + 256 * sizeof(int) + (((size_t)M * M + 3) & ~(size_t)3);
-  if (int rc = allow_full_lds<sp_features_kernel>(lds, who)) return rc;
-  RunsLayout o = runs_layout(run_col ? nullptr : aligned_base(workspace), (size_t)graphs);
-  RunOut ro{o.counts, reinterpret_cast<const long long*>(run_ptr), reinterpret_cast<u64*>(run_col), run_graph, run_count,
-            (long long)capacity, 0ull};
-  hipLaunchKernelGGL(sp_features_kernel, dim3((unsigned)graphs), dim3(256), lds, s, a->rowptr, a->cv, num_nodes, labels, M, key_words, ro);
-  if (int rc = check_launch(who)) return rc;
-  return run_col ? 0 : scan_counts(who, o, graphs, run_ptr, s);
+  return sp_features_run("kgcn_sp_features_i32", a, num_nodes, labels, 1, num_labels, run_ptr, run_col, run_graph, run_count, capacity,
+                         workspace, workspace_bytes, stream);
 }
 
 extern "C" int64_t kgcn_graph_gram_workspace_bytes(int64_t runs, int32_t graphs, int32_t chunk_cols) {

@@ -28,16 +28,40 @@ Deviations from the reference
     test graphs.
   * The shuffle of the data set is seeded (examples/graph_kernel.py --seed).
   * No cut to 3,000 graphs by default (--limit).
-  * hashed_attributes (continuous attributes) is not supported.
+
+Continuous node attributes: hash_graph_kernel (graphkernel/hash_graph_kernel.py over auxiliary_methods.py:23-36 and the
+hashed_attributes argument of both base kernels).  The attribute rows of the existing nodes are scaled to zero mean and unit
+variance, projected on R random directions and cut into buckets floor((x . v + b) / w) in fp64 by csrc/hashkern.hip (ops.attr_scale,
+ops.lsh_buckets; a stated summation order, nothing fused, so the tests restate them in numpy bit for bit); the base kernel
+runs on the buckets' dense ranks and the R feature maps share one Gram.  batched=True takes the R colourings through ONE launch
+sequence over the one stored adjacency (ops.wl_refine_copies / wl_rank_copies / wl_runs_copies: one mismatch read-back a
+refinement for all draws; ops.sp_features_copies: one breadth-first search a graph for all draws); batched=False runs the draws one
+after another through the plain ops and gives the same bits.  HASH_BATCHED is the measured default (tools/hash_kernel_bench.py).
+  Deviations of hash_graph_kernel from the reference
+  * K = F F^T / R exactly: the integer Gram over the runs of all draws, divided by R in one fp64 division.
+    hash_graph_kernel.py:63-65 rounds sqrt(1 / R) into every count first (measured difference: at most 1.6e-14 relative at R = 20).
+  * base="sp" with labels: the endpoint class is the joint (label, hash) class, the key (l_k, h_k, l_j, h_j, distance) of the
+    commented shortest_path_kernel_explicit.py:67.  The live line 68 ignores the hashes, so its result is shortest_path_kernel
+    itself, R times over.
+  * The projections are drawn on the host from np.random.default_rng(seed) (lsh_draws), not from numpy's global state; explicit
+    `projections` / `offsets` reproduce any other draw.
+  * A column whose values are all equal has variance 0 and becomes 0 (sklearn also treats a variance within rounding of 0 so).
+  * base="wl" with labels (use_labels 1 | 2, wl_kernel.py:63-82): label colours and hashed colours are refined separately and
+    every iteration counts the joint classes, as the reference does; the joint class is the exact pair, not a hash of it.
 Limits: shortest_path_kernel takes graphs of up to 128 nodes and 4,096 distinct labels (a distance is a byte and the key packs
-12 + 12 + 8 bits); wl_subtree_kernel up to 4,096 nodes a graph; up to 46,340 graphs a Gram."""
+12 + 12 + 8 bits); wl_subtree_kernel up to 4,096 nodes a graph; up to 46,340 graphs a Gram.  hash_graph_kernel: the base kernel's
+limits, with base="sp" up to 4,096 (joint) classes in every draw; up to 4,096 attributes a node; R * T * M below 2^31 - 1; a
+projected value that is not finite or reaches 2^62 is refused."""
+import copy
+
 import numpy as np
 import torch
 
 from . import _lib, ops
 from .batched_csr import BatchedAdjacency, BatchedCSR
 
-__all__ = ["wl_subtree_kernel", "shortest_path_kernel", "dense_label_ranks", "dataset_graphs", "svm_cv", "GraphSet"]
+__all__ = ["wl_subtree_kernel", "shortest_path_kernel", "hash_graph_kernel", "lsh_draws", "dense_label_ranks", "dataset_graphs",
+           "dataset_attributes", "svm_cv", "GraphSet"]
 
 
 def dense_label_ranks(labels):
@@ -185,6 +209,156 @@ def shortest_path_kernel(adjacency, num_nodes=None, node_labels=None, iterations
     gs = _as_graph_set(adjacency, num_nodes, node_labels)
     col, count = gs.initial_colours(labels)
     return _finish([ops.sp_features(gs.csr, gs.num_nodes, col, count)], gs.T, normalize, return_gram, chunk_cols)
+
+
+HASH_BATCHED = True          # hash_graph_kernel(batched=None): the route tools/hash_kernel_bench.py measured faster
+_SP_MAX_CLASSES = 4096
+
+
+def lsh_draws(seed, hash_iterations, d, sigma=1.0, bin_width=1.0):
+    """The R projections of auxiliary_methods.py:25-28 drawn on the host from np.random.default_rng(seed), draw after draw:
+    v_r = standard_normal(d) * sigma, b_r = bin_width * random() * sigma -> (V [R, d], b [R]) float64."""
+    rng = np.random.default_rng(seed)
+    V, b = np.empty((int(hash_iterations), int(d)), np.float64), np.empty(int(hash_iterations), np.float64)
+    for r in range(int(hash_iterations)):
+        V[r] = rng.standard_normal(int(d)) * sigma
+        b[r] = bin_width * rng.random() * sigma
+    return V, b
+
+
+def _attribute_rows(attributes, gs):
+    """[T, M', d] float32 / float64 -> the rows of the existing nodes [Nv, d] float64 in graph order (host)."""
+    a = np.asarray(attributes)
+    if a.dtype not in (np.float32, np.float64):
+        raise ValueError("attributes must be float32 or float64, got %s" % a.dtype)
+    if a.ndim != 3 or a.shape[0] != gs.T or a.shape[1] < (gs.num_nodes_host.max() if gs.T else 0) or a.shape[2] < 1:
+        raise ValueError("attributes must be [%d graphs, at least %d nodes, d >= 1], got %s"
+                         % (gs.T, gs.num_nodes_host.max() if gs.T else 0, a.shape))
+    if a.shape[2] > ops.LSH_MAX_DIM:
+        raise ValueError("%d attributes a node, up to %d" % (a.shape[2], ops.LSH_MAX_DIM))
+    rows = a[np.arange(a.shape[1])[None, :] < gs.num_nodes_host[:, None]].astype(np.float64)
+    if not np.all(np.isfinite(rows)):
+        raise ValueError("attributes hold NaN or Inf at %d of %d existing nodes" % (int((~np.isfinite(rows)).any(axis=1).sum()), len(rows)))
+    return np.ascontiguousarray(rows)
+
+
+def _refuse_mismatches(info, it, mask):
+    mismatches = int(info[1].item())
+    if mismatches:
+        raise _lib.KgcnHipError("wl refinement %d: %d pairs of nodes share a 128-bit key (mask %#x) but differ in their "
+                                "signatures; the partition would merge them, refused" % (it + 1, mismatches, mask))
+
+
+def _refuse_classes(count, what):
+    if count > _SP_MAX_CLASSES:
+        raise _lib.KgcnHipError("hash_graph_kernel: %d %s in one draw, up to %d: the shortest-path key packs (class, class, distance) "
+                                "into 12 + 12 + 8 bits; a wider bin_width or fewer labels give fewer classes" % (count, what, _SP_MAX_CLASSES))
+
+
+@torch.no_grad()
+def hash_graph_kernel(adjacency, num_nodes=None, attributes=None, base="wl", node_labels=None, labels=None, hash_iterations=20,
+                      wl_iterations=3, bin_width=1.0, sigma=1.0, scale_attributes=True, seed=0, projections=None, offsets=None,
+                      normalize=True, return_gram=True, batched=None, chunk_cols=None, hash_mask=None):
+    """hash_graph_kernel(graph_db, base_kernel, params, iterations=hash_iterations, lsh_bin_width=bin_width, sigma,
+    normalize_gram_matrix=normalize, scale_attributes) of the reference (hash_graph_kernel.py:13-71) -> the Gram [G, G] float64 on the
+    device.  attributes [T, M, d] float32 / float64 (promoted to float64; only existing nodes enter the statistics; NaN / Inf is
+    refused); base "wl" (wl_iterations refinements) or "sp"; labels None (use_labels == 0: the hashes alone), "node" or "degree"
+    (joint (label, hash) classes: see the module text).  projections [R, d] / offsets [R] override the seeded lsh_draws.
+    return_gram=False: the integer counts of all draws as a scipy CSR [G, features] (K = F F^T / R).  batched: the module text."""
+    if base not in ("wl", "sp"):
+        raise ValueError('base must be "wl" or "sp", got %r' % (base,))
+    if labels not in (None, "node", "degree"):
+        raise ValueError('labels must be None, "node" or "degree", got %r' % (labels,))
+    if attributes is None:
+        raise ValueError("hash_graph_kernel needs attributes [T, M, d]; without them use wl_subtree_kernel / shortest_path_kernel")
+    gs = _as_graph_set(adjacency, num_nodes, node_labels)
+    X = _attribute_rows(attributes, gs)
+    d = X.shape[1]
+    if (projections is None) != (offsets is None):
+        raise ValueError("projections and offsets come together")
+    if projections is None:
+        if int(hash_iterations) < 1:
+            raise ValueError("hash_iterations must be at least 1, got %r" % (hash_iterations,))
+        projections, offsets = lsh_draws(seed, hash_iterations, d, sigma, bin_width)
+    V, b = np.ascontiguousarray(projections, np.float64), np.ascontiguousarray(offsets, np.float64).reshape(-1)
+    if V.ndim != 2 or V.shape[0] < 1 or V.shape[1] != d or b.shape[0] != V.shape[0]:
+        raise ValueError("projections must be [R >= 1, %d] and offsets [R], got %s and %s" % (d, V.shape, b.shape))
+    R, T, M, dev = V.shape[0], gs.T, gs.M, gs.device
+    batched = HASH_BATCHED if batched is None else bool(batched)
+    mask = ops.HASH_MASK_FULL if hash_mask is None else int(hash_mask)
+    if X.shape[0] == 0:                                               # no node: no feature
+        if return_gram:
+            return torch.zeros((T, T), device=dev, dtype=torch.float64)
+        import scipy.sparse as sps
+        return sps.csr_matrix((T, 1), dtype=np.int64)
+
+    x = torch.from_numpy(X).to(dev)
+    if scale_attributes:
+        x = ops.attr_scale(x)[0]
+    bucket = ops.lsh_buckets(x, torch.from_numpy(V).to(dev), torch.from_numpy(b).to(dev), bin_width)            # [R, Nv]
+    exists = torch.from_numpy(gs.exists.reshape(-1)).to(dev)
+    mark = exists.to(torch.int32) - 1                                                                           # [T*M]: 0 / -1
+    full = torch.zeros((R, T * M), device=dev, dtype=torch.int64)
+    full[:, exists] = bucket
+    lab_cols = wl_colourings(gs, iterations=wl_iterations, labels=labels, hash_mask=hash_mask)[0] if labels and base == "wl" else None
+    lab0 = gs.initial_colours(labels)[0].to(torch.int64) if labels and base == "sp" else None
+    stride = int(wl_iterations) + 1
+    runs = []
+    if batched:
+        markR = mark.repeat(R)
+        draw = torch.arange(R, device=dev, dtype=torch.int64)[:, None]
+        col = ops.rank_pairs(draw.expand(R, T * M).reshape(-1).contiguous(), full.reshape(-1), markR)[0]     # of (draw, bucket)
+        if base == "wl":
+            cols = [col]
+            for it in range(int(wl_iterations)):
+                sorted_nbr, hi, lo = ops.wl_refine_copies(gs.csr, gs.num_nodes, col, R, mask)
+                col, info = ops.wl_rank_copies(gs.csr, gs.num_nodes, col, R, sorted_nbr, hi, lo)
+                _refuse_mismatches(info, it, mask)
+                cols.append(col)
+            for it, c in enumerate(cols):
+                if lab_cols is not None:                                                          # wl_kernel.py:66-70
+                    c = ops.rank_pairs(lab_cols[it].reshape(-1).to(torch.int64).repeat(R), c.to(torch.int64), markR)[0]
+                runs.append(ops.wl_runs_copies(c, gs.num_nodes, T, M, R, it << 32, stride << 32))
+        else:
+            if lab0 is not None:                                      # shortest_path_kernel_explicit.py:67
+                col = ops.rank_pairs(((draw << 32) + lab0[None, :]).reshape(-1), col.to(torch.int64), markR)[0]
+            c = col.view(R, T * M)                                    # ascending in the draw: every draw's classes are one range
+            first = torch.where(c >= 0, c, torch.full_like(c, 2 ** 31 - 1)).amin(dim=1, keepdim=True)
+            c = torch.where(c >= 0, c - first, c).contiguous()
+            count = int(c.max().item()) + 1
+            _refuse_classes(count, "joint (label, hash) classes" if labels else "hash classes")
+            runs.append(ops.sp_features_copies(gs.csr, gs.num_nodes, c.reshape(-1), R, count))
+    else:
+        host = full.view(R, T, M).cpu().numpy()
+        for r in range(R):
+            one = copy.copy(gs)                                       # the same device adjacency, this draw's buckets as its labels
+            one.node_labels = host[r]
+            if base == "wl":
+                cols = wl_colourings(one, iterations=wl_iterations, labels="node", hash_mask=hash_mask)[0]
+                for it, c in enumerate(cols):
+                    c = c.reshape(-1)
+                    if lab_cols is not None:
+                        c = ops.rank_pairs(lab_cols[it].reshape(-1).to(torch.int64), c.to(torch.int64), mark)[0]
+                    runs.append(ops.wl_runs(c.contiguous(), gs.num_nodes, T, M, (r * stride + it) << 32))
+            else:
+                c, count = one.initial_colours("node")
+                if lab0 is not None:
+                    c, info = ops.rank_pairs(lab0, c.to(torch.int64), mark)
+                    count = int(info[0].item())
+                _refuse_classes(count, "joint (label, hash) classes" if labels else "hash classes")
+                col, graph, n = ops.sp_features(gs.csr, gs.num_nodes, c, count)
+                runs.append((col + (r << 32), graph, n))
+    if not return_gram:
+        return _finish(runs, T, False, False, chunk_cols)
+    K = _finish(runs, T, False, True, chunk_cols)
+    K = K / torch.tensor(float(R), device=dev, dtype=torch.float64)   # a device divisor: one IEEE division an entry (a host
+    return ops.gram_normalize(K) if normalize else K                  # scalar would be multiplied in as its rounded reciprocal)
+
+
+def dataset_attributes(obj):
+    """The node feature tensor of a kGCN data set, "feature" [T, M, F], as hash_graph_kernel's attributes -> float array or None."""
+    feat = obj.get("feature")
+    return None if feat is None else np.asarray(feat)
 
 
 def dataset_graphs(obj):

@@ -3237,3 +3237,169 @@ def gram_normalize(K):
     out = torch.empty_like(K)
     check(lib.kgcn_gram_normalize_f64(ptr(K), K.shape[0], ptr(out), current_stream()), "kgcn_gram_normalize_f64")
     return out
+
+
+# -------------------------------------------------------------------------------------------------
+# hash graph kernels for continuous node attributes (csrc/hashkern.hip; the driver is graph_kernel.hash_graph_kernel): the fp64
+# scaling and bucketing of attribute rows, the ranking of int64 pairs, and R colourings ("copies") of the same graphs through
+# one launch sequence of the refinement, run and shortest-path kernels.  fp64 and integers: bitwise reproducible.
+# -------------------------------------------------------------------------------------------------
+LSH_MAX_DIM = _lib.K["KGCN_LSH_MAX_DIM"]
+
+
+def _dev_tensor(t, name, dtype, shape, who):
+    require_gpu(t, name)
+    if t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise _lib.KgcnHipError("%s: %s must be a contiguous %s device tensor of shape %s, got %s %s"
+                                % (who, name, dtype, tuple(shape), t.dtype, tuple(t.shape)))
+    return t
+
+
+def _attr_rows(x, name, who):
+    require_gpu(x, name)
+    if x.dtype != torch.float64 or x.dim() != 2 or not x.is_contiguous():
+        raise _lib.KgcnHipError("%s: %s must be a contiguous [rows, d] float64 device tensor, got %s %s" % (who, name, x.dtype, tuple(x.shape)))
+    rows, d = x.shape
+    if rows < 1 or d < 1 or d > LSH_MAX_DIM:
+        raise _lib.KgcnHipError("%s: %d rows of %d attributes; at least one row and 1..%d attributes a row" % (who, rows, d, LSH_MAX_DIM))
+    return rows, d
+
+
+def _copies(copies, T, M, who):
+    copies = int(copies)
+    if copies < 1 or copies * T * M >= 2 ** 31 - 1:
+        raise _lib.KgcnHipError("%s: %d copies of %d graphs x %d rows; at least one copy and fewer than 2^31 - 1 rows in all "
+                                "(positions and colours are int32)" % (who, copies, T, M))
+    return copies
+
+
+@torch.no_grad()
+def attr_scale(x):
+    """Attribute rows x [rows, d] float64 (the existing nodes in graph order) -> (scaled [rows, d], mean [d], std [d]):
+    sklearn.preprocessing.scale of hash_graph_kernel.py:40 in the summation order csrc/hashkern.hip states (chunks of 256 rows,
+    then the chunk sums, nothing fused); a column of equal values becomes 0."""
+    rows, d = _attr_rows(x, "x", "attr_scale")
+    dev = x.device
+    scaled = torch.empty_like(x)
+    stats = torch.empty((2, d), device=dev, dtype=torch.float64)
+    ws, wsb = _ws_bytes(lib.kgcn_attr_scale_workspace_bytes(rows, d), "kgcn_attr_scale_workspace_bytes", dev)
+    check(lib.kgcn_attr_scale_f64(ptr(x), rows, d, ptr(scaled), ptr(stats[0]), ptr(stats[1]), ptr(ws), wsb, current_stream()),
+          "kgcn_attr_scale_f64")
+    return scaled, stats[0], stats[1]
+
+
+@torch.no_grad()
+def lsh_buckets(x, v, b, bin_width):
+    """bucket [R, rows] int64 = floor((x . v_r + b_r) / bin_width) of auxiliary_methods.py:31, the dot product added for k
+    ascending and unfused.  x [rows, d], v [R, d], b [R] float64 on the device.  A value that is not finite or reaches 2^62 in
+    magnitude raises (one read-back of the device's error count): nothing wraps silently."""
+    rows, d = _attr_rows(x, "x", "lsh_buckets")
+    require_gpu(v, "v")
+    if v.dim() != 2 or v.shape[0] < 1:
+        raise _lib.KgcnHipError("lsh_buckets: v must be [R, d] with R >= 1, got %s" % (tuple(v.shape),))
+    R = v.shape[0]
+    _dev_tensor(v, "v", torch.float64, (R, d), "lsh_buckets"), _dev_tensor(b, "b", torch.float64, (R,), "lsh_buckets")
+    w = float(bin_width)
+    if not 0.0 < w < float("inf"):
+        raise _lib.KgcnHipError("lsh_buckets: the bin width %r must be positive and finite" % (bin_width,))
+    if R * rows >= 2 ** 31 - 1:
+        raise _lib.KgcnHipError("lsh_buckets: %d draws x %d rows; fewer than 2^31 - 1 buckets a call" % (R, rows))
+    bucket = torch.empty((R, rows), device=x.device, dtype=torch.int64)
+    errors = torch.empty((1,), device=x.device, dtype=torch.int64)
+    check(lib.kgcn_lsh_buckets_f64(ptr(x), rows, d, ptr(v), ptr(b), R, ctypes.byref(ctypes.c_double(w)), ptr(bucket), ptr(errors),
+                                   current_stream()), "kgcn_lsh_buckets_f64")
+    bad = int(errors.item())
+    if bad:
+        raise _lib.KgcnHipError("lsh_buckets: %d of %d projected values (x . v + b) / %g are not finite or reach 2^62: no int64 "
+                                "bucket holds them, refused" % (bad, R * rows, w))
+    return bucket
+
+
+@torch.no_grad()
+def rank_pairs(hi, lo, mark=None):
+    """Dense ranks int32 [n] of the int64 pairs (hi, lo) in ascending signed order -- np.unique(..., return_inverse=True) of the
+    pairs -- and info [2] int64 on the device = (number of classes, existing rows with hi == 2^63 - 1: refuse when not 0).
+    mark: None or int32 [n]; a row with mark < 0 does not exist, takes no part and gets -1."""
+    require_gpu(hi, "hi")
+    n = int(hi.numel())
+    _dev_tensor(hi, "hi", torch.int64, (n,), "rank_pairs"), _dev_tensor(lo, "lo", torch.int64, (n,), "rank_pairs")
+    if mark is not None:
+        _dev_tensor(mark, "mark", torch.int32, (n,), "rank_pairs")
+    dev = hi.device
+    ranks = torch.empty((max(n, 1),), device=dev, dtype=torch.int32)
+    info = torch.empty((2,), device=dev, dtype=torch.int64)
+    ws, wsb = _ws_bytes(lib.kgcn_rank_pairs_workspace_bytes(n), "kgcn_rank_pairs_workspace_bytes", dev)
+    check(lib.kgcn_rank_pairs_i64(ptr(hi) if n else None, ptr(lo) if n else None, None if mark is None or not n else ptr(mark), n,
+                                  ptr(ranks), ptr(info), ptr(ws), wsb, current_stream()), "kgcn_rank_pairs_i64")
+    return ranks[:n], info
+
+
+@torch.no_grad()
+def wl_refine_copies(csr, num_nodes, colors, copies, hash_mask=HASH_MASK_FULL):
+    """wl_refine for colors [copies, T*M] over the one stored batch -> (sorted_nbr [copies, nnz], key_hi, key_lo [copies * T*M])."""
+    T, M = _plain_square(csr, "wl_refine_copies")
+    R = _copies(copies, T, M, "wl_refine_copies")
+    dev = csr.device
+    _i32_dev(num_nodes, "num_nodes", T), _i32_dev(colors, "colors", R * T * M)
+    sorted_nbr = torch.empty((R, max(csr.nnz, 1)), device=dev, dtype=torch.int32)
+    keys = torch.empty((2, max(R * T * M, 1)), device=dev, dtype=torch.int64)
+    check(lib.kgcn_wl_refine_copies_i32(ctypes.byref(csr.desc()), ptr(num_nodes), ptr(colors), R, int(hash_mask) & HASH_MASK_FULL,
+                                        ptr(sorted_nbr), ptr(keys[0]), ptr(keys[1]), current_stream()), "kgcn_wl_refine_copies_i32")
+    return sorted_nbr, keys[0], keys[1]
+
+
+@torch.no_grad()
+def wl_rank_copies(csr, num_nodes, colors, copies, sorted_nbr, key_hi, key_lo):
+    """wl_rank over all copies in one ranking -> (new_colors [copies * T*M] int32, info [2]): copies whose colours are disjoint
+    stay disjoint, and one info -- one read-back -- serves them all."""
+    T, M = _plain_square(csr, "wl_rank_copies")
+    R = _copies(copies, T, M, "wl_rank_copies")
+    dev = csr.device
+    n = R * T * M
+    _i32_dev(num_nodes, "num_nodes", T), _i32_dev(colors, "colors", n)
+    _dev_tensor(sorted_nbr, "sorted_nbr", torch.int32, (R, max(csr.nnz, 1)), "wl_rank_copies")
+    _dev_tensor(key_hi, "key_hi", torch.int64, (max(n, 1),), "wl_rank_copies")
+    _dev_tensor(key_lo, "key_lo", torch.int64, (max(n, 1),), "wl_rank_copies")
+    new = torch.empty((max(n, 1),), device=dev, dtype=torch.int32)
+    info = torch.empty((2,), device=dev, dtype=torch.int64)
+    ws, wsb = _ws_bytes(lib.kgcn_wl_rank_copies_workspace_bytes(T * M, R), "kgcn_wl_rank_copies_workspace_bytes", dev)
+    check(lib.kgcn_wl_rank_copies_i32(ctypes.byref(csr.desc()), ptr(num_nodes), ptr(colors), R, ptr(sorted_nbr), ptr(key_hi),
+                                      ptr(key_lo), ptr(new), ptr(info), ptr(ws), wsb, current_stream()), "kgcn_wl_rank_copies_i32")
+    return new[:n], info
+
+
+def _two_pass_runs_copies(call, T, R, dev, what):
+    """_two_pass_runs over copies * T run slots."""
+    run_ptr = torch.empty((R * T + 1,), device=dev, dtype=torch.int64)
+    ws, wsb = _ws_bytes(lib.kgcn_graph_runs_copies_workspace_bytes(T, R), "kgcn_graph_runs_copies_workspace_bytes", dev)
+    check(call(run_ptr, None, None, None, 0, ws, wsb), what)
+    total = int(run_ptr[R * T].item())
+    col = torch.empty((max(total, 1),), device=dev, dtype=torch.int64)
+    graph = torch.empty((max(total, 1),), device=dev, dtype=torch.int32)
+    count = torch.empty((max(total, 1),), device=dev, dtype=torch.int32)
+    check(call(run_ptr, col, graph, count, total, ws, wsb), what)
+    return col[:total], graph[:total], count[:total]
+
+
+@torch.no_grad()
+def wl_runs_copies(colors, num_nodes, T, M, copies, column_offset, column_stride):
+    """The colour histograms of every (copy, graph) as feature runs in slot order (all graphs of copy 0, then copy 1, ...),
+    column = column_offset + copy * column_stride + colour, graph = t."""
+    R = _copies(copies, T, M, "wl_runs_copies")
+    _i32_dev(num_nodes, "num_nodes", T), _i32_dev(colors, "colors", R * T * M)
+    return _two_pass_runs_copies(lambda rp, c, g, n, cap, ws, wsb: lib.kgcn_wl_runs_copies_i32(
+        ptr(colors), ptr(num_nodes), T, M, R, int(column_offset), int(column_stride), ptr(rp), ptr(c), ptr(g), ptr(n), cap, ptr(ws),
+        wsb, current_stream()), T, R, colors.device, "kgcn_wl_runs_copies_i32")
+
+
+@torch.no_grad()
+def sp_features_copies(csr, num_nodes, labels, copies, num_labels):
+    """sp_features for labels [copies, T*M]: the breadth-first searches run once a graph, the keys of every copy are sorted and
+    counted from the same distances; runs in slot order, column = copy << 32 | label_k << 20 | label_j << 8 | distance.
+    num_labels: every copy's labels are below it, up to 4,096."""
+    T, M = _plain_square(csr, "sp_features_copies")
+    R = _copies(copies, T, M, "sp_features_copies")
+    _i32_dev(num_nodes, "num_nodes", T), _i32_dev(labels, "labels", R * T * M)
+    return _two_pass_runs_copies(lambda rp, c, g, n, cap, ws, wsb: lib.kgcn_sp_features_copies_i32(
+        ctypes.byref(csr.desc()), ptr(num_nodes), ptr(labels), R, int(num_labels), ptr(rp), ptr(c), ptr(g), ptr(n), cap, ptr(ws),
+        wsb, current_stream()), T, R, csr.device, "kgcn_sp_features_copies_i32")
