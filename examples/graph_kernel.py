@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """graph_kernel/gk.py --kernel wl|sp on the MI355X path: the Weisfeiler-Lehman subtree (3 iterations) or shortest-path Gram matrix
-of a data set on the device (kgcn_amd.graph_kernel), normalised, then the nested k-fold SVM of gk.py on the host (scikit-learn).
+of a data set on the device (kgcn_amd.graph_kernel), normalised, then the nested k-fold SVM of gk.py: --svm host (the default;
+scikit-learn, one fit after another) or --svm device (all fits as one batch of the HIP solver; the Gram never leaves the device
+before the SVM; the two agree to the solver's tolerance --svm-tol, not bit for bit).
 --kernel hgk-wl|hgk-sp: the hash graph kernel over the data set's continuous node attributes ("feature" [T, M, F]) with the WL or
 SP base kernel (graphkernel/hash_graph_kernel.py): --hash-iterations draws seeded by --seed, buckets --bin-width wide, --use-labels
 none (the hashes alone) | node | degree (joint (label, hash) classes).
@@ -11,6 +13,7 @@ after the shuffle (default: no cut; the reference cuts at 3,000).
 
     python examples/graph_kernel.py --kernel wl|sp|hgk-wl|hgk-sp [--input_dataset X.jbl] [--limit N] [--output DIR]
         [--test_splits 5] [--seed 0] [--hash-iterations 20] [--bin-width 1.0] [--sigma 1.0] [--use-labels none|node|degree]
+        [--svm host|device] [--svm-tol 1e-3]
 """
 import argparse
 import os
@@ -33,6 +36,8 @@ ap.add_argument("--hash-iterations", type=int, default=20, help="hgk-*: random p
 ap.add_argument("--bin-width", type=float, default=1.0, help="hgk-*: bucket width w")
 ap.add_argument("--sigma", type=float, default=1.0, help="hgk-*: scale of the projections")
 ap.add_argument("--use-labels", choices=("none", "node", "degree"), default="none", help="hgk-*: discrete labels beside the hashes")
+ap.add_argument("--svm", choices=("host", "device"), default="host", help="where the nested-CV SVMs are fitted")
+ap.add_argument("--svm-tol", type=float, default=1e-3, help="stopping tolerance of the SVM solver (SVC's tol)")
 a = ap.parse_args()
 hashed = a.kernel.startswith("hgk-")
 
@@ -74,17 +79,21 @@ labels = None if labels is None else [labels[i] for i in order]
 if hashed:
     K = gk.hash_graph_kernel(adjs, nn, np.asarray(attrs)[order], base=a.kernel[4:], node_labels=labels,
                              labels=None if a.use_labels == "none" else a.use_labels, hash_iterations=a.hash_iterations,
-                             wl_iterations=3, bin_width=a.bin_width, sigma=a.sigma, seed=a.seed).cpu().numpy()
+                             wl_iterations=3, bin_width=a.bin_width, sigma=a.sigma, seed=a.seed)
 else:
     kernel = gk.wl_subtree_kernel if a.kernel == "wl" else gk.shortest_path_kernel
-    K = kernel(adjs, nn, labels, iterations=3).cpu().numpy()
+    K = kernel(adjs, nn, labels, iterations=3)
+if a.svm == "device":                                                   # the SVM reads the Gram where it was built
+    res = gk.svm_cv(K, y, test_splits=a.test_splits, device=True, tol=a.svm_tol)
+K = K.cpu().numpy()
 os.makedirs(a.output, exist_ok=True)
 for name, arr in (("gram_%s.npy" % a.kernel.replace("-", "_"), K), ("label.npy", y)):
     print("[SAVE] " + os.path.join(a.output, name))
     np.save(os.path.join(a.output, name), arr)
 
-res = gk.svm_cv(K, y, test_splits=a.test_splits)
-print("%d graphs, %s kernel" % (len(y), a.kernel))
+if a.svm == "host":
+    res = gk.svm_cv(K, y, test_splits=a.test_splits, device=False, tol=a.svm_tol)
+print("%d graphs, %s kernel, SVM on the %s" % (len(y), a.kernel, a.svm))
 print("split  best C     acc. (validation)  acc. (test)")
 for k, (c, v, t) in enumerate(zip(res["best_C"], res["val_acc"], res["test_acc"])):
     print("%5d  %-9.4f %-18.6f %.6f" % (k, c, v, t))

@@ -99,7 +99,9 @@ extern "C" {
  * The hash graph kernels added entry points only (version still 2): kgcn_attr_scale_f64 (+ kgcn_attr_scale_workspace_bytes),
  * kgcn_lsh_buckets_f64, kgcn_rank_pairs_i64 (+ kgcn_rank_pairs_workspace_bytes), kgcn_wl_refine_copies_i32, kgcn_wl_rank_copies_i32
  * (+ kgcn_wl_rank_copies_workspace_bytes), kgcn_wl_runs_copies_i32, kgcn_sp_features_copies_i32
- * (+ kgcn_graph_runs_copies_workspace_bytes). */
+ * (+ kgcn_graph_runs_copies_workspace_bytes).
+ * The batched kernel SVM added entry points only (version still 2): kgcn_svm_smo_f64 (+ kgcn_svm_workspace_bytes),
+ * kgcn_svm_decision_f64, kgcn_svm_vote_i32. */
 #define KGCN_HIP_ABI_VERSION 2
 
 /* Column index of the padding entries of a row-padded batch (see row_pad): they carry value 0 and
@@ -1170,6 +1172,61 @@ int kgcn_wl_runs_copies_i32(const int32_t* colors, const int32_t* num_nodes, int
 int kgcn_sp_features_copies_i32(const kgcn_csr_batch* a, const int32_t* num_nodes, const int32_t* labels, int32_t copies,
                                 int32_t num_labels, int64_t* run_ptr, uint64_t* run_col, int32_t* run_graph, int32_t* run_count,
                                 int64_t capacity, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* -- batched C-SVC over a precomputed kernel (csrc/svm.hip; kgcn_amd/graph_kernel.py svm_fit / svm_decision / svm_predict / svm_cv)
+ * The nested KFold / SVC(kernel="precomputed") loop of graph_kernel/gk.py:243-292 as one batch of independent dual problems
+ *   min 1/2 a^T Q a - e^T a,  0 <= a_t <= C,  y^T a = 0,   Q_st = y_s y_t K[idx_s, idx_t]
+ * over ONE shared matrix K [graphs, graphs] fp64 (row-major, read in place through the index sets; no sub-matrix is formed),
+ * solved by libsvm's SMO (svm.cpp Solver::Solve, select_working_set: second-order working-set selection, TAU = 1e-12;
+ * calculate_rho) in fp64, without shrinking and without a kernel cache, one workgroup a problem.  fp64 and integers, no float
+ * atomics, nothing fused: bitwise reproducible, and independent of the workgroup size, the wave order and the slicing below.
+ *
+ * Index sets: `sets` of them, set s = set_idx[set_ptr[s] .. set_ptr[s+1]) rows of K (set_ptr [sets + 1] ascending from 0 to
+ * set_total), set_sign [set_total] the label +1 / -1 of each entry (the sign lives with the set, not with the row: a one-vs-one pair
+ * relabels rows; evaluation sets have none), max_rows >= the longest set.  All arrays on the device.  A problem p is (set
+ * prob_set[p], C = prob_C[p] > 0); problems that differ only in C share a set.
+ *
+ *   kgcn_svm_smo_f64   one SLICE of at most iters_per_launch iterations of every unfinished problem (a kernel's running time is
+ *       bounded; the caller relaunches while the word below is not 0).  first != 0 starts from alpha = 0, G = -1; otherwise from
+ *       the alpha [problems, max_rows] and the G in the workspace the previous slice left, so slicing changes no bit.  An iteration:
+ *       i = argmax of -y_t G_t over I_up; row i of K gathered into registers; j = argmin of -b^2 / a over I_low with b = Gmax +
+ *       y_t G_t > 0, a = (QD_i + QD_t) - 2 K_it (TAU where a <= 0); row j gathered; the clipped two-variable update exactly as
+ *       libsvm orders it, both label cases; G_t = G_t + ((Q_it d_i) + (Q_jt d_j)).  Reductions carry (value, index) and among equal
+ *       values the LAST index wins, as libsvm's `>=` / `<=` scans do.  Stops when m(alpha) - M(alpha) < *tol (status
+ *       KGCN_SVM_CONVERGED) or after max_iter iterations in all (KGCN_SVM_MAX_ITER; max_iter <= 0: libsvm's max(10^7, 100 n)).
+ *       Then rho: with free vectors acc = +0.0, acc = acc + y_t G_t over the free t ascending, rho = acc / count; with none the
+ *       midpoint of the bounds.  Outputs: alpha, rho [problems], n_iter [problems], status [problems] (KGCN_SVM_*); a problem
+ *       whose descriptor is out of range (set, length, row index, sign, C) touches no memory and gets KGCN_SVM_REFUSED.  The
+ *       first 4 bytes of the 256-byte aligned workspace hold the number of problems still KGCN_SVM_RUNNING after the slice.
+ *       Refused before any launch: max_rows > KGCN_SVM_MAX_ROWS (G, alpha, QD, the indices and signs of a problem live in LDS).
+ *   kgcn_svm_decision_f64   job q = (problem job_prob[q], evaluation set job_eval[q]) writes dec[job_out[q] + r] for every row
+ *       r of the set: acc = +0.0, acc = acc + (alpha_t y_t) K[row_r, idx_t] for t = 0, 1, ... over ALL training rows, dec =
+ *       acc - rho.  job_out [jobs + 1] ascending, job_out[q + 1] - job_out[q] = the set's length, job_out[jobs] = dec_total.
+ *       Positive: the +1 class (scikit-learn's two-class decision_function is the negative).
+ *   kgcn_svm_vote_i32   vote v takes the classes (classes - 1) / 2 consecutive jobs vote_first_job[v] ... (libsvm's pair order (0, 1),
+ *       (0, 2), ..., (1, 2), ...; +1 is the pair's first class; all on evaluation set vote_eval[v]) and writes pred[vote_out[v] + r]
+ *       = the class index with the most votes, dec > 0 voting for the first class of a pair and anything else for the second, the
+ *       lowest index among equals (svm_predict_values).  correct[v] = the rows whose prediction equals labels[row] (class
+ *       indices of the rows of K; integer atomics).  2 <= classes <= KGCN_SVM_MAX_CLASSES.
+ * decision and vote: errors [1] (device) counts jobs / rows whose descriptors are out of range (nothing is read or written for
+ * them): the caller refuses a non-zero count.  Asynchronous on `stream`. */
+enum { KGCN_SVM_MAX_ROWS = 4096, KGCN_SVM_MAX_CLASSES = 64, KGCN_SVM_DEFAULT_SLICE = 2048 };
+enum { KGCN_SVM_RUNNING = 0, KGCN_SVM_CONVERGED = 1, KGCN_SVM_MAX_ITER = 2, KGCN_SVM_REFUSED = 3 };
+int64_t kgcn_svm_workspace_bytes(int32_t problems, int32_t max_rows);
+int kgcn_svm_smo_f64(const double* K, int32_t graphs, const int64_t* set_ptr, const int32_t* set_idx, const int8_t* set_sign,
+                     int32_t sets, int64_t set_total, int32_t max_rows, const int32_t* prob_set, const double* prob_C,
+                     int32_t problems, const double* tol, int64_t max_iter, int32_t iters_per_launch, int32_t first, double* alpha,
+                     double* rho, int64_t* n_iter, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
+int kgcn_svm_decision_f64(const double* K, int32_t graphs, const int64_t* set_ptr, const int32_t* set_idx, const int8_t* set_sign,
+                          int32_t sets, int64_t set_total, int32_t max_rows, const int32_t* prob_set, int32_t problems,
+                          const double* alpha, const double* rho, const int64_t* eval_ptr, const int32_t* eval_idx, int32_t evals,
+                          int64_t eval_total, int32_t eval_max_rows, const int32_t* job_prob, const int32_t* job_eval,
+                          const int64_t* job_out, int32_t jobs, double* dec, int64_t dec_total, int64_t* errors, void* stream);
+int kgcn_svm_vote_i32(const double* dec, int64_t dec_total, const int64_t* job_out, int32_t jobs, const int64_t* eval_ptr,
+                      const int32_t* eval_idx, int32_t evals, int64_t eval_total, int32_t eval_max_rows,
+                      const int32_t* vote_first_job, const int32_t* vote_eval, const int64_t* vote_out, int32_t votes,
+                      int32_t classes, const int32_t* labels, int32_t graphs, int32_t* pred, int64_t pred_total, int64_t* correct,
+                      int64_t* errors, void* stream);
 
 /* -- k-fold cross-validation of the compound-protein interaction networks (gcn.py train_cv; csrc/cvloss.hip, csrc/cvmetrics.hip)
  * Loss head of sample_chem/compound-protein_interaction/multitask.py:53-86 (singletask.py: tasks = 1): logits [batch, 2, tasks],

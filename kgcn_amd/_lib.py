@@ -40,7 +40,7 @@ if active_overrides():
 _SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint32_t": ctypes.c_uint32,
             "uint64_t": ctypes.c_uint64, "float": ctypes.c_float}
 _FIELD_SCALARS = ("int32_t", "int64_t", "float")
-_POINTEES = tuple(_SCALARS) + ("void", "char", "uint8_t", "double")      # what an untyped pointer may point to
+_POINTEES = tuple(_SCALARS) + ("void", "char", "int8_t", "uint8_t", "double")    # what an untyped pointer may point to
 # Structures an entry point takes by typed pointer (ctypes then checks what a caller passes).  Pointers to the other
 # structures stay untyped like every pointer to plain data: their callers hand over job arrays or raw addresses.
 _TYPED_POINTERS = ("kgcn_csr_batch", "kgcn_stack_layer", "kgcn_assemble_plan", "kgcn_spmm_route")

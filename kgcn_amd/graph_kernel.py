@@ -1,10 +1,18 @@
 """Classical graph-kernel baselines of the reference's graph_kernel/gk.py on the device: the Weisfeiler-Lehman subtree kernel
 (graphkernel/wl_kernel.py) and the shortest-path kernel (graphkernel/shortest_path_kernel_explicit.py) as exact float64 Gram
-matrices, and the nested k-fold SVM of gk.py:243-292 over them (host, scikit-learn).
+matrices, and the nested k-fold SVM of gk.py:243-292 over them: on the host (scikit-learn, the default) or on the device.
 
     K = wl_subtree_kernel(adjs, num_nodes, node_labels, iterations=3)      # [G, G] float64 on the device, normalised
     K = shortest_path_kernel(adjs, num_nodes, node_labels)
-    result = svm_cv(K.cpu().numpy(), y)
+    result = svm_cv(K.cpu().numpy(), y)                                    # 125 SVC fits one after another on the host
+    result = svm_cv(K, y, device=True)                                     # the same fits as one batch, K stays on the device
+
+The device route (svm_fit / svm_decision / svm_predict, csrc/svm.hip through ops.svm_smo_batch / svm_decision_batch / svm_vote) is
+libsvm's SMO with second-order working-set selection in fp64, one workgroup a problem, without shrinking and without a kernel
+cache, in bounded launches; a problem that reaches max_iter raises ops.SvmNotConverged.  Its iterates are a pure function of the
+input (the tests restate them in numpy bit for bit); it agrees with SVC to the solver tolerance, not bit for bit (libsvm
+keeps its kernel rows in float32), so SVM_DEVICE = False keeps the host route the default.  Up to 4,096 training rows a fit; every
+training set must hold every class of y.
 
 The features are computed by csrc/graphkern.hip (ops.wl_refine / wl_rank / wl_runs / sp_features) as runs (column, graph, count),
 the Gram by ops.gram_from_runs: columns that occur in one graph on an int64 diagonal, the others on v_mfma_f64_16x16x4_f64.
@@ -61,7 +69,8 @@ from . import _lib, ops
 from .batched_csr import BatchedAdjacency, BatchedCSR
 
 __all__ = ["wl_subtree_kernel", "shortest_path_kernel", "hash_graph_kernel", "lsh_draws", "dense_label_ranks", "dataset_graphs",
-           "dataset_attributes", "svm_cv", "GraphSet"]
+           "dataset_attributes", "svm_cv", "svm_fit", "svm_decision", "svm_predict", "SvmBatch",
+           "GraphSet"]
 
 
 def dense_label_ranks(labels):
@@ -387,19 +396,162 @@ def dataset_graphs(obj):
     return adjs, np.asarray(nn, np.int32), labels, y
 
 
-def svm_cv(K, y, test_splits=5, C_grid=None, idx_train_val=None, idx_test=None, val_splits=None):
-    """The nested KFold / SVC(kernel="precomputed") loop of gk.py:243-292 on the host.  For each outer split every C of the
+SVM_DEVICE = False           # svm_cv(device=None): the host route (scikit-learn), whose numbers every earlier result holds
+
+
+class SvmBatch:
+    """What svm_fit returns: the fits of F training sets x the C grid, every fit classes (classes - 1) / 2 one-vs-one problems.
+    classes: the sorted labels; codes [G] the class index of every row of K (host; labels: the same on the device);
+    train: ops.SvmSets, set f * pairs + s = the rows of training set f that belong to pair s, the pair's first class first and +1;
+    problem ((f * len(C_grid)) + c) * pairs + s; alpha [P, train.max_rows], rho [P], n_iter [P] on the device; slices: launches."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def problem(self, fit, c, pair=0):
+        return (fit * len(self.C_grid) + c) * self.pairs + pair
+
+
+def _device_gram(K):
+    """K as a contiguous float64 device tensor: a device tensor of that form is returned as it is (read in place), an array is uploaded."""
+    if not torch.is_tensor(K):
+        K = torch.from_numpy(np.ascontiguousarray(K, np.float64))
+    if K.is_cuda and K.dtype == torch.float64:
+        return K.contiguous()
+    return K.to(device="cuda", dtype=torch.float64).contiguous()
+
+
+@torch.no_grad()
+def svm_fit(K, y, train_sets, C_grid, tol=1e-3, max_iter=None, iters_per_launch=None):
+    """SVC(kernel="precomputed", C=C, tol=tol).fit(K[tr][:, tr], y[tr]) for every tr of train_sets and every C of C_grid as ONE
+    batch on the device (ops.svm_smo_batch: libsvm's SMO in fp64, no shrinking, bounded launches) -> SvmBatch.  K [G, G]: a device
+    tensor (read in place) or an array; y [G] any labels.  More than two classes: libsvm's one-vs-one problems, built here.
+    A training set that holds one class raises ValueError, as SVC.fit does; so does one that lacks a class of y (SVC would drop
+    the class; the batch keeps one class list).  A problem that reaches max_iter raises ops.SvmNotConverged."""
+    K = _device_gram(K)
+    G = int(K.shape[0])
+    y = np.asarray(y).reshape(-1)
+    if y.shape[0] != G:
+        raise ValueError("y holds %d labels for a %d-row K" % (y.shape[0], G))
+    classes, codes = np.unique(y, return_inverse=True)
+    codes = codes.reshape(-1).astype(np.int32)
+    k = int(classes.shape[0])
+    if k > ops.SVM_MAX_CLASSES:
+        raise ValueError("%d classes, up to %d" % (k, ops.SVM_MAX_CLASSES))
+    C_grid = np.asarray(C_grid, np.float64).reshape(-1)
+    pair_list = [(a, b) for a in range(k) for b in range(a + 1, k)]
+    sets, signs = [], []
+    train_sets = [np.asarray(tr, np.int64).reshape(-1) for tr in train_sets]
+    for f, tr in enumerate(train_sets):
+        if tr.size and (tr.min() < 0 or tr.max() >= G):
+            raise ValueError("training set %d names a row outside 0..%d" % (f, G - 1))
+        present = np.unique(codes[tr])
+        if present.size < 2:
+            raise ValueError("The number of classes has to be greater than one; got %d class (training set %d)" % (present.size, f))
+        if present.size < k:
+            raise ValueError("training set %d holds %d of the %d classes of y; every training set must hold them all" % (f, present.size, k))
+        for a, b in pair_list:                                       # svm.cpp svm_train: the rows of class a, then those of class b
+            rows = np.concatenate([tr[codes[tr] == a], tr[codes[tr] == b]])
+            sets.append(rows)
+            signs.append(np.where(codes[rows] == a, 1, -1))
+    train = ops.SvmSets(sets, signs, graphs=G, device=K.device)
+    F, nC, pairs = len(train_sets), C_grid.shape[0], len(pair_list)
+    fit_of, c_of, pair_of = np.unravel_index(np.arange(F * nC * pairs), (F, nC, pairs)) if F * nC * pairs else (np.zeros(0, np.int64),) * 3
+    prob_set, prob_C = fit_of * pairs + pair_of, C_grid[c_of] if nC else np.zeros(0)
+    alpha, rho, n_iter, status, slices = ops.svm_smo_batch(K, train, prob_set, prob_C, tol=tol, max_iter=max_iter,
+                                                           iters_per_launch=iters_per_launch)
+    return SvmBatch(classes=classes, codes=codes, labels=torch.from_numpy(codes).to(K.device), train=train, train_sets=train_sets,
+                    C_grid=C_grid, pairs=pairs, pair_list=pair_list, prob_set=prob_set.astype(np.int32), prob_C=prob_C, alpha=alpha,
+                    rho=rho, n_iter=n_iter, status=status, slices=slices, tol=float(tol))
+
+
+def _eval_lists(batch, eval_sets):
+    F = len(batch.train_sets)
+    if len(eval_sets) != F:
+        raise ValueError("eval_sets must hold one entry (an index array or a list of them) for each of the %d training sets" % F)
+    out = []
+    for e in eval_sets:
+        one = isinstance(e, np.ndarray) or (len(e) > 0 and np.isscalar(e[0]))
+        out.append([np.asarray(e, np.int64).reshape(-1)] if one else [np.asarray(x, np.int64).reshape(-1) for x in e])
+    return out
+
+
+def _svm_jobs(batch, K, eval_sets):
+    """-> (dec flat device, job_out, errors, the evaluation SvmSets, groups [(fit, c, e, first job, evaluation set)]: the jobs of a
+    group are its pair problems in libsvm's order)."""
+    K = _device_gram(K)
+    lists = _eval_lists(batch, eval_sets)
+    ev = ops.SvmSets([x for l in lists for x in l], graphs=int(K.shape[0]), device=K.device)
+    first = np.concatenate([[0], np.cumsum([len(l) for l in lists])])
+    groups, job_prob, job_eval = [], [], []
+    for f, l in enumerate(lists):
+        for c in range(len(batch.C_grid)):
+            for e in range(len(l)):
+                groups.append((f, c, e, len(job_prob), int(first[f] + e)))
+                for s in range(batch.pairs):
+                    job_prob.append(batch.problem(f, c, s))
+                    job_eval.append(first[f] + e)
+    dec, job_out, errors = ops.svm_decision_batch(K, batch.train, batch.prob_set, batch.alpha, batch.rho, ev, job_prob, job_eval,
+                                                  check_errors=False)
+    return dec, job_out, errors, ev, groups
+
+
+def _nested(batch, groups, values):
+    out = [[[] for _ in batch.C_grid] for _ in batch.train_sets]
+    for (f, c, _, _, _), v in zip(groups, values):
+        out[f][c].append(v)
+    return out
+
+
+@torch.no_grad()
+def svm_decision(batch, K, eval_sets):
+    """decision_function of every fit of `batch` on its evaluation rows: eval_sets[f] an index array, or a list of them (validation,
+    test, ...), for training set f -> out[f][c][e], a host float64 array: two classes [rows], scikit-learn's sign (>= 0 predicts
+    classes[1]); more classes [rows, pairs], libsvm's one-vs-one values (SVC(decision_function_shape="ovo"))."""
+    dec, job_out, errors, ev, groups = _svm_jobs(batch, K, eval_sets)
+    ops._svm_refuse_errors(errors, "svm_decision")
+    d = dec.cpu().numpy()
+    vals = []
+    for _, _, _, q, _ in groups:
+        block = np.stack([d[job_out[q + s]:job_out[q + s + 1]] for s in range(batch.pairs)], axis=1)
+        vals.append(-block[:, 0] if len(batch.classes) == 2 else block)
+    return _nested(batch, groups, vals)
+
+
+@torch.no_grad()
+def svm_predict(batch, K, eval_sets, return_correct=False):
+    """predict of every fit on its evaluation rows (the decision and vote kernels, one read-back) -> out[f][c][e]: the predicted labels;
+    return_correct: also correct[f][c][e], the number of rows whose prediction equals y."""
+    dec, job_out, errors, ev, groups = _svm_jobs(batch, K, eval_sets)
+    pred, vote_out, counts = ops.svm_vote(dec, job_out, ev, [g[3] for g in groups], [g[4] for g in groups], len(batch.classes),
+                                          batch.labels, check_errors=False)
+    host = torch.cat([counts, errors]).cpu().numpy()                  # the one read-back: correct counts and both error words
+    if host[-1] or host[-2]:
+        raise _lib.KgcnHipError("svm_predict: the device found %d descriptors out of range" % int(host[-1] + host[-2]))
+    p = pred.cpu().numpy()
+    preds = _nested(batch, groups, [batch.classes[p[vote_out[i]:vote_out[i + 1]]] for i in range(len(groups))])
+    return (preds, _nested(batch, groups, [int(v) for v in host[:len(groups)]])) if return_correct else preds
+
+
+def svm_cv(K, y, test_splits=5, C_grid=None, idx_train_val=None, idx_test=None, val_splits=None, device=None, tol=1e-3):
+    """The nested KFold / SVC(kernel="precomputed") loop of gk.py:243-292.  For each outer split every C of the
     grid is fitted on each inner training fold; the C with the best mean validation accuracy gives the split's test accuracy
     (the mean over the inner folds, as the reference reports it).  Inner fold positions index idx_train_val (gk.py:264 uses
     them as global indices).  idx_train_val / idx_test: one explicit outer split instead of the KFold.
+    device: False the host route (scikit-learn, one fit after another), True the device route: all outer splits x inner folds x C
+    are ONE svm_fit, one decision launch and one vote, K a device tensor or an array; None reads SVM_DEVICE.  tol: SVC's tol on
+    the host route, the stopping tolerance of the device solver.  The two routes agree to that tolerance, not bit for bit.
     -> {"best_C", "val_acc", "test_acc": per outer split; "mean", "std": of test_acc; "fit_indices": the index array of every fit}."""
-    from sklearn.metrics import accuracy_score
-    from sklearn.model_selection import KFold
-    from sklearn.svm import SVC
-    K = np.asarray(K, np.float64)
+    device = SVM_DEVICE if device is None else bool(device)
     y = np.asarray(y).reshape(-1)
     C_grid = np.linspace(1e-4, 10, 5) if C_grid is None else np.asarray(C_grid, np.float64)
     val_splits = test_splits if val_splits is None else val_splits
+    if device:
+        return _svm_cv_device(K, y, test_splits, C_grid, idx_train_val, idx_test, val_splits, tol)
+    from sklearn.metrics import accuracy_score
+    from sklearn.model_selection import KFold
+    from sklearn.svm import SVC
+    K = np.asarray(K.cpu() if torch.is_tensor(K) else K, np.float64)
     if idx_train_val is None:
         outer = [(np.asarray(a), np.asarray(b)) for a, b in KFold(n_splits=test_splits).split(np.arange(K.shape[0]))]
     else:
@@ -413,13 +565,50 @@ def svm_cv(K, y, test_splits=5, C_grid=None, idx_train_val=None, idx_test=None, 
             base = K[:, tr]
             accs_v, accs_t = [], []
             for C in C_grid:
-                clf = SVC(kernel="precomputed", C=float(C))
+                clf = SVC(kernel="precomputed", C=float(C), tol=tol)
                 clf.fit(base[tr, :], y[tr])
                 accs_v.append(accuracy_score(y[va], clf.predict(base[va, :])))
                 accs_t.append(accuracy_score(y[te], clf.predict(base[te, :])))
             val.append(accs_v)
             test.append(accs_t)
         val, test = np.mean(val, axis=0), np.mean(test, axis=0)
+        best = int(np.argmax(val))
+        out["best_C"].append(float(C_grid[best]))
+        out["val_acc"].append(float(val[best]))
+        out["test_acc"].append(float(test[best]))
+    out["mean"] = float(np.mean(out["test_acc"]))
+    out["std"] = float(np.std(out["test_acc"]))
+    return out
+
+
+def _kfold(m, splits):
+    """KFold(n_splits=splits).split(range(m)) without shuffling -> [(train positions, test positions)]."""
+    if not 2 <= splits <= m:
+        raise ValueError("%d splits of %d samples" % (splits, m))
+    sizes = np.full(splits, m // splits, np.int64)
+    sizes[:m % splits] += 1
+    stops = np.cumsum(sizes)
+    return [(np.r_[0:s - z, s:m].astype(np.int64), np.arange(s - z, s, dtype=np.int64)) for s, z in zip(stops, sizes)]
+
+
+def _svm_cv_device(K, y, test_splits, C_grid, idx_train_val, idx_test, val_splits, tol):
+    K = _device_gram(K)
+    if idx_train_val is None:
+        outer = _kfold(int(K.shape[0]), test_splits)
+    else:
+        outer = [(np.asarray(idx_train_val, np.int64), np.asarray(idx_test, np.int64))]
+    trains, evals = [], []
+    for tv, te in outer:
+        for a, b in _kfold(len(tv), val_splits):
+            trains.append(tv[a])
+            evals.append([tv[b], te])
+    batch = svm_fit(K, y, trains, C_grid, tol=tol)
+    _, correct = svm_predict(batch, K, evals, return_correct=True)
+    out = {"best_C": [], "val_acc": [], "test_acc": [], "fit_indices": list(trains)}
+    for o in range(len(outer)):
+        fits = range(o * val_splits, (o + 1) * val_splits)
+        val = np.mean([[correct[f][c][0] / len(evals[f][0]) for c in range(len(C_grid))] for f in fits], axis=0)
+        test = np.mean([[correct[f][c][1] / len(evals[f][1]) for c in range(len(C_grid))] for f in fits], axis=0)
         best = int(np.argmax(val))
         out["best_C"].append(float(C_grid[best]))
         out["val_acc"].append(float(val[best]))

@@ -3403,3 +3403,234 @@ def sp_features_copies(csr, num_nodes, labels, copies, num_labels):
     return _two_pass_runs_copies(lambda rp, c, g, n, cap, ws, wsb: lib.kgcn_sp_features_copies_i32(
         ctypes.byref(csr.desc()), ptr(num_nodes), ptr(labels), R, int(num_labels), ptr(rp), ptr(c), ptr(g), ptr(n), cap, ptr(ws),
         wsb, current_stream()), T, R, csr.device, "kgcn_sp_features_copies_i32")
+
+
+# -------------------------------------------------------------------------------------------------
+# batched C-SVC over a precomputed kernel (csrc/svm.hip; the drivers are graph_kernel.svm_fit / svm_decision / svm_predict /
+# svm_cv): libsvm's SMO in fp64, one workgroup a problem, bounded launches.  fp64 and integers: bitwise reproducible.
+# -------------------------------------------------------------------------------------------------
+SVM_MAX_ROWS, SVM_MAX_CLASSES, SVM_DEFAULT_SLICE = (_lib.K[n] for n in ("KGCN_SVM_MAX_ROWS", "KGCN_SVM_MAX_CLASSES",
+                                                                        "KGCN_SVM_DEFAULT_SLICE"))
+SVM_RUNNING, SVM_CONVERGED, SVM_MAX_ITER, SVM_REFUSED = (_lib.K[n] for n in ("KGCN_SVM_RUNNING", "KGCN_SVM_CONVERGED",
+                                                                             "KGCN_SVM_MAX_ITER", "KGCN_SVM_REFUSED"))
+_SVM_MAX_GRAPHS = 46340              # what gram_from_runs builds
+
+
+class SvmNotConverged(_lib.KgcnHipError):
+    """svm_smo_batch stopped problems at max_iter.  problems: their indices; result: what svm_smo_batch would have returned
+    (the state after max_iter iterations, as libsvm returns it with a warning)."""
+
+    def __init__(self, problems, n_iter, result):
+        self.problems, self.result = problems, result
+        shown = ", ".join("%d (%d iterations)" % (p, n_iter[p]) for p in problems[:8])
+        super().__init__("svm_smo_batch: %d of %d problems reached max_iter before m(alpha) - M(alpha) < tol: problem %s%s"
+                         % (len(problems), len(n_iter), shown, ", ..." if len(problems) > 8 else ""))
+
+
+class SvmSets:
+    """Index sets into the rows of a Gram matrix, on the host (checked there) and on the device (read there): sets[s] an
+    integer array of rows of K; signs[s] (training sets) the label +1 / -1 of each entry, None for evaluation sets."""
+
+    def __init__(self, sets, signs=None, graphs=None, device="cuda"):
+        import numpy as np
+        sets = [np.asarray(s, np.int64).reshape(-1) for s in sets]
+        self.lengths = np.array([s.shape[0] for s in sets], np.int64)
+        self.count, self.total = len(sets), int(self.lengths.sum())
+        self.max_rows = int(self.lengths.max()) if sets else 0
+        self.ptr_host = np.concatenate([[0], np.cumsum(self.lengths)]).astype(np.int64)
+        self.idx_host = (np.concatenate(sets) if self.total else np.zeros(0, np.int64)).astype(np.int64)
+        if self.total and (self.idx_host.min() < 0 or (graphs is not None and self.idx_host.max() >= graphs)):
+            raise ValueError("an index set names a row outside 0..%s" % ("?" if graphs is None else graphs - 1))
+        if self.total and self.idx_host.max() >= 2 ** 31 - 1:
+            raise ValueError("row indices are int32")
+        self.sign_host = None
+        if signs is not None:
+            signs = [np.asarray(s).reshape(-1) for s in signs]
+            if len(signs) != len(sets) or any(a.shape != b.shape for a, b in zip(signs, sets)):
+                raise ValueError("signs must match the sets entry for entry")
+            self.sign_host = (np.concatenate(signs) if self.total else np.zeros(0)).astype(np.int8)
+            if self.total and not np.all(np.abs(np.concatenate(signs)) == 1):
+                raise ValueError("signs must be +1 or -1")
+        self.ptr = torch.from_numpy(self.ptr_host).to(device)
+        self.idx = torch.from_numpy(np.concatenate([self.idx_host.astype(np.int32), np.zeros(1, np.int32)])).to(device)
+        self.sign = None if self.sign_host is None else torch.from_numpy(np.concatenate([self.sign_host, np.ones(1, np.int8)])).to(device)
+        self.device = self.ptr.device
+
+    def rows(self, s):
+        return self.idx_host[self.ptr_host[s]:self.ptr_host[s + 1]]
+
+    def args(self):
+        """What the C entry points take for a list of sets: (ptr, idx, [sign,] count, total, max_rows)."""
+        signs = () if self.sign is None else (ptr(self.sign),)
+        return (ptr(self.ptr), ptr(self.idx)) + signs + (self.count, self.total, self.max_rows)
+
+
+def _svm_gram(K, who):
+    require_gpu(K, "K")
+    if K.dtype != torch.float64 or K.dim() != 2 or K.shape[0] != K.shape[1] or not K.is_contiguous() or not 1 <= K.shape[0] <= _SVM_MAX_GRAPHS:
+        raise _lib.KgcnHipError("%s: K must be a contiguous square float64 device matrix of 1..%d rows, got %s %s"
+                                % (who, _SVM_MAX_GRAPHS, K.dtype, tuple(K.shape)))
+    return int(K.shape[0])
+
+
+def _svm_host_i32(a, name, n, lo, hi, who):
+    import numpy as np
+    a = np.asarray(a, np.int64).reshape(-1)
+    if a.shape[0] != n or (n and (a.min() < lo or a.max() >= hi)):
+        raise ValueError("%s: %s must hold %d values in %d..%d" % (who, name, n, lo, hi - 1))
+    return a.astype(np.int32)
+
+
+def _svm_train_sets(sets, G, who):
+    if not isinstance(sets, SvmSets) or sets.sign is None:
+        raise _lib.KgcnHipError("%s: the training sets must be an SvmSets with signs" % who)
+    if sets.total and sets.idx_host.max() >= G:
+        raise ValueError("%s: a training set names row %d of a %d-row K" % (who, int(sets.idx_host.max()), G))
+    if sets.max_rows > SVM_MAX_ROWS:
+        raise _lib.KgcnHipError("%s: %d training rows in one set, up to %d (G, alpha and QD of a problem live in LDS); refused before "
+                                "any launch" % (who, sets.max_rows, SVM_MAX_ROWS))
+    if sets.count and sets.lengths.min() < 1:
+        raise ValueError("%s: an empty training set" % who)
+
+
+@torch.no_grad()
+def svm_smo_batch(K, sets, prob_set, prob_C, tol=1e-3, max_iter=None, iters_per_launch=None):
+    """Solve P C-SVC duals over the one Gram matrix K [G, G] float64 on the device: problem p trains on set prob_set[p] of `sets` (an
+    SvmSets with signs) with C = prob_C[p].  -> (alpha [P, sets.max_rows] float64, rho [P] float64, n_iter [P] int64 device tensors;
+    status [P] host int32 of SVM_* codes; the number of launches).  Each launch runs at most iters_per_launch (default
+    SVM_DEFAULT_SLICE) iterations a problem and one word is read back after it; slicing changes no bit.  max_iter None: libsvm's
+    max(10^7, 100 n) per problem.  A problem that reaches max_iter raises SvmNotConverged (which carries the state): unconverged
+    coefficients are never returned silently.  Sets of more than SVM_MAX_ROWS rows are refused before any launch."""
+    import numpy as np
+    who = "svm_smo_batch"
+    G = _svm_gram(K, who)
+    _svm_train_sets(sets, G, who)
+    P = len(np.asarray(prob_set).reshape(-1))
+    ps = _svm_host_i32(prob_set, "prob_set", P, 0, max(sets.count, 1), who)
+    pc = np.asarray(prob_C, np.float64).reshape(-1)
+    if pc.shape[0] != P or not np.all((pc > 0) & np.isfinite(pc)):
+        raise ValueError("%s: prob_C must hold %d positive finite values" % (who, P))
+    tol = float(tol)
+    if not 0.0 < tol < float("inf"):
+        raise ValueError("%s: tol must be positive and finite, got %r" % (who, tol))
+    ipl = SVM_DEFAULT_SLICE if iters_per_launch is None else int(iters_per_launch)
+    cap = 0 if max_iter is None else int(max_iter)
+    if ipl < 1 or ipl >= 2 ** 31 or (max_iter is not None and cap < 1):
+        raise ValueError("%s: iters_per_launch and max_iter must be at least 1" % who)
+    dev = K.device
+    stride = max(sets.max_rows, 1)
+    alpha = torch.zeros((P, stride), device=dev, dtype=torch.float64)
+    rho = torch.zeros((P,), device=dev, dtype=torch.float64)
+    n_iter = torch.zeros((P,), device=dev, dtype=torch.int64)
+    status = torch.zeros((P,), device=dev, dtype=torch.int32)
+    if P == 0:
+        return alpha, rho, n_iter, np.zeros(0, np.int32), 0
+    d_ps, d_pc = torch.from_numpy(ps).to(dev), torch.from_numpy(pc).to(dev)
+    ws, wsb = _ws_bytes(lib.kgcn_svm_workspace_bytes(P, stride), "kgcn_svm_workspace_bytes", dev)
+    word = ws[(-ws.data_ptr()) % 256:][:4].view(torch.int32)          # the entry point aligns the workspace to 256 bytes
+    longest = max(int(10_000_000), 100 * stride) if max_iter is None else cap
+    slices = 0
+    while True:
+        check(lib.kgcn_svm_smo_f64(ptr(K), G, *sets.args(), ptr(d_ps), ptr(d_pc), P, ctypes.byref(ctypes.c_double(tol)), cap, ipl,
+                                   1 if slices == 0 else 0, ptr(alpha), ptr(rho), ptr(n_iter), ptr(status), ptr(ws), wsb,
+                                   current_stream()), "kgcn_svm_smo_f64")
+        slices += 1
+        if int(word.item()) == 0:
+            break
+        if slices > longest // ipl + 2:
+            raise _lib.KgcnHipError("%s: problems still running after %d launches of %d iterations" % (who, slices, ipl))
+    st = status.cpu().numpy()
+    refused = np.flatnonzero(st == SVM_REFUSED)
+    if refused.size:
+        raise _lib.KgcnHipError("%s: the device refused the descriptors of %d problems (first: %d)" % (who, refused.size, refused[0]))
+    result = (alpha, rho, n_iter, st, slices)
+    late = np.flatnonzero(st != SVM_CONVERGED)
+    if late.size:
+        raise SvmNotConverged([int(p) for p in late], n_iter.cpu().numpy(), result)
+    return result
+
+
+def _svm_refuse_errors(errors, who):
+    bad = int(errors.item())
+    if bad:
+        raise _lib.KgcnHipError("%s: the device found %d descriptors out of range; nothing was written for them" % (who, bad))
+
+
+@torch.no_grad()
+def svm_decision_batch(K, sets, prob_set, alpha, rho, eval_sets, job_prob, job_eval, check_errors=True):
+    """Decision values of jobs (problem job_prob[q], evaluation set job_eval[q] of the SvmSets eval_sets) -> (dec flat float64 device
+    tensor, job_out host int64 [jobs + 1]: job q owns dec[job_out[q]:job_out[q + 1]], one value a row of its set; errors [1] device).
+    dec = sum_t (alpha_t y_t) K[row, idx_t] - rho, t ascending over all training rows (libsvm's sign: positive is the +1 class)."""
+    import numpy as np
+    who = "svm_decision_batch"
+    G = _svm_gram(K, who)
+    _svm_train_sets(sets, G, who)
+    if not isinstance(eval_sets, SvmSets):
+        raise _lib.KgcnHipError("%s: the evaluation sets must be an SvmSets" % who)
+    if eval_sets.total and eval_sets.idx_host.max() >= G:
+        raise ValueError("%s: an evaluation set names row %d of a %d-row K" % (who, int(eval_sets.idx_host.max()), G))
+    P = len(np.asarray(prob_set).reshape(-1))
+    ps = _svm_host_i32(prob_set, "prob_set", P, 0, max(sets.count, 1), who)
+    J = len(np.asarray(job_prob).reshape(-1))
+    jp = _svm_host_i32(job_prob, "job_prob", J, 0, max(P, 1), who)
+    je = _svm_host_i32(job_eval, "job_eval", J, 0, max(eval_sets.count, 1), who)
+    if J > 65535:
+        raise ValueError("%s: %d jobs, up to 65,535 a call" % (who, J))
+    stride = max(sets.max_rows, 1)
+    _dev_tensor(alpha, "alpha", torch.float64, (P, stride), who), _dev_tensor(rho, "rho", torch.float64, (P,), who)
+    job_out = np.concatenate([[0], np.cumsum(eval_sets.lengths[je])]).astype(np.int64)
+    total, dev = int(job_out[-1]), K.device
+    dec = torch.zeros((max(total, 1),), device=dev, dtype=torch.float64)
+    errors = torch.zeros((1,), device=dev, dtype=torch.int64)
+    d_ps, d_jp, d_je, d_jo = (torch.from_numpy(a).to(dev) for a in (ps, jp, je, job_out))
+    check(lib.kgcn_svm_decision_f64(ptr(K), G, *sets.args(), ptr(d_ps), P, ptr(alpha), ptr(rho), *eval_sets.args(), ptr(d_jp), ptr(d_je),
+                                    ptr(d_jo), J, ptr(dec), total, ptr(errors), current_stream()), "kgcn_svm_decision_f64")
+    if check_errors:
+        _svm_refuse_errors(errors, who)
+    return dec[:total], job_out, errors
+
+
+@torch.no_grad()
+def svm_vote(dec, job_out, eval_sets, vote_first_job, vote_eval, classes, labels, check_errors=True):
+    """libsvm's one-vs-one vote: vote v reads the classes (classes - 1) / 2 consecutive jobs from vote_first_job[v] (pair order (0, 1),
+    (0, 2), ..., (1, 2), ...; all on evaluation set vote_eval[v]) -> (pred flat int32 class indices, vote_out host int64 [votes + 1],
+    counts int64 [votes + 1] on the device: counts[v] = rows of vote v whose prediction equals labels[row], counts[votes] = descriptors
+    the device refused -- one read-back serves a whole nested cross-validation).  labels [G] int32 device: class index of every row of K.
+    Two classes: class 1 unless dec > 0 (scikit-learn: classes_[1] where its decision_function >= 0)."""
+    import numpy as np
+    who = "svm_vote"
+    classes = int(classes)
+    if not 2 <= classes <= SVM_MAX_CLASSES:
+        raise ValueError("%s: %d classes, 2..%d" % (who, classes, SVM_MAX_CLASSES))
+    if not isinstance(eval_sets, SvmSets):
+        raise _lib.KgcnHipError("%s: the evaluation sets must be an SvmSets" % who)
+    job_out = np.ascontiguousarray(job_out, np.int64).reshape(-1)
+    J, npairs = job_out.shape[0] - 1, classes * (classes - 1) // 2
+    total = int(job_out[-1]) if J >= 0 else 0
+    require_gpu(dec, "dec")
+    if J < 0 or dec.dtype != torch.float64 or not dec.is_contiguous() or dec.numel() != total:
+        raise _lib.KgcnHipError("%s: dec must be a contiguous float64 device tensor of job_out[-1] = %d values" % (who, total))
+    G = int(labels.numel())
+    _dev_tensor(labels, "labels", torch.int32, (G,), who)
+    if eval_sets.total and eval_sets.idx_host.max() >= G:
+        raise ValueError("%s: an evaluation set names row %d, labels holds %d" % (who, int(eval_sets.idx_host.max()), G))
+    V = len(np.asarray(vote_first_job).reshape(-1))
+    vf = _svm_host_i32(vote_first_job, "vote_first_job", V, 0, max(J - npairs + 1, 1), who)
+    ve = _svm_host_i32(vote_eval, "vote_eval", V, 0, max(eval_sets.count, 1), who)
+    if V > 65535:
+        raise ValueError("%s: %d votes, up to 65,535 a call" % (who, V))
+    m = eval_sets.lengths[ve]
+    for s in range(npairs):
+        if V and not np.array_equal(job_out[vf + s + 1] - job_out[vf + s], m):
+            raise ValueError("%s: the jobs of a vote do not all cover its evaluation set" % who)
+    vote_out = np.concatenate([[0], np.cumsum(m)]).astype(np.int64)
+    ptotal, dev = int(vote_out[-1]), dec.device
+    pred = torch.zeros((max(ptotal, 1),), device=dev, dtype=torch.int32)
+    counts = torch.zeros((V + 1,), device=dev, dtype=torch.int64)
+    d_jo, d_vf, d_ve, d_vo = (torch.from_numpy(a).to(dev) for a in (job_out, vf, ve, vote_out))
+    dec1 = dec if total else torch.zeros((1,), device=dev, dtype=torch.float64)
+    check(lib.kgcn_svm_vote_i32(ptr(dec1), total, ptr(d_jo), J, *eval_sets.args(), ptr(d_vf), ptr(d_ve), ptr(d_vo), V, classes, ptr(labels),
+                                G, ptr(pred), ptotal, ptr(counts), ptr(counts[V:]), current_stream()), "kgcn_svm_vote_i32")
+    if check_errors:
+        _svm_refuse_errors(counts[V], who)
+    return pred[:ptotal], vote_out, counts
