@@ -101,7 +101,9 @@ extern "C" {
  * (+ kgcn_wl_rank_copies_workspace_bytes), kgcn_wl_runs_copies_i32, kgcn_sp_features_copies_i32
  * (+ kgcn_graph_runs_copies_workspace_bytes).
  * The batched kernel SVM added entry points only (version still 2): kgcn_svm_smo_f64 (+ kgcn_svm_workspace_bytes),
- * kgcn_svm_decision_f64, kgcn_svm_vote_i32. */
+ * kgcn_svm_decision_f64, kgcn_svm_vote_i32.
+ * Active learning added entry points only (version still 2): kgcn_rbf_affinity_f64, kgcn_lp_degrees_f64, kgcn_lp_propagate_f64
+ * (+ kgcn_lp_workspace_bytes), kgcn_lp_finish_f64, kgcn_lp_scores_f64, kgcn_lp_select_f64. */
 #define KGCN_HIP_ABI_VERSION 2
 
 /* Column index of the padding entries of a row-padded batch (see row_pad): they carry value 0 and
@@ -1227,6 +1229,74 @@ int kgcn_svm_vote_i32(const double* dec, int64_t dec_total, const int64_t* job_o
                       const int32_t* vote_first_job, const int32_t* vote_eval, const int64_t* vote_out, int32_t votes,
                       int32_t classes, const int32_t* labels, int32_t graphs, int32_t* pred, int64_t pred_total, int64_t* correct,
                       int64_t* errors, void* stream);
+
+/* -- active learning: label propagation and query scoring (csrc/labelprop.hip; kgcn_amd/active_learning.py) -----------------------
+ * active_learning/models.py of the reference fits scikit-learn's LabelPropagation / LabelSpreading once per task and scores the
+ * unlabelled rows.  Here ONE affinity matrix W [n, n] fp64 (row-major) serves every task and every query over the same points; the
+ * variants' scalings are applied to W F instead of being stored as a second matrix.  fp64 and integers, no float atomics, nothing
+ * fused: a pure function of the input.  "The lane tree": of 64 values v_0 .. v_63, v_l = v_l + v_(l ^ off) for off = 32, 16, 8, 4,
+ * 2, 1 in turn.  All arrays on the device unless said otherwise; doubles are passed by address (host memory).  Asynchronous.
+ *
+ *   kgcn_rbf_affinity_f64   x [n, d] -> W_ij = exp(-gamma max(0, (|x_i|^2 + |x_j|^2) - 2 x_i.x_j)), W_ii = exp(-0) = 1
+ *       (sklearn.metrics.pairwise.rbf_kernel).  norms [n] receives |x_i|^2 = acc + x_ik x_ik for k ascending from +0.0.  The dot
+ *       products are formed on v_mfma_f64_16x16x4_f64 (its internal order and the device exp are not restated: W is compared by
+ *       tolerance).  Entries with i <= j are computed and stored at (i, j) and (j, i): W is symmetric bit for bit.  Refused before
+ *       any launch: n * n * 8 > max_bytes, n > KGCN_LP_MAX_ROWS.
+ *   kgcn_lp_degrees_f64     s_i = sum_j W_ij (LabelPropagation's normaliser), d_i = the same with the term j = i replaced by +0.0 (the
+ *       degree of scipy's normed Laplacian).  Lane l adds j = l, l + 64, ... ascending from +0.0; then the lane tree.
+ *   kgcn_lp_propagate_f64   the label block F [n, cols] holds the class columns of task t at task_col[t] .. task_col[t + 1] (task_col
+ *       [tasks + 1] ascending from 0 to cols, every task at least one column); labels [n, tasks] = the class index inside the task or
+ *       -1.  first_step == 0 starts: F = one-hot labels, status = KGCN_LP_RUNNING, n_iter = 0.  Then `steps` steps, numbered from
+ *       first_step.  A step, for the tasks still running:
+ *         raw_ic = sum_j w_ij G_jc: lane l adds the rounded products for j = l, l + 64, ... ascending from +0.0, then the lane tree;
+ *         propagation (scale = s): G = F, w = W; v_c = raw_ic / s_i; norm = the v_c of the task added in column order from +0.0
+ *           (0 counts as 1); F'_ic = v_c / norm on rows with label -1 in the task, the one-hot label on the others;
+ *         spreading (scale = d): G_jc = F_jc / q_j with q_j = sqrt(d_j) (1 where d_j = 0), w = W without its diagonal;
+ *           F'_ic = alpha (raw_ic / q_i) + (1 - alpha) onehot_ic;
+ *         delta (row, task) = |F'_ic - F_ic| added in column order from +0.0; the partial of a block of KGCN_LP_BLOCK_ROWS rows = its
+ *           rows' deltas added in row order from +0.0; the task's sum = the partials added in block order from +0.0.
+ *       After step number k - 1 (and, with k = 0, after the start, where the sum is over |F|) a running task with k >= max_iter gets
+ *       KGCN_LP_MAX_ITER and n_iter = max_iter, otherwise one whose sum < *tol gets KGCN_LP_CONVERGED and n_iter = k
+ *       (BaseLabelPropagation.fit).  A task that is not running is frozen: its columns keep their bits.  The first 4 bytes of the
+ *       256-byte aligned workspace hold the number of tasks still running: the one word a caller reads back, after as many steps
+ *       as it likes; how the steps are cut into calls changes no bit and no n_iter.  *alpha is read for spreading only.
+ *   kgcn_lp_finish_f64      dist [n, cols] = F / (the task's columns added in order from +0.0; 0 counts as 1) after steps_done steps in
+ *       all (the caller's count of the steps it asked for).
+ *   kgcn_lp_scores_f64      scores [5, m] of the rows cand [m] of dist (a row outside 0..n-1: NaN), p = the row's block of task t:
+ *         KGCN_LP_SCORE_E         sum over tasks, in task order from +0.0, of sum_c entr(p_c / sum_c p_c) (scipy.stats.entropy; both sums in
+ *                                 column order from +0.0; entr(0) = 0; an all-zero block gives NaN)
+ *         KGCN_LP_SCORE_LC_MEAN   1 - max_c mean_c, mean_c = (p_c added over the tasks in order from +0.0) / tasks (query_next_data_points)
+ *         KGCN_LP_SCORE_MS_MEAN   the largest minus the second largest mean_c; both _MEAN scores are NaN unless all tasks have the same
+ *                                 number of classes, MS_MEAN also with one class
+ *         KGCN_LP_SCORE_LC_TASKS  (max_c p_c added over the tasks from +0.0) / tasks (ActiveLearner.query)
+ *         KGCN_LP_SCORE_MS_TASKS  the tasks' margins added in order from +0.0: largest minus second largest p_c, the only column of a
+ *                                 one-class task
+ *   kgcn_lp_select_f64      out [k] = positions into cand, -1 where fewer than k take part.  THE TIE RULE: candidates are ordered as a
+ *       stable ascending sort orders them, NaN last (by score, then by position; all NaN equal).  largest != 0: out = the last k of
+ *       that order, in that order (out[k - 1] is the very last: the E / LC top-k of query_next_data_points, the E pick of
+ *       ActiveLearner.query); largest == 0: its first k (MS top-k; with k = 1 the first among equal minima, np.argmin).  numpy's
+ *       default argsort is not stable: where scores tie the reference's own order is unspecified.  active NULL or [n]: a candidate
+ *       whose row has active == 0 takes no part.  truth != NULL (k = 1 only) teaches the picked row on the device: labels[row, :] =
+ *       truth[row, :] ([n, tasks] both), active[row] = 0, log[0] = the picked position (log may be NULL).  1 <= k <= KGCN_LP_MAX_PICKS. */
+enum { KGCN_LP_MAX_ROWS = 131072, KGCN_LP_MAX_TASKS = 32, KGCN_LP_MAX_COLS = 64, KGCN_LP_BLOCK_ROWS = 32, KGCN_LP_MAX_PICKS = 8,
+       KGCN_LP_DEFAULT_CHECK = 8 };
+enum { KGCN_LP_PROPAGATION = 0, KGCN_LP_SPREADING = 1 };
+enum { KGCN_LP_RUNNING = 0, KGCN_LP_CONVERGED = 1, KGCN_LP_MAX_ITER = 2 };
+enum { KGCN_LP_SCORE_E = 0, KGCN_LP_SCORE_LC_MEAN = 1, KGCN_LP_SCORE_MS_MEAN = 2, KGCN_LP_SCORE_LC_TASKS = 3, KGCN_LP_SCORE_MS_TASKS = 4 };
+int kgcn_rbf_affinity_f64(const double* x, int64_t n, int32_t d, const double* gamma, int64_t max_bytes, double* W, double* norms,
+                          void* stream);
+int kgcn_lp_degrees_f64(const double* W, int64_t n, double* s_out, double* d_out, void* stream);
+int64_t kgcn_lp_workspace_bytes(int64_t n, int32_t tasks, int32_t cols);
+int kgcn_lp_propagate_f64(const double* W, const double* scale, int64_t n, const int32_t* labels, const int32_t* task_col,
+                          int32_t tasks, int32_t cols, int32_t variant, const double* alpha, const double* tol, int32_t max_iter,
+                          int32_t first_step, int32_t steps, int32_t* n_iter, int32_t* status, void* workspace, int64_t workspace_bytes,
+                          void* stream);
+int kgcn_lp_finish_f64(int64_t n, const int32_t* task_col, int32_t tasks, int32_t cols, int32_t steps_done, double* dist,
+                       const void* workspace, int64_t workspace_bytes, void* stream);
+int kgcn_lp_scores_f64(const double* dist, int64_t n, const int32_t* task_col, int32_t tasks, int32_t cols, const int32_t* cand,
+                       int64_t m, double* scores, void* stream);
+int kgcn_lp_select_f64(const double* score, const int32_t* cand, int64_t m, int64_t n, int32_t* active, int32_t k, int32_t largest,
+                       int32_t* out, int32_t* labels, const int32_t* truth, int32_t tasks, int32_t* log, void* stream);
 
 /* -- k-fold cross-validation of the compound-protein interaction networks (gcn.py train_cv; csrc/cvloss.hip, csrc/cvmetrics.hip)
  * Loss head of sample_chem/compound-protein_interaction/multitask.py:53-86 (singletask.py: tasks = 1): logits [batch, 2, tasks],

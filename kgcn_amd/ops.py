@@ -3634,3 +3634,161 @@ def svm_vote(dec, job_out, eval_sets, vote_first_job, vote_eval, classes, labels
     if check_errors:
         _svm_refuse_errors(counts[V], who)
     return pred[:ptotal], vote_out, counts
+
+
+# -------------------------------------------------------------------------------------------------
+# active learning (csrc/labelprop.hip; the driver is kgcn_amd/active_learning.py): one RBF affinity matrix for every task and
+# every query over the same points, label propagation / spreading for all tasks in one sweep over it, uncertainty scores and
+# the pick on the device.  fp64 and integers, stated summation orders (include/kgcn_hip.h): bitwise reproducible.
+# -------------------------------------------------------------------------------------------------
+LP_MAX_ROWS, LP_MAX_TASKS, LP_MAX_COLS, LP_BLOCK_ROWS, LP_MAX_PICKS, LP_DEFAULT_CHECK = (_lib.K["KGCN_LP_" + n] for n in (
+    "MAX_ROWS", "MAX_TASKS", "MAX_COLS", "BLOCK_ROWS", "MAX_PICKS", "DEFAULT_CHECK"))
+LP_PROPAGATION, LP_SPREADING = _lib.K["KGCN_LP_PROPAGATION"], _lib.K["KGCN_LP_SPREADING"]
+LP_RUNNING, LP_CONVERGED, LP_MAX_ITER = _lib.K["KGCN_LP_RUNNING"], _lib.K["KGCN_LP_CONVERGED"], _lib.K["KGCN_LP_MAX_ITER"]
+LP_SCORES = {"E": _lib.K["KGCN_LP_SCORE_E"], "LC_MEAN": _lib.K["KGCN_LP_SCORE_LC_MEAN"], "MS_MEAN": _lib.K["KGCN_LP_SCORE_MS_MEAN"],
+             "LC_TASKS": _lib.K["KGCN_LP_SCORE_LC_TASKS"], "MS_TASKS": _lib.K["KGCN_LP_SCORE_MS_TASKS"]}
+LP_DEFAULT_MAX_BYTES = 16 << 30      # the affinity matrix of 46,340 points
+
+
+def _lp_matrix(W, who):
+    require_gpu(W, "W")
+    if W.dtype != torch.float64 or W.dim() != 2 or W.shape[0] != W.shape[1] or not W.is_contiguous() or not 1 <= W.shape[0] <= LP_MAX_ROWS:
+        raise _lib.KgcnHipError("%s: W must be a contiguous square float64 device matrix of 1..%d rows, got %s %s"
+                                % (who, LP_MAX_ROWS, W.dtype, tuple(W.shape)))
+    return int(W.shape[0])
+
+
+def _lp_task_col(task_col, who):
+    import numpy as np
+    tc = np.asarray(task_col, np.int64).reshape(-1)
+    T = tc.shape[0] - 1
+    if T < 1 or T > LP_MAX_TASKS or tc[0] != 0 or np.any(np.diff(tc) < 1) or tc[-1] > LP_MAX_COLS:
+        raise _lib.KgcnHipError("%s: task_col must ascend from 0 over 1..%d tasks of at least one class each, up to %d columns in "
+                                "all, got %s" % (who, LP_MAX_TASKS, LP_MAX_COLS, tc.tolist()))
+    return tc.astype(np.int32), T, int(tc[-1])
+
+
+@torch.no_grad()
+def rbf_affinity(X, gamma, max_bytes=LP_DEFAULT_MAX_BYTES):
+    """X [n, d] float64 on the device -> W [n, n] = exp(-gamma max(0, |x_i|^2 + |x_j|^2 - 2 x_i.x_j)) (sklearn's rbf_kernel), the dot
+    products on the fp64 matrix pipe; symmetric bit for bit, unit diagonal.  Refused before any launch: a matrix of more than
+    max_bytes bytes, more than LP_MAX_ROWS points, a gamma that is not positive and finite, an X that is not finite."""
+    who = "rbf_affinity"
+    require_gpu(X, "X")
+    if X.dtype != torch.float64 or X.dim() != 2 or not X.is_contiguous() or X.shape[0] < 1 or X.shape[1] < 1:
+        raise _lib.KgcnHipError("%s: X must be a contiguous [n, d] float64 device tensor, got %s %s" % (who, X.dtype, tuple(X.shape)))
+    n, d = int(X.shape[0]), int(X.shape[1])
+    gamma, max_bytes = float(gamma), int(max_bytes)
+    if n > LP_MAX_ROWS or n * n * 8 > max_bytes:
+        raise _lib.KgcnHipError("%s: the %d x %d affinity matrix takes %d bytes, over max_bytes = %d (or over %d points); refused "
+                                "before any launch" % (who, n, n, n * n * 8, max_bytes, LP_MAX_ROWS))
+    if not 0.0 < gamma < float("inf"):
+        raise _lib.KgcnHipError("%s: gamma must be positive and finite, got %r" % (who, gamma))
+    if not bool(torch.isfinite(X).all()):
+        raise _lib.KgcnHipError("%s: X holds values that are not finite; refused before any launch" % who)
+    W = torch.empty((n, n), device=X.device, dtype=torch.float64)
+    norms = torch.empty((n,), device=X.device, dtype=torch.float64)
+    check(lib.kgcn_rbf_affinity_f64(ptr(X), n, d, ctypes.byref(ctypes.c_double(gamma)), max_bytes, ptr(W), ptr(norms),
+                                    current_stream()), "kgcn_rbf_affinity_f64")
+    return W
+
+
+@torch.no_grad()
+def lp_degrees(W):
+    """-> (s, d) [n] float64: s_i = sum_j W_ij (LabelPropagation's normaliser) and d_i = the same without the diagonal term (the degree
+    of LabelSpreading's normed Laplacian); per row the columns j = l (mod 64) in ascending order, then the lane tree."""
+    n = _lp_matrix(W, "lp_degrees")
+    out = torch.empty((2, n), device=W.device, dtype=torch.float64)
+    check(lib.kgcn_lp_degrees_f64(ptr(W), n, ptr(out[0]), ptr(out[1]), current_stream()), "kgcn_lp_degrees_f64")
+    return out[0], out[1]
+
+
+@torch.no_grad()
+def lp_propagate(W, scale, labels, task_col, variant, alpha=0.2, tol=1e-3, max_iter=1000, iters_per_check=None):
+    """Label propagation (variant LP_PROPAGATION, scale = s of lp_degrees) or spreading (LP_SPREADING, scale = d) of all tasks at
+    once over W: labels [n, T] int32 on the device (class index inside the task, -1 = unlabelled), task_col [T + 1] on the host.
+    -> (dist [n, K] float64: the normalised label distributions, task t in columns task_col[t]:task_col[t + 1]; n_iter [T] and
+    status [T] int32, all on the device; the number of words read back).  Each task runs until its sum |F' - F| < tol
+    (LP_CONVERGED) or for max_iter steps (LP_MAX_ITER, n_iter = max_iter, as scikit-learn warns and goes on); a finished task
+    is frozen.  One word is read back per iters_per_check steps (default LP_DEFAULT_CHECK); the grouping changes no bit."""
+    who = "lp_propagate"
+    n = _lp_matrix(W, who)
+    tc, T, K = _lp_task_col(task_col, who)
+    _dev_tensor(scale, "scale", torch.float64, (n,), who), _dev_tensor(labels, "labels", torch.int32, (n, T), who)
+    if variant not in (LP_PROPAGATION, LP_SPREADING):
+        raise ValueError("%s: variant must be LP_PROPAGATION or LP_SPREADING" % who)
+    alpha, tol, max_iter = float(alpha), float(tol), int(max_iter)
+    ipc = LP_DEFAULT_CHECK if iters_per_check is None else int(iters_per_check)
+    if variant == LP_SPREADING and not 0.0 < alpha < 1.0:
+        raise ValueError("%s: alpha must lie in (0, 1), got %r" % (who, alpha))
+    if not 0.0 <= tol < float("inf") or not 1 <= max_iter < 2 ** 30 or ipc < 1:
+        raise ValueError("%s: tol %r, max_iter %r, iters_per_check %r" % (who, tol, max_iter, ipc))
+    dev = W.device
+    d_tc = torch.from_numpy(tc).to(dev)
+    meta = torch.zeros((2, T), device=dev, dtype=torch.int32)           # n_iter | status
+    dist = torch.empty((n, K), device=dev, dtype=torch.float64)
+    ws, wsb = _ws_bytes(lib.kgcn_lp_workspace_bytes(n, T, K), "kgcn_lp_workspace_bytes", dev)
+    word = ws[(-ws.data_ptr()) % 256:][:4].view(torch.int32)            # the entry point aligns the workspace to 256 bytes
+    c_alpha, c_tol = ctypes.c_double(alpha), ctypes.c_double(tol)
+    done = reads = 0
+    while True:
+        steps = min(ipc, max_iter - done)
+        check(lib.kgcn_lp_propagate_f64(ptr(W), ptr(scale), n, ptr(labels), ptr(d_tc), T, K, variant, ctypes.byref(c_alpha),
+                                        ctypes.byref(c_tol), max_iter, done, steps, ptr(meta[0]), ptr(meta[1]), ptr(ws), wsb,
+                                        current_stream()), "kgcn_lp_propagate_f64")
+        done += steps
+        reads += 1
+        if int(word.item()) == 0:
+            break
+        if done >= max_iter:
+            raise _lib.KgcnHipError("%s: tasks still running after max_iter = %d steps" % (who, max_iter))
+    check(lib.kgcn_lp_finish_f64(n, ptr(d_tc), T, K, done, ptr(dist), ptr(ws), wsb, current_stream()), "kgcn_lp_finish_f64")
+    return dist, meta[0], meta[1], reads
+
+
+@torch.no_grad()
+def lp_scores(dist, task_col, cand):
+    """Uncertainty scores of the rows cand [m] (int32, device) of dist [n, K] -> [5, m] float64, row LP_SCORES[name]: "E" the entropy
+    summed over tasks; "LC_MEAN" / "MS_MEAN" least confidence and margin of the mean distribution over tasks
+    (query_next_data_points; NaN unless all tasks have the same number of classes); "LC_TASKS" / "MS_TASKS" the mean of the
+    tasks' maxima and the sum of their margins (ActiveLearner.query)."""
+    who = "lp_scores"
+    tc, T, K = _lp_task_col(task_col, who)
+    require_gpu(dist, "dist")
+    if dist.dtype != torch.float64 or dist.dim() != 2 or dist.shape[1] != K or not dist.is_contiguous() or not 1 <= dist.shape[0] <= LP_MAX_ROWS:
+        raise _lib.KgcnHipError("%s: dist must be a contiguous [n, %d] float64 device tensor, got %s %s" % (who, K, dist.dtype, tuple(dist.shape)))
+    m = int(cand.numel())
+    _dev_tensor(cand, "cand", torch.int32, (m,), who)
+    scores = torch.empty((5, m), device=dist.device, dtype=torch.float64)
+    d_tc = torch.from_numpy(tc).to(dist.device)
+    check(lib.kgcn_lp_scores_f64(ptr(dist), int(dist.shape[0]), ptr(d_tc), T, K, ptr(cand), m, ptr(scores), current_stream()),
+          "kgcn_lp_scores_f64")
+    return scores
+
+
+@torch.no_grad()
+def lp_select(score, cand, n, k, largest, active=None, labels=None, truth=None, log=None):
+    """The k picks among the candidates cand [m] (rows of an n-row problem) by score [m] -> out [k] int32 positions into cand (-1
+    where fewer take part), in the order of a STABLE ascending sort with NaN last: its last k entries (largest) or its first k.
+    active [n] int32: rows with 0 take no part.  truth [n, T] (k = 1): the picked row is taught on the device -- labels[row] =
+    truth[row], active[row] = 0, log[0] = the position -- so a query-and-teach loop needs no read-back for it."""
+    who = "lp_select"
+    m, n, k = int(cand.numel()), int(n), int(k)
+    _dev_tensor(cand, "cand", torch.int32, (m,), who), _dev_tensor(score, "score", torch.float64, (m,), who)
+    if not 1 <= k <= LP_MAX_PICKS or not 1 <= n <= LP_MAX_ROWS:
+        raise _lib.KgcnHipError("%s: %d picks (1..%d) among rows of %d" % (who, k, LP_MAX_PICKS, n))
+    if active is not None:
+        _dev_tensor(active, "active", torch.int32, (n,), who)
+    T = 0
+    if truth is not None:
+        if k != 1 or labels is None or truth.dim() != 2:
+            raise _lib.KgcnHipError("%s: teaching takes the single pick (k = 1), labels and truth [n, T]" % who)
+        T = int(truth.shape[1])
+        _dev_tensor(truth, "truth", torch.int32, (n, T), who), _dev_tensor(labels, "labels", torch.int32, (n, T), who)
+        if log is not None:
+            _dev_tensor(log, "log", torch.int32, (1,), who)
+    out = torch.empty((k,), device=cand.device, dtype=torch.int32)
+    check(lib.kgcn_lp_select_f64(ptr(score), ptr(cand), m, n, ptr(active), k, 1 if largest else 0, ptr(out),
+                                 ptr(labels if truth is not None else None), ptr(truth), T, ptr(log), current_stream()),
+          "kgcn_lp_select_f64")
+    return out
