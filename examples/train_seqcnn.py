@@ -7,7 +7,9 @@ stand-in kept as a test fixture (tests/golden/g9_seqcnn.npz: two classes told ap
 dataset.jbl written by the sample's 02make_dataset.py.  The token table lives in HBM, every mini-batch is assembled on the device
 and the whole step is one hipGraph replay with the sequences as the model's forward keyword.  Prints cost and accuracy per epoch.
 
-    python examples/train_seqcnn.py [--epochs 20] [--batch-size 1] [--learning-rate 1e-4] [--dataset dataset.jbl]
+    python examples/train_seqcnn.py [--epochs 20] [--batch-size 1] [--learning-rate 1e-4] [--dataset dataset.jbl] [--save PATH]
+
+--save PATH writes the trained model's state dict (torch.save), which examples/visualize_seqcnn.py --params reads.
 """
 import argparse
 import os
@@ -25,6 +27,7 @@ ap.add_argument("--epochs", type=int, default=20)
 ap.add_argument("--batch-size", type=int, default=1)
 ap.add_argument("--learning-rate", type=float, default=1e-4)
 ap.add_argument("--dataset", default=None, help="dataset.jbl of 02make_dataset.py (default: the committed synthetic fixture)")
+ap.add_argument("--save", default=None, help="write the trained model's state dict here (torch.save)")
 args = ap.parse_args()
 
 dev = torch.device("cuda:0")
@@ -87,3 +90,6 @@ for epoch in range(args.epochs):
     print("epoch %3d  training cost %.5f  accuracy %.4f  validation cost %.5f  accuracy %.4f"
           % (epoch, cost / len(train_idx), right / len(train_idx), vcost, vacc))
 print("training cost %.5f -> %.5f over %d epochs" % (history[0], history[-1], args.epochs))
+if args.save:
+    torch.save(model.state_dict(), args.save)
+    print("state dict saved to %s" % args.save)

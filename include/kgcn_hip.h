@@ -103,7 +103,9 @@ extern "C" {
  * The batched kernel SVM added entry points only (version still 2): kgcn_svm_smo_f64 (+ kgcn_svm_workspace_bytes),
  * kgcn_svm_decision_f64, kgcn_svm_vote_i32.
  * Active learning added entry points only (version still 2): kgcn_rbf_affinity_f64, kgcn_lp_degrees_f64, kgcn_lp_propagate_f64
- * (+ kgcn_lp_workspace_bytes), kgcn_lp_finish_f64, kgcn_lp_scores_f64, kgcn_lp_select_f64. */
+ * (+ kgcn_lp_workspace_bytes), kgcn_lp_finish_f64, kgcn_lp_scores_f64, kgcn_lp_select_f64.
+ * Integrated gradients of the protein-sequence CNN added entry points only (version still 2): kgcn_ig_conv1d_expand_f32,
+ * kgcn_ig_conv1d_reduce_f32. */
 #define KGCN_HIP_ABI_VERSION 2
 
 /* Column index of the padding entries of a row-padded batch (see row_pad): they carry value 0 and
@@ -1424,6 +1426,38 @@ int kgcn_ig_copies_expand_f32(const float* P, int64_t compounds, int32_t copies,
                               float* Y, int64_t y_ld, void* stream);
 int kgcn_ig_copies_reduce_f32(const float* dY, int64_t dy_ld, const float* Y, int64_t y_ld, int64_t compounds, int32_t copies,
                               int32_t width, const float* w, const float* scale, int32_t act, float* S, void* stream);
+
+/* Integrated gradients of the protein-sequence CNN (kgcn visualize on sample_protein/sequence/cnn.py; kgcn/visualization.py:187-260):
+ * the sweeps over the `copies` scaled copies of `proteins` proteins through the model's first layer, Conv1D(filters, k, same, relu)
+ * -> MaxPooling1D(pool) (csrc/convig.hip; entry points only, version still 2; named kgcn_ig_conv1d_* beside kgcn_ig_copies_*, the
+ * kgcn_conv1d_* prefix being the layer's own set of entry points).  Copy k feeds alpha[k] e, alpha[k] >= 0, so its
+ * pre-activation is alpha[k] P + bias with P = conv(e) without the bias, and p -> relu(fl(fl(alpha p) + b)) is non-decreasing:
+ * the window maximum commutes with it, also after fp32 rounding.  The caller forms Pm [proteins, positions, filters] = the
+ * window maxima of P and their arg-max ONCE per protein with kgcn_conv1d_pool_fwd_f32 (zero bias, KGCN_ACT_NONE).
+ * expand: out [proteins copies, positions, filters], copy k of protein c in row c copies + k:
+ *     v = fl(fl(alpha[k] * Pm[c, t, f]) + bias[f]);  out[c copies + k, t, f] = v > 0 ? v : +0
+ *   -- two roundings, the product is NOT fused into the sum.  kgcn_conv1d_pool_fwd_f32 adds its bias AFTER the accumulation
+ *   (act(acc + bias), csrc/conv1d.hip), so at alpha[k] == 1 the row is bit for bit the first layer that kernel computes from e.
+ * reduce: dout (the gradient arriving at `out`) and out as above, w [copies] -> r [proteins, positions, filters] contiguous:
+ *     acc = +0;  for k = 0, 1, ..: if w[k] != 0 and out[c copies + k, t, f] > 0: acc = fl(acc + fl(w[k] * dout[c copies + k, t, f]))
+ *   in that order, unfused, without atomics.  A copy with w[k] == 0 is neither read nor added (its rows must exist; NaN there
+ *   never reaches the sum).  One kgcn_conv1d_pool_bwd_f32 (KGCN_ACT_NONE, dout = r, the arg-max and out of the Pm pass, dx only)
+ *   then gives sum_k w[k] d score_k / d (alpha[k] e), because conv is linear.
+ * Deviation from the per-copy route: where two candidates of a window of P differ but their scaled, biased values round to the same
+ * positive fp32 number, the per-copy kernel routes the gradient to the lowest index among the equal values and this route to the
+ * arg-max of P -- the one exact arithmetic picks.  (Where both are cut to 0 by the relu no gradient flows on either route.)
+ * Both: a protein's rows do not depend on the other proteins of the call (chunking changes no bit); bitwise reproducible; the
+ * accesses are 16 bytes wide along (t, f) and 4-byte aligned, the last n mod 4 floats of a row (n = positions filters) go float by
+ * float, nothing past a row is touched.  proteins == 0 is a no-op.  Scales are checked by the caller (kgcn_amd.ops refuses a
+ * negative or non-finite one before any launch).
+ * Limits: positions <= KGCN_CONV1D_MAX_LENGTH, filters <= KGCN_CONV1D_MAX_CHANNELS, 1 <= copies <= KGCN_CONV1D_IG_MAX_COPIES,
+ * proteins copies < 2^31 and a grid below 2^31 workgroups (pass fewer proteins); anything else is refused before any launch.
+ * Asynchronous. */
+enum { KGCN_CONV1D_IG_MAX_COPIES = 1024 };
+int kgcn_ig_conv1d_expand_f32(const float* Pm, int64_t proteins, int32_t copies, int32_t positions, int32_t filters,
+                              const float* alpha, const float* bias, float* out, void* stream);
+int kgcn_ig_conv1d_reduce_f32(const float* dout, const float* out, int64_t proteins, int32_t copies, int32_t positions,
+                              int32_t filters, const float* w, float* r, void* stream);
 
 #ifdef __cplusplus
 }

@@ -647,8 +647,10 @@ class SeqCNN(nn.Module):
             raise ValueError("class_weight has %d entries for %d classes" % (cw.numel(), self.label_dim))
         self.register_buffer("class_weight", cw)
 
-    def forward(self, features=None, adjs=None, sequences=None, embedded=None):
-        if embedded is not None:
+    def forward(self, features=None, adjs=None, sequences=None, embedded=None, first=None):
+        if first is not None:                                                                     # the first layer's output itself
+            layer = first
+        elif embedded is not None:
             layer = self.convs[0](embedded)                                                       # :39-40
         elif sequences is not None:
             layer = self.convs[0](tokens=sequences, table=self.embeddings)

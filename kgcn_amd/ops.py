@@ -2341,6 +2341,112 @@ def embedding_grad(tokens, dembedded, symbols):
     return dtable
 
 
+# -------------------------------------------------------------------------------------------------
+# integrated gradients of the protein-sequence CNN, fused over the copies (csrc/convig.hip; include/kgcn_hip.h): the first
+# Conv1D -> MaxPooling1D layer of K scaled copies from ONE bias-free pass per protein, and the copies' gradients summed before ONE
+# input-gradient pass.  Read-outs: no autograd.
+# -------------------------------------------------------------------------------------------------
+CONV1D_IG_MAX_COPIES = _lib.K["KGCN_CONV1D_IG_MAX_COPIES"]
+
+
+def conv1d_ig_scales(alpha):
+    """The scales of the copies as a host fp32 array [K], checked before any launch: 1 <= K <= CONV1D_IG_MAX_COPIES, every scale
+    finite and >= 0 (the window maximum commutes with a non-negative scale only)."""
+    import numpy as np
+    a = np.asarray(alpha.detach().cpu().numpy() if torch.is_tensor(alpha) else alpha, np.float32).reshape(-1)
+    if not 1 <= a.size <= CONV1D_IG_MAX_COPIES:
+        raise ValueError("conv1d_ig: K = %d copies outside 1..%d" % (a.size, CONV1D_IG_MAX_COPIES))
+    if not (np.isfinite(a).all() and (a >= 0).all()):
+        raise ValueError("conv1d_ig: every scale must be finite and >= 0, got %s" % (a[~(np.isfinite(a) & (a >= 0))][:4],))
+    return a
+
+
+def _conv1d_ig_rows(t, name, K):
+    t = _f32c(t.detach(), name)
+    if t.dim() != 3 or t.shape[0] % K:
+        raise ValueError("conv1d_ig: %s must be [C K, T, F] with K = %d, got %s" % (name, K, tuple(t.shape)))
+    conv1d_limits_check(length=t.shape[1], filters=t.shape[2])
+    return t
+
+
+@torch.no_grad()
+def conv1d_pool_window_max(tokens, table, w, pool):
+    """Pm [C, L // pool, F], the window maxima of conv(table[tokens], w) WITHOUT bias or activation, and their arg-max bytes
+    (the lowest index among equal maxima): kgcn_conv1d_pool_fwd_f32 in token mode with a zero bias and KGCN_ACT_NONE."""
+    tokens, table, w = _tokens2d(tokens), _f32c(table.detach(), "embedding table"), _f32c(w.detach(), "conv kernel")
+    if w.dim() != 3 or table.dim() != 2 or table.shape[1] != w.shape[1]:
+        raise _lib.KgcnHipError("embedding table %s does not match a conv kernel %s" % (tuple(table.shape), tuple(w.shape)))
+    (C, L), S, (k, Cin, F) = tokens.shape, table.shape[0], w.shape
+    conv1d_limits_check(L, Cin, F, k, pool, S)
+    T = L // int(pool)
+    Pm = torch.empty((C, T, F), device=w.device, dtype=torch.float32)
+    arg = torch.empty((C, T, F), device=w.device, dtype=torch.uint8)
+    zero = torch.zeros((F,), device=w.device, dtype=torch.float32)
+    check(lib.kgcn_conv1d_pool_fwd_f32(None, ptr(tokens), ptr(table), S, C, L, Cin, ptr(w), ptr(zero), k, F, int(pool), ACT_CODES[None],
+                                       ptr(Pm), ptr(arg), current_stream()), "kgcn_conv1d_pool_fwd_f32")
+    return Pm, arg
+
+
+@torch.no_grad()
+def conv1d_ig_expand(Pm, alpha, bias):
+    """The first Conv1D(relu) -> MaxPooling1D layer of K scaled copies of C proteins from conv1d_pool_window_max's Pm [C, T, F]:
+    out[c K + k] = max(0, fl(fl(alpha[k] Pm[c]) + bias)) -> [C K, T, F] (two roundings; at alpha 1 the composed layer bit for
+    bit).  alpha [K]: conv1d_ig_scales refuses a negative or non-finite scale before any launch."""
+    a = conv1d_ig_scales(alpha)
+    require_gpu(Pm, "Pm")
+    Pm = _conv1d_ig_rows(Pm, "Pm", 1)
+    C, T, F = Pm.shape
+    K = int(a.size)
+    b = _conv_bias(bias.detach(), F)
+    out = torch.empty((C * K, T, F), device=Pm.device, dtype=torch.float32)
+    if T:
+        al = torch.as_tensor(a, device=Pm.device)
+        check(lib.kgcn_ig_conv1d_expand_f32(ptr(Pm), C, K, T, F, ptr(al), ptr(b), ptr(out), current_stream()), "kgcn_ig_conv1d_expand_f32")
+    return out
+
+
+@torch.no_grad()
+def conv1d_ig_reduce(dout, out, weights):
+    """r [C, T, F] = sum_k weights[k] dout[c K + k] [out[c K + k] > 0] over the K copies of every protein, k ascending from +0 in
+    fp32 (product and sum unfused), no atomics; a copy of weight 0 is neither read nor added.  dout, out [C K, T, F]."""
+    import numpy as np
+    wh = np.asarray(weights.detach().cpu().numpy() if torch.is_tensor(weights) else weights, np.float32).reshape(-1)
+    K = int(wh.size)
+    if not 1 <= K <= CONV1D_IG_MAX_COPIES:
+        raise ValueError("conv1d_ig: K = %d copies outside 1..%d" % (K, CONV1D_IG_MAX_COPIES))
+    require_gpu(out, "out")
+    out, dout = _conv1d_ig_rows(out, "out", K), _conv1d_ig_rows(dout, "dout", K)
+    if tuple(dout.shape) != tuple(out.shape):
+        raise ValueError("conv1d_ig_reduce: dout %s and out %s differ" % (tuple(dout.shape), tuple(out.shape)))
+    B, T, F = out.shape
+    r = torch.empty((B // K, T, F), device=out.device, dtype=torch.float32)
+    if T:
+        w = torch.as_tensor(wh, device=out.device)
+        check(lib.kgcn_ig_conv1d_reduce_f32(ptr(dout), ptr(out), B // K, K, T, F, ptr(w), ptr(r), current_stream()),
+              "kgcn_ig_conv1d_reduce_f32")
+    return r
+
+
+@torch.no_grad()
+def conv1d_pool_window_grad(r, arg, Pm, tokens, table, w, pool):
+    """d rows [C, L, Cin] of conv1d_pool_window_max for the gradient r [C, T, F] arriving at Pm: r routed through `arg`, then the
+    transposed convolution -- ONE kgcn_conv1d_pool_bwd_f32 with KGCN_ACT_NONE, dx only."""
+    tokens, table, w = _tokens2d(tokens), _f32c(table.detach(), "embedding table"), _f32c(w.detach(), "conv kernel")
+    r, Pm = _f32c(r, "r"), _f32c(Pm, "Pm")
+    (C, L), S, (k, Cin, F) = tokens.shape, table.shape[0], w.shape
+    conv1d_limits_check(L, Cin, F, k, pool, S)
+    shape = (C, L // int(pool), F)
+    if tuple(r.shape) != shape or tuple(Pm.shape) != shape or tuple(arg.shape) != shape or arg.dtype != torch.uint8 or not arg.is_contiguous():
+        raise _lib.KgcnHipError("conv1d_pool_window_grad: r, Pm and the arg-max bytes must be %s" % (shape,))
+    dx = torch.empty((C, L, Cin), device=w.device, dtype=torch.float32)
+    wsb = lib.kgcn_conv1d_pool_workspace_bytes(C, L, Cin, k, F, int(pool))
+    wsp = _lib.workspace(wsb, w.device)
+    check(lib.kgcn_conv1d_pool_bwd_f32(None, ptr(tokens), ptr(table), S, C, L, Cin, ptr(w), k, F, int(pool), ACT_CODES[None], ptr(r),
+                                       ptr(arg), ptr(Pm), ptr(dx), None, None, ptr(wsp), wsb, current_stream()),
+          "kgcn_conv1d_pool_bwd_f32")
+    return dx
+
+
 class _GatherInto(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, join, join_col):

@@ -737,6 +737,159 @@ def vecmodal_integrated_gradients(model, features, adjacency, vectors, labels=No
 
 
 # -------------------------------------------------------------------------------------------------
+# the protein-sequence CNN (sample_protein/sequence/cnn.py; 03run.sh: kgcn visualize --config config_cnn.pos.json
+# --ig_label_target 1): the embedded sequence is the one modal, the sample's graph a dummy the model never reads.  The first
+# conv-pool layer is fused over the copies (csrc/convig.hip)
+# -------------------------------------------------------------------------------------------------
+SEQCNN_IG_ROWS_PER_CHUNK = 2048   # rows (proteins x copies) per forward + backward: the first layer's output is L / 4 x 505 floats a row
+# The default of `fused` follows the measurement (tools/seqcnn_ig_bench.py, profiles/seqcnn_ig_bench.json: L = 1000, E = 25, D = 100
+# on the MI355X, both routes in the same run, median of 10 calls with smallest - largest).  The fused route IS ahead, by far more than
+# the run-to-run spread: 18.0 ms (17.9 - 18.5) against 32.8 ms (32.7 - 33.5) composed at 16 proteins, 70.0 ms (69.8 - 70.2) against
+# 129.0 ms (128.8 - 129.3) at 64, and 2.8 against 3.4 ms at one protein -- 1.83x, 1.84x and 1.25x; the per-step loop takes 99 ms a
+# protein.  Here, unlike in the vector-modality models, the layer the fused route takes out of the per-copy work is about 39 % of
+# the per-copy arithmetic and no graph branch runs beside it.  So the default is the fused route; fused=False stays available under
+# the same tests.
+SEQCNN_IG_FUSED = True
+
+
+def _seqcnn_scores(model, masks, rep, dev, **fed):
+    """The softmax probability of every row's target class(es): masks [C, K] selects them per protein, rep rows each."""
+    logits = model(None, None, **fed)
+    return (torch.softmax(logits, dim=1) * torch.as_tensor(masks, device=dev).repeat_interleave(rep, 0)).sum(1)
+
+
+def _seqcnn_copy_grads(model, e, ids, plan, masks, need_grad=True):
+    """The composed route: one forward + backward over len(ids) proteins x len(plan.scales) copies of their clean embedded rows
+    e [C, L, E] -> the per-copy quantities _seqcnn_reduce sums: 'grad' [B, L, E] with respect to the fed rows -- e * scale, or on
+    the noisy path ops.ig_perturb's e * scale + sigma z on the stream the multimodal conv-pool draws from
+    (ops.IG_STREAM_SEQUENCE, row l, column e, the protein's dataset index, the sample number) -- 'score' [B] and 'weight' [B].
+    need_grad=False: the forward alone (a copy of weight 0, run for its score), the gradient zero."""
+    from . import ops
+    C, rep, dev = e.shape[0], len(plan.scales), e.device
+    sc = torch.tensor(plan.scales, dtype=torch.float32, device=dev).repeat(C)
+    wt = torch.tensor(plan.weights, dtype=torch.float32, device=dev).repeat(C)
+    if plan.noise is None:
+        fed = e.repeat_interleave(rep, 0) * sc.view(-1, 1, 1)
+    else:
+        sg = torch.tensor(plan.noise[0], dtype=torch.float32, device=dev).repeat(C)
+        smp = torch.tensor(plan.noise[1], dtype=torch.int32, device=dev).repeat(C)
+        cid = torch.tensor([int(i) for i in ids], dtype=torch.int32, device=dev)
+        fed = ops.ig_perturb(e, sc, sg, smp, cid, rep, ops.IG_STREAM_SEQUENCE, plan.noise[2])
+    fed = fed.detach().requires_grad_(need_grad)
+    with torch.set_grad_enabled(need_grad):
+        score = _seqcnn_scores(model, masks, rep, dev, embedded=fed)
+    grad = torch.autograd.grad(score.sum(), [fed])[0] if need_grad else torch.zeros_like(fed)
+    return {"grad": grad, "score": score.detach(), "weight": wt}
+
+
+def _seqcnn_reduce(gr, e, plan):
+    """The per-copy quantities of _seqcnn_copy_grads (C proteins x B / C copies, or as many one-copy results concatenated) -> per
+    protein 'embedded_layer', the sum over the copies weighted by 'weight' in one fixed order for the batched and the per-step
+    form alike, times the clean rows e unless plan.method is one of IG_RAW_METHODS; 'start' and 'end'."""
+    C, L, E = e.shape
+    rep = gr["score"].shape[0] // C
+    ig = (gr["grad"].view(C, rep, L, E) * gr["weight"].view(C, rep, 1, 1)).sum(1)
+    s = gr["score"].view(C, rep)
+    return {"embedded_layer": ig if plan.method in IG_RAW_METHODS else ig * e, "start": s[:, plan.start_row], "end": s[:, plan.end_row]}
+
+
+def _seqcnn_fused_chunk(model, tok, e, plan, masks):
+    """The fused route over the proteins tok [C, L] (clean rows e) x len(plan.scales) clean copies: Pm = the window maxima of the
+    bias-free first convolution and their arg-max ONCE per protein (ops.conv1d_pool_window_max), the first layer of every copy
+    from ops.conv1d_ig_expand, handed to the model as first=; the gradient arriving there is summed over the copies by
+    ops.conv1d_ig_reduce and ONE input-gradient pass (ops.conv1d_pool_window_grad) follows.  Neither the [C K, L, E] scaled rows
+    nor a per-copy gradient of them is formed.  -> what _seqcnn_reduce returns."""
+    from . import ops
+    C, rep, dev = tok.shape[0], len(plan.scales), tok.device
+    conv = model.convs[0]
+    table, w = model.embeddings.detach(), conv.conv_kernel.detach()
+    Pm, arg = ops.conv1d_pool_window_max(tok, table, w, conv.pool)
+    first = ops.conv1d_ig_expand(Pm, plan.scales, conv.conv_bias).requires_grad_(True)
+    score = _seqcnn_scores(model, masks, rep, dev, first=first)
+    dout = torch.autograd.grad(score.sum(), [first])[0]
+    r = ops.conv1d_ig_reduce(dout, first, plan.weights)
+    G = ops.conv1d_pool_window_grad(r, arg, Pm, tok, table, w, conv.pool)
+    s = score.detach().view(C, rep)
+    return {"embedded_layer": G if plan.method in IG_RAW_METHODS else G * e, "start": s[:, plan.start_row], "end": s[:, plan.end_row]}
+
+
+def seqcnn_integrated_gradients(model, tokens, labels=None, divide_number=100, method="ig", label_target="max", chunk=None,
+                                proteins=None, sequence_symbol=None, fused=None, batched=True, noise_scale=0.1, seed=1234):
+    """`kgcn visualize` of sample_protein/sequence (03run.sh step 2) for a models.SeqCNN by the protocol of the compound drivers
+    above -> their records with embedded_layer [L, E] / embedded_layer_IG [L, E] as the one modal (the dummy graph is not
+    attributed) and amino_acid_seq when sequence_symbol is given.
+
+    tokens int32 [G, L] device tensor (data_util.sequence_table); labels [G, K], true_label = argmax; proteins: dataset indices
+    (default all).  The score is the softmax probability of the target class; label_target as select_label_target takes it (the
+    sample uses 1).  All five methods.
+    fused=True ('ig', 'grad_prod', 'grad'): the first layer, Conv1D(505, 4, relu) -> MaxPooling1D(4), is not run per copy.  It is
+    linear in the scale before its bias and the window maximum commutes with a non-negative scale, so the bias-free convolution
+    and its window maxima are formed ONCE per protein and ops.conv1d_ig_expand sweeps the copies; the convolution's input
+    gradient is linear in the pre-activation's, so ops.conv1d_ig_reduce sums the copies and ONE input-gradient pass follows
+    (_seqcnn_fused_chunk; include/kgcn_hip.h states the arithmetic and the one deviation, ties created by rounding).
+    fused=False: the scaled rows go through the model as embedded=, with autograd to them.  fused=None (the default): the route
+    the measurement favours, SEQCNN_IG_FUSED.  The smooth methods always take the composed route -- every sample has its own
+    noise, drawn by ops.ig_perturb on the embedded rows -- and fused=True with one of them is refused.
+    batched=False runs the reference's loop instead: one batch-1 pass per protein and copy through the composed route's ops
+    (forward only for a copy of weight 0), the per-copy gradients summed by the reduction the batched form uses; it sees the same
+    noise."""
+    import numpy as np
+    import string
+    from . import models
+    if not isinstance(model, models.SeqCNN) or not getattr(model, "ROW_INDEPENDENT", False):
+        raise TypeError("seqcnn_integrated_gradients batches the scaled copies as rows and feeds the first conv-pool layer: it needs "
+                        "a models.SeqCNN, got %s" % type(model).__name__)
+    plan = ig_row_plan(method, divide_number, noise_scale, seed)
+    if method in SMOOTH_METHODS:
+        if fused:
+            raise ValueError("method %r draws its own noise for every copy: it has no fused route (fused=True)" % (method,))
+        fused = False
+    else:
+        fused = SEQCNN_IG_FUSED if fused is None else bool(fused)
+    if not (torch.is_tensor(tokens) and tokens.dim() == 2 and tokens.dtype == torch.int32):
+        raise ValueError("tokens must be an int32 [G, L] tensor")
+    rep = len(plan.scales)
+    chunk = _compounds_per_chunk(chunk, SEQCNN_IG_ROWS_PER_CHUNK // rep)
+    G, dev = tokens.shape[0], tokens.device
+    ids = list(range(G)) if proteins is None else [int(i) for i in proteins]
+
+    def rows_of(part):
+        return tokens[torch.as_tensor([int(i) for i in part], device=dev)]
+
+    def predict(part):
+        return torch.softmax(model(None, None, sequences=rows_of(part)), 1).cpu().numpy()
+
+    jobs = list(_ig_jobs(predict, ids, chunk * rep, label_target, _one_job_per_compound(_host_array(labels))))
+    table = model.embeddings.detach()
+    res = {}
+    with frozen_parameters(model):
+        if batched:
+            for i in range(0, len(jobs), chunk):
+                part = jobs[i:i + chunk]
+                cids, masks = [j[0] for j in part], np.stack([j[5] for j in part])
+                tok = rows_of(cids)
+                e = table[tok.long()]
+                out = _seqcnn_fused_chunk(model, tok, e, plan, masks) if fused else \
+                    _seqcnn_reduce(_seqcnn_copy_grads(model, e, cids, plan, masks), e, plan)
+                _rows_to_host(res, cids, out)
+        else:
+            for j in jobs:                                   # one batch-1 pass per copy; a copy of weight 0 runs forward only
+                e = table[rows_of([j[0]]).long()]
+                rows = [_seqcnn_copy_grads(model, e, [j[0]], ig_plan_row(plan, r), j[5][None], need_grad=w != 0.0)
+                        for r, w in enumerate(plan.weights)]
+                _rows_to_host(res, [j[0]], _seqcnn_reduce({k: torch.cat([p[k] for p in rows]) for k in rows[0]}, e, plan))
+    results = []
+    for job in jobs:
+        cid, r = job[0], res[job[0]]
+        rec = {"compound_id": cid, "assay": assay_string(job[1], job[3])}
+        if sequence_symbol is not None:
+            rec["amino_acid_seq"] = "".join(string.ascii_uppercase[int(t)] for t in np.asarray(sequence_symbol[cid]).reshape(-1))
+        data = {"embedded_layer": lambda: table[tokens[cid].long()].cpu().numpy()}
+        results.append(_ig_record(rec, job, ("embedded_layer",), data, r, r["start"], r["end"]))
+    return results
+
+
+# -------------------------------------------------------------------------------------------------
 # the link-prediction model (sample_kg/network_prediction/model_py/{gcn,distmult,ip}.py): kgcn/visualization.py:289-439
 # (KnowledgeGraphVisualizer, cal_feature_IG_for_kg), many targets per launch
 # -------------------------------------------------------------------------------------------------
