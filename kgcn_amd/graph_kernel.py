@@ -44,7 +44,9 @@ ops.lsh_buckets; a stated summation order, nothing fused, so the tests restate t
 runs on the buckets' dense ranks and the R feature maps share one Gram.  batched=True takes the R colourings through ONE launch
 sequence over the one stored adjacency (ops.wl_refine_copies / wl_rank_copies / wl_runs_copies: one mismatch read-back a
 refinement for all draws; ops.sp_features_copies: one breadth-first search a graph for all draws); batched=False runs the draws one
-after another through the plain ops and gives the same bits.  HASH_BATCHED is the measured default (tools/hash_kernel_bench.py).
+after another through the plain ops and gives the same bits.  Each plain op and its _copies form are one body in ops.py, the
+plain one being copies = 1 through its own C entry point; _refine here is the one refinement loop of both routes.
+HASH_BATCHED is the measured default (tools/hash_kernel_bench.py).
   Deviations of hash_graph_kernel from the reference
   * K = F F^T / R exactly: the integer Gram over the runs of all draws, divided by R in one fp64 division.
     hash_graph_kernel.py:63-65 rounds sqrt(1 / R) into every count first (measured difference: at most 1.6e-14 relative at R = 20).
@@ -178,23 +180,37 @@ def _finish(runs, G, normalize, return_gram, chunk_cols):
     return sps.csr_matrix((count.cpu().numpy().astype(np.int64), (graph.cpu().numpy(), inv.reshape(-1))), shape=(G, max(uniq.size, 1)))
 
 
+def _refuse_mismatches(info, it, mask):
+    mismatches = int(info[1].item())                                  # the read-back
+    if mismatches:
+        raise _lib.KgcnHipError("wl refinement %d: %d pairs of nodes share a 128-bit key (mask %#x) but differ in their "
+                                "signatures; the partition would merge them, refused" % (it + 1, mismatches, mask))
+
+
+def _refine(gs, col, iterations, hash_mask, copies=None):
+    """refine -> rank -> refuse, `iterations` times -> the [iterations + 1] colourings, col first.  copies None: the one
+    colouring col [T*M] through the plain ops; otherwise col [copies * T*M] through the copies ops, all copies at once: the one
+    read-back a refinement (the mismatch count) serves them all.  A hash collision that merged two signatures raises."""
+    mask = ops.HASH_MASK_FULL if hash_mask is None else int(hash_mask)
+    out = [col]
+    for it in range(int(iterations)):
+        if copies is None:
+            sorted_nbr, hi, lo = ops.wl_refine(gs.csr, gs.num_nodes, col, mask)
+            col, info = ops.wl_rank(gs.csr, gs.num_nodes, col, sorted_nbr, hi, lo)
+        else:
+            sorted_nbr, hi, lo = ops.wl_refine_copies(gs.csr, gs.num_nodes, col, copies, mask)
+            col, info = ops.wl_rank_copies(gs.csr, gs.num_nodes, col, copies, sorted_nbr, hi, lo)
+        _refuse_mismatches(info, it, mask)
+        out.append(col)
+    return out
+
+
 @torch.no_grad()
 def wl_colourings(adjacency, num_nodes=None, node_labels=None, iterations=3, labels="node", hash_mask=None):
     """The colours after every refinement -> ([iterations + 1] device int32 [T, M] tensors, -1 where no node exists; the
     GraphSet).  Raises when a hash collision merged two different signatures (never silently)."""
     gs = _as_graph_set(adjacency, num_nodes, node_labels)
-    mask = ops.HASH_MASK_FULL if hash_mask is None else int(hash_mask)
-    col, _ = gs.initial_colours(labels)
-    out = [col]
-    for it in range(int(iterations)):
-        sorted_nbr, hi, lo = ops.wl_refine(gs.csr, gs.num_nodes, col, mask)
-        col, info = ops.wl_rank(gs.csr, gs.num_nodes, col, sorted_nbr, hi, lo)
-        mismatches = int(info[1].item())
-        if mismatches:
-            raise _lib.KgcnHipError("wl refinement %d: %d pairs of nodes share a 128-bit key (mask %#x) but differ in their "
-                                    "signatures; the partition would merge them, refused" % (it + 1, mismatches, mask))
-        out.append(col)
-    return [c.view(gs.T, gs.M) for c in out], gs
+    return [c.view(gs.T, gs.M) for c in _refine(gs, gs.initial_colours(labels)[0], iterations, hash_mask)], gs
 
 
 @torch.no_grad()
@@ -251,13 +267,6 @@ def _attribute_rows(attributes, gs):
     return np.ascontiguousarray(rows)
 
 
-def _refuse_mismatches(info, it, mask):
-    mismatches = int(info[1].item())
-    if mismatches:
-        raise _lib.KgcnHipError("wl refinement %d: %d pairs of nodes share a 128-bit key (mask %#x) but differ in their "
-                                "signatures; the partition would merge them, refused" % (it + 1, mismatches, mask))
-
-
 def _refuse_classes(count, what):
     if count > _SP_MAX_CLASSES:
         raise _lib.KgcnHipError("hash_graph_kernel: %d %s in one draw, up to %d: the shortest-path key packs (class, class, distance) "
@@ -294,7 +303,6 @@ def hash_graph_kernel(adjacency, num_nodes=None, attributes=None, base="wl", nod
         raise ValueError("projections must be [R >= 1, %d] and offsets [R], got %s and %s" % (d, V.shape, b.shape))
     R, T, M, dev = V.shape[0], gs.T, gs.M, gs.device
     batched = HASH_BATCHED if batched is None else bool(batched)
-    mask = ops.HASH_MASK_FULL if hash_mask is None else int(hash_mask)
     if X.shape[0] == 0:                                               # no node: no feature
         if return_gram:
             return torch.zeros((T, T), device=dev, dtype=torch.float64)
@@ -318,13 +326,7 @@ def hash_graph_kernel(adjacency, num_nodes=None, attributes=None, base="wl", nod
         draw = torch.arange(R, device=dev, dtype=torch.int64)[:, None]
         col = ops.rank_pairs(draw.expand(R, T * M).reshape(-1).contiguous(), full.reshape(-1), markR)[0]     # of (draw, bucket)
         if base == "wl":
-            cols = [col]
-            for it in range(int(wl_iterations)):
-                sorted_nbr, hi, lo = ops.wl_refine_copies(gs.csr, gs.num_nodes, col, R, mask)
-                col, info = ops.wl_rank_copies(gs.csr, gs.num_nodes, col, R, sorted_nbr, hi, lo)
-                _refuse_mismatches(info, it, mask)
-                cols.append(col)
-            for it, c in enumerate(cols):
+            for it, c in enumerate(_refine(gs, col, wl_iterations, hash_mask, copies=R)):
                 if lab_cols is not None:                                                          # wl_kernel.py:66-70
                     c = ops.rank_pairs(lab_cols[it].reshape(-1).to(torch.int64).repeat(R), c.to(torch.int64), markR)[0]
                 runs.append(ops.wl_runs_copies(c, gs.num_nodes, T, M, R, it << 32, stride << 32))
@@ -552,30 +554,35 @@ def svm_cv(K, y, test_splits=5, C_grid=None, idx_train_val=None, idx_test=None, 
     from sklearn.model_selection import KFold
     from sklearn.svm import SVC
     K = np.asarray(K.cpu() if torch.is_tensor(K) else K, np.float64)
-    if idx_train_val is None:
-        outer = [(np.asarray(a), np.asarray(b)) for a, b in KFold(n_splits=test_splits).split(np.arange(K.shape[0]))]
-    else:
-        outer = [(np.asarray(idx_train_val, np.int64), np.asarray(idx_test, np.int64))]
-    out = {"best_C": [], "val_acc": [], "test_acc": [], "fit_indices": []}
+    outer = _explicit_split(idx_train_val, idx_test) or [(np.asarray(a), np.asarray(b))
+                                                         for a, b in KFold(n_splits=test_splits).split(np.arange(K.shape[0]))]
+    fit_indices, val, test = [], [], []
     for tv, te in outer:
-        val, test = [], []
         for a, b in KFold(n_splits=val_splits).split(tv):
             tr, va = tv[a], tv[b]
-            out["fit_indices"].append(tr)
+            fit_indices.append(tr)
             base = K[:, tr]
-            accs_v, accs_t = [], []
-            for C in C_grid:
-                clf = SVC(kernel="precomputed", C=float(C), tol=tol)
-                clf.fit(base[tr, :], y[tr])
-                accs_v.append(accuracy_score(y[va], clf.predict(base[va, :])))
-                accs_t.append(accuracy_score(y[te], clf.predict(base[te, :])))
-            val.append(accs_v)
-            test.append(accs_t)
-        val, test = np.mean(val, axis=0), np.mean(test, axis=0)
-        best = int(np.argmax(val))
+            fits = [SVC(kernel="precomputed", C=float(C), tol=tol).fit(base[tr, :], y[tr]) for C in C_grid]
+            val.append([accuracy_score(y[va], clf.predict(base[va, :])) for clf in fits])
+            test.append([accuracy_score(y[te], clf.predict(base[te, :])) for clf in fits])
+    return _cv_summary(C_grid, val, test, fit_indices, val_splits)
+
+
+def _explicit_split(idx_train_val, idx_test):
+    """svm_cv's outer splits [(training-and-validation rows, test rows)] when one is given; None: the route's own k-fold makes them."""
+    return None if idx_train_val is None else [(np.asarray(idx_train_val, np.int64), np.asarray(idx_test, np.int64))]
+
+
+def _cv_summary(C_grid, val, test, fit_indices, val_splits):
+    """val, test [fit][C]: the accuracies of every fit, the val_splits inner folds of an outer split one after another -> what
+    svm_cv returns: per outer split the C of the best mean validation accuracy and the two means at it; mean and std of test_acc."""
+    out = {"best_C": [], "val_acc": [], "test_acc": [], "fit_indices": fit_indices}
+    for o in range(0, len(val), val_splits):
+        v, t = np.mean(val[o:o + val_splits], axis=0), np.mean(test[o:o + val_splits], axis=0)
+        best = int(np.argmax(v))
         out["best_C"].append(float(C_grid[best]))
-        out["val_acc"].append(float(val[best]))
-        out["test_acc"].append(float(test[best]))
+        out["val_acc"].append(float(v[best]))
+        out["test_acc"].append(float(t[best]))
     out["mean"] = float(np.mean(out["test_acc"]))
     out["std"] = float(np.std(out["test_acc"]))
     return out
@@ -593,26 +600,12 @@ def _kfold(m, splits):
 
 def _svm_cv_device(K, y, test_splits, C_grid, idx_train_val, idx_test, val_splits, tol):
     K = _device_gram(K)
-    if idx_train_val is None:
-        outer = _kfold(int(K.shape[0]), test_splits)
-    else:
-        outer = [(np.asarray(idx_train_val, np.int64), np.asarray(idx_test, np.int64))]
     trains, evals = [], []
-    for tv, te in outer:
+    for tv, te in _explicit_split(idx_train_val, idx_test) or _kfold(int(K.shape[0]), test_splits):
         for a, b in _kfold(len(tv), val_splits):
             trains.append(tv[a])
             evals.append([tv[b], te])
     batch = svm_fit(K, y, trains, C_grid, tol=tol)
     _, correct = svm_predict(batch, K, evals, return_correct=True)
-    out = {"best_C": [], "val_acc": [], "test_acc": [], "fit_indices": list(trains)}
-    for o in range(len(outer)):
-        fits = range(o * val_splits, (o + 1) * val_splits)
-        val = np.mean([[correct[f][c][0] / len(evals[f][0]) for c in range(len(C_grid))] for f in fits], axis=0)
-        test = np.mean([[correct[f][c][1] / len(evals[f][1]) for c in range(len(C_grid))] for f in fits], axis=0)
-        best = int(np.argmax(val))
-        out["best_C"].append(float(C_grid[best]))
-        out["val_acc"].append(float(val[best]))
-        out["test_acc"].append(float(test[best]))
-    out["mean"] = float(np.mean(out["test_acc"]))
-    out["std"] = float(np.std(out["test_acc"]))
-    return out
+    val, test = ([[correct[f][c][e] / len(evals[f][e]) for c in range(len(C_grid))] for f in range(len(trains))] for e in (0, 1))
+    return _cv_summary(C_grid, val, test, list(trains), val_splits)

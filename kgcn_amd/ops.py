@@ -3232,12 +3232,42 @@ def _ws_bytes(nbytes, what, device):
     return _lib.workspace(nbytes, device, torch.uint8), nbytes
 
 
-def _i32_dev(t, name, numel):
-    require_gpu(t, name)
-    if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != numel:
-        raise _lib.KgcnHipError("%s must be a contiguous int32 device tensor of %d elements, got %s %s"
-                                % (name, numel, t.dtype, tuple(t.shape)))
-    return t
+_SAME = "same"                      # a shape entry of _operand: the size of the dimension before it
+
+
+def _operand(who, name, t, dtype, shape):
+    """THE operand check of this section and the three below it: t is a contiguous device tensor of `dtype` and `shape` -> t, or
+    a KgcnHipError that names the op, the operand, what was expected and what came.  shape: an int is an element count (any
+    contiguous layout of it); a tuple has one entry a dimension -- an int, None (open: the op reads the size from the operand),
+    (lo, hi) (open within lo..hi; hi None: no upper limit) or _SAME; None leaves the whole shape open."""
+    got = t.shape
+    if shape is None or isinstance(shape, int):
+        fits = shape is None or t.numel() == shape
+    else:
+        fits = len(got) == len(shape)
+        for i, want in enumerate(shape if fits else ()):
+            if want == _SAME:
+                fits = got[i] == got[i - 1]
+            elif isinstance(want, tuple):
+                fits = got[i] >= want[0] and (want[1] is None or got[i] <= want[1])
+            elif want is not None:
+                fits = got[i] == want
+            if not fits:
+                break
+    if fits and t.is_cuda and t.dtype == dtype and t.is_contiguous():
+        return t
+    if isinstance(shape, tuple):                                      # the refusal: only now is the expectation spelled out
+        expected = "shape [%s]" % ", ".join("*" if w is None else "%d..%s" % (w[0], "" if w[1] is None else w[1]) if isinstance(w, tuple)
+                                            else str(w) for w in shape)
+    else:
+        expected = "any shape" if shape is None else "%d elements" % shape
+    raise _lib.KgcnHipError("%s: %s must be a contiguous %s device tensor of %s, got a %s%s %s tensor of shape %s" % (
+        who, name, dtype, expected, "" if t.is_contiguous() else "non-contiguous ", t.dtype, "device" if t.is_cuda else "host", list(got)))
+
+
+def _ptr_if(t, n):
+    """The pointer of an operand of n elements, NULL when there are none (an empty tensor's pointer is not defined)."""
+    return ptr(t) if n else None
 
 
 def _plain_square(csr, who):
@@ -3246,65 +3276,104 @@ def _plain_square(csr, who):
     return csr.num_graphs, csr.rows
 
 
+# The four ops below have a plain form and a copies form (R colourings of the same graphs: the next section).  As in
+# csrc/graphkern.h, where both C entry points wrap one launcher and plain is copies == 1, each has ONE host body: `who` is the
+# public name, `entry` its C entry point kgcn_<who>_i32, `copies` None the plain form, whose entry point takes no copies argument.
+def _copies(copies, T, M, who):
+    """-> (R, the arguments only the copies entry points take)."""
+    if copies is None:
+        return 1, ()
+    copies = int(copies)
+    if copies < 1 or copies * T * M >= 2 ** 31 - 1:
+        raise _lib.KgcnHipError("%s: %d copies of %d graphs x %d rows; at least one copy and fewer than 2^31 - 1 rows in all "
+                                "(positions and colours are int32)" % (who, copies, T, M))
+    return copies, (copies,)
+
+
+def _wl_refine(who, entry, csr, num_nodes, colors, copies, hash_mask):
+    T, M = _plain_square(csr, who)
+    R, extra = _copies(copies, T, M, who)
+    _operand(who, "num_nodes", num_nodes, torch.int32, T), _operand(who, "colors", colors, torch.int32, R * T * M)
+    sorted_nbr = torch.empty((R, max(csr.nnz, 1)), device=csr.device, dtype=torch.int32)
+    keys = torch.empty((2, max(R * T * M, 1)), device=csr.device, dtype=torch.int64)
+    check(entry(ctypes.byref(csr.desc()), ptr(num_nodes), ptr(colors), *extra, int(hash_mask) & HASH_MASK_FULL, ptr(sorted_nbr),
+                ptr(keys[0]), ptr(keys[1]), current_stream()), "kgcn_%s_i32" % who)
+    return sorted_nbr[0] if copies is None else sorted_nbr, keys[0], keys[1]
+
+
+def _wl_rank(who, entry, csr, num_nodes, colors, copies, sorted_nbr, key_hi, key_lo):
+    T, M = _plain_square(csr, who)
+    R, extra = _copies(copies, T, M, who)
+    n = R * T * M
+    _operand(who, "num_nodes", num_nodes, torch.int32, T), _operand(who, "colors", colors, torch.int32, n)
+    _operand(who, "sorted_nbr", sorted_nbr, torch.int32, (R,) * len(extra) + (max(csr.nnz, 1),))     # what _wl_refine returns
+    _operand(who, "key_hi", key_hi, torch.int64, max(n, 1)), _operand(who, "key_lo", key_lo, torch.int64, max(n, 1))
+    new = torch.empty((max(n, 1),), device=csr.device, dtype=torch.int32)
+    info = torch.empty((2,), device=csr.device, dtype=torch.int64)
+    query = lib.kgcn_wl_rank_copies_workspace_bytes if extra else lib.kgcn_wl_rank_workspace_bytes
+    ws, wsb = _ws_bytes(query(T * M, *extra), "kgcn_%s_workspace_bytes" % who, csr.device)
+    check(entry(ctypes.byref(csr.desc()), ptr(num_nodes), ptr(colors), *extra, ptr(sorted_nbr), ptr(key_hi), ptr(key_lo), ptr(new),
+                ptr(info), ptr(ws), wsb, current_stream()), "kgcn_%s_i32" % who)
+    return new[:n], info
+
+
+def _two_pass_runs(call, T, extra, dev, what):
+    """The count call over the copies * T run slots, the read of the total, the emit call -> (run_col int64 (u64 bits),
+    run_graph, run_count int32)."""
+    slots = T * (extra[0] if extra else 1)
+    run_ptr = torch.empty((slots + 1,), device=dev, dtype=torch.int64)
+    query = lib.kgcn_graph_runs_copies_workspace_bytes if extra else lib.kgcn_graph_runs_workspace_bytes
+    ws, wsb = _ws_bytes(query(T, *extra), "kgcn_graph_runs_copies_workspace_bytes" if extra else "kgcn_graph_runs_workspace_bytes", dev)
+    check(call(run_ptr, None, None, None, 0, ws, wsb), what)
+    total = int(run_ptr[slots].item())
+    col, graph, count = (torch.empty((max(total, 1),), device=dev, dtype=dt) for dt in (torch.int64, torch.int32, torch.int32))
+    check(call(run_ptr, col, graph, count, total, ws, wsb), what)
+    return col[:total], graph[:total], count[:total]
+
+
+def _wl_runs(who, entry, colors, num_nodes, T, M, copies, column_offset, column_stride):
+    R, extra = _copies(copies, T, M, who)
+    _operand(who, "num_nodes", num_nodes, torch.int32, T), _operand(who, "colors", colors, torch.int32, R * T * M)
+    stride = (int(column_stride),) if extra else ()
+    return _two_pass_runs(lambda rp, c, g, n, cap, ws, wsb: entry(
+        ptr(colors), ptr(num_nodes), T, M, *extra, int(column_offset), *stride, ptr(rp), ptr(c), ptr(g), ptr(n), cap, ptr(ws), wsb,
+        current_stream()), T, extra, colors.device, "kgcn_%s_i32" % who)
+
+
+def _sp_features(who, entry, csr, num_nodes, labels, copies, num_labels):
+    T, M = _plain_square(csr, who)
+    R, extra = _copies(copies, T, M, who)
+    _operand(who, "num_nodes", num_nodes, torch.int32, T), _operand(who, "labels", labels, torch.int32, R * T * M)
+    return _two_pass_runs(lambda rp, c, g, n, cap, ws, wsb: entry(
+        ctypes.byref(csr.desc()), ptr(num_nodes), ptr(labels), *extra, int(num_labels), ptr(rp), ptr(c), ptr(g), ptr(n), cap, ptr(ws),
+        wsb, current_stream()), T, extra, csr.device, "kgcn_%s_i32" % who)
+
+
 @torch.no_grad()
 def wl_refine(csr, num_nodes, colors, hash_mask=HASH_MASK_FULL):
-    """First half of one Weisfeiler-Lehman refinement -> (sorted_nbr [nnz] int32: every row's neighbour colours ascending,
+    """First half of one Weisfeiler-Lehman refinement -> (sorted_nbr [max(nnz, 1)] int32: every row's neighbour colours ascending,
     key_hi, key_lo [T*M] int64 holding the two words of the 128-bit signature mix, and-ed with hash_mask)."""
-    T, M = _plain_square(csr, "wl_refine")
-    dev = csr.device
-    _i32_dev(num_nodes, "num_nodes", T), _i32_dev(colors, "colors", T * M)
-    sorted_nbr = torch.empty((max(csr.nnz, 1),), device=dev, dtype=torch.int32)
-    keys = torch.empty((2, max(T * M, 1)), device=dev, dtype=torch.int64)
-    check(lib.kgcn_wl_refine_i32(ctypes.byref(csr.desc()), ptr(num_nodes), ptr(colors), int(hash_mask) & HASH_MASK_FULL,
-                                 ptr(sorted_nbr), ptr(keys[0]), ptr(keys[1]), current_stream()), "kgcn_wl_refine_i32")
-    return sorted_nbr, keys[0], keys[1]
+    return _wl_refine("wl_refine", lib.kgcn_wl_refine_i32, csr, num_nodes, colors, None, hash_mask)
 
 
 @torch.no_grad()
 def wl_rank(csr, num_nodes, colors, sorted_nbr, key_hi, key_lo):
     """Second half: dense colours of the key classes -> (new_colors [T*M] int32, -1 for rows that do not exist; info [2] int64
     device tensor = number of colours, pairs of equal keys with different true signatures -- 0 iff the partition is exact)."""
-    T, M = _plain_square(csr, "wl_rank")
-    dev = csr.device
-    new = torch.empty((max(T * M, 1),), device=dev, dtype=torch.int32)
-    info = torch.empty((2,), device=dev, dtype=torch.int64)
-    ws, wsb = _ws_bytes(lib.kgcn_wl_rank_workspace_bytes(T * M), "kgcn_wl_rank_workspace_bytes", dev)
-    check(lib.kgcn_wl_rank_i32(ctypes.byref(csr.desc()), ptr(num_nodes), ptr(colors), ptr(sorted_nbr), ptr(key_hi), ptr(key_lo),
-                               ptr(new), ptr(info), ptr(ws), wsb, current_stream()), "kgcn_wl_rank_i32")
-    return new[:T * M], info
-
-
-def _two_pass_runs(call, T, dev, what):
-    """The count call, the read of the total, the emit call -> (run_col int64 (u64 bits), run_graph, run_count int32)."""
-    run_ptr = torch.empty((T + 1,), device=dev, dtype=torch.int64)
-    ws, wsb = _ws_bytes(lib.kgcn_graph_runs_workspace_bytes(T), "kgcn_graph_runs_workspace_bytes", dev)
-    check(call(run_ptr, None, None, None, 0, ws, wsb), what)
-    total = int(run_ptr[T].item())
-    col = torch.empty((max(total, 1),), device=dev, dtype=torch.int64)
-    graph = torch.empty((max(total, 1),), device=dev, dtype=torch.int32)
-    count = torch.empty((max(total, 1),), device=dev, dtype=torch.int32)
-    check(call(run_ptr, col, graph, count, total, ws, wsb), what)
-    return col[:total], graph[:total], count[:total]
+    return _wl_rank("wl_rank", lib.kgcn_wl_rank_i32, csr, num_nodes, colors, None, sorted_nbr, key_hi, key_lo)
 
 
 @torch.no_grad()
 def wl_runs(colors, num_nodes, T, M, column_offset):
     """The colour histogram of every graph as feature runs, column = column_offset + colour."""
-    _i32_dev(num_nodes, "num_nodes", T), _i32_dev(colors, "colors", T * M)
-    return _two_pass_runs(lambda rp, c, g, n, cap, ws, wsb: lib.kgcn_wl_runs_i32(
-        ptr(colors), ptr(num_nodes), T, M, int(column_offset), ptr(rp), ptr(c), ptr(g), ptr(n), cap, ptr(ws), wsb,
-        current_stream()), T, colors.device, "kgcn_wl_runs_i32")
+    return _wl_runs("wl_runs", lib.kgcn_wl_runs_i32, colors, num_nodes, T, M, None, column_offset, None)
 
 
 @torch.no_grad()
 def sp_features(csr, num_nodes, labels, num_labels):
     """Shortest-path feature runs: per graph the counts of (label_k, label_j, distance) over all ordered node pairs, k = j
     and unreachable pairs (distance 255) included; column = label_k << 20 | label_j << 8 | distance."""
-    T, M = _plain_square(csr, "sp_features")
-    _i32_dev(num_nodes, "num_nodes", T), _i32_dev(labels, "labels", T * M)
-    return _two_pass_runs(lambda rp, c, g, n, cap, ws, wsb: lib.kgcn_sp_features_i32(
-        ctypes.byref(csr.desc()), ptr(num_nodes), ptr(labels), int(num_labels), ptr(rp), ptr(c), ptr(g), ptr(n), cap, ptr(ws),
-        wsb, current_stream()), T, csr.device, "kgcn_sp_features_i32")
+    return _sp_features("sp_features", lib.kgcn_sp_features_i32, csr, num_nodes, labels, None, num_labels)
 
 
 @torch.no_grad()
@@ -3313,20 +3382,18 @@ def gram_from_runs(run_col, run_graph, run_count, G, chunk_cols=None, normalize=
     int64 diagonal, the others through v_mfma_f64_16x16x4_f64, chunk_cols dense columns a pass).  normalize: K_ij /
     sqrt(K_ii K_jj).  return_stats: also {"columns", "diag_columns", "dense_columns"}.  One read-back (the dense column count)."""
     chunk_cols = GRAM_CHUNK_COLS if chunk_cols is None else int(chunk_cols)
-    n = int(run_col.numel())
+    who = "gram_from_runs"
+    n = int(_operand(who, "run_col", run_col, torch.int64, None).numel())
     dev = run_col.device
-    for t, name, dt in ((run_col, "run_col", torch.int64), (run_graph, "run_graph", torch.int32), (run_count, "run_count", torch.int32)):
-        require_gpu(t, name)
-        if t.dtype != dt or not t.is_contiguous() or t.numel() != n:
-            raise _lib.KgcnHipError("gram_from_runs: %s must be a contiguous %s device tensor of %d elements" % (name, dt, n))
+    _operand(who, "run_graph", run_graph, torch.int32, n), _operand(who, "run_count", run_count, torch.int32, n)
     ws, wsb = _ws_bytes(lib.kgcn_graph_gram_workspace_bytes(n, G, chunk_cols), "kgcn_graph_gram_workspace_bytes", dev)
     stats = torch.empty((3,), device=dev, dtype=torch.int64)
-    check(lib.kgcn_gram_plan_i64(ptr(run_col) if n else None, ptr(run_graph) if n else None, ptr(run_count) if n else None, n, G,
-                                 chunk_cols, ptr(stats), ptr(ws), wsb, current_stream()), "kgcn_gram_plan_i64")
+    col, graph, count = _ptr_if(run_col, n), _ptr_if(run_graph, n), _ptr_if(run_count, n)
+    check(lib.kgcn_gram_plan_i64(col, graph, count, n, G, chunk_cols, ptr(stats), ptr(ws), wsb, current_stream()), "kgcn_gram_plan_i64")
     cols, diag_cols, dense_cols = stats.tolist()
     K = torch.empty((G, G), device=dev, dtype=torch.float64)
-    check(lib.kgcn_gram_dense_f64(ptr(run_graph) if n else None, ptr(run_count) if n else None, n, G, dense_cols, chunk_cols, ptr(K),
-                                  ptr(ws), wsb, current_stream()), "kgcn_gram_dense_f64")
+    check(lib.kgcn_gram_dense_f64(graph, count, n, G, dense_cols, chunk_cols, ptr(K), ptr(ws), wsb, current_stream()),
+          "kgcn_gram_dense_f64")
     if normalize:
         K = gram_normalize(K)
     if return_stats:
@@ -3337,10 +3404,7 @@ def gram_from_runs(run_col, run_graph, run_count, G, chunk_cols=None, normalize=
 @torch.no_grad()
 def gram_normalize(K):
     """auxiliary_methods.normalize_gram_matrix in fp64 on the device: K_ij / sqrt(K_ii K_jj), 0 where a diagonal entry is 0."""
-    require_gpu(K, "gram")
-    if K.dtype != torch.float64 or K.dim() != 2 or K.shape[0] != K.shape[1] or not K.is_contiguous():
-        raise _lib.KgcnHipError("gram_normalize: a contiguous square float64 matrix is required, got %s %s" % (K.dtype, tuple(K.shape)))
-    out = torch.empty_like(K)
+    out = torch.empty_like(_operand("gram_normalize", "K", K, torch.float64, (None, _SAME)))
     check(lib.kgcn_gram_normalize_f64(ptr(K), K.shape[0], ptr(out), current_stream()), "kgcn_gram_normalize_f64")
     return out
 
@@ -3353,30 +3417,7 @@ def gram_normalize(K):
 LSH_MAX_DIM = _lib.K["KGCN_LSH_MAX_DIM"]
 
 
-def _dev_tensor(t, name, dtype, shape, who):
-    require_gpu(t, name)
-    if t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
-        raise _lib.KgcnHipError("%s: %s must be a contiguous %s device tensor of shape %s, got %s %s"
-                                % (who, name, dtype, tuple(shape), t.dtype, tuple(t.shape)))
-    return t
-
-
-def _attr_rows(x, name, who):
-    require_gpu(x, name)
-    if x.dtype != torch.float64 or x.dim() != 2 or not x.is_contiguous():
-        raise _lib.KgcnHipError("%s: %s must be a contiguous [rows, d] float64 device tensor, got %s %s" % (who, name, x.dtype, tuple(x.shape)))
-    rows, d = x.shape
-    if rows < 1 or d < 1 or d > LSH_MAX_DIM:
-        raise _lib.KgcnHipError("%s: %d rows of %d attributes; at least one row and 1..%d attributes a row" % (who, rows, d, LSH_MAX_DIM))
-    return rows, d
-
-
-def _copies(copies, T, M, who):
-    copies = int(copies)
-    if copies < 1 or copies * T * M >= 2 ** 31 - 1:
-        raise _lib.KgcnHipError("%s: %d copies of %d graphs x %d rows; at least one copy and fewer than 2^31 - 1 rows in all "
-                                "(positions and colours are int32)" % (who, copies, T, M))
-    return copies
+_ATTR_ROWS = ((1, None), (1, LSH_MAX_DIM))   # the shape of attribute rows [rows, d]: at least one row, 1..LSH_MAX_DIM attributes
 
 
 @torch.no_grad()
@@ -3384,7 +3425,7 @@ def attr_scale(x):
     """Attribute rows x [rows, d] float64 (the existing nodes in graph order) -> (scaled [rows, d], mean [d], std [d]):
     sklearn.preprocessing.scale of hash_graph_kernel.py:40 in the summation order csrc/hashkern.hip states (chunks of 256 rows,
     then the chunk sums, nothing fused); a column of equal values becomes 0."""
-    rows, d = _attr_rows(x, "x", "attr_scale")
+    rows, d = _operand("attr_scale", "x", x, torch.float64, _ATTR_ROWS).shape
     dev = x.device
     scaled = torch.empty_like(x)
     stats = torch.empty((2, d), device=dev, dtype=torch.float64)
@@ -3399,12 +3440,9 @@ def lsh_buckets(x, v, b, bin_width):
     """bucket [R, rows] int64 = floor((x . v_r + b_r) / bin_width) of auxiliary_methods.py:31, the dot product added for k
     ascending and unfused.  x [rows, d], v [R, d], b [R] float64 on the device.  A value that is not finite or reaches 2^62 in
     magnitude raises (one read-back of the device's error count): nothing wraps silently."""
-    rows, d = _attr_rows(x, "x", "lsh_buckets")
-    require_gpu(v, "v")
-    if v.dim() != 2 or v.shape[0] < 1:
-        raise _lib.KgcnHipError("lsh_buckets: v must be [R, d] with R >= 1, got %s" % (tuple(v.shape),))
-    R = v.shape[0]
-    _dev_tensor(v, "v", torch.float64, (R, d), "lsh_buckets"), _dev_tensor(b, "b", torch.float64, (R,), "lsh_buckets")
+    rows, d = _operand("lsh_buckets", "x", x, torch.float64, _ATTR_ROWS).shape
+    R = _operand("lsh_buckets", "v", v, torch.float64, ((1, None), d)).shape[0]
+    _operand("lsh_buckets", "b", b, torch.float64, (R,))
     w = float(bin_width)
     if not 0.0 < w < float("inf"):
         raise _lib.KgcnHipError("lsh_buckets: the bin width %r must be positive and finite" % (bin_width,))
@@ -3426,76 +3464,37 @@ def rank_pairs(hi, lo, mark=None):
     """Dense ranks int32 [n] of the int64 pairs (hi, lo) in ascending signed order -- np.unique(..., return_inverse=True) of the
     pairs -- and info [2] int64 on the device = (number of classes, existing rows with hi == 2^63 - 1: refuse when not 0).
     mark: None or int32 [n]; a row with mark < 0 does not exist, takes no part and gets -1."""
-    require_gpu(hi, "hi")
-    n = int(hi.numel())
-    _dev_tensor(hi, "hi", torch.int64, (n,), "rank_pairs"), _dev_tensor(lo, "lo", torch.int64, (n,), "rank_pairs")
+    n = int(_operand("rank_pairs", "hi", hi, torch.int64, (None,)).numel())
+    _operand("rank_pairs", "lo", lo, torch.int64, (n,))
     if mark is not None:
-        _dev_tensor(mark, "mark", torch.int32, (n,), "rank_pairs")
+        _operand("rank_pairs", "mark", mark, torch.int32, (n,))
     dev = hi.device
     ranks = torch.empty((max(n, 1),), device=dev, dtype=torch.int32)
     info = torch.empty((2,), device=dev, dtype=torch.int64)
     ws, wsb = _ws_bytes(lib.kgcn_rank_pairs_workspace_bytes(n), "kgcn_rank_pairs_workspace_bytes", dev)
-    check(lib.kgcn_rank_pairs_i64(ptr(hi) if n else None, ptr(lo) if n else None, None if mark is None or not n else ptr(mark), n,
+    check(lib.kgcn_rank_pairs_i64(_ptr_if(hi, n), _ptr_if(lo, n), None if mark is None else _ptr_if(mark, n), n,
                                   ptr(ranks), ptr(info), ptr(ws), wsb, current_stream()), "kgcn_rank_pairs_i64")
     return ranks[:n], info
 
 
 @torch.no_grad()
 def wl_refine_copies(csr, num_nodes, colors, copies, hash_mask=HASH_MASK_FULL):
-    """wl_refine for colors [copies, T*M] over the one stored batch -> (sorted_nbr [copies, nnz], key_hi, key_lo [copies * T*M])."""
-    T, M = _plain_square(csr, "wl_refine_copies")
-    R = _copies(copies, T, M, "wl_refine_copies")
-    dev = csr.device
-    _i32_dev(num_nodes, "num_nodes", T), _i32_dev(colors, "colors", R * T * M)
-    sorted_nbr = torch.empty((R, max(csr.nnz, 1)), device=dev, dtype=torch.int32)
-    keys = torch.empty((2, max(R * T * M, 1)), device=dev, dtype=torch.int64)
-    check(lib.kgcn_wl_refine_copies_i32(ctypes.byref(csr.desc()), ptr(num_nodes), ptr(colors), R, int(hash_mask) & HASH_MASK_FULL,
-                                        ptr(sorted_nbr), ptr(keys[0]), ptr(keys[1]), current_stream()), "kgcn_wl_refine_copies_i32")
-    return sorted_nbr, keys[0], keys[1]
+    """wl_refine for colors [copies, T*M] over the one stored batch -> (sorted_nbr [copies, max(nnz, 1)], key_hi, key_lo [copies * T*M])."""
+    return _wl_refine("wl_refine_copies", lib.kgcn_wl_refine_copies_i32, csr, num_nodes, colors, copies, hash_mask)
 
 
 @torch.no_grad()
 def wl_rank_copies(csr, num_nodes, colors, copies, sorted_nbr, key_hi, key_lo):
     """wl_rank over all copies in one ranking -> (new_colors [copies * T*M] int32, info [2]): copies whose colours are disjoint
     stay disjoint, and one info -- one read-back -- serves them all."""
-    T, M = _plain_square(csr, "wl_rank_copies")
-    R = _copies(copies, T, M, "wl_rank_copies")
-    dev = csr.device
-    n = R * T * M
-    _i32_dev(num_nodes, "num_nodes", T), _i32_dev(colors, "colors", n)
-    _dev_tensor(sorted_nbr, "sorted_nbr", torch.int32, (R, max(csr.nnz, 1)), "wl_rank_copies")
-    _dev_tensor(key_hi, "key_hi", torch.int64, (max(n, 1),), "wl_rank_copies")
-    _dev_tensor(key_lo, "key_lo", torch.int64, (max(n, 1),), "wl_rank_copies")
-    new = torch.empty((max(n, 1),), device=dev, dtype=torch.int32)
-    info = torch.empty((2,), device=dev, dtype=torch.int64)
-    ws, wsb = _ws_bytes(lib.kgcn_wl_rank_copies_workspace_bytes(T * M, R), "kgcn_wl_rank_copies_workspace_bytes", dev)
-    check(lib.kgcn_wl_rank_copies_i32(ctypes.byref(csr.desc()), ptr(num_nodes), ptr(colors), R, ptr(sorted_nbr), ptr(key_hi),
-                                      ptr(key_lo), ptr(new), ptr(info), ptr(ws), wsb, current_stream()), "kgcn_wl_rank_copies_i32")
-    return new[:n], info
-
-
-def _two_pass_runs_copies(call, T, R, dev, what):
-    """_two_pass_runs over copies * T run slots."""
-    run_ptr = torch.empty((R * T + 1,), device=dev, dtype=torch.int64)
-    ws, wsb = _ws_bytes(lib.kgcn_graph_runs_copies_workspace_bytes(T, R), "kgcn_graph_runs_copies_workspace_bytes", dev)
-    check(call(run_ptr, None, None, None, 0, ws, wsb), what)
-    total = int(run_ptr[R * T].item())
-    col = torch.empty((max(total, 1),), device=dev, dtype=torch.int64)
-    graph = torch.empty((max(total, 1),), device=dev, dtype=torch.int32)
-    count = torch.empty((max(total, 1),), device=dev, dtype=torch.int32)
-    check(call(run_ptr, col, graph, count, total, ws, wsb), what)
-    return col[:total], graph[:total], count[:total]
+    return _wl_rank("wl_rank_copies", lib.kgcn_wl_rank_copies_i32, csr, num_nodes, colors, copies, sorted_nbr, key_hi, key_lo)
 
 
 @torch.no_grad()
 def wl_runs_copies(colors, num_nodes, T, M, copies, column_offset, column_stride):
     """The colour histograms of every (copy, graph) as feature runs in slot order (all graphs of copy 0, then copy 1, ...),
     column = column_offset + copy * column_stride + colour, graph = t."""
-    R = _copies(copies, T, M, "wl_runs_copies")
-    _i32_dev(num_nodes, "num_nodes", T), _i32_dev(colors, "colors", R * T * M)
-    return _two_pass_runs_copies(lambda rp, c, g, n, cap, ws, wsb: lib.kgcn_wl_runs_copies_i32(
-        ptr(colors), ptr(num_nodes), T, M, R, int(column_offset), int(column_stride), ptr(rp), ptr(c), ptr(g), ptr(n), cap, ptr(ws),
-        wsb, current_stream()), T, R, colors.device, "kgcn_wl_runs_copies_i32")
+    return _wl_runs("wl_runs_copies", lib.kgcn_wl_runs_copies_i32, colors, num_nodes, T, M, copies, column_offset, column_stride)
 
 
 @torch.no_grad()
@@ -3503,12 +3502,7 @@ def sp_features_copies(csr, num_nodes, labels, copies, num_labels):
     """sp_features for labels [copies, T*M]: the breadth-first searches run once a graph, the keys of every copy are sorted and
     counted from the same distances; runs in slot order, column = copy << 32 | label_k << 20 | label_j << 8 | distance.
     num_labels: every copy's labels are below it, up to 4,096."""
-    T, M = _plain_square(csr, "sp_features_copies")
-    R = _copies(copies, T, M, "sp_features_copies")
-    _i32_dev(num_nodes, "num_nodes", T), _i32_dev(labels, "labels", R * T * M)
-    return _two_pass_runs_copies(lambda rp, c, g, n, cap, ws, wsb: lib.kgcn_sp_features_copies_i32(
-        ctypes.byref(csr.desc()), ptr(num_nodes), ptr(labels), R, int(num_labels), ptr(rp), ptr(c), ptr(g), ptr(n), cap, ptr(ws),
-        wsb, current_stream()), T, R, csr.device, "kgcn_sp_features_copies_i32")
+    return _sp_features("sp_features_copies", lib.kgcn_sp_features_copies_i32, csr, num_nodes, labels, copies, num_labels)
 
 
 # -------------------------------------------------------------------------------------------------
@@ -3571,12 +3565,12 @@ class SvmSets:
         return (ptr(self.ptr), ptr(self.idx)) + signs + (self.count, self.total, self.max_rows)
 
 
-def _svm_gram(K, who):
-    require_gpu(K, "K")
-    if K.dtype != torch.float64 or K.dim() != 2 or K.shape[0] != K.shape[1] or not K.is_contiguous() or not 1 <= K.shape[0] <= _SVM_MAX_GRAPHS:
-        raise _lib.KgcnHipError("%s: K must be a contiguous square float64 device matrix of 1..%d rows, got %s %s"
-                                % (who, _SVM_MAX_GRAPHS, K.dtype, tuple(K.shape)))
-    return int(K.shape[0])
+_SVM_GRAM = ((1, _SVM_MAX_GRAPHS), _SAME)
+
+
+def _ws_word(ws):
+    """The int32 control word of a workspace (what is still running), at its head as the entry point aligns it to 256 bytes."""
+    return ws[(-ws.data_ptr()) % 256:][:4].view(torch.int32)
 
 
 def _svm_host_i32(a, name, n, lo, hi, who):
@@ -3609,7 +3603,7 @@ def svm_smo_batch(K, sets, prob_set, prob_C, tol=1e-3, max_iter=None, iters_per_
     coefficients are never returned silently.  Sets of more than SVM_MAX_ROWS rows are refused before any launch."""
     import numpy as np
     who = "svm_smo_batch"
-    G = _svm_gram(K, who)
+    G = _operand(who, "K", K, torch.float64, _SVM_GRAM).shape[0]
     _svm_train_sets(sets, G, who)
     P = len(np.asarray(prob_set).reshape(-1))
     ps = _svm_host_i32(prob_set, "prob_set", P, 0, max(sets.count, 1), who)
@@ -3633,7 +3627,7 @@ def svm_smo_batch(K, sets, prob_set, prob_C, tol=1e-3, max_iter=None, iters_per_
         return alpha, rho, n_iter, np.zeros(0, np.int32), 0
     d_ps, d_pc = torch.from_numpy(ps).to(dev), torch.from_numpy(pc).to(dev)
     ws, wsb = _ws_bytes(lib.kgcn_svm_workspace_bytes(P, stride), "kgcn_svm_workspace_bytes", dev)
-    word = ws[(-ws.data_ptr()) % 256:][:4].view(torch.int32)          # the entry point aligns the workspace to 256 bytes
+    word = _ws_word(ws)
     longest = max(int(10_000_000), 100 * stride) if max_iter is None else cap
     slices = 0
     while True:
@@ -3669,7 +3663,7 @@ def svm_decision_batch(K, sets, prob_set, alpha, rho, eval_sets, job_prob, job_e
     dec = sum_t (alpha_t y_t) K[row, idx_t] - rho, t ascending over all training rows (libsvm's sign: positive is the +1 class)."""
     import numpy as np
     who = "svm_decision_batch"
-    G = _svm_gram(K, who)
+    G = _operand(who, "K", K, torch.float64, _SVM_GRAM).shape[0]
     _svm_train_sets(sets, G, who)
     if not isinstance(eval_sets, SvmSets):
         raise _lib.KgcnHipError("%s: the evaluation sets must be an SvmSets" % who)
@@ -3683,7 +3677,7 @@ def svm_decision_batch(K, sets, prob_set, alpha, rho, eval_sets, job_prob, job_e
     if J > 65535:
         raise ValueError("%s: %d jobs, up to 65,535 a call" % (who, J))
     stride = max(sets.max_rows, 1)
-    _dev_tensor(alpha, "alpha", torch.float64, (P, stride), who), _dev_tensor(rho, "rho", torch.float64, (P,), who)
+    _operand(who, "alpha", alpha, torch.float64, (P, stride)), _operand(who, "rho", rho, torch.float64, (P,))
     job_out = np.concatenate([[0], np.cumsum(eval_sets.lengths[je])]).astype(np.int64)
     total, dev = int(job_out[-1]), K.device
     dec = torch.zeros((max(total, 1),), device=dev, dtype=torch.float64)
@@ -3712,12 +3706,11 @@ def svm_vote(dec, job_out, eval_sets, vote_first_job, vote_eval, classes, labels
         raise _lib.KgcnHipError("%s: the evaluation sets must be an SvmSets" % who)
     job_out = np.ascontiguousarray(job_out, np.int64).reshape(-1)
     J, npairs = job_out.shape[0] - 1, classes * (classes - 1) // 2
-    total = int(job_out[-1]) if J >= 0 else 0
-    require_gpu(dec, "dec")
-    if J < 0 or dec.dtype != torch.float64 or not dec.is_contiguous() or dec.numel() != total:
-        raise _lib.KgcnHipError("%s: dec must be a contiguous float64 device tensor of job_out[-1] = %d values" % (who, total))
-    G = int(labels.numel())
-    _dev_tensor(labels, "labels", torch.int32, (G,), who)
+    if J < 0:
+        raise _lib.KgcnHipError("%s: job_out must hold jobs + 1 offsets, got none" % who)
+    total = int(job_out[-1])
+    _operand(who, "dec", dec, torch.float64, total)                   # job_out[-1] values
+    G = int(_operand(who, "labels", labels, torch.int32, (None,)).numel())
     if eval_sets.total and eval_sets.idx_host.max() >= G:
         raise ValueError("%s: an evaluation set names row %d, labels holds %d" % (who, int(eval_sets.idx_host.max()), G))
     V = len(np.asarray(vote_first_job).reshape(-1))
@@ -3756,12 +3749,7 @@ LP_SCORES = {"E": _lib.K["KGCN_LP_SCORE_E"], "LC_MEAN": _lib.K["KGCN_LP_SCORE_LC
 LP_DEFAULT_MAX_BYTES = 16 << 30      # the affinity matrix of 46,340 points
 
 
-def _lp_matrix(W, who):
-    require_gpu(W, "W")
-    if W.dtype != torch.float64 or W.dim() != 2 or W.shape[0] != W.shape[1] or not W.is_contiguous() or not 1 <= W.shape[0] <= LP_MAX_ROWS:
-        raise _lib.KgcnHipError("%s: W must be a contiguous square float64 device matrix of 1..%d rows, got %s %s"
-                                % (who, LP_MAX_ROWS, W.dtype, tuple(W.shape)))
-    return int(W.shape[0])
+_LP_MATRIX = ((1, LP_MAX_ROWS), _SAME)
 
 
 def _lp_task_col(task_col, who):
@@ -3780,10 +3768,7 @@ def rbf_affinity(X, gamma, max_bytes=LP_DEFAULT_MAX_BYTES):
     products on the fp64 matrix pipe; symmetric bit for bit, unit diagonal.  Refused before any launch: a matrix of more than
     max_bytes bytes, more than LP_MAX_ROWS points, a gamma that is not positive and finite, an X that is not finite."""
     who = "rbf_affinity"
-    require_gpu(X, "X")
-    if X.dtype != torch.float64 or X.dim() != 2 or not X.is_contiguous() or X.shape[0] < 1 or X.shape[1] < 1:
-        raise _lib.KgcnHipError("%s: X must be a contiguous [n, d] float64 device tensor, got %s %s" % (who, X.dtype, tuple(X.shape)))
-    n, d = int(X.shape[0]), int(X.shape[1])
+    n, d = _operand(who, "X", X, torch.float64, ((1, None), (1, None))).shape
     gamma, max_bytes = float(gamma), int(max_bytes)
     if n > LP_MAX_ROWS or n * n * 8 > max_bytes:
         raise _lib.KgcnHipError("%s: the %d x %d affinity matrix takes %d bytes, over max_bytes = %d (or over %d points); refused "
@@ -3803,7 +3788,7 @@ def rbf_affinity(X, gamma, max_bytes=LP_DEFAULT_MAX_BYTES):
 def lp_degrees(W):
     """-> (s, d) [n] float64: s_i = sum_j W_ij (LabelPropagation's normaliser) and d_i = the same without the diagonal term (the degree
     of LabelSpreading's normed Laplacian); per row the columns j = l (mod 64) in ascending order, then the lane tree."""
-    n = _lp_matrix(W, "lp_degrees")
+    n = _operand("lp_degrees", "W", W, torch.float64, _LP_MATRIX).shape[0]
     out = torch.empty((2, n), device=W.device, dtype=torch.float64)
     check(lib.kgcn_lp_degrees_f64(ptr(W), n, ptr(out[0]), ptr(out[1]), current_stream()), "kgcn_lp_degrees_f64")
     return out[0], out[1]
@@ -3818,9 +3803,9 @@ def lp_propagate(W, scale, labels, task_col, variant, alpha=0.2, tol=1e-3, max_i
     (LP_CONVERGED) or for max_iter steps (LP_MAX_ITER, n_iter = max_iter, as scikit-learn warns and goes on); a finished task
     is frozen.  One word is read back per iters_per_check steps (default LP_DEFAULT_CHECK); the grouping changes no bit."""
     who = "lp_propagate"
-    n = _lp_matrix(W, who)
+    n = _operand(who, "W", W, torch.float64, _LP_MATRIX).shape[0]
     tc, T, K = _lp_task_col(task_col, who)
-    _dev_tensor(scale, "scale", torch.float64, (n,), who), _dev_tensor(labels, "labels", torch.int32, (n, T), who)
+    _operand(who, "scale", scale, torch.float64, (n,)), _operand(who, "labels", labels, torch.int32, (n, T))
     if variant not in (LP_PROPAGATION, LP_SPREADING):
         raise ValueError("%s: variant must be LP_PROPAGATION or LP_SPREADING" % who)
     alpha, tol, max_iter = float(alpha), float(tol), int(max_iter)
@@ -3834,7 +3819,7 @@ def lp_propagate(W, scale, labels, task_col, variant, alpha=0.2, tol=1e-3, max_i
     meta = torch.zeros((2, T), device=dev, dtype=torch.int32)           # n_iter | status
     dist = torch.empty((n, K), device=dev, dtype=torch.float64)
     ws, wsb = _ws_bytes(lib.kgcn_lp_workspace_bytes(n, T, K), "kgcn_lp_workspace_bytes", dev)
-    word = ws[(-ws.data_ptr()) % 256:][:4].view(torch.int32)            # the entry point aligns the workspace to 256 bytes
+    word = _ws_word(ws)
     c_alpha, c_tol = ctypes.c_double(alpha), ctypes.c_double(tol)
     done = reads = 0
     while True:
@@ -3860,14 +3845,11 @@ def lp_scores(dist, task_col, cand):
     tasks' maxima and the sum of their margins (ActiveLearner.query)."""
     who = "lp_scores"
     tc, T, K = _lp_task_col(task_col, who)
-    require_gpu(dist, "dist")
-    if dist.dtype != torch.float64 or dist.dim() != 2 or dist.shape[1] != K or not dist.is_contiguous() or not 1 <= dist.shape[0] <= LP_MAX_ROWS:
-        raise _lib.KgcnHipError("%s: dist must be a contiguous [n, %d] float64 device tensor, got %s %s" % (who, K, dist.dtype, tuple(dist.shape)))
-    m = int(cand.numel())
-    _dev_tensor(cand, "cand", torch.int32, (m,), who)
+    n = _operand(who, "dist", dist, torch.float64, ((1, LP_MAX_ROWS), K)).shape[0]
+    m = int(_operand(who, "cand", cand, torch.int32, (None,)).numel())
     scores = torch.empty((5, m), device=dist.device, dtype=torch.float64)
     d_tc = torch.from_numpy(tc).to(dist.device)
-    check(lib.kgcn_lp_scores_f64(ptr(dist), int(dist.shape[0]), ptr(d_tc), T, K, ptr(cand), m, ptr(scores), current_stream()),
+    check(lib.kgcn_lp_scores_f64(ptr(dist), n, ptr(d_tc), T, K, ptr(cand), m, ptr(scores), current_stream()),
           "kgcn_lp_scores_f64")
     return scores
 
@@ -3879,20 +3861,20 @@ def lp_select(score, cand, n, k, largest, active=None, labels=None, truth=None, 
     active [n] int32: rows with 0 take no part.  truth [n, T] (k = 1): the picked row is taught on the device -- labels[row] =
     truth[row], active[row] = 0, log[0] = the position -- so a query-and-teach loop needs no read-back for it."""
     who = "lp_select"
-    m, n, k = int(cand.numel()), int(n), int(k)
-    _dev_tensor(cand, "cand", torch.int32, (m,), who), _dev_tensor(score, "score", torch.float64, (m,), who)
+    m, n, k = int(_operand(who, "cand", cand, torch.int32, (None,)).numel()), int(n), int(k)
+    _operand(who, "score", score, torch.float64, (m,))
     if not 1 <= k <= LP_MAX_PICKS or not 1 <= n <= LP_MAX_ROWS:
         raise _lib.KgcnHipError("%s: %d picks (1..%d) among rows of %d" % (who, k, LP_MAX_PICKS, n))
     if active is not None:
-        _dev_tensor(active, "active", torch.int32, (n,), who)
+        _operand(who, "active", active, torch.int32, (n,))
     T = 0
     if truth is not None:
         if k != 1 or labels is None or truth.dim() != 2:
             raise _lib.KgcnHipError("%s: teaching takes the single pick (k = 1), labels and truth [n, T]" % who)
         T = int(truth.shape[1])
-        _dev_tensor(truth, "truth", torch.int32, (n, T), who), _dev_tensor(labels, "labels", torch.int32, (n, T), who)
+        _operand(who, "truth", truth, torch.int32, (n, T)), _operand(who, "labels", labels, torch.int32, (n, T))
         if log is not None:
-            _dev_tensor(log, "log", torch.int32, (1,), who)
+            _operand(who, "log", log, torch.int32, (1,))
     out = torch.empty((k,), device=cand.device, dtype=torch.int32)
     check(lib.kgcn_lp_select_f64(ptr(score), ptr(cand), m, n, ptr(active), k, 1 if largest else 0, ptr(out),
                                  ptr(labels if truth is not None else None), ptr(truth), T, ptr(log), current_stream()),
