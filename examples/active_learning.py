@@ -5,8 +5,10 @@ on the rows still in the pool (mean over tasks).  Default data: the 257-point, t
 tests/golden/g16_active_learning.npz (its first 40 rows are the training set).
 
     python examples/active_learning.py [--algorithm LP|LS] [--strategy E|LC|MS|RS|all] [--gamma G] [--n 10] [--seed 0]
+                                        [--matrix-free off|on|auto]
 
---gamma defaults to 1 / d on the standardised points (the reference's own default, 20, leaves these points unconnected)."""
+--matrix-free on never stores the affinity matrix (its tiles are rebuilt where they are used; the same picks and accuracies, bit
+for bit), auto stores it when it fits the estimator's max_bytes.  --gamma defaults to 1 / d on the standardised points (the reference's own default, 20, leaves these points unconnected)."""
 import argparse
 import os
 import sys
@@ -23,6 +25,7 @@ ap.add_argument("--strategy", choices=("E", "LC", "MS", "RS", "all"), default="a
 ap.add_argument("--gamma", type=float, default=None)
 ap.add_argument("--n", type=int, default=10)
 ap.add_argument("--seed", type=int, default=0)
+ap.add_argument("--matrix-free", choices=("off", "on", "auto"), default="off")
 a = ap.parse_args()
 
 z = np.load(os.path.join(ROOT, "tests", "golden", "g16_active_learning.npz"))
@@ -31,7 +34,9 @@ gamma = 1.0 / X.shape[1] if a.gamma is None else a.gamma
 
 
 def estimator():
-    return al.LabelSpreading(gamma=gamma) if a.algorithm == "LS" else al.LabelPropagation(gamma=gamma)
+    est = al.LabelSpreading(gamma=gamma) if a.algorithm == "LS" else al.LabelPropagation(gamma=gamma)
+    est.matrix_free = {"off": False, "on": True, "auto": "auto"}[a.matrix_free]
+    return est
 
 
 def pool_accuracy(learner, X_pool, Y_pool):

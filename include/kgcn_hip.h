@@ -103,7 +103,8 @@ extern "C" {
  * The batched kernel SVM added entry points only (version still 2): kgcn_svm_smo_f64 (+ kgcn_svm_workspace_bytes),
  * kgcn_svm_decision_f64, kgcn_svm_vote_i32.
  * Active learning added entry points only (version still 2): kgcn_rbf_affinity_f64, kgcn_lp_degrees_f64, kgcn_lp_propagate_f64
- * (+ kgcn_lp_workspace_bytes), kgcn_lp_finish_f64, kgcn_lp_scores_f64, kgcn_lp_select_f64.
+ * (+ kgcn_lp_workspace_bytes), kgcn_lp_finish_f64, kgcn_lp_scores_f64, kgcn_lp_select_f64; and, without a
+ * stored affinity matrix, kgcn_rbf_apply_f64, kgcn_rbf_degrees_f64, kgcn_lp_propagate_free_f64.
  * Integrated gradients of the protein-sequence CNN added entry points only (version still 2): kgcn_ig_conv1d_expand_f32,
  * kgcn_ig_conv1d_reduce_f32. */
 #define KGCN_HIP_ABI_VERSION 2
@@ -1279,7 +1280,24 @@ int kgcn_svm_vote_i32(const double* dec, int64_t dec_total, const int64_t* job_o
  *       ActiveLearner.query); largest == 0: its first k (MS top-k; with k = 1 the first among equal minima, np.argmin).  numpy's
  *       default argsort is not stable: where scores tie the reference's own order is unspecified.  active NULL or [n]: a candidate
  *       whose row has active == 0 takes no part.  truth != NULL (k = 1 only) teaches the picked row on the device: labels[row, :] =
- *       truth[row, :] ([n, tasks] both), active[row] = 0, log[0] = the picked position (log may be NULL).  1 <= k <= KGCN_LP_MAX_PICKS. */
+ *       truth[row, :] ([n, tasks] both), active[row] = 0, log[0] = the picked position (log may be NULL).  1 <= k <= KGCN_LP_MAX_PICKS.
+ *
+ * The same without a stored W (entry points only, version still 2): each 64 x 64 tile of w is rebuilt where it is consumed, in
+ * O(n (d + cols)) memory.  Every w_ij is formed as kgcn_rbf_affinity_f64 forms it (the same norms, 16 attributes staged and 4 fed
+ * to the MFMA at a time, NaN kept, distance 0 where the two points are the same row of the same set), column tiles start at
+ * multiples of 64 and are walked upwards, a column past the set adds no term: the results below are the stored route's bit for bit.
+ *   kgcn_rbf_apply_f64      out [m, cols] = sum_j w(q_i, r_j) G_jc for queries xq [m, d], references xr [n, d] (1 <= n <=
+ *       KGCN_LP_MAX_ROWS; m >= 1 is not bounded by it) and G [n, cols], 1 <= cols <= KGCN_LP_MAX_COLS: lane l adds the rounded
+ *       products for j = l, l + 64, ... ascending from +0.0, then the lane tree.  same_set != 0: xq == xr and m == n, the diagonal
+ *       distance is 0, and zero_diagonal != 0 counts w_ii as +0.0 (refused without same_set).  norms_q [m] and norms_r [n] receive
+ *       the squared norms (norms_q is not touched, and may be NULL, with same_set).
+ *   kgcn_rbf_degrees_f64    s_out, d_out [n] of kgcn_lp_degrees_f64 from x [n, d], in its order; norms [n] receives the squared norms.
+ *   kgcn_lp_propagate_free_f64   kgcn_lp_propagate_f64 with (x [n, d], d, gamma) in place of W: the same protocol (first_step / steps,
+ *       the workspace of kgcn_lp_workspace_bytes, status / n_iter / the running word), the same steps, partials (one per block of
+ *       KGCN_LP_BLOCK_ROWS rows, in block order) and decisions.  norms [n] is written by the call with first_step == 0 and read by
+ *       the later ones.  scale = s or d of kgcn_rbf_degrees_f64.
+ *   All three refuse before any launch: a NULL operand, d < 1, n outside 1..KGCN_LP_MAX_ROWS, a gamma that is not positive and
+ *   finite, cols out of range, a short workspace. */
 enum { KGCN_LP_MAX_ROWS = 131072, KGCN_LP_MAX_TASKS = 32, KGCN_LP_MAX_COLS = 64, KGCN_LP_BLOCK_ROWS = 32, KGCN_LP_MAX_PICKS = 8,
        KGCN_LP_DEFAULT_CHECK = 8 };
 enum { KGCN_LP_PROPAGATION = 0, KGCN_LP_SPREADING = 1 };
@@ -1299,6 +1317,15 @@ int kgcn_lp_scores_f64(const double* dist, int64_t n, const int32_t* task_col, i
                        int64_t m, double* scores, void* stream);
 int kgcn_lp_select_f64(const double* score, const int32_t* cand, int64_t m, int64_t n, int32_t* active, int32_t k, int32_t largest,
                        int32_t* out, int32_t* labels, const int32_t* truth, int32_t tasks, int32_t* log, void* stream);
+int kgcn_rbf_apply_f64(const double* xq, int64_t m, const double* xr, int64_t n, int32_t d, const double* gamma, const double* G,
+                       int32_t cols, int32_t same_set, int32_t zero_diagonal, double* out, double* norms_q, double* norms_r,
+                       void* stream);
+int kgcn_rbf_degrees_f64(const double* x, int64_t n, int32_t d, const double* gamma, double* s_out, double* d_out, double* norms,
+                         void* stream);
+int kgcn_lp_propagate_free_f64(const double* x, int32_t d, const double* gamma, double* norms, const double* scale, int64_t n,
+                               const int32_t* labels, const int32_t* task_col, int32_t tasks, int32_t cols, int32_t variant,
+                               const double* alpha, const double* tol, int32_t max_iter, int32_t first_step, int32_t steps,
+                               int32_t* n_iter, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* -- k-fold cross-validation of the compound-protein interaction networks (gcn.py train_cv; csrc/cvloss.hip, csrc/cvmetrics.hip)
  * Loss head of sample_chem/compound-protein_interaction/multitask.py:53-86 (singletask.py: tasks = 1): logits [batch, 2, tasks],

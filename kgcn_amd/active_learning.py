@@ -8,6 +8,14 @@ which is a change of the label matrix on the device.  What remains per iteration
 warm start: an iteration equals a refit), the scores of the rows still in the pool and the pick, with one word read back per
 ops.LP_DEFAULT_CHECK steps.
 
+The affinity matrix need not be stored.  An estimator's attribute matrix_free (set after construction, like max_bytes; False by
+default) chooses: False keeps W [n, n] on the device and refuses above max_bytes; True never forms it -- degrees and every step
+rebuild its 64 x 64 tiles from the points where they are consumed (ops.rbf_degrees, ops.lp_propagate_free), in O(n (d + classes))
+memory and with the stored route's bits; "auto" stores W when it fits max_bytes and goes matrix-free otherwise.  After fit the
+estimators predict as scikit-learn's do: predict_proba(X) = rbf_kernel(X, X_) . label_distributions_, normalised by rows, through
+ops.rbf_apply (the [m, n] kernel is never formed), predict and score on top of it; after fit_tasks, predict_proba_tasks serves
+every task from one such product.
+
 Deviations from the reference, all of them where its own result is unspecified or differs in the last bit only:
   * ties: picks follow a STABLE ascending sort with NaN last (include/kgcn_hip.h, kgcn_lp_select_f64); numpy's default argsort,
     which the reference calls, is not stable, so where scores tie exactly its order is an accident of the sort;
@@ -27,11 +35,21 @@ import torch
 from . import ops
 from ._lib import KgcnHipError
 
-__all__ = ["LabelPropagation", "LabelSpreading", "ConvergenceWarning", "query_next_data_points", "ActiveLearner"]
+__all__ = ["LabelPropagation", "LabelSpreading", "ConvergenceWarning", "NotFittedError", "query_next_data_points", "ActiveLearner"]
 
 
 class ConvergenceWarning(UserWarning):
     """A task reached max_iter before sum |F' - F| < tol; n_iter_ = max_iter and the state is returned, as scikit-learn does."""
+
+
+class NotFittedError(ValueError, AttributeError):
+    """predict_proba, predict or score before fit (scikit-learn's exception of the same name has the same two bases)."""
+
+
+def _check_matrix_free(value):
+    if not any(value is v for v in (False, True)) and value != "auto":
+        raise ValueError("matrix_free must be False, True or 'auto', got %r" % (value,))
+    return value
 
 
 def _check_kernel(kernel):
@@ -82,12 +100,20 @@ def encode_labels(Y, classes=None):
 
 
 class _Graph:
-    """One point set on the device: W and the two degree vectors, shared by every task and every query over these points."""
+    """One point set on the device, shared by every task and every query over these points: the two degree vectors and either W
+    (the stored form) or the points and gamma that W is rebuilt from tile by tile (the matrix-free form, W = None)."""
 
-    def __init__(self, X, gamma, max_bytes=None):
-        self.W = ops.rbf_affinity(X, gamma) if max_bytes is None else ops.rbf_affinity(X, gamma, max_bytes)
-        self.s, self.d = ops.lp_degrees(self.W)
-        self.n = int(X.shape[0])
+    def __init__(self, X, gamma, max_bytes=None, matrix_free=False):
+        max_bytes = ops.LP_DEFAULT_MAX_BYTES if max_bytes is None else int(max_bytes)
+        self.n, self.X, self.gamma = int(X.shape[0]), X, gamma
+        if _check_matrix_free(matrix_free) == "auto":
+            matrix_free = self.n * self.n * 8 > max_bytes
+        if matrix_free:
+            self.W = None
+            self.s, self.d = ops.rbf_degrees(X, gamma)
+        else:
+            self.W = ops.rbf_affinity(X, gamma, max_bytes)
+            self.s, self.d = ops.lp_degrees(self.W)
 
 
 class _BaseLabelPropagation:
@@ -98,6 +124,16 @@ class _BaseLabelPropagation:
         self.alpha = None
         self.iters_per_check = None
         self.max_bytes = None
+        self._matrix_free = False
+
+    @property
+    def matrix_free(self):
+        """False: store W (refused above max_bytes); True: never store it; "auto": store it when it fits max_bytes."""
+        return self._matrix_free
+
+    @matrix_free.setter
+    def matrix_free(self, value):
+        self._matrix_free = _check_matrix_free(value)
 
     def get_params(self, deep=True):
         p = {"kernel": self.kernel, "gamma": self.gamma, "n_neighbors": self.n_neighbors, "max_iter": self.max_iter, "tol": self.tol,
@@ -111,9 +147,12 @@ class _BaseLabelPropagation:
         """-> (dist [n, K] device, n_iter [T] device, status [T] device)."""
         _check_kernel(self.kernel)
         spreading = self._variant == ops.LP_SPREADING
-        dist, n_iter, status, _ = ops.lp_propagate(graph.W, graph.d if spreading else graph.s, labels_dev, task_col, self._variant,
-                                                   alpha=self.alpha if spreading else 0.2, tol=self.tol, max_iter=self.max_iter,
-                                                   iters_per_check=self.iters_per_check)
+        kw = dict(alpha=self.alpha if spreading else 0.2, tol=self.tol, max_iter=self.max_iter, iters_per_check=self.iters_per_check)
+        scale = graph.d if spreading else graph.s
+        if graph.W is None:
+            dist, n_iter, status, _ = ops.lp_propagate_free(graph.X, graph.gamma, scale, labels_dev, task_col, self._variant, **kw)
+        else:
+            dist, n_iter, status, _ = ops.lp_propagate(graph.W, scale, labels_dev, task_col, self._variant, **kw)
         return dist, n_iter, status
 
     def _warn(self, status):
@@ -130,9 +169,11 @@ class _BaseLabelPropagation:
         labels, classes, task_col = encode_labels(Y)
         if labels.shape[0] != Xd.shape[0]:
             raise ValueError("X has %d rows, Y %d" % (Xd.shape[0], labels.shape[0]))
-        graph = _Graph(Xd, self.gamma, self.max_bytes)
+        graph = _Graph(Xd, self.gamma, self.max_bytes, self.matrix_free)
         dist, n_iter, status = self._propagate(graph, torch.from_numpy(labels).to(Xd.device), task_col)
         self._set(dist.cpu().numpy(), n_iter.cpu().numpy(), status.cpu().numpy(), classes, task_col)
+        self.X_, self._dist, self._task_col, self._single = Xd, dist, task_col, False
+        self.matrix_free_ = graph.W is None                           # the route this fit took
         return self
 
     def _set(self, dist, n_iter, status, classes, task_col):
@@ -152,7 +193,46 @@ class _BaseLabelPropagation:
         self.fit_tasks(X, y[:, None])
         self.label_distributions_, self.classes_ = self.label_distributions_[0], self.classes_[0]
         self.transduction_, self.n_iter_ = self.transduction_[0], int(self.n_iter_[0])
+        self._single = True
         return self
+
+    # -- prediction: rbf_kernel(X, X_) . label_distributions_ by ops.rbf_apply, on either route
+    def _proba(self, X, single):
+        if getattr(self, "_dist", None) is None or (single and not self._single):
+            raise NotFittedError("this %s instance is not fitted yet: call %s first" % (type(self).__name__,
+                                                                                        "fit" if single else "fit or fit_tasks"))
+        Xq = _points(X, "X")
+        if Xq.shape[1] != self.X_.shape[1]:
+            raise ValueError("X has %d attributes, the fitted points %d" % (Xq.shape[1], self.X_.shape[1]))
+        raw = ops.rbf_apply(Xq, self.X_, self.gamma, self._dist).cpu().numpy()
+        out = []
+        with np.errstate(divide="ignore", invalid="ignore"):
+            for t in range(len(self._task_col) - 1):                # scikit-learn's division: no guard, a zero row becomes NaN
+                block = raw[:, self._task_col[t]:self._task_col[t + 1]]
+                norm = np.zeros(block.shape[0])
+                for c in range(block.shape[1]):
+                    norm = norm + block[:, c]
+                out.append(block / norm[:, None])
+        return out
+
+    def predict_proba_tasks(self, X):
+        """After fit_tasks (or fit): the list over the tasks of [m, classes of the task] probabilities of the rows of X, all tasks
+        from ONE product with the kernel between X and the fitted points."""
+        return self._proba(X, False)
+
+    def predict_proba(self, X):
+        """After fit: [m, classes], rbf_kernel(X, X_) . label_distributions_ with its rows divided by their sums (the task's columns
+        added in order from +0.0).  As in scikit-learn a row whose whole kernel row underflows to 0 is NaN."""
+        return self._proba(X, True)[0]
+
+    def predict(self, X):
+        """classes_[argmax predict_proba(X)]; a NaN row gives classes_[0], as numpy's argmax does in scikit-learn."""
+        best = np.argmax(self.predict_proba(X), axis=1)
+        return self.classes_[best]
+
+    def score(self, X, y):
+        """The mean accuracy of predict(X) against y."""
+        return float(np.mean(self.predict(X) == np.asarray(y)))
 
 
 class LabelPropagation(_BaseLabelPropagation):
@@ -199,10 +279,12 @@ _LEARNER_SCORES = {"E": ("E", True), "LC": ("LC_TASKS", False), "MS": ("MS_TASKS
 
 
 def query_next_data_points(X, Y, label_presence=None, algorithm="LP", kernel="rbf", gamma=20, n_neighbors=7, max_iter=1000,
-                           tol=1e-3, n_jobs=None, alpha=0.2, US_strategy="E", seed=None):
+                           tol=1e-3, n_jobs=None, alpha=0.2, US_strategy="E", seed=None, matrix_free=False):
     """Up to five indices into X of the unlabelled rows the classifier is least certain about, in the reference's order
     (models.py:18-165): "E" the entropy summed over tasks and "LC" one minus the largest mean probability (the last five of the
-    ascending order), "MS" the margin of the mean distribution (its first five), "RS" five random unlabelled rows."""
+    ascending order), "MS" the margin of the mean distribution (its first five), "RS" five random unlabelled rows.
+    matrix_free: False, True or "auto", as the estimators' attribute."""
+    _check_matrix_free(matrix_free)
     _Y, unlabeled = unlabeled_rows(Y, label_presence)
     if US_strategy == "RS":
         return np.random.default_rng(seed).permutation(unlabeled)[:5]
@@ -220,7 +302,7 @@ def query_next_data_points(X, Y, label_presence=None, algorithm="LP", kernel="rb
     Xd = _points(X, "X")
     if Xd.shape[0] != labels.shape[0]:
         raise ValueError("X has %d rows, Y %d" % (Xd.shape[0], labels.shape[0]))
-    graph = _Graph(Xd, gamma)
+    graph = _Graph(Xd, gamma, matrix_free=matrix_free)
     dist, _, status = model._propagate(graph, torch.from_numpy(labels).to(Xd.device), task_col)
     cand = torch.from_numpy(unlabeled.astype(np.int32)).to(Xd.device)
     row, largest = _QUERY_SCORES[US_strategy]
@@ -281,7 +363,7 @@ class ActiveLearner:
         """The standardised points and their graph.  The standardisation is ops.attr_scale: StandardScaler's population-variance
         scaling with a stated summation order, a constant column becoming 0."""
         Xd = _points(X, "X")
-        return _Graph(ops.attr_scale(Xd)[0], self.estimator.gamma, self.estimator.max_bytes)
+        return _Graph(ops.attr_scale(Xd)[0], self.estimator.gamma, self.estimator.max_bytes, self.estimator.matrix_free)
 
     def query(self, X_pool):
         """-> (the index into X_pool of the row to label next, that row)."""
@@ -293,7 +375,7 @@ class ActiveLearner:
         graph = self._graph(np.vstack([self.X_training_vectors, pool]))
         Y = np.vstack([self.Y_training, np.full((len(pool), self.Y_training.shape[1]), -1, self.Y_training.dtype)])
         labels, _, task_col = encode_labels(Y)
-        dev = graph.W.device
+        dev = graph.X.device
         dist, n_iter, status = self.estimator._propagate(graph, torch.from_numpy(labels).to(dev), task_col)
         cand = torch.arange(n_train, graph.n, device=dev, dtype=torch.int32)
         row, largest = _LEARNER_SCORES[self.query_strategy]
@@ -331,7 +413,7 @@ class ActiveLearner:
             return []
         n_train = self.X_training_vectors.shape[0]
         graph = self._graph(np.vstack([self.X_training_vectors, pool]))
-        dev = graph.W.device
+        dev = graph.X.device
         truth = np.vstack([self.Y_training, Y_pool])
         truth_idx, classes, task_col = encode_labels(truth)             # the class columns of the whole loop
         start = truth_idx.copy()

@@ -10,6 +10,9 @@
 //             lane the columns j = lane (mod 64) of W, so a row of F is fetched once for 8 rows of W.  The raw sums go through LDS to
 //             an epilogue that owns one (row, task) a thread: scaling, clamp, |F' - F|.  The per-task sums of a workgroup are its
 //             partial; a one-workgroup `decide` launch adds the partials in workgroup order and freezes tasks.
+//   matrix-free   rbf_apply, rbf_degrees and the step without W: a workgroup rebuilds each 64 x 64 tile of w in LDS where it is
+//             consumed, with the arithmetic of `affinity` and the summation order of `degrees` / `step`, so the results are theirs
+//             bit for bit in O(n (d + K)) memory.
 //   finish / scores / select   one thread a (row, task) / a candidate; one workgroup picks the k best in a total order.
 // Nothing is fused: the Makefile builds this file with -ffp-contract=off (see hashkern.hip for why a pragma is not enough).
 #include <math.h>
@@ -58,13 +61,12 @@ __device__ __forceinline__ void tile_of(long b, int& ti, int& tj) {
 
 // v_mfma_f64_16x16x4_f64: lane l holds A[row l & 15][k l >> 4] and B[k l >> 4][col l & 15], result r of the lane is
 // C[row (l >> 4) + 4 r][col l & 15] (graphkern.hip's gram_tile_kernel).
-__global__ __launch_bounds__(256) void lp_affinity_kernel(const double* __restrict__ x, const double* __restrict__ norms, long n, int d,
-                                                          double gamma, double* __restrict__ W) {
-  __shared__ double as[kTile * kLd], bs[kTile * kLd];
+// THE Gram tile of this file: acc = x_a . x_b for the 64 rows of xa [na, d] from ia0 against the 64 rows of xb [nb, d] from ib0, four
+// waves of 2 x 2 MFMA blocks; 16 attributes staged at a time in as / bs [kTile][kLd], the MFMA fed 4 at a time.  Rows past the set
+// and attributes past d are staged as 0.  The panels are free again on return.
+__device__ __forceinline__ void gram_tile(const double* __restrict__ xa, long ia0, long na, const double* __restrict__ xb, long ib0,
+                                          long nb, int d, double* as, double* bs, f64x4 (&acc)[2][2]) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, li = lane & 15, hi = lane >> 4, wr = wv >> 1, wc = wv & 1;
-  int ti, tj;
-  tile_of((long)blockIdx.x, ti, tj);
-  f64x4 acc[2][2];
 #pragma unroll
   for (int a = 0; a < 2; ++a)
 #pragma unroll
@@ -73,11 +75,11 @@ __global__ __launch_bounds__(256) void lp_affinity_kernel(const double* __restri
       for (int r = 0; r < 4; ++r) acc[a][b][r] = 0.0;
   const int kk = tid & (kKc - 1);
   for (int k0 = 0; k0 < d; k0 += kKc) {
-    for (int r = tid >> 4; r < kTile; r += 16) {              // rows past n and attributes past d are staged as 0
-      const long ia = (long)ti * kTile + r, ib = (long)tj * kTile + r;
+    for (int r = tid >> 4; r < kTile; r += 16) {
+      const long ia = ia0 + r, ib = ib0 + r;
       const bool kin = k0 + kk < d;
-      as[r * kLd + kk] = (kin && ia < n) ? x[ia * d + k0 + kk] : 0.0;
-      bs[r * kLd + kk] = (kin && ib < n) ? x[ib * d + k0 + kk] : 0.0;
+      as[r * kLd + kk] = (kin && ia < na) ? xa[ia * d + k0 + kk] : 0.0;
+      bs[r * kLd + kk] = (kin && ib < nb) ? xb[ib * d + k0 + kk] : 0.0;
     }
     __syncthreads();
 #pragma unroll
@@ -95,6 +97,24 @@ __global__ __launch_bounds__(256) void lp_affinity_kernel(const double* __restri
     }
     __syncthreads();
   }
+}
+
+// w = exp(-gamma max(0, (|a|^2 + |b|^2) - 2 a.b)), NaN kept; same_point: the two are the same row of the same set, dist = 0
+__device__ __forceinline__ double rbf_weight(double na, double nb, double dot, double gamma, bool same_point) {
+  double dist = (na + nb) - 2.0 * dot;
+  if (!(dist > 0.0)) dist = dist != dist ? dist : 0.0;          // max(0, .), NaN kept
+  if (same_point) dist = 0.0;
+  return exp(-gamma * dist);
+}
+
+__global__ __launch_bounds__(256) void lp_affinity_kernel(const double* __restrict__ x, const double* __restrict__ norms, long n, int d,
+                                                          double gamma, double* __restrict__ W) {
+  __shared__ double as[kTile * kLd], bs[kTile * kLd];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, li = lane & 15, hi = lane >> 4, wr = wv >> 1, wc = wv & 1;
+  int ti, tj;
+  tile_of((long)blockIdx.x, ti, tj);
+  f64x4 acc[2][2];
+  gram_tile(x, (long)ti * kTile, n, x, (long)tj * kTile, n, d, as, bs, acc);
 #pragma unroll
   for (int p = 0; p < 2; ++p)
 #pragma unroll
@@ -103,13 +123,127 @@ __global__ __launch_bounds__(256) void lp_affinity_kernel(const double* __restri
       for (int r = 0; r < 4; ++r) {
         const long i = (long)ti * kTile + wr * 32 + p * 16 + hi + 4 * r, j = (long)tj * kTile + wc * 32 + q * 16 + li;
         if (i >= n || j >= n || i > j) continue;             // a diagonal tile stores its upper half and mirrors it, like the others
-        double dist = (norms[i] + norms[j]) - 2.0 * acc[p][q][r];
-        if (!(dist > 0.0)) dist = dist != dist ? dist : 0.0;  // max(0, .), NaN kept
-        if (i == j) dist = 0.0;
-        const double w = exp(-gamma * dist);
+        const double w = rbf_weight(norms[i], norms[j], acc[p][q][r], gamma, i == j);
         W[i * n + j] = w;
         W[j * n + i] = w;
       }
+}
+
+// ---- the affinity without its matrix ---------------------------------------------------------------------------------------------
+// A tile of w is rebuilt where it is consumed.  Every w_ij carries the bits lp_affinity_kernel stores: the same gram_tile, the same
+// norms, the same rbf_weight (a.b and b.a are the same products in the same k order).  The consumers keep the stored kernels'
+// summation order: lane l owns the columns j = l (mod 64), so column tiles start at multiples of 64 and are walked upwards.
+struct RbfSets {
+  const double *xq, *nq;       // queries [m, d] and their norms
+  long m;
+  const double *xr, *nr;       // references [n, d] and their norms
+  long n;
+  int d, same;                 // same: xq IS xr (row i of one is row i of the other)
+  double gamma;
+};
+
+constexpr int kWt = kTile + 1;                                  // the tile's row pitch in LDS
+constexpr int kTileDoubles = kTile * kWt;                       // ... which lies over the two staging panels
+constexpr int kRowsTileWave = kTile / 4;                        // rows of a tile a wave consumes
+static_assert(2 * kTile * kLd <= kTileDoubles, "the tile covers the panels it is built from");
+
+// tile (rows i0 .., columns j0 ..) of w -> wt [kTile][kWt] at smem; entries outside the sets are 0 and unused
+__device__ __forceinline__ void rbf_tile(const RbfSets& s, long i0, long j0, double* smem) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, li = lane & 15, hi = lane >> 4, wr = wv >> 1, wc = wv & 1;
+  f64x4 acc[2][2];
+  gram_tile(s.xq, i0, s.m, s.xr, j0, s.n, s.d, smem, smem + kTile * kLd, acc);
+#pragma unroll
+  for (int p = 0; p < 2; ++p)
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int tr = wr * 32 + p * 16 + hi + 4 * r, tc = wc * 32 + q * 16 + li;
+        const long i = i0 + tr, j = j0 + tc;
+        smem[tr * kWt + tc] = (i < s.m && j < s.n) ? rbf_weight(s.nq[i], s.nr[j], acc[p][q][r], s.gamma, s.same && i == j) : 0.0;
+      }
+  __syncthreads();
+}
+
+// use(j0) once per column tile, in ascending order, with the tile in smem
+template <typename Fn>
+__device__ __forceinline__ void rbf_for_tiles(const RbfSets& s, long i0, double* smem, Fn&& use) {
+  for (long j0 = 0; j0 < s.n; j0 += kTile) {
+    rbf_tile(s, i0, j0, smem);
+    use(j0);
+    __syncthreads();
+  }
+}
+
+// The terms of one tile: acc[r][c] = acc[r][c] + w_ij G_jc for the wave's rows i = irow0 + r and the lane's column j, each
+// product rounded before it is added; a column past the set adds nothing; zero_diag: w_ii counts as +0.0.
+template <int KC>
+__device__ __forceinline__ void rbf_terms(const double* wt, long irow0, long j, long n, bool zero_diag, const double* __restrict__ G,
+                                          int K, int c0, double (&acc)[kRowsTileWave][KC]) {
+  if (j >= n) return;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  double g[KC];
+#pragma unroll
+  for (int c = 0; c < KC; ++c) g[c] = c0 + c < K ? G[j * K + c0 + c] : 0.0;
+#pragma unroll
+  for (int r = 0; r < kRowsTileWave; ++r) {
+    double w = wt[(wv * kRowsTileWave + r) * kWt + lane];
+    if (zero_diag && j == irow0 + r) w = 0.0;
+#pragma unroll
+    for (int c = 0; c < KC; ++c) acc[r][c] = acc[r][c] + w * g[c];
+  }
+}
+
+// out[i, c] = sum_j w(q_i, r_j) G_jc: a workgroup owns 64 queries, a wave 16 of them, KC columns of G at a time
+template <int KC>
+__global__ __launch_bounds__(256) void rbf_apply_kernel(RbfSets s, int zero_diag, const double* __restrict__ G, int K,
+                                                        double* __restrict__ out) {
+  __shared__ double smem[kTileDoubles];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const long i0 = (long)blockIdx.x * kTile, irow0 = i0 + wv * kRowsTileWave;
+  for (int c0 = 0; c0 < K; c0 += KC) {
+    double acc[kRowsTileWave][KC];
+#pragma unroll
+    for (int r = 0; r < kRowsTileWave; ++r)
+#pragma unroll
+      for (int c = 0; c < KC; ++c) acc[r][c] = 0.0;
+    rbf_for_tiles(s, i0, smem, [&](long j0) { rbf_terms<KC>(smem, irow0, j0 + lane, s.n, zero_diag != 0, G, K, c0, acc); });
+#pragma unroll
+    for (int r = 0; r < kRowsTileWave; ++r)
+#pragma unroll
+      for (int c = 0; c < KC; ++c) {
+        const double v = wave_tree_sum(acc[r][c]);
+        if (lane == 0 && irow0 + r < s.m && c0 + c < K) out[(irow0 + r) * K + c0 + c] = v;
+      }
+  }
+}
+
+// lp_degrees_kernel without W: the same two sums in the same order
+__global__ __launch_bounds__(256) void rbf_degrees_kernel(RbfSets s, double* __restrict__ s_out, double* __restrict__ d_out) {
+  __shared__ double smem[kTileDoubles];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const long i0 = (long)blockIdx.x * kTile, irow0 = i0 + wv * kRowsTileWave;
+  double sum[kRowsTileWave], dg[kRowsTileWave];
+#pragma unroll
+  for (int r = 0; r < kRowsTileWave; ++r) sum[r] = dg[r] = 0.0;
+  rbf_for_tiles(s, i0, smem, [&](long j0) {
+    const long j = j0 + lane;
+    if (j >= s.n) return;
+#pragma unroll
+    for (int r = 0; r < kRowsTileWave; ++r) {
+      const double w = smem[(wv * kRowsTileWave + r) * kWt + lane];
+      sum[r] = sum[r] + w;
+      dg[r] = dg[r] + (j == irow0 + r ? 0.0 : w);
+    }
+  });
+#pragma unroll
+  for (int r = 0; r < kRowsTileWave; ++r) {
+    const double a = wave_tree_sum(sum[r]), b = wave_tree_sum(dg[r]);
+    if (lane == 0 && irow0 + r < s.n) {
+      s_out[irow0 + r] = a;
+      d_out[irow0 + r] = b;
+    }
+  }
 }
 
 // s_i = sum over ALL j, d_i = the same sum with the diagonal term replaced by +0.0.  Lane l adds the columns j = l, l + 64, ... in
@@ -135,8 +269,9 @@ __global__ __launch_bounds__(256) void lp_degrees_kernel(const double* __restric
 
 // ---- propagation ----------------------------------------------------------------------------------------------------------------
 struct LpArgs {
-  const double* W;
-  const double* scale;         // propagation: s [n]; spreading: d [n]
+  const double* W;             // the stored route; NULL on the matrix-free one, which reads `pts`
+  RbfSets pts;
+  const double* scale;        // propagation: s [n]; spreading: d [n]
   const int32_t* labels;       // [n, T] class index of the task or -1
   const int32_t* task_col;     // [T + 1]
   long n;
@@ -161,12 +296,12 @@ __device__ __forceinline__ double y_static(const LpArgs& a, int label, int c) {
 }
 
 // the tail shared by init and step: rowdelta [32][T] in LDS -> partial[block][t], rows in ascending order from +0.0
-__device__ __forceinline__ void block_partials(const LpArgs& a, const double (*rowdelta)[kMaxTasks]) {
+__device__ __forceinline__ void block_partials(const LpArgs& a, const double (*rowdelta)[kMaxTasks], long block) {
   __syncthreads();
   if ((int)threadIdx.x < a.T) {
     double p = 0.0;
     for (int r = 0; r < kRowsWg; ++r) p = p + rowdelta[r][threadIdx.x];
-    a.partial[(long)blockIdx.x * a.T + threadIdx.x] = p;
+    a.partial[block * a.T + threadIdx.x] = p;
   }
 }
 
@@ -189,7 +324,7 @@ __global__ __launch_bounds__(256) void lp_init_kernel(LpArgs a) {
     }
     rowdelta[r][t] = delta;
   }
-  block_partials(a, rowdelta);
+  block_partials(a, rowdelta, (long)blockIdx.x);
 }
 
 // After `step` steps: a running task whose partials add up (workgroup order, from +0.0) to less than tol has converged with n_iter =
@@ -221,6 +356,53 @@ __global__ __launch_bounds__(64) void lp_decide_kernel(LpArgs a, int blocks) {
     for (int q = 0; q < a.T; ++q) c += left[q];
     *a.running = c;
   }
+}
+
+// THE epilogue of a step, for one block of kRowsWg rows whose raw sums are in LDS: one (row, task) a thread -- scaling, clamp,
+// |F' - F|, the copy of a frozen task -- and the block's partials.  Every thread of the workgroup calls it.
+__device__ __forceinline__ void step_epilogue(const LpArgs& a, const double (*raw)[kMaxCols], double (*rowdelta)[kMaxTasks], long block,
+                                              const int* frozen, const int* tcol) {
+  const long n = a.n;
+  const int K = a.K;
+  for (int e = threadIdx.x; e < kRowsWg * a.T; e += 256) {
+    const int r = e / a.T, t = e - r * a.T;
+    const long i = block * kRowsWg + r;
+    double delta = 0.0;
+    if (i < n) {
+      const int b0 = tcol[t], b1 = tcol[t + 1];
+      const double* fp = a.Fprev + i * K;
+      double* fn = a.Fnext + i * K;
+      if (frozen[t]) {
+        for (int c = b0; c < b1; ++c) {
+          fn[c] = fp[c];
+          if (a.spreading) a.Gnext[i * K + c] = a.Gprev[i * K + c];
+        }
+      } else {
+        const int label = a.labels[i * a.T + t];
+        if (a.spreading) {
+          const double sd = sqrt_degree(a.scale[i]);
+          for (int c = b0; c < b1; ++c) {
+            const double v = a.alpha * (raw[r][c] / sd) + y_static(a, label, c - b0);
+            delta = delta + fabs(v - fp[c]);
+            fn[c] = v;
+            a.Gnext[i * K + c] = v / sd;
+          }
+        } else {
+          const double s = a.scale[i];
+          double norm = 0.0;
+          for (int c = b0; c < b1; ++c) norm = norm + raw[r][c] / s;
+          if (norm == 0.0) norm = 1.0;
+          for (int c = b0; c < b1; ++c) {
+            const double v = label >= 0 ? y_static(a, label, c - b0) : (raw[r][c] / s) / norm;
+            delta = delta + fabs(v - fp[c]);
+            fn[c] = v;
+          }
+        }
+      }
+    }
+    rowdelta[r][t] = delta;
+  }
+  block_partials(a, rowdelta, block);
 }
 
 // One step.  raw[r][c] = sum_j w_ij G_jc: lane l adds j = l, l + 64, ... ascending from +0.0, each term w * g rounded before it is
@@ -293,45 +475,57 @@ __global__ __launch_bounds__(256) void lp_step_kernel(LpArgs a) {
       }
   }
   __syncthreads();
-  for (int e = tid; e < kRowsWg * a.T; e += 256) {
-    const int r = e / a.T, t = e - r * a.T;
-    const long i = (long)blockIdx.x * kRowsWg + r;
-    double delta = 0.0;
-    if (i < n) {
-      const int b0 = tcol[t], b1 = tcol[t + 1];
-      const double* fp = a.Fprev + i * K;
-      double* fn = a.Fnext + i * K;
-      if (frozen[t]) {
-        for (int c = b0; c < b1; ++c) {
-          fn[c] = fp[c];
-          if (a.spreading) a.Gnext[i * K + c] = a.Gprev[i * K + c];
-        }
-      } else {
-        const int label = a.labels[i * a.T + t];
-        if (a.spreading) {
-          const double sd = sqrt_degree(a.scale[i]);
-          for (int c = b0; c < b1; ++c) {
-            const double v = a.alpha * (raw[r][c] / sd) + y_static(a, label, c - b0);
-            delta = delta + fabs(v - fp[c]);
-            fn[c] = v;
-            a.Gnext[i * K + c] = v / sd;
-          }
-        } else {
-          const double s = a.scale[i];
-          double norm = 0.0;
-          for (int c = b0; c < b1; ++c) norm = norm + raw[r][c] / s;
-          if (norm == 0.0) norm = 1.0;
-          for (int c = b0; c < b1; ++c) {
-            const double v = label >= 0 ? y_static(a, label, c - b0) : (raw[r][c] / s) / norm;
-            delta = delta + fabs(v - fp[c]);
-            fn[c] = v;
-          }
-        }
+  step_epilogue(a, raw, rowdelta, (long)blockIdx.x, frozen, tcol);
+}
+
+// The step without W: a workgroup owns 64 rows (two blocks of the convergence partials), a wave 16 of them; the tiles of w come
+// from rbf_for_tiles, the terms from rbf_terms in lp_step_kernel's order, the rest is lp_step_kernel's.  LDS: the tile (under the
+// panels it is built from, and later under rowdelta), raw [64][kMaxCols], frozen and tcol -- all of it dynamic: a kernel that is
+// allowed the CU's full LDS can hold no static LDS beside it.
+constexpr size_t kFreeStepLds = (size_t)(kTileDoubles + kTile * kMaxCols) * sizeof(double) + (2 * kMaxTasks + 2) * sizeof(int);
+static_assert(kRowsWg * kMaxTasks <= kTileDoubles && kTile == 2 * kRowsWg, "rowdelta lies over the tile; a workgroup is two blocks");
+
+template <int KC>
+__global__ __launch_bounds__(256) void lp_free_step_kernel(LpArgs a) {
+  extern __shared__ double lds[];
+  int* frozen = reinterpret_cast<int*>(lds + kTileDoubles + kTile * kMaxCols);
+  int* tcol = frozen + kMaxTasks;
+  double* smem = lds;
+  double(*raw)[kMaxCols] = reinterpret_cast<double(*)[kMaxCols]>(lds + kTileDoubles);
+  double(*rowdelta)[kMaxTasks] = reinterpret_cast<double(*)[kMaxTasks]>(lds);
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  if (tid < a.T) frozen[tid] = a.status[tid] != KGCN_LP_RUNNING;
+  if (tid <= a.T) tcol[tid] = a.task_col[tid];
+  __syncthreads();
+  const long i0 = (long)blockIdx.x * kTile, irow0 = i0 + wv * kRowsTileWave;
+  const int K = a.K;
+  for (int c0 = 0; c0 < K; c0 += KC) {
+    bool live = false;                                        // workgroup-uniform, as in lp_step_kernel
+    for (int t = 0; t < a.T; ++t) live = live || (!frozen[t] && tcol[t] < c0 + KC && tcol[t + 1] > c0);
+    if (!live) continue;
+    double acc[kRowsTileWave][KC];
+#pragma unroll
+    for (int r = 0; r < kRowsTileWave; ++r)
+#pragma unroll
+      for (int c = 0; c < KC; ++c) acc[r][c] = 0.0;
+    rbf_for_tiles(a.pts, i0, smem,
+                  [&](long j0) { rbf_terms<KC>(smem, irow0, j0 + lane, a.n, a.spreading != 0, a.Gprev, K, c0, acc); });
+#pragma unroll
+    for (int r = 0; r < kRowsTileWave; ++r)
+#pragma unroll
+      for (int c = 0; c < KC; ++c) {
+        const double v = wave_tree_sum(acc[r][c]);
+        if (lane == 0 && c0 + c < K) raw[wv * kRowsTileWave + r][c0 + c] = v;
       }
-    }
-    rowdelta[r][t] = delta;
   }
-  block_partials(a, rowdelta);
+  __syncthreads();
+  const long blocks = (a.n + kRowsWg - 1) / kRowsWg;
+  for (int h = 0; h < 2; ++h) {                                 // the second block of the last workgroup may not exist
+    const long block = (long)blockIdx.x * 2 + h;
+    if (block >= blocks) break;
+    if (h) __syncthreads();                                     // the first block's partials have been read
+    step_epilogue(a, raw + h * kRowsWg, rowdelta, block, frozen, tcol);
+  }
 }
 
 // dist = F / (row sum over the task's columns, ascending from +0.0; 0 counts as 1)
@@ -506,6 +700,79 @@ Workspace carve(void* workspace, int64_t n, int32_t K) {
   return o;
 }
 
+int check_points(const char* who, int64_t n, int32_t d, const double* gamma) {
+  if (n < 1 || n > KGCN_LP_MAX_ROWS || d < 1) return fail("%s: %lld points of %d attributes (1..%d points)", who, (long long)n, d, KGCN_LP_MAX_ROWS);
+  if (!gamma || !(*gamma > 0.0) || !(*gamma < INFINITY)) return fail("%s: gamma must be positive and finite", who);
+  return 0;
+}
+
+void launch_norms(const double* x, int64_t n, int32_t d, double* norms, hipStream_t s) {
+  hipLaunchKernelGGL(lp_norms_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, (long)n, d, norms);
+}
+
+template <int KC>
+int launch_free_step(const char* who, const LpArgs& a, hipStream_t s) {
+  if (int rc = allow_full_lds<lp_free_step_kernel<KC>>(kFreeStepLds, who)) return rc;
+  hipLaunchKernelGGL(lp_free_step_kernel<KC>, dim3((unsigned)((a.n + kTile - 1) / kTile)), dim3(256), kFreeStepLds, s, a);
+  return 0;
+}
+
+// THE protocol of both propagation entry points: W != NULL sweeps the stored matrix, W == NULL rebuilds it from x (whose norms the
+// start writes to `norms` and the later calls read there).
+int lp_propagate_steps(const char* who, const double* W, const double* x, double* norms, int32_t d, const double* gamma,
+                       const double* scale, int64_t n, const int32_t* labels, const int32_t* task_col, int32_t tasks, int32_t cols,
+                       int32_t variant, const double* alpha, const double* tol, int32_t max_iter, int32_t first_step, int32_t steps,
+                       int32_t* n_iter, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (int rc = check_shape(who, n, tasks, cols)) return rc;
+  if (!W)
+    if (int rc = check_points(who, n, d, gamma)) return rc;
+  if (variant != KGCN_LP_PROPAGATION && variant != KGCN_LP_SPREADING) return fail("%s: variant %d", who, variant);
+  if (variant == KGCN_LP_SPREADING && !(alpha && *alpha > 0.0 && *alpha < 1.0)) return fail("%s: alpha must lie in (0, 1)", who);
+  if (!tol || !(*tol >= 0.0) || !(*tol < INFINITY)) return fail("%s: the tolerance must be finite and not negative", who);
+  if (max_iter < 0 || first_step < 0 || steps < 0 || (int64_t)first_step + steps >= INT32_MAX)
+    return fail("%s: max_iter %d, first_step %d, steps %d", who, max_iter, first_step, steps);
+  const int64_t need = kgcn_lp_workspace_bytes(n, tasks, cols);
+  if (!workspace || workspace_bytes < need) return fail("%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes, (long long)need);
+  if ((!W && (!x || !norms)) || !scale || !labels || !task_col || !n_iter || !status) return fail("%s: NULL operand", who);
+  const Workspace ws = carve(workspace, n, cols);
+  hipStream_t s = as_stream(stream);
+  const long blocks = step_blocks(n);
+  const bool spreading = variant == KGCN_LP_SPREADING;
+  LpArgs a{};
+  a.W = W;
+  if (!W) a.pts = RbfSets{x, norms, (long)n, x, norms, (long)n, d, 1, *gamma};
+  a.scale = scale, a.labels = labels, a.task_col = task_col;
+  a.n = (long)n, a.T = tasks, a.K = cols, a.spreading = spreading ? 1 : 0;
+  a.alpha = spreading ? *alpha : 0.0, a.tol = *tol, a.max_iter = max_iter;
+  a.partial = ws.partial, a.status = status, a.n_iter = n_iter, a.running = ws.running;
+  if (first_step == 0) {
+    if (hipMemsetAsync(status, 0, (size_t)tasks * sizeof(int32_t), s) != hipSuccess ||
+        hipMemsetAsync(n_iter, 0, (size_t)tasks * sizeof(int32_t), s) != hipSuccess)
+      return fail("%s: hipMemsetAsync failed", who);
+    if (!W) launch_norms(x, n, d, norms, s);
+    a.Fnext = ws.F[0];
+    a.Gnext = ws.G[0];
+    hipLaunchKernelGGL(lp_init_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(lp_decide_kernel, dim3(1), dim3(64), 0, s, a, (int)blocks);
+  }
+  for (int k = first_step; k < first_step + steps; ++k) {
+    a.step = k;
+    a.Fprev = ws.F[k & 1];
+    a.Gprev = spreading ? ws.G[k & 1] : ws.F[k & 1];
+    a.Fnext = ws.F[(k + 1) & 1];
+    a.Gnext = ws.G[(k + 1) & 1];
+    if (W) {
+      if (cols <= 4) hipLaunchKernelGGL(lp_step_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, s, a);
+      else hipLaunchKernelGGL(lp_step_kernel<8>, dim3((unsigned)blocks), dim3(256), 0, s, a);
+    } else if (int rc = cols <= 4 ? launch_free_step<4>(who, a, s) : launch_free_step<8>(who, a, s)) {
+      return rc;
+    }
+    a.step = k + 1;
+    hipLaunchKernelGGL(lp_decide_kernel, dim3(1), dim3(64), 0, s, a, (int)blocks);
+  }
+  return check_launch(who);
+}
+
 }  // namespace
 }  // namespace kgcn
 
@@ -545,41 +812,50 @@ extern "C" int kgcn_lp_propagate_f64(const double* W, const double* scale, int64
                                      int32_t first_step, int32_t steps, int32_t* n_iter, int32_t* status, void* workspace,
                                      int64_t workspace_bytes, void* stream) {
   const char* who = "kgcn_lp_propagate_f64";
-  if (int rc = check_shape(who, n, tasks, cols)) return rc;
-  if (variant != KGCN_LP_PROPAGATION && variant != KGCN_LP_SPREADING) return fail("%s: variant %d", who, variant);
-  if (variant == KGCN_LP_SPREADING && !(alpha && *alpha > 0.0 && *alpha < 1.0)) return fail("%s: alpha must lie in (0, 1)", who);
-  if (!tol || !(*tol >= 0.0) || !(*tol < INFINITY)) return fail("%s: the tolerance must be finite and not negative", who);
-  if (max_iter < 0 || first_step < 0 || steps < 0 || (int64_t)first_step + steps >= INT32_MAX)
-    return fail("%s: max_iter %d, first_step %d, steps %d", who, max_iter, first_step, steps);
-  const int64_t need = kgcn_lp_workspace_bytes(n, tasks, cols);
-  if (!workspace || workspace_bytes < need) return fail("%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes, (long long)need);
-  if (!W || !scale || !labels || !task_col || !n_iter || !status) return fail("%s: NULL operand", who);
-  const Workspace ws = carve(workspace, n, cols);
+  if (!W) return fail("%s: NULL operand", who);
+  return lp_propagate_steps(who, W, nullptr, nullptr, 0, nullptr, scale, n, labels, task_col, tasks, cols, variant, alpha, tol, max_iter,
+                            first_step, steps, n_iter, status, workspace, workspace_bytes, stream);
+}
+
+extern "C" int kgcn_lp_propagate_free_f64(const double* x, int32_t d, const double* gamma, double* norms, const double* scale, int64_t n,
+                                          const int32_t* labels, const int32_t* task_col, int32_t tasks, int32_t cols, int32_t variant,
+                                          const double* alpha, const double* tol, int32_t max_iter, int32_t first_step, int32_t steps,
+                                          int32_t* n_iter, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* who = "kgcn_lp_propagate_free_f64";
+  if (!x || !norms) return fail("%s: NULL operand", who);
+  return lp_propagate_steps(who, nullptr, x, norms, d, gamma, scale, n, labels, task_col, tasks, cols, variant, alpha, tol, max_iter,
+                            first_step, steps, n_iter, status, workspace, workspace_bytes, stream);
+}
+
+extern "C" int kgcn_rbf_apply_f64(const double* xq, int64_t m, const double* xr, int64_t n, int32_t d, const double* gamma, const double* G,
+                                  int32_t cols, int32_t same_set, int32_t zero_diagonal, double* out, double* norms_q, double* norms_r,
+                                  void* stream) {
+  const char* who = "kgcn_rbf_apply_f64";
+  if (int rc = check_points(who, n, d, gamma)) return rc;
+  if (m < 1 || m > ((int64_t)1 << 36)) return fail("%s: %lld queries", who, (long long)m);
+  if (cols < 1 || cols > kMaxCols) return fail("%s: %d columns outside 1..%d", who, cols, kMaxCols);
+  if (!xq || !xr || !G || !out || !norms_r || (!same_set && !norms_q)) return fail("%s: NULL operand", who);
+  if (same_set ? (xq != xr || m != n) : zero_diagonal != 0)
+    return fail("%s: same_set takes one point set as queries and references; zero_diagonal takes same_set", who);
   hipStream_t s = as_stream(stream);
-  const long blocks = step_blocks(n);
-  const bool spreading = variant == KGCN_LP_SPREADING;
-  LpArgs a{W, scale, labels, task_col, (long)n, tasks, cols, spreading ? 1 : 0, spreading ? *alpha : 0.0, *tol, max_iter, 0, nullptr, nullptr, nullptr,
-           nullptr, ws.partial, status, n_iter, ws.running};
-  if (first_step == 0) {
-    if (hipMemsetAsync(status, 0, (size_t)tasks * sizeof(int32_t), s) != hipSuccess ||
-        hipMemsetAsync(n_iter, 0, (size_t)tasks * sizeof(int32_t), s) != hipSuccess)
-      return fail("%s: hipMemsetAsync failed", who);
-    a.Fnext = ws.F[0];
-    a.Gnext = ws.G[0];
-    hipLaunchKernelGGL(lp_init_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(lp_decide_kernel, dim3(1), dim3(64), 0, s, a, (int)blocks);
-  }
-  for (int k = first_step; k < first_step + steps; ++k) {
-    a.step = k;
-    a.Fprev = ws.F[k & 1];
-    a.Gprev = spreading ? ws.G[k & 1] : ws.F[k & 1];
-    a.Fnext = ws.F[(k + 1) & 1];
-    a.Gnext = ws.G[(k + 1) & 1];
-    if (cols <= 4) hipLaunchKernelGGL(lp_step_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(lp_step_kernel<8>, dim3((unsigned)blocks), dim3(256), 0, s, a);
-    a.step = k + 1;
-    hipLaunchKernelGGL(lp_decide_kernel, dim3(1), dim3(64), 0, s, a, (int)blocks);
-  }
+  launch_norms(xr, n, d, norms_r, s);
+  if (!same_set) launch_norms(xq, m, d, norms_q, s);
+  const RbfSets sets{xq, same_set ? norms_r : norms_q, (long)m, xr, norms_r, (long)n, d, same_set ? 1 : 0, *gamma};
+  const dim3 grid((unsigned)((m + kTile - 1) / kTile));
+  if (cols <= 4) hipLaunchKernelGGL(rbf_apply_kernel<4>, grid, dim3(256), 0, s, sets, zero_diagonal ? 1 : 0, G, cols, out);
+  else hipLaunchKernelGGL(rbf_apply_kernel<8>, grid, dim3(256), 0, s, sets, zero_diagonal ? 1 : 0, G, cols, out);
+  return check_launch(who);
+}
+
+extern "C" int kgcn_rbf_degrees_f64(const double* x, int64_t n, int32_t d, const double* gamma, double* s_out, double* d_out, double* norms,
+                                    void* stream) {
+  const char* who = "kgcn_rbf_degrees_f64";
+  if (int rc = check_points(who, n, d, gamma)) return rc;
+  if (!x || !s_out || !d_out || !norms) return fail("%s: NULL operand", who);
+  hipStream_t s = as_stream(stream);
+  launch_norms(x, n, d, norms, s);
+  const RbfSets sets{x, norms, (long)n, x, norms, (long)n, d, 1, *gamma};
+  hipLaunchKernelGGL(rbf_degrees_kernel, dim3((unsigned)((n + kTile - 1) / kTile)), dim3(256), 0, s, sets, s_out, d_out);
   return check_launch(who);
 }
 

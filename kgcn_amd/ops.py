@@ -3738,7 +3738,8 @@ def svm_vote(dec, job_out, eval_sets, vote_first_job, vote_eval, classes, labels
 # -------------------------------------------------------------------------------------------------
 # active learning (csrc/labelprop.hip; the driver is kgcn_amd/active_learning.py): one RBF affinity matrix for every task and
 # every query over the same points, label propagation / spreading for all tasks in one sweep over it, uncertainty scores and
-# the pick on the device.  fp64 and integers, stated summation orders (include/kgcn_hip.h): bitwise reproducible.
+# the pick on the device.  fp64 and integers, stated summation orders (include/kgcn_hip.h): bitwise reproducible.  The matrix
+# need not be stored: rbf_apply / rbf_degrees / lp_propagate_free rebuild its tiles where they are consumed, with the same bits.
 # -------------------------------------------------------------------------------------------------
 LP_MAX_ROWS, LP_MAX_TASKS, LP_MAX_COLS, LP_BLOCK_ROWS, LP_MAX_PICKS, LP_DEFAULT_CHECK = (_lib.K["KGCN_LP_" + n] for n in (
     "MAX_ROWS", "MAX_TASKS", "MAX_COLS", "BLOCK_ROWS", "MAX_PICKS", "DEFAULT_CHECK"))
@@ -3794,6 +3795,40 @@ def lp_degrees(W):
     return out[0], out[1]
 
 
+def _lp_run(who, entry, front, n, labels, task_col, variant, alpha, tol, max_iter, iters_per_check, dev):
+    """THE launch / read-back loop of lp_propagate and lp_propagate_free: `entry` is the C entry point, `front` its arguments
+    before n (the matrix, or the points): both share everything from n on.  -> (dist, n_iter, status, words read back)."""
+    tc, T, K = _lp_task_col(task_col, who)
+    _operand(who, "labels", labels, torch.int32, (n, T))
+    if variant not in (LP_PROPAGATION, LP_SPREADING):
+        raise ValueError("%s: variant must be LP_PROPAGATION or LP_SPREADING" % who)
+    alpha, tol, max_iter = float(alpha), float(tol), int(max_iter)
+    ipc = LP_DEFAULT_CHECK if iters_per_check is None else int(iters_per_check)
+    if variant == LP_SPREADING and not 0.0 < alpha < 1.0:
+        raise ValueError("%s: alpha must lie in (0, 1), got %r" % (who, alpha))
+    if not 0.0 <= tol < float("inf") or not 1 <= max_iter < 2 ** 30 or ipc < 1:
+        raise ValueError("%s: tol %r, max_iter %r, iters_per_check %r" % (who, tol, max_iter, ipc))
+    d_tc = torch.from_numpy(tc).to(dev)
+    meta = torch.zeros((2, T), device=dev, dtype=torch.int32)           # n_iter | status
+    dist = torch.empty((n, K), device=dev, dtype=torch.float64)
+    ws, wsb = _ws_bytes(lib.kgcn_lp_workspace_bytes(n, T, K), "kgcn_lp_workspace_bytes", dev)
+    word = _ws_word(ws)
+    c_alpha, c_tol = ctypes.c_double(alpha), ctypes.c_double(tol)
+    done = reads = 0
+    while True:
+        steps = min(ipc, max_iter - done)
+        check(entry(*front, n, ptr(labels), ptr(d_tc), T, K, variant, ctypes.byref(c_alpha), ctypes.byref(c_tol), max_iter, done,
+                    steps, ptr(meta[0]), ptr(meta[1]), ptr(ws), wsb, current_stream()), entry.__name__)
+        done += steps
+        reads += 1
+        if int(word.item()) == 0:
+            break
+        if done >= max_iter:
+            raise _lib.KgcnHipError("%s: tasks still running after max_iter = %d steps" % (who, max_iter))
+    check(lib.kgcn_lp_finish_f64(n, ptr(d_tc), T, K, done, ptr(dist), ptr(ws), wsb, current_stream()), "kgcn_lp_finish_f64")
+    return dist, meta[0], meta[1], reads
+
+
 @torch.no_grad()
 def lp_propagate(W, scale, labels, task_col, variant, alpha=0.2, tol=1e-3, max_iter=1000, iters_per_check=None):
     """Label propagation (variant LP_PROPAGATION, scale = s of lp_degrees) or spreading (LP_SPREADING, scale = d) of all tasks at
@@ -3804,37 +3839,71 @@ def lp_propagate(W, scale, labels, task_col, variant, alpha=0.2, tol=1e-3, max_i
     is frozen.  One word is read back per iters_per_check steps (default LP_DEFAULT_CHECK); the grouping changes no bit."""
     who = "lp_propagate"
     n = _operand(who, "W", W, torch.float64, _LP_MATRIX).shape[0]
-    tc, T, K = _lp_task_col(task_col, who)
-    _operand(who, "scale", scale, torch.float64, (n,)), _operand(who, "labels", labels, torch.int32, (n, T))
-    if variant not in (LP_PROPAGATION, LP_SPREADING):
-        raise ValueError("%s: variant must be LP_PROPAGATION or LP_SPREADING" % who)
-    alpha, tol, max_iter = float(alpha), float(tol), int(max_iter)
-    ipc = LP_DEFAULT_CHECK if iters_per_check is None else int(iters_per_check)
-    if variant == LP_SPREADING and not 0.0 < alpha < 1.0:
-        raise ValueError("%s: alpha must lie in (0, 1), got %r" % (who, alpha))
-    if not 0.0 <= tol < float("inf") or not 1 <= max_iter < 2 ** 30 or ipc < 1:
-        raise ValueError("%s: tol %r, max_iter %r, iters_per_check %r" % (who, tol, max_iter, ipc))
-    dev = W.device
-    d_tc = torch.from_numpy(tc).to(dev)
-    meta = torch.zeros((2, T), device=dev, dtype=torch.int32)           # n_iter | status
-    dist = torch.empty((n, K), device=dev, dtype=torch.float64)
-    ws, wsb = _ws_bytes(lib.kgcn_lp_workspace_bytes(n, T, K), "kgcn_lp_workspace_bytes", dev)
-    word = _ws_word(ws)
-    c_alpha, c_tol = ctypes.c_double(alpha), ctypes.c_double(tol)
-    done = reads = 0
-    while True:
-        steps = min(ipc, max_iter - done)
-        check(lib.kgcn_lp_propagate_f64(ptr(W), ptr(scale), n, ptr(labels), ptr(d_tc), T, K, variant, ctypes.byref(c_alpha),
-                                        ctypes.byref(c_tol), max_iter, done, steps, ptr(meta[0]), ptr(meta[1]), ptr(ws), wsb,
-                                        current_stream()), "kgcn_lp_propagate_f64")
-        done += steps
-        reads += 1
-        if int(word.item()) == 0:
-            break
-        if done >= max_iter:
-            raise _lib.KgcnHipError("%s: tasks still running after max_iter = %d steps" % (who, max_iter))
-    check(lib.kgcn_lp_finish_f64(n, ptr(d_tc), T, K, done, ptr(dist), ptr(ws), wsb, current_stream()), "kgcn_lp_finish_f64")
-    return dist, meta[0], meta[1], reads
+    _operand(who, "scale", scale, torch.float64, (n,))
+    return _lp_run(who, lib.kgcn_lp_propagate_f64, (ptr(W), ptr(scale)), n, labels, task_col, variant, alpha, tol, max_iter,
+                   iters_per_check, W.device)
+
+
+# ---- the same without a stored W: every tile of it is rebuilt from the points where it is consumed, bit for bit ----------------
+def _lp_points(who, name, X, gamma, rows=(1, LP_MAX_ROWS)):
+    """-> (rows, d, gamma) of a point set; refused before any launch: a shape out of range, a gamma that is not positive and finite,
+    values that are not finite."""
+    n, d = _operand(who, name, X, torch.float64, (rows, (1, None))).shape
+    gamma = float(gamma)
+    if not 0.0 < gamma < float("inf"):
+        raise _lib.KgcnHipError("%s: gamma must be positive and finite, got %r" % (who, gamma))
+    if not bool(torch.isfinite(X).all()):
+        raise _lib.KgcnHipError("%s: %s holds values that are not finite; refused before any launch" % (who, name))
+    return n, d, gamma
+
+
+@torch.no_grad()
+def rbf_apply(Xq, Xr, gamma, G, same_set=False, zero_diagonal=False):
+    """out [m, K] = sum_j w(q_i, r_j) G_jc with w the entries rbf_affinity would store, for queries Xq [m, d], references Xr [n, d]
+    (n <= LP_MAX_ROWS; m is not bounded) and G [n, K], K <= LP_MAX_COLS, without forming the [m, n] kernel: per (i, c) lane l adds
+    the rounded products of j = l (mod 64) in ascending order, then the lane tree (lp_propagate's product).  same_set: Xq is Xr
+    (the same tensor), the diagonal distance is 0 and zero_diagonal counts w_ii as +0.0."""
+    who = "rbf_apply"
+    n, d, gamma = _lp_points(who, "Xr", Xr, gamma)
+    K = _operand(who, "G", G, torch.float64, (n, (1, LP_MAX_COLS))).shape[1]
+    if same_set:
+        if Xq is not Xr and (Xq.data_ptr() != Xr.data_ptr() or Xq.shape != Xr.shape):
+            raise ValueError("%s: same_set takes one tensor as Xq and Xr" % who)
+        Xq, m = Xr, n
+    else:
+        if zero_diagonal:
+            raise ValueError("%s: zero_diagonal takes same_set" % who)
+        m = _lp_points(who, "Xq", Xq, gamma, (1, None))[0]
+        _operand(who, "Xq", Xq, torch.float64, (m, d))
+    out = torch.empty((m, K), device=Xr.device, dtype=torch.float64)
+    norms = torch.empty((n + (0 if same_set else m),), device=Xr.device, dtype=torch.float64)
+    check(lib.kgcn_rbf_apply_f64(ptr(Xq), m, ptr(Xr), n, d, ctypes.byref(ctypes.c_double(gamma)), ptr(G), K, 1 if same_set else 0,
+                                 1 if zero_diagonal else 0, ptr(out), _ptr_if(norms[n:], 0 if same_set else m), ptr(norms[:n]),
+                                 current_stream()), "kgcn_rbf_apply_f64")
+    return out
+
+
+@torch.no_grad()
+def rbf_degrees(X, gamma):
+    """lp_degrees(rbf_affinity(X, gamma)) without the matrix: -> (s, d) [n] float64, the same bits."""
+    n, d, gamma = _lp_points("rbf_degrees", "X", X, gamma)
+    out = torch.empty((3, n), device=X.device, dtype=torch.float64)      # s | d | the squared norms
+    check(lib.kgcn_rbf_degrees_f64(ptr(X), n, d, ctypes.byref(ctypes.c_double(gamma)), ptr(out[0]), ptr(out[1]), ptr(out[2]),
+                                   current_stream()), "kgcn_rbf_degrees_f64")
+    return out[0], out[1]
+
+
+@torch.no_grad()
+def lp_propagate_free(X, gamma, scale, labels, task_col, variant, alpha=0.2, tol=1e-3, max_iter=1000, iters_per_check=None):
+    """lp_propagate over the affinity matrix of X [n, d] without storing it (scale = s or d of rbf_degrees): the same return values,
+    the same bits, O(n (d + K)) memory; every step rebuilds the tiles of W on the matrix pipe."""
+    who = "lp_propagate_free"
+    n, d, gamma = _lp_points(who, "X", X, gamma)
+    _operand(who, "scale", scale, torch.float64, (n,))
+    norms = torch.empty((n,), device=X.device, dtype=torch.float64)
+    c_gamma = ctypes.c_double(gamma)
+    return _lp_run(who, lib.kgcn_lp_propagate_free_f64, (ptr(X), d, ctypes.byref(c_gamma), ptr(norms), ptr(scale)), n, labels,
+                   task_col, variant, alpha, tol, max_iter, iters_per_check, X.device)
 
 
 @torch.no_grad()
