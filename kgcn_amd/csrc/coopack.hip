@@ -21,13 +21,11 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "block_reduce.h"
-#include "kgcn_common.h"
+#include "workspace.h"
 
 namespace kgcn {
 
 constexpr int kPackBlock = 256;
-
-static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 static unsigned key_bits(int64_t max_key) {
   unsigned b = 1;
@@ -203,8 +201,7 @@ using namespace kgcn;
 extern "C" int64_t kgcn_coo_pack_workspace_bytes(int64_t nnz, int32_t num_graphs, int32_t rows, int32_t cols) {
   if (nnz <= 0) return 256;
   const int64_t mx = (int64_t)(num_graphs > 0 ? num_graphs : 1) * (rows > 0 ? rows : 1) * (cols > 0 ? cols : 1);
-  return (int64_t)(2 * align256((size_t)nnz * 8) + 2 * align256((size_t)nnz * 4) + align256(sort_temp_bytes(nnz, key_bits(mx))) +
-                   256);
+  return (int64_t)(2 * al256((size_t)nnz * 8) + 2 * al256((size_t)nnz * 4) + al256(sort_temp_bytes(nnz, key_bits(mx))) + 256);
 }
 
 extern "C" int kgcn_coo_pack_f32(const int32_t* graph, const int32_t* row, const int32_t* col, const float* val,
@@ -225,15 +222,14 @@ extern "C" int kgcn_coo_pack_f32(const int32_t* graph, const int32_t* row, const
     return 0;
   }
   if (!graph || !row || !col || !cv_out) return fail("kgcn_coo_pack_f32: NULL operand");
-  const int64_t need = kgcn_coo_pack_workspace_bytes(nnz, num_graphs, rows, cols);
-  if (!workspace || workspace_bytes < need)
-    return fail("kgcn_coo_pack_f32: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
-  unsigned char* w = static_cast<unsigned char*>(workspace);
-  w = reinterpret_cast<unsigned char*>(align256(reinterpret_cast<size_t>(w)));
-  unsigned long long* keys_in = reinterpret_cast<unsigned long long*>(w); w += align256((size_t)nnz * 8);
-  unsigned long long* keys_out = reinterpret_cast<unsigned long long*>(w); w += align256((size_t)nnz * 8);
-  int* idx_in = reinterpret_cast<int*>(w); w += align256((size_t)nnz * 4);
-  int* idx_out = reinterpret_cast<int*>(w); w += align256((size_t)nnz * 4);
+  if (int rc = check_workspace("kgcn_coo_pack_f32", workspace, workspace_bytes, kgcn_coo_pack_workspace_bytes(nnz, num_graphs, rows, cols)))
+    return rc;
+  Taker t{aligned_base(workspace)};
+  unsigned long long* keys_in = t.take<unsigned long long>((size_t)nnz);
+  unsigned long long* keys_out = t.take<unsigned long long>((size_t)nnz);
+  int* idx_in = t.take<int>((size_t)nnz);
+  int* idx_out = t.take<int>((size_t)nnz);
+  unsigned char* w = t.base + t.off;                           // the sort's scratch
   const int64_t max_key = transposed ? (int64_t)num_graphs * cols * rows : (int64_t)num_graphs * rows;
   const unsigned bits = key_bits(max_key);
   size_t temp = sort_temp_bytes(nnz, bits);
@@ -254,7 +250,7 @@ extern "C" int kgcn_coo_pack_f32(const int32_t* graph, const int32_t* row, const
 
 extern "C" int64_t kgcn_csr_pad4_workspace_bytes(int32_t num_graphs, int32_t rows) {
   const int64_t n = (int64_t)(num_graphs > 0 ? num_graphs : 0) * (rows > 0 ? rows : 0) + 1;
-  return (int64_t)(align256((size_t)n * 4) + align256(scan_temp_bytes(n)) + 256);
+  return (int64_t)(al256((size_t)n * 4) + al256(scan_temp_bytes(n)) + 256);
 }
 
 extern "C" int kgcn_csr_pad4(const kgcn_csr_batch* a, int32_t* rowptr4_out, void* cv4_out, int64_t cv4_capacity,
@@ -275,11 +271,10 @@ extern "C" int kgcn_csr_pad4(const kgcn_csr_batch* a, int32_t* rowptr4_out, void
     (void)hipMemsetAsync(graph_ptr_out, 0, (size_t)(T + 1) * 4, s);
     return 0;
   }
-  const int64_t need = kgcn_csr_pad4_workspace_bytes(T, M);
-  if (!workspace || workspace_bytes < need)
-    return fail("kgcn_csr_pad4: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
-  unsigned char* w = reinterpret_cast<unsigned char*>(align256(reinterpret_cast<size_t>(workspace)));
-  int* padded = reinterpret_cast<int*>(w); w += align256((size_t)(nrows + 1) * 4);
+  if (int rc = check_workspace("kgcn_csr_pad4", workspace, workspace_bytes, kgcn_csr_pad4_workspace_bytes(T, M))) return rc;
+  Taker t{aligned_base(workspace)};
+  int* padded = t.take<int>((size_t)nrows + 1);
+  unsigned char* w = t.base + t.off;                           // the scan's scratch
   size_t temp = scan_temp_bytes(nrows + 1);
   const unsigned nb = (unsigned)((nrows + 1 + kPackBlock - 1) / kPackBlock);
   hipLaunchKernelGGL(pad_count_kernel, dim3(nb), dim3(kPackBlock), 0, s, a->rowptr, nrows, padded);

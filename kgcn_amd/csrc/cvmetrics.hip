@@ -19,7 +19,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "block_reduce.h"
-#include "kgcn_common.h"
+#include "workspace.h"
 
 namespace kgcn {
 namespace {
@@ -29,8 +29,6 @@ constexpr int kItems = 4;                     // consecutive elements per thread
 constexpr int kChunk = kBlock * kItems;
 constexpr int kWaves = kBlock / kWave;
 typedef unsigned long long u64;
-
-__host__ __device__ __forceinline__ size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // all on the bits: the order of finite floats, denormals included, whatever the denormal mode of the float compares
 __device__ __forceinline__ uint32_t ordered(float v) {
@@ -235,13 +233,12 @@ struct Layout {
 };
 Layout layout(unsigned char* base, int64_t m, int32_t tasks) {
   Layout o{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) { void* p = base ? base + off : nullptr; off += al256(bytes); return p; };
-  o.keys = (u64*)take((size_t)m * 8);
-  o.sorted = (u64*)take((size_t)m * 8);
+  Taker t{base};
+  o.keys = t.take<u64>((size_t)m);
+  o.sorted = t.take<u64>((size_t)m);
   o.temp_bytes = sort_temp_bytes((size_t)m, end_bit_of(tasks));
-  o.temp = take(o.temp_bytes);
-  o.total = off + 256;
+  o.temp = t.take<unsigned char>(o.temp_bytes);
+  o.total = t.off + 256;
   return o;
 }
 
@@ -272,10 +269,9 @@ extern "C" int kgcn_binary_metrics_f32(const float* score, int64_t score_ld, con
   if (threshold != threshold) return fail("%s: the threshold is NaN", who);
   if (!score || !label || !counts || !ap) return fail("%s: NULL operand", who);
   const int64_t m = n * tasks;
-  const int64_t need = (int64_t)layout(nullptr, m, tasks).total;
-  if (!workspace || workspace_bytes < need) return fail("%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes, (long long)need);
+  if (int rc = check_workspace(who, workspace, workspace_bytes, (int64_t)layout(nullptr, m, tasks).total)) return rc;
   hipStream_t s = as_stream(stream);
-  Layout o = layout(reinterpret_cast<unsigned char*>(al256(reinterpret_cast<size_t>(workspace))), m, tasks);
+  const Layout o = layout(aligned_base(workspace), m, tasks);
   long blocks = (long)((m + kBlock - 1) / kBlock);
   if (blocks > 8L * kNumCU) blocks = 8L * kNumCU;
   hipLaunchKernelGGL(metrics_key_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, s, score, (long)score_ld, label, mask, (long)n,

@@ -35,20 +35,16 @@
 //   copies   refine, rank, wl runs and sp also serve `copies` colourings of the same graphs in one launch sequence (graphkern.h;
 //            the hash graph kernels of hashkern.hip): colours [copies, T*M] over the one stored batch.  Copies whose initial
 //            colours are disjoint stay apart in the one global ranking.  copies == 1 is the plain kernel, bit for bit.
+#include "gram_tile.h"
 #include "graphkern.h"
 
 namespace kgcn {
 namespace {
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
 constexpr int kGroup = 8;            // lanes that share a row in the refinement
 constexpr int kSpMaxNodes = 128;     // distances and queue entries are bytes, n^2 keys fit the LDS
 constexpr int kSpMaxLabels = 4096;   // 12 bits a label in the 32-bit key
 constexpr int kWlRunsMaxNodes = 4096;
-constexpr int kTile = 64;            // Gram tile edge of a workgroup
-constexpr int kKc = 16;              // columns staged per step; chunk_cols is a multiple of it
-constexpr int kLd = kKc + 1;
 
 __device__ __forceinline__ u64 mix64(u64 x) {
   x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
@@ -105,6 +101,8 @@ __global__ __launch_bounds__(256) void wl_refine_kernel(const int32_t* __restric
   }
 }
 
+// Two rows that do not exist are one signature whatever the batch stores in them (entries, a colour): they share the all-ones
+// key and get no colour.
 struct RankArgs {
   const int32_t* rowptr;
   const int32_t* num_nodes;
@@ -113,57 +111,37 @@ struct RankArgs {
   const u64* key_hi;
   const u64* key_lo;
   const uint32_t* order;             // rows in (key_hi, key_lo) order
-  int* flags;
-  const int* pos;
-  int32_t* out;
   u64* info;                         // colours, mismatches
-  long n;                            // copies * stored
   long nnz;
   uint32_t stored;                   // T * M
   int M;
-};
 
-__device__ __forceinline__ bool row_exists(const RankArgs& a, uint32_t row) {
-  const uint32_t p = row % a.stored, t = p / (uint32_t)a.M;
-  return (int)(p - t * (uint32_t)a.M) < a.num_nodes[t];
-}
-
-// true signatures of two rows: existence, own colour, degree, sorted neighbour colours.  Two rows that do not exist are one
-// signature whatever the batch stores in them (entries, a colour): they share the all-ones key and get no colour.
-__device__ bool same_signature(const RankArgs& a, uint32_t x, uint32_t y) {
-  const bool ex = row_exists(a, x);
-  if (ex != row_exists(a, y)) return false;
-  if (!ex) return true;
-  if (a.colors[x] != a.colors[y]) return false;
-  const uint32_t cx = x / a.stored, px = x - cx * a.stored, cy = y / a.stored, py = y - cy * a.stored;
-  const int bx = a.rowptr[px], by = a.rowptr[py], d = a.rowptr[px + 1] - bx;
-  if (a.rowptr[py + 1] - by != d) return false;
-  const int32_t *sx = a.sorted + cx * a.nnz + bx, *sy = a.sorted + cy * a.nnz + by;
-  for (int e = 0; e < d; ++e)
-    if (sx[e] != sy[e]) return false;
-  return true;
-}
-
-__global__ __launch_bounds__(256) void wl_flag_kernel(RankArgs a) {
-  const long p = (long)blockIdx.x * 256 + threadIdx.x;
-  if (p >= a.n) return;
-  const uint32_t row = a.order[p];
-  bool eq_prev = false;
-  if (p > 0) {
-    const uint32_t prev = a.order[p - 1];
-    eq_prev = a.key_hi[row] == a.key_hi[prev] && a.key_lo[row] == a.key_lo[prev];
-    if (eq_prev && !same_signature(a, row, prev)) atomicAdd(&a.info[1], 1ull);
+  __device__ __forceinline__ bool exists(uint32_t row) const {
+    const uint32_t p = row % stored, t = p / (uint32_t)M;
+    return (int)(p - t * (uint32_t)M) < num_nodes[t];
   }
-  a.flags[p] = (row_exists(a, row) && !eq_prev) ? 1 : 0;
-}
-
-__global__ __launch_bounds__(256) void wl_colour_kernel(RankArgs a) {
-  const long p = (long)blockIdx.x * 256 + threadIdx.x;
-  if (p >= a.n) return;
-  const uint32_t row = a.order[p];
-  a.out[row] = row_exists(a, row) ? a.pos[p] - 1 : -1;
-  if (p == a.n - 1) a.info[0] = (u64)a.pos[p];
-}
+  // true signatures of two rows: existence, own colour, degree, sorted neighbour colours
+  __device__ bool same_signature(uint32_t x, uint32_t y) const {
+    const bool ex = exists(x);
+    if (ex != exists(y)) return false;
+    if (!ex) return true;
+    if (colors[x] != colors[y]) return false;
+    const uint32_t cx = x / stored, px = x - cx * stored, cy = y / stored, py = y - cy * stored;
+    const int bx = rowptr[px], by = rowptr[py], d = rowptr[px + 1] - bx;
+    if (rowptr[py + 1] - by != d) return false;
+    const int32_t *sx = sorted + cx * nnz + bx, *sy = sorted + cy * nnz + by;
+    for (int e = 0; e < d; ++e)
+      if (sx[e] != sy[e]) return false;
+    return true;
+  }
+  // equal keys; a pair of equal keys over different signatures is counted for the caller to refuse
+  __device__ __forceinline__ bool same_as_prev(long p) const {
+    const uint32_t row = order[p], prev = order[p - 1];
+    const bool eq = key_hi[row] == key_hi[prev] && key_lo[row] == key_lo[prev];
+    if (eq && !same_signature(row, prev)) atomicAdd(&info[1], 1ull);
+    return eq;
+  }
+};
 
 // ---- runs of a sorted key list in LDS -----------------------------------------------------------------------------------------
 struct RunOut {
@@ -350,23 +328,13 @@ __global__ __launch_bounds__(256) void gram_scatter_kernel(const int* __restrict
   if ((unsigned)g < (unsigned)G) counts[(long)g * cc + d] = run_count[r];
 }
 
-// block index b -> (ti, tj), ti <= tj, b = tj (tj + 1) / 2 + ti
-__device__ __forceinline__ void tile_of(unsigned b, int& ti, int& tj) {
-  int t = (int)((sqrtf(8.0f * (float)b + 1.0f) - 1.0f) * 0.5f);
-  while ((unsigned)t * (unsigned)(t + 1) / 2u > b) --t;
-  while ((unsigned)(t + 1) * (unsigned)(t + 2) / 2u <= b) ++t;
-  tj = t;
-  ti = (int)(b - (unsigned)t * (unsigned)(t + 1) / 2u);
-}
-
-// K tile (ti, tj) += counts[ti rows] . counts[tj rows]^T over the chunk.  Four waves, each a 32 x 32 block = 2 x 2 MFMA
-// blocks.  v_mfma_f64_16x16x4_f64: lane l holds A[row l & 15][k l >> 4] and B[k l >> 4][col l & 15], and result r of the lane
-// is C[row (l >> 4) + 4 r][col l & 15].
+// K tile (ti, tj) += counts[ti rows] . counts[tj rows]^T over the chunk (gram_tile.h; chunk_cols is a multiple of kKc).  The
+// panels stay int32: a count becomes a double where the fragment is read.
 __global__ __launch_bounds__(256) void gram_tile_kernel(const int32_t* __restrict__ counts, int cc, int G, double* __restrict__ K) {
   __shared__ int32_t as[kTile * kLd], bs[kTile * kLd];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, li = lane & 15, hi = lane >> 4, wr = wv >> 1, wc = wv & 1;
   int ti, tj;
-  tile_of(blockIdx.x, ti, tj);
+  tile_of((long)blockIdx.x, ti, tj);
   f64x4 acc[2][2];
 #pragma unroll
   for (int x = 0; x < 2; ++x)
@@ -377,28 +345,9 @@ __global__ __launch_bounds__(256) void gram_tile_kernel(const int32_t* __restric
         const int i = ti * kTile + wr * 32 + x * 16 + hi + 4 * r, j = tj * kTile + wc * 32 + y * 16 + li;
         acc[x][y][r] = (i < G && j < G) ? K[(long)i * G + j] : 0.0;
       }
-  const int kk = tid & (kKc - 1);
-  for (int k0 = 0; k0 < cc; k0 += kKc) {
-    for (int r = tid >> 4; r < kTile; r += 16) {               // G_pad rows: no row is past the matrix
-      as[r * kLd + kk] = counts[((long)ti * kTile + r) * cc + k0 + kk];
-      bs[r * kLd + kk] = counts[((long)tj * kTile + r) * cc + k0 + kk];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int s = 0; s < kKc; s += 4) {
-      double a[2], b[2];
-#pragma unroll
-      for (int x = 0; x < 2; ++x) {
-        a[x] = (double)as[(wr * 32 + x * 16 + li) * kLd + s + hi];
-        b[x] = (double)bs[(wc * 32 + x * 16 + li) * kLd + s + hi];
-      }
-#pragma unroll
-      for (int x = 0; x < 2; ++x)
-#pragma unroll
-        for (int y = 0; y < 2; ++y) acc[x][y] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[x], b[y], acc[x][y], 0, 0, 0);
-    }
-    __syncthreads();
-  }
+  gram_tile_64(                                                // G_pad rows: no row is past the matrix
+      as, bs, cc, [&](int r, int k0, int kk) { return counts[((long)ti * kTile + r) * cc + k0 + kk]; },
+      [&](int r, int k0, int kk) { return counts[((long)tj * kTile + r) * cc + k0 + kk]; }, acc);
 #pragma unroll
   for (int x = 0; x < 2; ++x)
 #pragma unroll
@@ -493,7 +442,7 @@ int check_gram(const char* who, int64_t runs, int32_t graphs, int32_t chunk_cols
 
 // count mode: counts -> run_ptr (0, inclusive scan)
 int scan_counts(const char* who, const RunsLayout& o, int32_t graphs, int64_t* run_ptr, hipStream_t s) {
-  if (hipMemsetAsync(run_ptr, 0, sizeof(int64_t), s) != hipSuccess) return fail("%s: hipMemsetAsync failed", who);
+  if (int rc = zero_async(who, run_ptr, sizeof(int64_t), s)) return rc;
   size_t temp = o.temp_bytes;
   if (rocprim::inclusive_scan(o.temp, temp, o.counts, reinterpret_cast<long long*>(run_ptr) + 1, (size_t)graphs,
                               rocprim::plus<long long>(), s) != hipSuccess)
@@ -506,10 +455,7 @@ int check_runs_args(const char* who, int64_t* run_ptr, uint64_t* run_col, int32_
   if (!run_ptr) return fail("%s: run_ptr is NULL", who);
   if (run_col && (!run_graph || !run_count)) return fail("%s: run_col without run_graph / run_count", who);
   if (run_col && capacity < 0) return fail("%s: negative capacity", who);
-  const int64_t need = (int64_t)runs_layout(nullptr, (size_t)graphs).total;
-  if (!run_col && (!workspace || workspace_bytes < need))
-    return fail("%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes, (long long)need);
-  return 0;
+  return run_col ? 0 : check_workspace(who, workspace, workspace_bytes, (int64_t)runs_layout(nullptr, (size_t)graphs).total);
 }
 
 }  // namespace
@@ -544,30 +490,16 @@ int wl_rank_run(const char* who, const kgcn_csr_batch* a, const int32_t* num_nod
   if (int rc = check_copies(who, a, copies)) return rc;
   if (!key_hi || !key_lo || !new_colors || !info || (a->nnz > 0 && !sorted_nbr)) return fail("%s: NULL operand", who);
   const long stored = (long)a->num_graphs * a->rows, n = copies * stored;
-  const int64_t need = (int64_t)rank_layout(nullptr, (size_t)n).total;
-  if (!workspace || workspace_bytes < need) return fail("%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes, (long long)need);
+  if (int rc = check_workspace(who, workspace, workspace_bytes, (int64_t)rank_layout(nullptr, (size_t)n).total)) return rc;
   hipStream_t s = as_stream(stream);
-  if (hipMemsetAsync(info, 0, 2 * sizeof(int64_t), s) != hipSuccess) return fail("%s: hipMemsetAsync failed", who);
+  if (int rc = zero_async(who, info, 2 * sizeof(int64_t), s)) return rc;
   if (n == 0) return 0;
-  RankLayout o = rank_layout(aligned_base(workspace), (size_t)n);
+  const RankLayout o = rank_layout(aligned_base(workspace), (size_t)n);
   const u64 *hi = reinterpret_cast<const u64*>(key_hi), *lo = reinterpret_cast<const u64*>(key_lo);
-  const unsigned nb = blocks_of(n);
-  hipLaunchKernelGGL(iota_kernel, dim3(nb), dim3(256), 0, s, o.idx0, n);
-  size_t temp = o.temp_bytes;
-  if (rocprim::radix_sort_pairs(o.temp, temp, lo, o.lo_s, o.idx0, o.idx1, (size_t)n, 0u, 64u, s) != hipSuccess)
-    return fail("%s: rocprim::radix_sort_pairs failed", who);
-  hipLaunchKernelGGL(gather_u64_kernel, dim3(nb), dim3(256), 0, s, hi, o.idx1, o.hi_g, n);
-  temp = o.temp_bytes;
-  if (rocprim::radix_sort_pairs(o.temp, temp, o.hi_g, o.hi_s, o.idx1, o.idx2, (size_t)n, 0u, 64u, s) != hipSuccess)
-    return fail("%s: rocprim::radix_sort_pairs failed", who);
-  RankArgs r{a->rowptr, num_nodes, colors, sorted_nbr, hi, lo, o.idx2, o.flags, o.pos, new_colors, reinterpret_cast<u64*>(info), n,
-             (long)a->nnz, (uint32_t)stored, a->rows};
-  hipLaunchKernelGGL(wl_flag_kernel, dim3(nb), dim3(256), 0, s, r);
-  temp = o.temp_bytes;
-  if (rocprim::inclusive_scan(o.temp, temp, o.flags, o.pos, (size_t)n, rocprim::plus<int>(), s) != hipSuccess)
-    return fail("%s: rocprim::inclusive_scan failed", who);
-  hipLaunchKernelGGL(wl_colour_kernel, dim3(nb), dim3(256), 0, s, r);
-  return check_launch(who);
+  if (int rc = rank_order(who, o, hi, lo, n, s)) return rc;
+  const RankArgs r{a->rowptr, num_nodes, colors, sorted_nbr, hi, lo, o.idx2, reinterpret_cast<u64*>(info), (long)a->nnz, (uint32_t)stored,
+                   a->rows};
+  return rank_sorted(who, r, o, new_colors, r.info, n, s);
 }
 
 int wl_runs_run(const char* who, const int32_t* colors, const int32_t* num_nodes, int32_t graphs, int32_t rows, int copies,
@@ -581,7 +513,7 @@ int wl_runs_run(const char* who, const int32_t* colors, const int32_t* num_nodes
   const int slots = copies * graphs;
   if (int rc = check_runs_args(who, run_ptr, run_col, run_graph, run_count, capacity, workspace, workspace_bytes, slots)) return rc;
   hipStream_t s = as_stream(stream);
-  if (slots == 0) return hipMemsetAsync(run_ptr, 0, sizeof(int64_t), s) == hipSuccess ? 0 : fail("%s: hipMemsetAsync failed", who);
+  if (slots == 0) return zero_async(who, run_ptr, sizeof(int64_t), s);
   RunsLayout o = runs_layout(run_col ? nullptr : aligned_base(workspace), (size_t)slots);
   RunOut ro{o.counts, reinterpret_cast<const long long*>(run_ptr), reinterpret_cast<u64*>(run_col), run_graph, run_count,
             (long long)capacity, (u64)column_offset, (u64)column_stride};
@@ -605,7 +537,7 @@ int sp_features_run(const char* who, const kgcn_csr_batch* a, const int32_t* num
   const int graphs = a->num_graphs, M = a->rows, slots = copies * graphs;
   if (int rc = check_runs_args(who, run_ptr, run_col, run_graph, run_count, capacity, workspace, workspace_bytes, slots)) return rc;
   hipStream_t s = as_stream(stream);
-  if (graphs == 0) return hipMemsetAsync(run_ptr, 0, sizeof(int64_t), s) == hipSuccess ? 0 : fail("%s: hipMemsetAsync failed", who);
+  if (graphs == 0) return zero_async(who, run_ptr, sizeof(int64_t), s);
   int key_words = 1;
   while (key_words < M * M) key_words <<= 1;
   const size_t lds = (size_t)key_words * 4 + 256 * sizeof(int) + (((size_t)M * M + 3) & ~(size_t)3);
@@ -629,10 +561,7 @@ extern "C" int kgcn_wl_refine_i32(const kgcn_csr_batch* a, const int32_t* num_no
 }
 
 extern "C" int64_t kgcn_wl_rank_workspace_bytes(int64_t rows) {
-  if (rows < 0 || rows >= (int64_t)INT32_MAX) {
-    fail("kgcn_wl_rank_workspace_bytes: %lld rows outside 0..2^31-2", (long long)rows);
-    return -1;
-  }
+  if (rows < 0 || rows >= (int64_t)INT32_MAX) return refuse_query("kgcn_wl_rank_workspace_bytes: %lld rows outside 0..2^31-2", (long long)rows);
   return (int64_t)rank_layout(nullptr, (size_t)rows).total;
 }
 
@@ -644,10 +573,7 @@ extern "C" int kgcn_wl_rank_i32(const kgcn_csr_batch* a, const int32_t* num_node
 }
 
 extern "C" int64_t kgcn_graph_runs_workspace_bytes(int32_t graphs) {
-  if (graphs < 0) {
-    fail("kgcn_graph_runs_workspace_bytes: %d graphs", graphs);
-    return -1;
-  }
+  if (graphs < 0) return refuse_query("kgcn_graph_runs_workspace_bytes: %d graphs", graphs);
   return (int64_t)runs_layout(nullptr, (size_t)graphs).total;
 }
 
@@ -676,12 +602,11 @@ extern "C" int kgcn_gram_plan_i64(const uint64_t* run_col, const int32_t* run_gr
   const char* who = "kgcn_gram_plan_i64";
   if (int rc = check_gram(who, runs, graphs, chunk_cols)) return rc;
   if (!stats || (runs > 0 && (!run_col || !run_graph || !run_count))) return fail("%s: NULL operand", who);
-  const int64_t need = (int64_t)gram_layout(nullptr, (size_t)runs, graphs, chunk_cols).total;
-  if (!workspace || workspace_bytes < need) return fail("%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes, (long long)need);
+  if (int rc = check_workspace(who, workspace, workspace_bytes, (int64_t)gram_layout(nullptr, (size_t)runs, graphs, chunk_cols).total)) return rc;
   hipStream_t s = as_stream(stream);
   GramLayout o = gram_layout(aligned_base(workspace), (size_t)runs, graphs, chunk_cols);
-  if (hipMemsetAsync(stats, 0, 3 * sizeof(int64_t), s) != hipSuccess || hipMemsetAsync(o.diag, 0, (size_t)graphs * sizeof(u64), s) != hipSuccess)
-    return fail("%s: hipMemsetAsync failed", who);
+  if (int rc = zero_async(who, stats, 3 * sizeof(int64_t), s)) return rc;
+  if (int rc = zero_async(who, o.diag, (size_t)graphs * sizeof(u64), s)) return rc;
   if (runs == 0) return 0;
   const long n = (long)runs;
   const unsigned nb = blocks_of(n);
@@ -705,15 +630,13 @@ extern "C" int kgcn_gram_dense_f64(const int32_t* run_graph, const int32_t* run_
   if (int rc = check_gram(who, runs, graphs, chunk_cols)) return rc;
   if (!gram || (runs > 0 && (!run_graph || !run_count))) return fail("%s: NULL operand", who);
   if (dense_cols < 0 || dense_cols > runs / 2) return fail("%s: %lld dense columns for %lld runs", who, (long long)dense_cols, (long long)runs);
-  const int64_t need = (int64_t)gram_layout(nullptr, (size_t)runs, graphs, chunk_cols).total;
-  if (!workspace || workspace_bytes < need) return fail("%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes, (long long)need);
+  if (int rc = check_workspace(who, workspace, workspace_bytes, (int64_t)gram_layout(nullptr, (size_t)runs, graphs, chunk_cols).total)) return rc;
   hipStream_t s = as_stream(stream);
   GramLayout o = gram_layout(aligned_base(workspace), (size_t)runs, graphs, chunk_cols);
-  if (hipMemsetAsync(gram, 0, (size_t)graphs * graphs * sizeof(double), s) != hipSuccess) return fail("%s: hipMemsetAsync failed", who);
+  if (int rc = zero_async(who, gram, (size_t)graphs * graphs * sizeof(double), s)) return rc;
   const unsigned nt = (unsigned)(o.g_pad / kTile);
   for (int64_t c0 = 0; c0 < dense_cols; c0 += chunk_cols) {
-    if (hipMemsetAsync(o.counts, 0, (size_t)o.g_pad * chunk_cols * sizeof(int32_t), s) != hipSuccess)
-      return fail("%s: hipMemsetAsync failed", who);
+    if (int rc = zero_async(who, o.counts, (size_t)o.g_pad * chunk_cols * sizeof(int32_t), s)) return rc;
     hipLaunchKernelGGL(gram_scatter_kernel, dim3(blocks_of((long)runs)), dim3(256), 0, s, o.dcol, o.idx_s, run_graph, run_count,
                        (long)runs, (long)c0, chunk_cols, graphs, o.counts);
     hipLaunchKernelGGL(gram_tile_kernel, dim3(nt * (nt + 1) / 2), dim3(256), 0, s, o.counts, chunk_cols, graphs, gram);

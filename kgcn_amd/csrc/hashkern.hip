@@ -117,29 +117,12 @@ struct PairArgs {
   const u64* klo;                    // low words by row
   const uint32_t* order;             // rows in (hi, lo) order
   const int32_t* mark;
-  int* flags;
-  const int* pos;
-  int32_t* out;
-  u64* info;                         // classes, refused rows
-  long n;
+
+  __device__ __forceinline__ bool exists(uint32_t row) const { return !mark || mark[row] >= 0; }
+  __device__ __forceinline__ bool same_as_prev(long p) const {
+    return hi_s[p] == hi_s[p - 1] && klo[order[p]] == klo[order[p - 1]];
+  }
 };
-
-__global__ __launch_bounds__(256) void pair_flag_kernel(PairArgs a) {
-  const long p = (long)blockIdx.x * 256 + threadIdx.x;
-  if (p >= a.n) return;
-  const uint32_t row = a.order[p];
-  const bool exists = !a.mark || a.mark[row] >= 0;
-  const bool eq_prev = p > 0 && a.hi_s[p] == a.hi_s[p - 1] && a.klo[row] == a.klo[a.order[p - 1]];
-  a.flags[p] = (exists && !eq_prev) ? 1 : 0;
-}
-
-__global__ __launch_bounds__(256) void pair_rank_kernel(PairArgs a) {
-  const long p = (long)blockIdx.x * 256 + threadIdx.x;
-  if (p >= a.n) return;
-  const uint32_t row = a.order[p];
-  a.out[row] = (!a.mark || a.mark[row] >= 0) ? a.pos[p] - 1 : -1;
-  if (p == a.n - 1) a.info[0] = (u64)a.pos[p];
-}
 
 struct PairLayout {
   u64 *khi, *klo;
@@ -148,13 +131,16 @@ struct PairLayout {
 };
 PairLayout pair_layout(unsigned char* base, size_t n) {
   PairLayout o{};
-  const size_t words = al256(n * sizeof(u64));
-  o.khi = base ? reinterpret_cast<u64*>(base) : nullptr;
-  o.klo = base ? reinterpret_cast<u64*>(base + words) : nullptr;
-  o.rank = rank_layout(base ? base + 2 * words : nullptr, n);
-  o.total = 2 * words + o.rank.total;
+  Taker t{base};
+  o.khi = t.take<u64>(n);
+  o.klo = t.take<u64>(n);
+  o.rank = rank_layout(t, n);
+  o.total = t.off + 256;
   return o;
 }
+
+// one array: the chunk sums
+size_t attr_scale_bytes(long chunks, int32_t d) { return al256((size_t)chunks * d * sizeof(double)) + 256; }
 
 int check_attr(const char* who, int64_t rows, int32_t d) {
   if (rows < 1 || rows >= (int64_t)INT32_MAX) return fail("%s: %lld rows outside 1..2^31-2", who, (long long)rows);
@@ -171,7 +157,7 @@ using namespace kgcn;
 
 extern "C" int64_t kgcn_attr_scale_workspace_bytes(int64_t rows, int32_t d) {
   if (check_attr("kgcn_attr_scale_workspace_bytes", rows, d)) return -1;
-  return (int64_t)al256((size_t)chunks_of(rows) * d * sizeof(double)) + 256;
+  return (int64_t)attr_scale_bytes(chunks_of(rows), d);
 }
 
 extern "C" int kgcn_attr_scale_f64(const double* x, int64_t rows, int32_t d, double* scaled, double* mean, double* std_dev,
@@ -180,8 +166,7 @@ extern "C" int kgcn_attr_scale_f64(const double* x, int64_t rows, int32_t d, dou
   if (int rc = check_attr(who, rows, d)) return rc;
   if (!x || !scaled || !mean || !std_dev) return fail("%s: NULL operand", who);
   const long chunks = chunks_of(rows);
-  const int64_t need = (int64_t)al256((size_t)chunks * d * sizeof(double)) + 256;
-  if (!workspace || workspace_bytes < need) return fail("%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes, (long long)need);
+  if (int rc = check_workspace(who, workspace, workspace_bytes, (int64_t)attr_scale_bytes(chunks, d))) return rc;
   double* part = reinterpret_cast<double*>(aligned_base(workspace));
   hipStream_t s = as_stream(stream);
   const unsigned nb1 = blocks_of(chunks * d), nb2 = blocks_of(d);
@@ -203,7 +188,7 @@ extern "C" int kgcn_lsh_buckets_f64(const double* scaled, int64_t rows, int32_t 
   const double w = *bin_width;
   if (!(w > 0.0) || !isfinite(w)) return fail("%s: the bin width %g must be positive and finite", who, w);
   hipStream_t s = as_stream(stream);
-  if (hipMemsetAsync(errors, 0, sizeof(int64_t), s) != hipSuccess) return fail("%s: hipMemsetAsync failed", who);
+  if (int rc = zero_async(who, errors, sizeof(int64_t), s)) return rc;
   const int ld = d | 1, rows_pb = 8192 / ld < 64 ? 8192 / ld : 64;   // at most 64 KB of LDS; kLshMaxDim keeps it >= 1
   const unsigned nb = (unsigned)((rows + rows_pb - 1) / rows_pb);
   hipLaunchKernelGGL(lsh_buckets_kernel, dim3(nb), dim3(256), (size_t)rows_pb * ld * sizeof(double), s, scaled, v, b, w, (long)rows, d,
@@ -212,10 +197,7 @@ extern "C" int kgcn_lsh_buckets_f64(const double* scaled, int64_t rows, int32_t 
 }
 
 extern "C" int64_t kgcn_rank_pairs_workspace_bytes(int64_t n) {
-  if (n < 0 || n >= (int64_t)INT32_MAX) {
-    fail("kgcn_rank_pairs_workspace_bytes: %lld pairs outside 0..2^31-2", (long long)n);
-    return -1;
-  }
+  if (n < 0 || n >= (int64_t)INT32_MAX) return refuse_query("kgcn_rank_pairs_workspace_bytes: %lld pairs outside 0..2^31-2", (long long)n);
   return (int64_t)pair_layout(nullptr, (size_t)n).total;
 }
 
@@ -224,31 +206,16 @@ extern "C" int kgcn_rank_pairs_i64(const int64_t* hi, const int64_t* lo, const i
   const char* who = "kgcn_rank_pairs_i64";
   if (n < 0 || n >= (int64_t)INT32_MAX) return fail("%s: %lld pairs outside 0..2^31-2", who, (long long)n);
   if (!info || (n > 0 && (!hi || !lo || !ranks))) return fail("%s: NULL operand", who);
-  const int64_t need = (int64_t)pair_layout(nullptr, (size_t)n).total;
-  if (!workspace || workspace_bytes < need) return fail("%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes, (long long)need);
+  if (int rc = check_workspace(who, workspace, workspace_bytes, (int64_t)pair_layout(nullptr, (size_t)n).total)) return rc;
   hipStream_t s = as_stream(stream);
-  if (hipMemsetAsync(info, 0, 2 * sizeof(int64_t), s) != hipSuccess) return fail("%s: hipMemsetAsync failed", who);
+  if (int rc = zero_async(who, info, 2 * sizeof(int64_t), s)) return rc;
   if (n == 0) return 0;
-  PairLayout o = pair_layout(aligned_base(workspace), (size_t)n);
-  const RankLayout& k = o.rank;
-  const unsigned nb = blocks_of((long)n);
-  hipLaunchKernelGGL(pair_keys_kernel, dim3(nb), dim3(256), 0, s, reinterpret_cast<const long long*>(hi),
+  const PairLayout o = pair_layout(aligned_base(workspace), (size_t)n);
+  hipLaunchKernelGGL(pair_keys_kernel, dim3(blocks_of((long)n)), dim3(256), 0, s, reinterpret_cast<const long long*>(hi),
                      reinterpret_cast<const long long*>(lo), mark, (long)n, o.khi, o.klo, reinterpret_cast<u64*>(info));
-  hipLaunchKernelGGL(iota_kernel, dim3(nb), dim3(256), 0, s, k.idx0, (long)n);
-  size_t temp = k.temp_bytes;
-  if (rocprim::radix_sort_pairs(k.temp, temp, o.klo, k.lo_s, k.idx0, k.idx1, (size_t)n, 0u, 64u, s) != hipSuccess)
-    return fail("%s: rocprim::radix_sort_pairs failed", who);
-  hipLaunchKernelGGL(gather_u64_kernel, dim3(nb), dim3(256), 0, s, o.khi, k.idx1, k.hi_g, (long)n);
-  temp = k.temp_bytes;
-  if (rocprim::radix_sort_pairs(k.temp, temp, k.hi_g, k.hi_s, k.idx1, k.idx2, (size_t)n, 0u, 64u, s) != hipSuccess)
-    return fail("%s: rocprim::radix_sort_pairs failed", who);
-  PairArgs a{k.hi_s, o.klo, k.idx2, mark, k.flags, k.pos, ranks, reinterpret_cast<u64*>(info), (long)n};
-  hipLaunchKernelGGL(pair_flag_kernel, dim3(nb), dim3(256), 0, s, a);
-  temp = k.temp_bytes;
-  if (rocprim::inclusive_scan(k.temp, temp, k.flags, k.pos, (size_t)n, rocprim::plus<int>(), s) != hipSuccess)
-    return fail("%s: rocprim::inclusive_scan failed", who);
-  hipLaunchKernelGGL(pair_rank_kernel, dim3(nb), dim3(256), 0, s, a);
-  return check_launch(who);
+  if (int rc = rank_order(who, o.rank, o.khi, o.klo, (long)n, s)) return rc;
+  const PairArgs a{o.rank.hi_s, o.klo, o.rank.idx2, mark};
+  return rank_sorted(who, a, o.rank, ranks, reinterpret_cast<u64*>(info), (long)n, s);
 }
 
 // ---- R colourings of the same graphs through the kernels of graphkern.hip ---------------------------------------------------------
@@ -258,10 +225,8 @@ extern "C" int kgcn_wl_refine_copies_i32(const kgcn_csr_batch* a, const int32_t*
 }
 
 extern "C" int64_t kgcn_wl_rank_copies_workspace_bytes(int64_t rows, int32_t copies) {
-  if (rows < 0 || copies < 1 || rows * copies >= (int64_t)INT32_MAX) {
-    fail("kgcn_wl_rank_copies_workspace_bytes: %d copies x %lld rows outside 0..2^31-2", copies, (long long)rows);
-    return -1;
-  }
+  if (rows < 0 || copies < 1 || rows * copies >= (int64_t)INT32_MAX)
+    return refuse_query("kgcn_wl_rank_copies_workspace_bytes: %d copies x %lld rows outside 0..2^31-2", copies, (long long)rows);
   return kgcn_wl_rank_workspace_bytes(rows * copies);
 }
 
@@ -273,10 +238,8 @@ extern "C" int kgcn_wl_rank_copies_i32(const kgcn_csr_batch* a, const int32_t* n
 }
 
 extern "C" int64_t kgcn_graph_runs_copies_workspace_bytes(int32_t graphs, int32_t copies) {
-  if (graphs < 0 || copies < 1 || (int64_t)graphs * copies >= (int64_t)INT32_MAX) {
-    fail("kgcn_graph_runs_copies_workspace_bytes: %d copies x %d graphs", copies, graphs);
-    return -1;
-  }
+  if (graphs < 0 || copies < 1 || (int64_t)graphs * copies >= (int64_t)INT32_MAX)
+    return refuse_query("kgcn_graph_runs_copies_workspace_bytes: %d copies x %d graphs", copies, graphs);
   return kgcn_graph_runs_workspace_bytes(graphs * copies);
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -84,6 +85,16 @@ int allow_full_lds(size_t need = 0, const char* who = nullptr) {
     done = true;
   }
   return 0;
+}
+
+// Block b of a grid over the upper triangle of a tile matrix, column by column -> (ti, tj), ti <= tj, b = tj (tj + 1) / 2 + ti.
+// In double the root is off by at most one for every b below 2^52; the two loops correct that.
+__host__ __device__ __forceinline__ void tile_of(long b, int& ti, int& tj) {
+  long t = (long)((sqrt(8.0 * (double)b + 1.0) - 1.0) * 0.5);
+  while (t * (t + 1) / 2 > b) --t;
+  while ((t + 1) * (t + 2) / 2 <= b) ++t;
+  tj = (int)t;
+  ti = (int)(b - t * (t + 1) / 2);
 }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));

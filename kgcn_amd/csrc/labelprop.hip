@@ -17,20 +17,16 @@
 // Nothing is fused: the Makefile builds this file with -ffp-contract=off (see hashkern.hip for why a pragma is not enough).
 #include <math.h>
 
-#include "kgcn_common.h"
+#include "gram_tile.h"
+#include "workspace.h"
 
 namespace kgcn {
 namespace {
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-constexpr int kTile = 64;                  // affinity tile edge of a workgroup
-constexpr int kKc = 16;                    // attributes staged per step
-constexpr int kLd = kKc + 1;
 constexpr int kRowsWave = 8;               // rows of W a wave carries through the step
 constexpr int kRowsWg = KGCN_LP_BLOCK_ROWS;   // 4 waves x 8 rows: the unit of the convergence partials
 constexpr int kMaxTasks = KGCN_LP_MAX_TASKS;
 constexpr int kMaxCols = KGCN_LP_MAX_COLS;
-constexpr size_t kHead = 256;              // the workspace's first bytes: the running-task word
 static_assert(kRowsWg == 4 * kRowsWave, "a step workgroup is four waves");
 
 // the sum of a value over the 64 lanes in the stated tree: v = v + (v of lane ^ off) for off = 32, 16, 8, 4, 2, 1; every lane ends
@@ -50,53 +46,15 @@ __global__ __launch_bounds__(256) void lp_norms_kernel(const double* __restrict_
   norms[i] = acc;
 }
 
-// upper-triangle tile b -> (ti <= tj), column by column: b = tj (tj + 1) / 2 + ti
-__device__ __forceinline__ void tile_of(long b, int& ti, int& tj) {
-  long t = (long)((sqrt(8.0 * (double)b + 1.0) - 1.0) * 0.5);
-  while (t * (t + 1) / 2 > b) --t;
-  while ((t + 1) * (t + 2) / 2 <= b) ++t;
-  tj = (int)t;
-  ti = (int)(b - t * (t + 1) / 2);
-}
-
-// v_mfma_f64_16x16x4_f64: lane l holds A[row l & 15][k l >> 4] and B[k l >> 4][col l & 15], result r of the lane is
-// C[row (l >> 4) + 4 r][col l & 15] (graphkern.hip's gram_tile_kernel).
-// THE Gram tile of this file: acc = x_a . x_b for the 64 rows of xa [na, d] from ia0 against the 64 rows of xb [nb, d] from ib0, four
-// waves of 2 x 2 MFMA blocks; 16 attributes staged at a time in as / bs [kTile][kLd], the MFMA fed 4 at a time.  Rows past the set
-// and attributes past d are staged as 0.  The panels are free again on return.
+// THE Gram tile of this file (gram_tile.h): acc = x_a . x_b for the 64 rows of xa [na, d] from ia0 against the 64 rows of xb [nb, d]
+// from ib0.  Rows past the set and attributes past d are staged as 0.  The panels are free again on return.
 __device__ __forceinline__ void gram_tile(const double* __restrict__ xa, long ia0, long na, const double* __restrict__ xb, long ib0,
                                           long nb, int d, double* as, double* bs, f64x4 (&acc)[2][2]) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, li = lane & 15, hi = lane >> 4, wr = wv >> 1, wc = wv & 1;
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[a][b][r] = 0.0;
-  const int kk = tid & (kKc - 1);
-  for (int k0 = 0; k0 < d; k0 += kKc) {
-    for (int r = tid >> 4; r < kTile; r += 16) {
-      const long ia = ia0 + r, ib = ib0 + r;
-      const bool kin = k0 + kk < d;
-      as[r * kLd + kk] = (kin && ia < na) ? xa[ia * d + k0 + kk] : 0.0;
-      bs[r * kLd + kk] = (kin && ib < nb) ? xb[ib * d + k0 + kk] : 0.0;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int s = 0; s < kKc; s += 4) {
-      double a[2], b[2];
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        a[q] = as[(wr * 32 + q * 16 + li) * kLd + s + hi];
-        b[q] = bs[(wc * 32 + q * 16 + li) * kLd + s + hi];
-      }
-#pragma unroll
-      for (int p = 0; p < 2; ++p)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) acc[p][q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[p], b[q], acc[p][q], 0, 0, 0);
-    }
-    __syncthreads();
-  }
+  for (auto& row : acc)
+    for (auto& blk : row) blk = f64x4{0.0, 0.0, 0.0, 0.0};
+  gram_tile_64(
+      as, bs, d, [&](int r, int k0, int kk) { const long ia = ia0 + r; return (k0 + kk < d && ia < na) ? xa[ia * d + k0 + kk] : 0.0; },
+      [&](int r, int k0, int kk) { const long ib = ib0 + r; return (k0 + kk < d && ib < nb) ? xb[ib * d + k0 + kk] : 0.0; }, acc);
 }
 
 // w = exp(-gamma max(0, (|a|^2 + |b|^2) - 2 a.b)), NaN kept; same_point: the two are the same row of the same set, dist = 0
@@ -682,16 +640,19 @@ int check_shape(const char* who, int64_t n, int32_t T, int32_t K) {
 long step_blocks(int64_t n) { return (long)((n + kRowsWg - 1) / kRowsWg); }
 
 struct Workspace {
-  unsigned* running;
-  double *F[2], *G[2], *partial;
+  unsigned* running;                 // the running-task word
+  double *F[2], *G[2], *partial;     // one run of doubles: 4 x [n, K], then [step blocks, T]
+  size_t total;
 };
 
-Workspace carve(void* workspace, int64_t n, int32_t K) {
-  unsigned char* ws = reinterpret_cast<unsigned char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-  Workspace o;
-  o.running = reinterpret_cast<unsigned*>(ws);
-  double* p = reinterpret_cast<double*>(ws + kHead);
-  const size_t nk = (size_t)n * K;
+Workspace carve(unsigned char* base, int64_t n, int32_t T, int32_t K) {
+  Workspace o{};
+  Taker t{base};
+  o.running = t.take<unsigned>(1);
+  const size_t head = t.off, nk = (size_t)n * K, doubles = 4 * nk + (size_t)step_blocks(n) * T;
+  double* p = t.take<double>(doubles);
+  o.total = head + doubles * sizeof(double) + 256;             // the run is counted as it is, not rounded up
+  if (!p) return o;
   o.F[0] = p;
   o.F[1] = p + nk;
   o.G[0] = p + 2 * nk;
@@ -700,14 +661,18 @@ Workspace carve(void* workspace, int64_t n, int32_t K) {
   return o;
 }
 
-int check_points(const char* who, int64_t n, int32_t d, const double* gamma) {
+// max_bytes: what the caller grants a stored n x n affinity matrix
+int check_points(const char* who, int64_t n, int32_t d, const double* gamma, int64_t max_bytes = INT64_MAX) {
   if (n < 1 || n > KGCN_LP_MAX_ROWS || d < 1) return fail("%s: %lld points of %d attributes (1..%d points)", who, (long long)n, d, KGCN_LP_MAX_ROWS);
+  if (n * n * 8 > max_bytes)
+    return fail("%s: the %lld x %lld affinity matrix takes %lld bytes, over max_bytes = %lld; refused before any launch", who,
+                (long long)n, (long long)n, (long long)(n * n * 8), (long long)max_bytes);
   if (!gamma || !(*gamma > 0.0) || !(*gamma < INFINITY)) return fail("%s: gamma must be positive and finite", who);
   return 0;
 }
 
 void launch_norms(const double* x, int64_t n, int32_t d, double* norms, hipStream_t s) {
-  hipLaunchKernelGGL(lp_norms_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, (long)n, d, norms);
+  hipLaunchKernelGGL(lp_norms_kernel, dim3(blocks_of((long)n)), dim3(256), 0, s, x, (long)n, d, norms);
 }
 
 template <int KC>
@@ -731,10 +696,9 @@ int lp_propagate_steps(const char* who, const double* W, const double* x, double
   if (!tol || !(*tol >= 0.0) || !(*tol < INFINITY)) return fail("%s: the tolerance must be finite and not negative", who);
   if (max_iter < 0 || first_step < 0 || steps < 0 || (int64_t)first_step + steps >= INT32_MAX)
     return fail("%s: max_iter %d, first_step %d, steps %d", who, max_iter, first_step, steps);
-  const int64_t need = kgcn_lp_workspace_bytes(n, tasks, cols);
-  if (!workspace || workspace_bytes < need) return fail("%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes, (long long)need);
+  if (int rc = check_workspace(who, workspace, workspace_bytes, (int64_t)carve(nullptr, n, tasks, cols).total)) return rc;
   if ((!W && (!x || !norms)) || !scale || !labels || !task_col || !n_iter || !status) return fail("%s: NULL operand", who);
-  const Workspace ws = carve(workspace, n, cols);
+  const Workspace ws = carve(aligned_base(workspace), n, tasks, cols);
   hipStream_t s = as_stream(stream);
   const long blocks = step_blocks(n);
   const bool spreading = variant == KGCN_LP_SPREADING;
@@ -746,9 +710,8 @@ int lp_propagate_steps(const char* who, const double* W, const double* x, double
   a.alpha = spreading ? *alpha : 0.0, a.tol = *tol, a.max_iter = max_iter;
   a.partial = ws.partial, a.status = status, a.n_iter = n_iter, a.running = ws.running;
   if (first_step == 0) {
-    if (hipMemsetAsync(status, 0, (size_t)tasks * sizeof(int32_t), s) != hipSuccess ||
-        hipMemsetAsync(n_iter, 0, (size_t)tasks * sizeof(int32_t), s) != hipSuccess)
-      return fail("%s: hipMemsetAsync failed", who);
+    if (int rc = zero_async(who, status, (size_t)tasks * sizeof(int32_t), s)) return rc;
+    if (int rc = zero_async(who, n_iter, (size_t)tasks * sizeof(int32_t), s)) return rc;
     if (!W) launch_norms(x, n, d, norms, s);
     a.Fnext = ws.F[0];
     a.Gnext = ws.G[0];
@@ -781,14 +744,10 @@ using namespace kgcn;
 extern "C" int kgcn_rbf_affinity_f64(const double* x, int64_t n, int32_t d, const double* gamma, int64_t max_bytes, double* W,
                                      double* norms, void* stream) {
   const char* who = "kgcn_rbf_affinity_f64";
-  if (n < 1 || n > KGCN_LP_MAX_ROWS || d < 1) return fail("%s: %lld points of %d attributes (1..%d points)", who, (long long)n, d, KGCN_LP_MAX_ROWS);
-  if (n * n * 8 > max_bytes)
-    return fail("%s: the %lld x %lld affinity matrix takes %lld bytes, over max_bytes = %lld; refused before any launch", who,
-                (long long)n, (long long)n, (long long)(n * n * 8), (long long)max_bytes);
-  if (!gamma || !(*gamma > 0.0) || !(*gamma < INFINITY)) return fail("%s: gamma must be positive and finite", who);
+  if (int rc = check_points(who, n, d, gamma, max_bytes)) return rc;
   if (!x || !W || !norms) return fail("%s: NULL operand", who);
   hipStream_t s = as_stream(stream);
-  hipLaunchKernelGGL(lp_norms_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, (long)n, d, norms);
+  launch_norms(x, n, d, norms, s);
   const long nt = (long)((n + kTile - 1) / kTile);
   hipLaunchKernelGGL(lp_affinity_kernel, dim3((unsigned)(nt * (nt + 1) / 2)), dim3(256), 0, s, x, norms, (long)n, d, *gamma, W);
   return check_launch(who);
@@ -804,7 +763,7 @@ extern "C" int kgcn_lp_degrees_f64(const double* W, int64_t n, double* s_out, do
 
 extern "C" int64_t kgcn_lp_workspace_bytes(int64_t n, int32_t tasks, int32_t cols) {
   if (check_shape("kgcn_lp_workspace_bytes", n, tasks, cols)) return -1;
-  return (int64_t)(kHead + ((size_t)4 * n * cols + (size_t)step_blocks(n) * tasks) * sizeof(double) + 256);
+  return (int64_t)carve(nullptr, n, tasks, cols).total;
 }
 
 extern "C" int kgcn_lp_propagate_f64(const double* W, const double* scale, int64_t n, const int32_t* labels, const int32_t* task_col,
@@ -863,11 +822,10 @@ extern "C" int kgcn_lp_finish_f64(int64_t n, const int32_t* task_col, int32_t ta
                                   const void* workspace, int64_t workspace_bytes, void* stream) {
   const char* who = "kgcn_lp_finish_f64";
   if (int rc = check_shape(who, n, tasks, cols)) return rc;
-  const int64_t need = kgcn_lp_workspace_bytes(n, tasks, cols);
-  if (!workspace || workspace_bytes < need) return fail("%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes, (long long)need);
+  if (int rc = check_workspace(who, workspace, workspace_bytes, (int64_t)carve(nullptr, n, tasks, cols).total)) return rc;
   if (!task_col || !dist || steps_done < 0) return fail("%s: NULL operand or %d steps", who, steps_done);
-  const Workspace ws = carve(const_cast<void*>(workspace), n, cols);
-  hipLaunchKernelGGL(lp_finish_kernel, dim3((unsigned)((n * tasks + 255) / 256)), dim3(256), 0, as_stream(stream), ws.F[steps_done & 1],
+  const Workspace ws = carve(aligned_base(const_cast<void*>(workspace)), n, tasks, cols);   // read only
+  hipLaunchKernelGGL(lp_finish_kernel, dim3(blocks_of((long)n * tasks)), dim3(256), 0, as_stream(stream), ws.F[steps_done & 1],
                      task_col, (long)n, tasks, cols, dist);
   return check_launch(who);
 }
@@ -879,7 +837,7 @@ extern "C" int kgcn_lp_scores_f64(const double* dist, int64_t n, const int32_t* 
   if (m < 0 || m > KGCN_LP_MAX_ROWS) return fail("%s: %lld candidates", who, (long long)m);
   if (m == 0) return 0;
   if (!dist || !task_col || !cand || !scores) return fail("%s: NULL operand", who);
-  hipLaunchKernelGGL(lp_scores_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, as_stream(stream), dist, task_col, (long)n, tasks,
+  hipLaunchKernelGGL(lp_scores_kernel, dim3(blocks_of((long)m)), dim3(256), 0, as_stream(stream), dist, task_col, (long)n, tasks,
                      cols, cand, (long)m, scores);
   return check_launch(who);
 }

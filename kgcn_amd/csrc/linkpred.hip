@@ -22,7 +22,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "block_reduce.h"
-#include "kgcn_common.h"
+#include "workspace.h"
 #include "philox.h"
 
 namespace kgcn {
@@ -34,7 +34,6 @@ constexpr int kDwGroups = 256;       // workgroups (= partials) of the relation-
 constexpr float kLogEps = 1.0e-10f;
 constexpr float kGamma = 0.1f;
 
-__host__ __device__ __forceinline__ size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 __device__ __forceinline__ uint64_t read_step(const int64_t* step) { return step ? (uint64_t)*step : 0ull; }
 
 // u in [0, K) for row `row` of step `step`: no modulo bias (rejection of the 2^64 mod K lowest product halves)
@@ -329,19 +328,18 @@ size_t sort_temp_bytes(long E, unsigned bits) {
 Layout layout(unsigned char* base, long N, int D, int R, int L) {
   Layout o{};
   const long E = 4l * L, nch = (E + kChunk - 1) / kChunk;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { void* p = base ? base + off : nullptr; off += al256(bytes); return p; };
-  o.keys_in = (uint32_t*)take(E * 4);
-  o.keys_out = (uint32_t*)take(E * 4);
-  o.vals_in = (uint32_t*)take(E * 4);
-  o.vals_out = (uint32_t*)take(E * 4);
-  o.start = (int32_t*)take((N + 1) * 4);
-  o.up = (float*)take((size_t)L * 4);
-  o.part = (float*)take((size_t)nch * 2 * D * 4);
-  o.dwpart = (float*)take(R > 0 ? (size_t)dw_groups(L) * R * D * 4 : 0);
+  Taker t{base};
+  o.keys_in = t.take<uint32_t>((size_t)E);
+  o.keys_out = t.take<uint32_t>((size_t)E);
+  o.vals_in = t.take<uint32_t>((size_t)E);
+  o.vals_out = t.take<uint32_t>((size_t)E);
+  o.start = t.take<int32_t>((size_t)N + 1);
+  o.up = t.take<float>((size_t)L);
+  o.part = t.take<float>((size_t)nch * 2 * D);
+  o.dwpart = t.take<float>(R > 0 ? (size_t)dw_groups(L) * R * D : 0);
   o.temp_bytes = sort_temp_bytes(E, key_bits(N));
-  o.temp = take(o.temp_bytes);
-  o.total = off + 256;
+  o.temp = t.take<unsigned char>(o.temp_bytes);
+  o.total = t.off + 256;
   return o;
 }
 
@@ -390,20 +388,18 @@ extern "C" int kgcn_linkpred_bwd_f32(const float* h, int64_t nodes, int32_t dim,
   const bool dm = mode == KGCN_LP_DISTMULT;
   if (!h || !rows || !s1 || !s2 || !sums || !dh || (dm && (!w || !dw))) return fail("kgcn_linkpred_bwd_f32: NULL operand");
   const int R = dm ? relations : 0;
-  const int64_t need = (int64_t)layout(nullptr, nodes, dim, R, batch).total;
-  if (!workspace || workspace_bytes < need)
-    return fail("kgcn_linkpred_bwd_f32: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
+  if (int rc = check_workspace("kgcn_linkpred_bwd_f32", workspace, workspace_bytes, (int64_t)layout(nullptr, nodes, dim, R, batch).total))
+    return rc;
   hipStream_t s = as_stream(stream);
-  unsigned char* base = reinterpret_cast<unsigned char*>(al256(reinterpret_cast<size_t>(workspace)));
-  Layout o = layout(base, nodes, dim, R, batch);
+  const Layout o = layout(aligned_base(workspace), nodes, dim, R, batch);
   const long E = 4l * batch, nch = (E + kChunk - 1) / kChunk;
-  hipLaunchKernelGGL(lp_keys_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, s, rows, s1, s2, sums, batch, mode,
+  hipLaunchKernelGGL(lp_keys_kernel, dim3(blocks_of(batch)), dim3(256), 0, s, rows, s1, s2, sums, batch, mode,
                      g_opt, g_sum, o.keys_in, o.vals_in, o.up);
   size_t temp = o.temp_bytes;
   if (rocprim::radix_sort_pairs(o.temp, temp, o.keys_in, o.keys_out, o.vals_in, o.vals_out, (size_t)E, 0u, key_bits(nodes), s) !=
       hipSuccess)
     return fail("kgcn_linkpred_bwd_f32: rocprim::radix_sort_pairs failed");
-  hipLaunchKernelGGL(lp_start_kernel, dim3((unsigned)((E + 1 + 255) / 256)), dim3(256), 0, s, o.keys_out, E, (long)nodes, o.start);
+  hipLaunchKernelGGL(lp_start_kernel, dim3(blocks_of(E + 1)), dim3(256), 0, s, o.keys_out, E, (long)nodes, o.start);
   SumArgs sa{h, dm ? w : nullptr, rows, o.up, o.keys_out, o.vals_out, o.start, dh, o.part, E, nch, dim};
   hipLaunchKernelGGL(lp_chunk_sum_kernel, dim3((unsigned)((nch + 3) / 4)), dim3(256), 0, s, sa);
   hipLaunchKernelGGL(lp_node_sum_kernel, dim3((unsigned)((nodes + 3) / 4)), dim3(256), 0, s, o.start, o.part, (long)nodes, dim, dh);

@@ -27,7 +27,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
-#include "kgcn_common.h"
+#include "workspace.h"
 
 namespace kgcn {
 
@@ -38,7 +38,6 @@ constexpr int kLd = kKc + 1;         // LDS row stride (floats)
 constexpr int kBins = 2048;          // bins of the widest digit
 constexpr int kMaxTop = KGCN_PAIRRANK_MAX_TOP;
 
-__host__ __device__ __forceinline__ size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 __host__ __device__ __forceinline__ int digit_bits(int pass) { return pass == 2 ? 10 : 11; }
 __host__ __device__ __forceinline__ int digit_shift(int pass) { return pass == 0 ? 21 : pass == 1 ? 10 : 0; }
 
@@ -58,15 +57,6 @@ __device__ __forceinline__ uint32_t score_key(float v) {
 __device__ __forceinline__ float key_score(uint32_t key) {
   if (key == 0u) return __uint_as_float(0x7fc00000u);
   return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
-}
-
-// block index b -> (ti, tj), ti <= tj, b = tj (tj + 1) / 2 + ti
-__device__ __forceinline__ void tile_of(unsigned b, int& ti, int& tj) {
-  int t = (int)((sqrtf(8.0f * (float)b + 1.0f) - 1.0f) * 0.5f);
-  while ((unsigned)t * (unsigned)(t + 1) / 2u > b) --t;
-  while ((unsigned)(t + 1) * (unsigned)(t + 2) / 2u <= b) ++t;
-  tj = t;
-  ti = (int)(b - (unsigned)t * (unsigned)(t + 1) / 2u);
 }
 
 // the wave's 32 x 32 block of tile (ti, tj): acc[r] is pair (ti 64 + wr 32 + (r & 3) + 8 (r >> 2) + 4 hi, tj 64 + wc 32 + li)
@@ -121,7 +111,7 @@ __global__ __launch_bounds__(256) void pair_tile_kernel(TileArgs a) {
   __shared__ unsigned lh[MODE == 0 ? kBins : 1];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, li = lane & 31, hi = lane >> 5, wr = wv >> 1, wc = wv & 1;
   int ti, tj;
-  tile_of(blockIdx.x, ti, tj);
+  tile_of((long)blockIdx.x, ti, tj);
   if (MODE == 0)
     for (int q = tid; q < kBins; q += 256) lh[q] = 0u;   // ordered before the atomics by score_block's barriers
   const f32x16 acc = score_block(a.h, a.w, a.N, a.D, ti, tj, as, bs);
@@ -308,15 +298,14 @@ struct Layout {
 };
 Layout rank_layout(unsigned char* base, long long capacity) {
   Layout o{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) { void* p = base ? base + off : nullptr; off += al256(bytes); return p; };
-  o.st = (State*)take(sizeof(State));
-  o.hist = (unsigned*)take(kBins * sizeof(unsigned));
-  o.cand = (unsigned long long*)take((size_t)capacity * 8);
-  o.sorted = (unsigned long long*)take((size_t)capacity * 8);
+  Taker t{base};
+  o.st = t.take<State>(1);
+  o.hist = t.take<unsigned>(kBins);
+  o.cand = t.take<unsigned long long>((size_t)capacity);
+  o.sorted = t.take<unsigned long long>((size_t)capacity);
   o.temp_bytes = capacity > 0 ? sort_temp_bytes((size_t)capacity) : 0;
-  o.temp = take(o.temp_bytes);
-  o.total = off + 256;
+  o.temp = t.take<unsigned char>(o.temp_bytes);
+  o.total = t.off + 256;
   return o;
 }
 
@@ -327,13 +316,12 @@ struct TableLayout {
 };
 TableLayout table_layout(unsigned char* base, long long n) {
   TableLayout o{};
-  size_t off = 0;
-  auto take = [&](size_t bytes) { void* p = base ? base + off : nullptr; off += al256(bytes); return p; };
-  o.nontrain = (int*)take((size_t)n * 4);
-  o.pos = (int*)take((size_t)n * 4);
+  Taker t{base};
+  o.nontrain = t.take<int>((size_t)n);
+  o.pos = t.take<int>((size_t)n);
   o.temp_bytes = n > 0 ? scan_temp_bytes((size_t)n) : 0;
-  o.temp = take(o.temp_bytes);
-  o.total = off + 256;
+  o.temp = t.take<unsigned char>(o.temp_bytes);
+  o.total = t.off + 256;
   return o;
 }
 
@@ -361,14 +349,10 @@ using namespace kgcn;
 extern "C" int64_t kgcn_pair_rank_workspace_bytes(int32_t nodes, int32_t dim, int64_t capacity, int64_t entries) {
   const char* who = "kgcn_pair_rank_workspace_bytes";
   if (check_shape(who, nodes, dim)) return -1;
-  if (capacity < 0 || capacity > KGCN_PAIRRANK_MAX_CANDIDATES) {
-    fail("%s: %lld candidates outside 0..%d", who, (long long)capacity, KGCN_PAIRRANK_MAX_CANDIDATES);
-    return -1;
-  }
-  if (entries < 0 || entries > KGCN_PAIRRANK_MAX_CANDIDATES) {
-    fail("%s: %lld table entries outside 0..%d", who, (long long)entries, KGCN_PAIRRANK_MAX_CANDIDATES);
-    return -1;
-  }
+  if (capacity < 0 || capacity > KGCN_PAIRRANK_MAX_CANDIDATES)
+    return refuse_query("%s: %lld candidates outside 0..%d", who, (long long)capacity, KGCN_PAIRRANK_MAX_CANDIDATES);
+  if (entries < 0 || entries > KGCN_PAIRRANK_MAX_CANDIDATES)
+    return refuse_query("%s: %lld table entries outside 0..%d", who, (long long)entries, KGCN_PAIRRANK_MAX_CANDIDATES);
   const size_t a = rank_layout(nullptr, capacity).total, b = table_layout(nullptr, entries).total;
   return (int64_t)(a > b ? a : b);
 }
@@ -379,12 +363,10 @@ extern "C" int kgcn_pair_rank_select_f32(const float* h, int32_t nodes, int32_t 
   if (int rc = check_shape(who, nodes, dim)) return rc;
   if (cutoff < 0) return fail("%s: negative cutoff %lld", who, (long long)cutoff);
   if (!h || !counts) return fail("%s: NULL operand", who);
-  const int64_t need = (int64_t)rank_layout(nullptr, 0).total;
-  if (!workspace || workspace_bytes < need) return fail("%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes, (long long)need);
+  if (int rc = check_workspace(who, workspace, workspace_bytes, (int64_t)rank_layout(nullptr, 0).total)) return rc;
   hipStream_t s = as_stream(stream);
-  Layout o = rank_layout(reinterpret_cast<unsigned char*>(al256(reinterpret_cast<size_t>(workspace))), 0);
-  if (hipError_t e = hipMemsetAsync(o.st, 0, al256(sizeof(State)) + kBins * sizeof(unsigned), s); e != hipSuccess)
-    return fail("%s: hipMemsetAsync failed: %s", who, hipGetErrorString(e));
+  const Layout o = rank_layout(aligned_base(workspace), 0);
+  if (int rc = zero_async(who, o.st, al256(sizeof(State)) + kBins * sizeof(unsigned), s)) return rc;   // the state and the histogram
   const long long k = entries_of(nodes, cutoff);
   for (int pass = 0; pass < 3; ++pass) {
     TileArgs a{h, w, o.st, o.hist, nullptr, nullptr, 0, nodes, dim, pass};
@@ -405,11 +387,10 @@ extern "C" int kgcn_pair_rank_emit_f32(const float* h, int32_t nodes, int32_t di
   if (capacity < k || capacity > KGCN_PAIRRANK_MAX_CANDIDATES)
     return fail("%s: capacity %lld outside %lld..%d (the %lld entries asked for .. KGCN_PAIRRANK_MAX_CANDIDATES)", who,
                 (long long)capacity, k, KGCN_PAIRRANK_MAX_CANDIDATES, k);
-  const int64_t need = (int64_t)rank_layout(nullptr, capacity).total;
-  if (!workspace || workspace_bytes < need) return fail("%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes, (long long)need);
+  if (int rc = check_workspace(who, workspace, workspace_bytes, (int64_t)rank_layout(nullptr, capacity).total)) return rc;
   hipStream_t s = as_stream(stream);
-  Layout o = rank_layout(reinterpret_cast<unsigned char*>(al256(reinterpret_cast<size_t>(workspace))), capacity);
-  if (hipMemsetAsync(&o.st->appended, 0, sizeof(unsigned long long), s) != hipSuccess) return fail("%s: hipMemsetAsync failed", who);
+  const Layout o = rank_layout(aligned_base(workspace), capacity);
+  if (int rc = zero_async(who, &o.st->appended, sizeof(unsigned long long), s)) return rc;
   TileArgs a{h, w, o.st, o.hist, reinterpret_cast<const long long*>(counts), o.cand, (long long)capacity, nodes, dim, 0};
   hipLaunchKernelGGL(pair_tile_kernel<1>, dim3(tile_blocks(nodes)), dim3(256), 0, s, a);
   if (int rc = check_launch(who)) return rc;
@@ -427,7 +408,7 @@ extern "C" int kgcn_pair_rank_emit_f32(const float* h, int32_t nodes, int32_t di
   if (temp > o.temp_bytes) return fail("%s: sort scratch %zu > %zu bytes", who, temp, o.temp_bytes);
   if (rocprim::radix_sort_keys_desc(o.temp, temp, o.cand, o.sorted, (size_t)appended, 0u, 64u, s) != hipSuccess)
     return fail("%s: rocprim::radix_sort_keys_desc failed", who);
-  hipLaunchKernelGGL(pair_unpack_kernel, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, s, o.sorted, (long)k, score, row, col);
+  hipLaunchKernelGGL(pair_unpack_kernel, dim3(blocks_of((long)k)), dim3(256), 0, s, o.sorted, (long)k, score, row, col);
   return check_launch(who);
 }
 
@@ -445,21 +426,20 @@ extern "C" int kgcn_pair_rank_table_i32(const float* score, const int32_t* row, 
   if (!score || !row || !col || !train_edge || !test_edge || !new_edge || !score_ranking || (num_target > 0 && !target_codes) ||
       (num_test > 0 && !test_codes) || (num_top > 0 && (!top_ratio || !hits || !covered)))
     return fail("%s: NULL operand", who);
-  const int64_t need = (int64_t)table_layout(nullptr, entries).total;
-  if (!workspace || workspace_bytes < need) return fail("%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes, (long long)need);
+  if (int rc = check_workspace(who, workspace, workspace_bytes, (int64_t)table_layout(nullptr, entries).total)) return rc;
   hipStream_t s = as_stream(stream);
-  TableLayout o = table_layout(reinterpret_cast<unsigned char*>(al256(reinterpret_cast<size_t>(workspace))), entries);
+  const TableLayout o = table_layout(aligned_base(workspace), entries);
   TableArgs a{score, row, col, target_codes, test_codes, train_edge, test_edge, new_edge, reinterpret_cast<long long*>(score_ranking),
               o.nontrain, o.pos, reinterpret_cast<unsigned long long*>(hits), reinterpret_cast<long long*>(covered),
               (long)entries, (long)num_target, (long)num_test, {}, num_top};
   for (int q = 0; q < num_top; ++q) a.top[q] = top_ratio[q];
-  const unsigned nb = (unsigned)((entries + 255) / 256);
+  const unsigned nb = blocks_of((long)entries);
   hipLaunchKernelGGL(pair_mark_kernel, dim3(nb), dim3(256), 0, s, a);
   size_t temp = o.temp_bytes;
   if (rocprim::exclusive_scan(o.temp, temp, o.nontrain, o.pos, 0, (size_t)entries, rocprim::plus<int>(), s) != hipSuccess)
     return fail("%s: rocprim::exclusive_scan failed", who);
   if (num_top > 0) {
-    if (hipMemsetAsync(hits, 0, (size_t)num_top * sizeof(int64_t), s) != hipSuccess) return fail("%s: hipMemsetAsync failed", who);
+    if (int rc = zero_async(who, hits, (size_t)num_top * sizeof(int64_t), s)) return rc;
     hipLaunchKernelGGL(pair_hits_kernel, dim3(nb), dim3(256), 0, s, a);
   }
   return check_launch(who);

@@ -15,7 +15,7 @@
 // descriptor a kernel reads is range-checked in the kernel before it is used as an address: a bad one is reported, never followed.
 #include <math.h>
 
-#include "kgcn_common.h"
+#include "workspace.h"
 
 namespace kgcn {
 namespace {
@@ -25,7 +25,6 @@ constexpr int kMaxRows = KGCN_SVM_MAX_ROWS;
 constexpr int kPerThread = 4;                    // elements a thread owns: 64 / 256 / 1,024 threads for 256 / 1,024 / 4,096 rows
 constexpr int kSlotDoubles = 4 * 16;             // one reduction slot: (value, carried, maximum, index) of up to 16 waves
 constexpr double kTau = 1e-12;                   // svm.cpp: #define TAU 1e-12
-constexpr size_t kHead = 256;                    // the workspace's first bytes: the unfinished-problem word
 
 struct Sets {
   const long long* ptr;
@@ -414,6 +413,21 @@ size_t smo_lds_bytes(int stride) {
   return (size_t)stride * (3 * sizeof(double) + sizeof(int32_t) + sizeof(int8_t)) + 2 * kSlotDoubles * sizeof(double);
 }
 
+struct Workspace {
+  unsigned* unfinished;              // the unfinished-problem word
+  double* grad;                      // [problems, max_rows]
+  size_t total;
+};
+Workspace carve(unsigned char* base, int32_t problems, int32_t max_rows) {
+  Workspace o{};
+  Taker t{base};
+  o.unfinished = t.take<unsigned>(1);
+  const size_t head = t.off, rows = (size_t)problems * max_rows;
+  o.grad = t.take<double>(rows);
+  o.total = head + rows * sizeof(double) + 256;                // the last array is counted as it is, not rounded up
+  return o;
+}
+
 template <int kThreads>
 int launch_smo(const char* who, const SmoArgs& a, int problems, hipStream_t s) {
   const size_t lds = smo_lds_bytes(a.train.max_rows);
@@ -428,11 +442,9 @@ int launch_smo(const char* who, const SmoArgs& a, int problems, hipStream_t s) {
 using namespace kgcn;
 
 extern "C" int64_t kgcn_svm_workspace_bytes(int32_t problems, int32_t max_rows) {
-  if (problems < 0 || check_rows("kgcn_svm_workspace_bytes", max_rows)) {
-    if (problems < 0) fail("kgcn_svm_workspace_bytes: %d problems", problems);
-    return -1;
-  }
-  return (int64_t)(kHead + (size_t)problems * max_rows * sizeof(double) + 256);
+  if (problems < 0) return refuse_query("kgcn_svm_workspace_bytes: %d problems", problems);
+  if (check_rows("kgcn_svm_workspace_bytes", max_rows)) return -1;
+  return (int64_t)carve(nullptr, problems, max_rows).total;
 }
 
 extern "C" int kgcn_svm_smo_f64(const double* K, int32_t graphs, const int64_t* set_ptr, const int32_t* set_idx, const int8_t* set_sign,
@@ -448,15 +460,14 @@ extern "C" int kgcn_svm_smo_f64(const double* K, int32_t graphs, const int64_t* 
   if (problems < 0) return fail("%s: %d problems", who, problems);
   if (!tol || !(*tol > 0.0) || !(*tol < INFINITY)) return fail("%s: the tolerance must be positive and finite", who);
   if (iters_per_launch < 1) return fail("%s: %d iterations a launch, at least 1", who, iters_per_launch);
-  const int64_t need = kgcn_svm_workspace_bytes(problems, max_rows);
-  if (!workspace || workspace_bytes < need) return fail("%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes, (long long)need);
-  unsigned char* ws = reinterpret_cast<unsigned char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
+  if (int rc = check_workspace(who, workspace, workspace_bytes, (int64_t)carve(nullptr, problems, max_rows).total)) return rc;
+  const Workspace ws = carve(aligned_base(workspace), problems, max_rows);
   hipStream_t s = as_stream(stream);
-  if (hipMemsetAsync(ws, 0, sizeof(unsigned), s) != hipSuccess) return fail("%s: hipMemsetAsync failed", who);
+  if (int rc = zero_async(who, ws.unfinished, sizeof(unsigned), s)) return rc;
   if (problems == 0) return 0;
   if (!K || !prob_set || !prob_C || !alpha || !rho || !n_iter || !status) return fail("%s: NULL operand", who);
   SmoArgs a{K, graphs, train, prob_set, prob_C, *tol, (long long)max_iter, iters_per_launch, first ? 1 : 0, alpha, rho,
-            reinterpret_cast<double*>(ws + kHead), reinterpret_cast<long long*>(n_iter), status, reinterpret_cast<unsigned*>(ws)};
+            ws.grad, reinterpret_cast<long long*>(n_iter), status, ws.unfinished};
   if (max_rows <= 64 * kPerThread) return launch_smo<64>(who, a, problems, s);
   if (max_rows <= 256 * kPerThread) return launch_smo<256>(who, a, problems, s);
   return launch_smo<1024>(who, a, problems, s);
@@ -477,12 +488,12 @@ extern "C" int kgcn_svm_decision_f64(const double* K, int32_t graphs, const int6
   if (problems < 0 || jobs < 0 || jobs > 65535 || dec_total < 0) return fail("%s: %d problems, %d jobs (up to 65,535)", who, problems, jobs);
   if (!errors) return fail("%s: NULL operand", who);
   hipStream_t s = as_stream(stream);
-  if (hipMemsetAsync(errors, 0, sizeof(int64_t), s) != hipSuccess) return fail("%s: hipMemsetAsync failed", who);
+  if (int rc = zero_async(who, errors, sizeof(int64_t), s)) return rc;
   if (jobs == 0 || eval_max_rows == 0) return 0;
   if (!K || !prob_set || !alpha || !rho || !job_prob || !job_eval || !job_out || !dec) return fail("%s: NULL operand", who);
   DecArgs a{K, graphs, train, prob_set, problems, alpha, rho, eval, job_prob, job_eval,
             reinterpret_cast<const long long*>(job_out), jobs, dec, (long long)dec_total, reinterpret_cast<u64*>(errors)};
-  hipLaunchKernelGGL(svm_decision_kernel, dim3((eval_max_rows + 255) / 256, jobs), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(svm_decision_kernel, dim3(blocks_of(eval_max_rows), jobs), dim3(256), 0, s, a);
   return check_launch(who);
 }
 
@@ -499,14 +510,14 @@ extern "C" int kgcn_svm_vote_i32(const double* dec, int64_t dec_total, const int
     return fail("%s: %d graphs, %d jobs, %d votes (up to 65,535)", who, graphs, jobs, votes);
   if (!errors) return fail("%s: NULL operand", who);
   hipStream_t s = as_stream(stream);
-  if (hipMemsetAsync(errors, 0, sizeof(int64_t), s) != hipSuccess) return fail("%s: hipMemsetAsync failed", who);
+  if (int rc = zero_async(who, errors, sizeof(int64_t), s)) return rc;
   if (votes == 0) return 0;
   if (!correct || !dec || !job_out || !vote_first_job || !vote_eval || !vote_out || !labels || !pred) return fail("%s: NULL operand", who);
-  if (hipMemsetAsync(correct, 0, (size_t)votes * sizeof(int64_t), s) != hipSuccess) return fail("%s: hipMemsetAsync failed", who);
+  if (int rc = zero_async(who, correct, (size_t)votes * sizeof(int64_t), s)) return rc;
   if (eval_max_rows == 0) return 0;
   VoteArgs a{dec, (long long)dec_total, reinterpret_cast<const long long*>(job_out), jobs, eval, vote_first_job, vote_eval,
              reinterpret_cast<const long long*>(vote_out), votes, classes, labels, graphs, pred, (long long)pred_total,
              reinterpret_cast<u64*>(correct), reinterpret_cast<u64*>(errors)};
-  hipLaunchKernelGGL(svm_vote_kernel, dim3((eval_max_rows + 255) / 256, votes), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(svm_vote_kernel, dim3(blocks_of(eval_max_rows), votes), dim3(256), 0, s, a);
   return check_launch(who);
 }
