@@ -16,6 +16,12 @@
  *    by the CALLER.  The library never allocates or frees device memory and keeps no global
  *    mutable state besides a thread-local error string; scratch space is passed in and sized
  *    by the *_workspace_bytes queries.
+ *  - a workspace of too few bytes is refused with "<entry>: workspace <have> < <need> bytes" before anything is launched.  The
+ *    sort-and-rank entry points (graph / hash kernels, pair ranking, CV metrics, link prediction, SVM, label propagation, COO
+ *    packing) round the pointer up themselves and take any address.  Every other entry point uses the pointer as given and
+ *    accesses it as 4-byte words, except where its layout holds a wider word: kgcn_graph_bn_stats_f32 / kgcn_graph_bn_bwd*_f32
+ *    (a 64-bit count) and kgcn_ragged_plan (64-bit pairs) need an 8-byte aligned workspace and refuse another one with
+ *    "<entry>: workspace not 8-byte aligned", nothing launched.  Pointers from a device allocator satisfy all of this.
  *  - every launch is asynchronous on the given stream (hipStream_t passed as void*); no
  *    implicit synchronisation.  Entry points are re-entrant.
  *  - return value: 0 = ok, non-zero = error; text via kgcn_last_error().  No exception crosses
@@ -867,7 +873,9 @@ int kgcn_vae_recon_bwd_f32(const kgcn_csr_batch* adj_ch, int32_t num_channels, c
  * stash (NULL under no_grad): kgcn_seq_lstm_stash_floats(B, T, H) floats, per (b, t) the 4H gate pre-activations, h and c
  * (6H floats, 768 bytes a sequence step at H = 32).  The backward reads dh[b * dh_ld + u] (NULL = 0), OVERWRITES the
  * pre-activations of the stash with their gradients, writes dx [B, T, D] (may be NULL) and -- all three or none -- d wx, d wh,
- * d bias through partials in `workspace` (>= kgcn_seq_lstm_workspace_bytes) and fixed-order second stages (deferrable).
+ * d bias through partials in `workspace` (>= kgcn_seq_lstm_workspace_bytes) and fixed-order second stages (deferrable).  An
+ * incomplete set of the three, or a workspace too small for them, is refused before the first launch: neither dx nor the stash
+ * is touched by a refused call.
  * Limits: D <= 64, H <= 64, T <= 8192.  No float atomics: results are bitwise reproducible. */
 #define KGCN_SEQ_MAX_EMBED 32
 #define KGCN_SEQ_MAX_FILTERS 64

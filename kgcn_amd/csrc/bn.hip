@@ -11,7 +11,7 @@
 //                                inference: dx = gamma rstd g                       (valid rows; 0 on padding rows)
 // All of them are HBM-bound streaming passes; reductions are deterministic (per-workgroup partials, fixed-order second stage).
 #include "block_reduce.h"
-#include "kgcn_common.h"
+#include "workspace.h"
 
 namespace kgcn {
 
@@ -226,6 +226,28 @@ static int bn_check(const char* who, const float* x, int64_t graphs, int32_t n_n
   return 0;
 }
 
+// two partial arrays [BN_BLOCKS, d] | the valid-row count, a long 16 bytes-aligned from the base.  Everything else is accessed as
+// 4-byte words, so the base has to be aligned for the long (bn_scale_kernel stores it, bn_bwd_dx_kernel loads it): 8 bytes
+struct BnWorkspace { float *part0, *part1; long* count; size_t bytes; };
+constexpr int kBnBaseAlign = 8;
+static BnWorkspace bn_layout(void* base, int32_t d) {
+  Taker t(base, 4);
+  BnWorkspace w;
+  w.part0 = t.take<float>((size_t)BN_BLOCKS * d);
+  w.part1 = t.take<float>((size_t)BN_BLOCKS * d);
+  t.align = 16;
+  w.count = t.take<long>(1);
+  w.bytes = t.off;
+  return w;
+}
+// the query's size is what the entry points ask for; the layout has to fit it
+static int bn_workspace(const char* who, void* workspace, int64_t workspace_bytes, int32_t d, BnWorkspace& w) {
+  const int64_t need = kgcn_graph_bn_workspace_bytes(d);
+  w = bn_layout(workspace, d);
+  if (int rc = check_layout_fits(who, w.bytes, need)) return rc;
+  return check_workspace(who, workspace, workspace_bytes, need, kBnBaseAlign);
+}
+
 }  // namespace kgcn
 
 using namespace kgcn;
@@ -239,12 +261,11 @@ extern "C" int kgcn_graph_bn_stats_f32(const float* x, int64_t graphs, int32_t n
                                        float* mean, float* var, void* workspace, int64_t workspace_bytes, void* stream) {
   if (int rc = bn_check("kgcn_graph_bn_stats_f32", x, graphs, n_nodes, d)) return rc;
   if (!mean || !var) return fail("kgcn_graph_bn_stats_f32: mean/var is NULL");
-  if (!workspace || workspace_bytes < kgcn_graph_bn_workspace_bytes(d))
-    return fail("kgcn_graph_bn_stats_f32: workspace %lld < %lld bytes", (long long)workspace_bytes,
-                (long long)kgcn_graph_bn_workspace_bytes(d));
+  BnWorkspace w;
+  if (int rc = bn_workspace("kgcn_graph_bn_stats_f32", workspace, workspace_bytes, d, w)) return rc;
   hipStream_t s = as_stream(stream);
   const long rows = (long)graphs * n_nodes;
-  float* part = static_cast<float*>(workspace);
+  float* part = w.part0;
   int nb = bn_blocks(rows, d);
   hipLaunchKernelGGL(bn_colreduce_kernel<0>, dim3(nb), dim3(256), 0, s, x, nullptr, rows, n_nodes, d, enabled, nullptr,
                      nullptr, 0.f, part, nullptr);
@@ -318,15 +339,12 @@ static int bn_bwd_impl(const float* x, const float* grad, const float* aout, int
   if (dact != KGCN_ACT_NONE && !aout) return fail("kgcn_graph_bn_bwd_f32: act_out is NULL");
   if (int rc = bn_check("kgcn_graph_bn_bwd_f32", x, graphs, n_nodes, d)) return rc;
   if (!grad || !mean || !var || !gamma || !dgamma || !dbeta) return fail("kgcn_graph_bn_bwd_f32: NULL operand");
-  if (!workspace || workspace_bytes < kgcn_graph_bn_workspace_bytes(d))
-    return fail("kgcn_graph_bn_bwd_f32: workspace %lld < %lld bytes", (long long)workspace_bytes,
-                (long long)kgcn_graph_bn_workspace_bytes(d));
+  BnWorkspace w;
+  if (int rc = bn_workspace("kgcn_graph_bn_bwd_f32", workspace, workspace_bytes, d, w)) return rc;
   hipStream_t s = as_stream(stream);
   const long rows = (long)graphs * n_nodes;
-  float* part0 = static_cast<float*>(workspace);
-  float* part1 = part0 + (long)BN_BLOCKS * d;
-  long* count = reinterpret_cast<long*>(reinterpret_cast<char*>(workspace) +
-                                        ((((size_t)2 * BN_BLOCKS * d) * 4 + 15) & ~(size_t)15));
+  float *part0 = w.part0, *part1 = w.part1;
+  long* count = w.count;
   int nb = bn_blocks(rows, d);
   if (dx && !training) {
     // inference phase: dx does not depend on the reductions -> one pass over x and g

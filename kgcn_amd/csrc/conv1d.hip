@@ -23,7 +23,7 @@
 //             8 position classes mod 8 summed in order, then added in class order.
 // Precision: plain fp32 MFMA (an exact k-ordered fmaf chain), as dense.hip; the split-bf16 product of gemmh.hip would need the
 // staged window split per tap or held three times in LDS, and the model's widest reduction (3 x 505) is small.
-#include "kgcn_common.h"
+#include "workspace.h"
 
 namespace kgcn {
 
@@ -279,6 +279,20 @@ int wgrad_parts(int32_t B, int32_t L, int32_t Cin, int32_t k, int32_t F, int32_t
   if (parts > total) parts = total;
   return parts < 1 ? 1 : (int)parts;
 }
+
+// the flipped weights wt [k, F, Cin] | `parts` partials of d w [k, Cin, F] | `parts` partials of d bias [F]
+struct BwdWorkspace { int parts; long nw; float *wt, *part_w, *part_b; size_t bytes; };
+BwdWorkspace bwd_layout(void* base, int32_t batch, int32_t length, int32_t in_dim, int32_t kernel_size, int32_t filters, int32_t pool) {
+  Taker t(base, 4);
+  BwdWorkspace w;
+  w.parts = wgrad_parts(batch, length, in_dim, kernel_size, filters, pool);
+  w.nw = (long)kernel_size * in_dim * filters;
+  w.wt = t.take<float>((size_t)w.nw);
+  w.part_w = t.take<float>((size_t)w.parts * w.nw);
+  w.part_b = t.take<float>((size_t)w.parts * filters);
+  w.bytes = t.off;
+  return w;
+}
 }  // namespace
 }  // namespace kgcn
 
@@ -287,9 +301,7 @@ using namespace kgcn;
 extern "C" int64_t kgcn_conv1d_pool_workspace_bytes(int32_t batch, int32_t length, int32_t in_dim, int32_t kernel_size,
                                                     int32_t filters, int32_t pool) {
   if (conv_check(batch, length, in_dim, kernel_size, filters, pool, KGCN_ACT_NONE, "kgcn_conv1d_pool_workspace_bytes")) return -1;
-  const int64_t nw = (int64_t)kernel_size * in_dim * filters;
-  return ((wgrad_parts(batch, length, in_dim, kernel_size, filters, pool) + 1) * nw +
-          (int64_t)wgrad_parts(batch, length, in_dim, kernel_size, filters, pool) * filters) * 4;
+  return (int64_t)bwd_layout(nullptr, batch, length, in_dim, kernel_size, filters, pool).bytes;
 }
 
 extern "C" int kgcn_conv1d_pool_fwd_f32(const float* x, const int32_t* tokens, const float* table, int32_t symbols, int32_t batch,
@@ -325,23 +337,18 @@ extern "C" int kgcn_conv1d_pool_bwd_f32(const float* x, const int32_t* tokens, c
   if (batch > 0)
     if (int rc = source_check(x, tokens, table, symbols, who)) return rc;
   if (any && (!dout || !argmax || !out || !w)) return fail("%s: NULL operand", who);
-  const int64_t need = kgcn_conv1d_pool_workspace_bytes(batch, length, in_dim, kernel_size, filters, pool);
-  if (!workspace || workspace_bytes < need)
-    return fail("%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes, (long long)need);
+  const BwdWorkspace ws = bwd_layout(workspace, batch, length, in_dim, kernel_size, filters, pool);
+  if (int rc = check_workspace(who, workspace, workspace_bytes, (int64_t)ws.bytes)) return rc;
   hipStream_t s = as_stream(stream);
-  const long nw = (long)kernel_size * in_dim * filters;
-  const int parts = wgrad_parts(batch, length, in_dim, kernel_size, filters, pool);
-  float* wt = static_cast<float*>(workspace);
-  float* part_w = wt + nw;
-  float* part_b = part_w + (size_t)parts * nw;
+  const int parts = ws.parts;
+  float *wt = ws.wt, *part_w = ws.part_w, *part_b = ws.part_b;
   ConvArgs a = {};
   a.x = x; a.tok = tokens; a.table = table; a.dout = dout; a.arg = argmax; a.y = out;
   a.B = batch; a.L = length; a.S = symbols; a.K = filters; a.k = kernel_size; a.gpool = pool; a.act = act; a.T = T;
   if (!any) {                                        // no pooled output: zero gradients
-    if (hipMemsetAsync(part_w, 0, ((size_t)parts * nw + (size_t)parts * filters) * 4, s) != hipSuccess)
-      return fail("%s: memset failed", who);
-    if (dx && batch > 0 && hipMemsetAsync(dx, 0, (size_t)batch * length * in_dim * 4, s) != hipSuccess)
-      return fail("%s: memset failed", who);
+    if (int rc = zero_async(who, part_w, (size_t)parts * (ws.nw + filters) * 4, s)) return rc;   // part_w | part_b
+    if (dx && batch > 0)
+      if (int rc = zero_async(who, dx, (size_t)batch * length * in_dim * 4, s)) return rc;
   } else {
     if (dx) {
       hipLaunchKernelGGL(conv1d_flip_kernel, dim3((filters + 31) / 32, (in_dim + 31) / 32, kernel_size), dim3(256), 0, s, w,
@@ -363,7 +370,7 @@ extern "C" int kgcn_conv1d_pool_bwd_f32(const float* x, const int32_t* tokens, c
     if (int rc = check_launch("conv1d_wgrad_kernel")) return rc;
   }
   if (!dw) return 0;
-  if (int rc = reduce_or_defer(part_w, parts, nw, dw, s)) return rc;
+  if (int rc = reduce_or_defer(part_w, parts, ws.nw, dw, s)) return rc;
   return reduce_or_defer(part_b, parts, filters, dbias, s);
 }
 

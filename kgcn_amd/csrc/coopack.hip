@@ -216,11 +216,8 @@ extern "C" int kgcn_coo_pack_f32(const int32_t* graph, const int32_t* row, const
     return fail("kgcn_coo_pack_f32: batch too large for int32 offsets");
   if (!rowptr_out || !stats_out) return fail("kgcn_coo_pack_f32: rowptr_out / stats_out is NULL");
   hipStream_t s = as_stream(stream);
-  (void)hipMemsetAsync(stats_out, 0, 2 * sizeof(int32_t), s);
-  if (nnz == 0) {
-    (void)hipMemsetAsync(rowptr_out, 0, (size_t)(nrows + 1) * 4, s);
-    return 0;
-  }
+  if (int rc = zero_async("kgcn_coo_pack_f32", stats_out, 2 * sizeof(int32_t), s)) return rc;
+  if (nnz == 0) return zero_async("kgcn_coo_pack_f32", rowptr_out, (size_t)(nrows + 1) * 4, s);
   if (!graph || !row || !col || !cv_out) return fail("kgcn_coo_pack_f32: NULL operand");
   if (int rc = check_workspace("kgcn_coo_pack_f32", workspace, workspace_bytes, kgcn_coo_pack_workspace_bytes(nnz, num_graphs, rows, cols)))
     return rc;
@@ -263,13 +260,12 @@ extern "C" int kgcn_csr_pad4(const kgcn_csr_batch* a, int32_t* rowptr4_out, void
   if (!rowptr4_out || !graph_ptr_out || !stats_out || (a->num_graphs > 0 && a->rows > 0 && (!slots_out || !cv4_out)))
     return fail("kgcn_csr_pad4: NULL output");
   hipStream_t s = as_stream(stream);
-  (void)hipMemsetAsync(stats_out, 0, 3 * sizeof(int32_t), s);
+  if (int rc = zero_async("kgcn_csr_pad4", stats_out, 3 * sizeof(int32_t), s)) return rc;
   const int T = a->num_graphs, M = a->rows;
   const long nrows = (long)T * M;
   if (nrows == 0) {
-    (void)hipMemsetAsync(rowptr4_out, 0, 4, s);
-    (void)hipMemsetAsync(graph_ptr_out, 0, (size_t)(T + 1) * 4, s);
-    return 0;
+    if (int rc = zero_async("kgcn_csr_pad4", rowptr4_out, 4, s)) return rc;
+    return zero_async("kgcn_csr_pad4", graph_ptr_out, (size_t)(T + 1) * 4, s);
   }
   if (int rc = check_workspace("kgcn_csr_pad4", workspace, workspace_bytes, kgcn_csr_pad4_workspace_bytes(T, M))) return rc;
   Taker t{aligned_base(workspace)};
@@ -300,7 +296,7 @@ extern "C" int kgcn_csr_compact4(const kgcn_csr_batch* a4, void* cv_out, int wit
   if ((a4->nnz > 0 && !aligned16(a4->cv)) || (with_values && !aligned16(cv_out)))
     return fail("kgcn_csr_compact4: cv / cv_out not 16-byte aligned");
   hipStream_t s = as_stream(stream);
-  (void)hipMemsetAsync(stats_out, 0, 2 * sizeof(int32_t), s);
+  if (int rc = zero_async("kgcn_csr_compact4", stats_out, 2 * sizeof(int32_t), s)) return rc;
   const long groups = (long)(a4->nnz / 4);
   unsigned* cw = static_cast<unsigned*>(cv_out);
   if (groups > 0)

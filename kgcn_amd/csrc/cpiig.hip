@@ -22,7 +22,7 @@
 //   Every sum runs in one fixed order, there are no atomics, and no block works on more than one compound: the outputs are
 //   bitwise reproducible and do not depend on which compounds share a launch.
 #include "block_reduce.h"
-#include "kgcn_common.h"
+#include "workspace.h"
 
 namespace kgcn {
 
@@ -163,6 +163,17 @@ __global__ __launch_bounds__(256) void cpi_ig_accum_kernel(const float* __restri
   }
 }
 
+// the column sums S [C, K, Wd] | p (1 - p) [C, K, T]
+struct IgWorkspace { float *S, *pq; size_t bytes; };
+IgWorkspace ig_layout(void* base, int64_t CK, int32_t width, int32_t tasks) {
+  Taker t(base, 4);
+  IgWorkspace w;
+  w.S = t.take<float>((size_t)CK * width);
+  w.pq = t.take<float>((size_t)CK * tasks);
+  w.bytes = t.off;
+  return w;
+}
+
 }  // namespace
 }  // namespace kgcn
 
@@ -170,7 +181,7 @@ using namespace kgcn;
 
 extern "C" int64_t kgcn_cpi_ig_workspace_bytes(int32_t compounds, int32_t width, int32_t tasks, int32_t steps) {
   if (compounds <= 0 || width <= 0 || tasks <= 0 || steps <= 0) return 0;
-  return (int64_t)compounds * steps * ((int64_t)width + tasks) * 4;       // S [C, K, Wd] | p (1 - p) [C, K, T]
+  return (int64_t)ig_layout(nullptr, (int64_t)compounds * steps, width, tasks).bytes;
 }
 
 extern "C" int kgcn_cpi_ig_f32(const float* P, const float* Q, int32_t compounds, int32_t nodes, int32_t width, const float* u,
@@ -184,20 +195,18 @@ extern "C" int kgcn_cpi_ig_f32(const float* P, const float* Q, int32_t compounds
   if (compounds == 0) return 0;
   if (!P || !Q || !u || !e || !alpha || !gamma || !wA || !p || !GA) return fail("%s: NULL operand", who);
   if ((wB == nullptr) != (GB == nullptr)) return fail("%s: wB and GB go together", who);
-  const int64_t need = kgcn_cpi_ig_workspace_bytes(compounds, width, tasks, steps);
-  if (!workspace || workspace_bytes < need)
-    return fail("%s: workspace of %lld bytes, %lld needed", who, (long long)workspace_bytes, (long long)need);
+  const int64_t CK = (int64_t)compounds * steps;
+  const IgWorkspace ws = ig_layout(workspace, CK, width, tasks);
+  if (int rc = check_workspace(who, workspace, workspace_bytes, (int64_t)ws.bytes)) return rc;
   const int64_t NW = (int64_t)nodes * width;
   const int jblocks = (width + 255) / 256, kblocks = (steps + kStepBlock - 1) / kStepBlock;
   const int passes = (tasks + kTaskCap - 1) / kTaskCap;
   const int64_t eblocks = (NW + 255) / 256;
-  const int64_t CK = (int64_t)compounds * steps;
   const int64_t grid_a = (int64_t)compounds * kblocks * jblocks, grid_b = (CK + 3) / 4, grid_c = (int64_t)compounds * passes * eblocks;
   if (grid_a >= INT32_MAX || grid_b >= INT32_MAX || grid_c >= INT32_MAX || eblocks >= INT32_MAX)
     return fail("%s: %d compounds of %d x %d with %d copies exceed one launch's grid: pass fewer compounds", who, compounds, nodes,
                 width, steps);
-  float* S = static_cast<float*>(workspace);
-  float* pq = S + CK * width;
+  float *S = ws.S, *pq = ws.pq;
   hipStream_t s = as_stream(stream);
   hipLaunchKernelGGL(cpi_ig_colsum_kernel, dim3((unsigned)grid_a), dim3(256), 0, s, P, Q, alpha, gamma, S, nodes, width, steps, jblocks,
                      kblocks);

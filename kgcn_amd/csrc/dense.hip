@@ -24,6 +24,7 @@
 
 #include "block_reduce.h"
 #include "dense_kernels.h"
+#include "grad_parts.h"
 
 namespace kgcn {
 
@@ -704,9 +705,8 @@ extern "C" int kgcn_dense_dx_dact_dot_f32(const float* grad, const float* act_ou
   if (ld < dout || dotx_ld < din || w_ld < dout || dotx_ld % 4 != 0 || !aligned16(dotx))
     return fail("kgcn_dense_dx_dact_dot_f32: leading dimension too small / dotx not 16-byte aligned rows");
   if (!table || table_bytes < wtable_bytes(dout, din)) return fail("kgcn_dense_dx_dact_dot_f32: table / workspace too small");
-  if (!workspace || workspace_bytes < kgcn_dense_dx_dact_dot_workspace_bytes(m, din))
-    return fail("kgcn_dense_dx_dact_dot_f32: workspace %lld < %lld bytes", (long long)workspace_bytes,
-                (long long)kgcn_dense_dx_dact_dot_workspace_bytes(m, din));
+  if (int rc = check_workspace("kgcn_dense_dx_dact_dot_f32", workspace, workspace_bytes, kgcn_dense_dx_dact_dot_workspace_bytes(m, din)))
+    return rc;
   hipStream_t s = as_stream(stream);
   float* part = static_cast<float*>(workspace);
   const int rc = launch_dx_dact_wide(grad, act_out, dpre, (long)m, dout, (long)ld, w, (long)w_ld, table, true, table_ready != 0,
@@ -716,6 +716,19 @@ extern "C" int kgcn_dense_dx_dact_dot_f32(const float* grad, const float* act_ou
   hipLaunchKernelGGL(dx_dot_final_kernel, dim3(1), dim3(256), 0, s, part, gemmh_dot_parts((long)m, din), dot_out);
   return check_launch("dx_dot_final_kernel");
 }
+
+// ---- the weight-gradient workspace (GradParts of workspace.h): nparts partials of dW [din x dout] | nparts of dbias [dout] | ndot
+// inner-product partials.  Every entry point that carves it asks for kgcn_dense_wgrad_workspace_bytes (an upper bound over the
+// routes) and refuses a plan whose layout would not fit that.
+namespace kgcn {
+static int wgrad_workspace(const char* who, void* workspace, int64_t workspace_bytes, int64_t m, int32_t din, int32_t dout, int nparts,
+                           int ndot, GradParts& w) {
+  const int64_t need = kgcn_dense_wgrad_workspace_bytes(m, din, dout);
+  w = grad_parts_layout(workspace, nparts, (long)din * dout, dout, (size_t)ndot);
+  if (int rc = check_layout_fits(who, w.bytes, need)) return rc;
+  return check_workspace(who, workspace, workspace_bytes, need);
+}
+}  // namespace kgcn
 
 // ---- one-pass backward of a wide dense layer (gemmb.hip): dX, dW and dbias from ONE sweep over (grad, act_out, x); the
 // d pre-activation tensor is never written.  The weight-gradient partials go through the same second stage as every other
@@ -741,20 +754,16 @@ extern "C" int kgcn_dense_bwd_f32(const float* grad, const float* pooled_grad, i
   if (ld < dout || x_ld < din || dx_ld < din || w_ld < dout) return fail("kgcn_dense_bwd_f32: leading dimension too small");
   if (dx == x || dx == grad || dx == act_out) return fail("kgcn_dense_bwd_f32: dx must not alias an input");
   if (!table || table_bytes < wtable_bytes(dout, din)) return fail("kgcn_dense_bwd_f32: table / workspace too small");
-  const int64_t need = kgcn_dense_wgrad_workspace_bytes(m, din, dout);
-  if (!workspace || workspace_bytes < need)
-    return fail("kgcn_dense_bwd_f32: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
+  GradParts ws;                                             // one partial per workgroup pair (launch_gemmb)
+  if (int rc = wgrad_workspace("kgcn_dense_bwd_f32", workspace, workspace_bytes, m, din, dout, kNumCU / 2, 0, ws)) return rc;
   hipStream_t s = as_stream(stream);
   if (!table_ready) launch_wtable_split(w, (long)w_ld, 1, dout, din, table, s);
-  const int pairs = kNumCU / 2;
-  float* part_dw = static_cast<float*>(workspace);
-  float* part_db = part_dw + (long)pairs * din * dout;
   const int rc = launch_gemmb(grad, act_out, (long)m, din, dout, (long)ld, x, (long)x_ld,
-                              f16_table(table, dout, din), dx, (long)dx_ld, part_dw, dbias ? part_db : nullptr, act, pooled_grad,
+                              f16_table(table, dout, din), dx, (long)dx_ld, ws.part_dw, dbias ? ws.part_db : nullptr, act, pooled_grad,
                               n_nodes, (long)pooled_ld, s, nullptr);
   if (rc == -1) return fail("kgcn_dense_bwd_f32: operands must be 16-byte aligned with ld %% 4 == 0");
   if (rc < 0) return 1;
-  return launch_reduce_pair(part_dw, (long)din * dout, dw, part_db, dout, dbias, rc, s);
+  return reduce_grad_parts(ws, rc, dw, dbias, s);
 }
 
 // the one-pass backward where the d-input product is only needed for an inner product (kgcn_dense_dx_dact_dot_f32's case): dW, dbias
@@ -770,23 +779,18 @@ extern "C" int kgcn_dense_bwd_dot_f32(const float* grad, const float* act_out, i
   if (!grad || !act_out || !x || !w || !dotx || !dw || !dot_out) return fail("kgcn_dense_bwd_dot_f32: NULL operand");
   if (ld < dout || x_ld < din || dotx_ld < din || w_ld < dout) return fail("kgcn_dense_bwd_dot_f32: leading dimension too small");
   if (!table || table_bytes < wtable_bytes(dout, din)) return fail("kgcn_dense_bwd_dot_f32: table / workspace too small");
-  const int pairs = kNumCU / 2;
-  const int64_t need = kgcn_dense_wgrad_workspace_bytes(m, din, dout);
-  if (!workspace || workspace_bytes < need || need < (int64_t)(pairs * ((int64_t)din * dout + dout) + kNumCU) * 4)
-    return fail("kgcn_dense_bwd_dot_f32: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
+  GradParts ws;                                             // ... and one inner-product partial per workgroup
+  if (int rc = wgrad_workspace("kgcn_dense_bwd_dot_f32", workspace, workspace_bytes, m, din, dout, kNumCU / 2, kNumCU, ws)) return rc;
   hipStream_t s = as_stream(stream);
   if (!table_ready) launch_wtable_split(w, (long)w_ld, 1, dout, din, table, s);
-  float* part_dw = static_cast<float*>(workspace);
-  float* part_db = part_dw + (long)pairs * din * dout;
-  float* part_dot = part_db + (long)pairs * dout;                // one partial per workgroup: kNumCU floats
   const int rc = launch_gemmb(grad, act_out, (long)m, din, dout, (long)ld, x, (long)x_ld,
-                              f16_table(table, dout, din), const_cast<float*>(dotx), (long)dotx_ld, part_dw,
-                              dbias ? part_db : nullptr, act, nullptr, 0, 0, s, part_dot);
+                              f16_table(table, dout, din), const_cast<float*>(dotx), (long)dotx_ld, ws.part_dw,
+                              dbias ? ws.part_db : nullptr, act, nullptr, 0, 0, s, ws.extra);
   if (rc == -1) return fail("kgcn_dense_bwd_dot_f32: operands must be 16-byte aligned with ld %% 4 == 0");
   if (rc < 0) return 1;
-  hipLaunchKernelGGL(dx_dot_final_kernel, dim3(1), dim3(256), 0, s, part_dot, kNumCU, dot_out);
+  hipLaunchKernelGGL(dx_dot_final_kernel, dim3(1), dim3(256), 0, s, ws.extra, kNumCU, dot_out);
   if (int rc2 = check_launch("dx_dot_final_kernel")) return rc2;
-  return launch_reduce_pair(part_dw, (long)din * dout, dw, part_db, dout, dbias, rc, s);
+  return reduce_grad_parts(ws, rc, dw, dbias, s);
 }
 
 extern "C" int kgcn_dense_dx_dact_f32(const float* grad, const float* act_out, int64_t m, int32_t dout, int64_t ld,
@@ -948,19 +952,17 @@ static int dense_wgrad_impl(const float* x, int64_t x_ld, const float* dy, int64
   if (!dw && !dbias) return 0;
   hipStream_t s = as_stream(stream);
   if (m == 0) {
-    if (dw) (void)hipMemsetAsync(dw, 0, (size_t)din * dout * 4, s);
-    if (dbias) (void)hipMemsetAsync(dbias, 0, (size_t)dout * 4, s);
-    return 0;
+    if (dw)
+      if (int rc = zero_async("kgcn_dense_wgrad_f32", dw, (size_t)din * dout * 4, s)) return rc;
+    return dbias ? zero_async("kgcn_dense_wgrad_f32", dbias, (size_t)dout * 4, s) : 0;
   }
   if (!x || !dy) return fail("kgcn_dense_wgrad_f32: NULL operand");
-  const int64_t need = kgcn_dense_wgrad_workspace_bytes(m, din, dout);
-  if (!workspace || workspace_bytes < need)
-    return fail("kgcn_dense_wgrad_f32: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
   const long M = (long)m, xl = (long)x_ld, gl = (long)dy_ld;
   const WgradPlan plan = wgrad_route(M, din, dout, yact != nullptr, RowFacts{aligned16(x), xl, aligned16(dy), gl});
   const int np = plan.nparts;
-  float* part_dw = static_cast<float*>(workspace);
-  float* part_db = part_dw + (long)np * din * dout;
+  GradParts ws;
+  if (int rc = wgrad_workspace("kgcn_dense_wgrad_f32", workspace, workspace_bytes, m, din, dout, np, 0, ws)) return rc;
+  float *part_dw = ws.part_dw, *part_db = ws.part_db;
   int rc = 0;
   switch (plan.route) {
     case WgradRoute::Skinny: rc = launch_skinny_n_wgrad(x, M, din, xl, dy, gl, dout, part_dw, part_db, np, s); break;
@@ -971,7 +973,7 @@ static int dense_wgrad_impl(const float* x, int64_t x_ld, const float* dy, int64
     case WgradRoute::Narrow: rc = launch_narrow_wgrad(x, dy, M, din, dout, part_dw, part_db, np, s); break;
     case WgradRoute::Persist: rc = launch_wgrad_persist(x, xl, dy, gl, M, din, dout, part_dw, part_db, np, s); break;
   }
-  return rc ? rc : launch_reduce_pair(part_dw, (long)din * dout, dw, part_db, dout, dbias, np, s);
+  return rc ? rc : reduce_grad_parts(ws, np, dw, dbias, s);
 }
 
 extern "C" int kgcn_dense_wgrad_f32(const float* x, int64_t x_ld, const float* dy, int64_t dy_ld,

@@ -27,7 +27,7 @@
 // kgcn_dense_* + kgcn_bconv_f32.
 #include <type_traits>
 
-#include "kgcn_common.h"
+#include "grad_parts.h"
 #include "kgcn_probe.h"
 
 namespace kgcn {
@@ -2511,9 +2511,8 @@ extern "C" int kgcn_graphconv_bwd_f32(const kgcn_csr_batch* at, const float* x, 
   if (!dw || !dbias) return fail("kgcn_graphconv_bwd_f32: dw/dbias is NULL");
   hipStream_t s = as_stream(stream);
   if (at->num_graphs == 0) {
-    (void)hipMemsetAsync(dw, 0, (size_t)din * dout * 4, s);
-    (void)hipMemsetAsync(dbias, 0, (size_t)dout * 4, s);
-    return 0;
+    if (int rc = zero_async("kgcn_graphconv_bwd_f32", dw, (size_t)din * dout * 4, s)) return rc;
+    return zero_async("kgcn_graphconv_bwd_f32", dbias, (size_t)dout * 4, s);
   }
   if (!x || !w || !dout_grad) return fail("kgcn_graphconv_bwd_f32: NULL operand");
   const bool vec = !(din & 3) && !(dout & 3);
@@ -2532,12 +2531,11 @@ extern "C" int kgcn_graphconv_bwd_f32(const kgcn_csr_batch* at, const float* x, 
   if (is_compact(at) && !pairs)
     return fail("kgcn_graphconv_bwd_f32: the compact adjacency layout is read by the pairs kernel only (T=%d N=%d din=%d "
                 "dout=%d, dx %s): pass the row-padded batch", at->num_graphs, at->rows, din, dout, dx ? "wanted" : "NULL");
-  const int64_t need = (int64_t)blocks * ((int64_t)din * dout + dout) * 4;
-  if (!workspace || workspace_bytes < need)
-    return fail("kgcn_graphconv_bwd_f32: workspace %lld < %lld bytes", (long long)workspace_bytes,
-                (long long)need);
-  float* part_dw = static_cast<float*>(workspace);
-  float* part_db = part_dw + (long)blocks * din * dout;
+  const GradParts ws = grad_parts_layout(workspace, blocks, (long)din * dout, dout);   // one partial of each per workgroup
+  if (int rc = check_layout_fits("kgcn_graphconv_bwd_f32", ws.bytes, kgcn_graphconv_bwd_workspace_bytes(at->num_graphs, din, dout)))
+    return rc;
+  if (int rc = check_workspace("kgcn_graphconv_bwd_f32", workspace, workspace_bytes, (int64_t)ws.bytes)) return rc;
+  float *part_dw = ws.part_dw, *part_db = ws.part_db;
   const size_t lds = full ? full_lds : FD * FD * 4 + (size_t)wpb * per;
   const int2* cv = reinterpret_cast<const int2*>(at->cv);
   const int lay = lay_of(at);
@@ -2567,5 +2565,5 @@ extern "C" int kgcn_graphconv_bwd_f32(const kgcn_csr_batch* at, const float* x, 
     });
   if (rc) return rc;
   if ((rc = check_launch("graphconv_bwd_kernel"))) return rc;
-  return launch_reduce_pair(part_dw, (long)din * dout, dw, part_db, dout, dbias, blocks, s);      // (queued inside a deferral scope)
+  return reduce_grad_parts(ws, blocks, dw, dbias, s);      // (queued inside a deferral scope)
 }

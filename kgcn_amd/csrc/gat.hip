@@ -7,7 +7,7 @@
 // The reference builds this with one-hot matmuls per graph (O(N * nnz * D)); here it is three / six small
 // CSR-vector kernels (lane group per row, gathers through L1/L2), all quantities per NODE (u, v, denom,
 // d denom, du, dv) in a caller-provided workspace, no atomics: sums grouped by column walk the A^T container.
-#include "kgcn_common.h"
+#include "workspace.h"
 
 namespace kgcn {
 
@@ -198,34 +198,44 @@ constexpr int kGatDotBlocks = 512;
 
 using namespace kgcn;
 
-extern "C" int64_t kgcn_gat_workspace_bytes(int32_t num_graphs, int32_t n_nodes, int32_t d) {
-  if (num_graphs <= 0 || n_nodes <= 0 || d <= 0) return 0;
-  const int64_t nodes = (int64_t)num_graphs * n_nodes;
-  // u, v, denom, ddenom, du1, du, dv | dr [nodes x d] | d wa partials
-  return (7 * nodes + nodes * d + (int64_t)kGatDotBlocks * 2 * d) * 4;
+// per node: u, v, denom (forward and backward) | ddenom, du1, du, dv | dr [nodes x d] | d wa partials [kGatDotBlocks x 2d]
+struct GatWorkspace { float *u, *v, *denom, *ddenom, *du1, *du, *dv, *dr, *part; size_t bytes; };
+static GatWorkspace gat_layout(void* base, int64_t nodes, int32_t d) {
+  Taker t(base, 4);
+  GatWorkspace w;
+  for (float** p : {&w.u, &w.v, &w.denom, &w.ddenom, &w.du1, &w.du, &w.dv}) *p = t.take<float>((size_t)nodes);
+  w.dr = t.take<float>((size_t)nodes * d);
+  w.part = t.take<float>((size_t)kGatDotBlocks * 2 * d);
+  w.bytes = t.off;
+  return w;
 }
 
-static int gat_check(const kgcn_csr_batch* a, const char* who, int d, const void* ws, int64_t ws_bytes) {
+extern "C" int64_t kgcn_gat_workspace_bytes(int32_t num_graphs, int32_t n_nodes, int32_t d) {
+  if (num_graphs <= 0 || n_nodes <= 0 || d <= 0) return 0;
+  return (int64_t)gat_layout(nullptr, (int64_t)num_graphs * n_nodes, d).bytes;
+}
+
+static int gat_check(const kgcn_csr_batch* a, const char* who, int d, void* ws, int64_t ws_bytes, GatWorkspace& w) {
   if (int rc = validate_csr(a, who)) return rc;
   if (a->rows != a->cols) return fail("%s: adjacency must be square", who);
   if (d <= 0) return fail("%s: d=%d", who, d);
   const int64_t need = kgcn_gat_workspace_bytes(a->num_graphs, a->rows, d);
-  if (need > 0 && (!ws || ws_bytes < need))
-    return fail("%s: workspace %lld < %lld bytes", who, (long long)ws_bytes, (long long)need);
+  if (need > 0)
+    if (int rc = check_workspace(who, ws, ws_bytes, need)) return rc;
+  w = gat_layout(ws, (int64_t)a->num_graphs * a->rows, d);
   return 0;
 }
 
 extern "C" int kgcn_gat_fwd_f32(const kgcn_csr_batch* a, const float* x, int32_t d, const float* weight_a,
                                 float* out, float beta, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (int rc = gat_check(a, "kgcn_gat_fwd_f32", d, workspace, workspace_bytes)) return rc;
+  GatWorkspace w;
+  if (int rc = gat_check(a, "kgcn_gat_fwd_f32", d, workspace, workspace_bytes, w)) return rc;
   if (a->num_graphs == 0 || a->rows == 0) return 0;
   if (!x || !weight_a || !out) return fail("kgcn_gat_fwd_f32: NULL operand");
   if (beta != 0.f && beta != 1.f) return fail("kgcn_gat_fwd_f32: beta must be 0 or 1");
   hipStream_t s = as_stream(stream);
   const long nodes = (long)a->num_graphs * a->rows;
-  float* u = static_cast<float*>(workspace);
-  float* v = u + nodes;
-  float* denom = v + nodes;
+  float *u = w.u, *v = w.v, *denom = w.denom;
   const int2* cv = reinterpret_cast<const int2*>(a->cv);
   const int lg = ilog2c(d);
   hipLaunchKernelGGL(gat_scores_kernel, dim3(row_blocks(nodes, lg)), dim3(256), 0, s, x, weight_a, u, v, nodes, d, lg);
@@ -239,28 +249,20 @@ extern "C" int kgcn_gat_fwd_f32(const kgcn_csr_batch* a, const float* x, int32_t
 extern "C" int kgcn_gat_bwd_f32(const kgcn_csr_batch* a, const kgcn_csr_batch* at, const float* x, int32_t d,
                                 const float* weight_a, const float* dout_grad, float* dx, float beta,
                                 float* dweight_a, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (int rc = gat_check(a, "kgcn_gat_bwd_f32", d, workspace, workspace_bytes)) return rc;
+  GatWorkspace w;
+  if (int rc = gat_check(a, "kgcn_gat_bwd_f32", d, workspace, workspace_bytes, w)) return rc;
   if (int rc = validate_csr(at, "kgcn_gat_bwd_f32")) return rc;
   if (at->num_graphs != a->num_graphs || at->rows != a->cols || at->cols != a->rows || at->nnz != a->nnz)
     return fail("kgcn_gat_bwd_f32: `at` is not the transposed batch of `a`");
   if (!dweight_a) return fail("kgcn_gat_bwd_f32: dweight_a is NULL");
   hipStream_t s = as_stream(stream);
   if (a->num_graphs == 0 || a->rows == 0) {
-    (void)hipMemsetAsync(dweight_a, 0, (size_t)2 * d * 4, s);
-    return 0;
+    return zero_async("kgcn_gat_bwd_f32", dweight_a, (size_t)2 * d * 4, s);
   }
   if (!x || !weight_a || !dout_grad || !dx) return fail("kgcn_gat_bwd_f32: NULL operand");
   if (beta != 0.f && beta != 1.f) return fail("kgcn_gat_bwd_f32: beta must be 0 or 1");
   const long nodes = (long)a->num_graphs * a->rows;
-  float* u = static_cast<float*>(workspace);
-  float* v = u + nodes;
-  float* denom = v + nodes;
-  float* ddenom = denom + nodes;
-  float* du1 = ddenom + nodes;
-  float* du = du1 + nodes;
-  float* dv = du + nodes;
-  float* dr = dv + nodes;
-  float* part = dr + nodes * d;
+  float *u = w.u, *v = w.v, *denom = w.denom, *ddenom = w.ddenom, *du1 = w.du1, *du = w.du, *dv = w.dv, *dr = w.dr, *part = w.part;
   const int2* cv = reinterpret_cast<const int2*>(a->cv);
   const int2* cvt = reinterpret_cast<const int2*>(at->cv);
   const int lg = ilog2c(d);

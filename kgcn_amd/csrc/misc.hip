@@ -2,7 +2,7 @@
 // GraphGather (kgcn/layers.py:163-164) forward/backward, also into / out of a column block of a wider
 // buffer, and the dot product behind d eps of GINAggregate (kgcn/layers.py:469).
 #include "block_reduce.h"
-#include "kgcn_common.h"
+#include "workspace.h"
 
 namespace kgcn {
 
@@ -344,13 +344,9 @@ extern "C" int kgcn_dot_f32(const float* a, const float* b, int64_t n, float* ou
   if (n < 0) return fail("kgcn_dot_f32: n < 0");
   if (!out) return fail("kgcn_dot_f32: out is NULL");
   hipStream_t s = as_stream(stream);
-  if (n == 0) {
-    (void)hipMemsetAsync(out, 0, 4, s);
-    return 0;
-  }
+  if (n == 0) return zero_async("kgcn_dot_f32", out, 4, s);
   if (!a || !b) return fail("kgcn_dot_f32: NULL operand");
-  if (!workspace || workspace_bytes < kgcn_dot_workspace_bytes(n))
-    return fail("kgcn_dot_f32: workspace too small");
+  if (int rc = check_workspace("kgcn_dot_f32", workspace, workspace_bytes, kgcn_dot_workspace_bytes(n))) return rc;
   long blocks = (n + 255) / 256;
   if (blocks > kDotBlocks) blocks = kDotBlocks;
   float* part = static_cast<float*>(workspace);
@@ -463,18 +459,14 @@ extern "C" int kgcn_gram_bwd_f32(const float* x, int32_t num_graphs, int32_t n_n
                                  int64_t workspace_bytes, void* stream) {
   if (num_graphs < 0 || n_nodes <= 0 || d <= 0) return kgcn::fail("kgcn_gram_bwd_f32: bad shape");
   hipStream_t s = kgcn::as_stream(stream);
-  if (num_graphs == 0) {
-    if (dw) (void)hipMemsetAsync(dw, 0, (size_t)d * 4, s);
-    return 0;
-  }
+  if (num_graphs == 0) return dw ? kgcn::zero_async("kgcn_gram_bwd_f32", dw, (size_t)d * 4, s) : 0;
   if (!x || !dout_grad || !dx) return kgcn::fail("kgcn_gram_bwd_f32: NULL operand");
   if (beta != 0.f && beta != 1.f) return kgcn::fail("kgcn_gram_bwd_f32: beta must be 0 or 1");
   const size_t lds = gram_lds(n_nodes, d, true);
   if (lds > (size_t)kgcn::kLdsBytes) return kgcn::fail("kgcn_gram_bwd_f32: graph tile %d x %d does not fit LDS", n_nodes, d);
   const int blocks = num_graphs < 512 ? num_graphs : 512;
-  if (dw && (!workspace || workspace_bytes < (int64_t)blocks * d * 4))
-    return kgcn::fail("kgcn_gram_bwd_f32: workspace %lld < %lld bytes", (long long)workspace_bytes,
-                      (long long)blocks * d * 4);
+  if (dw)
+    if (int rc = kgcn::check_workspace("kgcn_gram_bwd_f32", workspace, workspace_bytes, (int64_t)blocks * d * 4)) return rc;
   if (int rc = kgcn::allow_full_lds<kgcn::gram_bwd_kernel>(0, "gram_bwd_kernel")) return rc;
   float* part = dw ? static_cast<float*>(workspace) : nullptr;
   hipLaunchKernelGGL(kgcn::gram_bwd_kernel, dim3(blocks), dim3(256), lds, s, x, w, dout_grad, dx, part, num_graphs,

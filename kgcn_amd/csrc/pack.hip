@@ -11,7 +11,7 @@
 //                            coalesced), slot table slice; writes graph_ptr
 // A row-padded source (row_pad = 4) yields a row-padded batch; its dummy graphs are synthesised (every row
 // = 4 padding entries), exactly what BatchedCSR.padded4() builds for an empty graph.
-#include "kgcn_common.h"
+#include "workspace.h"
 
 namespace kgcn {
 
@@ -242,14 +242,11 @@ extern "C" int kgcn_csr_gather_graphs(const kgcn_csr_batch* src, const int32_t* 
     return fail("kgcn_csr_gather_graphs: T*M exceeds int32 row indexing");
   hipStream_t s = as_stream(stream);
   if (num_sel == 0) {                                  // empty batch: rowptr = [0], graph_ptr = [0]
-    hipError_t e = hipMemsetAsync(dst_rowptr, 0, 4, s);
-    if (e == hipSuccess) e = hipMemsetAsync(dst_graph_ptr, 0, 4, s);
-    return e == hipSuccess ? 0 : fail("kgcn_csr_gather_graphs: memset failed: %s", hipGetErrorString(e));
+    if (int rc = zero_async("kgcn_csr_gather_graphs", dst_rowptr, 4, s)) return rc;
+    return zero_async("kgcn_csr_gather_graphs", dst_graph_ptr, 4, s);
   }
   if (!sel) return fail("kgcn_csr_gather_graphs: sel is NULL");
-  const int64_t need = kgcn_csr_gather_workspace_bytes(num_sel);
-  if (!workspace || workspace_bytes < need)
-    return fail("kgcn_csr_gather_graphs: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
+  if (int rc = check_workspace("kgcn_csr_gather_graphs", workspace, workspace_bytes, kgcn_csr_gather_workspace_bytes(num_sel))) return rc;
   // dst_cv holds dst_cv_capacity entries: the exact total (the caller knows every graph's entry count) or
   // the worst case num_sel * max(max_nnz_per_graph, 4*rows for dummy graphs of a row-padded batch)
   if (dst_cv_capacity < 0 || (dst_cv_capacity > 0 && !dst_cv))
@@ -322,17 +319,14 @@ extern "C" int kgcn_batch_assemble(const kgcn_assemble_plan* plan, const int32_t
   hipStream_t s = as_stream(stream);
   if (num_sel == 0) {
     for (int c = 0; c < plan->num_csr; ++c) {
-      hipError_t e = hipMemsetAsync(plan->dst_rowptr[c], 0, 4, s);
-      if (e == hipSuccess) e = hipMemsetAsync(plan->dst_graph_ptr[c], 0, 4, s);
-      if (e != hipSuccess) return fail("kgcn_batch_assemble: memset failed: %s", hipGetErrorString(e));
+      if (int rc = zero_async("kgcn_batch_assemble", plan->dst_rowptr[c], 4, s)) return rc;
+      if (int rc = zero_async("kgcn_batch_assemble", plan->dst_graph_ptr[c], 4, s)) return rc;
     }
     return 0;
   }
   if (!sel) return fail("kgcn_batch_assemble: sel is NULL");
   if (plan->num_csr + plan->num_tables == 0) return 0;
-  const int64_t need = kgcn_batch_assemble_workspace_bytes(num_sel);
-  if (!workspace || workspace_bytes < need)
-    return fail("kgcn_batch_assemble: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
+  if (int rc = check_workspace("kgcn_batch_assemble", workspace, workspace_bytes, kgcn_batch_assemble_workspace_bytes(num_sel))) return rc;
   int* block_sums = static_cast<int*>(workspace);
   if (plan->num_csr > 0) {
     hipLaunchKernelGGL(assemble_count_kernel, dim3(p.nb, plan->num_csr), dim3(kScanBlock), 0, s, p, sel, num_sel, block_sums);

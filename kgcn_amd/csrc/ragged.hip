@@ -24,7 +24,7 @@
 //   ragged_csr_kernel     one wave per graph: re-based rowptr slice, cv slice with global columns; tail rows
 //   ragged_rows_kernel    one wave per graph: its n_t x d feature rows are ONE contiguous run in source and destination
 //   ragged_gather_*       GraphGather over graph_ptr with the padding multiplicity
-#include "kgcn_common.h"
+#include "workspace.h"
 
 namespace kgcn {
 
@@ -408,16 +408,15 @@ extern "C" int kgcn_ragged_plan(const kgcn_csr_batch* src, const int32_t* sizes,
   if (src->rows != src->cols) return fail("kgcn_ragged_plan: adjacency must be square (M=%d K=%d)", src->rows, src->cols);
   hipStream_t s = as_stream(stream);
   if (num_sel == 0) {
-    hipError_t e = hipMemsetAsync(graph_ptr, 0, 4, s);
-    if (e == hipSuccess) e = hipMemsetAsync(entry_ptr, 0, 4, s);
-    return e == hipSuccess ? 0 : fail("kgcn_ragged_plan: memset failed: %s", hipGetErrorString(e));
+    if (int rc = zero_async("kgcn_ragged_plan", graph_ptr, 4, s)) return rc;
+    return zero_async("kgcn_ragged_plan", entry_ptr, 4, s);
   }
   if (!sizes) return fail("kgcn_ragged_plan: sizes is NULL");
   if (!sel && num_sel != src->num_graphs)
     return fail("kgcn_ragged_plan: sel is NULL (identity) but num_sel=%d != %d graphs", num_sel, src->num_graphs);
-  const int64_t need = kgcn_ragged_workspace_bytes(num_sel);
-  if (!workspace || workspace_bytes < need)
-    return fail("kgcn_ragged_plan: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
+  // one int2 of block sums per scan block: stored and loaded as 8-byte words
+  if (int rc = check_workspace("kgcn_ragged_plan", workspace, workspace_bytes, kgcn_ragged_workspace_bytes(num_sel), alignof(int2)))
+    return rc;
   const int nb = (num_sel + kRScan - 1) / kRScan;
   int2* bs = static_cast<int2*>(workspace);
   hipLaunchKernelGGL(ragged_plan_count_kernel, dim3(nb), dim3(kRScan), 0, s, src->rowptr, sizes, sel, num_sel, src->rows,
@@ -581,9 +580,8 @@ extern "C" int kgcn_ragged_gather_bwd_f32(const float* dout_grad, const int32_t*
   if (pad_row < 0 || pad_row >= capacity_rows) return fail("kgcn_ragged_gather_bwd_f32: pad_row outside the capacity");
   if (!graph_ptr || !dx || (!dout_grad && batch > 0)) return fail("kgcn_ragged_gather_bwd_f32: NULL operand");
   if (batch >= INT32_MAX) return fail("kgcn_ragged_gather_bwd_f32: batch too large");
-  if (!workspace || workspace_bytes < kgcn_ragged_gather_bwd_workspace_bytes(d))
-    return fail("kgcn_ragged_gather_bwd_f32: workspace %lld < %lld bytes", (long long)workspace_bytes,
-                (long long)kgcn_ragged_gather_bwd_workspace_bytes(d));
+  if (int rc = check_workspace("kgcn_ragged_gather_bwd_f32", workspace, workspace_bytes, kgcn_ragged_gather_bwd_workspace_bytes(d)))
+    return rc;
   hipStream_t s = as_stream(stream);
   hipLaunchKernelGGL(ragged_gather_bwd_kernel, dim3(grid_cap((batch > 0 ? batch : 1) * kWave, (long)kNumCU * 32)), dim3(256),
                      0, s, dout_grad, graph_ptr, (int)batch, d, capacity_rows, dx);

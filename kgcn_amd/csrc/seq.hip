@@ -24,7 +24,7 @@
 //              stream keyed by (seed, compound, sample, position, column), so the noisy input is never written either.
 // Every second stage is a parameter gradient and goes through reduce_or_defer (kgcn_reduce_defer).  No float atomics: results
 // are bitwise reproducible.
-#include "kgcn_common.h"
+#include "workspace.h"
 #include "philox.h"
 
 namespace kgcn {
@@ -661,6 +661,30 @@ long wgrad_rows_per_chunk(const LstmArgs& a) {
   long per = (rows + kLstmChunks - 1) / kLstmChunks;
   return per < 1 ? 1 : per;
 }
+
+// `parts` partial results of each gradient, one array after the other; n[i] is the length of one partial of array i
+struct PartWorkspace { int parts; float* part[3]; long n[3]; size_t bytes; };
+PartWorkspace part_layout(void* base, int parts, long n0, long n1, long n2) {
+  Taker t(base, 4);
+  PartWorkspace w{parts, {}, {n0, n1, n2}, 0};
+  for (int i = 0; i < 3; ++i) w.part[i] = t.take<float>((size_t)parts * w.n[i]);
+  w.bytes = t.off;
+  return w;
+}
+// conv-pool backward: d W [k, E, F] | d bias [F] | d table [S, E], one partial per workgroup of the grid
+PartWorkspace convpool_bwd_layout(void* base, const ConvArgs& a) {
+  return part_layout(base, convpool_bwd_grid(a), (long)a.k * a.E * a.F, a.F, (long)a.S * a.E);
+}
+// LSTM weight gradients: d W_x [D, 4H] | d W_h [H, 4H] | d bias [4H], one partial per row chunk
+PartWorkspace lstm_wgrad_layout(void* base, int32_t in_dim, int32_t units) {
+  return part_layout(base, kLstmChunks, (long)in_dim * 4 * units, (long)units * 4 * units, 4L * units);
+}
+int reduce_parts(const PartWorkspace& w, float* out0, float* out1, float* out2, hipStream_t s) {
+  float* out[3] = {out0, out1, out2};
+  for (int i = 0; i < 3; ++i)
+    if (int rc = reduce_or_defer(w.part[i], w.parts, w.n[i], out[i], s)) return rc;
+  return 0;
+}
 }  // namespace
 }  // namespace kgcn
 
@@ -671,8 +695,7 @@ extern "C" int64_t kgcn_seq_convpool_workspace_bytes(int32_t batch, int32_t leng
   ConvArgs a;
   if (conv_args(nullptr, 0, length, nullptr, symbols, embed_dim, nullptr, kernel_size, filters, pool, "workspace", a)) return -1;
   a.tiles = (long)(batch > 0 ? batch : 0) * ((a.T + kTile - 1) / kTile);
-  const long grid = convpool_bwd_grid(a);
-  return (int64_t)grid * ((long)kernel_size * embed_dim * filters + filters + (long)symbols * embed_dim) * 4;
+  return (int64_t)convpool_bwd_layout(nullptr, a).bytes;
 }
 
 extern "C" int kgcn_seq_convpool_fwd_f32(const int32_t* tokens, int32_t batch, int32_t length, const float* table, int32_t symbols,
@@ -695,16 +718,13 @@ extern "C" int kgcn_seq_convpool_bwd_f32(const int32_t* tokens, int32_t batch, i
   if (int rc = conv_args(tokens, batch, length, table, symbols, embed_dim, w, kernel_size, filters, pool, who, a)) return rc;
   if (!dtable || !dw || !dbias) return fail("%s: NULL gradient", who);
   if (a.tiles > 0 && (!dout || !argmax)) return fail("%s: NULL operand", who);
-  const int64_t need = kgcn_seq_convpool_workspace_bytes(batch, length, symbols, embed_dim, kernel_size, filters, pool);
-  if (!workspace || workspace_bytes < need)
-    return fail("%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes, (long long)need);
+  const PartWorkspace ws = convpool_bwd_layout(workspace, a);
+  if (int rc = check_workspace(who, workspace, workspace_bytes, (int64_t)ws.bytes)) return rc;
   hipStream_t s = as_stream(stream);
-  const int grid = convpool_bwd_grid(a);
-  float* part_w = static_cast<float*>(workspace);
-  float* part_b = part_w + (size_t)grid * kernel_size * embed_dim * filters;
-  float* part_t = part_b + (size_t)grid * filters;
+  const int grid = ws.parts;
+  float *part_w = ws.part[0], *part_b = ws.part[1], *part_t = ws.part[2];
   if (a.tiles == 0) {                                 // no pooled output: zero gradients (the partials are zeroed and reduced)
-    if (hipMemsetAsync(workspace, 0, need, s) != hipSuccess) return fail("%s: memset failed", who);
+    if (int rc = zero_async(who, workspace, ws.bytes, s)) return rc;
   } else {
     const bool in_lds = convpool_bwd_lds(a, true) <= (size_t)kLdsBytes;
     const size_t lds = convpool_bwd_lds(a, in_lds);
@@ -717,9 +737,7 @@ extern "C" int kgcn_seq_convpool_bwd_f32(const int32_t* tokens, int32_t batch, i
     }
     if (int rc = check_launch("convpool_bwd_kernel")) return rc;
   }
-  if (int rc = reduce_or_defer(part_w, grid, (long)kernel_size * embed_dim * filters, dw, s)) return rc;
-  if (int rc = reduce_or_defer(part_b, grid, filters, dbias, s)) return rc;
-  return reduce_or_defer(part_t, grid, (long)symbols * embed_dim, dtable, s);
+  return reduce_parts(ws, dw, dbias, dtable, s);
 }
 
 extern "C" int kgcn_seq_convpool_scaled_fwd_f32(const int32_t* tokens, int32_t batch, int32_t rep, const float* scale, int32_t length,
@@ -775,7 +793,7 @@ extern "C" int64_t kgcn_seq_lstm_stash_floats(int32_t batch, int32_t steps, int3
 
 extern "C" int64_t kgcn_seq_lstm_workspace_bytes(int32_t batch, int32_t steps, int32_t in_dim, int32_t units) {
   (void)batch; (void)steps;
-  return (int64_t)kLstmChunks * ((int64_t)in_dim + units + 1) * 4 * units * 4;
+  return (int64_t)lstm_wgrad_layout(nullptr, in_dim, units).bytes;
 }
 
 extern "C" int kgcn_seq_lstm_fwd_f32(const float* x, int32_t batch, int32_t steps, int32_t in_dim, const float* wx, const float* wh,
@@ -802,6 +820,12 @@ extern "C" int kgcn_seq_lstm_bwd_f32(const float* x, int32_t batch, int32_t step
   if (int rc = lstm_args(x, batch, steps, in_dim, wx, wh, bias, units, recurrent_act, who, a)) return rc;
   if (dh && dh_ld < units) return fail("%s: gradient row stride %lld < %d", who, (long long)dh_ld, units);
   if (batch > 0 && steps > 0 && !stash) return fail("%s: NULL stash", who);
+  // the weight gradients' refusals come before the first launch: a refused call has written nothing
+  const bool wgrad = dwx || dwh || dbias;
+  if (wgrad && (!dwx || !dwh || !dbias)) return fail("%s: d W_x, d W_h and d bias are formed together", who);
+  const PartWorkspace ws = lstm_wgrad_layout(wgrad ? workspace : nullptr, in_dim, units);
+  if (wgrad)
+    if (int rc = check_workspace(who, workspace, workspace_bytes, (int64_t)ws.bytes)) return rc;
   hipStream_t s = as_stream(stream);
   const int N4 = 4 * units;
   if (batch > 0 && steps > 0) {
@@ -810,25 +834,16 @@ extern "C" int kgcn_seq_lstm_bwd_f32(const float* x, int32_t batch, int32_t step
     hipLaunchKernelGGL(lstm_bwd_kernel, dim3((batch + a.seqs - 1) / a.seqs), dim3(256), lds, s, a, dh, (long)dh_ld, stash, dx);
     if (int rc = check_launch("lstm_bwd_kernel")) return rc;
   }
-  if (!dwx && !dwh && !dbias) return 0;
-  if (!dwx || !dwh || !dbias) return fail("%s: d W_x, d W_h and d bias are formed together", who);
-  const int64_t need = kgcn_seq_lstm_workspace_bytes(batch, steps, in_dim, units);
-  if (!workspace || workspace_bytes < need)
-    return fail("%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes, (long long)need);
-  float* part_x = static_cast<float*>(workspace);
-  float* part_h = part_x + (size_t)kLstmChunks * in_dim * N4;
-  float* part_b = part_h + (size_t)kLstmChunks * units * N4;
+  if (!wgrad) return 0;
   const long rows = (long)batch * steps;
   if (rows == 0) {
-    if (hipMemsetAsync(workspace, 0, need, s) != hipSuccess) return fail("%s: memset failed", who);
+    if (int rc = zero_async(who, workspace, ws.bytes, s)) return rc;
   } else {
     const long per = wgrad_rows_per_chunk(a);
     const int ktiles = (in_dim + units + 1 + kWgK - 1) / kWgK;
     hipLaunchKernelGGL(lstm_wgrad_kernel, dim3(kLstmChunks, ktiles), dim3(N4 <= 64 ? 64 : (N4 <= 128 ? 128 : 256)), 0, s, a, stash,
-                       rows, per, part_x, part_h, part_b);
+                       rows, per, ws.part[0], ws.part[1], ws.part[2]);
     if (int rc = check_launch("lstm_wgrad_kernel")) return rc;
   }
-  if (int rc = reduce_or_defer(part_x, kLstmChunks, (long)in_dim * N4, dwx, s)) return rc;
-  if (int rc = reduce_or_defer(part_h, kLstmChunks, (long)units * N4, dwh, s)) return rc;
-  return reduce_or_defer(part_b, kLstmChunks, N4, dbias, s);
+  return reduce_parts(ws, dwx, dwh, dbias, s);
 }

@@ -35,7 +35,7 @@
 //                            forward / adjoint (profiles/r04_spmm_block.txt)
 //   KGCN_SPMM_NO_SLICE_WAVES round 5: one workgroup per 32-column slice instead of spmm_slices_kernel: traffic x 1.109 against
 //                            x 1.028 of the algorithmic bytes (profiles/r05_headline_experiments.txt)
-#include "kgcn_common.h"
+#include "workspace.h"
 
 namespace kgcn {
 
@@ -1569,13 +1569,13 @@ extern "C" int kgcn_gin_aggregate_bwd_f32(const kgcn_csr_batch* at_ch, int32_t n
   hipStream_t s = as_stream(stream);
   const int T = at_ch[0].num_graphs, N = at_ch[0].rows;
   if (T == 0 || N == 0 || d == 0) {
-    if (deps) (void)hipMemsetAsync(deps, 0, 4, s);
-    return 0;
+    return deps ? zero_async("kgcn_gin_aggregate_bwd_f32", deps, 4, s) : 0;
   }
   if (!grad || (!dx && !deps)) return fail("kgcn_gin_aggregate_bwd_f32: NULL operand");
-  if (deps && (!x || !workspace || workspace_bytes < kgcn_gin_aggregate_bwd_workspace_bytes(T, N, d)))
-    return fail("kgcn_gin_aggregate_bwd_f32: d eps needs x and a workspace of %lld bytes",
-                (long long)kgcn_gin_aggregate_bwd_workspace_bytes(T, N, d));
+  if (deps && !x) return fail("kgcn_gin_aggregate_bwd_f32: d eps needs x");
+  if (deps)
+    if (int rc = check_workspace("kgcn_gin_aggregate_bwd_f32", workspace, workspace_bytes, kgcn_gin_aggregate_bwd_workspace_bytes(T, N, d)))
+      return rc;
   const long gs = (long)N * d;
   bool dot_done = false;
   if (dx) {
@@ -1626,9 +1626,20 @@ extern "C" int kgcn_graph_maxpool_fwd_f32(const kgcn_csr_batch* a, const float* 
   return check_launch("maxpool_fwd_kernel");
 }
 
+// per element of x [T, rows, d]: the maximum over the row's neighbours | 1 / the number of neighbours that attain it
+struct MaxpoolWorkspace { float *mm, *inv; size_t bytes; };
+static MaxpoolWorkspace maxpool_bwd_layout(void* base, int64_t elements) {
+  Taker t(base, 4);
+  MaxpoolWorkspace w;
+  w.mm = t.take<float>((size_t)elements);
+  w.inv = t.take<float>((size_t)elements);
+  w.bytes = t.off;
+  return w;
+}
+
 extern "C" int64_t kgcn_graph_maxpool_bwd_workspace_bytes(int32_t num_graphs, int32_t rows, int32_t d) {
   if (num_graphs <= 0 || rows <= 0 || d <= 0) return 0;
-  return (int64_t)2 * num_graphs * rows * d * 4;
+  return (int64_t)maxpool_bwd_layout(nullptr, (int64_t)num_graphs * rows * d).bytes;
 }
 
 extern "C" int kgcn_graph_maxpool_bwd_f32(const kgcn_csr_batch* a, const kgcn_csr_batch* at,
@@ -1642,12 +1653,9 @@ extern "C" int kgcn_graph_maxpool_bwd_f32(const kgcn_csr_batch* a, const kgcn_cs
   if (a->num_graphs == 0 || a->rows == 0 || a->cols == 0 || d <= 0) return 0;
   if (!x || !dout_grad || !dx) return fail("kgcn_graph_maxpool_bwd_f32: NULL operand");
   if (beta != 0.f && beta != 1.f) return fail("kgcn_graph_maxpool_bwd_f32: beta must be 0 or 1");
-  const int64_t need = kgcn_graph_maxpool_bwd_workspace_bytes(a->num_graphs, a->rows, d);
-  if (!workspace || workspace_bytes < need)
-    return fail("kgcn_graph_maxpool_bwd_f32: workspace %lld < %lld bytes", (long long)workspace_bytes,
-                (long long)need);
-  float* mm = static_cast<float*>(workspace);
-  float* inv = mm + (long)a->num_graphs * a->rows * d;
+  const MaxpoolWorkspace ws = maxpool_bwd_layout(workspace, (int64_t)a->num_graphs * a->rows * d);
+  if (int rc = check_workspace("kgcn_graph_maxpool_bwd_f32", workspace, workspace_bytes, (int64_t)ws.bytes)) return rc;
+  float *mm = ws.mm, *inv = ws.inv;
   hipStream_t s = as_stream(stream);
   const long total_rows = (long)a->num_graphs * a->rows;
   const LaneGrid g = lane_group_grid(total_rows, d);

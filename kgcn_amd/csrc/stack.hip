@@ -23,6 +23,7 @@
 // accumulate over the workgroup's graphs in LDS slots owned by exactly one thread (no atomics), one partial per workgroup,
 // reduce_partials adds the partials in a fixed order: deterministic.
 #include "stack_common.h"
+#include "workspace.h"
 
 namespace kgcn {
 
@@ -500,8 +501,7 @@ extern "C" int kgcn_gcn_stack_bwd_f32(const kgcn_csr_batch* at, const float* x, 
   if (!dparams) return fail("kgcn_gcn_stack_bwd_f32: dparams is NULL");
   hipStream_t s = as_stream(stream);
   if (at->num_graphs == 0) {
-    hipError_t e = hipMemsetAsync(dparams, 0, (size_t)p.a.ptotal * 4, s);
-    return e == hipSuccess ? 0 : fail("kgcn_gcn_stack_bwd_f32: memset failed");
+    return zero_async("kgcn_gcn_stack_bwd_f32", dparams, (size_t)p.a.ptotal * 4, s);
   }
   if (!x || !dlast) return fail("kgcn_gcn_stack_bwd_f32: NULL operand");
   for (int l = 0; l < num_layers; ++l) {
@@ -510,9 +510,11 @@ extern "C" int kgcn_gcn_stack_bwd_f32(const kgcn_csr_batch* at, const float* x, 
   }
   p.a.gather = gather ? 1 : 0;
   const int blocks = tiles ? stack2_blocks(at->num_graphs, p.a.G) : stack_blocks(at->num_graphs, p.lds_bwd);
-  const int64_t need = (int64_t)blocks * p.a.ptotal * 4;
-  if (!workspace || workspace_bytes < need)
-    return fail("kgcn_gcn_stack_bwd_f32: workspace %lld < %lld bytes", (long long)workspace_bytes, (long long)need);
+  const int64_t need = (int64_t)blocks * p.a.ptotal * 4;         // one partial [ptotal] per workgroup: never more than the query's
+  if (int rc = check_layout_fits("kgcn_gcn_stack_bwd_f32", (size_t)need,
+                                 kgcn_gcn_stack_bwd_workspace_bytes(at->num_graphs, layers, num_layers)))
+    return rc;
+  if (int rc = check_workspace("kgcn_gcn_stack_bwd_f32", workspace, workspace_bytes, need)) return rc;
   float* part = static_cast<float*>(workspace);
   const int2* cvp = reinterpret_cast<const int2*>(at->cv);
   if (tiles) {

@@ -12,7 +12,7 @@
 //                                             p -= lr_t m / (sqrt(v) + eps)              ("epsilon hat" OUTSIDE the root)
 //                                           t lives in device memory (a captured hipGraph advances it on replay).
 #include "block_reduce.h"
-#include "kgcn_common.h"
+#include "workspace.h"
 
 namespace kgcn {
 
@@ -203,8 +203,7 @@ static int loss_args(const char* who, const void* logits, const void* labels, co
                      int32_t width, const void* dlogits, const void* sums, const void* ws, int64_t wsb) {
   if (batch <= 0 || width <= 0) return fail("%s: bad shape batch=%lld width=%d", who, (long long)batch, width);
   if (!logits || !labels || (need_mask && !mask) || !dlogits || !sums) return fail("%s: NULL operand", who);
-  if (!ws || wsb < kgcn_loss_workspace_bytes(batch))
-    return fail("%s: workspace %lld < %lld bytes", who, (long long)wsb, (long long)kgcn_loss_workspace_bytes(batch));
+  if (int rc = check_workspace(who, ws, wsb, kgcn_loss_workspace_bytes(batch))) return rc;
   if ((batch + kLossBlock - 1) / kLossBlock > 0x7fffffffLL) return fail("%s: batch too large", who);
   return 0;
 }

@@ -16,7 +16,7 @@
 // One workgroup owns one graph at a time and keeps Y_c and the N x N label / gradient matrix in LDS; L is evaluated in
 // 4 x 4 register tiles of the upper triangle only (L is symmetric), in fp32 with fused multiply-adds.
 #include "block_reduce.h"
-#include "kgcn_common.h"
+#include "workspace.h"
 #include "philox.h"
 
 namespace kgcn {
@@ -469,6 +469,17 @@ int recon_args(const kgcn_csr_batch* adj_ch, int C, const float* const* y, const
 }
 
 int recon_bwd_grid(int B) { return B < 1024 ? B : 1024; }
+
+// d w partials: per channel one array [grid, d] of `n` floats, channel after channel from `part` (the kernel indexes them as one)
+struct ReconWorkspace { int grid; size_t n; float* part; size_t bytes; };
+ReconWorkspace recon_layout(void* base, int32_t B, int32_t C, int32_t d) {
+  Taker t(base, 4);
+  ReconWorkspace w{recon_bwd_grid(B), 0, nullptr, 0};
+  w.n = (size_t)w.grid * d;
+  w.part = t.take<float>((size_t)C * w.n);
+  w.bytes = t.off;
+  return w;
+}
 }  // namespace
 }  // namespace kgcn
 
@@ -532,7 +543,7 @@ extern "C" int kgcn_vae_sample_bwd_f32(const float* m_pre, const float* s_pre, i
 
 extern "C" int64_t kgcn_vae_recon_workspace_bytes(int32_t num_graphs, int32_t num_channels, int32_t d) {
   if (num_graphs <= 0 || num_channels <= 0 || d <= 0) return 0;
-  return (int64_t)recon_bwd_grid(num_graphs) * num_channels * d * 4;
+  return (int64_t)recon_layout(nullptr, num_graphs, num_channels, d).bytes;
 }
 
 extern "C" int kgcn_vae_recon_fwd_f32(const kgcn_csr_batch* adj_ch, int32_t num_channels, const float* const* y,
@@ -567,13 +578,13 @@ extern "C" int kgcn_vae_recon_bwd_f32(const kgcn_csr_batch* adj_ch, int32_t num_
     if (!dy[c]) return fail("%s: NULL dY of channel %d", who, c);
     a.dy[c] = dy[c];
   }
-  const int grid = recon_bwd_grid(a.B);
-  if (dw && (!workspace || workspace_bytes < kgcn_vae_recon_workspace_bytes(a.B, a.C, d)))
-    return fail("%s: workspace %lld < %lld bytes", who, (long long)workspace_bytes,
-                (long long)kgcn_vae_recon_workspace_bytes(a.B, a.C, d));
+  const ReconWorkspace ws = recon_layout(dw ? workspace : nullptr, a.B, a.C, d);
+  const int grid = ws.grid;
+  if (dw)
+    if (int rc = check_workspace(who, workspace, workspace_bytes, (int64_t)ws.bytes)) return rc;
   hipStream_t s = as_stream(stream);
   if (int rc = allow_full_lds<vae_recon_bwd_kernel>(0, who)) return rc;
-  float* part = dw ? static_cast<float*>(workspace) : nullptr;
+  float* part = ws.part;
   const size_t lds = recon_lds_floats(a.NP, a.D4, true, a.C) * 4;
   hipLaunchKernelGGL(vae_recon_bwd_kernel, dim3(grid), dim3(256), lds, s, a, feat_logits, feat_target, mask, g_opt, g_sum, dfeat,
                      dkl, part);
@@ -581,6 +592,6 @@ extern "C" int kgcn_vae_recon_bwd_f32(const kgcn_csr_batch* adj_ch, int32_t num_
   if (dw)
     for (int c = 0; c < a.C; ++c)
       if (dw[c])
-        if (int rc = reduce_or_defer(part + (size_t)c * grid * d, grid, d, dw[c], s)) return rc;
+        if (int rc = reduce_or_defer(part + c * ws.n, grid, d, dw[c], s)) return rc;
   return 0;
 }

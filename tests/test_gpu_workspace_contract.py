@@ -10,7 +10,13 @@ cvmetrics, linkpred, svm and labelprop), each called through _lib at the smalles
 `need` is what the entry point itself names when it is handed no bytes at all; it is the size its *_workspace_bytes query returns
 (kgcn_pair_rank_table_i32 needs less than the query, which covers the select and the emit of the same ranking too).  No contract in
 include/kgcn_hip.h asks for an aligned workspace, so (c) holds for all of them.  The *_copies_i32 entry points are the plain ones'
-launchers with copies > 1 and are not repeated here."""
+launchers with copies > 1 and are not repeated here.
+
+The multi-array layouts of the training step's ops (bn, gat, max-pooling, seq, conv1d, cpi-ig, vae, dense, fused GraphConv, stack)
+follow in the second half.  They are packed (carved at 4 bytes) and use the caller's pointer as it is, so (c) is not run for them: a
+skewed pointer would be a misaligned access.  Where the layout declares a base alignment above 4 bytes (batch normalisation's
+64-bit count, the 64-bit block sums of kgcn_ragged_plan), a base 4 bytes off is refused with `workspace not <n>-byte aligned` and no output is touched.  kgcn_graphconv_bwd_f32
+and kgcn_gcn_stack_bwd_f32 need one partial per workgroup they launch, at most what their queries (sized for a full grid) return."""
 import ctypes
 import re
 
@@ -36,9 +42,11 @@ def bytes_of(t):
     return t.cpu().numpy().reshape(-1).view(np.uint8)
 
 
-def contract(entry, call, outputs, query=None, exact=True, prepare=None):
+def contract(entry, call, outputs, query=None, exact=True, prepare=None, packed_align=None):
     """call(outs, ws, nbytes) -> rc with ws a uint8 tensor; outputs() -> fresh sentinel-filled outputs; prepare(ws, nbytes) fills a
-    workspace with what an earlier call of the protocol leaves in it."""
+    workspace with what an earlier call of the protocol leaves in it.  packed_align: the entry point does not round its base (the
+    packed layouts) and its layout declares this base alignment: (c) is not run; above 4, a base 4 bytes past the aligned one is
+    refused by name with no output touched."""
     import torch
     from kgcn_amd import _lib
     empty = torch.empty((1,), device="cuda", dtype=torch.uint8)
@@ -52,17 +60,23 @@ def contract(entry, call, outputs, query=None, exact=True, prepare=None):
     a0 = (-big.data_ptr()) % 256
     aligned, skewed = big[a0:a0 + need], big[a0 + 8:a0 + 8 + need]
     assert aligned.data_ptr() % 256 == 0 and skewed.data_ptr() % 256 == 8
+
+    def refused(ws, nbytes, message):
+        outs = outputs()
+        before = [bytes_of(t) for t in outs]
+        assert call(outs, ws, nbytes) == 1
+        assert _lib.lib.kgcn_last_error().decode() == message
+        torch.cuda.synchronize()
+        for t, b in zip(outs, before):
+            np.testing.assert_array_equal(bytes_of(t), b)
+
     # (a)
-    outs = outputs()
-    before = [bytes_of(t) for t in outs]
-    assert call(outs, aligned, need - 1) == 1
-    assert _lib.lib.kgcn_last_error().decode() == "%s: workspace %d < %d bytes" % (entry, need - 1, need)
-    torch.cuda.synchronize()
-    for t, b in zip(outs, before):
-        np.testing.assert_array_equal(bytes_of(t), b)
+    refused(aligned, need - 1, "%s: workspace %d < %d bytes" % (entry, need - 1, need))
+    if packed_align is not None and packed_align > 4:
+        refused(big[a0 + 4:a0 + 4 + need], need, "%s: workspace not %d-byte aligned" % (entry, packed_align))
     # (b), (c)
     got = []
-    for ws in (aligned, skewed):
+    for ws in (aligned, skewed) if packed_align is None else (aligned,):
         big.fill_(0xA5)
         if prepare is not None:
             prepare(ws, need)
@@ -72,7 +86,7 @@ def contract(entry, call, outputs, query=None, exact=True, prepare=None):
         got.append([bytes_of(t) for t in outs])
         first = ws.data_ptr() - big.data_ptr()                        # nothing outside the `need` bytes handed in is written
         assert bool((big[:first] == 0xA5).all()) and bool((big[first + need:] == 0xA5).all())
-    for b, c in zip(*got):
+    for b, c in zip(got[0], got[-1]):
         np.testing.assert_array_equal(b, c)
     return need
 
@@ -281,3 +295,263 @@ def test_linkpred_bwd():
              lambda o, ws, nb: L.kgcn_linkpred_bwd_f32(ptr(h), 4, 2, ptr(w), 1, mode, ptr(rows), ptr(s1), ptr(s2), ptr(sums), 1, ptr(g_opt),
                                                        None, ptr(o[0]), ptr(o[1]), ptr(ws), nb, stream()),
              lambda: [filled((4, 2), torch.float32), filled((1, 2), torch.float32)], L.kgcn_linkpred_workspace_bytes(4, 2, 1, mode, 1))
+
+
+# ---- the packed layouts of the training step's ops: carved at 4 bytes from the caller's pointer as it is (packed_align) -------------
+# One test per multi-array layout, at the smallest shape that uses every array.  Whether the gradients are right is the job of the
+# per-family tests, which run the same code with exactly-sized workspaces; here the operands only have to be finite.
+
+def rnd(*shape, seed=0, lo=None):
+    """float32 N(0, 1) on the device (lo: uniform in [lo, lo + 1) instead)"""
+    rng = np.random.default_rng([seed, len(shape)] + list(shape))
+    a = rng.standard_normal(shape) if lo is None else lo + rng.random(shape)
+    return up(a.astype(np.float32))
+
+
+def test_graph_bn():
+    import torch
+    from kgcn_amd import _lib
+    L, ptr, stream = _lib.lib, _lib.ptr, _lib.current_stream
+    T, N, d = 2, 3, 5
+    x, grad, enabled = rnd(T, N, d), rnd(T, N, d, seed=1), up(np.array([3, 2], np.int32))
+    mean, var, gamma = rnd(d, seed=2), rnd(d, lo=0.5), rnd(d, lo=0.5, seed=3)
+    need = L.kgcn_graph_bn_workspace_bytes(d)
+    vec = lambda: filled((d,), torch.float32)
+    contract("kgcn_graph_bn_stats_f32",
+             lambda o, ws, nb: L.kgcn_graph_bn_stats_f32(ptr(x), T, N, d, ptr(enabled), ptr(o[0]), ptr(o[1]), ptr(ws), nb, stream()),
+             lambda: [vec(), vec()], need, packed_align=8)
+    last = []
+
+    def bwd(o, ws, nb):                                               # training with dx: both partial arrays and the count
+        last[:] = o
+        return L.kgcn_graph_bn_bwd_f32(ptr(x), ptr(grad), T, N, d, ptr(enabled), ptr(mean), ptr(var), ptr(gamma), 1e-3, 1, ptr(o[0]),
+                                       ptr(o[1]), ptr(o[2]), ptr(ws), nb, stream())
+
+    contract("kgcn_graph_bn_bwd_f32", bwd, lambda: [filled((T, N, d), torch.float32), vec(), vec()], need, packed_align=8)
+    assert all(bool(torch.isfinite(t).all()) for t in last) and not bool((last[0][0] == SENTINEL).any())
+
+
+def test_ragged_plan():
+    """a single array, but of 8-byte words (int2 block sums): the one alignment refusal beside batch normalisation's"""
+    import torch
+    from kgcn_amd import _lib
+    L, ptr, stream = _lib.lib, _lib.ptr, _lib.current_stream
+    csr, nn, _ = two_graphs()
+    a = csr.desc()
+    last = []
+
+    def call(o, ws, nb):
+        last[:] = o
+        return L.kgcn_ragged_plan(ctypes.byref(a), ptr(nn), None, 2, ptr(o[0]), ptr(o[1]), ptr(ws), nb, stream())
+
+    contract("kgcn_ragged_plan", call, lambda: [filled((3,), torch.int32), filled((3,), torch.int32)],
+             L.kgcn_ragged_workspace_bytes(2), packed_align=8)
+    assert last[0].tolist() == [0, 3, 5] and last[1].tolist() == [0, 4, 6]      # valid rows and stored entries, scanned
+
+
+def test_gat():
+    import torch
+    from kgcn_amd import _lib
+    L, ptr, stream = _lib.lib, _lib.ptr, _lib.current_stream
+    csr, _, _ = two_graphs()
+    d = 3
+    x, wa, g = rnd(2, 3, d), rnd(2 * d, seed=1), rnd(2, 3, d, seed=2)
+    a, at = csr.desc(), csr.transpose().desc()
+    need = L.kgcn_gat_workspace_bytes(2, 3, d)
+    contract("kgcn_gat_fwd_f32",
+             lambda o, ws, nb: L.kgcn_gat_fwd_f32(ctypes.byref(a), ptr(x), d, ptr(wa), ptr(o[0]), 0.0, ptr(ws), nb, stream()),
+             lambda: [filled((2, 3, d), torch.float32)], need, packed_align=4)
+    contract("kgcn_gat_bwd_f32",
+             lambda o, ws, nb: L.kgcn_gat_bwd_f32(ctypes.byref(a), ctypes.byref(at), ptr(x), d, ptr(wa), ptr(g), ptr(o[0]), 0.0, ptr(o[1]),
+                                                  ptr(ws), nb, stream()),
+             lambda: [filled((2, 3, d), torch.float32), filled((2 * d,), torch.float32)], need, packed_align=4)
+
+
+def test_graph_maxpool_bwd():
+    import torch
+    from kgcn_amd import _lib
+    L, ptr, stream = _lib.lib, _lib.ptr, _lib.current_stream
+    csr, _, _ = two_graphs()
+    d = 3
+    x, g = rnd(2, 3, d), rnd(2, 3, d, seed=1)
+    a, at = csr.desc(), csr.transpose().desc()
+    contract("kgcn_graph_maxpool_bwd_f32",
+             lambda o, ws, nb: L.kgcn_graph_maxpool_bwd_f32(ctypes.byref(a), ctypes.byref(at), ptr(x), ptr(g), d, ptr(o[0]), 0.0, ptr(ws),
+                                                            nb, stream()),
+             lambda: [filled((2, 3, d), torch.float32)], L.kgcn_graph_maxpool_bwd_workspace_bytes(2, 3, d), packed_align=4)
+
+
+def test_seq_convpool_bwd():
+    import torch
+    from kgcn_amd import _lib, ops
+    L, ptr, stream = _lib.lib, _lib.ptr, _lib.current_stream
+    B, length, S, E, k, F, pool = 2, 2, 1, 1, 1, 1, 1                 # the smallest of everything; 2 pooled positions
+    ops.seq_limits_check(length=length, symbols=S, embed_dim=E, kernel_size=k, filters=F, pool=pool)
+    tokens, table, w, bias = up(np.zeros((B, length), np.int32)), rnd(S, E, lo=0.5), rnd(k, E, F, lo=0.5), rnd(F, lo=0.5)
+    out, argmax = filled((B, length // pool, F), torch.float32), filled((B, length // pool, F), torch.uint8)
+    assert L.kgcn_seq_convpool_fwd_f32(ptr(tokens), B, length, ptr(table), S, E, ptr(w), ptr(bias), k, F, pool, ptr(out), ptr(argmax),
+                                       stream()) == 0
+    dout = rnd(B, length // pool, F, seed=1)
+    contract("kgcn_seq_convpool_bwd_f32",
+             lambda o, ws, nb: L.kgcn_seq_convpool_bwd_f32(ptr(tokens), B, length, ptr(table), S, E, ptr(w), k, F, pool, ptr(dout),
+                                                           ptr(argmax), ptr(o[0]), ptr(o[1]), ptr(o[2]), ptr(ws), nb, stream()),
+             lambda: [filled((S, E), torch.float32), filled((k, E, F), torch.float32), filled((F,), torch.float32)],
+             L.kgcn_seq_convpool_workspace_bytes(B, length, S, E, k, F, pool), packed_align=4)
+
+
+def test_seq_lstm_bwd():
+    import torch
+    from kgcn_amd import _lib
+    L, ptr, stream = _lib.lib, _lib.ptr, _lib.current_stream
+    B, steps, D, H = 2, 2, 3, 2
+    act = _lib.K["KGCN_SEQ_ACT_HARD_SIGMOID"]
+    x, wx, wh, bias, dh = rnd(B, steps, D), rnd(D, 4 * H, seed=1), rnd(H, 4 * H, seed=2), rnd(4 * H, seed=3), rnd(B, H, seed=4)
+    h, stash = filled((B, H), torch.float32), filled((int(L.kgcn_seq_lstm_stash_floats(B, steps, H)),), torch.float32)
+    assert L.kgcn_seq_lstm_fwd_f32(ptr(x), B, steps, D, ptr(wx), ptr(wh), ptr(bias), H, act, ptr(h), H, ptr(stash), stream()) == 0
+    keep = []
+
+    def call(o, ws, nb):                                              # the backward overwrites the stash: every call gets a copy
+        keep[:] = [stash.clone()]
+        return L.kgcn_seq_lstm_bwd_f32(ptr(x), B, steps, D, ptr(wx), ptr(wh), ptr(bias), H, act, ptr(dh), H, ptr(keep[0]), ptr(o[0]),
+                                       ptr(o[1]), ptr(o[2]), ptr(o[3]), ptr(ws), nb, stream())
+
+    contract("kgcn_seq_lstm_bwd_f32", call,
+             lambda: [filled((B, steps, D), torch.float32), filled((D, 4 * H), torch.float32), filled((H, 4 * H), torch.float32),
+                      filled((4 * H,), torch.float32)], L.kgcn_seq_lstm_workspace_bytes(B, steps, D, H), packed_align=4)
+
+
+def test_conv1d_pool_bwd():
+    import torch
+    from kgcn_amd import _lib, ops
+    L, ptr, stream = _lib.lib, _lib.ptr, _lib.current_stream
+    B, length, Cin, k, F, pool = 2, 2, 1, 1, 1, 1                     # the smallest of everything; 2 pooled positions
+    ops.conv1d_limits_check(length=length, in_dim=Cin, filters=F, kernel_size=k, pool=pool)
+    act = _lib.K["KGCN_ACT_RELU"]
+    x, w, bias = rnd(B, length, Cin, lo=0.5), rnd(k, Cin, F, lo=0.5), rnd(F, lo=0.5)
+    out, argmax = filled((B, length // pool, F), torch.float32), filled((B, length // pool, F), torch.uint8)
+    assert L.kgcn_conv1d_pool_fwd_f32(ptr(x), None, None, 0, B, length, Cin, ptr(w), ptr(bias), k, F, pool, act, ptr(out), ptr(argmax),
+                                      stream()) == 0
+    dout = rnd(B, length // pool, F, seed=1)
+    contract("kgcn_conv1d_pool_bwd_f32",                              # dx and dw: the flipped weights and both partial arrays
+             lambda o, ws, nb: L.kgcn_conv1d_pool_bwd_f32(ptr(x), None, None, 0, B, length, Cin, ptr(w), k, F, pool, act, ptr(dout),
+                                                          ptr(argmax), ptr(out), ptr(o[0]), ptr(o[1]), ptr(o[2]), ptr(ws), nb, stream()),
+             lambda: [filled((B, length, Cin), torch.float32), filled((k, Cin, F), torch.float32), filled((F,), torch.float32)],
+             L.kgcn_conv1d_pool_workspace_bytes(B, length, Cin, k, F, pool), packed_align=4)
+
+
+def test_cpi_ig():
+    import torch
+    from kgcn_amd import _lib
+    L, ptr, stream = _lib.lib, _lib.ptr, _lib.current_stream
+    C, N, Wd, T, K = 2, 2, 3, 2, 2
+    P, Q, u, e = rnd(C, N, Wd), rnd(C, N, Wd, seed=1), rnd(T, Wd, seed=2), rnd(T, seed=3)
+    alpha, gamma, wA, wB = (up(np.array(v, np.float32)) for v in ([0.0, 1.0], [1.0, 1.0], [0.5, 0.5], [0.25, 0.75]))
+    contract("kgcn_cpi_ig_f32",
+             lambda o, ws, nb: L.kgcn_cpi_ig_f32(ptr(P), ptr(Q), C, N, Wd, ptr(u), ptr(e), T, ptr(alpha), ptr(gamma), ptr(wA), ptr(wB), K,
+                                                 ptr(o[0]), ptr(o[1]), ptr(o[2]), ptr(ws), nb, stream()),
+             lambda: [filled((C, K, T), torch.float32), filled((C, T, N, Wd), torch.float32), filled((C, T, N, Wd), torch.float32)],
+             L.kgcn_cpi_ig_workspace_bytes(C, Wd, T, K), packed_align=4)
+
+
+def test_vae_recon_bwd():
+    import torch
+    from kgcn_amd import _lib, ops
+    L, ptr, stream = _lib.lib, _lib.ptr, _lib.current_stream
+    csr, _, _ = two_graphs()
+    B, N, C, d, f = 2, 3, 2, 1, 1                                     # d = 1: the smallest decoder width recon_args admits
+    adj = (_lib.CsrBatch * C)(csr.desc(), csr.desc())
+    ys, ws_ = [rnd(B, N, d, seed=c) for c in range(C)], [rnd(d, lo=0.5, seed=c) for c in range(C)]
+    logits, target, g_opt = rnd(B, N, f, seed=5), rnd(B, N, f, lo=0.0, seed=6), up(np.ones(1, np.float32))
+    contract("kgcn_vae_recon_bwd_f32",                                # dw of both channels
+             lambda o, ws, nb: L.kgcn_vae_recon_bwd_f32(adj, C, ops._ptr_array(ys), ops._ptr_array(ws_), d, ptr(logits), ptr(target), f,
+                                                        None, ptr(g_opt), None, ops._ptr_array(o[0:2]), ops._ptr_array(o[2:4]), ptr(o[4]),
+                                                        None, ptr(ws), nb, stream()),
+             lambda: [filled((B, N, d), torch.float32) for _ in range(C)] + [filled((d,), torch.float32) for _ in range(C)] +
+                     [filled((B, N, f), torch.float32)], L.kgcn_vae_recon_workspace_bytes(B, C, d), packed_align=4)
+
+
+def test_dense_wgrad():
+    import torch
+    from kgcn_amd import _lib
+    L, ptr, stream = _lib.lib, _lib.ptr, _lib.current_stream
+    m, din, dout = 5, 3, 2
+    x, dy = rnd(m, din), rnd(m, dout, seed=1)
+    contract("kgcn_dense_wgrad_f32",
+             lambda o, ws, nb: L.kgcn_dense_wgrad_f32(ptr(x), din, ptr(dy), dout, m, din, dout, ptr(o[0]), ptr(o[1]), ptr(ws), nb, stream()),
+             lambda: [filled((din, dout), torch.float32), filled((dout,), torch.float32)],
+             L.kgcn_dense_wgrad_workspace_bytes(m, din, dout), packed_align=4)
+
+
+def test_dense_bwd_and_bwd_dot():
+    import torch
+    from kgcn_amd import _lib
+    L, ptr, stream = _lib.lib, _lib.ptr, _lib.current_stream
+    m, din, dout = 16384, 132, 256                                    # the smallest shape kgcn_dense_bwd_supported admits
+    assert L.kgcn_dense_bwd_supported(m, din, dout) and not L.kgcn_dense_bwd_supported(m - 1, din, dout)
+    assert not L.kgcn_dense_bwd_supported(m, din - 4, dout)
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    x, grad, dotx = (torch.randn((m, n), device="cuda", generator=gen) for n in (din, dout, din))
+    act_out = torch.rand((m, dout), device="cuda", generator=gen)
+    w = torch.randn((din, dout), device="cuda", generator=gen) / 16
+    act = _lib.K["KGCN_ACT_SIGMOID"]
+    tb = L.kgcn_dense_fwd_workspace_bytes(dout, din)
+    table = torch.empty((tb,), device="cuda", dtype=torch.uint8)
+    need = L.kgcn_dense_wgrad_workspace_bytes(m, din, dout)
+    grads = lambda: [filled((din, dout), torch.float32), filled((dout,), torch.float32)]
+    contract("kgcn_dense_bwd_f32",
+             lambda o, ws, nb: L.kgcn_dense_bwd_f32(ptr(grad), None, 0, 0, ptr(act_out), act, dout, ptr(x), din, m, din, dout, ptr(w), dout,
+                                                    ptr(o[2]), din, ptr(o[0]), ptr(o[1]), ptr(table), tb, 0, ptr(ws), nb, stream()),
+             lambda: grads() + [filled((m, din), torch.float32)], need, packed_align=4)
+    contract("kgcn_dense_bwd_dot_f32",
+             lambda o, ws, nb: L.kgcn_dense_bwd_dot_f32(ptr(grad), ptr(act_out), act, dout, ptr(x), din, m, din, dout, ptr(w), dout,
+                                                        ptr(dotx), din, ptr(o[0]), ptr(o[1]), ptr(o[2]), ptr(table), tb, 0, ptr(ws), nb,
+                                                        stream()),
+             lambda: grads() + [filled((1,), torch.float32)], need, packed_align=4)
+
+
+def test_graphconv_bwd():
+    import torch
+    import fused_cases
+    from kgcn_amd import BatchedCSR, _lib, ops
+    L, ptr, stream = _lib.lib, _lib.ptr, _lib.current_stream
+    name = min(fused_cases.FULL_CASES + fused_cases.PACK_CASES, key=lambda n: np.prod(fused_cases.shape_of(n)))
+    T = 2
+    N, din, dout = fused_cases.shape_of(name)
+    case = fused_cases.build(name, T)
+    csr = BatchedCSR.from_arrays(case.graph, case.row, case.col, case.val, T, N, N, device="cuda")
+    at = ops._fused_adjacency(csr.transpose(), True, T, din, dout, True)
+    x, w, g = rnd(T, N, din), rnd(din, dout, seed=1), rnd(T, N, dout, seed=2)
+    contract("kgcn_graphconv_bwd_f32",                                # one partial pair per workgroup, at most one workgroup a graph
+             lambda o, ws, nb: L.kgcn_graphconv_bwd_f32(at, ptr(x), ptr(w), ptr(g), din, dout, ptr(o[0]), ptr(o[1]), ptr(o[2]), ptr(ws), nb,
+                                                        stream()),
+             lambda: [filled((T, N, din), torch.float32), filled((din, dout), torch.float32), filled((dout,), torch.float32)],
+             L.kgcn_graphconv_bwd_workspace_bytes(T, din, dout), exact=False, packed_align=4)
+
+
+def test_gcn_stack_bwd():
+    import torch
+    import stack_cases
+    from kgcn_amd import _lib, ops
+    L, ptr, stream = _lib.lib, _lib.ptr, _lib.current_stream
+    csr, nn, _ = two_graphs()
+    name = min(stack_cases.CASES, key=lambda n: (len(stack_cases.CASES[n]["widths"]), sum(stack_cases.CASES[n]["widths"])))
+    spec = stack_cases.spec_of(name)
+    assert ops.gcn_stack_supported(csr, spec)
+    T, N = 2, 3
+    params = []
+    for l, (kind, act, din, dout, eps) in enumerate(spec):
+        assert kind != 2                                              # (a list with a normalisation would need its buffers here)
+        params += [rnd(din, dout, seed=l) / np.sqrt(din), rnd(dout, seed=10 + l)]
+    arr, keep = ops._stack_descriptors(spec, params, [None] * len(spec))
+    x, dlast = rnd(T, N, spec[0][2]), rnd(T, spec[-1][3], seed=1)
+    outs = [filled((T, N, s[3]), torch.float32) for s in spec]
+    optr = (ctypes.c_void_p * len(spec))(*[o.data_ptr() for o in outs])
+    pooled = filled((T, spec[-1][3]), torch.float32)
+    assert L.kgcn_gcn_stack_fwd_f32(ctypes.byref(csr.desc()), ptr(x), ptr(nn), arr, len(spec), optr, ptr(pooled), stream()) == 0
+    at = csr.transpose().desc()
+    n = int(L.kgcn_gcn_stack_param_floats(arr, len(spec)))
+    contract("kgcn_gcn_stack_bwd_f32",
+             lambda o, ws, nb: L.kgcn_gcn_stack_bwd_f32(ctypes.byref(at), ptr(x), ptr(nn), arr, len(spec), optr, ptr(dlast), 1, ptr(o[0]),
+                                                        ptr(o[1]), ptr(ws), nb, stream()),
+             lambda: [filled((T, N, spec[0][2]), torch.float32), filled((n,), torch.float32)],
+             L.kgcn_gcn_stack_bwd_workspace_bytes(T, arr, len(spec)), exact=False, packed_align=4)
